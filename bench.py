@@ -8,6 +8,7 @@ batch (global batch fixed -> strong scaling) and one RCCL all-reduce of the flat
 [dW | db | loss] buffer follows.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
@@ -46,6 +47,8 @@ CONFIGS = {
 PEAK_F32_MFMA_TFLOPS = 157.3  # /opt/skills/guides/MI355X_MICROARCH.md, "Peak FP32 (matrix)"
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # same table: "Peak BF16/FP16 MFMA ~2.5 PF dense"; bf16x3 spends 6 bf16 products per fp32 product
 PEAK_HBM_GBS = 8000.0
+DUMP_MAX_BYTES = 64 * 10 ** 6  # --dump-outputs: every file together
+DUMP_SEED = 2024  # --dump-outputs: the sample drawn from an array too large for its share
 
 
 def synth(B, T, U, H, V, seed, device, permuted_enc=False):
@@ -65,6 +68,30 @@ def synth(B, T, U, H, V, seed, device, permuted_enc=False):
     ll = torch.full((B,), T, dtype=torch.int32)
     tl = torch.full((B,), U, dtype=torch.int32)
     return [x.to(device) for x in (enc, pred, W, bias, targets, ll, tl)]  # .to() keeps the permuted view's strides
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES, seed=DUMP_SEED):
+    """Write each (name, array) of `arrays` to out_dir/<name>.npy in float32, all files together within max_bytes.
+    Smallest first, every array gets an equal share of what is left; an array larger than its share is written as a
+    fixed sample instead: its flattened values at sorted flat indices drawn without replacement by
+    numpy.random.default_rng([seed, position in `arrays`]).  The same arguments draw the same indices, so the dumps of two
+    builds compare element for element.  Returns {name: {"shape", "elements", "sampled"}}."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = [(name, np.asarray(a, dtype=np.float32)) for name, a in arrays]
+    left, info = max_bytes, {}
+    order = sorted(range(len(host)), key=lambda i: host[i][1].size)
+    for n, i in enumerate(order):
+        name, a = host[i]
+        keep = max(0, (left // (len(order) - n) - 4096) // a.itemsize)  # 4096: room for the .npy header
+        sampled = a.size > keep
+        if sampled:
+            idx = np.sort(np.random.default_rng([seed, i]).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        left -= os.path.getsize(path)
+        info[name] = {"shape": list(host[i][1].shape), "elements": int(a.size), "sampled": sampled}
+    return info
 
 
 def cpu_baseline(T, U, H, V, budget_s=40.0):
@@ -221,7 +248,13 @@ def main():
                     help="skip the secondary `exact_fp32` object (the exact-fp32 MFMA route timed in the same run)")
     ap.add_argument("--no-parity", action="store_true",
                     help="skip the down-scaled parity twin of the CPU leg (it also goes with --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32): loss, "
+                         "costs, grad_enc, grad_pred, grad_W, grad_bias (rank 0's shard of costs / grad_enc / grad_pred); at most "
+                         "64 MB in all, an array too large for its share as a fixed seeded sample (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)  # never returns
@@ -326,6 +359,11 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt, med_ms = float(tmax[0].item()), float(tmax[1].item())
     loss = float(flat[V * H + V].item())
+    # what the last timed step computed, copied off the device before the stage timing below reuses `outs`
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, [(k, t.cpu().numpy()) for k, t in (
+            ("loss", fg.loss), ("costs", costs), ("grad_enc", ge), ("grad_pred", gp), ("grad_W", gW), ("grad_bias", gb))])
 
     # ---- per-stage timing with HIP events on the launch stream (torch's current stream IS the
     # stream every kernel was enqueued on: engine._stream()).
@@ -510,6 +548,8 @@ def main():
         engine.release_workspaces()
         out["cpu_baseline"] = cpu_baseline(T, U, H, V)
         out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     print(json.dumps(out), flush=True)
     if dist_on:
         dist.destroy_process_group()

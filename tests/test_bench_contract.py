@@ -134,3 +134,97 @@ def test_bench_refuses_to_run_fewer_gpus_than_asked():
     assert out.returncode != 0
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert "error" in line and line["n_gpus_requested"] == 2 and line["hipGetDeviceCount"] < 2
+
+
+def test_dump_outputs_fits_the_budget_and_samples_reproducibly(tmp_path):
+    """bench.py --dump-outputs writes through bench.dump_outputs: float32 .npy files, all together within the byte budget;
+    arrays that fit are written whole, a larger one as a sample whose indices depend on the seed only, so two dumps of
+    the same arguments compare element for element."""
+    import numpy as np
+
+    import bench
+    rng = np.random.default_rng(0)
+    big = rng.standard_normal((300, 1000)).astype(np.float32)
+    small = rng.standard_normal((4, 5))
+    arrays = [("loss", np.float32(3.5)), ("big", big), ("small", small)]
+    budget = 600_000
+    info = bench.dump_outputs(str(tmp_path / "a"), arrays, max_bytes=budget)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, max_bytes=budget)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["big.npy", "loss.npy", "small.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= budget
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+    assert not info["loss"]["sampled"] and not info["small"]["sampled"] and info["big"]["sampled"]
+    assert info["big"]["shape"] == [300, 1000]
+    loss = np.load(tmp_path / "a" / "loss.npy")
+    assert loss.shape == () and loss == np.float32(3.5)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "small.npy"), small.astype(np.float32))
+    sample = np.load(tmp_path / "a" / "big.npy")
+    assert sample.shape == (info["big"]["elements"],) and 100_000 < sample.size < 150_000
+    flat = big.reshape(-1)
+    pos = np.searchsorted(np.sort(flat), sample)
+    assert np.array_equal(np.sort(flat)[pos], sample)  # every sampled value is one of the array's
+    # the default budget holds for the largest headline output (config 4's grad_enc: 82 MB in float32)
+    B, T, U, H, V = bench.CONFIGS["cfg4"]
+    info = bench.dump_outputs(str(tmp_path / "c"), [("grad_enc", np.zeros((B, T, H), np.float32)),
+                                                   ("grad_pred", np.zeros((B, U + 1, H), np.float32))])
+    assert info["grad_enc"]["sampled"] and not info["grad_pred"]["sampled"]
+    assert sum(os.path.getsize(tmp_path / "c" / f) for f in os.listdir(tmp_path / "c")) <= bench.DUMP_MAX_BYTES
+
+
+def test_bench_inputs_are_the_same_every_run():
+    """The benchmark's inputs come from a seeded generator: the same arguments give the same tensors, so the outputs
+    --dump-outputs writes for two builds are comparable."""
+    import torch
+
+    import bench
+    a = bench.synth(2, 30, 7, 64, 128, 1234, "cpu")
+    b = bench.synth(2, 30, 7, 64, 128, 1234, "cpu")
+    assert all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+def test_bench_refuses_zero_steps():
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"],
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 2 and "--steps" in out.stderr
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_what_the_timed_step_computed(tmp_path):
+    """`bench.py --dump-outputs DIR` on a small config: the result line reports the number of timed steps asked for and
+    ms_per_step, and DIR holds the loss, costs and four gradients of the fused step on the bench's seeded inputs, equal
+    to one call of the engine on the same inputs."""
+    import subprocess
+    import sys
+
+    import numpy as np
+    import torch
+
+    import bench
+    import rnnt_amd
+    d = tmp_path / "dump"
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "small", "--steps", "3",
+                          "--warmup", "1", "--no-cpu-baseline", "--no-stage-timing", "--no-exact-fp32", "--dump-outputs", str(d)],
+                         env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-1500:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    names = ["loss", "costs", "grad_enc", "grad_pred", "grad_W", "grad_bias"]
+    assert sorted(os.listdir(d)) == sorted(n + ".npy" for n in names)
+    assert sum(os.path.getsize(d / (n + ".npy")) for n in names) <= bench.DUMP_MAX_BYTES
+    B, T, U, H, V = bench.CONFIGS["small"]
+    enc, pred, W, bias, targets, ll, tl = bench.synth(B, T, U, H, V, 1234, "cuda")
+    ref = rnnt_amd.engine.joint_loss_fwd_bwd(enc, pred, W, bias, targets, ll, tl, V - 1, 1.0 / B, dtype="f16x2")
+    torch.cuda.synchronize()
+    ref = [r.cpu().numpy() for r in ref]
+    for name, r in zip(names[1:], ref):
+        got = np.load(d / (name + ".npy"))
+        assert got.dtype == np.float32 and got.shape == r.shape, name
+        np.testing.assert_allclose(got, r, rtol=0, atol=1e-6 * np.abs(r).max(), err_msg=name)
+    loss = float(np.load(d / "loss.npy"))
+    assert abs(loss - float(ref[0].astype(np.float64).sum()) / B) <= 1e-5 * abs(loss)

@@ -151,16 +151,56 @@ def test_projected_joint_single_forward_stays_plain_torch_on_cpu(golden_dir):
     np.testing.assert_allclose(out, z["logits_f32"][:, 1, 2, :], rtol=0, atol=2e-5)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/rnnt"), reason="needs the reference checkout (build container only)")
-def test_overlay_package_swaps_joint_model_and_conv_predictor_only():
+def _standin_reference_package(dest, golden_dir):
+    """A stand-in for the reference checkout's `rnnt` package, written under `dest`: the submodules the overlay test touches
+    (jasper, lr_sched, causalconv as empty modules; predictor with an LSTMPredictor whose forward(input, lengths, state=None)
+    has the reference's stateful signature, and a ConvPredictor whose state-dict keys are the ones recorded from the reference's
+    own module in tests/golden/predictor_small.npz).  Returns the directory to put on PYTHONPATH."""
+    z = np.load(os.path.join(golden_dir, "predictor_small.npz"))
+    keys = [k[4:].replace("__", ".") for k in z.files if k.startswith("sd__")]  # the reference's state_dict() order
+    pkg = os.path.join(dest, "rnnt")
+    os.makedirs(pkg)
+    for name in ("__init__", "jasper", "lr_sched", "causalconv"):
+        with open(os.path.join(pkg, name + ".py"), "w") as f:
+            f.write('"""stand-in for the reference module of this name"""\n')
+    with open(os.path.join(pkg, "predictor.py"), "w") as f:
+        f.write(
+            '"""stand-in for the reference rnnt/predictor.py (interface only)"""\n'
+            "import torch\n\n"
+            f"STATE_DICT_KEYS = {keys!r}\n\n\n"
+            "class LSTMPredictor(torch.nn.Module):\n"
+            "    def __init__(self, num_symbols, output_dim, symbol_embedding_dim, num_lstm_layers, lstm_hidden_dim,\n"
+            "                 lstm_layer_norm=False, lstm_layer_norm_epsilon=1e-5, lstm_dropout=0.0):\n"
+            "        super().__init__()\n\n"
+            "    def forward(self, input, lengths, state=None):\n"
+            "        raise NotImplementedError\n\n\n"
+            "class ConvPredictor(torch.nn.Module):\n"
+            "    def __init__(self, num_symbols, output_dim, symbol_embedding_dim, dropout):\n"
+            "        super().__init__()\n"
+            "        for key in STATE_DICT_KEYS:\n"
+            "            *path, leaf = key.split('.')\n"
+            "            m = self\n"
+            "            for p in path:\n"
+            "                if not hasattr(m, p):\n"
+            "                    m.add_module(p, torch.nn.Module())\n"
+            "                m = getattr(m, p)\n"
+            "            m.register_parameter(leaf, torch.nn.Parameter(torch.zeros(1)))\n\n"
+            "    def forward(self, input):\n"
+            "        raise NotImplementedError\n")
+    return dest
+
+
+def test_overlay_package_swaps_joint_model_and_conv_predictor_only(golden_dir, tmp_path):
     """integration/rnnt placed before the reference on PYTHONPATH: `rnnt.joint.JointNetwork` (the hydra target, train.py:63),
     `rnnt.model.RNNTModel` (train.py:19) and `rnnt.predictor.ConvPredictor` (the hydra target of config/basic_sp_convjs*.yaml:20-25,
     train.py:61) become the engine's classes — rnnt.model imports without torchaudio — while rnnt.predictor.LSTMPredictor IS the
     reference's class and rnnt.jasper / rnnt.lr_sched / rnnt.causalconv still come from the reference's own files.  With the engine's
-    ConvPredictor in place the model's evaluation decode is eligible for the device loop (the rest of `_device_loop_ok` needs a GPU)."""
+    ConvPredictor in place the model's evaluation decode is eligible for the device loop (the rest of `_device_loop_ok` needs a GPU).
+    The reference checkout is played by a stand-in package with its module layout (_standin_reference_package)."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    ref_dir = _standin_reference_package(str(tmp_path / "reference"), golden_dir)
     code = (
         "import rnnt, rnnt.joint, rnnt.model, rnnt.predictor, rnnt.jasper, rnnt.lr_sched, rnnt.causalconv, rnnt_amd\n"
         "assert rnnt.joint.JointNetwork is rnnt_amd.JointNetwork\n"
@@ -168,8 +208,9 @@ def test_overlay_package_swaps_joint_model_and_conv_predictor_only():
         "assert rnnt.predictor.ConvPredictor is rnnt_amd.ConvPredictor\n"
         "assert rnnt.predictor.LSTMPredictor.__module__ == 'rnnt._reference_predictor'\n"
         "assert rnnt.predictor.ReferenceConvPredictor is not rnnt_amd.ConvPredictor\n"
-        "import inspect; assert inspect.getsourcefile(rnnt.predictor.LSTMPredictor).startswith('/root/reference/')\n"
-        "assert rnnt.jasper.__file__.startswith('/root/reference/') and rnnt.causalconv.__file__.startswith('/root/reference/')\n"
+        f"ref_root = {os.path.join(ref_dir, '')!r}\n"
+        "import inspect; assert inspect.getsourcefile(rnnt.predictor.LSTMPredictor).startswith(ref_root)\n"
+        "assert all(m.__file__.startswith(ref_root) for m in (rnnt.jasper, rnnt.lr_sched, rnnt.causalconv))\n"
         "from rnnt.predictor import LSTMPredictor, ConvPredictor\n"  # (the reference's own import line, rnnt/model.py:3)
         "m = rnnt.model.RNNTModel(rnnt.predictor.ConvPredictor(16, 32, 8, 0.1), None, rnnt.joint.JointNetwork(-1, -1, 32, 16))\n"
         "assert sorted(k for k in m.state_dict() if k.startswith('joint.')) == ['joint.joint_ln.bias', 'joint.joint_ln.weight']\n"
@@ -183,7 +224,7 @@ def test_overlay_package_swaps_joint_model_and_conv_predictor_only():
         "except AttributeError:\n"
         "    pass\n"
         "print('overlay ok')\n")
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(root, "integration"), root, "/root/reference"]))
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(root, "integration"), root, ref_dir]))
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "overlay ok" in out.stdout, out.stderr[-1500:]
 
