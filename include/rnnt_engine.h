@@ -331,6 +331,31 @@ int rnnt_engine_greedy_decode_persistent(const void *frames, int64_t frame_strid
                                          void *workspace, size_t ws_bytes, void *stream);
 
 /*
+ * Frame-synchronous beam search of ONE utterance on the device, with the stateless ConvPredictor of
+ * rnnt/predictor.py:189-229 (eval mode) and the joint of rnnt/joint.py:44-55: at most `max_per_frame` labels per frame,
+ * hypotheses merged by token sequence (logaddexp of their scores), output capped at max_length - 1 labels; beam 1 is the
+ * reference's greedy decode (rnnt/model.py:95-128 with max_per_frame = 10).  The call only ENQUEUES: (init != 0) the search's
+ * initialisation, then `iterations` ROUNDS (0 = the upper bound T * max_per_frame + 1), each a fixed kernel sequence whose
+ * kernels return at once after the search has ended.  A caller may enqueue the bound in one call, or a chunk at a time
+ * (init = 1 first, then init = 0 with the same buffers) and stop when `host_flag` (NULL, or one int32 of PINNED host memory the
+ * caller zeroed) has been set to 1 by the device.  The caller synchronises once and reads
+ *   state  int32[32]: [0] t, [1] round within the frame, [2] n = entries of the result, [3] done, [5] rounds that did work,
+ *                     [8 + j] the length of entry j (labels after the leading blank);
+ *   tokens int32[beam, max_length]: tokens[j][0] = blank, tokens[j][1 .. state[8 + j]] the labels of entry j;
+ *   scores double[beam]: log-probability of entry j (fp64 accumulation of fp32 log-softmax terms);
+ * entries j < n sorted best first.  Arguments as rnnt_engine_greedy_decode; `tables`: NULL (rebuilt in the workspace by every
+ * call) or a buffer of rnnt_engine_greedy_decode_build_tables for the SAME parameters.  1 <= beam <= 16 (RNNT_ERR_UNSUPPORTED
+ * above), E, O <= 1024, E % 4 == 0, O % 4 == 0, H % 8 == 0, V % 4 == 0, 2 <= max_length <= 65536.  Every argument is checked
+ * before anything is enqueued.
+ */
+int rnnt_engine_beam_decode_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int beam, size_t *out);
+int rnnt_engine_beam_decode(const void *frames, int64_t frame_stride, int T, const rnnt_conv_predictor_params *p,
+                            int S, int E, int O, float ln_in_eps, float ln_out_eps, const void *text_W, const void *text_b,
+                            const void *W, const void *bias, int H, int V, int blank, int max_length, int max_per_frame,
+                            int beam, const void *tables, int iterations, int init, int32_t *host_flag, int32_t *state,
+                            int32_t *tokens, double *scores, void *workspace, size_t ws_bytes, void *stream);
+
+/*
  * y = x W^T + b and its backward as MFMA kernels: the joint's optional input projections
  * audio_ln / text_ln (next-step row SURVEY.md 8f-1; reference rnnt/joint.py:8-12,26-30).
  * x [M,K] with rows ldx floats apart, W [N,K] (torch.nn.Linear layout), y / dy [M,N] contiguous.

@@ -1,0 +1,600 @@
+// beam.hip — frame-synchronous beam search of ONE utterance on the device (rnnt_engine_beam_decode).
+//
+// The search (exact definition: DESIGN.md §4h, tests/beam_oracle.py): at most `m` labels per frame, hypotheses merged by
+// token sequence; beam 1 is the reference's greedy decode (rnnt/model.py:95-128).  Per frame t, rounds r = 0 .. m-1: every
+// ACTIVE hypothesis h is scored lp = log_softmax(single_forward(frame_t, predictor([blank] + y_h)[-1])); its blank candidate
+// (y_h, score + lp[blank]) joins the finished set N of the frame (merged by sequence with logaddexp), its label candidates
+// (y_h + [k], score + lp[k]), k != blank, are generated while len(y_h) < max_length - 1; the best `beam` of N + labels are
+// kept, the kept labels are the next round's actives.  The frame ends when no label is kept; after round m-1 kept labels
+// are CAPPED: they move to the next frame without a blank term, merged with N by sequence.
+//
+// One ROUND is a fixed kernel sequence over the <= 16 slots of the beam — the slots are the M = 16 rows of every product:
+//   k_beam_conv1   conv1 outputs of the last 5 positions of every slot that just took a label, from the tap tables of
+//                  rnnt_engine_greedy_decode_build_tables (A_j[s] = W1_j LN(embedding[s])): the conv1-output ring, rebuilt
+//                  from the slot's last 7 tokens (the module is causal: its last frame is a function of those only)
+//   k_beam_gemm16  conv2 (5 taps, GELU), linear, with joint.text_ln the projection of LN(z): 16 rows x 16 outputs per
+//                  workgroup on v_mfma_f32_16x16x4_f32, every weight read once per round for all slots
+//   k_beam_ln16    (no text_ln) the predictor's output LayerNorm -> the slot's text vector
+//   k_beam_joint   logits [16][V] = tanh(frame_t + text_slot) W^T + bias: vocabulary-parallel, 16 entries per workgroup,
+//                  tanh of the SUM (no factored form, no range limit)
+//   k_beam_reduce  per active slot: log-sum-exp, the blank logit and the top-`beam` non-blank labels
+//   k_beam_select  one workgroup: candidates, merges by sequence (64-bit hash as a pre-filter, exact comparison), the best
+//                  `beam`, the cap, max_length, t / round / done, the next slot buffer (tokens, lengths, scores, text vectors)
+// The predictor kernels return at once in rounds where no slot took a label (round 0 of a frame after a blank-only one),
+// every kernel once the search is over.  Nothing spins; no workgroup waits for another.
+// Arithmetic: fp32 products (fp32 MFMA, exact fp32 as fmaf chains), log-sum-exp in fp32, SCORES in fp64 (the log-probability
+// (double)logit - (double)lse is added to a double score; logaddexp in double).
+// Ties (no result may depend on one): finished entries first, then parent slot ascending, then token id ascending; the
+// per-slot top labels break ties by the lower token id (torch.argmax's first index at beam 1).
+#include "kernels.hpp"
+
+#define BM 16          // slots: the M dimension of every product
+#define BEAM_RED 48    // floats per slot of k_beam_reduce's output: [0] lse, [1] blank logit, [16 + 2q] q-th label logit, [17 + 2q] its id
+#define BEAM_NC (32 + BM * BM)  // candidates of one selection: <= 32 finished, beam x beam labels
+#define BEAM_HASH_MUL 0x100000001b3ULL
+
+// state (int32[32]) — also the caller's view of the search:
+//   [0] t  [1] round within the frame  [2] entries of the beam  [3] done  [4] some slot awaits its predictor step
+//   [5] rounds that did work  [6] current slot buffer (0 / 1)  [8 + j] length of entry j of the result (done)
+enum { BS_T = 0, BS_R = 1, BS_N = 2, BS_DONE = 3, BS_NEW = 4, BS_ROUNDS = 5, BS_CUR = 6, BS_LEN = 8 };
+// slot status
+enum { SL_EMPTY = 0, SL_ACTIVE = 1, SL_FINISHED = 2 };
+
+struct BeamSlots {
+    double *score;               // [2][BM]
+    unsigned long long *hash;    // [2][BM]  hash of the token sequence (pre-filter of the merges)
+    int *len, *status, *need;    // [2][BM]  tokens after the leading blank | SL_* | text vector still to compute
+    int *tok;                    // [2][BM][max_length]: tok[.][.][0] = blank, [1 .. len] the labels
+    float *pvec;                 // [2][BM][H]: the joint's text input of the slot's sequence (after text_ln / LayerNorm)
+};
+
+__device__ __forceinline__ float beam_gelu(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
+
+__device__ __forceinline__ double beam_logaddexp(double a, double b)
+{
+    const double m = fmax(a, b);
+    if (m == -__builtin_inf()) return m;
+    return m + log1p(exp(-fabs(a - b)));
+}
+
+__device__ __forceinline__ float beam_block_sum(float v, float *red)  // 256 threads; red[4]
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const float s = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    return s;
+}
+
+// ---- start of a search: slot 0 of buffer 0 = the empty hypothesis (score 0, text vector to compute), everything else empty
+// (the workspace was zero-filled by the launcher: no value of a previous call, or of the caller's memory, is ever read)
+__global__ void k_beam_init(BeamSlots P, int32_t *state, int blank, int max_length)
+{
+    if (threadIdx.x != 0) return;
+    P.status[0] = SL_ACTIVE; P.need[0] = 1; P.len[0] = 0; P.score[0] = 0.0; P.hash[0] = 0ull;
+    P.tok[0] = blank;
+    for (int i = 0; i < 32; ++i) state[i] = 0;
+    state[BS_N] = 1; state[BS_NEW] = 1;
+}
+
+// ---- conv1 outputs of positions p-4 .. p of every slot awaiting its predictor step (p = len: the newest token), as
+// g1[slot][q][E], q = 0 .. 4 (zero rows before position 0 = conv2's left padding):
+//   g1[pos] = gelu(b1 + A2[tok pos] + A1[tok pos-1] + A0[tok pos-2])      (rnnt/predictor.py:214-219, eval mode)
+__global__ __launch_bounds__(256) void k_beam_conv1(const int32_t *__restrict__ state, BeamSlots P, int max_length, int S, int E,
+                                                    const float *__restrict__ tab, const float *__restrict__ b1, float *__restrict__ g1)
+{
+    if (state[BS_DONE] || !state[BS_NEW]) return;
+    const int cur = state[BS_CUR], j = blockIdx.x;
+    if (!P.need[cur * BM + j]) return;
+    const int p = P.len[cur * BM + j];
+    const int *tk = P.tok + ((size_t)cur * BM + j) * max_length;
+    for (int q = 0; q < 5; ++q) {
+        const int pos = p - 4 + q;
+        float *out = g1 + ((size_t)j * 5 + q) * E;
+        if (pos < 0) {
+            for (int i = threadIdx.x; i < E; i += 256) out[i] = 0.f;
+            continue;
+        }
+        auto row = [&](int at, int tap) {
+            int s = tk[at];
+            s = s < 0 ? 0 : (s >= S ? S - 1 : s);
+            return tab + (size_t)s * 3 * E + (size_t)tap * E;
+        };
+        const float *a2 = row(pos, 2), *a1 = pos >= 1 ? row(pos - 1, 1) : nullptr, *a0 = pos >= 2 ? row(pos - 2, 0) : nullptr;
+        for (int i = threadIdx.x; i < E; i += 256) {
+            float v = b1[i] + a2[i];
+            if (a1) v += a1[i];
+            if (a0) v += a0[i];
+            out[i] = beam_gelu(v);
+        }
+    }
+}
+
+// ---- Y[16][N] = act(bias + X[16][taps*Kin] . W^T) for the 16 slots.  W element (n, tap*Kin + i) at W[(tap*N + n)*Kin + i]:
+// taps = 1 is torch.nn.Linear's [N][K], taps = 5 the [tap][out][in] conv pack.  LNIN: X is LN(z) * gamma + beta of the rows
+// of `X` (Kin = taps * Kin features), normalised by the workgroup itself.  A workgroup: 16 outputs, its 4 waves split the
+// reduction (16 k per chunk: a float4 per lane and operand -> 4 MFMAs, the k order inside the chunk permuted alike for both),
+// partial tiles meet in LDS.  `masked`: only rows of slots awaiting their predictor step are written, into the CURRENT
+// buffer (Y + cur * y_par).  Kin % 4 == 0, ldx % 4 == 0.
+template <bool LNIN>
+__global__ __launch_bounds__(256) void k_beam_gemm16(const int32_t *__restrict__ state, const int *__restrict__ need,
+                                                     const float *__restrict__ X, int ldx, const float *__restrict__ W, int taps, int Kin,
+                                                     int N, const float *__restrict__ bias, int act, const float *__restrict__ gamma,
+                                                     const float *__restrict__ beta, float eps, float *__restrict__ Y, int ldy,
+                                                     long y_par, int masked)
+{
+    __shared__ float s_acc[4][16][17];
+    __shared__ float s_mean[16], s_rstd[16];
+    if (state[BS_DONE] || !state[BS_NEW]) return;
+    const int cur = state[BS_CUR];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+    const int n0 = blockIdx.x * 16, ncol = min(n0 + r, N - 1);
+    const int Kred = taps * Kin;
+    if (LNIN) {  // mean / rstd of the 16 rows (two passes, a wave per 4 rows)
+        for (int rr = wave * 4; rr < wave * 4 + 4; ++rr) {
+            const float *x = X + (size_t)rr * ldx;
+            float s = 0.f;
+            for (int i = lane; i < Kred; i += 64) s += x[i];
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+            const float mean = s / Kred;
+            float s2 = 0.f;
+            for (int i = lane; i < Kred; i += 64) { const float d = x[i] - mean; s2 += d * d; }
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) s2 += __shfl_xor(s2, m, 64);
+            if (lane == 0) { s_mean[rr] = mean; s_rstd[rr] = rsqrtf(s2 / Kred + eps); }
+        }
+        __syncthreads();
+    }
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const float *xr = X + (size_t)r * ldx;
+    const int nchunk = (Kred + 15) / 16;
+    for (int c = wave; c < nchunk; c += 4) {
+        const int k = 16 * c + 4 * g;
+        f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
+        if (k < Kred) {  // (Kred % 4 == 0: the whole float4 is in range)
+            a = *(const f32x4 *)(xr + k);
+            if (LNIN) {
+                const f32x4 ga = *(const f32x4 *)(gamma + k), be = *(const f32x4 *)(beta + k);
+                a = (a - s_mean[r]) * s_rstd[r] * ga + be;
+            }
+            const int tap = k / Kin, i = k - tap * Kin;
+            b = *(const f32x4 *)(W + ((size_t)tap * N + ncol) * Kin + i);
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], b[s], acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s_acc[wave][4 * g + i][r] = acc[i];  // D: row (slot) 4 (lane >> 4) + i, column lane & 15
+    __syncthreads();
+    const int row = threadIdx.x >> 4, col = threadIdx.x & 15, n = n0 + col;
+    if (n >= N || (masked && !need[cur * BM + row])) return;
+    float v = ((s_acc[0][row][col] + s_acc[1][row][col]) + (s_acc[2][row][col] + s_acc[3][row][col])) + (bias ? bias[n] : 0.f);
+    if (act) v = beam_gelu(v);
+    Y[(masked ? (size_t)cur * y_par : 0) + (size_t)row * ldy + n] = v;
+}
+
+// ---- the predictor's output LayerNorm (rnnt/predictor.py:229) as the joint's text vector when the joint has no text_ln
+__global__ __launch_bounds__(256) void k_beam_ln16(const int32_t *__restrict__ state, const int *__restrict__ need, const float *__restrict__ z,
+                                                   int O, const float *__restrict__ gamma, const float *__restrict__ beta, float eps,
+                                                   float *__restrict__ pvec)
+{
+    __shared__ float red[4];
+    if (state[BS_DONE] || !state[BS_NEW]) return;
+    const int cur = state[BS_CUR], j = blockIdx.x;
+    if (!need[cur * BM + j]) return;
+    const float *x = z + (size_t)j * O;
+    float s = 0.f;
+    for (int i = threadIdx.x; i < O; i += 256) s += x[i];
+    const float mean = beam_block_sum(s, red) / O;
+    float s2 = 0.f;
+    for (int i = threadIdx.x; i < O; i += 256) { const float d = x[i] - mean; s2 += d * d; }
+    const float rstd = rsqrtf(beam_block_sum(s2, red) / O + eps);
+    float *y = pvec + ((size_t)cur * BM + j) * O;
+    for (int i = threadIdx.x; i < O; i += 256) y[i] = (x[i] - mean) * rstd * gamma[i] + beta[i];
+}
+
+// ---- logits[slot][v] = tanh(frame_t + pvec[slot]) . W[v] + bias[v] for all 16 slots, 16 vocabulary entries per workgroup
+// (rnnt/joint.py:44-55 after the projections).  The hidden operand is built in registers: lane (slot r, k group g) takes
+// tanh of its own sums, each element once per workgroup.  H % 4 == 0.
+__global__ __launch_bounds__(256) void k_beam_joint(const int32_t *__restrict__ state, const float *__restrict__ frames, long fstride,
+                                                    const float *__restrict__ pvec, const float *__restrict__ W, const float *__restrict__ bias,
+                                                    int H, int V, float *__restrict__ logits)
+{
+    __shared__ float s_acc[4][16][17];
+    if (state[BS_DONE]) return;
+    const int t = state[BS_T], cur = state[BS_CUR];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+    const int v0 = blockIdx.x * 16, vcol = min(v0 + r, V - 1);
+    const float *f = frames + (size_t)t * fstride, *pv = pvec + ((size_t)cur * BM + r) * H, *wr = W + (size_t)vcol * H;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const int nchunk = (H + 15) / 16;
+    for (int c = wave; c < nchunk; c += 4) {
+        const int k = 16 * c + 4 * g;
+        f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
+        if (k < H) {
+            const f32x4 e = *(const f32x4 *)(f + k), p = *(const f32x4 *)(pv + k);
+            b = *(const f32x4 *)(wr + k);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) a[s] = fast_tanh(e[s] + p[s]);
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], b[s], acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s_acc[wave][4 * g + i][r] = acc[i];
+    __syncthreads();
+    const int row = threadIdx.x >> 4, col = threadIdx.x & 15, v = v0 + col;
+    if (v >= V) return;
+    logits[(size_t)row * V + v] = ((s_acc[0][row][col] + s_acc[1][row][col]) + (s_acc[2][row][col] + s_acc[3][row][col])) + bias[v];
+}
+
+// (value, id) order of the label lists: larger value first, then the lower id
+__device__ __forceinline__ bool beam_before(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
+
+__device__ __forceinline__ void beam_wave_best(float &v, int &id)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const float ov = __shfl_xor(v, m, 64);
+        const int oi = __shfl_xor(id, m, 64);
+        if (beam_before(ov, oi, v, id)) { v = ov; id = oi; }
+    }
+}
+
+// ---- per active slot (a workgroup of 16 waves each): log-sum-exp of the V logits, the blank logit and the `beam` best
+// non-blank labels.  Waves walk 256-entry chunks, merging each into a running list of `beam` entries (lane q holds entry q)
+// by `beam` wave-wide extractions; wave 0 merges the 16 lists the same way.
+__global__ __launch_bounds__(1024) void k_beam_reduce(const int32_t *__restrict__ state, const int *__restrict__ status,
+                                                      const float *__restrict__ logits, int V, int blank, int beam, float *__restrict__ red)
+{
+    __shared__ float s_v[16][BM], s_m[16], s_s[16];
+    __shared__ int s_i[16][BM];
+    if (state[BS_DONE]) return;
+    const int cur = state[BS_CUR], j = blockIdx.x;
+    if (status[cur * BM + j] != SL_ACTIVE) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float *x = logits + (size_t)j * V;
+    const float NEG = RNNT_NEG_INF;
+    const int NONE = 0x7fffffff;
+    float lm = NEG, ls = 0.f;            // this lane's running (max, sum of exp)
+    float lv = NEG;                      // entry `lane` of the wave's list
+    int li = NONE;
+    for (int c0 = wave * 256; c0 < V; c0 += 16 * 256) {
+        const int v = c0 + 4 * lane;
+        float cv[5];
+        int ci[5];
+        if (v < V) {  // V % 4 == 0
+            const f32x4 q = *(const f32x4 *)(x + v);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float y = q[e];
+                if (y > lm) { ls = ls * expf(lm - y) + 1.f; lm = y; }
+                else ls += expf(y - lm);
+                cv[e] = (v + e == blank) ? NEG : y;
+                ci[e] = (v + e == blank) ? NONE : v + e;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { cv[e] = NEG; ci[e] = NONE; }
+        }
+        cv[4] = lv; ci[4] = li;
+        float nv = NEG;
+        int ni = NONE;
+        for (int q = 0; q < beam; ++q) {
+            float bv = cv[0];
+            int bi = ci[0], bw = 0;
+#pragma unroll
+            for (int e = 1; e < 5; ++e)
+                if (beam_before(cv[e], ci[e], bv, bi)) { bv = cv[e]; bi = ci[e]; bw = e; }
+            float wv = bv;
+            int wi = bi;
+            beam_wave_best(wv, wi);
+            if (lane == q) { nv = wv; ni = wi; }
+            if (wi != NONE && bi == wi) {  // the owner drops the extracted entry (ids are unique)
+#pragma unroll
+                for (int e = 0; e < 5; ++e)
+                    if (e == bw) { cv[e] = NEG; ci[e] = NONE; }
+            }
+        }
+        lv = nv; li = ni;
+    }
+    // the wave's (max, sum): combine the lanes
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const float om = __shfl_xor(lm, m, 64), os = __shfl_xor(ls, m, 64);
+        const float nm = fmaxf(lm, om);
+        if (nm != NEG) {
+            ls = (lm == NEG ? 0.f : ls * expf(lm - nm)) + (om == NEG ? 0.f : os * expf(om - nm));
+            lm = nm;
+        }
+    }
+    if (lane == 0) { s_m[wave] = lm; s_s[wave] = ls; }
+    if (lane < BM) { s_v[wave][lane] = lane < beam ? lv : NEG; s_i[wave][lane] = lane < beam ? li : NONE; }
+    __syncthreads();
+    if (wave != 0) return;
+    float cv[4];
+    int ci[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int k = 4 * lane + e;  // 256 entries: list k >> 4, entry k & 15
+        cv[e] = s_v[k >> 4][k & 15];
+        ci[e] = s_i[k >> 4][k & 15];
+    }
+    float *out = red + (size_t)j * BEAM_RED;
+    for (int q = 0; q < beam; ++q) {
+        float bv = cv[0];
+        int bi = ci[0], bw = 0;
+#pragma unroll
+        for (int e = 1; e < 4; ++e)
+            if (beam_before(cv[e], ci[e], bv, bi)) { bv = cv[e]; bi = ci[e]; bw = e; }
+        float wv = bv;
+        int wi = bi;
+        beam_wave_best(wv, wi);
+        if (lane == 0) { out[16 + 2 * q] = wv; out[17 + 2 * q] = __int_as_float(wi); }
+        if (wi != NONE && bi == wi) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (e == bw) { cv[e] = NEG; ci[e] = NONE; }
+        }
+    }
+    if (lane == 0) {
+        float M = NEG;
+        for (int w = 0; w < 16; ++w) M = fmaxf(M, s_m[w]);
+        float S = 0.f;
+        for (int w = 0; w < 16; ++w)
+            if (s_m[w] != NEG) S += s_s[w] * expf(s_m[w] - M);
+        out[0] = M + logf(S);
+        out[1] = x[blank];
+    }
+}
+
+__device__ bool beam_same_prefix(const int *a, const int *b, int len)  // positions 1 .. len
+{
+    for (int i = 1; i <= len; ++i)
+        if (a[i] != b[i]) return false;
+    return true;
+}
+
+// ---- one workgroup: the selection of the round and the search's bookkeeping
+__global__ __launch_bounds__(256) void k_beam_select(BeamSlots P, const float *__restrict__ red, int beam, int V, int H, int T, int max_length,
+                                                     int max_per_frame, int32_t *__restrict__ state, int32_t *__restrict__ out_tokens,
+                                                     double *__restrict__ out_scores, int32_t *host_flag)
+{
+    __shared__ double c_score[BEAM_NC];
+    __shared__ int c_kind[BEAM_NC], c_a[BEAM_NC], c_b[BEAM_NC], c_src[BEAM_NC];
+    __shared__ unsigned char c_valid[BEAM_NC];
+    __shared__ double o_score[BM];
+    __shared__ unsigned long long o_hash[BM];
+    __shared__ int o_len[BM], o_st[BM], s_bmatch[BM], s_keep[BM], s_final[BM];
+    __shared__ int s_nfinal, s_frame_end, s_done;
+    if (state[BS_DONE]) return;
+    const int tid = threadIdx.x, cur = state[BS_CUR], nb = cur ^ 1, r = state[BS_R];
+    const int *tok_old = P.tok + (size_t)cur * BM * max_length;
+    if (tid < BM) {
+        const int idx = cur * BM + tid;
+        o_st[tid] = tid < beam ? P.status[idx] : SL_EMPTY;
+        o_score[tid] = P.score[idx]; o_hash[tid] = P.hash[idx]; o_len[tid] = P.len[idx];
+    }
+    if (tid < BM) s_keep[tid] = -1;
+    for (int c = tid; c < BEAM_NC; c += 256) c_valid[c] = 0;
+    __syncthreads();
+    // the finished entry each active slot's blank candidate merges with (the actives are distinct sequences, so are N's)
+    if (tid < beam && o_st[tid] == SL_ACTIVE) {
+        int mt = -1;
+        for (int i = 0; i < beam && mt < 0; ++i)
+            if (o_st[i] == SL_FINISHED && o_hash[i] == o_hash[tid] && o_len[i] == o_len[tid] &&
+                beam_same_prefix(tok_old + (size_t)i * max_length, tok_old + (size_t)tid * max_length, o_len[tid]))
+                mt = i;
+        s_bmatch[tid] = mt;
+    }
+    // label candidates (parent j, its q-th label): at 32 + j * beam + q
+    for (int c = tid; c < beam * beam; c += 256) {
+        const int j = c / beam, q = c - j * beam, pos = 32 + c;
+        if (o_st[j] != SL_ACTIVE || o_len[j] >= max_length - 1) continue;
+        const float *rj = red + (size_t)j * BEAM_RED;
+        const int id = __float_as_int(rj[17 + 2 * q]);
+        if (id < 0 || id >= V) continue;
+        c_score[pos] = o_score[j] + ((double)rj[16 + 2 * q] - (double)rj[0]);
+        c_kind[pos] = 1; c_a[pos] = j; c_b[pos] = id; c_src[pos] = j; c_valid[pos] = 1;
+    }
+    __syncthreads();
+    if (tid == 0) {  // N: the finished entries in slot order, then the unmerged blank candidates in slot order
+        int nF = 0, fpos[BM];
+        for (int i = 0; i < beam; ++i) {
+            fpos[i] = -1;
+            if (o_st[i] != SL_FINISHED) continue;
+            c_score[nF] = o_score[i]; c_src[nF] = i; fpos[i] = nF++;
+        }
+        for (int j = 0; j < beam; ++j) {
+            if (o_st[j] != SL_ACTIVE) continue;
+            const float *rj = red + (size_t)j * BEAM_RED;
+            const double bs = o_score[j] + ((double)rj[1] - (double)rj[0]);
+            if (s_bmatch[j] >= 0) { const int k = fpos[s_bmatch[j]]; c_score[k] = beam_logaddexp(c_score[k], bs); }
+            else { c_score[nF] = bs; c_src[nF] = j; ++nF; }
+        }
+        for (int f = 0; f < nF; ++f) { c_kind[f] = 0; c_a[f] = f; c_b[f] = 0; c_valid[f] = 1; }
+    }
+    __syncthreads();
+    // rank of every candidate = how many beat it; the best `beam` are kept, at their rank
+    const int ncand = 32 + beam * beam;
+    for (int c = tid; c < ncand; c += 256) {
+        if (!c_valid[c]) continue;
+        const double sc = c_score[c];
+        int rank = 0;
+        for (int d = 0; d < ncand; ++d) {
+            if (!c_valid[d] || d == c) continue;
+            const double sd = c_score[d];
+            const bool better = sd > sc || (sd == sc && (c_kind[d] < c_kind[c] || (c_kind[d] == c_kind[c] &&
+                                                       (c_a[d] < c_a[c] || (c_a[d] == c_a[c] && c_b[d] < c_b[c])))));
+            rank += better;
+        }
+        if (rank < beam) s_keep[rank] = c;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int nk = 0;  // (the ranks are a permutation: keys are distinct)
+        while (nk < beam && s_keep[nk] >= 0) ++nk;
+        int nact = 0;
+        for (int i = 0; i < nk; ++i) nact += c_kind[s_keep[i]];
+        const int frame_end = nact == 0 || r >= max_per_frame - 1;
+        int n = 0;
+        if (frame_end && nact > 0) {  // the cap: kept labels join N without a blank term, merged by sequence
+            for (int i = 0; i < nk; ++i)
+                if (c_kind[s_keep[i]] == 0) s_final[n++] = s_keep[i];
+            const int nfin = n;
+            for (int i = 0; i < nk; ++i) {
+                const int c = s_keep[i];
+                if (c_kind[c] == 0) continue;
+                const int src = c_src[c], len = o_len[src] + 1;
+                const unsigned long long h = o_hash[src] * BEAM_HASH_MUL + (unsigned long long)(c_b[c] + 1);
+                int hit = -1;
+                for (int f = 0; f < nfin && hit < 0; ++f) {
+                    const int fs = c_src[s_final[f]];
+                    if (o_len[fs] != len || o_hash[fs] != h) continue;
+                    const int *a = tok_old + (size_t)fs * max_length, *b = tok_old + (size_t)src * max_length;
+                    if (a[len] == c_b[c] && beam_same_prefix(a, b, len - 1)) hit = f;
+                }
+                if (hit >= 0) c_score[s_final[hit]] = beam_logaddexp(c_score[s_final[hit]], c_score[c]);
+                else s_final[n++] = c;
+            }
+            for (int i = 1; i < n; ++i) {  // stable: by score, finished before capped at equal scores
+                const int c = s_final[i];
+                int k = i;
+                while (k > 0 && c_score[s_final[k - 1]] < c_score[c]) { s_final[k] = s_final[k - 1]; --k; }
+                s_final[k] = c;
+            }
+        } else {
+            for (int i = 0; i < nk; ++i) s_final[n++] = s_keep[i];
+        }
+        s_nfinal = n;
+        s_frame_end = frame_end;
+        s_done = frame_end && state[BS_T] + 1 >= T;
+    }
+    __syncthreads();
+    const int n = s_nfinal, frame_end = s_frame_end, done = s_done;
+    // the next slot buffer
+    if (tid < BM) {
+        const int idx = nb * BM + tid;
+        if (tid < n) {
+            const int c = s_final[tid], src = c_src[c], lab = c_kind[c];
+            P.score[idx] = c_score[c];
+            P.len[idx] = o_len[src] + lab;
+            P.hash[idx] = lab ? o_hash[src] * BEAM_HASH_MUL + (unsigned long long)(c_b[c] + 1) : o_hash[src];
+            P.status[idx] = frame_end || lab ? SL_ACTIVE : SL_FINISHED;
+            P.need[idx] = lab;
+            if (done) { out_scores[tid] = c_score[c]; state[BS_LEN + tid] = o_len[src] + lab; }
+        } else {
+            P.score[idx] = -__builtin_inf(); P.len[idx] = 0; P.hash[idx] = 0ull; P.status[idx] = SL_EMPTY; P.need[idx] = 0;
+        }
+    }
+    int *tok_new = P.tok + (size_t)nb * BM * max_length;
+    for (int e = tid; e < n * max_length; e += 256) {
+        const int s = e / max_length, i = e - s * max_length, c = s_final[s], src = c_src[c], len = o_len[src];
+        int v;
+        if (i <= len) v = tok_old[(size_t)src * max_length + i];
+        else if (i == len + 1 && c_kind[c]) v = c_b[c];
+        else continue;
+        tok_new[(size_t)s * max_length + i] = v;
+        if (done) out_tokens[(size_t)s * max_length + i] = v;
+    }
+    // text vectors move with their hypotheses (a new label's is computed by the next round's predictor step)
+    const int H4 = H / 4;
+    for (int e = tid; e < n * H4; e += 256) {
+        const int s = e / H4, h = 4 * (e - s * H4), c = s_final[s];
+        if (c_kind[c]) continue;
+        *(f32x4 *)(P.pvec + ((size_t)nb * BM + s) * H + h) = *(const f32x4 *)(P.pvec + ((size_t)cur * BM + c_src[c]) * H + h);
+    }
+    if (tid == 0) {
+        int any_new = 0;
+        for (int s = 0; s < n; ++s) any_new |= c_kind[s_final[s]];
+        state[BS_T] = state[BS_T] + frame_end;
+        state[BS_R] = frame_end ? 0 : r + 1;
+        state[BS_N] = n;
+        state[BS_NEW] = any_new;
+        state[BS_ROUNDS] += 1;
+        state[BS_CUR] = nb;
+        state[BS_DONE] = done;
+        // the host's cue to stop enqueueing rounds (mapped pinned memory, polled without a synchronisation)
+        if (done && host_flag) __hip_atomic_store(host_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// ---- workspace: slot buffers | predictor intermediates | logits | reduce output | the model's tables (when built here)
+struct BeamLayout { size_t score, hash, len, status, need, tok, pvec, g1, g2, z, logits, red, state_end, tables, total; };
+static BeamLayout beam_layout(int S, int E, int O, int H, int V, int has_text, int max_length)
+{
+    BeamLayout L;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+    L.score = take(2 * BM * sizeof(double));
+    L.hash = take(2 * BM * sizeof(unsigned long long));
+    L.len = take(2 * BM * 4);
+    L.status = take(2 * BM * 4);
+    L.need = take(2 * BM * 4);
+    L.tok = take((size_t)2 * BM * max_length * 4);
+    L.pvec = take((size_t)2 * BM * H * 4);
+    L.g1 = take((size_t)BM * 5 * E * 4);
+    L.g2 = take((size_t)BM * E * 4);
+    L.z = take((size_t)BM * O * 4);
+    L.logits = take((size_t)BM * V * 4);
+    L.red = take((size_t)BM * BEAM_RED * 4);
+    L.state_end = o;
+    L.tables = take(dec_tables_floats(S, E, O, H, has_text) * 4);
+    L.total = o;
+    return L;
+}
+size_t beam_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length)
+{
+    return beam_layout(S, E, O, H, V, has_text, max_length).total;
+}
+
+void launch_beam_decode(const BeamArgs &ba, hipStream_t st)
+{
+    const DecLoopArgs &a = ba.d;
+    const int S = a.S, E = a.E, O = a.O, H = a.H, V = a.V, ML = a.max_length, has_text = a.text_W ? 1 : 0;
+    const BeamLayout L = beam_layout(S, E, O, H, V, has_text, ML);
+    char *ws = (char *)a.workspace;
+    BeamSlots P;
+    P.score = (double *)(ws + L.score); P.hash = (unsigned long long *)(ws + L.hash);
+    P.len = (int *)(ws + L.len); P.status = (int *)(ws + L.status); P.need = (int *)(ws + L.need);
+    P.tok = (int *)(ws + L.tok); P.pvec = (float *)(ws + L.pvec);
+    float *g1 = (float *)(ws + L.g1), *g2 = (float *)(ws + L.g2), *z = (float *)(ws + L.z);
+    float *logits = (float *)(ws + L.logits), *red = (float *)(ws + L.red);
+    const float *tb = (const float *)a.tables;
+    if (a.init) {
+        launch_fill32(ws, 0u, L.state_end, st);
+        hipLaunchKernelGGL(k_beam_init, dim3(1), dim3(64), 0, st, P, a.state, a.blank, ML);
+    }
+    if (!tb) {  // (rebuilt on every call that brings none: a function of the parameters only)
+        launch_dec_build_tables(a.p, S, E, O, a.ln_in_eps, a.text_W, a.text_b, H, (float *)(ws + L.tables), st);
+        tb = (const float *)(ws + L.tables);
+    }
+    size_t otab, owp2;
+    dec_tables_offsets(S, E, O, H, has_text, &otab, &owp2);
+    const float *tab = tb + otab, *wp2 = tb + owp2;
+    const float *nul = nullptr;
+    for (int it = 0; it < a.iterations; ++it) {
+        hipLaunchKernelGGL(k_beam_conv1, dim3(BM), dim3(256), 0, st, a.state, P, ML, S, E, tab, a.p.conv1_b, g1);
+        // g2 = gelu(conv2(g1[p-4 .. p]))                                                  rnnt/predictor.py:222-223
+        hipLaunchKernelGGL(k_beam_gemm16<false>, dim3((E + 15) / 16), dim3(256), 0, st, a.state, P.need, g1, 5 * E, wp2, 5, E, E,
+                           a.p.conv2_b, 1, nul, nul, 0.f, g2, E, 0L, 0);
+        // z = linear(g2)                                                                  rnnt/predictor.py:228
+        hipLaunchKernelGGL(k_beam_gemm16<false>, dim3((O + 15) / 16), dim3(256), 0, st, a.state, P.need, g2, E, a.p.linear_w, 1, E, O,
+                           a.p.linear_b, 0, nul, nul, 0.f, z, O, 0L, 0);
+        // the slot's text vector: text_ln(LN(z)) (rnnt/joint.py:28-30) or LN(z) itself         rnnt/predictor.py:229
+        if (has_text)
+            hipLaunchKernelGGL(k_beam_gemm16<true>, dim3((H + 15) / 16), dim3(256), 0, st, a.state, P.need, z, O, a.text_W, 1, O, H,
+                               a.text_b, 0, a.p.ln_out_w, a.p.ln_out_b, a.ln_eps, P.pvec, H, (long)BM * H, 1);
+        else
+            hipLaunchKernelGGL(k_beam_ln16, dim3(BM), dim3(256), 0, st, a.state, P.need, z, O, a.p.ln_out_w, a.p.ln_out_b, a.ln_eps, P.pvec);
+        hipLaunchKernelGGL(k_beam_joint, dim3((V + 15) / 16), dim3(256), 0, st, a.state, a.frames, a.frame_stride, P.pvec, a.W, a.bias, H, V,
+                           logits);
+        hipLaunchKernelGGL(k_beam_reduce, dim3(ba.beam), dim3(1024), 0, st, a.state, P.status, logits, V, a.blank, ba.beam, red);
+        hipLaunchKernelGGL(k_beam_select, dim3(1), dim3(256), 0, st, P, red, ba.beam, V, H, a.T, ML, a.max_per_frame, a.state, a.tokens,
+                           ba.scores, a.host_flag);
+    }
+}

@@ -1103,6 +1103,12 @@ static DecTablesLayout dec_tables_layout(int S, int E, int O, int H, int has_tex
     return L;
 }
 size_t dec_tables_floats(int S, int E, int O, int H, int has_text) { return dec_tables_layout(S, E, O, H, has_text).total; }
+void dec_tables_offsets(int S, int E, int O, int H, int has_text, size_t *tab, size_t *wp2)
+{
+    const DecTablesLayout L = dec_tables_layout(S, E, O, H, has_text);
+    *tab = L.tab;
+    *wp2 = L.wp2;
+}
 
 void launch_dec_build_tables(const rnnt_conv_predictor_params &p, int S, int E, int O, float ln_in_eps, const float *text_W, const float *text_b, int H,
                              float *tb, hipStream_t st)

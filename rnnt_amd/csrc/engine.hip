@@ -745,6 +745,49 @@ int rnnt_engine_greedy_decode(const void *frames, int64_t frame_stride, int T, c
     return launch_status("rnnt_engine_greedy_decode");
 }
 
+int rnnt_engine_beam_decode_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int beam, size_t *out)
+{
+    if (!out) return fail(RNNT_ERR_INVALID_ARG, "null size pointer");
+    if (beam < 1) return fail(RNNT_ERR_INVALID_ARG, "beam=%d must be >= 1", beam);
+    if (beam > 16) return fail(RNNT_ERR_UNSUPPORTED, "beam decode takes beam <= 16 (beam=%d)", beam);
+    if (S < 1 || max_length < 2) return fail(RNNT_ERR_INVALID_ARG, "S=%d max_length=%d (S >= 1, max_length >= 2)", S, max_length);
+    if (max_length > 65536) return fail(RNNT_ERR_UNSUPPORTED, "beam decode takes max_length <= 65536 (max_length=%d)", max_length);
+    if (int rc = check_dims(1, 1, 1, H, V, RNNT_DTYPE_F32, true)) return rc;
+    if (H % 8 != 0) return fail(RNNT_ERR_UNSUPPORTED, "beam decode needs H %% 8 == 0 (H=%d)", H);
+    if (E < 4 || O < 4 || E > 1024 || O > 1024 || E % 4 || O % 4)
+        return fail(RNNT_ERR_UNSUPPORTED, "beam decode needs 4 <= E, O <= 1024, multiples of 4 (E=%d, O=%d)", E, O);
+    if (!has_text && O != H) return fail(RNNT_ERR_INVALID_ARG, "without text_ln the predictor's output dim (%d) must equal H (%d)", O, H);
+    *out = align_up(beam_workspace_bytes(S, E, O, H, V, has_text ? 1 : 0, max_length));
+    return RNNT_OK;
+}
+
+int rnnt_engine_beam_decode(const void *frames, int64_t frame_stride, int T, const rnnt_conv_predictor_params *p,
+                            int S, int E, int O, float ln_in_eps, float ln_out_eps, const void *text_W, const void *text_b,
+                            const void *W, const void *bias, int H, int V, int blank, int max_length, int max_per_frame,
+                            int beam, const void *tables, int iterations, int init, int32_t *host_flag, int32_t *state,
+                            int32_t *tokens, double *scores, void *workspace, size_t ws_bytes, void *stream)
+{
+    size_t need;
+    if (int rc = rnnt_engine_beam_decode_workspace_bytes(S, E, O, H, V, text_W ? 1 : 0, max_length, beam, &need)) return rc;
+    if (iterations < 0) return fail(RNNT_ERR_INVALID_ARG, "iterations=%d", iterations);
+    if (!scores) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument (scores)");
+    if (tables && !aligned16(tables)) return fail(RNNT_ERR_INVALID_ARG, "tables must be 16-byte aligned");
+    if (max_per_frame > 0 && T > 0 && (long)T * max_per_frame + 1 > 0x7fffffffL)
+        return fail(RNNT_ERR_UNSUPPORTED, "T * max_per_frame must stay below 2^31 (T=%d, max_per_frame=%d)", T, max_per_frame);
+    BeamArgs a;
+    if (int rc = dec_check_args(frames, frame_stride, T, p, S, E, O, ln_in_eps, ln_out_eps, text_W, text_b, W, bias, H, V, blank, max_length,
+                                max_per_frame, host_flag, state, tokens, workspace, a.d))
+        return rc;
+    if (ws_bytes < need) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
+    a.d.iterations = iterations ? iterations : T * max_per_frame + 1;
+    a.d.init = init;
+    a.d.tables = tables;
+    a.beam = beam;
+    a.scores = scores;
+    launch_beam_decode(a, (hipStream_t)stream);
+    return launch_status("rnnt_engine_beam_decode");
+}
+
 static int dec_persist_check(int T, int S, int E, int O, int H, int V, int has_text, int max_length)
 {
     if (int rc = check_dims(1, 16, 1, H, V, RNNT_DTYPE_F32, true)) return rc;

@@ -238,3 +238,14 @@ int launch_dec_persist(const DecLoopArgs &a, hipStream_t st);  // hipSuccess, or
 size_t dec_tables_floats(int S, int E, int O, int H, int has_text);
 void launch_dec_build_tables(const rnnt_conv_predictor_params &p, int S, int E, int O, float ln_in_eps, const float *text_W, const float *text_b, int H,
                              float *tables, hipStream_t st);
+// offsets (floats) of the conv1 tap tables tab[s][tap][E] and of conv2's [tap][out][in] pack inside those tables
+void dec_tables_offsets(int S, int E, int O, int H, int has_text, size_t *tab, size_t *wp2);
+
+// ---- beam.hip: frame-synchronous beam search of one utterance (rnnt_engine_beam_decode), kernel-per-step rounds
+struct BeamArgs {
+    DecLoopArgs d;       // frames, predictor, joint, blank, max_length, max_per_frame, iterations (= rounds), init, host_flag, state, tokens
+    int beam;            // 1 .. 16
+    double *scores;      // [beam] out
+};
+size_t beam_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length);
+void launch_beam_decode(const BeamArgs &a, hipStream_t st);

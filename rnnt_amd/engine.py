@@ -73,6 +73,8 @@ SIGNATURES = {
     "rnnt_engine_greedy_decode_persistent": "pqipiiiffppppiiiiipppppzp",
     "rnnt_engine_greedy_decode_tables_bytes": "iiiiip",
     "rnnt_engine_greedy_decode_build_tables": "piiifppipzp",
+    "rnnt_engine_beam_decode_workspace_bytes": "iiiiiiiip",
+    "rnnt_engine_beam_decode": "pqipiiiffppppiiiiiipiipppppzp",
     "rnnt_engine_grad_norm_workspace_bytes": "ipp",
     "rnnt_engine_grad_norm": "ippppzp",
     "rnnt_engine_adamw_step": "ipppppdddddqpfip",
@@ -114,6 +116,7 @@ EXPORTS = (
     "rnnt_engine_greedy_decode_workspace_bytes", "rnnt_engine_greedy_decode",
     "rnnt_engine_greedy_decode_persistent_workspace_bytes", "rnnt_engine_greedy_decode_persistent",
     "rnnt_engine_greedy_decode_tables_bytes", "rnnt_engine_greedy_decode_build_tables",
+    "rnnt_engine_beam_decode_workspace_bytes", "rnnt_engine_beam_decode",
     "rnnt_engine_joint_loss_fwd", "rnnt_engine_run_stages",
     "rnnt_engine_joint_bwd_workspace_bytes", "rnnt_engine_joint_bwd",
     "rnnt_engine_grad_norm_workspace_bytes", "rnnt_engine_grad_norm", "rnnt_engine_adamw_step",
@@ -709,3 +712,59 @@ def greedy_decode_loop(frames, pred_params, ln_eps, text_W, text_b, W, bias, bla
             done += it
         state._keepalive = (flag, frames, params, W, bias, text_W, text_b)  # until the caller has synchronised
     return state, tokens
+
+
+BEAM_MAX = 16  # rnnt_engine_beam_decode: 1 <= beam <= 16 (the slots are the M = 16 rows of every product)
+
+
+def beam_decode_supported(S, E, O, H, V, has_text, max_length, beam):
+    """Whether rnnt_engine_beam_decode takes these sizes (no device work)."""
+    n = ctypes.c_size_t(0)
+    return lib().rnnt_engine_beam_decode_workspace_bytes(int(S), int(E), int(O), int(H), int(V), int(bool(has_text)), int(max_length),
+                                                         int(beam), ctypes.byref(n)) == 0
+
+
+def beam_decode(frames, pred_params, ln_eps, text_W, text_b, W, bias, blank, max_length, beam, max_per_frame=10, tables=None,
+                chunk=32, in_flight=2):
+    """Frame-synchronous beam search of one utterance on the device (C ABI rnnt_engine_beam_decode).  Arguments as
+    greedy_decode_loop, plus `beam` (1 .. 16) and `tables` (greedy_decode_tables(...) of the same parameters, or None: rebuilt inside).
+    Rounds are enqueued `chunk` at a time until the device has raised the end flag in a pinned host word (polled, never waited for);
+    at most `in_flight` chunks are ahead of the device (the host waits for the oldest one's completion event), so the rounds enqueued
+    after the end stay few.  Returns (state int32[32], tokens int32[beam, max_length], scores float64[beam]) device tensors WITHOUT a
+    final synchronisation: afterwards entry j < state[2] is tokens[j, 1 : 1 + state[8 + j]] with log-probability scores[j], best first."""
+    dev, frames, params, text_W, text_b, W, bias = _decode_inputs(frames, pred_params, text_W, text_b, W, bias)
+    T, H = frames.shape
+    V = W.shape[0]
+    S, E = params[0].shape
+    O = params[7].shape[0]
+    beam, max_length, max_per_frame = int(beam), int(max_length), int(max_per_frame)
+    chunk = max(1, int(chunk))
+    bound = T * max(1, max_per_frame) + 1
+    with torch.cuda.device(dev):
+        n = ctypes.c_size_t(0)
+        _check(lib().rnnt_engine_beam_decode_workspace_bytes(S, E, O, H, V, 1 if text_W is not None else 0, max_length, beam, ctypes.byref(n)))
+        ws = workspace(dev, n.value)
+        state = torch.empty(32, dtype=torch.int32, device=dev)
+        tokens = torch.empty(beam, max_length, dtype=torch.int32, device=dev)
+        scores = torch.empty(beam, dtype=torch.float64, device=dev)
+        flag = torch.zeros(1, dtype=torch.int32).pin_memory()
+        st = _PredParams(*[t.data_ptr() for t in params])
+        stream = _stream(dev)
+        eps_in, eps_out = _eps_pair(ln_eps)
+        pending = []
+        done = 0
+        while done < bound and (done == 0 or int(flag[0]) == 0):
+            it = min(chunk, bound - done)
+            _check(lib().rnnt_engine_beam_decode(
+                _p(frames), ctypes.c_int64(frames.stride(0)), T, ctypes.byref(st), S, E, O, ctypes.c_float(eps_in), ctypes.c_float(eps_out),
+                _p(text_W), _p(text_b), _p(W), _p(bias), H, V, int(blank), max_length, max_per_frame, beam, _p(tables), it,
+                1 if done == 0 else 0, ctypes.c_void_p(flag.data_ptr()), _p(state), _p(tokens), _p(scores), _p(ws),
+                ctypes.c_size_t(ws.numel()), stream))
+            done += it
+            ev = torch.cuda.Event()
+            ev.record()
+            pending.append(ev)
+            if len(pending) > max(1, int(in_flight)):
+                pending.pop(0).synchronize()
+        state._keepalive = (flag, frames, params, W, bias, text_W, text_b, tables)  # until the caller has synchronised
+    return state, tokens, scores

@@ -3,6 +3,7 @@ routes the joint + loss through the fused HIP engine.  Encoder and predictor are
 torch modules the caller supplies (stock PyTorch-ROCm; out of scope for the engine).
 """
 import inspect
+import math
 import warnings
 
 import torch
@@ -236,3 +237,109 @@ class RNNTModel(torch.nn.Module):
             else:
                 out.append(host[9:9 + host[2]])
         return out
+
+    # ---- beam search: frame-synchronous, <= max_symbols_per_frame labels per frame, hypotheses merged by sequence
+    @torch.no_grad()
+    def beam_search(self, mel_features: torch.Tensor, mel_feature_lens: torch.Tensor, beam_size: int = 4, max_length: int = 200,
+                    max_symbols_per_frame: int = 10, return_nbest: bool = False):
+        """Beam search over the whole encoder output (like greedy_decode, `mel_feature_lens` is not used).  Returns the best
+        entry's token list, or with `return_nbest` the final beam as [(tokens, log-probability), ...] best first.  beam_size 1 is
+        greedy_decode's result.  The search runs on the device (rnnt_engine_beam_decode: a fixed kernel sequence per round, one
+        synchronisation per utterance) where greedy_decode's device loop does — engine ConvPredictor, eval mode, fp32 HIP tensors,
+        sizes the kernels cover, beam_size <= 16 — else as a plain-torch host loop of the same search over any stateless
+        `predictor(ids)` and `joint.single_forward` (CPU too).  A stateful (LSTM) predictor raises NotImplementedError."""
+        assert mel_features.shape[0] == 1, "Beam search only works with a batch size of 1"
+        beam_size, max_length, m = int(beam_size), int(max_length), int(max_symbols_per_frame)
+        if beam_size < 1 or m < 1:
+            raise ValueError(f"beam_search: beam_size={beam_size} and max_symbols_per_frame={m} must be >= 1")
+        if self._predictor_is_stateful():
+            raise NotImplementedError("beam_search needs a stateless predictor (forward(ids), e.g. ConvPredictor); "
+                                      "stateful (LSTM) predictors are not supported")
+        audio = self.encoder(mel_features).permute(0, 2, 1)
+        if self._beam_device_ok(audio, beam_size, max_length):
+            nbest = self._beam_search_device(audio, beam_size, max_length, m)
+        else:
+            nbest = self._beam_search_host(audio, beam_size, max_length, m)
+        return nbest if return_nbest else list(nbest[0][0])
+
+    def _beam_device_ok(self, audio, beam_size, max_length) -> bool:
+        if not (1 <= beam_size <= 16 and max_length >= 2 and self._device_loop_ok(audio)):
+            return False
+        from . import engine
+        p = self.predictor
+        S, E = p.embedding.weight.shape
+        return engine.beam_decode_supported(S, E, p.linear.out_features, self.joint.joint_ln.in_features,
+                                            self.joint.joint_ln.out_features, hasattr(self.joint, "text_ln"), max_length, beam_size)
+
+    def _beam_search_device(self, audio, beam_size, max_length, m):
+        from . import engine
+        frames = audio[0]
+        if hasattr(self.joint, "audio_ln"):
+            frames = self.joint.audio_ln(frames)
+        frames = frames.float().contiguous()
+        tl = getattr(self.joint, "text_ln", None)
+        p = self.predictor
+        state, tokens, scores = engine.beam_decode(
+            frames, p._params(), (float(p.input_layer_norm.eps), float(p.output_layer_norm.eps)),
+            tl.weight if tl is not None else None, tl.bias if tl is not None else None,
+            self.joint.joint_ln.weight, self.joint.joint_ln.bias, self.joint.blank_idx, max_length, beam_size, max_per_frame=m)
+        st, toks, sc = state.tolist(), tokens.tolist(), scores.tolist()  # the utterance's one synchronisation
+        if not st[3]:
+            raise RuntimeError(f"rnnt_engine: the beam search did not finish (t={st[0]}, {st[5]} rounds)")
+        return [(toks[j][1:1 + st[8 + j]], sc[j]) for j in range(st[2])]
+
+    def _beam_search_host(self, audio, beam_size, max_length, m):
+        """The search of DESIGN.md §4h as a host loop: the predictor on the whole history of each new hypothesis (cached by
+        sequence), single_forward batched over the round's active hypotheses, scores as Python floats (double)."""
+        blank, dev = self.joint.blank_idx, self.device
+        feats = {}
+
+        def text(y):
+            if y not in feats:
+                ids = torch.tensor([[blank, *y]], dtype=torch.int64, device=dev)
+                feats[y] = self.predictor(ids)[0, -1]
+            return feats[y]
+
+        def lae(a, b):
+            hi, lo = max(a, b), min(a, b)
+            return hi if lo == -math.inf else hi + math.log1p(math.exp(lo - hi))
+
+        beam = [((), 0.0)]
+        for t in range(audio.shape[1]):
+            active, fin = beam, []  # fin: [[y, score]] in order of arrival
+            for r in range(m):
+                frame = audio[:, t, :].expand(len(active), -1)
+                lp = self.joint.single_forward(frame, torch.stack([text(y) for y, _ in active])).double().log_softmax(-1).cpu()
+                for i, (y, s) in enumerate(active):  # blank candidates join N, merged by sequence
+                    b = s + float(lp[i, blank])
+                    hit = next((e for e in fin if e[0] == y), None)
+                    if hit is not None:
+                        hit[1] = lae(hit[1], b)
+                    else:
+                        fin.append([y, b])
+                cands = [(s, 0, f, 0, y) for f, (y, s) in enumerate(fin)]
+                for i, (y, s) in enumerate(active):
+                    if len(y) >= max_length - 1:
+                        continue
+                    row = lp[i].clone()
+                    row[blank] = -math.inf
+                    vals, idx = torch.sort(row, descending=True, stable=True)  # lower id first among equal values
+                    for v, k in zip(vals[:beam_size].tolist(), idx[:beam_size].tolist()):
+                        if v != -math.inf:
+                            cands.append((s + v, 1, i, k, y + (k,)))
+                cands.sort(key=lambda c: (-c[0], c[1], c[2], c[3]))
+                kept = cands[:beam_size]
+                fin = [[c[4], c[0]] for c in kept if c[1] == 0]
+                active = [(c[4], c[0]) for c in kept if c[1] == 1]
+                if not active:
+                    break
+            # the cap: labels still active after round m-1 move on without a blank term, merged with N by sequence
+            for y, s in active:
+                hit = next((e for e in fin if e[0] == y), None)
+                if hit is not None:
+                    hit[1] = lae(hit[1], s)
+                else:
+                    fin.append([y, s])
+            order = sorted(range(len(fin)), key=lambda i: (-fin[i][1], i))
+            beam = [(fin[i][0], fin[i][1]) for i in order]
+        return [(list(y), s) for y, s in beam]
