@@ -9,11 +9,15 @@ batch (global batch fixed -> strong scaling) and one RCCL all-reduce of the flat
 
     python bench.py --gpus 1 --steps 5 --warmup 2
     python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full               # + everything the headline figure does not need
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
-"roofline" (dominant kernel vs the fp32 MFMA peak, timed live with HIP events on the launch
-stream) and "cpu_baseline" (the CPU port of the same path on this box's host cores).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the
+steps, dumps (--dump-outputs) and prints.  --full adds, after the timed steps: "stages_ms" and "roofline"
+(every stage and the dominant kernel vs the route's MFMA peak, timed live with HIP events on the launch
+stream), "exact_fp32" and "bf16x3" (the other fp32-bar routes timed on the same inputs), "parity" (a
+down-scaled twin against the fp64 oracle) and "cpu_baseline" (the CPU port of the same path on the host's
+cores); each of them can be left out with its --no-* option.
 """
 import argparse
 import json
@@ -242,12 +246,16 @@ def main():
     ap.add_argument("--permuted-enc", action="store_true",
                     help="hand `enc` over as the reference does: the permute(0,2,1) view of an (N,C,L) tensor "
                          "(rnnt/model.py:27-28); the engine's tiled transpose is then part of every step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stage-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: per-stage timing and the "
+                         "roofline, the exact-fp32 and bf16x3 routes, the parity twin and the CPU baseline (the --no-* options "
+                         "below leave parts of it out); without it the run only sets up, warms up, times, dumps and prints")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-stage-timing", action="store_true", help="--full without the per-stage timing and roofline")
     ap.add_argument("--no-exact-fp32", action="store_true",
-                    help="skip the secondary `exact_fp32` object (the exact-fp32 MFMA route timed in the same run)")
+                    help="--full without the secondary `exact_fp32` and `bf16x3` objects (the other routes timed in the same run)")
     ap.add_argument("--no-parity", action="store_true",
-                    help="skip the down-scaled parity twin of the CPU leg (it also goes with --no-cpu-baseline)")
+                    help="--full without the down-scaled parity twin of the CPU leg (it also goes with --no-cpu-baseline)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32): loss, "
                          "costs, grad_enc, grad_pred, grad_W, grad_bias (rank 0's shard of costs / grad_enc / grad_pred); at most "
@@ -368,7 +376,7 @@ def main():
     # ---- per-stage timing with HIP events on the launch stream (torch's current stream IS the
     # stream every kernel was enqueued on: engine._stream()).
     stage_ms = None
-    if not args.no_stage_timing:
+    if args.full and not args.no_stage_timing:
         names = ["producers_hidden_wpack", "joint_fwd_gemm", "lattice_sweep", "grad_coef_make_g",
                  "dhidden_gemm", "dhidden_reduce", "dw_gemm", "dw_reduce"]
         # as many repetitions per stage as timed steps (default 20): the three GEMM stages then keep the GPU busy
@@ -424,7 +432,7 @@ def main():
                 "timing": f"hipEventElapsedTime per step, median of {n}, same process and inputs as the headline"}
 
     exact_fp32 = route_bf16x3 = None
-    if world == 1 and args.dtype in ("f16x2", "bf16x3") and not args.no_exact_fp32:
+    if args.full and world == 1 and args.dtype in ("f16x2", "bf16x3") and not args.no_exact_fp32:
         exact_fp32 = time_route("fp32", "v_mfma_f32_32x32x2_f32 (exact fp32 products)", PEAK_F32_MFMA_TFLOPS)
         if args.dtype == "f16x2":
             route_bf16x3 = time_route("bf16x3", "6 x v_mfma_f32_32x32x16_bf16 per fp32 product (operands split hi+mid+lo)", PEAK_BF16_MFMA_TFLOPS / 6.0)
@@ -537,7 +545,7 @@ def main():
         out["exact_fp32"] = exact_fp32
     if route_bf16x3 is not None:
         out["bf16x3"] = route_bf16x3  # round 3's default route (six bf16 products of 3-way split operands) on the same inputs
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # the CPU leg (rank 0, N = 1 only; the one place bench.py touches oracle/): the oracle as checker of a
         # down-scaled twin of the workload, then the CPU port timed on this box's host cores
         if not args.no_parity:

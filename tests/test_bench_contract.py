@@ -228,3 +228,41 @@ def test_bench_dump_outputs_are_what_the_timed_step_computed(tmp_path):
         np.testing.assert_allclose(got, r, rtol=0, atol=1e-6 * np.abs(r).max(), err_msg=name)
     loss = float(np.load(d / "loss.npy"))
     assert abs(loss - float(ref[0].astype(np.float64).sum()) / B) <= 1e-5 * abs(loss)
+
+
+def _bench_line(*args):
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "small", "--steps", "3",
+                          "--warmup", "1"] + list(args), env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-1500:]
+    return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_full_run_carries_the_rest():
+    """A plain run prints the headline line only; --full on the same arguments adds the per-stage timing and roofline, the
+    other fp32-bar routes, the parity twin and the CPU baseline.  Both time the same steps on the same inputs: the headline
+    fields are there in both and the losses agree."""
+    import bench
+    B, T, U, H, V = bench.CONFIGS["small"]
+    plain = _bench_line()
+    full = _bench_line("--full")
+    extras = ("stages_ms", "roofline", "lattice_sweep", "exact_fp32", "bf16x3", "parity", "cpu_baseline", "gpu_over_cpu")
+    for k in extras:
+        assert k not in plain, k
+        assert k in full, k
+    for d in (plain, full):
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "loss"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "cells/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f32(f16x2)" and d["ms_per_step"] > 0
+        assert abs(d["value"] - B * T * U / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert abs(plain["loss"] - full["loss"]) <= 1e-6 * abs(full["loss"])
+    assert set(full["stages_ms"]) >= {"joint_fwd_gemm", "lattice_sweep", "dhidden_gemm", "dw_gemm"}
+    assert 0.0 < full["roofline"]["frac"] < 1.0
+    for route in ("exact_fp32", "bf16x3"):
+        assert abs(full[route]["loss"] - full["loss"]) <= 1e-4 * abs(full["loss"])
+    assert full["parity"]["loss_rel_err"] < 1e-4 and full["parity"]["grad_rel_err"] < 1e-4
+    assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["kind"] == "port"

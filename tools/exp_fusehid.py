@@ -9,7 +9,7 @@ if __name__ == "__main__":
     import bench
     for flags in (0, 64, 0, 64):
         engine.lib().rnnt_engine_set_flags(flags)
-        sys.argv = ["bench.py", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"]
+        sys.argv = ["bench.py", "--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"]
         t0 = time.time()
         bench.main()
         print("flags", flags, "wall", round(time.time() - t0, 1), flush=True)

@@ -3,7 +3,7 @@
 # usage: tools/profile_bf16.sh <tag> [pmc]
 TAG=${1:-bf}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-CMD="python3 bench.py --dtype bf16 --steps 5 --warmup 2 --no-cpu-baseline --no-parity"
+CMD="python3 bench.py --full --dtype bf16 --steps 5 --warmup 2 --no-cpu-baseline --no-parity"
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/$TAG/trace -- $CMD > gpurun_out/$TAG.trace.log 2>&1
 echo "trace rc=$?"
 grep '"metric"' gpurun_out/$TAG.trace.log | tail -1 > gpurun_out/$TAG.bench.json
