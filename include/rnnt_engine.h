@@ -331,6 +331,46 @@ int rnnt_engine_greedy_decode_persistent(const void *frames, int64_t frame_strid
                                          void *workspace, size_t ws_bytes, void *stream);
 
 /*
+ * Streaming greedy decode: the loop of rnnt_engine_greedy_decode carried from one chunk of audio frames (a "push") to
+ * the next.  For every way of cutting an utterance's frames into pushes, empty ones included, the labels of the pushes concatenated
+ * equal the decode of all frames at once with the same max_length.  The caller owns the stream's state, a device block of
+ * RNNT_STREAM_STATE_WORDS int32:
+ *   [RNNT_STREAM_FRAMES] frames consumed, [RNNT_STREAM_EMITTED] labels emitted at the current frame, [RNNT_STREAM_LABELS] labels so far,
+ *   [RNNT_STREAM_DONE] 1 once 1 + labels reached max_length (later pushes consume nothing),
+ *   [RNNT_STREAM_TOKENS + j] j < 7: the last 7 tokens, newest first, the leading blank included, -1 before the start,
+ *   [RNNT_STREAM_PUSH_LABELS] labels the last push emitted, [RNNT_STREAM_PUSH_ITERATIONS] its iterations that did work,
+ *   [RNNT_STREAM_STATUS] its status: 0, or a persistent push's state[7] code of rnnt_engine_greedy_decode_persistent (1..9 a hand-off
+ *   never arrived, 10 / 11 an audio frame / a text vector beyond +-30).  A push with a non-zero status changes only the three push
+ *   words: redo it from the same state with persistent = 0.
+ * rnnt_engine_greedy_stream_init writes the initial block ([blank, -1 x 6] as the tokens, zeros elsewhere) by a kernel.
+ * rnnt_engine_greedy_stream_decode enqueues one push of n >= 0 frames (rows frame_stride apart, unit element stride, audio_ln already
+ * applied; frame 0 is the push's first) and writes its labels to out_tokens[0 .. state[RNNT_STREAM_PUSH_LABELS]) — room for
+ * n * max_per_frame labels, or fewer when max_length leaves fewer.  max_length 0 = unbounded, else >= 2 (labels + 1 <= max_length).
+ * Model arguments as rnnt_engine_greedy_decode_persistent; `tables` as there.  persistent = 1: one k_dec_persist launch resumed from the
+ * block (RNNT_ERR_UNSUPPORTED where the persistent decode refuses the sizes or n + n * max_per_frame >= 2^20); 0: the kernel-per-layer
+ * loop, rings refilled from the last 7 tokens.  Both leave the same labels wherever the argmax is not a rounding-level tie.  The
+ * workspace query with persistent = 1 covers both paths.  Every argument is checked before anything is enqueued; the call only
+ * enqueues, the caller synchronises once per push.  The model's weights and tables must not change while a stream is open.
+ */
+#define RNNT_STREAM_STATE_WORDS 16
+#define RNNT_STREAM_FRAMES 0
+#define RNNT_STREAM_EMITTED 1
+#define RNNT_STREAM_LABELS 2
+#define RNNT_STREAM_DONE 3
+#define RNNT_STREAM_TOKENS 4
+#define RNNT_STREAM_PUSH_LABELS 11
+#define RNNT_STREAM_PUSH_ITERATIONS 12
+#define RNNT_STREAM_STATUS 13
+int rnnt_engine_greedy_stream_init(int32_t *state, int blank, void *stream);
+int rnnt_engine_greedy_stream_decode_workspace_bytes(int n, int S, int E, int O, int H, int V, int has_text, int max_length,
+                                                     int max_per_frame, int persistent, size_t *out);
+int rnnt_engine_greedy_stream_decode(const void *frames, int64_t frame_stride, int n, const rnnt_conv_predictor_params *p,
+                                     int S, int E, int O, float ln_in_eps, float ln_out_eps, const void *text_W, const void *text_b,
+                                     const void *W, const void *bias, int H, int V, int blank, int max_length, int max_per_frame,
+                                     const void *tables, int persistent, int32_t *state, int32_t *out_tokens, void *workspace,
+                                     size_t ws_bytes, void *stream);
+
+/*
  * Frame-synchronous beam search of ONE utterance on the device, with the stateless ConvPredictor of
  * rnnt/predictor.py:189-229 (eval mode) and the joint of rnnt/joint.py:44-55: at most `max_per_frame` labels per frame,
  * hypotheses merged by token sequence (logaddexp of their scores), output capped at max_length - 1 labels; beam 1 is the

@@ -9,5 +9,6 @@ from .functional import joint_rnnt_loss, rnnt_loss, joint_logits, linear  # noqa
 from .joint import JointNetwork  # noqa: F401
 from .predictor import ConvPredictor  # noqa: F401
 from .model import RNNTModel  # noqa: F401
+from .stream import GreedyStream  # noqa: F401
 
-__all__ = ["engine", "optim", "joint_rnnt_loss", "rnnt_loss", "joint_logits", "JointNetwork", "RNNTModel", "ConvPredictor"]
+__all__ = ["engine", "optim", "joint_rnnt_loss", "rnnt_loss", "joint_logits", "JointNetwork", "RNNTModel", "ConvPredictor", "GreedyStream"]

@@ -132,7 +132,7 @@ __global__ void k_dec_init(int32_t *state, int32_t *tokens, float *rings, int nr
     if (i < nring) rings[i] = 0.f;
     if (i == 0) {
         state[0] = 0; state[1] = 0; state[2] = 0; state[3] = 0; state[4] = 1; state[5] = 0; state[6] = 0; state[7] = 0;
-        tokens[0] = blank;
+        if (tokens) tokens[0] = blank;
     }
 }
 
@@ -329,7 +329,7 @@ __global__ __launch_bounds__(256) void k_dec_scan_logits(const int32_t *__restri
 //   hit = first frame of [t, t + n) whose argmax is not blank, n = min(K, T - t)
 //   none: t += n, emitted = 0                                  (an all-blank block)
 //   else: t = hit (emitted = 0 if hit > t), append the token, ++emitted; emitted == max_per_frame: ++t, emitted = 0
-//   done = t >= T or 1 + ntok >= max_length
+//   done = t >= T or 1 + ntok >= max_length     (max_length 0: state[8] holds it — a stream's push, whose cap depends on the labels so far)
 __global__ __launch_bounds__(128) void k_dec_update(const float2 *__restrict__ part, int K, int NB, int blank, int T, int max_length,
                                                     int max_per_frame, int32_t *__restrict__ state, int32_t *__restrict__ tokens,
                                                     int32_t *host_flag)
@@ -363,7 +363,8 @@ __global__ __launch_bounds__(128) void k_dec_update(const float2 *__restrict__ p
             if (++emitted >= max_per_frame) { ++t; emitted = 0; }
         }
         state[0] = t; state[1] = emitted; state[2] = ntok; state[4] = newtok;
-        const int done = (t >= T || ntok + 1 >= max_length) ? 1 : 0;
+        const int ml = max_length > 0 ? max_length : state[8];
+        const int done = (t >= T || ntok + 1 >= ml) ? 1 : 0;
         state[3] = done;
         state[5] += 1;  // iterations that did work (diagnostic)
         // the host's cue to stop enqueueing iterations (mapped pinned memory, polled without a synchronisation)
@@ -377,16 +378,33 @@ size_t dec_loop_workspace_floats(int H, int V, int E, int O, int nframes)
     return (size_t)4 * E + 8 * E + E + 2 * (size_t)O + H + (size_t)nframes * ((V + 31) / 32) * 2 + (size_t)8 * E * E + 64;
 }
 
-void launch_dec_loop(const DecLoopArgs &a, hipStream_t st)
+struct DecLoopBufs { float *x1ring, *g1ring, *g2, *z, *pvec, *wp1, *wp2; float2 *part; };
+static DecLoopBufs dec_loop_bufs(const DecLoopArgs &a)
 {
     float *ws = (float *)a.workspace;
     const int E = a.E, O = a.O, H = a.H, V = a.V, n = a.scan_frames;
-    float *x1ring = ws, *g1ring = x1ring + 4 * (size_t)E, *g2 = g1ring + 8 * (size_t)E, *z = g2 + E, *y = z + O, *pvec = y + O;
+    DecLoopBufs b;
+    b.x1ring = ws; b.g1ring = b.x1ring + 4 * (size_t)E; b.g2 = b.g1ring + 8 * (size_t)E; b.z = b.g2 + E;
+    float *y = b.z + O;
+    b.pvec = y + O;
     const int NB = (V + 31) / 32;
-    float2 *part = (float2 *)(pvec + ((H + 15) / 16) * 16);
-    float *wp1 = (float *)part + (((size_t)n * NB * 2 + 3) & ~(size_t)3), *wp2 = wp1 + (size_t)3 * E * E;  // 16-byte aligned whatever n * NB
+    b.part = (float2 *)(b.pvec + ((H + 15) / 16) * 16);
+    b.wp1 = (float *)b.part + (((size_t)n * NB * 2 + 3) & ~(size_t)3); b.wp2 = b.wp1 + (size_t)3 * E * E;  // 16-byte aligned whatever n * NB
+    return b;
+}
+
+void launch_dec_loop(const DecLoopArgs &a, hipStream_t st)
+{
+    const int E = a.E, O = a.O, H = a.H, V = a.V, n = a.scan_frames;
+    const DecLoopBufs b = dec_loop_bufs(a);
+    float *x1ring = b.x1ring, *g1ring = b.g1ring, *g2 = b.g2, *z = b.z, *pvec = b.pvec, *wp1 = b.wp1, *wp2 = b.wp2;
+    const int NB = (V + 31) / 32;
+    float2 *part = b.part;
     const int nring = 12 * E;
-    if (a.init) {
+    if (a.init == 2) {  // a stream's push: state and rings come from k_stream_loop_prep, the packs are made here
+        launch_pack_conv_w(a.p.conv1_w, wp1, E, E, 3, st);
+        launch_pack_conv_w(a.p.conv2_w, wp2, E, E, 5, st);
+    } else if (a.init) {
         hipLaunchKernelGGL(k_dec_init, dim3((nring + 255) / 256), dim3(256), 0, st, a.state, a.tokens, x1ring, nring, a.blank);
         launch_pack_conv_w(a.p.conv1_w, wp1, E, E, 3, st);  // [tap][out][in]
         launch_pack_conv_w(a.p.conv2_w, wp2, E, E, 5, st);
@@ -589,7 +607,22 @@ __global__ __launch_bounds__(256) void k_dec_persist(DecPersistArgs a)
     const int HW = H / 4, NCH = HW / 16;                                             // a wave's share of H, in MFMA chunks of 16
     const int i16 = lane & 15, kq = lane >> 4;
     const int fr = tid >> 4, vv = tid & 15;
-    for (int j = tid; j < 8 * E; j += 256) s_ring[j] = 0.f;
+    if (a.sstate) {  // a stream's push: g1 of positions 0, -1 .. -4 (0 = the newest token) from the last 7 tokens, zeros before the start
+        const int *hist = a.sstate + RNNT_STREAM_TOKENS;  // newest first, -1 before the start
+        for (int j = tid; j < 8 * E; j += 256) {
+            const int slot = j / E, e = j - slot * E, back = (8 - slot) & 7;
+            float v = 0.f;
+            if (back <= 4 && hist[back] >= 0) {  // k_dec_persist's own conv1 row below, for the token `back` places before the newest
+                const int h1 = hist[back + 1], h2 = hist[back + 2];
+                const int c0 = min(hist[back], a.S - 1), c1 = min(max(h1, 0), a.S - 1), c2 = min(max(h2, 0), a.S - 1);
+                const float a2 = a.A2[(long)c0 * 3 * E + e], a1 = h1 >= 0 ? a.A1[(long)c1 * 3 * E + e] : 0.f, a0 = h2 >= 0 ? a.A0[(long)c2 * 3 * E + e] : 0.f;
+                v = dec_gelu(((a.conv1_b[e] + a2) + a1) + a0);
+            }
+            s_ring[j] = v;
+        }
+    } else {
+        for (int j = tid; j < 8 * E; j += 256) s_ring[j] = 0.f;
+    }
     for (int j = tid; j < H; j += 256) {
         s_g[j] = a.has_text ? a.rvec[j] : a.gamma[j];
         s_b[j] = a.has_text ? a.cvec[j] : a.beta[j];
@@ -634,8 +667,45 @@ __global__ __launch_bounds__(256) void k_dec_persist(DecPersistArgs a)
     }
     __syncthreads();
 
+    // conv2's four older taps for the token after position p (g1[p-3 .. p], in this order): prA (KF > 0) / s_pre (KF = 0)
+    auto conv2_old_taps = [&](const int p) {
+        if constexpr (RES) {
+            float acc[2] = {0.f, 0.f};
+#pragma unroll
+            for (int tap = 0; tap < 4; ++tap)
+#pragma unroll
+                for (int ra = 0; ra < 2; ++ra) acc[ra] += dp_row_mul<KR>(wA[ra][tap], s_ring + ((p - 3 + tap) & 7) * E, E, lane);
+            dp_wave_sums<2>(acc);
+            prA[0] = acc[0]; prA[1] = acc[1];
+        } else {
+            for (int r = wave; r < rpA; r += 4) {
+                const int o = g * rpA + r;
+                if (o < E) {
+                    float acc = 0.f;
+#pragma unroll
+                    for (int tap = 0; tap < 4; ++tap) {
+                        f32x4 w[KR];
+                        dp_row_load<KR>(w, a.wp2 + ((long)tap * E + o) * E, E, lane, true);
+                        acc += dp_row_mul<KR>(w, s_ring + ((p - 3 + tap) & 7) * E, E, lane);
+                    }
+                    acc = dp_wave_sum(acc);
+                    if (lane == 0) s_pre[r] = acc;
+                }
+            }
+        }
+    };
+
     int t = 0, emitted = 0, ntok = 0, newtok = 1, done = 0;
     int tk0 = a.blank, tk1 = -1, tk2 = -1;  // tokens at positions p, p-1, p-2 (-1: before the start)
+    int maxlen = a.max_length;              // the loop ends once 1 + ntok reaches it
+    if (a.sstate) {  // a stream's push resumes: t and ntok count from 0 in this push, position 0 is the newest token so far
+        const int *ss = a.sstate;
+        emitted = ss[RNNT_STREAM_EMITTED];
+        tk0 = ss[RNNT_STREAM_TOKENS]; tk1 = ss[RNNT_STREAM_TOKENS + 1]; tk2 = ss[RNNT_STREAM_TOKENS + 2];
+        maxlen = a.max_length > 0 ? a.max_length - ss[RNNT_STREAM_LABELS] : 0x7fffffff;
+        if (ss[RNNT_STREAM_DONE]) done = 1;
+        conv2_old_taps(-1);  // what the uninterrupted loop accumulated while the newest token's predecessor was handed off
+    }
     int it = 0, code = 0;
     int fheld = -1;  // the frame whose exp(2 enc) fragments this lane holds
     f32x4 ef[16];
@@ -752,32 +822,7 @@ __global__ __launch_bounds__(256) void k_dec_persist(DecPersistArgs a)
             }
             DP_T(3);
             // ---- while hand-off 2 is in flight: the four old taps of the NEXT token's conv2 (its newest tap needs the token)
-            {
-                if constexpr (RES) {
-                    float acc[2] = {0.f, 0.f};
-#pragma unroll
-                    for (int tap = 0; tap < 4; ++tap)
-#pragma unroll
-                        for (int ra = 0; ra < 2; ++ra) acc[ra] += dp_row_mul<KR>(wA[ra][tap], s_ring + ((p - 3 + tap) & 7) * E, E, lane);
-                    dp_wave_sums<2>(acc);
-                    prA[0] = acc[0]; prA[1] = acc[1];
-                } else {
-                    for (int r = wave; r < rpA; r += 4) {
-                        const int o = g * rpA + r;
-                        if (o < E) {
-                            float acc = 0.f;
-#pragma unroll
-                            for (int tap = 0; tap < 4; ++tap) {
-                                f32x4 w[KR];
-                                dp_row_load<KR>(w, a.wp2 + ((long)tap * E + o) * E, E, lane, true);
-                                acc += dp_row_mul<KR>(w, s_ring + ((p - 3 + tap) & 7) * E, E, lane);
-                            }
-                            acc = dp_wave_sum(acc);
-                            if (lane == 0) s_pre[r] = acc;
-                        }
-                    }
-                }
-            }
+            conv2_old_taps(p);
             DP_T(4);
             // ---- the joint's text input and exp(2 text)
             if (!dp_sweep<256>(a.zg, H, (unsigned)it, s_y, tid)) s_fail = 1;
@@ -976,14 +1021,14 @@ __global__ __launch_bounds__(256) void k_dec_persist(DecPersistArgs a)
                 t += hit;
                 ++ntok;
                 if (g == 0 && tid == 0) {
-                    if (a.max_length <= DP_TOKS) s_toks[ntok] = tok;
-                    else a.tokens[ntok] = tok;
+                    if (a.lds_toks) s_toks[ntok] = tok;
+                    else a.tokens[a.tok0 + ntok - 1] = tok;
                 }
                 tk2 = tk1; tk1 = tk0; tk0 = tok;
                 newtok = 1;
                 if (++emitted >= a.max_per_frame) { ++t; emitted = 0; }
             }
-            done = (t >= T || ntok + 1 >= a.max_length) ? 1 : 0;
+            done = (t >= T || ntok + 1 >= maxlen) ? 1 : 0;
             __syncthreads();  // s_tok is rewritten by the next iteration
         }
         DP_T(9);
@@ -992,8 +1037,8 @@ __global__ __launch_bounds__(256) void k_dec_persist(DecPersistArgs a)
     if (g == 0 && tid == 0)
         for (int k = 0; k < 16; ++k) a.cg[2 * DP_FRAMES * 128 + k] = dpt[k];
 #endif
-    if (g == 0 && a.max_length <= DP_TOKS)
-        for (int j = 1 + tid; j <= ntok; j += 256) a.tokens[j] = s_toks[j];
+    if (g == 0 && a.lds_toks)
+        for (int j = 1 + tid; j <= ntok; j += 256) a.tokens[a.tok0 + j - 1] = s_toks[j];
     if (g == 0 && tid == 0) {
         a.state[0] = t; a.state[1] = emitted; a.state[2] = ntok; a.state[3] = done; a.state[4] = newtok; a.state[5] = it - 1; a.state[6] = G;
         if (a.host_flag) __hip_atomic_store(a.host_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1172,7 +1217,7 @@ int launch_dec_persist(const DecLoopArgs &a, hipStream_t st)
     if (const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return (int)e;
     // (the limit is raised BEFORE anything is enqueued: a refusal leaves the stream untouched)
     const int ngran = (int)(L.eenc - L.gran);
-    hipLaunchKernelGGL(k_dec_init, dim3((ngran + 255) / 256), dim3(256), 0, st, a.state, a.tokens, ws + L.gran, ngran, a.blank);
+    hipLaunchKernelGGL(k_dec_init, dim3((ngran + 255) / 256), dim3(256), 0, st, a.state, a.sstate ? nullptr : a.tokens, ws + L.gran, ngran, a.blank);
     hipLaunchKernelGGL(k_dp_exp_frames, dim3(512), dim3(256), 0, st, a.frames, a.frame_stride, T, H, ws + L.eenc, a.state);
     const float *tb = (const float *)a.tables;
     if (!tb) {
@@ -1192,8 +1237,150 @@ int launch_dec_persist(const DecLoopArgs &a, hipStream_t st)
     k.S = S; k.E = E; k.O = O; k.H = H; k.V = V; k.blank = a.blank; k.max_length = a.max_length; k.max_per_frame = a.max_per_frame;
     k.has_text = has_text; k.max_iters = a.max_length + T + 2;
     k.state = a.state; k.tokens = a.tokens; k.host_flag = a.host_flag;
+    k.sstate = a.sstate; k.tok0 = 1; k.lds_toks = a.max_length <= DP_TOKS;
+    if (a.sstate) {  // a stream's push: at most stream_cap labels, written from tokens[0]
+        k.max_iters = a.stream_cap + T + 2; k.tok0 = 0; k.lds_toks = a.stream_cap + 1 <= DP_TOKS;
+    }
     if (kf == 1) hipLaunchKernelGGL(k_dec_persist<1>, dim3(G), dim3(256), lds, st, k);
     else if (kf == 2) hipLaunchKernelGGL(k_dec_persist<2>, dim3(G), dim3(256), lds, st, k);
     else hipLaunchKernelGGL(k_dec_persist<0>, dim3(G), dim3(256), lds, st, k);
+    return (int)hipSuccess;
+}
+
+// ---------------------------------------------------------------------------------------
+// Streaming greedy decode (rnnt_engine_greedy_stream_decode).  The caller owns the canonical state block
+// (int32[RNNT_STREAM_STATE_WORDS], include/rnnt_engine.h); a push of n frames runs the loop above from it over the push's frames and
+// pauses at their end.  Only k_stream_commit writes the block, after the push's kernels, and only when the push decoded (code 0):
+// a persistent push that gave up or met an activation beyond +-30 leaves it as it was, so that the same push can be redone on
+// the kernel-per-layer loop.
+// ---------------------------------------------------------------------------------------
+__global__ void k_stream_init(int32_t *s, int blank)
+{
+    const int i = threadIdx.x;
+    if (i < RNNT_STREAM_STATE_WORDS)
+        s[i] = i == RNNT_STREAM_TOKENS ? blank : (i > RNNT_STREAM_TOKENS && i < RNNT_STREAM_TOKENS + 7) ? -1 : 0;
+}
+
+// is: the push's loop state (int32[10]: [0] frames consumed, [1] emitted, [2] ntok, [5] iterations, [7] code, [9] base), or NULL for an
+// empty push.  src: the loop path's token buffer (labels at src[base + 1 ..]), copied to out; NULL: the persistent path wrote out itself.
+__global__ __launch_bounds__(256) void k_stream_commit(int32_t *s, const int32_t *is, const int32_t *src, int32_t *out, int max_length)
+{
+    const int tid = threadIdx.x;
+    if (!is) {
+        if (tid == 0) { s[RNNT_STREAM_PUSH_LABELS] = 0; s[RNNT_STREAM_PUSH_ITERATIONS] = 0; s[RNNT_STREAM_STATUS] = 0; }
+        return;
+    }
+    const int code = is[7];
+    const int base = src ? is[9] : 0, count = is[2] - base;
+    if (code == 0 && src)
+        for (int j = tid; j < count; j += 256) out[j] = src[base + 1 + j];
+    if (tid != 0) return;
+    s[RNNT_STREAM_PUSH_ITERATIONS] = is[5];
+    s[RNNT_STREAM_STATUS] = code;
+    if (code != 0) { s[RNNT_STREAM_PUSH_LABELS] = 0; return; }  // not a decode: the stream's state stays as it was
+    int h[7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) h[k] = s[RNNT_STREAM_TOKENS + k];
+#pragma unroll
+    for (int k = 0; k < 7; ++k)  // newest first: the push's labels from its last, then the older ones
+        s[RNNT_STREAM_TOKENS + k] = k < count ? (src ? src[base + count - k] : out[count - 1 - k]) : h[k - count];
+    const int labels = s[RNNT_STREAM_LABELS] + count;
+    s[RNNT_STREAM_FRAMES] += is[0];
+    s[RNNT_STREAM_EMITTED] = is[1];
+    s[RNNT_STREAM_LABELS] = labels;
+    s[RNNT_STREAM_DONE] = (s[RNNT_STREAM_DONE] || (max_length > 0 && labels + 1 >= max_length)) ? 1 : 0;
+    s[RNNT_STREAM_PUSH_LABELS] = count;
+}
+
+// The kernel-per-layer loop resumes: its token buffer starts with the last k <= 7 tokens (oldest first; k < 7 only when the stream
+// holds fewer), position base = k - 1 is the newest, and the six replay records make k_dec_gemv<2> refill the LN'd-embedding and conv1
+// rings at positions 0 .. base - 1 (the first iteration computes position base itself).  conv2 at position base reads g1[base - 4 ..
+// base], conv1 at base - 4 reads x1[base - 6 ..]: with k = 7 every value the loop reads from here on is what an uninterrupted loop
+// holds; with k < 7 the local positions are the stream's own.  is[8]: the push's cap on 1 + ntok (k_dec_update, max_length = 0).
+__global__ void k_stream_loop_prep(const int32_t *s, int32_t *is, int32_t *recs, int32_t *ltok, float *rings, int nring, int n,
+                                   int max_length, int cap)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nring) rings[i] = 0.f;
+    if (i == 0) {
+        int k = 1;  // (the leading blank is always there)
+        while (k < 7 && s[RNNT_STREAM_TOKENS + k] >= 0) ++k;
+        for (int j = 0; j < k; ++j) ltok[j] = s[RNNT_STREAM_TOKENS + k - 1 - j];
+        const int base = k - 1, idle = (s[RNNT_STREAM_DONE] || n < 1) ? 1 : 0;
+        is[0] = 0; is[1] = s[RNNT_STREAM_EMITTED]; is[2] = base; is[3] = idle; is[4] = 1; is[5] = 0; is[6] = 0; is[7] = 0;
+        is[8] = max_length > 0 ? max_length - s[RNNT_STREAM_LABELS] + base : base + cap + 2;
+        is[9] = base;
+        for (int j = 0; j < 6; ++j) {
+            int32_t *r = recs + 8 * j;
+            r[0] = 0; r[1] = 0; r[2] = j; r[3] = (idle || j >= base) ? 1 : 0; r[4] = 1; r[5] = 0; r[6] = 0; r[7] = 0;
+        }
+    }
+}
+
+void launch_stream_init(int32_t *state, int blank, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_stream_init, dim3(1), dim3(64), 0, st, state, blank);
+}
+
+static int stream_scan_frames(int n) { return n < 1 ? 1 : (n < 32 ? n : 32); }
+
+struct DecStreamLayout { size_t is, recs, ltok, total; };  // bytes
+static DecStreamLayout dec_stream_layout(size_t main_bytes, int cap)
+{
+    DecStreamLayout L;
+    L.is = (main_bytes + 255) & ~(size_t)255;
+    L.recs = L.is + 64;
+    L.ltok = L.recs + 6 * 8 * 4;
+    L.total = L.ltok + ((size_t)cap + 8) * 4;
+    return L;
+}
+size_t dec_stream_workspace_bytes(int n, int S, int E, int O, int H, int V, int has_text, int cap, int persistent)
+{
+    size_t need = dec_stream_layout(dec_loop_workspace_floats(H, V, E, O, stream_scan_frames(n)) * 4, cap).total;
+    if (persistent) need = std::max(need, dec_stream_layout(dec_persist_workspace_floats(n < 1 ? 1 : n, S, E, O, H, V, has_text) * 4, cap).total);
+    return need;
+}
+
+// `a`: the model and the push's frames (T = n >= 0), a.max_length 0 = unbounded, a.stream_cap = the push's label cap, a.sstate = the
+// canonical state, a.tokens = the caller's label buffer, a.tables.  hipSuccess, or the error of raising the persistent kernel's LDS limit
+// (nothing enqueued then).
+int launch_dec_stream(const DecLoopArgs &a, int persistent, hipStream_t st)
+{
+    int32_t *sstate = const_cast<int32_t *>(a.sstate);
+    if (a.T < 1 || !a.frames) {
+        hipLaunchKernelGGL(k_stream_commit, dim3(1), dim3(256), 0, st, sstate, (const int32_t *)nullptr, (const int32_t *)nullptr, a.tokens, a.max_length);
+        return (int)hipSuccess;
+    }
+    const int has_text = a.text_W ? 1 : 0;
+    if (persistent) {
+        const DecStreamLayout L = dec_stream_layout(dec_persist_workspace_floats(a.T, a.S, a.E, a.O, a.H, a.V, has_text) * 4, a.stream_cap);
+        DecLoopArgs d = a;
+        d.state = (int32_t *)((char *)a.workspace + L.is);
+        d.host_flag = nullptr;
+        if (const int e = launch_dec_persist(d, st)) return e;
+        hipLaunchKernelGGL(k_stream_commit, dim3(1), dim3(256), 0, st, sstate, (const int32_t *)d.state, (const int32_t *)nullptr, a.tokens, a.max_length);
+        return (int)hipSuccess;
+    }
+    DecLoopArgs d = a;
+    d.scan_frames = stream_scan_frames(a.T);
+    const DecStreamLayout L = dec_stream_layout(dec_loop_workspace_floats(a.H, a.V, a.E, a.O, d.scan_frames) * 4, a.stream_cap);
+    char *ws = (char *)a.workspace;
+    int32_t *is = (int32_t *)(ws + L.is), *recs = (int32_t *)(ws + L.recs), *ltok = (int32_t *)(ws + L.ltok);
+    const DecLoopBufs b = dec_loop_bufs(d);
+    const int E = a.E, nring = 12 * E;
+    hipLaunchKernelGGL(k_stream_loop_prep, dim3((nring + 255) / 256), dim3(256), 0, st, (const int32_t *)sstate, is, recs, ltok, b.x1ring, nring,
+                       a.T, a.max_length, a.stream_cap);
+    d.state = is; d.tokens = ltok; d.host_flag = nullptr; d.max_length = 0;
+    d.init = 2; d.iterations = 0;
+    launch_dec_loop(d, st);  // the weight packs only
+    // the rings: positions 0 .. base - 1 through conv1 (k_dec_gemv<2>, as the loop's iteration runs it), nothing emitted
+    for (int j = 0; j < 6; ++j)
+        hipLaunchKernelGGL(k_dec_gemv<2>, dim3((E + 3) / 4), dim3(256), 0, st, (const int32_t *)(recs + 8 * j), (const int32_t *)ltok, (const float *)b.wp1,
+                           a.p.conv1_b, (const float *)b.x1ring, 3, 3, E, E, 1, a.p.embedding, a.p.ln_in_w, a.p.ln_in_b, a.ln_in_eps, a.S, b.g1ring, 1, 7,
+                           b.x1ring);
+    d.init = 0;
+    d.iterations = a.stream_cap + (a.T + d.scan_frames - 1) / d.scan_frames + 2;
+    launch_dec_loop(d, st);
+    hipLaunchKernelGGL(k_stream_commit, dim3(1), dim3(256), 0, st, sstate, (const int32_t *)is, (const int32_t *)ltok, a.tokens, a.max_length);
     return (int)hipSuccess;
 }

@@ -871,6 +871,78 @@ int rnnt_engine_greedy_decode_persistent(const void *frames, int64_t frame_strid
     return launch_status("rnnt_engine_greedy_decode_persistent");
 }
 
+int rnnt_engine_greedy_stream_init(int32_t *state, int blank, void *stream)
+{
+    if (!state) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument (state)");
+    if (((uintptr_t)state & 3) || blank < 0) return fail(RNNT_ERR_INVALID_ARG, "state must be 4-byte aligned, blank >= 0 (blank=%d)", blank);
+    launch_stream_init(state, blank, (hipStream_t)stream);
+    return launch_status("rnnt_engine_greedy_stream_init");
+}
+
+// the labels a push may emit: n * max_per_frame, fewer when max_length leaves fewer
+static long stream_cap(int n, int max_length, int max_per_frame)
+{
+    const long cap = (long)n * max_per_frame;
+    return max_length > 0 ? std::min(cap, (long)max_length - 1) : cap;
+}
+
+int rnnt_engine_greedy_stream_decode_workspace_bytes(int n, int S, int E, int O, int H, int V, int has_text, int max_length,
+                                                     int max_per_frame, int persistent, size_t *out)
+{
+    if (!out) return fail(RNNT_ERR_INVALID_ARG, "null size pointer");
+    if (n < 0 || S < 1 || max_per_frame < 1 || max_length < 0 || max_length == 1 || (persistent != 0 && persistent != 1))
+        return fail(RNNT_ERR_INVALID_ARG, "stream decode: n=%d S=%d max_length=%d max_per_frame=%d persistent=%d (n >= 0, S >= 1, "
+                    "max_length 0 or >= 2, max_per_frame >= 1, persistent 0 or 1)", n, S, max_length, max_per_frame, persistent);
+    if ((long)n * max_per_frame >= (1L << 30))
+        return fail(RNNT_ERR_UNSUPPORTED, "stream decode: n * max_per_frame must stay below 2^30 (n=%d, max_per_frame=%d)", n, max_per_frame);
+    if (!has_text && O != H) return fail(RNNT_ERR_INVALID_ARG, "without text_ln the predictor's output dim (%d) must equal H (%d)", O, H);
+    size_t loop_bytes;  // the kernel-per-layer loop's own checks (sizes)
+    if (int rc = rnnt_engine_greedy_decode_workspace_bytes(H, V, E, O, 32, &loop_bytes)) return rc;
+    const long cap = stream_cap(n, max_length, max_per_frame);
+    if (persistent) {
+        if (int rc = dec_persist_check(n < 1 ? 1 : n, S, E, O, H, V, has_text, 2)) return rc;
+        if ((long)n + cap + 2 >= (1L << 20)) return fail(RNNT_ERR_UNSUPPORTED, "persistent stream decode: n + labels per push must stay below 2^20");
+    }
+    *out = align_up(dec_stream_workspace_bytes(n, S, E, O, H, V, has_text ? 1 : 0, (int)cap, persistent));
+    return RNNT_OK;
+}
+
+int rnnt_engine_greedy_stream_decode(const void *frames, int64_t frame_stride, int n, const rnnt_conv_predictor_params *p,
+                                     int S, int E, int O, float ln_in_eps, float ln_out_eps, const void *text_W, const void *text_b,
+                                     const void *W, const void *bias, int H, int V, int blank, int max_length, int max_per_frame,
+                                     const void *tables, int persistent, int32_t *state, int32_t *out_tokens, void *workspace,
+                                     size_t ws_bytes, void *stream)
+{
+    size_t need;
+    if (int rc = rnnt_engine_greedy_stream_decode_workspace_bytes(n, S, E, O, H, V, text_W ? 1 : 0, max_length, max_per_frame, persistent, &need))
+        return rc;
+    if (!state || !out_tokens || (n > 0 && !frames)) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument (frames, state or out_tokens)");
+    if (((uintptr_t)state & 3) || ((uintptr_t)out_tokens & 3)) return fail(RNNT_ERR_INVALID_ARG, "state and out_tokens must be 4-byte aligned");
+    if (tables && ((uintptr_t)tables & 255)) return fail(RNNT_ERR_INVALID_ARG, "tables must be 256-byte aligned");
+    DecLoopArgs a;  // (an empty push has no frames: the checks look at W in their place)
+    if (int rc = dec_check_args(n > 0 ? frames : W, frame_stride, n > 0 ? n : 1, p, S, E, O, ln_in_eps, ln_out_eps, text_W, text_b, W, bias, H, V,
+                                blank, max_length > 0 ? max_length : 2, max_per_frame, nullptr, state, out_tokens, workspace, a))
+        return rc;
+    if (ws_bytes < need) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
+    if (persistent && n > 0) {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+            return fail(RNNT_ERR_LAUNCH, "cannot query the device's compute-unit count");
+        if (dec_persist_groups(V) > cus)
+            return fail(RNNT_ERR_UNSUPPORTED, "persistent stream decode needs %d compute units, the device has %d", dec_persist_groups(V), cus);
+    }
+    a.frames = n > 0 ? (const float *)frames : nullptr;
+    a.T = n;
+    a.max_length = max_length;
+    a.stream_cap = (int)stream_cap(n, max_length, max_per_frame);
+    a.sstate = state;
+    a.tables = tables;
+    if (const int e = launch_dec_stream(a, persistent, (hipStream_t)stream))
+        return fail(RNNT_ERR_LAUNCH, "persistent stream decode: cannot raise the kernel's dynamic LDS limit to %zu bytes: %s",
+                    dec_persist_lds_bytes(E), hipGetErrorString((hipError_t)e));
+    return launch_status("rnnt_engine_greedy_stream_decode");
+}
+
 int rnnt_engine_loss_fwd_bwd(const void *logits, const int32_t *targets, const int32_t *logit_lens,
                              const int32_t *target_lens, int B, int T, int U1, int V, int blank,
                              float clamp, int dtype, float *costs, void *grad_logits,

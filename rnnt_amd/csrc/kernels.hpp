@@ -214,6 +214,8 @@ struct DecLoopArgs {
     int32_t *state, *tokens;
     void *workspace;
     const void *tables = nullptr;  // launch_dec_persist: the model's tables (launch_dec_build_tables), or NULL: built in the workspace
+    const int32_t *sstate = nullptr;  // a stream's push (launch_dec_stream): the canonical state block, read; NULL: a whole utterance
+    int stream_cap = 0;               // a stream's push: labels it may emit at most (max_length then 0 = unbounded)
 };
 size_t dec_loop_workspace_floats(int H, int V, int E, int O, int nframes);
 void launch_dec_loop(const DecLoopArgs &a, hipStream_t st);
@@ -229,6 +231,8 @@ struct DecPersistArgs {
     const float *W, *bias;                           // joint_ln [V,H], [V]
     int S, E, O, H, V, blank, max_length, max_per_frame, has_text, max_iters;
     int32_t *state, *tokens, *host_flag;
+    const int32_t *sstate;                           // a stream's push: resume from this state block, else NULL
+    int tok0, lds_toks;                              // label i (1-based) goes to tokens[tok0 + i - 1]; collected in LDS first (<= DP_TOKS - 1 labels)
 };
 int dec_persist_groups(int V);
 const char *dec_persist_refusal(int T, int S, int E, int O, int H, int V, int has_text);  // NULL: supported
@@ -240,6 +244,10 @@ void launch_dec_build_tables(const rnnt_conv_predictor_params &p, int S, int E, 
                              float *tables, hipStream_t st);
 // offsets (floats) of the conv1 tap tables tab[s][tap][E] and of conv2's [tap][out][in] pack inside those tables
 void dec_tables_offsets(int S, int E, int O, int H, int has_text, size_t *tab, size_t *wp2);
+// streaming greedy decode (decode.hip): one push of a.T >= 0 frames from the state block a.sstate (rnnt_engine_greedy_stream_decode)
+void launch_stream_init(int32_t *state, int blank, hipStream_t st);
+size_t dec_stream_workspace_bytes(int n, int S, int E, int O, int H, int V, int has_text, int cap, int persistent);
+int launch_dec_stream(const DecLoopArgs &a, int persistent, hipStream_t st);  // hipSuccess, or the persistent kernel's LDS-limit error (nothing launched)
 
 // ---- beam.hip: frame-synchronous beam search of one utterance (rnnt_engine_beam_decode), kernel-per-step rounds
 struct BeamArgs {

@@ -73,6 +73,9 @@ SIGNATURES = {
     "rnnt_engine_greedy_decode_persistent": "pqipiiiffppppiiiiipppppzp",
     "rnnt_engine_greedy_decode_tables_bytes": "iiiiip",
     "rnnt_engine_greedy_decode_build_tables": "piiifppipzp",
+    "rnnt_engine_greedy_stream_init": "pip",
+    "rnnt_engine_greedy_stream_decode_workspace_bytes": "iiiiiiiiiip",
+    "rnnt_engine_greedy_stream_decode": "pqipiiiffppppiiiiipipppzp",
     "rnnt_engine_beam_decode_workspace_bytes": "iiiiiiiip",
     "rnnt_engine_beam_decode": "pqipiiiffppppiiiiiipiipppppzp",
     "rnnt_engine_grad_norm_workspace_bytes": "ipp",
@@ -116,6 +119,7 @@ EXPORTS = (
     "rnnt_engine_greedy_decode_workspace_bytes", "rnnt_engine_greedy_decode",
     "rnnt_engine_greedy_decode_persistent_workspace_bytes", "rnnt_engine_greedy_decode_persistent",
     "rnnt_engine_greedy_decode_tables_bytes", "rnnt_engine_greedy_decode_build_tables",
+    "rnnt_engine_greedy_stream_init", "rnnt_engine_greedy_stream_decode_workspace_bytes", "rnnt_engine_greedy_stream_decode",
     "rnnt_engine_beam_decode_workspace_bytes", "rnnt_engine_beam_decode",
     "rnnt_engine_joint_loss_fwd", "rnnt_engine_run_stages",
     "rnnt_engine_joint_bwd_workspace_bytes", "rnnt_engine_joint_bwd",
@@ -712,6 +716,63 @@ def greedy_decode_loop(frames, pred_params, ln_eps, text_W, text_b, W, bias, bla
             done += it
         state._keepalive = (flag, frames, params, W, bias, text_W, text_b)  # until the caller has synchronised
     return state, tokens
+
+
+# ---- streaming greedy decode (include/rnnt_engine.h RNNT_STREAM_*)
+STREAM_STATE_WORDS = 16
+STREAM_FRAMES, STREAM_EMITTED, STREAM_LABELS, STREAM_DONE, STREAM_TOKENS = 0, 1, 2, 3, 4
+STREAM_PUSH_LABELS, STREAM_PUSH_ITERATIONS, STREAM_STATUS = 11, 12, 13
+
+
+def greedy_stream_init(state, blank):
+    """Write the initial stream state into `state` (int32 device tensor of >= STREAM_STATE_WORDS entries) on the current stream."""
+    dev = _require_cuda(state)
+    _require_dtype(torch.int32, state=state)
+    if state.numel() < STREAM_STATE_WORDS or not state.is_contiguous():
+        raise RuntimeError(f"greedy_stream_init: a contiguous int32 block of {STREAM_STATE_WORDS} words expected")
+    with torch.cuda.device(dev):
+        _check(lib().rnnt_engine_greedy_stream_init(_p(state), int(blank), _stream(dev)))
+
+
+def greedy_stream_supported(n, S, E, O, H, V, has_text, max_length, max_per_frame):
+    """Whether a push of n frames can take the persistent launch (rnnt_engine_greedy_stream_decode with persistent = 1); no device work.
+    max_length 0 or None: unbounded."""
+    q = ctypes.c_size_t(0)
+    return lib().rnnt_engine_greedy_stream_decode_workspace_bytes(int(n), int(S), int(E), int(O), int(H), int(V), int(bool(has_text)),
+                                                                  int(max_length or 0), int(max_per_frame), 1, ctypes.byref(q)) == 0
+
+
+def greedy_stream_decode(frames, pred_params, ln_eps, text_W, text_b, W, bias, blank, max_length, max_per_frame, tables, persistent,
+                         state, out_tokens):
+    """Enqueue one push of a stream (C ABI rnnt_engine_greedy_stream_decode): `frames` [n, H] fp32 (audio_ln applied), `state` the
+    stream's int32 block (greedy_stream_init), `out_tokens` int32 with room for the push's labels (n * max_per_frame, or fewer when
+    max_length leaves fewer); max_length 0 / None = unbounded.  No synchronisation: afterwards state[STREAM_STATUS] == 0 means the push
+    decoded and out_tokens[:state[STREAM_PUSH_LABELS]] are its labels; non-zero (persistent only) means nothing changed — redo the push
+    with persistent=False."""
+    dev, frames, params, text_W, text_b, W, bias = _decode_inputs(frames, pred_params, text_W, text_b, W, bias)
+    _require_cuda(frames, state, out_tokens)
+    _require_dtype(torch.int32, state=state, out_tokens=out_tokens)
+    _require_contiguous(state=state, out_tokens=out_tokens)
+    n, H = frames.shape
+    V = W.shape[0]
+    S, E = params[0].shape
+    O = params[7].shape[0]
+    ml, m = int(max_length or 0), int(max_per_frame)
+    cap = n * m if ml == 0 else min(n * m, ml - 1)
+    if state.numel() < STREAM_STATE_WORDS or out_tokens.numel() < cap:
+        raise RuntimeError(f"greedy_stream_decode: state needs {STREAM_STATE_WORDS} words, out_tokens {cap} (got {state.numel()}, {out_tokens.numel()})")
+    with torch.cuda.device(dev):
+        q = ctypes.c_size_t(0)
+        _check(lib().rnnt_engine_greedy_stream_decode_workspace_bytes(n, S, E, O, H, V, 1 if text_W is not None else 0, ml, m,
+                                                                      1 if persistent else 0, ctypes.byref(q)))
+        ws = workspace(dev, q.value)
+        st = _PredParams(*[t.data_ptr() for t in params])
+        eps_in, eps_out = _eps_pair(ln_eps)
+        _check(lib().rnnt_engine_greedy_stream_decode(
+            _p(frames) if n > 0 else None, ctypes.c_int64(frames.stride(0)), n, ctypes.byref(st), S, E, O, ctypes.c_float(eps_in),
+            ctypes.c_float(eps_out), _p(text_W), _p(text_b), _p(W), _p(bias), H, V, int(blank), ml, m, _p(tables), 1 if persistent else 0,
+            _p(state), _p(out_tokens), _p(ws), ctypes.c_size_t(ws.numel()), _stream(dev)))
+        state._keepalive = (frames, params, W, bias, text_W, text_b, tables)  # until the caller has synchronised
 
 
 BEAM_MAX = 16  # rnnt_engine_beam_decode: 1 <= beam <= 16 (the slots are the M = 16 rows of every product)

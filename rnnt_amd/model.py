@@ -134,52 +134,17 @@ class RNNTModel(torch.nn.Module):
                 st, host = state.tolist(), None
             engine.check_decode_state(st)
             return host[9:9 + st[2]] if host is not None else toks[1:1 + st[2]].tolist()
-        tokens = [self.joint.blank_idx]
-        dev = self.device
+        from .stream import HostGreedyLoop  # (one host loop, resumable: GreedyStream's host path runs it too)
+        loop = HostGreedyLoop(self, max_length, max_symbols_per_frame=10, scan_frames=scan_frames)
+        loop.run(audio)
+        return loop.tokens[1:]
 
-        def run_predictor(ids, state=None):
-            ids_t = torch.tensor([ids], dtype=torch.int64, device=dev)
-            if stateful:
-                lens = torch.tensor([len(tokens)], dtype=torch.int64, device=dev)
-                feats, _, st = (self.predictor(ids_t, lens) if state is None
-                                else self.predictor(ids_t, lens, state))
-                return feats, st
-            return self.predictor(ids_t), None
-
-        feats, state = run_predictor(tokens)
-        T = audio.shape[1]
-        use_scan = scan_frames > 0 and audio.is_cuda
-        if use_scan:
-            frames = audio[0]  # [T,C] view of the encoder output; projected once for all frames
-            if hasattr(self.joint, "audio_ln"):
-                frames = self.joint.audio_ln(frames)
-            frames = frames.float()
-        t, emitted = 0, 0
-        while t < T and len(tokens) < max_length:
-            if emitted >= 10:  # reference: max_outputs_per_step reached -> next frame, whatever the token
-                t += 1
-                emitted = 0
-                continue
-            if use_scan:
-                n = min(scan_frames, T - t)
-                res = self.joint.greedy_scan(frames, feats[0, -1, :].float(), t, n)
-                t_hit, tok = res[:2].tolist()  # the one sync of this block
-                if t_hit > t:
-                    emitted = 0
-                t = t_hit
-                if tok == self.joint.blank_idx:  # every scanned frame said blank
-                    continue
-            else:
-                logits = self.joint.single_forward(audio[:, t, :], feats[:, -1, :])
-                tok = int(logits.argmax(dim=-1))
-                if tok == self.joint.blank_idx:
-                    t += 1
-                    emitted = 0
-                    continue
-            tokens.append(tok)
-            feats, state = run_predictor([tok], state) if stateful else run_predictor(tokens)
-            emitted += 1
-        return tokens[1:]
+    def greedy_stream(self, max_length=None, max_symbols_per_frame=10, persistent=None):
+        """A GreedyStream (rnnt_amd/stream.py): greedy decoding push by push — `push(mel_chunk)` through the encoder's
+        streaming_forward, or `push_encoded(audio_features)` — whose labels, concatenated, equal greedy_decode of all frames at once with
+        the same max_length (None: unbounded).  The device paths and their choice follow greedy_decode; `persistent` forces one."""
+        from .stream import GreedyStream
+        return GreedyStream(self, max_length=max_length, max_symbols_per_frame=max_symbols_per_frame, persistent=persistent)
 
     @torch.no_grad()
     def greedy_decode_many(self, mels, max_length: int = 200, concurrency=None):
