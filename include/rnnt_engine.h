@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define RNNT_ENGINE_VERSION 3
+#define RNNT_ENGINE_VERSION 4
 
 #define RNNT_DTYPE_F32 0 /* fp32 in, fp32 MFMA (v_mfma_f32_32x32x2_f32), fp32 out */
 /* BASELINE config 3 ("bf16"): pointers stay fp32 at this boundary (inputs, parameters, costs,
@@ -170,6 +170,33 @@ int rnnt_engine_joint_loss_fwd(const void *enc, const int64_t enc_strides[3], co
                                const int32_t *logit_lens, const int32_t *target_lens, int B, int T,
                                int U1, int H, int V, int blank, int dtype, float *costs,
                                void *workspace, size_t ws_bytes, void *stream);
+
+/*
+ * Forced alignment: the best path through the same lattice, with the same log-probs
+ * (lp_blank, lp_emit) as the loss, padded H / V of each route included.  For utterance b with
+ * T_b = logit_lens[b], U_b = target_lens[b], a path runs from (0,0) to (T_b-1, U_b): a label arc
+ * (t,u) -> (t,u+1) adds lp_emit(t,u) (the log-prob of targets[b,u]), a blank arc (t,u) -> (t+1,u)
+ * adds lp_blank(t,u), and the final blank out of (T_b-1, U_b) ends it.
+ *   scores [B] fp32 out: log-probability of the best path (accumulated in fp64);
+ *   frames [B, U1-1] int32 out: frames[b,u] = the frame at which label u is emitted (non-decreasing, in
+ *          [0, T_b-1]) for u < U_b, -1 for u >= U_b.
+ * Ties: where the two predecessors of a cell score exactly equal, the path takes the blank
+ * predecessor (t-1,u) — with all log-probs equal every label is emitted at frame 0.  A NaN log-prob
+ * on any cell the sweep reads makes scores[b] NaN and every frames[b,:] -1; other utterances are
+ * unaffected.  No state carries over between calls; the workspace needs no initialisation; results
+ * are bit-identical from run to run.  Neither entry needs more workspace than the loss entry of the
+ * same shape, so a caller's loss workspace serves both.
+ */
+/* best alignment on given logits [B,T,U1,V] fp32; workspace <= rnnt_engine_loss_workspace_bytes(B,T,U1,V,RNNT_DTYPE_F32) */
+int rnnt_engine_align(const void *logits, const int32_t *targets, const int32_t *logit_lens,
+                      const int32_t *target_lens, int B, int T, int U1, int V, int blank,
+                      float *scores, int32_t *frames, void *workspace, size_t ws_bytes, void *stream);
+/* fused joint + best alignment, every dtype of the fused entry; workspace <= rnnt_engine_workspace_bytes(...) */
+int rnnt_engine_joint_align(const void *enc, const int64_t enc_strides[3], const void *pred,
+                            const void *W, const void *bias, const int32_t *targets,
+                            const int32_t *logit_lens, const int32_t *target_lens, int B, int T,
+                            int U1, int H, int V, int blank, int dtype, float *scores,
+                            int32_t *frames, void *workspace, size_t ws_bytes, void *stream);
 
 /*
  * Backward of the UNFUSED joint: given d loss / d logits (any upstream gradient, [B,T,U1,V]

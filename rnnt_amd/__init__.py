@@ -5,10 +5,10 @@ rnnt.model.RNNTModel) over hand-written HIP kernels reached through a C ABI
 (include/rnnt_engine.h -> rnnt_amd/csrc/librnnt_engine.so, bound with ctypes).
 """
 from . import engine, optim  # noqa: F401
-from .functional import joint_rnnt_loss, rnnt_loss, joint_logits, linear  # noqa: F401
+from .functional import joint_rnnt_loss, rnnt_loss, joint_logits, linear, rnnt_align, joint_rnnt_align  # noqa: F401
 from .joint import JointNetwork  # noqa: F401
 from .predictor import ConvPredictor  # noqa: F401
 from .model import RNNTModel  # noqa: F401
 from .stream import GreedyStream  # noqa: F401
 
-__all__ = ["engine", "optim", "joint_rnnt_loss", "rnnt_loss", "joint_logits", "JointNetwork", "RNNTModel", "ConvPredictor", "GreedyStream"]
+__all__ = ["engine", "optim", "joint_rnnt_loss", "rnnt_loss", "joint_logits", "rnnt_align", "joint_rnnt_align", "JointNetwork", "RNNTModel", "ConvPredictor", "GreedyStream"]

@@ -1004,6 +1004,56 @@ int rnnt_engine_joint_loss_fwd(const void *enc, const int64_t enc_strides[3], co
                      nullptr, nullptr, workspace, ws_bytes, stream);
 }
 
+// ---- forced alignment: the loss's producers fill lp_blank / lp_emit, then the Viterbi sweep and the
+// backtrace of align.hip.  The backpointer words take the alpha_s region, which the alignment does not use for alpha.
+int rnnt_engine_align(const void *logits, const int32_t *targets, const int32_t *logit_lens,
+                      const int32_t *target_lens, int B, int T, int U1, int V, int blank,
+                      float *scores, int32_t *frames, void *workspace, size_t ws_bytes, void *stream)
+{
+    if (int rc = check_dims(B, T, U1, 4, V, RNNT_DTYPE_F32, false)) return rc;
+    if (!logits || !targets || !logit_lens || !target_lens || !scores || !frames || !workspace)
+        return fail(RNNT_ERR_INVALID_ARG, "null pointer argument");
+    if (blank < 0 || blank >= V) return fail(RNNT_ERR_INVALID_ARG, "blank=%d outside [0,%d)", blank, V);
+    if (!aligned16(logits) || ((uintptr_t)workspace & 255))
+        return fail(RNNT_ERR_INVALID_ARG, "pointers must be 16-byte aligned (workspace 256)");
+    size_t need;
+    rnnt_engine_loss_workspace_bytes(B, T, U1, V, RNNT_DTYPE_F32, &need);
+    if (ws_bytes < need) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
+    const int D = T + U1 - 1;
+    const size_t skew = (size_t)B * D * U1;
+    char *ws = (char *)workspace;  // the loss entry's layout: denom_s, lpb_s, lpe_s, alpha_s, ...
+    float *denom_s = (float *)ws; ws += align_up(skew * 4);
+    float *lpb_s = (float *)ws;   ws += align_up(skew * 4);
+    float *lpe_s = (float *)ws;   ws += align_up(skew * 4);
+    void *bp = ws;
+    hipStream_t st = (hipStream_t)stream;
+    launch_logsoftmax_gather((const float *)logits, targets, logit_lens, target_lens, denom_s, lpb_s,
+                             lpe_s, B, T, U1, V, D, blank, st);
+    launch_align(lpb_s, lpe_s, bp, logit_lens, target_lens, scores, frames, B, U1, D, st);
+    return launch_status("rnnt_engine_align");
+}
+
+int rnnt_engine_joint_align(const void *enc, const int64_t enc_strides[3], const void *pred,
+                            const void *W, const void *bias, const int32_t *targets,
+                            const int32_t *logit_lens, const int32_t *target_lens, int B, int T,
+                            int U1, int H, int V, int blank, int dtype, float *scores,
+                            int32_t *frames, void *workspace, size_t ws_bytes, void *stream)
+{
+    if (!scores || !frames) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument");
+    // operand producers + the joint-forward GEMM (log-softmax in its epilogue) of the loss; every
+    // argument is checked there before anything is enqueued
+    if (int rc = run_fused(ST_PROD | ST_FWD, 0, enc, enc_strides, pred, W, bias, targets, logit_lens,
+                           target_lens, B, T, U1, H, V, blank, -1.0f, 1.0f, dtype, scores, nullptr,
+                           nullptr, nullptr, nullptr, workspace, ws_bytes, stream))
+        return rc;
+    rnnt_engine_ws_layout L;
+    layout(B, T, U1, H, V, dtype, &L);
+    char *ws = (char *)workspace;
+    launch_align((const float *)(ws + L.lpb_s), (const float *)(ws + L.lpe_s), ws + L.alpha_s,
+                 logit_lens, target_lens, scores, frames, B, U1, L.D, (hipStream_t)stream);
+    return launch_status("rnnt_engine_joint_align");
+}
+
 int rnnt_engine_run_stages(int stage_mask, int variant, const void *enc, const int64_t enc_strides[3],
                            const void *pred, const void *W, const void *bias, const int32_t *targets,
                            const int32_t *logit_lens, const int32_t *target_lens, int B, int T, int U1,

@@ -28,6 +28,13 @@ void launch_coef(const double *alpha_s, const double *beta_s, const float *denom
 void launch_grad_logits(const float *logits, const CellCoef *coef, float *grad, long nrows,
                         int V, int blank, float clamp, hipStream_t st);
 
+// ---- align.hip: forced alignment on the lp arrays of either producer.  `bp`: the
+// backpointer words, B * D * ceil(U1/64) u64 (fits in the alpha_s region of both workspaces);
+// frames [B, U1-1] int32; scores [B].
+void launch_align(const float *lpb_s, const float *lpe_s, void *bp, const int32_t *logit_lens,
+                  const int32_t *target_lens, float *scores, int32_t *frames, int B, int U1, int D,
+                  hipStream_t st);
+
 // ---- joint_fwd.hip
 struct JointFwdArgs {
     const float *enc;   // [B,T,H], h-stride 1

@@ -63,6 +63,8 @@ SIGNATURES = {
     "rnnt_engine_loss_fwd_bwd": "ppppiiiiifipppzp",
     "rnnt_engine_joint_loss_fwd_bwd": "ppppppppiiiiiiffippppppzp",
     "rnnt_engine_joint_loss_fwd": "ppppppppiiiiiiippzp",
+    "rnnt_engine_align": "ppppiiiiipppzp",
+    "rnnt_engine_joint_align": "ppppppppiiiiiiipppzp",
     "rnnt_engine_joint_bwd_workspace_bytes": "iiiiiip",
     "rnnt_engine_joint_bwd": "pppppiiiiiipppppzp",
     "rnnt_engine_greedy_scan_workspace_bytes": "iiip",
@@ -129,6 +131,7 @@ EXPORTS = (
     "rnnt_engine_conv_predictor_bwd", "rnnt_engine_linear_fwd", "rnnt_engine_linear_bwd_workspace_bytes",
     "rnnt_engine_linear_bwd", "rnnt_engine_allreduce",
     "rnnt_engine_linear_x2_workspace_bytes", "rnnt_engine_linear_x2_fwd", "rnnt_engine_linear_x2_bwd",
+    "rnnt_engine_align", "rnnt_engine_joint_align",
 )
 
 # per-call kernel variants (include/rnnt_engine.h RNNT_VARIANT_*): bit-identical results
@@ -462,6 +465,52 @@ def joint_loss_fwd(enc, pred, W, bias, targets, logit_lens, target_lens, blank, 
             _p(target_lens), B, T, U1, H, V, int(blank), code, _p(costs), _p(ws),
             ctypes.c_size_t(ws.numel()), _stream(dev)))
     return costs
+
+
+def _frames_out(B, U1, dev):
+    """frames [B, U1-1] int32 and the buffer behind it (never empty: U1 == 1 still hands the ABI a valid pointer)."""
+    buf = torch.empty(max(B * (U1 - 1), 1), dtype=torch.int32, device=dev)
+    return buf[:B * (U1 - 1)].view(B, U1 - 1), buf
+
+
+def align(logits, targets, logit_lens, target_lens, blank):
+    """Best alignment on materialised logits [B,T,U1,V] (C ABI rnnt_engine_align): (scores [B] fp32, frames [B,U1-1] int32).
+    Workspace: the loss entry's (loss_fwd_bwd's buffer serves both)."""
+    dev = _require_cuda(logits, targets, logit_lens, target_lens)
+    _require_dtype(torch.float32, logits=logits)
+    _require_dtype(torch.int32, targets=targets, logit_lens=logit_lens, target_lens=target_lens)
+    _require_contiguous(logits=logits, targets=targets, logit_lens=logit_lens, target_lens=target_lens)
+    B, T, U1, V = logits.shape
+    targets = _nonempty(targets)
+    with torch.cuda.device(dev):
+        scores = torch.empty(B, dtype=torch.float32, device=dev)
+        frames, fbuf = _frames_out(B, U1, dev)
+        n = ctypes.c_size_t(0)
+        _check(lib().rnnt_engine_loss_workspace_bytes(B, T, U1, V, DTYPE_F32, ctypes.byref(n)))
+        ws = workspace(dev, n.value)
+        _check(lib().rnnt_engine_align(_p(logits), _p(targets), _p(logit_lens), _p(target_lens), B, T, U1, V, int(blank),
+                                       _p(scores), _p(fbuf), _p(ws), ctypes.c_size_t(ws.numel()), _stream(dev)))
+    return scores, frames
+
+
+def joint_align(enc, pred, W, bias, targets, logit_lens, target_lens, blank, *, dtype):
+    """Fused joint + best alignment (C ABI rnnt_engine_joint_align): the joint-forward GEMM of the loss, then the Viterbi sweep
+    and the backtrace.  (scores [B] fp32, frames [B,U1-1] int32); workspace: the fused loss entry's."""
+    dev = _check_fused_inputs(enc, pred, W, bias, targets, logit_lens, target_lens)
+    B, T, H = enc.shape
+    U1 = pred.shape[1]
+    V = W.shape[0]
+    targets = _nonempty(targets)
+    code = dtype_code(dtype)
+    with torch.cuda.device(dev):
+        scores = torch.empty(B, dtype=torch.float32, device=dev)
+        frames, fbuf = _frames_out(B, U1, dev)
+        ws = workspace(dev, workspace_bytes(B, T, U1, H, V, code))
+        _check(lib().rnnt_engine_joint_align(
+            _p(enc), _strides3(enc), _p(pred), _p(W), _p(bias), _p(targets), _p(logit_lens),
+            _p(target_lens), B, T, U1, H, V, int(blank), code, _p(scores), _p(fbuf), _p(ws),
+            ctypes.c_size_t(ws.numel()), _stream(dev)))
+    return scores, frames
 
 
 def _rows(x):

@@ -5,6 +5,9 @@
   joint_logits(...)     the T x U joint expansion of reference rnnt/joint.py:32-39.
   joint_rnnt_loss(...)  the fused hot path: joint + loss, forward and backward in ONE engine
                         call; the (B,T,U+1,V) logits never leave the engine's workspace.
+  rnnt_align(...), joint_rnnt_align(...)
+                        forced alignment on the same lattice: the best path's
+                        log-probability and the frame of every label; no autograd.
 Every operator runs on the HIP engine; CPU tensors are rejected (no fallback).
 """
 import torch
@@ -231,3 +234,49 @@ def joint_rnnt_loss(enc, pred, W, bias, targets, logit_lengths, target_lengths, 
     loss, costs = _JointRNNTLoss.apply(enc_p, pred_p, W_p, bias_p, targets, logit_lengths,
                                        target_lengths, blank, scale, code, need_grad)
     return (loss, costs) if return_costs else loss
+
+
+def _align_checks(T, U1, V, B, targets, logit_lengths, target_lengths, blank, check_lengths):
+    return _check_loss_args(T, U1, V, B, targets, logit_lengths, target_lengths, blank, "mean", check_lengths)
+
+
+def rnnt_align(logits, targets, logit_lengths, target_lengths, blank=-1, check_lengths=True):
+    """Forced alignment on materialised logits [B,T,U+1,V]: the best path through the lattice rnnt_loss sums
+    over.  Returns (scores [B] float32: the best path's log-probability, frames [B,U] int32: the frame at which label u is
+    emitted, -1 for u >= target_lengths[b]).  Same argument checks and errors as rnnt_loss; no autograd; enqueues only
+    (apart from the check_lengths host checks)."""
+    if logits.dim() != 4:
+        raise RuntimeError("logits must have 4 dimensions")
+    if logits.dtype != torch.float32:
+        raise RuntimeError("logits must be float32 type")
+    if not logits.is_contiguous():
+        raise RuntimeError("logits must be contiguous")
+    B, T, U1, V = logits.shape
+    blank = _align_checks(T, U1, V, B, targets, logit_lengths, target_lengths, blank, check_lengths)
+    logits = logits.detach()
+    if V % 4 != 0:
+        logits = torch.nn.functional.pad(logits, (0, 4 - V % 4), value=_PAD_NEG)
+    return engine.align(logits, targets, logit_lengths, target_lengths, blank)
+
+
+def joint_rnnt_align(enc, pred, W, bias, targets, logit_lengths, target_lengths, blank=-1,
+                     dtype=engine.DEFAULT_DTYPE, check_lengths=True):
+    """Forced alignment of the fused path: the joint GEMM of joint_rnnt_loss on the same route, with H and V
+    padded exactly as there, then the best path through the lattice.  Returns (scores [B] float32, frames [B,U] int32) as
+    rnnt_align does; the (B,T,U+1,V) logits never leave the engine's workspace.  No autograd."""
+    if enc.dim() != 3 or pred.dim() != 3:
+        raise RuntimeError("enc and pred must have 3 dimensions")
+    if any(t.dtype != torch.float32 for t in (enc, pred, W, bias)):
+        raise RuntimeError("enc, pred, W and bias must be float32 type")
+    B, T, _ = enc.shape
+    U1 = pred.shape[1]
+    V = W.shape[0]
+    if pred.shape[0] != B or pred.shape[2] != enc.shape[2] or W.shape[1] != enc.shape[2]:
+        raise RuntimeError("enc / pred / W shape mismatch")
+    blank = _align_checks(T, U1, V, B, targets, logit_lengths, target_lengths, blank, check_lengths)
+    code = engine.dtype_code(dtype)
+    enc, pred, W, bias = enc.detach(), pred.detach(), W.detach(), bias.detach()
+    if code != engine.DTYPE_BF16:  # bf16: no host-side padding, the C side validates (as joint_rnnt_loss)
+        enc, pred, W, bias, _, _ = _pad_hv(enc, pred, W, bias, 128 if code in (engine.DTYPE_F32_BF16X3, engine.DTYPE_F32_F16X2) else 4)
+    return engine.joint_align(enc, pred.contiguous(), W.contiguous(), bias.contiguous(), targets, logit_lengths,
+                              target_lengths, blank, dtype=code)

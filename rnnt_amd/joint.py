@@ -73,6 +73,14 @@ class JointNetwork(torch.nn.Module):
                                      self.joint_ln.bias, targets, logit_lengths, target_lengths,
                                      blank=blank, reduction=reduction, **kw)
 
+    def align(self, audio_frame, text_frame, targets, logit_lengths, target_lengths, blank=-1, **kw):
+        """Forced alignment of the fused path: the inputs of fused_loss (audio_ln / text_ln applied the same way,
+        compute_dtype unless `dtype` is given) -> (scores [N] float32, frames [N,U] int32)."""
+        kw.setdefault("dtype", self.compute_dtype)
+        audio_frame, text_frame = self._project(audio_frame, text_frame)
+        return F_amd.joint_rnnt_align(audio_frame, text_frame, self.joint_ln.weight, self.joint_ln.bias, targets,
+                                      logit_lengths, target_lengths, blank=blank, **kw)
+
     def greedy_scan(self, audio_frames, text_frame, t0, nframes):
         """Decode helper (reference rnnt/model.py:108-125): argmax of single_forward for frames
         t0 .. t0+nframes-1 of `audio_frames` [T,H] (ALREADY projected by audio_ln) against one

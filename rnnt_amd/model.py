@@ -43,6 +43,22 @@ class RNNTModel(torch.nn.Module):
                                      target_lengths=input_id_lens.int(),
                                      blank=-1, reduction="mean", check_lengths=self.check_lengths)
 
+    # ---- forced alignment
+    @torch.no_grad()
+    def align(self, mel_features: torch.Tensor, mel_feature_lens: torch.Tensor, input_ids: torch.Tensor,
+              input_id_lens: torch.Tensor, blank_idx: int):
+        """The best alignment of each transcript against its audio, inputs prepared exactly as `forward` prepares them.
+        Returns (scores [N] float32: the best path's log-probability, frames [N,U] int32: the ENCODER frame at which each
+        label is emitted, -1 past input_id_lens[n]).  Seconds: frame * the encoder's stride (calc_output_lens) * the
+        featurizer's hop."""
+        start = torch.full((input_ids.shape[0], 1), blank_idx, dtype=input_ids.dtype, device=self.device)
+        decoder_features = self.predictor(torch.cat([start, input_ids], dim=1))
+        audio_features = self.encoder(mel_features).permute(0, 2, 1)
+        audio_feature_lens = self.encoder.calc_output_lens(mel_feature_lens)
+        return self.joint.align(audio_features, decoder_features, targets=input_ids.int(),
+                                logit_lengths=audio_feature_lens.int(), target_lengths=input_id_lens.int(),
+                                blank=-1, check_lengths=self.check_lengths)
+
     # ---- greedy decode (reference model.py:45-139); host loop, not on the engine's path
     def _predictor_is_stateful(self) -> bool:
         # forward(ids, lengths[, state]) (the reference's LSTMPredictor) against forward(ids) (its ConvPredictor); optional
