@@ -172,6 +172,42 @@ int rnnt_engine_joint_loss_fwd(const void *enc, const int64_t enc_strides[3], co
                                void *workspace, size_t ws_bytes, void *stream);
 
 /*
+ * Latency regularisers: the three loss entries above with FastEmit's lambda and
+ * the delay penalty delta added; same workspace as their counterparts.  Both must be finite and
+ * >= 0 (else RNNT_ERR_INVALID_ARG before anything is enqueued); at lambda = delta = 0 each launches
+ * exactly its counterpart's kernels.  Per utterance, T_b / U_b clamped as everywhere:
+ *   delay penalty: the lattice runs on lp_emit'(t,u) = lp_emit(t,u) + delta ((T_b - 1) / 2 - t)
+ *                  (k2's definition); costs[b] = -log P'_b of that lattice, gradients its exact ones.
+ *   FastEmit:      d/d logits gains lambda E(t,u) (p_k - [k = y_{u+1}]) for u < U_b, with
+ *                  E = exp(alpha + lp_emit' + beta(t,u+1) - log P'_b) the label arc's occupancy (as
+ *                  NeMo's warp-transducer kernel).  The reported cost does NOT change with lambda:
+ *                  FastEmit is defined by its gradient, so costs stay comparable across lambda.
+ * `clamp` (loss entry) applies to the final, regularised gradient.  The stage runner
+ * (rnnt_engine_run_stage(s)) never applies either option.
+ */
+int rnnt_engine_loss_fwd_bwd_reg(const void *logits, const int32_t *targets,
+                                 const int32_t *logit_lens, const int32_t *target_lens, int B,
+                                 int T, int U1, int V, int blank, float clamp,
+                                 float fastemit_lambda, float delay_penalty, int dtype,
+                                 float *costs, void *grad_logits, void *workspace,
+                                 size_t ws_bytes, void *stream);
+int rnnt_engine_joint_loss_fwd_bwd_reg(const void *enc, const int64_t enc_strides[3],
+                                       const void *pred, const void *W, const void *bias,
+                                       const int32_t *targets, const int32_t *logit_lens,
+                                       const int32_t *target_lens, int B, int T, int U1, int H,
+                                       int V, int blank, float clamp, float grad_scale,
+                                       float fastemit_lambda, float delay_penalty, int dtype,
+                                       float *costs, void *grad_enc, void *grad_pred,
+                                       void *grad_W, void *grad_bias, void *workspace,
+                                       size_t ws_bytes, void *stream);
+int rnnt_engine_joint_loss_fwd_reg(const void *enc, const int64_t enc_strides[3], const void *pred,
+                                   const void *W, const void *bias, const int32_t *targets,
+                                   const int32_t *logit_lens, const int32_t *target_lens, int B,
+                                   int T, int U1, int H, int V, int blank, float delay_penalty,
+                                   int dtype, float *costs, void *workspace, size_t ws_bytes,
+                                   void *stream);
+
+/*
  * Forced alignment: the best path through the same lattice, with the same log-probs
  * (lp_blank, lp_emit) as the loss, padded H / V of each route included.  For utterance b with
  * T_b = logit_lens[b], U_b = target_lens[b], a path runs from (0,0) to (T_b-1, U_b): a label arc

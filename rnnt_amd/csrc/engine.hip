@@ -4,6 +4,7 @@
 // caller's stream.  No allocation, no synchronisation, no state kept between calls.
 #include "../../include/rnnt_engine.h"
 
+#include <cfloat>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -62,6 +63,16 @@ int check_dims(int B, int T, int U1, int H, int V, int dtype, bool need_h)
     if (need_h && H % 4 != 0) return fail(RNNT_ERR_UNSUPPORTED, "H=%d must be a multiple of 4 (pad on the host side)", H);
     if (U1 > 1024) return fail(RNNT_ERR_UNSUPPORTED, "U1=%d exceeds 1024 lattice columns", U1);
     if ((long)T * U1 > 0x7fffffffL / 2) return fail(RNNT_ERR_UNSUPPORTED, "T*U1 too large");
+    return RNNT_OK;
+}
+
+// FastEmit lambda / delay penalty delta of the *_reg entries: finite and >= 0, checked before anything else
+int check_reg(float fastemit_lambda, float delay_penalty)
+{
+    if (!(fastemit_lambda >= 0.f && fastemit_lambda <= FLT_MAX))
+        return fail(RNNT_ERR_INVALID_ARG, "fastemit_lambda=%g must be finite and >= 0", (double)fastemit_lambda);
+    if (!(delay_penalty >= 0.f && delay_penalty <= FLT_MAX))
+        return fail(RNNT_ERR_INVALID_ARG, "delay_penalty=%g must be finite and >= 0", (double)delay_penalty);
     return RNNT_OK;
 }
 
@@ -225,9 +236,9 @@ enum { ST_PROD = 1, ST_FWD = 2, ST_LATTICE = 4, ST_COEF = 8, ST_DH = 16, ST_DH_R
 int run_fused(int stages, int variant, const void *enc, const int64_t enc_strides[3], const void *pred,
               const void *W, const void *bias, const int32_t *targets, const int32_t *logit_lens,
               const int32_t *target_lens, int B, int T, int U1, int H, int V, int blank,
-              float clamp, float grad_scale, int dtype, float *costs, void *grad_enc,
-              void *grad_pred, void *grad_W, void *grad_bias, void *workspace, size_t ws_bytes,
-              void *stream)
+              float clamp, float grad_scale, float fastemit, float delay, int dtype, float *costs,
+              void *grad_enc, void *grad_pred, void *grad_W, void *grad_bias, void *workspace,
+              size_t ws_bytes, void *stream)
 {
     if (int rc = check_dims(B, T, U1, H, V, dtype, true)) return rc;
     if (!enc || !enc_strides || !pred || !W || !bias || !targets || !logit_lens || !target_lens ||
@@ -271,6 +282,25 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
 
     const float *encp; long esb, est;
     resolve_enc(enc, enc_strides, B, T, H, (float *)(ws + L.enc_copy), st, &encp, &esb, &est);
+    // lattice sweep and coefficients (every route): the delay penalty goes on lp_emit before the sweep and its cost
+    // shift comes off after it, FastEmit's coefficients replace k_coef's; zero options launch exactly
+    // the plain loss's kernels
+    auto loss_stages = [&]() {
+        if (stages & ST_LATTICE) {
+            if (delay > 0.f) launch_delay_penalty(lpe_s, logit_lens, target_lens, B, T, U1, L.D, delay, st);
+            launch_lattice(lpb_s, lpe_s, alpha_s, beta_s, logit_lens, target_lens, costs, B, U1, L.D,
+                           (unsigned *)(ws + L.counters + 768), st);
+            if (delay > 0.f) launch_delay_cost(beta_s, logit_lens, target_lens, costs, B, T, U1, L.D, delay, st);
+        }
+        if (stages & ST_COEF) {
+            if (fastemit > 0.f)
+                launch_coef_fastemit(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef,
+                                     B, T, U1, L.D, grad_scale, fastemit, st);
+            else
+                launch_coef(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef,
+                            B, T, U1, L.D, grad_scale, st);
+        }
+    };
 
     JointBwdArgs g;
     g.enc = encp; g.enc_sb = esb; g.enc_st = est; g.pred = (const float *)pred;
@@ -295,9 +325,11 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
         h.rows_pad = (long)L.rows_pad; h.rows_alloc = bf16_rows_alloc(L.rows_pad);
         h.hidden = (unsigned short *)(ws + L.hidden); h.plane_stride = h.rows_alloc * (long)H;
         h.wpack_fwd = ws + L.wpack; h.wpack_dh = ws + L.wpack + align_up(x2 ? x2_wpack_fwd_bytes(H, V) : x3_wpack_fwd_bytes(H, V));
-        {   // f16x2 operand scales: |G| <= grad_scale <= 2^e -> g_scale = 2^(13 - e); hidden: 2^14 (x2.hip)
+        {   // f16x2 operand scales: |G| <= (1 + fastemit) grad_scale <= 2^e -> g_scale = 2^(13 - e); hidden: 2^14 (x2.hip).
+            // (FastEmit adds lambda E (p_k - [k = y]) with E <= 1 to a cell's G: DESIGN.md §4k; the bound of the f32_dh
+            // fallback's split of G is the same g_scale)
             int e = 0;
-            (void)frexpf(grad_scale, &e);
+            (void)frexpf(grad_scale * (1.0f + fastemit), &e);
             const int k = 13 - e < -100 ? -100 : (13 - e > 100 ? 100 : 13 - e);
             h.g_scale = ldexpf(1.0f, k);
             h.dw_rescale = 1.0f / (h.g_scale * 16384.0f); h.db_rescale = 1.0f / h.g_scale;
@@ -367,12 +399,7 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
                 launch_joint_fwd_x3(h, st);
             }
         }
-        if (stages & ST_LATTICE)
-            launch_lattice(lpb_s, lpe_s, alpha_s, beta_s, logit_lens, target_lens, costs, B, U1, L.D,
-                           (unsigned *)(ws + L.counters + 768), st);
-        if (stages & ST_COEF)
-            launch_coef(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef,
-                        B, T, U1, L.D, grad_scale, st);
+        loss_stages();
         if (stages & ST_DH) {
             if (x2) launch_x2_zero_padding(h, 2, st);
             else launch_x3_zero_padding(h, 2, st);
@@ -417,12 +444,7 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
         h.debug = g_debug;
         if (stages & ST_PROD) launch_bf16_producers(h, st);
         if (stages & ST_FWD) launch_joint_fwd_bf16(h, st);  // softmax statistics in its epilogue
-        if (stages & ST_LATTICE)
-            launch_lattice(lpb_s, lpe_s, alpha_s, beta_s, logit_lens, target_lens, costs, B, U1, L.D,
-                           (unsigned *)(ws + L.counters + 768), st);
-        if (stages & ST_COEF)
-            launch_coef(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef,
-                        B, T, U1, L.D, grad_scale, st);
+        loss_stages();
         if (stages & ST_DH) launch_dhidden_bf16(h, st);
         if (stages & ST_DH_RED) launch_dhidden_reduce(g, st);
         if (stages & ST_DW) launch_dw_bf16(h, st);
@@ -458,12 +480,7 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
         f.counter = (unsigned *)(ws + L.counters + 512); f.n_cu = device_cus();
         launch_joint_fwd(f, st);
     }
-    if (stages & ST_LATTICE)
-        launch_lattice(lpb_s, lpe_s, alpha_s, beta_s, logit_lens, target_lens, costs, B, U1, L.D,
-                           (unsigned *)(ws + L.counters + 768), st);
-    if (stages & ST_COEF)
-        launch_coef(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef,
-                    B, T, U1, L.D, grad_scale, st);
+    loss_stages();
     {
         if ((stages & ST_COEF) && !fuse_g) launch_make_g(g, st);  // logits -> G in place
         if (stages & ST_DH) launch_dhidden(g, st);
@@ -943,10 +960,10 @@ int rnnt_engine_greedy_stream_decode(const void *frames, int64_t frame_stride, i
     return launch_status("rnnt_engine_greedy_stream_decode");
 }
 
-int rnnt_engine_loss_fwd_bwd(const void *logits, const int32_t *targets, const int32_t *logit_lens,
-                             const int32_t *target_lens, int B, int T, int U1, int V, int blank,
-                             float clamp, int dtype, float *costs, void *grad_logits,
-                             void *workspace, size_t ws_bytes, void *stream)
+static int loss_fwd_bwd(const void *logits, const int32_t *targets, const int32_t *logit_lens,
+                        const int32_t *target_lens, int B, int T, int U1, int V, int blank, float clamp,
+                        float fastemit, float delay, int dtype, float *costs, void *grad_logits,
+                        void *workspace, size_t ws_bytes, void *stream)
 {
     if (int rc = check_dims(B, T, U1, 4, V, dtype, false)) return rc;
     if (!logits || !targets || !logit_lens || !target_lens || !costs || !workspace)
@@ -970,14 +987,68 @@ int rnnt_engine_loss_fwd_bwd(const void *logits, const int32_t *targets, const i
     hipStream_t st = (hipStream_t)stream;
     launch_logsoftmax_gather((const float *)logits, targets, logit_lens, target_lens, denom_s, lpb_s,
                              lpe_s, B, T, U1, V, D, blank, st);
+    if (delay > 0.f) launch_delay_penalty(lpe_s, logit_lens, target_lens, B, T, U1, D, delay, st);
     launch_lattice(lpb_s, lpe_s, alpha_s, beta_s, logit_lens, target_lens, costs, B, U1, D, err, st);
+    if (delay > 0.f) launch_delay_cost(beta_s, logit_lens, target_lens, costs, B, T, U1, D, delay, st);
     if (grad_logits) {
-        launch_coef(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef,
-                    B, T, U1, D, 1.0f, st);
+        if (fastemit > 0.f)
+            launch_coef_fastemit(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef,
+                                 B, T, U1, D, 1.0f, fastemit, st);
+        else
+            launch_coef(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef,
+                        B, T, U1, D, 1.0f, st);
         launch_grad_logits((const float *)logits, coef, (float *)grad_logits, (long)B * T * U1, V,
                            blank, clamp, st);
     }
     return launch_status("rnnt_engine_loss_fwd_bwd");
+}
+
+int rnnt_engine_loss_fwd_bwd(const void *logits, const int32_t *targets, const int32_t *logit_lens,
+                             const int32_t *target_lens, int B, int T, int U1, int V, int blank,
+                             float clamp, int dtype, float *costs, void *grad_logits,
+                             void *workspace, size_t ws_bytes, void *stream)
+{
+    return loss_fwd_bwd(logits, targets, logit_lens, target_lens, B, T, U1, V, blank, clamp, 0.f, 0.f, dtype,
+                        costs, grad_logits, workspace, ws_bytes, stream);
+}
+
+// ---- FastEmit and the delay penalty: the entries above with the two options added
+int rnnt_engine_loss_fwd_bwd_reg(const void *logits, const int32_t *targets, const int32_t *logit_lens,
+                                 const int32_t *target_lens, int B, int T, int U1, int V, int blank,
+                                 float clamp, float fastemit_lambda, float delay_penalty, int dtype,
+                                 float *costs, void *grad_logits, void *workspace, size_t ws_bytes,
+                                 void *stream)
+{
+    if (int rc = check_reg(fastemit_lambda, delay_penalty)) return rc;
+    return loss_fwd_bwd(logits, targets, logit_lens, target_lens, B, T, U1, V, blank, clamp, fastemit_lambda,
+                        delay_penalty, dtype, costs, grad_logits, workspace, ws_bytes, stream);
+}
+
+int rnnt_engine_joint_loss_fwd_bwd_reg(const void *enc, const int64_t enc_strides[3], const void *pred,
+                                       const void *W, const void *bias, const int32_t *targets,
+                                       const int32_t *logit_lens, const int32_t *target_lens, int B,
+                                       int T, int U1, int H, int V, int blank, float clamp,
+                                       float grad_scale, float fastemit_lambda, float delay_penalty,
+                                       int dtype, float *costs, void *grad_enc, void *grad_pred,
+                                       void *grad_W, void *grad_bias, void *workspace, size_t ws_bytes,
+                                       void *stream)
+{
+    if (int rc = check_reg(fastemit_lambda, delay_penalty)) return rc;
+    return run_fused(ST_ALL, 0, enc, enc_strides, pred, W, bias, targets, logit_lens, target_lens, B, T,
+                     U1, H, V, blank, clamp, grad_scale, fastemit_lambda, delay_penalty, dtype, costs,
+                     grad_enc, grad_pred, grad_W, grad_bias, workspace, ws_bytes, stream);
+}
+
+int rnnt_engine_joint_loss_fwd_reg(const void *enc, const int64_t enc_strides[3], const void *pred,
+                                   const void *W, const void *bias, const int32_t *targets,
+                                   const int32_t *logit_lens, const int32_t *target_lens, int B, int T,
+                                   int U1, int H, int V, int blank, float delay_penalty, int dtype,
+                                   float *costs, void *workspace, size_t ws_bytes, void *stream)
+{
+    if (int rc = check_reg(0.f, delay_penalty)) return rc;
+    return run_fused(ST_PROD | ST_FWD | ST_LATTICE, 0, enc, enc_strides, pred, W, bias, targets, logit_lens,
+                     target_lens, B, T, U1, H, V, blank, -1.0f, 1.0f, 0.f, delay_penalty, dtype, costs, nullptr,
+                     nullptr, nullptr, nullptr, workspace, ws_bytes, stream);
 }
 
 int rnnt_engine_joint_loss_fwd_bwd(const void *enc, const int64_t enc_strides[3], const void *pred,
@@ -989,7 +1060,7 @@ int rnnt_engine_joint_loss_fwd_bwd(const void *enc, const int64_t enc_strides[3]
                                    size_t ws_bytes, void *stream)
 {
     return run_fused(ST_ALL, 0, enc, enc_strides, pred, W, bias, targets, logit_lens, target_lens, B, T,
-                     U1, H, V, blank, clamp, grad_scale, dtype, costs, grad_enc, grad_pred, grad_W,
+                     U1, H, V, blank, clamp, grad_scale, 0.f, 0.f, dtype, costs, grad_enc, grad_pred, grad_W,
                      grad_bias, workspace, ws_bytes, stream);
 }
 
@@ -1000,7 +1071,7 @@ int rnnt_engine_joint_loss_fwd(const void *enc, const int64_t enc_strides[3], co
                                void *workspace, size_t ws_bytes, void *stream)
 {
     return run_fused(ST_PROD | ST_FWD | ST_LATTICE, 0, enc, enc_strides, pred, W, bias, targets, logit_lens,
-                     target_lens, B, T, U1, H, V, blank, -1.0f, 1.0f, dtype, costs, nullptr, nullptr,
+                     target_lens, B, T, U1, H, V, blank, -1.0f, 1.0f, 0.f, 0.f, dtype, costs, nullptr, nullptr,
                      nullptr, nullptr, workspace, ws_bytes, stream);
 }
 
@@ -1043,7 +1114,7 @@ int rnnt_engine_joint_align(const void *enc, const int64_t enc_strides[3], const
     // operand producers + the joint-forward GEMM (log-softmax in its epilogue) of the loss; every
     // argument is checked there before anything is enqueued
     if (int rc = run_fused(ST_PROD | ST_FWD, 0, enc, enc_strides, pred, W, bias, targets, logit_lens,
-                           target_lens, B, T, U1, H, V, blank, -1.0f, 1.0f, dtype, scores, nullptr,
+                           target_lens, B, T, U1, H, V, blank, -1.0f, 1.0f, 0.f, 0.f, dtype, scores, nullptr,
                            nullptr, nullptr, nullptr, workspace, ws_bytes, stream))
         return rc;
     rnnt_engine_ws_layout L;
@@ -1063,7 +1134,7 @@ int rnnt_engine_run_stages(int stage_mask, int variant, const void *enc, const i
 {
     if (stage_mask <= 0 || stage_mask > ST_ALL) return fail(RNNT_ERR_INVALID_ARG, "stage_mask %d outside [1,255]", stage_mask);
     return run_fused(stage_mask, variant, enc, enc_strides, pred, W, bias, targets, logit_lens, target_lens,
-                     B, T, U1, H, V, blank, clamp, grad_scale, dtype, costs, grad_enc, grad_pred, grad_W,
+                     B, T, U1, H, V, blank, clamp, grad_scale, 0.f, 0.f, dtype, costs, grad_enc, grad_pred, grad_W,
                      grad_bias, workspace, ws_bytes, stream);
 }
 
@@ -1077,7 +1148,7 @@ int rnnt_engine_run_stage(int stage, const void *enc, const int64_t enc_strides[
 {
     if (stage < 0 || stage > 7) return fail(RNNT_ERR_INVALID_ARG, "stage %d outside [0,7]", stage);
     return run_fused(1 << stage, 0, enc, enc_strides, pred, W, bias, targets, logit_lens, target_lens,
-                     B, T, U1, H, V, blank, clamp, grad_scale, dtype, costs, grad_enc, grad_pred,
+                     B, T, U1, H, V, blank, clamp, grad_scale, 0.f, 0.f, dtype, costs, grad_enc, grad_pred,
                      grad_W, grad_bias, workspace, ws_bytes, stream);
 }
 

@@ -25,6 +25,16 @@ void launch_coef(const double *alpha_s, const double *beta_s, const float *denom
                  const float *lpb_s, const float *lpe_s, const int32_t *targets,
                  const int32_t *logit_lens, const int32_t *target_lens, CellCoef *coef, int B,
                  int T, int U1, int D, float scale, hipStream_t st);
+// FastEmit / delay penalty: k_coef with lambda > 0; the penalty on lp_emit before
+// launch_lattice and the cost it shifts, put back after it (every call that penalises runs both)
+void launch_coef_fastemit(const double *alpha_s, const double *beta_s, const float *denom_s,
+                          const float *lpb_s, const float *lpe_s, const int32_t *targets,
+                          const int32_t *logit_lens, const int32_t *target_lens, CellCoef *coef, int B,
+                          int T, int U1, int D, float scale, float lambda, hipStream_t st);
+void launch_delay_penalty(float *lpe_s, const int32_t *logit_lens, const int32_t *target_lens, int B,
+                          int T, int U1, int D, float delay, hipStream_t st);
+void launch_delay_cost(const double *beta_s, const int32_t *logit_lens, const int32_t *target_lens,
+                       float *costs, int B, int T, int U1, int D, float delay, hipStream_t st);
 void launch_grad_logits(const float *logits, const CellCoef *coef, float *grad, long nrows,
                         int V, int blank, float clamp, hipStream_t st);
 

@@ -8,6 +8,8 @@
 //   k_lattice<DIR>       alpha / beta anti-diagonal wavefront sweep, one workgroup per
 //                        (utterance, direction), previous diagonal staged in LDS
 //   k_coef               per-cell gradient coefficients (CellCoef) from alpha/beta
+//                        (k_coef_fastemit: the same with FastEmit's lambda)
+//   k_delay_penalty      delay penalty on lp_emit before the sweep; k_delay_cost after it
 //   k_grad_logits        d cost / d logits, elementwise (standalone loss entry only)
 //
 // All per-cell work arrays use the skewed layout of common.hpp (anti-diagonal contiguous),
@@ -369,12 +371,20 @@ __global__ void k_lattice_status(const unsigned *__restrict__ err, float *__rest
 // Per-cell gradient coefficients.  One thread per skewed slot (b,d,u); reads are coalesced
 // rows of the skewed arrays, the 16-byte CellCoef is written at the cell's natural
 // (b,t,u) index where the GEMM kernels gather it.
-__global__ __launch_bounds__(256) void k_coef(
+//
+// FE (FastEmit): the gradient of the logits gains lambda E(t,u) (p_k - [k = y]),
+// E = the posterior occupancy of the label arc.  In CellCoef terms the label term is scaled by
+// (1 + lambda) and the softmax term by 1 + lambda E / gamma, gamma = exp(alpha + beta - log P) the
+// cell's occupancy: E / gamma = exp(lp_emit + beta(t,u+1) - beta(t,u)) <= 1 (beta(t,u) is the
+// log-sum of that term and the blank one, so the exponent is never positive; fp64 sums, then one
+// fp32 exp and log1p of a value in [0, lambda]).  FE = false is the plain loss's code unchanged.
+template <bool FE>
+__device__ __forceinline__ void coef_cell(
     const double *__restrict__ alpha_s, const double *__restrict__ beta_s,
     const float *__restrict__ denom_s, const float *__restrict__ lpb_s,
     const float *__restrict__ lpe_s, const int32_t *__restrict__ targets,
     const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
-    CellCoef *__restrict__ coef, int B, int T, int U1, int D, float scale)
+    CellCoef *__restrict__ coef, int B, int T, int U1, int D, float scale, float lambda)
 {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long per = (long)D * U1;
@@ -392,16 +402,86 @@ __global__ __launch_bounds__(256) void k_coef(
         const double a = alpha_s[idx];
         const double cost = -beta_s[(long)b * per];
         const double ac = a + cost;
-        c.c1 = (float)((ac + beta_s[idx] - (double)denom_s[idx] + (double)logf(scale)) *
-                       1.4426950408889634);
+        if (!FE || u == Ub) {
+            c.c1 = (float)((ac + beta_s[idx] - (double)denom_s[idx] + (double)logf(scale)) *
+                           1.4426950408889634);
+        } else {
+            const float r = expf((float)((double)lpe_s[idx] + beta_s[idx + U1 + 1] - beta_s[idx]));
+            c.c1 = (float)((ac + beta_s[idx] + (double)log1pf(lambda * r) - (double)denom_s[idx] +
+                            (double)logf(scale)) * 1.4426950408889634);
+        }
         if (t < Tb - 1) c.sb = scale * expf((float)(ac + beta_s[idx + U1] + (double)lpb_s[idx]));
         else if (u == Ub) c.sb = scale * expf((float)(ac + (double)lpb_s[idx]));
         if (u < Ub) {
             c.se = scale * expf((float)(ac + beta_s[idx + U1 + 1] + (double)lpe_s[idx]));
+            if (FE) c.se *= 1.0f + lambda;
             c.y = targets[(long)b * (U1 - 1) + u];
         }
     }
     coef[((long)b * T + t) * U1 + u] = c;
+}
+
+__global__ __launch_bounds__(256) void k_coef(
+    const double *__restrict__ alpha_s, const double *__restrict__ beta_s,
+    const float *__restrict__ denom_s, const float *__restrict__ lpb_s,
+    const float *__restrict__ lpe_s, const int32_t *__restrict__ targets,
+    const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
+    CellCoef *__restrict__ coef, int B, int T, int U1, int D, float scale)
+{
+    coef_cell<false>(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B, T, U1, D,
+                     scale, 0.f);
+}
+
+__global__ __launch_bounds__(256) void k_coef_fastemit(
+    const double *__restrict__ alpha_s, const double *__restrict__ beta_s,
+    const float *__restrict__ denom_s, const float *__restrict__ lpb_s,
+    const float *__restrict__ lpe_s, const int32_t *__restrict__ targets,
+    const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
+    CellCoef *__restrict__ coef, int B, int T, int U1, int D, float scale, float lambda)
+{
+    coef_cell<true>(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B, T, U1, D,
+                    scale, lambda);
+}
+
+// ---------------------------------------------------------------------------------------
+// Delay penalty: the lattice of the penalised cost runs on
+// lp_emit'(t,u) = lp_emit(t,u) + delta ((T_b - 1) / 2 - t).  The chained sweep clamps every lp
+// it reads to <= 0 (slots outside the lattice may hold anything, see lattice_chain), and
+// lp_emit' is positive early in the utterance, so the pass stores lp_emit' - delta (T_b - 1) / 2
+// = lp_emit - delta t instead: every path emits exactly U_b labels, so the shift multiplies every
+// path's probability by the same exp(-U_b delta (T_b - 1) / 2).  alpha + beta - log P, and with it
+// every gradient coefficient, is unchanged by such a shift; only the cost moves, and
+// k_delay_cost puts it back after the sweep.  Live label cells only (t < T_b, u < U_b); a NaN
+// stays a NaN.  One thread per skewed slot, in place.
+__global__ __launch_bounds__(256) void k_delay_penalty(float *__restrict__ lpe_s,
+                                                       const int32_t *__restrict__ logit_lens,
+                                                       const int32_t *__restrict__ target_lens,
+                                                       int B, int T, int U1, int D, float delay)
+{
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long per = (long)D * U1;
+    if (idx >= per * B) return;
+    const int b = (int)(idx / per);
+    const long rem = idx - (long)b * per;
+    const int d = (int)(rem / U1);
+    const int u = (int)(rem - (long)d * U1);
+    const int t = d - u;
+    if (t < 0 || t >= len_t(logit_lens, b, T) || u >= len_u(target_lens, b, U1)) return;
+    lpe_s[idx] -= delay * (float)t;
+}
+
+// cost_b = -log P'_b = -beta(0,0) - U_b delta (T_b - 1) / 2, from the fp64 beta of the shifted
+// lattice (one rounding); a NaN cost (NaN input, failed sweep) stays NaN.
+__global__ void k_delay_cost(const double *__restrict__ beta_s, const int32_t *__restrict__ logit_lens,
+                             const int32_t *__restrict__ target_lens, float *__restrict__ costs, int B,
+                             int T, int U1, int D, float delay)
+{
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        const float c = costs[b];
+        if (c != c) continue;
+        const int Tb = len_t(logit_lens, b, T), Ub = len_u(target_lens, b, U1);
+        costs[b] = (float)(-beta_s[(long)b * D * U1] - (double)Ub * (double)delay * 0.5 * (double)(Tb - 1));
+    }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -489,6 +569,32 @@ void launch_coef(const double *alpha_s, const double *beta_s, const float *denom
     hipLaunchKernelGGL(k_coef, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, alpha_s,
                        beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B,
                        T, U1, D, scale);
+}
+
+void launch_coef_fastemit(const double *alpha_s, const double *beta_s, const float *denom_s,
+                          const float *lpb_s, const float *lpe_s, const int32_t *targets,
+                          const int32_t *logit_lens, const int32_t *target_lens, CellCoef *coef, int B,
+                          int T, int U1, int D, float scale, float lambda, hipStream_t st)
+{
+    const long n = (long)B * D * U1;
+    hipLaunchKernelGGL(k_coef_fastemit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, alpha_s,
+                       beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B,
+                       T, U1, D, scale, lambda);
+}
+
+void launch_delay_penalty(float *lpe_s, const int32_t *logit_lens, const int32_t *target_lens, int B,
+                          int T, int U1, int D, float delay, hipStream_t st)
+{
+    const long n = (long)B * D * U1;
+    hipLaunchKernelGGL(k_delay_penalty, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, lpe_s,
+                       logit_lens, target_lens, B, T, U1, D, delay);
+}
+
+void launch_delay_cost(const double *beta_s, const int32_t *logit_lens, const int32_t *target_lens,
+                       float *costs, int B, int T, int U1, int D, float delay, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_delay_cost, dim3(1), dim3(256), 0, st, beta_s, logit_lens, target_lens, costs,
+                       B, T, U1, D, delay);
 }
 
 void launch_grad_logits(const float *logits, const CellCoef *coef, float *grad, long nrows,

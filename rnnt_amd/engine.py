@@ -5,6 +5,7 @@ through the C ABI.  There is NO fallback: if the library is missing or a call fa
 RuntimeError is raised.
 """
 import ctypes
+import math
 import os
 import subprocess
 import threading
@@ -63,6 +64,9 @@ SIGNATURES = {
     "rnnt_engine_loss_fwd_bwd": "ppppiiiiifipppzp",
     "rnnt_engine_joint_loss_fwd_bwd": "ppppppppiiiiiiffippppppzp",
     "rnnt_engine_joint_loss_fwd": "ppppppppiiiiiiippzp",
+    "rnnt_engine_loss_fwd_bwd_reg": "ppppiiiiifffipppzp",
+    "rnnt_engine_joint_loss_fwd_bwd_reg": "ppppppppiiiiiiffffippppppzp",
+    "rnnt_engine_joint_loss_fwd_reg": "ppppppppiiiiiifippzp",
     "rnnt_engine_align": "ppppiiiiipppzp",
     "rnnt_engine_joint_align": "ppppppppiiiiiiipppzp",
     "rnnt_engine_joint_bwd_workspace_bytes": "iiiiiip",
@@ -132,6 +136,7 @@ EXPORTS = (
     "rnnt_engine_linear_bwd", "rnnt_engine_allreduce",
     "rnnt_engine_linear_x2_workspace_bytes", "rnnt_engine_linear_x2_fwd", "rnnt_engine_linear_x2_bwd",
     "rnnt_engine_align", "rnnt_engine_joint_align",
+    "rnnt_engine_loss_fwd_bwd_reg", "rnnt_engine_joint_loss_fwd_bwd_reg", "rnnt_engine_joint_loss_fwd_reg",
 )
 
 # per-call kernel variants (include/rnnt_engine.h RNNT_VARIANT_*): bit-identical results
@@ -349,8 +354,35 @@ def joint_bwd(enc, pred, W, grad_logits):
     return ge, gp, gW, gb
 
 
+def check_reg(fastemit_lambda, delay_penalty):
+    """FastEmit's lambda and the delay penalty's delta as floats; ValueError unless both are finite and >= 0
+    (the C entries answer RNNT_ERR_INVALID_ARG for the same values)."""
+    out = []
+    for name, v in (("fastemit_lambda", fastemit_lambda), ("delay_penalty", delay_penalty)):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"rnnt_amd: {name} must be a finite number >= 0 (got {v!r})") from None
+        if not (math.isfinite(f) and f >= 0.0):
+            raise ValueError(f"rnnt_amd: {name} must be finite and >= 0 (got {v!r})")
+        out.append(f)
+    return tuple(out)
+
+
 def loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp=-1.0, want_grad=True):
     """Per-utterance costs and d(sum costs)/d logits (reference rnnt/model.py:35-41)."""
+    return _loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp, want_grad, None)
+
+
+def loss_fwd_bwd_reg(logits, targets, logit_lens, target_lens, blank, clamp, fastemit_lambda, delay_penalty,
+                     want_grad=True):
+    """loss_fwd_bwd with FastEmit and the delay penalty (C ABI rnnt_engine_loss_fwd_bwd_reg); `clamp`
+    applies to the regularised gradient."""
+    return _loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp, want_grad,
+                         check_reg(fastemit_lambda, delay_penalty))
+
+
+def _loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp, want_grad, reg):
     dev = _require_cuda(logits, targets, logit_lens, target_lens)
     _require_dtype(torch.float32, logits=logits)
     _require_dtype(torch.int32, targets=targets, logit_lens=logit_lens, target_lens=target_lens)
@@ -363,10 +395,12 @@ def loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp=-1.0, wa
         n = ctypes.c_size_t(0)
         _check(lib().rnnt_engine_loss_workspace_bytes(B, T, U1, V, DTYPE_F32, ctypes.byref(n)))
         ws = workspace(dev, n.value)
-        _check(lib().rnnt_engine_loss_fwd_bwd(_p(logits), _p(targets), _p(logit_lens), _p(target_lens),
-                                              B, T, U1, V, int(blank), ctypes.c_float(clamp), DTYPE_F32,
-                                              _p(costs), _p(grad), _p(ws), ctypes.c_size_t(ws.numel()),
-                                              _stream(dev)))
+        head = (_p(logits), _p(targets), _p(logit_lens), _p(target_lens), B, T, U1, V, int(blank), ctypes.c_float(clamp))
+        tail = (DTYPE_F32, _p(costs), _p(grad), _p(ws), ctypes.c_size_t(ws.numel()), _stream(dev))
+        if reg is None:
+            _check(lib().rnnt_engine_loss_fwd_bwd(*head, *tail))
+        else:
+            _check(lib().rnnt_engine_loss_fwd_bwd_reg(*head, ctypes.c_float(reg[0]), ctypes.c_float(reg[1]), *tail))
     return costs, grad
 
 
@@ -445,6 +479,48 @@ def joint_loss_fwd_bwd(enc, pred, W, bias, targets, logit_lens, target_lens, bla
         else:
             _check(lib().rnnt_engine_run_stage(int(stage), *args))
     return outs
+
+
+def joint_loss_fwd_bwd_reg(enc, pred, W, bias, targets, logit_lens, target_lens, blank, grad_scale, fastemit_lambda,
+                           delay_penalty, outs=None, *, dtype):
+    """joint_loss_fwd_bwd with FastEmit and the delay penalty (C ABI rnnt_engine_joint_loss_fwd_bwd_reg):
+    costs are the penalised -log P' (lambda does not change them), gradients those of grad_scale * the regularised loss."""
+    fe, dp = check_reg(fastemit_lambda, delay_penalty)
+    dev = _check_fused_inputs(enc, pred, W, bias, targets, logit_lens, target_lens)
+    targets = _nonempty(targets)
+    with torch.cuda.device(dev):
+        if outs is None:
+            outs = alloc_fused_outputs(enc, pred, W)
+        else:
+            _require_cuda(enc, *outs)
+            _require_dtype(torch.float32, **{f"outs[{i}]": o for i, o in enumerate(outs)})
+            _require_contiguous(**{f"outs[{i}]": o for i, o in enumerate(outs)})
+        code = dtype_code(dtype)
+        B, T, H = enc.shape
+        ws = workspace(dev, workspace_bytes(B, T, pred.shape[1], H, W.shape[0], code))
+        a = _fused_args(enc, pred, W, bias, targets, logit_lens, target_lens, blank, grad_scale, outs, ws, code)
+        _check(lib().rnnt_engine_joint_loss_fwd_bwd_reg(*a[:15], a[15], ctypes.c_float(fe), ctypes.c_float(dp), *a[16:]))
+    return outs
+
+
+def joint_loss_fwd_reg(enc, pred, W, bias, targets, logit_lens, target_lens, blank, delay_penalty, *, dtype):
+    """joint_loss_fwd with the delay penalty (C ABI rnnt_engine_joint_loss_fwd_reg): the penalised costs, forward kernels
+    only (FastEmit changes no cost)."""
+    _, dp = check_reg(0.0, delay_penalty)
+    dev = _check_fused_inputs(enc, pred, W, bias, targets, logit_lens, target_lens)
+    B, T, H = enc.shape
+    U1 = pred.shape[1]
+    V = W.shape[0]
+    targets = _nonempty(targets)
+    code = dtype_code(dtype)
+    with torch.cuda.device(dev):
+        costs = torch.empty(B, dtype=torch.float32, device=dev)
+        ws = workspace(dev, workspace_bytes(B, T, U1, H, V, code))
+        _check(lib().rnnt_engine_joint_loss_fwd_reg(
+            _p(enc), _strides3(enc), _p(pred), _p(W), _p(bias), _p(targets), _p(logit_lens),
+            _p(target_lens), B, T, U1, H, V, int(blank), ctypes.c_float(dp), code, _p(costs), _p(ws),
+            ctypes.c_size_t(ws.numel()), _stream(dev)))
+    return costs
 
 
 def joint_loss_fwd(enc, pred, W, bias, targets, logit_lens, target_lens, blank, *, dtype):

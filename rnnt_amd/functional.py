@@ -5,6 +5,8 @@
   joint_logits(...)     the T x U joint expansion of reference rnnt/joint.py:32-39.
   joint_rnnt_loss(...)  the fused hot path: joint + loss, forward and backward in ONE engine
                         call; the (B,T,U+1,V) logits never leave the engine's workspace.
+  fastemit_lambda / delay_penalty (both loss operators): FastEmit and the delay penalty, the
+                        latency regularisers of streaming transducers.
   rnnt_align(...), joint_rnnt_align(...)
                         forced alignment on the same lattice: the best path's
                         log-probability and the frame of every label; no autograd.
@@ -57,9 +59,14 @@ def _check_loss_args(T, U1, V, B, targets, logit_lengths, target_lengths, blank,
 
 class _RNNTLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, targets, logit_lengths, target_lengths, blank, clamp):
-        costs, grad = engine.loss_fwd_bwd(logits, targets, logit_lengths, target_lengths, blank,
-                                          clamp, want_grad=ctx.needs_input_grad[0])
+    def forward(ctx, logits, targets, logit_lengths, target_lengths, blank, clamp, fastemit_lambda=0.0,
+                delay_penalty=0.0):
+        if fastemit_lambda or delay_penalty:
+            costs, grad = engine.loss_fwd_bwd_reg(logits, targets, logit_lengths, target_lengths, blank, clamp,
+                                                  fastemit_lambda, delay_penalty, want_grad=ctx.needs_input_grad[0])
+        else:
+            costs, grad = engine.loss_fwd_bwd(logits, targets, logit_lengths, target_lengths, blank,
+                                              clamp, want_grad=ctx.needs_input_grad[0])
         ctx.save_for_backward(grad)
         return costs
 
@@ -67,13 +74,17 @@ class _RNNTLoss(torch.autograd.Function):
     def backward(ctx, grad_costs):
         (grad,) = ctx.saved_tensors
         if grad is None:
-            return None, None, None, None, None, None
-        return grad * grad_costs.view(-1, 1, 1, 1), None, None, None, None, None
+            return None, None, None, None, None, None, None, None
+        return grad * grad_costs.view(-1, 1, 1, 1), None, None, None, None, None, None, None
 
 
 def rnnt_loss(logits, targets, logit_lengths, target_lengths, blank=-1, clamp=-1, reduction="mean",
-              fused_log_softmax=True, check_lengths=True):
-    """Transducer loss on materialised logits [B,T,U+1,V] (reference rnnt/model.py:35-41)."""
+              fused_log_softmax=True, check_lengths=True, fastemit_lambda=0.0, delay_penalty=0.0):
+    """Transducer loss on materialised logits [B,T,U+1,V] (reference rnnt/model.py:35-41).
+    `fastemit_lambda` / `delay_penalty` (finite, >= 0): FastEmit adds lambda E (p_k - [k = y]) to the
+    gradient of every label cell and leaves the costs unchanged; the delay penalty runs the lattice on
+    lp_emit + delta ((T_b - 1) / 2 - t) and returns the penalised costs.  `clamp` applies to the regularised gradient."""
+    fastemit_lambda, delay_penalty = engine.check_reg(fastemit_lambda, delay_penalty)
     if not fused_log_softmax:
         raise NotImplementedError("rnnt_amd.rnnt_loss only implements fused_log_softmax=True")
     if logits.dim() != 4:
@@ -88,7 +99,8 @@ def rnnt_loss(logits, targets, logit_lengths, target_lengths, blank=-1, clamp=-1
     if V % 4 != 0:
         pad = 4 - V % 4
         logits = torch.nn.functional.pad(logits, (0, pad), value=_PAD_NEG)
-    costs = _RNNTLoss.apply(logits, targets, logit_lengths, target_lengths, blank, float(clamp))
+    costs = _RNNTLoss.apply(logits, targets, logit_lengths, target_lengths, blank, float(clamp), fastemit_lambda,
+                            delay_penalty)
     if reduction == "mean":
         return costs.mean()
     if reduction == "sum":
@@ -169,15 +181,24 @@ def linear(x, W, bias, backend="auto"):
 class _JointRNNTLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, enc, pred, W, bias, targets, logit_lengths, target_lengths, blank, scale,
-                dtype, need_grad=True):
+                dtype, need_grad=True, fastemit_lambda=0.0, delay_penalty=0.0):
         if not need_grad:  # torch.no_grad() / nothing requires grad: forward kernels only
-            costs = engine.joint_loss_fwd(enc, pred.contiguous(), W.contiguous(), bias.contiguous(),
-                                          targets, logit_lengths, target_lengths, blank, dtype=dtype)
+            if delay_penalty:  # (FastEmit changes no cost)
+                costs = engine.joint_loss_fwd_reg(enc, pred.contiguous(), W.contiguous(), bias.contiguous(), targets,
+                                                  logit_lengths, target_lengths, blank, delay_penalty, dtype=dtype)
+            else:
+                costs = engine.joint_loss_fwd(enc, pred.contiguous(), W.contiguous(), bias.contiguous(),
+                                              targets, logit_lengths, target_lengths, blank, dtype=dtype)
             ctx.mark_non_differentiable(costs)
             return costs.sum() * scale, costs
-        costs, ge, gp, gW, gb = engine.joint_loss_fwd_bwd(
-            enc, pred.contiguous(), W.contiguous(), bias.contiguous(), targets, logit_lengths,
-            target_lengths, blank, scale, dtype=dtype)
+        if fastemit_lambda or delay_penalty:
+            costs, ge, gp, gW, gb = engine.joint_loss_fwd_bwd_reg(
+                enc, pred.contiguous(), W.contiguous(), bias.contiguous(), targets, logit_lengths,
+                target_lengths, blank, scale, fastemit_lambda, delay_penalty, dtype=dtype)
+        else:
+            costs, ge, gp, gW, gb = engine.joint_loss_fwd_bwd(
+                enc, pred.contiguous(), W.contiguous(), bias.contiguous(), targets, logit_lengths,
+                target_lengths, blank, scale, dtype=dtype)
         ctx.save_for_backward(ge, gp, gW, gb)
         ctx.scale = scale
         ctx.mark_non_differentiable(costs)
@@ -187,12 +208,12 @@ class _JointRNNTLoss(torch.autograd.Function):
     def backward(ctx, grad_loss, _grad_costs):
         ge, gp, gW, gb = ctx.saved_tensors
         return (ge * grad_loss, gp * grad_loss, gW * grad_loss, gb * grad_loss,
-                None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None)
 
 
 def joint_rnnt_loss(enc, pred, W, bias, targets, logit_lengths, target_lengths, blank=-1,
                     reduction="mean", check_lengths=True, return_costs=False, grad_scale=None,
-                    dtype=engine.DEFAULT_DTYPE):
+                    dtype=engine.DEFAULT_DTYPE, fastemit_lambda=0.0, delay_penalty=0.0):
     """Fused replacement of
         logits = joint(enc, pred)                      # reference rnnt/model.py:32
         loss = torchaudio.functional.rnnt_loss(logits, targets, ..., blank, clamp=-1, reduction)
@@ -205,7 +226,10 @@ def joint_rnnt_loss(enc, pred, W, bias, targets, logit_lengths, target_lengths, 
     operands with fp32 accumulation; needs H % 128 == 0, V % 128 == 0.
     `dtype="bf16x3"`: fp32-accurate results (same 1e-4 bar as "fp32") from the bf16 matrix pipes — operands
     split three ways, six bf16 products per fp32 product (include/rnnt_engine.h RNNT_DTYPE_F32_BF16X3);
-    any H, V (zero-padded to multiples of 128 here)."""
+    any H, V (zero-padded to multiples of 128 here).
+    `fastemit_lambda` / `delay_penalty` (finite, >= 0): the latency regularisers, as rnnt_loss takes them (DESIGN.md §4k);
+    both are per utterance and FastEmit is linear in `grad_scale`, so sharded calls still sum to the full batch's gradients."""
+    fastemit_lambda, delay_penalty = engine.check_reg(fastemit_lambda, delay_penalty)
     if reduction not in ("mean", "sum"):
         if reduction == "none":
             raise NotImplementedError(
@@ -232,7 +256,7 @@ def joint_rnnt_loss(enc, pred, W, bias, targets, logit_lengths, target_lengths, 
     # validation / eval (reference rnnt/train.py:170-201 runs the model under no_grad): costs only
     need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (enc, pred, W, bias))
     loss, costs = _JointRNNTLoss.apply(enc_p, pred_p, W_p, bias_p, targets, logit_lengths,
-                                       target_lengths, blank, scale, code, need_grad)
+                                       target_lengths, blank, scale, code, need_grad, fastemit_lambda, delay_penalty)
     return (loss, costs) if return_costs else loss
 
 

@@ -19,6 +19,10 @@ class RNNTModel(torch.nn.Module):
         # them — the kernels clamp every length into range — so that forward + backward enqueue
         # device work only and can be captured into a HIP graph.
         self.check_lengths = True
+        # latency regularisers of the loss (rnnt_amd.joint_rnnt_loss's options of the same names): FastEmit's
+        # lambda and the delay penalty's delta, both >= 0; 0 = the reference's plain loss
+        self.fastemit_lambda = 0.0
+        self.delay_penalty = 0.0
 
     @property
     def device(self):
@@ -37,11 +41,16 @@ class RNNTModel(torch.nn.Module):
         audio_feature_lens = self.encoder.calc_output_lens(mel_feature_lens)
 
         # reference model.py:32-41 — blank=-1, clamp=-1, reduction="mean" — as one engine call
+        reg = {}
+        if self.fastemit_lambda:
+            reg["fastemit_lambda"] = self.fastemit_lambda
+        if self.delay_penalty:
+            reg["delay_penalty"] = self.delay_penalty
         return self.joint.fused_loss(audio_features, decoder_features,
                                      targets=input_ids.int(),
                                      logit_lengths=audio_feature_lens.int(),
                                      target_lengths=input_id_lens.int(),
-                                     blank=-1, reduction="mean", check_lengths=self.check_lengths)
+                                     blank=-1, reduction="mean", check_lengths=self.check_lengths, **reg)
 
     # ---- forced alignment
     @torch.no_grad()
