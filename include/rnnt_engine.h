@@ -90,6 +90,14 @@ void rnnt_engine_set_debug(void *buf);
  * NOT bit-identical to the default bf16x3 kernels (different summation), same tolerance. */
 #define RNNT_VARIANT_X3_FP32_FWD 4096       /* forward GEMM + hidden by the fp32 kernel, then k_x3_make_hidden */
 #define RNNT_VARIANT_X3_FP32_DH 8192        /* dHidden + G by the fp32 kernels, then k_x3_split_g (needs _FWD too) */
+/* RNNT_DTYPE_F32_F16X2 only: switch the flush rule off for this call.  By default that route gives every lattice cell whose
+ * gradient row its fp16 split provably rounds to zero (|g_scale G| < 2^-26: rnnt_amd/csrc/lattice.hip coef_cell, x2.hip) the
+ * coefficients of a cell outside the lattice; dHidden tiles and 16-cell dW k-steps without a live cell are then skipped.  With this
+ * bit no cell is flagged: tiles and k-steps are skipped by the utterances' lengths only.  costs, grad_enc and grad_pred are
+ * bit-identical with and without it; grad_W / grad_bias differ in summation order only (the split-K ranges cut the list of live
+ * k-steps at other cells).  The regularised entry (rnnt_engine_joint_loss_fwd_bwd_reg) always runs as if the bit were set:
+ * the bound is not extended to FastEmit's / the delay penalty's coefficients. */
+#define RNNT_VARIANT_X2_NO_FLUSH_SKIP 512
 /* Bits 14 and up name kernels of the DIAGNOSTIC library only (rnnt_amd/csrc/lab/rnnt_engine_lab.h, tools/build_lab.sh):
  * librnnt_engine.so answers them with RNNT_ERR_UNSUPPORTED. */
 #define RNNT_VARIANT_LAB_MASK 0x7fffc000
@@ -513,6 +521,9 @@ typedef struct rnnt_engine_ws_layout {
     size_t aux, aux_bytes; /* RNNT_DTYPE_F32_BF16X3: fp32 hidden + W pack of the RNNT_VARIANT_X3_FP32_* stages, placed BEHIND
                             * `total` (aux == total): only a call with such a variant needs total + aux_bytes */
     size_t ep;            /* RNNT_DTYPE_F32_F16X2: exp(2 enc) [B][H/16][T][16] then exp(2 pred) [B][H/16][U1][16], fp32 (0: none) */
+    size_t x2_live;       /* RNNT_DTYPE_F32_F16X2 (0: none): the live structures of the last call's backward.  At +0 four int32 counts:
+                           * live 16-cell dW k-steps, k-steps that hold a cell, live dHidden tiles (8 t x 16 u), dHidden tiles; at +256 one
+                           * byte per dHidden tile [B][ceil(T/8)][ceil(U1/16)], 1 = live (the k-step bitmap and list follow) */
 } rnnt_engine_ws_layout;
 
 int rnnt_engine_workspace_layout(int B, int T, int U1, int H, int V, int dtype,

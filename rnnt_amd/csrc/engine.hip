@@ -5,6 +5,7 @@
 #include "../../include/rnnt_engine.h"
 
 #include <cfloat>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -104,7 +105,7 @@ void layout(int B, int T, int U1, int H, int V, int dtype, rnnt_engine_ws_layout
     L->n_ublk = bf ? (U1 + 15) / 16 : x3 ? (U1 + 7) / 8 : (U1 + dhidden_gen_bu(T, U1) - 1) / dhidden_gen_bu(T, U1);
     L->n_ttile = (T + 3) / 4;  // dPred slabs: at most one per 4 t rows (the persistent kernel's 16-wide items)
     L->n_split = dw_splits(B, T, H, V, dtype);
-    L->g_lo = 0; L->aux = 0; L->aux_bytes = 0;
+    L->g_lo = 0; L->aux = 0; L->aux_bytes = 0; L->x2_live = 0;
     size_t o = 0;
     if (bf) {
         const size_t ra = (size_t)bf16_rows_alloc(rows_pad);
@@ -142,6 +143,7 @@ void layout(int B, int T, int U1, int H, int V, int dtype, rnnt_engine_ws_layout
         L->counters = o; o += 1024 + align_up(tab > lst ? tab : lst);
         if (bf || x2) o += align_up((size_t)L->n_split * 64);  // k_dw_bf16's / k_dw_x2's progress words, behind the table
     }
+    if (x2) { L->x2_live = o; o += align_up(x2_live_bytes(B, T, U1, (long)rows_pad)); }  // counts, tile flags, k-step bitmap and list (launch_x2_live)
     L->total = o;
     if (x3) {  // fp32 hidden + fp32 W pack of the stages that can run on the fp32 route's kernels (RNNT_VARIANT_X3_FP32_*):
         // BEHIND `total` — only a call that asks for such a variant needs a workspace of total + aux_bytes
@@ -266,6 +268,7 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
                                              RNNT_VARIANT_FWD_LDS_RING | RNNT_VARIANT_FWD_ONE_WG_PER_TILE |
                                              RNNT_VARIANT_X3_FP32_FWD | RNNT_VARIANT_X3_FP32_DH |
                                              RNNT_VARIANT_X3_FWD_2WG | RNNT_VARIANT_X3_FWD_8W | RNNT_VARIANT_X3_DW_P16 | RNNT_VARIANT_X3_FWD_Z | RNNT_VARIANT_X2_DW_8W | RNNT_VARIANT_X2_FWD_2WG | RNNT_VARIANT_X2_DW_P16));
+    const bool no_flush = (variant & RNNT_VARIANT_X2_NO_FLUSH_SKIP) != 0 || fastemit > 0.f || delay > 0.f;
     rnnt_engine_ws_layout L;
     layout(B, T, U1, H, V, dtype, &L);
     if (ws_bytes < L.total)
@@ -285,7 +288,8 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
     // lattice sweep and coefficients (every route): the delay penalty goes on lp_emit before the sweep and its cost
     // shift comes off after it, FastEmit's coefficients replace k_coef's; zero options launch exactly
     // the plain loss's kernels
-    auto loss_stages = [&]() {
+    // (flush: the f16x2 route's threshold — lattice.hip coef_cell — or null: the plain coefficients)
+    auto loss_stages = [&](const double *flush_log2 = nullptr, float flush_lin = 0.f) {
         if (stages & ST_LATTICE) {
             if (delay > 0.f) launch_delay_penalty(lpe_s, logit_lens, target_lens, B, T, U1, L.D, delay, st);
             launch_lattice(lpb_s, lpe_s, alpha_s, beta_s, logit_lens, target_lens, costs, B, U1, L.D,
@@ -296,6 +300,9 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
             if (fastemit > 0.f)
                 launch_coef_fastemit(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef,
                                      B, T, U1, L.D, grad_scale, fastemit, st);
+            else if (flush_log2)
+                launch_coef_flush(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef,
+                                  B, T, U1, L.D, grad_scale, *flush_log2, flush_lin, st);
             else
                 launch_coef(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef,
                             B, T, U1, L.D, grad_scale, st);
@@ -320,6 +327,9 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
         // fp32-accurate route on the bf16 matrix pipes (x3.hip).  Stage by stage the fp32 route's own kernel can
         // stand in (RNNT_VARIANT_X3_FP32_FWD / _DH): same data, one stage swapped — how each x3 kernel is checked.
         X3Args h;
+        h.tile_live = nullptr; h.ks_bitmap = nullptr; h.ks_list = nullptr; h.live_stats = nullptr; h.zero_all = 0;
+        double flush_log2 = -HUGE_VAL;  // the flush rule's threshold (x2.hip): log2 of 2^-26 / g_scale; -inf flags nothing
+        float flush_lin = 0.f;
         h.enc = encp; h.enc_sb = esb; h.enc_st = est; h.pred = (const float *)pred;
         h.W = (const float *)W; h.bias = (const float *)bias;
         h.rows_pad = (long)L.rows_pad; h.rows_alloc = bf16_rows_alloc(L.rows_pad);
@@ -332,6 +342,7 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
             (void)frexpf(grad_scale * (1.0f + fastemit), &e);
             const int k = 13 - e < -100 ? -100 : (13 - e > 100 ? 100 : 13 - e);
             h.g_scale = ldexpf(1.0f, k);
+            if (x2 && !no_flush) { flush_log2 = (double)(-26 - k); flush_lin = ldexpf(1.0f, -26 - k); }
             h.dw_rescale = 1.0f / (h.g_scale * 16384.0f); h.db_rescale = 1.0f / h.g_scale;
             h.scales = (const float *)(ws + L.counters + 640);
             h.dw_prog = x2 ? (int *)(ws + L.counters + 1024 + align_up((2 * (size_t)B + 2) * 8)) : nullptr;
@@ -352,6 +363,13 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
             return fail(RNNT_ERR_WORKSPACE, "workspace %zu < %zu bytes: a stage on the fp32 route's kernels (RNNT_VARIANT_X3_FP32_*, or a "
                         "shape k_joint_fwd_x3 / k_dhidden_x3 do not cover) needs total + aux_bytes of rnnt_engine_workspace_layout",
                         ws_bytes, L.total + L.aux_bytes);
+        if (x2) {
+            x2_live_carve(ws + L.x2_live, B, T, U1, (long)L.rows_pad, h);
+            h.zero_all = x2_dw_walks_table(H, V, xflags) ? 1 : 0;
+            // the fp32 kernels standing in for dHidden multiply G in fp32, where a flushed cell's G is small but not zero: no flush, no tile
+            // skipping there (k_x2_split_g writes every row, so the dW list walk still applies)
+            if (f32_dh) { flush_log2 = -HUGE_VAL; flush_lin = 0.f; }
+        }
         float *hid32 = (float *)(ws + L.aux);
         float *wpack32 = (float *)(ws + L.aux + align_up((L.rows_pad + 16) * (size_t)H * 4));
         g.hidden = hid32;
@@ -399,7 +417,12 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
                 launch_joint_fwd_x3(h, st);
             }
         }
-        loss_stages();
+        if (x2) {
+            loss_stages(&flush_log2, flush_lin);
+            if (stages & ST_COEF) launch_x2_live(h, st);  // tile flags, k-step bitmap / list, counts: from the coefficients
+        } else {
+            loss_stages();
+        }
         if (stages & ST_DH) {
             if (x2) launch_x2_zero_padding(h, 2, st);
             else launch_x3_zero_padding(h, 2, st);
@@ -422,7 +445,10 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
 #endif
             else launch_dw_x3(h, st);
         }
-        if (stages & ST_DW_RED) launch_dw_reduce(g, st);
+        if (stages & ST_DW_RED) {
+            if (x2) launch_dw_reduce_x2(h, g.grad_W, g.grad_bias, st);  // one rounding: dW does not follow where the splits cut the live list
+            else launch_dw_reduce(g, st);
+        }
         return launch_status(x2 ? "rnnt_engine fused pipeline (f16x2)" : "rnnt_engine fused pipeline (bf16x3)");
     }
     if (dtype == RNNT_DTYPE_BF16) {
@@ -1034,7 +1060,8 @@ int rnnt_engine_joint_loss_fwd_bwd_reg(const void *enc, const int64_t enc_stride
                                        void *stream)
 {
     if (int rc = check_reg(fastemit_lambda, delay_penalty)) return rc;
-    return run_fused(ST_ALL, 0, enc, enc_strides, pred, W, bias, targets, logit_lens, target_lens, B, T,
+    // (the f16x2 route's flush rule is not extended to the regularised coefficients: nothing is flushed here, whatever the options)
+    return run_fused(ST_ALL, RNNT_VARIANT_X2_NO_FLUSH_SKIP, enc, enc_strides, pred, W, bias, targets, logit_lens, target_lens, B, T,
                      U1, H, V, blank, clamp, grad_scale, fastemit_lambda, delay_penalty, dtype, costs,
                      grad_enc, grad_pred, grad_W, grad_bias, workspace, ws_bytes, stream);
 }

@@ -25,6 +25,12 @@ void launch_coef(const double *alpha_s, const double *beta_s, const float *denom
                  const float *lpb_s, const float *lpe_s, const int32_t *targets,
                  const int32_t *logit_lens, const int32_t *target_lens, CellCoef *coef, int B,
                  int T, int U1, int D, float scale, hipStream_t st);
+// the f16x2 route's k_coef: cells whose G the route's fp16 split provably rounds to zero get the coefficients of a cell outside
+// the lattice (lattice.hip coef_cell, FLUSH); flush_log2 = -inf, flush_lin = 0 flag nothing
+void launch_coef_flush(const double *alpha_s, const double *beta_s, const float *denom_s,
+                       const float *lpb_s, const float *lpe_s, const int32_t *targets,
+                       const int32_t *logit_lens, const int32_t *target_lens, CellCoef *coef, int B,
+                       int T, int U1, int D, float scale, double flush_log2, float flush_lin, hipStream_t st);
 // FastEmit / delay penalty: k_coef with lambda > 0; the penalty on lp_emit before
 // launch_lattice and the cost it shifts, put back after it (every call that penalises runs both)
 void launch_coef_fastemit(const double *alpha_s, const double *beta_s, const float *denom_s,
@@ -174,7 +180,16 @@ struct X3Args {
     int *dw_prog;               // [n_split][16] progress words of k_dw_x2's tiles (zeroed by its launcher), or NULL
     float *ep_enc, *ep_pred;    // exp(2 enc) [B][H/16][T][16], exp(2 pred) [B][H/16][U1][16] (k_x2_make_ep, every call)
     unsigned *ep_flag;          // device word: != 0 when an input lies outside the factored tanh's range (the exact forward runs)
+    // live structures of the backward (launch_x2_live, after the coefficients; x2.hip "flush rule"); the Linear layer's dW sets ks_list / live_stats only
+    const unsigned char *tile_live;  // [B][ceil(T/8)][n_ublk16]: 1 = the dHidden tile holds a cell with non-null coefficients; NULL: every tile inside the lengths runs
+    const unsigned *ks_bitmap;       // bit k: 16-cell k-step k of the dW GEMM is live (holds such a cell); NULL: a skipped tile zero-fills every row
+    int *ks_list;                    // ascending live k-steps, then >= 8 entries naming the first all-padding k-step (rows_pad / 16)
+    int *live_stats;                 // [0] live k-steps = length of ks_list, [1] k-steps with a cell, [2] live dHidden tiles, [3] dHidden tiles
+    int zero_all;                    // 1: the dW kernel of this call walks the 32-cell table (the lab's k_dw_x2p): skipped tiles zero-fill every row
 };
+size_t x2_live_bytes(int B, int T, int U1, long rows_pad);  // bytes of the region below
+void x2_live_carve(void *region, int B, int T, int U1, long rows_pad, X3Args &a);  // points tile_live .. live_stats into the region
+void launch_x2_live(const X3Args &a, hipStream_t st);  // builds all four from X3Args::coef
 bool x3_fwd_ok(int U1, int H, int V);      // the bf16x3 forward kernel covers this shape (else: the fp32 route's)
 bool x3_dhidden_ok(int U1, int H, int V);  // likewise k_dhidden_x3
 size_t x3_wpack_fwd_bytes(int H, int V);
@@ -212,6 +227,8 @@ void launch_linear_x2_fwd(const float *x, long ldx, const float *W, const float 
 void launch_linear_x2_bwd(const float *x, long ldx, const float *W, const float *dy, int M, int K, int N, float *dx, float *dW, float *db, void *ws,
                           hipStream_t st);
 int x2_dw_tiles(int H, int V);  // workgroup tiles per split of launch_dw_x2 (k_dw_x2 / k_dw_x2m)
+void launch_dw_reduce_x2(const X3Args &a, float *grad_W, float *grad_bias, hipStream_t st);  // the slabs' sum, fp64 accumulate, one rounding
+bool x2_dw_walks_table(int H, int V, int flags);  // launch_dw_x2's kernel for this shape reads k_dw_table's ranges, not X3Args::ks_list
 void launch_dw_x2(const X3Args &a, hipStream_t st, bool build_table = true, bool zero_prog = true);  // k_dw_x2<4> (k_dw_x2<4, true> when H % 256 == 128); -DRNNT_LAB builds: also k_dw_x2<8> / k_dw_x2p behind RNNT_VARIANT_X2_DW_8W / _P16
 
 // ---- decode.hip

@@ -378,13 +378,30 @@ __global__ void k_lattice_status(const unsigned *__restrict__ err, float *__rest
 // cell's occupancy: E / gamma = exp(lp_emit + beta(t,u+1) - beta(t,u)) <= 1 (beta(t,u) is the
 // log-sum of that term and the blank one, so the exponent is never positive; fp64 sums, then one
 // fp32 exp and log1p of a value in [0, lambda]).  FE = false is the plain loss's code unchanged.
-template <bool FE>
+//
+// FLUSH (the f16x2 route, x2.hip "flush rule"): a lattice cell whose gradient row is PROVABLY rounded to zero by that route's
+// split of g_scale G into two fp16 planes gets the coefficients of a cell outside the lattice (c1 = -inf, sb = se = 0, y = -1),
+// so that the backward GEMMs may skip it.  fp16's smallest subnormal is 2^-24 and the split rounds to nearest-even: |x| <= 2^-25
+// gives hi = +-0 and then mid = f16(x - hi) = +-0.  The test asks for one binade more, |g_scale G[v]| < 2^-26 for every v:
+//   * G[v] = e_v - [v = blank] sb - [v = y] se with e_v, sb, se >= 0, so |G[v]| <= max(e_v, sb + se); sb and se are compared
+//     as the very fp32 values the kernels subtract: sb + se < flush_lin = 2^-26 / g_scale (an exact power of two).
+//   * e_v = v_exp_f32(fma(x_v, L', c1')), L' = fp32(log2 e), c1' = fp32(c1), c1 = s1 - denom log2 e in fp64 with
+//     s1 = (alpha + beta - log P + log scale) log2 e.  denom is the forward's fp32 log-sum-exp of the row: x_v - denom <= 0.01
+//     while |denom| <= 4096 (20 ulps there; the test requires it).  Then the exact fma argument is
+//     z <= s1 + 0.01 log2 e + |x_v| (L' - log2 e) [L' > log2 e by 1.9e-8: <= 8e-5 for x_v <= 4097, negative for x_v < 0]
+//            + |c1| 2^-24.  Either z < -200, and the rounded argument is below -150: e_v = 0 exactly; or |c1| < 200 + 4096 log2 e
+//     < 2^13, its rounding is below 2^-11 and the fma's own below 2^-16: z_rounded < s1 + 0.02.  v_exp_f32 is good to one ulp:
+//     e_v < 2^(s1 + 0.03).  With s1 < flush_log2 = -26 - log2 g_scale:  g_scale e_v < 2^-25.97.
+// Both comparisons are ordered: a NaN anywhere (a non-finite cost poisons alpha + cost of every cell of its utterance) keeps the
+// cell live, and flush_log2 = -inf (flush_lin = 0) flags nothing.
+template <bool FE, bool FLUSH = false>
 __device__ __forceinline__ void coef_cell(
     const double *__restrict__ alpha_s, const double *__restrict__ beta_s,
     const float *__restrict__ denom_s, const float *__restrict__ lpb_s,
     const float *__restrict__ lpe_s, const int32_t *__restrict__ targets,
     const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
-    CellCoef *__restrict__ coef, int B, int T, int U1, int D, float scale, float lambda)
+    CellCoef *__restrict__ coef, int B, int T, int U1, int D, float scale, float lambda,
+    double flush_log2 = 0.0, float flush_lin = 0.f)
 {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long per = (long)D * U1;
@@ -417,8 +434,26 @@ __device__ __forceinline__ void coef_cell(
             if (FE) c.se *= 1.0f + lambda;
             c.y = targets[(long)b * (U1 - 1) + u];
         }
+        if (FLUSH) {  // (never with FE: the regularised entries pass no threshold)
+            const double s1 = (ac + beta_s[idx] + (double)logf(scale)) * 1.4426950408889634;
+            if (s1 < flush_log2 && fabsf(denom_s[idx]) <= 4096.f && c.sb + c.se < flush_lin) {
+                c.c1 = RNNT_NEG_INF; c.sb = 0.f; c.se = 0.f; c.y = -1;
+            }
+        }
     }
     coef[((long)b * T + t) * U1 + u] = c;
+}
+
+// k_coef with the f16x2 route's flush rule (coef_cell): launched by that route only
+__global__ __launch_bounds__(256) void k_coef_flush(
+    const double *__restrict__ alpha_s, const double *__restrict__ beta_s,
+    const float *__restrict__ denom_s, const float *__restrict__ lpb_s,
+    const float *__restrict__ lpe_s, const int32_t *__restrict__ targets,
+    const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
+    CellCoef *__restrict__ coef, int B, int T, int U1, int D, float scale, double flush_log2, float flush_lin)
+{
+    coef_cell<false, true>(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B, T, U1, D,
+                           scale, 0.f, flush_log2, flush_lin);
 }
 
 __global__ __launch_bounds__(256) void k_coef(
@@ -569,6 +604,17 @@ void launch_coef(const double *alpha_s, const double *beta_s, const float *denom
     hipLaunchKernelGGL(k_coef, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, alpha_s,
                        beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B,
                        T, U1, D, scale);
+}
+
+void launch_coef_flush(const double *alpha_s, const double *beta_s, const float *denom_s,
+                       const float *lpb_s, const float *lpe_s, const int32_t *targets,
+                       const int32_t *logit_lens, const int32_t *target_lens, CellCoef *coef, int B,
+                       int T, int U1, int D, float scale, double flush_log2, float flush_lin, hipStream_t st)
+{
+    const long n = (long)B * D * U1;
+    hipLaunchKernelGGL(k_coef_flush, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, alpha_s,
+                       beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B,
+                       T, U1, D, scale, flush_log2, flush_lin);
 }
 
 void launch_coef_fastemit(const double *alpha_s, const double *beta_s, const float *denom_s,

@@ -16,6 +16,10 @@
 // garbage operands) are clamped to +-65504 where they are split.
 // Same boundary, same workspace objects, same stage structure and variants as the bf16x3 route (engine.hip runs both through
 // one code path); logits, log-softmax, lattice, coefficients and all reductions are the fp32 / fp64 code of the fp32 route.
+// Flush rule (below, "The flush rule and the live structures of the backward"): fp16's narrow exponent makes both planes of g_scale G
+// exactly zero wherever the lattice's occupancy is below ~2^-38 — half the cells of the benchmark's batch.  The coefficient kernel
+// proves that per cell (|g_scale G| < 2^-26, one binade inside what rounds to zero: lattice.hip coef_cell), and the two backward GEMMs
+// skip the dHidden tiles and the 16-cell dW k-steps that hold no other cell.  RNNT_VARIANT_X2_NO_FLUSH_SKIP switches it off per call.
 //
 // MFMA operand maps (v_mfma_f32_32x32x16_f16, as the bf16 form): lane l = (r = l&31, h = l>>5) holds A[row r][k = 8h+j] and
 // B[k = 8h+j][col r], j = 0..7; C/D: col = l&31, row = (reg&3) + 8*(reg>>2) + 4*(l>>5).
@@ -104,6 +108,9 @@ __device__ __forceinline__ void x2_lds_barrier()
     __builtin_amdgcn_sched_barrier(0);
 }
 template <int N> struct X2Int { static constexpr int value = N; };
+#define XW2_ROWS_ 16  // = XW2_ROWS: cells per dW k-step
+#define XG2_BT_ 8    // = XG2_BT, XG2_BU: the dHidden tile
+#define XG2_BU_ 16
 #define X2_FLAG_LINEAR 0x40000000  // X3Args::flags: launch_joint_fwd_x2 runs the plain-GEMM form (k_joint_fwd_x2<2>: the joint's input projections)
 
 // ---------------------------------------------------------------------------------------
@@ -232,6 +239,188 @@ void launch_x2_zero_padding(const X3Args &a, int what, hipStream_t st)
 }
 
 // ---------------------------------------------------------------------------------------
+// The flush rule and the live structures of the backward.
+// g_scale G is split into two fp16 planes with round-to-nearest-even: a value of magnitude <= 2^-25 becomes hi = +-0, mid = +-0, and
+// a zero plane entry adds nothing to an MFMA accumulator.  |G[c,:]| <= grad_scale gamma(c), gamma = exp(alpha + beta - log P) the
+// posterior occupancy of lattice node c: an RNN-T lattice is occupied in a band around the alignment, and about half the cells of the
+// benchmark's batch lie below that threshold.  k_coef_flush (lattice.hip: the bound, its margin and the rounding it covers are
+// derived there) gives every such cell the coefficients of a cell OUTSIDE the lattice — for which k_dhidden_x2 always produced
+// G = 0 from the zero padding row — and the kernels below turn the coefficients into what lets the two backward GEMMs skip:
+//   tile_live[b][tt][ub]  the dHidden tile (8 t x 16 u) holds a cell with non-null coefficients: the others leave at the dead-tile exit;
+//   ks_bitmap / ks_list   the 16-cell k-steps of the dW GEMM (linear cell index / 16) that hold such a cell, as a bitmap and as the
+//                         ascending list k_dw_x2 walks (fixed order: dW stays bitwise reproducible), padded with entries that name
+//                         the first k-step of the zero padding rows for the ring's read-ahead;
+//   live_stats            the counts (readable from the workspace: rnnt_engine_ws_layout::x2_live).
+// Dropping a flushed cell changes no bit of costs, dEnc or dPred (its products were exact zeros); dW / db change in summation
+// order only (the splits cut the live list at other cells).  RNNT_VARIANT_X2_NO_FLUSH_SKIP flags no cell: the structures then hold
+// what is live by the utterances' lengths.  Everything is built on the device from the coefficients: no host read-back.
+// ---------------------------------------------------------------------------------------
+#define XL2_BLK 1024
+__device__ __forceinline__ bool x2_coef_live(const CellCoef &c) { return !(c.c1 == RNNT_NEG_INF && c.sb == 0.f && c.se == 0.f); }
+namespace {
+struct X2LiveWs { size_t tiles, bitmap, blk, list, total; long nks, ntile; int nblk; };
+X2LiveWs x2_live_layout(int B, int T, int U1, long rows_pad)
+{
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    X2LiveWs L{};
+    L.nks = rows_pad / XW2_ROWS_;
+    L.ntile = (long)B * ((T + 7) / 8) * ((U1 + 15) / 16);
+    L.nblk = (int)((L.nks + XL2_BLK - 1) / XL2_BLK);
+    size_t o = 256;  // live_stats
+    L.tiles = o; o += al((size_t)L.ntile);
+    L.bitmap = o; o += al((size_t)L.nblk * (XL2_BLK / 8));
+    L.blk = o; o += al((size_t)L.nblk * 4);
+    L.list = o; o += al((size_t)(L.nks + 8) * 4);
+    L.total = o;
+    return L;
+}
+}  // namespace
+size_t x2_live_bytes(int B, int T, int U1, long rows_pad) { return x2_live_layout(B, T, U1, rows_pad).total; }
+void x2_live_carve(void *region, int B, int T, int U1, long rows_pad, X3Args &a)
+{
+    const X2LiveWs L = x2_live_layout(B, T, U1, rows_pad);
+    char *r = (char *)region;
+    a.live_stats = (int *)r; a.tile_live = (const unsigned char *)(r + L.tiles); a.ks_bitmap = (const unsigned *)(r + L.bitmap);
+    a.ks_list = (int *)(r + L.list);
+}
+// one workgroup per 1024 k-steps (16384 cells, read coalesced: 16 rounds of one cell per thread; a wave's ballot covers 4 k-steps):
+// live flags -> 16 bitmap words, their number -> blk
+__global__ __launch_bounds__(XL2_BLK) void k_x2_live_count(const CellCoef *__restrict__ coef, long cells,
+                                                           unsigned long long *__restrict__ bitmap, int *__restrict__ blk)
+{
+    __shared__ unsigned short s_nib[16][16];  // [round = bitmap word][wave]: the wave's 4 k-step flags
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long base = (long)blockIdx.x * XL2_BLK * XW2_ROWS_;
+    for (int it = 0; it < 16; ++it) {
+        const long c = base + (long)it * XL2_BLK + threadIdx.x;
+        const bool live = c < cells && x2_coef_live(coef[c]);
+        const unsigned long long bal = __ballot(live);
+        if (lane == 0)
+            s_nib[it][wave] = (unsigned short)(((bal & 0xffffull) ? 1 : 0) | ((bal & 0xffff0000ull) ? 2 : 0) |
+                                               ((bal & 0xffff00000000ull) ? 4 : 0) | ((bal & 0xffff000000000000ull) ? 8 : 0));
+    }
+    __syncthreads();
+    int cnt = 0;
+    if (threadIdx.x < 16) {
+        unsigned long long w = 0;
+        for (int k = 0; k < 16; ++k) w |= (unsigned long long)s_nib[threadIdx.x][k] << (4 * k);
+        bitmap[(long)blockIdx.x * 16 + threadIdx.x] = w;
+        cnt = __popcll(w);
+    }
+    if (wave == 0) {
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+        if (lane == 0) blk[blockIdx.x] = cnt;
+    }
+}
+// exclusive scan of the block counts in place (one workgroup, k_dw_list_scan's); the counts; the list's padding entries
+__global__ __launch_bounds__(1024) void k_x2_live_scan(int *__restrict__ blk, int nblk, int *__restrict__ stats, int *__restrict__ list,
+                                                       long cells, long nks, long ntile, const unsigned char *__restrict__ tile_live)
+{
+    __shared__ int s_w[16];
+    __shared__ int s_carry;
+    if (threadIdx.x == 0) s_carry = 0;
+    __syncthreads();
+    for (int base = 0; base < nblk; base += 1024) {
+        const int i = base + threadIdx.x;
+        const int v = i < nblk ? blk[i] : 0;
+        int x = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d, 64); if ((threadIdx.x & 63) >= d) x += y; }
+        if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = x;
+        __syncthreads();
+        int off = s_carry;
+        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) off += s_w[w];
+        if (i < nblk) blk[i] = off + x - v;
+        __syncthreads();
+        if (threadIdx.x == 1023) s_carry = off + x;
+        __syncthreads();
+    }
+    const int total = s_carry;
+    int lt = 0;  // live dHidden tiles: the sum of k_x2_live_tiles' flag bytes
+    for (long k = threadIdx.x; k < ntile; k += 1024) lt += tile_live[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lt += __shfl_xor(lt, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = lt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        lt = 0;
+        for (int w = 0; w < 16; ++w) lt += s_w[w];
+        stats[0] = total; stats[1] = (int)((cells + XW2_ROWS_ - 1) / XW2_ROWS_); stats[2] = lt; stats[3] = (int)ntile;
+    }
+    if (threadIdx.x < 8) list[total + threadIdx.x] = (int)nks;  // rows rows_pad ..: zero padding (rows_alloc >= rows_pad + 96)
+}
+__global__ __launch_bounds__(XL2_BLK) void k_x2_live_write(const unsigned long long *__restrict__ bitmap, long nks, const int *__restrict__ blk,
+                                                           int *__restrict__ list)
+{
+    __shared__ int s_w[XL2_BLK / 64];
+    const long k = (long)blockIdx.x * XL2_BLK + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long bal = bitmap[k >> 6];
+    if (lane == 0) s_w[wave] = __popcll(bal);
+    __syncthreads();
+    int off = blk[blockIdx.x];
+    for (int w = 0; w < wave; ++w) off += s_w[w];
+    if ((bal >> lane) & 1ull) list[off + __popcll(bal & ((1ull << lane) - 1ull))] = (int)k;
+}
+// one wave per dHidden tile [b][tt][ub] (two rounds of 64 cells), four tiles per workgroup: the tile's flag byte.  (No counting here:
+// an atomic per live tile on one word cost 0.28 ms at config 2 — k_x2_live_scan sums the bytes.)
+__global__ __launch_bounds__(256) void k_x2_live_tiles(const CellCoef *__restrict__ coef, int T, int U1, int ntt, int nub, long ntile,
+                                                       unsigned char *__restrict__ tile_live)
+{
+    const int lane = threadIdx.x & 63;
+    const long tile = (long)blockIdx.x * 4 + (threadIdx.x >> 6);  // (wave-uniform)
+    if (tile >= ntile) return;
+    const int ub = (int)(tile % nub), tt = (int)((tile / nub) % ntt);
+    const long b = tile / ((long)nub * ntt);
+    bool live = false;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const int r = it * 64 + lane;
+        const int t = tt * XG2_BT_ + (r >> 4), u = ub * XG2_BU_ + (r & 15);
+        if (t < T && u < U1) live = live || x2_coef_live(coef[(b * T + t) * U1 + u]);
+    }
+    const bool any = __any(live ? 1 : 0) != 0;
+    if (lane == 0) tile_live[tile] = any ? 1 : 0;
+}
+void launch_x2_live(const X3Args &a, hipStream_t st)
+{
+    const X2LiveWs L = x2_live_layout(a.B, a.T, a.U1, a.rows_pad);
+    const long cells = (long)a.B * a.T * a.U1;
+    int *blk = (int *)((char *)a.live_stats + L.blk);
+    unsigned long long *bitmap = (unsigned long long *)a.ks_bitmap;
+    const int ntt = (a.T + XG2_BT_ - 1) / XG2_BT_, nub = (a.U1 + XG2_BU_ - 1) / XG2_BU_;
+    hipLaunchKernelGGL(k_x2_live_tiles, dim3((unsigned)((L.ntile + 3) / 4)), dim3(256), 0, st, a.coef, a.T, a.U1, ntt, nub, L.ntile, (unsigned char *)a.tile_live);
+    hipLaunchKernelGGL(k_x2_live_count, dim3(L.nblk), dim3(XL2_BLK), 0, st, a.coef, cells, bitmap, blk);
+    hipLaunchKernelGGL(k_x2_live_scan, dim3(1), dim3(1024), 0, st, blk, L.nblk, a.live_stats, a.ks_list, cells, L.nks, L.ntile, a.tile_live);
+    hipLaunchKernelGGL(k_x2_live_write, dim3(L.nblk), dim3(XL2_BLK), 0, st, bitmap, L.nks, blk, a.ks_list);
+}
+
+// dW / db = the sum of the split-K slabs, accumulated in fp64 and rounded ONCE (fixed order: bitwise reproducible).  The splits cut the
+// live k-step list evenly, so WHERE they cut depends on how many k-steps the flush rule left: an fp32 running sum over up to 256 slabs
+// rounds at every step at the size of the total (measured: 3 ulp of the largest dW entries between a call with and without
+// RNNT_VARIANT_X2_NO_FLUSH_SKIP), where the slabs themselves — fp32 sums of 1 / n_split of the cells — differ far below an ulp of the
+// total.  With one rounding the result no longer follows the cuts beyond that ulp.  Same bytes read, 0.03 ms at config 2.
+__global__ __launch_bounds__(256) void k_x2_reduce_slabs(const float *__restrict__ slab, float *__restrict__ out, long n4, int ns)
+{
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n4) return;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    for (int k = 0; k < ns; ++k) {
+        const f32x4 v = ((const f32x4 *)slab)[(long)k * n4 + idx];
+        s0 += (double)v[0]; s1 += (double)v[1]; s2 += (double)v[2]; s3 += (double)v[3];
+    }
+    ((f32x4 *)out)[idx] = f32x4{(float)s0, (float)s1, (float)s2, (float)s3};
+}
+void launch_dw_reduce_x2(const X3Args &a, float *grad_W, float *grad_bias, hipStream_t st)
+{
+    const long n4w = (long)a.V * a.H / 4, n4b = a.V / 4;
+    hipLaunchKernelGGL(k_x2_reduce_slabs, dim3((unsigned)((n4w + 255) / 256)), dim3(256), 0, st, a.slab_w, grad_W, n4w, a.n_split);
+    hipLaunchKernelGGL(k_x2_reduce_slabs, dim3((unsigned)((n4b + 255) / 256)), dim3(256), 0, st, a.slab_b, grad_bias, n4b, a.n_split);
+}
+
+// ---------------------------------------------------------------------------------------
 // k_dw_x2: dW[v,h] = sum_c G[c,v] hidden[c,h] (split-K slabs), db[v] = sum_c G[c,v] — k_dw_x3's design on two planes:
 // 4 waves = 2 (M) x 2 (N), workgroup tile 256 v x 256 h, wave 128 x 128 = 16 accumulator tiles (256 registers).  Both
 // operands row-major with K (the cell) as the ROW, two fp16 planes each:
@@ -243,16 +432,21 @@ void launch_x2_zero_padding(const X3Args &a, int what, hipStream_t st)
 // One k-step = 16 cells = 3 products x 16 tiles = 48 MFMAs (1536 matrix-pipe cycles) against 32 KiB staged.  Per k-step:
 // counted vmcnt + one barrier publish stage ks, the 8 DMAs of stage ks+2 go into the slot of ks-1 threaded through the
 // MFMAs (3 + 3 + 2), fragment reads run one product ahead of their MFMAs.  Products ah.bh, am.bh, ah.bm.
+// K walk: the split-K ranges are cut from the ascending list of LIVE k-steps (X3Args::ks_list: the k-steps that hold a cell with non-null
+// coefficients — inside the lengths, reachable, not flushed), evenly, so the splits are balanced whatever the lattices' shapes; k-step ks of
+// a split multiplies the 16 rows of k-step list[g_lo + ks], one pipeline run per split.  Rows of a live k-step that belong to no live cell
+// hold zeros (k_dhidden_x2 writes them).
 // The accumulators hold g_scale x 2^14 x dW: the epilogue multiplies by X3Args::dw_rescale (a power of two).
 // ---------------------------------------------------------------------------------------
 #define XW2_ROWS 16
+static_assert(XW2_ROWS == XW2_ROWS_, "k-step size");
 #ifndef XW2_NST
 #define XW2_NST 4   // ring stages: the DMAs of stage ks + NST - 1 are issued during k-step ks
 #endif
 #define XW2_PLANE 4096            // one operand tile of one plane: 16 rows x 256 B
 #define XW2_STAGE (2 * XW2_PLANE)  // one stage of one operand tile
 #define XW2_TILE (XW2_NST * XW2_STAGE)  // ring of one operand tile: [stage][plane][16 x 256 B] = 24 KiB
-#define XW2_GRAN 32  // granule of the live-row table (shared with the bf16 routes: 2 k-steps)
+#define XW2_GRAN 32  // granule of the live-row table the lab's k_dw_x2p still walks (k_dw_table, shared with the bf16 routes: 2 k-steps); the Linear layer's table unit
 
 struct X2Frag { u32x2 lo[4], hi[4]; };  // 4 tiles: cells 0-3 / 4-7 of a lane's 8
 #define X2_LANDED(f, N)                                                                                          \
@@ -290,10 +484,11 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
     }
     const int tile = id % tiles, split = id / tiles;
     const int vb = tile / n_hblk, hb = tile % n_hblk;
-    const long *tab = a.dw_tab;
-    const int B = a.B;
-    const long nlive = tab[2 * B + 1];
-    const long g_lo = nlive * split / a.n_split, g_hi = nlive * (split + 1) / a.n_split;
+    // this split's share [g_lo, g_hi) of the LIVE k-steps (X3Args::ks_list, launch_x2_live; the Linear layer: every k-step)
+    const long nlive = __builtin_amdgcn_readfirstlane(a.live_stats[0]);  // (uniform by construction; said so: the walk's control flow is scalar)
+    // (the 64-bit divisions run on the vector ALU: the quotients, at most nlive, are handed back to scalar registers)
+    const int g_lo = __builtin_amdgcn_readfirstlane((int)(nlive * split / a.n_split));
+    const int g_hi = __builtin_amdgcn_readfirstlane((int)(nlive * (split + 1) / a.n_split));
     X2_CLOCK_STAMP(128 + 104);
 
     f32x16 acc[4][QN];
@@ -347,7 +542,13 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
 #endif
         }
         const bool live_n = !PARTH || hb * 256 + wn * 32 * QN < H;  // this wave's h columns exist (wave-uniform)
-        long row_first = 0;  // first cell of the range being walked
+        // The walk: ONE pipeline run over the split's list entries — k-step ks multiplies the 16 cells of k-step list[g_lo + ks] of the
+        // [cells] buffers.  An entry is fetched by a scalar load (wave-uniform, outside the counted vector-memory stream; it only feeds
+        // the buffer resources' base) that is waited for in the same asm statement, so no register copy made before the data arrived
+        // can be what the address is built from; inside the k loop it is issued in front of the counted vmcnt wait it shares its
+        // latency with.  Past the split's end the read-ahead fetches the next split's entries (real rows, never multiplied) or the
+        // list's padding entries (zero rows).
+        const int *lptr = a.ks_list + g_lo;
         // ---- transposed fragment reads.  Fragment of 32-column tile m: lane (g = lane>>4, q = (lane&15)>>2,
         // p = lane&3) reads rows 8(g>>1) + 4sec + q at chunk 4m + 2(g&1) + (p>>1), +8(p&1) bytes, sec = 0,1.
         const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3, hh = g >> 1;
@@ -382,11 +583,18 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
         // one k-step on ring stage ST (compile-time: every LDS offset is an immediate)
         auto kstep = [&](auto st_c, long ks, f32x16 &dacc) {
             constexpr int ST = decltype(st_c)::value, DST = (ST + XW2_NST - 1) % XW2_NST;
-            // the 16 rows of stage ks+2 as two raw buffers (wave-uniform base; the per-lane part is the 32-bit soff)
+            // stage ks landed (the 8 (NST - 2) younger pieces of the stages after it may still fly); every wave is past its reads of
+            // stage ks-1, whose ring stage the DMAs below refill.  In front of the wait: the list entry of stage ks + NST - 1
+            int ent;
+            const int *ep = lptr + ks + (XW2_NST - 1);
+            if (ND * (XW2_NST - 2) == 16) asm volatile("s_load_dword %0, %1, 0x0\n\t" RNNT_VMCNT(16) "\n\ts_waitcnt lgkmcnt(0)" : "=s"(ent) : "s"(ep) : "memory");
+            else if (ND * (XW2_NST - 2) == 8) asm volatile("s_load_dword %0, %1, 0x0\n\t" RNNT_VMCNT(8) "\n\ts_waitcnt lgkmcnt(0)" : "=s"(ent) : "s"(ep) : "memory");
+            else asm volatile("s_load_dword %0, %1, 0x0\n\t" RNNT_VMCNT(4) "\n\ts_waitcnt lgkmcnt(0)" : "=s"(ent) : "s"(ep) : "memory");
+            // its 16 rows as two raw buffers (wave-uniform base; the per-lane part is the 32-bit soff)
             __amdgpu_buffer_rsrc_t rs[2];
 #pragma unroll
             for (int p = 0; p < 2; ++p)
-                rs[p] = __builtin_amdgcn_make_buffer_rsrc((void *)(pbase[p] + (row_first + (ks + XW2_NST - 1) * XW2_ROWS) * rstride), 0,
+                rs[p] = __builtin_amdgcn_make_buffer_rsrc((void *)(pbase[p] + ((long)ent * XW2_ROWS) * rstride), 0,
                                                           (int)(XW2_ROWS * rstride), 0x00020000);
             auto dma_piece = [&](auto n_c) {  // piece n of this wave's share of stage ks+NST-1 -> ring stage DST: plane n>>2 (8 waves: wave & 1), rows 4(n&3)..
                 constexpr int n = decltype(n_c)::value, i = n & 3;
@@ -449,11 +657,6 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
                 // accumulator in VGPRs, spelled as asm (left to hipcc the 17th tile is shuttled through the full AGPR file)
                 asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(dacc) : "v"(fa), "v"(sel));
             };
-            // stage ks landed (the 8 (NST - 2) younger pieces of the stages after it may still fly); every wave is past its reads of
-            // stage ks-1, whose ring stage the DMAs below refill
-            if (ND * (XW2_NST - 2) == 16) asm volatile(RNNT_VMCNT(16) ::: "memory");
-            else if (ND * (XW2_NST - 2) == 8) asm volatile(RNNT_VMCNT(8) ::: "memory");
-            else asm volatile(RNNT_VMCNT(4) ::: "memory");
             x2_lds_barrier();
             X2Frag Ah, Bh, Am, Bm;
             u32x2 dl[2], dh[2];
@@ -479,11 +682,14 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
             }
         };
         auto dma_stage = [&](long ks, int st) {  // pipeline prologue: this wave's pieces of stage ks
+            int ent;
+            const int *ep = lptr + ks;
+            asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ent) : "s"(ep) : "memory");
 #pragma unroll
             for (int n = 0; n < ND; ++n) {
                 const int p = NW == 8 ? (wave & 1) : n >> 2, i = n & 3;
                 const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
-                    (void *)(pbase[p] + (row_first + ks * XW2_ROWS) * rstride), 0, (int)(XW2_ROWS * rstride), 0x00020000);
+                    (void *)(pbase[p] + ((long)ent * XW2_ROWS) * rstride), 0, (int)(XW2_ROWS * rstride), 0x00020000);
 #if XF2_IMM
                 if (NW == 4) {
                     if (i == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_vptr)(s_ring + otile * XW2_TILE + st * XW2_STAGE + p * XW2_PLANE), 16, soff[i], 0, 0, 0);
@@ -510,7 +716,6 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
         bool sync_on = prog != nullptr && tiles > 1 && tiles <= 16;
         const int *nb = prog ? prog + (tile + 1 < tiles ? tile + 1 : 0) : nullptr;  // the neighbour's word
         int nb_at = 0x7fffffff;  // the neighbour's k-step count as of the last look
-        int done = 0;            // k-steps behind this workgroup, over all ranges
         auto lockstep = [&](int mine) {  // (wave-uniform)
             // the value requested at the previous look has long landed; the wait names nb_at so that no copy of the register made before
             // the data arrived can be what the comparison reads (round-4 advice: a stale value only mis-paces, but makes timing and traffic
@@ -527,21 +732,16 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
                 asm volatile("s_load_dword %0, %1, 0x0 glc" : "=s"(nb_at) : "s"(nb) : "memory");  // used at the next look
             }
         };
-        int ub = 0;
-        while (ub + 1 < B && tab[B + 1 + ub + 1] <= g_lo) ++ub;
-        for (long gq = g_lo; gq < g_hi; ++ub) {  // workgroup-uniform: one pipeline run per live range
-            const long cum0 = tab[B + 1 + ub], cum1 = ub + 1 < B ? tab[B + 1 + ub + 1] : nlive;
-            const long ge = cum1 < g_hi ? cum1 : g_hi;
-            if (ge <= gq) continue;
-            const long nks = 2 * (ge - gq);  // 16-cell k-steps of this range
-            row_first = (tab[ub] + (gq - cum0)) * XW2_GRAN;
-            gq = ge;
+        int runs = 1;  // ONE pipeline run; the count is opaque to hipcc, which keeps the accumulators in their registers across a loop of
+        asm volatile("" : "+s"(runs));  // runs (the per-range walk's shape) and spills all 256 of them around a straight-line run
+        for (int run = 0; run < runs; ++run) {
+            const int nks = g_hi - g_lo;  // workgroup-uniform
             dma_stage(0, 0);
             dma_stage(1, 1);
             if (XW2_NST == 4) dma_stage(2, 2);
-            for (long ks = 0;;) {  // the ring stage of a k-step is ks % NST: unrolled by NST
+            for (int ks = 0;;) {  // the ring stage of a k-step is ks % NST: unrolled by NST
                 if (ks >= nks) break;
-                lockstep(done + (int)ks);
+                lockstep(ks);
                 kstep(X2Int<0>{}, ks, dacc); ++ks;
                 if (ks >= nks) break;
                 kstep(X2Int<1>{}, ks, dacc); ++ks;
@@ -598,8 +798,8 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
 // operand tile (its 8 DMA pieces per stage shared out two per wave): 40 KiB per k-step instead of 32, a 5-tile ring = 160 KiB of LDS.
 // The kernel's two tile kinds are two complete copies of the loop behind ONE workgroup-uniform branch (a branch inside the k loop would split
 // the hand-placed MFMA / DMA / read schedule into scheduling regions); everything else — ring stage layout, source-side swizzle, transposed
-// reads, the three products, db on the matrix pipe (whole h blocks 0 and 1 only), live-row table, soft lockstep, slab epilogue — is
-// k_dw_x2<4>'s, statement for statement.
+// reads, the three products, db on the matrix pipe (whole h blocks 0 and 1 only), soft lockstep, slab epilogue — is k_dw_x2<4>'s,
+// statement for statement, its walk of the live k-step list (X3Args::ks_list, one pipeline run per split) included.
 // ---------------------------------------------------------------------------------------
 #ifndef X2_DW_MIXED
 #define X2_DW_MIXED 1  // 0 (diagnostic builds): k_dw_x2<4, true> everywhere, round 5's form — the A/B partner of k_dw_x2m
@@ -623,10 +823,10 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
         id = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + id / 8;
     }
     const int tile = id % tiles, split = id / tiles;
-    const long *tab = a.dw_tab;
-    const int B = a.B;
-    const long nlive = tab[2 * B + 1];
-    const long g_lo = nlive * split / a.n_split, g_hi = nlive * (split + 1) / a.n_split;
+    // this split's share [g_lo, g_hi) of the live k-steps (k_dw_x2's walk: X3Args::ks_list)
+    const long nlive = __builtin_amdgcn_readfirstlane(a.live_stats[0]);
+    const int g_lo = __builtin_amdgcn_readfirstlane((int)(nlive * split / a.n_split));
+    const int g_hi = __builtin_amdgcn_readfirstlane((int)(nlive * (split + 1) / a.n_split));
     const unsigned sel0 = (lane & 31) == 0 ? 0x3c003c00u : 0u;  // fp16 ones in column 0 of the selector fragment
 
     auto body = [&](auto tall_c) {
@@ -685,7 +885,7 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
                 const int jg = (lane & 15) ^ (((lane >> 4) << 2) | (i & 3));
                 xoff[k] = (int)((4 * i + (lane >> 4)) * xstride) + 16 * jg;
             }
-            long row_first = 0;
+            const int *lptr = a.ks_list + g_lo;  // k-step ks multiplies the 16 rows of k-step lptr[ks] (k_dw_x2's walk)
             // ---- transposed fragment reads (k_dw_x2's): A from operand tile wm (tall: wave), B from the hidden tile(s)
             const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3, hh = g >> 1;
             const int lds0 = (int)(size_t)(lds_vptr)s_ring;
@@ -706,13 +906,20 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
 
             auto kstep = [&](auto st_c, long ks, f32x16 &dacc) {
                 constexpr int ST = decltype(st_c)::value, DST = (ST + XW2_NST - 1) % XW2_NST;
+                // stage ks landed (the ND (NST - 2) younger pieces of the stages after it may still fly); every wave is past its reads of
+                // stage ks-1, whose ring stage the DMAs below refill.  In front of the wait: the list entry of stage ks + NST - 1 (k_dw_x2's)
+                static_assert(XW2_NST == 4, "counted waits below: two stages in flight behind the one waited for");
+                int ent;
+                const int *ep = lptr + ks + (XW2_NST - 1);
+                if (TALL) asm volatile("s_load_dword %0, %1, 0x0\n\t" RNNT_VMCNT(20) "\n\ts_waitcnt lgkmcnt(0)" : "=s"(ent) : "s"(ep) : "memory");
+                else asm volatile("s_load_dword %0, %1, 0x0\n\t" RNNT_VMCNT(16) "\n\ts_waitcnt lgkmcnt(0)" : "=s"(ent) : "s"(ep) : "memory");
                 __amdgpu_buffer_rsrc_t rs[2];
 #pragma unroll
                 for (int p = 0; p < 2; ++p)
-                    rs[p] = __builtin_amdgcn_make_buffer_rsrc((void *)(pbase[p] + (row_first + (ks + XW2_NST - 1) * XW2_ROWS) * rstride), 0,
+                    rs[p] = __builtin_amdgcn_make_buffer_rsrc((void *)(pbase[p] + ((long)ent * XW2_ROWS) * rstride), 0,
                                                               (int)(XW2_ROWS * rstride), 0x00020000);
                 const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
-                    (void *)(xbase + (row_first + (ks + XW2_NST - 1) * XW2_ROWS) * xstride), 0, (int)(XW2_ROWS * xstride), 0x00020000);
+                    (void *)(xbase + ((long)ent * XW2_ROWS) * xstride), 0, (int)(XW2_ROWS * xstride), 0x00020000);
                 auto dma_piece = [&](auto n_c) {  // piece n of this wave's share of stage ks+NST-1 -> ring stage DST
                     constexpr int n = decltype(n_c)::value;
                     if constexpr (n < 8) {
@@ -765,11 +972,6 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
                     const u32x4 sel = {sel0, sel0, sel0, sel0};
                     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(dacc) : "v"(fa), "v"(sel));
                 };
-                // stage ks landed (the ND (NST - 2) younger pieces of the stages after it may still fly); every wave is past its reads of
-                // stage ks-1, whose ring stage the DMAs below refill
-                static_assert(XW2_NST == 4, "counted waits below: two stages in flight behind the one waited for");
-                if (TALL) asm volatile(RNNT_VMCNT(20) ::: "memory");
-                else asm volatile(RNNT_VMCNT(16) ::: "memory");
                 x2_lds_barrier();
                 X2Frag Ah, Bh, Am, Bm;
                 u32x2 dl[2], dh[2];
@@ -788,11 +990,14 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
                 if (do_b) { bias_mfma(dl[0], dh[0], dacc); bias_mfma(dl[1], dh[1], dacc); }
             };
             auto dma_stage = [&](long ks, int st) {  // pipeline prologue: this wave's pieces of stage ks
+                int ent;
+                const int *ep = lptr + ks;
+                asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ent) : "s"(ep) : "memory");
 #pragma unroll
                 for (int n = 0; n < 8; ++n) {
                     const int p = n >> 2, i = n & 3;
                     const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
-                        (void *)(pbase[p] + (row_first + ks * XW2_ROWS) * rstride), 0, (int)(XW2_ROWS * rstride), 0x00020000);
+                        (void *)(pbase[p] + ((long)ent * XW2_ROWS) * rstride), 0, (int)(XW2_ROWS * rstride), 0x00020000);
                     lds_vptr d = (lds_vptr)(s_ring + own_tile * XW2_TILE + st * XW2_STAGE + p * XW2_PLANE);
                     if (i == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d, 16, soff[i], 0, 0, 0);
                     if (i == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d, 16, soff[i], 0, 1024, 0);
@@ -801,7 +1006,7 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
                 }
                 if (TALL) {
                     const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
-                        (void *)(xbase + (row_first + ks * XW2_ROWS) * xstride), 0, (int)(XW2_ROWS * xstride), 0x00020000);
+                        (void *)(xbase + ((long)ent * XW2_ROWS) * xstride), 0, (int)(XW2_ROWS * xstride), 0x00020000);
 #pragma unroll
                     for (int k = 0; k < 2; ++k)
                         __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_vptr)(s_ring + 4 * XW2_TILE + st * XW2_STAGE + xp * XW2_PLANE + 1024 * (xi0 + k)),
@@ -815,7 +1020,6 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
             bool sync_on = prog != nullptr && tiles > 1 && tiles <= 16;
             const int *nb = prog ? prog + (tile + 1 < tiles ? tile + 1 : 0) : nullptr;
             int nb_at = 0x7fffffff;
-            int done = 0;
             auto lockstep = [&](int mine) {  // (wave-uniform)
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(nb_at) :: "memory");
                 int naps = 0;
@@ -829,21 +1033,16 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
                     asm volatile("s_load_dword %0, %1, 0x0 glc" : "=s"(nb_at) : "s"(nb) : "memory");
                 }
             };
-            int ub = 0;
-            while (ub + 1 < B && tab[B + 1 + ub + 1] <= g_lo) ++ub;
-            for (long gq = g_lo; gq < g_hi; ++ub) {  // workgroup-uniform: one pipeline run per live range
-                const long cum0 = tab[B + 1 + ub], cum1 = ub + 1 < B ? tab[B + 1 + ub + 1] : nlive;
-                const long ge = cum1 < g_hi ? cum1 : g_hi;
-                if (ge <= gq) continue;
-                const long nks = 2 * (ge - gq);  // 16-cell k-steps of this range
-                row_first = (tab[ub] + (gq - cum0)) * XW2_GRAN;
-                gq = ge;
+            int runs = 1;  // ONE pipeline run per split (the opaque count: see k_dw_x2)
+            asm volatile("" : "+s"(runs));
+            for (int run = 0; run < runs; ++run) {
+                const int nks = g_hi - g_lo;  // workgroup-uniform
                 dma_stage(0, 0);
                 dma_stage(1, 1);
                 dma_stage(2, 2);
-                for (long ks = 0;;) {  // the ring stage of a k-step is ks % 4: unrolled by 4
+                for (int ks = 0;;) {  // the ring stage of a k-step is ks % 4: unrolled by 4
                     if (ks >= nks) break;
-                    lockstep(done + (int)ks);
+                    lockstep(ks);
                     kstep(X2Int<0>{}, ks, dacc); ++ks;
                     if (ks >= nks) break;
                     kstep(X2Int<1>{}, ks, dacc); ++ks;
@@ -852,7 +1051,6 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
                     if (ks >= nks) break;
                     kstep(X2Int<3>{}, ks, dacc); ++ks;
                 }
-                done += (int)nks;
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the over-issued DMAs before the ring
                 x2_lds_barrier();                                  // is refilled / the kernel exits
             }
@@ -882,9 +1080,20 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
 #include "lab/x2_lab_dw.inc"  // k_dw_x2p (RNNT_VARIANT_X2_DW_P16): measured equal to k_dw_x2<4>, kept as lab equipment
 #endif
 
+// the dW kernel launch_dw_x2 picks for this call walks k_dw_table's 32-cell ranges, not the live k-step list (the lab's k_dw_x2p only):
+// k_dhidden_x2's skipped tiles then zero-fill every row (X3Args::zero_all)
+bool x2_dw_walks_table(int H, int V, int flags)
+{
+    (void)H; (void)V; (void)flags;
+#ifdef RNNT_LAB
+    if (flags & RNNT_VARIANT_X2_DW_P16) return true;
+#endif
+    return false;
+}
+
 void launch_dw_x2(const X3Args &a, hipStream_t st, bool build_table, bool zero_prog)
 {
-    if (build_table) launch_dw_table(a.logit_lens, a.B, a.T, a.U1, XW2_GRAN, a.dw_tab, st);
+    if (build_table && x2_dw_walks_table(a.H, a.V, a.flags)) launch_dw_table(a.logit_lens, a.B, a.T, a.U1, XW2_GRAN, a.dw_tab, st);
     if (a.dw_prog && zero_prog) launch_fill32(a.dw_prog, 0u, (size_t)a.n_split * 64, st);
     const int tiles = x2_dw_tiles(a.H, a.V);
     static bool attr_set[16] = {false};  // > 64 KiB of dynamic LDS: opt-in once per device (read-mostly fact)
@@ -968,6 +1177,7 @@ size_t x2_wpack_dh_bytes(int H, int V) { return (size_t)((H + 511) / 512) * (V /
 // ---------------------------------------------------------------------------------------
 #define XG2_BT 8
 #define XG2_BU 16
+static_assert(XG2_BT == XG2_BT_ && XG2_BU == XG2_BU_, "dHidden tile");
 #define XG2_WSLOT 32768   // one k-step of W: 2 planes x 16 tiles x 1 KiB
 #define XG2_XSLOT 8192    // one k-step of G fragments: 4 M tiles x 2 planes x 1 KiB
 #define XG2_NW 3          // W ring slots: the DMAs of k-step c+2 are issued during k-step c (as in k_joint_fwd_x2)
@@ -1006,15 +1216,38 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
     const long zrow = (long)a.B * T * U1;  // first zero padding row
     const long pcell = pexists ? ((long)b * T + pt) * U1 + pu : zrow;
 
-    // workgroup-uniform: no products past the utterance's length or in a u block past U_b (no lattice cell; the reductions
-    // skip its slabs), but k_dw_x2 must find zeros in these rows (both planes = the whole logits row)
-    if (t0 >= Tb || u0 > Ub) {
+    // workgroup-uniform dead-tile exit: no products past the utterance's length or in a u block past U_b (no lattice cell; the
+    // reductions skip its slabs), nor in a tile none of whose cells has non-null coefficients (X3Args::tile_live: every cell outside
+    // the lattice, unreachable or flushed — each would have produced G = 0).  What a dead tile still owes:
+    //  * G: the dW GEMM must find zeros in the rows it reads — the rows of LIVE 16-cell k-steps (ks_bitmap: a k-step that straddles
+    //    the tile's edge), both planes = the whole logits row.  The other rows keep their logits: nothing reads them (zero_all: the
+    //    dW kernel of this call walks whole per-utterance ranges, so every row is filled);
+    //  * slabs: a dead tile INSIDE the lengths writes zeros over its pieces of the dEnc / dPred slabs (8 + 16 rows of this pass's
+    //    columns) — the reductions (shared with the other routes) skip slabs by length only;
+    //  * the later column passes (FIRST = false) and k_dhidden_x2r take the same exit by the same flag: the tile's rows may hold logits.
+    const bool past_len = t0 >= Tb || u0 > Ub;
+    if (past_len || (a.tile_live && !a.tile_live[((long)b * gridDim.y + tt) * gridDim.x + ub])) {
         if (FIRST && pexists) {
-            const u32x4 z = {0u, 0u, 0u, 0u};
-            u32x4 *g = (u32x4 *)(a.logits + pcell * V) + half;
-            for (int c = 0; c < VC; ++c) {  // this lane's 16 B of each plane per k-step (layout below)
-                g[8 * (c >> 1) + 2 * (c & 1)] = z;
-                g[8 * (c >> 1) + 4 + 2 * (c & 1)] = z;
+            const long ks = pcell / XW2_ROWS;
+            if (a.zero_all || !a.ks_bitmap || ((a.ks_bitmap[ks >> 5] >> (ks & 31)) & 1u)) {
+                const u32x4 z = {0u, 0u, 0u, 0u};
+                u32x4 *g = (u32x4 *)(a.logits + pcell * V) + half;
+                for (int c = 0; c < VC; ++c) {  // this lane's 16 B of each plane per k-step (layout below)
+                    g[8 * (c >> 1) + 2 * (c & 1)] = z;
+                    g[8 * (c >> 1) + 4 + 2 * (c & 1)] = z;
+                }
+            }
+        }
+        if (!past_len) {
+            const int col0 = 512 * hp, nc4 = ((H - col0 < 512 ? H - col0 : 512)) / 4;  // this pass's columns, in float4s
+            const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+            for (int k = tid; k < XG2_BT * nc4; k += 256) {
+                const int t = t0 + k / nc4;
+                if (t < Tb) *(f32x4 *)(a.slab_enc + (long)ub * a.B * T * H + ((long)b * T + t) * H + col0 + 4 * (k % nc4)) = z4;
+            }
+            for (int k = tid; k < XG2_BU * nc4; k += 256) {
+                const int u = u0 + k / nc4;
+                if (u < U1) *(f32x4 *)(a.slab_pred + (long)tt * a.B * U1 * H + ((long)b * U1 + u) * H + col0 + 4 * (k % nc4)) = z4;
             }
         }
         return;
@@ -1371,7 +1604,25 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2r(X3Args a, const int hp)
     const int tt = 4 * tq + wave, t0 = tt * XG2_BT;  // this wave's t block
     const int VC = V / 16;
     if (4 * tq * XG2_BT >= Tb || u0 > Ub) return;    // workgroup-uniform: no lattice cell in any of the four blocks
-    const bool wlive = t0 < Tb;                        // wave-uniform: this wave's block has lattice cells (else: zeros in, nothing out)
+    const bool winlen = t0 < Tb;                       // wave-uniform: this wave's block lies inside the lengths (else: zeros in, nothing out)
+    // k_dhidden_x2's dead-tile rule: a block without a live cell (X3Args::tile_live) was skipped by the first pass — its rows may hold
+    // logits — so it reads the zero padding row and owes the slabs zeros for this pass's columns
+    const bool wlive = winlen && (!a.tile_live || a.tile_live[((long)b * ((T + XG2_BT - 1) / XG2_BT) + tt) * gridDim.x + ub] != 0);
+    const int any_live = __syncthreads_or(wlive ? 1 : 0);
+    auto zero_slabs = [&]() {
+        const int colz = 512 * hp + 4 * i;
+        if (colz >= H) return;
+        const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+        if (half == 0)
+            for (int k = 0; k < XG2_BT; ++k)
+                if (t0 + k < Tb) *(f32x4 *)(a.slab_enc + (long)ub * a.B * T * H + ((long)b * T + t0 + k) * H + colz) = z4;
+        for (int k = half; k < XG2_BU; k += 2)
+            if (u0 + k < U1) *(f32x4 *)(a.slab_pred + (long)tt * a.B * U1 * H + ((long)b * U1 + u0 + k) * H + colz) = z4;
+    };
+    if (!any_live) {  // workgroup-uniform: none of the four blocks has a live cell
+        if (winlen) zero_slabs();
+        return;
+    }
     const long zrow = (long)a.B * T * U1;              // first zero padding row
     // row i of M tile m = cell (t0 + 2m + (i >> 4), u0 + (i & 15)); rows outside the lattice read the zero padding row.  G's planes of
     // k-step c: hi = 16 bytes at u32x4 index 8 (c >> 1) + 2 (c & 1) + half of the row, mid 64 bytes behind (k_dhidden_x2's layout)
@@ -1464,7 +1715,10 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2r(X3Args a, const int hp)
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the over-issued loads / DMAs: none may land in an LDS the next workgroup owns
-    if (!wlive) return;
+    if (!wlive) {
+        if (winlen) zero_slabs();
+        return;
+    }
 
     // ---- epilogue (k_dhidden_x2's, one wave = one block).  Accumulator register rr = 8 rh + r7 of M tile m, column tile n: t row
     // 2m + rh, u slot 8 (r7 >> 2) + (r7 & 3) + 4 half; column 512 hp + 4i + n.
@@ -2220,7 +2474,8 @@ __global__ __launch_bounds__(256) void k_x2_absmax(X2AbsArgs a, float *__restric
 // i = 0 .. n-1, from the partial maxima; the call's counter words zeroed (the forward's tile counter; dW's progress words) and dW's table written
 // (k_dw_table's format, B = 1, every granule live) — what four more launches did before
 __global__ __launch_bounds__(256) void k_x2_lin_scales(const float *__restrict__ partial, float *__restrict__ scales, int n, unsigned *__restrict__ zero0,
-                                                       int nzero0, unsigned *__restrict__ zero1, int nzero1, long *__restrict__ tab, long ngran)
+                                                       int nzero0, unsigned *__restrict__ zero1, int nzero1, long *__restrict__ tab, long ngran,
+                                                       int *__restrict__ list, int *__restrict__ stats)
 {
     __shared__ float s_m[4];
     for (int i = 0; i < n; ++i) {
@@ -2250,6 +2505,11 @@ __global__ __launch_bounds__(256) void k_x2_lin_scales(const float *__restrict__
     for (int j = threadIdx.x; j < nzero0; j += 256) zero0[j] = 0u;
     for (int j = threadIdx.x; j < nzero1; j += 256) zero1[j] = 0u;
     if (tab && threadIdx.x == 0) { tab[0] = 0; tab[1] = ngran; tab[2] = 0; tab[3] = ngran; }
+    if (list) {  // k_dw_x2's live k-step list: every 16-row k-step, then the padding entries (launch_x2_live's format)
+        const long nks = 2 * ngran;
+        for (long j = threadIdx.x; j < nks + 8; j += 256) list[j] = (int)(j < nks ? j : nks);
+        if (threadIdx.x == 0) { stats[0] = (int)nks; stats[1] = (int)nks; stats[2] = 0; stats[3] = 0; }
+    }
 }
 // rows of a row-major fp32 matrix -> s x as two fp16 planes.  INTER: the planes interleaved per 32-column chunk, [32 x hi | 32 x mid] over the
 // chunk's 128 bytes (the G operand's layout: one thread = one chunk); else two separate planes `plane_stride` elements apart (the hidden
@@ -2308,7 +2568,7 @@ __global__ __launch_bounds__(256) void k_x2_reduce_scaled(const float *__restric
 }
 
 namespace {
-struct LinWs { size_t wt, pack, pa, pb, slab_w, slab_b, prog, total; long rows_pad, rows_alloc; int n_split; };
+struct LinWs { size_t wt, pack, pa, pb, slab_w, slab_b, prog, list, total; long rows_pad, rows_alloc; int n_split; };
 LinWs lin_layout(int M, int K, int N, bool bwd)
 {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -2329,6 +2589,7 @@ LinWs lin_layout(int M, int K, int N, bool bwd)
     L.slab_w = o; o += al((size_t)L.n_split * N * K * 4);
     L.slab_b = o; o += al((size_t)L.n_split * N * 4);
     L.prog = o; o += al((size_t)L.n_split * 64);
+    L.list = o; o += al(64 + (size_t)(L.rows_pad / XW2_ROWS + 8) * 4);  // 4 count words, then the k-step list
     L.total = o;
     return L;
 }
@@ -2346,13 +2607,14 @@ int lin_cus()
 }
 // the operand scales of a call: one launch for the maxima of its n tensors, one for the scales (+ the counter words and dW's table)
 struct LinT { const float *x; long ld, rows; int cols; };
-void lin_scales(const LinT *t, int n, char *w, unsigned *zero1, int nzero1, long *tab, long ngran, hipStream_t st)
+void lin_scales(const LinT *t, int n, char *w, unsigned *zero1, int nzero1, long *tab, long ngran, int *list, hipStream_t st)
 {
     X2AbsArgs a{};
     for (int i = 0; i < n; ++i) { a.x[i] = t[i].x; a.ld[i] = t[i].ld; a.rows[i] = t[i].rows; a.cols4[i] = t[i].cols / 4; }
     float *partial = (float *)(w + 1024);
     hipLaunchKernelGGL(k_x2_absmax, dim3(256, n), dim3(256), 0, st, a, partial);
-    hipLaunchKernelGGL(k_x2_lin_scales, dim3(1), dim3(256), 0, st, partial, (float *)w, n, (unsigned *)(w + 128), 16, zero1, nzero1, tab, ngran);
+    hipLaunchKernelGGL(k_x2_lin_scales, dim3(1), dim3(256), 0, st, partial, (float *)w, n, (unsigned *)(w + 128), 16, zero1, nzero1, tab, ngran,
+                       list ? list + 16 : nullptr, list);
 }
 // y[M,N] = x[M,K] wmat[N,K]^T (+ bias) through k_joint_fwd_x2<2>; scales = {s_W, 1/s_W, s_X, 1/s_X} on the device, the pack made here
 void lin_gemm_nt(const float *x, long ldx, const float *wmat, const float *bias, int M, int K, int N, float *y, const float *scales, void *pack,
@@ -2377,7 +2639,7 @@ void launch_linear_x2_fwd(const float *x, long ldx, const float *W, const float 
     char *w = (char *)ws;
     float *scales = (float *)w;
     const LinT t[2] = {{W, K, N, K}, {x, ldx, M, K}};
-    lin_scales(t, 2, w, nullptr, 0, nullptr, 0, st);
+    lin_scales(t, 2, w, nullptr, 0, nullptr, 0, nullptr, st);
     lin_gemm_nt(x, ldx, W, bias, M, K, N, y, scales, w + L.pack, (unsigned *)(w + 128), st);
 }
 
@@ -2389,7 +2651,7 @@ void launch_linear_x2_bwd(const float *x, long ldx, const float *W, const float 
     float *scales = (float *)w;             // {s_W, 1/s_W, s_dy, 1/s_dy, s_x, 1/s_x}
     long *tab = (long *)(w + 192);
     const LinT t[3] = {{W, K, N, K}, {dy, N, M, N}, {x, ldx, M, K}};
-    lin_scales(t, 3, w, (unsigned *)(w + L.prog), L.n_split * 16, tab, L.rows_pad / XW2_GRAN, st);
+    lin_scales(t, 3, w, (unsigned *)(w + L.prog), L.n_split * 16, tab, L.rows_pad / XW2_GRAN, (int *)(w + L.list), st);
     if (dx) {  // dx[M,K] = dy[M,N] (W^T)[K,N]^T
         float *wt = (float *)(w + L.wt);
         launch_copy_enc(W, 0, 1, K, wt, 1, K, N, st);  // wt[k][n] = W[n][k]
@@ -2409,7 +2671,8 @@ void launch_linear_x2_bwd(const float *x, long ldx, const float *W, const float 
     a.logits = pa; a.hidden = pb; a.plane_stride = L.rows_alloc * (long)K; a.rows_pad = L.rows_pad; a.rows_alloc = L.rows_alloc;
     a.B = 1; a.T = 1; a.U1 = 1; a.H = K; a.V = N; a.n_split = L.n_split; a.dw_tab = tab; a.dw_prog = (int *)(w + L.prog);
     a.slab_w = (float *)(w + L.slab_w); a.slab_b = (float *)(w + L.slab_b); a.dw_rescale = 1.0f; a.db_rescale = 1.0f; a.n_cu = lin_cus();
-    launch_dw_x2(a, st, false, false);  // (no table kernel, no progress-word fill: both done by k_x2_lin_scales)
+    a.live_stats = (int *)(w + L.list); a.ks_list = a.live_stats + 16;
+    launch_dw_x2(a, st, false, false);  // (no table / list kernels, no progress-word fill: all done by k_x2_lin_scales)
     const long n4w = (long)N * K / 4, n4b = N / 4;
     hipLaunchKernelGGL(k_x2_reduce_scaled, dim3((unsigned)((n4w + 255) / 256)), dim3(256), 0, st, a.slab_w, dW, n4w, n4w, L.n_split,
                        (const float *)(scales + 3), (const float *)(scales + 5));

@@ -144,6 +144,7 @@ VARIANT_SEPARATE_G = 32
 VARIANT_SEPARATE_HIDDEN = 64
 VARIANT_FWD_LDS_RING = 128
 VARIANT_FWD_ONE_WG_PER_TILE = 256
+VARIANT_X2_NO_FLUSH_SKIP = 512  # f16x2 route: no cell flushed (costs / grad_enc / grad_pred bit-identical; grad_W / grad_bias: summation order)
 VARIANT_X3_FP32_FWD = 4096  # bf16x3 route: this stage on the fp32 route's kernel (isolation checks; not bit-identical)
 VARIANT_X3_FP32_DH = 8192
 # kernels of the diagnostic library only (rnnt_amd/csrc/lab/rnnt_engine_lab.h; tools/build_lab.sh): librnnt_engine.so refuses these bits
@@ -164,7 +165,7 @@ class WsLayout(ctypes.Structure):
         "logits", "hidden", "denom_s", "lpb_s", "lpe_s", "alpha_s", "beta_s", "coef", "wpack",
         "enc_copy", "slab_enc", "slab_pred", "slab_w", "slab_b", "counters", "total", "rows_pad")] + [
         (n, ctypes.c_int) for n in ("n_ublk", "n_ttile", "n_split", "D")] + [
-        (n, ctypes.c_size_t) for n in ("g_lo", "aux", "aux_bytes", "ep")]
+        (n, ctypes.c_size_t) for n in ("g_lo", "aux", "aux_bytes", "ep", "x2_live")]
 
 
 def build(force: bool = False) -> str:
@@ -296,6 +297,16 @@ def layout(B, T, U1, H, V, dtype="fp32"):
     L = WsLayout()
     _check(lib().rnnt_engine_workspace_layout(B, T, U1, H, V, dtype_code(dtype), ctypes.byref(L)))
     return L
+
+
+def x2_live_counts(device, B, T, U1, H, V):
+    """Device-side counts of the last f16x2 fused call of these dims on the current stream (rnnt_engine_ws_layout.x2_live):
+    dict(live_ksteps, ksteps, live_tiles, tiles) — the 16-cell dW k-steps the call walked of those that hold a cell, the
+    dHidden tiles (8 t x 16 u) it ran of all.  Synchronises."""
+    L = layout(B, T, U1, H, V, "f16x2")
+    ws = workspace(device, L.total)
+    c = ws[L.x2_live:L.x2_live + 16].view(torch.int32).cpu().tolist()
+    return dict(live_ksteps=c[0], ksteps=c[1], live_tiles=c[2], tiles=c[3])
 
 
 def workspace_bytes(B, T, U1, H, V, dtype="fp32"):
