@@ -467,6 +467,33 @@ int rnnt_engine_beam_decode(const void *frames, int64_t frame_stride, int T, con
                             int32_t *tokens, double *scores, void *workspace, size_t ws_bytes, void *stream);
 
 /*
+ * The same search for n_utt INDEPENDENT utterances of one model, advanced in lockstep (DESIGN.md §4h "Batched"): every round's
+ * kernels carry the utterance as a grid dimension, a search that has ended costs nothing more, and the result of each utterance is
+ * bit-identical to rnnt_engine_beam_decode of it alone, whatever its neighbours and its position.  Arguments as
+ * rnnt_engine_beam_decode, with
+ *   frames: the utterances' frames packed into `rows` rows (frame_stride apart);
+ *   utt    device int32[n_utt][2]: utterance u's first row and its frame count T_u >= 1 (rows the table names beyond `rows` are
+ *          read as the last row: the caller vouches for `rows`, never for the table);
+ *   max_frames: the largest T_u — `iterations` = 0 enqueues the bound max_frames * max_per_frame + 1.  The table lives on the
+ *          device, so it is NOT checked against max_frames: an entry above it can leave that search unfinished after the bound
+ *          (state[u][3] == 0) — `host_flag` then never rises and the call has still returned RNNT_OK; the caller sees it in
+ *          state[u][3] after its synchronisation;
+ *   state  int32[n_utt][32], tokens int32[n_utt][beam][max_length], scores double[n_utt][beam]: per utterance as above.
+ * beam, max_length, max_per_frame and blank are shared.  `host_flag` is set once ALL searches have ended.  The same iterations /
+ * init protocol; the workspace's state part (n_utt times the single search's, and a counter) is zero-filled at init.
+ * 1 <= n_utt <= 64 (RNNT_ERR_UNSUPPORTED otherwise, from the query and the call); every other limit as rnnt_engine_beam_decode.
+ * Every argument is checked before anything is enqueued.
+ */
+int rnnt_engine_beam_decode_batch_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int beam, int n_utt,
+                                                  size_t *out);
+int rnnt_engine_beam_decode_batch(const void *frames, int64_t frame_stride, int rows, const int32_t *utt, int n_utt, int max_frames,
+                                  const rnnt_conv_predictor_params *p, int S, int E, int O, float ln_in_eps, float ln_out_eps,
+                                  const void *text_W, const void *text_b, const void *W, const void *bias, int H, int V, int blank,
+                                  int max_length, int max_per_frame, int beam, const void *tables, int iterations, int init,
+                                  int32_t *host_flag, int32_t *state, int32_t *tokens, double *scores, void *workspace, size_t ws_bytes,
+                                  void *stream);
+
+/*
  * y = x W^T + b and its backward as MFMA kernels: the joint's optional input projections
  * audio_ln / text_ln (next-step row SURVEY.md 8f-1; reference rnnt/joint.py:8-12,26-30).
  * x [M,K] with rows ldx floats apart, W [N,K] (torch.nn.Linear layout), y / dy [M,N] contiguous.

@@ -1,4 +1,5 @@
-// beam.hip — frame-synchronous beam search of ONE utterance on the device (rnnt_engine_beam_decode).
+// beam.hip — frame-synchronous beam search on the device: ONE utterance (rnnt_engine_beam_decode) or N independent ones advanced in
+// lockstep by the same rounds (rnnt_engine_beam_decode_batch); DESIGN.md §4h.
 //
 // The search (exact definition: DESIGN.md §4h, tests/beam_oracle.py): at most `m` labels per frame, hypotheses merged by
 // token sequence; beam 1 is the reference's greedy decode (rnnt/model.py:95-128).  Per frame t, rounds r = 0 .. m-1: every
@@ -22,6 +23,12 @@
 //                  `beam`, the cap, max_length, t / round / done, the next slot buffer (tokens, lengths, scores, text vectors)
 // The predictor kernels return at once in rounds where no slot took a label (round 0 of a frame after a blank-only one),
 // every kernel once the search is over.  Nothing spins; no workgroup waits for another.
+// The batched search: every kernel is a template over a trailing argument pack `U... ub` — EMPTY for the single search, whose
+// instantiation has exactly the arguments and the body it had before there was a batch (u = 0 and a zero stride fold away), one
+// BeamBatch for the batched search, where the utterance is grid.y.  Everything a search owns — its slot buffers, intermediates,
+// logits, state, results — lies `stride` bytes (its own size) after its neighbour's, the weights and tables are shared, and a
+// workgroup of utterance u does exactly what the single search's workgroup does, on u's block.  A done search's workgroups return
+// at once; the last one to finish raises the host's flag (a device-scope counter, k_beam_select).
 // Arithmetic: fp32 products (fp32 MFMA, exact fp32 as fmaf chains), log-sum-exp in fp32, SCORES in fp64 (the log-probability
 // (double)logit - (double)lse is added to a double score; logaddexp in double).
 // Ties (no result may depend on one): finished entries first, then parent slot ascending, then token id ascending; the
@@ -40,6 +47,19 @@ enum { BS_T = 0, BS_R = 1, BS_N = 2, BS_DONE = 3, BS_NEW = 4, BS_ROUNDS = 5, BS_
 // slot status
 enum { SL_EMPTY = 0, SL_ACTIVE = 1, SL_FINISHED = 2 };
 
+// the batched search's arguments (the kernels' trailing pack)
+struct BeamBatch {
+    size_t stride;        // bytes from one utterance's block of the workspace to the next
+    const int32_t *utt;   // [N][2]: the utterance's first row of the packed frames, its frame count
+    int rows;             // rows of the packed frames (row indices are kept below it)
+    unsigned *n_done;     // zeroed device word: searches that have ended
+};
+__device__ __forceinline__ BeamBatch beam_batch() { return BeamBatch{0, nullptr, 0, nullptr}; }  // the single search
+__device__ __forceinline__ BeamBatch beam_batch(const BeamBatch &b) { return b; }
+#define BEAM_UTT(ub) const BeamBatch B = beam_batch(ub...); const unsigned u = sizeof...(U) ? blockIdx.y : 0u; const size_t uoff = u * B.stride
+// utterance u's copy of a per-search buffer, `off` = u * stride bytes on (0 for the single search)
+template <typename T> __device__ __forceinline__ T *beam_utt(T *p, size_t off) { return (T *)((char *)p + off); }
+
 struct BeamSlots {
     double *score;               // [2][BM]
     unsigned long long *hash;    // [2][BM]  hash of the token sequence (pre-filter of the merges)
@@ -47,6 +67,13 @@ struct BeamSlots {
     int *tok;                    // [2][BM][max_length]: tok[.][.][0] = blank, [1 .. len] the labels
     float *pvec;                 // [2][BM][H]: the joint's text input of the slot's sequence (after text_ln / LayerNorm)
 };
+__device__ __forceinline__ BeamSlots beam_utt(BeamSlots P, size_t stride)
+{
+    P.score = beam_utt(P.score, stride); P.hash = beam_utt(P.hash, stride); P.len = beam_utt(P.len, stride);
+    P.status = beam_utt(P.status, stride); P.need = beam_utt(P.need, stride); P.tok = beam_utt(P.tok, stride);
+    P.pvec = beam_utt(P.pvec, stride);
+    return P;
+}
 
 __device__ __forceinline__ float beam_gelu(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 
@@ -71,9 +98,11 @@ __device__ __forceinline__ float beam_block_sum(float v, float *red)  // 256 thr
 
 // ---- start of a search: slot 0 of buffer 0 = the empty hypothesis (score 0, text vector to compute), everything else empty
 // (the workspace was zero-filled by the launcher: no value of a previous call, or of the caller's memory, is ever read)
-__global__ void k_beam_init(BeamSlots P, int32_t *state, int blank, int max_length)
+template <typename... U> __global__ void k_beam_init(BeamSlots P, int32_t *state, int blank, int max_length, U... ub)
 {
     if (threadIdx.x != 0) return;
+    BEAM_UTT(ub);
+    P = beam_utt(P, uoff); state += 32 * u;
     P.status[0] = SL_ACTIVE; P.need[0] = 1; P.len[0] = 0; P.score[0] = 0.0; P.hash[0] = 0ull;
     P.tok[0] = blank;
     for (int i = 0; i < 32; ++i) state[i] = 0;
@@ -83,10 +112,14 @@ __global__ void k_beam_init(BeamSlots P, int32_t *state, int blank, int max_leng
 // ---- conv1 outputs of positions p-4 .. p of every slot awaiting its predictor step (p = len: the newest token), as
 // g1[slot][q][E], q = 0 .. 4 (zero rows before position 0 = conv2's left padding):
 //   g1[pos] = gelu(b1 + A2[tok pos] + A1[tok pos-1] + A0[tok pos-2])      (rnnt/predictor.py:214-219, eval mode)
+template <typename... U>
 __global__ __launch_bounds__(256) void k_beam_conv1(const int32_t *__restrict__ state, BeamSlots P, int max_length, int S, int E,
-                                                    const float *__restrict__ tab, const float *__restrict__ b1, float *__restrict__ g1)
+                                                    const float *__restrict__ tab, const float *__restrict__ b1, float *__restrict__ g1, U... ub)
 {
+    BEAM_UTT(ub);
+    state += 32 * u;
     if (state[BS_DONE] || !state[BS_NEW]) return;
+    P = beam_utt(P, uoff); g1 = beam_utt(g1, uoff);
     const int cur = state[BS_CUR], j = blockIdx.x;
     if (!P.need[cur * BM + j]) return;
     const int p = P.len[cur * BM + j];
@@ -118,17 +151,20 @@ __global__ __launch_bounds__(256) void k_beam_conv1(const int32_t *__restrict__ 
 // of `X` (Kin = taps * Kin features), normalised by the workgroup itself.  A workgroup: 16 outputs, its 4 waves split the
 // reduction (16 k per chunk: a float4 per lane and operand -> 4 MFMAs, the k order inside the chunk permuted alike for both),
 // partial tiles meet in LDS.  `masked`: only rows of slots awaiting their predictor step are written, into the CURRENT
-// buffer (Y + cur * y_par).  Kin % 4 == 0, ldx % 4 == 0.
-template <bool LNIN>
+// buffer (Y + cur * y_par).  Kin % 4 == 0, ldx % 4 == 0.  state, need, X and Y are the utterance's.
+template <bool LNIN, typename... U>
 __global__ __launch_bounds__(256) void k_beam_gemm16(const int32_t *__restrict__ state, const int *__restrict__ need,
                                                      const float *__restrict__ X, int ldx, const float *__restrict__ W, int taps, int Kin,
                                                      int N, const float *__restrict__ bias, int act, const float *__restrict__ gamma,
                                                      const float *__restrict__ beta, float eps, float *__restrict__ Y, int ldy,
-                                                     long y_par, int masked)
+                                                     long y_par, int masked, U... ub)
 {
     __shared__ float s_acc[4][16][17];
     __shared__ float s_mean[16], s_rstd[16];
+    BEAM_UTT(ub);
+    state += 32 * u;
     if (state[BS_DONE] || !state[BS_NEW]) return;
+    need = beam_utt(need, uoff); X = beam_utt(X, uoff); Y = beam_utt(Y, uoff);
     const int cur = state[BS_CUR];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
     const int n0 = blockIdx.x * 16, ncol = min(n0 + r, N - 1);
@@ -178,12 +214,16 @@ __global__ __launch_bounds__(256) void k_beam_gemm16(const int32_t *__restrict__
 }
 
 // ---- the predictor's output LayerNorm (rnnt/predictor.py:229) as the joint's text vector when the joint has no text_ln
+template <typename... U>
 __global__ __launch_bounds__(256) void k_beam_ln16(const int32_t *__restrict__ state, const int *__restrict__ need, const float *__restrict__ z,
                                                    int O, const float *__restrict__ gamma, const float *__restrict__ beta, float eps,
-                                                   float *__restrict__ pvec)
+                                                   float *__restrict__ pvec, U... ub)
 {
     __shared__ float red[4];
+    BEAM_UTT(ub);
+    state += 32 * u;
     if (state[BS_DONE] || !state[BS_NEW]) return;
+    need = beam_utt(need, uoff); z = beam_utt(z, uoff); pvec = beam_utt(pvec, uoff);
     const int cur = state[BS_CUR], j = blockIdx.x;
     if (!need[cur * BM + j]) return;
     const float *x = z + (size_t)j * O;
@@ -199,14 +239,20 @@ __global__ __launch_bounds__(256) void k_beam_ln16(const int32_t *__restrict__ s
 
 // ---- logits[slot][v] = tanh(frame_t + pvec[slot]) . W[v] + bias[v] for all 16 slots, 16 vocabulary entries per workgroup
 // (rnnt/joint.py:44-55 after the projections).  The hidden operand is built in registers: lane (slot r, k group g) takes
-// tanh of its own sums, each element once per workgroup.  H % 4 == 0.
+// tanh of its own sums, each element once per workgroup.  H % 4 == 0.  Batched search: frame t of the utterance is row
+// utt[u][0] + t of the packed `frames`, kept inside the `rows` rows the caller vouched for.
+template <typename... U>
 __global__ __launch_bounds__(256) void k_beam_joint(const int32_t *__restrict__ state, const float *__restrict__ frames, long fstride,
                                                     const float *__restrict__ pvec, const float *__restrict__ W, const float *__restrict__ bias,
-                                                    int H, int V, float *__restrict__ logits)
+                                                    int H, int V, float *__restrict__ logits, U... ub)
 {
     __shared__ float s_acc[4][16][17];
+    BEAM_UTT(ub);
+    state += 32 * u;
     if (state[BS_DONE]) return;
-    const int t = state[BS_T], cur = state[BS_CUR];
+    pvec = beam_utt(pvec, uoff); logits = beam_utt(logits, uoff);
+    const int cur = state[BS_CUR];
+    const int t = sizeof...(U) ? max(0, min(B.utt[2 * u] + state[BS_T], B.rows - 1)) : state[BS_T];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
     const int v0 = blockIdx.x * 16, vcol = min(v0 + r, V - 1);
     const float *f = frames + (size_t)t * fstride, *pv = pvec + ((size_t)cur * BM + r) * H, *wr = W + (size_t)vcol * H;
@@ -248,12 +294,17 @@ __device__ __forceinline__ void beam_wave_best(float &v, int &id)
 // ---- per active slot (a workgroup of 16 waves each): log-sum-exp of the V logits, the blank logit and the `beam` best
 // non-blank labels.  Waves walk 256-entry chunks, merging each into a running list of `beam` entries (lane q holds entry q)
 // by `beam` wave-wide extractions; wave 0 merges the 16 lists the same way.
+template <typename... U>
 __global__ __launch_bounds__(1024) void k_beam_reduce(const int32_t *__restrict__ state, const int *__restrict__ status,
-                                                      const float *__restrict__ logits, int V, int blank, int beam, float *__restrict__ red)
+                                                      const float *__restrict__ logits, int V, int blank, int beam, float *__restrict__ red,
+                                                      U... ub)
 {
     __shared__ float s_v[16][BM], s_m[16], s_s[16];
     __shared__ int s_i[16][BM];
+    BEAM_UTT(ub);
+    state += 32 * u;
     if (state[BS_DONE]) return;
+    status = beam_utt(status, uoff); logits = beam_utt(logits, uoff); red = beam_utt(red, uoff);
     const int cur = state[BS_CUR], j = blockIdx.x;
     if (status[cur * BM + j] != SL_ACTIVE) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -359,10 +410,13 @@ __device__ bool beam_same_prefix(const int *a, const int *b, int len)  // positi
     return true;
 }
 
-// ---- one workgroup: the selection of the round and the search's bookkeeping
+// ---- one workgroup per utterance: the selection of the round and the search's bookkeeping.  Batched search
+// (T then unused: the utterance's frame count is utt[u][1]): the search that ends counts itself in `n_done` and the one that
+// brings it to the n_utt = gridDim.y searches raises the host's flag.
+template <typename... U>
 __global__ __launch_bounds__(256) void k_beam_select(BeamSlots P, const float *__restrict__ red, int beam, int V, int H, int T, int max_length,
                                                      int max_per_frame, int32_t *__restrict__ state, int32_t *__restrict__ out_tokens,
-                                                     double *__restrict__ out_scores, int32_t *host_flag)
+                                                     double *__restrict__ out_scores, int32_t *host_flag, U... ub)
 {
     __shared__ double c_score[BEAM_NC];
     __shared__ int c_kind[BEAM_NC], c_a[BEAM_NC], c_b[BEAM_NC], c_src[BEAM_NC];
@@ -371,7 +425,12 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamSlots P, const float *_
     __shared__ unsigned long long o_hash[BM];
     __shared__ int o_len[BM], o_st[BM], s_bmatch[BM], s_keep[BM], s_final[BM];
     __shared__ int s_nfinal, s_frame_end, s_done;
+    BEAM_UTT(ub);
+    state += 32 * u;
     if (state[BS_DONE]) return;
+    P = beam_utt(P, uoff); red = beam_utt(red, uoff);
+    out_tokens += (size_t)u * beam * max_length; out_scores += (size_t)u * beam;
+    if (sizeof...(U)) T = B.utt[2 * u + 1];
     const int tid = threadIdx.x, cur = state[BS_CUR], nb = cur ^ 1, r = state[BS_R];
     const int *tok_old = P.tok + (size_t)cur * BM * max_length;
     if (tid < BM) {
@@ -519,13 +578,15 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamSlots P, const float *_
         state[BS_CUR] = nb;
         state[BS_DONE] = done;
         // the host's cue to stop enqueueing rounds (mapped pinned memory, polled without a synchronisation)
-        if (done && host_flag) __hip_atomic_store(host_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        const bool all_done = done && (!sizeof...(U) || atomicAdd(B.n_done, 1u) + 1 == gridDim.y);
+        if (all_done && host_flag) __hip_atomic_store(host_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
-// ---- workspace: slot buffers | predictor intermediates | logits | reduce output | the model's tables (when built here)
-struct BeamLayout { size_t score, hash, len, status, need, tok, pvec, g1, g2, z, logits, red, state_end, tables, total; };
-static BeamLayout beam_layout(int S, int E, int O, int H, int V, int has_text, int max_length)
+// ---- workspace: per utterance { slot buffers | predictor intermediates | logits | reduce output }, `block` bytes each; then the
+// batched search's done counter and the model's tables (when built here)
+struct BeamLayout { size_t score, hash, len, status, need, tok, pvec, g1, g2, z, logits, red, block, n_done, state_end, tables, total; };
+static BeamLayout beam_layout(int S, int E, int O, int H, int V, int has_text, int max_length, int n_utt, bool batched)
 {
     BeamLayout L;
     size_t o = 0;
@@ -542,6 +603,9 @@ static BeamLayout beam_layout(int S, int E, int O, int H, int V, int has_text, i
     L.z = take((size_t)BM * O * 4);
     L.logits = take((size_t)BM * V * 4);
     L.red = take((size_t)BM * BEAM_RED * 4);
+    L.block = o;
+    o *= (size_t)n_utt;
+    L.n_done = take(batched ? 4 : 0);
     L.state_end = o;
     L.tables = take(dec_tables_floats(S, E, O, H, has_text) * 4);
     L.total = o;
@@ -549,14 +613,21 @@ static BeamLayout beam_layout(int S, int E, int O, int H, int V, int has_text, i
 }
 size_t beam_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length)
 {
-    return beam_layout(S, E, O, H, V, has_text, max_length).total;
+    return beam_layout(S, E, O, H, V, has_text, max_length, 1, false).total;
+}
+size_t beam_batch_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int n_utt)
+{
+    return beam_layout(S, E, O, H, V, has_text, max_length, n_utt, true).total;
 }
 
+// the single search (ba.utt == NULL: one utterance of a.T frames) and the batched one (ba.n_utt utterances, rows of a.frames by ba.utt)
 void launch_beam_decode(const BeamArgs &ba, hipStream_t st)
 {
     const DecLoopArgs &a = ba.d;
     const int S = a.S, E = a.E, O = a.O, H = a.H, V = a.V, ML = a.max_length, has_text = a.text_W ? 1 : 0;
-    const BeamLayout L = beam_layout(S, E, O, H, V, has_text, ML);
+    const bool batched = ba.utt != nullptr;
+    const unsigned N = batched ? ba.n_utt : 1;
+    const BeamLayout L = beam_layout(S, E, O, H, V, has_text, ML, N, batched);
     char *ws = (char *)a.workspace;
     BeamSlots P;
     P.score = (double *)(ws + L.score); P.hash = (unsigned long long *)(ws + L.hash);
@@ -565,10 +636,7 @@ void launch_beam_decode(const BeamArgs &ba, hipStream_t st)
     float *g1 = (float *)(ws + L.g1), *g2 = (float *)(ws + L.g2), *z = (float *)(ws + L.z);
     float *logits = (float *)(ws + L.logits), *red = (float *)(ws + L.red);
     const float *tb = (const float *)a.tables;
-    if (a.init) {
-        launch_fill32(ws, 0u, L.state_end, st);
-        hipLaunchKernelGGL(k_beam_init, dim3(1), dim3(64), 0, st, P, a.state, a.blank, ML);
-    }
+    if (a.init) launch_fill32(ws, 0u, L.state_end, st);
     if (!tb) {  // (rebuilt on every call that brings none: a function of the parameters only)
         launch_dec_build_tables(a.p, S, E, O, a.ln_in_eps, a.text_W, a.text_b, H, (float *)(ws + L.tables), st);
         tb = (const float *)(ws + L.tables);
@@ -577,24 +645,36 @@ void launch_beam_decode(const BeamArgs &ba, hipStream_t st)
     dec_tables_offsets(S, E, O, H, has_text, &otab, &owp2);
     const float *tab = tb + otab, *wp2 = tb + owp2;
     const float *nul = nullptr;
-    for (int it = 0; it < a.iterations; ++it) {
-        hipLaunchKernelGGL(k_beam_conv1, dim3(BM), dim3(256), 0, st, a.state, P, ML, S, E, tab, a.p.conv1_b, g1);
-        // g2 = gelu(conv2(g1[p-4 .. p]))                                                  rnnt/predictor.py:222-223
-        hipLaunchKernelGGL(k_beam_gemm16<false>, dim3((E + 15) / 16), dim3(256), 0, st, a.state, P.need, g1, 5 * E, wp2, 5, E, E,
-                           a.p.conv2_b, 1, nul, nul, 0.f, g2, E, 0L, 0);
-        // z = linear(g2)                                                                  rnnt/predictor.py:228
-        hipLaunchKernelGGL(k_beam_gemm16<false>, dim3((O + 15) / 16), dim3(256), 0, st, a.state, P.need, g2, E, a.p.linear_w, 1, E, O,
-                           a.p.linear_b, 0, nul, nul, 0.f, z, O, 0L, 0);
-        // the slot's text vector: text_ln(LN(z)) (rnnt/joint.py:28-30) or LN(z) itself         rnnt/predictor.py:229
-        if (has_text)
-            hipLaunchKernelGGL(k_beam_gemm16<true>, dim3((H + 15) / 16), dim3(256), 0, st, a.state, P.need, z, O, a.text_W, 1, O, H,
-                               a.text_b, 0, a.p.ln_out_w, a.p.ln_out_b, a.ln_eps, P.pvec, H, (long)BM * H, 1);
-        else
-            hipLaunchKernelGGL(k_beam_ln16, dim3(BM), dim3(256), 0, st, a.state, P.need, z, O, a.p.ln_out_w, a.p.ln_out_b, a.ln_eps, P.pvec);
-        hipLaunchKernelGGL(k_beam_joint, dim3((V + 15) / 16), dim3(256), 0, st, a.state, a.frames, a.frame_stride, P.pvec, a.W, a.bias, H, V,
-                           logits);
-        hipLaunchKernelGGL(k_beam_reduce, dim3(ba.beam), dim3(1024), 0, st, a.state, P.status, logits, V, a.blank, ba.beam, red);
-        hipLaunchKernelGGL(k_beam_select, dim3(1), dim3(256), 0, st, P, red, ba.beam, V, H, a.T, ML, a.max_per_frame, a.state, a.tokens,
-                           ba.scores, a.host_flag);
-    }
+    // `ub`: nothing (the single search's kernels) or the batch's BeamBatch
+    auto enqueue = [&](auto... ub) {
+        if (a.init) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_init<decltype(ub)...>), dim3(1, N), dim3(64), 0, st, P, a.state, a.blank, ML, ub...);
+        for (int it = 0; it < a.iterations; ++it) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_conv1<decltype(ub)...>), dim3(BM, N), dim3(256), 0, st, a.state, P, ML, S, E, tab,
+                               a.p.conv1_b, g1, ub...);
+            // g2 = gelu(conv2(g1[p-4 .. p]))                                                  rnnt/predictor.py:222-223
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_gemm16<false, decltype(ub)...>), dim3((E + 15) / 16, N), dim3(256), 0, st, a.state, P.need,
+                               g1, 5 * E, wp2, 5, E, E, a.p.conv2_b, 1, nul, nul, 0.f, g2, E, 0L, 0, ub...);
+            // z = linear(g2)                                                                  rnnt/predictor.py:228
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_gemm16<false, decltype(ub)...>), dim3((O + 15) / 16, N), dim3(256), 0, st, a.state, P.need,
+                               g2, E, a.p.linear_w, 1, E, O, a.p.linear_b, 0, nul, nul, 0.f, z, O, 0L, 0, ub...);
+            // the slot's text vector: text_ln(LN(z)) (rnnt/joint.py:28-30) or LN(z) itself         rnnt/predictor.py:229
+            if (has_text)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_gemm16<true, decltype(ub)...>), dim3((H + 15) / 16, N), dim3(256), 0, st, a.state,
+                                   P.need, z, O, a.text_W, 1, O, H, a.text_b, 0, a.p.ln_out_w, a.p.ln_out_b, a.ln_eps, P.pvec, H, (long)BM * H, 1,
+                                   ub...);
+            else
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_ln16<decltype(ub)...>), dim3(BM, N), dim3(256), 0, st, a.state, P.need, z, O,
+                                   a.p.ln_out_w, a.p.ln_out_b, a.ln_eps, P.pvec, ub...);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_joint<decltype(ub)...>), dim3((V + 15) / 16, N), dim3(256), 0, st, a.state, a.frames,
+                               a.frame_stride, P.pvec, a.W, a.bias, H, V, logits, ub...);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_reduce<decltype(ub)...>), dim3(ba.beam, N), dim3(1024), 0, st, a.state, P.status, logits, V,
+                               a.blank, ba.beam, red, ub...);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_select<decltype(ub)...>), dim3(1, N), dim3(256), 0, st, P, red, ba.beam, V, H, a.T, ML,
+                               a.max_per_frame, a.state, a.tokens, ba.scores, a.host_flag, ub...);
+        }
+    };
+    if (batched)
+        enqueue(BeamBatch{L.block, ba.utt, ba.rows, (unsigned *)(ws + L.n_done)});
+    else
+        enqueue();
 }

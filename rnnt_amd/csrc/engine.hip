@@ -831,6 +831,49 @@ int rnnt_engine_beam_decode(const void *frames, int64_t frame_stride, int T, con
     return launch_status("rnnt_engine_beam_decode");
 }
 
+int rnnt_engine_beam_decode_batch_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int beam, int n_utt,
+                                                  size_t *out)
+{
+    if (!out) return fail(RNNT_ERR_INVALID_ARG, "null size pointer");
+    if (n_utt < 1 || n_utt > 64) return fail(RNNT_ERR_UNSUPPORTED, "batched beam decode takes 1 <= n_utt <= 64 (n_utt=%d)", n_utt);
+    if (int rc = rnnt_engine_beam_decode_workspace_bytes(S, E, O, H, V, has_text, max_length, beam, out)) return rc;
+    *out = align_up(beam_batch_workspace_bytes(S, E, O, H, V, has_text ? 1 : 0, max_length, n_utt));
+    return RNNT_OK;
+}
+
+int rnnt_engine_beam_decode_batch(const void *frames, int64_t frame_stride, int rows, const int32_t *utt, int n_utt, int max_frames,
+                                  const rnnt_conv_predictor_params *p, int S, int E, int O, float ln_in_eps, float ln_out_eps,
+                                  const void *text_W, const void *text_b, const void *W, const void *bias, int H, int V, int blank,
+                                  int max_length, int max_per_frame, int beam, const void *tables, int iterations, int init,
+                                  int32_t *host_flag, int32_t *state, int32_t *tokens, double *scores, void *workspace, size_t ws_bytes,
+                                  void *stream)
+{
+    size_t need;
+    if (int rc = rnnt_engine_beam_decode_batch_workspace_bytes(S, E, O, H, V, text_W ? 1 : 0, max_length, beam, n_utt, &need)) return rc;
+    if (iterations < 0) return fail(RNNT_ERR_INVALID_ARG, "iterations=%d", iterations);
+    if (!scores || !utt) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument (scores / utt)");
+    if ((uintptr_t)utt & 7) return fail(RNNT_ERR_INVALID_ARG, "utt must be 8-byte aligned");
+    if (tables && !aligned16(tables)) return fail(RNNT_ERR_INVALID_ARG, "tables must be 16-byte aligned");
+    if (max_frames < 1 || rows < max_frames)
+        return fail(RNNT_ERR_INVALID_ARG, "rows=%d max_frames=%d (1 <= max_frames <= rows)", rows, max_frames);
+    if (max_per_frame > 0 && (long)max_frames * max_per_frame + 1 > 0x7fffffffL)
+        return fail(RNNT_ERR_UNSUPPORTED, "max_frames * max_per_frame must stay below 2^31 (max_frames=%d, max_per_frame=%d)", max_frames,
+                    max_per_frame);
+    BeamArgs a;
+    if (int rc = dec_check_args(frames, frame_stride, max_frames, p, S, E, O, ln_in_eps, ln_out_eps, text_W, text_b, W, bias, H, V, blank,
+                                max_length, max_per_frame, host_flag, state, tokens, workspace, a.d))
+        return rc;
+    if (ws_bytes < need) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
+    a.d.iterations = iterations ? iterations : max_frames * max_per_frame + 1;
+    a.d.init = init;
+    a.d.tables = tables;
+    a.beam = beam;
+    a.scores = scores;
+    a.utt = utt; a.n_utt = n_utt; a.rows = rows;
+    launch_beam_decode(a, (hipStream_t)stream);
+    return launch_status("rnnt_engine_beam_decode_batch");
+}
+
 static int dec_persist_check(int T, int S, int E, int O, int H, int V, int has_text, int max_length)
 {
     if (int rc = check_dims(1, 16, 1, H, V, RNNT_DTYPE_F32, true)) return rc;

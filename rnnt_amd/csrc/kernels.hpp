@@ -283,11 +283,16 @@ void launch_stream_init(int32_t *state, int blank, hipStream_t st);
 size_t dec_stream_workspace_bytes(int n, int S, int E, int O, int H, int V, int has_text, int cap, int persistent);
 int launch_dec_stream(const DecLoopArgs &a, int persistent, hipStream_t st);  // hipSuccess, or the persistent kernel's LDS-limit error (nothing launched)
 
-// ---- beam.hip: frame-synchronous beam search of one utterance (rnnt_engine_beam_decode), kernel-per-step rounds
+// ---- beam.hip: frame-synchronous beam search (rnnt_engine_beam_decode: one utterance; rnnt_engine_beam_decode_batch: n_utt in lockstep),
+// kernel-per-step rounds
 struct BeamArgs {
     DecLoopArgs d;       // frames, predictor, joint, blank, max_length, max_per_frame, iterations (= rounds), init, host_flag, state, tokens
     int beam;            // 1 .. 16
-    double *scores;      // [beam] out
+    double *scores;      // [beam] out ([n_utt][beam])
+    // the batched search (else utt == NULL): d.frames holds `rows` packed rows, d.state is [n_utt][32], d.tokens [n_utt][beam][max_length]
+    const int32_t *utt = nullptr;  // device int32[n_utt][2]: each utterance's first row and frame count
+    int n_utt = 1, rows = 0;
 };
 size_t beam_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length);
+size_t beam_batch_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int n_utt);
 void launch_beam_decode(const BeamArgs &a, hipStream_t st);

@@ -84,6 +84,8 @@ SIGNATURES = {
     "rnnt_engine_greedy_stream_decode": "pqipiiiffppppiiiiipipppzp",
     "rnnt_engine_beam_decode_workspace_bytes": "iiiiiiiip",
     "rnnt_engine_beam_decode": "pqipiiiffppppiiiiiipiipppppzp",
+    "rnnt_engine_beam_decode_batch_workspace_bytes": "iiiiiiiiip",
+    "rnnt_engine_beam_decode_batch": "pqipiipiiiffppppiiiiiipiipppppzp",
     "rnnt_engine_grad_norm_workspace_bytes": "ipp",
     "rnnt_engine_grad_norm": "ippppzp",
     "rnnt_engine_adamw_step": "ipppppdddddqpfip",
@@ -127,6 +129,7 @@ EXPORTS = (
     "rnnt_engine_greedy_decode_tables_bytes", "rnnt_engine_greedy_decode_build_tables",
     "rnnt_engine_greedy_stream_init", "rnnt_engine_greedy_stream_decode_workspace_bytes", "rnnt_engine_greedy_stream_decode",
     "rnnt_engine_beam_decode_workspace_bytes", "rnnt_engine_beam_decode",
+    "rnnt_engine_beam_decode_batch_workspace_bytes", "rnnt_engine_beam_decode_batch",
     "rnnt_engine_joint_loss_fwd", "rnnt_engine_run_stages",
     "rnnt_engine_joint_bwd_workspace_bytes", "rnnt_engine_joint_bwd",
     "rnnt_engine_grad_norm_workspace_bytes", "rnnt_engine_grad_norm", "rnnt_engine_adamw_step",
@@ -964,4 +967,73 @@ def beam_decode(frames, pred_params, ln_eps, text_W, text_b, W, bias, blank, max
             if len(pending) > max(1, int(in_flight)):
                 pending.pop(0).synchronize()
         state._keepalive = (flag, frames, params, W, bias, text_W, text_b, tables)  # until the caller has synchronised
+    return state, tokens, scores
+
+
+BEAM_BATCH_MAX = 64  # rnnt_engine_beam_decode_batch: 1 <= n_utt <= 64
+
+
+def beam_decode_batch_supported(S, E, O, H, V, has_text, max_length, beam, n_utt):
+    """Whether rnnt_engine_beam_decode_batch takes these sizes (no device work)."""
+    n = ctypes.c_size_t(0)
+    return lib().rnnt_engine_beam_decode_batch_workspace_bytes(int(S), int(E), int(O), int(H), int(V), int(bool(has_text)), int(max_length),
+                                                               int(beam), int(n_utt), ctypes.byref(n)) == 0
+
+
+def beam_decode_batch(frames_list, pred_params, ln_eps, text_W, text_b, W, bias, blank, max_length, beam, max_per_frame=10, tables=None,
+                      chunk=32, in_flight=2):
+    """The beam search of beam_decode for SEVERAL utterances of one model, advanced in lockstep on the device (C ABI
+    rnnt_engine_beam_decode_batch; DESIGN.md §4h "Batched"): `frames_list` holds 1 .. 64 [T_u, H] fp32 frame tensors (audio_ln applied),
+    packed here into one buffer; the table of first rows and lengths is the call's one small host-to-device copy.  The other arguments
+    and the enqueueing (chunks of rounds, the pinned end flag — raised when ALL searches have ended —, `in_flight`) as beam_decode.
+    Returns (state int32[N, 32], tokens int32[N, beam, max_length], scores float64[N, beam]) device tensors WITHOUT a final
+    synchronisation; row u of each is what beam_decode returns for frames_list[u] alone, bit for bit."""
+    frames_list = list(frames_list)
+    if not frames_list:
+        raise ValueError("beam_decode_batch: no utterance")
+    lens = [int(f.shape[0]) for f in frames_list]
+    if min(lens) < 1:
+        raise ValueError("beam_decode_batch: an utterance without frames")
+    packed = frames_list[0] if len(frames_list) == 1 else torch.cat(list(frames_list), 0)
+    dev, packed, params, text_W, text_b, W, bias = _decode_inputs(packed, pred_params, text_W, text_b, W, bias)
+    rows, H = packed.shape
+    N = len(lens)
+    V = W.shape[0]
+    S, E = params[0].shape
+    O = params[7].shape[0]
+    beam, max_length, max_per_frame = int(beam), int(max_length), int(max_per_frame)
+    chunk = max(1, int(chunk))
+    bound = max(lens) * max(1, max_per_frame) + 1
+    begins = [0]
+    for t in lens[:-1]:
+        begins.append(begins[-1] + t)
+    with torch.cuda.device(dev):
+        n = ctypes.c_size_t(0)
+        _check(lib().rnnt_engine_beam_decode_batch_workspace_bytes(S, E, O, H, V, 1 if text_W is not None else 0, max_length, beam, N,
+                                                                   ctypes.byref(n)))
+        ws = workspace(dev, n.value)
+        utt = torch.tensor(list(zip(begins, lens)), dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        state = torch.empty(N, 32, dtype=torch.int32, device=dev)
+        tokens = torch.empty(N, beam, max_length, dtype=torch.int32, device=dev)
+        scores = torch.empty(N, beam, dtype=torch.float64, device=dev)
+        flag = torch.zeros(1, dtype=torch.int32).pin_memory()
+        st = _PredParams(*[t.data_ptr() for t in params])
+        stream = _stream(dev)
+        eps_in, eps_out = _eps_pair(ln_eps)
+        pending = []
+        done = 0
+        while done < bound and (done == 0 or int(flag[0]) == 0):
+            it = min(chunk, bound - done)
+            _check(lib().rnnt_engine_beam_decode_batch(
+                _p(packed), ctypes.c_int64(packed.stride(0)), rows, _p(utt), N, max(lens), ctypes.byref(st), S, E, O, ctypes.c_float(eps_in),
+                ctypes.c_float(eps_out), _p(text_W), _p(text_b), _p(W), _p(bias), H, V, int(blank), max_length, max_per_frame, beam,
+                _p(tables), it, 1 if done == 0 else 0, ctypes.c_void_p(flag.data_ptr()), _p(state), _p(tokens), _p(scores), _p(ws),
+                ctypes.c_size_t(ws.numel()), stream))
+            done += it
+            ev = torch.cuda.Event()
+            ev.record()
+            pending.append(ev)
+            if len(pending) > max(1, int(in_flight)):
+                pending.pop(0).synchronize()
+        state._keepalive = (flag, utt, packed, params, W, bias, text_W, text_b, tables)  # until the caller has synchronised
     return state, tokens, scores

@@ -278,6 +278,78 @@ class RNNTModel(torch.nn.Module):
             raise RuntimeError(f"rnnt_engine: the beam search did not finish (t={st[0]}, {st[5]} rounds)")
         return [(toks[j][1:1 + st[8 + j]], sc[j]) for j in range(st[2])]
 
+    BEAM_BATCH = 32  # beam_search_many's default batch: the best of N = 1 .. 32 in profiles/beam_batch_bench.txt, the only one within 10 % of it
+
+    @torch.no_grad()
+    def beam_search_many(self, mels, beam_size: int = 4, max_length: int = 200, max_symbols_per_frame: int = 10,
+                         return_nbest: bool = False, batch=None):
+        """Beam search of SEVERAL utterances (a list of (1, C, L) mel tensors, as greedy_decode_many takes): a list in input order whose
+        entry i is exactly what `beam_search(mels[i], ...)` returns — the same token lists, the same float64 scores.  Up to `batch`
+        utterances (at most 64) advance in lockstep through ONE sequence of rounds on the device (rnnt_engine_beam_decode_batch: the
+        round's kernels carry the utterance as a grid dimension, so its launch boundaries are paid once per batch, not once per
+        utterance); longer lists run as consecutive batches, the last one possibly partial, with one host synchronisation per batch.
+        `batch` defaults to BEAM_BATCH = 32: of N = 1 .. 32 measured at the reference's widths (profiles/beam_batch_bench.txt) the time per
+        utterance was still falling at 32 (7 - 21 ms against 106 - 336 ms one by one), so 32 is the smallest N within 10 % of the best.
+        Where beam_search would take its host loop (CPU, other stateless predictors, beam_size > 16, sizes the kernels do not cover)
+        this is a loop over beam_search; a stateful (LSTM) predictor raises NotImplementedError."""
+        beam_size, max_length, m = int(beam_size), int(max_length), int(max_symbols_per_frame)
+        if beam_size < 1 or m < 1:
+            raise ValueError(f"beam_search_many: beam_size={beam_size} and max_symbols_per_frame={m} must be >= 1")
+        if self._predictor_is_stateful():
+            raise NotImplementedError("beam_search_many needs a stateless predictor (forward(ids), e.g. ConvPredictor); "
+                                      "stateful (LSTM) predictors are not supported")
+        mels = list(mels)
+        if not mels:
+            return []
+        assert all(mel.shape[0] == 1 for mel in mels), "one utterance per entry"
+        from . import engine
+        batch = self.BEAM_BATCH if batch is None else int(batch)
+        if not 1 <= batch <= engine.BEAM_BATCH_MAX:
+            raise ValueError(f"beam_search_many: batch={batch} outside [1, {engine.BEAM_BATCH_MAX}]")
+        out = [None] * len(mels)
+        tables = None
+        for i in range(0, len(mels), batch):
+            audios = [self.encoder(mel).permute(0, 2, 1) for mel in mels[i:i + batch]]
+            # the utterances of the slice that beam_search would decode on the device advance together; any other takes its host loop
+            on_device = [self._beam_device_ok(a, beam_size, max_length) for a in audios]
+            batched = [u for u, ok in enumerate(on_device) if ok]
+            if batched and not self._beam_batch_ok(len(batched), beam_size, max_length):
+                raise RuntimeError(f"rnnt_engine: the batched beam search refuses {len(batched)} utterances of sizes the single search takes")
+            for u, a in enumerate(audios):
+                if not on_device[u]:
+                    out[i + u] = self._beam_search_host(a, beam_size, max_length, m)
+            if not batched:
+                continue
+            if tables is None:
+                tables = self._decode_tables()  # one build per call, shared by every batch and utterance
+            frames = []
+            for u in batched:
+                f = audios[u][0]
+                if hasattr(self.joint, "audio_ln"):
+                    f = self.joint.audio_ln(f)
+                frames.append(f.float().contiguous())
+            tl = getattr(self.joint, "text_ln", None)
+            p = self.predictor
+            state, tokens, scores = engine.beam_decode_batch(
+                frames, p._params(), (float(p.input_layer_norm.eps), float(p.output_layer_norm.eps)),
+                tl.weight if tl is not None else None, tl.bias if tl is not None else None,
+                self.joint.joint_ln.weight, self.joint.joint_ln.bias, self.joint.blank_idx, max_length, beam_size, max_per_frame=m,
+                tables=tables)
+            sts, toks, scs = state.tolist(), tokens.tolist(), scores.tolist()  # the batch's one synchronisation
+            for k, (u, st) in enumerate(zip(batched, sts)):
+                if not st[3]:
+                    raise RuntimeError(f"rnnt_engine: the beam search of utterance {i + u} did not finish (t={st[0]}, {st[5]} rounds)")
+                out[i + u] = [(toks[k][j][1:1 + st[8 + j]], scs[k][j]) for j in range(st[2])]
+        return out if return_nbest else [list(nbest[0][0]) for nbest in out]
+
+    def _beam_batch_ok(self, n_utt, beam_size, max_length) -> bool:
+        from . import engine
+        p = self.predictor
+        S, E = p.embedding.weight.shape
+        return engine.beam_decode_batch_supported(S, E, p.linear.out_features, self.joint.joint_ln.in_features,
+                                                  self.joint.joint_ln.out_features, hasattr(self.joint, "text_ln"), max_length, beam_size,
+                                                  n_utt)
+
     def _beam_search_host(self, audio, beam_size, max_length, m):
         """The search of DESIGN.md §4h as a host loop: the predictor on the whole history of each new hypothesis (cached by
         sequence), single_forward batched over the round's active hypotheses, scores as Python floats (double)."""
