@@ -81,7 +81,7 @@ void rnnt_engine_set_debug(void *buf);
 
 /* Kernel variants a caller may ask for per call (rnnt_engine_run_stages).  Every variant multiplies
  * the same numbers in the same order as the default kernels: results are bit-identical. */
-#define RNNT_VARIANT_SEPARATE_G 32          /* G by its own pass (k_make_g) + the persistent dHidden kernel */
+#define RNNT_VARIANT_SEPARATE_G 32          /* G by its own pass (k_make_g); the dHidden kernels read it    */
 #define RNNT_VARIANT_SEPARATE_HIDDEN 64     /* hidden by its own pass instead of the forward prologue       */
 #define RNNT_VARIANT_FWD_LDS_RING 128       /* forward main loop: W through an LDS-DMA ring                 */
 #define RNNT_VARIANT_FWD_ONE_WG_PER_TILE 256 /* forward: one workgroup per tile instead of persistent ones   */

@@ -319,7 +319,7 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
     g.grad_W = (float *)grad_W; g.grad_bias = (float *)grad_bias;
     g.B = B; g.T = T; g.U1 = U1; g.H = H; g.V = V; g.blank = blank;
     g.n_ublk = L.n_ublk; g.n_ttile = L.n_ttile; g.n_split = L.n_split;
-    g.counter = (unsigned *)(ws + L.counters); g.dw_tab = (long *)(ws + L.counters + 1024); g.n_cu = device_cus(); g.flags = xflags & ~16; g.debug = g_debug; g.pred_split_col = 0;
+    g.counter = (unsigned *)(ws + L.counters); g.dw_tab = (long *)(ws + L.counters + 1024); g.n_cu = device_cus(); g.flags = xflags & ~16; g.g_ready = 0; g.debug = g_debug; g.pred_split_col = 0;
     g.gen_bu = dtype == RNNT_DTYPE_BF16 ? 16 : dhidden_gen_bu(T, U1);  // u width of the dHidden tiles
     if (dtype == RNNT_DTYPE_F32_BF16X3 || dtype == RNNT_DTYPE_F32_F16X2) {
         // RNNT_DTYPE_F32_F16X2 (x2.hip): the same stages on two fp16 planes and three products; operand scales below
@@ -477,9 +477,13 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
         if (stages & ST_DW_RED) launch_dw_reduce(g, st);
         return launch_status("rnnt_engine fused pipeline (bf16)");
     }
-    // G inside the dHidden GEMM unless the shape needs the separate pass (or flag 32 forces it)
-    const bool fuse_g = dhidden_gen_ok(H, V, U1) && !(xflags & 32);
-    if (fuse_g) { g.flags |= 16; g.pred_split_col = 512 * dhidden_gen_groups(H); }  // columns on the tile kernel (8-row dPred slabs)
+    // G inside the dHidden GEMM unless the shape needs the separate pass (k_make_g, then the persistent k_dhidden on every column).
+    // Flag 32 (RNNT_VARIANT_SEPARATE_G) runs k_make_g at a shape the tile kernel takes: the tile kernel then READS G in its first
+    // column group too (GEN = false) and forms every sum in the default order — bit-identical results, as the header says
+    const bool gen_ok = dhidden_gen_ok(H, V, U1);
+    const bool fuse_g = gen_ok && !(xflags & 32);
+    if (gen_ok) { g.flags |= 16; g.pred_split_col = 512 * dhidden_gen_groups(H); }  // columns on the tile kernel (8-row dPred slabs)
+    g.g_ready = gen_ok && !fuse_g;
 
     // hidden (A operand of all three GEMMs) is produced by the forward kernel for its own tile
     // unless flag 64 asks for the separate k_make_hidden pass

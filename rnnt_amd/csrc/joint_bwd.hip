@@ -271,9 +271,10 @@ typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 #endif
 // BU = u width of the tile (16: 8 t x 16 u; 8: 16 t x 8 u, for short targets — U1 = 101 fills 7 blocks
 // of 16 with 10 % dead rows, 13 blocks of 8 with 3 %); an M tile of 32 rows is (32/BU) t rows of BU u.
-// GEN = false (H >= 1024: further whole groups of 512 columns, `col_base` = 512, 1024, ...): the same tile,
-// schedule and epilogue on the G the GEN launch left in place of the logits — loaded, handed through the
-// exchange and multiplied as is; nothing is produced or stored but the slabs.
+// GEN = false (H >= 1024: further whole groups of 512 columns, `col_base` = 512, 1024, ...; RNNT_VARIANT_SEPARATE_G: the
+// first group as well, on k_make_g's G): the same tile, schedule and epilogue on the G that stands in place of the logits —
+// loaded, handed through the exchange and multiplied as is, so every sum is formed in the GEN launch's order; nothing is
+// produced or stored but the slabs.
 template <int BU, bool GEN>
 __global__ __launch_bounds__(256, 1) void k_dhidden_gen(JointBwdArgs a, const int col_base)
 {
@@ -732,7 +733,7 @@ __global__ __launch_bounds__(256) void k_reduce_pred(const float *__restrict__ s
 void launch_dhidden(const JointBwdArgs &a, hipStream_t st)
 {
     int cb0 = 0;  // first 128-column block left to the persistent kernel
-    if (a.flags & 16) {  // fused G producer (engine decides: dhidden_gen_ok)
+    if (a.flags & 16) {  // the tile kernel (engine decides: dhidden_gen_ok), producing G unless k_make_g has (g_ready: RNNT_VARIANT_SEPARATE_G)
         // zero the padding rows k_dw may touch (k_make_g used to)
         const long cells = (long)a.B * a.T * a.U1;
         launch_fill32((float *)a.logits + cells * a.V, 0u, (size_t)(a.rows_pad + 16 - cells) * a.V * 4, st);
@@ -742,11 +743,13 @@ void launch_dhidden(const JointBwdArgs &a, hipStream_t st)
         const int n_full = dhidden_gen_groups(a.H);
         if (a.gen_bu == 8) {
             dim3 grid((a.U1 + 7) / 8, (a.T + 15) / 16, a.B);
-            hipLaunchKernelGGL((k_dhidden_gen<8, true>), grid, dim3(256), 0, st, a, 0);
+            if (a.g_ready) hipLaunchKernelGGL((k_dhidden_gen<8, false>), grid, dim3(256), 0, st, a, 0);
+            else hipLaunchKernelGGL((k_dhidden_gen<8, true>), grid, dim3(256), 0, st, a, 0);
             for (int hp = 1; hp < n_full; ++hp) hipLaunchKernelGGL((k_dhidden_gen<8, false>), grid, dim3(256), 0, st, a, hp * DG_COLS);
         } else {
             dim3 grid((a.U1 + 15) / 16, (a.T + DG_BT - 1) / DG_BT, a.B);
-            hipLaunchKernelGGL((k_dhidden_gen<16, true>), grid, dim3(256), 0, st, a, 0);
+            if (a.g_ready) hipLaunchKernelGGL((k_dhidden_gen<16, false>), grid, dim3(256), 0, st, a, 0);
+            else hipLaunchKernelGGL((k_dhidden_gen<16, true>), grid, dim3(256), 0, st, a, 0);
             for (int hp = 1; hp < n_full; ++hp) hipLaunchKernelGGL((k_dhidden_gen<16, false>), grid, dim3(256), 0, st, a, hp * DG_COLS);
         }
         cb0 = n_full * (DG_COLS / 128);

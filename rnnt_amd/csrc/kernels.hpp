@@ -100,6 +100,7 @@ struct JointBwdArgs {
     const int *dw_list; // set by launch_dw: the list inside that region
     int n_cu;           // compute units (grid size of the persistent kernels)
     int flags;          // bit 4 (16): G is produced by k_dhidden_gen; others: experiment switches
+    int g_ready;        // with bit 4: G already stands in place of the logits (k_make_g ran): the first column group reads it too (GEN = false)
     int gen_bu;         // u width of k_dhidden_gen's tiles (16, or 8 for short targets); dEnc slabs of columns < pred_split_col
     int pred_split_col; // dPred slabs: columns < this come in 8-row t tiles (k_dhidden_gen, bf16 route), the rest in 4-row tiles (k_dhidden)
     unsigned long long *debug;  // diagnostic stamp buffer (RNNT_STAMPS builds), else NULL

@@ -32,9 +32,53 @@ def make_inputs(B, T, U, H, V, seed, ragged=True):
     return d
 
 
-def oracle_fused(d):
+def blank_index_map(V, blank):
+    """new_of_old [V]: the order-preserving relabelling of the vocabulary that moves the blank from V - 1 to `blank`
+    (old V - 1 -> blank, every other old index -> the remaining new indices in order)."""
+    blank = blank + V if blank < 0 else blank
+    assert 0 <= blank < V, (blank, V)
+    new_of_old = np.arange(V, dtype=np.int64)
+    new_of_old[blank:V - 1] += 1
+    new_of_old[V - 1] = blank
+    return new_of_old
+
+
+def relabel_blank(d, blank, neighbours=False):
+    """A make_inputs dict (blank = V - 1, labels in [0, V - 1)) as the same problem with the blank at `blank`: the rows of W
+    and bias and the targets move by blank_index_map.  Returns (dict, new_of_old): x_new[new_of_old] is x in the old order,
+    for W, bias and their gradients (costs, grad_enc and grad_pred do not move).  Targets never contain `blank`.
+    `neighbours`: utterance 0's first two labels become blank - 1 and blank + 1 (each where it exists; needs
+    target_lens[0] >= 2), so that a label sits directly on either side of the blank — ANOTHER problem than d, with its own
+    reference."""
+    V = d["W"].shape[0]
+    blank = blank + V if blank < 0 else blank
+    new_of_old = blank_index_map(V, blank)
+    assert (d["targets"] >= 0).all() and (d["targets"] < V - 1).all(), "make_inputs convention: labels in [0, V - 1)"
+    r = dict(d)
+    r["W"] = np.empty_like(d["W"])
+    r["W"][new_of_old] = d["W"]
+    r["bias"] = np.empty_like(d["bias"])
+    r["bias"][new_of_old] = d["bias"]
+    r["targets"] = new_of_old[d["targets"]].astype(d["targets"].dtype)
+    if neighbours and d["targets"].shape[1] >= 2 and d["target_lens"][0] >= 2:
+        if blank >= 1:
+            r["targets"][0, 0] = blank - 1
+        if blank + 1 < V:
+            r["targets"][0, 1] = blank + 1
+    assert not (r["targets"] == blank).any()
+    return r, new_of_old
+
+
+def has_live_label(d, label):
+    """Does `label` occur among the targets the lattices read (u < target_lens[b])?"""
+    U = d["targets"].shape[1]
+    live = np.arange(U)[None, :] < np.asarray(d["target_lens"])[:, None]
+    return bool(((d["targets"] == label) & live).any())
+
+
+def oracle_fused(d, blank=-1):
     return cpu_oracle.joint_loss_fwd_bwd(d["enc"], d["pred"], d["W"], d["bias"], d["targets"],
-                                         d["logit_lens"], d["target_lens"], blank=-1,
+                                         d["logit_lens"], d["target_lens"], blank=blank,
                                          dtype=np.float64)
 
 
@@ -79,7 +123,7 @@ def bf16_round(x):
     return ((u + r) & 0xFFFF0000).astype(np.uint32).view(np.float32)
 
 
-def oracle_fused_bf16(d):
+def oracle_fused_bf16(d, blank=-1):
     enc, pred, W, bias = d["enc"], d["pred"], d["W"], d["bias"]
     B, T, H = enc.shape
     U1, V = pred.shape[1], W.shape[0]
@@ -89,7 +133,7 @@ def oracle_fused_bf16(d):
     logits = (hidden.reshape(-1, H) @ Wb.T + bias.astype(np.float64)).astype(np.float32)
     # the route stores its logits in fp16 and computes everything downstream from the stored values
     logits = logits.astype(np.float16).astype(np.float32).reshape(B, T, U1, V)
-    costs, G = cpu_oracle.rnnt_loss(logits, d["targets"], d["logit_lens"], d["target_lens"], blank=-1,
+    costs, G = cpu_oracle.rnnt_loss(logits, d["targets"], d["logit_lens"], d["target_lens"], blank=blank,
                                     dtype=np.float64)
     Gb = bf16_round((G / B).astype(np.float32)).astype(np.float64).reshape(-1, V)
     dpre = (Gb @ Wb).reshape(B, T, U1, H) * (1.0 - hidden * hidden)

@@ -91,17 +91,17 @@ def loss_and_grad(logits, targets, logit_lens, target_lens, blank=-1, fastemit_l
     return costs, grad
 
 
-def fused(d, fastemit_lambda=0.0, delay_penalty=0.0, grad_scale=None):
+def fused(d, fastemit_lambda=0.0, delay_penalty=0.0, grad_scale=None, blank=-1):
     """joint + regularised loss, forward and backward, on a tests.helpers.make_inputs dict: dict(loss, costs, grad_enc,
-    grad_pred, grad_W, grad_bias) of grad_scale * sum_b cost_b (grad_scale = 1/B: reduction "mean"), blank = V - 1."""
+    grad_pred, grad_W, grad_bias) of grad_scale * sum_b cost_b (grad_scale = 1/B: reduction "mean"), blank = V - 1 by default."""
     logits = cpu_oracle.joint_fwd(d["enc"], d["pred"], d["W"], d["bias"])
     scale = 1.0 / logits.shape[0] if grad_scale is None else grad_scale
-    costs, G = loss_and_grad(logits, d["targets"], d["logit_lens"], d["target_lens"], -1, fastemit_lambda, delay_penalty)
+    costs, G = loss_and_grad(logits, d["targets"], d["logit_lens"], d["target_lens"], blank, fastemit_lambda, delay_penalty)
     ge, gp, gW, gb = cpu_oracle.joint_bwd(d["enc"], d["pred"], d["W"], G * scale)
     return dict(loss=costs.sum() * scale, costs=costs, grad_enc=ge, grad_pred=gp, grad_W=gW, grad_bias=gb)
 
 
-def fused_bf16(d, fastemit_lambda=0.0, delay_penalty=0.0):
+def fused_bf16(d, fastemit_lambda=0.0, delay_penalty=0.0, blank=-1):
     """`fused` with the bf16 route's rounding points (tests.helpers.oracle_fused_bf16): bf16 hidden and W, fp16 logits,
     bf16 G of the mean."""
     enc, pred, W, bias = d["enc"], d["pred"], d["W"], d["bias"]
@@ -112,7 +112,7 @@ def fused_bf16(d, fastemit_lambda=0.0, delay_penalty=0.0):
     Wb = bf16_round(W).astype(np.float64)
     logits = (hidden.reshape(-1, H) @ Wb.T + bias.astype(np.float64)).astype(np.float32)
     logits = logits.astype(np.float16).astype(np.float32).reshape(B, T, U1, V)
-    costs, G = loss_and_grad(logits, d["targets"], d["logit_lens"], d["target_lens"], -1, fastemit_lambda, delay_penalty)
+    costs, G = loss_and_grad(logits, d["targets"], d["logit_lens"], d["target_lens"], blank, fastemit_lambda, delay_penalty)
     Gb = bf16_round((G / B).astype(np.float32)).astype(np.float64).reshape(-1, V)
     dpre = (Gb @ Wb).reshape(B, T, U1, H) * (1.0 - hidden * hidden)
     return dict(loss=costs.mean(), costs=costs, grad_enc=dpre.sum(2), grad_pred=dpre.sum(1),
