@@ -494,6 +494,47 @@ int rnnt_engine_beam_decode_batch(const void *frames, int64_t frame_stride, int 
                                   void *stream);
 
 /*
+ * Streaming beam search: the search of rnnt_engine_beam_decode stopped at frame boundaries, for n_streams (1 .. 64)
+ * INDEPENDENT streams of one model advanced in lockstep by the batched search's kernel sequence.  After any sequence of pushes that
+ * delivered frames 0 .. k-1 of a stream, in any chunking, its result is bit for bit what rnnt_engine_beam_decode returns for those k
+ * frames: a stream that completes the last frame of its push comes to REST (its result is written as at `done`, its kernels return at
+ * once) and the next push resumes from that very state.  The search never ends: max_length only stops hypotheses growing.
+ * Everything a stream carries from push to push lives in caller-owned memory:
+ *   block  rnnt_engine_beam_stream_bytes(...) bytes, 256-byte aligned: per stream the slot buffers and per-round intermediates of the
+ *          single search's workspace, and a counter.  A push uses no other scratch; the decode tables
+ *          (rnnt_engine_greedy_decode_build_tables) are REQUIRED and shared;
+ *   state  int32[n_streams][32]: words 1 .. 6 and 8 .. 23 as rnnt_engine_beam_decode's, [RNNT_BEAM_STREAM_FRAMES] the frames consumed
+ *          over all pushes, [3] always 0, [RNNT_BEAM_STREAM_AT_REST] 1 while every frame pushed so far is consumed,
+ *          [RNNT_BEAM_STREAM_BASE] the frames consumed when the current push began;
+ *   tokens int32[n_streams][beam][max_length], scores double[n_streams][beam]: the result after the last push, as above.
+ * rnnt_engine_beam_stream_init starts all streams (index = -1) or stream `index` alone ("this slot starts a new utterance", the others
+ * untouched) by kernels: the empty hypothesis, at rest, and the result of zero frames (one entry, length 0, score 0.0).
+ * rnnt_engine_beam_stream_push enqueues one push: `frames` holds the push's frames of all streams packed into `rows` >= 1 rows,
+ *   push_table device int32[n_streams][2]: stream u's first row in THIS push's frames and its frame count; 0 (or less): the stream
+ *          sits the push out.  Frame t of a stream is row first + (t - base), read as the last row beyond `rows`;
+ *   max_count: the largest count (>= 0) — `iterations` = 0 enqueues the bound max_count * max_per_frame + 1 rounds;
+ *   begin != 0 opens the push with a kernel that latches each stream's base, clears the at-rest word of the streams that got frames
+ *          and counts the others; begin = 0 continues it (chunked enqueueing, as `init` of rnnt_engine_beam_decode);
+ *   host_flag rises once ALL streams are at rest.
+ * The other arguments as rnnt_engine_beam_decode_batch.  The caller synchronises once per push.  Limits as
+ * rnnt_engine_beam_decode_batch (RNNT_ERR_UNSUPPORTED: beam > 16, n_streams outside 1 .. 64, sizes the beam kernels refuse;
+ * RNNT_ERR_WORKSPACE: a short block; RNNT_ERR_INVALID_ARG: null pointers or table, negative counts); every argument is checked before
+ * anything is enqueued.  The model's weights and tables must not change while a stream is open.
+ */
+#define RNNT_BEAM_STREAM_FRAMES 0
+#define RNNT_BEAM_STREAM_AT_REST 24
+#define RNNT_BEAM_STREAM_BASE 25
+int rnnt_engine_beam_stream_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int beam, int n_streams, size_t *out);
+int rnnt_engine_beam_stream_init(int S, int E, int O, int H, int V, int has_text, int max_length, int beam, int blank, int n_streams,
+                                 int index, int32_t *state, double *scores, void *block, size_t bytes, void *stream);
+int rnnt_engine_beam_stream_push(const void *frames, int64_t frame_stride, int rows, const int32_t *push_table, int n_streams, int max_count,
+                                 const rnnt_conv_predictor_params *p, int S, int E, int O, float ln_in_eps, float ln_out_eps,
+                                 const void *text_W, const void *text_b, const void *W, const void *bias, int H, int V, int blank,
+                                 int max_length, int max_per_frame, int beam, const void *tables, int iterations, int begin,
+                                 int32_t *host_flag, int32_t *state, int32_t *tokens, double *scores, void *block, size_t bytes,
+                                 void *stream);
+
+/*
  * y = x W^T + b and its backward as MFMA kernels: the joint's optional input projections
  * audio_ln / text_ln (next-step row SURVEY.md 8f-1; reference rnnt/joint.py:8-12,26-30).
  * x [M,K] with rows ldx floats apart, W [N,K] (torch.nn.Linear layout), y / dy [M,N] contiguous.

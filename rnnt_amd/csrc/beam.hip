@@ -1,5 +1,6 @@
-// beam.hip — frame-synchronous beam search on the device: ONE utterance (rnnt_engine_beam_decode) or N independent ones advanced in
-// lockstep by the same rounds (rnnt_engine_beam_decode_batch); DESIGN.md §4h.
+// beam.hip — frame-synchronous beam search on the device: ONE utterance (rnnt_engine_beam_decode), N independent ones advanced in
+// lockstep by the same rounds (rnnt_engine_beam_decode_batch), or N STREAMS whose searches rest at the end of every push of frames and
+// resume at the next (rnnt_engine_beam_stream_push); DESIGN.md §4h, §4l.
 //
 // The search (exact definition: DESIGN.md §4h, tests/beam_oracle.py): at most `m` labels per frame, hypotheses merged by
 // token sequence; beam 1 is the reference's greedy decode (rnnt/model.py:95-128).  Per frame t, rounds r = 0 .. m-1: every
@@ -29,6 +30,10 @@
 // logits, state, results — lies `stride` bytes (its own size) after its neighbour's, the weights and tables are shared, and a
 // workgroup of utterance u does exactly what the single search's workgroup does, on u's block.  A done search's workgroups return
 // at once; the last one to finish raises the host's flag (a device-scope counter, k_beam_select).
+// The streaming search: a third pack, one BeamStream — the batch's layout and grid, with the caller's persistent block in
+// the workspace's place.  A stream never ends: the search that completes the last frame of its push writes its result as a search that
+// ends does and sets its AT-REST word, which is what its kernels test where the other two test `done`; k_beam_stream_begin opens the
+// next push (the frames consumed so far become the base of the push's row addressing, the word is cleared).
 // Arithmetic: fp32 products (fp32 MFMA, exact fp32 as fmaf chains), log-sum-exp in fp32, SCORES in fp64 (the log-probability
 // (double)logit - (double)lse is added to a double score; logaddexp in double).
 // Ties (no result may depend on one): finished entries first, then parent slot ascending, then token id ascending; the
@@ -43,7 +48,12 @@
 // state (int32[32]) — also the caller's view of the search:
 //   [0] t  [1] round within the frame  [2] entries of the beam  [3] done  [4] some slot awaits its predictor step
 //   [5] rounds that did work  [6] current slot buffer (0 / 1)  [8 + j] length of entry j of the result (done)
-enum { BS_T = 0, BS_R = 1, BS_N = 2, BS_DONE = 3, BS_NEW = 4, BS_ROUNDS = 5, BS_CUR = 6, BS_LEN = 8 };
+//   a stream (RNNT_BEAM_STREAM_* of include/rnnt_engine.h): [0] counts the frames consumed over all pushes, [3] stays 0,
+//   [24] at rest: every frame pushed so far is consumed  [25] frames consumed when the current push began
+enum { BS_T = 0, BS_R = 1, BS_N = 2, BS_DONE = 3, BS_NEW = 4, BS_ROUNDS = 5, BS_CUR = 6, BS_LEN = 8,
+       BS_REST = RNNT_BEAM_STREAM_AT_REST, BS_BASE = RNNT_BEAM_STREAM_BASE };
+static_assert(RNNT_BEAM_STREAM_FRAMES == BS_T && BS_REST >= BS_LEN + BM && BS_BASE >= BS_LEN + BM && BS_REST != BS_BASE && BS_REST < 32 &&
+              BS_BASE < 32, "the stream's words lie in the free part of the state");
 // slot status
 enum { SL_EMPTY = 0, SL_ACTIVE = 1, SL_FINISHED = 2 };
 
@@ -56,6 +66,18 @@ struct BeamBatch {
 };
 __device__ __forceinline__ BeamBatch beam_batch() { return BeamBatch{0, nullptr, 0, nullptr}; }  // the single search
 __device__ __forceinline__ BeamBatch beam_batch(const BeamBatch &b) { return b; }
+// the streaming search's arguments: the batch's, over the caller's block
+struct BeamStream {
+    size_t stride;        // bytes from one stream's part of the block to the next
+    const int32_t *push;  // [N][2]: the stream's first row of this push's packed frames, its frame count (0: the stream sits this push out)
+    int rows;             // rows of the packed frames
+    unsigned *n_rest;     // device word: streams at rest in this push
+};
+__device__ __forceinline__ BeamBatch beam_batch(const BeamStream &s) { return BeamBatch{s.stride, s.push, s.rows, s.n_rest}; }
+template <typename... U> struct beam_streams { static constexpr bool value = false; };
+template <> struct beam_streams<BeamStream> { static constexpr bool value = true; };
+// the word that stops a search's kernels: `done`, a stream's `at rest`
+template <typename... U> __device__ __forceinline__ int beam_idle(const int32_t *state) { return state[beam_streams<U...>::value ? BS_REST : BS_DONE]; }
 #define BEAM_UTT(ub) const BeamBatch B = beam_batch(ub...); const unsigned u = sizeof...(U) ? blockIdx.y : 0u; const size_t uoff = u * B.stride
 // utterance u's copy of a per-search buffer, `off` = u * stride bytes on (0 for the single search)
 template <typename T> __device__ __forceinline__ T *beam_utt(T *p, size_t off) { return (T *)((char *)p + off); }
@@ -118,7 +140,7 @@ __global__ __launch_bounds__(256) void k_beam_conv1(const int32_t *__restrict__ 
 {
     BEAM_UTT(ub);
     state += 32 * u;
-    if (state[BS_DONE] || !state[BS_NEW]) return;
+    if (beam_idle<U...>(state) || !state[BS_NEW]) return;
     P = beam_utt(P, uoff); g1 = beam_utt(g1, uoff);
     const int cur = state[BS_CUR], j = blockIdx.x;
     if (!P.need[cur * BM + j]) return;
@@ -163,7 +185,7 @@ __global__ __launch_bounds__(256) void k_beam_gemm16(const int32_t *__restrict__
     __shared__ float s_mean[16], s_rstd[16];
     BEAM_UTT(ub);
     state += 32 * u;
-    if (state[BS_DONE] || !state[BS_NEW]) return;
+    if (beam_idle<U...>(state) || !state[BS_NEW]) return;
     need = beam_utt(need, uoff); X = beam_utt(X, uoff); Y = beam_utt(Y, uoff);
     const int cur = state[BS_CUR];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
@@ -222,7 +244,7 @@ __global__ __launch_bounds__(256) void k_beam_ln16(const int32_t *__restrict__ s
     __shared__ float red[4];
     BEAM_UTT(ub);
     state += 32 * u;
-    if (state[BS_DONE] || !state[BS_NEW]) return;
+    if (beam_idle<U...>(state) || !state[BS_NEW]) return;
     need = beam_utt(need, uoff); z = beam_utt(z, uoff); pvec = beam_utt(pvec, uoff);
     const int cur = state[BS_CUR], j = blockIdx.x;
     if (!need[cur * BM + j]) return;
@@ -240,7 +262,7 @@ __global__ __launch_bounds__(256) void k_beam_ln16(const int32_t *__restrict__ s
 // ---- logits[slot][v] = tanh(frame_t + pvec[slot]) . W[v] + bias[v] for all 16 slots, 16 vocabulary entries per workgroup
 // (rnnt/joint.py:44-55 after the projections).  The hidden operand is built in registers: lane (slot r, k group g) takes
 // tanh of its own sums, each element once per workgroup.  H % 4 == 0.  Batched search: frame t of the utterance is row
-// utt[u][0] + t of the packed `frames`, kept inside the `rows` rows the caller vouched for.
+// utt[u][0] + t of the packed `frames`, kept inside the `rows` rows the caller vouched for; a stream's: row push[u][0] + (t - base).
 template <typename... U>
 __global__ __launch_bounds__(256) void k_beam_joint(const int32_t *__restrict__ state, const float *__restrict__ frames, long fstride,
                                                     const float *__restrict__ pvec, const float *__restrict__ W, const float *__restrict__ bias,
@@ -249,10 +271,11 @@ __global__ __launch_bounds__(256) void k_beam_joint(const int32_t *__restrict__ 
     __shared__ float s_acc[4][16][17];
     BEAM_UTT(ub);
     state += 32 * u;
-    if (state[BS_DONE]) return;
+    if (beam_idle<U...>(state)) return;
     pvec = beam_utt(pvec, uoff); logits = beam_utt(logits, uoff);
     const int cur = state[BS_CUR];
-    const int t = sizeof...(U) ? max(0, min(B.utt[2 * u] + state[BS_T], B.rows - 1)) : state[BS_T];
+    // (a stream: row = the push's first row + frames consumed since the push began)
+    const int t = sizeof...(U) ? max(0, min(B.utt[2 * u] + state[BS_T] - (beam_streams<U...>::value ? state[BS_BASE] : 0), B.rows - 1)) : state[BS_T];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
     const int v0 = blockIdx.x * 16, vcol = min(v0 + r, V - 1);
     const float *f = frames + (size_t)t * fstride, *pv = pvec + ((size_t)cur * BM + r) * H, *wr = W + (size_t)vcol * H;
@@ -303,7 +326,7 @@ __global__ __launch_bounds__(1024) void k_beam_reduce(const int32_t *__restrict_
     __shared__ int s_i[16][BM];
     BEAM_UTT(ub);
     state += 32 * u;
-    if (state[BS_DONE]) return;
+    if (beam_idle<U...>(state)) return;
     status = beam_utt(status, uoff); logits = beam_utt(logits, uoff); red = beam_utt(red, uoff);
     const int cur = state[BS_CUR], j = blockIdx.x;
     if (status[cur * BM + j] != SL_ACTIVE) return;
@@ -412,7 +435,8 @@ __device__ bool beam_same_prefix(const int *a, const int *b, int len)  // positi
 
 // ---- one workgroup per utterance: the selection of the round and the search's bookkeeping.  Batched search
 // (T then unused: the utterance's frame count is utt[u][1]): the search that ends counts itself in `n_done` and the one that
-// brings it to the n_utt = gridDim.y searches raises the host's flag.
+// brings it to the n_utt = gridDim.y searches raises the host's flag.  A stream (T = base + push[u][1]) comes to REST there instead: the
+// same result, the same count (k_beam_stream_begin counted the streams without frames), and the next push resumes from this very state.
 template <typename... U>
 __global__ __launch_bounds__(256) void k_beam_select(BeamSlots P, const float *__restrict__ red, int beam, int V, int H, int T, int max_length,
                                                      int max_per_frame, int32_t *__restrict__ state, int32_t *__restrict__ out_tokens,
@@ -427,10 +451,10 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamSlots P, const float *_
     __shared__ int s_nfinal, s_frame_end, s_done;
     BEAM_UTT(ub);
     state += 32 * u;
-    if (state[BS_DONE]) return;
+    if (beam_idle<U...>(state)) return;
     P = beam_utt(P, uoff); red = beam_utt(red, uoff);
     out_tokens += (size_t)u * beam * max_length; out_scores += (size_t)u * beam;
-    if (sizeof...(U)) T = B.utt[2 * u + 1];
+    if (sizeof...(U)) T = B.utt[2 * u + 1] + (beam_streams<U...>::value ? state[BS_BASE] : 0);  // a stream: the frame its push ends before
     const int tid = threadIdx.x, cur = state[BS_CUR], nb = cur ^ 1, r = state[BS_R];
     const int *tok_old = P.tok + (size_t)cur * BM * max_length;
     if (tid < BM) {
@@ -576,10 +600,46 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamSlots P, const float *_
         state[BS_NEW] = any_new;
         state[BS_ROUNDS] += 1;
         state[BS_CUR] = nb;
-        state[BS_DONE] = done;
+        state[beam_streams<U...>::value ? BS_REST : BS_DONE] = done;  // a stream comes to rest: its result stands as at `done`, its search goes on
         // the host's cue to stop enqueueing rounds (mapped pinned memory, polled without a synchronisation)
         const bool all_done = done && (!sizeof...(U) || atomicAdd(B.n_done, 1u) + 1 == gridDim.y);
         if (all_done && host_flag) __hip_atomic_store(host_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// ---- a stream's start: k_beam_init's state for stream `first + blockIdx.x` of the (zero-filled) block, at rest, and the
+// result of zero frames: one entry, no labels, log-probability 0
+__global__ void k_beam_stream_init(BeamSlots P, int32_t *state, double *scores, int blank, int beam, size_t stride, int first)
+{
+    if (threadIdx.x != 0) return;
+    const unsigned u = first + blockIdx.x;
+    P = beam_utt(P, u * stride); state += 32 * u;
+    P.status[0] = SL_ACTIVE; P.need[0] = 1; P.len[0] = 0; P.score[0] = 0.0; P.hash[0] = 0ull;
+    P.tok[0] = blank;
+    for (int i = 0; i < 32; ++i) state[i] = 0;
+    state[BS_N] = 1; state[BS_NEW] = 1; state[BS_REST] = 1;
+    scores[(size_t)u * beam] = 0.0;
+}
+
+// ---- a push opens (one workgroup, a thread per stream): the frames consumed so far are the base of the push's rows; a stream that got
+// frames leaves its rest, one that got none is counted as resting already.  All without frames: the flag rises here.
+__global__ __launch_bounds__(64) void k_beam_stream_begin(int32_t *__restrict__ state, const int32_t *__restrict__ push, int n,
+                                                          unsigned *__restrict__ n_rest, int32_t *host_flag)
+{
+    __shared__ unsigned s_idle;
+    if (threadIdx.x == 0) s_idle = 0u;
+    __syncthreads();
+    if ((int)threadIdx.x < n) {
+        int32_t *st = state + 32 * threadIdx.x;
+        const int got = push[2 * threadIdx.x + 1] > 0;
+        st[BS_BASE] = st[BS_T];
+        st[BS_REST] = !got;
+        if (!got) atomicAdd(&s_idle, 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        *n_rest = s_idle;
+        if (s_idle == (unsigned)n && host_flag) __hip_atomic_store(host_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
@@ -619,8 +679,33 @@ size_t beam_batch_workspace_bytes(int S, int E, int O, int H, int V, int has_tex
 {
     return beam_layout(S, E, O, H, V, has_text, max_length, n_utt, true).total;
 }
+// a group of streams' persistent block: the batch's per-search parts and its counter (the tables are the caller's)
+size_t beam_stream_block_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int n_streams)
+{
+    return beam_layout(S, E, O, H, V, has_text, max_length, n_streams, true).state_end;
+}
 
-// the single search (ba.utt == NULL: one utterance of a.T frames) and the batched one (ba.n_utt utterances, rows of a.frames by ba.utt)
+static BeamSlots beam_slots(char *ws, const BeamLayout &L)
+{
+    BeamSlots P;
+    P.score = (double *)(ws + L.score); P.hash = (unsigned long long *)(ws + L.hash);
+    P.len = (int *)(ws + L.len); P.status = (int *)(ws + L.status); P.need = (int *)(ws + L.need);
+    P.tok = (int *)(ws + L.tok); P.pvec = (float *)(ws + L.pvec);
+    return P;
+}
+
+// streams [first, first + count) of the block start over (count == n_streams: the whole block, its counter included)
+void launch_beam_stream_init(void *block, int32_t *state, double *scores, int S, int E, int O, int H, int V, int has_text, int max_length,
+                             int beam, int blank, int n_streams, int first, int count, hipStream_t st)
+{
+    const BeamLayout L = beam_layout(S, E, O, H, V, has_text, max_length, n_streams, true);
+    char *ws = (char *)block;
+    launch_fill32(ws + (size_t)first * L.block, 0u, count == n_streams ? L.state_end : (size_t)count * L.block, st);
+    hipLaunchKernelGGL(k_beam_stream_init, dim3(count), dim3(64), 0, st, beam_slots(ws, L), state, scores, blank, beam, L.block, first);
+}
+
+// the single search (ba.utt == NULL: one utterance of a.T frames), the batched one (ba.n_utt utterances, rows of a.frames by ba.utt) and
+// a push of ba.n_utt streams (ba.streaming: ba.utt is the push's table, a.workspace the streams' block, a.init = the push begins)
 void launch_beam_decode(const BeamArgs &ba, hipStream_t st)
 {
     const DecLoopArgs &a = ba.d;
@@ -629,14 +714,11 @@ void launch_beam_decode(const BeamArgs &ba, hipStream_t st)
     const unsigned N = batched ? ba.n_utt : 1;
     const BeamLayout L = beam_layout(S, E, O, H, V, has_text, ML, N, batched);
     char *ws = (char *)a.workspace;
-    BeamSlots P;
-    P.score = (double *)(ws + L.score); P.hash = (unsigned long long *)(ws + L.hash);
-    P.len = (int *)(ws + L.len); P.status = (int *)(ws + L.status); P.need = (int *)(ws + L.need);
-    P.tok = (int *)(ws + L.tok); P.pvec = (float *)(ws + L.pvec);
+    const BeamSlots P = beam_slots(ws, L);
     float *g1 = (float *)(ws + L.g1), *g2 = (float *)(ws + L.g2), *z = (float *)(ws + L.z);
     float *logits = (float *)(ws + L.logits), *red = (float *)(ws + L.red);
     const float *tb = (const float *)a.tables;
-    if (a.init) launch_fill32(ws, 0u, L.state_end, st);
+    if (a.init && !ba.streaming) launch_fill32(ws, 0u, L.state_end, st);
     if (!tb) {  // (rebuilt on every call that brings none: a function of the parameters only)
         launch_dec_build_tables(a.p, S, E, O, a.ln_in_eps, a.text_W, a.text_b, H, (float *)(ws + L.tables), st);
         tb = (const float *)(ws + L.tables);
@@ -647,7 +729,8 @@ void launch_beam_decode(const BeamArgs &ba, hipStream_t st)
     const float *nul = nullptr;
     // `ub`: nothing (the single search's kernels) or the batch's BeamBatch
     auto enqueue = [&](auto... ub) {
-        if (a.init) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_init<decltype(ub)...>), dim3(1, N), dim3(64), 0, st, P, a.state, a.blank, ML, ub...);
+        if (a.init && !ba.streaming)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_init<decltype(ub)...>), dim3(1, N), dim3(64), 0, st, P, a.state, a.blank, ML, ub...);
         for (int it = 0; it < a.iterations; ++it) {
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_conv1<decltype(ub)...>), dim3(BM, N), dim3(256), 0, st, a.state, P, ML, S, E, tab,
                                a.p.conv1_b, g1, ub...);
@@ -673,7 +756,11 @@ void launch_beam_decode(const BeamArgs &ba, hipStream_t st)
                                a.max_per_frame, a.state, a.tokens, ba.scores, a.host_flag, ub...);
         }
     };
-    if (batched)
+    if (ba.streaming) {
+        unsigned *n_rest = (unsigned *)(ws + L.n_done);
+        if (a.init) hipLaunchKernelGGL(k_beam_stream_begin, dim3(1), dim3(64), 0, st, a.state, ba.utt, (int)N, n_rest, a.host_flag);
+        enqueue(BeamStream{L.block, ba.utt, ba.rows, n_rest});
+    } else if (batched)
         enqueue(BeamBatch{L.block, ba.utt, ba.rows, (unsigned *)(ws + L.n_done)});
     else
         enqueue();

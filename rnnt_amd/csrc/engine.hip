@@ -878,6 +878,64 @@ int rnnt_engine_beam_decode_batch(const void *frames, int64_t frame_stride, int 
     return launch_status("rnnt_engine_beam_decode_batch");
 }
 
+int rnnt_engine_beam_stream_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int beam, int n_streams, size_t *out)
+{
+    if (!out) return fail(RNNT_ERR_INVALID_ARG, "null size pointer");
+    if (n_streams < 1 || n_streams > 64) return fail(RNNT_ERR_UNSUPPORTED, "beam streams: 1 <= n_streams <= 64 (n_streams=%d)", n_streams);
+    if (int rc = rnnt_engine_beam_decode_workspace_bytes(S, E, O, H, V, has_text, max_length, beam, out)) return rc;
+    *out = align_up(beam_stream_block_bytes(S, E, O, H, V, has_text ? 1 : 0, max_length, n_streams));
+    return RNNT_OK;
+}
+
+int rnnt_engine_beam_stream_init(int S, int E, int O, int H, int V, int has_text, int max_length, int beam, int blank, int n_streams,
+                                 int index, int32_t *state, double *scores, void *block, size_t bytes, void *stream)
+{
+    size_t need;
+    if (int rc = rnnt_engine_beam_stream_bytes(S, E, O, H, V, has_text, max_length, beam, n_streams, &need)) return rc;
+    if (!state || !scores || !block) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument");
+    if (index < -1 || index >= n_streams) return fail(RNNT_ERR_INVALID_ARG, "index=%d outside [-1,%d)", index, n_streams);
+    if (blank < 0 || blank >= V) return fail(RNNT_ERR_INVALID_ARG, "blank=%d outside [0,%d)", blank, V);
+    if ((uintptr_t)block & 255) return fail(RNNT_ERR_INVALID_ARG, "block must be 256-byte aligned");
+    if (bytes < need) return fail(RNNT_ERR_WORKSPACE, "stream block (workspace) %zu < required %zu bytes", bytes, need);
+    launch_beam_stream_init(block, state, scores, S, E, O, H, V, has_text ? 1 : 0, max_length, beam, blank, n_streams, index < 0 ? 0 : index,
+                            index < 0 ? n_streams : 1, (hipStream_t)stream);
+    return launch_status("rnnt_engine_beam_stream_init");
+}
+
+int rnnt_engine_beam_stream_push(const void *frames, int64_t frame_stride, int rows, const int32_t *push_table, int n_streams, int max_count,
+                                 const rnnt_conv_predictor_params *p, int S, int E, int O, float ln_in_eps, float ln_out_eps,
+                                 const void *text_W, const void *text_b, const void *W, const void *bias, int H, int V, int blank,
+                                 int max_length, int max_per_frame, int beam, const void *tables, int iterations, int begin,
+                                 int32_t *host_flag, int32_t *state, int32_t *tokens, double *scores, void *block, size_t bytes,
+                                 void *stream)
+{
+    size_t need;
+    if (int rc = rnnt_engine_beam_stream_bytes(S, E, O, H, V, text_W ? 1 : 0, max_length, beam, n_streams, &need)) return rc;
+    if (iterations < 0) return fail(RNNT_ERR_INVALID_ARG, "iterations=%d", iterations);
+    if (!scores || !push_table || !tables) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument (scores / push_table / tables)");
+    if ((uintptr_t)push_table & 7) return fail(RNNT_ERR_INVALID_ARG, "push_table must be 8-byte aligned");
+    if (!aligned16(tables)) return fail(RNNT_ERR_INVALID_ARG, "tables must be 16-byte aligned");
+    if (max_count < 0 || rows < 1 || rows < max_count)
+        return fail(RNNT_ERR_INVALID_ARG, "rows=%d max_count=%d (0 <= max_count <= rows, rows >= 1)", rows, max_count);
+    if (max_per_frame > 0 && (long)max_count * max_per_frame + 1 > 0x7fffffffL)
+        return fail(RNNT_ERR_UNSUPPORTED, "max_count * max_per_frame must stay below 2^31 (max_count=%d, max_per_frame=%d)", max_count,
+                    max_per_frame);
+    BeamArgs a;
+    if (int rc = dec_check_args(frames, frame_stride, max_count > 0 ? max_count : 1, p, S, E, O, ln_in_eps, ln_out_eps, text_W, text_b, W, bias, H, V,
+                                blank, max_length, max_per_frame, host_flag, state, tokens, block, a.d))
+        return rc;
+    if (bytes < need) return fail(RNNT_ERR_WORKSPACE, "stream block (workspace) %zu < required %zu bytes", bytes, need);
+    a.d.iterations = iterations ? iterations : max_count * max_per_frame + 1;
+    a.d.init = begin;
+    a.d.tables = tables;
+    a.beam = beam;
+    a.scores = scores;
+    a.utt = push_table; a.n_utt = n_streams; a.rows = rows;
+    a.streaming = true;
+    launch_beam_decode(a, (hipStream_t)stream);
+    return launch_status("rnnt_engine_beam_stream_push");
+}
+
 static int dec_persist_check(int T, int S, int E, int O, int H, int V, int has_text, int max_length)
 {
     if (int rc = check_dims(1, 16, 1, H, V, RNNT_DTYPE_F32, true)) return rc;

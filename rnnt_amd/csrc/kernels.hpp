@@ -284,8 +284,8 @@ void launch_stream_init(int32_t *state, int blank, hipStream_t st);
 size_t dec_stream_workspace_bytes(int n, int S, int E, int O, int H, int V, int has_text, int cap, int persistent);
 int launch_dec_stream(const DecLoopArgs &a, int persistent, hipStream_t st);  // hipSuccess, or the persistent kernel's LDS-limit error (nothing launched)
 
-// ---- beam.hip: frame-synchronous beam search (rnnt_engine_beam_decode: one utterance; rnnt_engine_beam_decode_batch: n_utt in lockstep),
-// kernel-per-step rounds
+// ---- beam.hip: frame-synchronous beam search (rnnt_engine_beam_decode: one utterance; rnnt_engine_beam_decode_batch: n_utt in lockstep;
+// rnnt_engine_beam_stream_push: n_streams searches resting between pushes), kernel-per-step rounds
 struct BeamArgs {
     DecLoopArgs d;       // frames, predictor, joint, blank, max_length, max_per_frame, iterations (= rounds), init, host_flag, state, tokens
     int beam;            // 1 .. 16
@@ -293,7 +293,13 @@ struct BeamArgs {
     // the batched search (else utt == NULL): d.frames holds `rows` packed rows, d.state is [n_utt][32], d.tokens [n_utt][beam][max_length]
     const int32_t *utt = nullptr;  // device int32[n_utt][2]: each utterance's first row and frame count
     int n_utt = 1, rows = 0;
+    // a push of n_utt streams (rnnt_engine_beam_stream_push): utt is the push's table, d.workspace the streams' persistent block (its layout:
+    // beam_stream_block_bytes), d.tables required, d.init = open the push (k_beam_stream_begin) before the rounds
+    bool streaming = false;
 };
 size_t beam_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length);
 size_t beam_batch_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int n_utt);
 void launch_beam_decode(const BeamArgs &a, hipStream_t st);
+size_t beam_stream_block_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int n_streams);
+void launch_beam_stream_init(void *block, int32_t *state, double *scores, int S, int E, int O, int H, int V, int has_text, int max_length,
+                             int beam, int blank, int n_streams, int first, int count, hipStream_t st);

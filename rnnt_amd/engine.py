@@ -86,6 +86,9 @@ SIGNATURES = {
     "rnnt_engine_beam_decode": "pqipiiiffppppiiiiiipiipppppzp",
     "rnnt_engine_beam_decode_batch_workspace_bytes": "iiiiiiiiip",
     "rnnt_engine_beam_decode_batch": "pqipiipiiiffppppiiiiiipiipppppzp",
+    "rnnt_engine_beam_stream_bytes": "iiiiiiiiip",
+    "rnnt_engine_beam_stream_init": "iiiiiiiiiiipppzp",
+    "rnnt_engine_beam_stream_push": "pqipiipiiiffppppiiiiiipiipppppzp",
     "rnnt_engine_grad_norm_workspace_bytes": "ipp",
     "rnnt_engine_grad_norm": "ippppzp",
     "rnnt_engine_adamw_step": "ipppppdddddqpfip",
@@ -130,6 +133,7 @@ EXPORTS = (
     "rnnt_engine_greedy_stream_init", "rnnt_engine_greedy_stream_decode_workspace_bytes", "rnnt_engine_greedy_stream_decode",
     "rnnt_engine_beam_decode_workspace_bytes", "rnnt_engine_beam_decode",
     "rnnt_engine_beam_decode_batch_workspace_bytes", "rnnt_engine_beam_decode_batch",
+    "rnnt_engine_beam_stream_bytes", "rnnt_engine_beam_stream_init", "rnnt_engine_beam_stream_push",
     "rnnt_engine_joint_loss_fwd", "rnnt_engine_run_stages",
     "rnnt_engine_joint_bwd_workspace_bytes", "rnnt_engine_joint_bwd",
     "rnnt_engine_grad_norm_workspace_bytes", "rnnt_engine_grad_norm", "rnnt_engine_adamw_step",
@@ -1037,3 +1041,105 @@ def beam_decode_batch(frames_list, pred_params, ln_eps, text_W, text_b, W, bias,
                 pending.pop(0).synchronize()
         state._keepalive = (flag, utt, packed, params, W, bias, text_W, text_b, tables)  # until the caller has synchronised
     return state, tokens, scores
+
+
+# ---- streaming beam search (include/rnnt_engine.h RNNT_BEAM_STREAM_*)
+BEAM_STREAM_MAX = 64  # rnnt_engine_beam_stream_*: 1 <= n_streams <= 64
+BEAM_STREAM_FRAMES, BEAM_STREAM_AT_REST, BEAM_STREAM_BASE = 0, 24, 25
+
+
+def beam_stream_bytes(S, E, O, H, V, has_text, max_length, beam, n_streams):
+    """Bytes of the persistent block of `n_streams` beam streams (C ABI rnnt_engine_beam_stream_bytes; no device work)."""
+    n = ctypes.c_size_t(0)
+    _check(lib().rnnt_engine_beam_stream_bytes(int(S), int(E), int(O), int(H), int(V), int(bool(has_text)), int(max_length), int(beam),
+                                               int(n_streams), ctypes.byref(n)))
+    return n.value
+
+
+def beam_stream_supported(S, E, O, H, V, has_text, max_length, beam, n_streams=1):
+    """Whether rnnt_engine_beam_stream_push takes these sizes (no device work)."""
+    n = ctypes.c_size_t(0)
+    return lib().rnnt_engine_beam_stream_bytes(int(S), int(E), int(O), int(H), int(V), int(bool(has_text)), int(max_length), int(beam),
+                                               int(n_streams), ctypes.byref(n)) == 0
+
+
+def beam_stream_init(sizes, max_length, beam, blank, state, scores, block, index=None):
+    """Start every stream of a group (index None) or stream `index` alone (C ABI rnnt_engine_beam_stream_init): `sizes` =
+    (S, E, O, H, V, has_text), `state` int32[n, 32], `scores` float64[n, beam], `block` uint8[beam_stream_bytes(...)], all on one
+    device.  Enqueued on the current stream, no synchronisation."""
+    dev = _require_cuda(state, scores, block)
+    _require_dtype(torch.int32, state=state)
+    _require_dtype(torch.float64, scores=scores)
+    _require_dtype(torch.uint8, block=block)
+    _require_contiguous(state=state, scores=scores, block=block)
+    S, E, O, H, V, has_text = sizes
+    n, beam = int(state.shape[0]), int(beam)
+    if state.shape != (n, 32) or scores.shape != (n, beam):
+        raise RuntimeError(f"beam_stream_init: state [n, 32] and scores [n, {beam}] expected, got {tuple(state.shape)}, {tuple(scores.shape)}")
+    with torch.cuda.device(dev):
+        _check(lib().rnnt_engine_beam_stream_init(int(S), int(E), int(O), int(H), int(V), int(bool(has_text)), int(max_length), beam, int(blank), n,
+                                                  -1 if index is None else int(index), _p(state), _p(scores), _p(block),
+                                                  ctypes.c_size_t(block.numel()), _stream(dev)))
+
+
+def beam_stream_push(frames_list, pred_params, ln_eps, text_W, text_b, W, bias, blank, max_length, beam, max_per_frame, tables,
+                     state, tokens, scores, block, chunk=32, in_flight=2):
+    """Enqueue one push of a group of beam streams (C ABI rnnt_engine_beam_stream_push): `frames_list` holds one entry per
+    stream, a [k_u, H] fp32 frame tensor (audio_ln applied) or None / k_u = 0 for a stream that sits the push out; they are packed here
+    and the table of first rows and counts is the push's one small host-to-device copy.  `state` int32[n, 32], `tokens`
+    int32[n, beam, max_length], `scores` float64[n, beam] and `block` are the group's persistent tensors (beam_stream_init); `tables`
+    greedy_decode_tables(...) of the same parameters.  Rounds are enqueued in chunks until the device has raised the pinned flag (all
+    streams at rest; polled, never waited for): chunks of `chunk` rounds, fewer for a push of few frames (2 * frames + 1), at most
+    `in_flight` of them ahead of the device.  No synchronisation: afterwards entry j < state[u, 2] of stream u is tokens[u, j, 1 : 1 + state[u, 8 + j]] with
+    log-probability scores[u, j], best first, and state[u, BEAM_STREAM_FRAMES] its frames consumed.  A push without any frame enqueues
+    nothing."""
+    n = int(state.shape[0])
+    frames_list = list(frames_list)
+    if len(frames_list) != n:
+        raise ValueError(f"beam_stream_push: {len(frames_list)} entries for {n} streams")
+    counts = [0 if f is None else int(f.shape[0]) for f in frames_list]
+    live = [f for f, k in zip(frames_list, counts) if k > 0]
+    if not live:
+        return
+    packed = live[0] if len(live) == 1 else torch.cat(live, 0)
+    dev, packed, params, text_W, text_b, W, bias = _decode_inputs(packed, pred_params, text_W, text_b, W, bias)
+    _require_cuda(packed, state, tokens, scores, block, tables)
+    _require_dtype(torch.int32, state=state, tokens=tokens)
+    _require_dtype(torch.float64, scores=scores)
+    _require_contiguous(state=state, tokens=tokens, scores=scores, block=block)
+    rows, H = packed.shape
+    V = W.shape[0]
+    S, E = params[0].shape
+    O = params[7].shape[0]
+    beam, max_length, max_per_frame = int(beam), int(max_length), int(max_per_frame)
+    if state.shape != (n, 32) or tokens.shape != (n, beam, max_length) or scores.shape != (n, beam):
+        raise RuntimeError(f"beam_stream_push: state [{n}, 32], tokens [{n}, {beam}, {max_length}], scores [{n}, {beam}] expected")
+    chunk = max(1, int(chunk))
+    max_count = max(counts)
+    bound = max_count * max(1, max_per_frame) + 1
+    begins, at = [], 0
+    for k in counts:
+        begins.append(at)
+        at += k
+    with torch.cuda.device(dev):
+        table = torch.tensor(list(zip(begins, counts)), dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        flag = torch.zeros(1, dtype=torch.int32).pin_memory()
+        st = _PredParams(*[t.data_ptr() for t in params])
+        stream = _stream(dev)
+        eps_in, eps_out = _eps_pair(ln_eps)
+        pending = []
+        done = 0
+        while done < bound and (done == 0 or int(flag[0]) == 0):
+            it = min(chunk, 2 * max_count + 1, bound - done)  # sized to the push: a 1-frame push enqueues 3 rounds at a time, not `chunk`
+            _check(lib().rnnt_engine_beam_stream_push(
+                _p(packed), ctypes.c_int64(packed.stride(0)), rows, _p(table), n, max_count, ctypes.byref(st), S, E, O, ctypes.c_float(eps_in),
+                ctypes.c_float(eps_out), _p(text_W), _p(text_b), _p(W), _p(bias), H, V, int(blank), max_length, max_per_frame, beam,
+                _p(tables), it, 1 if done == 0 else 0, ctypes.c_void_p(flag.data_ptr()), _p(state), _p(tokens), _p(scores), _p(block),
+                ctypes.c_size_t(block.numel()), stream))
+            done += it
+            ev = torch.cuda.Event()
+            ev.record()
+            pending.append(ev)
+            if len(pending) >= max(1, int(in_flight)):  # (before the flag is read again: a short push ends after the chunk that served it)
+                pending.pop(0).synchronize()
+        state._keepalive = (flag, table, packed, params, W, bias, text_W, text_b, tables)  # until the caller has synchronised

@@ -3,7 +3,6 @@ routes the joint + loss through the fused HIP engine.  Encoder and predictor are
 torch modules the caller supplies (stock PyTorch-ROCm; out of scope for the engine).
 """
 import inspect
-import math
 import warnings
 
 import torch
@@ -342,6 +341,20 @@ class RNNTModel(torch.nn.Module):
                 out[i + u] = [(toks[k][j][1:1 + st[8 + j]], scs[k][j]) for j in range(st[2])]
         return out if return_nbest else [list(nbest[0][0]) for nbest in out]
 
+    def beam_stream(self, beam_size: int = 4, max_length: int = 200, max_symbols_per_frame: int = 10):
+        """A BeamStream (rnnt_amd/stream.py): beam search push by push — `push(mel_chunk)` through the encoder's
+        streaming_forward, or `push_encoded(audio_features)` — whose n-best list after frames 0 .. k-1, however they were chunked, is
+        `beam_search` of those k frames (`nbest`, `tokens`), with the `stable` prefix no later push can change.  On the device where
+        beam_search is (the search's state rests in a block the stream owns), else a resumable host loop."""
+        from .stream import BeamStream
+        return BeamStream(self, beam_size=beam_size, max_length=max_length, max_symbols_per_frame=max_symbols_per_frame)
+
+    def beam_streams(self, n: int, beam_size: int = 4, max_length: int = 200, max_symbols_per_frame: int = 10):
+        """A BeamStreamGroup of `n` (1 .. 64) independent beam streams sharing one block and ONE launch sequence per push
+        (`push_encoded(chunks)`, a list of n chunks or None); stream i's results are exactly a lone beam_stream's."""
+        from .stream import BeamStreamGroup
+        return BeamStreamGroup(self, n, beam_size=beam_size, max_length=max_length, max_symbols_per_frame=max_symbols_per_frame)
+
     def _beam_batch_ok(self, n_utt, beam_size, max_length) -> bool:
         from . import engine
         p = self.predictor
@@ -353,55 +366,7 @@ class RNNTModel(torch.nn.Module):
     def _beam_search_host(self, audio, beam_size, max_length, m):
         """The search of DESIGN.md §4h as a host loop: the predictor on the whole history of each new hypothesis (cached by
         sequence), single_forward batched over the round's active hypotheses, scores as Python floats (double)."""
-        blank, dev = self.joint.blank_idx, self.device
-        feats = {}
-
-        def text(y):
-            if y not in feats:
-                ids = torch.tensor([[blank, *y]], dtype=torch.int64, device=dev)
-                feats[y] = self.predictor(ids)[0, -1]
-            return feats[y]
-
-        def lae(a, b):
-            hi, lo = max(a, b), min(a, b)
-            return hi if lo == -math.inf else hi + math.log1p(math.exp(lo - hi))
-
-        beam = [((), 0.0)]
-        for t in range(audio.shape[1]):
-            active, fin = beam, []  # fin: [[y, score]] in order of arrival
-            for r in range(m):
-                frame = audio[:, t, :].expand(len(active), -1)
-                lp = self.joint.single_forward(frame, torch.stack([text(y) for y, _ in active])).double().log_softmax(-1).cpu()
-                for i, (y, s) in enumerate(active):  # blank candidates join N, merged by sequence
-                    b = s + float(lp[i, blank])
-                    hit = next((e for e in fin if e[0] == y), None)
-                    if hit is not None:
-                        hit[1] = lae(hit[1], b)
-                    else:
-                        fin.append([y, b])
-                cands = [(s, 0, f, 0, y) for f, (y, s) in enumerate(fin)]
-                for i, (y, s) in enumerate(active):
-                    if len(y) >= max_length - 1:
-                        continue
-                    row = lp[i].clone()
-                    row[blank] = -math.inf
-                    vals, idx = torch.sort(row, descending=True, stable=True)  # lower id first among equal values
-                    for v, k in zip(vals[:beam_size].tolist(), idx[:beam_size].tolist()):
-                        if v != -math.inf:
-                            cands.append((s + v, 1, i, k, y + (k,)))
-                cands.sort(key=lambda c: (-c[0], c[1], c[2], c[3]))
-                kept = cands[:beam_size]
-                fin = [[c[4], c[0]] for c in kept if c[1] == 0]
-                active = [(c[4], c[0]) for c in kept if c[1] == 1]
-                if not active:
-                    break
-            # the cap: labels still active after round m-1 move on without a blank term, merged with N by sequence
-            for y, s in active:
-                hit = next((e for e in fin if e[0] == y), None)
-                if hit is not None:
-                    hit[1] = lae(hit[1], s)
-                else:
-                    fin.append([y, s])
-            order = sorted(range(len(fin)), key=lambda i: (-fin[i][1], i))
-            beam = [(fin[i][0], fin[i][1]) for i in order]
-        return [(list(y), s) for y, s in beam]
+        from .stream import HostBeamLoop  # (one host loop, resumable frame by frame: BeamStream's host path runs it too)
+        loop = HostBeamLoop(self, beam_size, max_length, m)
+        loop.run(audio)
+        return loop.nbest

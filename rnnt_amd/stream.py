@@ -4,7 +4,12 @@ cutting an utterance into pushes, empty ones included, the labels of the pushes 
 frames at once with the same max_length, wherever the argmax is not a rounding-level tie.
 
 HostGreedyLoop is greedy_decode's host loop made resumable; greedy_decode and the host path of GreedyStream both run it.
+
+Streaming beam search: RNNTModel.beam_stream() / beam_streams(n) return a BeamStream / a BeamStreamGroup whose n-best
+list after any sequence of pushes equals RNNTModel.beam_search of the frames pushed so far — on the device bit for bit, from a block of
+device memory the stream owns; HostBeamLoop is the host search made resumable, which beam_search's host path runs too.
 """
+import math
 import warnings
 
 import torch
@@ -224,3 +229,262 @@ class GreedyStream:
         self._done = bool(st[engine.STREAM_DONE])
         self.last_path = path
         return h[W:W + st[engine.STREAM_PUSH_LABELS]].tolist()
+
+
+class HostBeamLoop:
+    """The search of DESIGN.md §4h as a host loop over any number of calls of `run`: the predictor on the whole history of each new
+    hypothesis (cached by sequence), single_forward batched over the round's active hypotheses, scores as Python floats (double).  The
+    beam after the last frame carries to the next call; `nbest` is beam_search's result for the frames so far."""
+
+    def __init__(self, model, beam_size, max_length, max_symbols_per_frame=10):
+        self.model = model
+        self.beam_size, self.max_length, self.m = int(beam_size), int(max_length), int(max_symbols_per_frame)
+        self.beam = [((), 0.0)]
+        self.frames = 0
+        self._feats = {}
+
+    @property
+    def nbest(self):
+        return [(list(y), s) for y, s in self.beam]
+
+    def _text(self, y):
+        if y not in self._feats:
+            ids = torch.tensor([[self.model.joint.blank_idx, *y]], dtype=torch.int64, device=self.model.device)
+            self._feats[y] = self.model.predictor(ids)[0, -1]
+        return self._feats[y]
+
+    @staticmethod
+    def _lae(a, b):
+        hi, lo = max(a, b), min(a, b)
+        return hi if lo == -math.inf else hi + math.log1p(math.exp(lo - hi))
+
+    def run(self, audio):
+        """Search the frames of `audio` (1, n, C) from the carried beam."""
+        joint, blank, beam_size, max_length, m, lae, text = (self.model.joint, self.model.joint.blank_idx, self.beam_size, self.max_length,
+                                                             self.m, self._lae, self._text)
+        beam = self.beam
+        for t in range(audio.shape[1]):
+            active, fin = beam, []  # fin: [[y, score]] in order of arrival
+            for r in range(m):
+                frame = audio[:, t, :].expand(len(active), -1)
+                lp = joint.single_forward(frame, torch.stack([text(y) for y, _ in active])).double().log_softmax(-1).cpu()
+                for i, (y, s) in enumerate(active):  # blank candidates join N, merged by sequence
+                    b = s + float(lp[i, blank])
+                    hit = next((e for e in fin if e[0] == y), None)
+                    if hit is not None:
+                        hit[1] = lae(hit[1], b)
+                    else:
+                        fin.append([y, b])
+                cands = [(s, 0, f, 0, y) for f, (y, s) in enumerate(fin)]
+                for i, (y, s) in enumerate(active):
+                    if len(y) >= max_length - 1:
+                        continue
+                    row = lp[i].clone()
+                    row[blank] = -math.inf
+                    vals, idx = torch.sort(row, descending=True, stable=True)  # lower id first among equal values
+                    for v, k in zip(vals[:beam_size].tolist(), idx[:beam_size].tolist()):
+                        if v != -math.inf:
+                            cands.append((s + v, 1, i, k, y + (k,)))
+                cands.sort(key=lambda c: (-c[0], c[1], c[2], c[3]))
+                kept = cands[:beam_size]
+                fin = [[c[4], c[0]] for c in kept if c[1] == 0]
+                active = [(c[4], c[0]) for c in kept if c[1] == 1]
+                if not active:
+                    break
+            # the cap: labels still active after round m-1 move on without a blank term, merged with N by sequence
+            for y, s in active:
+                hit = next((e for e in fin if e[0] == y), None)
+                if hit is not None:
+                    hit[1] = lae(hit[1], s)
+                else:
+                    fin.append([y, s])
+            order = sorted(range(len(fin)), key=lambda i: (-fin[i][1], i))
+            beam = [(fin[i][0], fin[i][1]) for i in order]
+        self.beam = beam
+        self.frames += audio.shape[1]
+        live = {y for y, _ in beam}  # (only the beam's text vectors are needed again; the others would only grow with the stream)
+        self._feats = {y: f for y, f in self._feats.items() if y in live}
+
+
+def _common_prefix(lists):
+    out = list(lists[0])
+    for y in lists[1:]:
+        k = 0
+        while k < len(out) and k < len(y) and out[k] == y[k]:
+            k += 1
+        del out[k:]
+    return out
+
+
+class BeamStreamGroup:
+    """`n` (1 .. 64) independent utterances beam-searched push by push (RNNTModel.beam_streams).
+    `push_encoded(chunks)` takes a list of n chunks of encoder output, each (1, C, k_i) or None, and returns every stream's current best
+    token list.  Per stream i: `nbest[i]` = [(tokens, log-probability), ...] best first — exactly `beam_search(..., return_nbest=True)` of
+    the frames stream i has been pushed so far, whatever the chunking and whatever the other streams do; `tokens[i]` the best entry;
+    `stable[i]` the longest common prefix of the beam's entries (every later hypothesis extends one of them, so it can only grow and
+    stays a prefix of every later best entry); `frames[i]` the frames consumed; `reset(i)` starts a new utterance in slot i.  A beam stream
+    has no `done`: max_length only stops hypotheses growing, as in beam_search.
+
+    With the engine's ConvPredictor in eval mode, fp32 HIP tensors, sizes the beam kernels cover and beam_size <= 16 the searches rest on
+    the device between pushes, in a block the group owns (rnnt_engine_beam_stream_push: all streams advance through ONE kernel sequence
+    per round, one host synchronisation per push); the decode tables are built when the group is created, so the model's weights must not
+    change while it is open.  Everything else, the CPU included, runs one HostBeamLoop per stream (`last_path`: "device" or "host")."""
+
+    def __init__(self, model, n, beam_size=4, max_length=200, max_symbols_per_frame=10):
+        from . import engine
+        n, beam_size, max_length, m = int(n), int(beam_size), int(max_length), int(max_symbols_per_frame)
+        if beam_size < 1 or m < 1:
+            raise ValueError(f"beam_stream: beam_size={beam_size} and max_symbols_per_frame={m} must be >= 1")
+        if not 1 <= n <= engine.BEAM_STREAM_MAX:
+            raise ValueError(f"beam_streams: n={n} outside [1, {engine.BEAM_STREAM_MAX}]")
+        if model._predictor_is_stateful():
+            raise NotImplementedError("beam_stream needs a stateless predictor (forward(ids), e.g. ConvPredictor); "
+                                      "stateful (LSTM) predictors are not supported")
+        self.model, self.n = model, n
+        self.beam_size, self.max_length, self.max_symbols_per_frame = beam_size, max_length, m
+        self.nbest = [[([], 0.0)] for _ in range(n)]
+        self.frames = [0] * n
+        self.last_path = None
+        dev = model.device
+        self._on_device = dev.type == "cuda" and model._beam_device_ok(torch.zeros(1, 1, device=dev), beam_size, max_length)
+        if self._on_device:
+            p, joint = model.predictor, model.joint
+            S, E = p.embedding.weight.shape
+            self._sizes = (S, E, p.linear.out_features, joint.joint_ln.in_features, joint.joint_ln.out_features, hasattr(joint, "text_ln"))
+            self._on_device = engine.beam_stream_supported(*self._sizes, max_length, beam_size, n)
+        if self._on_device:
+            self._tables = model._decode_tables()  # once per group, from the weights as they are now
+            self._block = torch.zeros(engine.beam_stream_bytes(*self._sizes, max_length, beam_size, n), dtype=torch.uint8, device=dev)
+            # scores | state | tokens in one buffer: ONE device-to-host copy reads a push's whole result
+            self._cut = (8 * n * beam_size, 8 * n * beam_size + 4 * 32 * n)
+            self._res = torch.zeros(self._cut[1] + 4 * n * beam_size * max_length, dtype=torch.uint8, device=dev)
+            self._scores, self._state, self._tokens = self._views(self._res)
+            engine.beam_stream_init(self._sizes, max_length, beam_size, joint.blank_idx, self._state, self._scores, self._block)
+        else:
+            self._loops = [HostBeamLoop(model, beam_size, max_length, m) for _ in range(n)]
+
+    def _views(self, res):
+        n, beam, a, b = self.n, self.beam_size, *self._cut
+        return (res[:a].view(torch.float64).view(n, beam), res[a:b].view(torch.int32).view(n, 32),
+                res[b:].view(torch.int32).view(n, beam, self.max_length))
+
+    @property
+    def tokens(self):
+        return [list(nb[0][0]) for nb in self.nbest]
+
+    @property
+    def stable(self):
+        return [_common_prefix([y for y, _ in nb]) for nb in self.nbest]
+
+    def reset(self, i):
+        """Stream i starts a new utterance (the others are untouched)."""
+        i = range(self.n)[i]
+        if self._on_device:
+            from . import engine
+            engine.beam_stream_init(self._sizes, self.max_length, self.beam_size, self.model.joint.blank_idx, self._state, self._scores,
+                                    self._block, index=i)
+        else:
+            self._loops[i] = HostBeamLoop(self.model, self.beam_size, self.max_length, self.max_symbols_per_frame)
+        self.nbest[i] = [([], 0.0)]
+        self.frames[i] = 0
+
+    @torch.no_grad()
+    def push_encoded(self, chunks):
+        """One push: `chunks[i]` is stream i's next chunk of encoder output (1, C, k_i), k_i >= 0, or None.  Returns the list of the
+        streams' best token lists."""
+        chunks = list(chunks)
+        if len(chunks) != self.n:
+            raise ValueError(f"BeamStreamGroup.push_encoded takes {self.n} chunks (None for a stream without new frames), got {len(chunks)}")
+        audios = []
+        for c in chunks:
+            if c is not None and (c.dim() != 3 or c.shape[0] != 1):
+                raise ValueError(f"a beam stream takes one chunk of encoder output (1, C, n), got {tuple(c.shape)}")
+            audios.append(None if c is None or c.shape[2] == 0 else c.permute(0, 2, 1))  # (1, n, C), as rnnt/model.py:93
+        if any(a is not None for a in audios):
+            (self._push_device if self._on_device else self._push_host)(audios)
+        return self.tokens
+
+    def _push_host(self, audios):
+        for i, a in enumerate(audios):
+            if a is None:
+                continue
+            self._loops[i].run(a)
+            self.nbest[i] = self._loops[i].nbest
+            self.frames[i] = self._loops[i].frames
+        self.last_path = "host"
+
+    def _push_device(self, audios):
+        from . import engine
+        model, joint = self.model, self.model.joint
+        frames = []
+        for a in audios:
+            f = None
+            if a is not None:
+                f = a[0]
+                if hasattr(joint, "audio_ln"):  # per frame: the same numbers chunk by chunk
+                    f = joint.audio_ln(f)
+                f = f.float().contiguous()
+                if f.device != self._res.device:
+                    raise ValueError(f"beam stream: the stream lives on {self._res.device}, the chunk on {f.device}")
+            frames.append(f)
+        p, tl = model.predictor, getattr(joint, "text_ln", None)
+        engine.beam_stream_push(frames, p._params(), (float(p.input_layer_norm.eps), float(p.output_layer_norm.eps)),
+                                tl.weight if tl is not None else None, tl.bias if tl is not None else None,
+                                joint.joint_ln.weight, joint.joint_ln.bias, joint.blank_idx, self.max_length, self.beam_size,
+                                self.max_symbols_per_frame, self._tables, self._state, self._tokens, self._scores, self._block)
+        scores, state, tokens = self._views(self._res.cpu())  # the push's one synchronisation
+        sts, toks, scs = state.tolist(), tokens.tolist(), scores.tolist()
+        for i, (f, st) in enumerate(zip(frames, sts)):
+            if f is None:
+                continue
+            if not st[engine.BEAM_STREAM_AT_REST] or st[engine.BEAM_STREAM_FRAMES] != self.frames[i] + f.shape[0]:
+                raise RuntimeError(f"rnnt_engine: beam stream {i} did not consume its push (frames={st[engine.BEAM_STREAM_FRAMES]}, "
+                                   f"{st[5]} rounds)")
+            self.frames[i] = st[engine.BEAM_STREAM_FRAMES]
+            self.nbest[i] = [(toks[i][j][1:1 + st[8 + j]], scs[i][j]) for j in range(st[2])]
+        self.last_path = "device"
+
+
+class BeamStream:
+    """One utterance beam-searched push by push (RNNTModel.beam_stream): a BeamStreamGroup of one, with the encoder's
+    streaming state.  `push_encoded(audio_features)` takes a chunk of encoder output (1, C, n), n >= 0, `push(mel_chunk)` runs the encoder's
+    streaming_forward on a (1, F, L) mel chunk first; both return the current best hypothesis's FULL token list (the best entry can
+    change from push to push — `stable` is the part that cannot).  `nbest`, `tokens`, `stable`, `frames`, `last_path` as the group's, for
+    the one stream; `reset()` starts a new utterance on the same block and tables."""
+
+    def __init__(self, model, beam_size=4, max_length=200, max_symbols_per_frame=10):
+        self.model = model
+        self._group = BeamStreamGroup(model, 1, beam_size, max_length, max_symbols_per_frame)
+        self._enc_state = None
+
+    nbest = property(lambda self: self._group.nbest[0])
+    tokens = property(lambda self: self._group.tokens[0])
+    stable = property(lambda self: self._group.stable[0])
+    frames = property(lambda self: self._group.frames[0])
+    last_path = property(lambda self: self._group.last_path)
+
+    def reset(self):
+        self._group.reset(0)
+        self._enc_state = None
+
+    @torch.no_grad()
+    def push(self, mel_chunk):
+        """Run the encoder's streaming_forward on `mel_chunk` (1, F, L) with the state it carries (streaming_init_state(1) on the first
+        push, moved to the model's device), then push_encoded its output."""
+        enc = self.model.encoder
+        if not (callable(getattr(enc, "streaming_forward", None)) and callable(getattr(enc, "streaming_init_state", None))):
+            raise TypeError(f"BeamStream.push needs an encoder with streaming_forward(x, state) and streaming_init_state(batch_size); "
+                            f"{type(enc).__name__} lacks them (push_encoded takes encoder output directly)")
+        if mel_chunk.dim() != 3 or mel_chunk.shape[0] != 1:
+            raise ValueError(f"BeamStream.push takes one mel chunk (1, F, L), got {tuple(mel_chunk.shape)}")
+        if self._enc_state is None:
+            self._enc_state = _to_device(enc.streaming_init_state(1), self.model.device)
+        out, self._enc_state = enc.streaming_forward(mel_chunk, self._enc_state)
+        return self.push_encoded(out)
+
+    @torch.no_grad()
+    def push_encoded(self, audio_features):
+        """Search one chunk of encoder output (1, C, n), n >= 0, from where the stream stands.  Returns the best token list."""
+        if audio_features.dim() != 3 or audio_features.shape[0] != 1:
+            raise ValueError(f"BeamStream.push_encoded takes one chunk of encoder output (1, C, n), got {tuple(audio_features.shape)}")
+        return self._group.push_encoded([audio_features])[0]
