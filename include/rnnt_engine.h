@@ -494,6 +494,53 @@ int rnnt_engine_beam_decode_batch(const void *frames, int64_t frame_stride, int 
                                   void *stream);
 
 /*
+ * Contextual biasing (hotword boosting) of the two searches above (DESIGN.md §4h "Context"): rnnt_engine_beam_decode_ctx and
+ * rnnt_engine_beam_decode_batch_ctx are rnnt_engine_beam_decode and rnnt_engine_beam_decode_batch with one more argument, a phrase list
+ * as an Aho-Corasick trie (ONE graph, shared by every utterance of a batch).  Node 0 is the root; node m's children are entries
+ * child_off[m] .. child_off[m + 1] - 1 of child_tok (their tokens, ASCENDING within a node) and child_node (the nodes they lead to);
+ * fail_link[m] is the node of the deepest proper suffix of m's path that is a path of the trie (the root's is 0); depth[m] (0 .. 64) the
+ * length of m's path, bonus(m) = score * depth[m]; terminal[m] != 0 where a phrase ends.  A hypothesis at node n that takes label k:
+ *   m = n; while m != 0 and k is no child of m: m = fail_link[m];  m' = child(m, k) if there is one, else 0;
+ *   its score gains delta = score * (depth[m'] - depth[n]);  its node becomes 0 if terminal[m'] (the bonus is banked), else m'.
+ * Blank candidates gain nothing.  The scores kept during the search AND RETURNED in `scores` are INTERNAL: they still hold the bonus
+ * of an unfinished match.  The caller FINALISES: walk entry j's labels through the graph from node 0 to its node n_j, report
+ * scores[j] - score * depth[n_j], and re-sort the entries by that value (stable, descending).
+ * The arrays live on the device, so their CONTENTS are not checked: the kernels clamp every node index to [0, n_nodes), every child
+ * range to [0, n_children], every depth to [0, 64], walk at most 64 fail links per step and bisect a child range in at most 32 steps — a
+ * malformed graph gives a wrong result, never an access out of range or a loop without end.  Refused before anything is enqueued:
+ * a null `ctx` or null array, n_nodes < 1, n_children outside [0, n_nodes) (a trie has n_nodes - 1), a negative or non-finite score
+ * (RNNT_ERR_INVALID_ARG), n_nodes > 65536 (RNNT_ERR_UNSUPPORTED), and everything the plain entry points refuse.  The workspace holds
+ * one node per slot more than the plain search's: each entry point has its own query.  RNNT_ENGINE_VERSION is unchanged: detect the
+ * feature by symbol.
+ */
+#define RNNT_BEAM_CONTEXT_MAX_NODES 65536
+typedef struct rnnt_beam_context {
+    int32_t n_nodes, n_children;
+    double score;
+    const int32_t *child_off;  /* device int32[n_nodes + 1] */
+    const int32_t *child_tok;  /* device int32[max(n_children, 1)] */
+    const int32_t *child_node; /* device int32[max(n_children, 1)] */
+    const int32_t *fail_link;  /* device int32[n_nodes] */
+    const int32_t *depth;      /* device int32[n_nodes] */
+    const int32_t *terminal;   /* device int32[n_nodes] */
+} rnnt_beam_context;
+int rnnt_engine_beam_decode_ctx_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int beam, size_t *out);
+int rnnt_engine_beam_decode_ctx(const void *frames, int64_t frame_stride, int T, const rnnt_conv_predictor_params *p,
+                                int S, int E, int O, float ln_in_eps, float ln_out_eps, const void *text_W, const void *text_b,
+                                const void *W, const void *bias, int H, int V, int blank, int max_length, int max_per_frame,
+                                int beam, const void *tables, int iterations, int init, int32_t *host_flag, int32_t *state,
+                                int32_t *tokens, double *scores, void *workspace, size_t ws_bytes, const rnnt_beam_context *ctx,
+                                void *stream);
+int rnnt_engine_beam_decode_batch_ctx_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int beam,
+                                                      int n_utt, size_t *out);
+int rnnt_engine_beam_decode_batch_ctx(const void *frames, int64_t frame_stride, int rows, const int32_t *utt, int n_utt, int max_frames,
+                                      const rnnt_conv_predictor_params *p, int S, int E, int O, float ln_in_eps, float ln_out_eps,
+                                      const void *text_W, const void *text_b, const void *W, const void *bias, int H, int V, int blank,
+                                      int max_length, int max_per_frame, int beam, const void *tables, int iterations, int init,
+                                      int32_t *host_flag, int32_t *state, int32_t *tokens, double *scores, void *workspace,
+                                      size_t ws_bytes, const rnnt_beam_context *ctx, void *stream);
+
+/*
  * Streaming beam search: the search of rnnt_engine_beam_decode stopped at frame boundaries, for n_streams (1 .. 64)
  * INDEPENDENT streams of one model advanced in lockstep by the batched search's kernel sequence.  After any sequence of pushes that
  * delivered frames 0 .. k-1 of a stream, in any chunking, its result is bit for bit what rnnt_engine_beam_decode returns for those k

@@ -34,11 +34,16 @@
 // the workspace's place.  A stream never ends: the search that completes the last frame of its push writes its result as a search that
 // ends does and sets its AT-REST word, which is what its kernels test where the other two test `done`; k_beam_stream_begin opens the
 // next push (the frames consumed so far become the base of the push's row addressing, the word is cleared).
+// Contextual biasing (DESIGN.md §4h "Context"; rnnt_engine_beam_decode_ctx / _batch_ctx): a BeamCtx — the caller's phrase list as an
+// Aho–Corasick trie in flat device arrays, and a node per slot — as the LAST member of the pack of k_beam_reduce and k_beam_select only:
+// the reduce re-ranks a slot's labels by logit + delta(node, label) in a tail of its wave 0, the selection adds the delta in fp64 and
+// moves the nodes with the hypotheses.  The packs <> and <BeamBatch> are the instantiations they were; a stream takes no graph.
 // Arithmetic: fp32 products (fp32 MFMA, exact fp32 as fmaf chains), log-sum-exp in fp32, SCORES in fp64 (the log-probability
 // (double)logit - (double)lse is added to a double score; logaddexp in double).
 // Ties (no result may depend on one): finished entries first, then parent slot ascending, then token id ascending; the
 // per-slot top labels break ties by the lower token id (torch.argmax's first index at beam 1).
 #include "kernels.hpp"
+#include <type_traits>
 
 #define BM 16          // slots: the M dimension of every product
 #define BEAM_RED 48    // floats per slot of k_beam_reduce's output: [0] lse, [1] blank logit, [16 + 2q] q-th label logit, [17 + 2q] its id
@@ -57,6 +62,62 @@ static_assert(RNNT_BEAM_STREAM_FRAMES == BS_T && BS_REST >= BS_LEN + BM && BS_BA
 // slot status
 enum { SL_EMPTY = 0, SL_ACTIVE = 1, SL_FINISHED = 2 };
 
+// ---- contextual biasing (DESIGN.md §4h "Context"): the phrase list as an Aho–Corasick trie in flat device arrays, one node per slot.
+// The tables are the caller's device memory and are NOT trusted: every node index read from them is clamped to [0, n_nodes), every
+// child range to [0, n_children], depths to [0, BEAM_CTX_DEPTH], the fail walk is a counted loop of BEAM_CTX_DEPTH hops and the child
+// search a counted bisection — a malformed table gives a wrong result, never an access out of range or a loop without end.
+#define BEAM_CTX_DEPTH 64
+struct BeamCtx {
+    const int32_t *child_off;   // [n_nodes + 1]: node m's children are entries child_off[m] .. child_off[m + 1] - 1
+    const int32_t *child_tok;   // [n_children]: their tokens, ascending within a node
+    const int32_t *child_node;  // [n_children]: the nodes they lead to
+    const int32_t *fail;        // [n_nodes]: the deepest proper suffix of the node's path that is a path of the trie
+    const int32_t *depth;       // [n_nodes]: bonus(n) = score * depth(n)
+    const int32_t *terminal;    // [n_nodes]: a phrase ends here (the next state is the root: its bonus is banked)
+    int n_nodes, n_children;
+    double score;
+    int *node;                  // [2][BM] the slots' nodes (workspace; double-buffered like len and hash)
+};
+struct BeamStep { int next, ddepth; };  // the next node | depth(m') - depth(n)
+__device__ __forceinline__ int beam_ctx_node(const BeamCtx &c, int n) { return n < 0 ? 0 : (n >= c.n_nodes ? c.n_nodes - 1 : n); }
+__device__ __forceinline__ int beam_ctx_depth(const BeamCtx &c, int n) { const int d = c.depth[n]; return d < 0 ? 0 : (d > BEAM_CTX_DEPTH ? BEAM_CTX_DEPTH : d); }
+__device__ __forceinline__ void beam_ctx_range(const BeamCtx &c, int m, int &lo, int &hi)
+{
+    lo = c.child_off[m]; hi = c.child_off[m + 1];
+    lo = lo < 0 ? 0 : (lo > c.n_children ? c.n_children : lo);
+    hi = hi < lo ? lo : (hi > c.n_children ? c.n_children : hi);
+}
+// the child of node m (already clamped) by token k: its index in the child arrays, or -1
+__device__ __forceinline__ int beam_ctx_child(const BeamCtx &c, int m, int k)
+{
+    int lo, hi;
+    beam_ctx_range(c, m, lo, hi);
+    for (int it = 0; it < 32 && lo < hi; ++it) {  // (hi - lo halves: 32 steps cover any int range)
+        const int mid = lo + ((hi - lo) >> 1);
+        const int t = c.child_tok[mid];
+        if (t == k) return mid;
+        if (t < k) lo = mid + 1; else hi = mid;
+    }
+    return -1;
+}
+// step(n, k) of the definition: m = n; while m is not the root and k is no child of m: m = fail(m); m' = child(m, k) or the root
+__device__ __forceinline__ BeamStep beam_ctx_step(const BeamCtx &c, int n, int k)
+{
+    n = beam_ctx_node(c, n);
+    int m = n, ch = -1;
+    for (int hop = 0; hop <= BEAM_CTX_DEPTH; ++hop) {
+        ch = beam_ctx_child(c, m, k);
+        if (ch >= 0 || m == 0) break;
+        m = beam_ctx_node(c, c.fail[m]);
+    }
+    const int mp = ch >= 0 ? beam_ctx_node(c, c.child_node[ch]) : 0;
+    BeamStep s;
+    s.next = c.terminal[mp] ? 0 : mp;
+    s.ddepth = beam_ctx_depth(c, mp) - beam_ctx_depth(c, n);
+    return s;
+}
+__device__ __forceinline__ double beam_ctx_delta(const BeamCtx &c, int ddepth) { return c.score * (double)ddepth; }
+
 // the batched search's arguments (the kernels' trailing pack)
 struct BeamBatch {
     size_t stride;        // bytes from one utterance's block of the workspace to the next
@@ -74,11 +135,20 @@ struct BeamStream {
     unsigned *n_rest;     // device word: streams at rest in this push
 };
 __device__ __forceinline__ BeamBatch beam_batch(const BeamStream &s) { return BeamBatch{s.stride, s.push, s.rows, s.n_rest}; }
+// a search with a context graph: its BeamCtx ends the pack of k_beam_reduce and k_beam_select (the other kernels never see it)
+__device__ __forceinline__ BeamBatch beam_batch(const BeamCtx &) { return beam_batch(); }
+__device__ __forceinline__ BeamBatch beam_batch(const BeamBatch &b, const BeamCtx &) { return b; }
+__device__ __forceinline__ const BeamCtx &beam_ctx(const BeamCtx &c) { return c; }
+__device__ __forceinline__ const BeamCtx &beam_ctx(const BeamBatch &, const BeamCtx &c) { return c; }
+template <typename... U> struct beam_has_ctx { static constexpr bool value = false; };
+template <> struct beam_has_ctx<BeamCtx> { static constexpr bool value = true; };
+template <> struct beam_has_ctx<BeamBatch, BeamCtx> { static constexpr bool value = true; };
+template <typename... U> struct beam_batched { static constexpr bool value = sizeof...(U) > (beam_has_ctx<U...>::value ? 1 : 0); };
 template <typename... U> struct beam_streams { static constexpr bool value = false; };
 template <> struct beam_streams<BeamStream> { static constexpr bool value = true; };
 // the word that stops a search's kernels: `done`, a stream's `at rest`
 template <typename... U> __device__ __forceinline__ int beam_idle(const int32_t *state) { return state[beam_streams<U...>::value ? BS_REST : BS_DONE]; }
-#define BEAM_UTT(ub) const BeamBatch B = beam_batch(ub...); const unsigned u = sizeof...(U) ? blockIdx.y : 0u; const size_t uoff = u * B.stride
+#define BEAM_UTT(ub) const BeamBatch B = beam_batch(ub...); const unsigned u = beam_batched<U...>::value ? blockIdx.y : 0u; const size_t uoff = u * B.stride
 // utterance u's copy of a per-search buffer, `off` = u * stride bytes on (0 for the single search)
 template <typename T> __device__ __forceinline__ T *beam_utt(T *p, size_t off) { return (T *)((char *)p + off); }
 
@@ -317,11 +387,17 @@ __device__ __forceinline__ void beam_wave_best(float &v, int &id)
 // ---- per active slot (a workgroup of 16 waves each): log-sum-exp of the V logits, the blank logit and the `beam` best
 // non-blank labels.  Waves walk 256-entry chunks, merging each into a running list of `beam` entries (lane q holds entry q)
 // by `beam` wave-wide extractions; wave 0 merges the 16 lists the same way.
+// CTX (the pack ends with a BeamCtx): the labels are ranked by their BIASED value logit + delta(n, k) at the slot's node n.  Every label that
+// lands on the root shares the constant -bonus(n) and no label has a smaller delta, so of those the raw top-`beam` suffice; the others are
+// the EXCEPTIONS: the children of the nodes of the fail chain n, fail(n), .., root (step() takes a label at the nearest node that has it).
+// Wave 0 merges the raw list and the exceptions, 64 at a time, into the list it writes — with each label's RAW logit: k_beam_select
+// recomputes step() and adds the delta in fp64.  No step() here: a chain walk and one level of loads per node.
 template <typename... U>
 __global__ __launch_bounds__(1024) void k_beam_reduce(const int32_t *__restrict__ state, const int *__restrict__ status,
                                                       const float *__restrict__ logits, int V, int blank, int beam, float *__restrict__ red,
                                                       U... ub)
 {
+    constexpr bool CTX = beam_has_ctx<U...>::value;
     __shared__ float s_v[16][BM], s_m[16], s_s[16];
     __shared__ int s_i[16][BM];
     BEAM_UTT(ub);
@@ -399,6 +475,8 @@ __global__ __launch_bounds__(1024) void k_beam_reduce(const int32_t *__restrict_
         ci[e] = s_i[k >> 4][k & 15];
     }
     float *out = red + (size_t)j * BEAM_RED;
+    float fv = NEG;  // (CTX) entry `lane` of the raw list
+    int fi = NONE;
     for (int q = 0; q < beam; ++q) {
         float bv = cv[0];
         int bi = ci[0], bw = 0;
@@ -408,7 +486,8 @@ __global__ __launch_bounds__(1024) void k_beam_reduce(const int32_t *__restrict_
         float wv = bv;
         int wi = bi;
         beam_wave_best(wv, wi);
-        if (lane == 0) { out[16 + 2 * q] = wv; out[17 + 2 * q] = __int_as_float(wi); }
+        if constexpr (CTX) { if (lane == q) { fv = wv; fi = wi; } }
+        else if (lane == 0) { out[16 + 2 * q] = wv; out[17 + 2 * q] = __int_as_float(wi); }
         if (wi != NONE && bi == wi) {
 #pragma unroll
             for (int e = 0; e < 4; ++e)
@@ -424,6 +503,61 @@ __global__ __launch_bounds__(1024) void k_beam_reduce(const int32_t *__restrict_
         out[0] = M + logf(S);
         out[1] = x[blank];
     }
+    if constexpr (CTX) {
+        const BeamCtx &cx = beam_ctx(ub...);
+        const int n = beam_ctx_node(cx, beam_utt(cx.node, uoff)[cur * BM + j]);
+        float rv = NEG;  // entry `lane` of the biased list
+        int ri = NONE;
+        auto merge = [&](float nv, int ni) {  // the best `beam` of the list and one new candidate per lane (every copy of an extracted id goes)
+            float mv[2] = {nv, rv};
+            int mi[2] = {ni, ri};
+            float ov = NEG;
+            int oi = NONE;
+            for (int q = 0; q < beam; ++q) {
+                const bool first = beam_before(mv[0], mi[0], mv[1], mi[1]);
+                float wv = first ? mv[0] : mv[1];
+                int wi = first ? mi[0] : mi[1];
+                beam_wave_best(wv, wi);
+                if (lane == q) { ov = wv; oi = wi; }
+                if (wi != NONE) {
+#pragma unroll
+                    for (int e = 0; e < 2; ++e)
+                        if (mi[e] == wi) { mv[e] = NEG; mi[e] = NONE; }
+                }
+            }
+            rv = ov; ri = oi;
+        };
+        // Copies of one label are told apart by value alone: the copy of the NEAREST chain node is the deepest match, so the largest, and a
+        // raw entry is entered as if it landed on the root — the smallest delta there is (delta >= -bonus(n)) —, so of a label's copies the
+        // true one is extracted first and takes the others with it.  A stale copy can only keep out what the true copy would keep out.
+        const int dn = beam_ctx_depth(cx, n);
+        merge(lane < beam && fi != NONE ? fv + (float)beam_ctx_delta(cx, -dn) : NEG, lane < beam ? fi : NONE);
+        int m = n;
+        for (int hop = 0; hop <= BEAM_CTX_DEPTH; ++hop) {  // (m, lo, hi are the same in every lane)
+            int lo, hi;
+            beam_ctx_range(cx, m, lo, hi);
+            const int up = m ? beam_ctx_node(cx, cx.fail[m]) : 0;
+            for (int c0 = lo; c0 < hi; c0 += 64) {
+                float nv = NEG;
+                int ni = NONE;
+                const int c = c0 + lane;
+                if (c < hi) {
+                    const int k = cx.child_tok[c];
+                    if (k >= 0 && k < V && k != blank) {
+                        nv = x[k] + (float)beam_ctx_delta(cx, beam_ctx_depth(cx, beam_ctx_node(cx, cx.child_node[c])) - dn);
+                        ni = k;
+                    }
+                }
+                merge(nv, ni);
+            }
+            if (m == 0) break;
+            m = up;
+        }
+        if (lane < beam) {
+            out[16 + 2 * lane] = ri != NONE ? x[ri] : NEG;
+            out[17 + 2 * lane] = __int_as_float(ri);
+        }
+    }
 }
 
 __device__ bool beam_same_prefix(const int *a, const int *b, int len)  // positions 1 .. len
@@ -437,11 +571,16 @@ __device__ bool beam_same_prefix(const int *a, const int *b, int len)  // positi
 // (T then unused: the utterance's frame count is utt[u][1]): the search that ends counts itself in `n_done` and the one that
 // brings it to the n_utt = gridDim.y searches raises the host's flag.  A stream (T = base + push[u][1]) comes to REST there instead: the
 // same result, the same count (k_beam_stream_begin counted the streams without frames), and the next push resumes from this very state.
+// CTX (the pack ends with a BeamCtx): a label candidate's score takes delta(n, k) of its parent's node n in fp64 and its node is step(n, k)'s;
+// finished, blank and merged candidates keep their source's node (a node is a function of the token sequence).  The scores it keeps
+// and returns are INTERNAL: the bonus of an unfinished match is still in them (include/rnnt_engine.h: the finalisation rule).
 template <typename... U>
 __global__ __launch_bounds__(256) void k_beam_select(BeamSlots P, const float *__restrict__ red, int beam, int V, int H, int T, int max_length,
                                                      int max_per_frame, int32_t *__restrict__ state, int32_t *__restrict__ out_tokens,
                                                      double *__restrict__ out_scores, int32_t *host_flag, U... ub)
 {
+    constexpr bool CTX = beam_has_ctx<U...>::value;
+    __shared__ int c_node[CTX ? BEAM_NC : 1], o_node[CTX ? BM : 1];
     __shared__ double c_score[BEAM_NC];
     __shared__ int c_kind[BEAM_NC], c_a[BEAM_NC], c_b[BEAM_NC], c_src[BEAM_NC];
     __shared__ unsigned char c_valid[BEAM_NC];
@@ -454,13 +593,14 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamSlots P, const float *_
     if (beam_idle<U...>(state)) return;
     P = beam_utt(P, uoff); red = beam_utt(red, uoff);
     out_tokens += (size_t)u * beam * max_length; out_scores += (size_t)u * beam;
-    if (sizeof...(U)) T = B.utt[2 * u + 1] + (beam_streams<U...>::value ? state[BS_BASE] : 0);  // a stream: the frame its push ends before
+    if (beam_batched<U...>::value) T = B.utt[2 * u + 1] + (beam_streams<U...>::value ? state[BS_BASE] : 0);  // a stream: the frame its push ends before
     const int tid = threadIdx.x, cur = state[BS_CUR], nb = cur ^ 1, r = state[BS_R];
     const int *tok_old = P.tok + (size_t)cur * BM * max_length;
     if (tid < BM) {
         const int idx = cur * BM + tid;
         o_st[tid] = tid < beam ? P.status[idx] : SL_EMPTY;
         o_score[tid] = P.score[idx]; o_hash[tid] = P.hash[idx]; o_len[tid] = P.len[idx];
+        if constexpr (CTX) o_node[tid] = beam_ctx_node(beam_ctx(ub...), beam_utt(beam_ctx(ub...).node, uoff)[idx]);
     }
     if (tid < BM) s_keep[tid] = -1;
     for (int c = tid; c < BEAM_NC; c += 256) c_valid[c] = 0;
@@ -482,6 +622,11 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamSlots P, const float *_
         const int id = __float_as_int(rj[17 + 2 * q]);
         if (id < 0 || id >= V) continue;
         c_score[pos] = o_score[j] + ((double)rj[16 + 2 * q] - (double)rj[0]);
+        if constexpr (CTX) {
+            const BeamStep s = beam_ctx_step(beam_ctx(ub...), o_node[j], id);
+            c_score[pos] += beam_ctx_delta(beam_ctx(ub...), s.ddepth);
+            c_node[pos] = s.next;
+        }
         c_kind[pos] = 1; c_a[pos] = j; c_b[pos] = id; c_src[pos] = j; c_valid[pos] = 1;
     }
     __syncthreads();
@@ -569,9 +714,11 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamSlots P, const float *_
             P.hash[idx] = lab ? o_hash[src] * BEAM_HASH_MUL + (unsigned long long)(c_b[c] + 1) : o_hash[src];
             P.status[idx] = frame_end || lab ? SL_ACTIVE : SL_FINISHED;
             P.need[idx] = lab;
+            if constexpr (CTX) beam_utt(beam_ctx(ub...).node, uoff)[idx] = lab ? c_node[c] : o_node[src];
             if (done) { out_scores[tid] = c_score[c]; state[BS_LEN + tid] = o_len[src] + lab; }
         } else {
             P.score[idx] = -__builtin_inf(); P.len[idx] = 0; P.hash[idx] = 0ull; P.status[idx] = SL_EMPTY; P.need[idx] = 0;
+            if constexpr (CTX) beam_utt(beam_ctx(ub...).node, uoff)[idx] = 0;
         }
     }
     int *tok_new = P.tok + (size_t)nb * BM * max_length;
@@ -602,11 +749,10 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamSlots P, const float *_
         state[BS_CUR] = nb;
         state[beam_streams<U...>::value ? BS_REST : BS_DONE] = done;  // a stream comes to rest: its result stands as at `done`, its search goes on
         // the host's cue to stop enqueueing rounds (mapped pinned memory, polled without a synchronisation)
-        const bool all_done = done && (!sizeof...(U) || atomicAdd(B.n_done, 1u) + 1 == gridDim.y);
+        const bool all_done = done && (!beam_batched<U...>::value || atomicAdd(B.n_done, 1u) + 1 == gridDim.y);
         if (all_done && host_flag) __hip_atomic_store(host_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
-
 // ---- a stream's start: k_beam_init's state for stream `first + blockIdx.x` of the (zero-filled) block, at rest, and the
 // result of zero frames: one entry, no labels, log-probability 0
 __global__ void k_beam_stream_init(BeamSlots P, int32_t *state, double *scores, int blank, int beam, size_t stride, int first)
@@ -645,8 +791,8 @@ __global__ __launch_bounds__(64) void k_beam_stream_begin(int32_t *__restrict__ 
 
 // ---- workspace: per utterance { slot buffers | predictor intermediates | logits | reduce output }, `block` bytes each; then the
 // batched search's done counter and the model's tables (when built here)
-struct BeamLayout { size_t score, hash, len, status, need, tok, pvec, g1, g2, z, logits, red, block, n_done, state_end, tables, total; };
-static BeamLayout beam_layout(int S, int E, int O, int H, int V, int has_text, int max_length, int n_utt, bool batched)
+struct BeamLayout { size_t score, hash, len, status, need, tok, pvec, g1, g2, z, logits, red, node, block, n_done, state_end, tables, total; };
+static BeamLayout beam_layout(int S, int E, int O, int H, int V, int has_text, int max_length, int n_utt, bool batched, bool ctx = false)
 {
     BeamLayout L;
     size_t o = 0;
@@ -663,6 +809,7 @@ static BeamLayout beam_layout(int S, int E, int O, int H, int V, int has_text, i
     L.z = take((size_t)BM * O * 4);
     L.logits = take((size_t)BM * V * 4);
     L.red = take((size_t)BM * BEAM_RED * 4);
+    L.node = take(ctx ? 2 * BM * 4 : 0);  // (a search with a context graph only: the others' layout is what it was)
     L.block = o;
     o *= (size_t)n_utt;
     L.n_done = take(batched ? 4 : 0);
@@ -671,13 +818,13 @@ static BeamLayout beam_layout(int S, int E, int O, int H, int V, int has_text, i
     L.total = o;
     return L;
 }
-size_t beam_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length)
+size_t beam_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, bool ctx)
 {
-    return beam_layout(S, E, O, H, V, has_text, max_length, 1, false).total;
+    return beam_layout(S, E, O, H, V, has_text, max_length, 1, false, ctx).total;
 }
-size_t beam_batch_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int n_utt)
+size_t beam_batch_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int n_utt, bool ctx)
 {
-    return beam_layout(S, E, O, H, V, has_text, max_length, n_utt, true).total;
+    return beam_layout(S, E, O, H, V, has_text, max_length, n_utt, true, ctx).total;
 }
 // a group of streams' persistent block: the batch's per-search parts and its counter (the tables are the caller's)
 size_t beam_stream_block_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int n_streams)
@@ -712,9 +859,15 @@ void launch_beam_decode(const BeamArgs &ba, hipStream_t st)
     const int S = a.S, E = a.E, O = a.O, H = a.H, V = a.V, ML = a.max_length, has_text = a.text_W ? 1 : 0;
     const bool batched = ba.utt != nullptr;
     const unsigned N = batched ? ba.n_utt : 1;
-    const BeamLayout L = beam_layout(S, E, O, H, V, has_text, ML, N, batched);
+    const bool ctx = ba.ctx != nullptr;  // (never with ba.streaming)
+    const BeamLayout L = beam_layout(S, E, O, H, V, has_text, ML, N, batched, ctx);
     char *ws = (char *)a.workspace;
     const BeamSlots P = beam_slots(ws, L);
+    BeamCtx cx{};
+    if (ctx) {
+        const rnnt_beam_context &g = *ba.ctx;
+        cx = BeamCtx{g.child_off, g.child_tok, g.child_node, g.fail_link, g.depth, g.terminal, g.n_nodes, g.n_children, g.score, (int *)(ws + L.node)};
+    }
     float *g1 = (float *)(ws + L.g1), *g2 = (float *)(ws + L.g2), *z = (float *)(ws + L.z);
     float *logits = (float *)(ws + L.logits), *red = (float *)(ws + L.red);
     const float *tb = (const float *)a.tables;
@@ -727,8 +880,9 @@ void launch_beam_decode(const BeamArgs &ba, hipStream_t st)
     dec_tables_offsets(S, E, O, H, has_text, &otab, &owp2);
     const float *tab = tb + otab, *wp2 = tb + owp2;
     const float *nul = nullptr;
-    // `ub`: nothing (the single search's kernels) or the batch's BeamBatch
-    auto enqueue = [&](auto... ub) {
+    // `ub`: nothing (the single search's kernels) or the batch's BeamBatch; `with_ctx`: the reduce and the selection get the BeamCtx as the pack's last member
+    // (a search with a context graph) — every other kernel, and every kernel of a search without one, is what it was
+    auto enqueue_as = [&](auto with_ctx, auto... ub) {
         if (a.init && !ba.streaming)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_init<decltype(ub)...>), dim3(1, N), dim3(64), 0, st, P, a.state, a.blank, ML, ub...);
         for (int it = 0; it < a.iterations; ++it) {
@@ -750,16 +904,28 @@ void launch_beam_decode(const BeamArgs &ba, hipStream_t st)
                                    a.p.ln_out_w, a.p.ln_out_b, a.ln_eps, P.pvec, ub...);
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_joint<decltype(ub)...>), dim3((V + 15) / 16, N), dim3(256), 0, st, a.state, a.frames,
                                a.frame_stride, P.pvec, a.W, a.bias, H, V, logits, ub...);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_reduce<decltype(ub)...>), dim3(ba.beam, N), dim3(1024), 0, st, a.state, P.status, logits, V,
-                               a.blank, ba.beam, red, ub...);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_select<decltype(ub)...>), dim3(1, N), dim3(256), 0, st, P, red, ba.beam, V, H, a.T, ML,
-                               a.max_per_frame, a.state, a.tokens, ba.scores, a.host_flag, ub...);
+            if constexpr (decltype(with_ctx)::value) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_reduce<decltype(ub)..., BeamCtx>), dim3(ba.beam, N), dim3(1024), 0, st, a.state,
+                                   P.status, logits, V, a.blank, ba.beam, red, ub..., cx);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_select<decltype(ub)..., BeamCtx>), dim3(1, N), dim3(256), 0, st, P, red, ba.beam, V, H,
+                                   a.T, ML, a.max_per_frame, a.state, a.tokens, ba.scores, a.host_flag, ub..., cx);
+            } else {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_reduce<decltype(ub)...>), dim3(ba.beam, N), dim3(1024), 0, st, a.state, P.status, logits,
+                                   V, a.blank, ba.beam, red, ub...);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_select<decltype(ub)...>), dim3(1, N), dim3(256), 0, st, P, red, ba.beam, V, H, a.T, ML,
+                                   a.max_per_frame, a.state, a.tokens, ba.scores, a.host_flag, ub...);
+            }
         }
     };
+    auto enqueue = [&](auto... ub) { enqueue_as(std::false_type{}, ub...); };
+    auto enqueue_ctx = [&](auto... ub) { enqueue_as(std::true_type{}, ub...); };
     if (ba.streaming) {
         unsigned *n_rest = (unsigned *)(ws + L.n_done);
         if (a.init) hipLaunchKernelGGL(k_beam_stream_begin, dim3(1), dim3(64), 0, st, a.state, ba.utt, (int)N, n_rest, a.host_flag);
         enqueue(BeamStream{L.block, ba.utt, ba.rows, n_rest});
+    } else if (ctx) {
+        if (batched) enqueue_ctx(BeamBatch{L.block, ba.utt, ba.rows, (unsigned *)(ws + L.n_done)});
+        else enqueue_ctx();
     } else if (batched)
         enqueue(BeamBatch{L.block, ba.utt, ba.rows, (unsigned *)(ws + L.n_done)});
     else

@@ -792,7 +792,7 @@ int rnnt_engine_greedy_decode(const void *frames, int64_t frame_stride, int T, c
     return launch_status("rnnt_engine_greedy_decode");
 }
 
-int rnnt_engine_beam_decode_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int beam, size_t *out)
+static int beam_ws_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int beam, bool ctx, size_t *out)
 {
     if (!out) return fail(RNNT_ERR_INVALID_ARG, "null size pointer");
     if (beam < 1) return fail(RNNT_ERR_INVALID_ARG, "beam=%d must be >= 1", beam);
@@ -804,18 +804,47 @@ int rnnt_engine_beam_decode_workspace_bytes(int S, int E, int O, int H, int V, i
     if (E < 4 || O < 4 || E > 1024 || O > 1024 || E % 4 || O % 4)
         return fail(RNNT_ERR_UNSUPPORTED, "beam decode needs 4 <= E, O <= 1024, multiples of 4 (E=%d, O=%d)", E, O);
     if (!has_text && O != H) return fail(RNNT_ERR_INVALID_ARG, "without text_ln the predictor's output dim (%d) must equal H (%d)", O, H);
-    *out = align_up(beam_workspace_bytes(S, E, O, H, V, has_text ? 1 : 0, max_length));
+    *out = align_up(beam_workspace_bytes(S, E, O, H, V, has_text ? 1 : 0, max_length, ctx));
+    return RNNT_OK;
+}
+int rnnt_engine_beam_decode_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int beam, size_t *out)
+{
+    return beam_ws_bytes(S, E, O, H, V, has_text, max_length, beam, false, out);
+}
+int rnnt_engine_beam_decode_ctx_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int beam, size_t *out)
+{
+    return beam_ws_bytes(S, E, O, H, V, has_text, max_length, beam, true, out);
+}
+
+// the context graph of the _ctx entry points: everything the host can see of it (its arrays' contents are the kernels' to distrust)
+static int beam_check_ctx(const rnnt_beam_context *g)
+{
+    if (!g) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument (ctx)");
+    if (!g->child_off || !g->child_tok || !g->child_node || !g->fail_link || !g->depth || !g->terminal)
+        return fail(RNNT_ERR_INVALID_ARG, "null pointer argument (an array of the context graph)");
+    if (g->n_nodes < 1 || g->n_children < 0 || g->n_children >= g->n_nodes)  // (a trie: every node but the root is one child)
+        return fail(RNNT_ERR_INVALID_ARG, "context graph: n_nodes=%d n_children=%d (n_nodes >= 1, 0 <= n_children < n_nodes)", g->n_nodes,
+                    g->n_children);
+    if (g->n_nodes > RNNT_BEAM_CONTEXT_MAX_NODES)
+        return fail(RNNT_ERR_UNSUPPORTED, "context graph: n_nodes=%d above %d", g->n_nodes, RNNT_BEAM_CONTEXT_MAX_NODES);
+    if (!(g->score >= 0.0) || g->score > 1.7976931348623157e308)
+        return fail(RNNT_ERR_INVALID_ARG, "context graph: score=%g must be finite and >= 0", g->score);
+    for (const int32_t *a : {g->child_off, g->child_tok, g->child_node, g->fail_link, g->depth, g->terminal})
+        if ((uintptr_t)a & 3) return fail(RNNT_ERR_INVALID_ARG, "context graph: arrays must be 4-byte aligned");
     return RNNT_OK;
 }
 
-int rnnt_engine_beam_decode(const void *frames, int64_t frame_stride, int T, const rnnt_conv_predictor_params *p,
-                            int S, int E, int O, float ln_in_eps, float ln_out_eps, const void *text_W, const void *text_b,
-                            const void *W, const void *bias, int H, int V, int blank, int max_length, int max_per_frame,
-                            int beam, const void *tables, int iterations, int init, int32_t *host_flag, int32_t *state,
-                            int32_t *tokens, double *scores, void *workspace, size_t ws_bytes, void *stream)
+static int beam_decode_any(const void *frames, int64_t frame_stride, int T, const rnnt_conv_predictor_params *p,
+                           int S, int E, int O, float ln_in_eps, float ln_out_eps, const void *text_W, const void *text_b,
+                           const void *W, const void *bias, int H, int V, int blank, int max_length, int max_per_frame,
+                           int beam, const void *tables, int iterations, int init, int32_t *host_flag, int32_t *state,
+                           int32_t *tokens, double *scores, void *workspace, size_t ws_bytes, const rnnt_beam_context *ctx, bool with_ctx,
+                           void *stream, const char *name)
 {
     size_t need;
-    if (int rc = rnnt_engine_beam_decode_workspace_bytes(S, E, O, H, V, text_W ? 1 : 0, max_length, beam, &need)) return rc;
+    if (int rc = beam_ws_bytes(S, E, O, H, V, text_W ? 1 : 0, max_length, beam, with_ctx, &need)) return rc;
+    if (with_ctx)
+        if (int rc = beam_check_ctx(ctx)) return rc;
     if (iterations < 0) return fail(RNNT_ERR_INVALID_ARG, "iterations=%d", iterations);
     if (!scores) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument (scores)");
     if (tables && !aligned16(tables)) return fail(RNNT_ERR_INVALID_ARG, "tables must be 16-byte aligned");
@@ -831,29 +860,62 @@ int rnnt_engine_beam_decode(const void *frames, int64_t frame_stride, int T, con
     a.d.tables = tables;
     a.beam = beam;
     a.scores = scores;
+    a.ctx = with_ctx ? ctx : nullptr;
     launch_beam_decode(a, (hipStream_t)stream);
-    return launch_status("rnnt_engine_beam_decode");
+    return launch_status(name);
+}
+int rnnt_engine_beam_decode(const void *frames, int64_t frame_stride, int T, const rnnt_conv_predictor_params *p,
+                            int S, int E, int O, float ln_in_eps, float ln_out_eps, const void *text_W, const void *text_b,
+                            const void *W, const void *bias, int H, int V, int blank, int max_length, int max_per_frame,
+                            int beam, const void *tables, int iterations, int init, int32_t *host_flag, int32_t *state,
+                            int32_t *tokens, double *scores, void *workspace, size_t ws_bytes, void *stream)
+{
+    return beam_decode_any(frames, frame_stride, T, p, S, E, O, ln_in_eps, ln_out_eps, text_W, text_b, W, bias, H, V, blank, max_length,
+                           max_per_frame, beam, tables, iterations, init, host_flag, state, tokens, scores, workspace, ws_bytes, nullptr, false,
+                           stream, "rnnt_engine_beam_decode");
+}
+int rnnt_engine_beam_decode_ctx(const void *frames, int64_t frame_stride, int T, const rnnt_conv_predictor_params *p,
+                                int S, int E, int O, float ln_in_eps, float ln_out_eps, const void *text_W, const void *text_b,
+                                const void *W, const void *bias, int H, int V, int blank, int max_length, int max_per_frame,
+                                int beam, const void *tables, int iterations, int init, int32_t *host_flag, int32_t *state,
+                                int32_t *tokens, double *scores, void *workspace, size_t ws_bytes, const rnnt_beam_context *ctx,
+                                void *stream)
+{
+    return beam_decode_any(frames, frame_stride, T, p, S, E, O, ln_in_eps, ln_out_eps, text_W, text_b, W, bias, H, V, blank, max_length,
+                           max_per_frame, beam, tables, iterations, init, host_flag, state, tokens, scores, workspace, ws_bytes, ctx, true,
+                           stream, "rnnt_engine_beam_decode_ctx");
 }
 
-int rnnt_engine_beam_decode_batch_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int beam, int n_utt,
-                                                  size_t *out)
+static int beam_batch_ws_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int beam, int n_utt, bool ctx, size_t *out)
 {
     if (!out) return fail(RNNT_ERR_INVALID_ARG, "null size pointer");
     if (n_utt < 1 || n_utt > 64) return fail(RNNT_ERR_UNSUPPORTED, "batched beam decode takes 1 <= n_utt <= 64 (n_utt=%d)", n_utt);
-    if (int rc = rnnt_engine_beam_decode_workspace_bytes(S, E, O, H, V, has_text, max_length, beam, out)) return rc;
-    *out = align_up(beam_batch_workspace_bytes(S, E, O, H, V, has_text ? 1 : 0, max_length, n_utt));
+    if (int rc = beam_ws_bytes(S, E, O, H, V, has_text, max_length, beam, ctx, out)) return rc;
+    *out = align_up(beam_batch_workspace_bytes(S, E, O, H, V, has_text ? 1 : 0, max_length, n_utt, ctx));
     return RNNT_OK;
 }
+int rnnt_engine_beam_decode_batch_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int beam, int n_utt,
+                                                  size_t *out)
+{
+    return beam_batch_ws_bytes(S, E, O, H, V, has_text, max_length, beam, n_utt, false, out);
+}
+int rnnt_engine_beam_decode_batch_ctx_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int beam,
+                                                      int n_utt, size_t *out)
+{
+    return beam_batch_ws_bytes(S, E, O, H, V, has_text, max_length, beam, n_utt, true, out);
+}
 
-int rnnt_engine_beam_decode_batch(const void *frames, int64_t frame_stride, int rows, const int32_t *utt, int n_utt, int max_frames,
-                                  const rnnt_conv_predictor_params *p, int S, int E, int O, float ln_in_eps, float ln_out_eps,
-                                  const void *text_W, const void *text_b, const void *W, const void *bias, int H, int V, int blank,
-                                  int max_length, int max_per_frame, int beam, const void *tables, int iterations, int init,
-                                  int32_t *host_flag, int32_t *state, int32_t *tokens, double *scores, void *workspace, size_t ws_bytes,
-                                  void *stream)
+static int beam_decode_batch_any(const void *frames, int64_t frame_stride, int rows, const int32_t *utt, int n_utt, int max_frames,
+                                 const rnnt_conv_predictor_params *p, int S, int E, int O, float ln_in_eps, float ln_out_eps,
+                                 const void *text_W, const void *text_b, const void *W, const void *bias, int H, int V, int blank,
+                                 int max_length, int max_per_frame, int beam, const void *tables, int iterations, int init,
+                                 int32_t *host_flag, int32_t *state, int32_t *tokens, double *scores, void *workspace, size_t ws_bytes,
+                                 const rnnt_beam_context *ctx, bool with_ctx, void *stream, const char *name)
 {
     size_t need;
-    if (int rc = rnnt_engine_beam_decode_batch_workspace_bytes(S, E, O, H, V, text_W ? 1 : 0, max_length, beam, n_utt, &need)) return rc;
+    if (int rc = beam_batch_ws_bytes(S, E, O, H, V, text_W ? 1 : 0, max_length, beam, n_utt, with_ctx, &need)) return rc;
+    if (with_ctx)
+        if (int rc = beam_check_ctx(ctx)) return rc;
     if (iterations < 0) return fail(RNNT_ERR_INVALID_ARG, "iterations=%d", iterations);
     if (!scores || !utt) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument (scores / utt)");
     if ((uintptr_t)utt & 7) return fail(RNNT_ERR_INVALID_ARG, "utt must be 8-byte aligned");
@@ -874,8 +936,31 @@ int rnnt_engine_beam_decode_batch(const void *frames, int64_t frame_stride, int 
     a.beam = beam;
     a.scores = scores;
     a.utt = utt; a.n_utt = n_utt; a.rows = rows;
+    a.ctx = with_ctx ? ctx : nullptr;
     launch_beam_decode(a, (hipStream_t)stream);
-    return launch_status("rnnt_engine_beam_decode_batch");
+    return launch_status(name);
+}
+int rnnt_engine_beam_decode_batch(const void *frames, int64_t frame_stride, int rows, const int32_t *utt, int n_utt, int max_frames,
+                                  const rnnt_conv_predictor_params *p, int S, int E, int O, float ln_in_eps, float ln_out_eps,
+                                  const void *text_W, const void *text_b, const void *W, const void *bias, int H, int V, int blank,
+                                  int max_length, int max_per_frame, int beam, const void *tables, int iterations, int init,
+                                  int32_t *host_flag, int32_t *state, int32_t *tokens, double *scores, void *workspace, size_t ws_bytes,
+                                  void *stream)
+{
+    return beam_decode_batch_any(frames, frame_stride, rows, utt, n_utt, max_frames, p, S, E, O, ln_in_eps, ln_out_eps, text_W, text_b, W, bias,
+                                 H, V, blank, max_length, max_per_frame, beam, tables, iterations, init, host_flag, state, tokens, scores,
+                                 workspace, ws_bytes, nullptr, false, stream, "rnnt_engine_beam_decode_batch");
+}
+int rnnt_engine_beam_decode_batch_ctx(const void *frames, int64_t frame_stride, int rows, const int32_t *utt, int n_utt, int max_frames,
+                                      const rnnt_conv_predictor_params *p, int S, int E, int O, float ln_in_eps, float ln_out_eps,
+                                      const void *text_W, const void *text_b, const void *W, const void *bias, int H, int V, int blank,
+                                      int max_length, int max_per_frame, int beam, const void *tables, int iterations, int init,
+                                      int32_t *host_flag, int32_t *state, int32_t *tokens, double *scores, void *workspace,
+                                      size_t ws_bytes, const rnnt_beam_context *ctx, void *stream)
+{
+    return beam_decode_batch_any(frames, frame_stride, rows, utt, n_utt, max_frames, p, S, E, O, ln_in_eps, ln_out_eps, text_W, text_b, W, bias,
+                                 H, V, blank, max_length, max_per_frame, beam, tables, iterations, init, host_flag, state, tokens, scores,
+                                 workspace, ws_bytes, ctx, true, stream, "rnnt_engine_beam_decode_batch_ctx");
 }
 
 int rnnt_engine_beam_stream_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int beam, int n_streams, size_t *out)

@@ -296,9 +296,12 @@ struct BeamArgs {
     // a push of n_utt streams (rnnt_engine_beam_stream_push): utt is the push's table, d.workspace the streams' persistent block (its layout:
     // beam_stream_block_bytes), d.tables required, d.init = open the push (k_beam_stream_begin) before the rounds
     bool streaming = false;
+    // contextual biasing (rnnt_engine_beam_decode_ctx / _batch_ctx; never with streaming): the caller's graph, its arrays on the device;
+    // the workspace is then the one of beam_workspace_bytes(..., ctx = true) (a node per slot more)
+    const rnnt_beam_context *ctx = nullptr;
 };
-size_t beam_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length);
-size_t beam_batch_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int n_utt);
+size_t beam_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, bool ctx = false);
+size_t beam_batch_workspace_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int n_utt, bool ctx = false);
 void launch_beam_decode(const BeamArgs &a, hipStream_t st);
 size_t beam_stream_block_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int n_streams);
 void launch_beam_stream_init(void *block, int32_t *state, double *scores, int S, int E, int O, int H, int V, int has_text, int max_length,

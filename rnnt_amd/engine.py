@@ -86,6 +86,10 @@ SIGNATURES = {
     "rnnt_engine_beam_decode": "pqipiiiffppppiiiiiipiipppppzp",
     "rnnt_engine_beam_decode_batch_workspace_bytes": "iiiiiiiiip",
     "rnnt_engine_beam_decode_batch": "pqipiipiiiffppppiiiiiipiipppppzp",
+    "rnnt_engine_beam_decode_ctx_workspace_bytes": "iiiiiiiip",
+    "rnnt_engine_beam_decode_ctx": "pqipiiiffppppiiiiiipiipppppzpp",
+    "rnnt_engine_beam_decode_batch_ctx_workspace_bytes": "iiiiiiiiip",
+    "rnnt_engine_beam_decode_batch_ctx": "pqipiipiiiffppppiiiiiipiipppppzpp",
     "rnnt_engine_beam_stream_bytes": "iiiiiiiiip",
     "rnnt_engine_beam_stream_init": "iiiiiiiiiiipppzp",
     "rnnt_engine_beam_stream_push": "pqipiipiiiffppppiiiiiipiipppppzp",
@@ -134,6 +138,8 @@ EXPORTS = (
     "rnnt_engine_beam_decode_workspace_bytes", "rnnt_engine_beam_decode",
     "rnnt_engine_beam_decode_batch_workspace_bytes", "rnnt_engine_beam_decode_batch",
     "rnnt_engine_beam_stream_bytes", "rnnt_engine_beam_stream_init", "rnnt_engine_beam_stream_push",
+    "rnnt_engine_beam_decode_ctx_workspace_bytes", "rnnt_engine_beam_decode_ctx",
+    "rnnt_engine_beam_decode_batch_ctx_workspace_bytes", "rnnt_engine_beam_decode_batch_ctx",
     "rnnt_engine_joint_loss_fwd", "rnnt_engine_run_stages",
     "rnnt_engine_joint_bwd_workspace_bytes", "rnnt_engine_joint_bwd",
     "rnnt_engine_grad_norm_workspace_bytes", "rnnt_engine_grad_norm", "rnnt_engine_adamw_step",
@@ -919,6 +925,26 @@ def greedy_stream_decode(frames, pred_params, ln_eps, text_W, text_b, W, bias, b
 
 
 BEAM_MAX = 16  # rnnt_engine_beam_decode: 1 <= beam <= 16 (the slots are the M = 16 rows of every product)
+BEAM_CONTEXT_MAX_NODES = 65536  # include/rnnt_engine.h RNNT_BEAM_CONTEXT_MAX_NODES
+
+
+class _BeamContext(ctypes.Structure):  # include/rnnt_engine.h: rnnt_beam_context
+    _fields_ = [("n_nodes", ctypes.c_int32), ("n_children", ctypes.c_int32), ("score", ctypes.c_double)] + [
+        (n, ctypes.c_void_p) for n in ("child_off", "child_tok", "child_node", "fail_link", "depth", "terminal")]
+
+
+def _beam_context(context, dev):
+    """`context` (None, or the dict of ContextGraph.device_tables: int32 tensors on the search's device and n_nodes, n_children, score)
+    -> (the rnnt_beam_context to pass, the tensors to keep alive)."""
+    if context is None:
+        return None, ()
+    arrays = [context[n] for n in ("child_off", "child_tok", "child_node", "fail_link", "depth", "terminal")]
+    n_nodes, n_children = int(context["n_nodes"]), int(context["n_children"])
+    for name, t, need in zip(("child_off", "child_tok", "child_node", "fail_link", "depth", "terminal"), arrays,
+                             (n_nodes + 1, n_children, n_children, n_nodes, n_nodes, n_nodes)):
+        if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous() or t.numel() < max(need, 1):
+            raise RuntimeError(f"beam context: {name} must be a contiguous int32 tensor of >= {max(need, 1)} entries on {dev}")
+    return _BeamContext(n_nodes, n_children, float(context["score"]), *[t.data_ptr() for t in arrays]), tuple(arrays)
 
 
 def beam_decode_supported(S, E, O, H, V, has_text, max_length, beam):
@@ -929,13 +955,15 @@ def beam_decode_supported(S, E, O, H, V, has_text, max_length, beam):
 
 
 def beam_decode(frames, pred_params, ln_eps, text_W, text_b, W, bias, blank, max_length, beam, max_per_frame=10, tables=None,
-                chunk=32, in_flight=2):
+                chunk=32, in_flight=2, context=None):
     """Frame-synchronous beam search of one utterance on the device (C ABI rnnt_engine_beam_decode).  Arguments as
     greedy_decode_loop, plus `beam` (1 .. 16) and `tables` (greedy_decode_tables(...) of the same parameters, or None: rebuilt inside).
     Rounds are enqueued `chunk` at a time until the device has raised the end flag in a pinned host word (polled, never waited for);
     at most `in_flight` chunks are ahead of the device (the host waits for the oldest one's completion event), so the rounds enqueued
     after the end stay few.  Returns (state int32[32], tokens int32[beam, max_length], scores float64[beam]) device tensors WITHOUT a
-    final synchronisation: afterwards entry j < state[2] is tokens[j, 1 : 1 + state[8 + j]] with log-probability scores[j], best first."""
+    final synchronisation: afterwards entry j < state[2] is tokens[j, 1 : 1 + state[8 + j]] with log-probability scores[j], best first.
+    `context` (ContextGraph.device_tables(device)): the search biased by a phrase list (C ABI rnnt_engine_beam_decode_ctx; DESIGN.md §4h
+    "Context") — the scores are then INTERNAL and the order is theirs: the caller finalises (ContextGraph.finalise)."""
     dev, frames, params, text_W, text_b, W, bias = _decode_inputs(frames, pred_params, text_W, text_b, W, bias)
     T, H = frames.shape
     V = W.shape[0]
@@ -946,7 +974,9 @@ def beam_decode(frames, pred_params, ln_eps, text_W, text_b, W, bias, blank, max
     bound = T * max(1, max_per_frame) + 1
     with torch.cuda.device(dev):
         n = ctypes.c_size_t(0)
-        _check(lib().rnnt_engine_beam_decode_workspace_bytes(S, E, O, H, V, 1 if text_W is not None else 0, max_length, beam, ctypes.byref(n)))
+        cx, cx_keep = _beam_context(context, dev)
+        query = lib().rnnt_engine_beam_decode_workspace_bytes if cx is None else lib().rnnt_engine_beam_decode_ctx_workspace_bytes
+        _check(query(S, E, O, H, V, 1 if text_W is not None else 0, max_length, beam, ctypes.byref(n)))
         ws = workspace(dev, n.value)
         state = torch.empty(32, dtype=torch.int32, device=dev)
         tokens = torch.empty(beam, max_length, dtype=torch.int32, device=dev)
@@ -959,18 +989,21 @@ def beam_decode(frames, pred_params, ln_eps, text_W, text_b, W, bias, blank, max
         done = 0
         while done < bound and (done == 0 or int(flag[0]) == 0):
             it = min(chunk, bound - done)
-            _check(lib().rnnt_engine_beam_decode(
-                _p(frames), ctypes.c_int64(frames.stride(0)), T, ctypes.byref(st), S, E, O, ctypes.c_float(eps_in), ctypes.c_float(eps_out),
-                _p(text_W), _p(text_b), _p(W), _p(bias), H, V, int(blank), max_length, max_per_frame, beam, _p(tables), it,
-                1 if done == 0 else 0, ctypes.c_void_p(flag.data_ptr()), _p(state), _p(tokens), _p(scores), _p(ws),
-                ctypes.c_size_t(ws.numel()), stream))
+            args = (_p(frames), ctypes.c_int64(frames.stride(0)), T, ctypes.byref(st), S, E, O, ctypes.c_float(eps_in), ctypes.c_float(eps_out),
+                    _p(text_W), _p(text_b), _p(W), _p(bias), H, V, int(blank), max_length, max_per_frame, beam, _p(tables), it,
+                    1 if done == 0 else 0, ctypes.c_void_p(flag.data_ptr()), _p(state), _p(tokens), _p(scores), _p(ws),
+                    ctypes.c_size_t(ws.numel()))
+            if cx is None:
+                _check(lib().rnnt_engine_beam_decode(*args, stream))
+            else:
+                _check(lib().rnnt_engine_beam_decode_ctx(*args, ctypes.byref(cx), stream))
             done += it
             ev = torch.cuda.Event()
             ev.record()
             pending.append(ev)
             if len(pending) > max(1, int(in_flight)):
                 pending.pop(0).synchronize()
-        state._keepalive = (flag, frames, params, W, bias, text_W, text_b, tables)  # until the caller has synchronised
+        state._keepalive = (flag, frames, params, W, bias, text_W, text_b, tables, cx_keep)  # until the caller has synchronised
     return state, tokens, scores
 
 
@@ -985,13 +1018,14 @@ def beam_decode_batch_supported(S, E, O, H, V, has_text, max_length, beam, n_utt
 
 
 def beam_decode_batch(frames_list, pred_params, ln_eps, text_W, text_b, W, bias, blank, max_length, beam, max_per_frame=10, tables=None,
-                      chunk=32, in_flight=2):
+                      chunk=32, in_flight=2, context=None):
     """The beam search of beam_decode for SEVERAL utterances of one model, advanced in lockstep on the device (C ABI
     rnnt_engine_beam_decode_batch; DESIGN.md §4h "Batched"): `frames_list` holds 1 .. 64 [T_u, H] fp32 frame tensors (audio_ln applied),
     packed here into one buffer; the table of first rows and lengths is the call's one small host-to-device copy.  The other arguments
     and the enqueueing (chunks of rounds, the pinned end flag — raised when ALL searches have ended —, `in_flight`) as beam_decode.
     Returns (state int32[N, 32], tokens int32[N, beam, max_length], scores float64[N, beam]) device tensors WITHOUT a final
-    synchronisation; row u of each is what beam_decode returns for frames_list[u] alone, bit for bit."""
+    synchronisation; row u of each is what beam_decode returns for frames_list[u] alone, bit for bit.  `context` as beam_decode's: ONE
+    graph biases every utterance of the batch (C ABI rnnt_engine_beam_decode_batch_ctx)."""
     frames_list = list(frames_list)
     if not frames_list:
         raise ValueError("beam_decode_batch: no utterance")
@@ -1013,8 +1047,9 @@ def beam_decode_batch(frames_list, pred_params, ln_eps, text_W, text_b, W, bias,
         begins.append(begins[-1] + t)
     with torch.cuda.device(dev):
         n = ctypes.c_size_t(0)
-        _check(lib().rnnt_engine_beam_decode_batch_workspace_bytes(S, E, O, H, V, 1 if text_W is not None else 0, max_length, beam, N,
-                                                                   ctypes.byref(n)))
+        cx, cx_keep = _beam_context(context, dev)
+        query = lib().rnnt_engine_beam_decode_batch_workspace_bytes if cx is None else lib().rnnt_engine_beam_decode_batch_ctx_workspace_bytes
+        _check(query(S, E, O, H, V, 1 if text_W is not None else 0, max_length, beam, N, ctypes.byref(n)))
         ws = workspace(dev, n.value)
         utt = torch.tensor(list(zip(begins, lens)), dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
         state = torch.empty(N, 32, dtype=torch.int32, device=dev)
@@ -1028,18 +1063,21 @@ def beam_decode_batch(frames_list, pred_params, ln_eps, text_W, text_b, W, bias,
         done = 0
         while done < bound and (done == 0 or int(flag[0]) == 0):
             it = min(chunk, bound - done)
-            _check(lib().rnnt_engine_beam_decode_batch(
-                _p(packed), ctypes.c_int64(packed.stride(0)), rows, _p(utt), N, max(lens), ctypes.byref(st), S, E, O, ctypes.c_float(eps_in),
-                ctypes.c_float(eps_out), _p(text_W), _p(text_b), _p(W), _p(bias), H, V, int(blank), max_length, max_per_frame, beam,
-                _p(tables), it, 1 if done == 0 else 0, ctypes.c_void_p(flag.data_ptr()), _p(state), _p(tokens), _p(scores), _p(ws),
-                ctypes.c_size_t(ws.numel()), stream))
+            args = (_p(packed), ctypes.c_int64(packed.stride(0)), rows, _p(utt), N, max(lens), ctypes.byref(st), S, E, O, ctypes.c_float(eps_in),
+                    ctypes.c_float(eps_out), _p(text_W), _p(text_b), _p(W), _p(bias), H, V, int(blank), max_length, max_per_frame, beam,
+                    _p(tables), it, 1 if done == 0 else 0, ctypes.c_void_p(flag.data_ptr()), _p(state), _p(tokens), _p(scores), _p(ws),
+                    ctypes.c_size_t(ws.numel()))
+            if cx is None:
+                _check(lib().rnnt_engine_beam_decode_batch(*args, stream))
+            else:
+                _check(lib().rnnt_engine_beam_decode_batch_ctx(*args, ctypes.byref(cx), stream))
             done += it
             ev = torch.cuda.Event()
             ev.record()
             pending.append(ev)
             if len(pending) > max(1, int(in_flight)):
                 pending.pop(0).synchronize()
-        state._keepalive = (flag, utt, packed, params, W, bias, text_W, text_b, tables)  # until the caller has synchronised
+        state._keepalive = (flag, utt, packed, params, W, bias, text_W, text_b, tables, cx_keep)  # until the caller has synchronised
     return state, tokens, scores
 
 

@@ -230,13 +230,18 @@ class RNNTModel(torch.nn.Module):
     # ---- beam search: frame-synchronous, <= max_symbols_per_frame labels per frame, hypotheses merged by sequence
     @torch.no_grad()
     def beam_search(self, mel_features: torch.Tensor, mel_feature_lens: torch.Tensor, beam_size: int = 4, max_length: int = 200,
-                    max_symbols_per_frame: int = 10, return_nbest: bool = False):
+                    max_symbols_per_frame: int = 10, return_nbest: bool = False, context=None):
         """Beam search over the whole encoder output (like greedy_decode, `mel_feature_lens` is not used).  Returns the best
         entry's token list, or with `return_nbest` the final beam as [(tokens, log-probability), ...] best first.  beam_size 1 is
         greedy_decode's result.  The search runs on the device (rnnt_engine_beam_decode: a fixed kernel sequence per round, one
         synchronisation per utterance) where greedy_decode's device loop does — engine ConvPredictor, eval mode, fp32 HIP tensors,
         sizes the kernels cover, beam_size <= 16 — else as a plain-torch host loop of the same search over any stateless
-        `predictor(ids)` and `joint.single_forward` (CPU too).  A stateful (LSTM) predictor raises NotImplementedError."""
+        `predictor(ids)` and `joint.single_forward` (CPU too).  A stateful (LSTM) predictor raises NotImplementedError.
+        `context` (a rnnt_amd.ContextGraph: phrases and a boost per matched token) biases the search towards the caller's phrases
+        (DESIGN.md §4h "Context"): on the device where the plain search is (graphs of up to 65536 nodes; the n-best list is finalised
+        and re-sorted on the host), else in the host loop.  The scores returned are FINALISED — the bonus of a match still unfinished at
+        the end is taken back; banked phrases keep theirs.  With a graph beam_size 1 is no longer the greedy decode.  None, a graph
+        without phrases and score 0 give exactly the plain search."""
         assert mel_features.shape[0] == 1, "Beam search only works with a batch size of 1"
         beam_size, max_length, m = int(beam_size), int(max_length), int(max_symbols_per_frame)
         if beam_size < 1 or m < 1:
@@ -244,23 +249,36 @@ class RNNTModel(torch.nn.Module):
         if self._predictor_is_stateful():
             raise NotImplementedError("beam_search needs a stateless predictor (forward(ids), e.g. ConvPredictor); "
                                       "stateful (LSTM) predictors are not supported")
+        g = self._beam_context(context)
         audio = self.encoder(mel_features).permute(0, 2, 1)
-        if self._beam_device_ok(audio, beam_size, max_length):
-            nbest = self._beam_search_device(audio, beam_size, max_length, m)
+        if self._beam_device_ok(audio, beam_size, max_length, g):
+            nbest = self._beam_search_device(audio, beam_size, max_length, m, g)
         else:
-            nbest = self._beam_search_host(audio, beam_size, max_length, m)
+            nbest = self._beam_search_host(audio, beam_size, max_length, m, g)
         return nbest if return_nbest else list(nbest[0][0])
 
-    def _beam_device_ok(self, audio, beam_size, max_length) -> bool:
+    def _beam_context(self, context):
+        """The ContextGraph a search runs with: checked against the vocabulary; None where it cannot change the search (no phrase, score 0)."""
+        if context is None:
+            return None
+        from .context import ContextGraph
+        if not isinstance(context, ContextGraph):
+            raise TypeError(f"context must be a rnnt_amd.ContextGraph, got {type(context).__name__}")
+        context.check(self.joint.joint_ln.out_features, self.joint.blank_idx)
+        return context if context.active else None
+
+    def _beam_device_ok(self, audio, beam_size, max_length, context=None) -> bool:
         if not (1 <= beam_size <= 16 and max_length >= 2 and self._device_loop_ok(audio)):
             return False
         from . import engine
+        if context is not None and context.n_nodes > engine.BEAM_CONTEXT_MAX_NODES:
+            return False
         p = self.predictor
         S, E = p.embedding.weight.shape
         return engine.beam_decode_supported(S, E, p.linear.out_features, self.joint.joint_ln.in_features,
                                             self.joint.joint_ln.out_features, hasattr(self.joint, "text_ln"), max_length, beam_size)
 
-    def _beam_search_device(self, audio, beam_size, max_length, m):
+    def _beam_search_device(self, audio, beam_size, max_length, m, context=None):
         from . import engine
         frames = audio[0]
         if hasattr(self.joint, "audio_ln"):
@@ -271,17 +289,19 @@ class RNNTModel(torch.nn.Module):
         state, tokens, scores = engine.beam_decode(
             frames, p._params(), (float(p.input_layer_norm.eps), float(p.output_layer_norm.eps)),
             tl.weight if tl is not None else None, tl.bias if tl is not None else None,
-            self.joint.joint_ln.weight, self.joint.joint_ln.bias, self.joint.blank_idx, max_length, beam_size, max_per_frame=m)
+            self.joint.joint_ln.weight, self.joint.joint_ln.bias, self.joint.blank_idx, max_length, beam_size, max_per_frame=m,
+            context=context.device_tables(frames.device) if context is not None else None)
         st, toks, sc = state.tolist(), tokens.tolist(), scores.tolist()  # the utterance's one synchronisation
         if not st[3]:
             raise RuntimeError(f"rnnt_engine: the beam search did not finish (t={st[0]}, {st[5]} rounds)")
-        return [(toks[j][1:1 + st[8 + j]], sc[j]) for j in range(st[2])]
+        nbest = [(toks[j][1:1 + st[8 + j]], sc[j]) for j in range(st[2])]
+        return context.finalise(nbest) if context is not None else nbest  # (the device's scores are internal)
 
     BEAM_BATCH = 32  # beam_search_many's default batch: the best of N = 1 .. 32 in profiles/beam_batch_bench.txt, the only one within 10 % of it
 
     @torch.no_grad()
     def beam_search_many(self, mels, beam_size: int = 4, max_length: int = 200, max_symbols_per_frame: int = 10,
-                         return_nbest: bool = False, batch=None):
+                         return_nbest: bool = False, batch=None, context=None):
         """Beam search of SEVERAL utterances (a list of (1, C, L) mel tensors, as greedy_decode_many takes): a list in input order whose
         entry i is exactly what `beam_search(mels[i], ...)` returns — the same token lists, the same float64 scores.  Up to `batch`
         utterances (at most 64) advance in lockstep through ONE sequence of rounds on the device (rnnt_engine_beam_decode_batch: the
@@ -290,7 +310,8 @@ class RNNTModel(torch.nn.Module):
         `batch` defaults to BEAM_BATCH = 32: of N = 1 .. 32 measured at the reference's widths (profiles/beam_batch_bench.txt) the time per
         utterance was still falling at 32 (7 - 21 ms against 106 - 336 ms one by one), so 32 is the smallest N within 10 % of the best.
         Where beam_search would take its host loop (CPU, other stateless predictors, beam_size > 16, sizes the kernels do not cover)
-        this is a loop over beam_search; a stateful (LSTM) predictor raises NotImplementedError."""
+        this is a loop over beam_search; a stateful (LSTM) predictor raises NotImplementedError.  `context` as beam_search's: ONE
+        ContextGraph biases every utterance (rnnt_engine_beam_decode_batch_ctx)."""
         beam_size, max_length, m = int(beam_size), int(max_length), int(max_symbols_per_frame)
         if beam_size < 1 or m < 1:
             raise ValueError(f"beam_search_many: beam_size={beam_size} and max_symbols_per_frame={m} must be >= 1")
@@ -305,18 +326,19 @@ class RNNTModel(torch.nn.Module):
         batch = self.BEAM_BATCH if batch is None else int(batch)
         if not 1 <= batch <= engine.BEAM_BATCH_MAX:
             raise ValueError(f"beam_search_many: batch={batch} outside [1, {engine.BEAM_BATCH_MAX}]")
+        g = self._beam_context(context)
         out = [None] * len(mels)
         tables = None
         for i in range(0, len(mels), batch):
             audios = [self.encoder(mel).permute(0, 2, 1) for mel in mels[i:i + batch]]
             # the utterances of the slice that beam_search would decode on the device advance together; any other takes its host loop
-            on_device = [self._beam_device_ok(a, beam_size, max_length) for a in audios]
+            on_device = [self._beam_device_ok(a, beam_size, max_length, g) for a in audios]
             batched = [u for u, ok in enumerate(on_device) if ok]
             if batched and not self._beam_batch_ok(len(batched), beam_size, max_length):
                 raise RuntimeError(f"rnnt_engine: the batched beam search refuses {len(batched)} utterances of sizes the single search takes")
             for u, a in enumerate(audios):
                 if not on_device[u]:
-                    out[i + u] = self._beam_search_host(a, beam_size, max_length, m)
+                    out[i + u] = self._beam_search_host(a, beam_size, max_length, m, g)
             if not batched:
                 continue
             if tables is None:
@@ -333,27 +355,34 @@ class RNNTModel(torch.nn.Module):
                 frames, p._params(), (float(p.input_layer_norm.eps), float(p.output_layer_norm.eps)),
                 tl.weight if tl is not None else None, tl.bias if tl is not None else None,
                 self.joint.joint_ln.weight, self.joint.joint_ln.bias, self.joint.blank_idx, max_length, beam_size, max_per_frame=m,
-                tables=tables)
+                tables=tables, context=g.device_tables(frames[0].device) if g is not None else None)
             sts, toks, scs = state.tolist(), tokens.tolist(), scores.tolist()  # the batch's one synchronisation
             for k, (u, st) in enumerate(zip(batched, sts)):
                 if not st[3]:
                     raise RuntimeError(f"rnnt_engine: the beam search of utterance {i + u} did not finish (t={st[0]}, {st[5]} rounds)")
-                out[i + u] = [(toks[k][j][1:1 + st[8 + j]], scs[k][j]) for j in range(st[2])]
+                nbest = [(toks[k][j][1:1 + st[8 + j]], scs[k][j]) for j in range(st[2])]
+                out[i + u] = g.finalise(nbest) if g is not None else nbest
         return out if return_nbest else [list(nbest[0][0]) for nbest in out]
 
-    def beam_stream(self, beam_size: int = 4, max_length: int = 200, max_symbols_per_frame: int = 10):
+    def beam_stream(self, beam_size: int = 4, max_length: int = 200, max_symbols_per_frame: int = 10, context=None):
         """A BeamStream (rnnt_amd/stream.py): beam search push by push — `push(mel_chunk)` through the encoder's
         streaming_forward, or `push_encoded(audio_features)` — whose n-best list after frames 0 .. k-1, however they were chunked, is
         `beam_search` of those k frames (`nbest`, `tokens`), with the `stable` prefix no later push can change.  On the device where
-        beam_search is (the search's state rests in a block the stream owns), else a resumable host loop."""
+        beam_search is (the search's state rests in a block the stream owns), else a resumable host loop.  With a `context`
+        (ContextGraph, as beam_search's) the stream runs the resumable host loop — the device stream with a context graph is not built
+        yet; `nbest`, `tokens` and `stable` are finalised views of the carried internal beam, so any chunking still equals
+        `beam_search(..., context=context)` of the same frames."""
         from .stream import BeamStream
-        return BeamStream(self, beam_size=beam_size, max_length=max_length, max_symbols_per_frame=max_symbols_per_frame)
+        return BeamStream(self, beam_size=beam_size, max_length=max_length, max_symbols_per_frame=max_symbols_per_frame,
+                          context=self._beam_context(context))
 
-    def beam_streams(self, n: int, beam_size: int = 4, max_length: int = 200, max_symbols_per_frame: int = 10):
+    def beam_streams(self, n: int, beam_size: int = 4, max_length: int = 200, max_symbols_per_frame: int = 10, context=None):
         """A BeamStreamGroup of `n` (1 .. 64) independent beam streams sharing one block and ONE launch sequence per push
-        (`push_encoded(chunks)`, a list of n chunks or None); stream i's results are exactly a lone beam_stream's."""
+        (`push_encoded(chunks)`, a list of n chunks or None); stream i's results are exactly a lone beam_stream's.  `context` as
+        beam_stream's: one graph for every stream, on the host loop."""
         from .stream import BeamStreamGroup
-        return BeamStreamGroup(self, n, beam_size=beam_size, max_length=max_length, max_symbols_per_frame=max_symbols_per_frame)
+        return BeamStreamGroup(self, n, beam_size=beam_size, max_length=max_length, max_symbols_per_frame=max_symbols_per_frame,
+                               context=self._beam_context(context))
 
     def _beam_batch_ok(self, n_utt, beam_size, max_length) -> bool:
         from . import engine
@@ -363,10 +392,10 @@ class RNNTModel(torch.nn.Module):
                                                   self.joint.joint_ln.out_features, hasattr(self.joint, "text_ln"), max_length, beam_size,
                                                   n_utt)
 
-    def _beam_search_host(self, audio, beam_size, max_length, m):
+    def _beam_search_host(self, audio, beam_size, max_length, m, context=None):
         """The search of DESIGN.md §4h as a host loop: the predictor on the whole history of each new hypothesis (cached by
         sequence), single_forward batched over the round's active hypotheses, scores as Python floats (double)."""
         from .stream import HostBeamLoop  # (one host loop, resumable frame by frame: BeamStream's host path runs it too)
-        loop = HostBeamLoop(self, beam_size, max_length, m)
+        loop = HostBeamLoop(self, beam_size, max_length, m, context)
         loop.run(audio)
         return loop.nbest

@@ -234,10 +234,15 @@ class GreedyStream:
 class HostBeamLoop:
     """The search of DESIGN.md §4h as a host loop over any number of calls of `run`: the predictor on the whole history of each new
     hypothesis (cached by sequence), single_forward batched over the round's active hypotheses, scores as Python floats (double).  The
-    beam after the last frame carries to the next call; `nbest` is beam_search's result for the frames so far."""
+    beam after the last frame carries to the next call; `nbest` is beam_search's result for the frames so far.  With a `context`
+    (ContextGraph; DESIGN.md §4h "Context") a label candidate takes delta(node, k) — the WHOLE log-probability row is biased before the
+    slot's top-`beam` is taken, never only the labels the raw row would have offered —, the carried beam holds internal scores and `nbest`
+    is its finalised view."""
 
-    def __init__(self, model, beam_size, max_length, max_symbols_per_frame=10):
+    def __init__(self, model, beam_size, max_length, max_symbols_per_frame=10, context=None):
         self.model = model
+        self.context = context
+        self._nodes = {}  # sequence -> node of the context graph (a function of the sequence)
         self.beam_size, self.max_length, self.m = int(beam_size), int(max_length), int(max_symbols_per_frame)
         self.beam = [((), 0.0)]
         self.frames = 0
@@ -245,7 +250,16 @@ class HostBeamLoop:
 
     @property
     def nbest(self):
+        if self.context is not None:
+            return self.context.finalise(self.beam)
         return [(list(y), s) for y, s in self.beam]
+
+    def _node(self, y):
+        if not y:
+            return 0
+        if y not in self._nodes:  # (a new hypothesis extends one of the beam's: one step)
+            self._nodes[y] = self.context.step(self._node(y[:-1]), y[-1])[0]
+        return self._nodes[y]
 
     def _text(self, y):
         if y not in self._feats:
@@ -280,6 +294,8 @@ class HostBeamLoop:
                     if len(y) >= max_length - 1:
                         continue
                     row = lp[i].clone()
+                    if self.context is not None:
+                        row += torch.from_numpy(self.context.delta_row(self._node(y), row.shape[0]))
                     row[blank] = -math.inf
                     vals, idx = torch.sort(row, descending=True, stable=True)  # lower id first among equal values
                     for v, k in zip(vals[:beam_size].tolist(), idx[:beam_size].tolist()):
@@ -304,6 +320,8 @@ class HostBeamLoop:
         self.frames += audio.shape[1]
         live = {y for y, _ in beam}  # (only the beam's text vectors are needed again; the others would only grow with the stream)
         self._feats = {y: f for y, f in self._feats.items() if y in live}
+        if self.context is not None:
+            self._nodes = {y: self._node(y) for y in live}
 
 
 def _common_prefix(lists):
@@ -328,10 +346,13 @@ class BeamStreamGroup:
     With the engine's ConvPredictor in eval mode, fp32 HIP tensors, sizes the beam kernels cover and beam_size <= 16 the searches rest on
     the device between pushes, in a block the group owns (rnnt_engine_beam_stream_push: all streams advance through ONE kernel sequence
     per round, one host synchronisation per push); the decode tables are built when the group is created, so the model's weights must not
-    change while it is open.  Everything else, the CPU included, runs one HostBeamLoop per stream (`last_path`: "device" or "host")."""
+    change while it is open.  Everything else, the CPU included, runs one HostBeamLoop per stream (`last_path`: "device" or "host").
+    With a `context` (ContextGraph; DESIGN.md §4h "Context") every stream runs the host loop — the device stream with a context graph is
+    out of scope so far (§4l) —, the carried beams are internal and `nbest`, `tokens`, `stable` their finalised views."""
 
-    def __init__(self, model, n, beam_size=4, max_length=200, max_symbols_per_frame=10):
+    def __init__(self, model, n, beam_size=4, max_length=200, max_symbols_per_frame=10, context=None):
         from . import engine
+        self.context = context  # (a ContextGraph that can change the search, or None: RNNTModel._beam_context)
         n, beam_size, max_length, m = int(n), int(beam_size), int(max_length), int(max_symbols_per_frame)
         if beam_size < 1 or m < 1:
             raise ValueError(f"beam_stream: beam_size={beam_size} and max_symbols_per_frame={m} must be >= 1")
@@ -346,7 +367,8 @@ class BeamStreamGroup:
         self.frames = [0] * n
         self.last_path = None
         dev = model.device
-        self._on_device = dev.type == "cuda" and model._beam_device_ok(torch.zeros(1, 1, device=dev), beam_size, max_length)
+        # (with a context graph: the host loop — the device stream carries no node per slot yet)
+        self._on_device = context is None and dev.type == "cuda" and model._beam_device_ok(torch.zeros(1, 1, device=dev), beam_size, max_length)
         if self._on_device:
             p, joint = model.predictor, model.joint
             S, E = p.embedding.weight.shape
@@ -361,7 +383,7 @@ class BeamStreamGroup:
             self._scores, self._state, self._tokens = self._views(self._res)
             engine.beam_stream_init(self._sizes, max_length, beam_size, joint.blank_idx, self._state, self._scores, self._block)
         else:
-            self._loops = [HostBeamLoop(model, beam_size, max_length, m) for _ in range(n)]
+            self._loops = [HostBeamLoop(model, beam_size, max_length, m, context) for _ in range(n)]
 
     def _views(self, res):
         n, beam, a, b = self.n, self.beam_size, *self._cut
@@ -384,7 +406,7 @@ class BeamStreamGroup:
             engine.beam_stream_init(self._sizes, self.max_length, self.beam_size, self.model.joint.blank_idx, self._state, self._scores,
                                     self._block, index=i)
         else:
-            self._loops[i] = HostBeamLoop(self.model, self.beam_size, self.max_length, self.max_symbols_per_frame)
+            self._loops[i] = HostBeamLoop(self.model, self.beam_size, self.max_length, self.max_symbols_per_frame, self.context)
         self.nbest[i] = [([], 0.0)]
         self.frames[i] = 0
 
@@ -452,9 +474,9 @@ class BeamStream:
     change from push to push — `stable` is the part that cannot).  `nbest`, `tokens`, `stable`, `frames`, `last_path` as the group's, for
     the one stream; `reset()` starts a new utterance on the same block and tables."""
 
-    def __init__(self, model, beam_size=4, max_length=200, max_symbols_per_frame=10):
+    def __init__(self, model, beam_size=4, max_length=200, max_symbols_per_frame=10, context=None):
         self.model = model
-        self._group = BeamStreamGroup(model, 1, beam_size, max_length, max_symbols_per_frame)
+        self._group = BeamStreamGroup(model, 1, beam_size, max_length, max_symbols_per_frame, context)
         self._enc_state = None
 
     nbest = property(lambda self: self._group.nbest[0])
