@@ -143,7 +143,7 @@ void layout(int B, int T, int U1, int H, int V, int dtype, rnnt_engine_ws_layout
         L->counters = o; o += 1024 + align_up(tab > lst ? tab : lst);
         if (bf || x2) o += align_up((size_t)L->n_split * 64);  // k_dw_bf16's / k_dw_x2's progress words, behind the table
     }
-    if (x2) { L->x2_live = o; o += align_up(x2_live_bytes(B, T, U1, (long)rows_pad)); }  // counts, tile flags, k-step bitmap and list (launch_x2_live)
+    if (x2) { L->x2_live = o; o += align_up(x2_live_bytes(B, T, U1, (long)rows_pad)); }  // counts, tile flags and list, k-step bitmap and list (launch_x2_live)
     L->total = o;
     if (x3) {  // fp32 hidden + fp32 W pack of the stages that can run on the fp32 route's kernels (RNNT_VARIANT_X3_FP32_*):
         // BEHIND `total` — only a call that asks for such a variant needs a workspace of total + aux_bytes
@@ -321,13 +321,14 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
     g.n_ublk = L.n_ublk; g.n_ttile = L.n_ttile; g.n_split = L.n_split;
     g.counter = (unsigned *)(ws + L.counters); g.dw_tab = (long *)(ws + L.counters + 1024); g.n_cu = device_cus(); g.flags = xflags & ~16; g.g_ready = 0; g.debug = g_debug; g.pred_split_col = 0;
     g.gen_bu = dtype == RNNT_DTYPE_BF16 ? 16 : dhidden_gen_bu(T, U1);  // u width of the dHidden tiles
+    g.tile_flag = nullptr; g.flag_ntt = 0; g.flag_nub = 0;  // (f16x2 route: below)
     if (dtype == RNNT_DTYPE_F32_BF16X3 || dtype == RNNT_DTYPE_F32_F16X2) {
         // RNNT_DTYPE_F32_F16X2 (x2.hip): the same stages on two fp16 planes and three products; operand scales below
         const bool x2 = dtype == RNNT_DTYPE_F32_F16X2;
         // fp32-accurate route on the bf16 matrix pipes (x3.hip).  Stage by stage the fp32 route's own kernel can
         // stand in (RNNT_VARIANT_X3_FP32_FWD / _DH): same data, one stage swapped — how each x3 kernel is checked.
         X3Args h;
-        h.tile_live = nullptr; h.ks_bitmap = nullptr; h.ks_list = nullptr; h.live_stats = nullptr; h.zero_all = 0;
+        h.tile_live = nullptr; h.ks_bitmap = nullptr; h.ks_list = nullptr; h.live_stats = nullptr; h.tile_list = nullptr; h.zero_all = 0;
         double flush_log2 = -HUGE_VAL;  // the flush rule's threshold (x2.hip): log2 of 2^-26 / g_scale; -inf flags nothing
         float flush_lin = 0.f;
         h.enc = encp; h.enc_sb = esb; h.enc_st = est; h.pred = (const float *)pred;
@@ -378,6 +379,8 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
             if (fuse_g32) { g.flags |= 16; g.pred_split_col = 512 * dhidden_gen_groups(H); }
         } else {
             g.gen_bu = 16; g.pred_split_col = H;  // x3 tiles: 8 t x 16 u, every dPred slab 8 t rows high
+            // f16x2: k_dhidden_x2 runs the live tiles only and no dead tile writes a slab: the reductions skip by the same flags
+            if (x2) { g.tile_flag = h.tile_live; g.flag_ntt = (T + 7) / 8; g.flag_nub = h.n_ublk16; }
         }
         if (stages & ST_PROD) {
             if (x2) { launch_x2_zero_padding(h, 1, st); launch_x2_pack_w(h, (float *)(ws + L.counters + 640), st); launch_x2_make_ep(h, st); }
@@ -432,6 +435,7 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
                 if (x2) launch_x2_split_g(h, st);
                 else launch_x3_split_g(h, st);  // -> hi | mid in place, lo beside
             } else if (x2) {
+                launch_x2_dead_rows(h, st);  // rows of dead tiles inside live k-steps: zeros for dW (disjoint from the live tiles' rows)
                 launch_dhidden_x2(h, st);
             } else {
                 launch_dhidden_x3(h, st);

@@ -682,12 +682,32 @@ bool dhidden_gen_ok(int H, int V, int U1)
 // column groups of 512 the tile kernel takes: the first (which produces G) and every further WHOLE one
 int dhidden_gen_groups(int H) { return H <= DG_COLS ? 1 : H / DG_COLS; }
 
+// `flag` (JointBwdArgs::tile_flag, the f16x2 route; NULL elsewhere): [B][ntt][nub] bytes, one per 8 t x 16 u dHidden tile.  A tile whose
+// flag is 0 wrote no slab piece (its memory may hold anything) and would have contributed exact zeros: its piece is left out of the
+// sum, which starts at +0 and so does not change a bit.  The flags of up to 32 pieces are gathered first (independent byte loads), then
+// the flagged pieces are added in ascending order, requested eight at a time (reduce_flagged: a loop that asks for one piece per set bit
+// has one load in flight and is bound by latency, not bytes).
+__device__ __forceinline__ void reduce_flagged(f32x4 &s, const f32x4 *__restrict__ p, long stride, int k0, unsigned m)
+{
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    while (m) {
+        f32x4 v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            v[j] = z;  // (a slot without a piece adds +0: s is never -0, so no bit moves)
+            if (m) { v[j] = p[(long)(k0 + __builtin_ctz(m)) * stride]; m &= m - 1; }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += v[j];
+    }
+}
 // out[b,t,:] = sum_ub slab_enc[ub][b,t,:]  (0 for t >= T_b)
 __global__ __launch_bounds__(256) void k_reduce_enc(const float *__restrict__ slab,
                                                     const int32_t *__restrict__ logit_lens,
                                                     const int32_t *__restrict__ target_lens,
                                                     float *__restrict__ out, int B, int T, int U1,
-                                                    int H, int n_ublk, int bu_lo, int col_split)
+                                                    int H, int n_ublk, int bu_lo, int col_split,
+                                                    const unsigned char *__restrict__ flag, int ntt, int nub_f)
 {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;  // float4 index
     const int H4 = H / 4;
@@ -703,7 +723,17 @@ __global__ __launch_bounds__(256) void k_reduce_enc(const float *__restrict__ sl
         const int bu = bu_lo;
         int nub = len_u(target_lens, b, U1) / bu + 1;
         if (nub > n_ublk) nub = n_ublk;
-        for (int k = 0; k < nub; ++k) s += ((const f32x4 *)slab)[(long)k * n + idx];
+        if (flag) {
+            const unsigned char *f = flag + ((long)b * ntt + t / 8) * nub_f;  // (bu = 16: piece k = tile column k)
+            for (int k0 = 0; k0 < nub; k0 += 32) {
+                const int kn = nub - k0 < 32 ? nub - k0 : 32;
+                unsigned m = 0;
+                for (int k = 0; k < kn; ++k) m |= (f[k0 + k] ? 1u : 0u) << k;
+                reduce_flagged(s, (const f32x4 *)slab + idx, n, k0, m);
+            }
+        } else {
+            for (int k = 0; k < nub; ++k) s += ((const f32x4 *)slab)[(long)k * n + idx];
+        }
     }
     ((f32x4 *)out)[idx] = s;
 }
@@ -714,7 +744,8 @@ __global__ __launch_bounds__(256) void k_reduce_pred(const float *__restrict__ s
                                                      const int32_t *__restrict__ logit_lens,
                                                      const int32_t *__restrict__ target_lens,
                                                      float *__restrict__ out, int B, int T, int U1,
-                                                     int H, int bt_lo, int bt_hi, int col_split)
+                                                     int H, int bt_lo, int bt_hi, int col_split,
+                                                     const unsigned char *__restrict__ flag, int ntt_f, int nub_f)
 {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const int H4 = H / 4;
@@ -725,8 +756,19 @@ __global__ __launch_bounds__(256) void k_reduce_pred(const float *__restrict__ s
     const int ntt = (len_t(logit_lens, b, T) + bt - 1) / bt;  // slabs written: t tiles of height bt
     const int u = (int)((idx / H4) % U1);
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    if (u <= len_u(target_lens, b, U1))  // rows past U_b: no lattice cell, and their u block may not have been written
-        for (int k = 0; k < ntt; ++k) s += ((const f32x4 *)slab)[(long)k * n + idx];
+    if (u <= len_u(target_lens, b, U1)) {  // rows past U_b: no lattice cell, and their u block may not have been written
+        if (flag) {
+            const unsigned char *f = flag + (long)b * ntt_f * nub_f + u / 16;  // (bt = 8: piece k = tile row k)
+            for (int k0 = 0; k0 < ntt; k0 += 32) {
+                const int kn = ntt - k0 < 32 ? ntt - k0 : 32;
+                unsigned m = 0;
+                for (int k = 0; k < kn; ++k) m |= (f[(long)(k0 + k) * nub_f] ? 1u : 0u) << k;
+                reduce_flagged(s, (const f32x4 *)slab + idx, n, k0, m);
+            }
+        } else {
+            for (int k = 0; k < ntt; ++k) s += ((const f32x4 *)slab)[(long)k * n + idx];
+        }
+    }
     ((f32x4 *)out)[idx] = s;
 }
 
@@ -764,11 +806,12 @@ void launch_dhidden_reduce(const JointBwdArgs &a, hipStream_t st)
 {
     const long n4e = (long)a.B * a.T * (a.H / 4);
     hipLaunchKernelGGL(k_reduce_enc, dim3((unsigned)((n4e + 255) / 256)), dim3(256), 0, st,
-                       a.slab_enc, a.logit_lens, a.target_lens, a.grad_enc, a.B, a.T, a.U1, a.H, a.n_ublk, a.gen_bu, a.pred_split_col);
+                       a.slab_enc, a.logit_lens, a.target_lens, a.grad_enc, a.B, a.T, a.U1, a.H, a.n_ublk, a.gen_bu, a.pred_split_col,
+                       a.tile_flag, a.flag_ntt, a.flag_nub);
     const long n4p = (long)a.B * a.U1 * (a.H / 4);
     hipLaunchKernelGGL(k_reduce_pred, dim3((unsigned)((n4p + 255) / 256)), dim3(256), 0, st,
                        a.slab_pred, a.logit_lens, a.target_lens, a.grad_pred, a.B, a.T, a.U1, a.H,
-                       128 / a.gen_bu, 64 / a.gen_bu, a.pred_split_col);
+                       128 / a.gen_bu, 64 / a.gen_bu, a.pred_split_col, a.tile_flag, a.flag_ntt, a.flag_nub);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -103,6 +103,10 @@ struct JointBwdArgs {
     int g_ready;        // with bit 4: G already stands in place of the logits (k_make_g ran): the first column group reads it too (GEN = false)
     int gen_bu;         // u width of k_dhidden_gen's tiles (16, or 8 for short targets); dEnc slabs of columns < pred_split_col
     int pred_split_col; // dPred slabs: columns < this come in 8-row t tiles (k_dhidden_gen, bf16 route), the rest in 4-row tiles (k_dhidden)
+    // f16x2 route only (x2.hip "flush rule"), NULL on every other: the reductions add a slab piece only where its 8 t x 16 u tile's flag is 1
+    // (dead tiles write no slab); [B][flag_ntt][flag_nub]
+    const unsigned char *tile_flag;
+    int flag_ntt, flag_nub;
     unsigned long long *debug;  // diagnostic stamp buffer (RNNT_STAMPS builds), else NULL
 };
 void launch_dhidden(const JointBwdArgs &a, hipStream_t st);
@@ -182,11 +186,12 @@ struct X3Args {
     float *ep_enc, *ep_pred;    // exp(2 enc) [B][H/16][T][16], exp(2 pred) [B][H/16][U1][16] (k_x2_make_ep, every call)
     unsigned *ep_flag;          // device word: != 0 when an input lies outside the factored tanh's range (the exact forward runs)
     // live structures of the backward (launch_x2_live, after the coefficients; x2.hip "flush rule"); the Linear layer's dW sets ks_list / live_stats only
-    const unsigned char *tile_live;  // [B][ceil(T/8)][n_ublk16]: 1 = the dHidden tile holds a cell with non-null coefficients; NULL: every tile inside the lengths runs
-    const unsigned *ks_bitmap;       // bit k: 16-cell k-step k of the dW GEMM is live (holds such a cell); NULL: a skipped tile zero-fills every row
+    const unsigned char *tile_live;  // [B][ceil(T/8)][n_ublk16]: 1 = the dHidden tile holds a cell with non-null coefficients
+    const unsigned *ks_bitmap;       // bit k: 16-cell k-step k of the dW GEMM is live (holds such a cell); what k_dw_x2 walks as ks_list
     int *ks_list;                    // ascending live k-steps, then >= 8 entries naming the first all-padding k-step (rows_pad / 16)
-    int *live_stats;                 // [0] live k-steps = length of ks_list, [1] k-steps with a cell, [2] live dHidden tiles, [3] dHidden tiles
-    int zero_all;                    // 1: the dW kernel of this call walks the 32-cell table (the lab's k_dw_x2p): skipped tiles zero-fill every row
+    int *live_stats;                 // [0] live k-steps = length of ks_list, [1] k-steps with a cell, [2] live dHidden tiles = length of tile_list, [3] dHidden tiles
+    const int *tile_list;            // ascending indices [b][tt][ub] of the tiles whose flag is 1: the workgroups of k_dhidden_x2 (entries past live_stats[2] hold anything)
+    int zero_all;                    // 1: the dW kernel of this call walks the 32-cell table (the lab's k_dw_x2p): k_x2_dead_rows zero-fills every row of the tiles that are not live
 };
 size_t x2_live_bytes(int B, int T, int U1, long rows_pad);  // bytes of the region below
 void x2_live_carve(void *region, int B, int T, int U1, long rows_pad, X3Args &a);  // points tile_live .. live_stats into the region
@@ -220,6 +225,7 @@ size_t x2_ep_bytes(int B, int T, int U1, int H);
 void launch_joint_fwd_x2(const X3Args &a, hipStream_t st);   // one 512-register wave per SIMD
 bool x2_fwd_d_ok(int U1, int H, int V);
 void launch_joint_fwd_x2d(const X3Args &a, hipStream_t st);  // two 4-wave workgroups per CU, A in registers (RNNT_VARIANT_X2_FWD_2WG)
+void launch_x2_dead_rows(const X3Args &a, hipStream_t st);  // zero G rows of dead tiles' cells inside live k-steps (what k_dw_x2 reads beside the live tiles' rows)
 void launch_dhidden_x2(const X3Args &a, hipStream_t st);
 // the joint's input projections (audio_ln / text_ln) and their backward on the f16x2 pipes (x2.hip, round 5)
 size_t x2_linear_ws_bytes(int M, int K, int N, bool bwd);

@@ -19,7 +19,8 @@
 // Flush rule (below, "The flush rule and the live structures of the backward"): fp16's narrow exponent makes both planes of g_scale G
 // exactly zero wherever the lattice's occupancy is below ~2^-38 — half the cells of the benchmark's batch.  The coefficient kernel
 // proves that per cell (|g_scale G| < 2^-26, one binade inside what rounds to zero: lattice.hip coef_cell), and the two backward GEMMs
-// skip the dHidden tiles and the 16-cell dW k-steps that hold no other cell.  RNNT_VARIANT_X2_NO_FLUSH_SKIP switches it off per call.
+// run the dHidden tiles and the 16-cell dW k-steps that hold another cell, each from an ascending list built on the device: k_dhidden_x2's
+// workgroups are the entries of the live-tile list.  RNNT_VARIANT_X2_NO_FLUSH_SKIP switches the rule off per call (same lists, by length).
 //
 // MFMA operand maps (v_mfma_f32_32x32x16_f16, as the bf16 form): lane l = (r = l&31, h = l>>5) holds A[row r][k = 8h+j] and
 // B[k = 8h+j][col r], j = 0..7; C/D: col = l&31, row = (reg&3) + 8*(reg>>2) + 4*(l>>5).
@@ -246,7 +247,12 @@ void launch_x2_zero_padding(const X3Args &a, int what, hipStream_t st)
 // benchmark's batch lie below that threshold.  k_coef_flush (lattice.hip: the bound, its margin and the rounding it covers are
 // derived there) gives every such cell the coefficients of a cell OUTSIDE the lattice — for which k_dhidden_x2 always produced
 // G = 0 from the zero padding row — and the kernels below turn the coefficients into what lets the two backward GEMMs skip:
-//   tile_live[b][tt][ub]  the dHidden tile (8 t x 16 u) holds a cell with non-null coefficients: the others leave at the dead-tile exit;
+//   tile_live[b][tt][ub]  the dHidden tile (8 t x 16 u) holds a cell with non-null coefficients;
+//   tile_list             the ascending indices of those tiles (k_x2_live_scan: counted and scanned, no atomics): workgroup g of
+//                         k_dhidden_x2 (every pass) runs tile_list[g], the workgroups past the list's length return at once.  A tile that
+//                         is not on it costs nothing there and writes nothing: its slab pieces may hold anything — k_reduce_enc /
+//                         k_reduce_pred add a piece only where the tile's flag is 1 (JointBwdArgs::tile_flag; the sums start at +0 and the
+//                         pieces left out were exact zeros) — and the G rows dW reads of it are zeroed by k_x2_dead_rows;
 //   ks_bitmap / ks_list   the 16-cell k-steps of the dW GEMM (linear cell index / 16) that hold such a cell, as a bitmap and as the
 //                         ascending list k_dw_x2 walks (fixed order: dW stays bitwise reproducible), padded with entries that name
 //                         the first k-step of the zero padding rows for the ring's read-ahead;
@@ -258,7 +264,7 @@ void launch_x2_zero_padding(const X3Args &a, int what, hipStream_t st)
 #define XL2_BLK 1024
 __device__ __forceinline__ bool x2_coef_live(const CellCoef &c) { return !(c.c1 == RNNT_NEG_INF && c.sb == 0.f && c.se == 0.f); }
 namespace {
-struct X2LiveWs { size_t tiles, bitmap, blk, list, total; long nks, ntile; int nblk; };
+struct X2LiveWs { size_t tiles, bitmap, blk, list, tlist, total; long nks, ntile; int nblk; };
 X2LiveWs x2_live_layout(int B, int T, int U1, long rows_pad)
 {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -271,6 +277,7 @@ X2LiveWs x2_live_layout(int B, int T, int U1, long rows_pad)
     L.bitmap = o; o += al((size_t)L.nblk * (XL2_BLK / 8));
     L.blk = o; o += al((size_t)L.nblk * 4);
     L.list = o; o += al((size_t)(L.nks + 8) * 4);
+    L.tlist = o; o += al((size_t)L.ntile * 4);
     L.total = o;
     return L;
 }
@@ -281,7 +288,7 @@ void x2_live_carve(void *region, int B, int T, int U1, long rows_pad, X3Args &a)
     const X2LiveWs L = x2_live_layout(B, T, U1, rows_pad);
     char *r = (char *)region;
     a.live_stats = (int *)r; a.tile_live = (const unsigned char *)(r + L.tiles); a.ks_bitmap = (const unsigned *)(r + L.bitmap);
-    a.ks_list = (int *)(r + L.list);
+    a.ks_list = (int *)(r + L.list); a.tile_list = (const int *)(r + L.tlist);
 }
 // one workgroup per 1024 k-steps (16384 cells, read coalesced: 16 rounds of one cell per thread; a wave's ballot covers 4 k-steps):
 // live flags -> 16 bitmap words, their number -> blk
@@ -313,9 +320,14 @@ __global__ __launch_bounds__(XL2_BLK) void k_x2_live_count(const CellCoef *__res
         if (lane == 0) blk[blockIdx.x] = cnt;
     }
 }
-// exclusive scan of the block counts in place (one workgroup, k_dw_list_scan's); the counts; the list's padding entries
+// exclusive scan of the block counts in place (one workgroup, k_dw_list_scan's); the counts; the list's padding entries; and the live-tile
+// list: a thread takes 64 consecutive flag bytes (four 16-byte loads; the flag region is padded to 256 bytes, bytes past ntile are masked),
+// counts them, the workgroup scans the counts and the thread writes its tiles' indices at its offset — 65536 tiles per round, positions by
+// counting and scanning alone (ascending, the same every call).
+#define XL2_TPT 64  // tiles per thread and round
 __global__ __launch_bounds__(1024) void k_x2_live_scan(int *__restrict__ blk, int nblk, int *__restrict__ stats, int *__restrict__ list,
-                                                       long cells, long nks, long ntile, const unsigned char *__restrict__ tile_live)
+                                                       long cells, long nks, long ntile, const unsigned char *__restrict__ tile_live,
+                                                       int *__restrict__ tile_list)
 {
     __shared__ int s_w[16];
     __shared__ int s_carry;
@@ -337,17 +349,39 @@ __global__ __launch_bounds__(1024) void k_x2_live_scan(int *__restrict__ blk, in
         __syncthreads();
     }
     const int total = s_carry;
-    int lt = 0;  // live dHidden tiles: the sum of k_x2_live_tiles' flag bytes
-    for (long k = threadIdx.x; k < ntile; k += 1024) lt += tile_live[k];
+    __syncthreads();
+    if (threadIdx.x == 0) s_carry = 0;  // now: live tiles before this round (their number = the sum of k_x2_live_tiles' flag bytes)
+    __syncthreads();
+    for (long base = 0; base < ntile; base += 1024L * XL2_TPT) {
+        const long k0 = base + (long)threadIdx.x * XL2_TPT;
+        unsigned long long m = 0;  // bit j: tile k0 + j is live
+        if (k0 < ntile) {
+            u32x4 f[XL2_TPT / 16];
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) lt += __shfl_xor(lt, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = lt;
-    __syncthreads();
+            for (int q = 0; q < XL2_TPT / 16; ++q) f[q] = ((const u32x4 *)(tile_live + k0))[q];
+#pragma unroll
+            for (int q = 0; q < XL2_TPT / 16; ++q)
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    if ((f[q][j >> 2] >> (8 * (j & 3))) & 0xffu) m |= 1ull << (16 * q + j);
+            if (ntile - k0 < XL2_TPT) m &= (1ull << (ntile - k0)) - 1ull;
+        }
+        const int v = __popcll(m);
+        int x = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d, 64); if ((threadIdx.x & 63) >= d) x += y; }
+        if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = x;
+        __syncthreads();
+        int off = s_carry;
+        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) off += s_w[w];
+        off += x - v;
+        for (; m; m &= m - 1) tile_list[off++] = (int)(k0 + __builtin_ctzll(m));
+        __syncthreads();
+        if (threadIdx.x == 1023) s_carry = off;
+        __syncthreads();
+    }
     if (threadIdx.x == 0) {
-        lt = 0;
-        for (int w = 0; w < 16; ++w) lt += s_w[w];
-        stats[0] = total; stats[1] = (int)((cells + XW2_ROWS_ - 1) / XW2_ROWS_); stats[2] = lt; stats[3] = (int)ntile;
+        stats[0] = total; stats[1] = (int)((cells + XW2_ROWS_ - 1) / XW2_ROWS_); stats[2] = s_carry; stats[3] = (int)ntile;
     }
     if (threadIdx.x < 8) list[total + threadIdx.x] = (int)nks;  // rows rows_pad ..: zero padding (rows_alloc >= rows_pad + 96)
 }
@@ -393,7 +427,7 @@ void launch_x2_live(const X3Args &a, hipStream_t st)
     const int ntt = (a.T + XG2_BT_ - 1) / XG2_BT_, nub = (a.U1 + XG2_BU_ - 1) / XG2_BU_;
     hipLaunchKernelGGL(k_x2_live_tiles, dim3((unsigned)((L.ntile + 3) / 4)), dim3(256), 0, st, a.coef, a.T, a.U1, ntt, nub, L.ntile, (unsigned char *)a.tile_live);
     hipLaunchKernelGGL(k_x2_live_count, dim3(L.nblk), dim3(XL2_BLK), 0, st, a.coef, cells, bitmap, blk);
-    hipLaunchKernelGGL(k_x2_live_scan, dim3(1), dim3(1024), 0, st, blk, L.nblk, a.live_stats, a.ks_list, cells, L.nks, L.ntile, a.tile_live);
+    hipLaunchKernelGGL(k_x2_live_scan, dim3(1), dim3(1024), 0, st, blk, L.nblk, a.live_stats, a.ks_list, cells, L.nks, L.ntile, a.tile_live, (int *)a.tile_list);
     hipLaunchKernelGGL(k_x2_live_write, dim3(L.nblk), dim3(XL2_BLK), 0, st, bitmap, L.nks, blk, a.ks_list);
 }
 
@@ -435,7 +469,7 @@ void launch_dw_reduce_x2(const X3Args &a, float *grad_W, float *grad_bias, hipSt
 // K walk: the split-K ranges are cut from the ascending list of LIVE k-steps (X3Args::ks_list: the k-steps that hold a cell with non-null
 // coefficients — inside the lengths, reachable, not flushed), evenly, so the splits are balanced whatever the lattices' shapes; k-step ks of
 // a split multiplies the 16 rows of k-step list[g_lo + ks], one pipeline run per split.  Rows of a live k-step that belong to no live cell
-// hold zeros (k_dhidden_x2 writes them).
+// hold zeros (k_dhidden_x2 writes them inside its live tiles, k_x2_dead_rows those of the tiles that are not live).
 // The accumulators hold g_scale x 2^14 x dW: the epilogue multiplies by X3Args::dw_rescale (a power of two).
 // ---------------------------------------------------------------------------------------
 #define XW2_ROWS 16
@@ -1081,7 +1115,7 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
 #endif
 
 // the dW kernel launch_dw_x2 picks for this call walks k_dw_table's 32-cell ranges, not the live k-step list (the lab's k_dw_x2p only):
-// k_dhidden_x2's skipped tiles then zero-fill every row (X3Args::zero_all)
+// k_x2_dead_rows then zeroes every row of the tiles k_dhidden_x2 does not run (X3Args::zero_all)
 bool x2_dw_walks_table(int H, int V, int flags)
 {
     (void)H; (void)V; (void)flags;
@@ -1173,7 +1207,8 @@ size_t x2_wpack_dh_bytes(int H, int V) { return (size_t)((H + 511) / 512) * (V /
 // FIRST = false (H > 512: columns 512.., one launch per further 512): G's planes are read back from memory into the exchange
 // instead of being produced; nothing is stored but the slabs.
 // The accumulators hold g_scale s_W dHidden: the epilogue's sums are multiplied by 1 / (g_scale s_W) (a power of two).
-// grid (n_ublk, ceil(T/8), B).  Requires V % 128 == 0, H % 128 == 0.
+// grid: one workgroup per tile, 1-D; workgroup g runs tile tile_list[g] = [b][tt][ub] (the live tiles, ascending) and returns at once when
+// g >= live_stats[2].  Requires V % 128 == 0, H % 128 == 0.
 // ---------------------------------------------------------------------------------------
 #define XG2_BT 8
 #define XG2_BU 16
@@ -1201,7 +1236,13 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
     const int wm = wave >> 1, wn = wave & 1;
     const int i = lane & 31, half = lane >> 5;
     const int T = a.T, U1 = a.U1, H = a.H, V = a.V;
-    const int ub = blockIdx.x, tt = blockIdx.y, b = blockIdx.z;
+    // workgroup g runs the g-th LIVE tile (X3Args::tile_list, ascending [b][tt][ub]: the order the full grid was dispatched in); the grid
+    // has a workgroup per tile, those past the list's length leave here: one scalar load, no store
+    if ((int)blockIdx.x >= a.live_stats[2]) return;
+    const int tile = __builtin_amdgcn_readfirstlane(a.tile_list[blockIdx.x]);
+    const int nub = a.n_ublk16, ntt = (T + XG2_BT - 1) / XG2_BT;
+    const int ub = __builtin_amdgcn_readfirstlane(tile % nub), tt = __builtin_amdgcn_readfirstlane((tile / nub) % ntt);
+    const int b = __builtin_amdgcn_readfirstlane(tile / (nub * ntt));
     int Tb, Ub;
     len_tu_uniform(a.logit_lens, a.target_lens, b, a.T, a.U1, Tb, Ub);
     const int t0 = tt * XG2_BT, u0 = ub * XG2_BU;
@@ -1216,42 +1257,10 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
     const long zrow = (long)a.B * T * U1;  // first zero padding row
     const long pcell = pexists ? ((long)b * T + pt) * U1 + pu : zrow;
 
-    // workgroup-uniform dead-tile exit: no products past the utterance's length or in a u block past U_b (no lattice cell; the
-    // reductions skip its slabs), nor in a tile none of whose cells has non-null coefficients (X3Args::tile_live: every cell outside
-    // the lattice, unreachable or flushed — each would have produced G = 0).  What a dead tile still owes:
-    //  * G: the dW GEMM must find zeros in the rows it reads — the rows of LIVE 16-cell k-steps (ks_bitmap: a k-step that straddles
-    //    the tile's edge), both planes = the whole logits row.  The other rows keep their logits: nothing reads them (zero_all: the
-    //    dW kernel of this call walks whole per-utterance ranges, so every row is filled);
-    //  * slabs: a dead tile INSIDE the lengths writes zeros over its pieces of the dEnc / dPred slabs (8 + 16 rows of this pass's
-    //    columns) — the reductions (shared with the other routes) skip slabs by length only;
-    //  * the later column passes (FIRST = false) and k_dhidden_x2r take the same exit by the same flag: the tile's rows may hold logits.
-    const bool past_len = t0 >= Tb || u0 > Ub;
-    if (past_len || (a.tile_live && !a.tile_live[((long)b * gridDim.y + tt) * gridDim.x + ub])) {
-        if (FIRST && pexists) {
-            const long ks = pcell / XW2_ROWS;
-            if (a.zero_all || !a.ks_bitmap || ((a.ks_bitmap[ks >> 5] >> (ks & 31)) & 1u)) {
-                const u32x4 z = {0u, 0u, 0u, 0u};
-                u32x4 *g = (u32x4 *)(a.logits + pcell * V) + half;
-                for (int c = 0; c < VC; ++c) {  // this lane's 16 B of each plane per k-step (layout below)
-                    g[8 * (c >> 1) + 2 * (c & 1)] = z;
-                    g[8 * (c >> 1) + 4 + 2 * (c & 1)] = z;
-                }
-            }
-        }
-        if (!past_len) {
-            const int col0 = 512 * hp, nc4 = ((H - col0 < 512 ? H - col0 : 512)) / 4;  // this pass's columns, in float4s
-            const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-            for (int k = tid; k < XG2_BT * nc4; k += 256) {
-                const int t = t0 + k / nc4;
-                if (t < Tb) *(f32x4 *)(a.slab_enc + (long)ub * a.B * T * H + ((long)b * T + t) * H + col0 + 4 * (k % nc4)) = z4;
-            }
-            for (int k = tid; k < XG2_BU * nc4; k += 256) {
-                const int u = u0 + k / nc4;
-                if (u < U1) *(f32x4 *)(a.slab_pred + (long)tt * a.B * U1 * H + ((long)b * U1 + u) * H + col0 + 4 * (k % nc4)) = z4;
-            }
-        }
-        return;
-    }
+    // A live tile holds a cell with non-null coefficients, so it lies inside the lengths (t0 < T_b, u0 <= U_b).  The tiles that are not on
+    // the list — past the lengths, or every cell outside the lattice, unreachable or flushed: each would have produced G = 0 — run nowhere
+    // and owe nothing here: the G rows the dW GEMM reads of them are zeroed by k_x2_dead_rows, their slab pieces are never written and the
+    // reductions leave them out by the same flag (JointBwdArgs::tile_flag).  The later column passes (FIRST = false) walk the same list.
 
     CellCoef cf = a.coef[pexists ? pcell : 0];
     const bool live = pexists && pt < Tb && cf.c1 != RNNT_NEG_INF;
@@ -1605,24 +1614,11 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2r(X3Args a, const int hp)
     const int VC = V / 16;
     if (4 * tq * XG2_BT >= Tb || u0 > Ub) return;    // workgroup-uniform: no lattice cell in any of the four blocks
     const bool winlen = t0 < Tb;                       // wave-uniform: this wave's block lies inside the lengths (else: zeros in, nothing out)
-    // k_dhidden_x2's dead-tile rule: a block without a live cell (X3Args::tile_live) was skipped by the first pass — its rows may hold
-    // logits — so it reads the zero padding row and owes the slabs zeros for this pass's columns
-    const bool wlive = winlen && (!a.tile_live || a.tile_live[((long)b * ((T + XG2_BT - 1) / XG2_BT) + tt) * gridDim.x + ub] != 0);
+    // k_dhidden_x2's dead-tile rule: a block without a live cell (X3Args::tile_live) was not run by the first pass — its rows may hold
+    // logits — so it reads the zero padding row, and writes nothing: the reductions leave a dead tile's slab pieces out by the same flag
+    const bool wlive = winlen && a.tile_live[((long)b * ((T + XG2_BT - 1) / XG2_BT) + tt) * gridDim.x + ub] != 0;
     const int any_live = __syncthreads_or(wlive ? 1 : 0);
-    auto zero_slabs = [&]() {
-        const int colz = 512 * hp + 4 * i;
-        if (colz >= H) return;
-        const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-        if (half == 0)
-            for (int k = 0; k < XG2_BT; ++k)
-                if (t0 + k < Tb) *(f32x4 *)(a.slab_enc + (long)ub * a.B * T * H + ((long)b * T + t0 + k) * H + colz) = z4;
-        for (int k = half; k < XG2_BU; k += 2)
-            if (u0 + k < U1) *(f32x4 *)(a.slab_pred + (long)tt * a.B * U1 * H + ((long)b * U1 + u0 + k) * H + colz) = z4;
-    };
-    if (!any_live) {  // workgroup-uniform: none of the four blocks has a live cell
-        if (winlen) zero_slabs();
-        return;
-    }
+    if (!any_live) return;  // workgroup-uniform: none of the four blocks has a live cell
     const long zrow = (long)a.B * T * U1;              // first zero padding row
     // row i of M tile m = cell (t0 + 2m + (i >> 4), u0 + (i & 15)); rows outside the lattice read the zero padding row.  G's planes of
     // k-step c: hi = 16 bytes at u32x4 index 8 (c >> 1) + 2 (c & 1) + half of the row, mid 64 bytes behind (k_dhidden_x2's layout)
@@ -1715,10 +1711,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2r(X3Args a, const int hp)
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the over-issued loads / DMAs: none may land in an LDS the next workgroup owns
-    if (!wlive) {
-        if (winlen) zero_slabs();
-        return;
-    }
+    if (!wlive) return;
 
     // ---- epilogue (k_dhidden_x2's, one wave = one block).  Accumulator register rr = 8 rh + r7 of M tile m, column tile n: t row
     // 2m + rh, u slot 8 (r7 >> 2) + (r7 & 3) + 4 half; column 512 hp + 4i + n.
@@ -1774,6 +1767,55 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2r(X3Args a, const int hp)
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// k_x2_dead_rows: the zeros the dW GEMM must find.  k_dw_x2 reads all 16 rows of every LIVE k-step (X3Args::ks_list); the rows that belong
+// to a live dHidden tile are written by k_dhidden_x2 (G, or zeros for cells outside the lattice), the rows of tiles that are not live —
+// a k-step straddles tile edges: 16 consecutive cells of a (b, t) line against 16-aligned u blocks — still hold logits.  One wave per four
+// live k-steps (grid-stride over the list): lane l looks up the tile flag of cell l & 15 of k-step l >> 4, then the whole wave zeroes each
+// flagged row, both planes = the V x 4 bytes of the logits row, 16 bytes per lane and store.  Most k-steps have no such row and cost two
+// loads.  No LDS, 4 waves per workgroup: it runs beside anything.  zero_all (the lab's table-walking dW kernel reads every row): every k-step that has a cell.
+// Rows of dead tiles and rows of live tiles are disjoint: the order against k_dhidden_x2 is free; both precede k_dw_x2.
+// ---------------------------------------------------------------------------------------
+#define XZ2_WG_WAVES 4
+__global__ __launch_bounds__(64 * XZ2_WG_WAVES) void k_x2_dead_rows(X3Args a, int ntt, int nub)
+{
+    const int lane = threadIdx.x & 63;
+    const long wave = (long)blockIdx.x * XZ2_WG_WAVES + (threadIdx.x >> 6), nwave = (long)gridDim.x * XZ2_WG_WAVES;
+    const long cells = (long)a.B * a.T * a.U1;
+    const long n = a.zero_all ? a.live_stats[1] : a.live_stats[0];
+    const int V4 = a.V / 4;
+    const u32x4 z = {0u, 0u, 0u, 0u};
+    for (long k = 4 * wave; k < n; k += 4 * nwave) {
+        const long kk = k + (lane >> 4);
+        int ks = 0;  // (a k-step index fits an int: ks_list's entries do)
+        bool dead = false;
+        if (kk < n) {
+            ks = a.zero_all ? (int)kk : a.ks_list[kk];
+            const long c = (long)ks * XW2_ROWS_ + (lane & 15);
+            if (c < cells) {
+                const int u = (int)(c % a.U1);
+                const long bt = c / a.U1;
+                const int t = (int)(bt % a.T);
+                const long b = bt / a.T;
+                dead = a.tile_live[(b * ntt + t / XG2_BT_) * nub + u / XG2_BU_] == 0;
+            }
+        }
+        unsigned long long m = __ballot(dead);  // (wave-uniform) bit l: row 16 ks(l >> 4) + (l & 15) belongs to a tile that is not live
+        for (; m; m &= m - 1) {
+            const int r = __builtin_ctzll(m);
+            u32x4 *row = (u32x4 *)(a.logits + ((long)__shfl(ks, r, 64) * XW2_ROWS_ + (r & 15)) * a.V);
+            for (int q = lane; q < V4; q += 64) row[q] = z;
+        }
+    }
+}
+void launch_x2_dead_rows(const X3Args &a, hipStream_t st)
+{
+    const long nks = ((long)a.B * a.T * a.U1 + XW2_ROWS_ - 1) / XW2_ROWS_;  // k-steps with a cell: the most the walk can hold
+    const long want = (nks + 4 * XZ2_WG_WAVES - 1) / (4 * XZ2_WG_WAVES), cap = (long)(a.n_cu > 0 ? a.n_cu : 256) * 8;
+    const int ntt = (a.T + XG2_BT_ - 1) / XG2_BT_;
+    hipLaunchKernelGGL(k_x2_dead_rows, dim3((unsigned)(want < cap ? want : cap)), dim3(64 * XZ2_WG_WAVES), 0, st, a, ntt, a.n_ublk16);
+}
+
 bool x2_dhidden_ok(int U1, int H, int V)
 {
     // raw buffers over one tile's logits rows (32-bit byte offsets), W pack addressing
@@ -1793,7 +1835,8 @@ void launch_dhidden_x2(const X3Args &a, hipStream_t st)
         (void)hipFuncSetAttribute((const void *)k_dhidden_x2<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (dev >= 0) attr_set[dev] = true;
     }
-    dim3 grid(a.n_ublk16, (a.T + XG2_BT - 1) / XG2_BT, a.B);
+    // one workgroup per tile; those past the live-tile list's length (known on the device only) return at once
+    dim3 grid((unsigned)((long)a.n_ublk16 * ((a.T + XG2_BT - 1) / XG2_BT) * a.B));
     if (a.H < 512) hipLaunchKernelGGL((k_dhidden_x2<true, true>), grid, dim3(256), lds, st, a, 0);
     else hipLaunchKernelGGL((k_dhidden_x2<true, false>), grid, dim3(256), lds, st, a, 0);
     for (int hp = 1; hp * 512 < a.H; ++hp) {
@@ -1968,8 +2011,8 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
         for (int k = tid; k < 256; k += 256) { s_part[2 * k] = RNNT_NEG_INF; s_part[2 * k + 1] = 0.f; }
         __syncthreads();  // s_next, s_part visible; every wave is past the previous tile's LDS reads
         const int next = s_next[it & 1];
-        // A tile entirely in the time steps past one utterance's length: its logits are never read (k_dhidden_x2 zero-fills the
-        // G rows of dead tiles itself), but its hidden rows must be finite (k_dw_x2 multiplies them by zeros): such a tile runs
+        // A tile entirely in the time steps past one utterance's length: its logits are never read (k_x2_dead_rows zeroes the
+        // G rows dW reads of the tiles k_dhidden_x2 does not run), but its hidden rows must be finite (k_dw_x2 multiplies them by zeros): such a tile runs
         // the production of its first pass WITHOUT the MFMAs.
         bool dead = false;
         if (!LIN) {
