@@ -103,11 +103,13 @@ def test_engine_linear_x2_fwd_bwd_vs_float64(M, K, N, xscale, gscale):
     """The projections on the f16x2 matrix pipes (rnnt_engine_linear_x2_fwd / _bwd, round 5: reference rnnt/joint.py:8-12,26-30 —
     y through the joint forward's pipeline as a plain GEMM, dx through the same kernel on W^T, dW / db through the joint's dW kernel)
     against float64 torch at the fp32 tolerances (1e-4 of each result's largest entry), over operand magnitudes that need the
-    device-found power-of-two scales, row counts that are not multiples of any tile, a permuted row stride."""
+    device-found power-of-two scales, row counts that are not multiples of any tile.  x is a row-strided slice of a wider buffer:
+    not contiguous, so engine._rows gathers it into contiguous rows and the kernels see ldx == K — this checks that gather, not a
+    row stride; ldx != K is passed to the kernels by tests/test_linear_abi_gpu.py::test_row_stride."""
     import rnnt_amd
     torch.manual_seed(M + K + N)
     xbuf = torch.randn(M, K + 8, device="cuda") * xscale
-    x = xbuf[:, :K].requires_grad_(True)  # rows K + 8 floats apart
+    x = xbuf[:, :K].requires_grad_(True)  # rows K + 8 floats apart (until engine._rows copies them)
     W = (torch.randn(N, K, device="cuda") / K ** 0.5).requires_grad_(True)
     b = torch.randn(N, device="cuda", requires_grad=True)
     G = torch.randn(M, N, device="cuda") * gscale
