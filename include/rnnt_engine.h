@@ -636,9 +636,10 @@ typedef struct rnnt_engine_ws_layout {
     size_t aux, aux_bytes; /* RNNT_DTYPE_F32_BF16X3: fp32 hidden + W pack of the RNNT_VARIANT_X3_FP32_* stages, placed BEHIND
                             * `total` (aux == total): only a call with such a variant needs total + aux_bytes */
     size_t ep;            /* RNNT_DTYPE_F32_F16X2: exp(2 enc) [B][H/16][T][16] then exp(2 pred) [B][H/16][U1][16], fp32 (0: none) */
-    size_t x2_live;       /* RNNT_DTYPE_F32_F16X2 (0: none): the live structures of the last call's backward.  At +0 four int32 counts:
-                           * live 16-cell dW k-steps, k-steps that hold a cell, live dHidden tiles (8 t x 16 u), dHidden tiles; at +256 one
-                           * byte per dHidden tile [B][ceil(T/8)][ceil(U1/16)], 1 = live (the k-step bitmap and list follow) */
+    size_t x2_live;       /* RNNT_DTYPE_F32_F16X2 (0: none): the live structures of the last call's backward.  At +0 six int32 counts:
+                           * live 16-cell dW k-steps, k-steps that hold a cell, live dHidden tiles (8 t x 16 u), dHidden tiles, live 4-cell
+                           * dW groups, groups that hold a cell; at +256 one byte per dHidden tile [B][ceil(T/8)][ceil(U1/16)], 1 = live (the
+                           * k-step bitmap and list, the tile list, the group bitmap and list follow) */
 } rnnt_engine_ws_layout;
 
 int rnnt_engine_workspace_layout(int B, int T, int U1, int H, int V, int dtype,

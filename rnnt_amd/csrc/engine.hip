@@ -143,7 +143,7 @@ void layout(int B, int T, int U1, int H, int V, int dtype, rnnt_engine_ws_layout
         L->counters = o; o += 1024 + align_up(tab > lst ? tab : lst);
         if (bf || x2) o += align_up((size_t)L->n_split * 64);  // k_dw_bf16's / k_dw_x2's progress words, behind the table
     }
-    if (x2) { L->x2_live = o; o += align_up(x2_live_bytes(B, T, U1, (long)rows_pad)); }  // counts, tile flags and list, k-step bitmap and list (launch_x2_live)
+    if (x2) { L->x2_live = o; o += align_up(x2_live_bytes(B, T, U1, (long)rows_pad)); }  // counts, tile flags and list, k-step and group bitmaps and lists (launch_x2_live)
     L->total = o;
     if (x3) {  // fp32 hidden + fp32 W pack of the stages that can run on the fp32 route's kernels (RNNT_VARIANT_X3_FP32_*):
         // BEHIND `total` — only a call that asks for such a variant needs a workspace of total + aux_bytes
@@ -329,6 +329,7 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
         // stand in (RNNT_VARIANT_X3_FP32_FWD / _DH): same data, one stage swapped — how each x3 kernel is checked.
         X3Args h;
         h.tile_live = nullptr; h.ks_bitmap = nullptr; h.ks_list = nullptr; h.live_stats = nullptr; h.tile_list = nullptr; h.zero_all = 0;
+        h.grp_bitmap = nullptr; h.grp_list = nullptr; h.dw_ksteps = 0;
         double flush_log2 = -HUGE_VAL;  // the flush rule's threshold (x2.hip): log2 of 2^-26 / g_scale; -inf flags nothing
         float flush_lin = 0.f;
         h.enc = encp; h.enc_sb = esb; h.enc_st = est; h.pred = (const float *)pred;
@@ -367,6 +368,7 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
         if (x2) {
             x2_live_carve(ws + L.x2_live, B, T, U1, (long)L.rows_pad, h);
             h.zero_all = x2_dw_walks_table(H, V, xflags) ? 1 : 0;
+            h.dw_ksteps = x2_dw_walks_ksteps(H, V, xflags) ? 1 : 0;
             // the fp32 kernels standing in for dHidden multiply G in fp32, where a flushed cell's G is small but not zero: no flush, no tile
             // skipping there (k_x2_split_g writes every row, so the dW list walk still applies)
             if (f32_dh) { flush_log2 = -HUGE_VAL; flush_lin = 0.f; }
@@ -422,7 +424,7 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
         }
         if (x2) {
             loss_stages(&flush_log2, flush_lin);
-            if (stages & ST_COEF) launch_x2_live(h, st);  // tile flags, k-step bitmap / list, counts: from the coefficients
+            if (stages & ST_COEF) launch_x2_live(h, st);  // tile flags, k-step and group bitmaps / lists, counts: from the coefficients
         } else {
             loss_stages();
         }
@@ -435,7 +437,7 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
                 if (x2) launch_x2_split_g(h, st);
                 else launch_x3_split_g(h, st);  // -> hi | mid in place, lo beside
             } else if (x2) {
-                launch_x2_dead_rows(h, st);  // rows of dead tiles inside live k-steps: zeros for dW (disjoint from the live tiles' rows)
+                launch_x2_dead_rows(h, st);  // rows of dead tiles inside live groups (k_dw_x2m: k-steps): zeros for dW (disjoint from the live tiles' rows)
                 launch_dhidden_x2(h, st);
             } else {
                 launch_dhidden_x3(h, st);

@@ -185,17 +185,21 @@ struct X3Args {
     int *dw_prog;               // [n_split][16] progress words of k_dw_x2's tiles (zeroed by its launcher), or NULL
     float *ep_enc, *ep_pred;    // exp(2 enc) [B][H/16][T][16], exp(2 pred) [B][H/16][U1][16] (k_x2_make_ep, every call)
     unsigned *ep_flag;          // device word: != 0 when an input lies outside the factored tanh's range (the exact forward runs)
-    // live structures of the backward (launch_x2_live, after the coefficients; x2.hip "flush rule"); the Linear layer's dW sets ks_list / live_stats only
+    // live structures of the backward (launch_x2_live, after the coefficients; x2.hip "flush rule"); the Linear layer's dW sets ks_list / grp_list / live_stats only
     const unsigned char *tile_live;  // [B][ceil(T/8)][n_ublk16]: 1 = the dHidden tile holds a cell with non-null coefficients
-    const unsigned *ks_bitmap;       // bit k: 16-cell k-step k of the dW GEMM is live (holds such a cell); what k_dw_x2 walks as ks_list
+    const unsigned *ks_bitmap;       // bit k: 16-cell k-step k of the dW GEMM is live (holds such a cell); what k_dw_x2m walks as ks_list
     int *ks_list;                    // ascending live k-steps, then >= 8 entries naming the first all-padding k-step (rows_pad / 16)
-    int *live_stats;                 // [0] live k-steps = length of ks_list, [1] k-steps with a cell, [2] live dHidden tiles = length of tile_list, [3] dHidden tiles
+    const unsigned *grp_bitmap;      // bit g: cells 4g .. 4g+3 (linear cell order) hold a live cell; what k_dw_x2 walks as grp_list
+    int *grp_list;                   // ascending live groups, 16-byte aligned, then >= 4 ring stages + 3 entries naming the first all-padding group (rows_pad / 4)
+    int *live_stats;                 // [0] live k-steps = length of ks_list, [1] k-steps with a cell, [2] live dHidden tiles = length of tile_list, [3] dHidden tiles,
+                                     // [4] live groups = length of grp_list, [5] groups with a cell
     const int *tile_list;            // ascending indices [b][tt][ub] of the tiles whose flag is 1: the workgroups of k_dhidden_x2 (entries past live_stats[2] hold anything)
     int zero_all;                    // 1: the dW kernel of this call walks the 32-cell table (the lab's k_dw_x2p): k_x2_dead_rows zero-fills every row of the tiles that are not live
+    int dw_ksteps;                   // 1: the dW kernel of this call walks ks_list (k_dw_x2m): k_x2_dead_rows zeroes the dead tiles' rows of the live k-steps, not of the live groups
 };
 size_t x2_live_bytes(int B, int T, int U1, long rows_pad);  // bytes of the region below
-void x2_live_carve(void *region, int B, int T, int U1, long rows_pad, X3Args &a);  // points tile_live .. live_stats into the region
-void launch_x2_live(const X3Args &a, hipStream_t st);  // builds all four from X3Args::coef
+void x2_live_carve(void *region, int B, int T, int U1, long rows_pad, X3Args &a);  // points tile_live .. grp_list into the region
+void launch_x2_live(const X3Args &a, hipStream_t st);  // builds them all from X3Args::coef
 bool x3_fwd_ok(int U1, int H, int V);      // the bf16x3 forward kernel covers this shape (else: the fp32 route's)
 bool x3_dhidden_ok(int U1, int H, int V);  // likewise k_dhidden_x3
 size_t x3_wpack_fwd_bytes(int H, int V);
@@ -225,7 +229,7 @@ size_t x2_ep_bytes(int B, int T, int U1, int H);
 void launch_joint_fwd_x2(const X3Args &a, hipStream_t st);   // one 512-register wave per SIMD
 bool x2_fwd_d_ok(int U1, int H, int V);
 void launch_joint_fwd_x2d(const X3Args &a, hipStream_t st);  // two 4-wave workgroups per CU, A in registers (RNNT_VARIANT_X2_FWD_2WG)
-void launch_x2_dead_rows(const X3Args &a, hipStream_t st);  // zero G rows of dead tiles' cells inside live k-steps (what k_dw_x2 reads beside the live tiles' rows)
+void launch_x2_dead_rows(const X3Args &a, hipStream_t st);  // zero G rows of dead tiles' cells inside live groups (what k_dw_x2 reads beside the live tiles' rows; X3Args::dw_ksteps: inside live k-steps)
 void launch_dhidden_x2(const X3Args &a, hipStream_t st);
 // the joint's input projections (audio_ln / text_ln) and their backward on the f16x2 pipes (x2.hip, round 5)
 size_t x2_linear_ws_bytes(int M, int K, int N, bool bwd);
@@ -235,7 +239,8 @@ void launch_linear_x2_bwd(const float *x, long ldx, const float *W, const float 
                           hipStream_t st);
 int x2_dw_tiles(int H, int V);  // workgroup tiles per split of launch_dw_x2 (k_dw_x2 / k_dw_x2m)
 void launch_dw_reduce_x2(const X3Args &a, float *grad_W, float *grad_bias, hipStream_t st);  // the slabs' sum, fp64 accumulate, one rounding
-bool x2_dw_walks_table(int H, int V, int flags);  // launch_dw_x2's kernel for this shape reads k_dw_table's ranges, not X3Args::ks_list
+bool x2_dw_walks_table(int H, int V, int flags);  // launch_dw_x2's kernel for this shape reads k_dw_table's ranges, not X3Args::grp_list
+bool x2_dw_walks_ksteps(int H, int V, int flags);  // ... reads X3Args::ks_list (k_dw_x2m)
 void launch_dw_x2(const X3Args &a, hipStream_t st, bool build_table = true, bool zero_prog = true);  // k_dw_x2<4> (k_dw_x2<4, true> when H % 256 == 128); -DRNNT_LAB builds: also k_dw_x2<8> / k_dw_x2p behind RNNT_VARIANT_X2_DW_8W / _P16
 
 // ---- decode.hip

@@ -19,8 +19,8 @@
 // Flush rule (below, "The flush rule and the live structures of the backward"): fp16's narrow exponent makes both planes of g_scale G
 // exactly zero wherever the lattice's occupancy is below ~2^-38 — half the cells of the benchmark's batch.  The coefficient kernel
 // proves that per cell (|g_scale G| < 2^-26, one binade inside what rounds to zero: lattice.hip coef_cell), and the two backward GEMMs
-// run the dHidden tiles and the 16-cell dW k-steps that hold another cell, each from an ascending list built on the device: k_dhidden_x2's
-// workgroups are the entries of the live-tile list.  RNNT_VARIANT_X2_NO_FLUSH_SKIP switches the rule off per call (same lists, by length).
+// run the dHidden tiles and the 4-cell dW groups that hold another cell, each from an ascending list built on the device: k_dhidden_x2's
+// workgroups are the entries of the live-tile list, a k-step of k_dw_x2 is four entries of the live-group list.  RNNT_VARIANT_X2_NO_FLUSH_SKIP switches the rule off per call (same lists, by length).
 //
 // MFMA operand maps (v_mfma_f32_32x32x16_f16, as the bf16 form): lane l = (r = l&31, h = l>>5) holds A[row r][k = 8h+j] and
 // B[k = 8h+j][col r], j = 0..7; C/D: col = l&31, row = (reg&3) + 8*(reg>>2) + 4*(l>>5).
@@ -30,6 +30,7 @@ typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((address_space(3))) void *lds_vptr;
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -253,9 +254,12 @@ void launch_x2_zero_padding(const X3Args &a, int what, hipStream_t st)
 //                         is not on it costs nothing there and writes nothing: its slab pieces may hold anything — k_reduce_enc /
 //                         k_reduce_pred add a piece only where the tile's flag is 1 (JointBwdArgs::tile_flag; the sums start at +0 and the
 //                         pieces left out were exact zeros) — and the G rows dW reads of it are zeroed by k_x2_dead_rows;
-//   ks_bitmap / ks_list   the 16-cell k-steps of the dW GEMM (linear cell index / 16) that hold such a cell, as a bitmap and as the
-//                         ascending list k_dw_x2 walks (fixed order: dW stays bitwise reproducible), padded with entries that name
-//                         the first k-step of the zero padding rows for the ring's read-ahead;
+//   grp_bitmap / grp_list the 4-cell groups of the dW GEMM (linear cell index / 4: the rows of one DMA piece) that hold such a cell, as a
+//                         bitmap and as the ascending list k_dw_x2 walks four entries to a k-step (fixed order: dW stays bitwise
+//                         reproducible); the list is 16-byte aligned and padded with entries that name the first group of the zero
+//                         padding rows, for the ring's read-ahead and the missing groups of the last k-step.  The live cells of a (b, t)
+//                         line form a band of ~100 cells; 16-cell k-steps cut it at 16-cell boundaries and list ~12 % more rows;
+//   ks_bitmap / ks_list   the same for the 16-cell k-steps (linear cell index / 16): what k_dw_x2m and the lab kernels still walk;
 //   live_stats            the counts (readable from the workspace: rnnt_engine_ws_layout::x2_live).
 // Dropping a flushed cell changes no bit of costs, dEnc or dPred (its products were exact zeros); dW / db change in summation
 // order only (the splits cut the live list at other cells).  RNNT_VARIANT_X2_NO_FLUSH_SKIP flags no cell: the structures then hold
@@ -264,7 +268,8 @@ void launch_x2_zero_padding(const X3Args &a, int what, hipStream_t st)
 #define XL2_BLK 1024
 __device__ __forceinline__ bool x2_coef_live(const CellCoef &c) { return !(c.c1 == RNNT_NEG_INF && c.sb == 0.f && c.se == 0.f); }
 namespace {
-struct X2LiveWs { size_t tiles, bitmap, blk, list, tlist, total; long nks, ntile; int nblk; };
+#define XL2_GPAD 32  // padding entries behind the group list (k_dw_x2 reads up to 4 XW2_NST + 3 entries past the live ones: asserted there)
+struct X2LiveWs { size_t tiles, bitmap, blk, list, tlist, gbitmap, gblk, glist, total; long nks, ntile; int nblk; };
 X2LiveWs x2_live_layout(int B, int T, int U1, long rows_pad)
 {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -278,6 +283,10 @@ X2LiveWs x2_live_layout(int B, int T, int U1, long rows_pad)
     L.blk = o; o += al((size_t)L.nblk * 4);
     L.list = o; o += al((size_t)(L.nks + 8) * 4);
     L.tlist = o; o += al((size_t)L.ntile * 4);
+    // the 4-cell groups (4 per k-step): bitmap, live groups per 1024 (4 counts per block of 1024 k-steps), list (256-byte aligned)
+    L.gbitmap = o; o += al((size_t)L.nblk * (XL2_BLK / 2));
+    L.gblk = o; o += al((size_t)L.nblk * 16);
+    L.glist = o; o += al((size_t)(4 * L.nks + XL2_GPAD) * 4);
     L.total = o;
     return L;
 }
@@ -289,13 +298,17 @@ void x2_live_carve(void *region, int B, int T, int U1, long rows_pad, X3Args &a)
     char *r = (char *)region;
     a.live_stats = (int *)r; a.tile_live = (const unsigned char *)(r + L.tiles); a.ks_bitmap = (const unsigned *)(r + L.bitmap);
     a.ks_list = (int *)(r + L.list); a.tile_list = (const int *)(r + L.tlist);
+    a.grp_bitmap = (const unsigned *)(r + L.gbitmap); a.grp_list = (int *)(r + L.glist);
 }
 // one workgroup per 1024 k-steps (16384 cells, read coalesced: 16 rounds of one cell per thread; a wave's ballot covers 4 k-steps):
-// live flags -> 16 bitmap words, their number -> blk
+// live flags -> 16 bitmap words, their number -> blk.  The same ballots give the 4-cell groups (16 per wave and round: 64 bitmap words per
+// workgroup, their number per 1024 groups -> gblk[4 block + 0..3]: the unit k_x2_live_scan / k_x2_live_write work in)
 __global__ __launch_bounds__(XL2_BLK) void k_x2_live_count(const CellCoef *__restrict__ coef, long cells,
-                                                           unsigned long long *__restrict__ bitmap, int *__restrict__ blk)
+                                                           unsigned long long *__restrict__ bitmap, int *__restrict__ blk,
+                                                           unsigned long long *__restrict__ gbitmap, int *__restrict__ gblk)
 {
     __shared__ unsigned short s_nib[16][16];  // [round = bitmap word][wave]: the wave's 4 k-step flags
+    __shared__ unsigned short s_grp[16][16];  // [round][wave]: the wave's 16 group flags
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long base = (long)blockIdx.x * XL2_BLK * XW2_ROWS_;
     for (int it = 0; it < 16; ++it) {
@@ -305,6 +318,14 @@ __global__ __launch_bounds__(XL2_BLK) void k_x2_live_count(const CellCoef *__res
         if (lane == 0)
             s_nib[it][wave] = (unsigned short)(((bal & 0xffffull) ? 1 : 0) | ((bal & 0xffff0000ull) ? 2 : 0) |
                                                ((bal & 0xffff00000000ull) ? 4 : 0) | ((bal & 0xffff000000000000ull) ? 8 : 0));
+        // bit 4j of x: any of the ballot's bits 4j .. 4j+3; then every fourth bit gathered into the low 16
+        unsigned long long x = bal | (bal >> 1);
+        x = (x | (x >> 2)) & 0x1111111111111111ull;
+        x = (x | (x >> 3)) & 0x0303030303030303ull;
+        x = (x | (x >> 6)) & 0x000f000f000f000full;
+        x = (x | (x >> 12)) & 0x000000ff000000ffull;
+        x = (x | (x >> 24)) & 0xffffull;
+        if (lane == 0) s_grp[it][wave] = (unsigned short)x;
     }
     __syncthreads();
     int cnt = 0;
@@ -318,38 +339,52 @@ __global__ __launch_bounds__(XL2_BLK) void k_x2_live_count(const CellCoef *__res
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
         if (lane == 0) blk[blockIdx.x] = cnt;
+        // group word j = lane: groups 64 j .. of the workgroup's 4096 = round j >> 2, waves 4 (j & 3) .. + 3
+        unsigned long long w = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w |= (unsigned long long)s_grp[lane >> 2][4 * (lane & 3) + k] << (16 * k);
+        gbitmap[(long)blockIdx.x * 64 + lane] = w;
+        int gcnt = __popcll(w);
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) gcnt += __shfl_xor(gcnt, o, 64);  // 16 words = 1024 groups
+        if ((lane & 15) == 0) gblk[(long)blockIdx.x * 4 + (lane >> 4)] = gcnt;
     }
 }
-// exclusive scan of the block counts in place (one workgroup, k_dw_list_scan's); the counts; the list's padding entries; and the live-tile
+// exclusive scan of the block counts in place (one workgroup, k_dw_list_scan's), k-steps then groups; the counts; the lists' padding entries; and the live-tile
 // list: a thread takes 64 consecutive flag bytes (four 16-byte loads; the flag region is padded to 256 bytes, bytes past ntile are masked),
 // counts them, the workgroup scans the counts and the thread writes its tiles' indices at its offset — 65536 tiles per round, positions by
 // counting and scanning alone (ascending, the same every call).
 #define XL2_TPT 64  // tiles per thread and round
 __global__ __launch_bounds__(1024) void k_x2_live_scan(int *__restrict__ blk, int nblk, int *__restrict__ stats, int *__restrict__ list,
                                                        long cells, long nks, long ntile, const unsigned char *__restrict__ tile_live,
-                                                       int *__restrict__ tile_list)
+                                                       int *__restrict__ tile_list, int *__restrict__ gblk, int *__restrict__ glist)
 {
     __shared__ int s_w[16];
     __shared__ int s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nblk; base += 1024) {
-        const int i = base + threadIdx.x;
-        const int v = i < nblk ? blk[i] : 0;
-        int x = v;
+    auto scan_counts = [&](int *cnt, int n) {  // exclusive scan of cnt[0 .. n) in place; returns the sum
+        if (threadIdx.x == 0) s_carry = 0;
+        __syncthreads();
+        for (int base = 0; base < n; base += 1024) {
+            const int i = base + threadIdx.x;
+            const int v = i < n ? cnt[i] : 0;
+            int x = v;
 #pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d, 64); if ((threadIdx.x & 63) >= d) x += y; }
-        if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = x;
+            for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d, 64); if ((threadIdx.x & 63) >= d) x += y; }
+            if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = x;
+            __syncthreads();
+            int off = s_carry;
+            for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) off += s_w[w];
+            if (i < n) cnt[i] = off + x - v;
+            __syncthreads();
+            if (threadIdx.x == 1023) s_carry = off + x;
+            __syncthreads();
+        }
+        const int sum = s_carry;
         __syncthreads();
-        int off = s_carry;
-        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) off += s_w[w];
-        if (i < nblk) blk[i] = off + x - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = off + x;
-        __syncthreads();
-    }
-    const int total = s_carry;
-    __syncthreads();
+        return sum;
+    };
+    const int total = scan_counts(blk, nblk);
+    const int gtotal = scan_counts(gblk, 4 * nblk);
     if (threadIdx.x == 0) s_carry = 0;  // now: live tiles before this round (their number = the sum of k_x2_live_tiles' flag bytes)
     __syncthreads();
     for (long base = 0; base < ntile; base += 1024L * XL2_TPT) {
@@ -382,19 +417,25 @@ __global__ __launch_bounds__(1024) void k_x2_live_scan(int *__restrict__ blk, in
     }
     if (threadIdx.x == 0) {
         stats[0] = total; stats[1] = (int)((cells + XW2_ROWS_ - 1) / XW2_ROWS_); stats[2] = s_carry; stats[3] = (int)ntile;
+        stats[4] = gtotal; stats[5] = (int)((cells + 3) / 4);
     }
     if (threadIdx.x < 8) list[total + threadIdx.x] = (int)nks;  // rows rows_pad ..: zero padding (rows_alloc >= rows_pad + 96)
+    if (threadIdx.x < XL2_GPAD) glist[gtotal + threadIdx.x] = (int)(4 * nks);  // group rows_pad / 4: the same rows' first four
 }
-__global__ __launch_bounds__(XL2_BLK) void k_x2_live_write(const unsigned long long *__restrict__ bitmap, long nks, const int *__restrict__ blk,
-                                                           int *__restrict__ list)
+// workgroups [0, nblk): 1024 k-steps each -> list; workgroups [nblk, 5 nblk): 1024 groups each -> glist (same code on the groups' bitmap and offsets)
+__global__ __launch_bounds__(XL2_BLK) void k_x2_live_write(const unsigned long long *__restrict__ bitmap, int nblk, const int *__restrict__ blk,
+                                                           int *__restrict__ list, const unsigned long long *__restrict__ gbitmap,
+                                                           const int *__restrict__ gblk, int *__restrict__ glist)
 {
     __shared__ int s_w[XL2_BLK / 64];
-    const long k = (long)blockIdx.x * XL2_BLK + threadIdx.x;
+    int bid = blockIdx.x;  // (workgroup-uniform)
+    if (bid >= nblk) { bid -= nblk; bitmap = gbitmap; blk = gblk; list = glist; }
+    const long k = (long)bid * XL2_BLK + threadIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned long long bal = bitmap[k >> 6];
     if (lane == 0) s_w[wave] = __popcll(bal);
     __syncthreads();
-    int off = blk[blockIdx.x];
+    int off = blk[bid];
     for (int w = 0; w < wave; ++w) off += s_w[w];
     if ((bal >> lane) & 1ull) list[off + __popcll(bal & ((1ull << lane) - 1ull))] = (int)k;
 }
@@ -423,12 +464,13 @@ void launch_x2_live(const X3Args &a, hipStream_t st)
     const X2LiveWs L = x2_live_layout(a.B, a.T, a.U1, a.rows_pad);
     const long cells = (long)a.B * a.T * a.U1;
     int *blk = (int *)((char *)a.live_stats + L.blk);
-    unsigned long long *bitmap = (unsigned long long *)a.ks_bitmap;
+    int *gblk = (int *)((char *)a.live_stats + L.gblk);
+    unsigned long long *bitmap = (unsigned long long *)a.ks_bitmap, *gbitmap = (unsigned long long *)a.grp_bitmap;
     const int ntt = (a.T + XG2_BT_ - 1) / XG2_BT_, nub = (a.U1 + XG2_BU_ - 1) / XG2_BU_;
     hipLaunchKernelGGL(k_x2_live_tiles, dim3((unsigned)((L.ntile + 3) / 4)), dim3(256), 0, st, a.coef, a.T, a.U1, ntt, nub, L.ntile, (unsigned char *)a.tile_live);
-    hipLaunchKernelGGL(k_x2_live_count, dim3(L.nblk), dim3(XL2_BLK), 0, st, a.coef, cells, bitmap, blk);
-    hipLaunchKernelGGL(k_x2_live_scan, dim3(1), dim3(1024), 0, st, blk, L.nblk, a.live_stats, a.ks_list, cells, L.nks, L.ntile, a.tile_live, (int *)a.tile_list);
-    hipLaunchKernelGGL(k_x2_live_write, dim3(L.nblk), dim3(XL2_BLK), 0, st, bitmap, L.nks, blk, a.ks_list);
+    hipLaunchKernelGGL(k_x2_live_count, dim3(L.nblk), dim3(XL2_BLK), 0, st, a.coef, cells, bitmap, blk, gbitmap, gblk);
+    hipLaunchKernelGGL(k_x2_live_scan, dim3(1), dim3(1024), 0, st, blk, L.nblk, a.live_stats, a.ks_list, cells, L.nks, L.ntile, a.tile_live, (int *)a.tile_list, gblk, a.grp_list);
+    hipLaunchKernelGGL(k_x2_live_write, dim3(5 * L.nblk), dim3(XL2_BLK), 0, st, bitmap, L.nblk, blk, a.ks_list, gbitmap, gblk, a.grp_list);
 }
 
 // dW / db = the sum of the split-K slabs, accumulated in fp64 and rounded ONCE (fixed order: bitwise reproducible).  The splits cut the
@@ -466,9 +508,12 @@ void launch_dw_reduce_x2(const X3Args &a, float *grad_W, float *grad_bias, hipSt
 // One k-step = 16 cells = 3 products x 16 tiles = 48 MFMAs (1536 matrix-pipe cycles) against 32 KiB staged.  Per k-step:
 // counted vmcnt + one barrier publish stage ks, the 8 DMAs of stage ks+2 go into the slot of ks-1 threaded through the
 // MFMAs (3 + 3 + 2), fragment reads run one product ahead of their MFMAs.  Products ah.bh, am.bh, ah.bm.
-// K walk: the split-K ranges are cut from the ascending list of LIVE k-steps (X3Args::ks_list: the k-steps that hold a cell with non-null
-// coefficients — inside the lengths, reachable, not flushed), evenly, so the splits are balanced whatever the lattices' shapes; k-step ks of
-// a split multiplies the 16 rows of k-step list[g_lo + ks], one pipeline run per split.  Rows of a live k-step that belong to no live cell
+// K walk: the split-K ranges are cut from the ascending list of LIVE 4-cell groups (X3Args::grp_list: the groups that hold a cell with
+// non-null coefficients — inside the lengths, reachable, not flushed) in units of k-steps of four entries, n_k = ceil(live groups / 4),
+// evenly, so the splits are balanced whatever the lattices' shapes; k-step ks of a split multiplies the 16 rows of the groups
+// list[4 (g_lo + ks)] .. + 3 — DMA piece i of a plane reads the four rows of entry i through a raw buffer of its own — one pipeline run per
+// split; the groups the last k-step lacks are padding entries (zero rows, read like any other: every vector memory operation of a k-step
+// is unconditional and in one order, the counted waits do not know the difference).  Rows of a live group that belong to no live cell
 // hold zeros (k_dhidden_x2 writes them inside its live tiles, k_x2_dead_rows those of the tiles that are not live).
 // The accumulators hold g_scale x 2^14 x dW: the epilogue multiplies by X3Args::dw_rescale (a power of two).
 // ---------------------------------------------------------------------------------------
@@ -482,6 +527,15 @@ static_assert(XW2_ROWS == XW2_ROWS_, "k-step size");
 #define XW2_TILE (XW2_NST * XW2_STAGE)  // ring of one operand tile: [stage][plane][16 x 256 B] = 24 KiB
 #define XW2_GRAN 32  // granule of the live-row table the lab's k_dw_x2p still walks (k_dw_table, shared with the bf16 routes: 2 k-steps); the Linear layer's table unit
 
+// the four list entries of a k-step (X3Args::grp_list): ONE 16-byte scalar load, then WAIT (a counted vmcnt or nothing), then the wait for
+// the load itself — one statement, so that the entries have landed wherever they are named
+#define XW2_LOAD_ENT4(ent, ep, WAIT) asm volatile("s_load_dwordx4 %0, %1, 0x0\n\t" WAIT "s_waitcnt lgkmcnt(0)" : "=s"(ent) : "s"(ep) : "memory")
+// rows 4 ent .. 4 ent + 3 of a plane (base: the plane's row 0, gbytes: four rows) as the raw buffer of a DMA piece whose instruction carries the
+// immediate offset imm: taken back out of the base, added to the range (wave-uniform)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t x2_piece_rsrc(const char *base, int ent, unsigned gbytes, int imm)
+{
+    return __builtin_amdgcn_make_buffer_rsrc((void *)(base + (unsigned long long)(unsigned)ent * gbytes - imm), 0, (int)gbytes + imm, 0x00020000);
+}
 struct X2Frag { u32x2 lo[4], hi[4]; };  // 4 tiles: cells 0-3 / 4-7 of a lane's 8
 #define X2_LANDED(f, N)                                                                                          \
     asm volatile("s_waitcnt lgkmcnt(" #N ")"                                                                     \
@@ -518,8 +572,10 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
     }
     const int tile = id % tiles, split = id / tiles;
     const int vb = tile / n_hblk, hb = tile % n_hblk;
-    // this split's share [g_lo, g_hi) of the LIVE k-steps (X3Args::ks_list, launch_x2_live; the Linear layer: every k-step)
-    const long nlive = __builtin_amdgcn_readfirstlane(a.live_stats[0]);  // (uniform by construction; said so: the walk's control flow is scalar)
+    // this split's share [g_lo, g_hi) of the k-steps of LIVE groups, four list entries each (X3Args::grp_list, launch_x2_live; the Linear
+    // layer: every group); the last k-step is filled up with the list's padding entries
+    static_assert(XL2_GPAD >= 4 * XW2_NST + 3, "read-ahead of NST k-steps behind a partly filled last one");
+    const long nlive = (__builtin_amdgcn_readfirstlane(a.live_stats[4]) + 3) / 4;  // (uniform by construction; said so: the walk's control flow is scalar)
     // (the 64-bit divisions run on the vector ALU: the quotients, at most nlive, are handed back to scalar registers)
     const int g_lo = __builtin_amdgcn_readfirstlane((int)(nlive * split / a.n_split));
     const int g_hi = __builtin_amdgcn_readfirstlane((int)(nlive * (split + 1) / a.n_split));
@@ -561,28 +617,29 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
             for (int p = 0; p < 2; ++p) pbase[p] = (const char *)(a.hidden + p * a.plane_stride) + 2L * col0;
             rstride = 2L * H;
         }
-        // DMA i (0..3) of a plane's 16 rows: rows 4i .. 4i+3; lane L: row 4i + (L>>4), LDS chunk position L&15
-        // <- global chunk jg = (L&15) ^ swz(row), swz = ((L>>4)<<2) | (i&3)
+        // DMA i (0..3) of a plane's 16 rows: ring rows 4i .. 4i+3 <- the four rows of the k-step's list entry i, a raw buffer of its own;
+        // lane L: row L>>4 of the group, LDS chunk position L&15 <- global chunk jg = (L&15) ^ swz(ring row), swz = ((L>>4)<<2) | (i&3)
         int soff[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int jg = (lane & 15) ^ (((lane >> 4) << 2) | (i & 3));
             // interleaved planes (G): chunk jg of the plane is 16 bytes at 128*(jg>>2) + 16*(jg&3)
             const int cb = is_g ? 128 * (jg >> 2) + 16 * (jg & 3) : 16 * jg;
-            soff[i] = dead_tile ? 0x7ffffff0 : (int)((4 * i + (lane >> 4)) * rstride) + cb;
-#if XF2_IMM  // the four pieces of a plane share one LDS base (M0): piece i carries the immediate offset 1024 i, which advances the memory
-            // address too — taken back out of its per-lane offset (rstride >= 256 bytes: 4 i rows >= 1024 i bytes, never negative)
-            if (NW == 4 && !dead_tile) soff[i] -= 1024 * i;
-#endif
+            soff[i] = dead_tile ? 0x7ffffff0 : (int)((lane >> 4) * rstride) + cb;
         }
+        // XF2_IMM: the four pieces of a plane share one LDS base (M0); piece i carries the immediate offset 1024 i, which advances the memory
+        // address too and counts in the range check.  It is taken back out of the piece's buffer BASE and added to its range (the per-lane
+        // offset of the group's row 0 is below 1024 i: subtracting there would wrap, and the range check would hand back zeros)
+        constexpr bool IMM = XF2_IMM && NW == 4;
+        const unsigned gbytes = (unsigned)(4 * rstride);  // one group of one plane (rstride < 2^29: x2_dhidden_ok / x2_linear_ok)
         const bool live_n = !PARTH || hb * 256 + wn * 32 * QN < H;  // this wave's h columns exist (wave-uniform)
-        // The walk: ONE pipeline run over the split's list entries — k-step ks multiplies the 16 cells of k-step list[g_lo + ks] of the
-        // [cells] buffers.  An entry is fetched by a scalar load (wave-uniform, outside the counted vector-memory stream; it only feeds
-        // the buffer resources' base) that is waited for in the same asm statement, so no register copy made before the data arrived
-        // can be what the address is built from; inside the k loop it is issued in front of the counted vmcnt wait it shares its
-        // latency with.  Past the split's end the read-ahead fetches the next split's entries (real rows, never multiplied) or the
-        // list's padding entries (zero rows).
-        const int *lptr = a.ks_list + g_lo;
+        // The walk: ONE pipeline run over the split's list entries — k-step ks multiplies the 16 cells of the four groups
+        // list[4 (g_lo + ks)] .. + 3 of the [cells] buffers.  The four entries are fetched by ONE 16-byte scalar load (the list is 16-byte
+        // aligned; wave-uniform, outside the counted vector-memory stream; they only feed the buffer resources' bases) that is waited
+        // for in the same asm statement, so no register copy made before the data arrived can be what an address is built from; inside
+        // the k loop it is issued in front of the counted vmcnt wait it shares its latency with.  Past the split's end the read-ahead
+        // fetches the next split's entries (real rows, never multiplied) or the list's padding entries (zero rows).
+        const int *lptr = a.grp_list + 4L * g_lo;
         // ---- transposed fragment reads.  Fragment of 32-column tile m: lane (g = lane>>4, q = (lane&15)>>2,
         // p = lane&3) reads rows 8(g>>1) + 4sec + q at chunk 4m + 2(g&1) + (p>>1), +8(p&1) bytes, sec = 0,1.
         const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3, hh = g >> 1;
@@ -618,32 +675,24 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
         auto kstep = [&](auto st_c, long ks, f32x16 &dacc) {
             constexpr int ST = decltype(st_c)::value, DST = (ST + XW2_NST - 1) % XW2_NST;
             // stage ks landed (the 8 (NST - 2) younger pieces of the stages after it may still fly); every wave is past its reads of
-            // stage ks-1, whose ring stage the DMAs below refill.  In front of the wait: the list entry of stage ks + NST - 1
-            int ent;
-            const int *ep = lptr + ks + (XW2_NST - 1);
-            if (ND * (XW2_NST - 2) == 16) asm volatile("s_load_dword %0, %1, 0x0\n\t" RNNT_VMCNT(16) "\n\ts_waitcnt lgkmcnt(0)" : "=s"(ent) : "s"(ep) : "memory");
-            else if (ND * (XW2_NST - 2) == 8) asm volatile("s_load_dword %0, %1, 0x0\n\t" RNNT_VMCNT(8) "\n\ts_waitcnt lgkmcnt(0)" : "=s"(ent) : "s"(ep) : "memory");
-            else asm volatile("s_load_dword %0, %1, 0x0\n\t" RNNT_VMCNT(4) "\n\ts_waitcnt lgkmcnt(0)" : "=s"(ent) : "s"(ep) : "memory");
-            // its 16 rows as two raw buffers (wave-uniform base; the per-lane part is the 32-bit soff)
-            __amdgpu_buffer_rsrc_t rs[2];
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-                rs[p] = __builtin_amdgcn_make_buffer_rsrc((void *)(pbase[p] + ((long)ent * XW2_ROWS) * rstride), 0,
-                                                          (int)(XW2_ROWS * rstride), 0x00020000);
-            auto dma_piece = [&](auto n_c) {  // piece n of this wave's share of stage ks+NST-1 -> ring stage DST: plane n>>2 (8 waves: wave & 1), rows 4(n&3)..
+            // stage ks-1, whose ring stage the DMAs below refill.  In front of the wait: the four list entries of stage ks + NST - 1
+            i32x4 ent;
+            const int *ep = lptr + 4 * (ks + (XW2_NST - 1));
+            if (ND * (XW2_NST - 2) == 16) XW2_LOAD_ENT4(ent, ep, RNNT_VMCNT(16) "\n\t");
+            else if (ND * (XW2_NST - 2) == 8) XW2_LOAD_ENT4(ent, ep, RNNT_VMCNT(8) "\n\t");
+            else XW2_LOAD_ENT4(ent, ep, RNNT_VMCNT(4) "\n\t");
+            // piece n of this wave's share of stage ks+NST-1 -> ring stage DST: plane n>>2 (8 waves: wave & 1), ring rows 4(n&3).. <- the
+            // four rows of entry n&3 as a raw buffer (wave-uniform base, built here between the MFMAs; the per-lane part is the 32-bit soff)
+            auto dma_piece = [&](auto n_c) {
                 constexpr int n = decltype(n_c)::value, i = n & 3;
                 if (NW == 8) {
-                    if (wave & 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[1], (lds_vptr)(s_ring + otile * XW2_TILE + DST * XW2_STAGE + XW2_PLANE + 1024 * i), 16, soff[i], 0, 0, 0);
-                    else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[0], (lds_vptr)(s_ring + otile * XW2_TILE + DST * XW2_STAGE + 1024 * i), 16, soff[i], 0, 0, 0);
+                    if (wave & 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(x2_piece_rsrc(pbase[1], ent[i], gbytes, 0), (lds_vptr)(s_ring + otile * XW2_TILE + DST * XW2_STAGE + XW2_PLANE + 1024 * i), 16, soff[i], 0, 0, 0);
+                    else __builtin_amdgcn_raw_ptr_buffer_load_lds(x2_piece_rsrc(pbase[0], ent[i], gbytes, 0), (lds_vptr)(s_ring + otile * XW2_TILE + DST * XW2_STAGE + 1024 * i), 16, soff[i], 0, 0, 0);
                 } else {
-                    constexpr int p = (n >> 2) & 1;
-#if XF2_IMM
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[p], (lds_vptr)(s_ring + otile * XW2_TILE + DST * XW2_STAGE + p * XW2_PLANE),
-                                                             16, soff[i], 0, 1024 * i, (X2_NT & 2) ? 2 : 0);
-#else
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[p], (lds_vptr)(s_ring + otile * XW2_TILE + DST * XW2_STAGE + p * XW2_PLANE + 1024 * i),
-                                                             16, soff[i], 0, 0, (X2_NT & 2) ? 2 : 0);  // (experiment 2: aux = 2, non-temporal)
-#endif
+                    constexpr int p = (n >> 2) & 1, imm = IMM ? 1024 * i : 0;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(x2_piece_rsrc(pbase[p], ent[i], gbytes, imm),
+                                                             (lds_vptr)(s_ring + otile * XW2_TILE + DST * XW2_STAGE + p * XW2_PLANE + 1024 * i - imm),
+                                                             16, soff[i], 0, imm, (X2_NT & 2) ? 2 : 0);  // (experiment 2: aux = 2, non-temporal)
                 }
             };
             // 8 transposed reads of plane P of the A / B operand (inline asm: hipcc guards every LDS read it can see behind
@@ -716,22 +765,19 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
             }
         };
         auto dma_stage = [&](long ks, int st) {  // pipeline prologue: this wave's pieces of stage ks
-            int ent;
-            const int *ep = lptr + ks;
-            asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ent) : "s"(ep) : "memory");
+            i32x4 ent;
+            const int *ep = lptr + 4 * ks;
+            XW2_LOAD_ENT4(ent, ep, "");
 #pragma unroll
             for (int n = 0; n < ND; ++n) {
                 const int p = NW == 8 ? (wave & 1) : n >> 2, i = n & 3;
-                const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
-                    (void *)(pbase[p] + ((long)ent * XW2_ROWS) * rstride), 0, (int)(XW2_ROWS * rstride), 0x00020000);
-#if XF2_IMM
-                if (NW == 4) {
+                const __amdgpu_buffer_rsrc_t r = x2_piece_rsrc(pbase[p], ent[i], gbytes, IMM ? 1024 * i : 0);
+                if (IMM) {
                     if (i == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_vptr)(s_ring + otile * XW2_TILE + st * XW2_STAGE + p * XW2_PLANE), 16, soff[i], 0, 0, 0);
                     if (i == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_vptr)(s_ring + otile * XW2_TILE + st * XW2_STAGE + p * XW2_PLANE), 16, soff[i], 0, 1024, 0);
                     if (i == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_vptr)(s_ring + otile * XW2_TILE + st * XW2_STAGE + p * XW2_PLANE), 16, soff[i], 0, 2048, 0);
                     if (i == 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_vptr)(s_ring + otile * XW2_TILE + st * XW2_STAGE + p * XW2_PLANE), 16, soff[i], 0, 3072, 0);
                 } else
-#endif
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_vptr)(s_ring + otile * XW2_TILE + st * XW2_STAGE + p * XW2_PLANE + 1024 * i),
                                                          16, soff[i], 0, 0, 0);
             }
@@ -1123,6 +1169,16 @@ bool x2_dw_walks_table(int H, int V, int flags)
     if (flags & RNNT_VARIANT_X2_DW_P16) return true;
 #endif
     return false;
+}
+
+// the dW kernel launch_dw_x2 picks for this call walks the 16-cell k-step list (k_dw_x2m), not the group list: k_x2_dead_rows walks it too
+bool x2_dw_walks_ksteps(int H, int V, int flags)
+{
+    (void)flags;
+#ifdef RNNT_LAB
+    if (flags & (RNNT_VARIANT_X2_DW_P16 | RNNT_VARIANT_X2_DW_8W)) return false;
+#endif
+    return x2_dw_mixed_ok(H, V) != 0;
 }
 
 void launch_dw_x2(const X3Args &a, hipStream_t st, bool build_table, bool zero_prog)
@@ -1768,13 +1824,15 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2r(X3Args a, const int hp)
 }
 
 // ---------------------------------------------------------------------------------------
-// k_x2_dead_rows: the zeros the dW GEMM must find.  k_dw_x2 reads all 16 rows of every LIVE k-step (X3Args::ks_list); the rows that belong
+// k_x2_dead_rows: the zeros the dW GEMM must find.  k_dw_x2 reads all four rows of every LIVE group (X3Args::grp_list); the rows that belong
 // to a live dHidden tile are written by k_dhidden_x2 (G, or zeros for cells outside the lattice), the rows of tiles that are not live —
-// a k-step straddles tile edges: 16 consecutive cells of a (b, t) line against 16-aligned u blocks — still hold logits.  One wave per four
-// live k-steps (grid-stride over the list): lane l looks up the tile flag of cell l & 15 of k-step l >> 4, then the whole wave zeroes each
-// flagged row, both planes = the V x 4 bytes of the logits row, 16 bytes per lane and store.  Most k-steps have no such row and cost two
-// loads.  No LDS, 4 waves per workgroup: it runs beside anything.  zero_all (the lab's table-walking dW kernel reads every row): every k-step that has a cell.
-// Rows of dead tiles and rows of live tiles are disjoint: the order against k_dhidden_x2 is free; both precede k_dw_x2.
+// a group straddles tile edges: 4 consecutive cells of the linear cell order against 16-aligned u blocks of a (b, t) line — still hold logits.
+// One lane per row, so a wave round covers 16 list entries (grid-stride over the list): lane l looks up the tile flag of cell l & 3 of entry
+// l >> 2, then the whole wave zeroes each flagged row, both planes = the V x 4 bytes of the logits row, 16 bytes per lane and store.  Most
+// rounds have no such row and cost two loads.  No LDS, 4 waves per workgroup: it runs beside anything.
+// X3Args::dw_ksteps (the call's dW kernel is k_dw_x2m, which reads all 16 rows of every live k-step): the same walk over ks_list, 4 entries
+// of 16 rows per round.  zero_all (the lab's table-walking dW kernel reads every row): every group that has a cell.
+// Rows of dead tiles and rows of live tiles are disjoint: the order against k_dhidden_x2 is free; both precede the dW kernel.
 // ---------------------------------------------------------------------------------------
 #define XZ2_WG_WAVES 4
 __global__ __launch_bounds__(64 * XZ2_WG_WAVES) void k_x2_dead_rows(X3Args a, int ntt, int nub)
@@ -1782,16 +1840,19 @@ __global__ __launch_bounds__(64 * XZ2_WG_WAVES) void k_x2_dead_rows(X3Args a, in
     const int lane = threadIdx.x & 63;
     const long wave = (long)blockIdx.x * XZ2_WG_WAVES + (threadIdx.x >> 6), nwave = (long)gridDim.x * XZ2_WG_WAVES;
     const long cells = (long)a.B * a.T * a.U1;
-    const long n = a.zero_all ? a.live_stats[1] : a.live_stats[0];
+    const bool by_ks = a.dw_ksteps && !a.zero_all;  // (kernel-uniform)
+    const int sh = by_ks ? 4 : 2, per = 64 >> sh;   // rows per list entry = 1 << sh; entries per wave round
+    const int *list = by_ks ? a.ks_list : a.grp_list;
+    const long n = a.zero_all ? a.live_stats[5] : a.live_stats[by_ks ? 0 : 4];
     const int V4 = a.V / 4;
     const u32x4 z = {0u, 0u, 0u, 0u};
-    for (long k = 4 * wave; k < n; k += 4 * nwave) {
-        const long kk = k + (lane >> 4);
-        int ks = 0;  // (a k-step index fits an int: ks_list's entries do)
+    for (long k = per * wave; k < n; k += per * nwave) {
+        const long kk = k + (lane >> sh);
+        int e = 0;  // (an entry fits an int: the lists' entries do)
         bool dead = false;
         if (kk < n) {
-            ks = a.zero_all ? (int)kk : a.ks_list[kk];
-            const long c = (long)ks * XW2_ROWS_ + (lane & 15);
+            e = a.zero_all ? (int)kk : list[kk];
+            const long c = ((long)e << sh) + (lane & ((1 << sh) - 1));
             if (c < cells) {
                 const int u = (int)(c % a.U1);
                 const long bt = c / a.U1;
@@ -1800,18 +1861,18 @@ __global__ __launch_bounds__(64 * XZ2_WG_WAVES) void k_x2_dead_rows(X3Args a, in
                 dead = a.tile_live[(b * ntt + t / XG2_BT_) * nub + u / XG2_BU_] == 0;
             }
         }
-        unsigned long long m = __ballot(dead);  // (wave-uniform) bit l: row 16 ks(l >> 4) + (l & 15) belongs to a tile that is not live
+        unsigned long long m = __ballot(dead);  // (wave-uniform) bit l: row (l & (1 << sh) - 1) of entry l >> sh belongs to a tile that is not live
         for (; m; m &= m - 1) {
             const int r = __builtin_ctzll(m);
-            u32x4 *row = (u32x4 *)(a.logits + ((long)__shfl(ks, r, 64) * XW2_ROWS_ + (r & 15)) * a.V);
+            u32x4 *row = (u32x4 *)(a.logits + (((long)__shfl(e, r, 64) << sh) + (r & ((1 << sh) - 1))) * a.V);
             for (int q = lane; q < V4; q += 64) row[q] = z;
         }
     }
 }
 void launch_x2_dead_rows(const X3Args &a, hipStream_t st)
 {
-    const long nks = ((long)a.B * a.T * a.U1 + XW2_ROWS_ - 1) / XW2_ROWS_;  // k-steps with a cell: the most the walk can hold
-    const long want = (nks + 4 * XZ2_WG_WAVES - 1) / (4 * XZ2_WG_WAVES), cap = (long)(a.n_cu > 0 ? a.n_cu : 256) * 8;
+    const long rounds = ((long)a.B * a.T * a.U1 + 63) / 64;  // wave rounds of 64 rows: the most the walk can hold
+    const long want = (rounds + XZ2_WG_WAVES - 1) / XZ2_WG_WAVES, cap = (long)(a.n_cu > 0 ? a.n_cu : 256) * 8;
     const int ntt = (a.T + XG2_BT_ - 1) / XG2_BT_;
     hipLaunchKernelGGL(k_x2_dead_rows, dim3((unsigned)(want < cap ? want : cap)), dim3(64 * XZ2_WG_WAVES), 0, st, a, ntt, a.n_ublk16);
 }
@@ -2518,7 +2579,7 @@ __global__ __launch_bounds__(256) void k_x2_absmax(X2AbsArgs a, float *__restric
 // (k_dw_table's format, B = 1, every granule live) — what four more launches did before
 __global__ __launch_bounds__(256) void k_x2_lin_scales(const float *__restrict__ partial, float *__restrict__ scales, int n, unsigned *__restrict__ zero0,
                                                        int nzero0, unsigned *__restrict__ zero1, int nzero1, long *__restrict__ tab, long ngran,
-                                                       int *__restrict__ list, int *__restrict__ stats)
+                                                       int *__restrict__ list, int *__restrict__ stats, int *__restrict__ glist)
 {
     __shared__ float s_m[4];
     for (int i = 0; i < n; ++i) {
@@ -2548,10 +2609,11 @@ __global__ __launch_bounds__(256) void k_x2_lin_scales(const float *__restrict__
     for (int j = threadIdx.x; j < nzero0; j += 256) zero0[j] = 0u;
     for (int j = threadIdx.x; j < nzero1; j += 256) zero1[j] = 0u;
     if (tab && threadIdx.x == 0) { tab[0] = 0; tab[1] = ngran; tab[2] = 0; tab[3] = ngran; }
-    if (list) {  // k_dw_x2's live k-step list: every 16-row k-step, then the padding entries (launch_x2_live's format)
-        const long nks = 2 * ngran;
+    if (list) {  // the dW kernels' lists (launch_x2_live's format): every 16-row k-step (k_dw_x2m) and every 4-row group (k_dw_x2), then the padding entries
+        const long nks = 2 * ngran, ngrp = 8 * ngran;
         for (long j = threadIdx.x; j < nks + 8; j += 256) list[j] = (int)(j < nks ? j : nks);
-        if (threadIdx.x == 0) { stats[0] = (int)nks; stats[1] = (int)nks; stats[2] = 0; stats[3] = 0; }
+        for (long j = threadIdx.x; j < ngrp + XL2_GPAD; j += 256) glist[j] = (int)(j < ngrp ? j : ngrp);
+        if (threadIdx.x == 0) { stats[0] = (int)nks; stats[1] = (int)nks; stats[2] = 0; stats[3] = 0; stats[4] = (int)ngrp; stats[5] = (int)ngrp; }
     }
 }
 // rows of a row-major fp32 matrix -> s x as two fp16 planes.  INTER: the planes interleaved per 32-column chunk, [32 x hi | 32 x mid] over the
@@ -2611,7 +2673,7 @@ __global__ __launch_bounds__(256) void k_x2_reduce_scaled(const float *__restric
 }
 
 namespace {
-struct LinWs { size_t wt, pack, pa, pb, slab_w, slab_b, prog, list, total; long rows_pad, rows_alloc; int n_split; };
+struct LinWs { size_t wt, pack, pa, pb, slab_w, slab_b, prog, list, glist, total; long rows_pad, rows_alloc; int n_split; };
 LinWs lin_layout(int M, int K, int N, bool bwd)
 {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -2632,7 +2694,8 @@ LinWs lin_layout(int M, int K, int N, bool bwd)
     L.slab_w = o; o += al((size_t)L.n_split * N * K * 4);
     L.slab_b = o; o += al((size_t)L.n_split * N * 4);
     L.prog = o; o += al((size_t)L.n_split * 64);
-    L.list = o; o += al(64 + (size_t)(L.rows_pad / XW2_ROWS + 8) * 4);  // 4 count words, then the k-step list
+    L.list = o; o += al(64 + (size_t)(L.rows_pad / XW2_ROWS + 8) * 4);  // the count words, then the k-step list
+    L.glist = o; o += al((size_t)(L.rows_pad / 4 + XL2_GPAD) * 4);        // the group list
     L.total = o;
     return L;
 }
@@ -2650,14 +2713,14 @@ int lin_cus()
 }
 // the operand scales of a call: one launch for the maxima of its n tensors, one for the scales (+ the counter words and dW's table)
 struct LinT { const float *x; long ld, rows; int cols; };
-void lin_scales(const LinT *t, int n, char *w, unsigned *zero1, int nzero1, long *tab, long ngran, int *list, hipStream_t st)
+void lin_scales(const LinT *t, int n, char *w, unsigned *zero1, int nzero1, long *tab, long ngran, int *list, int *glist, hipStream_t st)
 {
     X2AbsArgs a{};
     for (int i = 0; i < n; ++i) { a.x[i] = t[i].x; a.ld[i] = t[i].ld; a.rows[i] = t[i].rows; a.cols4[i] = t[i].cols / 4; }
     float *partial = (float *)(w + 1024);
     hipLaunchKernelGGL(k_x2_absmax, dim3(256, n), dim3(256), 0, st, a, partial);
     hipLaunchKernelGGL(k_x2_lin_scales, dim3(1), dim3(256), 0, st, partial, (float *)w, n, (unsigned *)(w + 128), 16, zero1, nzero1, tab, ngran,
-                       list ? list + 16 : nullptr, list);
+                       list ? list + 16 : nullptr, list, glist);
 }
 // y[M,N] = x[M,K] wmat[N,K]^T (+ bias) through k_joint_fwd_x2<2>; scales = {s_W, 1/s_W, s_X, 1/s_X} on the device, the pack made here
 void lin_gemm_nt(const float *x, long ldx, const float *wmat, const float *bias, int M, int K, int N, float *y, const float *scales, void *pack,
@@ -2682,7 +2745,7 @@ void launch_linear_x2_fwd(const float *x, long ldx, const float *W, const float 
     char *w = (char *)ws;
     float *scales = (float *)w;
     const LinT t[2] = {{W, K, N, K}, {x, ldx, M, K}};
-    lin_scales(t, 2, w, nullptr, 0, nullptr, 0, nullptr, st);
+    lin_scales(t, 2, w, nullptr, 0, nullptr, 0, nullptr, nullptr, st);
     lin_gemm_nt(x, ldx, W, bias, M, K, N, y, scales, w + L.pack, (unsigned *)(w + 128), st);
 }
 
@@ -2694,7 +2757,7 @@ void launch_linear_x2_bwd(const float *x, long ldx, const float *W, const float 
     float *scales = (float *)w;             // {s_W, 1/s_W, s_dy, 1/s_dy, s_x, 1/s_x}
     long *tab = (long *)(w + 192);
     const LinT t[3] = {{W, K, N, K}, {dy, N, M, N}, {x, ldx, M, K}};
-    lin_scales(t, 3, w, (unsigned *)(w + L.prog), L.n_split * 16, tab, L.rows_pad / XW2_GRAN, (int *)(w + L.list), st);
+    lin_scales(t, 3, w, (unsigned *)(w + L.prog), L.n_split * 16, tab, L.rows_pad / XW2_GRAN, (int *)(w + L.list), (int *)(w + L.glist), st);
     if (dx) {  // dx[M,K] = dy[M,N] (W^T)[K,N]^T
         float *wt = (float *)(w + L.wt);
         launch_copy_enc(W, 0, 1, K, wt, 1, K, N, st);  // wt[k][n] = W[n][k]
@@ -2714,7 +2777,7 @@ void launch_linear_x2_bwd(const float *x, long ldx, const float *W, const float 
     a.logits = pa; a.hidden = pb; a.plane_stride = L.rows_alloc * (long)K; a.rows_pad = L.rows_pad; a.rows_alloc = L.rows_alloc;
     a.B = 1; a.T = 1; a.U1 = 1; a.H = K; a.V = N; a.n_split = L.n_split; a.dw_tab = tab; a.dw_prog = (int *)(w + L.prog);
     a.slab_w = (float *)(w + L.slab_w); a.slab_b = (float *)(w + L.slab_b); a.dw_rescale = 1.0f; a.db_rescale = 1.0f; a.n_cu = lin_cus();
-    a.live_stats = (int *)(w + L.list); a.ks_list = a.live_stats + 16;
+    a.live_stats = (int *)(w + L.list); a.ks_list = a.live_stats + 16; a.grp_list = (int *)(w + L.glist);
     launch_dw_x2(a, st, false, false);  // (no table / list kernels, no progress-word fill: all done by k_x2_lin_scales)
     const long n4w = (long)N * K / 4, n4b = N / 4;
     hipLaunchKernelGGL(k_x2_reduce_scaled, dim3((unsigned)((n4w + 255) / 256)), dim3(256), 0, st, a.slab_w, dW, n4w, n4w, L.n_split,

@@ -322,6 +322,15 @@ def x2_live_counts(device, B, T, U1, H, V):
     return dict(live_ksteps=c[0], ksteps=c[1], live_tiles=c[2], tiles=c[3])
 
 
+def x2_live_group_counts(device, B, T, U1, H, V):
+    """Beside x2_live_counts, the 4-cell groups (linear cell index // 4) of the dW GEMM's walk: dict(live_groups, groups) — the
+    groups the last f16x2 fused call of these dims listed of those that hold a cell (four list entries make a k-step).  Synchronises."""
+    L = layout(B, T, U1, H, V, "f16x2")
+    ws = workspace(device, L.total)
+    c = ws[L.x2_live + 16:L.x2_live + 24].view(torch.int32).cpu().tolist()
+    return dict(live_groups=c[0], groups=c[1])
+
+
 def workspace_bytes(B, T, U1, H, V, dtype="fp32"):
     n = ctypes.c_size_t(0)
     _check(lib().rnnt_engine_workspace_bytes(B, T, U1, H, V, dtype_code(dtype), ctypes.byref(n)))
