@@ -98,8 +98,8 @@ void rnnt_engine_set_debug(void *buf);
  * k-steps at other cells).  The regularised entry (rnnt_engine_joint_loss_fwd_bwd_reg) always runs as if the bit were set:
  * the bound is not extended to FastEmit's / the delay penalty's coefficients. */
 #define RNNT_VARIANT_X2_NO_FLUSH_SKIP 512
-/* Bits 14 and up name kernels of the DIAGNOSTIC library only (rnnt_amd/csrc/lab/rnnt_engine_lab.h, tools/build_lab.sh):
- * librnnt_engine.so answers them with RNNT_ERR_UNSUPPORTED. */
+/* Bits 14 and up are reserved (they once named experimental kernels that have left the tree): every entry point that takes a
+ * variant answers any of them with RNNT_ERR_UNSUPPORTED before it launches anything. */
 #define RNNT_VARIANT_LAB_MASK 0x7fffc000
 
 /* Diagnostic queries (0/1: predicted resident forward-kernel workgroups per CU). */

@@ -30,7 +30,7 @@
 // fragments are consumed, so staging a chunk is a linear copy L2 -> VGPR -> LDS.
 #include "kernels.hpp"
 
-// Diagnostic build only (-DBF_CLOCK, with an engine.o built -DRNNT_STAMPS so that Bf16Args::debug is set; tools/bf16_whatif.sh): workgroup
+// Diagnostic build only (-DBF_CLOCK, with an engine.o built -DRNNT_STAMPS so that Bf16Args::debug is set): workgroup
 // (0,0,0) stamps the core clock counter and the 100 MHz reference at its start and end into debug[SLOT .. SLOT+3] (a buffer nothing
 // else reads): the clock the launch ran at = d(s_memtime) / d(s_memrealtime) x 100 MHz (tools/exp_bf16_clock.py).
 #ifdef BF_CLOCK
@@ -451,13 +451,6 @@ __global__ __launch_bounds__(256, 2) void k_joint_fwd_bf16(Bf16Args a)
 // Requires V % 128 == 0.  Same rounding points as the kernel above (bf16 operands, fp32 accumulation, fp16 logits,
 // statistics from the stored values); the k order inside an accumulator differs.
 // ---------------------------------------------------------------------------------------
-// Diagnostic builds only (-DFR_EXP=bits, tools/build_bf16_variants.sh): parts of k_joint_fwd_bf16_ra compiled out —
-// 1 no MFMAs, 2 no statistics, 4 no logits stores, 8 no hidden stores, 16 no W DMA, 32 no tanh,
-// 64 one workgroup per CU (100 KiB of LDS requested), 128 every W fragment feeds two MFMAs and half of W's DMA pieces are issued
-#ifndef FR_EXP
-#define FR_EXP 0
-#endif
-#define FR_OFF(bit) ((FR_EXP) & (bit))
 #ifdef RNNT_STAMPS
 // Diagnostic build only (-DRNNT_STAMPS): s_memtime stamps of workgroup FRS_BLOCK, every wave: debug[wave*128 + slot]
 #ifndef FRS_BLOCK
@@ -533,7 +526,6 @@ __global__ __launch_bounds__(256, (KC <= 8 ? 2 : 1)) void k_joint_fwd_bf16_ra(Bf
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(a.wpack_fwd, 0, (int)((long)V * H * 2), 0x00020000);
     const int wvo = wave * 4096 + lane * 16;
     auto wdma = [&](int n, int q) {
-        if (FR_OFF(16)) return;
         const int src = n < NC ? n : NC - 1;  // past the end: the last chunk again (landed, never read)
         // (round 5: the four pieces of a chunk on ONE LDS base (M0) and ONE scalar offset — the instruction's 12-bit immediate offset
         // advances the memory and the LDS address alike; an M0 write in front of every LDS-DMA cost the f16x2 forward 0.6 ms of 21.7)
@@ -602,11 +594,11 @@ __global__ __launch_bounds__(256, (KC <= 8 ? 2 : 1)) void k_joint_fwd_bf16_ra(Bf
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int i = i0 + k;
-                const f32x4 tv = FR_OFF(32) ? b[k] + b[4 + k] : fast_tanh_sum4(b[k], b[4 + k]);
+                const f32x4 tv = fast_tanh_sum4(b[k], b[4 + k]);
                 const u32x2 o = {pack_bf16(tv[0], tv[1]), pack_bf16(tv[2], tv[3])};
                 const int row = 4 * i + sub;
                 const int r = row < rmax ? row : rmax;
-                if (!FR_OFF(8)) *(u32x2 *)(hbase + (unsigned)(r * H) + 64 * c) = o;
+                *(u32x2 *)(hbase + (unsigned)(r * H) + 64 * c) = o;
                 const int wa = tbase + row * 128 + (((kq >> 1) ^ ((row >> 1) & 7)) << 4) + 8 * (kq & 1);
                 asm volatile("ds_write_b64 %0, %1" :: "v"(wa), "v"(o) : "memory");
             }
@@ -643,25 +635,14 @@ __global__ __launch_bounds__(256, (KC <= 8 ? 2 : 1)) void k_joint_fwd_bf16_ra(Bf
     // 4 MFMAs: W fragments g (A operand: 32 vocabulary rows each) x this wave's cells (B operand, registers)
     auto mma4 = [&](auto first_c, const u32x4 &hf, const u32x4 (&g)[4], int n, int q) {
         constexpr bool FIRST = decltype(first_c)::value != 0;  // first k-step of a pass: C = 0
-        if (!FR_OFF(1)) {
-            const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            acc[0] = mfma_bf16(g[0], hf, FIRST ? z : acc[0]);
-            acc[1] = mfma_bf16(g[1], hf, FIRST ? z : acc[1]);
-        }
+        const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        acc[0] = mfma_bf16(g[0], hf, FIRST ? z : acc[0]);
+        acc[1] = mfma_bf16(g[1], hf, FIRST ? z : acc[1]);
         wdma(n + 3, q);
-        if (!FR_OFF(1)) {
-            const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            acc[2] = mfma_bf16(g[2], hf, FIRST ? z : acc[2]);
-            acc[3] = mfma_bf16(g[3], hf, FIRST ? z : acc[3]);
-        }
+        acc[2] = mfma_bf16(g[2], hf, FIRST ? z : acc[2]);
+        acc[3] = mfma_bf16(g[3], hf, FIRST ? z : acc[3]);
         __builtin_amdgcn_sched_barrier(0);
     };
-    if (FR_OFF(1)) {
-#pragma unroll
-        for (int tl = 0; tl < 4; ++tl)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[tl][r] = 0.f;
-    }
 
     // chunks 0..2 have landed (the production consumed loads issued after their DMAs; stores may still fly)
     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(8 * KC < 63 ? 8 * KC : 63) : "memory");
@@ -681,23 +662,13 @@ __global__ __launch_bounds__(256, (KC <= 8 ? 2 : 1)) void k_joint_fwd_bf16_ra(Bf
             // this wave's share of chunk n+1 has landed.  vmcnt retires in order; younger than those DMAs are the 4
             // of chunk n+2 and, in the first two chunks of a pass, the 8 logits stores + the bias load of the epilogue
             // (the first pass's chunks 1 and 2 landed before the loop: no wait behind the hidden stores)
-            if (FR_OFF(128)) { if (c < 2) { if (pass != 0) asm volatile(RNNT_VMCNT(10) ::: "memory"); } else asm volatile(RNNT_VMCNT(2) ::: "memory"); }
-            else if (c < 2) { if (pass != 0) asm volatile(RNNT_VMCNT(12) ::: "memory"); }
+            if (c < 2) { if (pass != 0) asm volatile(RNNT_VMCNT(12) ::: "memory"); }
             else asm volatile(RNNT_VMCNT(4) ::: "memory");
             if (pass == 3) FRSTAMP(64 + 3 * c);
             lds_barrier();  // publishes chunk n+1; every wave is past its reads of chunk n-1 (slot of chunk n+3)
             if (pass == 3) FRSTAMP(65 + 3 * c);
             landed(g0, false);
             const int sb = rb + ((n & 3) << 14), sbn = rb + (((n + 1) & 3) << 14);
-            if (FR_OFF(128)) {  // what-if (wrong results): every W fragment feeds TWO MFMAs and half of W's bytes move — the price list of a 256-cell tile
-                mma4(BInt<(c == 0)>{}, A[c][0], g0, n, 0);
-                reads(g1, sb, BInt<2>{});
-                mma4(BInt<0>{}, A[c][1], g0, n, 5);
-                landed(g1, true);
-                mma4(BInt<0>{}, A[c][2], g1, n, 2);
-                reads(g0, sbn, BInt<0>{});
-                mma4(BInt<0>{}, A[c][3], g1, n, 5);
-            } else {
             reads(g1, sb, BInt<1>{});
             mma4(BInt<(c == 0)>{}, A[c][0], g0, n, 0);
             landed(g1, true);
@@ -709,7 +680,6 @@ __global__ __launch_bounds__(256, (KC <= 8 ? 2 : 1)) void k_joint_fwd_bf16_ra(Bf
             landed(g1, true);
             reads(g0, sbn, BInt<0>{});  // first group of chunk n+1 (published above; past the end: an unused landed slot)
             mma4(BInt<0>{}, A[c][3], g1, n, 3);
-            }
             if (pass == 3) FRSTAMP(66 + 3 * c);
         };
         if constexpr (KC >= 1) chunk(BInt<0>{});
@@ -760,31 +730,28 @@ __global__ __launch_bounds__(256, (KC <= 8 ? 2 : 1)) void k_joint_fwd_bf16_ra(Bf
                     const unsigned lo = pack_f16(x0 + bq[t][0], x1 + bq[t][1]), hi = pack_f16(x2 + bq[t][2], x3 + bq[t][3]);
                     if (t < 2) { q0[2 * t] = lo; q0[2 * t + 1] = hi; } else { q1[2 * (t - 2)] = lo; q1[2 * (t - 2) + 1] = hi; }
                 }
-                if (!FR_OFF(4)) asm volatile("ds_write_b128 %0, %2\n\tds_write_b128 %1, %3" :: "v"(stw0), "v"(stw1), "v"(q0), "v"(q1) : "memory");
-                if (!FR_OFF(2)) {
-                    const unsigned m4 = pk_max_f16(pk_max_f16(pk_max_f16(q0[0], q0[1]), pk_max_f16(q0[2], q0[3])),
-                                                   pk_max_f16(pk_max_f16(q1[0], q1[1]), pk_max_f16(q1[2], q1[3])));
-                    const float lmax = f16_lo(max_halves_f16(m4));
-                    float mn;
-                    asm("v_max_f32 %0, %1, %2" : "=v"(mn) : "v"(st_m), "v"(lmax));
-                    const float nm2 = -mn * RNNT_LOG2E;
-                    float e = st_s * __builtin_amdgcn_exp2f(fmaf(st_m, RNNT_LOG2E, nm2));
-                    float e2 = 0.f;
+                asm volatile("ds_write_b128 %0, %2\n\tds_write_b128 %1, %3" :: "v"(stw0), "v"(stw1), "v"(q0), "v"(q1) : "memory");
+                const unsigned m4 = pk_max_f16(pk_max_f16(pk_max_f16(q0[0], q0[1]), pk_max_f16(q0[2], q0[3])),
+                                               pk_max_f16(pk_max_f16(q1[0], q1[1]), pk_max_f16(q1[2], q1[3])));
+                const float lmax = f16_lo(max_halves_f16(m4));
+                float mn;
+                asm("v_max_f32 %0, %1, %2" : "=v"(mn) : "v"(st_m), "v"(lmax));
+                const float nm2 = -mn * RNNT_LOG2E;
+                float e = st_s * __builtin_amdgcn_exp2f(fmaf(st_m, RNNT_LOG2E, nm2));
+                float e2 = 0.f;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        e += __builtin_amdgcn_exp2f(fmaf(f16_lo(q0[k]), RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(f16_hi(q0[k]), RNNT_LOG2E, nm2));
-                        e2 += __builtin_amdgcn_exp2f(fmaf(f16_lo(q1[k]), RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(f16_hi(q1[k]), RNNT_LOG2E, nm2));
-                    }
-                    st_s = e + e2;
-                    st_m = mn;
+                for (int k = 0; k < 4; ++k) {
+                    e += __builtin_amdgcn_exp2f(fmaf(f16_lo(q0[k]), RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(f16_hi(q0[k]), RNNT_LOG2E, nm2));
+                    e2 += __builtin_amdgcn_exp2f(fmaf(f16_lo(q1[k]), RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(f16_hi(q1[k]), RNNT_LOG2E, nm2));
                 }
-                if (!FR_OFF(4)) {  // the staged group leaves row-major: rows l>>2 and 16 + (l>>2), 16 bytes per lane
-                    u32x4 o0, o1;
-                    asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:1024\n\ts_waitcnt lgkmcnt(0)"
-                                 : "=&v"(o0), "=&v"(o1) : "v"(strd) : "memory");
-                    *(u32x4 *)(rowp + lane_off + 64 * g) = o0;
-                    *(u32x4 *)(rowp + (long)V * 32 + lane_off + 64 * g) = o1;
-                }
+                st_s = e + e2;
+                st_m = mn;
+                // the staged group leaves row-major: rows l>>2 and 16 + (l>>2), 16 bytes per lane
+                u32x4 o0, o1;
+                asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:1024\n\ts_waitcnt lgkmcnt(0)"
+                             : "=&v"(o0), "=&v"(o1) : "v"(strd) : "memory");
+                *(u32x4 *)(rowp + lane_off + 64 * g) = o0;
+                *(u32x4 *)(rowp + (long)V * 32 + lane_off + 64 * g) = o1;
                 __builtin_amdgcn_sched_barrier(0);
             }
             asm volatile("ds_write_b128 %0, %1 offset:%2" :: "v"(bias_w ^ ((pass & 1) ? 0 : 512)), "v"(bn), "n"(0) : "memory");
@@ -843,7 +810,7 @@ static void launch_fwd_ra(const Bf16Args &a, hipStream_t st)
     static bool attr_set[16] = {false};
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;
-    const int lds = FR_OFF(64) ? 100 * 1024 : 4 * FR_SLOT + 2 * 512 + 4 * 2048;
+    const int lds = 4 * FR_SLOT + 2 * 512 + 4 * 2048;
     if (dev < 0 || !attr_set[dev]) {
         (void)hipFuncSetAttribute((const void *)k_joint_fwd_bf16_ra<KC>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (dev >= 0) attr_set[dev] = true;
@@ -895,12 +862,6 @@ void launch_joint_fwd_bf16(const Bf16Args &a, hipStream_t st)
 // FIRST = false launch per further 512 columns (`hp`), which finds G in place of the logits, copies
 // it into the exchange instead of producing it, and stores nothing but its slabs.
 // ---------------------------------------------------------------------------------------
-// Diagnostic builds only (-DDH_EXP=bits, tools/build_bf16_variants.sh): parts of k_dhidden_bf16 compiled out — 1 no MFMAs,
-// 2 no G arithmetic (exponentials), 4 no G stores, 8 no logits loads, 16 no W staging (loads + LDS writes), 32 no epilogue
-#ifndef DH_EXP
-#define DH_EXP 0
-#endif
-#define DH_OFF(bit) ((DH_EXP) & (bit))
 #define BG_BT 8
 #define BG_BU 16
 template <bool FIRST>
@@ -960,7 +921,6 @@ __global__ __launch_bounds__(512, 1) void k_dhidden_bf16(Bf16Args a, const int h
     if (FIRST) BF_CLOCK_STAMP(304);
     auto produce = [&](const u32x4 &x, int c, int slot) {
         if constexpr (!FIRST) { s_g[slot * 512 + gdst] = x; return; }
-        if (DH_OFF(2)) { s_g[slot * 512 + gdst] = x; return; }
         float g[8];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -996,18 +956,16 @@ __global__ __launch_bounds__(512, 1) void k_dhidden_bf16(Bf16Args a, const int h
         gst[i] = (u32x4 *)(a.logits + (gst_ok[i] ? ((long)b * T + pt) * U1 + su : zrow) * V) + sp;
     }
     auto wload = [&](u32x4 (&w)[4], int c) {
-        if (DH_OFF(16)) return;
         const u32x4 *p = wp + (long)(c < VC ? c : VC - 1) * 2048;
 #pragma unroll
         for (int i = 0; i < 4; ++i) w[i] = p[i * 64];
     };
     auto wstore = [&](const u32x4 (&w)[4], int slot) {
-        if (DH_OFF(16)) return;
         u32x4 *p = s_b + slot * 2048 + (wave * 4) * 64 + lane;
 #pragma unroll
         for (int i = 0; i < 4; ++i) p[i * 64] = w[i];
     };
-    auto xload = [&](u32x4 &x, int c) { if (!DH_OFF(8)) x = xsrc[4 * (c < VC ? c : VC - 1)]; };
+    auto xload = [&](u32x4 &x, int c) { x = xsrc[4 * (c < VC ? c : VC - 1)]; };
 
     u32x4 xr[4] = {};  // logits ring (slot = chunk & 3), 4 chunks ahead of production
     u32x4 wx[4] = {}, wy[4] = {};  // staged W: even / odd chunks
@@ -1045,10 +1003,8 @@ __global__ __launch_bounds__(512, 1) void k_dhidden_bf16(Bf16Args a, const int h
 #pragma unroll
                 for (int n = 0; n < 8; ++n) {
                     if (n + DEPTH < 8) bf[(n + DEPTH) % (DEPTH + 1)] = pb[(((n + DEPTH) >> 2) * 16 + ((n + DEPTH) & 3)) * 64];
-                    if (!DH_OFF(1)) {
-                        acc[n & 3] = mfma_bf16(af[0][n >> 2], bf[n % (DEPTH + 1)], acc[n & 3]);
-                        acc[4 + (n & 3)] = mfma_bf16(af[1][n >> 2], bf[n % (DEPTH + 1)], acc[4 + (n & 3)]);
-                    }
+                    acc[n & 3] = mfma_bf16(af[0][n >> 2], bf[n % (DEPTH + 1)], acc[n & 3]);
+                    acc[4 + (n & 3)] = mfma_bf16(af[1][n >> 2], bf[n % (DEPTH + 1)], acc[4 + (n & 3)]);
                 }
                 __builtin_amdgcn_sched_group_barrier(0x100, 4 + DEPTH + 2, 0);
 #pragma unroll
@@ -1058,7 +1014,7 @@ __global__ __launch_bounds__(512, 1) void k_dhidden_bf16(Bf16Args a, const int h
                 }
                 __builtin_amdgcn_sched_group_barrier(0x008, 2 * DEPTH, 0);
             }
-            if (FIRST && !(q & 1) && !RNNT_XP(a.flags, 256) && !DH_OFF(4)) {  // chunk c+1 is odd: the pair (c, c+1) is complete
+            if (FIRST && !(q & 1) && !RNNT_XP(a.flags, 256)) {  // chunk c+1 is odd: the pair (c, c+1) is complete
                 __builtin_amdgcn_sched_barrier(0);
                 const u32x4 gb0 = s_g[gsrc], gb1 = s_g[gsrc + 8];
                 if (gst_ok[0]) gst[0][4 * c] = gb0;
@@ -1071,7 +1027,7 @@ __global__ __launch_bounds__(512, 1) void k_dhidden_bf16(Bf16Args a, const int h
     if (FIRST) BF_CLOCK_STAMP(306);
     // ---- epilogue.  Accumulator register r of tile 4mt+q (mt = 0,1): row (r&3) + 8(r>>2) + 4*half
     // of M-tile 2wm+mt = (t-row 2(2wm+mt) + (r>>3), u (r&3) + 8((r>>2)&1) + 4*half), column 128wn + 4j + q.
-    if (RNNT_XP(a.flags, 8192) || DH_OFF(32)) {  // (the accumulators stay "used": without this the MFMAs are dead code too)
+    if (RNNT_XP(a.flags, 8192)) {  // (the accumulators stay "used": without this the MFMAs are dead code too)
 #pragma unroll
         for (int tl = 0; tl < 8; ++tl) asm volatile("" :: "a"(acc[tl]));
         return;
@@ -1183,13 +1139,6 @@ void launch_dhidden_bf16(const Bf16Args &a, hipStream_t st)
 // ---------------------------------------------------------------------------------------
 #define BW_ROWS 32   // cells per stage (2 MFMA k-steps)
 #define BW_NST 4     // ring stages
-// Diagnostic builds only (-DBW_EXP=bits, VAR=BW_EXP tools/build_bf16_variants.sh): parts of k_dw_bf16 compiled out (results wrong by
-// construction) — 1 no MFMAs, 2 no db (v_dot2c), 4 no transposed fragment reads, 8 no DMA bytes (requested past the buffer's range: the
-// instruction and its vmcnt stay), 16 no DMA instructions, 32 no barrier, 64 no lockstep with the split's other tiles
-#ifndef BW_EXP
-#define BW_EXP 0
-#endif
-#define BW_OFF(bit) ((BW_EXP) & (bit))
 
 __global__ __launch_bounds__(256, 1) void k_dw_bf16(Bf16Args a)
 {
@@ -1242,7 +1191,7 @@ __global__ __launch_bounds__(256, 1) void k_dw_bf16(Bf16Args a)
         int soff[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-            soff[i] = BW_OFF(8) ? 0x7ffffff0 : (int)((4 * i + (lane >> 4)) * rstride) + 16 * ((lane & 15) ^ (((lane >> 4) << 2) | (i & 3))) - 1024 * (i & 3);
+            soff[i] = (int)((4 * i + (lane >> 4)) * rstride) + 16 * ((lane & 15) ^ (((lane >> 4) << 2) | (i & 3))) - 1024 * (i & 3);
         // (round 5: pieces 4g .. 4g+3 share one LDS base (M0) and carry the immediate offset 1024 (i & 3), which advances the memory address
         // too — taken back out of the per-lane offset above: rstride >= 256 bytes, so 4 i rows >= 1024 (i & 3) bytes)
         // (raw-buffer form: the 32 rows of a stage as a buffer with a wave-uniform base — scalar arithmetic only; the
@@ -1252,7 +1201,6 @@ __global__ __launch_bounds__(256, 1) void k_dw_bf16(Bf16Args a)
             return __builtin_amdgcn_make_buffer_rsrc((void *)(src + st * (BW_ROWS * rstride)), 0, (int)(BW_ROWS * rstride), 0x00020000);
         };
         auto dma_stage = [&](long st, int slot) {
-            if (BW_OFF(16)) return;
             const __amdgpu_buffer_rsrc_t r = stage_rsrc(st);
             char *dst = s_ring + slot * 32768 + wave * 8192;
 #pragma unroll
@@ -1292,7 +1240,7 @@ __global__ __launch_bounds__(256, 1) void k_dw_bf16(Bf16Args a)
         };
         struct Frags { u32x2 al[4], ah[4], bl[4], bh[4]; };
         auto reads = [&](Frags &f, int slot, int ks) {  // 16 transposed reads, NOT waited for
-            if (RNNT_XP(a.flags, 4096) || BW_OFF(4)) return;  // experiment switch
+            if (RNNT_XP(a.flags, 4096)) return;  // experiment switch
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 const int a0 = a_tile + slot * 32768 + 4096 * ks, b0 = b_tile + slot * 32768 + 4096 * ks;
@@ -1325,14 +1273,14 @@ __global__ __launch_bounds__(256, 1) void k_dw_bf16(Bf16Args a)
             }
 #pragma unroll
             for (int qm = 0; qm < 4; ++qm) {
-                if (!RNNT_XP(a.flags, 1024) && !BW_OFF(1)) {
+                if (!RNNT_XP(a.flags, 1024)) {
 #pragma unroll
                     for (int qn = 0; qn < 4; ++qn) acc[qm][qn] = mfma_bf16(fa[qm], fb[qn], acc[qm][qn]);
                 }
-                if (!RNNT_XP(a.flags, 8192) && !BW_OFF(16)) dma_piece(dst, dslot, piece0 + qm);
+                if (!RNNT_XP(a.flags, 8192)) dma_piece(dst, dslot, piece0 + qm);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (do_b && !RNNT_XP(a.flags, 2048) && !BW_OFF(2)) {
+            if (do_b && !RNNT_XP(a.flags, 2048)) {
 #pragma unroll
                 for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -1353,7 +1301,7 @@ __global__ __launch_bounds__(256, 1) void k_dw_bf16(Bf16Args a)
         // looking, so every wave reaches the end whatever the others do.
         constexpr int DW_LAG = 3, DW_NAPS = 256;
         int *prog = a.dw_prog ? a.dw_prog + split * 16 : nullptr;
-        bool sync_on = prog != nullptr && tiles > 1 && tiles <= 16 && !BW_OFF(64);
+        bool sync_on = prog != nullptr && tiles > 1 && tiles <= 16;
         const int *nb = prog ? prog + (tile + 1 < tiles ? tile + 1 : 0) : nullptr;  // the neighbour's word
         int nb_at = 0x7fffffff;  // the neighbour's stage count as of the last look
         int done = 0;  // stages behind this workgroup, over all ranges
@@ -1397,7 +1345,6 @@ __global__ __launch_bounds__(256, 1) void k_dw_bf16(Bf16Args a)
             // stage st+1: younger in flight = stage st+2 (8 DMAs) + the 4 pieces just issued
             // (+ wave 0's progress store now and then: one more outstanding operation only makes the wait stricter)
             asm volatile(RNNT_VMCNT(12) ::: "memory");
-            if (BW_OFF(32)) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); else
             lds_barrier();  // B_{st+1}; its lgkmcnt(0) also covers Y and the neighbour's progress word
             landed(Y, false);
             reads(X, (slot + 1) & 3, 0);  // past the last stage: reads a landed, unused slot

@@ -256,18 +256,14 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
         !aligned16(grad_pred) || !aligned16(grad_W) || !aligned16(grad_bias) ||
         ((uintptr_t)workspace & 255))
         return fail(RNNT_ERR_INVALID_ARG, "pointers must be 16-byte aligned (workspace 256)");
-    // kernels that were measured equal to (or slower than) the shipped ones live in the diagnostic library only
-    // (-DRNNT_LAB, tools/build_lab.sh): the product library refuses their variant bits instead of silently running something else
-    constexpr int lab_only = RNNT_VARIANT_LAB_MASK;
-#ifndef RNNT_LAB
-    if (variant & lab_only)
-        return fail(RNNT_ERR_UNSUPPORTED, "variant 0x%x names a kernel of the diagnostic library (build_variants/lab/librnnt_engine_lab.so, "
-                    "tools/build_lab.sh): librnnt_engine.so ships the default kernels only", variant & lab_only);
-#endif
+    // bits 14 and up once named kernels measured equal to (or slower than) the shipped ones; those kernels are gone and the bits stay
+    // reserved: refused here, before anything is launched, instead of silently running something else
+    if (variant & RNNT_VARIANT_LAB_MASK)
+        return fail(RNNT_ERR_UNSUPPORTED, "variant bits 0x%x are reserved: no kernel of librnnt_engine.so answers to them",
+                    variant & RNNT_VARIANT_LAB_MASK);
     const int xflags = g_flags | (variant & (RNNT_VARIANT_SEPARATE_G | RNNT_VARIANT_SEPARATE_HIDDEN |
                                              RNNT_VARIANT_FWD_LDS_RING | RNNT_VARIANT_FWD_ONE_WG_PER_TILE |
-                                             RNNT_VARIANT_X3_FP32_FWD | RNNT_VARIANT_X3_FP32_DH |
-                                             RNNT_VARIANT_X3_FWD_2WG | RNNT_VARIANT_X3_FWD_8W | RNNT_VARIANT_X3_DW_P16 | RNNT_VARIANT_X3_FWD_Z | RNNT_VARIANT_X2_DW_8W | RNNT_VARIANT_X2_FWD_2WG | RNNT_VARIANT_X2_DW_P16));
+                                             RNNT_VARIANT_X3_FP32_FWD | RNNT_VARIANT_X3_FP32_DH));
     const bool no_flush = (variant & RNNT_VARIANT_X2_NO_FLUSH_SKIP) != 0 || fastemit > 0.f || delay > 0.f;
     rnnt_engine_ws_layout L;
     layout(B, T, U1, H, V, dtype, &L);
@@ -328,7 +324,7 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
         // fp32-accurate route on the bf16 matrix pipes (x3.hip).  Stage by stage the fp32 route's own kernel can
         // stand in (RNNT_VARIANT_X3_FP32_FWD / _DH): same data, one stage swapped — how each x3 kernel is checked.
         X3Args h;
-        h.tile_live = nullptr; h.ks_bitmap = nullptr; h.ks_list = nullptr; h.live_stats = nullptr; h.tile_list = nullptr; h.zero_all = 0;
+        h.tile_live = nullptr; h.ks_bitmap = nullptr; h.ks_list = nullptr; h.live_stats = nullptr; h.tile_list = nullptr;
         h.grp_bitmap = nullptr; h.grp_list = nullptr; h.dw_ksteps = 0;
         double flush_log2 = -HUGE_VAL;  // the flush rule's threshold (x2.hip): log2 of 2^-26 / g_scale; -inf flags nothing
         float flush_lin = 0.f;
@@ -367,8 +363,7 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
                         ws_bytes, L.total + L.aux_bytes);
         if (x2) {
             x2_live_carve(ws + L.x2_live, B, T, U1, (long)L.rows_pad, h);
-            h.zero_all = x2_dw_walks_table(H, V, xflags) ? 1 : 0;
-            h.dw_ksteps = x2_dw_walks_ksteps(H, V, xflags) ? 1 : 0;
+            h.dw_ksteps = x2_dw_walks_ksteps(H, V) ? 1 : 0;
             // the fp32 kernels standing in for dHidden multiply G in fp32, where a flushed cell's G is small but not zero: no flush, no tile
             // skipping there (k_x2_split_g writes every row, so the dW list walk still applies)
             if (f32_dh) { flush_log2 = -HUGE_VAL; flush_lin = 0.f; }
@@ -407,18 +402,8 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
                 if (x2) launch_x2_make_hidden(h, st);
                 else launch_x3_make_hidden(h, st);  // the planes the backward reads
             } else if (x2) {
-#ifdef RNNT_LAB
-                if ((xflags & RNNT_VARIANT_X2_FWD_2WG) && x2_fwd_d_ok(U1, H, V)) launch_joint_fwd_x2d(h, st);
-                else
-#endif
                 launch_joint_fwd_x2(h, st);
             } else {
-#ifdef RNNT_LAB  // each variant bit launches exactly its own kernel (round-4 advice: _FWD_Z used to fall through to x3d<4>)
-                if ((xflags & RNNT_VARIANT_X3_FWD_Z) && x3_fwd_d_ok(U1, H, V)) launch_joint_fwd_x3z(h, st);
-                else if ((xflags & RNNT_VARIANT_X3_FWD_8W) && x3_fwd_d_ok(U1, H, V)) launch_joint_fwd_x3d(h, 8, st);
-                else if ((xflags & RNNT_VARIANT_X3_FWD_2WG) && x3_fwd_d_ok(U1, H, V)) launch_joint_fwd_x3d(h, 4, st);
-                else
-#endif
                 launch_joint_fwd_x3(h, st);
             }
         }
@@ -446,9 +431,6 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
         if (stages & ST_DH_RED) launch_dhidden_reduce(g, st);
         if (stages & ST_DW) {
             if (x2) launch_dw_x2(h, st);
-#ifdef RNNT_LAB
-            else if (xflags & RNNT_VARIANT_X3_DW_P16) launch_dw_x3p(h, st);
-#endif
             else launch_dw_x3(h, st);
         }
         if (stages & ST_DW_RED) {

@@ -2,7 +2,6 @@
 #pragma once
 #include "common.hpp"
 #include "../../include/rnnt_engine.h"  // rnnt_conv_predictor_params (DecLoopArgs)
-#include "lab/rnnt_engine_lab.h"       // variant bits of the diagnostic library (refused by the product library)
 
 // ---- engine.hip: sets the thread-local error message, returns `code`
 int engine_fail(int code, const char *fmt, ...);
@@ -194,7 +193,6 @@ struct X3Args {
     int *live_stats;                 // [0] live k-steps = length of ks_list, [1] k-steps with a cell, [2] live dHidden tiles = length of tile_list, [3] dHidden tiles,
                                      // [4] live groups = length of grp_list, [5] groups with a cell
     const int *tile_list;            // ascending indices [b][tt][ub] of the tiles whose flag is 1: the workgroups of k_dhidden_x2 (entries past live_stats[2] hold anything)
-    int zero_all;                    // 1: the dW kernel of this call walks the 32-cell table (the lab's k_dw_x2p): k_x2_dead_rows zero-fills every row of the tiles that are not live
     int dw_ksteps;                   // 1: the dW kernel of this call walks ks_list (k_dw_x2m): k_x2_dead_rows zeroes the dead tiles' rows of the live k-steps, not of the live groups
 };
 size_t x2_live_bytes(int B, int T, int U1, long rows_pad);  // bytes of the region below
@@ -209,12 +207,8 @@ void launch_x3_split_g(const X3Args &a, hipStream_t st);
 void launch_x3_zero_padding(const X3Args &a, int what, hipStream_t st);
 void launch_x3_pack_w(const X3Args &a, hipStream_t st);
 void launch_joint_fwd_x3(const X3Args &a, hipStream_t st);   // one 512-register wave per SIMD (default)
-bool x3_fwd_d_ok(int U1, int H, int V);
-void launch_joint_fwd_x3z(const X3Args &a, hipStream_t st);  // one wave per SIMD, 2 M tiles per wave, 256 x 256 tiles, A in registers (RNNT_VARIANT_X3_FWD_Z)
-void launch_joint_fwd_x3d(const X3Args &a, int nw, hipStream_t st);  // two waves per SIMD, A in registers (RNNT_VARIANT_X3_FWD_2WG / _8W)
 void launch_dhidden_x3(const X3Args &a, hipStream_t st);
 void launch_dw_x3(const X3Args &a, hipStream_t st);   // v_mfma_f32_32x32x16_bf16, six products per k-step (default)
-void launch_dw_x3p(const X3Args &a, hipStream_t st);
 // RNNT_DTYPE_F32_F16X2 (x2.hip): the bf16x3 route's stages on two fp16 planes and three products
 bool x2_fwd_ok(int U1, int H, int V);
 bool x2_dhidden_ok(int U1, int H, int V);
@@ -227,8 +221,6 @@ void launch_x2_pack_w(const X3Args &a, float *scales, hipStream_t st);  // s_W f
 void launch_x2_make_ep(const X3Args &a, hipStream_t st);               // exp(2 enc), exp(2 pred) in k-step-major layout + the range flag
 size_t x2_ep_bytes(int B, int T, int U1, int H);
 void launch_joint_fwd_x2(const X3Args &a, hipStream_t st);   // one 512-register wave per SIMD
-bool x2_fwd_d_ok(int U1, int H, int V);
-void launch_joint_fwd_x2d(const X3Args &a, hipStream_t st);  // two 4-wave workgroups per CU, A in registers (RNNT_VARIANT_X2_FWD_2WG)
 void launch_x2_dead_rows(const X3Args &a, hipStream_t st);  // zero G rows of dead tiles' cells inside live groups (what k_dw_x2 reads beside the live tiles' rows; X3Args::dw_ksteps: inside live k-steps)
 void launch_dhidden_x2(const X3Args &a, hipStream_t st);
 // the joint's input projections (audio_ln / text_ln) and their backward on the f16x2 pipes (x2.hip, round 5)
@@ -239,9 +231,8 @@ void launch_linear_x2_bwd(const float *x, long ldx, const float *W, const float 
                           hipStream_t st);
 int x2_dw_tiles(int H, int V);  // workgroup tiles per split of launch_dw_x2 (k_dw_x2 / k_dw_x2m)
 void launch_dw_reduce_x2(const X3Args &a, float *grad_W, float *grad_bias, hipStream_t st);  // the slabs' sum, fp64 accumulate, one rounding
-bool x2_dw_walks_table(int H, int V, int flags);  // launch_dw_x2's kernel for this shape reads k_dw_table's ranges, not X3Args::grp_list
-bool x2_dw_walks_ksteps(int H, int V, int flags);  // ... reads X3Args::ks_list (k_dw_x2m)
-void launch_dw_x2(const X3Args &a, hipStream_t st, bool build_table = true, bool zero_prog = true);  // k_dw_x2<4> (k_dw_x2<4, true> when H % 256 == 128); -DRNNT_LAB builds: also k_dw_x2<8> / k_dw_x2p behind RNNT_VARIANT_X2_DW_8W / _P16
+bool x2_dw_walks_ksteps(int H, int V);  // launch_dw_x2's kernel for this shape reads X3Args::ks_list (k_dw_x2m), not X3Args::grp_list
+void launch_dw_x2(const X3Args &a, hipStream_t st, bool zero_prog = true);  // k_dw_x2<4> (k_dw_x2<4, true> when H % 256 == 128), k_dw_x2m where x2_dw_mixed_ok
 
 // ---- decode.hip
 void launch_scan_logits(const float *enc, long enc_st, const float *pred, const float *W, const float *bias,

@@ -49,25 +49,6 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 #define X2_CLOCK_STAMP(SLOT) do {} while (0)
 #endif
 
-#ifndef X2_REREAD
-#define X2_REREAD 0  // 1: passes after a tile's first load the stored hidden planes back instead of producing them again — built, parity-green, measured SLOWER (cfg2 forward 21.23 vs 20.98 ms, same box: profiles/r06_fwd_whatif.txt): the planes are unique bytes per lane from L2, E and P are L1-resident rows
-#endif
-// compile-time experiment switches (-DX2_NT=bits): 1 non-temporal logits loads in k_dhidden_x2, 2 non-temporal operand DMAs in k_dw_x2<4>
-#ifndef X2_NT
-#define X2_NT 0
-#endif
-// -DX2_EXP=bits (what-if builds of k_joint_fwd_x2, WRONG results; tools/build_x2_variants.sh): 2 W DMAs requested past the buffer's range (instructions stay, no bytes move); 4 hidden stores aimed at the
-// first tile's rows (cache-resident); 8 logits stores aimed at the first tile's rows; 16 logits stores with the default cache policy
-// instead of non-temporal; 32 no production arithmetic; 64 no softmax statistics; 128 no MFMAs; 256 no logits stores at all; 512 no operand
-// loads; 1024 no W DMA instructions; 2048 no fragment reads from LDS; 4096 no barrier in the k-step
-// (round 5, on the round-4 schedule: 1 = half of W's bytes, 8192 / 16384 = a second set of operand loads / a second production per k-step;
-// 1 | 8192 | 16384 priced the memory / VALU mix of a 256-cell x 256-column tile: 22.0 ms against 22.0 — profiles/r05_fwd_whatif.txt)
-#ifndef X2_EXP
-#define X2_EXP 0
-#endif
-#ifndef XF2_IMM
-#define XF2_IMM 1  // 1: a k-step's W DMAs (forward, dHidden) in groups of four on one M0 / scalar offset, told apart by the instruction's 12-bit
-#endif             // immediate offset, which advances the memory AND the LDS address: 12 scalar instructions fewer per k-step (forward 21.7 -> 21.05 ms)
 #define X2_SH 16384.0f          // scale of the hidden operand (|tanh| <= 1)
 #define X2_INV_SH (1.0f / 16384.0f)
 #define X2_F16_MAX 65504.0f
@@ -259,7 +240,7 @@ void launch_x2_zero_padding(const X3Args &a, int what, hipStream_t st)
 //                         reproducible); the list is 16-byte aligned and padded with entries that name the first group of the zero
 //                         padding rows, for the ring's read-ahead and the missing groups of the last k-step.  The live cells of a (b, t)
 //                         line form a band of ~100 cells; 16-cell k-steps cut it at 16-cell boundaries and list ~12 % more rows;
-//   ks_bitmap / ks_list   the same for the 16-cell k-steps (linear cell index / 16): what k_dw_x2m and the lab kernels still walk;
+//   ks_bitmap / ks_list   the same for the 16-cell k-steps (linear cell index / 16): what k_dw_x2m walks;
 //   live_stats            the counts (readable from the workspace: rnnt_engine_ws_layout::x2_live).
 // Dropping a flushed cell changes no bit of costs, dEnc or dPred (its products were exact zeros); dW / db change in summation
 // order only (the splits cut the live list at other cells).  RNNT_VARIANT_X2_NO_FLUSH_SKIP flags no cell: the structures then hold
@@ -525,7 +506,6 @@ static_assert(XW2_ROWS == XW2_ROWS_, "k-step size");
 #define XW2_PLANE 4096            // one operand tile of one plane: 16 rows x 256 B
 #define XW2_STAGE (2 * XW2_PLANE)  // one stage of one operand tile
 #define XW2_TILE (XW2_NST * XW2_STAGE)  // ring of one operand tile: [stage][plane][16 x 256 B] = 24 KiB
-#define XW2_GRAN 32  // granule of the live-row table the lab's k_dw_x2p still walks (k_dw_table, shared with the bf16 routes: 2 k-steps); the Linear layer's table unit
 
 // the four list entries of a k-step (X3Args::grp_list): ONE 16-byte scalar load, then WAIT (a counted vmcnt or nothing), then the wait for
 // the load itself — one statement, so that the entries have landed wherever they are named
@@ -543,19 +523,18 @@ struct X2Frag { u32x2 lo[4], hi[4]; };  // 4 tiles: cells 0-3 / 4-7 of a lane's 
                    "+v"(f.hi[2]), "+v"(f.hi[3])                                                                  \
                  :: "memory")
 
-// NW = waves per workgroup.  4: one wave per SIMD, wave tile 128 v x 128 h.  8: TWO waves per SIMD (256 registers each), wave
-// tile 128 v x 64 h = 8 accumulator tiles: what one wave waits for — the barrier, a counted vmcnt, the ~80 cycles each of its
-// LDS-DMA issues blocks it — the SIMD's other wave fills with MFMAs.  MEASURED EQUAL (15.5 ms both, cfg2): the kernel is bound by
-// the bytes it stages — 32 KiB per k-step and CU at ~12.6 B/clk/CU (6.8 TB/s over the chip out of L2), the same rate the forward's
-// and dHidden's W streams reach — not by issue stalls.  4 is the default; 8 stays behind RNNT_VARIANT_X2_DW_8W.
+// NW = waves per workgroup: 4, one wave per SIMD, wave tile 128 v x 128 h = 16 accumulator tiles.  (Two waves per SIMD with 8 tiles each
+// were measured equal, 15.5 ms both at cfg2: the kernel is bound by the bytes it stages — 32 KiB per k-step and CU at ~12.6 B/clk/CU, the
+// rate the forward's and dHidden's W streams reach — not by issue stalls.  The parameter stays in the kernel's name: profiles/, DESIGN.md.)
 // PARTH (H % 256 == 128: the last h block is half empty — H = 640): the waves of the dead 128-column half run no product MFMAs and the
 // dead hidden tile's DMAs are requested past their buffer's range (no bytes moved; the instruction and its vmcnt stay).
 template <int NW, bool PARTH = false>
 __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
 {
-    constexpr int WN = NW / 2;      // waves along h
-    constexpr int QN = 8 / WN;      // 32-column h tiles per wave (4 or 2)
-    constexpr int ND = 32 / NW;     // DMA pieces per wave and stage (8 or 4)
+    static_assert(NW == 4, "one wave per SIMD");
+    constexpr int WN = 2;  // waves along h
+    constexpr int QN = 4;  // 32-column h tiles per wave
+    constexpr int ND = 8;  // DMA pieces per wave and stage
     extern __shared__ __attribute__((aligned(1024))) char s_ring[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -590,18 +569,17 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
             for (int r = 0; r < 16; ++r) acc[qm][qn][r] = 0.f;
     // db rides the matrix pipe as in k_dw_x3: one more MFMA per plane and k-step against a column SELECTOR of ones, for one
     // (one h block: two) of the wave's M tiles, into a 17th accumulator tile held in VGPRs
-    // (8 waves: the four wn of h block 0 take the four M tiles of their wm half)
-    const bool do_b = NW == 8 ? hb == 0 : hb < 2;  // workgroup-uniform
-    const int bsel0 = NW == 8 ? wn : (n_hblk >= 2 ? (hb & 1) * 2 + wn : wn);
-    const bool two_b = NW == 4 && n_hblk < 2;  // one h block, 4 waves: each wave takes two tiles, bsel0 and bsel0 + 2
+    const bool do_b = hb < 2;  // workgroup-uniform
+    const int bsel0 = n_hblk >= 2 ? (hb & 1) * 2 + wn : wn;
+    const bool two_b = n_hblk < 2;  // one h block: each wave takes two tiles, bsel0 and bsel0 + 2
     f32x16 dacc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) dacc[r] = 0.f;
     const unsigned sel0 = (lane & 31) == 0 ? 0x3c003c00u : 0u, sel1 = (lane & 31) == 1 ? 0x3c003c00u : 0u;  // fp16 ones
 
     if (g_hi > g_lo) {
-        // ---- DMA source of this wave's operand tile (8 waves: two waves per operand tile, one plane each)
-        const int otile = NW == 8 ? wave >> 1 : wave;
+        // ---- DMA source of this wave's operand tile
+        const int otile = wave;
         const bool is_g = otile < 2;
         int col0 = (is_g ? vb : hb) * 256 + 128 * (otile & 1);
         const bool dead_tile = PARTH && !is_g && col0 >= H;  // (wave-uniform)
@@ -627,10 +605,9 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
             const int cb = is_g ? 128 * (jg >> 2) + 16 * (jg & 3) : 16 * jg;
             soff[i] = dead_tile ? 0x7ffffff0 : (int)((lane >> 4) * rstride) + cb;
         }
-        // XF2_IMM: the four pieces of a plane share one LDS base (M0); piece i carries the immediate offset 1024 i, which advances the memory
+        // The four pieces of a plane share one LDS base (M0); piece i carries the immediate offset 1024 i, which advances the memory
         // address too and counts in the range check.  It is taken back out of the piece's buffer BASE and added to its range (the per-lane
         // offset of the group's row 0 is below 1024 i: subtracting there would wrap, and the range check would hand back zeros)
-        constexpr bool IMM = XF2_IMM && NW == 4;
         const unsigned gbytes = (unsigned)(4 * rstride);  // one group of one plane (rstride < 2^29: x2_dhidden_ok / x2_linear_ok)
         const bool live_n = !PARTH || hb * 256 + wn * 32 * QN < H;  // this wave's h columns exist (wave-uniform)
         // The walk: ONE pipeline run over the split's list entries — k-step ks multiplies the 16 cells of the four groups
@@ -653,11 +630,10 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
                 const int swz = ((row & 3) << 2) | ((row >> 2) & 3);
                 const int ch = 4 * m + 2 * (g & 1) + (pp >> 1);
                 abase[m][sec] = lds0 + wm * XW2_TILE + 256 * row + 16 * (ch ^ swz) + 8 * (pp & 1);
-                if (m < QN) {  // this wave's h tiles: columns 32 QN wn + 32 m of the 256 = operand tile 2 + (col >> 7), tile (col & 127) / 32
-                    const int col = 32 * QN * wn + 32 * m;
-                    const int chb = 4 * ((col & 127) >> 5) + 2 * (g & 1) + (pp >> 1);
-                    bbase[m < QN ? m : 0][sec] = lds0 + (2 + (col >> 7)) * XW2_TILE + 256 * row + 16 * (chb ^ swz) + 8 * (pp & 1);
-                }
+                // this wave's h tiles: columns 32 QN wn + 32 m of the 256 = operand tile 2 + (col >> 7), tile (col & 127) / 32
+                const int col = 32 * QN * wn + 32 * m;
+                const int chb = 4 * ((col & 127) >> 5) + 2 * (g & 1) + (pp >> 1);
+                bbase[m][sec] = lds0 + (2 + (col >> 7)) * XW2_TILE + 256 * row + 16 * (chb ^ swz) + 8 * (pp & 1);
             }
         int sbase[2][2];  // db: fragment bases of the M tile(s) this wave sums (bsel0, and bsel0 + 2 with one h block)
 #pragma unroll
@@ -679,21 +655,14 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
             i32x4 ent;
             const int *ep = lptr + 4 * (ks + (XW2_NST - 1));
             if (ND * (XW2_NST - 2) == 16) XW2_LOAD_ENT4(ent, ep, RNNT_VMCNT(16) "\n\t");
-            else if (ND * (XW2_NST - 2) == 8) XW2_LOAD_ENT4(ent, ep, RNNT_VMCNT(8) "\n\t");
-            else XW2_LOAD_ENT4(ent, ep, RNNT_VMCNT(4) "\n\t");
-            // piece n of this wave's share of stage ks+NST-1 -> ring stage DST: plane n>>2 (8 waves: wave & 1), ring rows 4(n&3).. <- the
+            else XW2_LOAD_ENT4(ent, ep, RNNT_VMCNT(8) "\n\t");
+            // piece n of this wave's share of stage ks+NST-1 -> ring stage DST: plane n>>2, ring rows 4(n&3).. <- the
             // four rows of entry n&3 as a raw buffer (wave-uniform base, built here between the MFMAs; the per-lane part is the 32-bit soff)
             auto dma_piece = [&](auto n_c) {
-                constexpr int n = decltype(n_c)::value, i = n & 3;
-                if (NW == 8) {
-                    if (wave & 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(x2_piece_rsrc(pbase[1], ent[i], gbytes, 0), (lds_vptr)(s_ring + otile * XW2_TILE + DST * XW2_STAGE + XW2_PLANE + 1024 * i), 16, soff[i], 0, 0, 0);
-                    else __builtin_amdgcn_raw_ptr_buffer_load_lds(x2_piece_rsrc(pbase[0], ent[i], gbytes, 0), (lds_vptr)(s_ring + otile * XW2_TILE + DST * XW2_STAGE + 1024 * i), 16, soff[i], 0, 0, 0);
-                } else {
-                    constexpr int p = (n >> 2) & 1, imm = IMM ? 1024 * i : 0;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(x2_piece_rsrc(pbase[p], ent[i], gbytes, imm),
-                                                             (lds_vptr)(s_ring + otile * XW2_TILE + DST * XW2_STAGE + p * XW2_PLANE + 1024 * i - imm),
-                                                             16, soff[i], 0, imm, (X2_NT & 2) ? 2 : 0);  // (experiment 2: aux = 2, non-temporal)
-                }
+                constexpr int n = decltype(n_c)::value, i = n & 3, p = (n >> 2) & 1, imm = 1024 * i;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(x2_piece_rsrc(pbase[p], ent[i], gbytes, imm),
+                                                         (lds_vptr)(s_ring + otile * XW2_TILE + DST * XW2_STAGE + p * XW2_PLANE),
+                                                         16, soff[i], 0, imm, 0);
             };
             // 8 transposed reads of plane P of the A / B operand (inline asm: hipcc guards every LDS read it can see behind
             // an LDS-DMA with vmcnt(0)); results are used only after X2_LANDED named them
@@ -712,7 +681,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
                     fa[m] = u32x4{fa_.lo[m][0], fa_.lo[m][1], fa_.hi[m][0], fa_.hi[m][1]};
-                    if (m < QN) fb[m < QN ? m : 0] = u32x4{fb_.lo[m][0], fb_.lo[m][1], fb_.hi[m][0], fb_.hi[m][1]};
+                    fb[m] = u32x4{fb_.lo[m][0], fb_.lo[m][1], fb_.hi[m][0], fb_.hi[m][1]};
                 }
 #pragma unroll
                 for (int qm = 0; qm < 4; ++qm) {
@@ -748,14 +717,14 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
             reads(Am, abase, X2Int<1>{}, X2Int<4>{});
             X2_LANDED(Ah, 8);
             X2_LANDED(Bh, 8);
-            // DMA pieces of the k-step: 3 + 3 + 2 (8 waves: 2 + 1 + 1)
-            product(Ah, Bh, X2Int<0>{}, X2Int<(NW == 8 ? 2 : 3)>{});
+            // DMA pieces of the k-step: 3 + 3 + 2
+            product(Ah, Bh, X2Int<0>{}, X2Int<3>{});
             reads(Bm, bbase, X2Int<1>{}, X2Int<QN>{});
-            if (QN == 4) X2_LANDED(Am, 8); else X2_LANDED(Am, 4);
-            product(Am, Bh, X2Int<(NW == 8 ? 2 : 3)>{}, X2Int<(NW == 8 ? 1 : 3)>{});
+            X2_LANDED(Am, 8);
+            product(Am, Bh, X2Int<3>{}, X2Int<3>{});
             X2_LANDED(Bm, 0);
             if (do_b) { bias_read(dl[0], dh[0], X2Int<0>{}, 0); bias_read(dl[1], dh[1], X2Int<1>{}, 0); }
-            product(Ah, Bm, X2Int<(NW == 8 ? 3 : 6)>{}, X2Int<(NW == 8 ? 1 : 2)>{});
+            product(Ah, Bm, X2Int<6>{}, X2Int<2>{});
             if (do_b) {
                 bias_mfma(dl[0], dh[0], dacc, 0); bias_mfma(dl[1], dh[1], dacc, 0);
                 if (two_b) {  // one h block: the wave's second tile (column 1 of the selector product), H <= 256 only
@@ -770,16 +739,13 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
             XW2_LOAD_ENT4(ent, ep, "");
 #pragma unroll
             for (int n = 0; n < ND; ++n) {
-                const int p = NW == 8 ? (wave & 1) : n >> 2, i = n & 3;
-                const __amdgpu_buffer_rsrc_t r = x2_piece_rsrc(pbase[p], ent[i], gbytes, IMM ? 1024 * i : 0);
-                if (IMM) {
-                    if (i == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_vptr)(s_ring + otile * XW2_TILE + st * XW2_STAGE + p * XW2_PLANE), 16, soff[i], 0, 0, 0);
-                    if (i == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_vptr)(s_ring + otile * XW2_TILE + st * XW2_STAGE + p * XW2_PLANE), 16, soff[i], 0, 1024, 0);
-                    if (i == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_vptr)(s_ring + otile * XW2_TILE + st * XW2_STAGE + p * XW2_PLANE), 16, soff[i], 0, 2048, 0);
-                    if (i == 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_vptr)(s_ring + otile * XW2_TILE + st * XW2_STAGE + p * XW2_PLANE), 16, soff[i], 0, 3072, 0);
-                } else
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_vptr)(s_ring + otile * XW2_TILE + st * XW2_STAGE + p * XW2_PLANE + 1024 * i),
-                                                         16, soff[i], 0, 0, 0);
+                const int p = n >> 2, i = n & 3;
+                const __amdgpu_buffer_rsrc_t r = x2_piece_rsrc(pbase[p], ent[i], gbytes, 1024 * i);
+                lds_vptr d = (lds_vptr)(s_ring + otile * XW2_TILE + st * XW2_STAGE + p * XW2_PLANE);
+                if (i == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d, 16, soff[i], 0, 0, 0);
+                if (i == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d, 16, soff[i], 0, 1024, 0);
+                if (i == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d, 16, soff[i], 0, 2048, 0);
+                if (i == 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d, 16, soff[i], 0, 3072, 0);
             }
         };
 
@@ -881,10 +847,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
 // reads, the three products, db on the matrix pipe (whole h blocks 0 and 1 only), soft lockstep, slab epilogue — is k_dw_x2<4>'s,
 // statement for statement, its walk of the live k-step list (X3Args::ks_list, one pipeline run per split) included.
 // ---------------------------------------------------------------------------------------
-#ifndef X2_DW_MIXED
-#define X2_DW_MIXED 1  // 0 (diagnostic builds): k_dw_x2<4, true> everywhere, round 5's form — the A/B partner of k_dw_x2m
-#endif
-int x2_dw_mixed_ok(int H, int V) { return X2_DW_MIXED && H % 256 == 128 && H >= 640 && V % 512 == 0; }
+int x2_dw_mixed_ok(int H, int V) { return H % 256 == 128 && H >= 640 && V % 512 == 0; }
 int x2_dw_tiles(int H, int V) { return x2_dw_mixed_ok(H, V) ? (V / 256) * (H / 256) + V / 512 : ((V + 255) / 256) * ((H + 255) / 256); }
 
 __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
@@ -1156,34 +1119,11 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
     else body(X2Int<0>{});
 }
 
-#ifdef RNNT_LAB
-#include "lab/x2_lab_dw.inc"  // k_dw_x2p (RNNT_VARIANT_X2_DW_P16): measured equal to k_dw_x2<4>, kept as lab equipment
-#endif
-
-// the dW kernel launch_dw_x2 picks for this call walks k_dw_table's 32-cell ranges, not the live k-step list (the lab's k_dw_x2p only):
-// k_x2_dead_rows then zeroes every row of the tiles k_dhidden_x2 does not run (X3Args::zero_all)
-bool x2_dw_walks_table(int H, int V, int flags)
-{
-    (void)H; (void)V; (void)flags;
-#ifdef RNNT_LAB
-    if (flags & RNNT_VARIANT_X2_DW_P16) return true;
-#endif
-    return false;
-}
-
 // the dW kernel launch_dw_x2 picks for this call walks the 16-cell k-step list (k_dw_x2m), not the group list: k_x2_dead_rows walks it too
-bool x2_dw_walks_ksteps(int H, int V, int flags)
-{
-    (void)flags;
-#ifdef RNNT_LAB
-    if (flags & (RNNT_VARIANT_X2_DW_P16 | RNNT_VARIANT_X2_DW_8W)) return false;
-#endif
-    return x2_dw_mixed_ok(H, V) != 0;
-}
+bool x2_dw_walks_ksteps(int H, int V) { return x2_dw_mixed_ok(H, V) != 0; }
 
-void launch_dw_x2(const X3Args &a, hipStream_t st, bool build_table, bool zero_prog)
+void launch_dw_x2(const X3Args &a, hipStream_t st, bool zero_prog)
 {
-    if (build_table && x2_dw_walks_table(a.H, a.V, a.flags)) launch_dw_table(a.logit_lens, a.B, a.T, a.U1, XW2_GRAN, a.dw_tab, st);
     if (a.dw_prog && zero_prog) launch_fill32(a.dw_prog, 0u, (size_t)a.n_split * 64, st);
     const int tiles = x2_dw_tiles(a.H, a.V);
     static bool attr_set[16] = {false};  // > 64 KiB of dynamic LDS: opt-in once per device (read-mostly fact)
@@ -1191,18 +1131,10 @@ void launch_dw_x2(const X3Args &a, hipStream_t st, bool build_table, bool zero_p
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;
     if (dev < 0 || !attr_set[dev]) {
         (void)hipFuncSetAttribute((const void *)k_dw_x2<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * XW2_TILE);
-#ifdef RNNT_LAB
-        (void)hipFuncSetAttribute((const void *)k_dw_x2<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * XW2_TILE);
-        (void)hipFuncSetAttribute((const void *)k_dw_x2p, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * XW2_TILE);
-#endif
         (void)hipFuncSetAttribute((const void *)k_dw_x2<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * XW2_TILE);
         (void)hipFuncSetAttribute((const void *)k_dw_x2m, hipFuncAttributeMaxDynamicSharedMemorySize, 5 * XW2_TILE);
         if (dev >= 0) attr_set[dev] = true;
     }
-#ifdef RNNT_LAB  // (the product build refuses these variants at the C boundary: engine.hip)
-    if (a.flags & RNNT_VARIANT_X2_DW_P16) { hipLaunchKernelGGL(k_dw_x2p, dim3(tiles * a.n_split), dim3(256), 4 * XW2_TILE, st, a); return; }
-    if (a.flags & RNNT_VARIANT_X2_DW_8W) { hipLaunchKernelGGL(k_dw_x2<8>, dim3(tiles * a.n_split), dim3(512), 4 * XW2_TILE, st, a); return; }
-#endif
     // H % 256 == 128: whole-block tiles + tall tiles over the odd block (k_dw_x2m) where the shape allows; else the half-empty last h block
     if (x2_dw_mixed_ok(a.H, a.V)) hipLaunchKernelGGL(k_dw_x2m, dim3(tiles * a.n_split), dim3(256), 5 * XW2_TILE, st, a);
     else if (a.H % 256 != 0) hipLaunchKernelGGL((k_dw_x2<4, true>), dim3(((a.V + 255) / 256) * ((a.H + 255) / 256) * a.n_split), dim3(256), 4 * XW2_TILE, st, a);
@@ -1272,13 +1204,6 @@ static_assert(XG2_BT == XG2_BT_ && XG2_BU == XG2_BU_, "dHidden tile");
 #define XG2_WSLOT 32768   // one k-step of W: 2 planes x 16 tiles x 1 KiB
 #define XG2_XSLOT 8192    // one k-step of G fragments: 4 M tiles x 2 planes x 1 KiB
 #define XG2_NW 3          // W ring slots: the DMAs of k-step c+2 are issued during k-step c (as in k_joint_fwd_x2)
-// -DXG2_EXP=bits (what-if builds of k_dhidden_x2, WRONG results; tools/build_x2_variants.sh with X2_FLAGS=-DXG2_EXP=..): 1 no MFMAs, 2 W's DMAs
-// requested past the pack's range (instructions stay, no bytes move), 4 no production arithmetic (the raw bits go to the exchange), 8 the line
-// stores aimed past the buffer's range (dropped), 16 the raw logits loads aimed at the zero padding row (cache-resident), 32 no fragment reads,
-// 64 no barrier
-#ifndef XG2_EXP
-#define XG2_EXP 0
-#endif
 // PART: the pass covers fewer than 512 columns (H = 640: the second pass has 128; H < 512): the dead 128-column groups run no MFMAs
 // and their W pieces are requested past the pack's range (an out-of-range LDS-DMA moves no bytes and writes zeros: the instruction
 // stays, so every vmcnt stays a count) — a pass then costs what its live columns cost plus the G stream.
@@ -1327,7 +1252,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
     //   G hi: 16 bytes at row + 128(c>>1) + 32(c&1) + 16half        (u32x4 index 8(c>>1) + 2(c&1) + half);  G mid: + 64 bytes
     // rows outside the lattice read the zero padding row (finite) with c1 = -inf -> G = 0; FIRST = false: every existing row
     // holds its G planes already
-    const float *xsrc = a.logits + ((XG2_EXP & 16) ? zrow : ((FIRST ? live : pexists) ? pcell : zrow)) * V;
+    const float *xsrc = a.logits + ((FIRST ? live : pexists) ? pcell : zrow) * V;
     const int blank = a.blank;
     // whole-line stores (k_dhidden_x3, round 4): lane L -> row 8n + (L >> 3) of the M tile (n = 0..3: four store instructions,
     // 8 whole lines each), piece L & 7 = (plane, k-step parity, half), read back from this wave's part of the exchange (both
@@ -1345,7 +1270,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
     for (int n = 0; n < 4; ++n) {
         const int lt = 2 * wave + (n >> 1), lu = 8 * (n & 1) + lrow;
         const bool ex = t0 + lt < T && u0 + lu < U1;
-        lvo[n] = (ex && !(XG2_EXP & 8)) ? (int)(((long)lt * U1 + lu) * V * 4) + 64 * (lpiece >> 2) + 16 * (lpiece & 3) : 0x7ffffff0;
+        lvo[n] = ex ? (int)(((long)lt * U1 + lu) * V * 4) + 64 * (lpiece >> 2) + 16 * (lpiece & 3) : 0x7ffffff0;
     }
 
     f32x16 acc[2][8];
@@ -1369,13 +1294,8 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
         const int cc = c < VC ? c : VC - 1;
         if (FIRST) {
             const f32x4 *p = (const f32x4 *)xsrc + 4 * cc + 2 * half;
-            if (X2_NT & 1) {  // experiment: the logits are read once, by this CU only -> non-temporal loads
-                if (part & 1) r.x0 = __builtin_nontemporal_load(p);
-                if (part & 2) r.x1 = __builtin_nontemporal_load(p + 1);
-            } else {
-                if (part & 1) r.x0 = p[0];
-                if (part & 2) r.x1 = p[1];
-            }
+            if (part & 1) r.x0 = p[0];
+            if (part & 2) r.x1 = p[1];
         } else {
             const u32x4 *p = (const u32x4 *)xsrc + 8 * (cc >> 1) + 2 * (cc & 1) + half;
             if (part & 1) r.x0 = __builtin_bit_cast(f32x4, p[0]);
@@ -1386,7 +1306,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
     // threads through the gaps of its first MFMA blocks.
     struct Prod { f32x4 g0, g1; u32x4 ph, pm; };
     auto produce_slice = [&](Prod &P, const Raw &r, int c, int sl) {
-        if (!FIRST || (XG2_EXP & 4)) {
+        if (!FIRST) {
             if (sl == 0) { P.ph = __builtin_bit_cast(u32x4, r.x0); P.pm = __builtin_bit_cast(u32x4, r.x1); }
         } else if (sl < 4) {
             P.g0[sl] = __builtin_amdgcn_exp2f(fmaf(r.x0[sl], RNNT_LOG2E, cf.c1));
@@ -1430,8 +1350,8 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
     };
     auto wdma = [&](int c, int slot, int n) {  // piece n (0..7) of this wave's share of W k-step c -> ring slot `slot`
         const int cc = c < VC ? c : VC - 1;
-        const int vo = (!(XG2_EXP & 2) && (!PART || (((wave * 8 + n) & 15) >> 2) < ngrp)) ? wvo : 0x7ffffff0;  // (piece = plane (pc >> 4), tile pc & 15 = group (pc & 15) >> 2)
-#if XF2_IMM  // pieces 4g .. 4g+3 on one LDS base (M0) and one scalar offset, told apart by the immediate offset (as the forward's)
+        const int vo = (!PART || (((wave * 8 + n) & 15) >> 2) < ngrp) ? wvo : 0x7ffffff0;  // (piece = plane (pc >> 4), tile pc & 15 = group (pc & 15) >> 2)
+        // pieces 4g .. 4g+3 on one LDS base (M0) and one scalar offset, told apart by the immediate offset (as the forward's)
         const int g4 = n & 4;
         lds_vptr dst = (lds_vptr)(s_dh + slot * XG2_WSLOT + (wave * 8 + g4) * 1024);
         const int so = (cc * 32 + wave * 8 + g4) * 1024;
@@ -1439,10 +1359,6 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
         if ((n & 3) == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, dst, 16, vo, so, 1024, 0);
         if ((n & 3) == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, dst, 16, vo, so, 2048, 0);
         if ((n & 3) == 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, dst, 16, vo, so, 3072, 0);
-#else
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_vptr)(s_dh + slot * XG2_WSLOT + (wave * 8 + n) * 1024), 16, vo,
-                                                 (cc * 32 + wave * 8 + n) * 1024, 0, 0);
-#endif
     };
 
     Raw xr[4];  // raw ring (slot = k-step & 3), 4 k-steps ahead of production
@@ -1467,12 +1383,11 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
             // k-steps, both loaded and consumed (production) before the store is issued.
             if (FIRST) asm volatile(RNNT_VMCNT(16) ::: "memory");
             else asm volatile(RNNT_VMCNT(12) ::: "memory");
-            if (!(XG2_EXP & 64)) x2_lds_barrier();
+            x2_lds_barrier();
             const int ws = wb + wsl * XG2_WSLOT, xs = xa + (j & 1) * XG2_XSLOT;
             const int wsn = wsl == 0 ? 2 : wsl - 1;  // (c + 2) % 3
             u32x4 af[2][2], bf[8], bn[8];
             // fragment reads: A (4) and the hi plane of W (8)
-            if (!(XG2_EXP & 32)) {
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -1480,7 +1395,6 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
                     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(af[mt][p]) : "v"(xs), "n"(mt * 2048 + p * 1024));
 #pragma unroll
             for (int q = 0; q < 8; ++q) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bf[q]) : "v"(ws), "n"(q * 1024));
-            }
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(af[0][0]), "+v"(af[0][1]), "+v"(af[1][0]), "+v"(af[1][1]),
                            "+v"(bf[0]), "+v"(bf[1]), "+v"(bf[2]), "+v"(bf[3]), "+v"(bf[4]), "+v"(bf[5]), "+v"(bf[6]), "+v"(bf[7])
@@ -1506,12 +1420,12 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
                 constexpr int PA = decltype(pa_c)::value, BLK = decltype(blk_c)::value;
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
-                    if (!(XG2_EXP & 1) && (!PART || 2 * wn + (q >> 2) < ngrp)) {  // (wave-uniform)
+                    if (!PART || 2 * wn + (q >> 2) < ngrp) {  // (wave-uniform)
                         acc[0][q] = x2_mfma(af[0][PA], bcur[q], acc[0][q]);
                         acc[1][q] = x2_mfma(af[1][PA], bcur[q], acc[1][q]);
                     }
                     if (BLK == 0) {
-                        if (!(XG2_EXP & 32)) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bn[q]) : "v"(ws), "n"(16384 + q * 1024));
+                        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bn[q]) : "v"(ws), "n"(16384 + q * 1024));
                         if (prod_on) produce_slice(P, rawn, c + 1, q);
                     }
                     if (BLK == 1) {
@@ -1831,7 +1745,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2r(X3Args a, const int hp)
 // l >> 2, then the whole wave zeroes each flagged row, both planes = the V x 4 bytes of the logits row, 16 bytes per lane and store.  Most
 // rounds have no such row and cost two loads.  No LDS, 4 waves per workgroup: it runs beside anything.
 // X3Args::dw_ksteps (the call's dW kernel is k_dw_x2m, which reads all 16 rows of every live k-step): the same walk over ks_list, 4 entries
-// of 16 rows per round.  zero_all (the lab's table-walking dW kernel reads every row): every group that has a cell.
+// of 16 rows per round.
 // Rows of dead tiles and rows of live tiles are disjoint: the order against k_dhidden_x2 is free; both precede the dW kernel.
 // ---------------------------------------------------------------------------------------
 #define XZ2_WG_WAVES 4
@@ -1840,10 +1754,10 @@ __global__ __launch_bounds__(64 * XZ2_WG_WAVES) void k_x2_dead_rows(X3Args a, in
     const int lane = threadIdx.x & 63;
     const long wave = (long)blockIdx.x * XZ2_WG_WAVES + (threadIdx.x >> 6), nwave = (long)gridDim.x * XZ2_WG_WAVES;
     const long cells = (long)a.B * a.T * a.U1;
-    const bool by_ks = a.dw_ksteps && !a.zero_all;  // (kernel-uniform)
+    const bool by_ks = a.dw_ksteps;  // (kernel-uniform)
     const int sh = by_ks ? 4 : 2, per = 64 >> sh;   // rows per list entry = 1 << sh; entries per wave round
     const int *list = by_ks ? a.ks_list : a.grp_list;
-    const long n = a.zero_all ? a.live_stats[5] : a.live_stats[by_ks ? 0 : 4];
+    const long n = a.live_stats[by_ks ? 0 : 4];
     const int V4 = a.V / 4;
     const u32x4 z = {0u, 0u, 0u, 0u};
     for (long k = per * wave; k < n; k += per * nwave) {
@@ -1851,7 +1765,7 @@ __global__ __launch_bounds__(64 * XZ2_WG_WAVES) void k_x2_dead_rows(X3Args a, in
         int e = 0;  // (an entry fits an int: the lists' entries do)
         bool dead = false;
         if (kk < n) {
-            e = a.zero_all ? (int)kk : list[kk];
+            e = list[kk];
             const long c = ((long)e << sh) + (lane & ((1 << sh) - 1));
             if (c < cells) {
                 const int u = (int)(c % a.U1);
@@ -1901,7 +1815,7 @@ void launch_dhidden_x2(const X3Args &a, hipStream_t st)
     if (a.H < 512) hipLaunchKernelGGL((k_dhidden_x2<true, true>), grid, dim3(256), lds, st, a, 0);
     else hipLaunchKernelGGL((k_dhidden_x2<true, false>), grid, dim3(256), lds, st, a, 0);
     for (int hp = 1; hp * 512 < a.H; ++hp) {
-        if (a.H - 512 * hp == 128 && !(X2_NT & 4)) {  // the last 128 columns: a wave per 8 t x 16 u block, A fragments straight from G's planes
+        if (a.H - 512 * hp == 128) {  // the last 128 columns: a wave per 8 t x 16 u block, A fragments straight from G's planes
             dim3 gr(a.n_ublk16, ((a.T + XG2_BT - 1) / XG2_BT + 3) / 4, a.B);
             hipLaunchKernelGGL(k_dhidden_x2r, gr, dim3(256), XR2_NW * XR2_WSLOT, st, a, hp);
         }
@@ -2098,7 +2012,7 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
         const long ek = EP ? (long)T * 16 : 16, pk = EP ? (long)U1 * 16 : 16;  // floats from one k-step's operands to the next's
         // (rows past the lattice produce — and store, unconditionally — the last cell's row again: the same bits to the
         // same place; hipcc counts vmcnt exactly only through unconditional memory operations)
-        u32x4 *hdst = (u32x4 *)a.hidden + ((X2_EXP & 4) ? (long)(32 * wave + i) : pc_) * (H / 8) + half;  // + 2c: this lane's 16 bytes of k-step c; planes `ps` apart
+        u32x4 *hdst = (u32x4 *)a.hidden + pc_ * (H / 8) + half;  // + 2c: this lane's 16 bytes of k-step c; planes `ps` apart
         const long ps = a.plane_stride / 8;
         struct Opd { f32x4 e0, e1, p0, p1; };
         struct Prod { f2 w[4]; float ra, rb; u32x4 ph, pm; };
@@ -2107,15 +2021,7 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
         // DMAs issued behind these loads a k-step ago.  Spelling the loads as asm with a counted wait was tried and is WRONG: the
         // loaded registers are loop-carried, and the copies hipcc places on the loop's back edge read them before the data has
         // landed — intermittently different results at full size, tools/dbg_x2_loss.py.)
-        // PL (round 6): the operand of k index kcs is the PAIR OF PLANES this lane stored for it in the tile's first pass (its own 2 x 16 bytes,
-        // hdst[2 kcs] and the same slot of the second plane): two loads instead of four, and nothing to compute — see run_pass.
-        auto op_load1 = [&](Opd &o, int kcs, int k, auto planes_c) {  // one of the four (PL: two) 16-byte operand loads of k index kcs
-            if (decltype(planes_c)::value) {
-                if (k == 0) o.e0 = __builtin_bit_cast(f32x4, hdst[2 * kcs]);
-                else if (k == 1) o.e1 = __builtin_bit_cast(f32x4, hdst[2 * kcs + ps]);
-                return;
-            }
-            if (X2_EXP & 512) { const float c = (float)kcs * 0.01f; o.e0 = o.e1 = o.p0 = o.p1 = f32x4{c, -c, 0.5f * c, 0.25f}; return; }
+        auto op_load1 = [&](Opd &o, int kcs, int k) {  // one of the four 16-byte operand loads of k index kcs
             const float *e = ep + ek * kcs, *q = pp + pk * kcs;
             if (k == 0) o.e0 = *(const f32x4 *)e;
             else if (k == 1) o.e1 = *(const f32x4 *)(e + 4);
@@ -2125,16 +2031,12 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
         };
         auto op_load = [&](Opd &o, int kcs) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) op_load1(o, kcs, k, X2Int<0>{});
+            for (int k = 0; k < 4; ++k) op_load1(o, kcs, k);
         };
         // pieces 0-7: 2^14 tanh of the 4 pairs (fast_tanh2's arithmetic: exp2 half, reciprocal half); 8-15: the 2-way split
         // of each pair (hi + residuals, then mid); 16: the two ring writes
-        auto prod_piece = [&](Prod &P, const Opd &o, auto off_c, int k, auto planes_c) {  // off_c: byte offset of the target A slot in the ring
-            if (decltype(planes_c)::value && k < 16) {  // the operand IS the two planes: nothing to produce
-                if (k == 15) { P.ph = __builtin_bit_cast(u32x4, o.e0); P.pm = __builtin_bit_cast(u32x4, o.e1); }
-            } else if ((X2_EXP & 32) && k < 16) {
-                if (k == 0) { P.ph = __builtin_bit_cast(u32x4, o.e0 + o.e1); P.pm = __builtin_bit_cast(u32x4, o.p0 + o.p1); }
-            } else if (k < 8) {
+        auto prod_piece = [&](Prod &P, const Opd &o, auto off_c, int k) {  // off_c: byte offset of the target A slot in the ring
+            if (k < 8) {
                 const int j = k >> 1;
                 const f32x4 &e = j < 2 ? o.e0 : o.e1, &pv = j < 2 ? o.p0 : o.p1;
                 const int q = 2 * (j & 1);
@@ -2174,19 +2076,13 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
         auto hid_store = [&](const Prod &P, int kcs) { hdst[2 * kcs] = P.ph; hdst[2 * kcs + ps] = P.pm; };
         // piece n (0..7) of this wave's share of W k-step cs -> ring slot `slot`
         auto wdma = [&](int cs, int slot, int n) {  // raw-buffer form: scalar base and offsets, one constant per-lane offset register
-            if (X2_EXP & 1024) return;
-#if XF2_IMM
             // pieces n = 4g .. 4g+3 share one LDS base (M0) and one scalar offset: the instruction's 12-bit immediate offset advances the
             // memory address AND the LDS address (LDS_ADDR = M0 + inst_offset + lane x 16) — the pack and the ring slot are both linear in n
             const int g4 = n & 4;
-            if ((n & 3) == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_vptr)(s_fw + slot * XF2_WSLOT + (wave * 8 + g4) * 1024), 16, wvo, (X2_EXP & 2) ? 0x7ff00000 : (cs * 32 + wave * 8 + g4) * 1024, 0, 0);
-            if ((n & 3) == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_vptr)(s_fw + slot * XF2_WSLOT + (wave * 8 + g4) * 1024), 16, wvo, (X2_EXP & 2) ? 0x7ff00000 : (cs * 32 + wave * 8 + g4) * 1024, 1024, 0);
-            if ((n & 3) == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_vptr)(s_fw + slot * XF2_WSLOT + (wave * 8 + g4) * 1024), 16, wvo, (X2_EXP & 2) ? 0x7ff00000 : (cs * 32 + wave * 8 + g4) * 1024, 2048, 0);
-            if ((n & 3) == 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_vptr)(s_fw + slot * XF2_WSLOT + (wave * 8 + g4) * 1024), 16, wvo, (X2_EXP & 2) ? 0x7ff00000 : (cs * 32 + wave * 8 + g4) * 1024, 3072, 0);
-#else
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_vptr)(s_fw + slot * XF2_WSLOT + (wave * 8 + n) * 1024), 16, wvo,
-                                                     (X2_EXP & 2) ? 0x7ff00000 : (cs * 32 + wave * 8 + n) * 1024, 0, 0);
-#endif
+            if ((n & 3) == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_vptr)(s_fw + slot * XF2_WSLOT + (wave * 8 + g4) * 1024), 16, wvo, (cs * 32 + wave * 8 + g4) * 1024, 0, 0);
+            if ((n & 3) == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_vptr)(s_fw + slot * XF2_WSLOT + (wave * 8 + g4) * 1024), 16, wvo, (cs * 32 + wave * 8 + g4) * 1024, 1024, 0);
+            if ((n & 3) == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_vptr)(s_fw + slot * XF2_WSLOT + (wave * 8 + g4) * 1024), 16, wvo, (cs * 32 + wave * 8 + g4) * 1024, 2048, 0);
+            if ((n & 3) == 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_vptr)(s_fw + slot * XF2_WSLOT + (wave * 8 + g4) * 1024), 16, wvo, (cs * 32 + wave * 8 + g4) * 1024, 3072, 0);
         };
 
         if (dead) {  // hidden rows only (finite values for k_dw_x2), no products
@@ -2194,7 +2090,7 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
                 Opd o; Prod P;
                 op_load(o, kc);
 #pragma unroll
-                for (int pc = 0; pc < 16; ++pc) prod_piece(P, o, X2Int<0>{}, pc, X2Int<0>{});
+                for (int pc = 0; pc < 16; ++pc) prod_piece(P, o, X2Int<0>{}, pc);
                 hid_store(P, kc);
             }
             tile = next;
@@ -2219,11 +2115,6 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
         // read n (0..11) of a k-step's fragments: 0-3 the A fragments (slot at byte offset xs_c of the A ring), 4-11 W's hi plane (slot `wslot`)
         auto frag_read1 = [&](Frag &f, auto xs_c, const int wslot, const int n) {  // (n: a constant once the caller's loop is unrolled)
             const int xs = xa, ws = wb + wslot * XF2_WSLOT;
-            if (X2_EXP & 2048) {
-                if (n >= 4) f.bf[n - 4] = u32x4{(unsigned)xs, (unsigned)ws, 0x3c003c00u, (unsigned)n};
-                else f.af[n >> 1][n & 1] = u32x4{(unsigned)xs, (unsigned)ws, 0x3c003c00u, (unsigned)n};
-                return;
-            }
             if (n < 4) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f.af[(n >> 1) & 1][n & 1]) : "v"(xs), "n"(decltype(xs_c)::value + ((n >> 1) & 1) * 2048 + (n & 1) * 1024));
             else asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f.bf[n >= 4 ? n - 4 : 0]) : "v"(ws), "n"((n >= 4 ? n - 4 : 0) * 1024));
         };
@@ -2250,7 +2141,7 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
             op_load(oset[1], KC > 1 ? 1 : 0);
             op_load(o, 0);
 #pragma unroll
-            for (int pc = 0; pc < 17; ++pc) prod_piece(P, o, X2Int<0>{}, pc, X2Int<0>{});
+            for (int pc = 0; pc < 17; ++pc) prod_piece(P, o, X2Int<0>{}, pc);
             if (!LIN) hid_store(P, 0);  // (the plain GEMM stores nothing beside Y: X3Args::hidden is null there)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // W of k-steps 0-2 (this wave's share), operands, the stores
             x2_lds_barrier();                                 // ... of every wave; A slot 0 written
@@ -2275,11 +2166,8 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
           //   block 2  ah.bm  + the 12 fragment reads of k-step cs+1 (into the other register set) + the 8 DMAs of W(cs+3) into
           //            the slot W(cs) just left (three slots, filled THREE k-steps ahead) + (first pass) the 2 hidden stores
           // PAR = the k-step's parity = its A ring slot and fragment register set (KC is even: cs and kc have the same parity).
-          // OCP: the operands of k-step cs+1 (requested during the previous k-step) are its stored planes; ONP: this k-step requests the
-          // planes of k-step cs+2 (round 6, below)
-          auto kstep = [&](auto par_c, const int kc, auto ocp_c, auto onp_c) {
+          auto kstep = [&](auto par_c, const int kc) {
             constexpr int par = decltype(par_c)::value;
-            constexpr bool OCP = decltype(ocp_c)::value != 0, ONP = decltype(onp_c)::value != 0;
             constexpr int XN = (1 - par) * XF2_ASLOT;
             Frag &fc = fr[par], &fn = fr[1 - par];
             const int ws = wb + wsl * XF2_WSLOT;  // (the W slot is a run-time third: one v_add per k-step)
@@ -2296,18 +2184,16 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
                 constexpr int PA = decltype(pa_c)::value, BLK = decltype(blk_c)::value;
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
-                    if (!(X2_EXP & 128)) {
-                        acc[0][q] = x2_mfma(fc.af[0][PA], bcur[q], acc[0][q]);
-                        acc[1][q] = x2_mfma(fc.af[1][PA], bcur[q], acc[1][q]);
-                    }
+                    acc[0][q] = x2_mfma(fc.af[0][PA], bcur[q], acc[0][q]);
+                    acc[1][q] = x2_mfma(fc.af[1][PA], bcur[q], acc[1][q]);
                     if (BLK == 0) {
-                        if (!(X2_EXP & 2048)) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bn[q]) : "v"(ws), "n"(16384 + q * 1024));
-                        prod_piece(P, ocur, X2Int<XN>{}, q, X2Int<OCP>{});
+                        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bn[q]) : "v"(ws), "n"(16384 + q * 1024));
+                        prod_piece(P, ocur, X2Int<XN>{}, q);
                     }
                     if (BLK == 1) {
-                        if (q < ((LIN || ONP) ? 2 : 4)) op_load1(onext, kcnn, q, X2Int<ONP>{});  // operands of k-step cs+2 (needed a whole k-step from now): in FRONT of the k-step's DMAs
-                        if (q < 4) { prod_piece(P, ocur, X2Int<XN>{}, 8 + 2 * q, X2Int<OCP>{}); prod_piece(P, ocur, X2Int<XN>{}, 9 + 2 * q, X2Int<OCP>{}); }
-                        if (q == 4) prod_piece(P, ocur, X2Int<XN>{}, 16, X2Int<OCP>{});  // the ring writes: done well before the barrier's lgkmcnt(0)
+                        if (q < (LIN ? 2 : 4)) op_load1(onext, kcnn, q);  // operands of k-step cs+2 (needed a whole k-step from now): in FRONT of the k-step's DMAs
+                        if (q < 4) { prod_piece(P, ocur, X2Int<XN>{}, 8 + 2 * q); prod_piece(P, ocur, X2Int<XN>{}, 9 + 2 * q); }
+                        if (q == 4) prod_piece(P, ocur, X2Int<XN>{}, 16);  // the ring writes: done well before the barrier's lgkmcnt(0)
                     }
                     if (BLK == 2) {  // nothing of the k-step is issued outside an MFMA's shadow: the 12 fragment reads of k-step cs+1, the 8 DMAs, the 2 stores
                         if (q < 4) { frag_read1(fn, X2Int<XN>{}, wsn, 2 * q); frag_read1(fn, X2Int<XN>{}, wsn, 2 * q + 1); }
@@ -2327,18 +2213,15 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
             // them came (first pass) 2 hidden stores, k-step cs-1's 4 operand loads, 8 DMAs and (first pass) 2 stores, and this
             // k-step's 4 operand loads.  The first two k-steps of a pass: their W(cs+1) was waited for before the previous pass's
             // logits stores (pass end below) / with the tile prologue.
-            // (round 6: a k-step whose operands are stored planes issues 2 loads, not 4: previous k-step's loads = OCP ? 2 : 4, this one's
-            // = ONP ? 2 : 4)
             if (kc >= 2) {
-                constexpr int NV = LIN ? 12 : (STORE ? 4 : 0) + (OCP ? 2 : 4) + 8 + (ONP ? 2 : 4);
-                static_assert(NV == 12 || NV == 16 || NV == 18 || NV == 20, "counted vmcnt of the forward's k-step");
-                if (NV == 12) asm volatile(RNNT_VMCNT(12) ::: "memory");  // (LIN: 2 operand loads per k-step: 2 + 8 + 2; planes: the same)
+                constexpr int NV = LIN ? 12 : (STORE ? 4 : 0) + 4 + 8 + 4;
+                static_assert(NV == 12 || NV == 16 || NV == 20, "counted vmcnt of the forward's k-step");
+                if (NV == 12) asm volatile(RNNT_VMCNT(12) ::: "memory");  // (LIN: 2 operand loads per k-step: 2 + 8 + 2)
                 else if (NV == 16) asm volatile(RNNT_VMCNT(16) ::: "memory");
-                else if (NV == 18) asm volatile(RNNT_VMCNT(18) ::: "memory");
                 else asm volatile(RNNT_VMCNT(20) ::: "memory");
             }
             X2STAMP(3);
-            if (!(X2_EXP & 4096)) x2_lds_barrier();  // (lgkmcnt(0): bn and the ring writes) publishes A(cs+1), W(cs+1); frees W(cs)'s slot
+            x2_lds_barrier();  // (lgkmcnt(0): bn and the ring writes) publishes A(cs+1), W(cs+1); frees W(cs)'s slot
             X2STAMP(4);
             asm volatile("" : "+v"(bn[0]), "+v"(bn[1]), "+v"(bn[2]), "+v"(bn[3]), "+v"(bn[4]), "+v"(bn[5]), "+v"(bn[6]), "+v"(bn[7]));
             block(X2Int<0>{}, bn, X2Int<2>{});   // ah.bm  (the hidden stores: the youngest memory operations of the k-step; the pass's last k-step re-stores k-step 0)
@@ -2348,21 +2231,7 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
             ++cs;
             wsl = wsn;
           };
-          // Round 6: only a tile's FIRST pass produces the hidden values.  It stores them as two fp16 planes for k_dw_x2 anyway, and every
-          // lane stores exactly the 2 x 16 bytes it later needs as its A-ring slot — so the passes after the first load those back (the
-          // lane's own stores, a whole pass old: landed; no other workgroup touches the rows) instead of loading E and P and running the
-          // fma / rcp / fma / split arithmetic again: 2 operand loads per k-step instead of 4 and no production VALU in V/512 - 1 of the
-          // V/512 passes (config 2: one of two; config 5: 31 of 32).  Operands are requested two k-steps ahead, so the first pass's last two
-          // k-steps already request planes (of the next pass's k-steps 0 and 1), and its last one copies where it used to produce.
-          if constexpr (LIN || !X2_REREAD) {
-              for (int kc0 = 0; kc0 < KC; kc0 += 2) { kstep(X2Int<0>{}, kc0, X2Int<0>{}, X2Int<0>{}); kstep(X2Int<1>{}, kc0 + 1, X2Int<0>{}, X2Int<0>{}); }
-          } else if constexpr (STORE) {
-              for (int kc0 = 0; kc0 < KC - 2; kc0 += 2) { kstep(X2Int<0>{}, kc0, X2Int<0>{}, X2Int<0>{}); kstep(X2Int<1>{}, kc0 + 1, X2Int<0>{}, X2Int<0>{}); }
-              kstep(X2Int<0>{}, KC - 2, X2Int<0>{}, X2Int<1>{});
-              kstep(X2Int<1>{}, KC - 1, X2Int<1>{}, X2Int<1>{});
-          } else {
-              for (int kc0 = 0; kc0 < KC; kc0 += 2) { kstep(X2Int<0>{}, kc0, X2Int<1>{}, X2Int<1>{}); kstep(X2Int<1>{}, kc0 + 1, X2Int<1>{}, X2Int<1>{}); }
-          }
+          for (int kc0 = 0; kc0 < KC; kc0 += 2) { kstep(X2Int<0>{}, kc0); kstep(X2Int<1>{}, kc0 + 1); }
           // pass complete: unscale, add the bias, store the logits, update the statistics.  V % 128 == 0: a lane's two 4-column
           // groups exist or not for the whole wave.  The row loop is ONE basic block per case; the store address is a scalar
           // row pointer + one 32-bit per-lane offset.
@@ -2373,7 +2242,7 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
           {
             const int cw = 512 * pass + 256 * wn;
             const unsigned lane_off = (unsigned)(((4 * half) * V + 4 * i) * 4);
-            char *tile_base = (char *)(a.logits + ((X2_EXP & 8) ? 0L : row0) * V + cw);
+            char *tile_base = (char *)(a.logits + row0 * V + cw);
             const bool has_b = !LIN || a.bias != nullptr;
             const f32x4 b0 = has_b && cw + 4 * i < V ? *(const f32x4 *)(a.bias + cw + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
             const f32x4 b1 = has_b && cw + 128 + 4 * i < V ? *(const f32x4 *)(a.bias + cw + 128 + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -2400,16 +2269,8 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
                         }
                         return;
                     }
-                    if (X2_EXP & 256) {
-                        asm volatile("" :: "v"(o0), "v"(o1));
-                    } else if (X2_EXP & 16) {
-                        *(f32x4 *)(rowp + lane_off) = o0;
-                        if (BOTH) *(f32x4 *)(rowp + lane_off + 512) = o1;
-                    } else {
-                        __builtin_nontemporal_store(o0, (f32x4 *)(rowp + lane_off));
-                        if (BOTH) __builtin_nontemporal_store(o1, (f32x4 *)(rowp + lane_off + 512));
-                    }
-                    if (X2_EXP & 64) return;
+                    __builtin_nontemporal_store(o0, (f32x4 *)(rowp + lane_off));
+                    if (BOTH) __builtin_nontemporal_store(o1, (f32x4 *)(rowp + lane_off + 512));
                     float m8 = fmaxf(fmaxf(o0[0], o0[1]), fmaxf(o0[2], o0[3]));
                     if (BOTH) m8 = fmaxf(m8, fmaxf(fmaxf(o1[0], o1[1]), fmaxf(o1[2], o1[3])));
                     const float M = half_max_dpp(m8, half);
@@ -2518,10 +2379,6 @@ void launch_joint_fwd_x2(const X3Args &a, hipStream_t st)
     hipLaunchKernelGGL(k_joint_fwd_x2<0>, dim3((unsigned)nwg), dim3(256), lds, st, a, ntiles);
 }
 
-#ifdef RNNT_LAB
-#include "lab/x2_lab_fwd.inc"  // k_joint_fwd_x2d (RNNT_VARIANT_X2_FWD_2WG): measured equal to k_joint_fwd_x2, kept as lab equipment
-#endif
-
 void launch_x2_pack_w(const X3Args &a, float *scales, hipStream_t st)
 {
     hipLaunchKernelGGL(k_x2_wscale, dim3(1), dim3(1024), 0, st, a.W, (long)a.V * a.H / 4, scales);
@@ -2541,7 +2398,7 @@ void launch_x2_pack_w(const X3Args &a, float *scales, hipStream_t st)
 //                                                   32-column chunk), x as the "hidden" operand (two separate planes), K = the M rows
 // Operand scales (powers of two) come from the data's largest magnitude, found on the device every call (k_x2_absmax + k_x2_lin_scales);
 // the packs / planes are scaled when they are made and the outputs unscaled where they are written.  K % 128 == 0, N % 128 == 0.
-// Workspace (caller-owned, rnnt_engine_linear_x2_workspace_bytes): 512 B of scale / counter / table words, then the forward's W pack
+// Workspace (caller-owned, rnnt_engine_linear_x2_workspace_bytes): 512 B of scale / counter words, then the forward's W pack
 // (forward) or W^T, its pack, dy's and x's planes and the dW split-K slabs (backward).
 // ---------------------------------------------------------------------------------------
 // largest magnitudes of up to three row-major matrices in ONE launch: grid (256, n), workgroup (b, t) leaves the maximum of its share of
@@ -2575,10 +2432,10 @@ __global__ __launch_bounds__(256) void k_x2_absmax(X2AbsArgs a, float *__restric
     if (threadIdx.x == 0) partial[t * 256 + blockIdx.x] = any_bad ? __uint_as_float(0x7fc00000u) : fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
 }
 // one workgroup of 256: scales[2i] = 2^(14 - ceil(log2 max_i)), scales[2i + 1] = its reciprocal (1 for an all-zero operand; NaN for an operand with a NaN or an infinity in it),
-// i = 0 .. n-1, from the partial maxima; the call's counter words zeroed (the forward's tile counter; dW's progress words) and dW's table written
-// (k_dw_table's format, B = 1, every granule live) — what four more launches did before
+// i = 0 .. n-1, from the partial maxima; the call's counter words zeroed (the forward's tile counter; dW's progress words) and dW's lists written
+// (nks 16-row k-steps, every one live) — what four more launches did before
 __global__ __launch_bounds__(256) void k_x2_lin_scales(const float *__restrict__ partial, float *__restrict__ scales, int n, unsigned *__restrict__ zero0,
-                                                       int nzero0, unsigned *__restrict__ zero1, int nzero1, long *__restrict__ tab, long ngran,
+                                                       int nzero0, unsigned *__restrict__ zero1, int nzero1, long nks,
                                                        int *__restrict__ list, int *__restrict__ stats, int *__restrict__ glist)
 {
     __shared__ float s_m[4];
@@ -2608,9 +2465,8 @@ __global__ __launch_bounds__(256) void k_x2_lin_scales(const float *__restrict__
     }
     for (int j = threadIdx.x; j < nzero0; j += 256) zero0[j] = 0u;
     for (int j = threadIdx.x; j < nzero1; j += 256) zero1[j] = 0u;
-    if (tab && threadIdx.x == 0) { tab[0] = 0; tab[1] = ngran; tab[2] = 0; tab[3] = ngran; }
     if (list) {  // the dW kernels' lists (launch_x2_live's format): every 16-row k-step (k_dw_x2m) and every 4-row group (k_dw_x2), then the padding entries
-        const long nks = 2 * ngran, ngrp = 8 * ngran;
+        const long ngrp = 4 * nks;
         for (long j = threadIdx.x; j < nks + 8; j += 256) list[j] = (int)(j < nks ? j : nks);
         for (long j = threadIdx.x; j < ngrp + XL2_GPAD; j += 256) glist[j] = (int)(j < ngrp ? j : ngrp);
         if (threadIdx.x == 0) { stats[0] = (int)nks; stats[1] = (int)nks; stats[2] = 0; stats[3] = 0; stats[4] = (int)ngrp; stats[5] = (int)ngrp; }
@@ -2678,7 +2534,7 @@ LinWs lin_layout(int M, int K, int N, bool bwd)
 {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     LinWs L{};
-    size_t o = 4096;  // +0 scales[8], +128 tile counter, +192 the dW table (4 longs), +1024 the partial maxima [3][256]
+    size_t o = 4096;  // +0 scales[8], +128 tile counter, +1024 the partial maxima [3][256]
     if (!bwd) { L.pack = o; o += al(x2_wpack_fwd_bytes(K, N)); L.total = o; return L; }
     L.rows_pad = ((long)M + 1 + 31) / 32 * 32;
     L.rows_alloc = (L.rows_pad + 96 + 127) / 128 * 128;
@@ -2711,15 +2567,15 @@ int lin_cus()
     }
     return cus[dev];
 }
-// the operand scales of a call: one launch for the maxima of its n tensors, one for the scales (+ the counter words and dW's table)
+// the operand scales of a call: one launch for the maxima of its n tensors, one for the scales (+ the counter words and dW's lists)
 struct LinT { const float *x; long ld, rows; int cols; };
-void lin_scales(const LinT *t, int n, char *w, unsigned *zero1, int nzero1, long *tab, long ngran, int *list, int *glist, hipStream_t st)
+void lin_scales(const LinT *t, int n, char *w, unsigned *zero1, int nzero1, long nks, int *list, int *glist, hipStream_t st)
 {
     X2AbsArgs a{};
     for (int i = 0; i < n; ++i) { a.x[i] = t[i].x; a.ld[i] = t[i].ld; a.rows[i] = t[i].rows; a.cols4[i] = t[i].cols / 4; }
     float *partial = (float *)(w + 1024);
     hipLaunchKernelGGL(k_x2_absmax, dim3(256, n), dim3(256), 0, st, a, partial);
-    hipLaunchKernelGGL(k_x2_lin_scales, dim3(1), dim3(256), 0, st, partial, (float *)w, n, (unsigned *)(w + 128), 16, zero1, nzero1, tab, ngran,
+    hipLaunchKernelGGL(k_x2_lin_scales, dim3(1), dim3(256), 0, st, partial, (float *)w, n, (unsigned *)(w + 128), 16, zero1, nzero1, nks,
                        list ? list + 16 : nullptr, list, glist);
 }
 // y[M,N] = x[M,K] wmat[N,K]^T (+ bias) through k_joint_fwd_x2<2>; scales = {s_W, 1/s_W, s_X, 1/s_X} on the device, the pack made here
@@ -2745,7 +2601,7 @@ void launch_linear_x2_fwd(const float *x, long ldx, const float *W, const float 
     char *w = (char *)ws;
     float *scales = (float *)w;
     const LinT t[2] = {{W, K, N, K}, {x, ldx, M, K}};
-    lin_scales(t, 2, w, nullptr, 0, nullptr, 0, nullptr, nullptr, st);
+    lin_scales(t, 2, w, nullptr, 0, 0, nullptr, nullptr, st);
     lin_gemm_nt(x, ldx, W, bias, M, K, N, y, scales, w + L.pack, (unsigned *)(w + 128), st);
 }
 
@@ -2755,9 +2611,8 @@ void launch_linear_x2_bwd(const float *x, long ldx, const float *W, const float 
     const LinWs L = lin_layout(M, K, N, true);
     char *w = (char *)ws;
     float *scales = (float *)w;             // {s_W, 1/s_W, s_dy, 1/s_dy, s_x, 1/s_x}
-    long *tab = (long *)(w + 192);
     const LinT t[3] = {{W, K, N, K}, {dy, N, M, N}, {x, ldx, M, K}};
-    lin_scales(t, 3, w, (unsigned *)(w + L.prog), L.n_split * 16, tab, L.rows_pad / XW2_GRAN, (int *)(w + L.list), (int *)(w + L.glist), st);
+    lin_scales(t, 3, w, (unsigned *)(w + L.prog), L.n_split * 16, L.rows_pad / XW2_ROWS, (int *)(w + L.list), (int *)(w + L.glist), st);
     if (dx) {  // dx[M,K] = dy[M,N] (W^T)[K,N]^T
         float *wt = (float *)(w + L.wt);
         launch_copy_enc(W, 0, 1, K, wt, 1, K, N, st);  // wt[k][n] = W[n][k]
@@ -2775,10 +2630,10 @@ void launch_linear_x2_bwd(const float *x, long ldx, const float *W, const float 
     }
     X3Args a{};
     a.logits = pa; a.hidden = pb; a.plane_stride = L.rows_alloc * (long)K; a.rows_pad = L.rows_pad; a.rows_alloc = L.rows_alloc;
-    a.B = 1; a.T = 1; a.U1 = 1; a.H = K; a.V = N; a.n_split = L.n_split; a.dw_tab = tab; a.dw_prog = (int *)(w + L.prog);
+    a.B = 1; a.T = 1; a.U1 = 1; a.H = K; a.V = N; a.n_split = L.n_split; a.dw_prog = (int *)(w + L.prog);
     a.slab_w = (float *)(w + L.slab_w); a.slab_b = (float *)(w + L.slab_b); a.dw_rescale = 1.0f; a.db_rescale = 1.0f; a.n_cu = lin_cus();
     a.live_stats = (int *)(w + L.list); a.ks_list = a.live_stats + 16; a.grp_list = (int *)(w + L.glist);
-    launch_dw_x2(a, st, false, false);  // (no table / list kernels, no progress-word fill: all done by k_x2_lin_scales)
+    launch_dw_x2(a, st, false);  // (no list kernels, no progress-word fill: all done by k_x2_lin_scales)
     const long n4w = (long)N * K / 4, n4b = N / 4;
     hipLaunchKernelGGL(k_x2_reduce_scaled, dim3((unsigned)((n4w + 255) / 256)), dim3(256), 0, st, a.slab_w, dW, n4w, n4w, L.n_split,
                        (const float *)(scales + 3), (const float *)(scales + 5));

@@ -25,11 +25,6 @@
 // around long MFMA streams (96 MFMAs = 3072 matrix-pipe cycles per 16-deep k-step), like the fp32 route's.
 #include "kernels.hpp"
 
-// compile-time experiment switches (tools/build_x3_variants.sh: -DX3_EXP=bits); the shipped build has none set
-#ifndef X3_EXP
-#define X3_EXP 0
-#endif
-#define X3_OFF(bit) ((X3_EXP) & (bit))
 // Diagnostic build only (-DRNNT_STAMPS): workgroup 0 stamps the core clock counter and the 100 MHz reference at its start and
 // end into debug[SLOT..] (a buffer nothing else reads): the clock this launch ran at (tools/exp_x3_clock.py).
 #ifdef RNNT_STAMPS
@@ -320,7 +315,7 @@ __global__ __launch_bounds__(256, 1) void k_dw_x3(X3Args a)
                                                           (int)(XW_ROWS * rstride[p]), 0x00020000);
             auto dma_piece = [&](auto n_c) {  // piece n of stage ks+2 -> ring stage DST: plane n>>2, rows 4(n&3)..
                 constexpr int n = decltype(n_c)::value, p = n >> 2, i = n & 3;
-                if (RNNT_XP(a.flags, 8192) || X3_OFF(8) || (X3_OFF(8388608) && wave >= 2) || (X3_OFF(33554432) && p == 2)) return;  // 8388608: no hidden stream
+                if (RNNT_XP(a.flags, 8192)) return;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[p], (lds_vptr)(s_ring + wave * XW_TILE + DST * XW_STAGE + p * XW_PLANE + 1024 * i),
                                                          16, soff[p][i], 0, 0, 0);
             };
@@ -338,7 +333,6 @@ __global__ __launch_bounds__(256, 1) void k_dw_x3(X3Args a)
             // 16 MFMAs of one product with DMA pieces N0, N0+1 threaded through them
             auto product = [&](const X3Frag &fa_, const X3Frag &fb_, auto n0_c) {
                 constexpr int N0 = decltype(n0_c)::value;
-                constexpr bool DROP = X3_OFF(16777216) && (N0 == 4 || N0 == 8 || N0 == 10);  // what-if: 3 of the 6 products
                 u32x4 fa[4], fb[4];
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
@@ -347,22 +341,12 @@ __global__ __launch_bounds__(256, 1) void k_dw_x3(X3Args a)
                 }
 #pragma unroll
                 for (int qm = 0; qm < 4; ++qm) {
-                    if (!RNNT_XP(a.flags, 1024) && !DROP) {
+                    if (!RNNT_XP(a.flags, 1024)) {
 #pragma unroll
                         for (int qn = 0; qn < 4; ++qn) acc[qm][qn] = x3_mfma(fa[qm], fb[qn], acc[qm][qn]);
                     }
-                    if (X3_OFF(4194304)) {  // experiment: the 12 DMAs in the two products that follow no fragment-read burst (am.bm, ah.bl), six each
-                        constexpr int B0 = N0 == 4 ? 0 : 6;
-                        if (N0 == 4 || N0 == 10) {
-                            if (qm == 0) { dma_piece(X3Int<B0>{}); dma_piece(X3Int<B0 + 1>{}); }
-                            if (qm == 1) dma_piece(X3Int<B0 + 2>{});
-                            if (qm == 2) { dma_piece(X3Int<B0 + 3>{}); dma_piece(X3Int<B0 + 4>{}); }
-                            if (qm == 3) dma_piece(X3Int<B0 + 5>{});
-                        }
-                    } else {
                     if (qm == 1) dma_piece(X3Int<N0>{});
                     if (qm == 3) dma_piece(X3Int<N0 + 1>{});
-                    }
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
@@ -494,13 +478,6 @@ void launch_dw_x3(const X3Args &a, hipStream_t st)
 }
 
 
-#ifdef RNNT_LAB
-#include "lab/x3_lab_dw.inc"  // k_dw_x3p (RNNT_VARIANT_X3_DW_P16): measured equal to k_dw_x3, kept as lab equipment
-#endif
-
-// compile-time experiment switches (tools/build_x3_variants.sh: -DX3_EXP=bits; the run-time switches of the
-// RNNT_ABLATE build make hipcc spill 149 registers in this kernel): 1 no MFMA, 2 no G stores, 4 no raw loads in
-// the loop, 8 no W DMA, 16 no epilogue, 32 no production arithmetic, 64 no fragment reads
 #define XG_WAIT8_BUT(b, N) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]), "+v"(b[6]), "+v"(b[7]) :: "memory")
 #define XG_WAIT8(b) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]), "+v"(b[6]), "+v"(b[7]) :: "memory")
 // ---------------------------------------------------------------------------------------
@@ -594,13 +571,8 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x3(X3Args a, const int nti
     const int xa = lds0 + 2 * XF_WSLOT + (2 * wm) * 3072 + 16 * lane;  // A read: M tiles 2wm, 2wm+1: [slot][M tile][plane][lane]
     const int xw = lds0 + 2 * XF_WSLOT + wave * 3072 + 16 * lane;       // A write: M tile `wave` (this lane's own fragment slot)
     const int wb = lds0 + (8 * wn) * 1024 + 16 * lane;                 // W read: tiles 8wn .. 8wn+7 of each plane
-    // (experiment 131072: W pieces by LDS-DMA with NO address register — the descriptor's ADD_TID_ENABLE (word 3 bit 23; stride
-    // 16 in word 1; the DATA_FORMAT bits extend the stride in this mode and stay 0) adds lane x 16 bytes itself.  Fetches the
-    // same bytes (tools/dma_vs_mfma.hip) and changes nothing: 33.2 vs 33.3 ms here, 32.3 vs 32.1 in k_dhidden_x3 — a DMA's
-    // issue cost is not its address register.)
-    const __amdgpu_buffer_rsrc_t wrs = !X3_OFF(131072) ? __builtin_amdgcn_make_buffer_rsrc(a.wpack_fwd, 0, npass * KC * 49152, 0x00020000)
-                                                       : __builtin_amdgcn_make_buffer_rsrc(a.wpack_fwd, 16, 0x7fffffff, 0x00800000);
-    const int wvo = !X3_OFF(131072) ? lane * 16 : 0;
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(a.wpack_fwd, 0, npass * KC * 49152, 0x00020000);
+    const int wvo = lane * 16;
 
     // Persistent workgroups (one per CU: 120 KiB of LDS), tiles from one atomic counter, the next tile requested a
     // tile ahead.
@@ -689,12 +661,9 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x3(X3Args a, const int nti
                 asm volatile("ds_write_b128 %0, %1 offset:2048" :: "v"(dst), "v"(P.pl) : "memory");
             }
         };
-        auto hid_store = [&](const Prod &P, int kcs) {
-            if (!X3_OFF(128)) { hdst[2 * kcs] = P.ph; hdst[2 * kcs + ps] = P.pm; if (!X3_OFF(33554432)) hdst[2 * kcs + 2 * ps] = P.pl; }
-        };
+        auto hid_store = [&](const Prod &P, int kcs) { hdst[2 * kcs] = P.ph; hdst[2 * kcs + ps] = P.pm; hdst[2 * kcs + 2 * ps] = P.pl; };
         // piece n (0..11) of this wave's share of W k-step cs -> ring slot cs & 1
         auto wdma = [&](int cs, int n) {  // raw-buffer form: scalar base and offsets, one constant per-lane offset register
-            if (X3_OFF(8) || (X3_OFF(33554432) && n >= 8)) return;  // 33554432: what-if, two planes' worth of bytes
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_vptr)(s_fw + (cs & 1) * XF_WSLOT + (wave * 12 + n) * 1024), 16, wvo,
                                                      (cs * 48 + wave * 12 + n) * 1024, 0, 0);
         };
@@ -755,14 +724,11 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x3(X3Args a, const int nti
             // 4 operand loads and (first pass) 3 hidden stores, which stay in flight; the first k-step of a pass also
             // follows the previous pass's logits stores
             XSTAMP(0);
-            if (X3_OFF(512)) {}  // experiment: no wait at all (NOT a valid build)
-            else if (kc == 0 || X3_OFF(128)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (kc == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             // (behind the k-step's last DMA (block 2) come only the first pass's 3 hidden stores; the 4 operand loads sit
             // between the two DMA groups and retire with them)
-            else if (!X3_OFF(2097152) && STORE) asm volatile(RNNT_VMCNT(3) ::: "memory");
-            else if (!X3_OFF(2097152)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (STORE) asm volatile(RNNT_VMCNT(7) ::: "memory");
-            else asm volatile(RNNT_VMCNT(4) ::: "memory");
+            else if (STORE) asm volatile(RNNT_VMCNT(3) ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             XSTAMP(1);
             x3_lds_barrier();  // publishes W slot and A slot of k-step cs; every wave is past its reads of cs-1
             XSTAMP(2);
@@ -786,28 +752,23 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x3(X3Args a, const int nti
                          :: "memory");
             auto block = [&](auto pa_c, const u32x4 (&bcur)[8], u32x4 (&bnext)[8], auto nb_c, auto d0_c, auto pb_c) {
                 constexpr int PA = decltype(pa_c)::value, NB = decltype(nb_c)::value, D0 = decltype(d0_c)::value, PB = decltype(pb_c)::value;
-                const bool drop = X3_OFF(16777216) && (PA == 2 || (PA == 1 && &bcur[0] == &bn[0]) || (PA == 0 && NB < 0 && PB < 0));  // what-if: 3 of the 6 products
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
-                    if (!X3_OFF(1) && !drop) {
-                        acc[0][q] = x3_mfma(af[0][PA], bcur[q], acc[0][q]);
-                        acc[1][q] = x3_mfma(af[1][PA], bcur[q], acc[1][q]);
-                    }
+                    acc[0][q] = x3_mfma(af[0][PA], bcur[q], acc[0][q]);
+                    acc[1][q] = x3_mfma(af[1][PA], bcur[q], acc[1][q]);
                     if (NB >= 0) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bnext[q]) : "v"(ws), "n"((NB < 0 ? 0 : NB) * 16384 + q * 1024));
-                    // D0: W DMA pieces D0+q of k-step cs+1; PB: production pieces PB+q of A's k-step cs+1
-                    // W DMA pieces of k-step cs+1: six each in blocks 1 and 2, none beside block 0's eight fragment reads
-                    // (round 3 had 8 + 4 in blocks 0 and 1: 36.5 -> 35.9 ms on one box; experiment 2097152 = the old placement)
-                    if (!X3_OFF(2097152)) {
-                        if (D0 == 8 && q < 6) wdma(csn, q);
-                        if (D0 == -2 && q < 6) wdma(csn, 6 + q);
-                    } else if (D0 >= 0 && D0 + q < 12) wdma(csn, (D0 < 0 ? 0 : D0) + q);
+                    // D0: the tag of the block's W DMA pieces of k-step cs+1 (8: pieces 0-5, -2: pieces 6-11, else none); PB: production pieces PB+q of A's k-step cs+1
+                    // six DMA pieces each in blocks 1 and 2, none beside block 0's eight fragment reads
+                    // (round 3 had 8 + 4 in blocks 0 and 1: 36.5 -> 35.9 ms on one box)
+                    if (D0 == 8 && q < 6) wdma(csn, q);
+                    if (D0 == -2 && q < 6) wdma(csn, 6 + q);
                     if (PB >= 0 && PB + q < 17) prod_piece(P, ocur, (cs + 1) & 1, (PB < 0 ? 0 : PB) + q);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
             // every fragment read is issued at least a block (16 MFMAs) before the wait that covers it
             XSTAMP(3);
-            block(X3Int<0>{}, bf, bn, X3Int<1>{}, X3Int<0>{}, X3Int<-1>{});    // ah.bh + reads of W mid
+            block(X3Int<0>{}, bf, bn, X3Int<1>{}, X3Int<-1>{}, X3Int<-1>{});   // ah.bh + reads of W mid
             block(X3Int<1>{}, bf, bn, X3Int<-1>{}, X3Int<8>{}, X3Int<-1>{});   // am.bh + DMA 0-5
             XSTAMP(4);
             op_load(onext, kcnn);  // operands of k-step cs+2: behind the DMAs (they are needed a whole k-step from now)
@@ -826,13 +787,7 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x3(X3Args a, const int nti
           // or not for the whole wave.  The row loop is ONE basic block per case; the store address is a scalar row
           // pointer + one 32-bit per-lane offset.
           XESTAMP(32 * pass + 1);
-          if (X3_OFF(16)) {  // (the accumulators stay "used": without this the MFMAs are dead code too)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int q = 0; q < 8; ++q) asm volatile("" :: "a"(acc[mt][q]));
-          }
-          if (!X3_OFF(16)) {
+          {
             const int cw = 512 * pass + 256 * wn;
             const unsigned lane_off = (unsigned)(((4 * half) * V + 4 * i) * 4);
             char *tile_base = (char *)(a.logits + row0 * V + cw);
@@ -853,30 +808,26 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x3(X3Args a, const int nti
                             o0[q] = x0; o1[q] = x1;
                         }
                         char *rowp = tile_base + (long)(32 * (2 * wm + mt) + (r & 3) + 8 * (r >> 2)) * V * 4;  // wave-uniform
-                        if (!X3_OFF(2)) {
-                            __builtin_nontemporal_store(o0, (f32x4 *)(rowp + lane_off));
-                            if (BOTH) __builtin_nontemporal_store(o1, (f32x4 *)(rowp + lane_off + 512));
-                        }
-                        if (!X3_OFF(32)) {
-                            // the row slot's (max, sum exp) over this wave's 128 / 256 columns of the pass: 8 values per
-                            // lane, then the 32 lanes of the half on the DPP crossbar
-                            float m8 = fmaxf(fmaxf(o0[0], o0[1]), fmaxf(o0[2], o0[3]));
-                            if (BOTH) m8 = fmaxf(m8, fmaxf(fmaxf(o1[0], o1[1]), fmaxf(o1[2], o1[3])));
-                            const float M = half_max_dpp(m8, half);
-                            const float nm2 = -M * RNNT_LOG2E;
-                            float e = (__builtin_amdgcn_exp2f(fmaf(o0[0], RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(o0[1], RNNT_LOG2E, nm2))) +
-                                      (__builtin_amdgcn_exp2f(fmaf(o0[2], RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(o0[3], RNNT_LOG2E, nm2)));
-                            if (BOTH)
-                                e += (__builtin_amdgcn_exp2f(fmaf(o1[0], RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(o1[1], RNNT_LOG2E, nm2))) +
-                                     (__builtin_amdgcn_exp2f(fmaf(o1[2], RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(o1[3], RNNT_LOG2E, nm2)));
-                            const float S_ = half_sum_dpp(e, half);  // lanes 31 / 63 hold the sums
-                            if (i == 31) {
-                                float *sp = s_part + (wn * 128 + 32 * (2 * wm + mt) + (r & 3) + 8 * (r >> 2) + 4 * half) * 2;
-                                const float m_o = sp[0], s_o = sp[1];
-                                const float mn = fmaxf(m_o, M);
-                                sp[0] = mn;
-                                sp[1] = s_o * __builtin_amdgcn_exp2f((m_o - mn) * RNNT_LOG2E) + S_ * __builtin_amdgcn_exp2f((M - mn) * RNNT_LOG2E);
-                            }
+                        __builtin_nontemporal_store(o0, (f32x4 *)(rowp + lane_off));
+                        if (BOTH) __builtin_nontemporal_store(o1, (f32x4 *)(rowp + lane_off + 512));
+                        // the row slot's (max, sum exp) over this wave's 128 / 256 columns of the pass: 8 values per
+                        // lane, then the 32 lanes of the half on the DPP crossbar
+                        float m8 = fmaxf(fmaxf(o0[0], o0[1]), fmaxf(o0[2], o0[3]));
+                        if (BOTH) m8 = fmaxf(m8, fmaxf(fmaxf(o1[0], o1[1]), fmaxf(o1[2], o1[3])));
+                        const float M = half_max_dpp(m8, half);
+                        const float nm2 = -M * RNNT_LOG2E;
+                        float e = (__builtin_amdgcn_exp2f(fmaf(o0[0], RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(o0[1], RNNT_LOG2E, nm2))) +
+                                  (__builtin_amdgcn_exp2f(fmaf(o0[2], RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(o0[3], RNNT_LOG2E, nm2)));
+                        if (BOTH)
+                            e += (__builtin_amdgcn_exp2f(fmaf(o1[0], RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(o1[1], RNNT_LOG2E, nm2))) +
+                                 (__builtin_amdgcn_exp2f(fmaf(o1[2], RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(o1[3], RNNT_LOG2E, nm2)));
+                        const float S_ = half_sum_dpp(e, half);  // lanes 31 / 63 hold the sums
+                        if (i == 31) {
+                            float *sp = s_part + (wn * 128 + 32 * (2 * wm + mt) + (r & 3) + 8 * (r >> 2) + 4 * half) * 2;
+                            const float m_o = sp[0], s_o = sp[1];
+                            const float mn = fmaxf(m_o, M);
+                            sp[0] = mn;
+                            sp[1] = s_o * __builtin_amdgcn_exp2f((m_o - mn) * RNNT_LOG2E) + S_ * __builtin_amdgcn_exp2f((M - mn) * RNNT_LOG2E);
                         }
                         __builtin_amdgcn_sched_barrier(0);  // one row slot at a time
                         if ((r & 7) == 7) XESTAMP(32 * pass + 2 + 2 * mt + (r >> 3));
@@ -963,9 +914,6 @@ void launch_joint_fwd_x3(const X3Args &a, hipStream_t st)
     hipLaunchKernelGGL(k_joint_fwd_x3, dim3((unsigned)nwg), dim3(256), lds, st, a, ntiles);
 }
 
-#ifdef RNNT_LAB
-#include "lab/x3_lab_fwd.inc"  // k_joint_fwd_x3d<4|8>, k_joint_fwd_x3z (RNNT_VARIANT_X3_FWD_2WG / _8W / _Z): lab equipment
-#endif
 
 // ---------------------------------------------------------------------------------------
 // W for the dHidden product, fragment order, three planes:
@@ -1073,7 +1021,6 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
         return;
     }
 
-    const bool wave_stores = __any(pexists) && !X3_OFF(2);  // wave-uniform: the G stores below are issued at all
     CellCoef cf = a.coef[pexists ? pcell : 0];
     const bool live = pexists && pt < Tb && cf.c1 != RNNT_NEG_INF;
     if (!live) { cf.c1 = RNNT_NEG_INF; cf.sb = 0.f; cf.se = 0.f; cf.y = -1; }
@@ -1084,8 +1031,6 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
     // rows outside the lattice read the zero padding row (finite) with c1 = -inf -> G = 0; FIRST = false: every
     // existing row holds its G planes already
     const float *xsrc = a.logits + ((FIRST ? live : pexists) ? pcell : zrow) * V;
-    u32x4 *gdst = (u32x4 *)(a.logits + pcell * V) + half;
-    u32x4 *ldst = (u32x4 *)(a.g_lo + pcell * V) + half;
     const u32x4 *lsrc = (const u32x4 *)(a.g_lo + (pexists ? pcell : zrow) * V) + half;
     const int blank = a.blank;
     // G's hi | mid planes leave in WHOLE 128-byte lines (round 4): a line = the 32 x hi | 32 x mid of one cell and one
@@ -1097,8 +1042,6 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
     // 60.7 GB for 39.5 GB of G, profiles/r03_traffic.json.)  Raw-buffer stores over the tile's rows: rows outside the
     // lattice get an offset past the range (dropped), so every wave issues the same store instructions.
     const int lds0 = (int)(size_t)(lds_vptr)s_dh;
-    constexpr bool LINES = FIRST && !X3_OFF(32768);
-    constexpr bool LINES_LO = LINES && !X3_OFF(65536);  // the lo plane's half lines too
     const int lpiece = lane & 7, lrow = lane >> 3;
     // LDS: [slot = parity][M tile wave][plane][lane slot = row + 32 half]
     const int xl = lds0 + 2 * XG_WSLOT + ((lpiece >> 1) & 1) * XG_XSLOT + wave * 3072 + (lpiece >> 2) * 1024 + 16 * (lrow + 32 * (lpiece & 1));
@@ -1124,7 +1067,6 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
         const bool ex = t0 + lt < T && u0 + lu < U1;
         lvo2[n] = ex ? (int)(((long)lt * U1 + lu) * V * 2) + 16 * (lane & 3) : 0x7ffffff0;
     }
-    const int lovo = pexists ? (int)((((long)(prow >> 4)) * U1 + (prow & 15)) * V * 2) + 16 * half : 0x7ffffff0;  // (pipeline prologue / LINES_LO off)
 
     f32x16 acc[2][8];
 #pragma unroll
@@ -1139,9 +1081,8 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
     const int wb = lds0 + (8 * wn) * 1024 + 16 * lane;                  // W read: tiles 8wn .. 8wn+7 of each plane
     // W DMA: wave w copies pieces 12w .. 12w+11 of the k-step's 48 (piece = 1 KiB = one (plane, tile))
     // W k-steps by raw-buffer LDS-DMA: scalar base (this launch's 512-column pass) and offsets, one constant per-lane offset
-    const __amdgpu_buffer_rsrc_t wrs = !X3_OFF(131072) ? __builtin_amdgcn_make_buffer_rsrc((char *)a.wpack_dh + (long)hp * VC * 49152, 0, VC * 49152, 0x00020000)
-                                                       : __builtin_amdgcn_make_buffer_rsrc((char *)a.wpack_dh + (long)hp * VC * 49152, 16, 0x7fffffff, 0x00800000);
-    const int wvo = !X3_OFF(131072) ? lane * 16 : 0;  // (experiment 131072: TID-addressed, as in k_joint_fwd_x3)
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((char *)a.wpack_dh + (long)hp * VC * 49152, 0, VC * 49152, 0x00020000);
+    const int wvo = lane * 16;
 
     struct Raw { f32x4 x0, x1; u32x4 l; };  // FIRST: 8 fp32 logits; else: hi | mid (as x0, x1 bits) and lo planes
     auto xload = [&](Raw &r, int c, int part = 3) {  // part: 1 first half, 2 second half, 3 both (FIRST)
@@ -1156,8 +1097,9 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
             r.l = lsrc[2 * cc];
         }
     };
-    // G of k-step c from the raw values -> exchange slot (c & 1), and (FIRST) to memory.  The work is cut into
-    // slices (0..10) that the main loop threads through the gaps of its first MFMA blocks: one wave per SIMD
+    // G of k-step c from the raw values -> exchange slot (c & 1); (FIRST) it leaves for memory from there, as whole lines
+    // (line_read / line_store, lo_read / lo_store below).  The work is cut into
+    // slices (0..8) that the main loop threads through the gaps of its first MFMA blocks: one wave per SIMD
     // issues ~1 instruction per 4-5 cycles and an MFMA leaves 24 of its 32 cycles to other instructions, so ~150
     // instructions in FRONT of a k-step's MFMAs would cost a quarter of it.
     struct Prod { f32x4 g0, g1; u32x4 ph, pm, pl; };
@@ -1197,28 +1139,14 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
             asm volatile("ds_write_b128 %0, %1 offset:1024" :: "v"(dst), "v"(P.pm) : "memory");
             asm volatile("ds_write_b128 %0, %1 offset:2048" :: "v"(dst), "v"(P.pl) : "memory");
         }
-        if (LINES) {
-            // the lo plane's store (slice 11); the hi | mid planes leave as whole lines (line_read / line_store below)
-            if (sl == 11 && !X3_OFF(2) && !LINES_LO) __builtin_amdgcn_raw_buffer_store_b128(P.pl, lrs, lovo, 32 * c, 0);
-        } else if (sl >= 9 && sl <= 11 && FIRST && pexists && !X3_OFF(2)) {  // the three stores, one slice each
-            if (X3_OFF(256)) {  // experiment: the same three stores, all to one cache-resident kilobyte (NOT a valid build)
-                u32x4 *dump = (u32x4 *)(a.g_lo + zrow * V) + lane;
-                if (sl == 9) dump[0] = P.ph; else if (sl == 10) dump[64] = P.pm; else dump[128] = P.pl;
-            } else {
-                if (sl == 9) gdst[8 * (c >> 1) + 2 * (c & 1)] = P.ph;
-                else if (sl == 10) gdst[8 * (c >> 1) + 4 + 2 * (c & 1)] = P.pm;
-                else ldst[2 * c] = P.pl;
-            }
-        }
     };
     auto produce = [&](const Raw &r, int c) {  // all slices at once (pipeline prologue)
         Prod P;
 #pragma unroll
-        for (int sl = 0; sl < 12; ++sl) produce_slice(P, r, c, sl);
+        for (int sl = 0; sl < 9; ++sl) produce_slice(P, r, c, sl);
     };
     auto wdma = [&](int c, int n) {  // piece n (0..11) of this wave's share of W k-step c -> ring slot c & 1
         const int cc = c < VC ? c : VC - 1;
-        if (X3_OFF(8) || (X3_OFF(33554432) && n >= 8)) return;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_vptr)(s_dh + (c & 1) * XG_WSLOT + (wave * 12 + n) * 1024), 16, wvo,
                                                  (cc * 48 + wave * 12 + n) * 1024, 0, 0);
     };
@@ -1241,14 +1169,8 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
             // DMAs.  In-place safety: a store of k-step s's G overwrites logits bytes of k-steps <= s+1, every one of
             // them loaded — and waited for by this counter — at least two k-steps before the store is issued.)
             GXSTAMP(0);
-            if (X3_OFF(512)) {}  // experiment: no wait at all (NOT a valid build: the W ring may be read before it landed)
-            else if (X3_OFF(4) || X3_OFF(2)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (LINES_LO && (j & 1)) asm volatile(RNNT_VMCNT(8) ::: "memory");  // behind the previous (even) k-step's DMAs: 4 + 2 line stores, 2 raw loads
-            else if (LINES_LO) asm volatile(RNNT_VMCNT(2) ::: "memory");            // previous k-step odd: 2 raw loads
-            else if (LINES && (j & 1)) asm volatile(RNNT_VMCNT(7) ::: "memory");  // lo store, 4 line stores, 2 raw loads
-            else if (LINES) asm volatile(RNNT_VMCNT(3) ::: "memory");            // previous k-step odd: lo store, 2 raw loads
-            else if (FIRST && wave_stores) asm volatile(RNNT_VMCNT(5) ::: "memory");  // 3 G stores + 2 raw loads behind the DMAs
-            else if (FIRST) asm volatile(RNNT_VMCNT(2) ::: "memory");  // a wave without an existing cell issues no store
+            if (FIRST && (j & 1)) asm volatile(RNNT_VMCNT(8) ::: "memory");  // behind the previous (even) k-step's DMAs: 4 + 2 line stores, 2 raw loads
+            else if (FIRST) asm volatile(RNNT_VMCNT(2) ::: "memory");            // previous k-step odd: 2 raw loads
             else asm volatile(RNNT_VMCNT(3) ::: "memory");
             GXSTAMP(1);
             x3_lds_barrier();
@@ -1261,17 +1183,15 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
 #pragma unroll
                 for (int p = 0; p < 3; ++p)
                     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(af[mt][p]) : "v"(xs), "n"(mt * 3072 + p * 1024));
-            if (!X3_OFF(64)) {
 #pragma unroll
-                for (int q = 0; q < 8; ++q) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bf[q]) : "v"(ws), "n"(q * 1024));
-            }
+            for (int q = 0; q < 8; ++q) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bf[q]) : "v"(ws), "n"(q * 1024));
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(af[0][0]), "+v"(af[0][1]), "+v"(af[0][2]), "+v"(af[1][0]), "+v"(af[1][1]), "+v"(af[1][2]),
                            "+v"(bf[0]), "+v"(bf[1]), "+v"(bf[2]), "+v"(bf[3]), "+v"(bf[4]), "+v"(bf[5]), "+v"(bf[6]), "+v"(bf[7])
                          :: "memory");
             // one product block: 16 MFMAs = (2 M tiles) x (8 column tiles) for A plane PA against the B plane held
             // in `bcur`; optionally the next B plane's 8 fragment reads (NB: plane index, -1 none), W DMA pieces of
-            // k-step c+1 (D0: first piece, -1 none) and production slices of G's k-step c+1 (S0: first slice, -1 none)
+            // k-step c+1 (D0 = 4: pieces 0-5, 8: pieces 6-11, else none) and production slices of G's k-step c+1 (S0: first slice, -1 none)
             Prod P;
             const bool prod_on = c + 1 < VC;  // workgroup-uniform
             const Raw &rawn = xr[(j + 1) & 3];
@@ -1289,66 +1209,53 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
             };
             auto lo_store = [&](u32x4 &v, int n, int ce) {
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v) :: "memory");
-                if (!X3_OFF(2)) __builtin_amdgcn_raw_buffer_store_b128(v, lrs, lvo2[n], 64 * (ce >> 1), 0);
+                __builtin_amdgcn_raw_buffer_store_b128(v, lrs, lvo2[n], 64 * (ce >> 1), 0);
             };
             auto line_store = [&](u32x4 &v, int n, int ce) {  // line n of the pair (ce, ce + 1): chunk ce >> 1 of the rows
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v) :: "memory");
-                if (!X3_OFF(2)) __builtin_amdgcn_raw_buffer_store_b128(v, grs, lvo[n], 128 * (ce >> 1), 0);
+                __builtin_amdgcn_raw_buffer_store_b128(v, grs, lvo[n], 128 * (ce >> 1), 0);
             };
             auto block = [&](auto pa_c, const u32x4 (&bcur)[8], u32x4 (&bnext)[8], auto nb_c, auto d0_c, auto s0_c, auto mem_c) {
                 constexpr int PA = decltype(pa_c)::value, NB = decltype(nb_c)::value, D0 = decltype(d0_c)::value, S0 = decltype(s0_c)::value;
                 constexpr int MEM = decltype(mem_c)::value;
-                constexpr bool DROP = X3_OFF(16777216) && (PA == 2 || MEM == 2 || MEM == 3);  // what-if: 3 of the 6 products
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
-                    if (!X3_OFF(1) && !DROP) {
-                        acc[0][q] = x3_mfma(af[0][PA], bcur[q], acc[0][q]);
-                        acc[1][q] = x3_mfma(af[1][PA], bcur[q], acc[1][q]);
-                    }
-                    if (NB >= 0 && !X3_OFF(64))
+                    acc[0][q] = x3_mfma(af[0][PA], bcur[q], acc[0][q]);
+                    acc[1][q] = x3_mfma(af[1][PA], bcur[q], acc[1][q]);
+                    if (NB >= 0)
                         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bnext[q]) : "v"(ws), "n"((NB < 0 ? 0 : NB) * 16384 + q * 1024));
                     // the 12 W DMAs of k-step c+1 ride in blocks 1 and 2 (six each, one per MFMA pair), none beside block 0's eight
                     // fragment reads and exp2 slices: 32.7 -> 32.3 ms against four per block in blocks 0-2 (a DMA's issue costs the
                     // more the more LDS / VALU traffic its phase carries); a burst of 12 at one point: 36 ms
-                    if (X3_OFF(262144)) {
-                        if (D0 >= 0 && (q & 1) == 0 && D0 + q / 2 < 12) wdma(c + 1, (D0 < 0 ? 0 : D0) + q / 2);
-                    } else {
-                        if (D0 == 4 && q < 6) wdma(c + 1, q);
-                        if (D0 == 8 && q < 6) wdma(c + 1, 6 + q);
-                    }
-                    if (S0 >= 0 && S0 + q < 9 && prod_on && !(X3_OFF(32) && S0 + q < 8)) produce_slice(P, rawn, c + 1, (S0 < 0 ? 0 : S0) + q);
-                    if (LINES) {
-                        // even k-step c: G of k-steps c and c+1 is in the exchange -> the pair's lines; every k-step: lo store, 2 raw loads
+                    if (D0 == 4 && q < 6) wdma(c + 1, q);
+                    if (D0 == 8 && q < 6) wdma(c + 1, 6 + q);
+                    if (S0 >= 0 && S0 + q < 9 && prod_on) produce_slice(P, rawn, c + 1, (S0 < 0 ? 0 : S0) + q);
+                    if (FIRST) {
+                        // even k-step c: G of k-steps c and c+1 is in the exchange -> the pair's lines (hi | mid) and lo half lines; every k-step: 2 raw loads
                         if (MEM == 1 && q == 1 && !(j & 1) && prod_on) { line_read(ln[0], X3Int<0>{}); line_read(ln[1], X3Int<1>{}); }
                         if (MEM == 1 && q == 3 && !(j & 1) && prod_on) { line_read(ln[2], X3Int<2>{}); line_read(ln[3], X3Int<3>{}); }
-                        if (MEM == 1 && q == 5 && prod_on) {
-                            if (!LINES_LO) produce_slice(P, rawn, c + 1, 11);
-                            else if (!(j & 1)) { lo_read(ll[0], X3Int<0>{}); lo_read(ll[1], X3Int<1>{}); }
-                        }
-                        if (LINES_LO && MEM == 3 && q == 2 && !(j & 1) && prod_on) lo_store(ll[0], 0, c);
-                        if (LINES_LO && MEM == 3 && q == 4 && !(j & 1) && prod_on) lo_store(ll[1], 1, c);
+                        if (MEM == 1 && q == 5 && !(j & 1) && prod_on) { lo_read(ll[0], X3Int<0>{}); lo_read(ll[1], X3Int<1>{}); }
+                        if (MEM == 3 && q == 2 && !(j & 1) && prod_on) lo_store(ll[0], 0, c);
+                        if (MEM == 3 && q == 4 && !(j & 1) && prod_on) lo_store(ll[1], 1, c);
                         if (MEM == 2 && q == 1 && !(j & 1) && prod_on) line_store(ln[0], 0, c);
                         if (MEM == 2 && q == 3 && !(j & 1) && prod_on) line_store(ln[1], 1, c);
                         if (MEM == 2 && q == 5 && !(j & 1) && prod_on) line_store(ln[2], 2, c);
                         if (MEM == 3 && q == 1 && !(j & 1) && prod_on) line_store(ln[3], 3, c);
-                        if (MEM == 3 && q == 3 && !X3_OFF(4)) xload(xr[(j + 1) & 3], c + 5, 1);
-                        if (MEM == 3 && q == 5 && !X3_OFF(4)) xload(xr[(j + 1) & 3], c + 5, 2);
-                    } else {
-                    if (MEM == 1 && q == 1 && prod_on) produce_slice(P, rawn, c + 1, 9);
-                    if (MEM == 1 && q == 5 && prod_on) produce_slice(P, rawn, c + 1, 10);
-                    if (MEM == 2 && q == 1 && prod_on) produce_slice(P, rawn, c + 1, 11);
-                    if (MEM == 2 && q == 5 && !X3_OFF(4)) xload(xr[(j + 1) & 3], c + 5, 1);
-                    if (MEM == 3 && q == 1 && !X3_OFF(4)) xload(xr[(j + 1) & 3], c + 5, 2);
+                        if (MEM == 3 && q == 3) xload(xr[(j + 1) & 3], c + 5, 1);
+                        if (MEM == 3 && q == 5) xload(xr[(j + 1) & 3], c + 5, 2);
+                    } else {  // the later column passes store nothing: the raw ring's refill (hi | mid and lo planes in one go)
+                        if (MEM == 2 && q == 5) xload(xr[(j + 1) & 3], c + 5, 1);
+                        if (MEM == 3 && q == 1) xload(xr[(j + 1) & 3], c + 5, 2);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
             // every fragment read is issued at least a block (16 MFMAs) before the wait that covers it
             GXSTAMP(3);
-            block(X3Int<0>{}, bf, bn, X3Int<1>{}, X3Int<0>{}, X3Int<0>{}, X3Int<0>{});     // ah.bh + reads of W mid, DMA 0-3, G slices 0-7 (exp2, corrections, split)
-            block(X3Int<1>{}, bf, bn, X3Int<-1>{}, X3Int<4>{}, X3Int<8>{}, X3Int<0>{});    // am.bh + DMA 4-7, G slice 8 (exchange)
+            block(X3Int<0>{}, bf, bn, X3Int<1>{}, X3Int<-1>{}, X3Int<0>{}, X3Int<0>{});    // ah.bh + reads of W mid, G slices 0-7 (exp2, corrections, split)
+            block(X3Int<1>{}, bf, bn, X3Int<-1>{}, X3Int<4>{}, X3Int<8>{}, X3Int<0>{});    // am.bh + DMA 0-5, G slice 8 (exchange)
             GXSTAMP(4);
-            block(X3Int<2>{}, bf, bf, X3Int<-1>{}, X3Int<8>{}, X3Int<-1>{}, X3Int<0>{});   // al.bh + DMA 8-11
+            block(X3Int<2>{}, bf, bf, X3Int<-1>{}, X3Int<8>{}, X3Int<-1>{}, X3Int<0>{});   // al.bh + DMA 6-11
             // G's stores and the raw ring refill come AFTER the k-step's DMAs (vmcnt retires in order: the next k-step's
             // wait for the DMAs must not also wait out a store acknowledgement or an HBM load needed 4 k-steps from
             // now), one per half block: five back-to-back HBM operations fill the CU's memory queue and block the wave
@@ -1365,14 +1272,12 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
     const int colg[2] = {512 * hp + 256 * wn + 4 * i, 512 * hp + 256 * wn + 128 + 4 * i};
     const bool colok[2] = {colg[0] < H, colg[1] < H};
     f32x4 pr[8][2];  // pred rows of this lane's 8 u slots, its 2 x 4 columns (zero where u >= U1 or the column >= H)
-    if (!X3_OFF(16)) {
 #pragma unroll
-        for (int r7 = 0; r7 < 8; ++r7) {
-            const int u = u0 + 8 * (r7 >> 2) + (r7 & 3) + 4 * half;
+    for (int r7 = 0; r7 < 8; ++r7) {
+        const int u = u0 + 8 * (r7 >> 2) + (r7 & 3) + 4 * half;
 #pragma unroll
-            for (int g = 0; g < 2; ++g)
-                pr[r7][g] = (u < U1 && colok[g]) ? *(const f32x4 *)(a.pred + ((long)b * U1 + u) * H + colg[g]) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
+        for (int g = 0; g < 2; ++g)
+            pr[r7][g] = (u < U1 && colok[g]) ? *(const f32x4 *)(a.pred + ((long)b * U1 + u) * H + colg[g]) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the over-issued ring loads / DMAs
     __syncthreads();
@@ -1380,13 +1285,6 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
     // ---- epilogue.  Accumulator register rr = 8rh + r7 of M tile (2wm + mt), column tile q: row (rr&3) + 8(rr>>2) +
     // 4half of its 32 = t row 2(2wm+mt) + rh, u slot 8(r7>>2) + (r7&3) + 4half; column 512hp + 256wn + 128(q>>2) +
     // 4i + (q&3).  hidden = hi + mid + lo of the planes (exact), through a raw buffer over the tile's rows.
-    if (X3_OFF(16)) {  // (the accumulators stay "used": without this the MFMAs are dead code too)
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int q = 0; q < 8; ++q) asm volatile("" :: "a"(acc[mt][q]));
-        return;
-    }
     float (*s_red)[64][65] = (float (*)[64][65])s_dh;  // [wn][lane][8 u slots x 8 columns]
     const long BTH = (long)a.B * T * H, BUH = (long)a.B * U1 * H;
     // The tanh' factor 1 - hidden^2 is RECOMPUTED from enc and pred (two small, cache-resident operands) instead of re-reading

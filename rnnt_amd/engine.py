@@ -160,15 +160,8 @@ VARIANT_FWD_ONE_WG_PER_TILE = 256
 VARIANT_X2_NO_FLUSH_SKIP = 512  # f16x2 route: no cell flushed (costs / grad_enc / grad_pred bit-identical; grad_W / grad_bias: summation order)
 VARIANT_X3_FP32_FWD = 4096  # bf16x3 route: this stage on the fp32 route's kernel (isolation checks; not bit-identical)
 VARIANT_X3_FP32_DH = 8192
-# kernels of the diagnostic library only (rnnt_amd/csrc/lab/rnnt_engine_lab.h; tools/build_lab.sh): librnnt_engine.so refuses these bits
+# bits 14 and up are reserved (include/rnnt_engine.h): librnnt_engine.so refuses every one of them with RNNT_ERR_UNSUPPORTED
 VARIANT_LAB_MASK = 0x7FFFC000
-VARIANT_X3_FWD_2WG = 16384
-VARIANT_X3_FWD_8W = 65536
-VARIANT_X3_FWD_Z = 262144
-VARIANT_X2_FWD_2WG = 1048576
-VARIANT_X2_DW_P16 = 2097152
-VARIANT_X2_DW_8W = 524288
-VARIANT_X3_DW_P16 = 131072
 STAGES_ALL = 255
 STAGES_FORWARD = 7  # operand producers + joint-forward GEMM + lattice sweep: costs only
 

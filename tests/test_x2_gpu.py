@@ -32,8 +32,7 @@ def amd():
 def test_x2_kernels_in_isolation(amd, variant, shape):
     """With RNNT_VARIANT_X3_FP32_FWD | _DH only k_dw_x2 runs (forward and dHidden on the fp32 route's kernels, k_x2_make_hidden
     / k_x2_split_g in between), with _FWD alone k_dhidden_x2 + k_dw_x2, without a variant all three — each against the fp64
-    oracle at the fp32 tolerances.  (k_dw_x2<8>, k_dw_x2p and k_joint_fwd_x2d — measured equal to the defaults — live in the
-    diagnostic library only since round 5: tools/lab_tests.py, tools/run_lab_tests.sh.)"""
+    oracle at the fp32 tolerances."""
     e = amd.engine
     var = {"dw_only": e.VARIANT_X3_FP32_FWD | e.VARIANT_X3_FP32_DH, "dw_dhidden": e.VARIANT_X3_FP32_FWD, "all": 0}[variant]
     B, T, U, H, V = shape
@@ -226,15 +225,19 @@ def test_x2_is_bitwise_reproducible(amd):
 
 
 def test_product_library_refuses_lab_variants(amd):
-    """librnnt_engine.so ships the default kernels only: a variant bit that names a kernel of the diagnostic library is refused at
-    the C boundary (RNNT_ERR_UNSUPPORTED), never mapped silently to another kernel (round-4 advice: _FWD_Z used to run x3d<4>)."""
+    """librnnt_engine.so ships the default kernels only: the bits of RNNT_VARIANT_LAB_MASK (14 and up) are reserved, and every one of them
+    is refused at the C boundary (RNNT_ERR_UNSUPPORTED) before anything is launched, never mapped silently to a kernel.  The seven values
+    below once named experimental kernels (three on the f16x2 route, four on the bf16x3 route)."""
     e = amd.engine
     if os.environ.get("RNNT_ENGINE_LIB"):
         pytest.skip("a diagnostic library is loaded")
     g = _dev(make_inputs(2, 9, 4, 128, 128, seed=3))
-    for dt, var in ((X2, e.VARIANT_X2_DW_8W), (X2, e.VARIANT_X2_DW_P16), (X2, e.VARIANT_X2_FWD_2WG), ("bf16x3", e.VARIANT_X3_FWD_2WG),
-                    ("bf16x3", e.VARIANT_X3_FWD_8W), ("bf16x3", e.VARIANT_X3_FWD_Z), ("bf16x3", e.VARIANT_X3_DW_P16)):
-        with pytest.raises(RuntimeError, match="diagnostic library"):
+    assert e.VARIANT_LAB_MASK == 0x7FFFC000
+    former = [(X2, 524288), (X2, 2097152), (X2, 1048576), ("bf16x3", 16384), ("bf16x3", 65536), ("bf16x3", 262144), ("bf16x3", 131072)]
+    every_bit = [(dt, 1 << b) for dt in (X2, "bf16x3") for b in range(31) if (1 << b) & e.VARIANT_LAB_MASK]
+    assert len(every_bit) == 2 * 17
+    for dt, var in former + every_bit:
+        with pytest.raises(RuntimeError, match="variant bits 0x%x are reserved" % var):
             e.joint_loss_fwd_bwd(g["enc"], g["pred"], g["W"], g["bias"], g["targets"], g["logit_lens"], g["target_lens"],
                                  127, 0.5, dtype=dt, variant=var)
 

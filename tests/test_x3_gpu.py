@@ -38,9 +38,7 @@ def golden_dir():
 def test_x3_kernels_in_isolation(amd, variant, shape):
     """One bf16x3 kernel at a time: with RNNT_VARIANT_X3_FP32_FWD | _DH only k_dw_x3 runs (forward and dHidden
     on the fp32 route's kernels, plain splitting kernels in between), with _FWD alone k_dhidden_x3 + k_dw_x3,
-    without a variant all three — each against the fp64 oracle at the fp32 tolerances.  (The kernels that were measured equal or
-    slower — k_joint_fwd_x3d<4|8>, k_joint_fwd_x3z, k_dw_x3p — live in the diagnostic library only since round 5 and are tested
-    by tools/lab_tests.py against that library: tools/run_lab_tests.sh.)"""
+    without a variant all three — each against the fp64 oracle at the fp32 tolerances."""
     e = amd.engine
     var = {"dw_only": e.VARIANT_X3_FP32_FWD | e.VARIANT_X3_FP32_DH, "dw_dhidden": e.VARIANT_X3_FP32_FWD, "all": 0}[variant]
     B, T, U, H, V = shape

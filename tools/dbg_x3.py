@@ -1,4 +1,4 @@
-"""debug: which bf16x3 kernel form breaks a shape (fp64 oracle check per variant)"""
+"""debug: which bf16x3 stage breaks a shape (fp64 oracle check per isolation variant)"""
 import sys
 sys.path.insert(0, ".")
 import numpy as np, torch
@@ -10,7 +10,7 @@ d = make_inputs(B, T, U, H, V, seed=1234)
 ref = oracle_fused(d)
 g = {k: torch.from_numpy(v).cuda() for k, v in d.items()}
 print("lens", d["logit_lens"], d["target_lens"])
-for name, var in (("default", 0), ("fwd 2wg", engine.VARIANT_X3_FWD_2WG), ("fwd 8w", engine.VARIANT_X3_FWD_8W)):
+for name, var in (("default", 0), ("fwd=fp32", engine.VARIANT_X3_FP32_FWD), ("fwd,dh=fp32", engine.VARIANT_X3_FP32_FWD | engine.VARIANT_X3_FP32_DH)):
     outs = engine.joint_loss_fwd_bwd(g["enc"], g["pred"], g["W"], g["bias"], g["targets"], g["logit_lens"], g["target_lens"],
                                      V - 1, 1.0 / B, dtype="bf16x3", variant=var)
     torch.cuda.synchronize()

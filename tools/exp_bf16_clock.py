@@ -1,12 +1,9 @@
-"""[diagnostic libraries of tools/bf16_whatif.sh] wall clock of the bf16 route's three GEMM kernels at cfg2 and the core clock workgroup 0
-of each ran at (s_memtime / s_memrealtime stamps at its start and end), for one variant library:
-    python3 tools/exp_bf16_clock.py FR_EXP_1:fwd      (library build_variants/bf16w/lib_FR_EXP_1.so; kernels: fwd, dh, dw or all)"""
+"""[diagnostic build: bf16.hip with -DBF_CLOCK, engine.hip with -DRNNT_STAMPS, every other object from the shipped build] wall clock of the
+bf16 route's three GEMM kernels at cfg2 and the core clock workgroup 0 of each ran at (s_memtime / s_memrealtime stamps at its start and end):
+    python3 tools/exp_bf16_clock.py build_variants/bf16w/lib_clock.so:all      (<library>:<kernels>; kernels: fwd, dh, dw or all)"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-LEGEND = {"FR_EXP": {1: "MFMAs", 2: "statistics", 4: "logits stores", 8: "hidden stores", 16: "W DMA", 32: "tanh", 64: "(one workgroup per CU)", 128: "half of the W fragment reads and of the W DMA pieces (two MFMAs per fragment)"},
-          "DH_EXP": {1: "MFMAs", 2: "G arithmetic", 4: "G stores", 8: "logits loads", 16: "W staging", 32: "epilogue"},
-          "BW_EXP": {1: "MFMAs", 2: "db dot2", 4: "fragment reads", 8: "DMA bytes", 16: "DMA instructions", 32: "barrier", 64: "lockstep"}}
 
 
 def measure(which):
@@ -45,9 +42,7 @@ if __name__ == "__main__":
         print(measure(sys.argv[2]), flush=True)
         sys.exit(0)
     for spec in sys.argv[1:]:
-        lib, which = spec.split(":")
-        var, bits = lib.rsplit("_", 1)
-        off = " + ".join(n for b, n in LEGEND[var].items() if int(bits) & b) or "nothing"
-        env = dict(os.environ, RNNT_ENGINE_LIB=os.path.join(ROOT, "build_variants", "bf16w", f"lib_{lib}.so"))
+        lib, which = spec.rsplit(":", 1)
+        env = dict(os.environ, RNNT_ENGINE_LIB=os.path.abspath(lib))
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", which], env=env, capture_output=True, text=True, timeout=600)
-        print(f"{lib:>10s}  without {off:45s} {r.stdout.strip().splitlines()[-1] if r.stdout.strip() else 'FAILED ' + r.stderr[-400:]}", flush=True)
+        print(f"{os.path.basename(lib):>16s}  {r.stdout.strip().splitlines()[-1] if r.stdout.strip() else 'FAILED ' + r.stderr[-400:]}", flush=True)

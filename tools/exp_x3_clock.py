@@ -1,6 +1,6 @@
-"""[diagnostic libraries of tools/build_x3_stamp_variants.sh] the core clock k_joint_fwd_x3 runs at, full kernel against
-stripped variants: workgroup 0 stamps s_memtime and s_memrealtime (100 MHz) at its start and end.
-    python3 tools/exp_x3_clock.py <exp> [<exp> ...]"""
+"""[diagnostic libraries of tools/build_x3_stamp_variants.sh / tools/build_x2_stamps.sh] the core clock the three GEMM kernels of the
+bf16x3 ("x3") or the f16x2 ("x2") route run at: workgroup 0 stamps s_memtime and s_memrealtime (100 MHz) at its start and end.
+    python3 tools/exp_x3_clock.py x3|x2 [...]"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -40,9 +40,9 @@ if __name__ == "__main__":
         print(measure(), flush=True)
         sys.exit(0)
     for e in sys.argv[1:]:
-        # <exp>: an X3_EXP variant of tools/build_x3_stamp_variants.sh; "x2": tools/build_x2_stamps.sh's library on the f16x2 route
-        env = dict(os.environ, RNNT_ENGINE_LIB=os.path.join(ROOT, "build_variants", "x3", "lib_x2_stamps.so" if e == "x2" else f"lib_stamps_{e}.so"))
+        # "x3": tools/build_x3_stamp_variants.sh's library on the bf16x3 route; "x2": tools/build_x2_stamps.sh's on the f16x2 route
+        env = dict(os.environ, RNNT_ENGINE_LIB=os.path.join(ROOT, "build_variants", "x3", "lib_x2_stamps.so" if e == "x2" else "lib_stamps.so"))
         if e == "x2":
             env["STAMP_DTYPE"] = "f16x2"
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, capture_output=True, text=True, timeout=300)
-        print(f"X3_EXP={e:>5s}  {r.stdout.strip().splitlines()[-1] if r.stdout.strip() else 'FAILED ' + r.stderr[-300:]}", flush=True)
+        print(f"{e:>5s}  {r.stdout.strip().splitlines()[-1] if r.stdout.strip() else 'FAILED ' + r.stderr[-300:]}", flush=True)
