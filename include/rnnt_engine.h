@@ -612,6 +612,66 @@ int rnnt_engine_linear_x2_bwd(const float *x, int64_t ldx, const float *W, const
                               void *stream);
 
 /*
+ * The AudioEncoder's inference forward (reference rnnt/jasper.py:90-183, rnnt/causalconv.py:9-40; eval mode, fp32): mel
+ * features to encoder output for a whole batch of utterances (rnnt_engine_encoder_fwd = AudioEncoder.forward) or for one
+ * streaming push (rnnt_engine_encoder_stream_push = AudioEncoder.streaming_forward).  The module is handed over as a flat
+ * list of layers in execution order, each  causal conv -> [norm] -> [+ residual branch] -> [exact GELU]:
+ *     prologue (PLAIN);  per JasperBlock: its residual 1x1 (RESIDUAL: conv + norm of the block's input, kept aside), then
+ *     its sub-blocks (FIRST .. PLAIN .. LAST; a block of one sub-block is FIRST | LAST; LAST adds the residual branch before
+ *     its GELU);  epilogue (PLAIN);  the output 1x1 (FINAL: conv + bias only).
+ * `cin` of a layer is `cout` of the layer before it (a RESIDUAL layer and the FIRST layer behind it read the same input; a
+ * block's LAST `cout` is its RESIDUAL `cout`); layers inside a block have stride 1.
+ *   weight [cout][cin][taps] (torch Conv1d), bias [cout]; gamma / beta [cout] or NULL (1 / 0); mean / var [cout]: the
+ *   running statistics of RNNT_ENC_NORM_BATCH.  RNNT_ENC_NORM_INSTANCE takes mean and biased variance per (batch entry,
+ *   channel) over the output frames of THIS call (so a streamed instance-norm encoder depends on the chunking, as the
+ *   reference's does).
+ * A conv of `taps` taps, stride s, dilation d reads X~ = state followed by the input frames; output frame t is
+ * bias + sum_j sum_ci W[co][ci][j] X~[ci][t*s + j*d]; frames out = (len(X~) - d*(taps-1) - 1) / s + 1; the next state is X~
+ * from frame out*s on.  A whole utterance starts from (taps-1)*d - s + 1 zero frames of state.
+ *
+ * rnnt_engine_encoder_pack writes the weights once as [tap][cout][cin rounded up to 4] per layer (only `weight` and the
+ * dimensions are read); the other calls read `packed` and never `weight`.  Repack after the weights change.
+ * x: N x cin x L fp32 with strides x_strides (floats; batch, channel, frame).  out: [N][L_out][cout of the last layer]
+ * contiguous (time-major; L_out by the frame arithmetic above, layer after layer).
+ * Streaming: state_in / state_out are HOST arrays of n_layers device pointers, state_in_lens / state_out_lens HOST arrays
+ * of n_layers frame counts (entries of RESIDUAL / FINAL layers are ignored); state i is (N, cin, len) contiguous fp32;
+ * state_out_lens must be what the push leaves (checked), a state is never updated in place, a length of 0 needs no pointer.
+ * regime: RNNT_ENC_REGIME_AUTO picks per layer the weight-streaming kernel (N * frames out <= 64 and N * len(X~) <= 224)
+ * or the MFMA GEMM; RNNT_ENC_REGIME_MANY_ROWS forces the GEMM.  rnnt_engine_encoder_workspace_bytes: state_lens NULL = whole
+ * utterance.  Results are bitwise reproducible.  RNNT_ERR_INVALID_ARG: null pointers, taps / stride / dilation < 1, an empty or
+ * inconsistent layer list, too few frames for one output frame; everything is checked before anything is enqueued.
+ */
+#define RNNT_ENC_MAX_LAYERS 64
+#define RNNT_ENC_NORM_NONE 0
+#define RNNT_ENC_NORM_BATCH 1
+#define RNNT_ENC_NORM_INSTANCE 2
+#define RNNT_ENC_ROLE_PLAIN 0
+#define RNNT_ENC_ROLE_FIRST 1
+#define RNNT_ENC_ROLE_LAST 2
+#define RNNT_ENC_ROLE_RESIDUAL 4
+#define RNNT_ENC_ROLE_FINAL 8
+#define RNNT_ENC_REGIME_AUTO 0
+#define RNNT_ENC_REGIME_MANY_ROWS 1
+typedef struct rnnt_encoder_layer {
+    int cin, cout, taps, stride, dilation;
+    int norm;  /* RNNT_ENC_NORM_* */
+    int role;  /* RNNT_ENC_ROLE_* */
+    float eps;
+    const void *weight, *bias, *gamma, *beta, *mean, *var;
+} rnnt_encoder_layer;
+int rnnt_engine_encoder_packed_bytes(const rnnt_encoder_layer *layers, int n_layers, size_t *out);
+int rnnt_engine_encoder_pack(const rnnt_encoder_layer *layers, int n_layers, void *packed, size_t packed_bytes, void *stream);
+int rnnt_engine_encoder_workspace_bytes(const rnnt_encoder_layer *layers, int n_layers, int N, int L, int regime,
+                                        const int32_t *state_lens, size_t *out);
+int rnnt_engine_encoder_fwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x,
+                            const int64_t x_strides[3], int N, int L, int regime, float *out, void *workspace, size_t ws_bytes,
+                            void *stream);
+int rnnt_engine_encoder_stream_push(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x,
+                                    const int64_t x_strides[3], int N, int L, void *const *state_in, const int32_t *state_in_lens,
+                                    void *const *state_out, const int32_t *state_out_lens, int regime, float *out, void *workspace,
+                                    size_t ws_bytes, void *stream);
+
+/*
  * Multi-GPU step of the path (the suggested export of 8b): ONE sum all-reduce, in
  * place, of `count` fp32 values — the flat [dW (V*H) | db (V) | loss] buffer of a batch-sharded
  * step — on the caller's RCCL communicator (`comm` is an ncclComm_t) and stream.  Stands where the

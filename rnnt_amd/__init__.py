@@ -8,8 +8,9 @@ from . import engine, optim  # noqa: F401
 from .functional import joint_rnnt_loss, rnnt_loss, joint_logits, linear, rnnt_align, joint_rnnt_align  # noqa: F401
 from .joint import JointNetwork  # noqa: F401
 from .predictor import ConvPredictor  # noqa: F401
+from .encoder import AudioEncoder, JasperBlock  # noqa: F401
 from .model import RNNTModel  # noqa: F401
 from .stream import BeamStream, BeamStreamGroup, GreedyStream  # noqa: F401
 from .context import ContextGraph  # noqa: F401
 
-__all__ = ["engine", "optim", "joint_rnnt_loss", "rnnt_loss", "joint_logits", "rnnt_align", "joint_rnnt_align", "JointNetwork", "RNNTModel", "ConvPredictor", "GreedyStream", "BeamStream", "BeamStreamGroup", "ContextGraph"]
+__all__ = ["engine", "optim", "joint_rnnt_loss", "rnnt_loss", "joint_logits", "rnnt_align", "joint_rnnt_align", "JointNetwork", "RNNTModel", "ConvPredictor", "AudioEncoder", "JasperBlock", "GreedyStream", "BeamStream", "BeamStreamGroup", "ContextGraph"]

@@ -106,6 +106,11 @@ SIGNATURES = {
     "rnnt_engine_linear_x2_workspace_bytes": "iiiip",
     "rnnt_engine_linear_x2_fwd": "pqppiiippzp",
     "rnnt_engine_linear_x2_bwd": "pqppiiippppzp",
+    "rnnt_engine_encoder_packed_bytes": "pip",
+    "rnnt_engine_encoder_pack": "pipzp",
+    "rnnt_engine_encoder_workspace_bytes": "piiiipp",
+    "rnnt_engine_encoder_fwd": "pipppiiippzp",
+    "rnnt_engine_encoder_stream_push": "pipppiippppippzp",
     "rnnt_engine_allreduce": "pzpp",
     "rnnt_engine_workspace_layout": "iiiiiip",
     "rnnt_engine_run_stage": "ippppppppiiiiiiffippppppzp",
@@ -150,6 +155,8 @@ EXPORTS = (
     "rnnt_engine_linear_x2_workspace_bytes", "rnnt_engine_linear_x2_fwd", "rnnt_engine_linear_x2_bwd",
     "rnnt_engine_align", "rnnt_engine_joint_align",
     "rnnt_engine_loss_fwd_bwd_reg", "rnnt_engine_joint_loss_fwd_bwd_reg", "rnnt_engine_joint_loss_fwd_reg",
+    "rnnt_engine_encoder_packed_bytes", "rnnt_engine_encoder_pack", "rnnt_engine_encoder_workspace_bytes",
+    "rnnt_engine_encoder_fwd", "rnnt_engine_encoder_stream_push",
 )
 
 # per-call kernel variants (include/rnnt_engine.h RNNT_VARIANT_*): bit-identical results
