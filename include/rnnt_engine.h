@@ -632,14 +632,17 @@ int rnnt_engine_linear_x2_bwd(const float *x, int64_t ldx, const float *W, const
  * rnnt_engine_encoder_pack writes the weights once as [tap][cout][cin rounded up to 4] per layer (only `weight` and the
  * dimensions are read); the other calls read `packed` and never `weight`.  Repack after the weights change.
  * x: N x cin x L fp32 with strides x_strides (floats; batch, channel, frame).  out: [N][L_out][cout of the last layer]
- * contiguous (time-major; L_out by the frame arithmetic above, layer after layer).
+ * contiguous (time-major; L_out by the frame arithmetic above, layer after layer).  The last layer of the list stores there
+ * whatever its role — a list need not end in FINAL; its norm, residual and GELU are what its role says.
  * Streaming: state_in / state_out are HOST arrays of n_layers device pointers, state_in_lens / state_out_lens HOST arrays
  * of n_layers frame counts (entries of RESIDUAL / FINAL layers are ignored); state i is (N, cin, len) contiguous fp32;
  * state_out_lens must be what the push leaves (checked), a state is never updated in place, a length of 0 needs no pointer.
  * regime: RNNT_ENC_REGIME_AUTO picks per layer the weight-streaming kernel (N * frames out <= 64 and N * len(X~) <= 224)
  * or the MFMA GEMM; RNNT_ENC_REGIME_MANY_ROWS forces the GEMM.  rnnt_engine_encoder_workspace_bytes: state_lens NULL = whole
  * utterance.  Results are bitwise reproducible.  RNNT_ERR_INVALID_ARG: null pointers, taps / stride / dilation < 1, an empty or
- * inconsistent layer list, too few frames for one output frame; everything is checked before anything is enqueued.
+ * inconsistent layer list, too few frames for one output frame, a RNNT_ENC_NORM_INSTANCE layer with a single output frame
+ * (no variance; the size query rnnt_engine_encoder_workspace_bytes refuses it as well); everything is checked before anything
+ * is enqueued.
  */
 #define RNNT_ENC_MAX_LAYERS 64
 #define RNNT_ENC_NORM_NONE 0

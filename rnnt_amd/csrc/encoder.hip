@@ -427,6 +427,8 @@ int make_plan(const rnnt_encoder_layer *layers, int n_layers, int N, int L, cons
         const long Lt = slen + cur;
         if (Lt < span + 1) return fail(RNNT_ERR_INVALID_ARG, "layer %d: %ld frames of state and input are too short for one output frame (needs %d)", i, Lt, span + 1);
         const long Lout = (Lt - span - 1) / l.stride + 1;
+        if (l.norm == RNNT_ENC_NORM_INSTANCE && Lout == 1)
+            return fail(RNNT_ERR_INVALID_ARG, "layer %d: instance norm over a single output frame (its variance is undefined)", i);
         const long M = (long)N * Lout;
         if (M > 65535L * 32 || (long)N * Lt > 0x7fffffffL / 4) return fail(RNNT_ERR_UNSUPPORTED, "N * L too large");
         P.Lin[i] = (int)cur; P.Lout[i] = (int)Lout; P.slen[i] = (int)slen;
@@ -515,8 +517,9 @@ int run(const char *what, const rnnt_encoder_layer *layers, int n_layers, const 
             hipLaunchKernelGGL(k_enc_conv_mfma, dim3((l.cout + 127) / 128, (N * Lout + 31) / 32, P.tsplit[i]), dim3(256), 0, st, c);
 
         const bool to_res = l.role == RNNT_ENC_ROLE_RESIDUAL, fin = l.role == RNNT_ENC_ROLE_FINAL;
-        float *dst = fin ? out : to_res ? res : buf[flip];
-        const long ldo = fin ? l.cout : pad4(l.cout);
+        const bool to_out = i == n_layers - 1;  // the list's last layer, FINAL or not, leaves `out` [N][L_out][cout]
+        float *dst = to_out ? out : to_res ? res : buf[flip];
+        const long ldo = to_out ? l.cout : pad4(l.cout);
         EncNorm nm;
         nm.slabs = slabs; nm.nsplit = P.nsplit[i];
         nm.bias = (const float *)l.bias; nm.gamma = (const float *)l.gamma; nm.beta = (const float *)l.beta;

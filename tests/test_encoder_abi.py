@@ -106,3 +106,50 @@ def test_run_entries_check_arguments_before_launching(lib):
                                              ctypes.c_size_t(0), None)
     assert rc == -1 and b"null" in lib.rnnt_engine_last_error()
     assert lib.rnnt_engine_encoder_pack(arr, len(SMALL), None, ctypes.c_size_t(0), None) == -1
+
+
+def test_instance_norm_over_one_output_frame_is_refused_by_the_size_query(lib):
+    """No variance over one frame: the reference and the Python path raise; the C ABI refuses from the size query on (no GPU needed)
+    and so, by the same make_plan, from the run entries before anything is enqueued."""
+    n = ctypes.c_size_t(0)
+
+    def ask(spec, L, lens=None, regime=REGIME_AUTO):
+        st = None if lens is None else (ctypes.c_int32 * len(spec))(*lens)
+        return lib.rnnt_engine_encoder_workspace_bytes(layers(spec), len(spec), 2, L, regime, st, ctypes.byref(n))
+
+    one = lambda norm: [(8, 12, 3, 1, 1, norm, ROLE_PLAIN)]
+    for regime in (REGIME_AUTO, REGIME_MANY_ROWS):
+        assert ask(one(NORM_INSTANCE), 1, regime=regime) == -1  # whole utterance: 2 zeros + 1 frame -> 1 output frame
+        msg = lib.rnnt_engine_last_error()
+        assert b"instance norm" in msg and b"layer 0" in msg, msg
+        assert ask(one(NORM_INSTANCE), 1, [2], regime) == -1 and b"instance norm" in lib.rnnt_engine_last_error()
+        assert ask(one(NORM_BATCH), 1, regime=regime) == 0 and n.value > 0   # the same layer with batch norm
+        assert ask(one(NORM_NONE), 1, regime=regime) == 0
+        assert ask(one(NORM_INSTANCE), 2, regime=regime) == 0 and n.value > 0  # ... or with two frames
+        assert ask(one(NORM_INSTANCE), 1, [3], regime) == 0                    # (3 of state + 1: two frames)
+    # the layer is named: here the block's residual 1x1 (layer 1) is the first with instance norm and one frame
+    block = [(8, 8, 3, 2, 1, NORM_BATCH, ROLE_PLAIN), (8, 16, 1, 1, 1, NORM_INSTANCE, ROLE_RESIDUAL),
+             (8, 16, 3, 1, 1, NORM_BATCH, ROLE_FIRST | ROLE_LAST), (16, 4, 1, 1, 1, NORM_NONE, ROLE_FINAL)]
+    assert ask(block, 2) == -1
+    msg = lib.rnnt_engine_last_error()
+    assert b"instance norm" in msg and b"layer 1" in msg, msg
+    assert ask(block, 4) == 0
+
+
+def test_lists_without_a_final_layer_are_accepted_by_the_size_queries(lib):
+    """`out` takes the last layer of the list whatever its role (the header); the workspace is what it was."""
+    n, w = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    lists = ([(8, 12, 3, 1, 1, NORM_BATCH, ROLE_PLAIN)],
+             [(8, 12, 3, 2, 1, NORM_NONE, ROLE_PLAIN), (12, 7, 5, 1, 2, NORM_INSTANCE, ROLE_PLAIN)],
+             [(8, 16, 1, 1, 1, NORM_BATCH, ROLE_RESIDUAL), (8, 16, 3, 1, 1, NORM_BATCH, ROLE_FIRST | ROLE_LAST)],
+             SMALL[:-1])
+    for spec in lists:
+        assert lib.rnnt_engine_encoder_packed_bytes(layers(spec), len(spec), ctypes.byref(n)) == 0 and n.value > 0
+        for regime in (REGIME_AUTO, REGIME_MANY_ROWS):
+            assert lib.rnnt_engine_encoder_workspace_bytes(layers(spec), len(spec), 3, 40, regime, None, ctypes.byref(w)) == 0
+            assert w.value > 0 and w.value % 256 == 0
+    # a trailing FINAL adds no activation buffer: the plan of the layers in front of it is the plan of the list without it
+    with_final, without = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    assert lib.rnnt_engine_encoder_workspace_bytes(layers(SMALL), len(SMALL), 3, 40, REGIME_AUTO, None, ctypes.byref(with_final)) == 0
+    assert lib.rnnt_engine_encoder_workspace_bytes(layers(SMALL), len(SMALL) - 1, 3, 40, REGIME_AUTO, None, ctypes.byref(without)) == 0
+    assert without.value <= with_final.value
