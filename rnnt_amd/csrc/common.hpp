@@ -145,6 +145,33 @@ __device__ __forceinline__ float half_sum_dpp(float v, int half)  // valid in la
     return v;
 }
 
+// FOUR independent reductions at once, interleaved step by step in one block: the same five steps per value (the row_bcast15 step,
+// row_mask 0xa, included: rows 0 and 2 keep their value, which is what max(v, -inf) / v + 0 leave), so every result has the bits of
+// half_max_dpp before its broadcast / of half_sum_dpp.  Between a register's write and the next DPP read of it stand the three
+// instructions of the other values: more than the two wait states, which only the block's first step has to buy with an s_nop
+// (the values come from VALU instructions right in front).  The trailing s_nop covers whatever the compiler places behind the block.
+#define RNNT_DPP4_STEP(op, ctrl)                     \
+    op " %0, %0, %0 " ctrl " bank_mask:0xf\n\t"     \
+    op " %1, %1, %1 " ctrl " bank_mask:0xf\n\t"     \
+    op " %2, %2, %2 " ctrl " bank_mask:0xf\n\t"     \
+    op " %3, %3, %3 " ctrl " bank_mask:0xf\n\t"
+#define RNNT_DPP4_TREE(op)                                        \
+    "s_nop 1\n\t"                                                 \
+    RNNT_DPP4_STEP(op, "quad_perm:[1,0,3,2] row_mask:0xf")        \
+    RNNT_DPP4_STEP(op, "quad_perm:[2,3,0,1] row_mask:0xf")        \
+    RNNT_DPP4_STEP(op, "row_ror:4 row_mask:0xf")                  \
+    RNNT_DPP4_STEP(op, "row_ror:8 row_mask:0xf")                  \
+    RNNT_DPP4_STEP(op, "row_bcast:15 row_mask:0xa")               \
+    "s_nop 1"
+__device__ __forceinline__ void half_max_dpp_x4(float &a, float &b, float &c, float &d)  // valid in lanes 16-31 / 48-63: half_bcast() next
+{
+    asm volatile(RNNT_DPP4_TREE("v_max_f32_dpp") : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+}
+__device__ __forceinline__ void half_sum_dpp_x4(float &a, float &b, float &c, float &d)  // valid in lanes 16-31 / 48-63
+{
+    asm volatile(RNNT_DPP4_TREE("v_add_f32_dpp") : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+}
+
 // Packed per-cell gradient coefficients written by k_coef, read by the backward GEMMs:
 //   G[v] = exp2(logit[v]*log2e + c1) - (v==blank)*sb - (v==y)*se
 struct __attribute__((aligned(16))) CellCoef {

@@ -1981,10 +1981,7 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
         if (tid == 0) s_next[it & 1] = (int)atomicAdd(a.counter, 1u);
         const long row0 = (long)(LIN ? tile / npass : tile) * 128;
         const int pass0 = LIN ? tile % npass : 0, cs0 = pass0 * KC;  // LIN: this tile's column pass and the pack index of its first k-step
-        // running (max, sum exp) of every row over the columns seen so far, per column half (wn): s_part[wn][row],
-        // kept by the lanes 31 / 63 that end up with a row slot's wave-level statistics
-        for (int k = tid; k < 256; k += 256) { s_part[2 * k] = RNNT_NEG_INF; s_part[2 * k + 1] = 0.f; }
-        __syncthreads();  // s_next, s_part visible; every wave is past the previous tile's LDS reads
+        __syncthreads();  // s_next visible; every wave is past the previous tile's LDS reads
         const int next = s_next[it & 1];
         // A tile entirely in the time steps past one utterance's length: its logits are never read (k_x2_dead_rows zeroes the
         // G rows dW reads of the tiles k_dhidden_x2 does not run), but its hidden rows must be finite (k_dw_x2 multiplies them by zeros): such a tile runs
@@ -2098,6 +2095,9 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
         }
 
         f32x16 acc[2][8];
+        // running (max, sum exp) over the columns of this wave's half (wn) seen so far, in registers across the passes: lane
+        // (i, half) keeps row slot i = 16 mt + r of the wave's 2 x 16 (row_of(mt, r) + 4 half) and hands it to s_part behind the last pass
+        float m_run = RNNT_NEG_INF, s_run = 0.f;
         auto acc_init = [&]() {
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
@@ -2248,12 +2248,9 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
             const f32x4 b1 = has_b && cw + 128 + 4 * i < V ? *(const f32x4 *)(a.bias + cw + 128 + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
             auto epilogue = [&](auto both_c) {
                 constexpr bool BOTH = decltype(both_c)::value != 0;
-                // one row slot: unscale + bias, store, (max, sum exp) over this wave's 128 / 256 columns of the pass (8 values per
-                // lane, then the 32 lanes of the half on the DPP crossbar), running statistics of the row (lanes 31 / 63)
-                auto slot = [&](int mt, int r) {
-                    // accumulator reads spelled as (volatile) asm: they stay here — left to hipcc, all 256 v_accvgpr_read are
-                    // hoisted in front of the first store and spilled
-                    f32x4 o0, o1;
+                // one row slot's logits: unscale + bias.  The accumulator reads are spelled as (volatile) asm: they stay here —
+                // left to hipcc, all 256 v_accvgpr_read are hoisted in front of the first store and spilled
+                auto read_slot = [&](int mt, int r, f32x4 &o0, f32x4 &o1) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         float x0, x1;
@@ -2261,44 +2258,95 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
                         asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(x1) : "a"(acc[mt][4 + q][r]));
                         o0[q] = fmaf(x0, unscale, b0[q]); o1[q] = fmaf(x1, unscale, b1[q]);
                     }
-                    char *rowp = tile_base + (long)(32 * (2 * wm + mt) + (r & 3) + 8 * (r >> 2)) * V * 4;  // wave-uniform
-                    if (LIN) {  // Y has no padding rows: rows past M are not stored (the k loop's memory operations stay unconditional)
+                };
+                auto row_of = [&](int mt, int r) { return 32 * (2 * wm + mt) + (r & 3) + 8 * (r >> 2); };  // (+ 4 half: this lane's row of the slot)
+                if constexpr (LIN) {  // the plain GEMM: the stores alone, a pair of row slots at a time
+                    // (reads and row spelled out here, not through read_slot / row_of: at 255 VGPRs this form's register allocation
+                    // turns on such details — through them hipcc spilled 70 registers across the k loop instead of 11)
+                    auto slot = [&](int mt, int r) {
+                        f32x4 o0, o1;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            float x0, x1;
+                            asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(x0) : "a"(acc[mt][q][r]));
+                            asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(x1) : "a"(acc[mt][4 + q][r]));
+                            o0[q] = fmaf(x0, unscale, b0[q]); o1[q] = fmaf(x1, unscale, b1[q]);
+                        }
+                        char *rowp = tile_base + (long)(32 * (2 * wm + mt) + (r & 3) + 8 * (r >> 2)) * V * 4;  // wave-uniform
+                        // Y has no padding rows: rows past M are not stored (the k loop's memory operations stay unconditional)
                         if (row0 + 32 * (2 * wm + mt) + (r & 3) + 8 * (r >> 2) + 4 * half < cells) {
                             *(f32x4 *)(rowp + lane_off) = o0;
                             if (BOTH) *(f32x4 *)(rowp + lane_off + 512) = o1;
                         }
-                        return;
-                    }
-                    __builtin_nontemporal_store(o0, (f32x4 *)(rowp + lane_off));
-                    if (BOTH) __builtin_nontemporal_store(o1, (f32x4 *)(rowp + lane_off + 512));
-                    float m8 = fmaxf(fmaxf(o0[0], o0[1]), fmaxf(o0[2], o0[3]));
-                    if (BOTH) m8 = fmaxf(m8, fmaxf(fmaxf(o1[0], o1[1]), fmaxf(o1[2], o1[3])));
-                    const float M = half_max_dpp(m8, half);
-                    const float nm2 = -M * RNNT_LOG2E;
-                    float e = (__builtin_amdgcn_exp2f(fmaf(o0[0], RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(o0[1], RNNT_LOG2E, nm2))) +
-                              (__builtin_amdgcn_exp2f(fmaf(o0[2], RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(o0[3], RNNT_LOG2E, nm2)));
-                    if (BOTH)
-                        e += (__builtin_amdgcn_exp2f(fmaf(o1[0], RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(o1[1], RNNT_LOG2E, nm2))) +
-                             (__builtin_amdgcn_exp2f(fmaf(o1[2], RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(o1[3], RNNT_LOG2E, nm2)));
-                    const float S_ = half_sum_dpp(e, half);  // lanes 31 / 63 hold the sums
-                    if (i == 31) {
-                        float *sp = s_part + (wn * 128 + 32 * (2 * wm + mt) + (r & 3) + 8 * (r >> 2) + 4 * half) * 2;
-                        const float m_o = sp[0], s_o = sp[1];
-                        const float mn = fmaxf(m_o, M);
-                        sp[0] = mn;
-                        sp[1] = s_o * __builtin_amdgcn_exp2f((m_o - mn) * RNNT_LOG2E) + S_ * __builtin_amdgcn_exp2f((M - mn) * RNNT_LOG2E);
-                    }
-                };
-                // TWO row slots at a time: with one wave per SIMD a slot is a chain of dependent latencies (accumulator reads, the
-                // two DPP reductions, exp2, the LDS update); the second slot's chain fills the first one's gaps
+                    };
 #pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
+                    for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-                    for (int r = 0; r < 16; r += 2) {
-                        slot(mt, r);
-                        slot(mt, r + 1);
-                        __builtin_amdgcn_sched_barrier(0);  // (a pair at a time: see the accumulator reads)
-                    }
+                        for (int r = 0; r < 16; r += 2) {
+                            slot(mt, r);
+                            slot(mt, r + 1);
+                            __builtin_amdgcn_sched_barrier(0);  // (a pair at a time: see the accumulator reads)
+                        }
+                } else {
+                    // FOUR row slots at a time, in straight-line phases with no branch and no LDS access: with one wave per SIMD a slot
+                    // is a chain of dependent latencies (accumulator reads, the two DPP reductions, exp2); the phases put the four
+                    // slots' chains side by side, and the two reductions run interleaved step by step (half_max_dpp_x4 / half_sum_dpp_x4).
+                    // A slot's (max, sum exp) over this pass's columns go from lanes 31 / 63 to the lanes that keep the slot's rows
+                    // (v_readlane + v_writelane); the running update is ONE unconditional sequence per pass, behind the last group.
+                    int m_pass = 0, s_pass = 0;  // (every lane is written: 32 slots x 2 halves)
+#pragma unroll
+                    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                        for (int r0 = 0; r0 < 16; r0 += 4) {
+                            f32x4 o0[4], o1[4];
+                            float mx[4], sm[4];
+                            // (a) unscale + bias, store, the lane's maximum over its 4 / 8 columns
+#pragma unroll
+                            for (int g = 0; g < 4; ++g) {
+                                read_slot(mt, r0 + g, o0[g], o1[g]);
+                                char *rowp = tile_base + (long)row_of(mt, r0 + g) * V * 4;  // wave-uniform
+                                __builtin_nontemporal_store(o0[g], (f32x4 *)(rowp + lane_off));
+                                if (BOTH) __builtin_nontemporal_store(o1[g], (f32x4 *)(rowp + lane_off + 512));
+                                float m8 = fmaxf(fmaxf(o0[g][0], o0[g][1]), fmaxf(o0[g][2], o0[g][3]));
+                                if (BOTH) m8 = fmaxf(m8, fmaxf(fmaxf(o1[g][0], o1[g][1]), fmaxf(o1[g][2], o1[g][3])));
+                                mx[g] = m8;
+                            }
+                            // (b) the maxima over the 32 lanes of each half (lanes 31 / 63 hold them)
+                            half_max_dpp_x4(mx[0], mx[1], mx[2], mx[3]);
+                            // (c) to every lane of the half and to the slot's lane pair of m_pass; sum exp over the lane's columns
+#pragma unroll
+                            for (int g = 0; g < 4; ++g) {
+                                const int lo = __builtin_amdgcn_readlane(__float_as_int(mx[g]), 31), hi = __builtin_amdgcn_readlane(__float_as_int(mx[g]), 63);
+                                asm("v_writelane_b32 %0, %1, %2" : "+v"(m_pass) : "s"(lo), "n"(16 * mt + r0 + g));
+                                asm("v_writelane_b32 %0, %1, %2" : "+v"(m_pass) : "s"(hi), "n"(32 + 16 * mt + r0 + g));
+                                const float M = __int_as_float(half ? hi : lo);
+                                const float nm2 = -M * RNNT_LOG2E;
+                                float e = (__builtin_amdgcn_exp2f(fmaf(o0[g][0], RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(o0[g][1], RNNT_LOG2E, nm2))) +
+                                          (__builtin_amdgcn_exp2f(fmaf(o0[g][2], RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(o0[g][3], RNNT_LOG2E, nm2)));
+                                if (BOTH)
+                                    e += (__builtin_amdgcn_exp2f(fmaf(o1[g][0], RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(o1[g][1], RNNT_LOG2E, nm2))) +
+                                         (__builtin_amdgcn_exp2f(fmaf(o1[g][2], RNNT_LOG2E, nm2)) + __builtin_amdgcn_exp2f(fmaf(o1[g][3], RNNT_LOG2E, nm2)));
+                                sm[g] = e;
+                            }
+                            // (d) the sums over the 32 lanes of each half (lanes 31 / 63 hold them), to the slot's lane pair of s_pass
+                            half_sum_dpp_x4(sm[0], sm[1], sm[2], sm[3]);
+#pragma unroll
+                            for (int g = 0; g < 4; ++g) {
+                                const int lo = __builtin_amdgcn_readlane(__float_as_int(sm[g]), 31), hi = __builtin_amdgcn_readlane(__float_as_int(sm[g]), 63);
+                                asm("v_writelane_b32 %0, %1, %2" : "+v"(s_pass) : "s"(lo), "n"(16 * mt + r0 + g));
+                                asm("v_writelane_b32 %0, %1, %2" : "+v"(s_pass) : "s"(hi), "n"(32 + 16 * mt + r0 + g));
+                            }
+                            __builtin_amdgcn_sched_barrier(0);  // (a group at a time: see the accumulator reads)
+                        }
+                    // (e) the running statistics of all 32 slots at once, each lane its own row's
+                    const float M = __int_as_float(m_pass), S_ = __int_as_float(s_pass);
+                    const float m_o = m_run, s_o = s_run;
+                    const float mn = fmaxf(m_o, M);
+                    m_run = mn;
+                    // (the fma spelled out, its addend a rounded product: what hipcc made of  s_o exp2(..) + S exp2(..)  when the update was
+                    // the tail of a row slot — left to contraction, the same line comes out as other roundings here)
+                    s_run = fmaf(s_o, __builtin_amdgcn_exp2f((m_o - mn) * RNNT_LOG2E), S_ * __builtin_amdgcn_exp2f((M - mn) * RNNT_LOG2E));
+                }
             };
             if (cw + 128 < V) epilogue(X2Int<1>{});
             else if (cw < V) epilogue(X2Int<0>{});
@@ -2308,7 +2356,13 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
         if (!LIN)
             for (int pass = 1; pass < npass; ++pass) run_pass(X2Int<0>{}, pass);
 
-        // ---- log-softmax denominators: the two column halves (wn) of every row
+        // ---- log-softmax denominators: the two column halves (wn) of every row.  s_part[wn][row] = the row's (max, sum exp) over
+        // that half's columns of every pass: all 256 entries are written, a half without columns (V = 128) leaves (-inf, 0)
+        if (!LIN) {
+            float *sp = s_part + (wn * 128 + 32 * (2 * wm + (i >> 4)) + (i & 3) + 8 * ((i & 15) >> 2) + 4 * half) * 2;
+            sp[0] = m_run;
+            sp[1] = s_run;
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // every logits / hidden store of the workgroup has left its wave; s_part complete
         if (LIN) { tile = next; continue; }
