@@ -314,16 +314,16 @@ __global__ __launch_bounds__(256, 2) void k_joint_fwd_bf16(Bf16Args a)
         for (int q = 0; q < 4; ++q) {
             // stage chunk cc+q+1 into the other slot, fetch chunk cc+q+3
             const long nxt = cc + q + 3 < NC ? cc + q + 3 : NC - 1;
-            if (q & 1) { bx.store(s_b[0], wave, lane); bx.load(wp, nxt, wave, lane, !RNNT_XP(a.flags, 2048)); }
-            else       { by.store(s_b[1], wave, lane); by.load(wp, nxt, wave, lane, !RNNT_XP(a.flags, 2048)); }
+            if (q & 1) { bx.store(s_b[0], wave, lane); bx.load(wp, nxt, wave, lane, !RNNT_XP(a.ablate, 2048)); }
+            else       { by.store(s_b[1], wave, lane); by.load(wp, nxt, wave, lane, !RNNT_XP(a.ablate, 2048)); }
             // A fragments of chunk cc+q+3 (same rows, k wraps into the next pass)
-            if (!RNNT_XP(a.flags, 4096)) {
+            if (!RNNT_XP(a.ablate, 4096)) {
                 int c3 = c + q + 3; if (c3 >= KC) c3 -= KC;
                 ar[(q + 3) & 3][0] = ap[4 * c3];
                 ar[(q + 3) & 3][1] = ap[4 * c3 + 1];
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (!RNNT_XP(a.flags, 1024)) mma_chunk<NT, 5>(acc, ar[q][0], ar[q][1], s_b[q & 1], lane);
+            if (!RNNT_XP(a.ablate, 1024)) mma_chunk<NT, 5>(acc, ar[q][0], ar[q][1], s_b[q & 1], lane);
             if (q == 3 && c + 4 == KC) {  // pass complete (KC % 4 == 0): bias, store, softmax statistics
                 const int col0 = 256 * pass + 8 * j;  // this lane's 8 adjacent columns
                 const bool cok = col0 < V;            // V % 128 == 0: the last pass may be half empty
@@ -339,10 +339,10 @@ __global__ __launch_bounds__(256, 2) void k_joint_fwd_bf16(Bf16Args a)
                                       pack_f16(acc[4][r], acc[5][r]), pack_f16(acc[6][r], acc[7][r])};
                     // streaming stores: the logits are not re-read by this kernel's CUs and should
                     // not evict the A rows the next pass re-reads from L2
-                    if (cok && !RNNT_XP(a.flags, 256)) __builtin_nontemporal_store(qv, (u32x4 *)(a.logits + orow * V + col0));
+                    if (cok && !RNNT_XP(a.ablate, 256)) __builtin_nontemporal_store(qv, (u32x4 *)(a.logits + orow * V + col0));
                     const f32x4 o0 = {f16_lo(qv[0]), f16_hi(qv[0]), f16_lo(qv[1]), f16_hi(qv[1])};
                     const f32x4 o1 = {f16_lo(qv[2]), f16_hi(qv[2]), f16_lo(qv[3]), f16_hi(qv[3])};
-                    if (RNNT_XP(a.flags, 512) || !cok) continue;  // columns past V (zero weights) are no logits
+                    if (RNNT_XP(a.ablate, 512) || !cok) continue;  // columns past V (zero weights) are no logits
                     // running (max, sum exp) of this lane's columns of row-slot r.  The max of the 8 rounded
                     // values is taken on the packed halves (3 v_pk_max_f16 + 1 + one conversion instead of 8
                     // conversions + 7 max; the exp arguments below read the halves through v_fma_mix_f32)
@@ -1014,7 +1014,7 @@ __global__ __launch_bounds__(512, 1) void k_dhidden_bf16(Bf16Args a, const int h
                 }
                 __builtin_amdgcn_sched_group_barrier(0x008, 2 * DEPTH, 0);
             }
-            if (FIRST && !(q & 1) && !RNNT_XP(a.flags, 256)) {  // chunk c+1 is odd: the pair (c, c+1) is complete
+            if (FIRST && !(q & 1) && !RNNT_XP(a.ablate, 256)) {  // chunk c+1 is odd: the pair (c, c+1) is complete
                 __builtin_amdgcn_sched_barrier(0);
                 const u32x4 gb0 = s_g[gsrc], gb1 = s_g[gsrc + 8];
                 if (gst_ok[0]) gst[0][4 * c] = gb0;
@@ -1027,7 +1027,7 @@ __global__ __launch_bounds__(512, 1) void k_dhidden_bf16(Bf16Args a, const int h
     if (FIRST) BF_CLOCK_STAMP(306);
     // ---- epilogue.  Accumulator register r of tile 4mt+q (mt = 0,1): row (r&3) + 8(r>>2) + 4*half
     // of M-tile 2wm+mt = (t-row 2(2wm+mt) + (r>>3), u (r&3) + 8((r>>2)&1) + 4*half), column 128wn + 4j + q.
-    if (RNNT_XP(a.flags, 8192)) {  // (the accumulators stay "used": without this the MFMAs are dead code too)
+    if (RNNT_XP(a.ablate, 8192)) {  // (the accumulators stay "used": without this the MFMAs are dead code too)
 #pragma unroll
         for (int tl = 0; tl < 8; ++tl) asm volatile("" :: "a"(acc[tl]));
         return;
@@ -1240,7 +1240,7 @@ __global__ __launch_bounds__(256, 1) void k_dw_bf16(Bf16Args a)
         };
         struct Frags { u32x2 al[4], ah[4], bl[4], bh[4]; };
         auto reads = [&](Frags &f, int slot, int ks) {  // 16 transposed reads, NOT waited for
-            if (RNNT_XP(a.flags, 4096)) return;  // experiment switch
+            if (RNNT_XP(a.ablate, 4096)) return;  // experiment switch
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 const int a0 = a_tile + slot * 32768 + 4096 * ks, b0 = b_tile + slot * 32768 + 4096 * ks;
@@ -1273,14 +1273,14 @@ __global__ __launch_bounds__(256, 1) void k_dw_bf16(Bf16Args a)
             }
 #pragma unroll
             for (int qm = 0; qm < 4; ++qm) {
-                if (!RNNT_XP(a.flags, 1024)) {
+                if (!RNNT_XP(a.ablate, 1024)) {
 #pragma unroll
                     for (int qn = 0; qn < 4; ++qn) acc[qm][qn] = mfma_bf16(fa[qm], fb[qn], acc[qm][qn]);
                 }
-                if (!RNNT_XP(a.flags, 8192)) dma_piece(dst, dslot, piece0 + qm);
+                if (!RNNT_XP(a.ablate, 8192)) dma_piece(dst, dslot, piece0 + qm);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (do_b && !RNNT_XP(a.flags, 2048)) {
+            if (do_b && !RNNT_XP(a.ablate, 2048)) {
 #pragma unroll
                 for (int m = 0; m < 4; ++m)
 #pragma unroll

@@ -7,8 +7,8 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
-#include <cstring>
 #include <dlfcn.h>
 #include <string>
 
@@ -48,6 +48,31 @@ namespace {
 
 inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// The control block of the fused workspace (rnnt_engine_ws_layout::counters): the one map of it, offset: member
+struct ControlBlock {
+    unsigned queue[128];       //    0: eight per-XCD work-item counters of the persistent dHidden kernel, 64 B apart
+    unsigned fwd_tile[32];     //  512: tile counter of the persistent forwards
+    float x2_scales[32];       //  640: f16x2 {s_W, 1 / s_W} (k_x2_wscale, every call)
+    unsigned lattice_err[32];  //  768: error word of the lattice sweep
+    unsigned ep_flag[32];      //  896: f16x2, != 0 when an input lies outside the factored tanh's range
+    long *dw_tab() { return (long *)(this + 1); }  // 1024: dW live-row table, 2B + 2 longs, or the fp32 route's larger live-granule list (dw_list_bytes)
+    static size_t dw_table_bytes(int B) { return align_up((2 * (size_t)B + 2) * 8); }
+    int *dw_prog(int B) { return (int *)((char *)(this + 1) + dw_table_bytes(B)); }  // behind the table: [n_split][16] progress words of k_dw_bf16 / k_dw_x2
+};
+static_assert(sizeof(ControlBlock) == 1024 && offsetof(ControlBlock, fwd_tile) == 512 && offsetof(ControlBlock, x2_scales) == 640 &&
+              offsetof(ControlBlock, lattice_err) == 768 && offsetof(ControlBlock, ep_flag) == 896, "control block map");
+
+// the loss arrays; carve_loss_ws: the standalone loss entries' workspace, denom_s | lpb_s | lpe_s | alpha_s | beta_s | coef | err (256 bytes)
+struct LossWs { float *denom_s, *lpb_s, *lpe_s; double *alpha_s, *beta_s; CellCoef *coef; unsigned *err; size_t bytes; };
+LossWs carve_loss_ws(void *workspace, int B, int T, int U1)
+{
+    const size_t skew = (size_t)B * ((size_t)T + U1 - 1) * U1, cells = (size_t)B * T * U1;
+    const size_t s4 = align_up(skew * 4), s8 = align_up(skew * 8), co = 3 * s4 + 2 * s8, er = co + align_up(cells * 16);
+    const uintptr_t p = (uintptr_t)workspace;
+    return LossWs{(float *)p, (float *)(p + s4), (float *)(p + 2 * s4), (double *)(p + 3 * s4), (double *)(p + 3 * s4 + s8),
+                  (CellCoef *)(p + co), (unsigned *)(p + er), er + 256};
+}
 
 int check_dims(int B, int T, int U1, int H, int V, int dtype, bool need_h)
 {
@@ -92,7 +117,7 @@ long bf16_rows_alloc(size_t rows_pad) { return (long)((rows_pad + 96 + 127) / 12
 void layout(int B, int T, int U1, int H, int V, int dtype, rnnt_engine_ws_layout *L)
 {
     const size_t D = (size_t)T + U1 - 1;
-    const size_t cells = (size_t)B * T * U1, skew = (size_t)B * D * U1;
+    const size_t cells = (size_t)B * T * U1;
     const bool bf = dtype == RNNT_DTYPE_BF16, x2 = dtype == RNNT_DTYPE_F32_F16X2, x3 = dtype == RNNT_DTYPE_F32_BF16X3 || x2;
     // (x3: the split-operand routes — bf16x3, and f16x2 with two planes instead of three)
     // G / hidden rows are padded with >= 1 zero row up to a multiple of 16 (dW chunk size)
@@ -120,12 +145,9 @@ void layout(int B, int T, int U1, int H, int V, int dtype, rnnt_engine_ws_layout
         L->logits = o;   o += align_up((rows_pad + 16) * V * 4);
         L->hidden = o;   o += align_up((rows_pad + 16) * H * 4);
     }
-    L->denom_s = o;  o += align_up(skew * 4);
-    L->lpb_s = o;    o += align_up(skew * 4);
-    L->lpe_s = o;    o += align_up(skew * 4);
-    L->alpha_s = o;  o += align_up(skew * 8);
-    L->beta_s = o;   o += align_up(skew * 8);
-    L->coef = o;     o += align_up(cells * 16);
+    const LossWs w = carve_loss_ws((void *)o, B, T, U1);  // the loss arrays: the standalone entries' carve, without its error word
+    L->denom_s = (size_t)w.denom_s; L->lpb_s = (size_t)w.lpb_s; L->lpe_s = (size_t)w.lpe_s;
+    L->alpha_s = (size_t)w.alpha_s; L->beta_s = (size_t)w.beta_s; L->coef = (size_t)w.coef; o = (size_t)w.err;
     L->wpack = o;
     if (bf) o += align_up(bf16_wpack_fwd_bytes(H, V)) + align_up(bf16_wpack_dh_bytes(H, V));
     else if (x2) o += align_up(x2_wpack_fwd_bytes(H, V)) + align_up(x2_wpack_dh_bytes(H, V));
@@ -138,11 +160,9 @@ void layout(int B, int T, int U1, int H, int V, int dtype, rnnt_engine_ws_layout
     L->slab_pred = o; o += align_up((size_t)L->n_ttile * B * U1 * H * 4);
     L->slab_w = o;   o += align_up((size_t)L->n_split * V * H * 4);
     L->slab_b = o;   o += align_up((size_t)L->n_split * V * 4);
-    {   // + the dW live-row table (bf16 routes) / live-granule list (fp32 route), whichever is larger
-        const size_t tab = (2 * (size_t)B + 2) * 8, lst = (bf || x3) ? 0 : dw_list_bytes(B, T, U1, 16);
-        L->counters = o; o += 1024 + align_up(tab > lst ? tab : lst);
-        if (bf || x2) o += align_up((size_t)L->n_split * 64);  // k_dw_bf16's / k_dw_x2's progress words, behind the table
-    }
+    // the control block + the dW live-row table (bf16 routes) / live-granule list (fp32 route), whichever is larger, + the progress words
+    const size_t tab = ControlBlock::dw_table_bytes(B), lst = (bf || x3) ? 0 : align_up(dw_list_bytes(B, T, U1, 16));
+    L->counters = o; o += sizeof(ControlBlock) + (tab > lst ? tab : lst) + ((bf || x2) ? align_up((size_t)L->n_split * 64) : 0);
     if (x2) { L->x2_live = o; o += align_up(x2_live_bytes(B, T, U1, (long)rows_pad)); }  // counts, tile flags and list, k-step and group bitmaps and lists (launch_x2_live)
     L->total = o;
     if (x3) {  // fp32 hidden + fp32 W pack of the stages that can run on the fp32 route's kernels (RNNT_VARIANT_X3_FP32_*):
@@ -217,24 +237,258 @@ void resolve_enc(const void *enc, const int64_t s[3], int B, int T, int H, float
     }
 }
 
-// compute units of the CURRENT device (the caller makes the tensors' device current); read-only
-// facts of the hardware, cached per device id
-int device_cus()
-{
-    static thread_local int cus[16] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-    if (!cus[dev]) {
-        hipDeviceProp_t p;
-        if (hipGetDeviceProperties(&p, dev) == hipSuccess) cus[dev] = p.multiProcessorCount;
-        if (cus[dev] <= 0) cus[dev] = 256;
-    }
-    return cus[dev];
-}
-
 enum { ST_PROD = 1, ST_FWD = 2, ST_LATTICE = 4, ST_COEF = 8, ST_DH = 16, ST_DH_RED = 32, ST_DW = 64,
        ST_DW_RED = 128, ST_ALL = 255 };
+// bits of the diagnostic word (-DRNNT_ABLATE builds) that are HOST-side experiments of the fp32 route
+enum { ABLATE_NO_HIDDEN = 8, ABLATE_SEPARATE_G = 32, ABLATE_SEPARATE_HIDDEN = 64, ABLATE_FWD_LDS_RING = 128, ABLATE_FWD_ONE_WG = 256 };
 
+// what the lattice and coefficient stages read (loss_stages): the fused routes' and the standalone loss entry's
+struct LossCall {
+    LossWs w;
+    const int32_t *targets, *logit_lens, *target_lens; float *costs;
+    int B, T, U1, stages /* ST_* mask */; float grad_scale, fastemit, delay; hipStream_t st;
+};
+
+// One fused call after validation: what the routes and the argument fillers read.  The standalone joint entries fill
+// what their launches read: fwd_args takes dims, the enc view, pred, bias and logits (cb may be null, w empty); bwd_args also ws, L, cb.
+struct FusedCall : LossCall {
+    int H, V, blank, n_cu;
+    const float *enc, *pred, *W, *bias; long enc_sb, enc_st;  // enc: the resolved view (resolve_enc)
+    float *grad_enc, *grad_pred, *grad_W, *grad_bias;
+    rnnt_engine_ws_layout L;
+    char *ws; ControlBlock *cb; float *logits;
+    bool separate_g, separate_hidden, fwd_lds_ring, fwd_one_wg_per_tile, no_hidden;  // the fp32 route's forms: RNNT_VARIANT_*, ABLATE_*
+    bool x3_fp32_fwd, x3_fp32_dh;  // split routes: the stage runs on the fp32 route's kernels (RNNT_VARIANT_X3_FP32_*, or a shape not covered)
+    bool x2_no_flush;              // f16x2: no cell is flushed (RNNT_VARIANT_X2_NO_FLUSH_SKIP, or a regularised loss)
+    int ablate; unsigned long long *debug;  // diagnostic builds: rnnt_engine_set_flags / rnnt_engine_set_debug, else 0 / NULL
+};
+float *f32_at(const FusedCall &c, size_t offset) { return (float *)(c.ws + offset); }
+
+// ---- the argument structs, each filled in one place (what a filler does not set is zero / NULL)
+JointFwdArgs fwd_args(const FusedCall &c, const float *wpack, const float *hidden, int make_hidden)
+{
+    JointFwdArgs f{};
+    f.enc = c.enc; f.enc_sb = c.enc_sb; f.enc_st = c.enc_st; f.pred = c.pred; f.logit_lens = c.logit_lens; f.target_lens = c.target_lens;
+    f.B = c.B; f.T = c.T; f.U1 = c.U1; f.H = c.H; f.V = c.V; f.blank = c.blank; f.ablate = c.ablate; f.debug = c.debug;
+    f.wpack = wpack; f.hidden = hidden; f.make_hidden = make_hidden; f.bias = c.bias; f.targets = c.targets; f.logits = c.logits;
+    f.denom_s = c.w.denom_s; f.lpb_s = c.w.lpb_s; f.lpe_s = c.w.lpe_s; f.D = c.L.D; f.counter = c.cb ? c.cb->fwd_tile : nullptr; f.n_cu = c.n_cu;
+    return f;
+}
+
+JointBwdArgs bwd_args(const FusedCall &c)
+{
+    JointBwdArgs g{};
+    g.enc = c.enc; g.enc_sb = c.enc_sb; g.enc_st = c.enc_st; g.pred = c.pred; g.logit_lens = c.logit_lens; g.target_lens = c.target_lens;
+    g.B = c.B; g.T = c.T; g.U1 = c.U1; g.H = c.H; g.V = c.V; g.blank = c.blank; g.ablate = c.ablate; g.debug = c.debug;
+    g.W = c.W; g.logits = c.logits; g.coef = c.w.coef; g.hidden = f32_at(c, c.L.hidden); g.rows_pad = (long)c.L.rows_pad;
+    g.slab_enc = f32_at(c, c.L.slab_enc); g.slab_pred = f32_at(c, c.L.slab_pred);
+    g.slab_w = f32_at(c, c.L.slab_w); g.slab_b = f32_at(c, c.L.slab_b);
+    g.grad_enc = c.grad_enc; g.grad_pred = c.grad_pred; g.grad_W = c.grad_W; g.grad_bias = c.grad_bias;
+    g.n_ublk = c.L.n_ublk; g.n_ttile = c.L.n_ttile; g.n_split = c.L.n_split;
+    g.counter = c.cb->queue; g.dw_tab = c.cb->dw_tab(); g.n_cu = c.n_cu;
+    g.gen_bu = dhidden_gen_bu(c.T, c.U1);  // u width of the fp32 route's dHidden tiles (the other routes: 16)
+    return g;
+}
+
+template <class Args> Args split_args(const FusedCall &c, size_t wpack_fwd_bytes)  // what Bf16Args and X3Args share; the dHidden pack lies behind the forward's
+{
+    Args h{};
+    h.enc = c.enc; h.enc_sb = c.enc_sb; h.enc_st = c.enc_st; h.pred = c.pred; h.logit_lens = c.logit_lens; h.target_lens = c.target_lens;
+    h.B = c.B; h.T = c.T; h.U1 = c.U1; h.H = c.H; h.V = c.V; h.blank = c.blank; h.ablate = c.ablate; h.debug = c.debug;
+    h.W = c.W; h.bias = c.bias; h.targets = c.targets; h.coef = c.w.coef; h.hidden = (unsigned short *)(c.ws + c.L.hidden);
+    h.denom_s = c.w.denom_s; h.lpb_s = c.w.lpb_s; h.lpe_s = c.w.lpe_s; h.D = c.L.D;
+    h.slab_enc = f32_at(c, c.L.slab_enc); h.slab_pred = f32_at(c, c.L.slab_pred);
+    h.slab_w = f32_at(c, c.L.slab_w); h.slab_b = f32_at(c, c.L.slab_b);
+    h.rows_pad = (long)c.L.rows_pad; h.rows_alloc = bf16_rows_alloc(c.L.rows_pad);
+    h.n_ublk = c.L.n_ublk; h.n_split = c.L.n_split; h.dw_tab = c.cb->dw_tab();
+    h.wpack_fwd = c.ws + c.L.wpack; h.wpack_dh = c.ws + c.L.wpack + align_up(wpack_fwd_bytes);
+    return h;
+}
+
+Bf16Args bf16_args(const FusedCall &c)
+{
+    Bf16Args h = split_args<Bf16Args>(c, bf16_wpack_fwd_bytes(c.H, c.V));
+    h.logits = (unsigned short *)c.logits; h.dw_prog = c.cb->dw_prog(c.B);
+    return h;
+}
+
+// f16x2 operand scales: |G| <= (1 + fastemit) grad_scale <= 2^e -> g_scale = 2^(13 - e); hidden: 2^14 (x2.hip).
+// (FastEmit adds lambda E (p_k - [k = y]) with E <= 1 to a cell's G: DESIGN.md §4k; the bound of the stand-in dHidden's split of G is the
+// same g_scale.)  flush_log2 / flush_lin: the flush rule's threshold (x2.hip), log2 of 2^-26 / g_scale and that value itself.
+struct OperandScales { float g_scale, dw_rescale, db_rescale; double flush_log2; float flush_lin; };
+OperandScales operand_scales(float grad_scale, float fastemit)
+{
+    OperandScales s; int e = 0;
+    (void)frexpf(grad_scale * (1.0f + fastemit), &e);
+    const int k = 13 - e < -100 ? -100 : (13 - e > 100 ? 100 : 13 - e);
+    s.g_scale = ldexpf(1.0f, k); s.flush_log2 = (double)(-26 - k); s.flush_lin = ldexpf(1.0f, -26 - k);
+    s.dw_rescale = 1.0f / (s.g_scale * 16384.0f); s.db_rescale = 1.0f / s.g_scale;
+    return s;
+}
+
+X3Args x3_args(const FusedCall &c, size_t wpack_fwd_bytes, const OperandScales &s)  // both split routes (f16x2 adds to it: route_f16x2)
+{
+    X3Args h = split_args<X3Args>(c, wpack_fwd_bytes);
+    h.g_scale = s.g_scale; h.dw_rescale = s.dw_rescale; h.db_rescale = s.db_rescale; h.scales = c.cb->x2_scales;
+    h.ep_enc = f32_at(c, c.L.ep); h.ep_pred = h.ep_enc + (size_t)c.B * c.T * c.H; h.ep_flag = c.cb->ep_flag;
+    h.logits = c.logits; h.g_lo = (unsigned short *)(c.ws + c.L.g_lo); h.n_ublk16 = (c.U1 + 15) / 16;
+    h.plane_stride = h.rows_alloc * (long)c.H; h.counter = c.cb->fwd_tile; h.n_cu = c.n_cu;
+    return h;
+}
+
+// lattice sweep and coefficients (every route): the delay penalty goes on lp_emit before the sweep and its cost shift comes off after it,
+// FastEmit's coefficients replace k_coef's; zero options launch exactly the plain loss's kernels.
+// flush_log2: the f16x2 route's threshold (lattice.hip coef_cell), or null: the plain coefficients
+void loss_stages(const LossCall &c, const double *flush_log2 = nullptr, float flush_lin = 0.f)
+{
+    const LossWs &w = c.w; const int D = c.T + c.U1 - 1;
+    if (c.stages & ST_LATTICE) {
+        if (c.delay > 0.f) launch_delay_penalty(w.lpe_s, c.logit_lens, c.target_lens, c.B, c.T, c.U1, D, c.delay, c.st);
+        launch_lattice(w.lpb_s, w.lpe_s, w.alpha_s, w.beta_s, c.logit_lens, c.target_lens, c.costs, c.B, c.U1, D, w.err, c.st);
+        if (c.delay > 0.f) launch_delay_cost(w.beta_s, c.logit_lens, c.target_lens, c.costs, c.B, c.T, c.U1, D, c.delay, c.st);
+    }
+    if (c.stages & ST_COEF) {
+        if (c.fastemit > 0.f)
+            launch_coef_fastemit(w.alpha_s, w.beta_s, w.denom_s, w.lpb_s, w.lpe_s, c.targets, c.logit_lens, c.target_lens, w.coef,
+                                 c.B, c.T, c.U1, D, c.grad_scale, c.fastemit, c.st);
+        else if (flush_log2)
+            launch_coef_flush(w.alpha_s, w.beta_s, w.denom_s, w.lpb_s, w.lpe_s, c.targets, c.logit_lens, c.target_lens, w.coef,
+                              c.B, c.T, c.U1, D, c.grad_scale, *flush_log2, flush_lin, c.st);
+        else
+            launch_coef(w.alpha_s, w.beta_s, w.denom_s, w.lpb_s, w.lpe_s, c.targets, c.logit_lens, c.target_lens, w.coef,
+                        c.B, c.T, c.U1, D, c.grad_scale, c.st);
+    }
+}
+
+void zero_unwritten_hidden(const FusedCall &c, float *hidden)  // what a forward filling fp32 hidden leaves: padding rows, dead cells
+{
+    const size_t cells = (size_t)c.B * c.T * c.U1;
+    launch_fill32(hidden + cells * c.H, 0u, (c.L.rows_pad + 16 - cells) * c.H * 4, c.st);
+    launch_zero_dead_hidden(hidden, c.logit_lens, c.target_lens, c.B, c.T, c.U1, c.H, c.st);
+}
+
+// columns the fp32 route's tile kernel (k_dhidden_gen) takes at this shape: whole groups of 512, 8-row dPred slabs; 0: the persistent k_dhidden on every column
+int tile_kernel_cols(const FusedCall &c) { return dhidden_gen_ok(c.H, c.V, c.U1) ? 512 * dhidden_gen_groups(c.H) : 0; }
+
+// The split routes' stand-in stages: the fp32 route's kernel in place of a split one, on the fp32 hidden and W pack in `aux`
+float *aux_hidden(const FusedCall &c) { return f32_at(c, c.L.aux); }
+typedef void (*x3_launcher)(const X3Args &, hipStream_t);
+
+void standin_forward(const FusedCall &c, const X3Args &h, x3_launcher make_hidden)
+{
+    float *wpack = (float *)(c.ws + c.L.aux + align_up((c.L.rows_pad + 16) * (size_t)c.H * 4));
+    if (c.stages & ST_PROD) { zero_unwritten_hidden(c, aux_hidden(c)); launch_pack_w_fwd(c.W, wpack, c.H, c.V, c.st); }
+    if (c.stages & ST_FWD) {
+        JointFwdArgs f = fwd_args(c, wpack, aux_hidden(c), 1);
+        f.ablate = 0; f.debug = nullptr;  // a stand-in takes no part in a diagnostic build's experiments
+        launch_joint_fwd(f, c.st); make_hidden(h, c.st);  // then the planes the backward reads
+    }
+}
+
+void standin_dhidden(const FusedCall &c, const JointBwdArgs &g, const X3Args &h, x3_launcher split_g)
+{
+    const bool tile = g.pred_split_col > 0;
+    if (!tile) launch_make_g(g, c.st);
+    launch_dhidden(g, tile, c.st);  // leaves fp32 G in place of the logits
+    split_g(h, c.st);               // -> the route's planes in place (bf16x3: lo beside)
+}
+
+int route_fp32(const FusedCall &c)
+{
+    JointBwdArgs g = bwd_args(c);
+    // G inside the dHidden GEMM unless the shape needs the separate pass (k_make_g, then the persistent k_dhidden on every column).
+    // RNNT_VARIANT_SEPARATE_G runs k_make_g at a shape the tile kernel takes: the tile kernel then READS G in its first column group too
+    // (GEN = false) and forms every sum in the default order — bit-identical results, as the header says
+    const bool tile = (g.pred_split_col = tile_kernel_cols(c)) > 0, fuse_g = tile && !c.separate_g;
+    g.g_ready = tile && !fuse_g;
+    // hidden (A operand of all three GEMMs) is produced by the forward kernel for its own tile unless the separate k_make_hidden pass is asked for
+    const bool fuse_hid = !c.separate_hidden && !c.no_hidden;
+    float *wpack = (float *)(c.ws + c.L.wpack);
+    if (c.stages & ST_PROD) {
+        if (fuse_hid) zero_unwritten_hidden(c, g.hidden);
+        else launch_make_hidden(g, c.st);
+        launch_pack_w_fwd(c.W, wpack, c.H, c.V, c.st);
+    }
+    if (c.stages & ST_FWD)
+        launch_joint_fwd(fwd_args(c, wpack, c.no_hidden ? nullptr : g.hidden, fuse_hid ? 1 : 0), c.st, c.fwd_lds_ring, c.fwd_one_wg_per_tile);
+    loss_stages(c);
+    if ((c.stages & ST_COEF) && !fuse_g) launch_make_g(g, c.st);  // logits -> G in place
+    if (c.stages & ST_DH) launch_dhidden(g, tile, c.st);
+    if (c.stages & ST_DH_RED) launch_dhidden_reduce(g, c.st);
+    if (c.stages & ST_DW) launch_dw(g, c.st);
+    if (c.stages & ST_DW_RED) launch_dw_reduce(g, c.st);
+    return launch_status("rnnt_engine fused pipeline");
+}
+
+int route_bf16(const FusedCall &c)
+{
+    const Bf16Args h = bf16_args(c);
+    JointBwdArgs g = bwd_args(c); g.gen_bu = 16; g.pred_split_col = c.H;  // the reductions: 16-wide u tiles, every dPred slab 8 t-rows high
+    if (c.stages & ST_PROD) launch_bf16_producers(h, c.st);
+    if (c.stages & ST_FWD) launch_joint_fwd_bf16(h, c.st);  // softmax statistics in its epilogue
+    loss_stages(c);
+    if (c.stages & ST_DH) launch_dhidden_bf16(h, c.st);
+    if (c.stages & ST_DH_RED) launch_dhidden_reduce(g, c.st);
+    if (c.stages & ST_DW) launch_dw_bf16(h, c.st);
+    if (c.stages & ST_DW_RED) launch_dw_reduce(g, c.st);
+    return launch_status("rnnt_engine fused pipeline (bf16)");
+}
+
+// fp32-accurate route on the bf16 matrix pipes (x3.hip)
+int route_bf16x3(const FusedCall &c)
+{
+    const X3Args h = x3_args(c, x3_wpack_fwd_bytes(c.H, c.V), operand_scales(c.grad_scale, c.fastemit));
+    JointBwdArgs g = bwd_args(c); g.hidden = aux_hidden(c);  // the fp32 kernels' view: the dHidden reductions', the stand-in dHidden's
+    if (c.x3_fp32_dh) g.pred_split_col = tile_kernel_cols(c);
+    else { g.gen_bu = 16; g.pred_split_col = c.H; }  // x3 / x2 tiles: 8 t x 16 u, every dPred slab 8 t rows high
+    if (c.stages & ST_PROD) { launch_x3_zero_padding(h, 1, c.st); launch_x3_pack_w(h, c.st); }
+    if (c.x3_fp32_fwd) standin_forward(c, h, launch_x3_make_hidden);
+    else if (c.stages & ST_FWD) launch_joint_fwd_x3(h, c.st);
+    loss_stages(c);
+    if (c.stages & ST_DH) {
+        launch_x3_zero_padding(h, 2, c.st);
+        if (c.x3_fp32_dh) standin_dhidden(c, g, h, launch_x3_split_g);  // -> hi | mid in place, lo beside
+        else launch_dhidden_x3(h, c.st);
+    }
+    if (c.stages & ST_DH_RED) launch_dhidden_reduce(g, c.st);
+    if (c.stages & ST_DW) launch_dw_x3(h, c.st);
+    if (c.stages & ST_DW_RED) launch_dw_reduce(g, c.st);
+    return launch_status("rnnt_engine fused pipeline (bf16x3)");
+}
+
+// the same stages on two fp16 planes and three products (x2.hip), with the flush rule: dHidden / dW walk the live tiles / groups only
+int route_f16x2(const FusedCall &c)
+{
+    OperandScales s = operand_scales(c.grad_scale, c.fastemit);
+    X3Args h = x3_args(c, x2_wpack_fwd_bytes(c.H, c.V), s);
+    h.dw_prog = c.cb->dw_prog(c.B); h.dw_ksteps = x2_dw_walks_ksteps(c.H, c.V) ? 1 : 0;
+    x2_live_carve(c.ws + c.L.x2_live, c.B, c.T, c.U1, (long)c.L.rows_pad, h);
+    JointBwdArgs g = bwd_args(c); g.hidden = aux_hidden(c);  // the fp32 kernels' view: the dHidden reductions', the stand-in dHidden's
+    if (c.x3_fp32_dh) g.pred_split_col = tile_kernel_cols(c);
+    else { g.gen_bu = 16; g.pred_split_col = c.H; }  // x3 / x2 tiles: 8 t x 16 u, every dPred slab 8 t rows high
+    // k_dhidden_x2 runs the live tiles only and no dead tile writes a slab: the reductions skip by the same flags
+    if (!c.x3_fp32_dh) { g.tile_flag = h.tile_live; g.flag_ntt = (c.T + 7) / 8; g.flag_nub = h.n_ublk16; }
+    // The threshold; -inf flags nothing.  The fp32 kernels standing in for dHidden multiply G in fp32, where a flushed cell's G is small but not
+    // zero: no flush, no tile skipping there (k_x2_split_g writes every row, so the dW list walk still applies)
+    if (c.x2_no_flush || c.x3_fp32_dh) { s.flush_log2 = -HUGE_VAL; s.flush_lin = 0.f; }
+    if (c.stages & ST_PROD) { launch_x2_zero_padding(h, 1, c.st); launch_x2_pack_w(h, c.cb->x2_scales, c.st); launch_x2_make_ep(h, c.st); }
+    if (c.x3_fp32_fwd) standin_forward(c, h, launch_x2_make_hidden);
+    else if (c.stages & ST_FWD) launch_joint_fwd_x2(h, c.st);
+    loss_stages(c, &s.flush_log2, s.flush_lin);
+    if (c.stages & ST_COEF) launch_x2_live(h, c.st);  // tile flags, k-step and group bitmaps / lists, counts: from the coefficients
+    if (c.stages & ST_DH) {
+        launch_x2_zero_padding(h, 2, c.st);
+        // (dead rows: those of dead tiles inside live groups — k_dw_x2m: k-steps —, zeros for dW; disjoint from the live tiles' rows)
+        if (c.x3_fp32_dh) standin_dhidden(c, g, h, launch_x2_split_g);
+        else { launch_x2_dead_rows(h, c.st); launch_dhidden_x2(h, c.st); }
+    }
+    if (c.stages & ST_DH_RED) launch_dhidden_reduce(g, c.st);
+    if (c.stages & ST_DW) launch_dw_x2(h, c.st);
+    if (c.stages & ST_DW_RED) launch_dw_reduce_x2(h, c.grad_W, c.grad_bias, c.st);  // one rounding: dW does not follow where the splits cut the live list
+    return launch_status("rnnt_engine fused pipeline (f16x2)");
+}
+
+// Every fused entry: validation (everything that can fail does so here, before anything is launched), the call context, the route.
 int run_fused(int stages, int variant, const void *enc, const int64_t enc_strides[3], const void *pred,
               const void *W, const void *bias, const int32_t *targets, const int32_t *logit_lens,
               const int32_t *target_lens, int B, int T, int U1, int H, int V, int blank,
@@ -261,252 +515,37 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
     if (variant & RNNT_VARIANT_LAB_MASK)
         return fail(RNNT_ERR_UNSUPPORTED, "variant bits 0x%x are reserved: no kernel of librnnt_engine.so answers to them",
                     variant & RNNT_VARIANT_LAB_MASK);
-    const int xflags = g_flags | (variant & (RNNT_VARIANT_SEPARATE_G | RNNT_VARIANT_SEPARATE_HIDDEN |
-                                             RNNT_VARIANT_FWD_LDS_RING | RNNT_VARIANT_FWD_ONE_WG_PER_TILE |
-                                             RNNT_VARIANT_X3_FP32_FWD | RNNT_VARIANT_X3_FP32_DH));
-    const bool no_flush = (variant & RNNT_VARIANT_X2_NO_FLUSH_SKIP) != 0 || fastemit > 0.f || delay > 0.f;
-    rnnt_engine_ws_layout L;
-    layout(B, T, U1, H, V, dtype, &L);
-    if (ws_bytes < L.total)
-        return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, L.total);
-
-    hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    float *logits = (float *)(ws + L.logits);
-    float *denom_s = (float *)(ws + L.denom_s), *lpb_s = (float *)(ws + L.lpb_s),
-          *lpe_s = (float *)(ws + L.lpe_s);
-    double *alpha_s = (double *)(ws + L.alpha_s), *beta_s = (double *)(ws + L.beta_s);
-    CellCoef *coef = (CellCoef *)(ws + L.coef);
-    float *wpack = (float *)(ws + L.wpack);
-
-    const float *encp; long esb, est;
-    resolve_enc(enc, enc_strides, B, T, H, (float *)(ws + L.enc_copy), st, &encp, &esb, &est);
-    // lattice sweep and coefficients (every route): the delay penalty goes on lp_emit before the sweep and its cost
-    // shift comes off after it, FastEmit's coefficients replace k_coef's; zero options launch exactly
-    // the plain loss's kernels
-    // (flush: the f16x2 route's threshold — lattice.hip coef_cell — or null: the plain coefficients)
-    auto loss_stages = [&](const double *flush_log2 = nullptr, float flush_lin = 0.f) {
-        if (stages & ST_LATTICE) {
-            if (delay > 0.f) launch_delay_penalty(lpe_s, logit_lens, target_lens, B, T, U1, L.D, delay, st);
-            launch_lattice(lpb_s, lpe_s, alpha_s, beta_s, logit_lens, target_lens, costs, B, U1, L.D,
-                           (unsigned *)(ws + L.counters + 768), st);
-            if (delay > 0.f) launch_delay_cost(beta_s, logit_lens, target_lens, costs, B, T, U1, L.D, delay, st);
-        }
-        if (stages & ST_COEF) {
-            if (fastemit > 0.f)
-                launch_coef_fastemit(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef,
-                                     B, T, U1, L.D, grad_scale, fastemit, st);
-            else if (flush_log2)
-                launch_coef_flush(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef,
-                                  B, T, U1, L.D, grad_scale, *flush_log2, flush_lin, st);
-            else
-                launch_coef(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef,
-                            B, T, U1, L.D, grad_scale, st);
-        }
-    };
-
-    JointBwdArgs g;
-    g.enc = encp; g.enc_sb = esb; g.enc_st = est; g.pred = (const float *)pred;
-    g.W = (const float *)W; g.logits = logits; g.coef = coef; g.logit_lens = logit_lens; g.target_lens = target_lens;
-    g.hidden = (float *)(ws + L.hidden); g.rows_pad = (long)L.rows_pad;
-    g.slab_enc = (float *)(ws + L.slab_enc); g.slab_pred = (float *)(ws + L.slab_pred);
-    g.slab_w = (float *)(ws + L.slab_w); g.slab_b = (float *)(ws + L.slab_b);
-    g.grad_enc = (float *)grad_enc; g.grad_pred = (float *)grad_pred;
-    g.grad_W = (float *)grad_W; g.grad_bias = (float *)grad_bias;
-    g.B = B; g.T = T; g.U1 = U1; g.H = H; g.V = V; g.blank = blank;
-    g.n_ublk = L.n_ublk; g.n_ttile = L.n_ttile; g.n_split = L.n_split;
-    g.counter = (unsigned *)(ws + L.counters); g.dw_tab = (long *)(ws + L.counters + 1024); g.n_cu = device_cus(); g.flags = xflags & ~16; g.g_ready = 0; g.debug = g_debug; g.pred_split_col = 0;
-    g.gen_bu = dtype == RNNT_DTYPE_BF16 ? 16 : dhidden_gen_bu(T, U1);  // u width of the dHidden tiles
-    g.tile_flag = nullptr; g.flag_ntt = 0; g.flag_nub = 0;  // (f16x2 route: below)
+    FusedCall c{};
+    layout(B, T, U1, H, V, dtype, &c.L);
+    if (ws_bytes < c.L.total)
+        return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, c.L.total);
+    c.ablate = g_flags; c.debug = g_debug;
+    const int xp = dtype == RNNT_DTYPE_F32 ? c.ablate : 0;  // the fp32 route's host-side experiments (no kernel of that route reads these bits)
+    c.separate_g = (variant & RNNT_VARIANT_SEPARATE_G) != 0 || (xp & ABLATE_SEPARATE_G) != 0;
+    c.separate_hidden = (variant & RNNT_VARIANT_SEPARATE_HIDDEN) != 0 || (xp & ABLATE_SEPARATE_HIDDEN) != 0;
+    c.fwd_lds_ring = (variant & RNNT_VARIANT_FWD_LDS_RING) != 0 || (xp & ABLATE_FWD_LDS_RING) != 0;
+    c.fwd_one_wg_per_tile = (variant & RNNT_VARIANT_FWD_ONE_WG_PER_TILE) != 0 || (xp & ABLATE_FWD_ONE_WG) != 0;
+    c.no_hidden = (xp & ABLATE_NO_HIDDEN) != 0;
+    c.x2_no_flush = (variant & RNNT_VARIANT_X2_NO_FLUSH_SKIP) != 0 || fastemit > 0.f || delay > 0.f;
     if (dtype == RNNT_DTYPE_F32_BF16X3 || dtype == RNNT_DTYPE_F32_F16X2) {
-        // RNNT_DTYPE_F32_F16X2 (x2.hip): the same stages on two fp16 planes and three products; operand scales below
         const bool x2 = dtype == RNNT_DTYPE_F32_F16X2;
-        // fp32-accurate route on the bf16 matrix pipes (x3.hip).  Stage by stage the fp32 route's own kernel can
-        // stand in (RNNT_VARIANT_X3_FP32_FWD / _DH): same data, one stage swapped — how each x3 kernel is checked.
-        X3Args h;
-        h.tile_live = nullptr; h.ks_bitmap = nullptr; h.ks_list = nullptr; h.live_stats = nullptr; h.tile_list = nullptr;
-        h.grp_bitmap = nullptr; h.grp_list = nullptr; h.dw_ksteps = 0;
-        double flush_log2 = -HUGE_VAL;  // the flush rule's threshold (x2.hip): log2 of 2^-26 / g_scale; -inf flags nothing
-        float flush_lin = 0.f;
-        h.enc = encp; h.enc_sb = esb; h.enc_st = est; h.pred = (const float *)pred;
-        h.W = (const float *)W; h.bias = (const float *)bias;
-        h.rows_pad = (long)L.rows_pad; h.rows_alloc = bf16_rows_alloc(L.rows_pad);
-        h.hidden = (unsigned short *)(ws + L.hidden); h.plane_stride = h.rows_alloc * (long)H;
-        h.wpack_fwd = ws + L.wpack; h.wpack_dh = ws + L.wpack + align_up(x2 ? x2_wpack_fwd_bytes(H, V) : x3_wpack_fwd_bytes(H, V));
-        {   // f16x2 operand scales: |G| <= (1 + fastemit) grad_scale <= 2^e -> g_scale = 2^(13 - e); hidden: 2^14 (x2.hip).
-            // (FastEmit adds lambda E (p_k - [k = y]) with E <= 1 to a cell's G: DESIGN.md §4k; the bound of the f32_dh
-            // fallback's split of G is the same g_scale)
-            int e = 0;
-            (void)frexpf(grad_scale * (1.0f + fastemit), &e);
-            const int k = 13 - e < -100 ? -100 : (13 - e > 100 ? 100 : 13 - e);
-            h.g_scale = ldexpf(1.0f, k);
-            if (x2 && !no_flush) { flush_log2 = (double)(-26 - k); flush_lin = ldexpf(1.0f, -26 - k); }
-            h.dw_rescale = 1.0f / (h.g_scale * 16384.0f); h.db_rescale = 1.0f / h.g_scale;
-            h.scales = (const float *)(ws + L.counters + 640);
-            h.dw_prog = x2 ? (int *)(ws + L.counters + 1024 + align_up((2 * (size_t)B + 2) * 8)) : nullptr;
-            h.ep_enc = (float *)(ws + L.ep); h.ep_pred = h.ep_enc + (size_t)B * T * H;
-            h.ep_flag = (unsigned *)(ws + L.counters + 896);
-        }
-        h.logits = logits; h.g_lo = (unsigned short *)(ws + L.g_lo); h.coef = coef;
-        h.targets = targets; h.logit_lens = logit_lens; h.target_lens = target_lens;
-        h.denom_s = denom_s; h.lpb_s = lpb_s; h.lpe_s = lpe_s; h.D = L.D;
-        h.slab_enc = g.slab_enc; h.slab_pred = g.slab_pred; h.slab_w = g.slab_w; h.slab_b = g.slab_b;
-        h.B = B; h.T = T; h.U1 = U1; h.H = H; h.V = V; h.blank = blank;
-        h.n_ublk = L.n_ublk; h.n_split = L.n_split; h.flags = xflags; h.n_ublk16 = (U1 + 15) / 16;
-        h.dw_tab = (long *)(ws + L.counters + 1024);
-        h.counter = (unsigned *)(ws + L.counters + 512); h.n_cu = device_cus(); h.debug = g_debug;
-        const bool f32_dh = (xflags & RNNT_VARIANT_X3_FP32_DH) != 0 || !(x2 ? x2_dhidden_ok(U1, H, V) : x3_dhidden_ok(U1, H, V));
-        const bool f32_fwd = (xflags & RNNT_VARIANT_X3_FP32_FWD) != 0 || !(x2 ? x2_fwd_ok(U1, H, V) : x3_fwd_ok(U1, H, V)) || f32_dh;  // fp32 dHidden reads fp32 hidden
-        if ((f32_fwd || f32_dh) && ws_bytes < L.total + L.aux_bytes)
+        c.x3_fp32_dh = (variant & RNNT_VARIANT_X3_FP32_DH) != 0 || !(x2 ? x2_dhidden_ok(U1, H, V) : x3_dhidden_ok(U1, H, V));
+        c.x3_fp32_fwd = (variant & RNNT_VARIANT_X3_FP32_FWD) != 0 || !(x2 ? x2_fwd_ok(U1, H, V) : x3_fwd_ok(U1, H, V)) || c.x3_fp32_dh;  // fp32 dHidden reads fp32 hidden
+        if (c.x3_fp32_fwd && ws_bytes < c.L.total + c.L.aux_bytes)
             return fail(RNNT_ERR_WORKSPACE, "workspace %zu < %zu bytes: a stage on the fp32 route's kernels (RNNT_VARIANT_X3_FP32_*, or a "
                         "shape k_joint_fwd_x3 / k_dhidden_x3 do not cover) needs total + aux_bytes of rnnt_engine_workspace_layout",
-                        ws_bytes, L.total + L.aux_bytes);
-        if (x2) {
-            x2_live_carve(ws + L.x2_live, B, T, U1, (long)L.rows_pad, h);
-            h.dw_ksteps = x2_dw_walks_ksteps(H, V) ? 1 : 0;
-            // the fp32 kernels standing in for dHidden multiply G in fp32, where a flushed cell's G is small but not zero: no flush, no tile
-            // skipping there (k_x2_split_g writes every row, so the dW list walk still applies)
-            if (f32_dh) { flush_log2 = -HUGE_VAL; flush_lin = 0.f; }
-        }
-        float *hid32 = (float *)(ws + L.aux);
-        float *wpack32 = (float *)(ws + L.aux + align_up((L.rows_pad + 16) * (size_t)H * 4));
-        g.hidden = hid32;
-        const bool fuse_g32 = dhidden_gen_ok(H, V, U1);
-        if (f32_dh) {
-            if (fuse_g32) { g.flags |= 16; g.pred_split_col = 512 * dhidden_gen_groups(H); }
-        } else {
-            g.gen_bu = 16; g.pred_split_col = H;  // x3 tiles: 8 t x 16 u, every dPred slab 8 t rows high
-            // f16x2: k_dhidden_x2 runs the live tiles only and no dead tile writes a slab: the reductions skip by the same flags
-            if (x2) { g.tile_flag = h.tile_live; g.flag_ntt = (T + 7) / 8; g.flag_nub = h.n_ublk16; }
-        }
-        if (stages & ST_PROD) {
-            if (x2) { launch_x2_zero_padding(h, 1, st); launch_x2_pack_w(h, (float *)(ws + L.counters + 640), st); launch_x2_make_ep(h, st); }
-            else { launch_x3_zero_padding(h, 1, st); launch_x3_pack_w(h, st); }
-            if (f32_fwd) {
-                const size_t cells = (size_t)B * T * U1;
-                launch_fill32(hid32 + cells * H, 0u, (L.rows_pad + 16 - cells) * H * 4, st);
-                launch_zero_dead_hidden(hid32, logit_lens, target_lens, B, T, U1, H, st);
-                launch_pack_w_fwd((const float *)W, wpack32, H, V, st);
-            }
-        }
-        if (stages & ST_FWD) {
-            if (f32_fwd) {
-                JointFwdArgs f;
-                f.enc = encp; f.enc_sb = esb; f.enc_st = est; f.pred = (const float *)pred;
-                f.wpack = wpack32; f.hidden = hid32; f.bias = (const float *)bias; f.targets = targets;
-                f.logit_lens = logit_lens; f.target_lens = target_lens; f.logits = logits;
-                f.denom_s = denom_s; f.lpb_s = lpb_s; f.lpe_s = lpe_s;
-                f.B = B; f.T = T; f.U1 = U1; f.H = H; f.V = V; f.D = L.D; f.blank = blank; f.flags = 0; f.debug = nullptr;
-                f.make_hidden = 1; f.counter = h.counter; f.n_cu = h.n_cu;
-                launch_joint_fwd(f, st);
-                if (x2) launch_x2_make_hidden(h, st);
-                else launch_x3_make_hidden(h, st);  // the planes the backward reads
-            } else if (x2) {
-                launch_joint_fwd_x2(h, st);
-            } else {
-                launch_joint_fwd_x3(h, st);
-            }
-        }
-        if (x2) {
-            loss_stages(&flush_log2, flush_lin);
-            if (stages & ST_COEF) launch_x2_live(h, st);  // tile flags, k-step and group bitmaps / lists, counts: from the coefficients
-        } else {
-            loss_stages();
-        }
-        if (stages & ST_DH) {
-            if (x2) launch_x2_zero_padding(h, 2, st);
-            else launch_x3_zero_padding(h, 2, st);
-            if (f32_dh) {
-                if (!fuse_g32) launch_make_g(g, st);
-                launch_dhidden(g, st);     // leaves fp32 G in place of the logits
-                if (x2) launch_x2_split_g(h, st);
-                else launch_x3_split_g(h, st);  // -> hi | mid in place, lo beside
-            } else if (x2) {
-                launch_x2_dead_rows(h, st);  // rows of dead tiles inside live groups (k_dw_x2m: k-steps): zeros for dW (disjoint from the live tiles' rows)
-                launch_dhidden_x2(h, st);
-            } else {
-                launch_dhidden_x3(h, st);
-            }
-        }
-        if (stages & ST_DH_RED) launch_dhidden_reduce(g, st);
-        if (stages & ST_DW) {
-            if (x2) launch_dw_x2(h, st);
-            else launch_dw_x3(h, st);
-        }
-        if (stages & ST_DW_RED) {
-            if (x2) launch_dw_reduce_x2(h, g.grad_W, g.grad_bias, st);  // one rounding: dW does not follow where the splits cut the live list
-            else launch_dw_reduce(g, st);
-        }
-        return launch_status(x2 ? "rnnt_engine fused pipeline (f16x2)" : "rnnt_engine fused pipeline (bf16x3)");
+                        ws_bytes, c.L.total + c.L.aux_bytes);
     }
-    if (dtype == RNNT_DTYPE_BF16) {
-        Bf16Args h;
-        h.enc = encp; h.enc_sb = esb; h.enc_st = est; h.pred = (const float *)pred;
-        h.W = (const float *)W; h.bias = (const float *)bias;
-        h.hidden = (unsigned short *)(ws + L.hidden);
-        h.wpack_fwd = ws + L.wpack; h.wpack_dh = ws + L.wpack + align_up(bf16_wpack_fwd_bytes(H, V));
-        h.logits = (unsigned short *)logits; h.coef = coef; h.logit_lens = logit_lens;
-        h.targets = targets; h.target_lens = target_lens;
-        h.denom_s = denom_s; h.lpb_s = lpb_s; h.lpe_s = lpe_s; h.D = L.D;
-        h.slab_enc = g.slab_enc; h.slab_pred = g.slab_pred; h.slab_w = g.slab_w; h.slab_b = g.slab_b;
-        h.rows_pad = (long)L.rows_pad; h.rows_alloc = bf16_rows_alloc(L.rows_pad);
-        h.B = B; h.T = T; h.U1 = U1; h.H = H; h.V = V; h.blank = blank;
-        h.n_ublk = L.n_ublk; h.n_split = L.n_split; h.flags = xflags;
-        h.dw_tab = (long *)(ws + L.counters + 1024);
-        h.dw_prog = (int *)(ws + L.counters + 1024 + align_up((2 * (size_t)B + 2) * 8));
-        g.pred_split_col = H;  // reductions: every dPred slab is 8 t-rows high, as in k_dhidden_gen
-        h.debug = g_debug;
-        if (stages & ST_PROD) launch_bf16_producers(h, st);
-        if (stages & ST_FWD) launch_joint_fwd_bf16(h, st);  // softmax statistics in its epilogue
-        loss_stages();
-        if (stages & ST_DH) launch_dhidden_bf16(h, st);
-        if (stages & ST_DH_RED) launch_dhidden_reduce(g, st);
-        if (stages & ST_DW) launch_dw_bf16(h, st);
-        if (stages & ST_DW_RED) launch_dw_reduce(g, st);
-        return launch_status("rnnt_engine fused pipeline (bf16)");
-    }
-    // G inside the dHidden GEMM unless the shape needs the separate pass (k_make_g, then the persistent k_dhidden on every column).
-    // Flag 32 (RNNT_VARIANT_SEPARATE_G) runs k_make_g at a shape the tile kernel takes: the tile kernel then READS G in its first
-    // column group too (GEN = false) and forms every sum in the default order — bit-identical results, as the header says
-    const bool gen_ok = dhidden_gen_ok(H, V, U1);
-    const bool fuse_g = gen_ok && !(xflags & 32);
-    if (gen_ok) { g.flags |= 16; g.pred_split_col = 512 * dhidden_gen_groups(H); }  // columns on the tile kernel (8-row dPred slabs)
-    g.g_ready = gen_ok && !fuse_g;
-
-    // hidden (A operand of all three GEMMs) is produced by the forward kernel for its own tile
-    // unless flag 64 asks for the separate k_make_hidden pass
-    const bool fuse_hid = !(xflags & 64) && !(xflags & 8);
-    if (stages & ST_PROD) {
-        if (fuse_hid) {  // only the zero padding rows the dW GEMM walks past the last cell
-            const size_t cells = (size_t)B * T * U1;
-            launch_fill32(g.hidden + cells * H, 0u, (L.rows_pad + 16 - cells) * H * 4, st);
-            // and the dead cells next to lattice cells (the forward writes lattice cells only)
-            launch_zero_dead_hidden(g.hidden, logit_lens, target_lens, B, T, U1, H, st);
-        } else {
-            launch_make_hidden(g, st);
-        }
-        launch_pack_w_fwd((const float *)W, wpack, H, V, st);
-    }
-    if (stages & ST_FWD) {
-        JointFwdArgs f;
-        f.enc = encp; f.enc_sb = esb; f.enc_st = est; f.pred = (const float *)pred;
-        f.wpack = wpack; f.hidden = (xflags & 8) ? nullptr : g.hidden; f.bias = (const float *)bias; f.targets = targets;
-        f.logit_lens = logit_lens; f.target_lens = target_lens; f.logits = logits;
-        f.denom_s = denom_s; f.lpb_s = lpb_s; f.lpe_s = lpe_s;
-        f.B = B; f.T = T; f.U1 = U1; f.H = H; f.V = V; f.D = L.D; f.blank = blank; f.flags = xflags; f.debug = g_debug;
-        f.make_hidden = fuse_hid ? 1 : 0;
-        f.counter = (unsigned *)(ws + L.counters + 512); f.n_cu = device_cus();
-        launch_joint_fwd(f, st);
-    }
-    loss_stages();
-    {
-        if ((stages & ST_COEF) && !fuse_g) launch_make_g(g, st);  // logits -> G in place
-        if (stages & ST_DH) launch_dhidden(g, st);
-        if (stages & ST_DH_RED) launch_dhidden_reduce(g, st);
-        if (stages & ST_DW) launch_dw(g, st);
-        if (stages & ST_DW_RED) launch_dw_reduce(g, st);
-    }
-    return launch_status("rnnt_engine fused pipeline");
+    c.B = B; c.T = T; c.U1 = U1; c.H = H; c.V = V; c.blank = blank; c.pred = (const float *)pred; c.W = (const float *)W;
+    c.bias = (const float *)bias; c.targets = targets; c.logit_lens = logit_lens; c.target_lens = target_lens; c.costs = costs;
+    c.grad_enc = (float *)grad_enc; c.grad_pred = (float *)grad_pred; c.grad_W = (float *)grad_W; c.grad_bias = (float *)grad_bias;
+    c.stages = stages; c.grad_scale = grad_scale; c.fastemit = fastemit; c.delay = delay; c.n_cu = device_cus(); c.st = (hipStream_t)stream;
+    c.ws = (char *)workspace; c.cb = (ControlBlock *)(c.ws + c.L.counters); c.logits = f32_at(c, c.L.logits);
+    c.w = carve_loss_ws(c.ws + c.L.denom_s, B, T, U1); c.w.err = c.cb->lattice_err;  // (layout() places the arrays by the same carve)
+    resolve_enc(enc, enc_strides, B, T, H, f32_at(c, c.L.enc_copy), c.st, &c.enc, &c.enc_sb, &c.enc_st);
+    if (dtype == RNNT_DTYPE_BF16) return route_bf16(c);
+    if (dtype == RNNT_DTYPE_F32_BF16X3) return route_bf16x3(c);
+    return dtype == RNNT_DTYPE_F32_F16X2 ? route_f16x2(c) : route_fp32(c);
 }
 
 }  // namespace
@@ -576,8 +615,7 @@ int rnnt_engine_loss_workspace_bytes(int B, int T, int U1, int V, int dtype, siz
 {
     if (!out) return fail(RNNT_ERR_INVALID_ARG, "null size pointer");
     if (int rc = check_dims(B, T, U1, 4, V, dtype, false)) return rc;
-    const size_t D = (size_t)T + U1 - 1, skew = (size_t)B * D * U1, cells = (size_t)B * T * U1;
-    *out = 3 * align_up(skew * 4) + 2 * align_up(skew * 8) + align_up(cells * 16) + 256;  // + error word
+    *out = carve_loss_ws(nullptr, B, T, U1).bytes;
     return RNNT_OK;
 }
 
@@ -603,19 +641,14 @@ int rnnt_engine_joint_fwd(const void *enc, const int64_t enc_strides[3], const v
     size_t need;
     rnnt_engine_joint_fwd_workspace_bytes(B, T, U1, H, V, dtype, &need);
     if (ws_bytes < need) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    float *wpack = (float *)ws;
-    float *enc_copy = (float *)(ws + align_up(wpack_floats(H, V) * 4));
-    const float *encp; long esb, est;
-    resolve_enc(enc, enc_strides, B, T, H, enc_copy, st, &encp, &esb, &est);
-    launch_pack_w_fwd((const float *)W, wpack, H, V, st);
-    JointFwdArgs f;
-    memset(&f, 0, sizeof f);
-    f.enc = encp; f.enc_sb = esb; f.enc_st = est; f.pred = (const float *)pred; f.wpack = wpack;
-    f.bias = (const float *)bias; f.logits = (float *)logits;
-    f.B = B; f.T = T; f.U1 = U1; f.H = H; f.V = V; f.D = T + U1 - 1; f.blank = V - 1; f.flags = g_flags; f.debug = g_debug;
-    launch_joint_fwd(f, st);
+    FusedCall c{};  // the plain joint: no loss arrays, no control block (one workgroup per tile); workspace: W pack | enc copy
+    c.B = B; c.T = T; c.U1 = U1; c.H = H; c.V = V; c.blank = V - 1; c.L.D = T + U1 - 1;
+    c.pred = (const float *)pred; c.W = (const float *)W; c.bias = (const float *)bias; c.logits = (float *)logits;
+    c.ablate = g_flags; c.debug = g_debug; c.st = (hipStream_t)stream;
+    float *wpack = (float *)workspace, *enc_copy = (float *)((char *)workspace + align_up(wpack_floats(H, V) * 4));
+    resolve_enc(enc, enc_strides, B, T, H, enc_copy, c.st, &c.enc, &c.enc_sb, &c.enc_st);
+    launch_pack_w_fwd(c.W, wpack, H, V, c.st);
+    launch_joint_fwd(fwd_args(c, wpack, nullptr, 0), c.st);
     return launch_status("rnnt_engine_joint_fwd");
 }
 
@@ -638,38 +671,27 @@ int rnnt_engine_joint_bwd(const void *enc, const int64_t enc_strides[3], const v
     if (!aligned16(pred) || !aligned16(W) || !aligned16(grad_logits) || !aligned16(grad_enc) ||
         !aligned16(grad_pred) || !aligned16(grad_W) || !aligned16(grad_bias) || ((uintptr_t)workspace & 255))
         return fail(RNNT_ERR_INVALID_ARG, "pointers must be 16-byte aligned (workspace 256)");
-    rnnt_engine_ws_layout L;
-    layout(B, T, U1, H, V, dtype, &L);
-    if (ws_bytes < L.total) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, L.total);
-    hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    const float *encp; long esb, est;
-    resolve_enc(enc, enc_strides, B, T, H, (float *)(ws + L.enc_copy), st, &encp, &esb, &est);
+    FusedCall c{};  // the fp32 route's workspace; no loss arrays (no coefficients), no diagnostics
+    layout(B, T, U1, H, V, dtype, &c.L);
+    if (ws_bytes < c.L.total) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, c.L.total);
+    hipStream_t st = c.st = (hipStream_t)stream;
+    c.ws = (char *)workspace; c.cb = (ControlBlock *)(c.ws + c.L.counters); c.logits = f32_at(c, c.L.logits);  // G
     // every utterance at full length: the upstream gradient is dense (zero where the caller's loss
     // ignored a cell); the length arrays the kernels read live in the (unused) coefficient region
-    int32_t *ll = (int32_t *)(ws + L.coef), *tl = ll + B;
+    int32_t *ll = (int32_t *)(c.ws + c.L.coef), *tl = ll + B;
+    c.B = B; c.T = T; c.U1 = U1; c.H = H; c.V = V; c.blank = V - 1; c.n_cu = device_cus();
+    c.pred = (const float *)pred; c.W = (const float *)W; c.logit_lens = ll; c.target_lens = tl;
+    c.grad_enc = (float *)grad_enc; c.grad_pred = (float *)grad_pred; c.grad_W = (float *)grad_W; c.grad_bias = (float *)grad_bias;
+    resolve_enc(enc, enc_strides, B, T, H, f32_at(c, c.L.enc_copy), st, &c.enc, &c.enc_sb, &c.enc_st);
     launch_fill32(ll, (unsigned)T, (size_t)B * 4, st);
     launch_fill32(tl, (unsigned)(U1 - 1), (size_t)B * 4, st);
     // G with the zero padding rows the dW GEMM walks past the last cell
     const size_t cells = (size_t)B * T * U1;
-    float *G = (float *)(ws + L.logits);
-    launch_copy_bytes(G, grad_logits, cells * V * 4, st);
-    launch_fill32(G + cells * V, 0u, (L.rows_pad + 16 - cells) * V * 4, st);
-    JointBwdArgs g;
-    memset(&g, 0, sizeof g);
-    g.enc = encp; g.enc_sb = esb; g.enc_st = est; g.pred = (const float *)pred; g.W = (const float *)W;
-    g.logits = G; g.hidden = (float *)(ws + L.hidden); g.rows_pad = (long)L.rows_pad;
-    g.logit_lens = ll; g.target_lens = tl;
-    g.slab_enc = (float *)(ws + L.slab_enc); g.slab_pred = (float *)(ws + L.slab_pred);
-    g.slab_w = (float *)(ws + L.slab_w); g.slab_b = (float *)(ws + L.slab_b);
-    g.grad_enc = (float *)grad_enc; g.grad_pred = (float *)grad_pred;
-    g.grad_W = (float *)grad_W; g.grad_bias = (float *)grad_bias;
-    g.B = B; g.T = T; g.U1 = U1; g.H = H; g.V = V; g.blank = V - 1;
-    g.n_ublk = L.n_ublk; g.n_ttile = L.n_ttile; g.n_split = L.n_split;
-    g.counter = (unsigned *)(ws + L.counters); g.dw_tab = (long *)(ws + L.counters + 1024);
-    g.n_cu = device_cus(); g.flags = 0; g.debug = nullptr; g.gen_bu = dhidden_gen_bu(T, U1);
+    launch_copy_bytes(c.logits, grad_logits, cells * V * 4, st);
+    launch_fill32(c.logits + cells * V, 0u, (c.L.rows_pad + 16 - cells) * V * 4, st);
+    const JointBwdArgs g = bwd_args(c);
     launch_make_hidden(g, st);
-    launch_dhidden(g, st);
+    launch_dhidden(g, false, st);  // G is given: the persistent kernel on every column
     launch_dhidden_reduce(g, st);
     launch_dw(g, st);
     launch_dw_reduce(g, st);
@@ -1178,32 +1200,14 @@ static int loss_fwd_bwd(const void *logits, const int32_t *targets, const int32_
     size_t need;
     rnnt_engine_loss_workspace_bytes(B, T, U1, V, dtype, &need);
     if (ws_bytes < need) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
-    const int D = T + U1 - 1;
-    const size_t skew = (size_t)B * D * U1;
-    char *ws = (char *)workspace;
-    float *denom_s = (float *)ws; ws += align_up(skew * 4);
-    float *lpb_s = (float *)ws;   ws += align_up(skew * 4);
-    float *lpe_s = (float *)ws;   ws += align_up(skew * 4);
-    double *alpha_s = (double *)ws; ws += align_up(skew * 8);
-    double *beta_s = (double *)ws;  ws += align_up(skew * 8);
-    CellCoef *coef = (CellCoef *)ws; ws += align_up((size_t)B * T * U1 * 16);
-    unsigned *err = (unsigned *)ws;
-    hipStream_t st = (hipStream_t)stream;
-    launch_logsoftmax_gather((const float *)logits, targets, logit_lens, target_lens, denom_s, lpb_s,
-                             lpe_s, B, T, U1, V, D, blank, st);
-    if (delay > 0.f) launch_delay_penalty(lpe_s, logit_lens, target_lens, B, T, U1, D, delay, st);
-    launch_lattice(lpb_s, lpe_s, alpha_s, beta_s, logit_lens, target_lens, costs, B, U1, D, err, st);
-    if (delay > 0.f) launch_delay_cost(beta_s, logit_lens, target_lens, costs, B, T, U1, D, delay, st);
-    if (grad_logits) {
-        if (fastemit > 0.f)
-            launch_coef_fastemit(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef,
-                                 B, T, U1, D, 1.0f, fastemit, st);
-        else
-            launch_coef(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef,
-                        B, T, U1, D, 1.0f, st);
-        launch_grad_logits((const float *)logits, coef, (float *)grad_logits, (long)B * T * U1, V,
-                           blank, clamp, st);
-    }
+    const LossCall c{carve_loss_ws(workspace, B, T, U1), targets, logit_lens, target_lens, costs, B, T, U1,
+                     grad_logits ? ST_LATTICE | ST_COEF : ST_LATTICE, 1.0f, fastemit, delay, (hipStream_t)stream};
+    launch_logsoftmax_gather((const float *)logits, targets, logit_lens, target_lens, c.w.denom_s, c.w.lpb_s,
+                             c.w.lpe_s, B, T, U1, V, T + U1 - 1, blank, c.st);
+    loss_stages(c);
+    if (grad_logits)
+        launch_grad_logits((const float *)logits, c.w.coef, (float *)grad_logits, (long)B * T * U1, V,
+                           blank, clamp, c.st);
     return launch_status("rnnt_engine_loss_fwd_bwd");
 }
 
@@ -1296,16 +1300,11 @@ int rnnt_engine_align(const void *logits, const int32_t *targets, const int32_t 
     rnnt_engine_loss_workspace_bytes(B, T, U1, V, RNNT_DTYPE_F32, &need);
     if (ws_bytes < need) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
     const int D = T + U1 - 1;
-    const size_t skew = (size_t)B * D * U1;
-    char *ws = (char *)workspace;  // the loss entry's layout: denom_s, lpb_s, lpe_s, alpha_s, ...
-    float *denom_s = (float *)ws; ws += align_up(skew * 4);
-    float *lpb_s = (float *)ws;   ws += align_up(skew * 4);
-    float *lpe_s = (float *)ws;   ws += align_up(skew * 4);
-    void *bp = ws;
+    const LossWs w = carve_loss_ws(workspace, B, T, U1);  // the loss entry's layout; the backpointer words take the alpha_s region
     hipStream_t st = (hipStream_t)stream;
-    launch_logsoftmax_gather((const float *)logits, targets, logit_lens, target_lens, denom_s, lpb_s,
-                             lpe_s, B, T, U1, V, D, blank, st);
-    launch_align(lpb_s, lpe_s, bp, logit_lens, target_lens, scores, frames, B, U1, D, st);
+    launch_logsoftmax_gather((const float *)logits, targets, logit_lens, target_lens, w.denom_s, w.lpb_s,
+                             w.lpe_s, B, T, U1, V, D, blank, st);
+    launch_align(w.lpb_s, w.lpe_s, w.alpha_s, logit_lens, target_lens, scores, frames, B, U1, D, st);
     return launch_status("rnnt_engine_align");
 }
 

@@ -157,7 +157,7 @@ __global__ __launch_bounds__(512, 2) void k_dhidden(JointBwdArgs a, int cb0)
                                                                           0, 0, 0);
                 }
         };
-        const bool xp_noepi = RNNT_XP(a.flags, 4) != 0;  // experiment switch
+        const bool xp_noepi = RNNT_XP(a.ablate, 4) != 0;  // experiment switch
         PwChunk r0, r1;
         load(r0, 0);
         load(r1, 1);
@@ -547,7 +547,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_gen(JointBwdArgs a, const in
     GSTAMP(2);
 
     // ---- epilogue: dPre = dHidden * (1 - hidden^2); reduce over u (dEnc) and over t (dPred)
-    if (RNNT_XP(a.flags, 8192)) return;  // experiment switch
+    if (RNNT_XP(a.ablate, 8192)) return;  // experiment switch
     // Accumulator register rr = 8 rh + r7 of M tile (2 wm + mt) is row (rr&3) + 8 (rr>>2) + 4 half of
     // its 32: BU = 16: t row rh, u slot 8 (r7>>2) + (r7&3) + 4 half;  BU = 8: t row 2 rh + (r7>>2), u
     // slot (r7&3) + 4 half.  A batch = (mt, rh) = 8 registers = 16 hidden loads.
@@ -772,10 +772,10 @@ __global__ __launch_bounds__(256) void k_reduce_pred(const float *__restrict__ s
     ((f32x4 *)out)[idx] = s;
 }
 
-void launch_dhidden(const JointBwdArgs &a, hipStream_t st)
+void launch_dhidden(const JointBwdArgs &a, bool tile_kernel, hipStream_t st)
 {
     int cb0 = 0;  // first 128-column block left to the persistent kernel
-    if (a.flags & 16) {  // the tile kernel (engine decides: dhidden_gen_ok), producing G unless k_make_g has (g_ready: RNNT_VARIANT_SEPARATE_G)
+    if (tile_kernel) {  // (the engine decides: dhidden_gen_ok) producing G unless k_make_g has (g_ready: RNNT_VARIANT_SEPARATE_G)
         // zero the padding rows k_dw may touch (k_make_g used to)
         const long cells = (long)a.B * a.T * a.U1;
         launch_fill32((float *)a.logits + cells * a.V, 0u, (size_t)(a.rows_pad + 16 - cells) * a.V * 4, st);

@@ -643,7 +643,7 @@ __device__ __forceinline__ void fwd_tile(const JointFwdArgs &a, const int bx_, c
                 if (rv && cok[g]) {
                     f32x4 o = {acc[g * 4 + 0][r], acc[g * 4 + 1][r], acc[g * 4 + 2][r],
                                acc[g * 4 + 3][r]};
-                    if (RNNT_XP(a.flags, 1))
+                    if (RNNT_XP(a.ablate, 1))
                         __builtin_nontemporal_store(o, (f32x4 *)(lrow + col0[g]));
                     else
                         *(f32x4 *)(lrow + col0[g]) = o;
@@ -760,15 +760,15 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void k_joint_fwd_persist(JointFwdAr
     }
 }
 
-void launch_joint_fwd(const JointFwdArgs &a, hipStream_t st)
+void launch_joint_fwd(const JointFwdArgs &a, hipStream_t st, bool lds_ring, bool one_wg_per_tile)
 {
     const int tiles = (int)(((long)a.T * a.U1 + FWD_ROWS - 1) / FWD_ROWS);
     dim3 grid(tiles, a.B), block(FWD_THREADS);
     if (a.denom_s && a.hidden) {
         const bool pairs = ((a.H + 7) / 8) % 2 == 0;  // even number of 8-wide chunks: the two-register-set main loop
-        if (pairs && !(a.flags & 128)) {
+        if (pairs && !lds_ring) {
             const long ntot = (long)tiles * a.B;
-            if (a.counter && !(a.flags & 256) && ntot < 0x7fffffffL) {
+            if (a.counter && !one_wg_per_tile && ntot < 0x7fffffffL) {
                 launch_fill32(a.counter, 0u, 4, st);
                 const int nwg = (int)(ntot < 2L * a.n_cu ? ntot : 2L * a.n_cu);
                 if (a.make_hidden)

@@ -11,6 +11,7 @@ int engine_fail(int code, const char *fmt, ...);
 // test_fused_call_is_hip_graph_capturable).  `bytes` and `p` multiples of 4.
 void launch_fill32(void *p, unsigned value, size_t bytes, hipStream_t st);
 void launch_copy_bytes(void *dst, const void *src, size_t bytes, hipStream_t st);
+int device_cus();  // compute units of the current device, cached (x2.hip; the engine's and the Linear layers' persistent grids)
 
 // ---- lattice.hip
 void launch_logsoftmax_gather(const float *logits, const int32_t *targets,
@@ -63,14 +64,15 @@ struct JointFwdArgs {
     float *logits;      // [B,T,U1,V]
     float *denom_s, *lpb_s, *lpe_s;  // skewed [B,D,U1]; NULL for the plain joint
     int B, T, U1, H, V, D, blank;
-    int flags;  // bit0: non-temporal logits stores
+    int ablate;  // diagnostic builds: the ablation word of rnnt_engine_set_flags, read through RNNT_XP only (bit0: non-temporal logits stores); never anything else
     unsigned *counter;  // one zeroable word: tile counter of the persistent forward (NULL: one workgroup per tile)
     int n_cu;           // compute units
     unsigned long long *debug;  // diagnostic stamp buffer (RNNT_STAMPS builds), else NULL
 };
 size_t wpack_floats(int H, int V);
 void launch_pack_w_fwd(const float *W, float *wpack, int H, int V, hipStream_t st);
-void launch_joint_fwd(const JointFwdArgs &a, hipStream_t st);
+// lds_ring: W through an LDS-DMA ring (RNNT_VARIANT_FWD_LDS_RING); one_wg_per_tile: no persistent workgroups (RNNT_VARIANT_FWD_ONE_WG_PER_TILE)
+void launch_joint_fwd(const JointFwdArgs &a, hipStream_t st, bool lds_ring = false, bool one_wg_per_tile = false);
 int fwd_occupancy(int with_loss);
 void launch_zero_dead_hidden(float *hidden, const int32_t *logit_lens, const int32_t *target_lens, int B, int T,
                              int U1, int H, hipStream_t st);
@@ -98,8 +100,8 @@ struct JointBwdArgs {
     long *dw_tab;       // dW live-granule region (launch_dw_list): [0] live count, block offsets, list
     const int *dw_list; // set by launch_dw: the list inside that region
     int n_cu;           // compute units (grid size of the persistent kernels)
-    int flags;          // bit 4 (16): G is produced by k_dhidden_gen; others: experiment switches
-    int g_ready;        // with bit 4: G already stands in place of the logits (k_make_g ran): the first column group reads it too (GEN = false)
+    int ablate;         // diagnostic builds: the ablation word of rnnt_engine_set_flags (RNNT_XP), nothing else
+    int g_ready;        // on the tile kernel (launch_dhidden): G already stands in place of the logits (k_make_g ran): the first column group reads it too (GEN = false)
     int gen_bu;         // u width of k_dhidden_gen's tiles (16, or 8 for short targets); dEnc slabs of columns < pred_split_col
     int pred_split_col; // dPred slabs: columns < this come in 8-row t tiles (k_dhidden_gen, bf16 route), the rest in 4-row tiles (k_dhidden)
     // f16x2 route only (x2.hip "flush rule"), NULL on every other: the reductions add a slab piece only where its 8 t x 16 u tile's flag is 1
@@ -108,7 +110,8 @@ struct JointBwdArgs {
     int flag_ntt, flag_nub;
     unsigned long long *debug;  // diagnostic stamp buffer (RNNT_STAMPS builds), else NULL
 };
-void launch_dhidden(const JointBwdArgs &a, hipStream_t st);
+// tile_kernel: k_dhidden_gen on the whole 512-column groups (the caller decides: dhidden_gen_ok), producing G unless g_ready; the persistent k_dhidden on the rest
+void launch_dhidden(const JointBwdArgs &a, bool tile_kernel, hipStream_t st);
 void launch_dw(const JointBwdArgs &a, hipStream_t st);
 int dw_tiles(int H, int V);  // workgroup tiles per split of k_dw
 void launch_dw_table(const int32_t *logit_lens, int B, int T, int U1, int gran, long *tab, hipStream_t st);
@@ -139,7 +142,7 @@ struct Bf16Args {
     long rows_pad;       // K extent of the dW GEMM (multiple of 32)
     int B, T, U1, H, V, blank;
     int n_ublk, n_split;
-    int flags;  // experiment switches (bits 8..: 256 no stores, 512 no statistics, 1024 no MFMA)
+    int ablate;  // diagnostic builds: the ablation word of rnnt_engine_set_flags (RNNT_XP; bits 8..: 256 no stores, 512 no statistics, 1024 no MFMA), nothing else
     long *dw_tab;  // 2B+2 longs: live-row table of k_dw_bf16 (k_dw_table, 32-cell granules)
     unsigned long long *debug;  // diagnostic stamp buffer (RNNT_STAMPS builds), else NULL
     int *dw_prog;  // [n_split][16] progress words of k_dw_bf16's tiles (zeroed by its launcher), or NULL
@@ -172,7 +175,7 @@ struct X3Args {
     int B, T, U1, H, V, blank;
     int n_ublk, n_split;
     int n_ublk16;        // u blocks of k_dhidden_x3 (16 wide)
-    int flags;
+    int ablate;          // diagnostic builds: the ablation word of rnnt_engine_set_flags (RNNT_XP), nothing else
     long *dw_tab;        // 2B+2 longs: live-row table of k_dw_x3 (k_dw_table, 32-cell granules)
     unsigned *counter;   // zeroable word: tile counter of the persistent forward
     int n_cu;
@@ -220,7 +223,7 @@ void launch_x2_zero_padding(const X3Args &a, int what, hipStream_t st);
 void launch_x2_pack_w(const X3Args &a, float *scales, hipStream_t st);  // s_W from max |W|, then both packs
 void launch_x2_make_ep(const X3Args &a, hipStream_t st);               // exp(2 enc), exp(2 pred) in k-step-major layout + the range flag
 size_t x2_ep_bytes(int B, int T, int U1, int H);
-void launch_joint_fwd_x2(const X3Args &a, hipStream_t st);   // one 512-register wave per SIMD
+void launch_joint_fwd_x2(const X3Args &a, hipStream_t st, bool plain_gemm = false);   // one 512-register wave per SIMD; plain_gemm: k_joint_fwd_x2<2> (the Linear layers)
 void launch_x2_dead_rows(const X3Args &a, hipStream_t st);  // zero G rows of dead tiles' cells inside live groups (what k_dw_x2 reads beside the live tiles' rows; X3Args::dw_ksteps: inside live k-steps)
 void launch_dhidden_x2(const X3Args &a, hipStream_t st);
 // the joint's input projections (audio_ln / text_ln) and their backward on the f16x2 pipes (x2.hip, round 5)

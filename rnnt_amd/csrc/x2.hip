@@ -94,7 +94,6 @@ template <int N> struct X2Int { static constexpr int value = N; };
 #define XW2_ROWS_ 16  // = XW2_ROWS: cells per dW k-step
 #define XG2_BT_ 8    // = XG2_BT, XG2_BU: the dHidden tile
 #define XG2_BU_ 16
-#define X2_FLAG_LINEAR 0x40000000  // X3Args::flags: launch_joint_fwd_x2 runs the plain-GEMM form (k_joint_fwd_x2<2>: the joint's input projections)
 
 // ---------------------------------------------------------------------------------------
 // s_W = 2^(14 - ceil(log2 max|W|)) (1 for an all-zero W): one workgroup, V*H/4 float4 reads.  A W with a NaN or an infinity in it (a diverged
@@ -2410,7 +2409,7 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
 
 bool x2_fwd_ok(int U1, int H, int V) { return H % 128 == 0 && V % 128 == 0 && (long)128 * H * 2 < 0x7fffffffL; }
 
-void launch_joint_fwd_x2(const X3Args &a, hipStream_t st)
+void launch_joint_fwd_x2(const X3Args &a, hipStream_t st, bool lin /* the plain-GEMM form, k_joint_fwd_x2<2>: the joint's input projections */)
 {
     static bool attr_set[16] = {false};
     int dev = -1;
@@ -2423,12 +2422,11 @@ void launch_joint_fwd_x2(const X3Args &a, hipStream_t st)
         if (dev >= 0) attr_set[dev] = true;
     }
     const long cells = (long)a.B * a.T * a.U1;
-    const bool lin = (a.flags & X2_FLAG_LINEAR) != 0;
     const int ntiles = (int)((cells + 127) / 128) * (lin ? (a.V + 511) / 512 : 1);  // (plain GEMM: a tile = one column pass of a row block)
     if (!lin) launch_fill32(a.counter, 0u, 4, st);  // tile counter of the persistent workgroups (plain GEMM: zeroed with its scales, k_x2_lin_scales)
     const int nwg = ntiles < a.n_cu ? ntiles : a.n_cu;  // one workgroup per CU
     // both forms; k_x2_make_ep's flag (device memory: no host round trip) selects the one that runs, the other's workgroups exit at once
-    if (a.flags & X2_FLAG_LINEAR) { hipLaunchKernelGGL(k_joint_fwd_x2<2>, dim3((unsigned)nwg), dim3(256), lds, st, a, ntiles); return; }
+    if (lin) { hipLaunchKernelGGL(k_joint_fwd_x2<2>, dim3((unsigned)nwg), dim3(256), lds, st, a, ntiles); return; }
     hipLaunchKernelGGL(k_joint_fwd_x2<1>, dim3((unsigned)nwg), dim3(256), lds, st, a, ntiles);
     hipLaunchKernelGGL(k_joint_fwd_x2<0>, dim3((unsigned)nwg), dim3(256), lds, st, a, ntiles);
 }
@@ -2582,6 +2580,20 @@ __global__ __launch_bounds__(256) void k_x2_reduce_scaled(const float *__restric
     ((f32x4 *)out)[i] = acc * r;
 }
 
+// compute units of the CURRENT device (the caller makes the tensors' device current); read-only facts of the hardware, cached per device id
+int device_cus()
+{
+    static thread_local int cus[16] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
+    if (!cus[dev]) {
+        hipDeviceProp_t p;
+        if (hipGetDeviceProperties(&p, dev) == hipSuccess) cus[dev] = p.multiProcessorCount;
+        if (cus[dev] <= 0) cus[dev] = 256;
+    }
+    return cus[dev];
+}
+
 namespace {
 struct LinWs { size_t wt, pack, pa, pb, slab_w, slab_b, prog, list, glist, total; long rows_pad, rows_alloc; int n_split; };
 LinWs lin_layout(int M, int K, int N, bool bwd)
@@ -2609,18 +2621,6 @@ LinWs lin_layout(int M, int K, int N, bool bwd)
     L.total = o;
     return L;
 }
-int lin_cus()
-{
-    static thread_local int cus[16] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-    if (!cus[dev]) {
-        hipDeviceProp_t p;
-        if (hipGetDeviceProperties(&p, dev) == hipSuccess) cus[dev] = p.multiProcessorCount;
-        if (cus[dev] <= 0) cus[dev] = 256;
-    }
-    return cus[dev];
-}
 // the operand scales of a call: one launch for the maxima of its n tensors, one for the scales (+ the counter words and dW's lists)
 struct LinT { const float *x; long ld, rows; int cols; };
 void lin_scales(const LinT *t, int n, char *w, unsigned *zero1, int nzero1, long nks, int *list, int *glist, hipStream_t st)
@@ -2641,8 +2641,8 @@ void lin_gemm_nt(const float *x, long ldx, const float *wmat, const float *bias,
     X3Args a{};
     a.enc = x; a.enc_sb = ldx; a.enc_st = 0; a.pred = nullptr; a.W = wmat; a.bias = bias;
     a.B = M; a.T = 1; a.U1 = 1; a.H = K; a.V = N; a.logits = y; a.wpack_fwd = pack; a.scales = scales;
-    a.counter = counter; a.n_cu = lin_cus(); a.flags = X2_FLAG_LINEAR;  // (the counter was zeroed by k_x2_lin_scales)
-    launch_joint_fwd_x2(a, st);
+    a.counter = counter; a.n_cu = device_cus();  // (the counter was zeroed by k_x2_lin_scales)
+    launch_joint_fwd_x2(a, st, true);  // the plain-GEMM form
 }
 }  // namespace
 
@@ -2685,7 +2685,7 @@ void launch_linear_x2_bwd(const float *x, long ldx, const float *W, const float 
     X3Args a{};
     a.logits = pa; a.hidden = pb; a.plane_stride = L.rows_alloc * (long)K; a.rows_pad = L.rows_pad; a.rows_alloc = L.rows_alloc;
     a.B = 1; a.T = 1; a.U1 = 1; a.H = K; a.V = N; a.n_split = L.n_split; a.dw_prog = (int *)(w + L.prog);
-    a.slab_w = (float *)(w + L.slab_w); a.slab_b = (float *)(w + L.slab_b); a.dw_rescale = 1.0f; a.db_rescale = 1.0f; a.n_cu = lin_cus();
+    a.slab_w = (float *)(w + L.slab_w); a.slab_b = (float *)(w + L.slab_b); a.dw_rescale = 1.0f; a.db_rescale = 1.0f; a.n_cu = device_cus();
     a.live_stats = (int *)(w + L.list); a.ks_list = a.live_stats + 16; a.grp_list = (int *)(w + L.glist);
     launch_dw_x2(a, st, false);  // (no list kernels, no progress-word fill: all done by k_x2_lin_scales)
     const long n4w = (long)N * K / 4, n4b = N / 4;

@@ -315,7 +315,7 @@ __global__ __launch_bounds__(256, 1) void k_dw_x3(X3Args a)
                                                           (int)(XW_ROWS * rstride[p]), 0x00020000);
             auto dma_piece = [&](auto n_c) {  // piece n of stage ks+2 -> ring stage DST: plane n>>2, rows 4(n&3)..
                 constexpr int n = decltype(n_c)::value, p = n >> 2, i = n & 3;
-                if (RNNT_XP(a.flags, 8192)) return;
+                if (RNNT_XP(a.ablate, 8192)) return;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[p], (lds_vptr)(s_ring + wave * XW_TILE + DST * XW_STAGE + p * XW_PLANE + 1024 * i),
                                                          16, soff[p][i], 0, 0, 0);
             };
@@ -323,7 +323,7 @@ __global__ __launch_bounds__(256, 1) void k_dw_x3(X3Args a)
             // see behind an LDS-DMA with vmcnt(0)); results are used only after X3_LANDED named them
             auto reads = [&](X3Frag &f, const int (&base)[4][2], auto p_c) {
                 constexpr int off = ST * XW_STAGE + decltype(p_c)::value * XW_PLANE;
-                if (RNNT_XP(a.flags, 4096)) return;
+                if (RNNT_XP(a.ablate, 4096)) return;
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
                     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.lo[m]) : "v"(base[m][0]), "n"(off));
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(256, 1) void k_dw_x3(X3Args a)
                 }
 #pragma unroll
                 for (int qm = 0; qm < 4; ++qm) {
-                    if (!RNNT_XP(a.flags, 1024)) {
+                    if (!RNNT_XP(a.ablate, 1024)) {
 #pragma unroll
                         for (int qn = 0; qn < 4; ++qn) acc[qm][qn] = x3_mfma(fa[qm], fb[qn], acc[qm][qn]);
                     }
@@ -392,7 +392,7 @@ __global__ __launch_bounds__(256, 1) void k_dw_x3(X3Args a)
             product(Al, Bh, X3Int<8>{});
             X3_LANDED(Bl, 0);
             product(Ah, Bl, X3Int<10>{});
-            if (do_b && !RNNT_XP(a.flags, 2048)) {
+            if (do_b && !RNNT_XP(a.ablate, 2048)) {
                 bias_mfma(dl[0], dh[0], dacc, 0); bias_mfma(dl[1], dh[1], dacc, 0); bias_mfma(dl[2], dh[2], dacc, 0);
                 if (n_hblk < 2) {  // one h block: the wave's second tile (column 1 of the selector product), H <= 256 only
                     bias_read(dl[0], dh[0], X3Int<0>{}, 1); bias_read(dl[1], dh[1], X3Int<1>{}, 1); bias_read(dl[2], dh[2], X3Int<2>{}, 1);
