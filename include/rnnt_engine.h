@@ -216,6 +216,44 @@ int rnnt_engine_joint_loss_fwd_reg(const void *enc, const int64_t enc_strides[3]
                                    void *stream);
 
 /*
+ * Alignment-restricted loss, "Ar-RNN-T" (DESIGN.md §4n): the three *_reg entries above with the label arcs confined to a
+ * window around a reference alignment; same workspace and return codes as their counterparts.
+ *   restrict_frames [B, U1-1] int32, device, contiguous: the reference frame of every label, as rnnt_engine_align /
+ *       rnnt_engine_joint_align write it; entries at u >= target_lens[b] are never read.  NULL: RNNT_ERR_INVALID_ARG.
+ *   restrict_left, restrict_right >= 0 (else RNNT_ERR_INVALID_ARG), in encoder frames.
+ * The label arc (t,u) -> (t,u+1) exists only for restrict_frames[b,u] - restrict_left <= t <= restrict_frames[b,u] +
+ * restrict_right; blank arcs are unrestricted.  costs[b] = -log of the sum over the paths that remain, the gradients are that
+ * cost's; a lattice cell no surviving path crosses contributes exactly zero.  FastEmit and the delay penalty act on the arcs
+ * that remain.  An utterance without a surviving path (frames that decrease, or lie outside [0, T_b - 1] by more than the
+ * buffers) has costs[b] = +inf and exactly zero gradient contributions; the other utterances of the batch are unaffected.  A
+ * NaN cost from non-finite inputs stays NaN.  Nothing synchronises; the frames are not validated on the device.
+ */
+int rnnt_engine_loss_fwd_bwd_restrict(const void *logits, const int32_t *targets,
+                                      const int32_t *logit_lens, const int32_t *target_lens, int B,
+                                      int T, int U1, int V, int blank, float clamp,
+                                      float fastemit_lambda, float delay_penalty,
+                                      const int32_t *restrict_frames, int restrict_left,
+                                      int restrict_right, int dtype, float *costs, void *grad_logits,
+                                      void *workspace, size_t ws_bytes, void *stream);
+int rnnt_engine_joint_loss_fwd_bwd_restrict(const void *enc, const int64_t enc_strides[3],
+                                            const void *pred, const void *W, const void *bias,
+                                            const int32_t *targets, const int32_t *logit_lens,
+                                            const int32_t *target_lens, int B, int T, int U1, int H,
+                                            int V, int blank, float clamp, float grad_scale,
+                                            float fastemit_lambda, float delay_penalty,
+                                            const int32_t *restrict_frames, int restrict_left,
+                                            int restrict_right, int dtype, float *costs, void *grad_enc,
+                                            void *grad_pred, void *grad_W, void *grad_bias,
+                                            void *workspace, size_t ws_bytes, void *stream);
+int rnnt_engine_joint_loss_fwd_restrict(const void *enc, const int64_t enc_strides[3], const void *pred,
+                                        const void *W, const void *bias, const int32_t *targets,
+                                        const int32_t *logit_lens, const int32_t *target_lens, int B,
+                                        int T, int U1, int H, int V, int blank, float delay_penalty,
+                                        const int32_t *restrict_frames, int restrict_left,
+                                        int restrict_right, int dtype, float *costs, void *workspace,
+                                        size_t ws_bytes, void *stream);
+
+/*
  * Forced alignment: the best path through the same lattice, with the same log-probs
  * (lp_blank, lp_emit) as the loss, padded H / V of each route included.  For utterance b with
  * T_b = logit_lens[b], U_b = target_lens[b], a path runs from (0,0) to (T_b-1, U_b): a label arc

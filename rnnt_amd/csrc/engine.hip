@@ -102,6 +102,15 @@ int check_reg(float fastemit_lambda, float delay_penalty)
     return RNNT_OK;
 }
 
+// the alignment restriction of the *_restrict entries: a frames pointer and two buffers >= 0
+int check_restrict(const int32_t *restrict_frames, int restrict_left, int restrict_right)
+{
+    if (!restrict_frames) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument (restrict_frames)");
+    if (restrict_left < 0 || restrict_right < 0)
+        return fail(RNNT_ERR_INVALID_ARG, "restrict_left=%d and restrict_right=%d must be >= 0", restrict_left, restrict_right);
+    return RNNT_OK;
+}
+
 int dw_splits(int B, int T, int H, int V, int dtype)
 {
     const long tiles = dtype == RNNT_DTYPE_F32 ? dw_tiles(H, V) : dtype == RNNT_DTYPE_F32_F16X2 ? x2_dw_tiles(H, V) : (long)((V + 255) / 256) * ((H + 255) / 256);
@@ -247,6 +256,7 @@ struct LossCall {
     LossWs w;
     const int32_t *targets, *logit_lens, *target_lens; float *costs;
     int B, T, U1, stages /* ST_* mask */; float grad_scale, fastemit, delay; hipStream_t st;
+    const int32_t *restrict_frames; int restrict_left, restrict_right;  // the *_restrict entries; null: no restriction
 };
 
 // One fused call after validation: what the routes and the argument fillers read.  The standalone joint entries fill
@@ -338,10 +348,23 @@ X3Args x3_args(const FusedCall &c, size_t wpack_fwd_bytes, const OperandScales &
 
 // lattice sweep and coefficients (every route): the delay penalty goes on lp_emit before the sweep and its cost shift comes off after it,
 // FastEmit's coefficients replace k_coef's; zero options launch exactly the plain loss's kernels.
-// flush_log2: the f16x2 route's threshold (lattice.hip coef_cell), or null: the plain coefficients
+// flush_log2: the f16x2 route's threshold (lattice.hip coef_cell), or null: the plain coefficients.
+// A restricted call masks lp_emit in the pass that applies the delay penalty and runs the -inf-safe sweep and coefficients.
 void loss_stages(const LossCall &c, const double *flush_log2 = nullptr, float flush_lin = 0.f)
 {
     const LossWs &w = c.w; const int D = c.T + c.U1 - 1;
+    if (c.restrict_frames) {
+        if (c.stages & ST_LATTICE) {
+            launch_restrict(w.lpe_s, c.restrict_frames, c.logit_lens, c.target_lens, c.B, c.T, c.U1, D, c.restrict_left, c.restrict_right,
+                            c.delay, c.st);
+            launch_lattice(w.lpb_s, w.lpe_s, w.alpha_s, w.beta_s, c.logit_lens, c.target_lens, c.costs, c.B, c.U1, D, w.err, c.st, true);
+            if (c.delay > 0.f) launch_delay_cost(w.beta_s, c.logit_lens, c.target_lens, c.costs, c.B, c.T, c.U1, D, c.delay, c.st);
+        }
+        if (c.stages & ST_COEF)
+            launch_coef_restrict(w.alpha_s, w.beta_s, w.denom_s, w.lpb_s, w.lpe_s, c.targets, c.logit_lens, c.target_lens, w.coef,
+                                 c.B, c.T, c.U1, D, c.grad_scale, c.fastemit, flush_log2, flush_lin, c.st);
+        return;
+    }
     if (c.stages & ST_LATTICE) {
         if (c.delay > 0.f) launch_delay_penalty(w.lpe_s, c.logit_lens, c.target_lens, c.B, c.T, c.U1, D, c.delay, c.st);
         launch_lattice(w.lpb_s, w.lpe_s, w.alpha_s, w.beta_s, c.logit_lens, c.target_lens, c.costs, c.B, c.U1, D, w.err, c.st);
@@ -494,7 +517,8 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
               const int32_t *target_lens, int B, int T, int U1, int H, int V, int blank,
               float clamp, float grad_scale, float fastemit, float delay, int dtype, float *costs,
               void *grad_enc, void *grad_pred, void *grad_W, void *grad_bias, void *workspace,
-              size_t ws_bytes, void *stream)
+              size_t ws_bytes, void *stream, const int32_t *restrict_frames = nullptr, int restrict_left = 0,
+              int restrict_right = 0)
 {
     if (int rc = check_dims(B, T, U1, H, V, dtype, true)) return rc;
     if (!enc || !enc_strides || !pred || !W || !bias || !targets || !logit_lens || !target_lens ||
@@ -540,6 +564,7 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
     c.bias = (const float *)bias; c.targets = targets; c.logit_lens = logit_lens; c.target_lens = target_lens; c.costs = costs;
     c.grad_enc = (float *)grad_enc; c.grad_pred = (float *)grad_pred; c.grad_W = (float *)grad_W; c.grad_bias = (float *)grad_bias;
     c.stages = stages; c.grad_scale = grad_scale; c.fastemit = fastemit; c.delay = delay; c.n_cu = device_cus(); c.st = (hipStream_t)stream;
+    c.restrict_frames = restrict_frames; c.restrict_left = restrict_left; c.restrict_right = restrict_right;
     c.ws = (char *)workspace; c.cb = (ControlBlock *)(c.ws + c.L.counters); c.logits = f32_at(c, c.L.logits);
     c.w = carve_loss_ws(c.ws + c.L.denom_s, B, T, U1); c.w.err = c.cb->lattice_err;  // (layout() places the arrays by the same carve)
     resolve_enc(enc, enc_strides, B, T, H, f32_at(c, c.L.enc_copy), c.st, &c.enc, &c.enc_sb, &c.enc_st);
@@ -1189,7 +1214,8 @@ int rnnt_engine_greedy_stream_decode(const void *frames, int64_t frame_stride, i
 static int loss_fwd_bwd(const void *logits, const int32_t *targets, const int32_t *logit_lens,
                         const int32_t *target_lens, int B, int T, int U1, int V, int blank, float clamp,
                         float fastemit, float delay, int dtype, float *costs, void *grad_logits,
-                        void *workspace, size_t ws_bytes, void *stream)
+                        void *workspace, size_t ws_bytes, void *stream, const int32_t *restrict_frames = nullptr,
+                        int restrict_left = 0, int restrict_right = 0)
 {
     if (int rc = check_dims(B, T, U1, 4, V, dtype, false)) return rc;
     if (!logits || !targets || !logit_lens || !target_lens || !costs || !workspace)
@@ -1201,7 +1227,8 @@ static int loss_fwd_bwd(const void *logits, const int32_t *targets, const int32_
     rnnt_engine_loss_workspace_bytes(B, T, U1, V, dtype, &need);
     if (ws_bytes < need) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
     const LossCall c{carve_loss_ws(workspace, B, T, U1), targets, logit_lens, target_lens, costs, B, T, U1,
-                     grad_logits ? ST_LATTICE | ST_COEF : ST_LATTICE, 1.0f, fastemit, delay, (hipStream_t)stream};
+                     grad_logits ? ST_LATTICE | ST_COEF : ST_LATTICE, 1.0f, fastemit, delay, (hipStream_t)stream,
+                     restrict_frames, restrict_left, restrict_right};
     launch_logsoftmax_gather((const float *)logits, targets, logit_lens, target_lens, c.w.denom_s, c.w.lpb_s,
                              c.w.lpe_s, B, T, U1, V, T + U1 - 1, blank, c.st);
     loss_stages(c);
@@ -1258,6 +1285,55 @@ int rnnt_engine_joint_loss_fwd_reg(const void *enc, const int64_t enc_strides[3]
     return run_fused(ST_PROD | ST_FWD | ST_LATTICE, 0, enc, enc_strides, pred, W, bias, targets, logit_lens,
                      target_lens, B, T, U1, H, V, blank, -1.0f, 1.0f, 0.f, delay_penalty, dtype, costs, nullptr,
                      nullptr, nullptr, nullptr, workspace, ws_bytes, stream);
+}
+
+// ---- alignment-restricted loss: the *_reg entries with the label arcs confined to a window around restrict_frames.
+// f16x2: the flush rule stays on (dead cells are skipped either way) unless an option of §4k is on, as in the *_reg entry.
+int rnnt_engine_loss_fwd_bwd_restrict(const void *logits, const int32_t *targets, const int32_t *logit_lens,
+                                      const int32_t *target_lens, int B, int T, int U1, int V, int blank,
+                                      float clamp, float fastemit_lambda, float delay_penalty,
+                                      const int32_t *restrict_frames, int restrict_left, int restrict_right,
+                                      int dtype, float *costs, void *grad_logits, void *workspace,
+                                      size_t ws_bytes, void *stream)
+{
+    if (int rc = check_reg(fastemit_lambda, delay_penalty)) return rc;
+    if (int rc = check_restrict(restrict_frames, restrict_left, restrict_right)) return rc;
+    return loss_fwd_bwd(logits, targets, logit_lens, target_lens, B, T, U1, V, blank, clamp, fastemit_lambda,
+                        delay_penalty, dtype, costs, grad_logits, workspace, ws_bytes, stream, restrict_frames,
+                        restrict_left, restrict_right);
+}
+
+int rnnt_engine_joint_loss_fwd_bwd_restrict(const void *enc, const int64_t enc_strides[3], const void *pred,
+                                            const void *W, const void *bias, const int32_t *targets,
+                                            const int32_t *logit_lens, const int32_t *target_lens, int B,
+                                            int T, int U1, int H, int V, int blank, float clamp,
+                                            float grad_scale, float fastemit_lambda, float delay_penalty,
+                                            const int32_t *restrict_frames, int restrict_left,
+                                            int restrict_right, int dtype, float *costs, void *grad_enc,
+                                            void *grad_pred, void *grad_W, void *grad_bias, void *workspace,
+                                            size_t ws_bytes, void *stream)
+{
+    if (int rc = check_reg(fastemit_lambda, delay_penalty)) return rc;
+    if (int rc = check_restrict(restrict_frames, restrict_left, restrict_right)) return rc;
+    return run_fused(ST_ALL, 0, enc, enc_strides, pred, W, bias, targets, logit_lens, target_lens, B, T, U1, H, V, blank,
+                     clamp, grad_scale, fastemit_lambda, delay_penalty, dtype, costs, grad_enc, grad_pred, grad_W,
+                     grad_bias, workspace, ws_bytes, stream, restrict_frames, restrict_left, restrict_right);
+}
+
+int rnnt_engine_joint_loss_fwd_restrict(const void *enc, const int64_t enc_strides[3], const void *pred,
+                                        const void *W, const void *bias, const int32_t *targets,
+                                        const int32_t *logit_lens, const int32_t *target_lens, int B, int T,
+                                        int U1, int H, int V, int blank, float delay_penalty,
+                                        const int32_t *restrict_frames, int restrict_left, int restrict_right,
+                                        int dtype, float *costs, void *workspace, size_t ws_bytes,
+                                        void *stream)
+{
+    if (int rc = check_reg(0.f, delay_penalty)) return rc;
+    if (int rc = check_restrict(restrict_frames, restrict_left, restrict_right)) return rc;
+    return run_fused(ST_PROD | ST_FWD | ST_LATTICE, 0, enc, enc_strides, pred, W, bias, targets, logit_lens,
+                     target_lens, B, T, U1, H, V, blank, -1.0f, 1.0f, 0.f, delay_penalty, dtype, costs, nullptr,
+                     nullptr, nullptr, nullptr, workspace, ws_bytes, stream, restrict_frames, restrict_left,
+                     restrict_right);
 }
 
 int rnnt_engine_joint_loss_fwd_bwd(const void *enc, const int64_t enc_strides[3], const void *pred,

@@ -20,7 +20,8 @@ void launch_logsoftmax_gather(const float *logits, const int32_t *targets,
                               int V, int D, int blank, hipStream_t st);
 void launch_lattice(const float *lpb_s, const float *lpe_s, double *alpha_s, double *beta_s,
                     const int32_t *logit_lens, const int32_t *target_lens, float *costs, int B,
-                    int U1, int D, unsigned *err /* one word of workspace */, hipStream_t st);
+                    int U1, int D, unsigned *err /* one word of workspace */, hipStream_t st,
+                    bool restricted = false /* lp_emit went through launch_restrict: the -inf-safe chained sweep */);
 void launch_coef(const double *alpha_s, const double *beta_s, const float *denom_s,
                  const float *lpb_s, const float *lpe_s, const int32_t *targets,
                  const int32_t *logit_lens, const int32_t *target_lens, CellCoef *coef, int B,
@@ -41,6 +42,19 @@ void launch_delay_penalty(float *lpe_s, const int32_t *logit_lens, const int32_t
                           int T, int U1, int D, float delay, hipStream_t st);
 void launch_delay_cost(const double *beta_s, const int32_t *logit_lens, const int32_t *target_lens,
                        float *costs, int B, int T, int U1, int D, float delay, hipStream_t st);
+// Alignment restriction.  launch_restrict: label arcs outside frames[b,u] - left .. frames[b,u] + right get
+// lp_emit = -inf, the others the delay penalty (it runs INSTEAD of launch_delay_penalty; delay = 0: none); then
+// launch_lattice(.., restricted = true), launch_delay_cost as usual, and launch_coef_restrict: the coefficients with dead cells
+// (alpha or beta = -inf, cost = +inf) set to those of a cell outside the lattice — FastEmit's when lambda > 0, else the flush
+// rule's when flush_log2 is not null, else the plain ones.
+void launch_restrict(float *lpe_s, const int32_t *frames /* [B, U1-1] */, const int32_t *logit_lens,
+                     const int32_t *target_lens, int B, int T, int U1, int D, int left, int right, float delay,
+                     hipStream_t st);
+void launch_coef_restrict(const double *alpha_s, const double *beta_s, const float *denom_s,
+                          const float *lpb_s, const float *lpe_s, const int32_t *targets,
+                          const int32_t *logit_lens, const int32_t *target_lens, CellCoef *coef, int B,
+                          int T, int U1, int D, float scale, float lambda, const double *flush_log2, float flush_lin,
+                          hipStream_t st);
 void launch_grad_logits(const float *logits, const CellCoef *coef, float *grad, long nrows,
                         int V, int blank, float clamp, hipStream_t st);
 

@@ -10,6 +10,8 @@
 //   k_coef               per-cell gradient coefficients (CellCoef) from alpha/beta
 //                        (k_coef_fastemit: the same with FastEmit's lambda)
 //   k_delay_penalty      delay penalty on lp_emit before the sweep; k_delay_cost after it
+//   k_restrict           alignment restriction: label arcs outside their window get lp_emit = -inf
+//                        before the sweep; k_lattice_chain_restrict / k_coef_restrict* are the -inf-safe instantiations
 //   k_grad_logits        d cost / d logits, elementwise (standalone loss entry only)
 //
 // All per-cell work arrays use the skewed layout of common.hpp (anti-diagonal contiguous),
@@ -209,8 +211,10 @@ __device__ __forceinline__ double wave_shift(double v, double fill)
     return __builtin_bit_cast(double, r);
 }
 
+// RS (restricted lattice): lp_emit may be -inf, so a cell INSIDE the lattice may have no finite predecessor; the
+// step then yields -inf instead of the NaN of (-inf) - (-inf).  RS = false is the plain sweep's code unchanged.
 #define LAT_PF 6
-template <int DIR>
+template <int DIR, bool RS = false>
 __device__ __forceinline__ void lattice_chain(
     const float *__restrict__ lpb_s, const float *__restrict__ lpe_s, double *__restrict__ out_s,
     const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
@@ -312,7 +316,8 @@ __device__ __forceinline__ void lattice_chain(
         // log(exp(a) + exp(e)) = max + log(1 + exp(-|a - e|)); the correction is < ln 2 and
         // evaluated in fp32 with the hardware exp2/log2.  A cell of the lattice has at least one
         // finite predecessor; everything else is overwritten by the select.
-        const float dl = -fabsf((float)(a - e));
+        float dl = -fabsf((float)(a - e));
+        if (RS) dl = fmax(a, e) == NINF ? 0.f : dl;  // both predecessors unreachable: -inf + log 2 = -inf
         const double v = fmax(a, e) +
             (double)(__builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f(dl * RNNT_LOG2E)) * 0.6931471805599453f);
         const bool valid = (unsigned)(d - ukey) < (unsigned)Tb;
@@ -358,6 +363,20 @@ __global__ __launch_bounds__(1024) void k_lattice_chain(
         lattice_chain<1>(lpb_s, lpe_s, beta_s, logit_lens, target_lens, costs, U1, D, err);
 }
 
+// the chained sweep on a restricted lattice (k_restrict ran on lp_emit): unreachable cells come out as -inf, an infeasible
+// utterance as cost +inf
+__global__ __launch_bounds__(1024) void k_lattice_chain_restrict(
+    const float *__restrict__ lpb_s, const float *__restrict__ lpe_s,
+    double *__restrict__ alpha_s, double *__restrict__ beta_s,
+    const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
+    float *__restrict__ costs, int U1, int D, unsigned *__restrict__ err)
+{
+    if (blockIdx.y == 0)
+        lattice_chain<0, true>(lpb_s, lpe_s, alpha_s, logit_lens, target_lens, costs, U1, D, err);
+    else
+        lattice_chain<1, true>(lpb_s, lpe_s, beta_s, logit_lens, target_lens, costs, U1, D, err);
+}
+
 // Failure report of the chained sweep: if any wave ran out of its bounded spin, the costs of the
 // whole call become NaN (a loud failure the training loop sees in its loss) instead of numbers
 // computed from a stale mailbox value.
@@ -394,7 +413,12 @@ __global__ void k_lattice_status(const unsigned *__restrict__ err, float *__rest
 //     e_v < 2^(s1 + 0.03).  With s1 < flush_log2 = -26 - log2 g_scale:  g_scale e_v < 2^-25.97.
 // Both comparisons are ordered: a NaN anywhere (a non-finite cost poisons alpha + cost of every cell of its utterance) keeps the
 // cell live, and flush_log2 = -inf (flush_lin = 0) flags nothing.
-template <bool FE, bool FLUSH = false>
+//
+// RS (restricted lattice): a cell that no surviving path crosses (alpha = -inf or beta = -inf) and every cell of an
+// infeasible utterance (cost = +inf) is DEAD: alpha + cost and FastEmit's beta difference would be (+-inf) - (+-inf) there.  A dead
+// cell gets the coefficients of a cell outside the lattice, so its gradient row is exactly zero on every route and the f16x2
+// backward skips it like a flushed one.  The tests are ordered compares: a NaN cost keeps its cells live and stays NaN.
+template <bool FE, bool FLUSH = false, bool RS = false>
 __device__ __forceinline__ void coef_cell(
     const double *__restrict__ alpha_s, const double *__restrict__ beta_s,
     const float *__restrict__ denom_s, const float *__restrict__ lpb_s,
@@ -415,7 +439,11 @@ __device__ __forceinline__ void coef_cell(
     const int Tb = len_t(logit_lens, b, T), Ub = len_u(target_lens, b, U1);
     CellCoef c;
     c.c1 = RNNT_NEG_INF; c.sb = 0.f; c.se = 0.f; c.y = -1;
-    if (t < Tb && u <= Ub) {
+    bool in_lattice = t < Tb && u <= Ub;
+    if (RS && in_lattice)
+        in_lattice = !(alpha_s[idx] == (double)RNNT_NEG_INF || beta_s[idx] == (double)RNNT_NEG_INF ||
+                       beta_s[(long)b * per] == (double)RNNT_NEG_INF);
+    if (in_lattice) {
         const double a = alpha_s[idx];
         const double cost = -beta_s[(long)b * per];
         const double ac = a + cost;
@@ -467,6 +495,40 @@ __global__ __launch_bounds__(256) void k_coef(
                      scale, 0.f);
 }
 
+// the three coefficient kernels on a restricted lattice (coef_cell, RS)
+__global__ __launch_bounds__(256) void k_coef_restrict(
+    const double *__restrict__ alpha_s, const double *__restrict__ beta_s,
+    const float *__restrict__ denom_s, const float *__restrict__ lpb_s,
+    const float *__restrict__ lpe_s, const int32_t *__restrict__ targets,
+    const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
+    CellCoef *__restrict__ coef, int B, int T, int U1, int D, float scale)
+{
+    coef_cell<false, false, true>(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B, T, U1, D,
+                                  scale, 0.f);
+}
+
+__global__ __launch_bounds__(256) void k_coef_restrict_flush(
+    const double *__restrict__ alpha_s, const double *__restrict__ beta_s,
+    const float *__restrict__ denom_s, const float *__restrict__ lpb_s,
+    const float *__restrict__ lpe_s, const int32_t *__restrict__ targets,
+    const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
+    CellCoef *__restrict__ coef, int B, int T, int U1, int D, float scale, double flush_log2, float flush_lin)
+{
+    coef_cell<false, true, true>(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B, T, U1, D,
+                                 scale, 0.f, flush_log2, flush_lin);
+}
+
+__global__ __launch_bounds__(256) void k_coef_restrict_fastemit(
+    const double *__restrict__ alpha_s, const double *__restrict__ beta_s,
+    const float *__restrict__ denom_s, const float *__restrict__ lpb_s,
+    const float *__restrict__ lpe_s, const int32_t *__restrict__ targets,
+    const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
+    CellCoef *__restrict__ coef, int B, int T, int U1, int D, float scale, float lambda)
+{
+    coef_cell<true, false, true>(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B, T, U1, D,
+                                 scale, lambda);
+}
+
 __global__ __launch_bounds__(256) void k_coef_fastemit(
     const double *__restrict__ alpha_s, const double *__restrict__ beta_s,
     const float *__restrict__ denom_s, const float *__restrict__ lpb_s,
@@ -505,8 +567,32 @@ __global__ __launch_bounds__(256) void k_delay_penalty(float *__restrict__ lpe_s
     lpe_s[idx] -= delay * (float)t;
 }
 
+// Alignment restriction: the label arc (t,u) -> (t,u+1) exists only for frames[b,u] - left <= t <= frames[b,u] +
+// right; outside its window lp_emit becomes -inf, inside it the delay penalty applies as k_delay_penalty applies it (delay = 0:
+// unchanged).  Live label cells only (t < T_b, u < U_b), so frames[b,u] is read for u < U_b alone; the window is formed in 64
+// bits (any int32 frame and buffer).  One thread per skewed slot, in place; runs instead of k_delay_penalty.
+__global__ __launch_bounds__(256) void k_restrict(float *__restrict__ lpe_s, const int32_t *__restrict__ frames,
+                                                  const int32_t *__restrict__ logit_lens,
+                                                  const int32_t *__restrict__ target_lens, int B, int T, int U1,
+                                                  int D, int left, int right, float delay)
+{
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long per = (long)D * U1;
+    if (idx >= per * B) return;
+    const int b = (int)(idx / per);
+    const long rem = idx - (long)b * per;
+    const int d = (int)(rem / U1);
+    const int u = (int)(rem - (long)d * U1);
+    const int t = d - u;
+    if (t < 0 || t >= len_t(logit_lens, b, T) || u >= len_u(target_lens, b, U1)) return;
+    const long f = frames[(long)b * (U1 - 1) + u];
+    if (t < f - left || t > f + right) lpe_s[idx] = RNNT_NEG_INF;
+    else if (delay > 0.f) lpe_s[idx] -= delay * (float)t;
+}
+
 // cost_b = -log P'_b = -beta(0,0) - U_b delta (T_b - 1) / 2, from the fp64 beta of the shifted
-// lattice (one rounding); a NaN cost (NaN input, failed sweep) stays NaN.
+// lattice (one rounding); a NaN cost (NaN input, failed sweep) stays NaN, and +inf (a restricted
+// lattice without a path: beta(0,0) = -inf) stays +inf.
 __global__ void k_delay_cost(const double *__restrict__ beta_s, const int32_t *__restrict__ logit_lens,
                              const int32_t *__restrict__ target_lens, float *__restrict__ costs, int B,
                              int T, int U1, int D, float delay)
@@ -578,17 +664,22 @@ __global__ __launch_bounds__(1024) void k_lattice(
 
 void launch_lattice(const float *lpb_s, const float *lpe_s, double *alpha_s, double *beta_s,
                     const int32_t *logit_lens, const int32_t *target_lens, float *costs, int B,
-                    int U1, int D, unsigned *err, hipStream_t st)
+                    int U1, int D, unsigned *err, hipStream_t st, bool restricted)
 {
     const int NW = (U1 + 63) / 64;
     const size_t mbox = (size_t)(NW - 1) * D * 12;  // chain mailboxes: 8 B value + 4 B tag per boundary and step
     if (mbox <= 64 * 1024) {
         if (NW > 1) launch_fill32(err, 0u, 4, st);  // one wave: no mailbox, no spin
-        hipLaunchKernelGGL(k_lattice_chain, dim3(B, 2), dim3(64 * NW), (mbox + 15) / 16 * 16, st, lpb_s, lpe_s, alpha_s,
-                           beta_s, logit_lens, target_lens, costs, U1, D, err);
+        if (restricted)
+            hipLaunchKernelGGL(k_lattice_chain_restrict, dim3(B, 2), dim3(64 * NW), (mbox + 15) / 16 * 16, st, lpb_s, lpe_s,
+                               alpha_s, beta_s, logit_lens, target_lens, costs, U1, D, err);
+        else
+            hipLaunchKernelGGL(k_lattice_chain, dim3(B, 2), dim3(64 * NW), (mbox + 15) / 16 * 16, st, lpb_s, lpe_s, alpha_s,
+                               beta_s, logit_lens, target_lens, costs, U1, D, err);
         if (NW > 1) hipLaunchKernelGGL(k_lattice_status, dim3(1), dim3(64), 0, st, err, costs, B);
         return;
     }
+    // (the barrier sweep needs no restricted form: its log-add-exp and its validity select are -inf-safe as they are)
     const int NT = ((U1 + 63) / 64) * 64;
     const size_t lds = 2 * (size_t)(NT + 2) * sizeof(double);
     hipLaunchKernelGGL(k_lattice, dim3(B, 2), dim3(NT), lds, st, lpb_s, lpe_s, alpha_s, beta_s,
@@ -626,6 +717,33 @@ void launch_coef_fastemit(const double *alpha_s, const double *beta_s, const flo
     hipLaunchKernelGGL(k_coef_fastemit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, alpha_s,
                        beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B,
                        T, U1, D, scale, lambda);
+}
+
+void launch_coef_restrict(const double *alpha_s, const double *beta_s, const float *denom_s,
+                          const float *lpb_s, const float *lpe_s, const int32_t *targets,
+                          const int32_t *logit_lens, const int32_t *target_lens, CellCoef *coef, int B,
+                          int T, int U1, int D, float scale, float lambda, const double *flush_log2, float flush_lin,
+                          hipStream_t st)
+{
+    const long n = (long)B * D * U1;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (lambda > 0.f)
+        hipLaunchKernelGGL(k_coef_restrict_fastemit, grid, dim3(256), 0, st, alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets,
+                           logit_lens, target_lens, coef, B, T, U1, D, scale, lambda);
+    else if (flush_log2)
+        hipLaunchKernelGGL(k_coef_restrict_flush, grid, dim3(256), 0, st, alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets,
+                           logit_lens, target_lens, coef, B, T, U1, D, scale, *flush_log2, flush_lin);
+    else
+        hipLaunchKernelGGL(k_coef_restrict, grid, dim3(256), 0, st, alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets,
+                           logit_lens, target_lens, coef, B, T, U1, D, scale);
+}
+
+void launch_restrict(float *lpe_s, const int32_t *frames, const int32_t *logit_lens, const int32_t *target_lens, int B,
+                     int T, int U1, int D, int left, int right, float delay, hipStream_t st)
+{
+    const long n = (long)B * D * U1;
+    hipLaunchKernelGGL(k_restrict, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, lpe_s, frames, logit_lens,
+                       target_lens, B, T, U1, D, left, right, delay);
 }
 
 void launch_delay_penalty(float *lpe_s, const int32_t *logit_lens, const int32_t *target_lens, int B,

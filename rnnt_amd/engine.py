@@ -67,6 +67,9 @@ SIGNATURES = {
     "rnnt_engine_loss_fwd_bwd_reg": "ppppiiiiifffipppzp",
     "rnnt_engine_joint_loss_fwd_bwd_reg": "ppppppppiiiiiiffffippppppzp",
     "rnnt_engine_joint_loss_fwd_reg": "ppppppppiiiiiifippzp",
+    "rnnt_engine_loss_fwd_bwd_restrict": "ppppiiiiifffpiiipppzp",
+    "rnnt_engine_joint_loss_fwd_bwd_restrict": "ppppppppiiiiiiffffpiiippppppzp",
+    "rnnt_engine_joint_loss_fwd_restrict": "ppppppppiiiiiifpiiippzp",
     "rnnt_engine_align": "ppppiiiiipppzp",
     "rnnt_engine_joint_align": "ppppppppiiiiiiipppzp",
     "rnnt_engine_joint_bwd_workspace_bytes": "iiiiiip",
@@ -155,6 +158,7 @@ EXPORTS = (
     "rnnt_engine_linear_x2_workspace_bytes", "rnnt_engine_linear_x2_fwd", "rnnt_engine_linear_x2_bwd",
     "rnnt_engine_align", "rnnt_engine_joint_align",
     "rnnt_engine_loss_fwd_bwd_reg", "rnnt_engine_joint_loss_fwd_bwd_reg", "rnnt_engine_joint_loss_fwd_reg",
+    "rnnt_engine_loss_fwd_bwd_restrict", "rnnt_engine_joint_loss_fwd_bwd_restrict", "rnnt_engine_joint_loss_fwd_restrict",
     "rnnt_engine_encoder_packed_bytes", "rnnt_engine_encoder_pack", "rnnt_engine_encoder_workspace_bytes",
     "rnnt_engine_encoder_fwd", "rnnt_engine_encoder_stream_push",
 )
@@ -402,6 +406,28 @@ def check_reg(fastemit_lambda, delay_penalty):
     return tuple(out)
 
 
+def check_restrict(restrict_frames, restrict_left, restrict_right, B, U, dev=None):
+    """The alignment restriction's arguments: frames int32 [B,U], contiguous, on the HIP device (`dev`: the
+    other tensors' device); the two buffers as ints >= 0.  No synchronisation: the entries are not read here."""
+    for name, v in (("restrict_left", restrict_left), ("restrict_right", restrict_right)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"rnnt_amd: {name} must be an int >= 0 (got {v!r})")
+        if not 0 <= v < 2 ** 31:
+            raise ValueError(f"rnnt_amd: {name} must be >= 0 and fit a C int (got {v!r})")
+    if not isinstance(restrict_frames, torch.Tensor):
+        raise RuntimeError("restrict_frames must be a tensor")
+    if restrict_frames.dtype != torch.int32:
+        raise RuntimeError("restrict_frames must be int32 type")
+    if restrict_frames.dim() != 2 or tuple(restrict_frames.shape) != (B, U):
+        raise RuntimeError("restrict_frames must have shape [B, U] (max target length), as targets")
+    if not restrict_frames.is_contiguous():
+        raise RuntimeError("restrict_frames must be contiguous")
+    _require_cuda(restrict_frames)
+    if dev is not None and restrict_frames.device != dev:
+        raise RuntimeError("restrict_frames must be on the device of the other tensors")
+    return restrict_left, restrict_right
+
+
 def loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp=-1.0, want_grad=True):
     """Per-utterance costs and d(sum costs)/d logits (reference rnnt/model.py:35-41)."""
     return _loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp, want_grad, None)
@@ -415,7 +441,17 @@ def loss_fwd_bwd_reg(logits, targets, logit_lens, target_lens, blank, clamp, fas
                          check_reg(fastemit_lambda, delay_penalty))
 
 
-def _loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp, want_grad, reg):
+def loss_fwd_bwd_restrict(logits, targets, logit_lens, target_lens, blank, clamp, fastemit_lambda, delay_penalty,
+                          restrict_frames, restrict_left, restrict_right, want_grad=True):
+    """loss_fwd_bwd_reg on the lattice restricted to restrict_frames[b,u] - restrict_left <= t <= restrict_frames[b,u] +
+    restrict_right for label u (C ABI rnnt_engine_loss_fwd_bwd_restrict)."""
+    B, _, U1, _ = logits.shape
+    win = check_restrict(restrict_frames, restrict_left, restrict_right, B, U1 - 1, logits.device)
+    return _loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp, want_grad,
+                         check_reg(fastemit_lambda, delay_penalty), (restrict_frames,) + win)
+
+
+def _loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp, want_grad, reg, restrict=None):
     dev = _require_cuda(logits, targets, logit_lens, target_lens)
     _require_dtype(torch.float32, logits=logits)
     _require_dtype(torch.int32, targets=targets, logit_lens=logit_lens, target_lens=target_lens)
@@ -430,7 +466,10 @@ def _loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp, want_g
         ws = workspace(dev, n.value)
         head = (_p(logits), _p(targets), _p(logit_lens), _p(target_lens), B, T, U1, V, int(blank), ctypes.c_float(clamp))
         tail = (DTYPE_F32, _p(costs), _p(grad), _p(ws), ctypes.c_size_t(ws.numel()), _stream(dev))
-        if reg is None:
+        if restrict is not None:
+            _check(lib().rnnt_engine_loss_fwd_bwd_restrict(*head, ctypes.c_float(reg[0]), ctypes.c_float(reg[1]),
+                                                           _p(_nonempty(restrict[0])), restrict[1], restrict[2], *tail))
+        elif reg is None:
             _check(lib().rnnt_engine_loss_fwd_bwd(*head, *tail))
         else:
             _check(lib().rnnt_engine_loss_fwd_bwd_reg(*head, ctypes.c_float(reg[0]), ctypes.c_float(reg[1]), *tail))
@@ -534,6 +573,52 @@ def joint_loss_fwd_bwd_reg(enc, pred, W, bias, targets, logit_lens, target_lens,
         a = _fused_args(enc, pred, W, bias, targets, logit_lens, target_lens, blank, grad_scale, outs, ws, code)
         _check(lib().rnnt_engine_joint_loss_fwd_bwd_reg(*a[:15], a[15], ctypes.c_float(fe), ctypes.c_float(dp), *a[16:]))
     return outs
+
+
+def joint_loss_fwd_bwd_restrict(enc, pred, W, bias, targets, logit_lens, target_lens, blank, grad_scale, fastemit_lambda,
+                                delay_penalty, restrict_frames, restrict_left, restrict_right, outs=None, *, dtype):
+    """joint_loss_fwd_bwd_reg on the restricted lattice (C ABI rnnt_engine_joint_loss_fwd_bwd_restrict): label u
+    of utterance b is emitted only at frames restrict_frames[b,u] - restrict_left .. restrict_frames[b,u] + restrict_right.  An
+    utterance without a surviving path has cost +inf and zero gradient contributions."""
+    fe, dp = check_reg(fastemit_lambda, delay_penalty)
+    dev = _check_fused_inputs(enc, pred, W, bias, targets, logit_lens, target_lens)
+    left, right = check_restrict(restrict_frames, restrict_left, restrict_right, enc.shape[0], pred.shape[1] - 1, dev)
+    targets = _nonempty(targets)
+    with torch.cuda.device(dev):
+        if outs is None:
+            outs = alloc_fused_outputs(enc, pred, W)
+        else:
+            _require_cuda(enc, *outs)
+            _require_dtype(torch.float32, **{f"outs[{i}]": o for i, o in enumerate(outs)})
+            _require_contiguous(**{f"outs[{i}]": o for i, o in enumerate(outs)})
+        code = dtype_code(dtype)
+        B, T, H = enc.shape
+        ws = workspace(dev, workspace_bytes(B, T, pred.shape[1], H, W.shape[0], code))
+        a = _fused_args(enc, pred, W, bias, targets, logit_lens, target_lens, blank, grad_scale, outs, ws, code)
+        _check(lib().rnnt_engine_joint_loss_fwd_bwd_restrict(*a[:15], a[15], ctypes.c_float(fe), ctypes.c_float(dp),
+                                                             _p(_nonempty(restrict_frames)), left, right, *a[16:]))
+    return outs
+
+
+def joint_loss_fwd_restrict(enc, pred, W, bias, targets, logit_lens, target_lens, blank, delay_penalty, restrict_frames,
+                            restrict_left, restrict_right, *, dtype):
+    """joint_loss_fwd_reg on the restricted lattice (C ABI rnnt_engine_joint_loss_fwd_restrict): costs only, forward kernels only."""
+    _, dp = check_reg(0.0, delay_penalty)
+    dev = _check_fused_inputs(enc, pred, W, bias, targets, logit_lens, target_lens)
+    B, T, H = enc.shape
+    U1 = pred.shape[1]
+    V = W.shape[0]
+    left, right = check_restrict(restrict_frames, restrict_left, restrict_right, B, U1 - 1, dev)
+    targets = _nonempty(targets)
+    code = dtype_code(dtype)
+    with torch.cuda.device(dev):
+        costs = torch.empty(B, dtype=torch.float32, device=dev)
+        ws = workspace(dev, workspace_bytes(B, T, U1, H, V, code))
+        _check(lib().rnnt_engine_joint_loss_fwd_restrict(
+            _p(enc), _strides3(enc), _p(pred), _p(W), _p(bias), _p(targets), _p(logit_lens),
+            _p(target_lens), B, T, U1, H, V, int(blank), ctypes.c_float(dp), _p(_nonempty(restrict_frames)), left, right,
+            code, _p(costs), _p(ws), ctypes.c_size_t(ws.numel()), _stream(dev)))
+    return costs
 
 
 def joint_loss_fwd_reg(enc, pred, W, bias, targets, logit_lens, target_lens, blank, delay_penalty, *, dtype):

@@ -7,6 +7,9 @@
                         call; the (B,T,U+1,V) logits never leave the engine's workspace.
   fastemit_lambda / delay_penalty (both loss operators): FastEmit and the delay penalty, the
                         latency regularisers of streaming transducers.
+  restrict_frames / restrict_left / restrict_right (both loss operators): the alignment-restricted
+                        loss, "Ar-RNN-T" (DESIGN.md §4n): label u only within a window of frames around
+                        a reference alignment, e.g. the `frames` of rnnt_align / joint_rnnt_align.
   rnnt_align(...), joint_rnnt_align(...)
                         forced alignment on the same lattice: the best path's
                         log-probability and the frame of every label; no autograd.
@@ -57,11 +60,33 @@ def _check_loss_args(T, U1, V, B, targets, logit_lengths, target_lengths, blank,
     return blank
 
 
+def _check_restrict_args(restrict_frames, restrict_left, restrict_right, B, U, logit_lengths, target_lengths, check_lengths):
+    """The alignment restriction's arguments -> (left, right).  Tensor and buffer checks always; under
+    `check_lengths` (which synchronises already) the live entries too: for u < target_lengths[b], 0 <= frames[b,u] <=
+    logit_lengths[b] - 1 and non-decreasing in u — such an alignment is itself a surviving path, so every cost is finite."""
+    left, right = engine.check_restrict(restrict_frames, restrict_left, restrict_right, B, U)
+    if check_lengths and U > 0:
+        live = torch.arange(U, device=restrict_frames.device)[None, :] < target_lengths[:, None]
+        f = restrict_frames.long()
+        in_range = (f >= 0) & (f <= logit_lengths.long()[:, None] - 1)
+        ordered = torch.ones_like(live)
+        ordered[:, 1:] = f[:, 1:] >= f[:, :-1]
+        if bool((live & ~in_range).any()):
+            raise ValueError("restrict_frames: a live entry lies outside [0, logit_lengths[b] - 1]")
+        if bool((live & ~ordered).any()):
+            raise ValueError("restrict_frames: the live entries of an utterance must be non-decreasing")
+    return left, right
+
+
 class _RNNTLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, targets, logit_lengths, target_lengths, blank, clamp, fastemit_lambda=0.0,
-                delay_penalty=0.0):
-        if fastemit_lambda or delay_penalty:
+                delay_penalty=0.0, restrict=None):
+        if restrict is not None:
+            costs, grad = engine.loss_fwd_bwd_restrict(logits, targets, logit_lengths, target_lengths, blank, clamp,
+                                                       fastemit_lambda, delay_penalty, *restrict,
+                                                       want_grad=ctx.needs_input_grad[0])
+        elif fastemit_lambda or delay_penalty:
             costs, grad = engine.loss_fwd_bwd_reg(logits, targets, logit_lengths, target_lengths, blank, clamp,
                                                   fastemit_lambda, delay_penalty, want_grad=ctx.needs_input_grad[0])
         else:
@@ -74,16 +99,22 @@ class _RNNTLoss(torch.autograd.Function):
     def backward(ctx, grad_costs):
         (grad,) = ctx.saved_tensors
         if grad is None:
-            return None, None, None, None, None, None, None, None
-        return grad * grad_costs.view(-1, 1, 1, 1), None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None, None
+        return grad * grad_costs.view(-1, 1, 1, 1), None, None, None, None, None, None, None, None
 
 
 def rnnt_loss(logits, targets, logit_lengths, target_lengths, blank=-1, clamp=-1, reduction="mean",
-              fused_log_softmax=True, check_lengths=True, fastemit_lambda=0.0, delay_penalty=0.0):
+              fused_log_softmax=True, check_lengths=True, fastemit_lambda=0.0, delay_penalty=0.0,
+              restrict_frames=None, restrict_left=0, restrict_right=0):
     """Transducer loss on materialised logits [B,T,U+1,V] (reference rnnt/model.py:35-41).
     `fastemit_lambda` / `delay_penalty` (finite, >= 0): FastEmit adds lambda E (p_k - [k = y]) to the
     gradient of every label cell and leaves the costs unchanged; the delay penalty runs the lattice on
-    lp_emit + delta ((T_b - 1) / 2 - t) and returns the penalised costs.  `clamp` applies to the regularised gradient."""
+    lp_emit + delta ((T_b - 1) / 2 - t) and returns the penalised costs.  `clamp` applies to the regularised gradient.
+    `restrict_frames` (int32 [B,U] on the device, e.g. rnnt_align's frames; None: no restriction) with `restrict_left` /
+    `restrict_right` (ints >= 0, in frames): label u of utterance b is emitted only at frames
+    restrict_frames[b,u] - restrict_left .. restrict_frames[b,u] + restrict_right; costs and gradients are those of the
+    paths that remain (an utterance without one: cost +inf, zero gradient).  Entries at u >= target_lengths[b] are ignored;
+    under `check_lengths` the live ones must lie in [0, logit_lengths[b] - 1] and not decrease (ValueError)."""
     fastemit_lambda, delay_penalty = engine.check_reg(fastemit_lambda, delay_penalty)
     if not fused_log_softmax:
         raise NotImplementedError("rnnt_amd.rnnt_loss only implements fused_log_softmax=True")
@@ -96,11 +127,15 @@ def rnnt_loss(logits, targets, logit_lengths, target_lengths, blank=-1, clamp=-1
     B, T, U1, V = logits.shape
     blank = _check_loss_args(T, U1, V, B, targets, logit_lengths, target_lengths, blank, reduction,
                              check_lengths)
+    restrict = None
+    if restrict_frames is not None:
+        restrict = (restrict_frames,) + _check_restrict_args(restrict_frames, restrict_left, restrict_right, B, U1 - 1,
+                                                             logit_lengths, target_lengths, check_lengths)
     if V % 4 != 0:
         pad = 4 - V % 4
         logits = torch.nn.functional.pad(logits, (0, pad), value=_PAD_NEG)
     costs = _RNNTLoss.apply(logits, targets, logit_lengths, target_lengths, blank, float(clamp), fastemit_lambda,
-                            delay_penalty)
+                            delay_penalty, restrict)
     if reduction == "mean":
         return costs.mean()
     if reduction == "sum":
@@ -181,9 +216,12 @@ def linear(x, W, bias, backend="auto"):
 class _JointRNNTLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, enc, pred, W, bias, targets, logit_lengths, target_lengths, blank, scale,
-                dtype, need_grad=True, fastemit_lambda=0.0, delay_penalty=0.0):
+                dtype, need_grad=True, fastemit_lambda=0.0, delay_penalty=0.0, restrict=None):
         if not need_grad:  # torch.no_grad() / nothing requires grad: forward kernels only
-            if delay_penalty:  # (FastEmit changes no cost)
+            if restrict is not None:
+                costs = engine.joint_loss_fwd_restrict(enc, pred.contiguous(), W.contiguous(), bias.contiguous(), targets,
+                                                       logit_lengths, target_lengths, blank, delay_penalty, *restrict, dtype=dtype)
+            elif delay_penalty:  # (FastEmit changes no cost)
                 costs = engine.joint_loss_fwd_reg(enc, pred.contiguous(), W.contiguous(), bias.contiguous(), targets,
                                                   logit_lengths, target_lengths, blank, delay_penalty, dtype=dtype)
             else:
@@ -191,7 +229,11 @@ class _JointRNNTLoss(torch.autograd.Function):
                                               targets, logit_lengths, target_lengths, blank, dtype=dtype)
             ctx.mark_non_differentiable(costs)
             return costs.sum() * scale, costs
-        if fastemit_lambda or delay_penalty:
+        if restrict is not None:
+            costs, ge, gp, gW, gb = engine.joint_loss_fwd_bwd_restrict(
+                enc, pred.contiguous(), W.contiguous(), bias.contiguous(), targets, logit_lengths,
+                target_lengths, blank, scale, fastemit_lambda, delay_penalty, *restrict, dtype=dtype)
+        elif fastemit_lambda or delay_penalty:
             costs, ge, gp, gW, gb = engine.joint_loss_fwd_bwd_reg(
                 enc, pred.contiguous(), W.contiguous(), bias.contiguous(), targets, logit_lengths,
                 target_lengths, blank, scale, fastemit_lambda, delay_penalty, dtype=dtype)
@@ -208,12 +250,13 @@ class _JointRNNTLoss(torch.autograd.Function):
     def backward(ctx, grad_loss, _grad_costs):
         ge, gp, gW, gb = ctx.saved_tensors
         return (ge * grad_loss, gp * grad_loss, gW * grad_loss, gb * grad_loss,
-                None, None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None, None)
 
 
 def joint_rnnt_loss(enc, pred, W, bias, targets, logit_lengths, target_lengths, blank=-1,
                     reduction="mean", check_lengths=True, return_costs=False, grad_scale=None,
-                    dtype=engine.DEFAULT_DTYPE, fastemit_lambda=0.0, delay_penalty=0.0):
+                    dtype=engine.DEFAULT_DTYPE, fastemit_lambda=0.0, delay_penalty=0.0,
+                    restrict_frames=None, restrict_left=0, restrict_right=0):
     """Fused replacement of
         logits = joint(enc, pred)                      # reference rnnt/model.py:32
         loss = torchaudio.functional.rnnt_loss(logits, targets, ..., blank, clamp=-1, reduction)
@@ -228,7 +271,9 @@ def joint_rnnt_loss(enc, pred, W, bias, targets, logit_lengths, target_lengths, 
     split three ways, six bf16 products per fp32 product (include/rnnt_engine.h RNNT_DTYPE_F32_BF16X3);
     any H, V (zero-padded to multiples of 128 here).
     `fastemit_lambda` / `delay_penalty` (finite, >= 0): the latency regularisers, as rnnt_loss takes them (DESIGN.md §4k);
-    both are per utterance and FastEmit is linear in `grad_scale`, so sharded calls still sum to the full batch's gradients."""
+    both are per utterance and FastEmit is linear in `grad_scale`, so sharded calls still sum to the full batch's gradients.
+    `restrict_frames` / `restrict_left` / `restrict_right`: the alignment-restricted loss, as rnnt_loss takes it (DESIGN.md §4n);
+    `restrict_frames` is what joint_rnnt_align returns as `frames`.  Per utterance as well: shards sum to the full batch."""
     fastemit_lambda, delay_penalty = engine.check_reg(fastemit_lambda, delay_penalty)
     if reduction not in ("mean", "sum"):
         if reduction == "none":
@@ -255,8 +300,12 @@ def joint_rnnt_loss(enc, pred, W, bias, targets, logit_lengths, target_lengths, 
     scale = float(grad_scale) if grad_scale is not None else (1.0 / B if reduction == "mean" else 1.0)
     # validation / eval (reference rnnt/train.py:170-201 runs the model under no_grad): costs only
     need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (enc, pred, W, bias))
+    restrict = None
+    if restrict_frames is not None:
+        restrict = (restrict_frames,) + _check_restrict_args(restrict_frames, restrict_left, restrict_right, B, U1 - 1,
+                                                             logit_lengths, target_lengths, check_lengths)
     loss, costs = _JointRNNTLoss.apply(enc_p, pred_p, W_p, bias_p, targets, logit_lengths,
-                                       target_lengths, blank, scale, code, need_grad, fastemit_lambda, delay_penalty)
+                                       target_lengths, blank, scale, code, need_grad, fastemit_lambda, delay_penalty, restrict)
     return (loss, costs) if return_costs else loss
 
 

@@ -66,7 +66,9 @@ class JointNetwork(torch.nn.Module):
 
     def fused_loss(self, audio_frame, text_frame, targets, logit_lengths, target_lengths,
                    blank=-1, reduction="mean", **kw):
-        """joint + transducer loss in one engine call (reference model.py:32-41)."""
+        """joint + transducer loss in one engine call (reference model.py:32-41).  Keywords go to joint_rnnt_loss: the latency
+        regularisers (fastemit_lambda, delay_penalty) and the alignment restriction (restrict_frames, restrict_left,
+        restrict_right) among them."""
         kw.setdefault("dtype", self.compute_dtype)
         audio_frame, text_frame = self._project(audio_frame, text_frame)
         return F_amd.joint_rnnt_loss(audio_frame, text_frame, self.joint_ln.weight,

@@ -22,10 +22,26 @@ class RNNTModel(torch.nn.Module):
         # lambda and the delay penalty's delta, both >= 0; 0 = the reference's plain loss
         self.fastemit_lambda = 0.0
         self.delay_penalty = 0.0
+        # alignment-restricted loss: called as model(..., blank_idx, restrict_frames=frames), label u is emitted only
+        # at encoder frames frames[n,u] - restrict_left .. frames[n,u] + restrict_right; ints >= 0
+        self.restrict_left = 0
+        self.restrict_right = 0
+        self._restrict_frames = None  # the frames of the call in progress (__call__)
 
     @property
     def device(self):
         return next(self.parameters()).device
+
+    def __call__(self, *args, restrict_frames=None, **kwargs):
+        """model(mel, mel_lens, ids, id_lens, blank_idx, restrict_frames=None): the reference's five arguments, and the optional
+        reference alignment of the alignment-restricted loss (int32 [N,U] on the device, e.g. a teacher's `align(...)[1]`;
+        DESIGN.md §4n).  `forward` keeps the reference's signature, which callers introspect and wrappers such as DDP pass
+        through; the frames travel beside it for the duration of the call."""
+        self._restrict_frames = restrict_frames
+        try:
+            return super().__call__(*args, **kwargs)
+        finally:
+            self._restrict_frames = None
 
     def forward(self, mel_features: torch.Tensor, mel_feature_lens: torch.Tensor,
                 input_ids: torch.Tensor, input_id_lens: torch.Tensor,
@@ -45,6 +61,8 @@ class RNNTModel(torch.nn.Module):
             reg["fastemit_lambda"] = self.fastemit_lambda
         if self.delay_penalty:
             reg["delay_penalty"] = self.delay_penalty
+        if self._restrict_frames is not None:
+            reg.update(restrict_frames=self._restrict_frames, restrict_left=self.restrict_left, restrict_right=self.restrict_right)
         return self.joint.fused_loss(audio_features, decoder_features,
                                      targets=input_ids.int(),
                                      logit_lengths=audio_feature_lens.int(),

@@ -21,6 +21,24 @@ def shard_bounds(batch: int, world: int, rank: int):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def shard_utterances(world: int, rank: int, *tensors):
+    """`rank`'s shard_bounds slice of every per-utterance tensor (leading dimension = the batch: enc, pred, targets, the two
+    length tensors, restrict_frames of the alignment-restricted loss, ...: views, contiguous where the whole was); a None passes
+    through (an option that is off).  Costs, grad_enc and grad_pred of the shards concatenate to the full batch's and dW / db
+    sum to it, with grad_scale = 1 / B_global on every shard — the restricted loss included, its costs being per utterance."""
+    batch = next(t.shape[0] for t in tensors if t is not None)
+    lo, hi = shard_bounds(batch, world, rank)
+    out = []
+    for t in tensors:
+        if t is None:
+            out.append(None)
+            continue
+        if t.shape[0] != batch:
+            raise RuntimeError("shard_utterances: every tensor must have the batch as its leading dimension")
+        out.append(t[lo:hi])
+    return tuple(out)
+
+
 class FlatGrad:
     """One flat fp32 buffer [dW (V*H) | db (V) | loss, pad]; grad_W / grad_bias are views of it,
     so the engine writes straight into the all-reduce buffer (no packing copy)."""
