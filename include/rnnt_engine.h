@@ -713,6 +713,61 @@ int rnnt_engine_encoder_stream_push(const rnnt_encoder_layer *layers, int n_laye
                                     size_t ws_bytes, void *stream);
 
 /*
+ * The audio featurizer (reference rnnt/featurizer.py): samples to the features the encoder reads.  Frame f,
+ * bin k (n_fft / 2 + 1 bins) of utterance n:
+ *     p = | sum_j w[j] x[f * hop_length + j] exp(-2 pi i j k / n_fft) |^2        (torch.stft, onesided, not normalized)
+ *     with n_filters > 0:  p[m] = sum_k p[k] fbank[k][m]                         (fbank: n_freq x n_filters fp32, row-major)
+ *     v = log(p + 1e-6)                                  RNNT_FEAT_LOG_PLAIN
+ *         p > 0.01 ? log p : 50 p + log(0.01) - 0.5      RNNT_FEAT_LOG_PIECEWISE
+ *         log((p + 1e-6) gain)                           RNNT_FEAT_LOG_GAIN
+ *     out[n * s0 + k * s1 + f * s2] = (v - mean[k]) * invstd[k]                  (mean, invstd: F floats on the device,
+ *                                                                                 F = n_filters, or the bins without one)
+ * The window (win_length fp32 values on the device) is centred in n_fft with zeros, as torch.stft does.  center = 1 reflects
+ * n_fft / 2 samples at both ends.  Frames per utterance of `len` samples, host arithmetic: (len - n_fft) / hop + 1 (0 below
+ * n_fft), or len / hop + 1 with center.
+ *
+ * rnnt_engine_featurizer_pack writes the windowed DFT basis once (rnnt_engine_featurizer_basis_bytes; 16-byte aligned); the
+ * other calls read it.  rnnt_engine_featurizer_fwd: N waveforms of T samples, wave_stride samples apart, fp32
+ * (RNNT_FEAT_PCM_F32) or int16 scaled by 1 / 32768 (RNNT_FEAT_PCM_S16); `lens`: HOST array of N sample counts (0 .. T), or
+ * NULL = all T.  `out` holds L frames per utterance through out_strides (floats; batch entry, bin, frame): L is at least the
+ * longest utterance's frame count (checked), frames from an utterance's own count up to L are stored as zeros.  workspace:
+ * rnnt_engine_featurizer_workspace_bytes(desc, N, L) — 0 without a filterbank, NULL is then fine.
+ * rnnt_engine_featurizer_stream_push: one push of N streams; X~ = state_in (N x state_in_len fp32, contiguous) followed by
+ * the chunk (N x T).  L must be the frames X~ completes and state_out_len what it leaves, len(X~) - L * hop_length (both
+ * checked; HOST ints); state_out (N x state_out_len fp32) is X~ from sample L * hop_length on and is never state_in.  A push
+ * that completes no frame is valid (L = 0, out may be NULL).  T = 0 is valid.  center = 1 is refused.
+ * Every (bin, frame) is summed in one fixed order: results are bitwise reproducible and a streamed utterance equals the whole
+ * one bit for bit.  No atomics, no host synchronisation.  RNNT_ERR_INVALID_ARG: null pointers, hop_length < 1,
+ * win_length > n_fft, odd n_fft - win_length, a reflect pad not shorter than the utterance, a wrong L or state length;
+ * RNNT_ERR_UNSUPPORTED: 31 hop_length + n_fft samples beyond the kernel's 64 KB stage, a stream with hop_length > n_fft
+ * (samples between frames would be skipped, not carried).  Everything is checked before
+ * anything is enqueued.
+ */
+#define RNNT_FEAT_LOG_PLAIN 0
+#define RNNT_FEAT_LOG_PIECEWISE 1
+#define RNNT_FEAT_LOG_GAIN 2
+#define RNNT_FEAT_PCM_F32 0
+#define RNNT_FEAT_PCM_S16 1
+typedef struct rnnt_featurizer_desc {
+    int n_fft, win_length, hop_length;
+    int center;   /* 0 or 1 */
+    int log_kind; /* RNNT_FEAT_LOG_* */
+    float gain;   /* RNNT_FEAT_LOG_GAIN */
+    int n_filters; /* 0: no filterbank */
+} rnnt_featurizer_desc;
+int rnnt_engine_featurizer_basis_bytes(const rnnt_featurizer_desc *desc, size_t *out);
+int rnnt_engine_featurizer_pack(const rnnt_featurizer_desc *desc, const float *window, void *basis, size_t basis_bytes, void *stream);
+int rnnt_engine_featurizer_workspace_bytes(const rnnt_featurizer_desc *desc, int N, int L, size_t *out);
+int rnnt_engine_featurizer_fwd(const rnnt_featurizer_desc *desc, const void *basis, const void *fbank, const void *wave,
+                               int64_t wave_stride, int N, int T, const int32_t *lens, int pcm, const float *mean,
+                               const float *invstd, float *out, const int64_t out_strides[3], int L, void *workspace,
+                               size_t ws_bytes, void *stream);
+int rnnt_engine_featurizer_stream_push(const rnnt_featurizer_desc *desc, const void *basis, const void *fbank,
+                                       const float *state_in, int state_in_len, const void *chunk, int64_t chunk_stride, int N, int T,
+                                       int pcm, const float *mean, const float *invstd, float *out, const int64_t out_strides[3],
+                                       int L, float *state_out, int state_out_len, void *workspace, size_t ws_bytes, void *stream);
+
+/*
  * Multi-GPU step of the path (the suggested export of 8b): ONE sum all-reduce, in
  * place, of `count` fp32 values — the flat [dW (V*H) | db (V) | loss] buffer of a batch-sharded
  * step — on the caller's RCCL communicator (`comm` is an ncclComm_t) and stream.  Stands where the

@@ -114,6 +114,11 @@ SIGNATURES = {
     "rnnt_engine_encoder_workspace_bytes": "piiiipp",
     "rnnt_engine_encoder_fwd": "pipppiiippzp",
     "rnnt_engine_encoder_stream_push": "pipppiippppippzp",
+    "rnnt_engine_featurizer_basis_bytes": "pp",
+    "rnnt_engine_featurizer_pack": "pppzp",
+    "rnnt_engine_featurizer_workspace_bytes": "piip",
+    "rnnt_engine_featurizer_fwd": "ppppqiipippppipzp",
+    "rnnt_engine_featurizer_stream_push": "ppppipqiiippppipipzp",
     "rnnt_engine_allreduce": "pzpp",
     "rnnt_engine_workspace_layout": "iiiiiip",
     "rnnt_engine_run_stage": "ippppppppiiiiiiffippppppzp",
@@ -161,6 +166,8 @@ EXPORTS = (
     "rnnt_engine_loss_fwd_bwd_restrict", "rnnt_engine_joint_loss_fwd_bwd_restrict", "rnnt_engine_joint_loss_fwd_restrict",
     "rnnt_engine_encoder_packed_bytes", "rnnt_engine_encoder_pack", "rnnt_engine_encoder_workspace_bytes",
     "rnnt_engine_encoder_fwd", "rnnt_engine_encoder_stream_push",
+    "rnnt_engine_featurizer_basis_bytes", "rnnt_engine_featurizer_pack", "rnnt_engine_featurizer_workspace_bytes",
+    "rnnt_engine_featurizer_fwd", "rnnt_engine_featurizer_stream_push",
 )
 
 # per-call kernel variants (include/rnnt_engine.h RNNT_VARIANT_*): bit-identical results

@@ -14,6 +14,9 @@ class RNNTModel(torch.nn.Module):
         self.predictor = predictor
         self.encoder = encoder
         self.joint = joint
+        # optional waveform front end (rnnt_amd.TFJSSpectrogram, ...): GreedyStream.push_audio / BeamStream.push_audio featurize with it;
+        # forward, greedy_decode and beam_search take mel features and never look at it
+        self.featurizer = None
         # torchaudio's host-side length checks (max(lengths) == T / U: they synchronise).  False skips
         # them — the kernels clamp every length into range — so that forward + backward enqueue
         # device work only and can be captured into a HIP graph.

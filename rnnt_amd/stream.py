@@ -95,6 +95,41 @@ def _to_device(x, dev):
     return x
 
 
+def _featurize_push(stream, samples, what):
+    """push_audio's front half, shared by GreedyStream and BeamStream: featurize one chunk of samples — (time,) or (1, time), fp32 or
+    int16, any length — from the sample state the stream keeps on the model's device (model.featurizer.streaming_forward) and append
+    the new frames to the stream's pending buffer.  Returns the pending (1, F, L) frames when the encoder can take them now, else None.
+    An rnnt_amd.AudioEncoder is asked through its own length arithmetic (`_lengths`: host ints, no launch) whether the push would
+    raise — no prologue output frame yet, or an instance norm over a single frame — and the frames are held back while it would; any
+    other encoder gets them as soon as there is one."""
+    from .encoder import AudioEncoder
+    model = stream.model
+    feat = getattr(model, "featurizer", None)
+    if feat is None:
+        raise TypeError(f"{what} needs model.featurizer (e.g. rnnt_amd.TFJSSpectrogram); push takes mel features directly")
+    if samples.dim() == 1:
+        samples = samples[None]
+    if samples.dim() != 2 or samples.shape[0] != 1:
+        raise ValueError(f"{what} takes one chunk of samples (time,) or (1, time), got {tuple(samples.shape)}")
+    dev = model.device
+    if stream._audio_state is None:
+        stream._audio_state = feat.streaming_init_state(1).to(dev)
+    frames, stream._audio_state = feat.streaming_forward(samples.to(dev), stream._audio_state)
+    if frames.shape[2]:
+        stream._pending = frames if stream._pending is None else torch.cat((stream._pending, frames), dim=2)
+    if stream._pending is None:
+        return None
+    enc = model.encoder
+    if isinstance(enc, AudioEncoder):
+        if stream._enc_state is None:
+            stream._enc_state = _to_device(enc.streaming_init_state(1), dev)
+        try:
+            enc._lengths(int(stream._pending.shape[2]), [int(s.shape[2]) for s in stream._enc_state])
+        except ValueError:
+            return None
+    return stream._pending
+
+
 class GreedyStream:
     """One utterance decoded push by push (RNNTModel.greedy_stream).  `push_encoded(audio_features)` takes a chunk of encoder output
     (1, C, n) as `encoder(...)` / `encoder.streaming_forward` return it and returns the labels it emitted; `push(mel_chunk)` runs the
@@ -123,6 +158,8 @@ class GreedyStream:
         self.last_path = None
         self._done = self.max_length is not None and self.max_length < 2  # (the reference's loop never runs: tokens = [blank] is full)
         self._enc_state = None
+        self._audio_state = None  # push_audio: the samples no frame has consumed yet (1, n), on the model's device
+        self._pending = None      # push_audio: frames featurized but not yet taken by the encoder (1, F, L)
         dev = model.device
         self._on_device = (dev.type == "cuda" and not model._predictor_is_stateful()
                            and model._device_loop_ok(torch.zeros(1, 1, device=dev)))
@@ -159,6 +196,21 @@ class GreedyStream:
             self._enc_state = _to_device(enc.streaming_init_state(1), self.model.device)
         out, self._enc_state = enc.streaming_forward(mel_chunk, self._enc_state)
         return self.push_encoded(out)
+
+    @torch.no_grad()
+    def push_audio(self, samples):
+        """Featurize one chunk of samples — (time,) or (1, time), fp32 or int16, any length — with model.featurizer from the sample
+        state the stream carries, then `push` the frames that are pending.  Frames an rnnt_amd.AudioEncoder cannot take yet (no
+        prologue output frame, an instance norm over one frame) wait for the next push; if `push` raises, they are kept.  Returns
+        the new labels."""
+        if self._done:
+            return []
+        mel = _featurize_push(self, samples, "GreedyStream.push_audio")
+        if mel is None:
+            return []
+        new = self.push(mel)
+        self._pending = None
+        return new
 
     @torch.no_grad()
     def push_encoded(self, audio_features):
@@ -478,6 +530,8 @@ class BeamStream:
         self.model = model
         self._group = BeamStreamGroup(model, 1, beam_size, max_length, max_symbols_per_frame, context)
         self._enc_state = None
+        self._audio_state = None  # push_audio: the samples no frame has consumed yet (1, n), on the model's device
+        self._pending = None      # push_audio: frames featurized but not yet taken by the encoder (1, F, L)
 
     nbest = property(lambda self: self._group.nbest[0])
     tokens = property(lambda self: self._group.tokens[0])
@@ -488,6 +542,8 @@ class BeamStream:
     def reset(self):
         self._group.reset(0)
         self._enc_state = None
+        self._audio_state = None
+        self._pending = None
 
     @torch.no_grad()
     def push(self, mel_chunk):
@@ -503,6 +559,17 @@ class BeamStream:
             self._enc_state = _to_device(enc.streaming_init_state(1), self.model.device)
         out, self._enc_state = enc.streaming_forward(mel_chunk, self._enc_state)
         return self.push_encoded(out)
+
+    @torch.no_grad()
+    def push_audio(self, samples):
+        """Featurize one chunk of samples — (time,) or (1, time), fp32 or int16, any length — with model.featurizer from the sample
+        state the stream carries, then `push` the frames that are pending (held back and kept as GreedyStream.push_audio does)."""
+        mel = _featurize_push(self, samples, "BeamStream.push_audio")
+        if mel is None:
+            return self.tokens
+        best = self.push(mel)
+        self._pending = None
+        return best
 
     @torch.no_grad()
     def push_encoded(self, audio_features):
