@@ -32,6 +32,7 @@ typedef __attribute__((address_space(3))) void *lds_void_ptr;
 
 #define DH_BT 8
 #define DW_KC 16   // cells per dW split-range granule (row padding unit)
+#define DW_ZERO_SPAN 32  // the widest live-row granule of a dW GEMM that reads k_dhidden_gen's G (k_dw: 16, k_dw_x3: 32)
 #define DH_BU 16
 
 // dHidden GEMM: dHidden[c,:] = G[c,:] @ W   (K = V), then dPre = dHidden * (1 - hidden^2)
@@ -302,10 +303,13 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_gen(JointBwdArgs a, const in
 
     if (!GEN && (t0 >= Tb || u0 > Ub)) return;  // dead tile: no slab is read
     if (t0 >= Tb) {  // workgroup-uniform: nothing to multiply, but k_dw must find zeros here
-        // k_dw only walks the live rows, rounded out to 16-cell granules (k_dw_table): up to 15
-        // cells past this utterance's live end, and up to 15 cells before the next utterance's
-        // first cell (= the last cells of this one).  Tiles that touch neither stay unwritten.
-        if ((long)t0 * U1 >= (long)Tb * U1 + DW_KC && (long)(t0 + BT) * U1 <= (long)T * U1 - DW_KC) return;
+        // The dW GEMMs only walk the live rows, rounded out to whole granules (k_dw_table): up to a granule
+        // less one cell past this utterance's live end, and as many before the next utterance's first
+        // cell (= the last cells of this one).  Tiles that touch neither stay unwritten.  The granule is
+        // DW_ZERO_SPAN = 32 cells, k_dw_x3's — that GEMM reads this G when the kernel stands in for
+        // k_dhidden_x3 (RNNT_VARIANT_X3_FP32_DH) — and covers k_dw's 16 (with 16 here, k_dw_x3 read the
+        // logits a tile 16..31 cells past a live end still held: tests/test_f32_stages_gpu.py rows_past_a_live_end).
+        if ((long)t0 * U1 >= (long)Tb * U1 + DW_ZERO_SPAN && (long)(t0 + BT) * U1 <= (long)T * U1 - DW_ZERO_SPAN) return;
         if (pexists) {
             const f32x4 z = {0.f, 0.f, 0.f, 0.f};
             for (int c8 = 0; c8 < VK; ++c8) *(f32x4 *)(lptr + 8 * c8) = z;

@@ -136,14 +136,15 @@ def coef64(d, work, costs, gs):
     return dict(c1=c1.reshape(-1), sb=sb.reshape(-1), se=se.reshape(-1), y=y.reshape(-1))
 
 
-def g_from_coef(logits, coef, V, real=np.float64):
-    """G [cells, V] from logits and coefficients, in `real` arithmetic (fp32: the kernels' formula, one fma and one exp2 per entry)."""
+def g_from_coef(logits, coef, V, real=np.float64, log2e=LOG2E):
+    """G [cells, V] from logits and coefficients, in `real` arithmetic (fp32: the kernels' formula, one fma and one exp2 per entry).
+    `log2e`: the constant of the fp64 form (tests/f32_stage_cases.py passes the kernels' fp32 one, to refer to their exponent)."""
     lg = np.where(np.isfinite(coef["c1"])[:, None], logits, 0.0).astype(real)
     c1 = coef["c1"].astype(real)[:, None]
     if real == np.float32:
         x = (lg.astype(np.float64) * float(LOG2E_F32) + c1.astype(np.float64)).astype(np.float32)  # fma: one rounding
     else:
-        x = lg * LOG2E + c1
+        x = lg * log2e + c1
     G = np.exp2(x).astype(real)
     rows = np.arange(G.shape[0])
     G[rows, V - 1] -= coef["sb"].astype(real)
