@@ -437,62 +437,68 @@ def check_restrict(restrict_frames, restrict_left, restrict_right, B, U, dev=Non
 
 def loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp=-1.0, want_grad=True):
     """Per-utterance costs and d(sum costs)/d logits (reference rnnt/model.py:35-41)."""
-    return _loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp, want_grad, None)
+    return _loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp, want_grad)
 
 
 def loss_fwd_bwd_reg(logits, targets, logit_lens, target_lens, blank, clamp, fastemit_lambda, delay_penalty,
                      want_grad=True):
     """loss_fwd_bwd with FastEmit and the delay penalty (C ABI rnnt_engine_loss_fwd_bwd_reg); `clamp`
     applies to the regularised gradient."""
-    return _loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp, want_grad,
-                         check_reg(fastemit_lambda, delay_penalty))
+    return _loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp, want_grad, (fastemit_lambda, delay_penalty))
 
 
 def loss_fwd_bwd_restrict(logits, targets, logit_lens, target_lens, blank, clamp, fastemit_lambda, delay_penalty,
                           restrict_frames, restrict_left, restrict_right, want_grad=True):
     """loss_fwd_bwd_reg on the lattice restricted to restrict_frames[b,u] - restrict_left <= t <= restrict_frames[b,u] +
     restrict_right for label u (C ABI rnnt_engine_loss_fwd_bwd_restrict)."""
-    B, _, U1, _ = logits.shape
-    win = check_restrict(restrict_frames, restrict_left, restrict_right, B, U1 - 1, logits.device)
-    return _loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp, want_grad,
-                         check_reg(fastemit_lambda, delay_penalty), (restrict_frames,) + win)
+    return _loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp, want_grad, (fastemit_lambda, delay_penalty),
+                         (restrict_frames, restrict_left, restrict_right))
 
 
-def _loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp, want_grad, reg, restrict=None):
+def _check_logits_inputs(logits, targets, logit_lens, target_lens):
     dev = _require_cuda(logits, targets, logit_lens, target_lens)
     _require_dtype(torch.float32, logits=logits)
     _require_dtype(torch.int32, targets=targets, logit_lens=logit_lens, target_lens=target_lens)
     _require_contiguous(logits=logits, targets=targets, logit_lens=logit_lens, target_lens=target_lens)
+    return dev
+
+
+def _call_on_logits(entry, logits, targets, logit_lens, target_lens, blank, mid, outs):
+    """One entry on materialised logits [B,T,U1,V] (rnnt_engine_loss_fwd_bwd*, rnnt_engine_align: one workspace serves them all):
+    the four input pointers, the dimensions and `blank`, the entry's own arguments `mid`, the output pointers, the workspace."""
+    dev = logits.device
     B, T, U1, V = logits.shape
     targets = _nonempty(targets)
+    n = ctypes.c_size_t(0)
+    _check(lib().rnnt_engine_loss_workspace_bytes(B, T, U1, V, DTYPE_F32, ctypes.byref(n)))
+    ws = workspace(dev, n.value)
+    _check(getattr(lib(), entry)(_p(logits), _p(targets), _p(logit_lens), _p(target_lens), B, T, U1, V, int(blank), *mid,
+                                 *[_p(o) for o in outs], _p(ws), ctypes.c_size_t(ws.numel()), _stream(dev)))
+
+
+def _loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, clamp, want_grad, reg=None, restrict=None):
+    """The three loss_fwd_bwd* entries: `reg` (fastemit_lambda, delay_penalty) or None, `restrict` (frames, left, right) or None
+    (only with `reg`); each optional group is appended where its entry declares it."""
+    if restrict is not None:
+        B, _, U1, _ = logits.shape
+        restrict = (restrict[0],) + check_restrict(*restrict, B, U1 - 1, logits.device)
+    if reg is not None:
+        reg = check_reg(*reg)
+    dev = _check_logits_inputs(logits, targets, logit_lens, target_lens)
     with torch.cuda.device(dev):
-        costs = torch.empty(B, dtype=torch.float32, device=dev)
+        costs = torch.empty(logits.shape[0], dtype=torch.float32, device=dev)
         grad = torch.empty_like(logits) if want_grad else None
-        n = ctypes.c_size_t(0)
-        _check(lib().rnnt_engine_loss_workspace_bytes(B, T, U1, V, DTYPE_F32, ctypes.byref(n)))
-        ws = workspace(dev, n.value)
-        head = (_p(logits), _p(targets), _p(logit_lens), _p(target_lens), B, T, U1, V, int(blank), ctypes.c_float(clamp))
-        tail = (DTYPE_F32, _p(costs), _p(grad), _p(ws), ctypes.c_size_t(ws.numel()), _stream(dev))
+        suffix, mid = "", [ctypes.c_float(clamp)]
+        if reg is not None:
+            suffix = "_reg"
+            mid += [ctypes.c_float(reg[0]), ctypes.c_float(reg[1])]
         if restrict is not None:
-            _check(lib().rnnt_engine_loss_fwd_bwd_restrict(*head, ctypes.c_float(reg[0]), ctypes.c_float(reg[1]),
-                                                           _p(_nonempty(restrict[0])), restrict[1], restrict[2], *tail))
-        elif reg is None:
-            _check(lib().rnnt_engine_loss_fwd_bwd(*head, *tail))
-        else:
-            _check(lib().rnnt_engine_loss_fwd_bwd_reg(*head, ctypes.c_float(reg[0]), ctypes.c_float(reg[1]), *tail))
+            suffix = "_restrict"
+            frames = _nonempty(restrict[0])
+            mid += [_p(frames), restrict[1], restrict[2]]
+        _call_on_logits("rnnt_engine_loss_fwd_bwd" + suffix, logits, targets, logit_lens, target_lens, blank, mid + [DTYPE_F32],
+                        (costs, grad))
     return costs, grad
-
-
-def _fused_args(enc, pred, W, bias, targets, logit_lens, target_lens, blank, grad_scale, outs, ws,
-                dtype=DTYPE_F32):
-    B, T, H = enc.shape
-    U1 = pred.shape[1]
-    V = W.shape[0]
-    costs, ge, gp, gW, gb = outs
-    return (_p(enc), _strides3(enc), _p(pred), _p(W), _p(bias), _p(targets), _p(logit_lens),
-            _p(target_lens), B, T, U1, H, V, int(blank), ctypes.c_float(-1.0),
-            ctypes.c_float(grad_scale), dtype, _p(costs), _p(ge), _p(gp), _p(gW), _p(gb),
-            _p(ws), ctypes.c_size_t(ws.numel()), _stream(enc.device))
 
 
 def alloc_fused_outputs(enc, pred, W):
@@ -523,21 +529,36 @@ def _check_fused_inputs(enc, pred, W, bias, targets, logit_lens, target_lens):
     return dev
 
 
-def joint_loss_fwd_bwd(enc, pred, W, bias, targets, logit_lens, target_lens, blank, grad_scale,
-                       outs=None, stage=None, *, dtype, stage_mask=None, variant=0):
-    """Fused joint + transducer loss forward AND backward (one C-ABI call).  `dtype` is REQUIRED (no default: a caller
-    that forgets it must not silently run a route other than the one it means; DEFAULT_DTYPE is what the product ships).
-    Returns (costs[B], grad_enc, grad_pred, grad_W, grad_bias); gradients are those of
-    grad_scale * sum_b costs[b].  `stage` (0..7) runs a single pipeline stage (bench aid);
-    `stage_mask` / `variant` run any subset of stages with per-call kernel variants (VARIANT_*).
-    `dtype` "bf16": the three GEMMs take bf16-rounded operands (tensors stay fp32)."""
+def _frames_out(B, U1, dev):
+    """frames [B, U1-1] int32 and the buffer behind it (never empty: U1 == 1 still hands the ABI a valid pointer)."""
+    buf = torch.empty(max(B * (U1 - 1), 1), dtype=torch.int32, device=dev)
+    return buf[:B * (U1 - 1)].view(B, U1 - 1), buf
+
+
+def _fused(enc, pred, W, bias, targets, logit_lens, target_lens, blank, dtype, grad_scale=None, reg=None, restrict=None,
+           outs=None, stage=None, stage_mask=None, variant=0, align=False):
+    """Every fused entry (rnnt_engine_joint_loss_fwd*, rnnt_engine_run_stage[s], rnnt_engine_joint_align): validation, outputs,
+    workspace and the argument list, once.  `grad_scale` None: costs only (the forward kernels); `reg` (fastemit_lambda,
+    delay_penalty) or None — a costs-only entry takes the delay penalty alone, FastEmit changes no cost; `restrict` (frames, left,
+    right) or None (only with `reg`); `stage` / `stage_mask` / `variant` as joint_loss_fwd_bwd's; `align`: the best path instead of
+    the loss.  Each optional group is appended where its entry declares it.  Returns the tuple of output tensors."""
+    if reg is not None:
+        reg = check_reg(*reg)
     dev = _check_fused_inputs(enc, pred, W, bias, targets, logit_lens, target_lens)
     B, T, H = enc.shape
     U1 = pred.shape[1]
     V = W.shape[0]
+    if restrict is not None:
+        restrict = (restrict[0],) + check_restrict(*restrict, B, U1 - 1, dev)
     targets = _nonempty(targets)
     with torch.cuda.device(dev):
-        if outs is None:
+        if align:
+            scores = torch.empty(B, dtype=torch.float32, device=dev)
+            frames, fbuf = _frames_out(B, U1, dev)
+            outs = (scores, fbuf)
+        elif grad_scale is None:
+            outs = (torch.empty(B, dtype=torch.float32, device=dev),)
+        elif outs is None:
             outs = alloc_fused_outputs(enc, pred, W)
         else:
             _require_cuda(enc, *outs)
@@ -548,38 +569,47 @@ def joint_loss_fwd_bwd(enc, pred, W, bias, targets, logit_lens, target_lens, bla
         if variant & (VARIANT_X3_FP32_FWD | VARIANT_X3_FP32_DH):
             need += layout(B, T, U1, H, V, code).aux_bytes  # fp32 hidden + W pack of the substituted stages
         ws = workspace(dev, need)
-        args = _fused_args(enc, pred, W, bias, targets, logit_lens, target_lens, blank, grad_scale,
-                           outs, ws, code)
-        if stage_mask is not None or variant:
-            mask = STAGES_ALL if stage_mask is None else int(stage_mask)
-            _check(lib().rnnt_engine_run_stages(mask, int(variant), *args))
-        elif stage is None:
-            _check(lib().rnnt_engine_joint_loss_fwd_bwd(*args))
+        args = []
+        if align:
+            entry = "rnnt_engine_joint_align"
+        elif stage_mask is not None or variant:
+            entry, args = "rnnt_engine_run_stages", [STAGES_ALL if stage_mask is None else int(stage_mask), int(variant)]
+        elif stage is not None:
+            entry, args = "rnnt_engine_run_stage", [int(stage)]
         else:
-            _check(lib().rnnt_engine_run_stage(int(stage), *args))
-    return outs
+            entry = ("rnnt_engine_joint_loss_fwd" + ("_bwd" if grad_scale is not None else "")
+                     + ("_restrict" if restrict is not None else "_reg" if reg is not None else ""))
+        args += [_p(enc), _strides3(enc), _p(pred), _p(W), _p(bias), _p(targets), _p(logit_lens), _p(target_lens),
+                 B, T, U1, H, V, int(blank)]
+        if grad_scale is not None:
+            args += [ctypes.c_float(-1.0), ctypes.c_float(grad_scale)]  # (clamp: none on the fused path)
+        if reg is not None:
+            args += [ctypes.c_float(f) for f in (reg if grad_scale is not None else reg[1:])]
+        if restrict is not None:
+            window = _nonempty(restrict[0])
+            args += [_p(window), restrict[1], restrict[2]]
+        _check(getattr(lib(), entry)(*args, code, *[_p(o) for o in outs], _p(ws), ctypes.c_size_t(ws.numel()), _stream(dev)))
+    return (outs[0], frames) if align else outs
+
+
+def joint_loss_fwd_bwd(enc, pred, W, bias, targets, logit_lens, target_lens, blank, grad_scale,
+                       outs=None, stage=None, *, dtype, stage_mask=None, variant=0):
+    """Fused joint + transducer loss forward AND backward (one C-ABI call).  `dtype` is REQUIRED (no default: a caller
+    that forgets it must not silently run a route other than the one it means; DEFAULT_DTYPE is what the product ships).
+    Returns (costs[B], grad_enc, grad_pred, grad_W, grad_bias); gradients are those of
+    grad_scale * sum_b costs[b].  `stage` (0..7) runs a single pipeline stage (bench aid);
+    `stage_mask` / `variant` run any subset of stages with per-call kernel variants (VARIANT_*).
+    `dtype` "bf16": the three GEMMs take bf16-rounded operands (tensors stay fp32)."""
+    return _fused(enc, pred, W, bias, targets, logit_lens, target_lens, blank, dtype, grad_scale, outs=outs, stage=stage,
+                  stage_mask=stage_mask, variant=variant)
 
 
 def joint_loss_fwd_bwd_reg(enc, pred, W, bias, targets, logit_lens, target_lens, blank, grad_scale, fastemit_lambda,
                            delay_penalty, outs=None, *, dtype):
     """joint_loss_fwd_bwd with FastEmit and the delay penalty (C ABI rnnt_engine_joint_loss_fwd_bwd_reg):
     costs are the penalised -log P' (lambda does not change them), gradients those of grad_scale * the regularised loss."""
-    fe, dp = check_reg(fastemit_lambda, delay_penalty)
-    dev = _check_fused_inputs(enc, pred, W, bias, targets, logit_lens, target_lens)
-    targets = _nonempty(targets)
-    with torch.cuda.device(dev):
-        if outs is None:
-            outs = alloc_fused_outputs(enc, pred, W)
-        else:
-            _require_cuda(enc, *outs)
-            _require_dtype(torch.float32, **{f"outs[{i}]": o for i, o in enumerate(outs)})
-            _require_contiguous(**{f"outs[{i}]": o for i, o in enumerate(outs)})
-        code = dtype_code(dtype)
-        B, T, H = enc.shape
-        ws = workspace(dev, workspace_bytes(B, T, pred.shape[1], H, W.shape[0], code))
-        a = _fused_args(enc, pred, W, bias, targets, logit_lens, target_lens, blank, grad_scale, outs, ws, code)
-        _check(lib().rnnt_engine_joint_loss_fwd_bwd_reg(*a[:15], a[15], ctypes.c_float(fe), ctypes.c_float(dp), *a[16:]))
-    return outs
+    return _fused(enc, pred, W, bias, targets, logit_lens, target_lens, blank, dtype, grad_scale, (fastemit_lambda, delay_penalty),
+                  outs=outs)
 
 
 def joint_loss_fwd_bwd_restrict(enc, pred, W, bias, targets, logit_lens, target_lens, blank, grad_scale, fastemit_lambda,
@@ -587,131 +617,46 @@ def joint_loss_fwd_bwd_restrict(enc, pred, W, bias, targets, logit_lens, target_
     """joint_loss_fwd_bwd_reg on the restricted lattice (C ABI rnnt_engine_joint_loss_fwd_bwd_restrict): label u
     of utterance b is emitted only at frames restrict_frames[b,u] - restrict_left .. restrict_frames[b,u] + restrict_right.  An
     utterance without a surviving path has cost +inf and zero gradient contributions."""
-    fe, dp = check_reg(fastemit_lambda, delay_penalty)
-    dev = _check_fused_inputs(enc, pred, W, bias, targets, logit_lens, target_lens)
-    left, right = check_restrict(restrict_frames, restrict_left, restrict_right, enc.shape[0], pred.shape[1] - 1, dev)
-    targets = _nonempty(targets)
-    with torch.cuda.device(dev):
-        if outs is None:
-            outs = alloc_fused_outputs(enc, pred, W)
-        else:
-            _require_cuda(enc, *outs)
-            _require_dtype(torch.float32, **{f"outs[{i}]": o for i, o in enumerate(outs)})
-            _require_contiguous(**{f"outs[{i}]": o for i, o in enumerate(outs)})
-        code = dtype_code(dtype)
-        B, T, H = enc.shape
-        ws = workspace(dev, workspace_bytes(B, T, pred.shape[1], H, W.shape[0], code))
-        a = _fused_args(enc, pred, W, bias, targets, logit_lens, target_lens, blank, grad_scale, outs, ws, code)
-        _check(lib().rnnt_engine_joint_loss_fwd_bwd_restrict(*a[:15], a[15], ctypes.c_float(fe), ctypes.c_float(dp),
-                                                             _p(_nonempty(restrict_frames)), left, right, *a[16:]))
-    return outs
+    return _fused(enc, pred, W, bias, targets, logit_lens, target_lens, blank, dtype, grad_scale, (fastemit_lambda, delay_penalty),
+                  (restrict_frames, restrict_left, restrict_right), outs=outs)
 
 
 def joint_loss_fwd_restrict(enc, pred, W, bias, targets, logit_lens, target_lens, blank, delay_penalty, restrict_frames,
                             restrict_left, restrict_right, *, dtype):
     """joint_loss_fwd_reg on the restricted lattice (C ABI rnnt_engine_joint_loss_fwd_restrict): costs only, forward kernels only."""
-    _, dp = check_reg(0.0, delay_penalty)
-    dev = _check_fused_inputs(enc, pred, W, bias, targets, logit_lens, target_lens)
-    B, T, H = enc.shape
-    U1 = pred.shape[1]
-    V = W.shape[0]
-    left, right = check_restrict(restrict_frames, restrict_left, restrict_right, B, U1 - 1, dev)
-    targets = _nonempty(targets)
-    code = dtype_code(dtype)
-    with torch.cuda.device(dev):
-        costs = torch.empty(B, dtype=torch.float32, device=dev)
-        ws = workspace(dev, workspace_bytes(B, T, U1, H, V, code))
-        _check(lib().rnnt_engine_joint_loss_fwd_restrict(
-            _p(enc), _strides3(enc), _p(pred), _p(W), _p(bias), _p(targets), _p(logit_lens),
-            _p(target_lens), B, T, U1, H, V, int(blank), ctypes.c_float(dp), _p(_nonempty(restrict_frames)), left, right,
-            code, _p(costs), _p(ws), ctypes.c_size_t(ws.numel()), _stream(dev)))
-    return costs
+    return _fused(enc, pred, W, bias, targets, logit_lens, target_lens, blank, dtype, None, (0.0, delay_penalty),
+                  (restrict_frames, restrict_left, restrict_right))[0]
 
 
 def joint_loss_fwd_reg(enc, pred, W, bias, targets, logit_lens, target_lens, blank, delay_penalty, *, dtype):
     """joint_loss_fwd with the delay penalty (C ABI rnnt_engine_joint_loss_fwd_reg): the penalised costs, forward kernels
     only (FastEmit changes no cost)."""
-    _, dp = check_reg(0.0, delay_penalty)
-    dev = _check_fused_inputs(enc, pred, W, bias, targets, logit_lens, target_lens)
-    B, T, H = enc.shape
-    U1 = pred.shape[1]
-    V = W.shape[0]
-    targets = _nonempty(targets)
-    code = dtype_code(dtype)
-    with torch.cuda.device(dev):
-        costs = torch.empty(B, dtype=torch.float32, device=dev)
-        ws = workspace(dev, workspace_bytes(B, T, U1, H, V, code))
-        _check(lib().rnnt_engine_joint_loss_fwd_reg(
-            _p(enc), _strides3(enc), _p(pred), _p(W), _p(bias), _p(targets), _p(logit_lens),
-            _p(target_lens), B, T, U1, H, V, int(blank), ctypes.c_float(dp), code, _p(costs), _p(ws),
-            ctypes.c_size_t(ws.numel()), _stream(dev)))
-    return costs
+    return _fused(enc, pred, W, bias, targets, logit_lens, target_lens, blank, dtype, None, (0.0, delay_penalty))[0]
 
 
 def joint_loss_fwd(enc, pred, W, bias, targets, logit_lens, target_lens, blank, *, dtype):
     """Costs only (C ABI rnnt_engine_joint_loss_fwd): the fused path's forward — joint GEMM with
     the log-softmax in its epilogue, lattice sweep — and none of the backward kernels or gradient
     buffers.  What RNNTModel.forward costs under torch.no_grad()."""
-    dev = _check_fused_inputs(enc, pred, W, bias, targets, logit_lens, target_lens)
-    B, T, H = enc.shape
-    U1 = pred.shape[1]
-    V = W.shape[0]
-    targets = _nonempty(targets)
-    code = dtype_code(dtype)
-    with torch.cuda.device(dev):
-        costs = torch.empty(B, dtype=torch.float32, device=dev)
-        ws = workspace(dev, workspace_bytes(B, T, U1, H, V, code))
-        _check(lib().rnnt_engine_joint_loss_fwd(
-            _p(enc), _strides3(enc), _p(pred), _p(W), _p(bias), _p(targets), _p(logit_lens),
-            _p(target_lens), B, T, U1, H, V, int(blank), code, _p(costs), _p(ws),
-            ctypes.c_size_t(ws.numel()), _stream(dev)))
-    return costs
-
-
-def _frames_out(B, U1, dev):
-    """frames [B, U1-1] int32 and the buffer behind it (never empty: U1 == 1 still hands the ABI a valid pointer)."""
-    buf = torch.empty(max(B * (U1 - 1), 1), dtype=torch.int32, device=dev)
-    return buf[:B * (U1 - 1)].view(B, U1 - 1), buf
+    return _fused(enc, pred, W, bias, targets, logit_lens, target_lens, blank, dtype)[0]
 
 
 def align(logits, targets, logit_lens, target_lens, blank):
     """Best alignment on materialised logits [B,T,U1,V] (C ABI rnnt_engine_align): (scores [B] fp32, frames [B,U1-1] int32).
     Workspace: the loss entry's (loss_fwd_bwd's buffer serves both)."""
-    dev = _require_cuda(logits, targets, logit_lens, target_lens)
-    _require_dtype(torch.float32, logits=logits)
-    _require_dtype(torch.int32, targets=targets, logit_lens=logit_lens, target_lens=target_lens)
-    _require_contiguous(logits=logits, targets=targets, logit_lens=logit_lens, target_lens=target_lens)
-    B, T, U1, V = logits.shape
-    targets = _nonempty(targets)
+    dev = _check_logits_inputs(logits, targets, logit_lens, target_lens)
+    B, _, U1, _ = logits.shape
     with torch.cuda.device(dev):
         scores = torch.empty(B, dtype=torch.float32, device=dev)
         frames, fbuf = _frames_out(B, U1, dev)
-        n = ctypes.c_size_t(0)
-        _check(lib().rnnt_engine_loss_workspace_bytes(B, T, U1, V, DTYPE_F32, ctypes.byref(n)))
-        ws = workspace(dev, n.value)
-        _check(lib().rnnt_engine_align(_p(logits), _p(targets), _p(logit_lens), _p(target_lens), B, T, U1, V, int(blank),
-                                       _p(scores), _p(fbuf), _p(ws), ctypes.c_size_t(ws.numel()), _stream(dev)))
+        _call_on_logits("rnnt_engine_align", logits, targets, logit_lens, target_lens, blank, [], (scores, fbuf))
     return scores, frames
 
 
 def joint_align(enc, pred, W, bias, targets, logit_lens, target_lens, blank, *, dtype):
     """Fused joint + best alignment (C ABI rnnt_engine_joint_align): the joint-forward GEMM of the loss, then the Viterbi sweep
     and the backtrace.  (scores [B] fp32, frames [B,U1-1] int32); workspace: the fused loss entry's."""
-    dev = _check_fused_inputs(enc, pred, W, bias, targets, logit_lens, target_lens)
-    B, T, H = enc.shape
-    U1 = pred.shape[1]
-    V = W.shape[0]
-    targets = _nonempty(targets)
-    code = dtype_code(dtype)
-    with torch.cuda.device(dev):
-        scores = torch.empty(B, dtype=torch.float32, device=dev)
-        frames, fbuf = _frames_out(B, U1, dev)
-        ws = workspace(dev, workspace_bytes(B, T, U1, H, V, code))
-        _check(lib().rnnt_engine_joint_align(
-            _p(enc), _strides3(enc), _p(pred), _p(W), _p(bias), _p(targets), _p(logit_lens),
-            _p(target_lens), B, T, U1, H, V, int(blank), code, _p(scores), _p(fbuf), _p(ws),
-            ctypes.c_size_t(ws.numel()), _stream(dev)))
-    return scores, frames
+    return _fused(enc, pred, W, bias, targets, logit_lens, target_lens, blank, dtype, align=True)
 
 
 def _rows(x):
@@ -842,25 +787,89 @@ class _PredParams(ctypes.Structure):  # include/rnnt_engine.h: rnnt_conv_predict
         "linear_b", "ln_out_w", "ln_out_b")]
 
 
-def _decode_inputs(frames, pred_params, text_W, text_b, W, bias):
-    params = [t.contiguous() for t in pred_params]
-    dev = _require_cuda(frames, W, bias, *params)
-    _require_dtype(torch.float32, frames=frames, W=W, bias=bias, **{f"param{i}": t for i, t in enumerate(params)})
-    if frames.dim() != 2 or frames.stride(1) != 1:
-        frames = frames.contiguous()
-    W, bias = W.contiguous(), bias.contiguous()
-    if text_W is not None:
-        _require_cuda(text_W, text_b)
-        _require_dtype(torch.float32, text_W=text_W, text_b=text_b)
-        text_W, text_b = text_W.contiguous(), text_b.contiguous()
-    return dev, frames, params, text_W, text_b, W, bias
+class _DecodeModel:
+    """What every decode entry is told about the model, checked once: the tensors (fp32, contiguous, on one HIP device; `frames` [n,H]
+    with unit column stride), the sizes, the predictor's struct and the run of arguments the C entries share.  greedy_decode_tables
+    has no frames and no joint: it passes `H` instead."""
+
+    def __init__(self, frames, pred_params, ln_eps, text_W, text_b, W=None, bias=None, H=None):
+        params = [t.contiguous() for t in pred_params]
+        self.dev = _require_cuda(*[t for t in (frames, W, bias) if t is not None], *params)
+        _require_dtype(torch.float32, frames=frames, W=W, bias=bias, **{f"param{i}": t for i, t in enumerate(params)})
+        if frames is not None and (frames.dim() != 2 or frames.stride(1) != 1):
+            frames = frames.contiguous()
+        if W is not None:
+            W, bias = W.contiguous(), bias.contiguous()
+        if text_W is not None:
+            _require_cuda(text_W, text_b)
+            _require_dtype(torch.float32, text_W=text_W, text_b=text_b)
+            text_W, text_b = text_W.contiguous(), text_b.contiguous()
+        self.frames, self.params, self.text_W, self.text_b, self.W, self.bias = frames, params, text_W, text_b, W, bias
+        self.S, self.E = params[0].shape
+        self.O = params[7].shape[0]
+        self.H = int(H) if frames is None else frames.shape[1]
+        self.V = None if W is None else W.shape[0]
+        self.has_text = 1 if text_W is not None else 0
+        self.sizes = (self.S, self.E, self.O, self.H, self.V, self.has_text)  # as the *_workspace_bytes queries take them
+        self.eps = _eps_pair(ln_eps)
+        self.struct = _PredParams(*[t.data_ptr() for t in params])
+        self.keep = (frames, params, W, bias, text_W, text_b)  # what a launch reads: alive until the caller has synchronised
+
+    def args(self, blank, max_length, max_per_frame):
+        """predictor struct, S, E, O, the two eps, text_ln, joint_ln, H, V, blank, max_length, max_per_frame: in every decode entry."""
+        return (ctypes.byref(self.struct), self.S, self.E, self.O, ctypes.c_float(self.eps[0]), ctypes.c_float(self.eps[1]),
+                _p(self.text_W), _p(self.text_b), _p(self.W), _p(self.bias), self.H, self.V, int(blank), int(max_length),
+                int(max_per_frame))
+
+
+def _supported(entry, *ints):
+    """Whether the size query `entry` takes these sizes: the C ABI's own answer, no device work."""
+    n = ctypes.c_size_t(0)
+    return getattr(lib(), entry)(*[int(v) for v in ints], ctypes.byref(n)) == 0
+
+
+def _enqueue_rounds(launch, bound, chunk, in_flight=None, wait_at_limit=False):
+    """The decode loops' enqueueing: `launch(it, first, flag)` enqueues `it` <= `chunk` rounds (`first`: 1 on the first call) until the
+    device has raised the end flag in a pinned host word (polled, never waited for) or `bound` rounds are enqueued.  `in_flight` None:
+    no events; else the host waits for the oldest chunk's completion event once more than `in_flight` chunks are ahead of the device —
+    with `wait_at_limit`, once `in_flight` are.  The wait comes before the flag is read again, so a short push ends after the chunk that
+    served it.  Returns the flag's tensor (to be kept alive until the caller has synchronised)."""
+    flag = torch.zeros(1, dtype=torch.int32).pin_memory()
+    flag_p = ctypes.c_void_p(flag.data_ptr())
+    limit = None if in_flight is None else max(1, int(in_flight)) + (0 if wait_at_limit else 1)
+    pending = []
+    done = 0
+    while done < bound and (done == 0 or int(flag[0]) == 0):
+        it = min(chunk, bound - done)
+        launch(it, 1 if done == 0 else 0, flag_p)
+        done += it
+        if limit is not None:
+            ev = torch.cuda.Event()
+            ev.record()
+            pending.append(ev)
+            if len(pending) >= limit:
+                pending.pop(0).synchronize()
+    return flag
+
+
+def _pack_rows(frames_list, counts):
+    """The entries with frames packed into one [rows, H] tensor, and [(first row, count)] of every entry (None / count 0 included)."""
+    live = [f for f, k in zip(frames_list, counts) if k > 0]
+    table, at = [], 0
+    for k in counts:
+        table.append((at, k))
+        at += k
+    return (live[0] if len(live) == 1 else torch.cat(live, 0)), table
+
+
+def _rows_table(table, dev):
+    """_pack_rows' table on the device: the call's one small host-to-device copy."""
+    return torch.tensor(table, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
 
 
 def greedy_decode_persistent_supported(T, S, E, O, H, V, has_text):
     """Whether rnnt_engine_greedy_decode_persistent takes these sizes (else: greedy_decode_loop's kernel-per-layer chain)."""
-    n = ctypes.c_size_t(0)
-    return lib().rnnt_engine_greedy_decode_persistent_workspace_bytes(int(T), int(S), int(E), int(O), int(H), int(V), int(bool(has_text)),
-                                                                      ctypes.byref(n)) == 0
+    return _supported("rnnt_engine_greedy_decode_persistent_workspace_bytes", T, S, E, O, H, V, bool(has_text))
 
 
 def greedy_decode_tables(pred_params, ln_eps, text_W, text_b, H):
@@ -868,23 +877,14 @@ def greedy_decode_tables(pred_params, ln_eps, text_W, text_b, H):
     three tap tables over the symbols, joint.text_ln folded into the predictor's linear layer — a function of the parameters only.  Returns a
     device buffer to pass as `tables=` to greedy_decode_persistent for every utterance decoded with THESE parameter values (build again after
     the weights change); enqueued on the current stream, no synchronisation."""
-    params = [t.contiguous() for t in pred_params]
-    dev = _require_cuda(*params)
-    _require_dtype(torch.float32, **{f"param{i}": t for i, t in enumerate(params)})
-    if text_W is not None:
-        _require_cuda(text_W, text_b)
-        _require_dtype(torch.float32, text_W=text_W, text_b=text_b)
-        text_W, text_b = text_W.contiguous(), text_b.contiguous()
-    S, E = params[0].shape
-    O = params[7].shape[0]
-    with torch.cuda.device(dev):
+    m = _DecodeModel(None, pred_params, ln_eps, text_W, text_b, H=H)
+    with torch.cuda.device(m.dev):
         n = ctypes.c_size_t(0)
-        _check(lib().rnnt_engine_greedy_decode_tables_bytes(S, E, O, int(H), 1 if text_W is not None else 0, ctypes.byref(n)))
-        tables = torch.empty(n.value, dtype=torch.uint8, device=dev)
-        st = _PredParams(*[t.data_ptr() for t in params])
-        _check(lib().rnnt_engine_greedy_decode_build_tables(ctypes.byref(st), S, E, O, ctypes.c_float(_eps_pair(ln_eps)[0]), _p(text_W), _p(text_b), int(H),
-                                                            _p(tables), ctypes.c_size_t(n.value), _stream(dev)))
-        tables._keepalive = (params, text_W, text_b)
+        _check(lib().rnnt_engine_greedy_decode_tables_bytes(m.S, m.E, m.O, m.H, m.has_text, ctypes.byref(n)))
+        tables = torch.empty(n.value, dtype=torch.uint8, device=m.dev)
+        _check(lib().rnnt_engine_greedy_decode_build_tables(ctypes.byref(m.struct), m.S, m.E, m.O, ctypes.c_float(m.eps[0]), _p(m.text_W),
+                                                            _p(m.text_b), m.H, _p(tables), ctypes.c_size_t(n.value), _stream(m.dev)))
+        tables._keepalive = (m.params, m.text_W, m.text_b)
     return tables
 
 
@@ -894,23 +894,18 @@ def greedy_decode_persistent(frames, pred_params, ln_eps, text_W, text_b, W, bia
     tokens int32[max_length]) device tensors WITHOUT synchronising: after one synchronisation tokens[1 : 1 + state[2]] are the
     decoded ids; state[7] != 0 means the loop gave up on a hand-off (check_decode_state raises).  `tables`: greedy_decode_tables(...) of
     the same parameters (else they are rebuilt inside this call, ~0.13 ms)."""
-    dev, frames, params, text_W, text_b, W, bias = _decode_inputs(frames, pred_params, text_W, text_b, W, bias)
-    T, H = frames.shape
-    V = W.shape[0]
-    S, E = params[0].shape
-    O = params[7].shape[0]
-    with torch.cuda.device(dev):
+    m = _DecodeModel(frames, pred_params, ln_eps, text_W, text_b, W, bias)
+    T = m.frames.shape[0]
+    with torch.cuda.device(m.dev):
         n = ctypes.c_size_t(0)
-        _check(lib().rnnt_engine_greedy_decode_persistent_workspace_bytes(T, S, E, O, H, V, 1 if text_W is not None else 0, ctypes.byref(n)))
-        ws = workspace(dev, n.value)
-        both = torch.empty(8 + int(max_length), dtype=torch.int32, device=dev)  # state | tokens: ONE device-to-host copy reads the whole result
+        _check(lib().rnnt_engine_greedy_decode_persistent_workspace_bytes(T, *m.sizes, ctypes.byref(n)))
+        ws = workspace(m.dev, n.value)
+        both = torch.empty(8 + int(max_length), dtype=torch.int32, device=m.dev)  # state | tokens: ONE device-to-host copy reads the whole result
         state, tokens = both[:8], both[8:]
-        st = _PredParams(*[t.data_ptr() for t in params])
         _check(lib().rnnt_engine_greedy_decode_persistent(
-            _p(frames), ctypes.c_int64(frames.stride(0)), T, ctypes.byref(st), S, E, O, ctypes.c_float(_eps_pair(ln_eps)[0]), ctypes.c_float(_eps_pair(ln_eps)[1]),
-            _p(text_W), _p(text_b), _p(W), _p(bias), H, V, int(blank), int(max_length), int(max_per_frame),
-            _p(tables), None, _p(state), _p(tokens), _p(ws), ctypes.c_size_t(ws.numel()), _stream(dev)))
-        state._keepalive = (frames, params, W, bias, text_W, text_b, tables)  # until the caller has synchronised
+            _p(m.frames), ctypes.c_int64(m.frames.stride(0)), T, *m.args(blank, max_length, max_per_frame),
+            _p(tables), None, _p(state), _p(tokens), _p(ws), ctypes.c_size_t(ws.numel()), _stream(m.dev)))
+        state._keepalive = (*m.keep, tables)  # until the caller has synchronised
         state._with_tokens = both
     return state, tokens
 
@@ -939,32 +934,21 @@ def greedy_decode_loop(frames, pred_params, ln_eps, text_W, text_b, W, bias, bla
     end-of-loop flag in a pinned host word (polled, never waited for) or the loop's upper bound is reached.
     Returns (state int32[8], tokens int32[max_length]) device tensors WITHOUT synchronising: after one
     synchronisation tokens[1 : 1 + state[2]] are the decoded ids."""
-    dev, frames, params, text_W, text_b, W, bias = _decode_inputs(frames, pred_params, text_W, text_b, W, bias)
-    T, H = frames.shape
-    V = W.shape[0]
-    S, E = params[0].shape
-    O = params[7].shape[0]
+    m = _DecodeModel(frames, pred_params, ln_eps, text_W, text_b, W, bias)
+    T = m.frames.shape[0]
     scan_frames, chunk = int(scan_frames), max(1, int(chunk))
     bound = int(max_length) + (T + scan_frames - 1) // scan_frames + 1
-    with torch.cuda.device(dev):
+    with torch.cuda.device(m.dev):
         n = ctypes.c_size_t(0)
-        _check(lib().rnnt_engine_greedy_decode_workspace_bytes(H, V, E, O, scan_frames, ctypes.byref(n)))
-        ws = workspace(dev, n.value)
-        state = torch.empty(8, dtype=torch.int32, device=dev)
-        tokens = torch.empty(int(max_length), dtype=torch.int32, device=dev)
-        flag = torch.zeros(1, dtype=torch.int32).pin_memory()
-        st = _PredParams(*[t.data_ptr() for t in params])
-        stream = _stream(dev)
-        done = 0
-        while done < bound and (done == 0 or int(flag[0]) == 0):
-            it = min(chunk, bound - done)
-            _check(lib().rnnt_engine_greedy_decode(
-                _p(frames), ctypes.c_int64(frames.stride(0)), T, ctypes.byref(st), S, E, O, ctypes.c_float(_eps_pair(ln_eps)[0]), ctypes.c_float(_eps_pair(ln_eps)[1]),
-                _p(text_W), _p(text_b), _p(W), _p(bias), H, V, int(blank), int(max_length), int(max_per_frame),
-                scan_frames, it, 1 if done == 0 else 0, ctypes.c_void_p(flag.data_ptr()), _p(state), _p(tokens), _p(ws),
-                ctypes.c_size_t(ws.numel()), stream))
-            done += it
-        state._keepalive = (flag, frames, params, W, bias, text_W, text_b)  # until the caller has synchronised
+        _check(lib().rnnt_engine_greedy_decode_workspace_bytes(m.H, m.V, m.E, m.O, scan_frames, ctypes.byref(n)))
+        ws = workspace(m.dev, n.value)
+        state = torch.empty(8, dtype=torch.int32, device=m.dev)
+        tokens = torch.empty(int(max_length), dtype=torch.int32, device=m.dev)
+        head = (_p(m.frames), ctypes.c_int64(m.frames.stride(0)), T, *m.args(blank, max_length, max_per_frame), scan_frames)
+        tail = (_p(state), _p(tokens), _p(ws), ctypes.c_size_t(ws.numel()), _stream(m.dev))
+        flag = _enqueue_rounds(lambda it, first, flag: _check(lib().rnnt_engine_greedy_decode(*head, it, first, flag, *tail)),
+                               bound, chunk)
+        state._keepalive = (flag, *m.keep)  # until the caller has synchronised
     return state, tokens
 
 
@@ -987,9 +971,8 @@ def greedy_stream_init(state, blank):
 def greedy_stream_supported(n, S, E, O, H, V, has_text, max_length, max_per_frame):
     """Whether a push of n frames can take the persistent launch (rnnt_engine_greedy_stream_decode with persistent = 1); no device work.
     max_length 0 or None: unbounded."""
-    q = ctypes.c_size_t(0)
-    return lib().rnnt_engine_greedy_stream_decode_workspace_bytes(int(n), int(S), int(E), int(O), int(H), int(V), int(bool(has_text)),
-                                                                  int(max_length or 0), int(max_per_frame), 1, ctypes.byref(q)) == 0
+    return _supported("rnnt_engine_greedy_stream_decode_workspace_bytes", n, S, E, O, H, V, bool(has_text), max_length or 0,
+                      max_per_frame, 1)
 
 
 def greedy_stream_decode(frames, pred_params, ln_eps, text_W, text_b, W, bias, blank, max_length, max_per_frame, tables, persistent,
@@ -999,30 +982,23 @@ def greedy_stream_decode(frames, pred_params, ln_eps, text_W, text_b, W, bias, b
     max_length leaves fewer); max_length 0 / None = unbounded.  No synchronisation: afterwards state[STREAM_STATUS] == 0 means the push
     decoded and out_tokens[:state[STREAM_PUSH_LABELS]] are its labels; non-zero (persistent only) means nothing changed — redo the push
     with persistent=False."""
-    dev, frames, params, text_W, text_b, W, bias = _decode_inputs(frames, pred_params, text_W, text_b, W, bias)
-    _require_cuda(frames, state, out_tokens)
+    m = _DecodeModel(frames, pred_params, ln_eps, text_W, text_b, W, bias)
+    _require_cuda(m.frames, state, out_tokens)
     _require_dtype(torch.int32, state=state, out_tokens=out_tokens)
     _require_contiguous(state=state, out_tokens=out_tokens)
-    n, H = frames.shape
-    V = W.shape[0]
-    S, E = params[0].shape
-    O = params[7].shape[0]
-    ml, m = int(max_length or 0), int(max_per_frame)
-    cap = n * m if ml == 0 else min(n * m, ml - 1)
+    n = m.frames.shape[0]
+    ml, mpf, persistent = int(max_length or 0), int(max_per_frame), 1 if persistent else 0
+    cap = n * mpf if ml == 0 else min(n * mpf, ml - 1)
     if state.numel() < STREAM_STATE_WORDS or out_tokens.numel() < cap:
         raise RuntimeError(f"greedy_stream_decode: state needs {STREAM_STATE_WORDS} words, out_tokens {cap} (got {state.numel()}, {out_tokens.numel()})")
-    with torch.cuda.device(dev):
+    with torch.cuda.device(m.dev):
         q = ctypes.c_size_t(0)
-        _check(lib().rnnt_engine_greedy_stream_decode_workspace_bytes(n, S, E, O, H, V, 1 if text_W is not None else 0, ml, m,
-                                                                      1 if persistent else 0, ctypes.byref(q)))
-        ws = workspace(dev, q.value)
-        st = _PredParams(*[t.data_ptr() for t in params])
-        eps_in, eps_out = _eps_pair(ln_eps)
+        _check(lib().rnnt_engine_greedy_stream_decode_workspace_bytes(n, *m.sizes, ml, mpf, persistent, ctypes.byref(q)))
+        ws = workspace(m.dev, q.value)
         _check(lib().rnnt_engine_greedy_stream_decode(
-            _p(frames) if n > 0 else None, ctypes.c_int64(frames.stride(0)), n, ctypes.byref(st), S, E, O, ctypes.c_float(eps_in),
-            ctypes.c_float(eps_out), _p(text_W), _p(text_b), _p(W), _p(bias), H, V, int(blank), ml, m, _p(tables), 1 if persistent else 0,
-            _p(state), _p(out_tokens), _p(ws), ctypes.c_size_t(ws.numel()), _stream(dev)))
-        state._keepalive = (frames, params, W, bias, text_W, text_b, tables)  # until the caller has synchronised
+            _p(m.frames) if n > 0 else None, ctypes.c_int64(m.frames.stride(0)), n, *m.args(blank, ml, mpf), _p(tables), persistent,
+            _p(state), _p(out_tokens), _p(ws), ctypes.c_size_t(ws.numel()), _stream(m.dev)))
+        state._keepalive = (*m.keep, tables)  # until the caller has synchronised
 
 
 BEAM_MAX = 16  # rnnt_engine_beam_decode: 1 <= beam <= 16 (the slots are the M = 16 rows of every product)
@@ -1050,9 +1026,7 @@ def _beam_context(context, dev):
 
 def beam_decode_supported(S, E, O, H, V, has_text, max_length, beam):
     """Whether rnnt_engine_beam_decode takes these sizes (no device work)."""
-    n = ctypes.c_size_t(0)
-    return lib().rnnt_engine_beam_decode_workspace_bytes(int(S), int(E), int(O), int(H), int(V), int(bool(has_text)), int(max_length),
-                                                         int(beam), ctypes.byref(n)) == 0
+    return _supported("rnnt_engine_beam_decode_workspace_bytes", S, E, O, H, V, bool(has_text), max_length, beam)
 
 
 def beam_decode(frames, pred_params, ln_eps, text_W, text_b, W, bias, blank, max_length, beam, max_per_frame=10, tables=None,
@@ -1065,46 +1039,25 @@ def beam_decode(frames, pred_params, ln_eps, text_W, text_b, W, bias, blank, max
     final synchronisation: afterwards entry j < state[2] is tokens[j, 1 : 1 + state[8 + j]] with log-probability scores[j], best first.
     `context` (ContextGraph.device_tables(device)): the search biased by a phrase list (C ABI rnnt_engine_beam_decode_ctx; DESIGN.md §4h
     "Context") — the scores are then INTERNAL and the order is theirs: the caller finalises (ContextGraph.finalise)."""
-    dev, frames, params, text_W, text_b, W, bias = _decode_inputs(frames, pred_params, text_W, text_b, W, bias)
-    T, H = frames.shape
-    V = W.shape[0]
-    S, E = params[0].shape
-    O = params[7].shape[0]
+    m = _DecodeModel(frames, pred_params, ln_eps, text_W, text_b, W, bias)
+    T = m.frames.shape[0]
     beam, max_length, max_per_frame = int(beam), int(max_length), int(max_per_frame)
-    chunk = max(1, int(chunk))
-    bound = T * max(1, max_per_frame) + 1
-    with torch.cuda.device(dev):
+    with torch.cuda.device(m.dev):
         n = ctypes.c_size_t(0)
-        cx, cx_keep = _beam_context(context, dev)
+        cx, cx_keep = _beam_context(context, m.dev)
+        cx_arg = () if cx is None else (ctypes.byref(cx),)  # the _ctx entries take it before the stream
         query = lib().rnnt_engine_beam_decode_workspace_bytes if cx is None else lib().rnnt_engine_beam_decode_ctx_workspace_bytes
-        _check(query(S, E, O, H, V, 1 if text_W is not None else 0, max_length, beam, ctypes.byref(n)))
-        ws = workspace(dev, n.value)
-        state = torch.empty(32, dtype=torch.int32, device=dev)
-        tokens = torch.empty(beam, max_length, dtype=torch.int32, device=dev)
-        scores = torch.empty(beam, dtype=torch.float64, device=dev)
-        flag = torch.zeros(1, dtype=torch.int32).pin_memory()
-        st = _PredParams(*[t.data_ptr() for t in params])
-        stream = _stream(dev)
-        eps_in, eps_out = _eps_pair(ln_eps)
-        pending = []
-        done = 0
-        while done < bound and (done == 0 or int(flag[0]) == 0):
-            it = min(chunk, bound - done)
-            args = (_p(frames), ctypes.c_int64(frames.stride(0)), T, ctypes.byref(st), S, E, O, ctypes.c_float(eps_in), ctypes.c_float(eps_out),
-                    _p(text_W), _p(text_b), _p(W), _p(bias), H, V, int(blank), max_length, max_per_frame, beam, _p(tables), it,
-                    1 if done == 0 else 0, ctypes.c_void_p(flag.data_ptr()), _p(state), _p(tokens), _p(scores), _p(ws),
-                    ctypes.c_size_t(ws.numel()))
-            if cx is None:
-                _check(lib().rnnt_engine_beam_decode(*args, stream))
-            else:
-                _check(lib().rnnt_engine_beam_decode_ctx(*args, ctypes.byref(cx), stream))
-            done += it
-            ev = torch.cuda.Event()
-            ev.record()
-            pending.append(ev)
-            if len(pending) > max(1, int(in_flight)):
-                pending.pop(0).synchronize()
-        state._keepalive = (flag, frames, params, W, bias, text_W, text_b, tables, cx_keep)  # until the caller has synchronised
+        _check(query(*m.sizes, max_length, beam, ctypes.byref(n)))
+        ws = workspace(m.dev, n.value)
+        state = torch.empty(32, dtype=torch.int32, device=m.dev)
+        tokens = torch.empty(beam, max_length, dtype=torch.int32, device=m.dev)
+        scores = torch.empty(beam, dtype=torch.float64, device=m.dev)
+        fn = lib().rnnt_engine_beam_decode if cx is None else lib().rnnt_engine_beam_decode_ctx
+        head = (_p(m.frames), ctypes.c_int64(m.frames.stride(0)), T, *m.args(blank, max_length, max_per_frame), beam, _p(tables))
+        tail = (_p(state), _p(tokens), _p(scores), _p(ws), ctypes.c_size_t(ws.numel()), *cx_arg, _stream(m.dev))
+        flag = _enqueue_rounds(lambda it, first, flag: _check(fn(*head, it, first, flag, *tail)),
+                               T * max(1, max_per_frame) + 1, max(1, int(chunk)), in_flight)
+        state._keepalive = (flag, *m.keep, tables, cx_keep)  # until the caller has synchronised
     return state, tokens, scores
 
 
@@ -1113,9 +1066,7 @@ BEAM_BATCH_MAX = 64  # rnnt_engine_beam_decode_batch: 1 <= n_utt <= 64
 
 def beam_decode_batch_supported(S, E, O, H, V, has_text, max_length, beam, n_utt):
     """Whether rnnt_engine_beam_decode_batch takes these sizes (no device work)."""
-    n = ctypes.c_size_t(0)
-    return lib().rnnt_engine_beam_decode_batch_workspace_bytes(int(S), int(E), int(O), int(H), int(V), int(bool(has_text)), int(max_length),
-                                                               int(beam), int(n_utt), ctypes.byref(n)) == 0
+    return _supported("rnnt_engine_beam_decode_batch_workspace_bytes", S, E, O, H, V, bool(has_text), max_length, beam, n_utt)
 
 
 def beam_decode_batch(frames_list, pred_params, ln_eps, text_W, text_b, W, bias, blank, max_length, beam, max_per_frame=10, tables=None,
@@ -1133,52 +1084,28 @@ def beam_decode_batch(frames_list, pred_params, ln_eps, text_W, text_b, W, bias,
     lens = [int(f.shape[0]) for f in frames_list]
     if min(lens) < 1:
         raise ValueError("beam_decode_batch: an utterance without frames")
-    packed = frames_list[0] if len(frames_list) == 1 else torch.cat(list(frames_list), 0)
-    dev, packed, params, text_W, text_b, W, bias = _decode_inputs(packed, pred_params, text_W, text_b, W, bias)
-    rows, H = packed.shape
+    packed, table = _pack_rows(frames_list, lens)
+    m = _DecodeModel(packed, pred_params, ln_eps, text_W, text_b, W, bias)
     N = len(lens)
-    V = W.shape[0]
-    S, E = params[0].shape
-    O = params[7].shape[0]
     beam, max_length, max_per_frame = int(beam), int(max_length), int(max_per_frame)
-    chunk = max(1, int(chunk))
-    bound = max(lens) * max(1, max_per_frame) + 1
-    begins = [0]
-    for t in lens[:-1]:
-        begins.append(begins[-1] + t)
-    with torch.cuda.device(dev):
+    with torch.cuda.device(m.dev):
         n = ctypes.c_size_t(0)
-        cx, cx_keep = _beam_context(context, dev)
+        cx, cx_keep = _beam_context(context, m.dev)
+        cx_arg = () if cx is None else (ctypes.byref(cx),)  # the _ctx entries take it before the stream
         query = lib().rnnt_engine_beam_decode_batch_workspace_bytes if cx is None else lib().rnnt_engine_beam_decode_batch_ctx_workspace_bytes
-        _check(query(S, E, O, H, V, 1 if text_W is not None else 0, max_length, beam, N, ctypes.byref(n)))
-        ws = workspace(dev, n.value)
-        utt = torch.tensor(list(zip(begins, lens)), dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-        state = torch.empty(N, 32, dtype=torch.int32, device=dev)
-        tokens = torch.empty(N, beam, max_length, dtype=torch.int32, device=dev)
-        scores = torch.empty(N, beam, dtype=torch.float64, device=dev)
-        flag = torch.zeros(1, dtype=torch.int32).pin_memory()
-        st = _PredParams(*[t.data_ptr() for t in params])
-        stream = _stream(dev)
-        eps_in, eps_out = _eps_pair(ln_eps)
-        pending = []
-        done = 0
-        while done < bound and (done == 0 or int(flag[0]) == 0):
-            it = min(chunk, bound - done)
-            args = (_p(packed), ctypes.c_int64(packed.stride(0)), rows, _p(utt), N, max(lens), ctypes.byref(st), S, E, O, ctypes.c_float(eps_in),
-                    ctypes.c_float(eps_out), _p(text_W), _p(text_b), _p(W), _p(bias), H, V, int(blank), max_length, max_per_frame, beam,
-                    _p(tables), it, 1 if done == 0 else 0, ctypes.c_void_p(flag.data_ptr()), _p(state), _p(tokens), _p(scores), _p(ws),
-                    ctypes.c_size_t(ws.numel()))
-            if cx is None:
-                _check(lib().rnnt_engine_beam_decode_batch(*args, stream))
-            else:
-                _check(lib().rnnt_engine_beam_decode_batch_ctx(*args, ctypes.byref(cx), stream))
-            done += it
-            ev = torch.cuda.Event()
-            ev.record()
-            pending.append(ev)
-            if len(pending) > max(1, int(in_flight)):
-                pending.pop(0).synchronize()
-        state._keepalive = (flag, utt, packed, params, W, bias, text_W, text_b, tables, cx_keep)  # until the caller has synchronised
+        _check(query(*m.sizes, max_length, beam, N, ctypes.byref(n)))
+        ws = workspace(m.dev, n.value)
+        utt = _rows_table(table, m.dev)
+        state = torch.empty(N, 32, dtype=torch.int32, device=m.dev)
+        tokens = torch.empty(N, beam, max_length, dtype=torch.int32, device=m.dev)
+        scores = torch.empty(N, beam, dtype=torch.float64, device=m.dev)
+        fn = lib().rnnt_engine_beam_decode_batch if cx is None else lib().rnnt_engine_beam_decode_batch_ctx
+        head = (_p(m.frames), ctypes.c_int64(m.frames.stride(0)), m.frames.shape[0], _p(utt), N, max(lens),
+                *m.args(blank, max_length, max_per_frame), beam, _p(tables))
+        tail = (_p(state), _p(tokens), _p(scores), _p(ws), ctypes.c_size_t(ws.numel()), *cx_arg, _stream(m.dev))
+        flag = _enqueue_rounds(lambda it, first, flag: _check(fn(*head, it, first, flag, *tail)),
+                               max(lens) * max(1, max_per_frame) + 1, max(1, int(chunk)), in_flight)
+        state._keepalive = (flag, utt, *m.keep, tables, cx_keep)  # until the caller has synchronised
     return state, tokens, scores
 
 
@@ -1197,9 +1124,7 @@ def beam_stream_bytes(S, E, O, H, V, has_text, max_length, beam, n_streams):
 
 def beam_stream_supported(S, E, O, H, V, has_text, max_length, beam, n_streams=1):
     """Whether rnnt_engine_beam_stream_push takes these sizes (no device work)."""
-    n = ctypes.c_size_t(0)
-    return lib().rnnt_engine_beam_stream_bytes(int(S), int(E), int(O), int(H), int(V), int(bool(has_text)), int(max_length), int(beam),
-                                               int(n_streams), ctypes.byref(n)) == 0
+    return _supported("rnnt_engine_beam_stream_bytes", S, E, O, H, V, bool(has_text), max_length, beam, n_streams)
 
 
 def beam_stream_init(sizes, max_length, beam, blank, state, scores, block, index=None):
@@ -1237,48 +1162,26 @@ def beam_stream_push(frames_list, pred_params, ln_eps, text_W, text_b, W, bias, 
     if len(frames_list) != n:
         raise ValueError(f"beam_stream_push: {len(frames_list)} entries for {n} streams")
     counts = [0 if f is None else int(f.shape[0]) for f in frames_list]
-    live = [f for f, k in zip(frames_list, counts) if k > 0]
-    if not live:
+    if not any(counts):
         return
-    packed = live[0] if len(live) == 1 else torch.cat(live, 0)
-    dev, packed, params, text_W, text_b, W, bias = _decode_inputs(packed, pred_params, text_W, text_b, W, bias)
-    _require_cuda(packed, state, tokens, scores, block, tables)
+    max_count = max(counts)
+    packed, rows = _pack_rows(frames_list, counts)
+    m = _DecodeModel(packed, pred_params, ln_eps, text_W, text_b, W, bias)
+    _require_cuda(m.frames, state, tokens, scores, block, tables)
     _require_dtype(torch.int32, state=state, tokens=tokens)
     _require_dtype(torch.float64, scores=scores)
     _require_contiguous(state=state, tokens=tokens, scores=scores, block=block)
-    rows, H = packed.shape
-    V = W.shape[0]
-    S, E = params[0].shape
-    O = params[7].shape[0]
     beam, max_length, max_per_frame = int(beam), int(max_length), int(max_per_frame)
     if state.shape != (n, 32) or tokens.shape != (n, beam, max_length) or scores.shape != (n, beam):
         raise RuntimeError(f"beam_stream_push: state [{n}, 32], tokens [{n}, {beam}, {max_length}], scores [{n}, {beam}] expected")
-    chunk = max(1, int(chunk))
-    max_count = max(counts)
-    bound = max_count * max(1, max_per_frame) + 1
-    begins, at = [], 0
-    for k in counts:
-        begins.append(at)
-        at += k
-    with torch.cuda.device(dev):
-        table = torch.tensor(list(zip(begins, counts)), dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-        flag = torch.zeros(1, dtype=torch.int32).pin_memory()
-        st = _PredParams(*[t.data_ptr() for t in params])
-        stream = _stream(dev)
-        eps_in, eps_out = _eps_pair(ln_eps)
-        pending = []
-        done = 0
-        while done < bound and (done == 0 or int(flag[0]) == 0):
-            it = min(chunk, 2 * max_count + 1, bound - done)  # sized to the push: a 1-frame push enqueues 3 rounds at a time, not `chunk`
-            _check(lib().rnnt_engine_beam_stream_push(
-                _p(packed), ctypes.c_int64(packed.stride(0)), rows, _p(table), n, max_count, ctypes.byref(st), S, E, O, ctypes.c_float(eps_in),
-                ctypes.c_float(eps_out), _p(text_W), _p(text_b), _p(W), _p(bias), H, V, int(blank), max_length, max_per_frame, beam,
-                _p(tables), it, 1 if done == 0 else 0, ctypes.c_void_p(flag.data_ptr()), _p(state), _p(tokens), _p(scores), _p(block),
-                ctypes.c_size_t(block.numel()), stream))
-            done += it
-            ev = torch.cuda.Event()
-            ev.record()
-            pending.append(ev)
-            if len(pending) >= max(1, int(in_flight)):  # (before the flag is read again: a short push ends after the chunk that served it)
-                pending.pop(0).synchronize()
-        state._keepalive = (flag, table, packed, params, W, bias, text_W, text_b, tables)  # until the caller has synchronised
+    with torch.cuda.device(m.dev):
+        table = _rows_table(rows, m.dev)
+        head = (_p(m.frames), ctypes.c_int64(m.frames.stride(0)), m.frames.shape[0], _p(table), n, max_count,
+                *m.args(blank, max_length, max_per_frame), beam, _p(tables))
+        tail = (_p(state), _p(tokens), _p(scores), _p(block), ctypes.c_size_t(block.numel()), _stream(m.dev))
+        # chunks sized to the push: a 1-frame push enqueues 3 rounds at a time, not `chunk`; and the wait as soon as `in_flight` chunks
+        # are out (before the flag is read again: a short push ends after the chunk that served it)
+        flag = _enqueue_rounds(lambda it, first, flag: _check(lib().rnnt_engine_beam_stream_push(*head, it, first, flag, *tail)),
+                               max_count * max(1, max_per_frame) + 1, min(max(1, int(chunk)), 2 * max_count + 1), in_flight,
+                               wait_at_limit=True)
+        state._keepalive = (flag, table, *m.keep, tables)  # until the caller has synchronised

@@ -82,16 +82,9 @@ class _RNNTLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, targets, logit_lengths, target_lengths, blank, clamp, fastemit_lambda=0.0,
                 delay_penalty=0.0, restrict=None):
-        if restrict is not None:
-            costs, grad = engine.loss_fwd_bwd_restrict(logits, targets, logit_lengths, target_lengths, blank, clamp,
-                                                       fastemit_lambda, delay_penalty, *restrict,
-                                                       want_grad=ctx.needs_input_grad[0])
-        elif fastemit_lambda or delay_penalty:
-            costs, grad = engine.loss_fwd_bwd_reg(logits, targets, logit_lengths, target_lengths, blank, clamp,
-                                                  fastemit_lambda, delay_penalty, want_grad=ctx.needs_input_grad[0])
-        else:
-            costs, grad = engine.loss_fwd_bwd(logits, targets, logit_lengths, target_lengths, blank,
-                                              clamp, want_grad=ctx.needs_input_grad[0])
+        reg = (fastemit_lambda, delay_penalty) if restrict is not None or fastemit_lambda or delay_penalty else None
+        costs, grad = engine._loss_fwd_bwd(logits, targets, logit_lengths, target_lengths, blank, clamp, ctx.needs_input_grad[0],
+                                           reg, restrict)
         ctx.save_for_backward(grad)
         return costs
 
@@ -217,32 +210,15 @@ class _JointRNNTLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, enc, pred, W, bias, targets, logit_lengths, target_lengths, blank, scale,
                 dtype, need_grad=True, fastemit_lambda=0.0, delay_penalty=0.0, restrict=None):
-        if not need_grad:  # torch.no_grad() / nothing requires grad: forward kernels only
-            if restrict is not None:
-                costs = engine.joint_loss_fwd_restrict(enc, pred.contiguous(), W.contiguous(), bias.contiguous(), targets,
-                                                       logit_lengths, target_lengths, blank, delay_penalty, *restrict, dtype=dtype)
-            elif delay_penalty:  # (FastEmit changes no cost)
-                costs = engine.joint_loss_fwd_reg(enc, pred.contiguous(), W.contiguous(), bias.contiguous(), targets,
-                                                  logit_lengths, target_lengths, blank, delay_penalty, dtype=dtype)
-            else:
-                costs = engine.joint_loss_fwd(enc, pred.contiguous(), W.contiguous(), bias.contiguous(),
-                                              targets, logit_lengths, target_lengths, blank, dtype=dtype)
-            ctx.mark_non_differentiable(costs)
-            return costs.sum() * scale, costs
-        if restrict is not None:
-            costs, ge, gp, gW, gb = engine.joint_loss_fwd_bwd_restrict(
-                enc, pred.contiguous(), W.contiguous(), bias.contiguous(), targets, logit_lengths,
-                target_lengths, blank, scale, fastemit_lambda, delay_penalty, *restrict, dtype=dtype)
-        elif fastemit_lambda or delay_penalty:
-            costs, ge, gp, gW, gb = engine.joint_loss_fwd_bwd_reg(
-                enc, pred.contiguous(), W.contiguous(), bias.contiguous(), targets, logit_lengths,
-                target_lengths, blank, scale, fastemit_lambda, delay_penalty, dtype=dtype)
-        else:
-            costs, ge, gp, gW, gb = engine.joint_loss_fwd_bwd(
-                enc, pred.contiguous(), W.contiguous(), bias.contiguous(), targets, logit_lengths,
-                target_lengths, blank, scale, dtype=dtype)
-        ctx.save_for_backward(ge, gp, gW, gb)
-        ctx.scale = scale
+        # need_grad False (torch.no_grad() / nothing requires grad): forward kernels only, and FastEmit changes no cost.  The
+        # regularised entries only where a regulariser is set (or the lattice is restricted): the plain ones keep the f16x2 flush rule
+        regularised = (fastemit_lambda or delay_penalty) if need_grad else delay_penalty
+        costs, *grads = engine._fused(enc, pred.contiguous(), W.contiguous(), bias.contiguous(), targets, logit_lengths,
+                                      target_lengths, blank, dtype, scale if need_grad else None,
+                                      (fastemit_lambda, delay_penalty) if restrict is not None or regularised else None, restrict)
+        if need_grad:
+            ctx.save_for_backward(*grads)
+            ctx.scale = scale
         ctx.mark_non_differentiable(costs)
         return costs.sum() * scale, costs
 

@@ -119,10 +119,36 @@ class RNNTModel(torch.nn.Module):
         sees, so a cache keyed on tensor identity went stale between the reference flow's evaluations (rnnt/train.py:165-201).  A build is
         ~0.13 ms; greedy_decode_many shares one build between all utterances of a call, greedy_decode lets the launch rebuild in place."""
         from . import engine
-        tl = getattr(self.joint, "text_ln", None)
-        return engine.greedy_decode_tables(self.predictor._params(), (float(self.predictor.input_layer_norm.eps), float(self.predictor.output_layer_norm.eps)),
-                                           tl.weight if tl is not None else None, tl.bias if tl is not None else None,
-                                           self.joint.joint_ln.in_features)
+        return engine.greedy_decode_tables(*self._decode_bundle()[:4], self.joint.joint_ln.in_features)
+
+    # ---- what the engine's decode entries are told about the model: greedy, beam and both kinds of stream share these
+    def _decode_sizes(self):
+        """(S, E, O, H, V, has_text), as the engine's *_supported queries take them."""
+        p, joint = self.predictor, self.joint
+        S, E = p.embedding.weight.shape
+        return (S, E, p.linear.out_features, joint.joint_ln.in_features, joint.joint_ln.out_features, hasattr(joint, "text_ln"))
+
+    def _decode_bundle(self):
+        """The arguments every engine decode entry takes after the frames: the predictor's parameters, its two LayerNorm eps,
+        joint.text_ln's weight and bias (or None, None), joint_ln's weight and bias, the blank."""
+        p, joint = self.predictor, self.joint
+        tl = getattr(joint, "text_ln", None)
+        return (p._params(), (float(p.input_layer_norm.eps), float(p.output_layer_norm.eps)),
+                tl.weight if tl is not None else None, tl.bias if tl is not None else None,
+                joint.joint_ln.weight, joint.joint_ln.bias, joint.blank_idx)
+
+    def _decode_frames(self, audio):
+        """Encoder output (1, n, C), permuted as rnnt/model.py:93 -> the [n, H] fp32 frames the decode entries read: audio_ln applied
+        (per frame: the same numbers chunk by chunk), contiguous."""
+        frames, joint = audio[0], self.joint
+        if hasattr(joint, "audio_ln"):
+            frames = joint.audio_ln(frames)
+        return frames.float().contiguous()
+
+    @staticmethod
+    def _nbest(st, toks, sc):
+        """One search's n-best list from its state words, token rows and scores (engine.beam_decode's layout), best first."""
+        return [(toks[j][1:1 + st[8 + j]], sc[j]) for j in range(st[2])]
 
     @torch.no_grad()
     def greedy_decode(self, mel_features: torch.Tensor, mel_feature_lens: torch.Tensor,
@@ -146,18 +172,10 @@ class RNNTModel(torch.nn.Module):
             from . import engine
             if stateful or not self._device_loop_ok(audio):
                 raise RuntimeError("greedy_decode(device_loop=True) needs the engine's stateless ConvPredictor in eval mode on a HIP device")
-            frames = audio[0]
-            if hasattr(self.joint, "audio_ln"):
-                frames = self.joint.audio_ln(frames)
-            frames = frames.float().contiguous()
-            tl = getattr(self.joint, "text_ln", None)
-            args = (frames, self.predictor._params(), (float(self.predictor.input_layer_norm.eps), float(self.predictor.output_layer_norm.eps)),
-                    tl.weight if tl is not None else None, tl.bias if tl is not None else None,
-                    self.joint.joint_ln.weight, self.joint.joint_ln.bias, self.joint.blank_idx, max_length)
-            S, E = self.predictor.embedding.weight.shape
+            frames = self._decode_frames(audio)
+            args = (frames, *self._decode_bundle(), max_length)
             if persistent is None:  # one persistent launch per utterance where the engine takes the sizes
-                persistent = engine.greedy_decode_persistent_supported(frames.shape[0], S, E, self.predictor.linear.weight.shape[0],
-                                                                       frames.shape[1], self.joint.joint_ln.weight.shape[0], tl is not None)
+                persistent = engine.greedy_decode_persistent_supported(frames.shape[0], *self._decode_sizes())
             if persistent:
                 state, toks = engine.greedy_decode_persistent(*args, max_per_frame=10)  # tables rebuilt inside the call, from the live weights
             else:
@@ -206,16 +224,13 @@ class RNNTModel(torch.nn.Module):
         assert all(m.shape[0] == 1 for m in mels), "one utterance per entry"
         lens = [torch.tensor([m.shape[-1]], device=m.device) for m in mels]
         dev = mels[0].device
-        tl = getattr(self.joint, "text_ln", None)
         ok = (max_length >= 2 and dev.type == "cuda" and not self._predictor_is_stateful()
               and self._device_loop_ok(torch.zeros(1, 1, device=dev)))
         if ok:
-            S, E = self.predictor.embedding.weight.shape
-            H, V = self.joint.joint_ln.in_features, self.joint.joint_ln.out_features
-            ok = engine.greedy_decode_persistent_supported(8, S, E, self.predictor.linear.weight.shape[0], H, V, tl is not None)
+            ok = engine.greedy_decode_persistent_supported(8, *self._decode_sizes())
         if not ok:
             return [self.greedy_decode(m, l, max_length=max_length) for m, l in zip(mels, lens)]
-        groups = min(max((V + 15) // 16, 16), 128)
+        groups = min(max((self.joint.joint_ln.out_features + 15) // 16, 16), 128)
         cus = torch.cuda.get_device_properties(dev).multi_processor_count
         n_par = max(1, min(int(concurrency) if concurrency else 8, cus // groups, len(mels)))
         cur = torch.cuda.current_stream(dev)
@@ -226,16 +241,8 @@ class RNNTModel(torch.nn.Module):
             st = streams[i % n_par]
             st.wait_stream(cur)
             with torch.cuda.stream(st):
-                audio = self.encoder(mel).permute(0, 2, 1)
-                frames = audio[0]
-                if hasattr(self.joint, "audio_ln"):
-                    frames = self.joint.audio_ln(frames)
-                frames = frames.float().contiguous()
-                state, toks = engine.greedy_decode_persistent(
-                    frames, self.predictor._params(), (float(self.predictor.input_layer_norm.eps), float(self.predictor.output_layer_norm.eps)),
-                    tl.weight if tl is not None else None, tl.bias if tl is not None else None,
-                    self.joint.joint_ln.weight, self.joint.joint_ln.bias, self.joint.blank_idx, max_length, max_per_frame=10,
-                    tables=tables)
+                frames = self._decode_frames(self.encoder(mel).permute(0, 2, 1))
+                state, toks = engine.greedy_decode_persistent(frames, *self._decode_bundle(), max_length, max_per_frame=10, tables=tables)
             pending.append((state, mel))
         for st in streams:
             st.synchronize()
@@ -294,28 +301,18 @@ class RNNTModel(torch.nn.Module):
         from . import engine
         if context is not None and context.n_nodes > engine.BEAM_CONTEXT_MAX_NODES:
             return False
-        p = self.predictor
-        S, E = p.embedding.weight.shape
-        return engine.beam_decode_supported(S, E, p.linear.out_features, self.joint.joint_ln.in_features,
-                                            self.joint.joint_ln.out_features, hasattr(self.joint, "text_ln"), max_length, beam_size)
+        return engine.beam_decode_supported(*self._decode_sizes(), max_length, beam_size)
 
     def _beam_search_device(self, audio, beam_size, max_length, m, context=None):
         from . import engine
-        frames = audio[0]
-        if hasattr(self.joint, "audio_ln"):
-            frames = self.joint.audio_ln(frames)
-        frames = frames.float().contiguous()
-        tl = getattr(self.joint, "text_ln", None)
-        p = self.predictor
+        frames = self._decode_frames(audio)
         state, tokens, scores = engine.beam_decode(
-            frames, p._params(), (float(p.input_layer_norm.eps), float(p.output_layer_norm.eps)),
-            tl.weight if tl is not None else None, tl.bias if tl is not None else None,
-            self.joint.joint_ln.weight, self.joint.joint_ln.bias, self.joint.blank_idx, max_length, beam_size, max_per_frame=m,
+            frames, *self._decode_bundle(), max_length, beam_size, max_per_frame=m,
             context=context.device_tables(frames.device) if context is not None else None)
         st, toks, sc = state.tolist(), tokens.tolist(), scores.tolist()  # the utterance's one synchronisation
         if not st[3]:
             raise RuntimeError(f"rnnt_engine: the beam search did not finish (t={st[0]}, {st[5]} rounds)")
-        nbest = [(toks[j][1:1 + st[8 + j]], sc[j]) for j in range(st[2])]
+        nbest = self._nbest(st, toks, sc)
         return context.finalise(nbest) if context is not None else nbest  # (the device's scores are internal)
 
     BEAM_BATCH = 32  # beam_search_many's default batch: the best of N = 1 .. 32 in profiles/beam_batch_bench.txt, the only one within 10 % of it
@@ -364,24 +361,15 @@ class RNNTModel(torch.nn.Module):
                 continue
             if tables is None:
                 tables = self._decode_tables()  # one build per call, shared by every batch and utterance
-            frames = []
-            for u in batched:
-                f = audios[u][0]
-                if hasattr(self.joint, "audio_ln"):
-                    f = self.joint.audio_ln(f)
-                frames.append(f.float().contiguous())
-            tl = getattr(self.joint, "text_ln", None)
-            p = self.predictor
+            frames = [self._decode_frames(audios[u]) for u in batched]
             state, tokens, scores = engine.beam_decode_batch(
-                frames, p._params(), (float(p.input_layer_norm.eps), float(p.output_layer_norm.eps)),
-                tl.weight if tl is not None else None, tl.bias if tl is not None else None,
-                self.joint.joint_ln.weight, self.joint.joint_ln.bias, self.joint.blank_idx, max_length, beam_size, max_per_frame=m,
+                frames, *self._decode_bundle(), max_length, beam_size, max_per_frame=m,
                 tables=tables, context=g.device_tables(frames[0].device) if g is not None else None)
             sts, toks, scs = state.tolist(), tokens.tolist(), scores.tolist()  # the batch's one synchronisation
             for k, (u, st) in enumerate(zip(batched, sts)):
                 if not st[3]:
                     raise RuntimeError(f"rnnt_engine: the beam search of utterance {i + u} did not finish (t={st[0]}, {st[5]} rounds)")
-                nbest = [(toks[k][j][1:1 + st[8 + j]], scs[k][j]) for j in range(st[2])]
+                nbest = self._nbest(st, toks[k], scs[k])
                 out[i + u] = g.finalise(nbest) if g is not None else nbest
         return out if return_nbest else [list(nbest[0][0]) for nbest in out]
 
@@ -407,11 +395,7 @@ class RNNTModel(torch.nn.Module):
 
     def _beam_batch_ok(self, n_utt, beam_size, max_length) -> bool:
         from . import engine
-        p = self.predictor
-        S, E = p.embedding.weight.shape
-        return engine.beam_decode_batch_supported(S, E, p.linear.out_features, self.joint.joint_ln.in_features,
-                                                  self.joint.joint_ln.out_features, hasattr(self.joint, "text_ln"), max_length, beam_size,
-                                                  n_utt)
+        return engine.beam_decode_batch_supported(*self._decode_sizes(), max_length, beam_size, n_utt)
 
     def _beam_search_host(self, audio, beam_size, max_length, m, context=None):
         """The search of DESIGN.md §4h as a host loop: the predictor on the whole history of each new hypothesis (cached by

@@ -166,13 +166,11 @@ class GreedyStream:
         self._host = None
         self._tables = None
         if self._on_device:
-            p, joint = model.predictor, model.joint
-            S, E = p.embedding.weight.shape
-            self._sizes = (S, E, p.linear.out_features, joint.joint_ln.in_features, joint.joint_ln.out_features, hasattr(joint, "text_ln"))
+            self._sizes = model._decode_sizes()
             if persistent is not False and engine.greedy_decode_persistent_supported(8, *self._sizes):
                 self._tables = model._decode_tables()  # once per stream, from the weights as they are now
             self._buf = torch.empty(engine.STREAM_STATE_WORDS + 16, dtype=torch.int32, device=dev)  # state block | the push's labels
-            engine.greedy_stream_init(self._buf[:engine.STREAM_STATE_WORDS], joint.blank_idx)
+            engine.greedy_stream_init(self._buf[:engine.STREAM_STATE_WORDS], model.joint.blank_idx)
         else:
             self._host = HostGreedyLoop(model, self.max_length, self.max_symbols_per_frame, scan_frames=32)
 
@@ -235,11 +233,7 @@ class GreedyStream:
 
     def _push_device(self, audio):
         from . import engine
-        model, joint = self.model, self.model.joint
-        frames = audio[0]
-        if hasattr(joint, "audio_ln"):  # per frame: the same numbers chunk by chunk
-            frames = joint.audio_ln(frames)
-        frames = frames.float().contiguous()
+        frames = self.model._decode_frames(audio)
         if frames.device != self._buf.device:
             raise ValueError(f"GreedyStream: the stream lives on {self._buf.device}, the chunk on {frames.device}")
         n = frames.shape[0]
@@ -254,10 +248,7 @@ class GreedyStream:
         persistent = self.persistent
         if persistent is None:
             persistent = self._tables is not None and engine.greedy_stream_supported(n, *self._sizes, ml, m)
-        p, tl = model.predictor, getattr(joint, "text_ln", None)
-        args = (frames, p._params(), (float(p.input_layer_norm.eps), float(p.output_layer_norm.eps)),
-                tl.weight if tl is not None else None, tl.bias if tl is not None else None,
-                joint.joint_ln.weight, joint.joint_ln.bias, joint.blank_idx, ml, m, self._tables)
+        args = (frames, *self.model._decode_bundle(), ml, m, self._tables)
 
         def run(persist):
             engine.greedy_stream_decode(*args, persist, self._buf[:W], self._buf[W:W + cap])
@@ -422,9 +413,7 @@ class BeamStreamGroup:
         # (with a context graph: the host loop — the device stream carries no node per slot yet)
         self._on_device = context is None and dev.type == "cuda" and model._beam_device_ok(torch.zeros(1, 1, device=dev), beam_size, max_length)
         if self._on_device:
-            p, joint = model.predictor, model.joint
-            S, E = p.embedding.weight.shape
-            self._sizes = (S, E, p.linear.out_features, joint.joint_ln.in_features, joint.joint_ln.out_features, hasattr(joint, "text_ln"))
+            self._sizes = model._decode_sizes()
             self._on_device = engine.beam_stream_supported(*self._sizes, max_length, beam_size, n)
         if self._on_device:
             self._tables = model._decode_tables()  # once per group, from the weights as they are now
@@ -433,7 +422,7 @@ class BeamStreamGroup:
             self._cut = (8 * n * beam_size, 8 * n * beam_size + 4 * 32 * n)
             self._res = torch.zeros(self._cut[1] + 4 * n * beam_size * max_length, dtype=torch.uint8, device=dev)
             self._scores, self._state, self._tokens = self._views(self._res)
-            engine.beam_stream_init(self._sizes, max_length, beam_size, joint.blank_idx, self._state, self._scores, self._block)
+            engine.beam_stream_init(self._sizes, max_length, beam_size, model.joint.blank_idx, self._state, self._scores, self._block)
         else:
             self._loops = [HostBeamLoop(model, beam_size, max_length, m, context) for _ in range(n)]
 
@@ -489,22 +478,11 @@ class BeamStreamGroup:
 
     def _push_device(self, audios):
         from . import engine
-        model, joint = self.model, self.model.joint
-        frames = []
-        for a in audios:
-            f = None
-            if a is not None:
-                f = a[0]
-                if hasattr(joint, "audio_ln"):  # per frame: the same numbers chunk by chunk
-                    f = joint.audio_ln(f)
-                f = f.float().contiguous()
-                if f.device != self._res.device:
-                    raise ValueError(f"beam stream: the stream lives on {self._res.device}, the chunk on {f.device}")
-            frames.append(f)
-        p, tl = model.predictor, getattr(joint, "text_ln", None)
-        engine.beam_stream_push(frames, p._params(), (float(p.input_layer_norm.eps), float(p.output_layer_norm.eps)),
-                                tl.weight if tl is not None else None, tl.bias if tl is not None else None,
-                                joint.joint_ln.weight, joint.joint_ln.bias, joint.blank_idx, self.max_length, self.beam_size,
+        frames = [None if a is None else self.model._decode_frames(a) for a in audios]
+        for f in frames:
+            if f is not None and f.device != self._res.device:
+                raise ValueError(f"beam stream: the stream lives on {self._res.device}, the chunk on {f.device}")
+        engine.beam_stream_push(frames, *self.model._decode_bundle(), self.max_length, self.beam_size,
                                 self.max_symbols_per_frame, self._tables, self._state, self._tokens, self._scores, self._block)
         scores, state, tokens = self._views(self._res.cpu())  # the push's one synchronisation
         sts, toks, scs = state.tolist(), tokens.tolist(), scores.tolist()
@@ -515,7 +493,7 @@ class BeamStreamGroup:
                 raise RuntimeError(f"rnnt_engine: beam stream {i} did not consume its push (frames={st[engine.BEAM_STREAM_FRAMES]}, "
                                    f"{st[5]} rounds)")
             self.frames[i] = st[engine.BEAM_STREAM_FRAMES]
-            self.nbest[i] = [(toks[i][j][1:1 + st[8 + j]], scs[i][j]) for j in range(st[2])]
+            self.nbest[i] = self.model._nbest(st, toks[i], scs[i])
         self.last_path = "device"
 
 
