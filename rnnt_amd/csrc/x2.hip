@@ -91,9 +91,9 @@ __device__ __forceinline__ void x2_lds_barrier()
     __builtin_amdgcn_sched_barrier(0);
 }
 template <int N> struct X2Int { static constexpr int value = N; };
-#define XW2_ROWS_ 16  // = XW2_ROWS: cells per dW k-step
-#define XG2_BT_ 8    // = XG2_BT, XG2_BU: the dHidden tile
-#define XG2_BU_ 16
+#define XW2_ROWS 16  // cells per dW k-step (the live structures below are built in these units)
+#define XG2_BT 8     // the dHidden tile: 8 t x 16 u cells
+#define XG2_BU 16
 
 // ---------------------------------------------------------------------------------------
 // s_W = 2^(14 - ceil(log2 max|W|)) (1 for an all-zero W): one workgroup, V*H/4 float4 reads.  A W with a NaN or an infinity in it (a diverged
@@ -254,7 +254,7 @@ X2LiveWs x2_live_layout(int B, int T, int U1, long rows_pad)
 {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     X2LiveWs L{};
-    L.nks = rows_pad / XW2_ROWS_;
+    L.nks = rows_pad / XW2_ROWS;
     L.ntile = (long)B * ((T + 7) / 8) * ((U1 + 15) / 16);
     L.nblk = (int)((L.nks + XL2_BLK - 1) / XL2_BLK);
     size_t o = 256;  // live_stats
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(XL2_BLK) void k_x2_live_count(const CellCoef *__res
     __shared__ unsigned short s_nib[16][16];  // [round = bitmap word][wave]: the wave's 4 k-step flags
     __shared__ unsigned short s_grp[16][16];  // [round][wave]: the wave's 16 group flags
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long base = (long)blockIdx.x * XL2_BLK * XW2_ROWS_;
+    const long base = (long)blockIdx.x * XL2_BLK * XW2_ROWS;
     for (int it = 0; it < 16; ++it) {
         const long c = base + (long)it * XL2_BLK + threadIdx.x;
         const bool live = c < cells && x2_coef_live(coef[c]);
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(1024) void k_x2_live_scan(int *__restrict__ blk, in
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        stats[0] = total; stats[1] = (int)((cells + XW2_ROWS_ - 1) / XW2_ROWS_); stats[2] = s_carry; stats[3] = (int)ntile;
+        stats[0] = total; stats[1] = (int)((cells + XW2_ROWS - 1) / XW2_ROWS); stats[2] = s_carry; stats[3] = (int)ntile;
         stats[4] = gtotal; stats[5] = (int)((cells + 3) / 4);
     }
     if (threadIdx.x < 8) list[total + threadIdx.x] = (int)nks;  // rows rows_pad ..: zero padding (rows_alloc >= rows_pad + 96)
@@ -433,7 +433,7 @@ __global__ __launch_bounds__(256) void k_x2_live_tiles(const CellCoef *__restric
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
         const int r = it * 64 + lane;
-        const int t = tt * XG2_BT_ + (r >> 4), u = ub * XG2_BU_ + (r & 15);
+        const int t = tt * XG2_BT + (r >> 4), u = ub * XG2_BU + (r & 15);
         if (t < T && u < U1) live = live || x2_coef_live(coef[(b * T + t) * U1 + u]);
     }
     const bool any = __any(live ? 1 : 0) != 0;
@@ -446,7 +446,7 @@ void launch_x2_live(const X3Args &a, hipStream_t st)
     int *blk = (int *)((char *)a.live_stats + L.blk);
     int *gblk = (int *)((char *)a.live_stats + L.gblk);
     unsigned long long *bitmap = (unsigned long long *)a.ks_bitmap, *gbitmap = (unsigned long long *)a.grp_bitmap;
-    const int ntt = (a.T + XG2_BT_ - 1) / XG2_BT_, nub = (a.U1 + XG2_BU_ - 1) / XG2_BU_;
+    const int ntt = (a.T + XG2_BT - 1) / XG2_BT, nub = (a.U1 + XG2_BU - 1) / XG2_BU;
     hipLaunchKernelGGL(k_x2_live_tiles, dim3((unsigned)((L.ntile + 3) / 4)), dim3(256), 0, st, a.coef, a.T, a.U1, ntt, nub, L.ntile, (unsigned char *)a.tile_live);
     hipLaunchKernelGGL(k_x2_live_count, dim3(L.nblk), dim3(XL2_BLK), 0, st, a.coef, cells, bitmap, blk, gbitmap, gblk);
     hipLaunchKernelGGL(k_x2_live_scan, dim3(1), dim3(1024), 0, st, blk, L.nblk, a.live_stats, a.ks_list, cells, L.nks, L.ntile, a.tile_live, (int *)a.tile_list, gblk, a.grp_list);
@@ -486,7 +486,7 @@ void launch_dw_reduce_x2(const X3Args &a, float *grad_W, float *grad_bias, hipSt
 //  * tile image: 256-byte rows, 16-byte chunk ch of row r at 16*(ch ^ swz(r)), swz(r) = ((r&3)<<2) | ((r>>2)&3), applied
 //    on the DMA's SOURCE side (the DMA writes LDS linearly).
 // One k-step = 16 cells = 3 products x 16 tiles = 48 MFMAs (1536 matrix-pipe cycles) against 32 KiB staged.  Per k-step:
-// counted vmcnt + one barrier publish stage ks, the 8 DMAs of stage ks+2 go into the slot of ks-1 threaded through the
+// counted vmcnt + one barrier publish stage ks, the 8 DMAs of stage ks+3 go into the slot of ks-1 threaded through the
 // MFMAs (3 + 3 + 2), fragment reads run one product ahead of their MFMAs.  Products ah.bh, am.bh, ah.bm.
 // K walk: the split-K ranges are cut from the ascending list of LIVE 4-cell groups (X3Args::grp_list: the groups that hold a cell with
 // non-null coefficients — inside the lengths, reachable, not flushed) in units of k-steps of four entries, n_k = ceil(live groups / 4),
@@ -497,11 +497,7 @@ void launch_dw_reduce_x2(const X3Args &a, float *grad_W, float *grad_bias, hipSt
 // hold zeros (k_dhidden_x2 writes them inside its live tiles, k_x2_dead_rows those of the tiles that are not live).
 // The accumulators hold g_scale x 2^14 x dW: the epilogue multiplies by X3Args::dw_rescale (a power of two).
 // ---------------------------------------------------------------------------------------
-#define XW2_ROWS 16
-static_assert(XW2_ROWS == XW2_ROWS_, "k-step size");
-#ifndef XW2_NST
 #define XW2_NST 4   // ring stages: the DMAs of stage ks + NST - 1 are issued during k-step ks
-#endif
 #define XW2_PLANE 4096            // one operand tile of one plane: 16 rows x 256 B
 #define XW2_STAGE (2 * XW2_PLANE)  // one stage of one operand tile
 #define XW2_TILE (XW2_NST * XW2_STAGE)  // ring of one operand tile: [stage][plane][16 x 256 B] = 24 KiB
@@ -522,6 +518,222 @@ struct X2Frag { u32x2 lo[4], hi[4]; };  // 4 tiles: cells 0-3 / 4-7 of a lane's 
                    "+v"(f.hi[2]), "+v"(f.hi[3])                                                                  \
                  :: "memory")
 
+// ---------------------------------------------------------------------------------------
+// The dW k-step pipeline: the pieces k_dw_x2<4>, k_dw_x2<4, true> and both tile kinds of k_dw_x2m are built from, each once.  A kernel keeps
+// what really differs — tile geometry and wave layout, which operand tile a wave stages and from where, its list walk with the counted
+// wait in front of it, dead tiles — and hands the pipeline two callables: the DMA pieces of a stage one by one (threaded through the
+// MFMAs), and all of them at once (prologue).
+// The pieces are plain `inline`, not __forceinline__: the regular inliner takes them bottom-up, as it took the lambdas they replace, and
+// k_dw_x2's k loops come out instruction for instruction as before; inlined by force (before any simplification) every k-step gained eight
+// v_mov of zeros for the db fragments (profiles/x2_dw_refactor_isa.txt).  Nothing here may stay a call: the accumulators go by reference.
+// ---------------------------------------------------------------------------------------
+// XCD-aware remap of the workgroup id: the tiles of one split share an XCD's L2
+__device__ inline int x2_dw_xcd_remap(int id, int total)
+{
+    const int q8 = total / 8, r8 = total % 8, x = id % 8;
+    return (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + id / 8;
+}
+// Transposed fragment reads.  Fragment of 32-column tile m of operand tile otile: lane (g = lane>>4, q = (lane&15)>>2, p = lane&3) reads
+// rows 8(g>>1) + 4sec + q at chunk 4m + 2(g&1) + (p>>1), +8(p&1) bytes, sec = 0,1 — its LDS address in stage 0, plane 0 of the tile's ring
+// (lds0: the ring's), the chunk where the DMA's source-side swizzle put it
+__device__ inline int x2_dw_frag_addr(int lds0, int otile, int m, int sec, int lane)
+{
+    const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3, hh = g >> 1;
+    const int row = 8 * hh + 4 * sec + q;
+    const int swz = ((row & 3) << 2) | ((row >> 2) & 3);
+    const int ch = 4 * m + 2 * (g & 1) + (pp >> 1);
+    return lds0 + otile * XW2_TILE + 256 * row + 16 * (ch ^ swz) + 8 * (pp & 1);
+}
+// 2 NT transposed reads of plane P, ring stage ST (compile-time: every LDS offset is an immediate) of an operand (inline asm: hipcc guards
+// every LDS read it can see behind an LDS-DMA with vmcnt(0)); results are used only after X2_LANDED named them
+template <int ST, int P, int NT>
+__device__ inline void x2_dw_reads(X2Frag &f, const int (&base)[4][2])
+{
+    constexpr int off = ST * XW2_STAGE + P * XW2_PLANE;
+#pragma unroll
+    for (int m = 0; m < NT; ++m) {
+        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.lo[m]) : "v"(base[m][0]), "n"(off));
+        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.hi[m]) : "v"(base[m][1]), "n"(off));
+    }
+}
+// 16 MFMAs of one product with the stage's DMA pieces N0 .. N0+CNT-1 (CNT <= 4) threaded through them, one per row of wave tiles: behind
+// row 0, 1 and 3, a fourth behind row 2.  dma_piece(X2Int<n>) issues piece n; live_n: this wave's h columns exist (wave-uniform)
+template <int N0, int CNT, class Piece>
+__device__ inline void x2_dw_product(f32x16 (&acc)[4][4], const X2Frag &fa_, const X2Frag &fb_, bool live_n, const Piece &dma_piece)
+{
+    u32x4 fa[4], fb[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        fa[m] = u32x4{fa_.lo[m][0], fa_.lo[m][1], fa_.hi[m][0], fa_.hi[m][1]};
+        fb[m] = u32x4{fb_.lo[m][0], fb_.lo[m][1], fb_.hi[m][0], fb_.hi[m][1]};
+    }
+#pragma unroll
+    for (int qm = 0; qm < 4; ++qm) {
+        if (live_n) {
+#pragma unroll
+            for (int qn = 0; qn < 4; ++qn) acc[qm][qn] = x2_mfma(fa[qm], fb[qn], acc[qm][qn]);
+        }
+        if (qm == 0 && CNT >= 1) dma_piece(X2Int<N0>{});
+        if (qm == 1 && CNT >= 2) dma_piece(X2Int<N0 + (CNT >= 2 ? 1 : 0)>{});
+        if (qm == 2 && CNT >= 4) dma_piece(X2Int<N0 + (CNT >= 4 ? 2 : 0)>{});
+        if (qm == 3 && CNT >= 3) dma_piece(X2Int<N0 + (CNT >= 3 ? CNT - 1 : 0)>{});
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+// db rides the matrix pipe as in k_dw_x3: one more MFMA per plane and k-step against a column SELECTOR of ones (sv: fp16 ones in the
+// selector's column), for one (one h block: two) of the wave's M tiles — fragment bases sbase — into a 17th accumulator tile held in VGPRs
+template <int ST, int P>
+__device__ inline void x2_dw_bias_read(u32x2 &lo, u32x2 &hi, const int (&sbase)[2])
+{
+    constexpr int off = ST * XW2_STAGE + P * XW2_PLANE;
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(sbase[0]), "n"(off));
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(sbase[1]), "n"(off));
+}
+__device__ inline void x2_dw_bias_mfma(u32x2 &lo, u32x2 &hi, f32x16 &dacc, unsigned sv)
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo), "+v"(hi) :: "memory");
+    const u32x4 fa = {lo[0], lo[1], hi[0], hi[1]};
+    const u32x4 sel = {sv, sv, sv, sv};
+    // accumulator in VGPRs, spelled as asm (left to hipcc the 17th tile is shuttled through the full AGPR file)
+    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(dacc) : "v"(fa), "v"(sel));
+}
+// what a wave sums into db: nothing, the tile at sbase[0] (selector column 0), or with one h block (two_b, H <= 256 only) also the one at
+// sbase[1] (column 1)
+struct X2DwBias { bool do_b, two_b; unsigned sel0, sel1; int sbase[2][2]; };
+// One k-step on ring stage ST, behind the kernel's counted wait for the stage: one barrier publishes it (every wave is past its reads of
+// the stage before, whose ring slot the DMA pieces refill), then the products ah.bh, am.bh, ah.bm with C0 + C1 + C2 DMA pieces threaded
+// through them; the fragment reads run one product ahead of their MFMAs
+template <int ST, int C0, int C1, int C2, class Piece>
+__device__ inline void x2_dw_kstep(f32x16 (&acc)[4][4], f32x16 &dacc, const int (&abase)[4][2], const int (&bbase)[4][2], const X2DwBias &b,
+                                            bool live_n, const Piece &dma_piece)
+{
+    x2_lds_barrier();
+    X2Frag Ah, Bh, Am, Bm;
+    u32x2 dl[2], dh[2];
+    x2_dw_reads<ST, 0, 4>(Ah, abase);
+    x2_dw_reads<ST, 0, 4>(Bh, bbase);
+    x2_dw_reads<ST, 1, 4>(Am, abase);
+    X2_LANDED(Ah, 8);
+    X2_LANDED(Bh, 8);
+    x2_dw_product<0, C0>(acc, Ah, Bh, live_n, dma_piece);
+    x2_dw_reads<ST, 1, 4>(Bm, bbase);
+    X2_LANDED(Am, 8);
+    x2_dw_product<C0, C1>(acc, Am, Bh, live_n, dma_piece);
+    X2_LANDED(Bm, 0);
+    if (b.do_b) { x2_dw_bias_read<ST, 0>(dl[0], dh[0], b.sbase[0]); x2_dw_bias_read<ST, 1>(dl[1], dh[1], b.sbase[0]); }
+    x2_dw_product<C0 + C1, C2>(acc, Ah, Bm, live_n, dma_piece);
+    if (b.do_b) {
+        x2_dw_bias_mfma(dl[0], dh[0], dacc, b.sel0); x2_dw_bias_mfma(dl[1], dh[1], dacc, b.sel0);
+        if (b.two_b) {
+            x2_dw_bias_read<ST, 0>(dl[0], dh[0], b.sbase[1]); x2_dw_bias_read<ST, 1>(dl[1], dh[1], b.sbase[1]);
+            x2_dw_bias_mfma(dl[0], dh[0], dacc, b.sel1); x2_dw_bias_mfma(dl[1], dh[1], dacc, b.sel1);
+        }
+    }
+}
+// Soft lockstep of the tiles of a split (k_dw_bf16's, round 3).  They walk the same k-steps and share every operand byte
+// through their XCD's L2 (G between the h blocks, hidden between the v blocks); nothing else holds them together, and at
+// this kernel's pace a tile that falls behind finds its lines evicted and becomes its own HBM stream — counted without
+// it: 83 GB fetched for 39.5 GB of operands (profiles/r04_f16x2_hbm_traffic_pmc.txt, first pass).  Every NST k-steps a
+// tile publishes its k-step count and looks at its right-hand neighbour's in the ring of the split's tiles (one coherent
+// scalar load, issued a look before its value is used); a tile more than DW_LAG k-steps ahead of that neighbour naps.
+// Bounded: after DW_NAPS naps without the neighbour catching up (a partner that is not resident) the tile stops looking,
+// so every wave reaches the end whatever the others do.
+struct X2DwLockstep {
+    int *prog;      // the progress words of the split's tiles
+    const int *nb;  // the right-hand neighbour's word
+    int nb_at;      // the neighbour's k-step count as of the last look
+    bool sync_on;
+};
+__device__ inline X2DwLockstep x2_dw_lockstep_init(int *dw_prog, int split, int tile, int tiles)
+{
+    X2DwLockstep s;
+    s.prog = dw_prog ? dw_prog + split * 16 : nullptr;
+    s.sync_on = s.prog != nullptr && tiles > 1 && tiles <= 16;
+    s.nb = s.prog ? s.prog + (tile + 1 < tiles ? tile + 1 : 0) : nullptr;
+    s.nb_at = 0x7fffffff;
+    return s;
+}
+__device__ inline void x2_dw_lockstep(X2DwLockstep &s, int mine, int tile, int tid)  // (wave-uniform)
+{
+    constexpr int DW_LAG = 6, DW_NAPS = 256;
+    // the value requested at the previous look has long landed; the wait names nb_at so that no copy of the register made before
+    // the data arrived can be what the comparison reads (round-4 advice: a stale value only mis-paces, but makes timing and traffic
+    // depend on the compiler's register copies)
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(s.nb_at) :: "memory");
+    int naps = 0;
+    while (s.sync_on && s.nb_at + DW_LAG + XW2_NST < mine) {  // (+NST: the value is one look old)
+        if (++naps > DW_NAPS) { s.sync_on = false; break; }
+        __builtin_amdgcn_s_sleep(4);
+        asm volatile("s_load_dword %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=s"(s.nb_at) : "s"(s.nb) : "memory");
+    }
+    if (s.sync_on) {
+        if (tid == 0) __hip_atomic_store(s.prog + tile, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (one more outstanding store only makes the counted waits stricter)
+        asm volatile("s_load_dword %0, %1, 0x0 glc" : "=s"(s.nb_at) : "s"(s.nb) : "memory");  // used at the next look
+    }
+}
+// The ring driver: ONE pipeline run over a split's nks k-steps.  dma_stage(ks, st) issues this wave's DMA pieces of k-step ks into ring
+// stage st (prologue: NST - 1 stages ahead); kstep(X2Int<ST>, ks) is k-step ks on ring stage ST = ks % NST — its counted wait for the
+// stage (the kernels': two stages in flight behind the one waited for), x2_dw_kstep, and inside it the pieces of k-step ks + NST - 1.
+// The loop is unrolled by NST with a look at the lockstep in front of stage 0.
+template <class KStep, class DmaStage>
+__device__ inline void x2_dw_ring(int nks, X2DwLockstep &ls, int tile, int tid, const KStep &kstep, const DmaStage &dma_stage)
+{
+    static_assert(XW2_NST == 4, "prologue and unrolling below");
+    int runs = 1;  // ONE pipeline run; the count is opaque to hipcc, which keeps the accumulators in their registers across a loop of
+    asm volatile("" : "+s"(runs));  // runs (the per-range walk's shape) and spills all 256 of them around a straight-line run
+    for (int run = 0; run < runs; ++run) {
+        dma_stage(0, 0);
+        dma_stage(1, 1);
+        dma_stage(2, 2);
+        for (int ks = 0;;) {
+            if (ks >= nks) break;
+            x2_dw_lockstep(ls, ks, tile, tid);
+            kstep(X2Int<0>{}, ks); ++ks;
+            if (ks >= nks) break;
+            kstep(X2Int<1>{}, ks); ++ks;
+            if (ks >= nks) break;
+            kstep(X2Int<2>{}, ks); ++ks;
+            if (ks >= nks) break;
+            kstep(X2Int<3>{}, ks); ++ks;
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the over-issued DMAs before the ring
+        x2_lds_barrier();                                  // is refilled / the kernel exits
+    }
+}
+// Epilogue: partial slab [split][V,H]; bias partial [split][V].  Wave tile at (v0, h0); accumulator register r of tile (qm,qn):
+// v = v0 + 32qm + (r&3) + 8(r>>2) + 4half, h = h0 + 32qn + (lane&31).  GUARD: rows / columns beyond V / H are not stored (without it
+// the column is added in 64 bits: the addresses of a row's four tiles differ by immediates).  db: column k of the selector products
+// (lanes k / 32+k) holds M tile bsel0 + 2k, k = 0 (two_b: 0, 1)
+template <bool GUARD>
+__device__ inline void x2_dw_store(const X3Args &a, int split, int v0, int h0, int lane, const f32x16 (&acc)[4][4], const f32x16 &dacc,
+                                            bool do_b, bool two_b, int bsel0)
+{
+    const int half = lane >> 5, H = a.H, V = a.V;
+    float *sw = a.slab_w + (long)split * V * H;
+    const float rw = a.dw_rescale, rb = a.db_rescale;
+#pragma unroll
+    for (int qm = 0; qm < 4; ++qm)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int v = v0 + 32 * qm + (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (!GUARD || v < V) {
+#pragma unroll
+                for (int qn = 0; qn < 4; ++qn) {
+                    const int h = h0 + 32 * qn + (lane & 31);
+                    if (!GUARD || h < H) sw[GUARD ? (long)v * H + h : (long)v * H + h0 + 32 * qn + (lane & 31)] = acc[qm][qn][r] * rw;
+                }
+            }
+        }
+    if (do_b && (lane & 31) < (two_b ? 2 : 1)) {
+        const int m = bsel0 + 2 * (lane & 31);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int v = v0 + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (!GUARD || v < V) a.slab_b[(long)split * V + v] = dacc[r] * rb;
+        }
+    }
+}
+
 // NW = waves per workgroup: 4, one wave per SIMD, wave tile 128 v x 128 h = 16 accumulator tiles.  (Two waves per SIMD with 8 tiles each
 // were measured equal, 15.5 ms both at cfg2: the kernel is bound by the bytes it stages — 32 KiB per k-step and CU at ~12.6 B/clk/CU, the
 // rate the forward's and dHidden's W streams reach — not by issue stalls.  The parameter stays in the kernel's name: profiles/, DESIGN.md.)
@@ -538,16 +750,10 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
-    const int half = lane >> 5;
     const int H = a.H, V = a.V;
     const int n_vblk = (V + 255) / 256, n_hblk = (H + 255) / 256;
     const int tiles = n_vblk * n_hblk;
-    const int total = tiles * a.n_split;
-    int id = blockIdx.x;  // XCD-aware remap: the tiles of one split share an XCD's L2
-    {
-        const int q8 = total / 8, r8 = total % 8, x = id % 8;
-        id = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + id / 8;
-    }
+    const int id = x2_dw_xcd_remap(blockIdx.x, tiles * a.n_split);
     const int tile = id % tiles, split = id / tiles;
     const int vb = tile / n_hblk, hb = tile % n_hblk;
     // this split's share [g_lo, g_hi) of the k-steps of LIVE groups, four list entries each (X3Args::grp_list, launch_x2_live; the Linear
@@ -566,15 +772,15 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
         for (int qn = 0; qn < QN; ++qn)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[qm][qn][r] = 0.f;
-    // db rides the matrix pipe as in k_dw_x3: one more MFMA per plane and k-step against a column SELECTOR of ones, for one
-    // (one h block: two) of the wave's M tiles, into a 17th accumulator tile held in VGPRs
-    const bool do_b = hb < 2;  // workgroup-uniform
+    // db (x2_dw_bias_mfma): the waves of h blocks 0 and 1 each take one of their wm half's four M tiles; one h block: two each
+    X2DwBias bias;
+    bias.do_b = hb < 2;  // workgroup-uniform
     const int bsel0 = n_hblk >= 2 ? (hb & 1) * 2 + wn : wn;
-    const bool two_b = n_hblk < 2;  // one h block: each wave takes two tiles, bsel0 and bsel0 + 2
+    bias.two_b = n_hblk < 2;  // each wave takes two tiles, bsel0 and bsel0 + 2
     f32x16 dacc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) dacc[r] = 0.f;
-    const unsigned sel0 = (lane & 31) == 0 ? 0x3c003c00u : 0u, sel1 = (lane & 31) == 1 ? 0x3c003c00u : 0u;  // fp16 ones
+    bias.sel0 = (lane & 31) == 0 ? 0x3c003c00u : 0u; bias.sel1 = (lane & 31) == 1 ? 0x3c003c00u : 0u;  // fp16 ones
 
     if (g_hi > g_lo) {
         // ---- DMA source of this wave's operand tile
@@ -616,45 +822,30 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
         // the k loop it is issued in front of the counted vmcnt wait it shares its latency with.  Past the split's end the read-ahead
         // fetches the next split's entries (real rows, never multiplied) or the list's padding entries (zero rows).
         const int *lptr = a.grp_list + 4L * g_lo;
-        // ---- transposed fragment reads.  Fragment of 32-column tile m: lane (g = lane>>4, q = (lane&15)>>2,
-        // p = lane&3) reads rows 8(g>>1) + 4sec + q at chunk 4m + 2(g&1) + (p>>1), +8(p&1) bytes, sec = 0,1.
-        const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3, hh = g >> 1;
+        // ---- fragment bases: A from operand tile wm; this wave's h tiles, columns 128 wn + 32 m of the 256, from operand tile 2 + wn;
+        // db: the M tile(s) this wave sums (bsel0, and bsel0 + 2 with one h block)
         const int lds0 = (int)(size_t)(lds_vptr)s_ring;
         int abase[4][2], bbase[QN][2];
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int sec = 0; sec < 2; ++sec) {
-                const int row = 8 * hh + 4 * sec + q;
-                const int swz = ((row & 3) << 2) | ((row >> 2) & 3);
-                const int ch = 4 * m + 2 * (g & 1) + (pp >> 1);
-                abase[m][sec] = lds0 + wm * XW2_TILE + 256 * row + 16 * (ch ^ swz) + 8 * (pp & 1);
-                // this wave's h tiles: columns 32 QN wn + 32 m of the 256 = operand tile 2 + (col >> 7), tile (col & 127) / 32
-                const int col = 32 * QN * wn + 32 * m;
-                const int chb = 4 * ((col & 127) >> 5) + 2 * (g & 1) + (pp >> 1);
-                bbase[m][sec] = lds0 + (2 + (col >> 7)) * XW2_TILE + 256 * row + 16 * (chb ^ swz) + 8 * (pp & 1);
+                abase[m][sec] = x2_dw_frag_addr(lds0, wm, m, sec, lane);
+                bbase[m][sec] = x2_dw_frag_addr(lds0, 2 + wn, m, sec, lane);
             }
-        int sbase[2][2];  // db: fragment bases of the M tile(s) this wave sums (bsel0, and bsel0 + 2 with one h block)
 #pragma unroll
         for (int k = 0; k < 2; ++k)
 #pragma unroll
-            for (int sec = 0; sec < 2; ++sec) {
-                const int m = (bsel0 + 2 * k) & 3;
-                const int row = 8 * hh + 4 * sec + q;
-                const int ch = 4 * m + 2 * (g & 1) + (pp >> 1);
-                const int swz = ((row & 3) << 2) | ((row >> 2) & 3);
-                sbase[k][sec] = lds0 + wm * XW2_TILE + 256 * row + 16 * (ch ^ swz) + 8 * (pp & 1);
-            }
+            for (int sec = 0; sec < 2; ++sec) bias.sbase[k][sec] = x2_dw_frag_addr(lds0, wm, (bsel0 + 2 * k) & 3, sec, lane);
 
-        // one k-step on ring stage ST (compile-time: every LDS offset is an immediate)
-        auto kstep = [&](auto st_c, long ks, f32x16 &dacc) {
+        auto kstep = [&](auto st_c, long ks) {
             constexpr int ST = decltype(st_c)::value, DST = (ST + XW2_NST - 1) % XW2_NST;
-            // stage ks landed (the 8 (NST - 2) younger pieces of the stages after it may still fly); every wave is past its reads of
-            // stage ks-1, whose ring stage the DMAs below refill.  In front of the wait: the four list entries of stage ks + NST - 1
+            // stage ks landed (the 8 (NST - 2) younger pieces of the stages after it may still fly).  In front of the wait: the four list
+            // entries of stage ks + NST - 1
             i32x4 ent;
             const int *ep = lptr + 4 * (ks + (XW2_NST - 1));
-            if (ND * (XW2_NST - 2) == 16) XW2_LOAD_ENT4(ent, ep, RNNT_VMCNT(16) "\n\t");
-            else XW2_LOAD_ENT4(ent, ep, RNNT_VMCNT(8) "\n\t");
+            static_assert(ND * (XW2_NST - 2) == 16, "the counted wait");
+            XW2_LOAD_ENT4(ent, ep, RNNT_VMCNT(16) "\n\t");
             // piece n of this wave's share of stage ks+NST-1 -> ring stage DST: plane n>>2, ring rows 4(n&3).. <- the
             // four rows of entry n&3 as a raw buffer (wave-uniform base, built here between the MFMAs; the per-lane part is the 32-bit soff)
             auto dma_piece = [&](auto n_c) {
@@ -663,74 +854,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
                                                          (lds_vptr)(s_ring + otile * XW2_TILE + DST * XW2_STAGE + p * XW2_PLANE),
                                                          16, soff[i], 0, imm, 0);
             };
-            // 8 transposed reads of plane P of the A / B operand (inline asm: hipcc guards every LDS read it can see behind
-            // an LDS-DMA with vmcnt(0)); results are used only after X2_LANDED named them
-            auto reads = [&](X2Frag &f, const auto &base, auto p_c, auto nt_c) {
-                constexpr int off = ST * XW2_STAGE + decltype(p_c)::value * XW2_PLANE;
-#pragma unroll
-                for (int m = 0; m < decltype(nt_c)::value; ++m) {
-                    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.lo[m]) : "v"(base[m][0]), "n"(off));
-                    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.hi[m]) : "v"(base[m][1]), "n"(off));
-                }
-            };
-            // 16 MFMAs of one product with DMA pieces N0 .. N0+CNT-1 threaded through them
-            auto product = [&](const X2Frag &fa_, const X2Frag &fb_, auto n0_c, auto cnt_c) {
-                constexpr int N0 = decltype(n0_c)::value, CNT = decltype(cnt_c)::value;
-                u32x4 fa[4], fb[QN];
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    fa[m] = u32x4{fa_.lo[m][0], fa_.lo[m][1], fa_.hi[m][0], fa_.hi[m][1]};
-                    fb[m] = u32x4{fb_.lo[m][0], fb_.lo[m][1], fb_.hi[m][0], fb_.hi[m][1]};
-                }
-#pragma unroll
-                for (int qm = 0; qm < 4; ++qm) {
-                    if (live_n) {
-#pragma unroll
-                        for (int qn = 0; qn < QN; ++qn) acc[qm][qn] = x2_mfma(fa[qm], fb[qn], acc[qm][qn]);
-                    }
-                    if (qm == 0 && CNT >= 1) dma_piece(X2Int<N0>{});
-                    if (qm == 1 && CNT >= 2) dma_piece(X2Int<N0 + (CNT >= 2 ? 1 : 0)>{});
-                    if (qm == 3 && CNT == 3) dma_piece(X2Int<N0 + (CNT == 3 ? 2 : 0)>{});
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            };
-            auto bias_read = [&](u32x2 &lo, u32x2 &hi, auto p_c, int k) {
-                constexpr int off = ST * XW2_STAGE + decltype(p_c)::value * XW2_PLANE;
-                const int b0 = sbase[k][0], b1 = sbase[k][1];  // (locals: asm operands cannot name a capture of the enclosing generic lambda)
-                asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(b0), "n"(off));
-                asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(b1), "n"(off));
-            };
-            auto bias_mfma = [&](u32x2 &lo, u32x2 &hi, f32x16 &dacc, int k) {
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo), "+v"(hi) :: "memory");
-                const u32x4 fa = {lo[0], lo[1], hi[0], hi[1]};
-                const unsigned sv = k ? sel1 : sel0;
-                const u32x4 sel = {sv, sv, sv, sv};
-                // accumulator in VGPRs, spelled as asm (left to hipcc the 17th tile is shuttled through the full AGPR file)
-                asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(dacc) : "v"(fa), "v"(sel));
-            };
-            x2_lds_barrier();
-            X2Frag Ah, Bh, Am, Bm;
-            u32x2 dl[2], dh[2];
-            reads(Ah, abase, X2Int<0>{}, X2Int<4>{});
-            reads(Bh, bbase, X2Int<0>{}, X2Int<QN>{});
-            reads(Am, abase, X2Int<1>{}, X2Int<4>{});
-            X2_LANDED(Ah, 8);
-            X2_LANDED(Bh, 8);
-            // DMA pieces of the k-step: 3 + 3 + 2
-            product(Ah, Bh, X2Int<0>{}, X2Int<3>{});
-            reads(Bm, bbase, X2Int<1>{}, X2Int<QN>{});
-            X2_LANDED(Am, 8);
-            product(Am, Bh, X2Int<3>{}, X2Int<3>{});
-            X2_LANDED(Bm, 0);
-            if (do_b) { bias_read(dl[0], dh[0], X2Int<0>{}, 0); bias_read(dl[1], dh[1], X2Int<1>{}, 0); }
-            product(Ah, Bm, X2Int<6>{}, X2Int<2>{});
-            if (do_b) {
-                bias_mfma(dl[0], dh[0], dacc, 0); bias_mfma(dl[1], dh[1], dacc, 0);
-                if (two_b) {  // one h block: the wave's second tile (column 1 of the selector product), H <= 256 only
-                    bias_read(dl[0], dh[0], X2Int<0>{}, 1); bias_read(dl[1], dh[1], X2Int<1>{}, 1);
-                    bias_mfma(dl[0], dh[0], dacc, 1); bias_mfma(dl[1], dh[1], dacc, 1);
-                }
-            }
+            x2_dw_kstep<ST, 3, 3, 2>(acc, dacc, abase, bbase, bias, live_n, dma_piece);
         };
         auto dma_stage = [&](long ks, int st) {  // pipeline prologue: this wave's pieces of stage ks
             i32x4 ent;
@@ -747,88 +871,12 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
                 if (i == 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d, 16, soff[i], 0, 3072, 0);
             }
         };
-
-        // Soft lockstep of the tiles of a split (k_dw_bf16's, round 3).  They walk the same k-steps and share every operand byte
-        // through their XCD's L2 (G between the h blocks, hidden between the v blocks); nothing else holds them together, and at
-        // this kernel's pace a tile that falls behind finds its lines evicted and becomes its own HBM stream — counted without
-        // it: 83 GB fetched for 39.5 GB of operands (profiles/r04_f16x2_hbm_traffic_pmc.txt, first pass).  Every NST k-steps a
-        // tile publishes its k-step count and looks at its right-hand neighbour's in the ring of the split's tiles (one coherent
-        // scalar load, issued a look before its value is used); a tile more than DW_LAG k-steps ahead of that neighbour naps.
-        // Bounded: after DW_NAPS naps without the neighbour catching up (a partner that is not resident) the tile stops looking,
-        // so every wave reaches the end whatever the others do.
-        constexpr int DW_LAG = 6, DW_NAPS = 256;
-        int *prog = a.dw_prog ? a.dw_prog + split * 16 : nullptr;
-        bool sync_on = prog != nullptr && tiles > 1 && tiles <= 16;
-        const int *nb = prog ? prog + (tile + 1 < tiles ? tile + 1 : 0) : nullptr;  // the neighbour's word
-        int nb_at = 0x7fffffff;  // the neighbour's k-step count as of the last look
-        auto lockstep = [&](int mine) {  // (wave-uniform)
-            // the value requested at the previous look has long landed; the wait names nb_at so that no copy of the register made before
-            // the data arrived can be what the comparison reads (round-4 advice: a stale value only mis-paces, but makes timing and traffic
-            // depend on the compiler's register copies)
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(nb_at) :: "memory");
-            int naps = 0;
-            while (sync_on && nb_at + DW_LAG + XW2_NST < mine) {  // (+NST: the value is one look old)
-                if (++naps > DW_NAPS) { sync_on = false; break; }
-                __builtin_amdgcn_s_sleep(4);
-                asm volatile("s_load_dword %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=s"(nb_at) : "s"(nb) : "memory");
-            }
-            if (sync_on) {
-                if (tid == 0) __hip_atomic_store(prog + tile, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (one more outstanding store only makes the counted waits stricter)
-                asm volatile("s_load_dword %0, %1, 0x0 glc" : "=s"(nb_at) : "s"(nb) : "memory");  // used at the next look
-            }
-        };
-        int runs = 1;  // ONE pipeline run; the count is opaque to hipcc, which keeps the accumulators in their registers across a loop of
-        asm volatile("" : "+s"(runs));  // runs (the per-range walk's shape) and spills all 256 of them around a straight-line run
-        for (int run = 0; run < runs; ++run) {
-            const int nks = g_hi - g_lo;  // workgroup-uniform
-            dma_stage(0, 0);
-            dma_stage(1, 1);
-            if (XW2_NST == 4) dma_stage(2, 2);
-            for (int ks = 0;;) {  // the ring stage of a k-step is ks % NST: unrolled by NST
-                if (ks >= nks) break;
-                lockstep(ks);
-                kstep(X2Int<0>{}, ks, dacc); ++ks;
-                if (ks >= nks) break;
-                kstep(X2Int<1>{}, ks, dacc); ++ks;
-                if (ks >= nks) break;
-                kstep(X2Int<2>{}, ks, dacc); ++ks;
-                if (XW2_NST == 4) {
-                    if (ks >= nks) break;
-                    kstep(X2Int<3 % XW2_NST>{}, ks, dacc); ++ks;
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the over-issued DMAs before the ring
-            x2_lds_barrier();                                  // is refilled / the kernel exits
-        }
+        X2DwLockstep ls = x2_dw_lockstep_init(a.dw_prog, split, tile, tiles);
+        x2_dw_ring(g_hi - g_lo, ls, tile, tid, kstep, dma_stage);
     }
 
-    // ---- epilogue: partial slab [split][V,H]; bias partial [split][V].  Accumulator register r of tile
-    // (qm,qn): v = v0 + 32qm + (r&3) + 8(r>>2) + 4half, h = h0 + 32qn + (lane&31).
     X2_CLOCK_STAMP(128 + 106);
-    const int v0 = vb * 256 + wm * 128, h0 = hb * 256 + wn * 32 * QN;
-    float *sw = a.slab_w + (long)split * V * H;
-    const float rw = a.dw_rescale, rb = a.db_rescale;
-#pragma unroll
-    for (int qm = 0; qm < 4; ++qm)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int v = v0 + 32 * qm + (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (v < V) {
-#pragma unroll
-                for (int qn = 0; qn < QN; ++qn) {
-                    const int h = h0 + 32 * qn + (lane & 31);
-                    if (h < H) sw[(long)v * H + h] = acc[qm][qn][r] * rw;
-                }
-            }
-        }
-    if (do_b && (lane & 31) < (two_b ? 2 : 1)) {  // column k of the selector products: lanes k / 32+k store
-        const int m = bsel0 + 2 * (lane & 31);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int v = v0 + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (v < V) a.slab_b[(long)split * V + v] = dacc[r] * rb;
-        }
-    }
+    x2_dw_store<true>(a, split, vb * 256 + wm * 128, hb * 256 + wn * 32 * QN, lane, acc, dacc, bias.do_b, bias.two_b, bsel0);
 }
 
 
@@ -841,10 +889,10 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
 // k-step: every wave of every workgroup works) — beside the ordinary 256 x 256 tiles of the whole h blocks: (V/256) (H/256) + V/512 tiles
 // per split (config 4: 10 tiles x 25 splits).  A tall tile stages 4 G operand tiles (one per wave: the wave's own A rows) and 1 hidden
 // operand tile (its 8 DMA pieces per stage shared out two per wave): 40 KiB per k-step instead of 32, a 5-tile ring = 160 KiB of LDS.
-// The kernel's two tile kinds are two complete copies of the loop behind ONE workgroup-uniform branch (a branch inside the k loop would split
-// the hand-placed MFMA / DMA / read schedule into scheduling regions); everything else — ring stage layout, source-side swizzle, transposed
-// reads, the three products, db on the matrix pipe (whole h blocks 0 and 1 only), soft lockstep, slab epilogue — is k_dw_x2<4>'s,
-// statement for statement, its walk of the live k-step list (X3Args::ks_list, one pipeline run per split) included.
+// The two tile kinds are two instantiations of the body behind ONE workgroup-uniform branch (a branch inside the k loop would split the
+// hand-placed MFMA / DMA / read schedule into scheduling regions).  Everything but the geometry, the DMA sources (tall: 10 pieces per wave
+// and stage, threaded 4 + 3 + 3) and the walk of the live k-step list (X3Args::ks_list: one entry per k-step, one buffer resource per
+// plane) is "The dW k-step pipeline" above, shared with k_dw_x2<4>; db from whole h blocks 0 and 1 only.
 // ---------------------------------------------------------------------------------------
 int x2_dw_mixed_ok(int H, int V) { return H % 256 == 128 && H >= 640 && V % 512 == 0; }
 int x2_dw_tiles(int H, int V) { return x2_dw_mixed_ok(H, V) ? (V / 256) * (H / 256) + V / 512 : ((V + 255) / 256) * ((H + 255) / 256); }
@@ -854,22 +902,15 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
     extern __shared__ __attribute__((aligned(1024))) char s_ring[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int half = lane >> 5;
     const int H = a.H, V = a.V;
     const int n_vblk = V / 256, n_fh = H / 256;  // whole h blocks; the odd block = columns 256 n_fh .. +127
     const int n_full = n_vblk * n_fh, tiles = n_full + n_vblk / 2;
-    const int total = tiles * a.n_split;
-    int id = blockIdx.x;  // XCD-aware remap: the tiles of one split share an XCD's L2
-    {
-        const int q8 = total / 8, r8 = total % 8, x = id % 8;
-        id = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + id / 8;
-    }
+    const int id = x2_dw_xcd_remap(blockIdx.x, tiles * a.n_split);
     const int tile = id % tiles, split = id / tiles;
     // this split's share [g_lo, g_hi) of the live k-steps (k_dw_x2's walk: X3Args::ks_list)
     const long nlive = __builtin_amdgcn_readfirstlane(a.live_stats[0]);
     const int g_lo = __builtin_amdgcn_readfirstlane((int)(nlive * split / a.n_split));
     const int g_hi = __builtin_amdgcn_readfirstlane((int)(nlive * (split + 1) / a.n_split));
-    const unsigned sel0 = (lane & 31) == 0 ? 0x3c003c00u : 0u;  // fp16 ones in column 0 of the selector fragment
 
     auto body = [&](auto tall_c) {
         constexpr bool TALL = decltype(tall_c)::value != 0;
@@ -887,11 +928,14 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[qm][qn][r] = 0.f;
         // db as in k_dw_x2<4>: the waves of the whole-block tiles of h blocks 0 and 1 each take one of their wm half's four M tiles
-        const bool do_b = !TALL && hb < 2;  // workgroup-uniform
+        X2DwBias bias;
+        bias.do_b = !TALL && hb < 2;  // workgroup-uniform
+        bias.two_b = false;
         const int bsel0 = (hb & 1) * 2 + wn;
         f32x16 dacc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) dacc[r] = 0.f;
+        bias.sel0 = (lane & 31) == 0 ? 0x3c003c00u : 0u; bias.sel1 = 0u;  // fp16 ones in column 0 of the selector fragment
 
         if (g_hi > g_lo) {
             // ---- DMA sources.  Own operand tile (8 pieces per stage): whole-block tile: waves 0, 1 the G tile's 128-column halves, waves 2, 3
@@ -928,29 +972,23 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
                 xoff[k] = (int)((4 * i + (lane >> 4)) * xstride) + 16 * jg;
             }
             const int *lptr = a.ks_list + g_lo;  // k-step ks multiplies the 16 rows of k-step lptr[ks] (k_dw_x2's walk)
-            // ---- transposed fragment reads (k_dw_x2's): A from operand tile wm (tall: wave), B from the hidden tile(s)
-            const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3, hh = g >> 1;
+            // ---- fragment bases: A from operand tile wm (tall: wave), the tile this wave stages when TALL; B from the hidden tile(s)
             const int lds0 = (int)(size_t)(lds_vptr)s_ring;
-            const int a_tile = TALL ? wave : wm;            // operand tile holding this wave's A rows
-            const int own_tile = TALL ? wave : wave;        // operand tile this wave stages
-            int abase[4][2], bbase[4][2], sbase[2];
+            const int own_tile = wave;  // operand tile this wave stages
+            int abase[4][2], bbase[4][2];
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
                 for (int sec = 0; sec < 2; ++sec) {
-                    const int row = 8 * hh + 4 * sec + q;
-                    const int swz = ((row & 3) << 2) | ((row >> 2) & 3);
-                    const int ch = 4 * m + 2 * (g & 1) + (pp >> 1);
-                    abase[m][sec] = lds0 + a_tile * XW2_TILE + 256 * row + 16 * (ch ^ swz) + 8 * (pp & 1);
-                    bbase[m][sec] = lds0 + (TALL ? 4 : 2 + wn) * XW2_TILE + 256 * row + 16 * (ch ^ swz) + 8 * (pp & 1);
-                    if (m == (bsel0 & 3)) sbase[sec] = abase[m][sec];
+                    abase[m][sec] = x2_dw_frag_addr(lds0, wm, m, sec, lane);
+                    bbase[m][sec] = x2_dw_frag_addr(lds0, TALL ? 4 : 2 + wn, m, sec, lane);
+                    bias.sbase[1][sec] = bias.sbase[0][sec] = x2_dw_frag_addr(lds0, wm, bsel0 & 3, sec, lane);
                 }
 
-            auto kstep = [&](auto st_c, long ks, f32x16 &dacc) {
+            auto kstep = [&](auto st_c, long ks) {
                 constexpr int ST = decltype(st_c)::value, DST = (ST + XW2_NST - 1) % XW2_NST;
-                // stage ks landed (the ND (NST - 2) younger pieces of the stages after it may still fly); every wave is past its reads of
-                // stage ks-1, whose ring stage the DMAs below refill.  In front of the wait: the list entry of stage ks + NST - 1 (k_dw_x2's)
-                static_assert(XW2_NST == 4, "counted waits below: two stages in flight behind the one waited for");
+                // stage ks landed (the ND (NST - 2) younger pieces of the stages after it may still fly: ND = 8, tall 10).  In front of the
+                // wait: the list entry of stage ks + NST - 1 (k_dw_x2's)
                 int ent;
                 const int *ep = lptr + ks + (XW2_NST - 1);
                 if (TALL) asm volatile("s_load_dword %0, %1, 0x0\n\t" RNNT_VMCNT(20) "\n\ts_waitcnt lgkmcnt(0)" : "=s"(ent) : "s"(ep) : "memory");
@@ -974,62 +1012,7 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
                                                                  16, xoff[k], 0, 0, 0);
                     }
                 };
-                auto reads = [&](X2Frag &f, const auto &base, auto p_c) {
-                    constexpr int off = ST * XW2_STAGE + decltype(p_c)::value * XW2_PLANE;
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) {
-                        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.lo[m]) : "v"(base[m][0]), "n"(off));
-                        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.hi[m]) : "v"(base[m][1]), "n"(off));
-                    }
-                };
-                // 16 MFMAs of one product with DMA pieces N0 .. N0+CNT-1 threaded through them (CNT <= 4: one per row of wave tiles)
-                auto product = [&](const X2Frag &fa_, const X2Frag &fb_, auto n0_c, auto cnt_c) {
-                    constexpr int N0 = decltype(n0_c)::value, CNT = decltype(cnt_c)::value;
-                    u32x4 fa[4], fb[4];
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) {
-                        fa[m] = u32x4{fa_.lo[m][0], fa_.lo[m][1], fa_.hi[m][0], fa_.hi[m][1]};
-                        fb[m] = u32x4{fb_.lo[m][0], fb_.lo[m][1], fb_.hi[m][0], fb_.hi[m][1]};
-                    }
-#pragma unroll
-                    for (int qm = 0; qm < 4; ++qm) {
-#pragma unroll
-                        for (int qn = 0; qn < 4; ++qn) acc[qm][qn] = x2_mfma(fa[qm], fb[qn], acc[qm][qn]);
-                        if (qm == 0 && CNT >= 1) dma_piece(X2Int<N0>{});
-                        if (qm == 1 && CNT >= 2) dma_piece(X2Int<N0 + (CNT >= 2 ? 1 : 0)>{});
-                        if (qm == 2 && CNT >= 4) dma_piece(X2Int<N0 + (CNT >= 4 ? 2 : 0)>{});
-                        if (qm == 3 && CNT >= 3) dma_piece(X2Int<N0 + (CNT >= 3 ? CNT - 1 : 0)>{});
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                };
-                auto bias_read = [&](u32x2 &lo, u32x2 &hi, auto p_c) {
-                    constexpr int off = ST * XW2_STAGE + decltype(p_c)::value * XW2_PLANE;
-                    const int b0 = sbase[0], b1 = sbase[1];
-                    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(b0), "n"(off));
-                    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(b1), "n"(off));
-                };
-                auto bias_mfma = [&](u32x2 &lo, u32x2 &hi, f32x16 &dacc) {
-                    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo), "+v"(hi) :: "memory");
-                    const u32x4 fa = {lo[0], lo[1], hi[0], hi[1]};
-                    const u32x4 sel = {sel0, sel0, sel0, sel0};
-                    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(dacc) : "v"(fa), "v"(sel));
-                };
-                x2_lds_barrier();
-                X2Frag Ah, Bh, Am, Bm;
-                u32x2 dl[2], dh[2];
-                reads(Ah, abase, X2Int<0>{});
-                reads(Bh, bbase, X2Int<0>{});
-                reads(Am, abase, X2Int<1>{});
-                X2_LANDED(Ah, 8);
-                X2_LANDED(Bh, 8);
-                product(Ah, Bh, X2Int<0>{}, X2Int<(TALL ? 4 : 3)>{});
-                reads(Bm, bbase, X2Int<1>{});
-                X2_LANDED(Am, 8);
-                product(Am, Bh, X2Int<(TALL ? 4 : 3)>{}, X2Int<3>{});
-                X2_LANDED(Bm, 0);
-                if (do_b) { bias_read(dl[0], dh[0], X2Int<0>{}); bias_read(dl[1], dh[1], X2Int<1>{}); }
-                product(Ah, Bm, X2Int<(TALL ? 7 : 6)>{}, X2Int<(TALL ? 3 : 2)>{});
-                if (do_b) { bias_mfma(dl[0], dh[0], dacc); bias_mfma(dl[1], dh[1], dacc); }
+                x2_dw_kstep<ST, (TALL ? 4 : 3), 3, (TALL ? 3 : 2)>(acc, dacc, abase, bbase, bias, true, dma_piece);
             };
             auto dma_stage = [&](long ks, int st) {  // pipeline prologue: this wave's pieces of stage ks
                 int ent;
@@ -1055,64 +1038,11 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
                                                                  16, xoff[k], 0, 0, 0);
                 }
             };
-
-            // soft lockstep of the tiles of a split (k_dw_x2's; tall and whole-block tiles walk the same k-steps and share G through L2)
-            constexpr int DW_LAG = 6, DW_NAPS = 256;
-            int *prog = a.dw_prog ? a.dw_prog + split * 16 : nullptr;
-            bool sync_on = prog != nullptr && tiles > 1 && tiles <= 16;
-            const int *nb = prog ? prog + (tile + 1 < tiles ? tile + 1 : 0) : nullptr;
-            int nb_at = 0x7fffffff;
-            auto lockstep = [&](int mine) {  // (wave-uniform)
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(nb_at) :: "memory");
-                int naps = 0;
-                while (sync_on && nb_at + DW_LAG + XW2_NST < mine) {
-                    if (++naps > DW_NAPS) { sync_on = false; break; }
-                    __builtin_amdgcn_s_sleep(4);
-                    asm volatile("s_load_dword %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=s"(nb_at) : "s"(nb) : "memory");
-                }
-                if (sync_on) {
-                    if (tid == 0) __hip_atomic_store(prog + tile, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_load_dword %0, %1, 0x0 glc" : "=s"(nb_at) : "s"(nb) : "memory");
-                }
-            };
-            int runs = 1;  // ONE pipeline run per split (the opaque count: see k_dw_x2)
-            asm volatile("" : "+s"(runs));
-            for (int run = 0; run < runs; ++run) {
-                const int nks = g_hi - g_lo;  // workgroup-uniform
-                dma_stage(0, 0);
-                dma_stage(1, 1);
-                dma_stage(2, 2);
-                for (int ks = 0;;) {  // the ring stage of a k-step is ks % 4: unrolled by 4
-                    if (ks >= nks) break;
-                    lockstep(ks);
-                    kstep(X2Int<0>{}, ks, dacc); ++ks;
-                    if (ks >= nks) break;
-                    kstep(X2Int<1>{}, ks, dacc); ++ks;
-                    if (ks >= nks) break;
-                    kstep(X2Int<2>{}, ks, dacc); ++ks;
-                    if (ks >= nks) break;
-                    kstep(X2Int<3>{}, ks, dacc); ++ks;
-                }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the over-issued DMAs before the ring
-                x2_lds_barrier();                                  // is refilled / the kernel exits
-            }
+            // (tall and whole-block tiles walk the same k-steps and share G through L2: one lockstep ring)
+            X2DwLockstep ls = x2_dw_lockstep_init(a.dw_prog, split, tile, tiles);
+            x2_dw_ring(g_hi - g_lo, ls, tile, tid, kstep, dma_stage);
         }
-
-        // ---- epilogue: partial slab [split][V,H]; bias partial [split][V] (k_dw_x2's)
-        float *sw = a.slab_w + (long)split * V * H;
-        const float rw = a.dw_rescale, rb = a.db_rescale;
-#pragma unroll
-        for (int qm = 0; qm < 4; ++qm)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int v = v0 + 32 * qm + (r & 3) + 8 * (r >> 2) + 4 * half;
-#pragma unroll
-                for (int qn = 0; qn < 4; ++qn) sw[(long)v * H + h0 + 32 * qn + (lane & 31)] = acc[qm][qn][r] * rw;  // (V % 512 == 0, H % 128 == 0: every column exists)
-            }
-        if (do_b && (lane & 31) == 0) {  // column 0 of the selector products: lanes 0 / 32 store
-#pragma unroll
-            for (int r = 0; r < 16; ++r) a.slab_b[(long)split * V + v0 + 32 * bsel0 + (r & 3) + 8 * (r >> 2) + 4 * half] = dacc[r] * rb;
-        }
+        x2_dw_store<false>(a, split, v0, h0, lane, acc, dacc, bias.do_b, false, bsel0);  // (V % 512 == 0, H % 128 == 0: every row and column exists)
     };
     if (tile >= n_full) body(X2Int<1>{});  // (workgroup-uniform)
     else body(X2Int<0>{});
@@ -1197,9 +1127,6 @@ size_t x2_wpack_dh_bytes(int H, int V) { return (size_t)((H + 511) / 512) * (V /
 // grid: one workgroup per tile, 1-D; workgroup g runs tile tile_list[g] = [b][tt][ub] (the live tiles, ascending) and returns at once when
 // g >= live_stats[2].  Requires V % 128 == 0, H % 128 == 0.
 // ---------------------------------------------------------------------------------------
-#define XG2_BT 8
-#define XG2_BU 16
-static_assert(XG2_BT == XG2_BT_ && XG2_BU == XG2_BU_, "dHidden tile");
 #define XG2_WSLOT 32768   // one k-step of W: 2 planes x 16 tiles x 1 KiB
 #define XG2_XSLOT 8192    // one k-step of G fragments: 4 M tiles x 2 planes x 1 KiB
 #define XG2_NW 3          // W ring slots: the DMAs of k-step c+2 are issued during k-step c (as in k_joint_fwd_x2)
@@ -1771,7 +1698,7 @@ __global__ __launch_bounds__(64 * XZ2_WG_WAVES) void k_x2_dead_rows(X3Args a, in
                 const long bt = c / a.U1;
                 const int t = (int)(bt % a.T);
                 const long b = bt / a.T;
-                dead = a.tile_live[(b * ntt + t / XG2_BT_) * nub + u / XG2_BU_] == 0;
+                dead = a.tile_live[(b * ntt + t / XG2_BT) * nub + u / XG2_BU] == 0;
             }
         }
         unsigned long long m = __ballot(dead);  // (wave-uniform) bit l: row (l & (1 << sh) - 1) of entry l >> sh belongs to a tile that is not live
@@ -1786,7 +1713,7 @@ void launch_x2_dead_rows(const X3Args &a, hipStream_t st)
 {
     const long rounds = ((long)a.B * a.T * a.U1 + 63) / 64;  // wave rounds of 64 rows: the most the walk can hold
     const long want = (rounds + XZ2_WG_WAVES - 1) / XZ2_WG_WAVES, cap = (long)(a.n_cu > 0 ? a.n_cu : 256) * 8;
-    const int ntt = (a.T + XG2_BT_ - 1) / XG2_BT_;
+    const int ntt = (a.T + XG2_BT - 1) / XG2_BT;
     hipLaunchKernelGGL(k_x2_dead_rows, dim3((unsigned)(want < cap ? want : cap)), dim3(64 * XZ2_WG_WAVES), 0, st, a, ntt, a.n_ublk16);
 }
 
