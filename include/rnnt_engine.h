@@ -387,6 +387,54 @@ int rnnt_engine_conv_predictor_bwd(const int64_t *ids, int B, int U1, int S, int
                                    void *stream);
 
 /*
+ * LSTMPredictor forward / backward / stateful step: reference rnnt/predictor.py:11-186 — embedding, LayerNorm,
+ * L layer-normalised LSTM layers (gates = x2g(x_t) + p2g(h_{t-1}), g_norm over all 4 Hd gates of a row, gate order input /
+ * forget / cell / output, c = c_norm(f c + i g) — the NORMALISED cell continues —, h = o tanh(c)), dropout after every layer, Linear,
+ * LayerNorm — on rows (b,u).  Exact fp32 products.  All pointers fp32 device pointers, 16-byte aligned, except `p->layers` / `g->layers`:
+ * HOST arrays of L structs.  Feature test: the symbols below (the ABI version stays 4).
+ *   ids [B,U1] int64; out [B,U1,O]; S symbols, E embedding width (layer 0's input), Hd hidden width, O output width;
+ *   layer_norm != 0: g_norm / c_norm present and x2g has no bias (x2g_b NULL); 0: no norms (their pointers NULL), x2g_b present;
+ *   state_in / state_out [L][2][B][Hd] (h then c of each layer); state_in NULL = zeros; state_out = the state after step U1-1 (h before
+ *   dropout); every row runs all U1 steps.  U1 = 1 with a state is the decode step.
+ *   keep [L][B,U1,Hd] bytes: dropout keep masks drawn by the caller (NULL = eval mode), kept values x 1/(1-dropout_p);
+ *   eps_in / eps_lstm / eps_out: input_layer_norm's, the LSTM layers' and output_layer_norm's eps;
+ *   `saved` (rnnt_engine_lstm_predictor_saved_bytes): what the backward of the SAME call reads; NULL = inference, nothing is kept;
+ *   `ws` (rnnt_engine_lstm_predictor_workspace_bytes, backward = 0 for _fwd, 1 for _bwd): scratch, free after the call's work ran;
+ *   `g`: where each parameter's gradient is written (the parameters' field order; overwritten, not accumulated).  There is no
+ *   gradient through the state.
+ * Two launches per time step and layer (the recurrent GEMM and one row kernel), no workgroup waits on another; no atomics, every
+ * reduction in a fixed order: results are bitwise reproducible.  Every argument is checked before anything is enqueued:
+ * RNNT_ERR_INVALID_ARG (null pointers, non-positive dims, dropout_p outside [0,1)), RNNT_ERR_UNSUPPORTED (E % 4, Hd % 4 or O % 4
+ * non-zero, Hd > 1024, E > 2048, L > 8), RNNT_ERR_WORKSPACE (short saved / ws).
+ */
+typedef struct rnnt_lstm_layer_params {
+    const float *x2g_w;               /* [4Hd,in]  lstm_layers.l.x2g.weight (in = E for layer 0, else Hd) */
+    const float *x2g_b;               /* [4Hd]     lstm_layers.l.x2g.bias; NULL with layer norm           */
+    const float *p2g_w;               /* [4Hd,Hd]  lstm_layers.l.p2g.weight                               */
+    const float *g_norm_w, *g_norm_b; /* [4Hd]     lstm_layers.l.g_norm.*; NULL without layer norm        */
+    const float *c_norm_w, *c_norm_b; /* [Hd]      lstm_layers.l.c_norm.*; NULL without layer norm        */
+} rnnt_lstm_layer_params;
+typedef struct rnnt_lstm_predictor_params {
+    const float *embedding;               /* [S,E]       embedding.weight      */
+    const float *ln_in_w, *ln_in_b;       /* [E]         input_layer_norm.*    */
+    const float *linear_w, *linear_b;     /* [O,Hd], [O] linear.*              */
+    const float *ln_out_w, *ln_out_b;     /* [O]         output_layer_norm.*   */
+    const rnnt_lstm_layer_params *layers; /* host array of L                   */
+} rnnt_lstm_predictor_params;
+
+int rnnt_engine_lstm_predictor_saved_bytes(int B, int U1, int S, int E, int Hd, int O, int L, int layer_norm, size_t *out);
+int rnnt_engine_lstm_predictor_workspace_bytes(int B, int U1, int S, int E, int Hd, int O, int L, int layer_norm, int backward,
+                                               size_t *out);
+int rnnt_engine_lstm_predictor_fwd(const int64_t *ids, int B, int U1, int S, int E, int Hd, int O, int L, int layer_norm,
+                                   const rnnt_lstm_predictor_params *p, const float *state_in, const uint8_t *keep,
+                                   float dropout_p, float eps_in, float eps_lstm, float eps_out, float *out, float *state_out,
+                                   void *saved, size_t saved_bytes, void *ws, size_t ws_bytes, void *stream);
+int rnnt_engine_lstm_predictor_bwd(const int64_t *ids, int B, int U1, int S, int E, int Hd, int O, int L, int layer_norm,
+                                   const rnnt_lstm_predictor_params *p, const uint8_t *keep, float dropout_p, float eps_in,
+                                   float eps_lstm, float eps_out, const float *d_out, const rnnt_lstm_predictor_params *g,
+                                   const void *saved, size_t saved_bytes, void *ws, size_t ws_bytes, void *stream);
+
+/*
  * Device-resident greedy decode of ONE utterance (next-step row SURVEY.md 8f-2, second half): the whole loop of
  * rnnt/model.py:108-125 — scan frames from t for the first non-blank argmax, append the token, at most `max_per_frame`
  * tokens per frame, re-run the predictor — with the stateless ConvPredictor of rnnt/predictor.py:189-229 (eval mode:

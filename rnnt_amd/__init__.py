@@ -8,10 +8,11 @@ from . import engine, optim  # noqa: F401
 from .functional import joint_rnnt_loss, rnnt_loss, joint_logits, linear, rnnt_align, joint_rnnt_align  # noqa: F401
 from .joint import JointNetwork  # noqa: F401
 from .predictor import ConvPredictor  # noqa: F401
+from .lstm_predictor import LSTMPredictor  # noqa: F401
 from .encoder import AudioEncoder, JasperBlock  # noqa: F401
 from .featurizer import NormalizedMelSpectrogram, TFJSOldPiecewiseSpectrogram, TFJSSpectrogram  # noqa: F401
 from .model import RNNTModel  # noqa: F401
 from .stream import BeamStream, BeamStreamGroup, GreedyStream  # noqa: F401
 from .context import ContextGraph  # noqa: F401
 
-__all__ = ["engine", "optim", "joint_rnnt_loss", "rnnt_loss", "joint_logits", "rnnt_align", "joint_rnnt_align", "JointNetwork", "RNNTModel", "ConvPredictor", "AudioEncoder", "JasperBlock", "TFJSSpectrogram", "TFJSOldPiecewiseSpectrogram", "NormalizedMelSpectrogram", "GreedyStream", "BeamStream", "BeamStreamGroup", "ContextGraph"]
+__all__ = ["engine", "optim", "joint_rnnt_loss", "rnnt_loss", "joint_logits", "rnnt_align", "joint_rnnt_align", "JointNetwork", "RNNTModel", "ConvPredictor", "LSTMPredictor", "AudioEncoder", "JasperBlock", "TFJSSpectrogram", "TFJSOldPiecewiseSpectrogram", "NormalizedMelSpectrogram", "GreedyStream", "BeamStream", "BeamStreamGroup", "ContextGraph"]

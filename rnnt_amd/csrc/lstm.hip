@@ -1,0 +1,656 @@
+// lstm.hip — LSTMPredictor forward / backward / stateful step for gfx950 behind the C ABI.
+//
+// Reference rnnt/predictor.py:11-186:
+//   x  = LayerNorm_E(embedding(ids))                                        [B,U1,E]
+//   per layer l, per step t:  gates = g_norm(x2g(x_t) + p2g(h_{t-1}))       [B,4Hd], order input / forget / cell / output
+//                             c_t = c_norm(sigmoid(f) c_{t-1} + sigmoid(i) tanh(g));  h_t = sigmoid(o) tanh(c_t)
+//   x  = dropout(h)  (after every layer);   y = LayerNorm_O(linear(x))       [B,U1,O]
+// Rows are (b,u) with features contiguous, as in predictor.hip.  x2g of a whole layer is ONE batched NT GEMM; the
+// recurrence is two launches per step: the recurrent product h_{t-1} p2g^T (k_rec_gemm, rows U1*Hd apart) and one row
+// kernel (k_lstm_step_fwd: a workgroup per batch row).  The backward walks the steps in reverse with a row kernel
+// (k_lstm_step_bwd) and the product dgates_t p2g (k_rec_gemm again); the weight gradients, dx and the affine gradients are
+// batched GEMMs and fixed-order column sums over all rows after the loop.
+// The recurrent products have M = B rows (one 32-row tile at the reference's batch) and sit on every step's critical path.
+// smallgemm's kernels give such a product 16 (NT) or 4 (NN) workgroups at Hd = 512 — 256 resp. 1024 dependent MFMAs per wave,
+// 7 and 27 us of matrix pipe alone —, so k_rec_gemm cuts it into 32 x 32 tiles AND contraction ranges, one workgroup each
+// (256 of them at Hd = 512, <= 32 MFMAs per wave); the partial tiles are added, in order, by the row kernel that follows.
+// Exact fp32 products (v_mfma_f32_32x32x2_f32 / FMA) only.
+// No workgroup waits on another; no atomics: every sum has a fixed order.
+#include "../../include/rnnt_engine.h"
+#include "kernels.hpp"
+#include "smallgemm.hpp"
+#include "predictor_kernels.hpp"
+
+namespace {
+
+constexpr int MAX_L = 8, MAX_HD = 1024, MAX_E = 2048;
+constexpr int UNITS = MAX_HD / 256;  // hidden units per thread of a row kernel: unit j = tid + 256 k, k < UNITS
+
+inline size_t al(size_t x) { return (x + 63) & ~(size_t)63; }  // in floats
+
+struct Dims { int B, U1, S, E, Hd, O, L, ln; };
+
+// contraction ranges of a recurrent product over K: a wave gets at most 4 chunks of 8 (8 beyond 16 ranges)
+inline int rec_splits(int K) { const int s = ((K + 7) / 8 + 15) / 16; return s < 1 ? 1 : (s > 16 ? 16 : s); }
+
+// what the forward keeps for the backward, per row: E + O + 4 floats and 8 Hd + 2 per layer
+struct SavedLayout {
+    size_t x1, st1, z, st2;
+    size_t ghat[MAX_L], chat[MAX_L], hp[MAX_L], cp[MAX_L], y[MAX_L], rs[MAX_L];
+    size_t total;
+};
+SavedLayout saved_layout(const Dims &d)
+{
+    const size_t M = (size_t)d.B * d.U1, Hd = d.Hd;
+    SavedLayout s;
+    size_t o = 0;
+    s.x1 = o;  o += al(M * d.E);
+    s.st1 = o; o += al(2 * M);
+    for (int l = 0; l < d.L; ++l) {
+        s.ghat[l] = o; o += al(M * 4 * Hd);  // normalised gates before the affine (no layer norm: the summed gates)
+        s.chat[l] = o; o += al(M * Hd);      // normalised cell before the affine (no layer norm: the cell)
+        s.hp[l] = o;   o += al(M * Hd);      // h_{t-1} of every step: row (b,0) is the initial state
+        s.cp[l] = o;   o += al(M * Hd);      // c_{t-1}
+        s.y[l] = o;    o += al(M * Hd);      // the layer's output after dropout
+        s.rs[l] = o;   o += al(2 * M);       // rstd of g_norm, c_norm
+    }
+    s.z = o;   o += al(M * d.O);
+    s.st2 = o; o += al(2 * M);
+    s.total = o;
+    return s;
+}
+
+// forward scratch: the x2g product of one layer, one step's recurrent product and — for a call that keeps nothing — the activations
+struct FwdLayout { size_t xg, rg, x1, st1, ya, yb, hb, cb, z, st2, total; };
+FwdLayout fwd_layout(const Dims &d)
+{
+    const size_t M = (size_t)d.B * d.U1, Hd = d.Hd;
+    FwdLayout f;
+    size_t o = 0;
+    f.xg = o;  o += al(M * 4 * Hd);
+    f.rg = o;  o += al((size_t)rec_splits(d.Hd) * d.B * 4 * Hd);  // the recurrent product's partial tiles
+    f.x1 = o;  o += al(M * d.E);
+    f.st1 = o; o += al(2 * M);
+    f.ya = o;  o += al(M * Hd);
+    f.yb = o;  o += al(M * Hd);
+    f.hb = o;  o += al(2 * (size_t)d.B * Hd);  // h and c of the running step, ping-pong
+    f.cb = o;  o += al(2 * (size_t)d.B * Hd);
+    f.z = o;   o += al(M * d.O);
+    f.st2 = o; o += al(2 * M);
+    f.total = o;
+    return f;
+}
+
+struct BwdLayout { size_t dz, t, dy, dpre, tg, draw, dcn, tc, dhrec, dc, slabs, cs, total; };
+BwdLayout bwd_layout(const Dims &d)
+{
+    const size_t M = (size_t)d.B * d.U1, Hd = d.Hd;
+    const size_t W = d.E > d.O ? d.E : d.O, Wi = d.E > d.Hd ? d.E : d.Hd;
+    BwdLayout b;
+    size_t o = 0;
+    b.dz = o;    o += al(M * W);
+    b.t = o;     o += al(M * W);
+    b.dy = o;    o += al(M * Wi);
+    b.dpre = o;  o += al(M * 4 * Hd);
+    b.tg = o;    o += al(M * 4 * Hd);
+    b.draw = o;  o += al(M * 4 * Hd);
+    b.dcn = o;   o += al(M * Hd);
+    b.tc = o;    o += al(M * Hd);
+    b.dhrec = o; o += al((size_t)rec_splits(4 * d.Hd) * d.B * Hd);
+    b.dc = o;    o += al((size_t)d.B * Hd);
+    const size_t wmax = 4 * Hd * Wi > (size_t)d.O * Hd ? 4 * Hd * Wi : (size_t)d.O * Hd;
+    b.slabs = o; o += al((size_t)sgemm_tn_splits((int)M) * wmax);
+    const size_t cw = 4 * Hd > W ? 4 * Hd : W;
+    b.cs = o;    o += al(colsum_scratch_floats((int)M, (int)cw));
+    b.total = o;
+    return b;
+}
+
+// sums of a and b over the workgroup's 256 threads in a fixed order, returned to every thread
+__device__ __forceinline__ void block_sum2(float &a, float &b, float *red)
+{
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) { a += __shfl_xor(a, k, 64); b += __shfl_xor(b, k, 64); }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[wave] = a; red[4 + wave] = b; }
+    __syncthreads();
+    a = (red[0] + red[1]) + (red[2] + red[3]);
+    b = (red[4] + red[5]) + (red[6] + red[7]);
+    __syncthreads();
+}
+
+__device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
+
+// training: row (b,0) of the h_{t-1} / c_{t-1} sequences = the initial state (NULL: zeros)
+__global__ __launch_bounds__(256) void k_lstm_init(const float *__restrict__ h0, const float *__restrict__ c0, int Hd, long ld,
+                                                   float *__restrict__ hp, float *__restrict__ cp)
+{
+    const int b = blockIdx.x;
+    for (int j = threadIdx.x; j < Hd; j += 256) {
+        hp[b * ld + j] = h0 ? h0[(long)b * Hd + j] : 0.f;
+        cp[b * ld + j] = c0 ? c0[(long)b * Hd + j] : 0.f;
+    }
+}
+
+// ---- the recurrent products: P[split][m][n] = sum over the split's k of A[m,k] W(n,k), M = B rows.
+// NN = false: W [N][K] rows ldw apart (h p2g^T: N = 4 Hd, K = Hd); NN = true: W [K][N] (dgates p2g: N = Hd, K = 4 Hd).
+// grid (ceil(N/32), KS, ceil(M/32)); chunk c of 8 contraction elements belongs to wave c % 4 of split (c / 4) % KS; the four
+// waves' tiles are added through LDS in wave order.
+struct RecArgs { const float *A; long lda; const float *W; long ldw; float *P; int M, N, K, KS; };
+
+template <bool NN>
+__global__ __launch_bounds__(256) void k_rec_gemm(RecArgs a)
+{
+    __shared__ float red[3 * 1024];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int i = lane & 31, half = lane >> 5;
+    const int n0 = blockIdx.x * 32, split = blockIdx.y, m0 = blockIdx.z * 32;
+    const int row = min(m0 + i, a.M - 1), col = min(n0 + i, a.N - 1);
+    const int KC = (a.K + 7) / 8;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int c0 = split * 4 + wave; c0 < KC; c0 += 16 * a.KS) {  // four chunks in flight
+        f32x4 x[4], w[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + 4 * a.KS * j, k = 8 * c + 4 * half;
+            const bool ok = c < KC && k < a.K;
+            const int kk = ok ? k : 0;
+            x[j] = *(const f32x4 *)(a.A + (long)row * a.lda + kk);
+            if (!ok) x[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (NN) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) w[j][s] = a.W[(long)(kk + s) * a.ldw + col];
+            } else {
+                w[j] = *(const f32x4 *)(a.W + (long)col * a.ldw + kk);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x[j][s], w[j][s], acc, 0, 0, 0);
+    }
+    if (wave != 0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) red[(wave - 1) * 1024 + r * 64 + lane] = acc[r];
+    }
+    __syncthreads();
+    if (wave != 0 || n0 + i >= a.N) return;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int m = m0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        if (m >= a.M) continue;
+        const float v = ((acc[r] + red[r * 64 + lane]) + red[1024 + r * 64 + lane]) + red[2048 + r * 64 + lane];
+        a.P[((long)split * a.M + m) * a.N + n0 + i] = v;
+    }
+}
+
+template <bool NN>
+void launch_rec_gemm(const float *A, long lda, const float *W, long ldw, float *P, int M, int N, int K, hipStream_t st)
+{
+    const RecArgs a = {A, lda, W, ldw, P, M, N, K, rec_splits(K)};
+    hipLaunchKernelGGL(k_rec_gemm<NN>, dim3((N + 31) / 32, a.KS, (M + 31) / 32), dim3(256), 0, st, a);
+}
+
+struct StepF {
+    const float *xg; long xg_ld;        // x2g(x_t): row b at xg + b xg_ld
+    const float *rg; int rg_n; long rg_ld;  // p2g(h_{t-1}): rg_n partial products [B,4Hd], rg_ld apart; NULL: h_{t-1} = 0
+    const float *cprev; long cprev_ld;  // c_{t-1}; NULL: zeros
+    const float *gw, *gb, *cw, *cb;     // g_norm / c_norm affines (LN only)
+    float eps;
+    float *hnext; long hnext_ld;        // h_t before dropout: the next step's h_{t-1}, or the state out
+    float *cnext; long cnext_ld;
+    float *y; long y_ld;                // h_t after dropout: the layer's output row
+    const unsigned char *keep; long keep_ld; float scale;
+    float *ghat; long ghat_ld; float *chat; long chat_ld; float *rs; long rs_ld;  // kept for the backward (NULL: inference)
+    int Hd;
+};
+
+// One workgroup per batch row: gates = xg + rg, g_norm over the row's 4 Hd gates, the nonlinearities, the cell update, c_norm, h.
+template <bool LN>
+__global__ __launch_bounds__(256) void k_lstm_step_fwd(StepF a)
+{
+    __shared__ float red[8];
+    const int b = blockIdx.x, tid = threadIdx.x, Hd = a.Hd;
+    const float *xg = a.xg + b * a.xg_ld;
+    const float *rg = a.rg ? a.rg + (long)b * 4 * Hd : nullptr;
+    float g[UNITS][4];
+#pragma unroll
+    for (int k = 0; k < UNITS; ++k) {
+        const int j = tid + 256 * k;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float v = 0.f;
+            if (j < Hd) {
+                v = xg[q * Hd + j];
+                if (rg) {
+                    float r = rg[q * Hd + j];
+                    for (int sp = 1; sp < a.rg_n; ++sp) r += rg[sp * a.rg_ld + q * Hd + j];
+                    v += r;
+                }
+            }
+            g[k][q] = v;
+        }
+    }
+    float rstd_g = 1.f, rstd_c = 1.f;
+    if (LN) {
+        const float n = 4.f * Hd;
+        float s = 0.f, unused = 0.f;
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k) s += (g[k][0] + g[k][1]) + (g[k][2] + g[k][3]);
+        block_sum2(s, unused, red);
+        const float mean = s / n;
+        float q2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k)
+            if (tid + 256 * k < Hd)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) q2 += (g[k][q] - mean) * (g[k][q] - mean);
+        block_sum2(q2, unused, red);
+        rstd_g = rsqrtf(q2 / n + a.eps);
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) g[k][q] = (g[k][q] - mean) * rstd_g;
+    }
+    float c[UNITS], o[UNITS];
+#pragma unroll
+    for (int k = 0; k < UNITS; ++k) {
+        const int j = tid + 256 * k;
+        c[k] = 0.f; o[k] = 0.f;
+        if (j >= Hd) continue;
+        float pre[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (a.ghat) a.ghat[b * a.ghat_ld + q * Hd + j] = g[k][q];
+            pre[q] = LN ? g[k][q] * a.gw[q * Hd + j] + a.gb[q * Hd + j] : g[k][q];
+        }
+        const float cp = a.cprev ? a.cprev[b * a.cprev_ld + j] : 0.f;
+        c[k] = sigmoidf(pre[1]) * cp + sigmoidf(pre[0]) * tanhf(pre[2]);
+        o[k] = sigmoidf(pre[3]);
+    }
+    if (LN) {
+        float s = 0.f, unused = 0.f;
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k) s += c[k];
+        block_sum2(s, unused, red);
+        const float mean = s / Hd;
+        float q2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k)
+            if (tid + 256 * k < Hd) q2 += (c[k] - mean) * (c[k] - mean);
+        block_sum2(q2, unused, red);
+        rstd_c = rsqrtf(q2 / Hd + a.eps);
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k) c[k] = (c[k] - mean) * rstd_c;
+    }
+#pragma unroll
+    for (int k = 0; k < UNITS; ++k) {
+        const int j = tid + 256 * k;
+        if (j >= Hd) continue;
+        if (a.chat) a.chat[b * a.chat_ld + j] = c[k];
+        const float cn = LN ? c[k] * a.cw[j] + a.cb[j] : c[k];
+        const float h = o[k] * tanhf(cn);
+        a.cnext[b * a.cnext_ld + j] = cn;
+        a.hnext[b * a.hnext_ld + j] = h;
+        float yv = h;
+        if (a.keep) yv = a.keep[b * a.keep_ld + j] ? h * a.scale : 0.f;
+        a.y[b * a.y_ld + j] = yv;
+    }
+    if (a.rs && tid == 0) { a.rs[b * a.rs_ld] = rstd_g; a.rs[b * a.rs_ld + 1] = rstd_c; }
+}
+
+struct StepB {
+    const float *dy; long dy_ld;        // gradient of the layer's output row (after dropout)
+    const unsigned char *keep; long keep_ld; float scale;
+    const float *dhrec; int dh_n; long dh_ld;  // recurrent part of dh_t (from step t+1): dh_n partial products [B,Hd]; NULL at the last step
+    float *dc; int dc_valid;            // [B,Hd] carried dc: read when valid, always written (dc_{t-1})
+    const float *ghat; long ghat_ld; const float *chat; long chat_ld; const float *rs; long rs_ld;
+    const float *cprev; long cprev_ld;
+    const float *gw, *gb, *cw, *cb;
+    float *dpre, *tg, *draw; long g_ld;  // rows of [M,4Hd]: d(gates after the affine), dpre * ghat, d(summed gates)
+    float *dcn, *tc; long c_ld;          // rows of [M,Hd]: d(normalised cell), dcn * chat
+    int Hd;
+};
+
+// One workgroup per batch row: back through h = o tanh(c), c_norm, the cell update, the gate nonlinearities and g_norm.
+template <bool LN>
+__global__ __launch_bounds__(256) void k_lstm_step_bwd(StepB a)
+{
+    __shared__ float red[8];
+    const int b = blockIdx.x, tid = threadIdx.x, Hd = a.Hd;
+    const float rstd_g = LN ? a.rs[b * a.rs_ld] : 1.f, rstd_c = LN ? a.rs[b * a.rs_ld + 1] : 1.f;
+    float gh[UNITS][4], act[UNITS][4], ch[UNITS], dcn[UNITS], dout[UNITS];
+#pragma unroll
+    for (int k = 0; k < UNITS; ++k) {
+        const int j = tid + 256 * k;
+        ch[k] = 0.f; dcn[k] = 0.f; dout[k] = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { gh[k][q] = 0.f; act[k][q] = 0.f; }
+        if (j >= Hd) continue;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            gh[k][q] = a.ghat[b * a.ghat_ld + q * Hd + j];
+            const float pre = LN ? gh[k][q] * a.gw[q * Hd + j] + a.gb[q * Hd + j] : gh[k][q];
+            act[k][q] = q == 2 ? tanhf(pre) : sigmoidf(pre);
+        }
+        ch[k] = a.chat[b * a.chat_ld + j];
+        const float cn = LN ? ch[k] * a.cw[j] + a.cb[j] : ch[k];
+        const float tc = tanhf(cn);
+        float dh = a.dy[b * a.dy_ld + j];
+        if (a.keep) dh = a.keep[b * a.keep_ld + j] ? dh * a.scale : 0.f;
+        if (a.dhrec) {
+            float r = a.dhrec[(long)b * Hd + j];
+            for (int sp = 1; sp < a.dh_n; ++sp) r += a.dhrec[sp * a.dh_ld + (long)b * Hd + j];
+            dh += r;
+        }
+        dout[k] = dh * tc;
+        dcn[k] = dh * act[k][3] * (1.f - tc * tc);
+        if (a.dc_valid) dcn[k] += a.dc[(long)b * Hd + j];
+    }
+    float dcr[UNITS];  // d(cell before c_norm)
+    if (LN) {
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k) {
+            const int j = tid + 256 * k;
+            dcr[k] = 0.f;
+            if (j >= Hd) continue;
+            a.dcn[b * a.c_ld + j] = dcn[k];
+            a.tc[b * a.c_ld + j] = dcn[k] * ch[k];
+            dcr[k] = dcn[k] * a.cw[j];
+            s1 += dcr[k];
+            s2 += dcr[k] * ch[k];
+        }
+        block_sum2(s1, s2, red);
+        const float c1 = s1 / Hd, c2 = s2 / Hd;
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k) dcr[k] = rstd_c * (dcr[k] - c1 - ch[k] * c2);
+    } else {
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k) dcr[k] = dcn[k];
+    }
+    float dp[UNITS][4];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < UNITS; ++k) {
+        const int j = tid + 256 * k;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) dp[k][q] = 0.f;
+        if (j >= Hd) continue;
+        const float i_ = act[k][0], f_ = act[k][1], g_ = act[k][2], o_ = act[k][3];
+        const float cp = a.cprev[b * a.cprev_ld + j];
+        a.dc[(long)b * Hd + j] = dcr[k] * f_;
+        dp[k][0] = dcr[k] * g_ * i_ * (1.f - i_);
+        dp[k][1] = dcr[k] * cp * f_ * (1.f - f_);
+        dp[k][2] = dcr[k] * i_ * (1.f - g_ * g_);
+        dp[k][3] = dout[k] * o_ * (1.f - o_);
+        if (LN) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                a.dpre[b * a.g_ld + q * Hd + j] = dp[k][q];
+                a.tg[b * a.g_ld + q * Hd + j] = dp[k][q] * gh[k][q];
+                dp[k][q] *= a.gw[q * Hd + j];
+                s1 += dp[k][q];
+                s2 += dp[k][q] * gh[k][q];
+            }
+        }
+    }
+    float c1 = 0.f, c2 = 0.f;
+    if (LN) {
+        block_sum2(s1, s2, red);
+        c1 = s1 / (4.f * Hd); c2 = s2 / (4.f * Hd);
+    }
+#pragma unroll
+    for (int k = 0; k < UNITS; ++k) {
+        const int j = tid + 256 * k;
+        if (j >= Hd) continue;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            a.draw[b * a.g_ld + q * Hd + j] = LN ? rstd_g * (dp[k][q] - c1 - gh[k][q] * c2) : dp[k][q];
+    }
+}
+
+int check_dims(const Dims &d)
+{
+    if (d.B <= 0 || d.U1 <= 0 || d.S <= 0 || d.E <= 0 || d.Hd <= 0 || d.O <= 0 || d.L <= 0)
+        return engine_fail(RNNT_ERR_INVALID_ARG, "non-positive dimension B=%d U1=%d S=%d E=%d Hd=%d O=%d L=%d", d.B, d.U1, d.S, d.E,
+                           d.Hd, d.O, d.L);
+    if (d.E % 4 != 0 || d.Hd % 4 != 0 || d.O % 4 != 0 || d.Hd > MAX_HD || d.E > MAX_E || d.L > MAX_L)
+        return engine_fail(RNNT_ERR_UNSUPPORTED,
+                           "LSTMPredictor kernels need E %% 4 == 0, Hd %% 4 == 0, O %% 4 == 0, Hd <= %d, E <= %d and L <= %d (E=%d Hd=%d O=%d L=%d)",
+                           MAX_HD, MAX_E, MAX_L, d.E, d.Hd, d.O, d.L);
+    if ((long)d.B * d.U1 > 0x3fffffffL / 4) return engine_fail(RNNT_ERR_UNSUPPORTED, "B*U1 too large");
+    return RNNT_OK;
+}
+
+bool bad(const void *q) { return !q || ((uintptr_t)q & 15); }
+
+int check_params(const rnnt_lstm_predictor_params *p, int L, int ln, const char *what)
+{
+    if (!p || !p->layers) return engine_fail(RNNT_ERR_INVALID_ARG, "null %s struct or layer array", what);
+    const void *outer[] = {p->embedding, p->ln_in_w, p->ln_in_b, p->linear_w, p->linear_b, p->ln_out_w, p->ln_out_b};
+    for (const void *q : outer)
+        if (bad(q)) return engine_fail(RNNT_ERR_INVALID_ARG, "null or not 16-byte aligned %s pointer", what);
+    for (int l = 0; l < L; ++l) {
+        const rnnt_lstm_layer_params &y = p->layers[l];
+        if (bad(y.x2g_w) || bad(y.p2g_w)) return engine_fail(RNNT_ERR_INVALID_ARG, "layer %d: null or not 16-byte aligned %s weight", l, what);
+        if (ln) {
+            if (bad(y.g_norm_w) || bad(y.g_norm_b) || bad(y.c_norm_w) || bad(y.c_norm_b))
+                return engine_fail(RNNT_ERR_INVALID_ARG, "layer %d: null or not 16-byte aligned %s g_norm / c_norm pointer", l, what);
+        } else if (bad(y.x2g_b)) {
+            return engine_fail(RNNT_ERR_INVALID_ARG, "layer %d: null or not 16-byte aligned %s x2g bias (no layer norm)", l, what);
+        }
+    }
+    return RNNT_OK;
+}
+
+int status(const char *what)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return engine_fail(RNNT_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
+    return RNNT_OK;
+}
+
+SgArgs sg(const float *A, long lda, const float *B, long ldb, float *C, long ldc, int M, int N, int K)
+{
+    SgArgs a;
+    a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc;
+    a.bias = nullptr; a.Cpre = nullptr; a.mask = nullptr; a.mask_scale = 1.f;
+    a.M = M; a.N = N; a.K = K; a.taps = 1; a.seg = M; a.act = 0; a.ksplit = 1;
+    return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rnnt_engine_lstm_predictor_saved_bytes(int B, int U1, int S, int E, int Hd, int O, int L, int layer_norm, size_t *out)
+{
+    if (!out) return engine_fail(RNNT_ERR_INVALID_ARG, "null size pointer");
+    const Dims d = {B, U1, S, E, Hd, O, L, layer_norm != 0};
+    if (int rc = check_dims(d)) return rc;
+    *out = saved_layout(d).total * 4;
+    return RNNT_OK;
+}
+
+int rnnt_engine_lstm_predictor_workspace_bytes(int B, int U1, int S, int E, int Hd, int O, int L, int layer_norm, int backward,
+                                               size_t *out)
+{
+    if (!out) return engine_fail(RNNT_ERR_INVALID_ARG, "null size pointer");
+    const Dims d = {B, U1, S, E, Hd, O, L, layer_norm != 0};
+    if (int rc = check_dims(d)) return rc;
+    *out = (backward ? bwd_layout(d).total : fwd_layout(d).total) * 4;
+    return RNNT_OK;
+}
+
+int rnnt_engine_lstm_predictor_fwd(const int64_t *ids, int B, int U1, int S, int E, int Hd, int O, int L, int layer_norm,
+                                   const rnnt_lstm_predictor_params *p, const float *state_in, const uint8_t *keep,
+                                   float dropout_p, float eps_in, float eps_lstm, float eps_out, float *out, float *state_out,
+                                   void *saved, size_t saved_bytes, void *ws, size_t ws_bytes, void *stream)
+{
+    const Dims d = {B, U1, S, E, Hd, O, L, layer_norm != 0};
+    if (int rc = check_dims(d)) return rc;
+    if (!ids || bad(out) || bad(state_out) || bad(ws)) return engine_fail(RNNT_ERR_INVALID_ARG, "null or not 16-byte aligned pointer argument");
+    if ((state_in && ((uintptr_t)state_in & 15)) || (saved && ((uintptr_t)saved & 15)))
+        return engine_fail(RNNT_ERR_INVALID_ARG, "state_in / saved not 16-byte aligned");
+    if (int rc = check_params(p, L, d.ln, "parameter")) return rc;
+    if (!(dropout_p >= 0.f && dropout_p < 1.f)) return engine_fail(RNNT_ERR_INVALID_ARG, "dropout_p outside [0,1)");
+    const SavedLayout SL = saved_layout(d);
+    const FwdLayout FL = fwd_layout(d);
+    if (saved && saved_bytes < SL.total * 4)
+        return engine_fail(RNNT_ERR_WORKSPACE, "saved buffer %zu < required %zu bytes", saved_bytes, SL.total * 4);
+    if (ws_bytes < FL.total * 4) return engine_fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, FL.total * 4);
+    hipStream_t st = (hipStream_t)stream;
+    float *w = (float *)ws, *sv = (float *)saved;
+    const int M = B * U1;
+    const long seq = (long)U1 * Hd, BH = (long)B * Hd;
+    const float scale = 1.f / (1.f - dropout_p);
+    const bool train = saved != nullptr;
+    if (dropout_p == 0.f) keep = nullptr;
+
+    float *x1 = train ? sv + SL.x1 : w + FL.x1;
+    launch_ln_fwd(p->embedding, ids, S, p->ln_in_w, p->ln_in_b, eps_in, M, E, x1, train ? sv + SL.st1 : w + FL.st1, st);
+    const float *x = x1;
+    int in = E;
+    for (int l = 0; l < L; ++l) {
+        const rnnt_lstm_layer_params &y = p->layers[l];
+        SgArgs gx = sg(x, in, y.x2g_w, in, w + FL.xg, 4 * Hd, M, 4 * Hd, in);
+        gx.bias = d.ln ? nullptr : y.x2g_b;
+        launch_sgemm_nt(gx, st);
+        const float *h0 = state_in ? state_in + (long)(2 * l) * BH : nullptr, *c0 = state_in ? h0 + BH : nullptr;
+        float *hout = state_out + (long)(2 * l) * BH, *cout = hout + BH;
+        float *yl = train ? sv + SL.y[l] : w + ((l & 1) ? FL.yb : FL.ya);
+        if (train)
+            hipLaunchKernelGGL(k_lstm_init, dim3(B), dim3(256), 0, st, h0, c0, Hd, seq, sv + SL.hp[l], sv + SL.cp[l]);
+        for (int t = 0; t < U1; ++t) {
+            StepF a;
+            const float *hprev; long hprev_ld;
+            if (train) {
+                hprev = sv + SL.hp[l] + (long)t * Hd; hprev_ld = seq;
+                a.cprev = sv + SL.cp[l] + (long)t * Hd; a.cprev_ld = seq;
+            } else if (t == 0) {
+                hprev = h0; hprev_ld = Hd;
+                a.cprev = c0; a.cprev_ld = Hd;
+            } else {
+                hprev = w + FL.hb + (t & 1) * BH; hprev_ld = Hd;
+                a.cprev = w + FL.cb + (t & 1) * BH; a.cprev_ld = Hd;
+            }
+            const bool rec = t > 0 || state_in;  // h_{t-1} = 0: no recurrent product
+            if (rec) launch_rec_gemm<false>(hprev, hprev_ld, y.p2g_w, Hd, w + FL.rg, B, 4 * Hd, Hd, st);
+            a.xg = w + FL.xg + (long)t * 4 * Hd; a.xg_ld = 4 * seq;
+            a.rg = rec ? w + FL.rg : nullptr; a.rg_n = rec_splits(Hd); a.rg_ld = 4 * BH;
+            a.gw = y.g_norm_w; a.gb = y.g_norm_b; a.cw = y.c_norm_w; a.cb = y.c_norm_b;
+            a.eps = eps_lstm;
+            if (t + 1 == U1) {
+                a.hnext = hout; a.cnext = cout; a.hnext_ld = a.cnext_ld = Hd;
+            } else if (train) {
+                a.hnext = sv + SL.hp[l] + (long)(t + 1) * Hd; a.cnext = sv + SL.cp[l] + (long)(t + 1) * Hd;
+                a.hnext_ld = a.cnext_ld = seq;
+            } else {
+                a.hnext = w + FL.hb + ((t + 1) & 1) * BH; a.cnext = w + FL.cb + ((t + 1) & 1) * BH;
+                a.hnext_ld = a.cnext_ld = Hd;
+            }
+            a.y = yl + (long)t * Hd; a.y_ld = seq;
+            a.keep = keep ? keep + (long)l * M * Hd + (long)t * Hd : nullptr; a.keep_ld = seq; a.scale = scale;
+            a.ghat = train ? sv + SL.ghat[l] + (long)t * 4 * Hd : nullptr; a.ghat_ld = 4 * seq;
+            a.chat = train ? sv + SL.chat[l] + (long)t * Hd : nullptr; a.chat_ld = seq;
+            a.rs = train ? sv + SL.rs[l] + 2 * t : nullptr; a.rs_ld = 2 * (long)U1;
+            a.Hd = Hd;
+            if (d.ln) hipLaunchKernelGGL(k_lstm_step_fwd<true>, dim3(B), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL(k_lstm_step_fwd<false>, dim3(B), dim3(256), 0, st, a);
+        }
+        x = yl;
+        in = Hd;
+    }
+    float *z = train ? sv + SL.z : w + FL.z;
+    SgArgs lin = sg(x, Hd, p->linear_w, Hd, z, O, M, O, Hd);
+    lin.bias = p->linear_b;
+    launch_sgemm_nt(lin, st);
+    launch_ln_fwd(z, nullptr, 0, p->ln_out_w, p->ln_out_b, eps_out, M, O, out, train ? sv + SL.st2 : w + FL.st2, st);
+    return status("rnnt_engine_lstm_predictor_fwd");
+}
+
+int rnnt_engine_lstm_predictor_bwd(const int64_t *ids, int B, int U1, int S, int E, int Hd, int O, int L, int layer_norm,
+                                   const rnnt_lstm_predictor_params *p, const uint8_t *keep, float dropout_p, float eps_in,
+                                   float eps_lstm, float eps_out, const float *d_out, const rnnt_lstm_predictor_params *g,
+                                   const void *saved, size_t saved_bytes, void *ws, size_t ws_bytes, void *stream)
+{
+    (void)eps_in; (void)eps_lstm; (void)eps_out;  // the forward kept every rstd
+    const Dims d = {B, U1, S, E, Hd, O, L, layer_norm != 0};
+    if (int rc = check_dims(d)) return rc;
+    if (!ids || bad(d_out) || bad(saved) || bad(ws)) return engine_fail(RNNT_ERR_INVALID_ARG, "null or not 16-byte aligned pointer argument");
+    if (int rc = check_params(p, L, d.ln, "parameter")) return rc;
+    if (int rc = check_params(g, L, d.ln, "gradient")) return rc;
+    if (!(dropout_p >= 0.f && dropout_p < 1.f)) return engine_fail(RNNT_ERR_INVALID_ARG, "dropout_p outside [0,1)");
+    const SavedLayout SL = saved_layout(d);
+    const BwdLayout BL = bwd_layout(d);
+    if (saved_bytes < SL.total * 4) return engine_fail(RNNT_ERR_WORKSPACE, "saved buffer %zu < required %zu bytes", saved_bytes, SL.total * 4);
+    if (ws_bytes < BL.total * 4) return engine_fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, BL.total * 4);
+    hipStream_t st = (hipStream_t)stream;
+    float *w = (float *)ws;
+    const float *sv = (const float *)saved;
+    const int M = B * U1;
+    const long seq = (long)U1 * Hd;
+    const float scale = 1.f / (1.f - dropout_p);
+    if (dropout_p == 0.f) keep = nullptr;
+    float *cs = w + BL.cs, *dy = w + BL.dy, *draw = w + BL.draw;
+
+    // weight gradient dW [N,K] = Y^T X over the M rows: split-K slabs, summed in order; db = colsum(Y) where asked for
+    auto wgrad = [&](const float *Y, int N, const float *X, int K, float *dW, float *db) {
+        SgArgs a = sg(Y, N, X, K, w + BL.slabs, K, M, N, K);
+        a.ksplit = sgemm_tn_splits_for(M, N, K, 1);
+        launch_sgemm_tn(a, st);
+        if (db) launch_colsum_stage1(Y, N, M, N, cs, st);
+        launch_wgrad_finish(w + BL.slabs, a.ksplit, dW, N, K, 1, cs, colsum_slabs(M), N, db, st);
+    };
+
+    // output LayerNorm and linear
+    launch_ln_bwd(sv + SL.z, nullptr, 0, p->ln_out_w, sv + SL.st2, d_out, M, O, w + BL.dz, w + BL.t, st);
+    launch_colsum_pair(w + BL.t, d_out, O, M, O, (float *)g->ln_out_w, (float *)g->ln_out_b, cs, st);
+    wgrad(w + BL.dz, O, sv + SL.y[L - 1], Hd, (float *)g->linear_w, (float *)g->linear_b);
+    launch_sgemm_nn(sg(w + BL.dz, O, p->linear_w, Hd, dy, Hd, M, Hd, O), st);
+
+    for (int l = L - 1; l >= 0; --l) {
+        const rnnt_lstm_layer_params &y = p->layers[l], &gy = g->layers[l];
+        const int in = l ? Hd : E;
+        const float *x = l ? sv + SL.y[l - 1] : sv + SL.x1;
+        for (int t = U1 - 1; t >= 0; --t) {
+            StepB a;
+            a.dy = dy + (long)t * Hd; a.dy_ld = seq;
+            a.keep = keep ? keep + (long)l * M * Hd + (long)t * Hd : nullptr; a.keep_ld = seq; a.scale = scale;
+            a.dhrec = t + 1 < U1 ? w + BL.dhrec : nullptr; a.dh_n = rec_splits(4 * Hd); a.dh_ld = (long)B * Hd;
+            a.dc = w + BL.dc; a.dc_valid = t + 1 < U1;
+            a.ghat = sv + SL.ghat[l] + (long)t * 4 * Hd; a.ghat_ld = 4 * seq;
+            a.chat = sv + SL.chat[l] + (long)t * Hd; a.chat_ld = seq;
+            a.rs = sv + SL.rs[l] + 2 * t; a.rs_ld = 2 * (long)U1;
+            a.cprev = sv + SL.cp[l] + (long)t * Hd; a.cprev_ld = seq;
+            a.gw = y.g_norm_w; a.gb = y.g_norm_b; a.cw = y.c_norm_w; a.cb = y.c_norm_b;
+            a.dpre = w + BL.dpre + (long)t * 4 * Hd; a.tg = w + BL.tg + (long)t * 4 * Hd; a.draw = draw + (long)t * 4 * Hd;
+            a.g_ld = 4 * seq;
+            a.dcn = w + BL.dcn + (long)t * Hd; a.tc = w + BL.tc + (long)t * Hd; a.c_ld = seq;
+            a.Hd = Hd;
+            if (d.ln) hipLaunchKernelGGL(k_lstm_step_bwd<true>, dim3(B), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL(k_lstm_step_bwd<false>, dim3(B), dim3(256), 0, st, a);
+            // recurrent part of dh_{t-1} = dgates_t p2g (nothing flows into the initial state)
+            if (t > 0) launch_rec_gemm<true>(draw + (long)t * 4 * Hd, 4 * seq, y.p2g_w, Hd, w + BL.dhrec, B, Hd, 4 * Hd, st);
+        }
+        // d p2g = sum_t dgates_t^T h_{t-1} (row (b,0) of the kept h_{t-1} sequence is the initial state), d x2g (+ bias), the affines
+        wgrad(draw, 4 * Hd, sv + SL.hp[l], Hd, (float *)gy.p2g_w, nullptr);
+        wgrad(draw, 4 * Hd, x, in, (float *)gy.x2g_w, d.ln ? nullptr : (float *)gy.x2g_b);
+        if (d.ln) {
+            launch_colsum_pair(w + BL.tg, w + BL.dpre, 4 * Hd, M, 4 * Hd, (float *)gy.g_norm_w, (float *)gy.g_norm_b, cs, st);
+            launch_colsum_pair(w + BL.tc, w + BL.dcn, Hd, M, Hd, (float *)gy.c_norm_w, (float *)gy.c_norm_b, cs, st);
+        }
+        // dx: the gradient of the layer below's output, or of the input LayerNorm's
+        launch_sgemm_nn(sg(draw, 4 * Hd, y.x2g_w, in, dy, in, M, in, 4 * Hd), st);
+    }
+    // input LayerNorm (its input is the embedding row) and the embedding table
+    launch_ln_bwd(p->embedding, ids, S, p->ln_in_w, sv + SL.st1, dy, M, E, w + BL.dz, w + BL.t, st);
+    launch_colsum_pair(w + BL.t, dy, E, M, E, (float *)g->ln_in_w, (float *)g->ln_in_b, cs, st);
+    launch_embed_bwd(ids, w + BL.dz, M, E, S, (float *)g->embedding, st);
+    return status("rnnt_engine_lstm_predictor_bwd");
+}
+
+}  // extern "C"

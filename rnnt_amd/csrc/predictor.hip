@@ -14,6 +14,7 @@
 #include "../../include/rnnt_engine.h"
 #include "kernels.hpp"
 #include "smallgemm.hpp"
+#include "predictor_kernels.hpp"
 
 namespace {
 
@@ -219,6 +220,24 @@ SgArgs sg(const float *A, long lda, const float *B, long ldb, float *C, long ldc
 }
 
 }  // namespace
+
+// the LayerNorm / embedding kernels above for lstm.hip (predictor_kernels.hpp)
+void launch_ln_fwd(const float *X, const int64_t *ids, int S, const float *gamma, const float *beta, float eps, int M, int N,
+                   float *Y, float *stats, hipStream_t st)
+{
+    if (ids) hipLaunchKernelGGL(k_ln_fwd<true>, dim3((M + 3) / 4), dim3(256), 0, st, X, ids, S, gamma, beta, eps, M, N, Y, stats);
+    else hipLaunchKernelGGL(k_ln_fwd<false>, dim3((M + 3) / 4), dim3(256), 0, st, X, ids, S, gamma, beta, eps, M, N, Y, stats);
+}
+void launch_ln_bwd(const float *X, const int64_t *ids, int S, const float *gamma, const float *stats, const float *dY, int M, int N,
+                   float *dX, float *T, hipStream_t st)
+{
+    if (ids) hipLaunchKernelGGL(k_ln_bwd<true>, dim3((M + 3) / 4), dim3(256), 0, st, X, ids, S, gamma, stats, dY, M, N, dX, T);
+    else hipLaunchKernelGGL(k_ln_bwd<false>, dim3((M + 3) / 4), dim3(256), 0, st, X, ids, S, gamma, stats, dY, M, N, dX, T);
+}
+void launch_embed_bwd(const int64_t *ids, const float *dX0, int M, int E, int S, float *dEmb, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_embed_bwd, dim3(S), dim3(256), 0, st, ids, dX0, M, E, S, dEmb);
+}
 
 extern "C" {
 

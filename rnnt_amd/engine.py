@@ -103,6 +103,10 @@ SIGNATURES = {
     "rnnt_engine_conv_predictor_saved_bytes": "iiiiip",
     "rnnt_engine_conv_predictor_fwd": "piiiiipppfffppzp",
     "rnnt_engine_conv_predictor_bwd": "piiiiipppfpppzp",
+    "rnnt_engine_lstm_predictor_saved_bytes": "iiiiiiiip",
+    "rnnt_engine_lstm_predictor_workspace_bytes": "iiiiiiiiip",
+    "rnnt_engine_lstm_predictor_fwd": "piiiiiiiipppffffpppzpzp",
+    "rnnt_engine_lstm_predictor_bwd": "piiiiiiiippffffpppzpzp",
     "rnnt_engine_linear_fwd": "pqppiiipp",
     "rnnt_engine_linear_bwd_workspace_bytes": "iiip",
     "rnnt_engine_linear_bwd": "pqppiiippppzp",
@@ -168,6 +172,8 @@ EXPORTS = (
     "rnnt_engine_encoder_fwd", "rnnt_engine_encoder_stream_push",
     "rnnt_engine_featurizer_basis_bytes", "rnnt_engine_featurizer_pack", "rnnt_engine_featurizer_workspace_bytes",
     "rnnt_engine_featurizer_fwd", "rnnt_engine_featurizer_stream_push",
+    "rnnt_engine_lstm_predictor_saved_bytes", "rnnt_engine_lstm_predictor_workspace_bytes",
+    "rnnt_engine_lstm_predictor_fwd", "rnnt_engine_lstm_predictor_bwd",
 )
 
 # per-call kernel variants (include/rnnt_engine.h RNNT_VARIANT_*): bit-identical results

@@ -1,6 +1,8 @@
 """RNNTModel container with the reference's interface (rnnt/model.py:7-139); `forward`
 routes the joint + loss through the fused HIP engine.  Encoder and predictor are whatever
-torch modules the caller supplies (stock PyTorch-ROCm; out of scope for the engine).
+torch modules the caller supplies: the engine's own (rnnt_amd.ConvPredictor, rnnt_amd.LSTMPredictor,
+rnnt_amd.AudioEncoder) or stock PyTorch-ROCm ones, stateless (forward(ids)) or stateful
+(forward(ids, lengths, state=None)).
 """
 import inspect
 import warnings
@@ -53,7 +55,7 @@ class RNNTModel(torch.nn.Module):
         # sees the un-prepended ids (model.py:36)
         start = torch.full((input_ids.shape[0], 1), blank_idx, dtype=input_ids.dtype,
                            device=self.device)
-        decoder_features = self.predictor(torch.cat([start, input_ids], dim=1))
+        decoder_features = self._predict(torch.cat([start, input_ids], dim=1), input_id_lens + 1)
 
         audio_features = self.encoder(mel_features).permute(0, 2, 1)  # (N,C,L) -> (N,L,C) view
         audio_feature_lens = self.encoder.calc_output_lens(mel_feature_lens)
@@ -72,6 +74,13 @@ class RNNTModel(torch.nn.Module):
                                      target_lengths=input_id_lens.int(),
                                      blank=-1, reduction="mean", check_lengths=self.check_lengths, **reg)
 
+    def _predict(self, ids_with_start, lens_with_start):
+        """The predictor's features for `forward` and `align`: a stateless predictor is called as predictor(ids); a stateful one
+        (the LSTM's forward(input, lengths, state=None) -> (features, lengths, state)) with the lengths, from zero state."""
+        if self._predictor_is_stateful():
+            return self.predictor(ids_with_start, lens_with_start)[0]
+        return self.predictor(ids_with_start)
+
     # ---- forced alignment (DESIGN.md §4j)
     @torch.no_grad()
     def align(self, mel_features: torch.Tensor, mel_feature_lens: torch.Tensor, input_ids: torch.Tensor,
@@ -81,7 +90,7 @@ class RNNTModel(torch.nn.Module):
         label is emitted, -1 past input_id_lens[n]).  Seconds: frame * the encoder's stride (calc_output_lens) * the
         featurizer's hop."""
         start = torch.full((input_ids.shape[0], 1), blank_idx, dtype=input_ids.dtype, device=self.device)
-        decoder_features = self.predictor(torch.cat([start, input_ids], dim=1))
+        decoder_features = self._predict(torch.cat([start, input_ids], dim=1), input_id_lens + 1)
         audio_features = self.encoder(mel_features).permute(0, 2, 1)
         audio_feature_lens = self.encoder.calc_output_lens(mel_feature_lens)
         return self.joint.align(audio_features, decoder_features, targets=input_ids.int(),
