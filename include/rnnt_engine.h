@@ -459,6 +459,35 @@ int rnnt_engine_greedy_decode(const void *frames, int64_t frame_stride, int T, c
                               int32_t *state, int32_t *tokens, void *workspace, size_t ws_bytes, void *stream);
 
 /*
+ * The same loop with the stateful LSTMPredictor (rnnt/predictor.py:93-186, eval mode; DESIGN.md 4p "Device decode") for n_utt
+ * (1 .. 32) INDEPENDENT utterances advancing in lockstep: the rows of one 32-row tile of every product.  Per iteration a fixed
+ * kernel sequence: embedding + input LayerNorm of the utterances that emitted a label, per layer both gate products in one launch
+ * and one row step (h and c updated in place; a row whose utterance emitted nothing keeps its h, c and text vector), linear + output
+ * LayerNorm, joint.text_ln where the joint has one, the scan of `scan_frames` frames from each utterance's own t (tanh of the sum: no
+ * range limit), argmax + bookkeeping per utterance.  5 + 2 L launches per iteration, 2 more with text_ln.
+ *   frames: `rows` packed rows [rows,H], frame_stride apart; utt: DEVICE int32[n_utt][2] = each utterance's first row and frame count
+ *   (the convention of rnnt_engine_beam_decode_batch; the kernels hold every entry inside the buffer); max_frames: the longest count.
+ *   p, S, E, Hd, O, L, layer_norm, eps_in / eps_lstm / eps_out: as rnnt_engine_lstm_predictor_fwd; text_W .. max_per_frame, scan_frames,
+ *   iterations (0 = the bound max_length + ceil(max_frames / scan_frames) + 1), init, host_flag (raised when ALL utterances have
+ *   ended): as rnnt_engine_greedy_decode.
+ *   state  int32[n_utt][8]: [0] t, [1] emitted, [2] ntok, [3] done, [4] a label the predictor has still to take in, [5] iterations
+ *   that did work, [6] settled (done, and the last label taken in); tokens int32[n_utt][max_length]: row u as rnnt_engine_greedy_decode's.
+ *   state_out: NULL or [L][2][n_utt][Hd], the LSTM state after each utterance's last label (after the start blank if it has none).
+ *   The workspace BEGINS with the text vectors [n_utt][H] (the joint's text input after each utterance's last label).
+ * An utterance's tokens, state words and state_out rows are bit-identical whatever its neighbours, its position and n_utt.
+ * Checked before anything is enqueued: RNNT_ERR_INVALID_ARG (null pointers, non-positive dims, max_length < 2), RNNT_ERR_UNSUPPORTED
+ * (rnnt_engine_lstm_predictor_fwd's limits, H % 8, V % 4, scan_frames outside 1..128, n_utt > 32), RNNT_ERR_WORKSPACE.
+ */
+int rnnt_engine_greedy_decode_lstm_workspace_bytes(int n_utt, int S, int E, int Hd, int O, int L, int layer_norm, int H, int V, int has_text,
+                                                   int scan_frames, size_t *out);
+int rnnt_engine_greedy_decode_lstm(const void *frames, int64_t frame_stride, int rows, const int32_t *utt, int n_utt, int max_frames,
+                                   const rnnt_lstm_predictor_params *p, int S, int E, int Hd, int O, int L, int layer_norm, float eps_in,
+                                   float eps_lstm, float eps_out, const void *text_W, const void *text_b, const void *W, const void *bias,
+                                   int H, int V, int blank, int max_length, int max_per_frame, int scan_frames, int iterations, int init,
+                                   int32_t *host_flag, int32_t *state, int32_t *tokens, float *state_out, void *workspace, size_t ws_bytes,
+                                   void *stream);
+
+/*
  * The same loop (rnnt/model.py:108-125 with the ConvPredictor of rnnt/predictor.py:189-229, eval mode) for one utterance as ONE
  * persistent launch: 16 - 128 workgroups stay resident for the whole utterance and hand scan candidates, the conv2 output and the
  * predictor's output to each other through tagged 8-byte words in the workspace (rnnt_amd/csrc/decode.hip, k_dec_persist), with

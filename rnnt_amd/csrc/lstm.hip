@@ -15,7 +15,8 @@
 // 7 and 27 us of matrix pipe alone —, so k_rec_gemm cuts it into 32 x 32 tiles AND contraction ranges, one workgroup each
 // (256 of them at Hd = 512, <= 32 MFMAs per wave); the partial tiles are added, in order, by the row kernel that follows.
 // Exact fp32 products (v_mfma_f32_32x32x2_f32 / FMA) only.
-// No workgroup waits on another; no atomics: every sum has a fixed order.
+// No workgroup waits on another; no atomics on results: every sum has a fixed order.
+// The greedy decode with this predictor as a device loop (rnnt_engine_greedy_decode_lstm, k_ld_*) is at the end of the file.
 #include "../../include/rnnt_engine.h"
 #include "kernels.hpp"
 #include "smallgemm.hpp"
@@ -138,13 +139,12 @@ __global__ __launch_bounds__(256) void k_lstm_init(const float *__restrict__ h0,
 // waves' tiles are added through LDS in wave order.
 struct RecArgs { const float *A; long lda; const float *W; long ldw; float *P; int M, N, K, KS; };
 
+// one workgroup's tile of such a product: output columns n0 .. n0 + 31, rows m0 .. m0 + 31, contraction range `split`; red: 3 * 1024 floats of LDS
 template <bool NN>
-__global__ __launch_bounds__(256) void k_rec_gemm(RecArgs a)
+__device__ __forceinline__ void rec_tile(const RecArgs &a, int n0, int split, int m0, float *red)
 {
-    __shared__ float red[3 * 1024];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i = lane & 31, half = lane >> 5;
-    const int n0 = blockIdx.x * 32, split = blockIdx.y, m0 = blockIdx.z * 32;
     const int row = min(m0 + i, a.M - 1), col = min(n0 + i, a.N - 1);
     const int KC = (a.K + 7) / 8;
     f32x16 acc;
@@ -184,6 +184,13 @@ __global__ __launch_bounds__(256) void k_rec_gemm(RecArgs a)
         const float v = ((acc[r] + red[r * 64 + lane]) + red[1024 + r * 64 + lane]) + red[2048 + r * 64 + lane];
         a.P[((long)split * a.M + m) * a.N + n0 + i] = v;
     }
+}
+
+template <bool NN>
+__global__ __launch_bounds__(256) void k_rec_gemm(RecArgs a)
+{
+    __shared__ float red[3 * 1024];
+    rec_tile<NN>(a, blockIdx.x * 32, blockIdx.y, blockIdx.z * 32, red);
 }
 
 template <bool NN>
@@ -462,6 +469,428 @@ SgArgs sg(const float *A, long lda, const float *B, long ldb, float *C, long ldc
     return a;
 }
 
+
+// ---------------------------------------------------------------------------------------
+// Device-resident greedy decode with this predictor (rnnt_engine_greedy_decode_lstm; DESIGN.md §4p "Device decode"): the loop of
+// reference rnnt/model.py:45-87 for n_utt <= 32 independent utterances in lockstep — the rows of ONE 32-row tile of every product —
+// as a fixed kernel sequence per ITERATION, every decision on the device (the control flow is decode.hip's k_dec_update):
+//   [embedding + input LayerNorm of the rows that emitted a label]  per layer [both gate products: x x2g^T and h p2g^T, one launch]
+//   [row step: gates, g_norm, cell, c_norm, h — in place]  [linear product] [+ bias, output LayerNorm]  with joint.text_ln
+//   [its product] [+ bias]  [scan of scan_frames frames from each utterance's own t]  [argmax + bookkeeping per utterance].
+// state (int32[n_utt][8]): [0] t  [1] emitted  [2] ntok  [3] done  [4] newtok: the predictor has a label to take in
+//   [5] iterations that did work  [6] settled: done and the last label taken in (nothing is left to do for the utterance).
+// A row whose utterance emitted nothing leaves h, c and its text vector untouched; a product computes every row of the tile and
+// the row kernels ignore the others.  Row m of a product reads row m of its operand only and the contraction ranges depend on K
+// alone, so an utterance's numbers do not depend on its neighbours, its position or n_utt.  No atomics on results (one counter of
+// settled utterances raises the host's flag), no workgroup waits on another, every sum in a fixed order.
+// ---------------------------------------------------------------------------------------
+struct LdLayout { size_t text, x1, hc, y, gp, part, ctrl, total; };  // floats; the text vectors [n_utt][H] come first (the ABI says so)
+LdLayout ld_layout(int n_utt, int E, int Hd, int O, int L, int H, int V, int scan_frames)
+{
+    const size_t n = n_utt;
+    LdLayout w;
+    size_t o = 0;
+    w.text = o; o += al(n * H);
+    w.x1 = o;   o += al(n * E);
+    w.hc = o;   o += al((size_t)L * 2 * n * Hd);
+    w.y = o;    o += al(n * O);
+    size_t g = (size_t)(rec_splits(E) + rec_splits(Hd)) * 4 * Hd;  // partial tiles of the widest product
+    if ((size_t)2 * rec_splits(Hd) * 4 * Hd > g) g = (size_t)2 * rec_splits(Hd) * 4 * Hd;
+    if ((size_t)rec_splits(Hd) * O > g) g = (size_t)rec_splits(Hd) * O;
+    if ((size_t)rec_splits(O) * H > g) g = (size_t)rec_splits(O) * H;
+    w.gp = o;   o += al(g * n);
+    w.part = o; o += al(n * scan_frames * ((V + 31) / 32) * 2);
+    w.ctrl = o; o += 64;
+    w.total = o;
+    return w;
+}
+
+__global__ __launch_bounds__(256) void k_ld_init(int32_t *__restrict__ states, int32_t *__restrict__ tokens, int max_length, int blank,
+                                                 int n_utt, float *__restrict__ hc, int nhc, int32_t *__restrict__ ctrl)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < nhc) hc[i] = 0.f;
+    if (i < n_utt) {
+        int32_t *s = states + 8 * i;
+        s[0] = 0; s[1] = 0; s[2] = 0; s[3] = 0; s[4] = 1; s[5] = 0; s[6] = 0; s[7] = 0;
+        tokens[(long)i * max_length] = blank;
+    }
+    if (i == 0) ctrl[0] = 0;
+}
+
+// x1[u] = LayerNorm_E(embedding[the utterance's newest token]) for the utterances that have one
+__global__ __launch_bounds__(256) void k_ld_embed(const int32_t *__restrict__ states, const int32_t *__restrict__ tokens, int max_length,
+                                                  const float *__restrict__ emb, int S, const float *__restrict__ gamma,
+                                                  const float *__restrict__ beta, float eps, int E, float *__restrict__ x1)
+{
+    __shared__ float red[8];
+    const int u = blockIdx.x, tid = threadIdx.x;
+    const int32_t *st = states + 8 * u;
+    if (!st[4]) return;
+    int tok = tokens[(long)u * max_length + st[2]];
+    tok = tok < 0 ? 0 : (tok >= S ? S - 1 : tok);
+    const float *e = emb + (long)tok * E;
+    float s = 0.f, q = 0.f, unused = 0.f;
+    for (int i = tid; i < E; i += 256) s += e[i];
+    block_sum2(s, unused, red);
+    const float mean = s / E;
+    for (int i = tid; i < E; i += 256) { const float d = e[i] - mean; q += d * d; }
+    block_sum2(q, unused, red);
+    const float rstd = rsqrtf(q / E + eps);
+    for (int i = tid; i < E; i += 256) x1[(long)u * E + i] = (e[i] - mean) * rstd * gamma[i] + beta[i];
+}
+
+// whether any utterance has a label for the predictor to take in (workgroup-uniform; n_utt <= 32)
+__device__ __forceinline__ bool ld_any_new(const int32_t *states, int n_utt)
+{
+    const int u = threadIdx.x & 63;
+    return __ballot(u < n_utt && states[8 * u + 4] != 0) != 0ull;
+}
+
+// up to two NT products of the same M = n_utt rows and N columns in one launch: grid (ceil(N/32), KS0 + KS1); the partial tiles of
+// product 0's ranges, then product 1's, at P[range][m][n] — the row kernel that follows adds them in that order
+struct LdGemm { const int32_t *states; int n_utt; RecArgs g[2]; };
+__global__ __launch_bounds__(256) void k_ld_gemm(LdGemm a)
+{
+    __shared__ float red[3 * 1024];
+    if (!ld_any_new(a.states, a.n_utt)) return;
+    const int which = (int)blockIdx.y >= a.g[0].KS ? 1 : 0;
+    rec_tile<false>(a.g[which], blockIdx.x * 32, blockIdx.y - (which ? a.g[0].KS : 0), 0, red);
+}
+
+struct LdStep {
+    const int32_t *states;
+    const float *gp; int nsp; long gp_ld;  // nsp partial products [n_utt,4Hd], gp_ld apart
+    const float *xb;                       // x2g bias (no layer norm) or NULL
+    const float *gw, *gb, *cw, *cb; float eps;
+    float *h, *c;                          // [n_utt,Hd], updated in place
+    float *h_out, *c_out;                  // the caller's state_out rows, or NULL
+    int Hd;
+};
+
+// k_lstm_step_fwd's definition in eval mode, nothing kept, for the rows whose utterance has a new label: one workgroup per utterance
+template <bool LN>
+__global__ __launch_bounds__(256) void k_ld_step(LdStep a)
+{
+    __shared__ float red[8];
+    const int b = blockIdx.x, tid = threadIdx.x, Hd = a.Hd;
+    if (!a.states[8 * b + 4]) return;
+    const float *gp = a.gp + (long)b * 4 * Hd;
+    float g[UNITS][4];
+#pragma unroll
+    for (int k = 0; k < UNITS; ++k) {
+        const int j = tid + 256 * k;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float v = 0.f;
+            if (j < Hd) {
+                v = gp[q * Hd + j];
+                for (int sp = 1; sp < a.nsp; ++sp) v += gp[sp * a.gp_ld + q * Hd + j];
+                if (a.xb) v += a.xb[q * Hd + j];
+            }
+            g[k][q] = v;
+        }
+    }
+    if (LN) {
+        const float n = 4.f * Hd;
+        float s = 0.f, unused = 0.f;
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k) s += (g[k][0] + g[k][1]) + (g[k][2] + g[k][3]);
+        block_sum2(s, unused, red);
+        const float mean = s / n;
+        float q2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k)
+            if (tid + 256 * k < Hd)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) q2 += (g[k][q] - mean) * (g[k][q] - mean);
+        block_sum2(q2, unused, red);
+        const float rstd_g = rsqrtf(q2 / n + a.eps);
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) g[k][q] = (g[k][q] - mean) * rstd_g;
+    }
+    float c[UNITS], o[UNITS];
+#pragma unroll
+    for (int k = 0; k < UNITS; ++k) {
+        const int j = tid + 256 * k;
+        c[k] = 0.f; o[k] = 0.f;
+        if (j >= Hd) continue;
+        float pre[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) pre[q] = LN ? g[k][q] * a.gw[q * Hd + j] + a.gb[q * Hd + j] : g[k][q];
+        c[k] = sigmoidf(pre[1]) * a.c[(long)b * Hd + j] + sigmoidf(pre[0]) * tanhf(pre[2]);
+        o[k] = sigmoidf(pre[3]);
+    }
+    if (LN) {
+        float s = 0.f, unused = 0.f;
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k) s += c[k];
+        block_sum2(s, unused, red);
+        const float mean = s / Hd;
+        float q2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k)
+            if (tid + 256 * k < Hd) q2 += (c[k] - mean) * (c[k] - mean);
+        block_sum2(q2, unused, red);
+        const float rstd_c = rsqrtf(q2 / Hd + a.eps);
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k) c[k] = (c[k] - mean) * rstd_c;
+    }
+#pragma unroll
+    for (int k = 0; k < UNITS; ++k) {
+        const int j = tid + 256 * k;
+        if (j >= Hd) continue;
+        const float cn = LN ? c[k] * a.cw[j] + a.cb[j] : c[k];
+        const float h = o[k] * tanhf(cn);
+        a.c[(long)b * Hd + j] = cn;
+        a.h[(long)b * Hd + j] = h;
+        if (a.h_out) { a.c_out[(long)b * Hd + j] = cn; a.h_out[(long)b * Hd + j] = h; }
+    }
+}
+
+// out[u] = sum of the nsp partial products + bias, LN: then LayerNorm_N (gamma, beta, eps) — for the rows with a new label
+template <bool LN>
+__global__ __launch_bounds__(256) void k_ld_rowfin(const int32_t *__restrict__ states, const float *__restrict__ gp, int nsp, long gp_ld, int N,
+                                                   const float *__restrict__ bias, const float *__restrict__ gamma,
+                                                   const float *__restrict__ beta, float eps, float *__restrict__ out)
+{
+    __shared__ float red[8];
+    const int u = blockIdx.x, tid = threadIdx.x;
+    if (!states[8 * u + 4]) return;
+    float *y = out + (long)u * N;
+    float s = 0.f, q = 0.f, unused = 0.f;
+    for (int i = tid; i < N; i += 256) {  // (a thread reads back only what it wrote itself)
+        float v = gp[(long)u * N + i];
+        for (int sp = 1; sp < nsp; ++sp) v += gp[sp * gp_ld + (long)u * N + i];
+        v += bias[i];
+        y[i] = v;
+        s += v;
+    }
+    if (!LN) return;
+    block_sum2(s, unused, red);
+    const float mean = s / N;
+    for (int i = tid; i < N; i += 256) { const float d = y[i] - mean; q += d * d; }
+    block_sum2(q, unused, red);
+    const float rstd = rsqrtf(q / N + eps);
+    for (int i = tid; i < N; i += 256) y[i] = (y[i] - mean) * rstd * gamma[i] + beta[i];
+}
+
+// an utterance's first row and frame count from the caller's device table, held inside the packed buffer whatever the table says
+__device__ __forceinline__ void ld_utt(const int32_t *utt, int u, int rows, int &first, int &T)
+{
+    first = min(max(utt[2 * u], 0), rows - 1);
+    T = min(max(utt[2 * u + 1], 1), rows - first);
+}
+
+// decode.hip's k_dec_scan_logits<false> with the utterance as grid dimension z: scan_frames frames from the utterance's own t against
+// its own text vector (tanh of the sum), one (max, first index) candidate per frame and 32 vocabulary entries
+__global__ __launch_bounds__(256) void k_ld_scan(const int32_t *__restrict__ states, const float *__restrict__ enc, long enc_st,
+                                                 const int32_t *__restrict__ utt, int rows, const float *__restrict__ text,
+                                                 const float *__restrict__ W, const float *__restrict__ bias, float2 *__restrict__ part, int K,
+                                                 int H, int V)
+{
+    __shared__ float s_acc[3][16][64];
+    const int u = blockIdx.z;
+    const int32_t *state = states + 8 * u;
+    if (state[3]) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = lane & 31, half = lane >> 5;
+    const int v0 = blockIdx.x * 32, k0 = blockIdx.y * 32;
+    int first, T;
+    ld_utt(utt, u, rows, first, T);
+    const int t0 = min(max(state[0], 0), T - 1);
+    const int frame = first + min(t0 + min(k0 + i, K - 1), T - 1), vrow = min(v0 + i, V - 1);
+    const float *er = enc + (long)frame * enc_st + 4 * half;
+    const float *pr = text + (long)u * H + 4 * half;
+    const float *wr = W + (long)vrow * H + 4 * half;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    const int NC = H / 8;
+    struct Ops { f32x4 e, p, w; };
+    auto load = [&](Ops &o, int c) {
+        const int cc = c < NC ? c : NC - 1;
+        o.e = *(const f32x4 *)(er + 8 * cc); o.p = *(const f32x4 *)(pr + 8 * cc); o.w = *(const f32x4 *)(wr + 8 * cc);
+    };
+    auto load8 = [&](Ops (&g)[8], int c0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) load(g[j], c0 + 4 * j);
+    };
+    auto mul8 = [&](const Ops (&g)[8], int c0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (c0 + 4 * j < NC) {  // wave-uniform
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fast_tanh(g[j].e[s] + g[j].p[s]), g[j].w[s], acc, 0, 0, 0);
+            }
+    };
+    Ops ga[8], gb[8];
+    load8(ga, wave);
+    for (int c = wave; c < NC; c += 64) {  // two groups (2 x 8 chunks x 4 waves) per trip, the next group's loads in flight
+        load8(gb, c + 32);
+        mul8(ga, c);
+        load8(ga, c + 64);
+        mul8(gb, c + 32);
+    }
+    if (wave > 0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s_acc[wave - 1][r][lane] = acc[r];
+    }
+    __syncthreads();
+    if (wave == 0) {
+        const int v = v0 + i;
+        const float bv = v < V ? bias[v] : 0.f;
+        float2 *pu = part + (long)u * K * gridDim.x;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int k = k0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            float x = ((acc[r] + s_acc[0][r][lane]) + (s_acc[1][r][lane] + s_acc[2][r][lane])) + bv;
+            if (v >= V) x = RNNT_NEG_INF;
+            const float M = half_max_dpp(x, half);
+            const unsigned long long hit = __ballot(x == M);  // first lane of the half that holds it = the lowest index
+            const unsigned h32 = half ? (unsigned)(hit >> 32) : (unsigned)hit;
+            if (i == 0 && k < K) pu[(long)k * gridDim.x + blockIdx.x] = float2{M, __int_as_float(v0 + __builtin_ctz(h32))};
+        }
+    }
+}
+
+// k_dec_update's rules per utterance (one workgroup each).  An utterance that ended on a label keeps newtok for one more iteration —
+// the predictor takes the label in, so that state_out and the text vector are those AFTER the last label — and settles in the next;
+// ctrl[0] counts the settled utterances, the last one raises the host's flag.
+__global__ __launch_bounds__(128) void k_ld_update(const float2 *__restrict__ part, int K, int NB, int blank, const int32_t *__restrict__ utt,
+                                                   int rows, int max_length, int max_per_frame, int n_utt, int32_t *__restrict__ states,
+                                                   int32_t *__restrict__ tokens, int32_t *__restrict__ ctrl, int32_t *host_flag)
+{
+    __shared__ int s_tok[128];
+    const int u = blockIdx.x;
+    int32_t *state = states + 8 * u;
+    if (state[6]) return;
+    const bool was_done = state[3] != 0;
+    if (!was_done && (int)threadIdx.x < K) {
+        const float2 *p = part + ((long)u * K + threadIdx.x) * NB;
+        float best = RNNT_NEG_INF;
+        int bi = 0;
+        for (int j = 0; j < NB; ++j) {
+            const float2 c = p[j];
+            if (c.x > best) { best = c.x; bi = __float_as_int(c.y); }
+        }
+        s_tok[threadIdx.x] = bi;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    int done = 1, newtok = 0;
+    if (!was_done) {
+        int first, T;
+        ld_utt(utt, u, rows, first, T);
+        int t = state[0], emitted = state[1], ntok = state[2];
+        const int n = min(K, T - t);
+        int hit = -1;
+        for (int k = 0; k < n; ++k)
+            if (s_tok[k] != blank) { hit = k; break; }
+        if (hit < 0) { t += n; emitted = 0; }
+        else {
+            if (hit > 0) emitted = 0;
+            t += hit;
+            tokens[(long)u * max_length + (++ntok)] = s_tok[hit];
+            newtok = 1;
+            if (++emitted >= max_per_frame) { ++t; emitted = 0; }
+        }
+        done = (t >= T || ntok + 1 >= max_length) ? 1 : 0;
+        state[0] = t; state[1] = emitted; state[2] = ntok; state[3] = done;
+        state[5] += 1;
+    }
+    state[4] = newtok;
+    if (done && !newtok) {
+        state[6] = 1;
+        if (atomicAdd(ctrl, 1) + 1 == n_utt && host_flag) __hip_atomic_store(host_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+struct LdArgs {
+    const float *frames; long frame_stride; int rows; const int32_t *utt; int n_utt;
+    rnnt_lstm_predictor_params p; int S, E, Hd, O, L, ln; float eps_in, eps_lstm, eps_out;
+    const float *text_W, *text_b, *W, *bias; int H, V, blank, max_length, max_per_frame, scan_frames, iterations, init;
+    int32_t *host_flag, *state, *tokens; float *state_out; float *ws;
+};
+
+RecArgs ld_prod(const float *A, const float *W, float *P, int M, int N, int K)
+{
+    return RecArgs{A, (long)K, W, (long)K, P, M, N, K, rec_splits(K)};
+}
+
+void launch_ld_loop(const LdArgs &a, hipStream_t st)
+{
+    const int n = a.n_utt, E = a.E, Hd = a.Hd, O = a.O, L = a.L, H = a.H, V = a.V, K = a.scan_frames, NB = (V + 31) / 32;
+    const LdLayout w = ld_layout(n, E, Hd, O, L, H, V, K);
+    float *text = a.ws + w.text, *x1 = a.ws + w.x1, *hc = a.ws + w.hc, *y = a.ws + w.y, *gp = a.ws + w.gp;
+    float2 *part = (float2 *)(a.ws + w.part);
+    int32_t *ctrl = (int32_t *)(a.ws + w.ctrl);
+    const long nH = (long)n * Hd;
+    if (a.init) {
+        const int nhc = (int)(2 * L * nH);
+        hipLaunchKernelGGL(k_ld_init, dim3((nhc + 255) / 256), dim3(256), 0, st, a.state, a.tokens, a.max_length, a.blank, n, hc, nhc, ctrl);
+    }
+    for (int it = 0; it < a.iterations; ++it) {
+        hipLaunchKernelGGL(k_ld_embed, dim3(n), dim3(256), 0, st, a.state, a.tokens, a.max_length, a.p.embedding, a.S, a.p.ln_in_w,
+                           a.p.ln_in_b, a.eps_in, E, x1);
+        for (int l = 0; l < L; ++l) {
+            const rnnt_lstm_layer_params &q = a.p.layers[l];
+            float *h = hc + (long)(2 * l) * nH, *c = h + nH;
+            const int in = l ? Hd : E;
+            LdGemm g;
+            g.states = a.state; g.n_utt = n;
+            g.g[0] = ld_prod(l ? h - 2 * nH : x1, q.x2g_w, gp, n, 4 * Hd, in);  // the layer below's NEW h (its row kernel has run)
+            g.g[1] = ld_prod(h, q.p2g_w, gp + (long)g.g[0].KS * n * 4 * Hd, n, 4 * Hd, Hd);  // this layer's h of the step before
+            hipLaunchKernelGGL(k_ld_gemm, dim3((4 * Hd + 31) / 32, g.g[0].KS + g.g[1].KS), dim3(256), 0, st, g);
+            LdStep s;
+            s.states = a.state; s.gp = gp; s.nsp = g.g[0].KS + g.g[1].KS; s.gp_ld = 4 * nH;
+            s.xb = a.ln ? nullptr : q.x2g_b;
+            s.gw = q.g_norm_w; s.gb = q.g_norm_b; s.cw = q.c_norm_w; s.cb = q.c_norm_b; s.eps = a.eps_lstm;
+            s.h = h; s.c = c;
+            s.h_out = a.state_out ? a.state_out + (long)(2 * l) * nH : nullptr; s.c_out = a.state_out ? s.h_out + nH : nullptr;
+            s.Hd = Hd;
+            if (a.ln) hipLaunchKernelGGL(k_ld_step<true>, dim3(n), dim3(256), 0, st, s);
+            else hipLaunchKernelGGL(k_ld_step<false>, dim3(n), dim3(256), 0, st, s);
+        }
+        LdGemm g;
+        g.states = a.state; g.n_utt = n;
+        g.g[0] = ld_prod(hc + (long)(2 * (L - 1)) * nH, a.p.linear_w, gp, n, O, Hd);
+        g.g[1] = g.g[0]; g.g[1].KS = 0;
+        hipLaunchKernelGGL(k_ld_gemm, dim3((O + 31) / 32, g.g[0].KS), dim3(256), 0, st, g);
+        // without joint.text_ln the output LayerNorm's row IS the text vector (O == H)
+        hipLaunchKernelGGL(k_ld_rowfin<true>, dim3(n), dim3(256), 0, st, a.state, gp, g.g[0].KS, (long)n * O, O, a.p.linear_b, a.p.ln_out_w,
+                           a.p.ln_out_b, a.eps_out, a.text_W ? y : text);
+        if (a.text_W) {
+            g.g[0] = ld_prod(y, a.text_W, gp, n, H, O);
+            g.g[1] = g.g[0]; g.g[1].KS = 0;
+            hipLaunchKernelGGL(k_ld_gemm, dim3((H + 31) / 32, g.g[0].KS), dim3(256), 0, st, g);
+            hipLaunchKernelGGL(k_ld_rowfin<false>, dim3(n), dim3(256), 0, st, a.state, gp, g.g[0].KS, (long)n * H, H, a.text_b,
+                               (const float *)nullptr, (const float *)nullptr, 0.f, text);
+        }
+        hipLaunchKernelGGL(k_ld_scan, dim3(NB, (K + 31) / 32, n), dim3(256), 0, st, a.state, a.frames, a.frame_stride, a.utt, a.rows, text, a.W,
+                           a.bias, part, K, H, V);
+        hipLaunchKernelGGL(k_ld_update, dim3(n), dim3(128), 0, st, part, K, NB, a.blank, a.utt, a.rows, a.max_length, a.max_per_frame, n, a.state,
+                           a.tokens, ctrl, a.host_flag);
+    }
+}
+
+int ld_check_sizes(int n_utt, int S, int E, int Hd, int O, int L, int ln, int H, int V, int has_text, int scan_frames)
+{
+    if (n_utt < 1) return engine_fail(RNNT_ERR_INVALID_ARG, "n_utt=%d must be >= 1", n_utt);
+    if (H <= 0 || V <= 0) return engine_fail(RNNT_ERR_INVALID_ARG, "non-positive dimension H=%d V=%d", H, V);
+    const Dims d = {n_utt, 1, S, E, Hd, O, L, ln};
+    if (int rc = check_dims(d)) return rc;
+    if (n_utt > 32) return engine_fail(RNNT_ERR_UNSUPPORTED, "the LSTM greedy decode takes 1 <= n_utt <= 32: one row tile (n_utt=%d)", n_utt);
+    if (H % 8 != 0 || V % 4 != 0) return engine_fail(RNNT_ERR_UNSUPPORTED, "the LSTM greedy decode needs H %% 8 == 0 and V %% 4 == 0 (H=%d V=%d)", H, V);
+    if (scan_frames < 1 || scan_frames > 128)
+        return engine_fail(RNNT_ERR_UNSUPPORTED, "the LSTM greedy decode takes scan_frames in [1,128] (scan_frames=%d)", scan_frames);
+    if (!has_text && O != H) return engine_fail(RNNT_ERR_INVALID_ARG, "without text_ln the predictor's output dim (%d) must equal H (%d)", O, H);
+    return RNNT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -651,6 +1080,61 @@ int rnnt_engine_lstm_predictor_bwd(const int64_t *ids, int B, int U1, int S, int
     launch_colsum_pair(w + BL.t, dy, E, M, E, (float *)g->ln_in_w, (float *)g->ln_in_b, cs, st);
     launch_embed_bwd(ids, w + BL.dz, M, E, S, (float *)g->embedding, st);
     return status("rnnt_engine_lstm_predictor_bwd");
+}
+
+int rnnt_engine_greedy_decode_lstm_workspace_bytes(int n_utt, int S, int E, int Hd, int O, int L, int layer_norm, int H, int V, int has_text,
+                                                   int scan_frames, size_t *out)
+{
+    if (!out) return engine_fail(RNNT_ERR_INVALID_ARG, "null size pointer");
+    if (int rc = ld_check_sizes(n_utt, S, E, Hd, O, L, layer_norm != 0, H, V, has_text, scan_frames)) return rc;
+    *out = (ld_layout(n_utt, E, Hd, O, L, H, V, scan_frames).total * 4 + 255) & ~(size_t)255;
+    return RNNT_OK;
+}
+
+int rnnt_engine_greedy_decode_lstm(const void *frames, int64_t frame_stride, int rows, const int32_t *utt, int n_utt, int max_frames,
+                                   const rnnt_lstm_predictor_params *p, int S, int E, int Hd, int O, int L, int layer_norm, float eps_in,
+                                   float eps_lstm, float eps_out, const void *text_W, const void *text_b, const void *W, const void *bias,
+                                   int H, int V, int blank, int max_length, int max_per_frame, int scan_frames, int iterations, int init,
+                                   int32_t *host_flag, int32_t *state, int32_t *tokens, float *state_out, void *workspace, size_t ws_bytes,
+                                   void *stream)
+{
+    size_t need;
+    if (int rc = rnnt_engine_greedy_decode_lstm_workspace_bytes(n_utt, S, E, Hd, O, L, layer_norm, H, V, text_W ? 1 : 0, scan_frames, &need))
+        return rc;
+    if (iterations < 0) return engine_fail(RNNT_ERR_INVALID_ARG, "iterations=%d", iterations);
+    if (bad(frames) || bad(W) || bad(bias) || !utt || !state || !tokens || !workspace)
+        return engine_fail(RNNT_ERR_INVALID_ARG, "null or not 16-byte aligned pointer argument");
+    if (((uintptr_t)utt & 7) || ((uintptr_t)workspace & 255) || (state_out && ((uintptr_t)state_out & 15)))
+        return engine_fail(RNNT_ERR_INVALID_ARG, "utt must be 8-byte, state_out 16-byte and the workspace 256-byte aligned");
+    if (int rc = check_params(p, L, layer_norm != 0, "parameter")) return rc;
+    if ((text_W == nullptr) != (text_b == nullptr) || (text_W && (bad(text_W) || bad(text_b))))
+        return engine_fail(RNNT_ERR_INVALID_ARG, "text_W / text_b: both or neither, 16-byte aligned");
+    if (max_length < 2 || max_per_frame < 1 || max_frames < 1 || rows < max_frames || frame_stride < H || frame_stride % 4)
+        return engine_fail(RNNT_ERR_INVALID_ARG, "max_length=%d max_per_frame=%d max_frames=%d rows=%d frame_stride=%lld", max_length,
+                           max_per_frame, max_frames, rows, (long long)frame_stride);
+    if (blank < 0 || blank >= V) return engine_fail(RNNT_ERR_INVALID_ARG, "blank=%d outside [0,%d)", blank, V);
+    if ((long)n_utt * max_length > 0x7fffffffL) return engine_fail(RNNT_ERR_UNSUPPORTED, "n_utt * max_length must stay below 2^31");
+    int32_t *flag_dev = nullptr;
+    if (host_flag) {  // the device's address of the caller's pinned word (an ordinary host pointer is refused, never written through)
+        void *dp = nullptr;
+        if (hipHostGetDevicePointer(&dp, host_flag, 0) != hipSuccess || !dp) {
+            (void)hipGetLastError();
+            return engine_fail(RNNT_ERR_INVALID_ARG, "host_flag is not mapped pinned host memory (hipHostMalloc / torch pin_memory)");
+        }
+        flag_dev = (int32_t *)dp;
+    }
+    if (ws_bytes < need) return engine_fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
+    LdArgs a;
+    a.frames = (const float *)frames; a.frame_stride = (long)frame_stride; a.rows = rows; a.utt = utt; a.n_utt = n_utt;
+    a.p = *p; a.S = S; a.E = E; a.Hd = Hd; a.O = O; a.L = L; a.ln = layer_norm != 0;
+    a.eps_in = eps_in; a.eps_lstm = eps_lstm; a.eps_out = eps_out;
+    a.text_W = (const float *)text_W; a.text_b = (const float *)text_b; a.W = (const float *)W; a.bias = (const float *)bias;
+    a.H = H; a.V = V; a.blank = blank; a.max_length = max_length; a.max_per_frame = max_per_frame; a.scan_frames = scan_frames;
+    a.iterations = iterations ? iterations : max_length + (max_frames + scan_frames - 1) / scan_frames + 1;
+    a.init = init;
+    a.host_flag = flag_dev; a.state = state; a.tokens = tokens; a.state_out = state_out; a.ws = (float *)workspace;
+    launch_ld_loop(a, (hipStream_t)stream);
+    return status("rnnt_engine_greedy_decode_lstm");
 }
 
 }  // extern "C"

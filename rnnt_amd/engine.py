@@ -78,6 +78,8 @@ SIGNATURES = {
     "rnnt_engine_greedy_scan": "pqqpppiiiiippzp",
     "rnnt_engine_greedy_decode_workspace_bytes": "iiiiip",
     "rnnt_engine_greedy_decode": "pqipiiiffppppiiiiiiiippppzp",
+    "rnnt_engine_greedy_decode_lstm_workspace_bytes": "iiiiiiiiiiip",
+    "rnnt_engine_greedy_decode_lstm": "pqipiipiiiiiifffppppiiiiiiiipppppzp",
     "rnnt_engine_greedy_decode_persistent_workspace_bytes": "iiiiiiip",
     "rnnt_engine_greedy_decode_persistent": "pqipiiiffppppiiiiipppppzp",
     "rnnt_engine_greedy_decode_tables_bytes": "iiiiip",
@@ -174,6 +176,7 @@ EXPORTS = (
     "rnnt_engine_featurizer_fwd", "rnnt_engine_featurizer_stream_push",
     "rnnt_engine_lstm_predictor_saved_bytes", "rnnt_engine_lstm_predictor_workspace_bytes",
     "rnnt_engine_lstm_predictor_fwd", "rnnt_engine_lstm_predictor_bwd",
+    "rnnt_engine_greedy_decode_lstm_workspace_bytes", "rnnt_engine_greedy_decode_lstm",
 )
 
 # per-call kernel variants (include/rnnt_engine.h RNNT_VARIANT_*): bit-identical results
@@ -956,6 +959,68 @@ def greedy_decode_loop(frames, pred_params, ln_eps, text_W, text_b, W, bias, bla
                                bound, chunk)
         state._keepalive = (flag, *m.keep)  # until the caller has synchronised
     return state, tokens
+
+
+# ---- greedy decode with the LSTMPredictor, n_utt utterances in lockstep (DESIGN.md §4p "Device decode")
+LSTM_DECODE_MAX = 32  # rnnt_engine_greedy_decode_lstm: 1 <= n_utt <= 32, the rows of one tile of every product
+
+
+def greedy_decode_lstm_supported(n_utt, S, E, Hd, O, L, layer_norm, H, V, has_text, scan_frames=32):
+    """Whether rnnt_engine_greedy_decode_lstm takes these sizes (no device work)."""
+    return _supported("rnnt_engine_greedy_decode_lstm_workspace_bytes", n_utt, S, E, Hd, O, L, bool(layer_norm), H, V, bool(has_text),
+                      scan_frames)
+
+
+def greedy_decode_lstm(frames_list, lstm_params, text_W, text_b, W, bias, blank, max_length, max_per_frame=10, scan_frames=32, chunk=8,
+                       want_state=True):
+    """Device-resident greedy decode of 1 .. 32 utterances of one LSTMPredictor model, advanced in lockstep (C ABI
+    rnnt_engine_greedy_decode_lstm; reference rnnt/model.py:45-87).  `frames_list`: [T_u, H] fp32 frame tensors (audio_ln applied), packed
+    here into one buffer; the table of first rows and lengths is the call's one small host-to-device copy.  `lstm_params`:
+    LSTMPredictor._decode_bundle() = (the parameter tensors in rnnt_lstm_predictor_params order, (L, Hd, layer_norm), the three eps).
+    The other arguments and the enqueueing (chunks of iterations until the device raises the pinned end flag — when ALL utterances have
+    ended) as greedy_decode_loop.  Returns (state int32[N, 8], tokens int32[N, max_length], state_out float32[L, 2, N, Hd] or None, text
+    float32[N, H]: the joint's text input after each utterance's last label, a view of the stream's workspace valid until the next engine
+    call on it) device tensors WITHOUT synchronising: afterwards tokens[u, 1 : 1 + state[u, 2]] are utterance u's ids, bit for bit
+    what it gives decoded alone."""
+    from .lstm_predictor import _struct
+    frames_list = list(frames_list)
+    lens = [int(f.shape[0]) for f in frames_list]
+    if not lens or min(lens) < 1:
+        raise ValueError("greedy_decode_lstm: no utterance, or an utterance without frames")
+    params, (L, Hd, layer_norm), eps = lstm_params
+    params = [t.contiguous() for t in params]
+    packed, table = _pack_rows(frames_list, lens)
+    if packed.dim() != 2 or packed.stride(1) != 1:
+        packed = packed.contiguous()
+    joint = [t.contiguous() for t in (W, bias)] + ([text_W.contiguous(), text_b.contiguous()] if text_W is not None else [])
+    dev = _require_cuda(packed, *joint, *params)
+    _require_dtype(torch.float32, frames=packed, **{f"joint{i}": t for i, t in enumerate(joint)}, **{f"param{i}": t for i, t in enumerate(params)})
+    N, H, V = len(lens), packed.shape[1], joint[0].shape[0]
+    S, E = params[0].shape
+    O = params[3].shape[0]
+    max_length, scan_frames, chunk = int(max_length), int(scan_frames), max(1, int(chunk))
+    bound = max_length + (max(lens) + scan_frames - 1) // max(1, scan_frames) + 1
+    with torch.cuda.device(dev):
+        n = ctypes.c_size_t(0)
+        _check(lib().rnnt_engine_greedy_decode_lstm_workspace_bytes(N, S, E, Hd, O, L, int(bool(layer_norm)), H, V, int(len(joint) == 4),
+                                                                    scan_frames, ctypes.byref(n)))
+        ws = workspace(dev, n.value)
+        utt = _rows_table(table, dev)
+        state = torch.empty(N, 8, dtype=torch.int32, device=dev)  # (a single row's stride is whatever torch says: the row is contiguous)
+        tokens = torch.empty(N, max_length, dtype=torch.int32, device=dev)
+        state_out = torch.empty(L, 2, N, Hd, dtype=torch.float32, device=dev) if want_state else None
+        st, arr = _struct(params, L, layer_norm)
+        head = (_p(packed), ctypes.c_int64(packed.stride(0) if packed.shape[0] > 1 else H), packed.shape[0], _p(utt), N, max(lens),
+                ctypes.byref(st), S, E, Hd, O, L,
+                int(bool(layer_norm)), *[ctypes.c_float(e) for e in eps], _p(joint[2]) if len(joint) == 4 else None,
+                _p(joint[3]) if len(joint) == 4 else None, _p(joint[0]), _p(joint[1]), H, V, int(blank), max_length, int(max_per_frame),
+                scan_frames)
+        tail = (_p(state), _p(tokens), _p(state_out), _p(ws), ctypes.c_size_t(ws.numel()), _stream(dev))
+        flag = _enqueue_rounds(lambda it, first, flag: _check(lib().rnnt_engine_greedy_decode_lstm(*head, it, first, flag, *tail)),
+                               bound, chunk)
+        state._keepalive = (flag, utt, packed, params, joint, arr)  # until the caller has synchronised
+        text = ws[:N * H * 4].view(torch.float32).view(N, H)
+    return state, tokens, state_out, text
 
 
 # ---- streaming greedy decode (include/rnnt_engine.h RNNT_STREAM_*; DESIGN.md §4i)

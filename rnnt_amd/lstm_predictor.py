@@ -177,6 +177,17 @@ class LSTMPredictor(torch.nn.Module):
                 out += [layer.x2g.weight, layer.x2g.bias, layer.p2g.weight]
         return tuple(out)
 
+    def _decode_sizes(self):
+        """(S, E, Hd, O, L, layer_norm), as engine.greedy_decode_lstm_supported takes them."""
+        S, E = self.embedding.weight.shape
+        return (S, E, self.lstm_layers[0].hidden_dim, self.linear.out_features, len(self.lstm_layers), self.lstm_layer_norm)
+
+    def _decode_bundle(self):
+        """What engine.greedy_decode_lstm is told about the predictor: the LIVE parameter tensors (nothing is cached on the module:
+        optimizers and replayed graphs write through raw pointers), (L, Hd, layer_norm) and the three eps."""
+        return (self._params(), (len(self.lstm_layers), self.lstm_layers[0].hidden_dim, self.lstm_layer_norm),
+                (float(self.input_layer_norm.eps), self.lstm_layer_norm_epsilon, float(self.output_layer_norm.eps)))
+
     def _engine_refusal(self, input, state):
         """Why the engine path does not apply to this call, or None."""
         L, Hd = len(self.lstm_layers), self.lstm_layers[0].hidden_dim

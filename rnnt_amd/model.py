@@ -32,6 +32,9 @@ class RNNTModel(torch.nn.Module):
         self.restrict_left = 0
         self.restrict_right = 0
         self._restrict_frames = None  # the frames of the call in progress (__call__)
+        # the path the last greedy_decode / greedy_decode_many took: "persistent", "loop", "lstm_loop" (DESIGN.md §4p "Device decode")
+        # or "host"; greedy_decode_many: "host" only if every utterance took the host loop
+        self.last_decode_path = None
 
     @property
     def device(self):
@@ -107,19 +110,43 @@ class RNNTModel(torch.nn.Module):
         return len(required) >= 2
 
     def _device_loop_ok(self, audio) -> bool:
-        """The whole decode loop can run on the device (rnnt_engine_greedy_decode): stateless engine ConvPredictor in
-        eval mode, fp32 HIP tensors, sizes the decode kernels cover."""
+        """The whole decode loop can run on the device: the engine's stateless ConvPredictor (rnnt_engine_greedy_decode) or its
+        LSTMPredictor (rnnt_engine_greedy_decode_lstm; backend not "torch") in eval mode or at p = 0, fp32 HIP tensors, sizes the
+        decode kernels cover."""
         from .predictor import ConvPredictor
+        from .lstm_predictor import LSTMPredictor
         p = self.predictor
-        if not (isinstance(p, ConvPredictor) and audio.is_cuda and audio.dtype == torch.float32):
+        if not (isinstance(p, (ConvPredictor, LSTMPredictor)) and audio.is_cuda and audio.dtype == torch.float32):
             return False
         if p.training and float(p.dropout.p) > 0.0:
             return False
         E, O = p.embedding.embedding_dim, p.linear.out_features
         H, V = self.joint.joint_ln.in_features, self.joint.joint_ln.out_features
+        has_text = hasattr(self.joint, "text_ln")
+        if isinstance(p, LSTMPredictor):
+            if p.backend == "torch" or p._engine_refusal(audio, None) is not None or self.joint.joint_ln.weight.dtype != torch.float32:
+                return False
+            from . import engine
+            return (has_text or O == H) and engine.greedy_decode_lstm_supported(1, *p._decode_sizes(), H, V, has_text)
         if E % 4 or O % 4 or E > 1024 or O > 1024 or H % 8 or V % 4:
             return False
-        return hasattr(self.joint, "text_ln") or O == H
+        return has_text or O == H
+
+    def _lstm_loop(self, frames_list, max_length, scan_frames):
+        """The token lists of up to 32 utterances' frames ([T_u, H] each) decoded in lockstep by engine.greedy_decode_lstm with the
+        model's live parameters; one host synchronisation."""
+        from . import engine
+        joint = self.joint
+        tl = getattr(joint, "text_ln", None)
+        out = engine.greedy_decode_lstm(frames_list, self.predictor._decode_bundle(), tl.weight if tl is not None else None,
+                                        tl.bias if tl is not None else None, joint.joint_ln.weight, joint.joint_ln.bias, joint.blank_idx,
+                                        max_length, max_per_frame=10,
+                                        scan_frames=max(1, min(int(scan_frames) if scan_frames > 0 else 32, 128)))
+        self.predictor.last_backend = "engine"
+        self.last_decode_path = "lstm_loop"
+        state, toks = out[:2]
+        host = torch.cat((state, toks), dim=1).tolist()  # the batch's one synchronisation: [N][8 state words | tokens]
+        return [row[9:9 + row[2]] for row in host]
 
     def _decode_tables(self):
         """The persistent decode's model tables (engine.greedy_decode_tables: conv2's pack, conv1 as tap tables, the folded text_ln) built
@@ -173,15 +200,21 @@ class RNNTModel(torch.nn.Module):
         stateful = self._predictor_is_stateful()
         audio = self.encoder(mel_features).permute(0, 2, 1)
         # device_loop (None: when possible): the WHOLE loop on the device — scan, argmax, the loop's bookkeeping and the
-        # ConvPredictor step per token as one fixed kernel sequence per iteration — and ONE host synchronisation per
-        # utterance (the scan path below still synchronises once per emitted token).
+        # predictor's step per token (ConvPredictor or LSTMPredictor) as one fixed kernel sequence per iteration — and ONE host
+        # synchronisation per utterance (the scan path below still synchronises once per emitted token).  An LSTM model takes
+        # it by default because it beat the host loop at both timed lengths (2.5x at T = 1000, 2.2x at T = 100;
+        # profiles/lstm_decode_bench.txt).
         if device_loop is None:
-            device_loop = scan_frames > 0 and not stateful and self._device_loop_ok(audio)
+            device_loop = scan_frames > 0 and self._device_loop_ok(audio)
         if device_loop:
             from . import engine
-            if stateful or not self._device_loop_ok(audio):
-                raise RuntimeError("greedy_decode(device_loop=True) needs the engine's stateless ConvPredictor in eval mode on a HIP device")
+            if not self._device_loop_ok(audio):
+                raise RuntimeError("greedy_decode(device_loop=True) needs the engine's ConvPredictor or LSTMPredictor in eval mode on a HIP device")
             frames = self._decode_frames(audio)
+            if stateful:
+                if persistent:
+                    raise RuntimeError("greedy_decode(persistent=True): there is no persistent decode kernel for the LSTMPredictor")
+                return self._lstm_loop([frames], max_length, scan_frames)[0]
             args = (frames, *self._decode_bundle(), max_length)
             if persistent is None:  # one persistent launch per utterance where the engine takes the sizes
                 persistent = engine.greedy_decode_persistent_supported(frames.shape[0], *self._decode_sizes())
@@ -205,7 +238,9 @@ class RNNTModel(torch.nn.Module):
                                                         scan_frames=max(1, min(int(scan_frames) if scan_frames > 0 else 64, 128)))
                 st, host = state.tolist(), None
             engine.check_decode_state(st)
+            self.last_decode_path = "persistent" if host is not None else "loop"
             return host[9:9 + st[2]] if host is not None else toks[1:1 + st[2]].tolist()
+        self.last_decode_path = "host"
         from .stream import HostGreedyLoop  # (one host loop, resumable: GreedyStream's host path runs it too)
         loop = HostGreedyLoop(self, max_length, max_symbols_per_frame=10, scan_frames=scan_frames)
         loop.run(audio)
@@ -218,21 +253,46 @@ class RNNTModel(torch.nn.Module):
         from .stream import GreedyStream
         return GreedyStream(self, max_length=max_length, max_symbols_per_frame=max_symbols_per_frame, persistent=persistent)
 
+    # greedy_decode_many's default batch with an LSTMPredictor: of 4, 8, 16 and 32 the only one within 10 % of the best time per utterance
+    # at both timed lengths (2.0 ms at T = 1000, 0.56 ms at T = 100; profiles/lstm_decode_bench.txt)
+    LSTM_DECODE_BATCH = 32
+
     @torch.no_grad()
-    def greedy_decode_many(self, mels, max_length: int = 200, concurrency=None):
+    def greedy_decode_many(self, mels, max_length: int = 200, concurrency=None, batch=None):
         """Greedy decode of SEVERAL utterances (a list of (1, C, L) mel tensors): `greedy_decode` of each, but with up to `concurrency`
         utterances in flight on streams of their own — the persistent decode of one utterance keeps 16-128 of the device's compute units
         (rnnt_engine_greedy_decode_persistent: one workgroup per 16 vocabulary entries), so a 256-CU device runs four 1024-entry decodes
         side by side.  Nothing synchronises until every utterance is enqueued.  The reference decodes utterance by utterance
         (rnnt/model.py:131-139 called from train.py:170-201); this is that loop, returning the same token lists in the same order.
         `concurrency` defaults to as many decodes as are guaranteed to be resident together (compute units // workgroups per decode, at most
-        8); more would risk none of them being complete on the device (each waits for all of its workgroups)."""
+        8); more would risk none of them being complete on the device (each waits for all of its workgroups).
+        With an rnnt_amd.LSTMPredictor the utterances the device loop takes (`_device_loop_ok`) advance `batch` (1 .. 32, default
+        LSTM_DECODE_BATCH) at a time through ONE loop (rnnt_engine_greedy_decode_lstm: the utterances are the rows of every product's
+        tile), one host synchronisation per batch; any other utterance, and every other stateful predictor, takes the host loop.
+        `concurrency` is not used then.  Entry i of the result is greedy_decode(mels[i]) either way."""
         from . import engine
         if not mels:
             return []
         assert all(m.shape[0] == 1 for m in mels), "one utterance per entry"
         lens = [torch.tensor([m.shape[-1]], device=m.device) for m in mels]
         dev = mels[0].device
+        if self._predictor_is_stateful():
+            batch = self.LSTM_DECODE_BATCH if batch is None else int(batch)
+            if not 1 <= batch <= engine.LSTM_DECODE_MAX:
+                raise ValueError(f"greedy_decode_many: batch={batch} outside [1, {engine.LSTM_DECODE_MAX}]")
+            out, path = [None] * len(mels), "host"
+            audios = [self.encoder(m).permute(0, 2, 1) for m in mels]
+            looped = [i for i, a in enumerate(audios) if max_length >= 2 and self._device_loop_ok(a)]
+            for i in range(len(mels)):
+                if i not in looped:
+                    out[i] = self.greedy_decode(mels[i], lens[i], max_length=max_length, device_loop=False)
+            for k in range(0, len(looped), batch):
+                group = looped[k:k + batch]
+                for i, toks in zip(group, self._lstm_loop([self._decode_frames(audios[i]) for i in group], max_length, 32)):
+                    out[i] = toks
+                path = "lstm_loop"
+            self.last_decode_path = path
+            return out
         ok = (max_length >= 2 and dev.type == "cuda" and not self._predictor_is_stateful()
               and self._device_loop_ok(torch.zeros(1, 1, device=dev)))
         if ok:
@@ -262,6 +322,7 @@ class RNNTModel(torch.nn.Module):
                 out.append(self.greedy_decode(mel, l, max_length=max_length))
             else:
                 out.append(host[9:9 + host[2]])
+        self.last_decode_path = "persistent"
         return out
 
     # ---- beam search: frame-synchronous, <= max_symbols_per_frame labels per frame, hypotheses merged by sequence
