@@ -609,6 +609,33 @@ int rnnt_engine_beam_decode_batch(const void *frames, int64_t frame_stride, int 
                                   void *stream);
 
 /*
+ * The same search with the stateful LSTMPredictor (DESIGN.md §4h "LSTM") for n_utt (1 .. 32) independent utterances in lockstep; the
+ * single search is n_utt = 1.  predictor([blank] + y)[-1] is the output of ONE step from the state after y[:-1], fed y[-1]; the start
+ * is the step from zero state fed the blank.  Row 16 u + s of every product is slot s of utterance u.  A hypothesis owns an LSTM
+ * state [L][2][Hd] that lives in one of its utterance's 32 rows of a pool in the workspace and follows it through the selection as
+ * an INDEX: a survivor keeps its row, a kept label records its parent's row and takes a row no slot refers to, nothing is copied.
+ * A round with a predictor step is 6 + 2 L launches (2 more with text_ln): embedding + input LayerNorm, per layer both gate products
+ * (the recurrent operand read through the parent's row) and the row step, linear + output LayerNorm, joint.text_ln, then the joint,
+ * reduce and selection kernels of rnnt_engine_beam_decode_batch.  Kernels return at once where no slot awaits a step.
+ *   model arguments (p .. eps_out, text_W .. blank) as rnnt_engine_greedy_decode_lstm; frames, rows, utt, max_frames, state
+ *   int32[n_utt][32], tokens int32[n_utt][beam][max_length], scores double[n_utt][beam], iterations (0 = max_frames * max_per_frame
+ *   + 1), init, host_flag as rnnt_engine_beam_decode_batch.  The workspace's state part (searches, pool) is zero-filled at init; no
+ *   value the caller left in the rest is read.
+ * An utterance's tokens, state words and scores are bit-identical whatever its neighbours, its position and n_utt.
+ * Checked before anything is enqueued: RNNT_ERR_INVALID_ARG (null pointers, non-positive dims, beam < 1, max_length < 2),
+ * RNNT_ERR_UNSUPPORTED (n_utt > 32, beam > 16, max_length > 65536, rnnt_engine_lstm_predictor_fwd's limits, H % 8, V % 4),
+ * RNNT_ERR_WORKSPACE.
+ */
+int rnnt_engine_beam_decode_lstm_workspace_bytes(int n_utt, int S, int E, int Hd, int O, int L, int layer_norm, int H, int V, int has_text,
+                                                 int max_length, int beam, size_t *out);
+int rnnt_engine_beam_decode_lstm(const void *frames, int64_t frame_stride, int rows, const int32_t *utt, int n_utt, int max_frames,
+                                 const rnnt_lstm_predictor_params *p, int S, int E, int Hd, int O, int L, int layer_norm, float eps_in,
+                                 float eps_lstm, float eps_out, const void *text_W, const void *text_b, const void *W, const void *bias,
+                                 int H, int V, int blank, int max_length, int max_per_frame, int beam, int iterations, int init,
+                                 int32_t *host_flag, int32_t *state, int32_t *tokens, double *scores, void *workspace, size_t ws_bytes,
+                                 void *stream);
+
+/*
  * Contextual biasing (hotword boosting) of the two searches above (DESIGN.md §4h "Context"): rnnt_engine_beam_decode_ctx and
  * rnnt_engine_beam_decode_batch_ctx are rnnt_engine_beam_decode and rnnt_engine_beam_decode_batch with one more argument, a phrase list
  * as an Aho-Corasick trie (ONE graph, shared by every utterance of a batch).  Node 0 is the root; node m's children are entries

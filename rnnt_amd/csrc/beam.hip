@@ -38,6 +38,8 @@
 // Aho–Corasick trie in flat device arrays, and a node per slot — as the LAST member of the pack of k_beam_reduce and k_beam_select only:
 // the reduce re-ranks a slot's labels by logit + delta(node, label) in a tail of its wave 0, the selection adds the delta in fp64 and
 // moves the nodes with the hypotheses.  The packs <> and <BeamBatch> are the instantiations they were; a stream takes no graph.
+// The search with the LSTMPredictor (DESIGN.md §4h "LSTM"; rnnt_engine_beam_decode_lstm, at the end of the file): the batched search whose
+// predictor step is lstm.hip's and whose selection takes a BeamLstm as the pack's last member — it moves a hypothesis's LSTM state as an index.
 // Arithmetic: fp32 products (fp32 MFMA, exact fp32 as fmaf chains), log-sum-exp in fp32, SCORES in fp64 (the log-probability
 // (double)logit - (double)lse is added to a double score; logaddexp in double).
 // Ties (no result may depend on one): finished entries first, then parent slot ascending, then token id ascending; the
@@ -140,6 +142,16 @@ __device__ __forceinline__ BeamBatch beam_batch(const BeamCtx &) { return beam_b
 __device__ __forceinline__ BeamBatch beam_batch(const BeamBatch &b, const BeamCtx &) { return b; }
 __device__ __forceinline__ const BeamCtx &beam_ctx(const BeamCtx &c) { return c; }
 __device__ __forceinline__ const BeamCtx &beam_ctx(const BeamBatch &, const BeamCtx &c) { return c; }
+// a search with the LSTMPredictor (DESIGN.md §4h "LSTM"): a BeamLstm ends the pack of k_beam_select only — the batched search whose selection
+// also moves the hypotheses' LSTM state, as an INDEX: a hypothesis owns one of its utterance's 32 rows of the state pool
+struct BeamLstm {
+    int *srow;        // [2][BM] per utterance (double-buffered like len and hash): the pool row (0 .. 31) that holds the slot's state
+    int *own, *par;   // [n_utt][BM] for the next round's predictor step: 32 u + the slot's row | 32 u + the row of the state it continues
+};
+__device__ __forceinline__ BeamBatch beam_batch(const BeamBatch &b, const BeamLstm &) { return b; }
+__device__ __forceinline__ const BeamLstm &beam_lstm(const BeamBatch &, const BeamLstm &l) { return l; }
+template <typename... U> struct beam_has_lstm { static constexpr bool value = false; };
+template <> struct beam_has_lstm<BeamBatch, BeamLstm> { static constexpr bool value = true; };
 template <typename... U> struct beam_has_ctx { static constexpr bool value = false; };
 template <> struct beam_has_ctx<BeamCtx> { static constexpr bool value = true; };
 template <> struct beam_has_ctx<BeamBatch, BeamCtx> { static constexpr bool value = true; };
@@ -579,8 +591,8 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamSlots P, const float *_
                                                      int max_per_frame, int32_t *__restrict__ state, int32_t *__restrict__ out_tokens,
                                                      double *__restrict__ out_scores, int32_t *host_flag, U... ub)
 {
-    constexpr bool CTX = beam_has_ctx<U...>::value;
-    __shared__ int c_node[CTX ? BEAM_NC : 1], o_node[CTX ? BM : 1];
+    constexpr bool CTX = beam_has_ctx<U...>::value, LSTM = beam_has_lstm<U...>::value;
+    __shared__ int c_node[CTX ? BEAM_NC : 1], o_node[CTX ? BM : 1], o_row[LSTM ? BM : 1];
     __shared__ double c_score[BEAM_NC];
     __shared__ int c_kind[BEAM_NC], c_a[BEAM_NC], c_b[BEAM_NC], c_src[BEAM_NC];
     __shared__ unsigned char c_valid[BEAM_NC];
@@ -601,6 +613,7 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamSlots P, const float *_
         o_st[tid] = tid < beam ? P.status[idx] : SL_EMPTY;
         o_score[tid] = P.score[idx]; o_hash[tid] = P.hash[idx]; o_len[tid] = P.len[idx];
         if constexpr (CTX) o_node[tid] = beam_ctx_node(beam_ctx(ub...), beam_utt(beam_ctx(ub...).node, uoff)[idx]);
+        if constexpr (LSTM) o_row[tid] = beam_utt(beam_lstm(ub...).srow, uoff)[idx] & 31;
     }
     if (tid < BM) s_keep[tid] = -1;
     for (int c = tid; c < BEAM_NC; c += 256) c_valid[c] = 0;
@@ -720,6 +733,30 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamSlots P, const float *_
             P.score[idx] = -__builtin_inf(); P.len[idx] = 0; P.hash[idx] = 0ull; P.status[idx] = SL_EMPTY; P.need[idx] = 0;
             if constexpr (CTX) beam_utt(beam_ctx(ub...).node, uoff)[idx] = 0;
         }
+        if constexpr (LSTM) {
+            // A survivor (a capped label merged into a finished entry is one) keeps its row: nothing is copied.  The q-th kept label takes the
+            // q-th row no slot of the current buffer refers to — at most 16 of the 32 are referred to, at most 16 labels are kept — and records
+            // its parent's: siblings read one row and write different ones, and no row read in the next round's step is written in it.
+            const BeamLstm &ls = beam_lstm(ub...);
+            int mine = 0, parent = 0;
+            if (tid < n) {
+                const int c = s_final[tid];
+                mine = parent = o_row[c_src[c]];
+                if (c_kind[c]) {
+                    unsigned used = 0u;
+                    for (int i = 0; i < beam; ++i)
+                        if (o_st[i] != SL_EMPTY) used |= 1u << o_row[i];
+                    int q = 0;
+                    for (int s = 0; s < tid; ++s) q += c_kind[s_final[s]];
+                    unsigned freer = ~used;
+                    for (int i = 0; i < q; ++i) freer &= freer - 1u;
+                    mine = freer ? __builtin_ctz(freer) : 0;  // (never 0 by the count above)
+                }
+            }
+            beam_utt(ls.srow, uoff)[idx] = mine;
+            ls.own[u * BM + tid] = 32 * (int)u + mine;
+            ls.par[u * BM + tid] = 32 * (int)u + parent;
+        }
     }
     int *tok_new = P.tok + (size_t)nb * BM * max_length;
     for (int e = tid; e < n * max_length; e += 256) {
@@ -832,7 +869,7 @@ size_t beam_stream_block_bytes(int S, int E, int O, int H, int V, int has_text, 
     return beam_layout(S, E, O, H, V, has_text, max_length, n_streams, true).state_end;
 }
 
-static BeamSlots beam_slots(char *ws, const BeamLayout &L)
+template <typename Layout> static BeamSlots beam_slots(char *ws, const Layout &L)  // (BeamLayout, or the LSTM search's BeamLstmLayout)
 {
     BeamSlots P;
     P.score = (double *)(ws + L.score); P.hash = (unsigned long long *)(ws + L.hash);
@@ -930,4 +967,81 @@ void launch_beam_decode(const BeamArgs &ba, hipStream_t st)
         enqueue(BeamBatch{L.block, ba.utt, ba.rows, (unsigned *)(ws + L.n_done)});
     else
         enqueue();
+}
+
+// ---- the search with the LSTMPredictor (rnnt_engine_beam_decode_lstm; DESIGN.md §4h "LSTM"): the batched search, n_utt = 1 included, whose
+// predictor step is lstm.hip's (launch_beam_lstm_step) and whose selection moves the LSTM state as an index into a pool of 32 rows per
+// utterance.  Workspace: per utterance { slot buffers | logits | reduce output | state rows' indices }, then the done counter, the
+// step's row indices, the pool — all zero-filled at init — and the step's scratch, of which no value outlives a round.
+static_assert(BEAM_ST_DONE == BS_DONE && BEAM_ST_NEW == BS_NEW && BEAM_ST_CUR == BS_CUR, "the predictor step reads the search's state words");
+struct BeamLstmLayout { size_t score, hash, len, status, need, tok, pvec, logits, red, srow, block, n_done, own, par, pool, state_end, scratch, total; };
+static BeamLstmLayout beam_lstm_layout(int n_utt, int E, int Hd, int O, int L, int H, int V, int max_length)
+{
+    BeamLstmLayout w;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+    w.score = take(2 * BM * sizeof(double));
+    w.hash = take(2 * BM * sizeof(unsigned long long));
+    w.len = take(2 * BM * 4);
+    w.status = take(2 * BM * 4);
+    w.need = take(2 * BM * 4);
+    w.tok = take((size_t)2 * BM * max_length * 4);
+    w.pvec = take((size_t)2 * BM * H * 4);
+    w.logits = take((size_t)BM * V * 4);
+    w.red = take((size_t)BM * BEAM_RED * 4);
+    w.srow = take(2 * BM * 4);
+    w.block = o;
+    o *= (size_t)n_utt;
+    w.n_done = take(4);
+    w.own = take((size_t)n_utt * BM * 4);
+    w.par = take((size_t)n_utt * BM * 4);
+    w.pool = take((size_t)n_utt * 32 * L * 2 * Hd * 4);
+    w.state_end = o;
+    w.scratch = take(beam_lstm_step_floats(n_utt, E, Hd, O, H) * 4);
+    w.total = o;
+    return w;
+}
+size_t beam_lstm_workspace_bytes(int n_utt, int E, int Hd, int O, int L, int H, int V, int max_length)
+{
+    return beam_lstm_layout(n_utt, E, Hd, O, L, H, V, max_length).total;
+}
+
+// the start: the empty hypothesis of every utterance continues the zero state of row 0 (the pool was zero-filled) and owns row 1
+__global__ void k_beam_lstm_init(BeamLstm ls, size_t stride)
+{
+    const unsigned u = blockIdx.x, s = threadIdx.x;
+    if (s >= BM) return;
+    if (s == 0) beam_utt(ls.srow, u * stride)[0] = 1;
+    ls.own[u * BM + s] = 32 * (int)u + (s == 0 ? 1 : 0);
+    ls.par[u * BM + s] = 32 * (int)u;
+}
+
+void launch_beam_decode_lstm(const BeamLstmArgs &a, hipStream_t st)
+{
+    const BeamLstmStep &m = a.s;
+    const int H = m.H, V = a.V, ML = m.max_length;
+    const unsigned N = m.n_utt;
+    const BeamLstmLayout w = beam_lstm_layout(N, m.E, m.Hd, m.O, m.L, H, V, ML);
+    char *ws = (char *)a.workspace;
+    const BeamSlots P = beam_slots(ws, w);
+    float *logits = (float *)(ws + w.logits), *red = (float *)(ws + w.red);
+    const BeamBatch bb{w.block, a.utt, a.rows, (unsigned *)(ws + w.n_done)};
+    const BeamLstm ls{(int *)(ws + w.srow), (int *)(ws + w.own), (int *)(ws + w.par)};
+    BeamLstmStep step = m;
+    step.state = a.state; step.need = P.need; step.len = P.len; step.tok = P.tok; step.pvec = P.pvec; step.stride = w.block;
+    step.own = ls.own; step.par = ls.par; step.pool = (float *)(ws + w.pool); step.scratch = (float *)(ws + w.scratch);
+    if (a.init) {
+        launch_fill32(ws, 0u, w.state_end, st);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_init<BeamBatch>), dim3(1, N), dim3(64), 0, st, P, a.state, a.blank, ML, bb);
+        hipLaunchKernelGGL(k_beam_lstm_init, dim3(N), dim3(64), 0, st, ls, w.block);
+    }
+    for (int it = 0; it < a.iterations; ++it) {
+        launch_beam_lstm_step(step, st);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_joint<BeamBatch>), dim3((V + 15) / 16, N), dim3(256), 0, st, a.state, a.frames, a.frame_stride,
+                           P.pvec, a.W, a.bias, H, V, logits, bb);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_reduce<BeamBatch>), dim3(a.beam, N), dim3(1024), 0, st, a.state, P.status, logits, V, a.blank,
+                           a.beam, red, bb);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_select<BeamBatch, BeamLstm>), dim3(1, N), dim3(256), 0, st, P, red, a.beam, V, H, 0, ML,
+                           a.max_per_frame, a.state, a.tokens, a.scores, a.host_flag, bb, ls);
+    }
 }

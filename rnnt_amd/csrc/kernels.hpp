@@ -325,3 +325,29 @@ void launch_beam_decode(const BeamArgs &a, hipStream_t st);
 size_t beam_stream_block_bytes(int S, int E, int O, int H, int V, int has_text, int max_length, int n_streams);
 void launch_beam_stream_init(void *block, int32_t *state, double *scores, int S, int E, int O, int H, int V, int has_text, int max_length,
                              int beam, int blank, int n_streams, int first, int count, hipStream_t st);
+
+// ---- beam search with the LSTMPredictor (rnnt_engine_beam_decode_lstm; DESIGN.md §4h "LSTM"): the batched search of beam.hip whose predictor
+// step is lstm.hip's.  Row 16 u + s of every product is slot s of utterance u.
+enum { BEAM_ST_DONE = 3, BEAM_ST_NEW = 4, BEAM_ST_CUR = 6 };  // the words of a search's state the predictor step reads (beam.hip: BS_*)
+struct BeamLstmStep {
+    // the searches, as beam.hip lays them out: utterance u's copy of a per-search array lies u * stride BYTES after utterance 0's
+    const int32_t *state;          // [n_utt][32]
+    const int *need, *len, *tok;   // [2][16] | [2][16] | [2][16][max_length]
+    float *pvec;                   // [2][16][H]: the step's result goes to the slot's row of the CURRENT buffer
+    size_t stride; int n_utt, max_length;
+    // LSTM state: `pool` [32 n_utt][L][2][Hd]; slot 16 u + s continues the state in row par[16 u + s] and owns row own[16 u + s]
+    const int *own, *par; float *pool;
+    rnnt_lstm_predictor_params p; int S, E, Hd, O, L, ln; float eps_in, eps_lstm, eps_out;
+    const float *text_W, *text_b; int H;  // joint.text_ln or NULL (then O == H)
+    float *scratch;                       // beam_lstm_step_floats(...) floats; no value in it outlives a round
+};
+size_t beam_lstm_step_floats(int n_utt, int E, int Hd, int O, int H);
+void launch_beam_lstm_step(const BeamLstmStep &a, hipStream_t st);  // lstm.hip: the predictor step of one round, 3 + 2 L launches (2 more with text_ln)
+struct BeamLstmArgs {
+    BeamLstmStep s;  // the model; state .. pool and scratch are filled in by launch_beam_decode_lstm
+    const float *frames; long frame_stride; int rows; const int32_t *utt;
+    const float *W, *bias; int V, blank, max_per_frame, beam, iterations, init;
+    int32_t *host_flag, *state, *tokens; double *scores; void *workspace;
+};
+size_t beam_lstm_workspace_bytes(int n_utt, int E, int Hd, int O, int L, int H, int V, int max_length);
+void launch_beam_decode_lstm(const BeamLstmArgs &a, hipStream_t st);  // beam.hip

@@ -16,7 +16,8 @@
 // (256 of them at Hd = 512, <= 32 MFMAs per wave); the partial tiles are added, in order, by the row kernel that follows.
 // Exact fp32 products (v_mfma_f32_32x32x2_f32 / FMA) only.
 // No workgroup waits on another; no atomics on results: every sum has a fixed order.
-// The greedy decode with this predictor as a device loop (rnnt_engine_greedy_decode_lstm, k_ld_*) is at the end of the file.
+// The greedy decode with this predictor as a device loop (rnnt_engine_greedy_decode_lstm, k_ld_*) is at the end of the file, and after it
+// the predictor step of a beam-search round (rnnt_engine_beam_decode_lstm, k_bl_*; the search itself is beam.hip's).
 #include "../../include/rnnt_engine.h"
 #include "kernels.hpp"
 #include "smallgemm.hpp"
@@ -137,7 +138,9 @@ __global__ __launch_bounds__(256) void k_lstm_init(const float *__restrict__ h0,
 // NN = false: W [N][K] rows ldw apart (h p2g^T: N = 4 Hd, K = Hd); NN = true: W [K][N] (dgates p2g: N = Hd, K = 4 Hd).
 // grid (ceil(N/32), KS, ceil(M/32)); chunk c of 8 contraction elements belongs to wave c % 4 of split (c / 4) % KS; the four
 // waves' tiles are added through LDS in wave order.
-struct RecArgs { const float *A; long lda; const float *W; long ldw; float *P; int M, N, K, KS; };
+// `rows` (NULL for every product but the beam search's): operand row m is A's row rows[m], held inside [0, R) — a hypothesis reads the
+// LSTM state it continues through its index (DESIGN.md §4h "LSTM"); the output row stays m.
+struct RecArgs { const float *A; long lda; const float *W; long ldw; float *P; int M, N, K, KS; const int *rows = nullptr; int R = 0; };
 
 // one workgroup's tile of such a product: output columns n0 .. n0 + 31, rows m0 .. m0 + 31, contraction range `split`; red: 3 * 1024 floats of LDS
 template <bool NN>
@@ -146,6 +149,7 @@ __device__ __forceinline__ void rec_tile(const RecArgs &a, int n0, int split, in
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i = lane & 31, half = lane >> 5;
     const int row = min(m0 + i, a.M - 1), col = min(n0 + i, a.N - 1);
+    const int arow = a.rows ? min(max(a.rows[row], 0), a.R - 1) : row;
     const int KC = (a.K + 7) / 8;
     f32x16 acc;
 #pragma unroll
@@ -157,7 +161,7 @@ __device__ __forceinline__ void rec_tile(const RecArgs &a, int n0, int split, in
             const int c = c0 + 4 * a.KS * j, k = 8 * c + 4 * half;
             const bool ok = c < KC && k < a.K;
             const int kk = ok ? k : 0;
-            x[j] = *(const f32x4 *)(a.A + (long)row * a.lda + kk);
+            x[j] = *(const f32x4 *)(a.A + (long)arow * a.lda + kk);
             if (!ok) x[j] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (NN) {
 #pragma unroll
@@ -518,16 +522,11 @@ __global__ __launch_bounds__(256) void k_ld_init(int32_t *__restrict__ states, i
     if (i == 0) ctrl[0] = 0;
 }
 
-// x1[u] = LayerNorm_E(embedding[the utterance's newest token]) for the utterances that have one
-__global__ __launch_bounds__(256) void k_ld_embed(const int32_t *__restrict__ states, const int32_t *__restrict__ tokens, int max_length,
-                                                  const float *__restrict__ emb, int S, const float *__restrict__ gamma,
-                                                  const float *__restrict__ beta, float eps, int E, float *__restrict__ x1)
+// one row of the embedding + input LayerNorm: out[E] = LayerNorm_E(embedding[tok]) (the workgroup's 256 threads; red: 8 floats of LDS)
+__device__ __forceinline__ void ld_embed_row(const float *__restrict__ emb, int S, int tok, const float *__restrict__ gamma,
+                                             const float *__restrict__ beta, float eps, int E, float *__restrict__ out, float *red)
 {
-    __shared__ float red[8];
-    const int u = blockIdx.x, tid = threadIdx.x;
-    const int32_t *st = states + 8 * u;
-    if (!st[4]) return;
-    int tok = tokens[(long)u * max_length + st[2]];
+    const int tid = threadIdx.x;
     tok = tok < 0 ? 0 : (tok >= S ? S - 1 : tok);
     const float *e = emb + (long)tok * E;
     float s = 0.f, q = 0.f, unused = 0.f;
@@ -537,7 +536,19 @@ __global__ __launch_bounds__(256) void k_ld_embed(const int32_t *__restrict__ st
     for (int i = tid; i < E; i += 256) { const float d = e[i] - mean; q += d * d; }
     block_sum2(q, unused, red);
     const float rstd = rsqrtf(q / E + eps);
-    for (int i = tid; i < E; i += 256) x1[(long)u * E + i] = (e[i] - mean) * rstd * gamma[i] + beta[i];
+    for (int i = tid; i < E; i += 256) out[i] = (e[i] - mean) * rstd * gamma[i] + beta[i];
+}
+
+// x1[u] = LayerNorm_E(embedding[the utterance's newest token]) for the utterances that have one
+__global__ __launch_bounds__(256) void k_ld_embed(const int32_t *__restrict__ states, const int32_t *__restrict__ tokens, int max_length,
+                                                  const float *__restrict__ emb, int S, const float *__restrict__ gamma,
+                                                  const float *__restrict__ beta, float eps, int E, float *__restrict__ x1)
+{
+    __shared__ float red[8];
+    const int u = blockIdx.x;
+    const int32_t *st = states + 8 * u;
+    if (!st[4]) return;
+    ld_embed_row(emb, S, tokens[(long)u * max_length + st[2]], gamma, beta, eps, E, x1 + (long)u * E, red);
 }
 
 // whether any utterance has a label for the predictor to take in (workgroup-uniform; n_utt <= 32)
@@ -568,14 +579,14 @@ struct LdStep {
     int Hd;
 };
 
-// k_lstm_step_fwd's definition in eval mode, nothing kept, for the rows whose utterance has a new label: one workgroup per utterance
+// k_lstm_step_fwd's definition in eval mode, nothing kept, for ONE row (the workgroup's 256 threads; red: 8 floats of LDS): `gp` the
+// row's first partial product, `c_prev` [Hd] the cell it continues, `h` / `c` [Hd] where the new state goes (c may be c_prev: a thread
+// reads a unit's cell before it writes it), `h2` / `c2` a second copy or NULL
 template <bool LN>
-__global__ __launch_bounds__(256) void k_ld_step(LdStep a)
+__device__ __forceinline__ void ld_step_row(const LdStep &a, const float *__restrict__ gp, const float *c_prev, float *h, float *c_new,
+                                            float *h2, float *c2, float *red)
 {
-    __shared__ float red[8];
-    const int b = blockIdx.x, tid = threadIdx.x, Hd = a.Hd;
-    if (!a.states[8 * b + 4]) return;
-    const float *gp = a.gp + (long)b * 4 * Hd;
+    const int tid = threadIdx.x, Hd = a.Hd;
     float g[UNITS][4];
 #pragma unroll
     for (int k = 0; k < UNITS; ++k) {
@@ -620,7 +631,7 @@ __global__ __launch_bounds__(256) void k_ld_step(LdStep a)
         float pre[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) pre[q] = LN ? g[k][q] * a.gw[q * Hd + j] + a.gb[q * Hd + j] : g[k][q];
-        c[k] = sigmoidf(pre[1]) * a.c[(long)b * Hd + j] + sigmoidf(pre[0]) * tanhf(pre[2]);
+        c[k] = sigmoidf(pre[1]) * c_prev[j] + sigmoidf(pre[0]) * tanhf(pre[2]);
         o[k] = sigmoidf(pre[3]);
     }
     if (LN) {
@@ -643,27 +654,36 @@ __global__ __launch_bounds__(256) void k_ld_step(LdStep a)
         const int j = tid + 256 * k;
         if (j >= Hd) continue;
         const float cn = LN ? c[k] * a.cw[j] + a.cb[j] : c[k];
-        const float h = o[k] * tanhf(cn);
-        a.c[(long)b * Hd + j] = cn;
-        a.h[(long)b * Hd + j] = h;
-        if (a.h_out) { a.c_out[(long)b * Hd + j] = cn; a.h_out[(long)b * Hd + j] = h; }
+        const float hv = o[k] * tanhf(cn);
+        c_new[j] = cn;
+        h[j] = hv;
+        if (h2) { c2[j] = cn; h2[j] = hv; }
     }
 }
 
-// out[u] = sum of the nsp partial products + bias, LN: then LayerNorm_N (gamma, beta, eps) — for the rows with a new label
+// the step of the rows whose utterance has a new label: one workgroup per utterance, h and c in place
 template <bool LN>
-__global__ __launch_bounds__(256) void k_ld_rowfin(const int32_t *__restrict__ states, const float *__restrict__ gp, int nsp, long gp_ld, int N,
-                                                   const float *__restrict__ bias, const float *__restrict__ gamma,
-                                                   const float *__restrict__ beta, float eps, float *__restrict__ out)
+__global__ __launch_bounds__(256) void k_ld_step(LdStep a)
 {
     __shared__ float red[8];
-    const int u = blockIdx.x, tid = threadIdx.x;
-    if (!states[8 * u + 4]) return;
-    float *y = out + (long)u * N;
+    const int b = blockIdx.x, Hd = a.Hd;
+    if (!a.states[8 * b + 4]) return;
+    float *h = a.h + (long)b * Hd, *c = a.c + (long)b * Hd;
+    ld_step_row<LN>(a, a.gp + (long)b * 4 * Hd, c, h, c, a.h_out ? a.h_out + (long)b * Hd : nullptr,
+                    a.h_out ? a.c_out + (long)b * Hd : nullptr, red);
+}
+
+// one row: y[N] = sum of the nsp partial products (the row's first at `gp`, gp_ld apart) + bias, LN: then LayerNorm_N (gamma, beta, eps)
+template <bool LN>
+__device__ __forceinline__ void ld_rowfin_row(const float *__restrict__ gp, int nsp, long gp_ld, int N, const float *__restrict__ bias,
+                                              const float *__restrict__ gamma, const float *__restrict__ beta, float eps,
+                                              float *__restrict__ y, float *red)
+{
+    const int tid = threadIdx.x;
     float s = 0.f, q = 0.f, unused = 0.f;
     for (int i = tid; i < N; i += 256) {  // (a thread reads back only what it wrote itself)
-        float v = gp[(long)u * N + i];
-        for (int sp = 1; sp < nsp; ++sp) v += gp[sp * gp_ld + (long)u * N + i];
+        float v = gp[i];
+        for (int sp = 1; sp < nsp; ++sp) v += gp[sp * gp_ld + i];
         v += bias[i];
         y[i] = v;
         s += v;
@@ -675,6 +695,18 @@ __global__ __launch_bounds__(256) void k_ld_rowfin(const int32_t *__restrict__ s
     block_sum2(q, unused, red);
     const float rstd = rsqrtf(q / N + eps);
     for (int i = tid; i < N; i += 256) y[i] = (y[i] - mean) * rstd * gamma[i] + beta[i];
+}
+
+// out[u] = that row — for the utterances with a new label
+template <bool LN>
+__global__ __launch_bounds__(256) void k_ld_rowfin(const int32_t *__restrict__ states, const float *__restrict__ gp, int nsp, long gp_ld, int N,
+                                                   const float *__restrict__ bias, const float *__restrict__ gamma,
+                                                   const float *__restrict__ beta, float eps, float *__restrict__ out)
+{
+    __shared__ float red[8];
+    const int u = blockIdx.x;
+    if (!states[8 * u + 4]) return;
+    ld_rowfin_row<LN>(gp + (long)u * N, nsp, gp_ld, N, bias, gamma, beta, eps, out + (long)u * N, red);
 }
 
 // an utterance's first row and frame count from the caller's device table, held inside the packed buffer whatever the table says
@@ -877,14 +909,103 @@ void launch_ld_loop(const LdArgs &a, hipStream_t st)
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// The predictor step of a beam-search round (rnnt_engine_beam_decode_lstm; DESIGN.md §4h "LSTM"): the kernels above with a beam's slots
+// as rows — row 16 u + s is slot s of utterance u, so a 32-row tile holds two utterances — for the slots that took a label
+// (BeamSlots::need of the search's current buffer).  A slot CONTINUES the state in pool row par[row] (its parent hypothesis's: siblings
+// share it) and writes its own to pool row own[row]; the selection (beam.hip) hands out rows so that nothing read in a round is written
+// in it.  Same tile body, contraction ranges and row definitions as the greedy loop: the numbers of a slot depend on its token
+// sequence alone.  Every kernel returns at once where nothing needs a step.
+// ---------------------------------------------------------------------------------------
+template <typename T> __device__ __forceinline__ T *bl_utt(T *p, size_t off) { return (T *)((char *)p + off); }
+
+// the slot (u, s) of this workgroup (grid (16, n_utt)) if it awaits its step: its search's current buffer, else -1
+__device__ __forceinline__ int bl_slot_cur(const BeamLstmStep &a, int u, int s)
+{
+    const int32_t *st = a.state + 32 * u;
+    if (st[BEAM_ST_DONE] || !st[BEAM_ST_NEW]) return -1;
+    const int cur = st[BEAM_ST_CUR] & 1;
+    return bl_utt(a.need, u * a.stride)[cur * 16 + s] ? cur : -1;
+}
+__device__ __forceinline__ long bl_pool_row(const BeamLstmStep &a, const int *idx, int row)
+{
+    return (long)min(max(idx[row], 0), 32 * a.n_utt - 1) * a.L * 2 * a.Hd;
+}
+
+__global__ __launch_bounds__(256) void k_bl_embed(BeamLstmStep a, float *__restrict__ x1)
+{
+    __shared__ float red[8];
+    const int s = blockIdx.x, u = blockIdx.y;
+    const int cur = bl_slot_cur(a, u, s);
+    if (cur < 0) return;
+    const int len = min(max(bl_utt(a.len, u * a.stride)[cur * 16 + s], 0), a.max_length - 1);
+    const int tok = bl_utt(a.tok, u * a.stride)[((long)cur * 16 + s) * a.max_length + len];  // the newest token (the start blank at len 0)
+    ld_embed_row(a.p.embedding, a.S, tok, a.p.ln_in_w, a.p.ln_in_b, a.eps_in, a.E, x1 + (long)(16 * u + s) * a.E, red);
+}
+
+// k_ld_gemm with the row tile as grid.z: a tile none of whose two utterances awaits a step is skipped
+struct BlGemm { const int32_t *state; int n_utt; RecArgs g[2]; };
+__global__ __launch_bounds__(256) void k_bl_gemm(BlGemm a)
+{
+    __shared__ float red[3 * 1024];
+    bool any = false;
+    for (int u = 2 * blockIdx.z; u < min(2 * (int)blockIdx.z + 2, a.n_utt); ++u)
+        any |= !a.state[32 * u + BEAM_ST_DONE] && a.state[32 * u + BEAM_ST_NEW];
+    if (!any) return;
+    const int which = (int)blockIdx.y >= a.g[0].KS ? 1 : 0;
+    rec_tile<false>(a.g[which], blockIdx.x * 32, blockIdx.y - (which ? a.g[0].KS : 0), blockIdx.z * 32, red);
+}
+
+template <bool LN>
+__global__ __launch_bounds__(256) void k_bl_step(BeamLstmStep a, LdStep q, int layer)
+{
+    __shared__ float red[8];
+    const int s = blockIdx.x, u = blockIdx.y, row = 16 * u + s;
+    if (bl_slot_cur(a, u, s) < 0) return;
+    const long at = (long)(2 * layer) * a.Hd;
+    float *mine = a.pool + bl_pool_row(a, a.own, row) + at;
+    ld_step_row<LN>(q, q.gp + (long)row * 4 * a.Hd, a.pool + bl_pool_row(a, a.par, row) + at + a.Hd, mine, mine + a.Hd, nullptr, nullptr, red);
+}
+
+// to_pvec: the row is the slot's text vector (N == H), else row 16 u + s of `out`
+template <bool LN>
+__global__ __launch_bounds__(256) void k_bl_rowfin(BeamLstmStep a, const float *__restrict__ gp, int nsp, long gp_ld, int N,
+                                                   const float *__restrict__ bias, const float *__restrict__ gamma,
+                                                   const float *__restrict__ beta, float eps, float *__restrict__ out, int to_pvec)
+{
+    __shared__ float red[8];
+    const int s = blockIdx.x, u = blockIdx.y, row = 16 * u + s;
+    const int cur = bl_slot_cur(a, u, s);
+    if (cur < 0) return;
+    float *y = to_pvec ? bl_utt(a.pvec, u * a.stride) + ((long)cur * 16 + s) * N : out + (long)row * N;
+    ld_rowfin_row<LN>(gp + (long)row * N, nsp, gp_ld, N, bias, gamma, beta, eps, y, red);
+}
+
+struct BlLayout { size_t x1, y, gp, total; };  // floats
+BlLayout bl_layout(int n_utt, int E, int Hd, int O, int H)
+{
+    const size_t M = (size_t)16 * n_utt;
+    BlLayout w;
+    size_t o = 0;
+    w.x1 = o; o += al(M * E);
+    w.y = o;  o += al(M * O);
+    size_t g = (size_t)(rec_splits(E) + rec_splits(Hd)) * 4 * Hd;  // partial tiles of the widest product (ld_layout's rule)
+    if ((size_t)2 * rec_splits(Hd) * 4 * Hd > g) g = (size_t)2 * rec_splits(Hd) * 4 * Hd;
+    if ((size_t)rec_splits(Hd) * O > g) g = (size_t)rec_splits(Hd) * O;
+    if ((size_t)rec_splits(O) * H > g) g = (size_t)rec_splits(O) * H;
+    w.gp = o; o += al(g * M);
+    w.total = o;
+    return w;
+}
+
 int ld_check_sizes(int n_utt, int S, int E, int Hd, int O, int L, int ln, int H, int V, int has_text, int scan_frames)
 {
     if (n_utt < 1) return engine_fail(RNNT_ERR_INVALID_ARG, "n_utt=%d must be >= 1", n_utt);
     if (H <= 0 || V <= 0) return engine_fail(RNNT_ERR_INVALID_ARG, "non-positive dimension H=%d V=%d", H, V);
     const Dims d = {n_utt, 1, S, E, Hd, O, L, ln};
     if (int rc = check_dims(d)) return rc;
-    if (n_utt > 32) return engine_fail(RNNT_ERR_UNSUPPORTED, "the LSTM greedy decode takes 1 <= n_utt <= 32: one row tile (n_utt=%d)", n_utt);
-    if (H % 8 != 0 || V % 4 != 0) return engine_fail(RNNT_ERR_UNSUPPORTED, "the LSTM greedy decode needs H %% 8 == 0 and V %% 4 == 0 (H=%d V=%d)", H, V);
+    if (n_utt > 32) return engine_fail(RNNT_ERR_UNSUPPORTED, "the LSTM decode entries take 1 <= n_utt <= 32 (n_utt=%d)", n_utt);
+    if (H % 8 != 0 || V % 4 != 0) return engine_fail(RNNT_ERR_UNSUPPORTED, "the LSTM decode entries need H %% 8 == 0 and V %% 4 == 0 (H=%d V=%d)", H, V);
     if (scan_frames < 1 || scan_frames > 128)
         return engine_fail(RNNT_ERR_UNSUPPORTED, "the LSTM greedy decode takes scan_frames in [1,128] (scan_frames=%d)", scan_frames);
     if (!has_text && O != H) return engine_fail(RNNT_ERR_INVALID_ARG, "without text_ln the predictor's output dim (%d) must equal H (%d)", O, H);
@@ -892,6 +1013,55 @@ int ld_check_sizes(int n_utt, int S, int E, int Hd, int O, int L, int ln, int H,
 }
 
 }  // namespace
+
+size_t beam_lstm_step_floats(int n_utt, int E, int Hd, int O, int H) { return bl_layout(n_utt, E, Hd, O, H).total; }
+
+void launch_beam_lstm_step(const BeamLstmStep &a, hipStream_t st)
+{
+    const int n = a.n_utt, M = 16 * n, E = a.E, Hd = a.Hd, O = a.O, L = a.L, H = a.H;
+    const BlLayout w = bl_layout(n, E, Hd, O, H);
+    float *x1 = a.scratch + w.x1, *y = a.scratch + w.y, *gp = a.scratch + w.gp;
+    const long ld = (long)L * 2 * Hd;  // floats from one pool row to the next
+    const dim3 slots(16, n), tiles_z((M + 31) / 32);
+    auto pooled = [&](int at, const int *idx, const float *W, float *P, int N) {  // operand rows read from the pool through `idx`
+        RecArgs g = RecArgs{a.pool + (long)at * Hd, ld, W, (long)Hd, P, M, N, Hd, rec_splits(Hd)};
+        g.rows = idx; g.R = 32 * n;
+        return g;
+    };
+    hipLaunchKernelGGL(k_bl_embed, slots, dim3(256), 0, st, a, x1);
+    for (int l = 0; l < L; ++l) {
+        const rnnt_lstm_layer_params &q = a.p.layers[l];
+        BlGemm g;
+        g.state = a.state; g.n_utt = n;
+        // the layer below's NEW h (the slot's own row: its row kernel has run), and this layer's h of the state the slot continues
+        g.g[0] = l ? pooled(2 * (l - 1), a.own, q.x2g_w, gp, 4 * Hd) : ld_prod(x1, q.x2g_w, gp, M, 4 * Hd, E);
+        g.g[1] = pooled(2 * l, a.par, q.p2g_w, gp + (long)g.g[0].KS * M * 4 * Hd, 4 * Hd);
+        hipLaunchKernelGGL(k_bl_gemm, dim3((4 * Hd + 31) / 32, g.g[0].KS + g.g[1].KS, tiles_z.x), dim3(256), 0, st, g);
+        LdStep s;
+        s.states = nullptr; s.gp = gp; s.nsp = g.g[0].KS + g.g[1].KS; s.gp_ld = (long)M * 4 * Hd;
+        s.xb = a.ln ? nullptr : q.x2g_b;
+        s.gw = q.g_norm_w; s.gb = q.g_norm_b; s.cw = q.c_norm_w; s.cb = q.c_norm_b; s.eps = a.eps_lstm;
+        s.h = s.c = s.h_out = s.c_out = nullptr;
+        s.Hd = Hd;
+        if (a.ln) hipLaunchKernelGGL(k_bl_step<true>, slots, dim3(256), 0, st, a, s, l);
+        else hipLaunchKernelGGL(k_bl_step<false>, slots, dim3(256), 0, st, a, s, l);
+    }
+    BlGemm g;
+    g.state = a.state; g.n_utt = n;
+    g.g[0] = pooled(2 * (L - 1), a.own, a.p.linear_w, gp, O);
+    g.g[1] = g.g[0]; g.g[1].KS = 0;
+    hipLaunchKernelGGL(k_bl_gemm, dim3((O + 31) / 32, g.g[0].KS, tiles_z.x), dim3(256), 0, st, g);
+    // without joint.text_ln the output LayerNorm's row IS the text vector (O == H)
+    hipLaunchKernelGGL(k_bl_rowfin<true>, slots, dim3(256), 0, st, a, gp, g.g[0].KS, (long)M * O, O, a.p.linear_b, a.p.ln_out_w, a.p.ln_out_b,
+                       a.eps_out, y, a.text_W ? 0 : 1);
+    if (a.text_W) {
+        g.g[0] = ld_prod(y, a.text_W, gp, M, H, O);
+        g.g[1] = g.g[0]; g.g[1].KS = 0;
+        hipLaunchKernelGGL(k_bl_gemm, dim3((H + 31) / 32, g.g[0].KS, tiles_z.x), dim3(256), 0, st, g);
+        hipLaunchKernelGGL(k_bl_rowfin<false>, slots, dim3(256), 0, st, a, gp, g.g[0].KS, (long)M * H, H, a.text_b, (const float *)nullptr,
+                           (const float *)nullptr, 0.f, y, 1);
+    }
+}
 
 extern "C" {
 
@@ -1135,6 +1305,68 @@ int rnnt_engine_greedy_decode_lstm(const void *frames, int64_t frame_stride, int
     a.host_flag = flag_dev; a.state = state; a.tokens = tokens; a.state_out = state_out; a.ws = (float *)workspace;
     launch_ld_loop(a, (hipStream_t)stream);
     return status("rnnt_engine_greedy_decode_lstm");
+}
+
+int rnnt_engine_beam_decode_lstm_workspace_bytes(int n_utt, int S, int E, int Hd, int O, int L, int layer_norm, int H, int V, int has_text,
+                                                 int max_length, int beam, size_t *out)
+{
+    if (!out) return engine_fail(RNNT_ERR_INVALID_ARG, "null size pointer");
+    if (beam < 1) return engine_fail(RNNT_ERR_INVALID_ARG, "beam=%d must be >= 1", beam);
+    if (beam > 16) return engine_fail(RNNT_ERR_UNSUPPORTED, "beam decode takes beam <= 16 (beam=%d)", beam);
+    if (max_length < 2) return engine_fail(RNNT_ERR_INVALID_ARG, "max_length=%d must be >= 2", max_length);
+    if (max_length > 65536) return engine_fail(RNNT_ERR_UNSUPPORTED, "beam decode takes max_length <= 65536 (max_length=%d)", max_length);
+    if (int rc = ld_check_sizes(n_utt, S, E, Hd, O, L, layer_norm != 0, H, V, has_text, 1)) return rc;
+    *out = beam_lstm_workspace_bytes(n_utt, E, Hd, O, L, H, V, max_length);
+    return RNNT_OK;
+}
+
+int rnnt_engine_beam_decode_lstm(const void *frames, int64_t frame_stride, int rows, const int32_t *utt, int n_utt, int max_frames,
+                                 const rnnt_lstm_predictor_params *p, int S, int E, int Hd, int O, int L, int layer_norm, float eps_in,
+                                 float eps_lstm, float eps_out, const void *text_W, const void *text_b, const void *W, const void *bias,
+                                 int H, int V, int blank, int max_length, int max_per_frame, int beam, int iterations, int init,
+                                 int32_t *host_flag, int32_t *state, int32_t *tokens, double *scores, void *workspace, size_t ws_bytes,
+                                 void *stream)
+{
+    size_t need;
+    if (int rc = rnnt_engine_beam_decode_lstm_workspace_bytes(n_utt, S, E, Hd, O, L, layer_norm, H, V, text_W ? 1 : 0, max_length, beam, &need))
+        return rc;
+    if (iterations < 0) return engine_fail(RNNT_ERR_INVALID_ARG, "iterations=%d", iterations);
+    if (bad(frames) || bad(W) || bad(bias) || !utt || !state || !tokens || !scores || !workspace)
+        return engine_fail(RNNT_ERR_INVALID_ARG, "null or not 16-byte aligned pointer argument");
+    if (((uintptr_t)utt & 7) || ((uintptr_t)workspace & 255) || ((uintptr_t)scores & 7))
+        return engine_fail(RNNT_ERR_INVALID_ARG, "utt and scores must be 8-byte and the workspace 256-byte aligned");
+    if (int rc = check_params(p, L, layer_norm != 0, "parameter")) return rc;
+    if ((text_W == nullptr) != (text_b == nullptr) || (text_W && (bad(text_W) || bad(text_b))))
+        return engine_fail(RNNT_ERR_INVALID_ARG, "text_W / text_b: both or neither, 16-byte aligned");
+    if (max_per_frame < 1 || max_frames < 1 || rows < max_frames || frame_stride < H || frame_stride % 4)
+        return engine_fail(RNNT_ERR_INVALID_ARG, "max_per_frame=%d max_frames=%d rows=%d frame_stride=%lld", max_per_frame, max_frames, rows,
+                           (long long)frame_stride);
+    if (blank < 0 || blank >= V) return engine_fail(RNNT_ERR_INVALID_ARG, "blank=%d outside [0,%d)", blank, V);
+    if ((long)max_frames * max_per_frame + 1 > 0x7fffffffL)
+        return engine_fail(RNNT_ERR_UNSUPPORTED, "max_frames * max_per_frame must stay below 2^31 (max_frames=%d, max_per_frame=%d)", max_frames,
+                           max_per_frame);
+    int32_t *flag_dev = nullptr;
+    if (host_flag) {  // the device's address of the caller's pinned word (an ordinary host pointer is refused, never written through)
+        void *dp = nullptr;
+        if (hipHostGetDevicePointer(&dp, host_flag, 0) != hipSuccess || !dp) {
+            (void)hipGetLastError();
+            return engine_fail(RNNT_ERR_INVALID_ARG, "host_flag is not mapped pinned host memory (hipHostMalloc / torch pin_memory)");
+        }
+        flag_dev = (int32_t *)dp;
+    }
+    if (ws_bytes < need) return engine_fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
+    BeamLstmArgs a{};
+    a.s.n_utt = n_utt; a.s.max_length = max_length;
+    a.s.p = *p; a.s.S = S; a.s.E = E; a.s.Hd = Hd; a.s.O = O; a.s.L = L; a.s.ln = layer_norm != 0;
+    a.s.eps_in = eps_in; a.s.eps_lstm = eps_lstm; a.s.eps_out = eps_out;
+    a.s.text_W = (const float *)text_W; a.s.text_b = (const float *)text_b; a.s.H = H;
+    a.frames = (const float *)frames; a.frame_stride = (long)frame_stride; a.rows = rows; a.utt = utt;
+    a.W = (const float *)W; a.bias = (const float *)bias; a.V = V; a.blank = blank; a.max_per_frame = max_per_frame; a.beam = beam;
+    a.iterations = iterations ? iterations : max_frames * max_per_frame + 1;
+    a.init = init;
+    a.host_flag = flag_dev; a.state = state; a.tokens = tokens; a.scores = scores; a.workspace = workspace;
+    launch_beam_decode_lstm(a, (hipStream_t)stream);
+    return status("rnnt_engine_beam_decode_lstm");
 }
 
 }  // extern "C"

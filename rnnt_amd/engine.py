@@ -91,6 +91,8 @@ SIGNATURES = {
     "rnnt_engine_beam_decode": "pqipiiiffppppiiiiiipiipppppzp",
     "rnnt_engine_beam_decode_batch_workspace_bytes": "iiiiiiiiip",
     "rnnt_engine_beam_decode_batch": "pqipiipiiiffppppiiiiiipiipppppzp",
+    "rnnt_engine_beam_decode_lstm_workspace_bytes": "iiiiiiiiiiiip",
+    "rnnt_engine_beam_decode_lstm": "pqipiipiiiiiifffppppiiiiiiiipppppzp",
     "rnnt_engine_beam_decode_ctx_workspace_bytes": "iiiiiiiip",
     "rnnt_engine_beam_decode_ctx": "pqipiiiffppppiiiiiipiipppppzpp",
     "rnnt_engine_beam_decode_batch_ctx_workspace_bytes": "iiiiiiiiip",
@@ -177,6 +179,7 @@ EXPORTS = (
     "rnnt_engine_lstm_predictor_saved_bytes", "rnnt_engine_lstm_predictor_workspace_bytes",
     "rnnt_engine_lstm_predictor_fwd", "rnnt_engine_lstm_predictor_bwd",
     "rnnt_engine_greedy_decode_lstm_workspace_bytes", "rnnt_engine_greedy_decode_lstm",
+    "rnnt_engine_beam_decode_lstm_workspace_bytes", "rnnt_engine_beam_decode_lstm",
 )
 
 # per-call kernel variants (include/rnnt_engine.h RNNT_VARIANT_*): bit-identical results
@@ -1177,6 +1180,59 @@ def beam_decode_batch(frames_list, pred_params, ln_eps, text_W, text_b, W, bias,
         flag = _enqueue_rounds(lambda it, first, flag: _check(fn(*head, it, first, flag, *tail)),
                                max(lens) * max(1, max_per_frame) + 1, max(1, int(chunk)), in_flight)
         state._keepalive = (flag, utt, *m.keep, tables, cx_keep)  # until the caller has synchronised
+    return state, tokens, scores
+
+
+# ---- beam search with the LSTMPredictor, n_utt utterances in lockstep (DESIGN.md §4h "LSTM")
+BEAM_LSTM_MAX = 32  # rnnt_engine_beam_decode_lstm: 1 <= n_utt <= 32 (16 slots each: two utterances to a 32-row tile)
+
+
+def beam_decode_lstm_supported(n_utt, S, E, Hd, O, L, layer_norm, H, V, has_text, max_length, beam):
+    """Whether rnnt_engine_beam_decode_lstm takes these sizes (no device work)."""
+    return _supported("rnnt_engine_beam_decode_lstm_workspace_bytes", n_utt, S, E, Hd, O, L, bool(layer_norm), H, V, bool(has_text),
+                      max_length, beam)
+
+
+def beam_decode_lstm(frames_list, lstm_params, text_W, text_b, W, bias, blank, max_length, beam, max_per_frame=10, chunk=32, in_flight=2):
+    """The beam search of beam_decode_batch for 1 .. 32 utterances of one LSTMPredictor model (C ABI rnnt_engine_beam_decode_lstm;
+    DESIGN.md §4h "LSTM").  `frames_list` and the enqueueing as beam_decode_batch's, `lstm_params` = LSTMPredictor._decode_bundle() as
+    greedy_decode_lstm's.  Returns (state int32[N, 32], tokens int32[N, beam, max_length], scores float64[N, beam]) device tensors WITHOUT
+    a final synchronisation; row u of each is, bit for bit, what the call gives for frames_list[u] alone."""
+    from .lstm_predictor import _struct
+    frames_list = list(frames_list)
+    lens = [int(f.shape[0]) for f in frames_list]
+    if not lens or min(lens) < 1:
+        raise ValueError("beam_decode_lstm: no utterance, or an utterance without frames")
+    params, (L, Hd, layer_norm), eps = lstm_params
+    params = [t.contiguous() for t in params]
+    packed, table = _pack_rows(frames_list, lens)
+    if packed.dim() != 2 or packed.stride(1) != 1:
+        packed = packed.contiguous()
+    joint = [t.contiguous() for t in (W, bias)] + ([text_W.contiguous(), text_b.contiguous()] if text_W is not None else [])
+    dev = _require_cuda(packed, *joint, *params)
+    _require_dtype(torch.float32, frames=packed, **{f"joint{i}": t for i, t in enumerate(joint)}, **{f"param{i}": t for i, t in enumerate(params)})
+    N, H, V = len(lens), packed.shape[1], joint[0].shape[0]
+    S, E = params[0].shape
+    O = params[3].shape[0]
+    beam, max_length, max_per_frame = int(beam), int(max_length), int(max_per_frame)
+    with torch.cuda.device(dev):
+        n = ctypes.c_size_t(0)
+        _check(lib().rnnt_engine_beam_decode_lstm_workspace_bytes(N, S, E, Hd, O, L, int(bool(layer_norm)), H, V, int(len(joint) == 4),
+                                                                  max_length, beam, ctypes.byref(n)))
+        ws = workspace(dev, n.value)
+        utt = _rows_table(table, dev)
+        state = torch.empty(N, 32, dtype=torch.int32, device=dev)
+        tokens = torch.empty(N, beam, max_length, dtype=torch.int32, device=dev)
+        scores = torch.empty(N, beam, dtype=torch.float64, device=dev)
+        st, arr = _struct(params, L, layer_norm)
+        head = (_p(packed), ctypes.c_int64(packed.stride(0) if packed.shape[0] > 1 else H), packed.shape[0], _p(utt), N, max(lens),
+                ctypes.byref(st), S, E, Hd, O, L,
+                int(bool(layer_norm)), *[ctypes.c_float(e) for e in eps], _p(joint[2]) if len(joint) == 4 else None,
+                _p(joint[3]) if len(joint) == 4 else None, _p(joint[0]), _p(joint[1]), H, V, int(blank), max_length, max_per_frame, beam)
+        tail = (_p(state), _p(tokens), _p(scores), _p(ws), ctypes.c_size_t(ws.numel()), _stream(dev))
+        flag = _enqueue_rounds(lambda it, first, flag: _check(lib().rnnt_engine_beam_decode_lstm(*head, it, first, flag, *tail)),
+                               max(lens) * max(1, max_per_frame) + 1, max(1, int(chunk)), in_flight)
+        state._keepalive = (flag, utt, packed, params, joint, arr)  # until the caller has synchronised
     return state, tokens, scores
 
 

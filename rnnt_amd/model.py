@@ -35,6 +35,9 @@ class RNNTModel(torch.nn.Module):
         # the path the last greedy_decode / greedy_decode_many took: "persistent", "loop", "lstm_loop" (DESIGN.md §4p "Device decode")
         # or "host"; greedy_decode_many: "host" only if every utterance took the host loop
         self.last_decode_path = None
+        # the path the last beam_search / beam_search_many took: "device" (ConvPredictor), "lstm_device" (LSTMPredictor,
+        # §4h "LSTM") or "host"; beam_search_many: "host" only if every utterance took the host loop
+        self.last_beam_path = None
 
     @property
     def device(self):
@@ -108,6 +111,11 @@ class RNNTModel(torch.nn.Module):
         required = [q for q in params if q.default is inspect.Parameter.empty
                     and q.kind in (inspect.Parameter.POSITIONAL_ONLY, inspect.Parameter.POSITIONAL_OR_KEYWORD)]
         return len(required) >= 2
+
+    def _predictor_is_lstm(self) -> bool:
+        """The predictor is the engine's own LSTMPredictor (any backend, any dtype): the one stateful predictor the beam searches take."""
+        from .lstm_predictor import LSTMPredictor
+        return isinstance(self.predictor, LSTMPredictor)
 
     def _device_loop_ok(self, audio) -> bool:
         """The whole decode loop can run on the device: the engine's stateless ConvPredictor (rnnt_engine_greedy_decode) or its
@@ -328,13 +336,17 @@ class RNNTModel(torch.nn.Module):
     # ---- beam search: frame-synchronous, <= max_symbols_per_frame labels per frame, hypotheses merged by sequence
     @torch.no_grad()
     def beam_search(self, mel_features: torch.Tensor, mel_feature_lens: torch.Tensor, beam_size: int = 4, max_length: int = 200,
-                    max_symbols_per_frame: int = 10, return_nbest: bool = False, context=None):
+                    max_symbols_per_frame: int = 10, return_nbest: bool = False, context=None, device_search=None):
         """Beam search over the whole encoder output (like greedy_decode, `mel_feature_lens` is not used).  Returns the best
         entry's token list, or with `return_nbest` the final beam as [(tokens, log-probability), ...] best first.  beam_size 1 is
         greedy_decode's result.  The search runs on the device (rnnt_engine_beam_decode: a fixed kernel sequence per round, one
         synchronisation per utterance) where greedy_decode's device loop does — engine ConvPredictor, eval mode, fp32 HIP tensors,
         sizes the kernels cover, beam_size <= 16 — else as a plain-torch host loop of the same search over any stateless
-        `predictor(ids)` and `joint.single_forward` (CPU too).  A stateful (LSTM) predictor raises NotImplementedError.
+        `predictor(ids)` and `joint.single_forward` (CPU too).  With an rnnt_amd.LSTMPredictor (DESIGN.md §4h "LSTM") the search runs on
+        the device under the same conditions and without a `context` (rnnt_engine_beam_decode_lstm: a hypothesis's LSTM state follows it
+        as an index into a pool), else as the host loop with one predictor step per new hypothesis from its parent's cached state;
+        `device_search` forces either (None: the device where it applies — it beat the host loop at every timed shape, 5.9x - 8.3x,
+        profiles/beam_lstm_bench.txt).  Any other stateful predictor raises NotImplementedError.  `last_beam_path` names the path taken.
         `context` (a rnnt_amd.ContextGraph: phrases and a boost per matched token) biases the search towards the caller's phrases
         (DESIGN.md §4h "Context"): on the device where the plain search is (graphs of up to 65536 nodes; the n-best list is finalised
         and re-sorted on the host), else in the host loop.  The scores returned are FINALISED — the bonus of a match still unfinished at
@@ -344,16 +356,53 @@ class RNNTModel(torch.nn.Module):
         beam_size, max_length, m = int(beam_size), int(max_length), int(max_symbols_per_frame)
         if beam_size < 1 or m < 1:
             raise ValueError(f"beam_search: beam_size={beam_size} and max_symbols_per_frame={m} must be >= 1")
-        if self._predictor_is_stateful():
+        lstm = self._predictor_is_lstm()
+        if self._predictor_is_stateful() and not lstm:
             raise NotImplementedError("beam_search needs a stateless predictor (forward(ids), e.g. ConvPredictor); "
                                       "stateful (LSTM) predictors are not supported")
         g = self._beam_context(context)
         audio = self.encoder(mel_features).permute(0, 2, 1)
-        if self._beam_device_ok(audio, beam_size, max_length, g):
+        if lstm:
+            ok = g is None and self._beam_lstm_ok(audio, beam_size, max_length)
+            if device_search and not ok:
+                raise RuntimeError("beam_search(device_search=True) needs the engine's LSTMPredictor in eval mode on a HIP device, sizes the "
+                                   "kernels cover, beam_size <= 16 and no context")
+            if ok and device_search is not False:
+                nbest = self._beam_search_lstm([self._decode_frames(audio)], beam_size, max_length, m)[0]
+            else:
+                nbest = self._beam_search_host(audio, beam_size, max_length, m, g)
+        elif self._beam_device_ok(audio, beam_size, max_length, g):
             nbest = self._beam_search_device(audio, beam_size, max_length, m, g)
+            self.last_beam_path = "device"
         else:
             nbest = self._beam_search_host(audio, beam_size, max_length, m, g)
         return nbest if return_nbest else list(nbest[0][0])
+
+    def _beam_lstm_ok(self, audio, beam_size, max_length, n_utt=1) -> bool:
+        """The LSTM model's beam search can run on the device: where its greedy loop can, beam_size <= 16, sizes the entry takes."""
+        if not (1 <= beam_size <= 16 and max_length >= 2 and self._device_loop_ok(audio)):
+            return False
+        from . import engine
+        H, V = self.joint.joint_ln.in_features, self.joint.joint_ln.out_features
+        return engine.beam_decode_lstm_supported(n_utt, *self.predictor._decode_sizes(), H, V, hasattr(self.joint, "text_ln"), max_length,
+                                                 beam_size)
+
+    def _beam_search_lstm(self, frames_list, beam_size, max_length, m):
+        """The n-best lists of up to 32 utterances' frames searched in lockstep by engine.beam_decode_lstm with the model's live
+        parameters; one host synchronisation."""
+        from . import engine
+        joint = self.joint
+        tl = getattr(joint, "text_ln", None)
+        state, tokens, scores = engine.beam_decode_lstm(
+            frames_list, self.predictor._decode_bundle(), tl.weight if tl is not None else None, tl.bias if tl is not None else None,
+            joint.joint_ln.weight, joint.joint_ln.bias, joint.blank_idx, max_length, beam_size, max_per_frame=m)
+        sts, toks, scs = state.tolist(), tokens.tolist(), scores.tolist()  # the batch's one synchronisation
+        for u, st in enumerate(sts):
+            if not st[3]:
+                raise RuntimeError(f"rnnt_engine: the beam search of utterance {u} did not finish (t={st[0]}, {st[5]} rounds)")
+        self.predictor.last_backend = "engine"
+        self.last_beam_path = "lstm_device"
+        return [self._nbest(st, toks[u], scs[u]) for u, st in enumerate(sts)]
 
     def _beam_context(self, context):
         """The ContextGraph a search runs with: checked against the vocabulary; None where it cannot change the search (no phrase, score 0)."""
@@ -386,6 +435,9 @@ class RNNTModel(torch.nn.Module):
         return context.finalise(nbest) if context is not None else nbest  # (the device's scores are internal)
 
     BEAM_BATCH = 32  # beam_search_many's default batch: the best of N = 1 .. 32 in profiles/beam_batch_bench.txt, the only one within 10 % of it
+    # beam_search_many's default batch with an LSTMPredictor: of 4, 8, 16 and 32 the only one within 10 % of the best time per utterance at
+    # both timed lengths and beams (19.0 / 23.3 ms at T = 1000, 2.2 / 3.0 ms at T = 100, beams 4 / 8; profiles/beam_lstm_bench.txt)
+    BEAM_LSTM_BATCH = 32
 
     @torch.no_grad()
     def beam_search_many(self, mels, beam_size: int = 4, max_length: int = 200, max_symbols_per_frame: int = 10,
@@ -398,12 +450,16 @@ class RNNTModel(torch.nn.Module):
         `batch` defaults to BEAM_BATCH = 32: of N = 1 .. 32 measured at the reference's widths (profiles/beam_batch_bench.txt) the time per
         utterance was still falling at 32 (7 - 21 ms against 106 - 336 ms one by one), so 32 is the smallest N within 10 % of the best.
         Where beam_search would take its host loop (CPU, other stateless predictors, beam_size > 16, sizes the kernels do not cover)
-        this is a loop over beam_search; a stateful (LSTM) predictor raises NotImplementedError.  `context` as beam_search's: ONE
-        ContextGraph biases every utterance (rnnt_engine_beam_decode_batch_ctx)."""
+        this is a loop over beam_search.  `context` as beam_search's: ONE ContextGraph biases every utterance
+        (rnnt_engine_beam_decode_batch_ctx).
+        With an rnnt_amd.LSTMPredictor the utterances beam_search would search on the device advance `batch` (1 .. 32, default
+        BEAM_LSTM_BATCH) at a time through rnnt_engine_beam_decode_lstm (DESIGN.md §4h "LSTM"), every other one — all of them with a
+        `context` — takes the host loop; any other stateful predictor raises NotImplementedError."""
         beam_size, max_length, m = int(beam_size), int(max_length), int(max_symbols_per_frame)
         if beam_size < 1 or m < 1:
             raise ValueError(f"beam_search_many: beam_size={beam_size} and max_symbols_per_frame={m} must be >= 1")
-        if self._predictor_is_stateful():
+        lstm = self._predictor_is_lstm()
+        if self._predictor_is_stateful() and not lstm:
             raise NotImplementedError("beam_search_many needs a stateless predictor (forward(ids), e.g. ConvPredictor); "
                                       "stateful (LSTM) predictors are not supported")
         mels = list(mels)
@@ -411,6 +467,26 @@ class RNNTModel(torch.nn.Module):
             return []
         assert all(mel.shape[0] == 1 for mel in mels), "one utterance per entry"
         from . import engine
+        if lstm:
+            batch = self.BEAM_LSTM_BATCH if batch is None else int(batch)
+            if not 1 <= batch <= engine.BEAM_LSTM_MAX:
+                raise ValueError(f"beam_search_many: batch={batch} outside [1, {engine.BEAM_LSTM_MAX}]")
+            g = self._beam_context(context)
+            out, path = [None] * len(mels), "host"
+            audios = [self.encoder(mel).permute(0, 2, 1) for mel in mels]
+            searched = [i for i, a in enumerate(audios) if g is None and self._beam_lstm_ok(a, beam_size, max_length)]
+            for i, a in enumerate(audios):
+                if i not in searched:
+                    out[i] = self._beam_search_host(a, beam_size, max_length, m, g)
+            for k in range(0, len(searched), batch):
+                group = searched[k:k + batch]
+                if not self._beam_lstm_ok(audios[group[0]], beam_size, max_length, len(group)):
+                    raise RuntimeError(f"rnnt_engine: the LSTM beam search refuses {len(group)} utterances of sizes the single search takes")
+                for i, nbest in zip(group, self._beam_search_lstm([self._decode_frames(audios[i]) for i in group], beam_size, max_length, m)):
+                    out[i] = nbest
+                path = "lstm_device"
+            self.last_beam_path = path
+            return out if return_nbest else [list(nbest[0][0]) for nbest in out]
         batch = self.BEAM_BATCH if batch is None else int(batch)
         if not 1 <= batch <= engine.BEAM_BATCH_MAX:
             raise ValueError(f"beam_search_many: batch={batch} outside [1, {engine.BEAM_BATCH_MAX}]")
@@ -441,6 +517,7 @@ class RNNTModel(torch.nn.Module):
                     raise RuntimeError(f"rnnt_engine: the beam search of utterance {i + u} did not finish (t={st[0]}, {st[5]} rounds)")
                 nbest = self._nbest(st, toks[k], scs[k])
                 out[i + u] = g.finalise(nbest) if g is not None else nbest
+            self.last_beam_path = "device"
         return out if return_nbest else [list(nbest[0][0]) for nbest in out]
 
     def beam_stream(self, beam_size: int = 4, max_length: int = 200, max_symbols_per_frame: int = 10, context=None):
@@ -450,7 +527,8 @@ class RNNTModel(torch.nn.Module):
         beam_search is (the search's state rests in a block the stream owns), else a resumable host loop.  With a `context`
         (ContextGraph, as beam_search's) the stream runs the resumable host loop — the device stream with a context graph is not built
         yet; `nbest`, `tokens` and `stable` are finalised views of the carried internal beam, so any chunking still equals
-        `beam_search(..., context=context)` of the same frames."""
+        `beam_search(..., context=context)` of the same frames.  An rnnt_amd.LSTMPredictor model runs the resumable host loop too (a
+        device stream with LSTM state is out of scope, DESIGN.md §4h "LSTM"); any other stateful predictor raises NotImplementedError."""
         from .stream import BeamStream
         return BeamStream(self, beam_size=beam_size, max_length=max_length, max_symbols_per_frame=max_symbols_per_frame,
                           context=self._beam_context(context))
@@ -469,8 +547,10 @@ class RNNTModel(torch.nn.Module):
 
     def _beam_search_host(self, audio, beam_size, max_length, m, context=None):
         """The search of DESIGN.md §4h as a host loop: the predictor on the whole history of each new hypothesis (cached by
-        sequence), single_forward batched over the round's active hypotheses, scores as Python floats (double)."""
+        sequence; an LSTMPredictor: one step from the parent's cached state), single_forward batched over the round's active
+        hypotheses, scores as Python floats (double)."""
         from .stream import HostBeamLoop  # (one host loop, resumable frame by frame: BeamStream's host path runs it too)
         loop = HostBeamLoop(self, beam_size, max_length, m, context)
         loop.run(audio)
+        self.last_beam_path = "host"
         return loop.nbest

@@ -277,7 +277,10 @@ class GreedyStream:
 class HostBeamLoop:
     """The search of DESIGN.md §4h as a host loop over any number of calls of `run`: the predictor on the whole history of each new
     hypothesis (cached by sequence), single_forward batched over the round's active hypotheses, scores as Python floats (double).  The
-    beam after the last frame carries to the next call; `nbest` is beam_search's result for the frames so far.  With a `context`
+    beam after the last frame carries to the next call; `nbest` is beam_search's result for the frames so far.  With an
+    rnnt_amd.LSTMPredictor (DESIGN.md §4h "LSTM") the cache holds (text vector, LSTM state) by sequence and a new hypothesis takes ONE
+    predictor step from its parent's state — the parent is always cached: an active of the round before or a member of the carried beam.
+    With a `context`
     (ContextGraph; DESIGN.md §4h "Context") a label candidate takes delta(node, k) — the WHOLE log-probability row is biased before the
     slot's top-`beam` is taken, never only the labels the raw row would have offered —, the carried beam holds internal scores and `nbest`
     is its finalised view."""
@@ -290,6 +293,7 @@ class HostBeamLoop:
         self.beam = [((), 0.0)]
         self.frames = 0
         self._feats = {}
+        self._lstm = model._predictor_is_lstm()
 
     @property
     def nbest(self):
@@ -305,6 +309,14 @@ class HostBeamLoop:
         return self._nodes[y]
 
     def _text(self, y):
+        if self._lstm:
+            if y not in self._feats:  # one step from the state after y[:-1], fed y[-1]; the start: the blank from zero state
+                dev = self.model.device
+                ids = torch.tensor([[y[-1] if y else self.model.joint.blank_idx]], dtype=torch.int64, device=dev)
+                out, _, state = self.model.predictor(ids, torch.ones(1, dtype=torch.int64, device=dev),
+                                                     self._feats[y[:-1]][1] if y else None)
+                self._feats[y] = (out[0, -1], state)
+            return self._feats[y][0]
         if y not in self._feats:
             ids = torch.tensor([[self.model.joint.blank_idx, *y]], dtype=torch.int64, device=self.model.device)
             self._feats[y] = self.model.predictor(ids)[0, -1]
@@ -362,6 +374,9 @@ class HostBeamLoop:
         self.beam = beam
         self.frames += audio.shape[1]
         live = {y for y, _ in beam}  # (only the beam's text vectors are needed again; the others would only grow with the stream)
+        if self._lstm:  # (a capped label has not taken its step yet: take it while its parent's state is still cached)
+            for y, _ in beam:
+                text(y)
         self._feats = {y: f for y, f in self._feats.items() if y in live}
         if self.context is not None:
             self._nodes = {y: self._node(y) for y in live}
@@ -389,7 +404,8 @@ class BeamStreamGroup:
     With the engine's ConvPredictor in eval mode, fp32 HIP tensors, sizes the beam kernels cover and beam_size <= 16 the searches rest on
     the device between pushes, in a block the group owns (rnnt_engine_beam_stream_push: all streams advance through ONE kernel sequence
     per round, one host synchronisation per push); the decode tables are built when the group is created, so the model's weights must not
-    change while it is open.  Everything else, the CPU included, runs one HostBeamLoop per stream (`last_path`: "device" or "host").
+    change while it is open.  Everything else, the CPU and every rnnt_amd.LSTMPredictor model included (a device stream with LSTM state is
+    out of scope, DESIGN.md §4h "LSTM"), runs one HostBeamLoop per stream (`last_path`: "device" or "host").
     With a `context` (ContextGraph; DESIGN.md §4h "Context") every stream runs the host loop — the device stream with a context graph is
     out of scope so far (§4l) —, the carried beams are internal and `nbest`, `tokens`, `stable` their finalised views."""
 
@@ -401,7 +417,8 @@ class BeamStreamGroup:
             raise ValueError(f"beam_stream: beam_size={beam_size} and max_symbols_per_frame={m} must be >= 1")
         if not 1 <= n <= engine.BEAM_STREAM_MAX:
             raise ValueError(f"beam_streams: n={n} outside [1, {engine.BEAM_STREAM_MAX}]")
-        if model._predictor_is_stateful():
+        lstm = model._predictor_is_lstm()  # (rnnt_amd.LSTMPredictor: the host loop; a device stream with LSTM state is out of scope)
+        if model._predictor_is_stateful() and not lstm:
             raise NotImplementedError("beam_stream needs a stateless predictor (forward(ids), e.g. ConvPredictor); "
                                       "stateful (LSTM) predictors are not supported")
         self.model, self.n = model, n
@@ -411,7 +428,7 @@ class BeamStreamGroup:
         self.last_path = None
         dev = model.device
         # (with a context graph: the host loop — the device stream carries no node per slot yet)
-        self._on_device = context is None and dev.type == "cuda" and model._beam_device_ok(torch.zeros(1, 1, device=dev), beam_size, max_length)
+        self._on_device = not lstm and context is None and dev.type == "cuda" and model._beam_device_ok(torch.zeros(1, 1, device=dev), beam_size, max_length)
         if self._on_device:
             self._sizes = model._decode_sizes()
             self._on_device = engine.beam_stream_supported(*self._sizes, max_length, beam_size, n)
