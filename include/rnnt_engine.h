@@ -336,6 +336,9 @@ int rnnt_engine_greedy_scan(const void *enc, int64_t enc_stride_t, int64_t enc_s
  *                           scalars go through `hyper_dev` (float[4], scratch).  Nothing of the update is
  *                           baked into the launch arguments, so the call can be captured into a HIP graph
  *                           and replayed every iteration (an LR scheduler writes lr_dev between replays).
+ * The first moment follows Tensor.lerp_: m + (1-b1)(g-m) while 1-b1 < 0.5, g - (g-m) b1 from there (b1 = 0: m = g exactly).
+ * Every entry of a list (element count >= 0; a tensor of numel > 0 non-NULL and 4-byte aligned) is checked before the first
+ * launch: a refused call (RNNT_ERR_INVALID_ARG) has changed no tensor and not moved `step_dev`.
  */
 int rnnt_engine_grad_norm_workspace_bytes(int n_tensors, const int64_t *numels, size_t *out);
 int rnnt_engine_grad_norm(int n_tensors, const void *const *grads, const int64_t *numels,

@@ -106,7 +106,10 @@ __device__ __forceinline__ void adamw_one(float &p, float &g, float &m, float &v
 {
     g *= coef;
     p *= a.decay;
-    m += a.omb1 * (g - m);                  // exp_avg.lerp_(grad, 1 - beta1)
+    // exp_avg.lerp_(grad, 1 - beta1): torch's lerp leaves from the END once the weight reaches 0.5, so that beta1 = 0 gives m = g
+    // exactly (the other form keeps an ulp of the OLD m, which m / (sqrt(v) + eps) magnifies at beta2 = 0).  omb1 is uniform.
+    if (a.omb1 < 0.5f) m += a.omb1 * (g - m);
+    else m = g - (g - m) * (1.f - a.omb1);
     v = a.beta2 * v + a.omb2 * (g * g);     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
     const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
     p -= a.step_size * (m / denom);         // param.addcdiv_(exp_avg, denom, value=-step_size)
@@ -187,6 +190,21 @@ __global__ __launch_bounds__(MT_THREADS) void k_mt_adamw(const MtAdamArgs a)
 
 namespace {
 long chunks_of(long n) { return (n + MT_CHUNK - 1) / MT_CHUNK; }
+
+// Every tensor of the WHOLE list before the first launch: a list is cut into launches of MT_MAX tensors, and a bad entry of a later
+// launch must not be found after the earlier ones have run.  `lists`: n_lists pointer arrays of n_tensors entries each.
+int check_tensor_list(int n_tensors, const void *const *const *lists, int n_lists, const int64_t *numels, const char *what)
+{
+    for (int i = 0; i < n_tensors; ++i) {
+        if (numels[i] < 0) return engine_fail(RNNT_ERR_INVALID_ARG, "negative element count");
+        if (numels[i] == 0) continue;
+        for (int k = 0; k < n_lists; ++k) {
+            const void *q = lists[k][i];
+            if (!q || ((uintptr_t)q & 3)) return engine_fail(RNNT_ERR_INVALID_ARG, "null / misaligned %s pointer (tensor %d)", what, i);
+        }
+    }
+    return RNNT_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -210,6 +228,7 @@ int rnnt_engine_grad_norm(int n_tensors, const void *const *grads, const int64_t
     if (int rc = rnnt_engine_grad_norm_workspace_bytes(n_tensors, numels, &need)) return rc;
     if (!total_norm || !workspace || (n_tensors > 0 && !grads)) return engine_fail(RNNT_ERR_INVALID_ARG, "null pointer argument");
     if (ws_bytes < need) return engine_fail(RNNT_ERR_WORKSPACE, "gradient-norm workspace too small");
+    if (int rc = check_tensor_list(n_tensors, &grads, 1, numels, "gradient")) return rc;
     hipStream_t st = (hipStream_t)stream;
     float *partials = (float *)workspace;
     int total_chunks = 0;
@@ -220,7 +239,6 @@ int rnnt_engine_grad_norm(int n_tensors, const void *const *grads, const int64_t
         a.partials = partials + total_chunks;
         while (i0 < n_tensors && a.count < MT_MAX) {
             if (numels[i0] > 0) {
-                if (!grads[i0] || ((uintptr_t)grads[i0] & 3)) return engine_fail(RNNT_ERR_INVALID_ARG, "null / misaligned gradient pointer");
                 a.g[a.count] = (const float *)grads[i0];
                 a.n[a.count] = numels[i0];
                 a.chunk0[a.count + 1] = a.chunk0[a.count] + (int)chunks_of(numels[i0]);
@@ -241,6 +259,13 @@ int rnnt_engine_grad_norm(int n_tensors, const void *const *grads, const int64_t
 namespace {
 int adamw_launch(MtAdamArgs &a, int n_tensors, void *const *params, const void *const *grads, void *const *exp_avg,
                  void *const *exp_avg_sq, const int64_t *numels, hipStream_t st);
+
+int adamw_check_list(int n_tensors, void *const *params, const void *const *grads, void *const *exp_avg, void *const *exp_avg_sq,
+                     const int64_t *numels)
+{
+    const void *const *lists[4] = {(const void *const *)params, grads, (const void *const *)exp_avg, (const void *const *)exp_avg_sq};
+    return check_tensor_list(n_tensors, lists, 4, numels, "tensor");
+}
 }
 
 int rnnt_engine_adamw_step(int n_tensors, void *const *params, const void *const *grads,
@@ -254,6 +279,7 @@ int rnnt_engine_adamw_step(int n_tensors, void *const *params, const void *const
     if (step < 1) return engine_fail(RNNT_ERR_INVALID_ARG, "step must be >= 1 (the count AFTER this update)");
     if (!(lr >= 0.) || !(eps >= 0.) || !(beta1 >= 0. && beta1 < 1.) || !(beta2 >= 0. && beta2 < 1.) || !(weight_decay >= 0.))
         return engine_fail(RNNT_ERR_INVALID_ARG, "invalid AdamW hyper-parameter");
+    if (int rc = adamw_check_list(n_tensors, params, grads, exp_avg, exp_avg_sq, numels)) return rc;
     MtAdamArgs a;
     // scalar arithmetic in double on the host, as torch does with python floats (1 - 0.9999 in
     // fp32 would be off by 1.6e-4 relative)
@@ -278,6 +304,7 @@ int rnnt_engine_adamw_step_dev(int n_tensors, void *const *params, const void *c
     if (!lr_dev || !step_dev || !hyper_dev) return engine_fail(RNNT_ERR_INVALID_ARG, "null device scalar (lr / step / hyper)");
     if (!(eps >= 0.) || !(beta1 >= 0. && beta1 < 1.) || !(beta2 >= 0. && beta2 < 1.) || !(weight_decay >= 0.))
         return engine_fail(RNNT_ERR_INVALID_ARG, "invalid AdamW hyper-parameter");
+    if (int rc = adamw_check_list(n_tensors, params, grads, exp_avg, exp_avg_sq, numels)) return rc;  // before the counter moves
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_adam_prepare, dim3(1), dim3(64), 0, st, (long long *)step_dev, lr_dev, beta1, beta2, weight_decay, hyper_dev);
     MtAdamArgs a;
@@ -299,11 +326,7 @@ int adamw_launch(MtAdamArgs &a, int n_tensors, void *const *params, const void *
         a.count = 0;
         a.chunk0[0] = 0;
         while (i0 < n_tensors && a.count < MT_MAX) {
-            if (numels[i0] < 0) return engine_fail(RNNT_ERR_INVALID_ARG, "negative element count");
             if (numels[i0] > 0) {
-                const void *ptrs[4] = {params[i0], grads[i0], exp_avg[i0], exp_avg_sq[i0]};
-                for (const void *q : ptrs)
-                    if (!q || ((uintptr_t)q & 3)) return engine_fail(RNNT_ERR_INVALID_ARG, "null / misaligned tensor pointer");
                 a.p[a.count] = (float *)params[i0]; a.g[a.count] = (const float *)grads[i0];
                 a.m[a.count] = (float *)exp_avg[i0]; a.v[a.count] = (float *)exp_avg_sq[i0];
                 a.n[a.count] = numels[i0];

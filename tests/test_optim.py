@@ -7,7 +7,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 HP = dict(lr=3e-4, betas=(0.95, 0.9999), eps=1e-8, weight_decay=0.01)  # the reference's optimizer block
-# > 40 tensors (two launches), sizes around the 16384-element chunk and the float4 tail
+# > 40 tensors (two launches), multi-chunk sizes (the chunk is 4096 elements) and the float4 tail; the chunk's own edges are
+# tests/test_optim_edges_gpu.py's
 SIZES = [(1024, 512), (1024,), (3,), (16384,), (16385,), (7, 9, 5), (1,), (40000,)] + [(33, 17)] * 45
 
 
