@@ -447,13 +447,26 @@ int rnnt_engine_lstm_predictor_bwd(const int64_t *ids, int B, int U1, int S, int
  * bound in one call, or a chunk at a time (init = 1 first, then init = 0 with the same buffers) and stop when the loop is
  * over: `host_flag` (NULL, or one int32 of PINNED host memory the caller zeroed) is set to 1 by the device when the loop
  * ends and can be polled without a synchronisation.  The caller synchronises once and reads
- *   state  int32[8]: [0] t, [1] emitted, [2] ntok = decoded tokens, [3] done, [5] iterations that did work;
+ *   state  int32[RNNT_DECODE_STATE_WORDS]: [RNNT_DECODE_T] t, [RNNT_DECODE_EMITTED] emitted, [RNNT_DECODE_NTOK] ntok = decoded tokens,
+ *          [RNNT_DECODE_DONE] done, [RNNT_DECODE_NEWTOK] a label the predictor has still to take in, [RNNT_DECODE_ITERATIONS]
+ *          iterations that did work; word 6 is [RNNT_DECODE_SETTLED] in rnnt_engine_greedy_decode_lstm's state and
+ *          [RNNT_DECODE_WORKGROUPS] in rnnt_engine_greedy_decode_persistent's, which also sets [RNNT_DECODE_CODE];
  *   tokens int32[max_length]: tokens[0] = blank (rnnt/model.py:100), tokens[1 .. ntok] = the decoded ids.
  * frames [T,H] fp32 audio frames, rows frame_stride apart, unit element stride (already projected by audio_ln when the
  * joint has one); text_W [H,O] / text_b [H]: joint.text_ln, or NULL when the joint adds the predictor output directly
  * (then O == H); W [V,H], bias [V]: joint_ln.  E, O <= 1024, E % 4 == 0, O % 4 == 0, H % 8 == 0, V % 4 == 0,
  * 1 <= scan_frames <= 128, max_length >= 2.
  */
+#define RNNT_DECODE_STATE_WORDS 8
+#define RNNT_DECODE_T 0
+#define RNNT_DECODE_EMITTED 1
+#define RNNT_DECODE_NTOK 2
+#define RNNT_DECODE_DONE 3
+#define RNNT_DECODE_NEWTOK 4
+#define RNNT_DECODE_ITERATIONS 5
+#define RNNT_DECODE_SETTLED 6     /* rnnt_engine_greedy_decode_lstm */
+#define RNNT_DECODE_WORKGROUPS 6  /* rnnt_engine_greedy_decode_persistent */
+#define RNNT_DECODE_CODE 7        /* rnnt_engine_greedy_decode_persistent: != 0 = not a decode */
 int rnnt_engine_greedy_decode_workspace_bytes(int H, int V, int E, int O, int scan_frames, size_t *out);
 int rnnt_engine_greedy_decode(const void *frames, int64_t frame_stride, int T, const rnnt_conv_predictor_params *p,
                               int S, int E, int O, float ln_in_eps, float ln_out_eps, const void *text_W, const void *text_b,
@@ -473,8 +486,8 @@ int rnnt_engine_greedy_decode(const void *frames, int64_t frame_stride, int T, c
  *   p, S, E, Hd, O, L, layer_norm, eps_in / eps_lstm / eps_out: as rnnt_engine_lstm_predictor_fwd; text_W .. max_per_frame, scan_frames,
  *   iterations (0 = the bound max_length + ceil(max_frames / scan_frames) + 1), init, host_flag (raised when ALL utterances have
  *   ended): as rnnt_engine_greedy_decode.
- *   state  int32[n_utt][8]: [0] t, [1] emitted, [2] ntok, [3] done, [4] a label the predictor has still to take in, [5] iterations
- *   that did work, [6] settled (done, and the last label taken in); tokens int32[n_utt][max_length]: row u as rnnt_engine_greedy_decode's.
+ *   state  int32[n_utt][RNNT_DECODE_STATE_WORDS]: the words of rnnt_engine_greedy_decode's, [RNNT_DECODE_SETTLED] settled (done, and the
+ *   last label taken in); tokens int32[n_utt][max_length]: row u as rnnt_engine_greedy_decode's.
  *   state_out: NULL or [L][2][n_utt][Hd], the LSTM state after each utterance's last label (after the start blank if it has none).
  *   The workspace BEGINS with the text vectors [n_utt][H] (the joint's text input after each utterance's last label).
  * An utterance's tokens, state words and state_out rows are bit-identical whatever its neighbours, its position and n_utt.
@@ -497,7 +510,7 @@ int rnnt_engine_greedy_decode_lstm(const void *frames, int64_t frame_stride, int
  * conv1 replaced by per-token table rows and joint.text_ln folded into the predictor's linear layer (tables and folded matrices
  * come from `tables`, below: the caller's buffer, or rebuilt from the parameters inside this call).  Same arguments, state and tokens
  * as rnnt_engine_greedy_decode without scan_frames / iterations / init (the block is 16 frames, the call is the whole decode);
- * state[5] = iterations, state[6] = workgroups, state[7] != 0: the loop did NOT decode (state and tokens are then not a decode;
+ * state[RNNT_DECODE_ITERATIONS] = iterations, state[RNNT_DECODE_WORKGROUPS] = workgroups, state[RNNT_DECODE_CODE] != 0: the loop did NOT decode (state and tokens are then not a decode;
  * nothing is raised on the stream) — 1..9: a hand-off never arrived within the bounded spin (~0.4 s: a workgroup was not resident)
  * and the loop gave up; 10 / 11: an audio frame / a text vector holds an entry beyond +-30 or a non-finite one, where the loop's
  * factored tanh(e + p) = 1 - 2 / (1 + exp 2e exp 2p) is not exact.  In every such case decode the utterance with
@@ -528,7 +541,7 @@ int rnnt_engine_greedy_decode_persistent(const void *frames, int64_t frame_strid
  *   [RNNT_STREAM_DONE] 1 once 1 + labels reached max_length (later pushes consume nothing),
  *   [RNNT_STREAM_TOKENS + j] j < 7: the last 7 tokens, newest first, the leading blank included, -1 before the start,
  *   [RNNT_STREAM_PUSH_LABELS] labels the last push emitted, [RNNT_STREAM_PUSH_ITERATIONS] its iterations that did work,
- *   [RNNT_STREAM_STATUS] its status: 0, or a persistent push's state[7] code of rnnt_engine_greedy_decode_persistent (1..9 a hand-off
+ *   [RNNT_STREAM_STATUS] its status: 0, or a persistent push's state[RNNT_DECODE_CODE] of rnnt_engine_greedy_decode_persistent (1..9 a hand-off
  *   never arrived, 10 / 11 an audio frame / a text vector beyond +-30).  A push with a non-zero status changes only the three push
  *   words: redo it from the same state with persistent = 0.
  * rnnt_engine_greedy_stream_init writes the initial block ([blank, -1 x 6] as the tokens, zeros elsewhere) by a kernel.

@@ -44,7 +44,7 @@
 // (double)logit - (double)lse is added to a double score; logaddexp in double).
 // Ties (no result may depend on one): finished entries first, then parent slot ascending, then token id ascending; the
 // per-slot top labels break ties by the lower token id (torch.argmax's first index at beam 1).
-#include "kernels.hpp"
+#include "decode_kernels.hpp"
 #include <type_traits>
 
 #define BM 16          // slots: the M dimension of every product
@@ -161,8 +161,6 @@ template <> struct beam_streams<BeamStream> { static constexpr bool value = true
 // the word that stops a search's kernels: `done`, a stream's `at rest`
 template <typename... U> __device__ __forceinline__ int beam_idle(const int32_t *state) { return state[beam_streams<U...>::value ? BS_REST : BS_DONE]; }
 #define BEAM_UTT(ub) const BeamBatch B = beam_batch(ub...); const unsigned u = beam_batched<U...>::value ? blockIdx.y : 0u; const size_t uoff = u * B.stride
-// utterance u's copy of a per-search buffer, `off` = u * stride bytes on (0 for the single search)
-template <typename T> __device__ __forceinline__ T *beam_utt(T *p, size_t off) { return (T *)((char *)p + off); }
 
 struct BeamSlots {
     double *score;               // [2][BM]
@@ -179,25 +177,11 @@ __device__ __forceinline__ BeamSlots beam_utt(BeamSlots P, size_t stride)
     return P;
 }
 
-__device__ __forceinline__ float beam_gelu(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
-
 __device__ __forceinline__ double beam_logaddexp(double a, double b)
 {
     const double m = fmax(a, b);
     if (m == -__builtin_inf()) return m;
     return m + log1p(exp(-fabs(a - b)));
-}
-
-__device__ __forceinline__ float beam_block_sum(float v, float *red)  // 256 threads; red[4]
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float s = (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
-    return s;
 }
 
 // ---- start of a search: slot 0 of buffer 0 = the empty hypothesis (score 0, text vector to compute), everything else empty
@@ -245,7 +229,7 @@ __global__ __launch_bounds__(256) void k_beam_conv1(const int32_t *__restrict__ 
             float v = b1[i] + a2[i];
             if (a1) v += a1[i];
             if (a0) v += a0[i];
-            out[i] = beam_gelu(v);
+            out[i] = gelu_erf(v);
         }
     }
 }
@@ -313,7 +297,7 @@ __global__ __launch_bounds__(256) void k_beam_gemm16(const int32_t *__restrict__
     const int row = threadIdx.x >> 4, col = threadIdx.x & 15, n = n0 + col;
     if (n >= N || (masked && !need[cur * BM + row])) return;
     float v = ((s_acc[0][row][col] + s_acc[1][row][col]) + (s_acc[2][row][col] + s_acc[3][row][col])) + (bias ? bias[n] : 0.f);
-    if (act) v = beam_gelu(v);
+    if (act) v = gelu_erf(v);
     Y[(masked ? (size_t)cur * y_par : 0) + (size_t)row * ldy + n] = v;
 }
 
@@ -331,12 +315,8 @@ __global__ __launch_bounds__(256) void k_beam_ln16(const int32_t *__restrict__ s
     const int cur = state[BS_CUR], j = blockIdx.x;
     if (!need[cur * BM + j]) return;
     const float *x = z + (size_t)j * O;
-    float s = 0.f;
-    for (int i = threadIdx.x; i < O; i += 256) s += x[i];
-    const float mean = beam_block_sum(s, red) / O;
-    float s2 = 0.f;
-    for (int i = threadIdx.x; i < O; i += 256) { const float d = x[i] - mean; s2 += d * d; }
-    const float rstd = rsqrtf(beam_block_sum(s2, red) / O + eps);
+    float mean, rstd;
+    row_ln_stats(x, O, eps, red, mean, rstd);
     float *y = pvec + ((size_t)cur * BM + j) * O;
     for (int i = threadIdx.x; i < O; i += 256) y[i] = (x[i] - mean) * rstd * gamma[i] + beta[i];
 }

@@ -9,14 +9,12 @@
 //   out[1] = its token (blank if none)
 //   out[2 + k] = argmax of frame t0 + k                 (first index on ties, like torch.argmax)
 // so the host synchronises once per emitted token or per all-blank block.
-#include "kernels.hpp"
+#include "decode_kernels.hpp"
 #include "smallgemm.hpp"
 
 // logits[k, v] = tanh(enc[t0+k, :] + pred[:]) . W[v, :] + bias[v] for a handful of frames: M is tiny,
-// so the parallelism is over the vocabulary — one workgroup per 32 vocabulary rows (x 32 frames),
-// its 4 waves split H and meet in LDS.  fp32 MFMA 32x32x2 with the engine's K permutation: a
-// lane's float4 of 4 consecutive h feeds 4 MFMAs, for enc/pred and W alike (W in its natural
-// [V,H] layout, no re-packing).  H % 8 == 0.
+// so the parallelism is over the vocabulary — one workgroup per 32 vocabulary rows (x 32 frames): the scan tile of
+// decode_kernels.hpp, leaving as logits.  H % 8 == 0.
 __global__ __launch_bounds__(256) void k_scan_logits(const float *__restrict__ enc, long enc_st,
                                                      const float *__restrict__ pred,
                                                      const float *__restrict__ W,
@@ -32,28 +30,15 @@ __global__ __launch_bounds__(256) void k_scan_logits(const float *__restrict__ e
     const float *pr = pred + 4 * half;
     const float *wr = W + (long)vrow * H + 4 * half;
     f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    for (int c = wave; c < H / 8; c += 4) {
-        const f32x4 e4 = *(const f32x4 *)(er + 8 * c), p4 = *(const f32x4 *)(pr + 8 * c);
-        const f32x4 w4 = *(const f32x4 *)(wr + 8 * c);
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fast_tanh(e4[s] + p4[s]), w4[s], acc, 0, 0, 0);
-    }
-    if (wave > 0) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s_acc[wave - 1][r][lane] = acc[r];
-    }
-    __syncthreads();
+    scan_tile_mul(acc, er, pr, wr, H / 8, wave);
+    scan_tile_reduce(acc, s_acc, lane, wave);
     if (wave == 0) {
         const int v = v0 + i;
         const float bv = v < V ? bias[v] : 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int k = k0 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            const float x = ((acc[r] + s_acc[0][r][lane]) + (s_acc[1][r][lane] + s_acc[2][r][lane])) + bv;
-            if (k < K && v < V) logits[(long)k * V + v] = x;
+            const int k = k0 + scan_tile_frame(r, half);
+            if (k < K && v < V) logits[(long)k * V + v] = acc[r] + bv;
         }
     }
 }
@@ -112,7 +97,7 @@ void launch_argmax_scan(const float *logits, int K, int V, int blank, int t0, in
 // kernel sequence per ITERATION with every decision taken on the device — the host enqueues an upper bound of
 // iterations and synchronises ONCE per utterance (rnnt_engine_greedy_scan alone still needed one sync per token).
 //
-// state (int32[8]): [0] t  [1] emitted  [2] ntok (tokens after the leading blank)  [3] done  [4] newtok
+// state (int32[8], the DEC_ST_* words of decode_kernels.hpp): t, emitted, ntok (tokens after the leading blank), done, newtok
 // tokens (int32[max_length]): tokens[0] = blank (model.py:100), tokens[1 .. ntok] the decoded ids.
 //
 // The reference re-runs the predictor on the whole history and keeps the LAST frame; the module is causal (left
@@ -131,21 +116,10 @@ __global__ void k_dec_init(int32_t *state, int32_t *tokens, float *rings, int nr
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < nring) rings[i] = 0.f;
     if (i == 0) {
-        state[0] = 0; state[1] = 0; state[2] = 0; state[3] = 0; state[4] = 1; state[5] = 0; state[6] = 0; state[7] = 0;
+        dec_state_init(state);
         if (tokens) tokens[0] = blank;
     }
 }
-
-__device__ __forceinline__ float dec_block_sum(float v, float *red)  // 256 threads; red[4]
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ float dec_gelu(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 
 // y[o] = act(bias[o] + sum_tap sum_i Wp[(tap * N + o) * K + i] * x_tap[i]),  one wave per o, 4 per workgroup.
 // MODE 0: x_tap = ring[(p - (TAPS-1) + tap) & mask] (zeros for positions < 0), p = ntok: the ring's newest entry.
@@ -163,9 +137,9 @@ __global__ __launch_bounds__(256) void k_dec_gemv(const int32_t *__restrict__ st
 {
     __shared__ float xs[5 * 1024];
     __shared__ float red[4];
-    if (state[3] || !state[4]) return;  // the loop is over / nothing new to predict from (workgroup-uniform)
+    if (state[DEC_ST_DONE] || !state[DEC_ST_NEWTOK]) return;  // the loop is over / nothing new to predict from (workgroup-uniform)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int p = state[2];
+    const int p = state[DEC_ST_NTOK];
     // this wave's weights (one output feature: taps x K floats, <= 20 float4 per lane) are requested FIRST: their round
     // trip through L2 overlaps the staging / normalisation of the input vector (a chain of dependent loads, reductions and
     // barriers: 6.3 us per layer with the weights behind it, tools/bench_decode.py)
@@ -181,11 +155,8 @@ __global__ __launch_bounds__(256) void k_dec_gemv(const int32_t *__restrict__ st
             }
     }
     if (MODE == 1 || MODE == 3) {  // x = LN(in) * gamma + beta
-        float s = 0.f, s2 = 0.f;
-        for (int i = tid; i < K; i += 256) { const float v = in[i]; s += v; }
-        const float mean = dec_block_sum(s, red) / K;
-        for (int i = tid; i < K; i += 256) { const float d = in[i] - mean; s2 += d * d; }
-        const float rstd = rsqrtf(dec_block_sum(s2, red) / K + eps);
+        float mean, rstd;
+        row_ln_stats(in, K, eps, red, mean, rstd);
         for (int i = tid; i < K; i += 256) {
             const float y = (in[i] - mean) * rstd * emb_or_gamma[i] + gamma_or_beta[i];
             if (MODE == 3) { if (blockIdx.x == 0) out[i] = y; }
@@ -203,11 +174,8 @@ __global__ __launch_bounds__(256) void k_dec_gemv(const int32_t *__restrict__ st
             int tok = tokens[p];
             tok = tok < 0 ? 0 : (tok >= S ? S - 1 : tok);
             const float *e = emb_or_gamma + (long)tok * K;
-            float s = 0.f, s2 = 0.f;
-            for (int i = tid; i < K; i += 256) s += e[i];
-            const float mean = dec_block_sum(s, red) / K;
-            for (int i = tid; i < K; i += 256) { const float d = e[i] - mean; s2 += d * d; }
-            const float rstd = rsqrtf(dec_block_sum(s2, red) / K + eps);
+            float mean, rstd;
+            row_ln_stats(e, K, eps, red, mean, rstd);
             for (int i = tid; i < K; i += 256) {
                 const float y = (e[i] - mean) * rstd * gamma_or_beta[i] + beta[i];
                 xs[(taps - 1) * K + i] = y;
@@ -232,14 +200,13 @@ __global__ __launch_bounds__(256) void k_dec_gemv(const int32_t *__restrict__ st
     for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
     if (lane == 0) {
         float v = acc + (bias ? bias[o] : 0.f);
-        if (act) v = dec_gelu(v);
+        if (act) v = gelu_erf(v);
         out[(ring_out ? (long)(p & out_mask) * N : 0) + o] = v;
     }
 }
 
-// the scan of `K` frames from t = state[0] (frames past T-1 repeat the last one; k_dec_update ignores them): each
-// workgroup's 32 frames x 32 vocabulary entries leave as ONE (max, first index) pair per frame — part[frame][v block] —
-// not as logits: k_dec_update then looks at V/32 candidates per frame instead of V values
+// the scan of `K` frames from the state's t (frames past T-1 repeat the last one; k_dec_update ignores them): the scan tile of
+// decode_kernels.hpp, leaving as candidates part[frame][v block]
 // LN: `pred` is the predictor's un-normalised output z (no text_ln in the joint): every workgroup applies the output
 // LayerNorm itself (H <= 1024 floats; saves the iteration a kernel), keeping the result in LDS.
 template <bool LN>
@@ -251,124 +218,48 @@ __global__ __launch_bounds__(256) void k_dec_scan_logits(const int32_t *__restri
     __shared__ float s_acc[3][16][64];
     __shared__ __attribute__((aligned(16))) float s_pred[LN ? 1024 : 4];
     __shared__ float red[4];
-    if (state[3]) return;
+    if (state[DEC_ST_DONE]) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31, half = lane >> 5;
     const int v0 = blockIdx.x * 32, k0 = blockIdx.y * 32;
-    const int t0 = state[0];
+    const int t0 = state[DEC_ST_T];
     const int frame = min(t0 + min(k0 + i, K - 1), T - 1), vrow = min(v0 + i, V - 1);
     const float *er = enc + (long)frame * enc_st + 4 * half;
     if (LN) {  // y = LN(z) * gamma + beta   (rnnt/predictor.py:229)
-        const int tid = threadIdx.x;
-        float s1 = 0.f, s2 = 0.f;
-        for (int j = tid; j < H; j += 256) s1 += pred[j];
-        const float mean = dec_block_sum(s1, red) / H;
-        for (int j = tid; j < H; j += 256) { const float d = pred[j] - mean; s2 += d * d; }
-        const float rstd = rsqrtf(dec_block_sum(s2, red) / H + eps);
-        for (int j = tid; j < H; j += 256) s_pred[j] = (pred[j] - mean) * rstd * gamma[j] + beta[j];
+        float mean, rstd;
+        row_ln_stats(pred, H, eps, red, mean, rstd);
+        for (int j = threadIdx.x; j < H; j += 256) s_pred[j] = (pred[j] - mean) * rstd * gamma[j] + beta[j];
         __syncthreads();
     }
     const float *pr = (LN ? (const float *)s_pred : pred) + 4 * half;
     const float *wr = W + (long)vrow * H + 4 * half;
     f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    // A chunk (8 h: 4 MFMAs, ~256 matrix-pipe cycles) does not cover an L2 round trip and a 32-frame block is only V/32
-    // workgroups: the wave's chunks go in GROUPS of 8 with all 24 loads of the next group in flight while the current
-    // one is multiplied (two chunks ahead measured 21 us per block at H = 1024: one round trip per chunk).
-    const int NC = H / 8;
-    struct Ops { f32x4 e, p, w; };
-    auto load = [&](Ops &o, int c) {
-        const int cc = c < NC ? c : NC - 1;
-        o.e = *(const f32x4 *)(er + 8 * cc); o.p = *(const f32x4 *)(pr + 8 * cc); o.w = *(const f32x4 *)(wr + 8 * cc);
-    };
-    auto load8 = [&](Ops (&g)[8], int c0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) load(g[j], c0 + 4 * j);
-    };
-    auto mul8 = [&](const Ops (&g)[8], int c0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (c0 + 4 * j < NC) {  // wave-uniform
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fast_tanh(g[j].e[s] + g[j].p[s]), g[j].w[s], acc, 0, 0, 0);
-            }
-    };
-    Ops ga[8], gb[8];
-    load8(ga, wave);
-    for (int c = wave; c < NC; c += 64) {  // two groups (2 x 8 chunks x 4 waves) per trip
-        load8(gb, c + 32);
-        mul8(ga, c);
-        load8(ga, c + 64);
-        mul8(gb, c + 32);
-    }
-    if (wave > 0) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s_acc[wave - 1][r][lane] = acc[r];
-    }
-    __syncthreads();
-    if (wave == 0) {
-        const int v = v0 + i;
-        const float bv = v < V ? bias[v] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int k = k0 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            float x = ((acc[r] + s_acc[0][r][lane]) + (s_acc[1][r][lane] + s_acc[2][r][lane])) + bv;
-            if (v >= V) x = RNNT_NEG_INF;
-            const float M = half_max_dpp(x, half);  // every lane of the half: the maximum of the frame's 32 entries
-            const unsigned long long hit = __ballot(x == M);  // first lane of the half that holds it = the lowest index
-            const unsigned h32 = half ? (unsigned)(hit >> 32) : (unsigned)hit;
-            if (i == 0 && k < K) part[(long)k * gridDim.x + blockIdx.x] = float2{M, __int_as_float(v0 + __builtin_ctz(h32))};
-        }
-    }
+    scan_tile_mul(acc, er, pr, wr, H / 8, wave);
+    scan_tile_reduce(acc, s_acc, lane, wave);
+    if (wave == 0) scan_tile_candidates(acc, bias, v0, k0, K, V, part, lane);
 }
 
-// argmax of every scanned frame from its V/32 candidates (first index on ties, like torch.argmax: candidates are in
-// increasing index order), then the loop's bookkeeping (rnnt/model.py:108-125; the host-side twin: rnnt_amd/model.py):
-//   hit = first frame of [t, t + n) whose argmax is not blank, n = min(K, T - t)
-//   none: t += n, emitted = 0                                  (an all-blank block)
-//   else: t = hit (emitted = 0 if hit > t), append the token, ++emitted; emitted == max_per_frame: ++t, emitted = 0
-//   done = t >= T or 1 + ntok >= max_length     (max_length 0: state[8] holds it — a stream's push, whose cap depends on the labels so far)
+// argmax of every scanned frame from its V/32 candidates, then the loop's bookkeeping over the n = min(K, T - t) frames scanned
+// (cand_argmax, dec_advance: decode_kernels.hpp).  max_length 0: the state's CAP word holds it — a stream's push, whose cap depends on
+// the labels so far.
 __global__ __launch_bounds__(128) void k_dec_update(const float2 *__restrict__ part, int K, int NB, int blank, int T, int max_length,
                                                     int max_per_frame, int32_t *__restrict__ state, int32_t *__restrict__ tokens,
                                                     int32_t *host_flag)
 {
     __shared__ int s_tok[128];
-    if (state[3]) return;
-    if ((int)threadIdx.x < K) {
-        const float2 *p = part + (long)threadIdx.x * NB;
-        float best = RNNT_NEG_INF;
-        int bi = 0;
-        for (int j = 0; j < NB; ++j) {
-            const float2 c = p[j];
-            if (c.x > best) { best = c.x; bi = __float_as_int(c.y); }
-        }
-        s_tok[threadIdx.x] = bi;
-    }
+    if (state[DEC_ST_DONE]) return;
+    if ((int)threadIdx.x < K) s_tok[threadIdx.x] = cand_argmax(part + (long)threadIdx.x * NB, NB);
     __syncthreads();
     if (threadIdx.x == 0) {
-        int t = state[0], emitted = state[1], ntok = state[2];
-        const int n = min(K, T - t);
-        int hit = -1;
-        for (int k = 0; k < n; ++k)
-            if (s_tok[k] != blank) { hit = k; break; }
-        int newtok = 0;
-        if (hit < 0) { t += n; emitted = 0; }
-        else {
-            if (hit > 0) emitted = 0;
-            t += hit;
-            tokens[++ntok] = s_tok[hit];
-            newtok = 1;
-            if (++emitted >= max_per_frame) { ++t; emitted = 0; }
-        }
-        state[0] = t; state[1] = emitted; state[2] = ntok; state[4] = newtok;
-        const int ml = max_length > 0 ? max_length : state[8];
-        const int done = (t >= T || ntok + 1 >= ml) ? 1 : 0;
-        state[3] = done;
-        state[5] += 1;  // iterations that did work (diagnostic)
+        const int t = state[DEC_ST_T], n = min(K, T - t);
+        const int hit = dec_first_hit(s_tok, n, blank);
+        const DecPos p = dec_advance(t, state[DEC_ST_EMITTED], state[DEC_ST_NTOK], hit, n, T, max_length > 0 ? max_length : state[DEC_ST_CAP],
+                                     max_per_frame, [&](int at) { tokens[at] = s_tok[hit]; });
+        state[DEC_ST_T] = p.t; state[DEC_ST_EMITTED] = p.emitted; state[DEC_ST_NTOK] = p.ntok; state[DEC_ST_NEWTOK] = p.newtok;
+        state[DEC_ST_DONE] = p.done;
+        state[DEC_ST_ITERS] += 1;  // iterations that did work (diagnostic)
         // the host's cue to stop enqueueing iterations (mapped pinned memory, polled without a synchronisation)
-        if (done && host_flag) __hip_atomic_store(host_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (p.done && host_flag) __hip_atomic_store(host_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
@@ -465,7 +356,7 @@ void launch_dec_loop(const DecLoopArgs &a, hipStream_t st)
 // k_dec_scan_logits); sums are associated differently from the per-kernel chain (tables, folded projection), i.e. logits
 // differ in the last bits — token lists are equal wherever the per-frame loop's argmax is not a rounding-level tie
 // (tests/test_gpu_parity.py::test_greedy_decode_persistent_matches_per_frame_loop).
-// Every spin is bounded: a workgroup that gives up writes state[7] and leaves, the others follow.
+// Every spin is bounded: a workgroup that gives up writes the state's CODE word and leaves, the others follow.
 // ---------------------------------------------------------------------------------------
 typedef unsigned long long dp_u64;
 // Diagnostic build only (make EXTRA=-DDP_STAMPS): s_memtime spent per phase, summed over the iterations, by workgroup 0 — 16 counters
@@ -484,13 +375,13 @@ typedef unsigned long long dp_u64;
 #define DP_FRAMES 16
 #define DP_TOKS 2048
 #define DP_FACTOR_RANGE 30.f      // |x| up to which exp(2 x) is used as a factor of the hidden value (k_dp_exp_frames below)
-#define DP_CODE_FRAME_RANGE 10   // state[7]: an audio frame, or (11) a text vector, beyond it — not a decode, the caller takes the other loop
+#define DP_CODE_FRAME_RANGE 10   // the state's CODE word: an audio frame, or (11) a text vector, beyond it — not a decode, the caller takes the other loop
 #define DP_CODE_TEXT_RANGE 11
 #ifndef DP_SPIN_LIMIT
 #define DP_SPIN_LIMIT (1 << 18)  // polls (~1.5 us each: ~0.4 s) before a sweep gives up — several times the longest kernel another stream can hold a compute unit with (a cfg4 training step: 0.2 s); round 5: 2^21 = 3 s of stall before the fallback
 #endif
 // -DDP_TEST_STALL=n (tools/check_decode_giveup.sh, with a small -DDP_SPIN_LIMIT): workgroup 1 leaves at iteration n without publishing — the
-// other workgroups must give up at their next sweep, report it in state[7] and leave: the "every spin is bounded" claim, exercised
+// other workgroups must give up at their next sweep, report it in the state's CODE word and leave: the "every spin is bounded" claim, exercised
 
 __device__ __forceinline__ dp_u64 dp_load(const dp_u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void dp_store(dp_u64 *p, unsigned tag, float v)
@@ -616,7 +507,7 @@ __global__ __launch_bounds__(256) void k_dec_persist(DecPersistArgs a)
                 const int h1 = hist[back + 1], h2 = hist[back + 2];
                 const int c0 = min(hist[back], a.S - 1), c1 = min(max(h1, 0), a.S - 1), c2 = min(max(h2, 0), a.S - 1);
                 const float a2 = a.A2[(long)c0 * 3 * E + e], a1 = h1 >= 0 ? a.A1[(long)c1 * 3 * E + e] : 0.f, a0 = h2 >= 0 ? a.A0[(long)c2 * 3 * E + e] : 0.f;
-                v = dec_gelu(((a.conv1_b[e] + a2) + a1) + a0);
+                v = gelu_erf(((a.conv1_b[e] + a2) + a1) + a0);
             }
             s_ring[j] = v;
         }
@@ -716,7 +607,7 @@ __global__ __launch_bounds__(256) void k_dec_persist(DecPersistArgs a)
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(dpt0)::"memory");
 #endif
 
-    if (__hip_atomic_load(a.state + 7, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) done = 1;  // k_dp_exp_frames: a frame beyond the factored form's range
+    if (__hip_atomic_load(a.state + DEC_ST_CODE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) done = 1;  // k_dp_exp_frames: a frame beyond the factored form's range
     for (it = 1; it <= a.max_iters && !done; ++it) {
         // ---- exp(2 enc) fragments: lane i16 holds the frame of [t, t + 16) that is i16 mod 16 (frames past T-1 repeat the last; the
         // bookkeeping ignores them); only lanes whose frame changed load
@@ -741,7 +632,7 @@ __global__ __launch_bounds__(256) void k_dec_persist(DecPersistArgs a)
                 const int c0 = min(max(tk0, 0), a.S - 1), c1 = min(max(tk1, 0), a.S - 1), c2 = min(max(tk2, 0), a.S - 1);
                 for (int e = tid; e < E; e += 256) {
                     const float a2 = a.A2[(long)c0 * 3 * E + e], a1 = tk1 >= 0 ? a.A1[(long)c1 * 3 * E + e] : 0.f, a0 = tk2 >= 0 ? a.A0[(long)c2 * 3 * E + e] : 0.f;
-                    s_ring[(p & 7) * E + e] = dec_gelu(((s_c1[e] + a2) + a1) + a0);
+                    s_ring[(p & 7) * E + e] = gelu_erf(((s_c1[e] + a2) + a1) + a0);
                 }
             }
             __syncthreads();
@@ -754,7 +645,7 @@ __global__ __launch_bounds__(256) void k_dec_persist(DecPersistArgs a)
                     dp_wave_sums<2>(acc);
                     const float v = lane == 0 ? cb2[0] + prA[0] + acc[0] : cb2[1] + prA[1] + acc[1];
                     const int r = wave + 4 * lane;
-                    if (lane < 2 && r < rpA) s_pub[r] = dec_gelu(v);
+                    if (lane < 2 && r < rpA) s_pub[r] = gelu_erf(v);
                 } else {
                     for (int r = wave; r < rpA; r += 4) {
                         const int o = g * rpA + r;
@@ -762,7 +653,7 @@ __global__ __launch_bounds__(256) void k_dec_persist(DecPersistArgs a)
                             f32x4 w[KR];
                             dp_row_load<KR>(w, a.wp2 + ((long)4 * E + o) * E, E, lane, true);
                             const float acc = dp_wave_sum(dp_row_mul<KR>(w, s_ring + (p & 7) * E, E, lane));
-                            if (lane == 0) s_pub[r] = dec_gelu(a.conv2_b[o] + s_pre[r] + acc);
+                            if (lane == 0) s_pub[r] = gelu_erf(a.conv2_b[o] + s_pre[r] + acc);
                         }
                     }
                 }
@@ -1015,6 +906,9 @@ __global__ __launch_bounds__(256) void k_dec_persist(DecPersistArgs a)
             const unsigned long long nb = __ballot(lane < n && mytok != a.blank);
             const int hit = nb ? (int)__builtin_ctzll(nb) : -1;
             const int tok = hit >= 0 ? __builtin_amdgcn_readlane(mytok, hit) : a.blank;
+            // dec_advance's rule (decode_kernels.hpp), written out: through the shared function this kernel — 256 VGPRs, its SGPRs
+            // spilling — compiles to other register traffic on the token's critical path and measured 0.5 - 3 % slower
+            // (profiles/decode_refactor_isa.txt); tests/test_decode_bits_gpu.py holds its state words and tokens to the other loops'
             if (hit < 0) { t += n; emitted = 0; newtok = 0; }
             else {
                 if (hit > 0) emitted = 0;
@@ -1040,16 +934,17 @@ __global__ __launch_bounds__(256) void k_dec_persist(DecPersistArgs a)
     if (g == 0 && a.lds_toks)
         for (int j = 1 + tid; j <= ntok; j += 256) a.tokens[a.tok0 + j - 1] = s_toks[j];
     if (g == 0 && tid == 0) {
-        a.state[0] = t; a.state[1] = emitted; a.state[2] = ntok; a.state[3] = done; a.state[4] = newtok; a.state[5] = it - 1; a.state[6] = G;
+        a.state[DEC_ST_T] = t; a.state[DEC_ST_EMITTED] = emitted; a.state[DEC_ST_NTOK] = ntok; a.state[DEC_ST_DONE] = done;
+        a.state[DEC_ST_NEWTOK] = newtok; a.state[DEC_ST_ITERS] = it - 1; a.state[DEC_ST_GROUPS] = G;
         if (a.host_flag) __hip_atomic_store(a.host_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    if (code && tid == 0) __hip_atomic_store(a.state + 7, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // a hand-off never arrived
+    if (code && tid == 0) __hip_atomic_store(a.state + DEC_ST_CODE, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // a hand-off never arrived
 #undef s_fail
 }
 
 // exp(2 x) of every audio frame.  tanh(e + p) = 1 - 2 / (1 + exp(2 e) exp(2 p)) is exact while neither factor leaves fp32's range:
 // |x| <= DP_FACTOR_RANGE.  A frame (here) or a text vector (in the loop) beyond it, or non-finite, is NOT clamped into a wrong answer
-// (enc = 40, text = -35: the clamped factors multiply to tanh(0), the truth is tanh(5)) — the decode reports it in state[7]
+// (enc = 40, text = -35: the clamped factors multiply to tanh(0), the truth is tanh(5)) — the decode reports it in the state's CODE word
 // (DP_CODE_*_RANGE) and leaves, and the caller runs the kernel-per-layer loop, which takes tanh of the SUM (round-5 advice).
 __global__ __launch_bounds__(256) void k_dp_exp_frames(const float *__restrict__ frames, long st, int T, int H, float *__restrict__ out,
                                                        int32_t *__restrict__ state)
@@ -1067,7 +962,7 @@ __global__ __launch_bounds__(256) void k_dp_exp_frames(const float *__restrict__
         }
         *(f32x4 *)(out + t * H + h) = y;
     }
-    if (__ballot(bad) && (threadIdx.x & 63) == 0) __hip_atomic_store(state + 7, DP_CODE_FRAME_RANGE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (__ballot(bad) && (threadIdx.x & 63) == 0) __hip_atomic_store(state + DEC_ST_CODE, DP_CODE_FRAME_RANGE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // XE[s] = LN(embedding[s]) gamma + beta for every symbol (rnnt/predictor.py:214-215)
@@ -1076,11 +971,8 @@ __global__ __launch_bounds__(256) void k_dp_ln_rows(const float *__restrict__ X,
 {
     __shared__ float red[4];
     const float *x = X + (long)blockIdx.x * K;
-    float s = 0.f, s2 = 0.f;
-    for (int i = threadIdx.x; i < K; i += 256) s += x[i];
-    const float mean = dec_block_sum(s, red) / K;
-    for (int i = threadIdx.x; i < K; i += 256) { const float d = x[i] - mean; s2 += d * d; }
-    const float rstd = rsqrtf(dec_block_sum(s2, red) / K + eps);
+    float mean, rstd;
+    row_ln_stats(x, K, eps, red, mean, rstd);
     for (int i = threadIdx.x; i < K; i += 256) Y[(long)blockIdx.x * K + i] = (x[i] - mean) * rstd * gamma[i] + beta[i];
 }
 
@@ -1261,7 +1153,7 @@ __global__ void k_stream_init(int32_t *s, int blank)
         s[i] = i == RNNT_STREAM_TOKENS ? blank : (i > RNNT_STREAM_TOKENS && i < RNNT_STREAM_TOKENS + 7) ? -1 : 0;
 }
 
-// is: the push's loop state (int32[10]: [0] frames consumed, [1] emitted, [2] ntok, [5] iterations, [7] code, [9] base), or NULL for an
+// is: the push's loop state (int32[10]: the DEC_ST_* words — T = frames consumed — with CAP and BASE), or NULL for an
 // empty push.  src: the loop path's token buffer (labels at src[base + 1 ..]), copied to out; NULL: the persistent path wrote out itself.
 __global__ __launch_bounds__(256) void k_stream_commit(int32_t *s, const int32_t *is, const int32_t *src, int32_t *out, int max_length)
 {
@@ -1270,12 +1162,12 @@ __global__ __launch_bounds__(256) void k_stream_commit(int32_t *s, const int32_t
         if (tid == 0) { s[RNNT_STREAM_PUSH_LABELS] = 0; s[RNNT_STREAM_PUSH_ITERATIONS] = 0; s[RNNT_STREAM_STATUS] = 0; }
         return;
     }
-    const int code = is[7];
-    const int base = src ? is[9] : 0, count = is[2] - base;
+    const int code = is[DEC_ST_CODE];
+    const int base = src ? is[DEC_ST_BASE] : 0, count = is[DEC_ST_NTOK] - base;
     if (code == 0 && src)
         for (int j = tid; j < count; j += 256) out[j] = src[base + 1 + j];
     if (tid != 0) return;
-    s[RNNT_STREAM_PUSH_ITERATIONS] = is[5];
+    s[RNNT_STREAM_PUSH_ITERATIONS] = is[DEC_ST_ITERS];
     s[RNNT_STREAM_STATUS] = code;
     if (code != 0) { s[RNNT_STREAM_PUSH_LABELS] = 0; return; }  // not a decode: the stream's state stays as it was
     int h[7];
@@ -1285,8 +1177,8 @@ __global__ __launch_bounds__(256) void k_stream_commit(int32_t *s, const int32_t
     for (int k = 0; k < 7; ++k)  // newest first: the push's labels from its last, then the older ones
         s[RNNT_STREAM_TOKENS + k] = k < count ? (src ? src[base + count - k] : out[count - 1 - k]) : h[k - count];
     const int labels = s[RNNT_STREAM_LABELS] + count;
-    s[RNNT_STREAM_FRAMES] += is[0];
-    s[RNNT_STREAM_EMITTED] = is[1];
+    s[RNNT_STREAM_FRAMES] += is[DEC_ST_T];
+    s[RNNT_STREAM_EMITTED] = is[DEC_ST_EMITTED];
     s[RNNT_STREAM_LABELS] = labels;
     s[RNNT_STREAM_DONE] = (s[RNNT_STREAM_DONE] || (max_length > 0 && labels + 1 >= max_length)) ? 1 : 0;
     s[RNNT_STREAM_PUSH_LABELS] = count;
@@ -1296,7 +1188,7 @@ __global__ __launch_bounds__(256) void k_stream_commit(int32_t *s, const int32_t
 // holds fewer), position base = k - 1 is the newest, and the six replay records make k_dec_gemv<2> refill the LN'd-embedding and conv1
 // rings at positions 0 .. base - 1 (the first iteration computes position base itself).  conv2 at position base reads g1[base - 4 ..
 // base], conv1 at base - 4 reads x1[base - 6 ..]: with k = 7 every value the loop reads from here on is what an uninterrupted loop
-// holds; with k < 7 the local positions are the stream's own.  is[8]: the push's cap on 1 + ntok (k_dec_update, max_length = 0).
+// holds; with k < 7 the local positions are the stream's own.  is[DEC_ST_CAP]: the push's cap on 1 + ntok (k_dec_update, max_length = 0).
 __global__ void k_stream_loop_prep(const int32_t *s, int32_t *is, int32_t *recs, int32_t *ltok, float *rings, int nring, int n,
                                    int max_length, int cap)
 {
@@ -1307,12 +1199,14 @@ __global__ void k_stream_loop_prep(const int32_t *s, int32_t *is, int32_t *recs,
         while (k < 7 && s[RNNT_STREAM_TOKENS + k] >= 0) ++k;
         for (int j = 0; j < k; ++j) ltok[j] = s[RNNT_STREAM_TOKENS + k - 1 - j];
         const int base = k - 1, idle = (s[RNNT_STREAM_DONE] || n < 1) ? 1 : 0;
-        is[0] = 0; is[1] = s[RNNT_STREAM_EMITTED]; is[2] = base; is[3] = idle; is[4] = 1; is[5] = 0; is[6] = 0; is[7] = 0;
-        is[8] = max_length > 0 ? max_length - s[RNNT_STREAM_LABELS] + base : base + cap + 2;
-        is[9] = base;
-        for (int j = 0; j < 6; ++j) {
-            int32_t *r = recs + 8 * j;
-            r[0] = 0; r[1] = 0; r[2] = j; r[3] = (idle || j >= base) ? 1 : 0; r[4] = 1; r[5] = 0; r[6] = 0; r[7] = 0;
+        dec_state_init(is);
+        is[DEC_ST_EMITTED] = s[RNNT_STREAM_EMITTED]; is[DEC_ST_NTOK] = base; is[DEC_ST_DONE] = idle;
+        is[DEC_ST_CAP] = max_length > 0 ? max_length - s[RNNT_STREAM_LABELS] + base : base + cap + 2;
+        is[DEC_ST_BASE] = base;
+        for (int j = 0; j < 6; ++j) {  // a replay record: k_dec_gemv<2> at position j, unless there is none
+            int32_t *r = recs + DEC_ST_WORDS * j;
+            dec_state_init(r);
+            r[DEC_ST_NTOK] = j; r[DEC_ST_DONE] = (idle || j >= base) ? 1 : 0;
         }
     }
 }
@@ -1330,7 +1224,7 @@ static DecStreamLayout dec_stream_layout(size_t main_bytes, int cap)
     DecStreamLayout L;
     L.is = (main_bytes + 255) & ~(size_t)255;
     L.recs = L.is + 64;
-    L.ltok = L.recs + 6 * 8 * 4;
+    L.ltok = L.recs + 6 * DEC_ST_WORDS * 4;
     L.total = L.ltok + ((size_t)cap + 8) * 4;
     return L;
 }
@@ -1375,7 +1269,7 @@ int launch_dec_stream(const DecLoopArgs &a, int persistent, hipStream_t st)
     launch_dec_loop(d, st);  // the weight packs only
     // the rings: positions 0 .. base - 1 through conv1 (k_dec_gemv<2>, as the loop's iteration runs it), nothing emitted
     for (int j = 0; j < 6; ++j)
-        hipLaunchKernelGGL(k_dec_gemv<2>, dim3((E + 3) / 4), dim3(256), 0, st, (const int32_t *)(recs + 8 * j), (const int32_t *)ltok, (const float *)b.wp1,
+        hipLaunchKernelGGL(k_dec_gemv<2>, dim3((E + 3) / 4), dim3(256), 0, st, (const int32_t *)(recs + DEC_ST_WORDS * j), (const int32_t *)ltok, (const float *)b.wp1,
                            a.p.conv1_b, (const float *)b.x1ring, 3, 3, E, E, 1, a.p.embedding, a.p.ln_in_w, a.p.ln_in_b, a.ln_in_eps, a.S, b.g1ring, 1, 7,
                            b.x1ring);
     d.init = 0;

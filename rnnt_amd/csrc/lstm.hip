@@ -19,7 +19,7 @@
 // The greedy decode with this predictor as a device loop (rnnt_engine_greedy_decode_lstm, k_ld_*) is at the end of the file, and after it
 // the predictor step of a beam-search round (rnnt_engine_beam_decode_lstm, k_bl_*; the search itself is beam.hip's).
 #include "../../include/rnnt_engine.h"
-#include "kernels.hpp"
+#include "decode_kernels.hpp"
 #include "smallgemm.hpp"
 #include "predictor_kernels.hpp"
 
@@ -106,19 +106,6 @@ BwdLayout bwd_layout(const Dims &d)
     b.cs = o;    o += al(colsum_scratch_floats((int)M, (int)cw));
     b.total = o;
     return b;
-}
-
-// sums of a and b over the workgroup's 256 threads in a fixed order, returned to every thread
-__device__ __forceinline__ void block_sum2(float &a, float &b, float *red)
-{
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) { a += __shfl_xor(a, k, 64); b += __shfl_xor(b, k, 64); }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[wave] = a; red[4 + wave] = b; }
-    __syncthreads();
-    a = (red[0] + red[1]) + (red[2] + red[3]);
-    b = (red[4] + red[5]) + (red[6] + red[7]);
-    __syncthreads();
 }
 
 __device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
@@ -222,7 +209,7 @@ struct StepF {
 template <bool LN>
 __global__ __launch_bounds__(256) void k_lstm_step_fwd(StepF a)
 {
-    __shared__ float red[8];
+    __shared__ float red[4];
     const int b = blockIdx.x, tid = threadIdx.x, Hd = a.Hd;
     const float *xg = a.xg + b * a.xg_ld;
     const float *rg = a.rg ? a.rg + (long)b * 4 * Hd : nullptr;
@@ -247,10 +234,10 @@ __global__ __launch_bounds__(256) void k_lstm_step_fwd(StepF a)
     float rstd_g = 1.f, rstd_c = 1.f;
     if (LN) {
         const float n = 4.f * Hd;
-        float s = 0.f, unused = 0.f;
+        float s = 0.f;
 #pragma unroll
         for (int k = 0; k < UNITS; ++k) s += (g[k][0] + g[k][1]) + (g[k][2] + g[k][3]);
-        block_sum2(s, unused, red);
+        s = block_sum(s, red);
         const float mean = s / n;
         float q2 = 0.f;
 #pragma unroll
@@ -258,7 +245,7 @@ __global__ __launch_bounds__(256) void k_lstm_step_fwd(StepF a)
             if (tid + 256 * k < Hd)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) q2 += (g[k][q] - mean) * (g[k][q] - mean);
-        block_sum2(q2, unused, red);
+        q2 = block_sum(q2, red);
         rstd_g = rsqrtf(q2 / n + a.eps);
 #pragma unroll
         for (int k = 0; k < UNITS; ++k)
@@ -282,16 +269,16 @@ __global__ __launch_bounds__(256) void k_lstm_step_fwd(StepF a)
         o[k] = sigmoidf(pre[3]);
     }
     if (LN) {
-        float s = 0.f, unused = 0.f;
+        float s = 0.f;
 #pragma unroll
         for (int k = 0; k < UNITS; ++k) s += c[k];
-        block_sum2(s, unused, red);
+        s = block_sum(s, red);
         const float mean = s / Hd;
         float q2 = 0.f;
 #pragma unroll
         for (int k = 0; k < UNITS; ++k)
             if (tid + 256 * k < Hd) q2 += (c[k] - mean) * (c[k] - mean);
-        block_sum2(q2, unused, red);
+        q2 = block_sum(q2, red);
         rstd_c = rsqrtf(q2 / Hd + a.eps);
 #pragma unroll
         for (int k = 0; k < UNITS; ++k) c[k] = (c[k] - mean) * rstd_c;
@@ -481,13 +468,23 @@ SgArgs sg(const float *A, long lda, const float *B, long ldb, float *C, long ldc
 //   [embedding + input LayerNorm of the rows that emitted a label]  per layer [both gate products: x x2g^T and h p2g^T, one launch]
 //   [row step: gates, g_norm, cell, c_norm, h — in place]  [linear product] [+ bias, output LayerNorm]  with joint.text_ln
 //   [its product] [+ bias]  [scan of scan_frames frames from each utterance's own t]  [argmax + bookkeeping per utterance].
-// state (int32[n_utt][8]): [0] t  [1] emitted  [2] ntok  [3] done  [4] newtok: the predictor has a label to take in
-//   [5] iterations that did work  [6] settled: done and the last label taken in (nothing is left to do for the utterance).
+// state (int32[n_utt][8], the DEC_ST_* words of decode_kernels.hpp): t, emitted, ntok, done, newtok: the predictor has a label to
+//   take in, iterations that did work, settled: done and the last label taken in (nothing is left to do for the utterance).
 // A row whose utterance emitted nothing leaves h, c and its text vector untouched; a product computes every row of the tile and
 // the row kernels ignore the others.  Row m of a product reads row m of its operand only and the contraction ranges depend on K
 // alone, so an utterance's numbers do not depend on its neighbours, its position or n_utt.  No atomics on results (one counter of
 // settled utterances raises the host's flag), no workgroup waits on another, every sum in a fixed order.
 // ---------------------------------------------------------------------------------------
+// floats per row of the partial tiles of the widest product of a predictor step (gates: both products of a layer; linear; text_ln)
+size_t ld_gp_floats(int E, int Hd, int O, int H)
+{
+    size_t g = (size_t)(rec_splits(E) + rec_splits(Hd)) * 4 * Hd;
+    if ((size_t)2 * rec_splits(Hd) * 4 * Hd > g) g = (size_t)2 * rec_splits(Hd) * 4 * Hd;
+    if ((size_t)rec_splits(Hd) * O > g) g = (size_t)rec_splits(Hd) * O;
+    if ((size_t)rec_splits(O) * H > g) g = (size_t)rec_splits(O) * H;
+    return g;
+}
+
 struct LdLayout { size_t text, x1, hc, y, gp, part, ctrl, total; };  // floats; the text vectors [n_utt][H] come first (the ABI says so)
 LdLayout ld_layout(int n_utt, int E, int Hd, int O, int L, int H, int V, int scan_frames)
 {
@@ -498,11 +495,7 @@ LdLayout ld_layout(int n_utt, int E, int Hd, int O, int L, int H, int V, int sca
     w.x1 = o;   o += al(n * E);
     w.hc = o;   o += al((size_t)L * 2 * n * Hd);
     w.y = o;    o += al(n * O);
-    size_t g = (size_t)(rec_splits(E) + rec_splits(Hd)) * 4 * Hd;  // partial tiles of the widest product
-    if ((size_t)2 * rec_splits(Hd) * 4 * Hd > g) g = (size_t)2 * rec_splits(Hd) * 4 * Hd;
-    if ((size_t)rec_splits(Hd) * O > g) g = (size_t)rec_splits(Hd) * O;
-    if ((size_t)rec_splits(O) * H > g) g = (size_t)rec_splits(O) * H;
-    w.gp = o;   o += al(g * n);
+    w.gp = o;   o += al(ld_gp_floats(E, Hd, O, H) * n);
     w.part = o; o += al(n * scan_frames * ((V + 31) / 32) * 2);
     w.ctrl = o; o += 64;
     w.total = o;
@@ -515,27 +508,21 @@ __global__ __launch_bounds__(256) void k_ld_init(int32_t *__restrict__ states, i
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < nhc) hc[i] = 0.f;
     if (i < n_utt) {
-        int32_t *s = states + 8 * i;
-        s[0] = 0; s[1] = 0; s[2] = 0; s[3] = 0; s[4] = 1; s[5] = 0; s[6] = 0; s[7] = 0;
+        dec_state_init(states + DEC_ST_WORDS * i);
         tokens[(long)i * max_length] = blank;
     }
     if (i == 0) ctrl[0] = 0;
 }
 
-// one row of the embedding + input LayerNorm: out[E] = LayerNorm_E(embedding[tok]) (the workgroup's 256 threads; red: 8 floats of LDS)
+// one row of the embedding + input LayerNorm: out[E] = LayerNorm_E(embedding[tok]) (the workgroup's 256 threads; red: 4 floats of LDS)
 __device__ __forceinline__ void ld_embed_row(const float *__restrict__ emb, int S, int tok, const float *__restrict__ gamma,
                                              const float *__restrict__ beta, float eps, int E, float *__restrict__ out, float *red)
 {
     const int tid = threadIdx.x;
     tok = tok < 0 ? 0 : (tok >= S ? S - 1 : tok);
     const float *e = emb + (long)tok * E;
-    float s = 0.f, q = 0.f, unused = 0.f;
-    for (int i = tid; i < E; i += 256) s += e[i];
-    block_sum2(s, unused, red);
-    const float mean = s / E;
-    for (int i = tid; i < E; i += 256) { const float d = e[i] - mean; q += d * d; }
-    block_sum2(q, unused, red);
-    const float rstd = rsqrtf(q / E + eps);
+    float mean, rstd;
+    row_ln_stats(e, E, eps, red, mean, rstd);
     for (int i = tid; i < E; i += 256) out[i] = (e[i] - mean) * rstd * gamma[i] + beta[i];
 }
 
@@ -544,18 +531,18 @@ __global__ __launch_bounds__(256) void k_ld_embed(const int32_t *__restrict__ st
                                                   const float *__restrict__ emb, int S, const float *__restrict__ gamma,
                                                   const float *__restrict__ beta, float eps, int E, float *__restrict__ x1)
 {
-    __shared__ float red[8];
+    __shared__ float red[4];
     const int u = blockIdx.x;
-    const int32_t *st = states + 8 * u;
-    if (!st[4]) return;
-    ld_embed_row(emb, S, tokens[(long)u * max_length + st[2]], gamma, beta, eps, E, x1 + (long)u * E, red);
+    const int32_t *st = states + DEC_ST_WORDS * u;
+    if (!st[DEC_ST_NEWTOK]) return;
+    ld_embed_row(emb, S, tokens[(long)u * max_length + st[DEC_ST_NTOK]], gamma, beta, eps, E, x1 + (long)u * E, red);
 }
 
 // whether any utterance has a label for the predictor to take in (workgroup-uniform; n_utt <= 32)
 __device__ __forceinline__ bool ld_any_new(const int32_t *states, int n_utt)
 {
     const int u = threadIdx.x & 63;
-    return __ballot(u < n_utt && states[8 * u + 4] != 0) != 0ull;
+    return __ballot(u < n_utt && states[DEC_ST_WORDS * u + DEC_ST_NEWTOK] != 0) != 0ull;
 }
 
 // up to two NT products of the same M = n_utt rows and N columns in one launch: grid (ceil(N/32), KS0 + KS1); the partial tiles of
@@ -579,7 +566,7 @@ struct LdStep {
     int Hd;
 };
 
-// k_lstm_step_fwd's definition in eval mode, nothing kept, for ONE row (the workgroup's 256 threads; red: 8 floats of LDS): `gp` the
+// k_lstm_step_fwd's definition in eval mode, nothing kept, for ONE row (the workgroup's 256 threads; red: 4 floats of LDS): `gp` the
 // row's first partial product, `c_prev` [Hd] the cell it continues, `h` / `c` [Hd] where the new state goes (c may be c_prev: a thread
 // reads a unit's cell before it writes it), `h2` / `c2` a second copy or NULL
 template <bool LN>
@@ -604,10 +591,10 @@ __device__ __forceinline__ void ld_step_row(const LdStep &a, const float *__rest
     }
     if (LN) {
         const float n = 4.f * Hd;
-        float s = 0.f, unused = 0.f;
+        float s = 0.f;
 #pragma unroll
         for (int k = 0; k < UNITS; ++k) s += (g[k][0] + g[k][1]) + (g[k][2] + g[k][3]);
-        block_sum2(s, unused, red);
+        s = block_sum(s, red);
         const float mean = s / n;
         float q2 = 0.f;
 #pragma unroll
@@ -615,7 +602,7 @@ __device__ __forceinline__ void ld_step_row(const LdStep &a, const float *__rest
             if (tid + 256 * k < Hd)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) q2 += (g[k][q] - mean) * (g[k][q] - mean);
-        block_sum2(q2, unused, red);
+        q2 = block_sum(q2, red);
         const float rstd_g = rsqrtf(q2 / n + a.eps);
 #pragma unroll
         for (int k = 0; k < UNITS; ++k)
@@ -635,16 +622,16 @@ __device__ __forceinline__ void ld_step_row(const LdStep &a, const float *__rest
         o[k] = sigmoidf(pre[3]);
     }
     if (LN) {
-        float s = 0.f, unused = 0.f;
+        float s = 0.f;
 #pragma unroll
         for (int k = 0; k < UNITS; ++k) s += c[k];
-        block_sum2(s, unused, red);
+        s = block_sum(s, red);
         const float mean = s / Hd;
         float q2 = 0.f;
 #pragma unroll
         for (int k = 0; k < UNITS; ++k)
             if (tid + 256 * k < Hd) q2 += (c[k] - mean) * (c[k] - mean);
-        block_sum2(q2, unused, red);
+        q2 = block_sum(q2, red);
         const float rstd_c = rsqrtf(q2 / Hd + a.eps);
 #pragma unroll
         for (int k = 0; k < UNITS; ++k) c[k] = (c[k] - mean) * rstd_c;
@@ -665,9 +652,9 @@ __device__ __forceinline__ void ld_step_row(const LdStep &a, const float *__rest
 template <bool LN>
 __global__ __launch_bounds__(256) void k_ld_step(LdStep a)
 {
-    __shared__ float red[8];
+    __shared__ float red[4];
     const int b = blockIdx.x, Hd = a.Hd;
-    if (!a.states[8 * b + 4]) return;
+    if (!a.states[DEC_ST_WORDS * b + DEC_ST_NEWTOK]) return;
     float *h = a.h + (long)b * Hd, *c = a.c + (long)b * Hd;
     ld_step_row<LN>(a, a.gp + (long)b * 4 * Hd, c, h, c, a.h_out ? a.h_out + (long)b * Hd : nullptr,
                     a.h_out ? a.c_out + (long)b * Hd : nullptr, red);
@@ -680,7 +667,7 @@ __device__ __forceinline__ void ld_rowfin_row(const float *__restrict__ gp, int 
                                               float *__restrict__ y, float *red)
 {
     const int tid = threadIdx.x;
-    float s = 0.f, q = 0.f, unused = 0.f;
+    float s = 0.f;
     for (int i = tid; i < N; i += 256) {  // (a thread reads back only what it wrote itself)
         float v = gp[i];
         for (int sp = 1; sp < nsp; ++sp) v += gp[sp * gp_ld + i];
@@ -689,11 +676,7 @@ __device__ __forceinline__ void ld_rowfin_row(const float *__restrict__ gp, int 
         s += v;
     }
     if (!LN) return;
-    block_sum2(s, unused, red);
-    const float mean = s / N;
-    for (int i = tid; i < N; i += 256) { const float d = y[i] - mean; q += d * d; }
-    block_sum2(q, unused, red);
-    const float rstd = rsqrtf(q / N + eps);
+    const float mean = block_sum(s, red) / N, rstd = row_ln_rstd(y, N, mean, eps, red);
     for (int i = tid; i < N; i += 256) y[i] = (y[i] - mean) * rstd * gamma[i] + beta[i];
 }
 
@@ -703,9 +686,9 @@ __global__ __launch_bounds__(256) void k_ld_rowfin(const int32_t *__restrict__ s
                                                    const float *__restrict__ bias, const float *__restrict__ gamma,
                                                    const float *__restrict__ beta, float eps, float *__restrict__ out)
 {
-    __shared__ float red[8];
+    __shared__ float red[4];
     const int u = blockIdx.x;
-    if (!states[8 * u + 4]) return;
+    if (!states[DEC_ST_WORDS * u + DEC_ST_NEWTOK]) return;
     ld_rowfin_row<LN>(gp + (long)u * N, nsp, gp_ld, N, bias, gamma, beta, eps, out + (long)u * N, red);
 }
 
@@ -717,7 +700,7 @@ __device__ __forceinline__ void ld_utt(const int32_t *utt, int u, int rows, int 
 }
 
 // decode.hip's k_dec_scan_logits<false> with the utterance as grid dimension z: scan_frames frames from the utterance's own t against
-// its own text vector (tanh of the sum), one (max, first index) candidate per frame and 32 vocabulary entries
+// its own text vector (the scan tile of decode_kernels.hpp), one (max, first index) candidate per frame and 32 vocabulary entries
 __global__ __launch_bounds__(256) void k_ld_scan(const int32_t *__restrict__ states, const float *__restrict__ enc, long enc_st,
                                                  const int32_t *__restrict__ utt, int rows, const float *__restrict__ text,
                                                  const float *__restrict__ W, const float *__restrict__ bias, float2 *__restrict__ part, int K,
@@ -725,68 +708,22 @@ __global__ __launch_bounds__(256) void k_ld_scan(const int32_t *__restrict__ sta
 {
     __shared__ float s_acc[3][16][64];
     const int u = blockIdx.z;
-    const int32_t *state = states + 8 * u;
-    if (state[3]) return;
+    const int32_t *state = states + DEC_ST_WORDS * u;
+    if (state[DEC_ST_DONE]) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31, half = lane >> 5;
     const int v0 = blockIdx.x * 32, k0 = blockIdx.y * 32;
     int first, T;
     ld_utt(utt, u, rows, first, T);
-    const int t0 = min(max(state[0], 0), T - 1);
+    const int t0 = min(max(state[DEC_ST_T], 0), T - 1);
     const int frame = first + min(t0 + min(k0 + i, K - 1), T - 1), vrow = min(v0 + i, V - 1);
     const float *er = enc + (long)frame * enc_st + 4 * half;
     const float *pr = text + (long)u * H + 4 * half;
     const float *wr = W + (long)vrow * H + 4 * half;
     f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    const int NC = H / 8;
-    struct Ops { f32x4 e, p, w; };
-    auto load = [&](Ops &o, int c) {
-        const int cc = c < NC ? c : NC - 1;
-        o.e = *(const f32x4 *)(er + 8 * cc); o.p = *(const f32x4 *)(pr + 8 * cc); o.w = *(const f32x4 *)(wr + 8 * cc);
-    };
-    auto load8 = [&](Ops (&g)[8], int c0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) load(g[j], c0 + 4 * j);
-    };
-    auto mul8 = [&](const Ops (&g)[8], int c0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (c0 + 4 * j < NC) {  // wave-uniform
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fast_tanh(g[j].e[s] + g[j].p[s]), g[j].w[s], acc, 0, 0, 0);
-            }
-    };
-    Ops ga[8], gb[8];
-    load8(ga, wave);
-    for (int c = wave; c < NC; c += 64) {  // two groups (2 x 8 chunks x 4 waves) per trip, the next group's loads in flight
-        load8(gb, c + 32);
-        mul8(ga, c);
-        load8(ga, c + 64);
-        mul8(gb, c + 32);
-    }
-    if (wave > 0) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s_acc[wave - 1][r][lane] = acc[r];
-    }
-    __syncthreads();
-    if (wave == 0) {
-        const int v = v0 + i;
-        const float bv = v < V ? bias[v] : 0.f;
-        float2 *pu = part + (long)u * K * gridDim.x;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int k = k0 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            float x = ((acc[r] + s_acc[0][r][lane]) + (s_acc[1][r][lane] + s_acc[2][r][lane])) + bv;
-            if (v >= V) x = RNNT_NEG_INF;
-            const float M = half_max_dpp(x, half);
-            const unsigned long long hit = __ballot(x == M);  // first lane of the half that holds it = the lowest index
-            const unsigned h32 = half ? (unsigned)(hit >> 32) : (unsigned)hit;
-            if (i == 0 && k < K) pu[(long)k * gridDim.x + blockIdx.x] = float2{M, __int_as_float(v0 + __builtin_ctz(h32))};
-        }
-    }
+    scan_tile_mul(acc, er, pr, wr, H / 8, wave);
+    scan_tile_reduce(acc, s_acc, lane, wave);
+    if (wave == 0) scan_tile_candidates(acc, bias, v0, k0, K, V, part + (long)u * K * gridDim.x, lane);
 }
 
 // k_dec_update's rules per utterance (one workgroup each).  An utterance that ended on a label keeps newtok for one more iteration —
@@ -798,45 +735,27 @@ __global__ __launch_bounds__(128) void k_ld_update(const float2 *__restrict__ pa
 {
     __shared__ int s_tok[128];
     const int u = blockIdx.x;
-    int32_t *state = states + 8 * u;
-    if (state[6]) return;
-    const bool was_done = state[3] != 0;
-    if (!was_done && (int)threadIdx.x < K) {
-        const float2 *p = part + ((long)u * K + threadIdx.x) * NB;
-        float best = RNNT_NEG_INF;
-        int bi = 0;
-        for (int j = 0; j < NB; ++j) {
-            const float2 c = p[j];
-            if (c.x > best) { best = c.x; bi = __float_as_int(c.y); }
-        }
-        s_tok[threadIdx.x] = bi;
-    }
+    int32_t *state = states + DEC_ST_WORDS * u;
+    if (state[DEC_ST_SETTLED]) return;
+    const bool was_done = state[DEC_ST_DONE] != 0;
+    if (!was_done && (int)threadIdx.x < K) s_tok[threadIdx.x] = cand_argmax(part + ((long)u * K + threadIdx.x) * NB, NB);
     __syncthreads();
     if (threadIdx.x != 0) return;
     int done = 1, newtok = 0;
     if (!was_done) {
         int first, T;
         ld_utt(utt, u, rows, first, T);
-        int t = state[0], emitted = state[1], ntok = state[2];
-        const int n = min(K, T - t);
-        int hit = -1;
-        for (int k = 0; k < n; ++k)
-            if (s_tok[k] != blank) { hit = k; break; }
-        if (hit < 0) { t += n; emitted = 0; }
-        else {
-            if (hit > 0) emitted = 0;
-            t += hit;
-            tokens[(long)u * max_length + (++ntok)] = s_tok[hit];
-            newtok = 1;
-            if (++emitted >= max_per_frame) { ++t; emitted = 0; }
-        }
-        done = (t >= T || ntok + 1 >= max_length) ? 1 : 0;
-        state[0] = t; state[1] = emitted; state[2] = ntok; state[3] = done;
-        state[5] += 1;
+        const int t = state[DEC_ST_T], n = min(K, T - t);
+        const int hit = dec_first_hit(s_tok, n, blank);
+        const DecPos p = dec_advance(t, state[DEC_ST_EMITTED], state[DEC_ST_NTOK], hit, n, T, max_length, max_per_frame,
+                                     [&](int at) { tokens[(long)u * max_length + at] = s_tok[hit]; });
+        state[DEC_ST_T] = p.t; state[DEC_ST_EMITTED] = p.emitted; state[DEC_ST_NTOK] = p.ntok; state[DEC_ST_DONE] = p.done;
+        done = p.done; newtok = p.newtok;
+        state[DEC_ST_ITERS] += 1;
     }
-    state[4] = newtok;
+    state[DEC_ST_NEWTOK] = newtok;
     if (done && !newtok) {
-        state[6] = 1;
+        state[DEC_ST_SETTLED] = 1;
         if (atomicAdd(ctrl, 1) + 1 == n_utt && host_flag) __hip_atomic_store(host_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
@@ -917,15 +836,13 @@ void launch_ld_loop(const LdArgs &a, hipStream_t st)
 // in it.  Same tile body, contraction ranges and row definitions as the greedy loop: the numbers of a slot depend on its token
 // sequence alone.  Every kernel returns at once where nothing needs a step.
 // ---------------------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ T *bl_utt(T *p, size_t off) { return (T *)((char *)p + off); }
-
 // the slot (u, s) of this workgroup (grid (16, n_utt)) if it awaits its step: its search's current buffer, else -1
 __device__ __forceinline__ int bl_slot_cur(const BeamLstmStep &a, int u, int s)
 {
     const int32_t *st = a.state + 32 * u;
     if (st[BEAM_ST_DONE] || !st[BEAM_ST_NEW]) return -1;
     const int cur = st[BEAM_ST_CUR] & 1;
-    return bl_utt(a.need, u * a.stride)[cur * 16 + s] ? cur : -1;
+    return beam_utt(a.need, u * a.stride)[cur * 16 + s] ? cur : -1;
 }
 __device__ __forceinline__ long bl_pool_row(const BeamLstmStep &a, const int *idx, int row)
 {
@@ -934,12 +851,12 @@ __device__ __forceinline__ long bl_pool_row(const BeamLstmStep &a, const int *id
 
 __global__ __launch_bounds__(256) void k_bl_embed(BeamLstmStep a, float *__restrict__ x1)
 {
-    __shared__ float red[8];
+    __shared__ float red[4];
     const int s = blockIdx.x, u = blockIdx.y;
     const int cur = bl_slot_cur(a, u, s);
     if (cur < 0) return;
-    const int len = min(max(bl_utt(a.len, u * a.stride)[cur * 16 + s], 0), a.max_length - 1);
-    const int tok = bl_utt(a.tok, u * a.stride)[((long)cur * 16 + s) * a.max_length + len];  // the newest token (the start blank at len 0)
+    const int len = min(max(beam_utt(a.len, u * a.stride)[cur * 16 + s], 0), a.max_length - 1);
+    const int tok = beam_utt(a.tok, u * a.stride)[((long)cur * 16 + s) * a.max_length + len];  // the newest token (the start blank at len 0)
     ld_embed_row(a.p.embedding, a.S, tok, a.p.ln_in_w, a.p.ln_in_b, a.eps_in, a.E, x1 + (long)(16 * u + s) * a.E, red);
 }
 
@@ -959,7 +876,7 @@ __global__ __launch_bounds__(256) void k_bl_gemm(BlGemm a)
 template <bool LN>
 __global__ __launch_bounds__(256) void k_bl_step(BeamLstmStep a, LdStep q, int layer)
 {
-    __shared__ float red[8];
+    __shared__ float red[4];
     const int s = blockIdx.x, u = blockIdx.y, row = 16 * u + s;
     if (bl_slot_cur(a, u, s) < 0) return;
     const long at = (long)(2 * layer) * a.Hd;
@@ -973,11 +890,11 @@ __global__ __launch_bounds__(256) void k_bl_rowfin(BeamLstmStep a, const float *
                                                    const float *__restrict__ bias, const float *__restrict__ gamma,
                                                    const float *__restrict__ beta, float eps, float *__restrict__ out, int to_pvec)
 {
-    __shared__ float red[8];
+    __shared__ float red[4];
     const int s = blockIdx.x, u = blockIdx.y, row = 16 * u + s;
     const int cur = bl_slot_cur(a, u, s);
     if (cur < 0) return;
-    float *y = to_pvec ? bl_utt(a.pvec, u * a.stride) + ((long)cur * 16 + s) * N : out + (long)row * N;
+    float *y = to_pvec ? beam_utt(a.pvec, u * a.stride) + ((long)cur * 16 + s) * N : out + (long)row * N;
     ld_rowfin_row<LN>(gp + (long)row * N, nsp, gp_ld, N, bias, gamma, beta, eps, y, red);
 }
 
@@ -989,11 +906,7 @@ BlLayout bl_layout(int n_utt, int E, int Hd, int O, int H)
     size_t o = 0;
     w.x1 = o; o += al(M * E);
     w.y = o;  o += al(M * O);
-    size_t g = (size_t)(rec_splits(E) + rec_splits(Hd)) * 4 * Hd;  // partial tiles of the widest product (ld_layout's rule)
-    if ((size_t)2 * rec_splits(Hd) * 4 * Hd > g) g = (size_t)2 * rec_splits(Hd) * 4 * Hd;
-    if ((size_t)rec_splits(Hd) * O > g) g = (size_t)rec_splits(Hd) * O;
-    if ((size_t)rec_splits(O) * H > g) g = (size_t)rec_splits(O) * H;
-    w.gp = o; o += al(g * M);
+    w.gp = o; o += al(ld_gp_floats(E, Hd, O, H) * M);
     w.total = o;
     return w;
 }

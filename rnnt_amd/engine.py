@@ -879,6 +879,14 @@ def _rows_table(table, dev):
     return torch.tensor(table, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
 
 
+# ---- the greedy loops' state words (include/rnnt_engine.h RNNT_DECODE_*): rnnt_engine_greedy_decode, _lstm and _persistent
+DECODE_STATE_WORDS = 8
+DECODE_T, DECODE_EMITTED, DECODE_NTOK, DECODE_DONE, DECODE_NEWTOK, DECODE_ITERATIONS = 0, 1, 2, 3, 4, 5
+DECODE_SETTLED = DECODE_WORKGROUPS = 6  # the LSTM loop's "settled", the persistent loop's workgroup count
+DECODE_CODE = 7  # the persistent loop: != 0 = not a decode
+DECODE_LABELS = DECODE_STATE_WORDS + 1  # state | tokens read as one list: the labels start after the state words and the leading blank
+
+
 def greedy_decode_persistent_supported(T, S, E, O, H, V, has_text):
     """Whether rnnt_engine_greedy_decode_persistent takes these sizes (else: greedy_decode_loop's kernel-per-layer chain)."""
     return _supported("rnnt_engine_greedy_decode_persistent_workspace_bytes", T, S, E, O, H, V, bool(has_text))
@@ -903,8 +911,8 @@ def greedy_decode_tables(pred_params, ln_eps, text_W, text_b, H):
 def greedy_decode_persistent(frames, pred_params, ln_eps, text_W, text_b, W, bias, blank, max_length, max_per_frame=10, tables=None):
     """Device-resident greedy decode of one utterance as ONE persistent launch (C ABI rnnt_engine_greedy_decode_persistent;
     reference rnnt/model.py:108-125 with the stateless ConvPredictor).  Arguments as greedy_decode_loop.  Returns (state int32[8],
-    tokens int32[max_length]) device tensors WITHOUT synchronising: after one synchronisation tokens[1 : 1 + state[2]] are the
-    decoded ids; state[7] != 0 means the loop gave up on a hand-off (check_decode_state raises).  `tables`: greedy_decode_tables(...) of
+    tokens int32[max_length]) device tensors WITHOUT synchronising: after one synchronisation tokens[1 : 1 + state[DECODE_NTOK]] are the
+    decoded ids; state[DECODE_CODE] != 0 means the loop gave up on a hand-off (check_decode_state raises).  `tables`: greedy_decode_tables(...) of
     the same parameters (else they are rebuilt inside this call, ~0.13 ms)."""
     m = _DecodeModel(frames, pred_params, ln_eps, text_W, text_b, W, bias)
     T = m.frames.shape[0]
@@ -912,8 +920,8 @@ def greedy_decode_persistent(frames, pred_params, ln_eps, text_W, text_b, W, bia
         n = ctypes.c_size_t(0)
         _check(lib().rnnt_engine_greedy_decode_persistent_workspace_bytes(T, *m.sizes, ctypes.byref(n)))
         ws = workspace(m.dev, n.value)
-        both = torch.empty(8 + int(max_length), dtype=torch.int32, device=m.dev)  # state | tokens: ONE device-to-host copy reads the whole result
-        state, tokens = both[:8], both[8:]
+        both = torch.empty(DECODE_STATE_WORDS + int(max_length), dtype=torch.int32, device=m.dev)  # state | tokens: ONE device-to-host copy reads the whole result
+        state, tokens = both[:DECODE_STATE_WORDS], both[DECODE_STATE_WORDS:]
         _check(lib().rnnt_engine_greedy_decode_persistent(
             _p(m.frames), ctypes.c_int64(m.frames.stride(0)), T, *m.args(blank, max_length, max_per_frame),
             _p(tables), None, _p(state), _p(tokens), _p(ws), ctypes.c_size_t(ws.numel()), _stream(m.dev)))
@@ -926,15 +934,16 @@ DECODE_RANGE_CODES = (10, 11)  # decode.hip DP_CODE_FRAME_RANGE / DP_CODE_TEXT_R
 
 
 def check_decode_state(state_list):
-    """After the synchronisation: raise if the persistent loop did not decode — state[7]: the hand-off that never arrived, or 10 / 11: an
+    """After the synchronisation: raise if the persistent loop did not decode — state[DECODE_CODE]: the hand-off that never arrived, or 10 / 11: an
     audio frame / a text vector with an entry beyond +-30 (or non-finite), where tanh(e + p) = 1 - 2 / (1 + exp 2e exp 2p) is not exact
     (greedy_decode_loop takes tanh of the sum and has no such limit)."""
-    if state_list[7] in DECODE_RANGE_CODES:
-        raise RuntimeError(f"rnnt_engine: the persistent greedy decode met an {'audio frame' if state_list[7] == 10 else 'text vector'} "
+    code = state_list[DECODE_CODE]
+    if code in DECODE_RANGE_CODES:
+        raise RuntimeError(f"rnnt_engine: the persistent greedy decode met an {'audio frame' if code == 10 else 'text vector'} "
                            "entry beyond +-30 (or non-finite): use greedy_decode_loop for this utterance")
-    if state_list[7] != 0:
-        raise RuntimeError(f"rnnt_engine: the persistent greedy decode gave up waiting for hand-off {state_list[7]} "
-                           f"(iteration {state_list[5]}, {state_list[6]} workgroups): are all of its workgroups resident?")
+    if code != 0:
+        raise RuntimeError(f"rnnt_engine: the persistent greedy decode gave up waiting for hand-off {code} "
+                           f"(iteration {state_list[DECODE_ITERATIONS]}, {state_list[DECODE_WORKGROUPS]} workgroups): are all of its workgroups resident?")
 
 
 def greedy_decode_loop(frames, pred_params, ln_eps, text_W, text_b, W, bias, blank, max_length,
@@ -945,7 +954,7 @@ def greedy_decode_loop(frames, pred_params, ln_eps, text_W, text_b, W, bias, bla
     joint.text_ln's parameters or None.  Iterations are enqueued `chunk` at a time until the device has raised the
     end-of-loop flag in a pinned host word (polled, never waited for) or the loop's upper bound is reached.
     Returns (state int32[8], tokens int32[max_length]) device tensors WITHOUT synchronising: after one
-    synchronisation tokens[1 : 1 + state[2]] are the decoded ids."""
+    synchronisation tokens[1 : 1 + state[DECODE_NTOK]] are the decoded ids."""
     m = _DecodeModel(frames, pred_params, ln_eps, text_W, text_b, W, bias)
     T = m.frames.shape[0]
     scan_frames, chunk = int(scan_frames), max(1, int(chunk))
@@ -954,7 +963,7 @@ def greedy_decode_loop(frames, pred_params, ln_eps, text_W, text_b, W, bias, bla
         n = ctypes.c_size_t(0)
         _check(lib().rnnt_engine_greedy_decode_workspace_bytes(m.H, m.V, m.E, m.O, scan_frames, ctypes.byref(n)))
         ws = workspace(m.dev, n.value)
-        state = torch.empty(8, dtype=torch.int32, device=m.dev)
+        state = torch.empty(DECODE_STATE_WORDS, dtype=torch.int32, device=m.dev)
         tokens = torch.empty(int(max_length), dtype=torch.int32, device=m.dev)
         head = (_p(m.frames), ctypes.c_int64(m.frames.stride(0)), T, *m.args(blank, max_length, max_per_frame), scan_frames)
         tail = (_p(state), _p(tokens), _p(ws), ctypes.c_size_t(ws.numel()), _stream(m.dev))
@@ -983,7 +992,7 @@ def greedy_decode_lstm(frames_list, lstm_params, text_W, text_b, W, bias, blank,
     The other arguments and the enqueueing (chunks of iterations until the device raises the pinned end flag — when ALL utterances have
     ended) as greedy_decode_loop.  Returns (state int32[N, 8], tokens int32[N, max_length], state_out float32[L, 2, N, Hd] or None, text
     float32[N, H]: the joint's text input after each utterance's last label, a view of the stream's workspace valid until the next engine
-    call on it) device tensors WITHOUT synchronising: afterwards tokens[u, 1 : 1 + state[u, 2]] are utterance u's ids, bit for bit
+    call on it) device tensors WITHOUT synchronising: afterwards tokens[u, 1 : 1 + state[u, DECODE_NTOK]] are utterance u's ids, bit for bit
     what it gives decoded alone."""
     from .lstm_predictor import _struct
     frames_list = list(frames_list)
@@ -1009,7 +1018,7 @@ def greedy_decode_lstm(frames_list, lstm_params, text_W, text_b, W, bias, blank,
                                                                     scan_frames, ctypes.byref(n)))
         ws = workspace(dev, n.value)
         utt = _rows_table(table, dev)
-        state = torch.empty(N, 8, dtype=torch.int32, device=dev)  # (a single row's stride is whatever torch says: the row is contiguous)
+        state = torch.empty(N, DECODE_STATE_WORDS, dtype=torch.int32, device=dev)  # (a single row's stride is whatever torch says: the row is contiguous)
         tokens = torch.empty(N, max_length, dtype=torch.int32, device=dev)
         state_out = torch.empty(L, 2, N, Hd, dtype=torch.float32, device=dev) if want_state else None
         st, arr = _struct(params, L, layer_norm)

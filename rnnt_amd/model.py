@@ -154,7 +154,7 @@ class RNNTModel(torch.nn.Module):
         self.last_decode_path = "lstm_loop"
         state, toks = out[:2]
         host = torch.cat((state, toks), dim=1).tolist()  # the batch's one synchronisation: [N][8 state words | tokens]
-        return [row[9:9 + row[2]] for row in host]
+        return [row[engine.DECODE_LABELS:engine.DECODE_LABELS + row[engine.DECODE_NTOK]] for row in host]
 
     def _decode_tables(self):
         """The persistent decode's model tables (engine.greedy_decode_tables: conv2's pack, conv1 as tap tables, the folded text_ln) built
@@ -233,21 +233,23 @@ class RNNTModel(torch.nn.Module):
                                                         scan_frames=max(1, min(int(scan_frames) if scan_frames > 0 else 64, 128)))
             both = getattr(state, "_with_tokens", None)  # (the persistent launch: state and tokens in one buffer, one copy)
             host = both.tolist() if both is not None else None  # the utterance's one synchronisation
-            st = host[:8] if host is not None else state.tolist()
-            if persistent and st[7] != 0:
-                # st[7] < 10: the persistent loop gave up waiting for a hand-off (its workgroups were not all resident: a device shared
-                # with another process or stream's long kernels).  st[7] >= 10 (engine.DECODE_RANGE_CODES): an audio frame or a text
+            st = host[:engine.DECODE_STATE_WORDS] if host is not None else state.tolist()
+            code = st[engine.DECODE_CODE]
+            if persistent and code != 0:
+                # code < 10: the persistent loop gave up waiting for a hand-off (its workgroups were not all resident: a device shared
+                # with another process or stream's long kernels).  code >= 10 (engine.DECODE_RANGE_CODES): an audio frame or a text
                 # vector beyond +-30, where the loop's factored tanh is not exact.  Either way nothing it wrote is a decode — run the
                 # kernel-per-layer loop, which needs no residency and takes tanh of the sum
-                if st[7] not in engine.DECODE_RANGE_CODES:
-                    warnings.warn(f"rnnt_amd: the persistent greedy decode gave up at hand-off {st[7]} (iteration {st[5]}); "
+                if code not in engine.DECODE_RANGE_CODES:
+                    warnings.warn(f"rnnt_amd: the persistent greedy decode gave up at hand-off {code} (iteration {st[engine.DECODE_ITERATIONS]}); "
                                   "falling back to the kernel-per-layer loop", RuntimeWarning)
                 state, toks = engine.greedy_decode_loop(*args, max_per_frame=10,
                                                         scan_frames=max(1, min(int(scan_frames) if scan_frames > 0 else 64, 128)))
                 st, host = state.tolist(), None
             engine.check_decode_state(st)
             self.last_decode_path = "persistent" if host is not None else "loop"
-            return host[9:9 + st[2]] if host is not None else toks[1:1 + st[2]].tolist()
+            ntok = st[engine.DECODE_NTOK]
+            return host[engine.DECODE_LABELS:engine.DECODE_LABELS + ntok] if host is not None else toks[1:1 + ntok].tolist()
         self.last_decode_path = "host"
         from .stream import HostGreedyLoop  # (one host loop, resumable: GreedyStream's host path runs it too)
         loop = HostGreedyLoop(self, max_length, max_symbols_per_frame=10, scan_frames=scan_frames)
@@ -326,10 +328,10 @@ class RNNTModel(torch.nn.Module):
         out = []
         for (state, mel), l in zip(pending, lens):
             host = state._with_tokens.tolist()
-            if host[7] != 0:  # this decode gave up waiting for a hand-off, or met an activation beyond +-30 (see greedy_decode): once more, alone
+            if host[engine.DECODE_CODE] != 0:  # this decode gave up waiting for a hand-off, or met an activation beyond +-30 (see greedy_decode): once more, alone
                 out.append(self.greedy_decode(mel, l, max_length=max_length))
             else:
-                out.append(host[9:9 + host[2]])
+                out.append(host[engine.DECODE_LABELS:engine.DECODE_LABELS + host[engine.DECODE_NTOK]])
         self.last_decode_path = "persistent"
         return out
 
