@@ -504,6 +504,76 @@ int rnnt_engine_greedy_decode_lstm(const void *frames, int64_t frame_stride, int
                                    void *stream);
 
 /*
+ * Streaming form of rnnt_engine_greedy_decode_lstm (DESIGN.md 4p "Device stream"): n_streams (1 .. 32) INDEPENDENT streams of one model,
+ * each decoded push by push, all advancing in lockstep through the same kernel sequence per iteration (5 + 2 L launches, 2 more with
+ * text_ln).  After any sequence of pushes that delivered frames 0 .. k-1 of a stream, in any chunking, its labels, its LSTM state and its
+ * text vector are bit for bit what rnnt_engine_greedy_decode_lstm gives for those k frames alone with the same max_length and
+ * max_per_frame, whatever scan_frames is, whatever the other streams do, whatever n_streams and the stream's slot.
+ * Everything a stream carries from push to push lives in the caller's BLOCK (rnnt_engine_greedy_stream_lstm_bytes bytes, 256-byte
+ * aligned), three sections each a multiple of 256 bytes:
+ *   state  int32[n_streams][RNNT_LSTM_STREAM_STATE_WORDS]:
+ *          [RNNT_LSTM_STREAM_T] frames of the CURRENT push consumed, [RNNT_LSTM_STREAM_EMITTED] labels emitted at the current frame,
+ *          [RNNT_LSTM_STREAM_LABELS] labels so far over all pushes, [RNNT_LSTM_STREAM_PAUSED] nothing to scan (the push's frames are
+ *          consumed, or done), [RNNT_LSTM_STREAM_NEWTOK] the predictor has still to take the newest token in,
+ *          [RNNT_LSTM_STREAM_PUSH_ITERATIONS] iterations of this push that did work, [RNNT_LSTM_STREAM_AT_REST] at rest,
+ *          [RNNT_LSTM_STREAM_DONE] 1 + labels reached max_length (later pushes consume nothing), [RNNT_LSTM_STREAM_FRAMES] frames
+ *          consumed over all pushes, [RNNT_LSTM_STREAM_NEWEST] the newest token (the blank after init), [RNNT_LSTM_STREAM_PUSH_LABELS]
+ *          labels this push emitted, [RNNT_LSTM_STREAM_BASE] the frames consumed when the current push began; the others 0;
+ *   h, c   float[L][2][n_streams][Hd]: the LSTM state after the stream's last label taken in;
+ *   text   float[n_streams][H]: the joint's text input after it.
+ * The workspace (rnnt_engine_greedy_stream_lstm_push_workspace_bytes) is scratch only: a push gives the same bits whatever it held.
+ * rnnt_engine_greedy_stream_lstm_init starts all streams (index = -1) or stream `index` alone ("this slot starts a new utterance"; no
+ * byte of another stream's part of the block is touched) by one kernel: zero LSTM state, newest token = blank, to be taken in, at rest.
+ * The step from zero state on the start blank runs in the first push that brings the stream a frame.
+ * rnnt_engine_greedy_stream_lstm_push enqueues one push: `frames` holds the push's frames of all streams packed into `rows` >= 1 rows,
+ *   push_table device int32[n_streams][2]: stream u's first row and frame count; a count <= 0: the stream sits the push out and no bit of
+ *          its words, h, c and text vector changes.  The kernels hold every entry inside the buffer;
+ *   max_count: the largest count (>= 0);
+ *   begin != 0 opens the push with a kernel that latches each stream's base, clears the at-rest word of the streams that got frames
+ *          (and are not done), resets their per-push words and counts the others; begin = 0 continues it (chunked enqueueing);
+ *   a stream comes to REST when all its pushed frames are consumed AND no label awaits the predictor: a push that ends on a label
+ *          capped by max_per_frame still takes that label in first (the offline loop's "settled");
+ *   max_length: 0 = unbounded, else >= 2 as rnnt_engine_greedy_decode_lstm's;
+ *   out_tokens int32[n_streams][out_stride]: row u = the labels this push gave stream u, [RNNT_LSTM_STREAM_PUSH_LABELS] of them;
+ *          out_stride >= max_count * max_per_frame is required (a stream emits at most that many in a push);
+ *   iterations: 0 = the push's bound max_count * max_per_frame + ceil(max_count / scan_frames) + 1 — every iteration of a stream not at
+ *          rest emits a label, or consumes a block of scan_frames frames or the rest of the push, and one more takes the last label
+ *          in; the pending start step shares the first iteration with its scan and adds none.  The bound does not grow with the
+ *          stream's history;
+ *   host_flag rises once ALL streams are at rest (a done stream is at rest once its last label is taken in).
+ * The model arguments as rnnt_engine_greedy_decode_lstm.  The caller synchronises once per push.  Every argument is checked before
+ * anything is enqueued: RNNT_ERR_INVALID_ARG (null or misaligned pointers, non-positive dims, max_length 1 or negative, negative
+ * max_count, rows < 1, index outside -1 .. n_streams - 1, out_stride too small), RNNT_ERR_UNSUPPORTED (n_streams > 32, scan_frames
+ * outside 1..128, rnnt_engine_lstm_predictor_fwd's limits, H % 8, V % 4), RNNT_ERR_WORKSPACE (a short workspace or a short block).
+ * The model's weights must not change while a stream is open.
+ */
+#define RNNT_LSTM_STREAM_STATE_WORDS 16
+#define RNNT_LSTM_STREAM_T 0
+#define RNNT_LSTM_STREAM_EMITTED 1
+#define RNNT_LSTM_STREAM_LABELS 2
+#define RNNT_LSTM_STREAM_PAUSED 3
+#define RNNT_LSTM_STREAM_NEWTOK 4
+#define RNNT_LSTM_STREAM_PUSH_ITERATIONS 5
+#define RNNT_LSTM_STREAM_AT_REST 6
+#define RNNT_LSTM_STREAM_DONE 7
+#define RNNT_LSTM_STREAM_FRAMES 8
+#define RNNT_LSTM_STREAM_NEWEST 9
+#define RNNT_LSTM_STREAM_PUSH_LABELS 10
+#define RNNT_LSTM_STREAM_BASE 11
+int rnnt_engine_greedy_stream_lstm_bytes(int n_streams, int S, int E, int Hd, int O, int L, int layer_norm, int H, int V, int has_text,
+                                         size_t *out);
+int rnnt_engine_greedy_stream_lstm_init(int n_streams, int Hd, int L, int H, int blank, int index, void *block, size_t bytes, void *stream);
+int rnnt_engine_greedy_stream_lstm_push_workspace_bytes(int n_streams, int S, int E, int Hd, int O, int L, int layer_norm, int H, int V,
+                                                        int has_text, int scan_frames, size_t *out);
+int rnnt_engine_greedy_stream_lstm_push(const void *frames, int64_t frame_stride, int rows, const int32_t *push_table, int n_streams,
+                                        int max_count, const rnnt_lstm_predictor_params *p, int S, int E, int Hd, int O, int L,
+                                        int layer_norm, float eps_in, float eps_lstm, float eps_out, const void *text_W,
+                                        const void *text_b, const void *W, const void *bias, int H, int V, int blank, int max_length,
+                                        int max_per_frame, int scan_frames, int iterations, int begin, int32_t *host_flag,
+                                        int32_t *out_tokens, int out_stride, void *block, size_t bytes, void *workspace, size_t ws_bytes,
+                                        void *stream);
+
+/*
  * The same loop (rnnt/model.py:108-125 with the ConvPredictor of rnnt/predictor.py:189-229, eval mode) for one utterance as ONE
  * persistent launch: 16 - 128 workgroups stay resident for the whole utterance and hand scan candidates, the conv2 output and the
  * predictor's output to each other through tagged 8-byte words in the workspace (rnnt_amd/csrc/decode.hip, k_dec_persist), with

@@ -502,6 +502,51 @@ LdLayout ld_layout(int n_utt, int E, int Hd, int O, int L, int H, int V, int sca
     return w;
 }
 
+// ---- the streaming form (rnnt_engine_greedy_stream_lstm_*): a stream's words are the loop's — the kernels below read them at the same
+// places, `st_ld` words from one row to the next — with "done" split in two: PAUSED (nothing to scan: the push's frames are consumed or
+// the cap is reached; the loop's DONE) and DONE (the cap alone, which outlives the push), "settled" read as AT REST, and the words a
+// stream needs beyond an utterance's
+enum {
+    LS_WORDS = RNNT_LSTM_STREAM_STATE_WORDS, LS_DONE = RNNT_LSTM_STREAM_DONE, LS_FRAMES = RNNT_LSTM_STREAM_FRAMES,
+    LS_NEWEST = RNNT_LSTM_STREAM_NEWEST, LS_PUSH_LABELS = RNNT_LSTM_STREAM_PUSH_LABELS, LS_BASE = RNNT_LSTM_STREAM_BASE
+};
+static_assert(RNNT_LSTM_STREAM_T == DEC_ST_T && RNNT_LSTM_STREAM_EMITTED == DEC_ST_EMITTED && RNNT_LSTM_STREAM_LABELS == DEC_ST_NTOK &&
+              RNNT_LSTM_STREAM_PAUSED == DEC_ST_DONE && RNNT_LSTM_STREAM_NEWTOK == DEC_ST_NEWTOK &&
+              RNNT_LSTM_STREAM_PUSH_ITERATIONS == DEC_ST_ITERS && RNNT_LSTM_STREAM_AT_REST == DEC_ST_SETTLED,
+              "a stream's words are the loop's");
+
+// the block of n streams: state words | h, c [L][2][n][Hd] | text vectors [n][H], in floats (= int32 words), each section 256-byte aligned
+struct LsBlock { size_t state, hc, text, total; };
+LsBlock ls_block(int n, int Hd, int L, int H)
+{
+    LsBlock b;
+    size_t o = 0;
+    b.state = o; o += al((size_t)n * LS_WORDS);
+    b.hc = o;    o += al((size_t)L * 2 * n * Hd);
+    b.text = o;  o += al((size_t)n * H);
+    b.total = o;
+    return b;
+}
+// a push's scratch (LdLayout without what the block holds)
+struct LsLayout { size_t x1, y, gp, part, ctrl, total; };
+LsLayout ls_layout(int n_streams, int E, int Hd, int O, int H, int V, int scan_frames)
+{
+    const size_t n = n_streams;
+    LsLayout w;
+    size_t o = 0;
+    w.x1 = o;   o += al(n * E);
+    w.y = o;    o += al(n * O);
+    w.gp = o;   o += al(ld_gp_floats(E, Hd, O, H) * n);
+    w.part = o; o += al(n * scan_frames * ((V + 31) / 32) * 2);
+    w.ctrl = o; o += 64;
+    w.total = o;
+    return w;
+}
+
+// whether the predictor has a label of this row's to take in NOW (a stream at rest keeps its start blank for the push that brings it a
+// frame; an utterance of the offline loop never has both words set)
+__device__ __forceinline__ bool ld_takes_label(const int32_t *st) { return st[DEC_ST_NEWTOK] != 0 && st[DEC_ST_SETTLED] == 0; }
+
 __global__ __launch_bounds__(256) void k_ld_init(int32_t *__restrict__ states, int32_t *__restrict__ tokens, int max_length, int blank,
                                                  int n_utt, float *__restrict__ hc, int nhc, int32_t *__restrict__ ctrl)
 {
@@ -526,38 +571,39 @@ __device__ __forceinline__ void ld_embed_row(const float *__restrict__ emb, int 
     for (int i = tid; i < E; i += 256) out[i] = (e[i] - mean) * rstd * gamma[i] + beta[i];
 }
 
-// x1[u] = LayerNorm_E(embedding[the utterance's newest token]) for the utterances that have one
-__global__ __launch_bounds__(256) void k_ld_embed(const int32_t *__restrict__ states, const int32_t *__restrict__ tokens, int max_length,
+// x1[u] = LayerNorm_E(embedding[the utterance's newest token]) for the utterances that have one; tokens NULL (a stream): the token is
+// the state's LS_NEWEST word
+__global__ __launch_bounds__(256) void k_ld_embed(const int32_t *__restrict__ states, int st_ld, const int32_t *__restrict__ tokens, int max_length,
                                                   const float *__restrict__ emb, int S, const float *__restrict__ gamma,
                                                   const float *__restrict__ beta, float eps, int E, float *__restrict__ x1)
 {
     __shared__ float red[4];
     const int u = blockIdx.x;
-    const int32_t *st = states + DEC_ST_WORDS * u;
-    if (!st[DEC_ST_NEWTOK]) return;
-    ld_embed_row(emb, S, tokens[(long)u * max_length + st[DEC_ST_NTOK]], gamma, beta, eps, E, x1 + (long)u * E, red);
+    const int32_t *st = states + st_ld * u;
+    if (!ld_takes_label(st)) return;
+    ld_embed_row(emb, S, tokens ? tokens[(long)u * max_length + st[DEC_ST_NTOK]] : st[LS_NEWEST], gamma, beta, eps, E, x1 + (long)u * E, red);
 }
 
 // whether any utterance has a label for the predictor to take in (workgroup-uniform; n_utt <= 32)
-__device__ __forceinline__ bool ld_any_new(const int32_t *states, int n_utt)
+__device__ __forceinline__ bool ld_any_new(const int32_t *states, int st_ld, int n_utt)
 {
     const int u = threadIdx.x & 63;
-    return __ballot(u < n_utt && states[DEC_ST_WORDS * u + DEC_ST_NEWTOK] != 0) != 0ull;
+    return __ballot(u < n_utt && ld_takes_label(states + st_ld * u)) != 0ull;
 }
 
 // up to two NT products of the same M = n_utt rows and N columns in one launch: grid (ceil(N/32), KS0 + KS1); the partial tiles of
 // product 0's ranges, then product 1's, at P[range][m][n] — the row kernel that follows adds them in that order
-struct LdGemm { const int32_t *states; int n_utt; RecArgs g[2]; };
+struct LdGemm { const int32_t *states; int st_ld, n_utt; RecArgs g[2]; };
 __global__ __launch_bounds__(256) void k_ld_gemm(LdGemm a)
 {
     __shared__ float red[3 * 1024];
-    if (!ld_any_new(a.states, a.n_utt)) return;
+    if (!ld_any_new(a.states, a.st_ld, a.n_utt)) return;
     const int which = (int)blockIdx.y >= a.g[0].KS ? 1 : 0;
     rec_tile<false>(a.g[which], blockIdx.x * 32, blockIdx.y - (which ? a.g[0].KS : 0), 0, red);
 }
 
 struct LdStep {
-    const int32_t *states;
+    const int32_t *states; int st_ld;
     const float *gp; int nsp; long gp_ld;  // nsp partial products [n_utt,4Hd], gp_ld apart
     const float *xb;                       // x2g bias (no layer norm) or NULL
     const float *gw, *gb, *cw, *cb; float eps;
@@ -654,7 +700,7 @@ __global__ __launch_bounds__(256) void k_ld_step(LdStep a)
 {
     __shared__ float red[4];
     const int b = blockIdx.x, Hd = a.Hd;
-    if (!a.states[DEC_ST_WORDS * b + DEC_ST_NEWTOK]) return;
+    if (!ld_takes_label(a.states + a.st_ld * b)) return;
     float *h = a.h + (long)b * Hd, *c = a.c + (long)b * Hd;
     ld_step_row<LN>(a, a.gp + (long)b * 4 * Hd, c, h, c, a.h_out ? a.h_out + (long)b * Hd : nullptr,
                     a.h_out ? a.c_out + (long)b * Hd : nullptr, red);
@@ -682,13 +728,13 @@ __device__ __forceinline__ void ld_rowfin_row(const float *__restrict__ gp, int 
 
 // out[u] = that row — for the utterances with a new label
 template <bool LN>
-__global__ __launch_bounds__(256) void k_ld_rowfin(const int32_t *__restrict__ states, const float *__restrict__ gp, int nsp, long gp_ld, int N,
+__global__ __launch_bounds__(256) void k_ld_rowfin(const int32_t *__restrict__ states, int st_ld, const float *__restrict__ gp, int nsp, long gp_ld, int N,
                                                    const float *__restrict__ bias, const float *__restrict__ gamma,
                                                    const float *__restrict__ beta, float eps, float *__restrict__ out)
 {
     __shared__ float red[4];
     const int u = blockIdx.x;
-    if (!states[DEC_ST_WORDS * u + DEC_ST_NEWTOK]) return;
+    if (!ld_takes_label(states + st_ld * u)) return;
     ld_rowfin_row<LN>(gp + (long)u * N, nsp, gp_ld, N, bias, gamma, beta, eps, out + (long)u * N, red);
 }
 
@@ -701,14 +747,14 @@ __device__ __forceinline__ void ld_utt(const int32_t *utt, int u, int rows, int 
 
 // decode.hip's k_dec_scan_logits<false> with the utterance as grid dimension z: scan_frames frames from the utterance's own t against
 // its own text vector (the scan tile of decode_kernels.hpp), one (max, first index) candidate per frame and 32 vocabulary entries
-__global__ __launch_bounds__(256) void k_ld_scan(const int32_t *__restrict__ states, const float *__restrict__ enc, long enc_st,
+__global__ __launch_bounds__(256) void k_ld_scan(const int32_t *__restrict__ states, int st_ld, const float *__restrict__ enc, long enc_st,
                                                  const int32_t *__restrict__ utt, int rows, const float *__restrict__ text,
                                                  const float *__restrict__ W, const float *__restrict__ bias, float2 *__restrict__ part, int K,
                                                  int H, int V)
 {
     __shared__ float s_acc[3][16][64];
     const int u = blockIdx.z;
-    const int32_t *state = states + DEC_ST_WORDS * u;
+    const int32_t *state = states + st_ld * u;
     if (state[DEC_ST_DONE]) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31, half = lane >> 5;
@@ -729,42 +775,100 @@ __global__ __launch_bounds__(256) void k_ld_scan(const int32_t *__restrict__ sta
 // k_dec_update's rules per utterance (one workgroup each).  An utterance that ended on a label keeps newtok for one more iteration —
 // the predictor takes the label in, so that state_out and the text vector are those AFTER the last label — and settles in the next;
 // ctrl[0] counts the settled utterances, the last one raises the host's flag.
-__global__ __launch_bounds__(128) void k_ld_update(const float2 *__restrict__ part, int K, int NB, int blank, const int32_t *__restrict__ utt,
-                                                   int rows, int max_length, int max_per_frame, int n_utt, int32_t *__restrict__ states,
-                                                   int32_t *__restrict__ tokens, int32_t *__restrict__ ctrl, int32_t *host_flag)
+//
+// STREAM (rnnt_engine_greedy_stream_lstm_push): the same rules with the push as the utterance — T its frame count, t relative to it, the
+// row's "done" word PAUSED, "settled" AT REST — and what a stream adds: a label goes to the push's out_tokens row and into the state's
+// NEWEST word (there is no tokens[max_length] row to index: max_length 0 is unbounded), the frames are counted over all pushes, and the
+// cap is kept in a word of its own, which outlives the push.
+struct LdUpdate {
+    const float2 *part; int K, NB, blank; const int32_t *utt; int rows, max_length, max_per_frame, n_utt;
+    int32_t *states;
+    int32_t *tokens; int tok_ld;  // [n_utt][max_length] with the leading blank; a stream: the push's out_tokens [n_streams][tok_ld]
+    int32_t *ctrl, *host_flag;
+};
+template <bool STREAM>
+__global__ __launch_bounds__(128) void k_ld_update(LdUpdate a)
 {
     __shared__ int s_tok[128];
-    const int u = blockIdx.x;
-    int32_t *state = states + DEC_ST_WORDS * u;
+    const int u = blockIdx.x, K = a.K;
+    int32_t *state = a.states + (STREAM ? (int)LS_WORDS : (int)DEC_ST_WORDS) * u;
     if (state[DEC_ST_SETTLED]) return;
     const bool was_done = state[DEC_ST_DONE] != 0;
-    if (!was_done && (int)threadIdx.x < K) s_tok[threadIdx.x] = cand_argmax(part + ((long)u * K + threadIdx.x) * NB, NB);
+    if (!was_done && (int)threadIdx.x < K) s_tok[threadIdx.x] = cand_argmax(a.part + ((long)u * K + threadIdx.x) * a.NB, a.NB);
     __syncthreads();
     if (threadIdx.x != 0) return;
     int done = 1, newtok = 0;
     if (!was_done) {
         int first, T;
-        ld_utt(utt, u, rows, first, T);
+        ld_utt(a.utt, u, a.rows, first, T);
         const int t = state[DEC_ST_T], n = min(K, T - t);
-        const int hit = dec_first_hit(s_tok, n, blank);
-        const DecPos p = dec_advance(t, state[DEC_ST_EMITTED], state[DEC_ST_NTOK], hit, n, T, max_length, max_per_frame,
-                                     [&](int at) { tokens[(long)u * max_length + at] = s_tok[hit]; });
+        const int hit = dec_first_hit(s_tok, n, a.blank);
+        const int maxlen = STREAM && a.max_length == 0 ? 0x7fffffff : a.max_length;
+        const DecPos p = dec_advance(t, state[DEC_ST_EMITTED], state[DEC_ST_NTOK], hit, n, T, maxlen, a.max_per_frame, [&](int at) {
+            if (STREAM) {  // (held inside the row whatever the caller's table says)
+                a.tokens[(long)u * a.tok_ld + min(state[LS_PUSH_LABELS], a.tok_ld - 1)] = s_tok[hit];
+                state[LS_PUSH_LABELS] += 1;
+                state[LS_NEWEST] = s_tok[hit];
+            } else
+                a.tokens[(long)u * a.tok_ld + at] = s_tok[hit];
+        });
         state[DEC_ST_T] = p.t; state[DEC_ST_EMITTED] = p.emitted; state[DEC_ST_NTOK] = p.ntok; state[DEC_ST_DONE] = p.done;
+        if (STREAM) {
+            state[LS_FRAMES] = state[LS_BASE] + p.t;
+            state[LS_DONE] = p.ntok + 1 >= maxlen ? 1 : 0;
+        }
         done = p.done; newtok = p.newtok;
         state[DEC_ST_ITERS] += 1;
     }
     state[DEC_ST_NEWTOK] = newtok;
     if (done && !newtok) {
         state[DEC_ST_SETTLED] = 1;
-        if (atomicAdd(ctrl, 1) + 1 == n_utt && host_flag) __hip_atomic_store(host_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (atomicAdd(a.ctrl, 1) + 1 == a.n_utt && a.host_flag) __hip_atomic_store(a.host_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
+// all streams (index < 0) or stream `index` alone start a new utterance: grid (ceil(max(2 L Hd, H, LS_WORDS) / 256), streams started).
+// Nothing of another stream's is written.
+__global__ __launch_bounds__(256) void k_ls_init(int32_t *__restrict__ states, float *__restrict__ hc, float *__restrict__ text, int n, int Hd,
+                                                 int L, int H, int blank, int index)
+{
+    const int u = index < 0 ? (int)blockIdx.y : index, i = blockIdx.x * 256 + threadIdx.x;
+    if (i < 2 * L * Hd) hc[((long)(i / Hd) * n + u) * Hd + i % Hd] = 0.f;
+    if (i < H) text[(long)u * H + i] = 0.f;
+    if (i < LS_WORDS)  // zero frames: at rest, the start blank waiting for the push that brings a frame
+        states[LS_WORDS * u + i] = i == DEC_ST_NEWTOK || i == DEC_ST_DONE || i == DEC_ST_SETTLED ? 1 : i == LS_NEWEST ? blank : 0;
+}
+
+// a push begins (one workgroup of 64, a lane per stream): a stream that got frames and is not done leaves its rest — base latched, the
+// per-push words cleared —, the others stay as they are, bit for bit, and are counted as at rest already
+__global__ __launch_bounds__(64) void k_ls_begin(int32_t *__restrict__ states, const int32_t *__restrict__ table, int n,
+                                                 int32_t *__restrict__ ctrl, int32_t *host_flag)
+{
+    const int u = threadIdx.x;
+    bool rests = false;
+    if (u < n) {
+        int32_t *st = states + LS_WORDS * u;
+        rests = table[2 * u + 1] <= 0 || st[LS_DONE] != 0;
+        if (!rests) {
+            st[LS_BASE] = st[LS_FRAMES];
+            st[DEC_ST_T] = 0; st[DEC_ST_DONE] = 0; st[DEC_ST_SETTLED] = 0; st[DEC_ST_ITERS] = 0; st[LS_PUSH_LABELS] = 0;
+        }
+    }
+    const int at_rest = __popcll(__ballot(rests));
+    if (u == 0) {
+        ctrl[0] = at_rest;
+        if (at_rest == n && host_flag) __hip_atomic_store(host_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// where a loop's buffers are: the offline loop keeps all of them in its workspace, a stream its states, hc and text in its block
 struct LdArgs {
     const float *frames; long frame_stride; int rows; const int32_t *utt; int n_utt;
     rnnt_lstm_predictor_params p; int S, E, Hd, O, L, ln; float eps_in, eps_lstm, eps_out;
     const float *text_W, *text_b, *W, *bias; int H, V, blank, max_length, max_per_frame, scan_frames, iterations, init;
-    int32_t *host_flag, *state, *tokens; float *state_out; float *ws;
+    int32_t *host_flag, *state, *tokens; float *state_out;
+    float *text, *x1, *hc, *y, *gp; float2 *part; int32_t *ctrl;
+    int stream = 0, tok_ld = 0;  // a stream's push: `init` = begin, `tokens` = out_tokens [n_utt][tok_ld], `utt` = the push table
 };
 
 RecArgs ld_prod(const float *A, const float *W, float *P, int M, int N, int K)
@@ -775,29 +879,32 @@ RecArgs ld_prod(const float *A, const float *W, float *P, int M, int N, int K)
 void launch_ld_loop(const LdArgs &a, hipStream_t st)
 {
     const int n = a.n_utt, E = a.E, Hd = a.Hd, O = a.O, L = a.L, H = a.H, V = a.V, K = a.scan_frames, NB = (V + 31) / 32;
-    const LdLayout w = ld_layout(n, E, Hd, O, L, H, V, K);
-    float *text = a.ws + w.text, *x1 = a.ws + w.x1, *hc = a.ws + w.hc, *y = a.ws + w.y, *gp = a.ws + w.gp;
-    float2 *part = (float2 *)(a.ws + w.part);
-    int32_t *ctrl = (int32_t *)(a.ws + w.ctrl);
+    float *text = a.text, *x1 = a.x1, *hc = a.hc, *y = a.y, *gp = a.gp;
+    float2 *part = a.part;
+    int32_t *ctrl = a.ctrl;
     const long nH = (long)n * Hd;
-    if (a.init) {
+    const int st_ld = a.stream ? (int)LS_WORDS : (int)DEC_ST_WORDS;
+    if (a.init && a.stream) hipLaunchKernelGGL(k_ls_begin, dim3(1), dim3(64), 0, st, a.state, a.utt, n, ctrl, a.host_flag);
+    else if (a.init) {
         const int nhc = (int)(2 * L * nH);
         hipLaunchKernelGGL(k_ld_init, dim3((nhc + 255) / 256), dim3(256), 0, st, a.state, a.tokens, a.max_length, a.blank, n, hc, nhc, ctrl);
     }
+    LdUpdate up{part, K, NB, a.blank, a.utt, a.rows, a.max_length, a.max_per_frame, n, a.state, a.tokens, a.stream ? a.tok_ld : a.max_length,
+                ctrl, a.host_flag};
     for (int it = 0; it < a.iterations; ++it) {
-        hipLaunchKernelGGL(k_ld_embed, dim3(n), dim3(256), 0, st, a.state, a.tokens, a.max_length, a.p.embedding, a.S, a.p.ln_in_w,
+        hipLaunchKernelGGL(k_ld_embed, dim3(n), dim3(256), 0, st, a.state, st_ld, a.stream ? (const int32_t *)nullptr : a.tokens, a.max_length, a.p.embedding, a.S, a.p.ln_in_w,
                            a.p.ln_in_b, a.eps_in, E, x1);
         for (int l = 0; l < L; ++l) {
             const rnnt_lstm_layer_params &q = a.p.layers[l];
             float *h = hc + (long)(2 * l) * nH, *c = h + nH;
             const int in = l ? Hd : E;
             LdGemm g;
-            g.states = a.state; g.n_utt = n;
+            g.states = a.state; g.st_ld = st_ld; g.n_utt = n;
             g.g[0] = ld_prod(l ? h - 2 * nH : x1, q.x2g_w, gp, n, 4 * Hd, in);  // the layer below's NEW h (its row kernel has run)
             g.g[1] = ld_prod(h, q.p2g_w, gp + (long)g.g[0].KS * n * 4 * Hd, n, 4 * Hd, Hd);  // this layer's h of the step before
             hipLaunchKernelGGL(k_ld_gemm, dim3((4 * Hd + 31) / 32, g.g[0].KS + g.g[1].KS), dim3(256), 0, st, g);
             LdStep s;
-            s.states = a.state; s.gp = gp; s.nsp = g.g[0].KS + g.g[1].KS; s.gp_ld = 4 * nH;
+            s.states = a.state; s.st_ld = st_ld; s.gp = gp; s.nsp = g.g[0].KS + g.g[1].KS; s.gp_ld = 4 * nH;
             s.xb = a.ln ? nullptr : q.x2g_b;
             s.gw = q.g_norm_w; s.gb = q.g_norm_b; s.cw = q.c_norm_w; s.cb = q.c_norm_b; s.eps = a.eps_lstm;
             s.h = h; s.c = c;
@@ -807,24 +914,24 @@ void launch_ld_loop(const LdArgs &a, hipStream_t st)
             else hipLaunchKernelGGL(k_ld_step<false>, dim3(n), dim3(256), 0, st, s);
         }
         LdGemm g;
-        g.states = a.state; g.n_utt = n;
+        g.states = a.state; g.st_ld = st_ld; g.n_utt = n;
         g.g[0] = ld_prod(hc + (long)(2 * (L - 1)) * nH, a.p.linear_w, gp, n, O, Hd);
         g.g[1] = g.g[0]; g.g[1].KS = 0;
         hipLaunchKernelGGL(k_ld_gemm, dim3((O + 31) / 32, g.g[0].KS), dim3(256), 0, st, g);
         // without joint.text_ln the output LayerNorm's row IS the text vector (O == H)
-        hipLaunchKernelGGL(k_ld_rowfin<true>, dim3(n), dim3(256), 0, st, a.state, gp, g.g[0].KS, (long)n * O, O, a.p.linear_b, a.p.ln_out_w,
+        hipLaunchKernelGGL(k_ld_rowfin<true>, dim3(n), dim3(256), 0, st, a.state, st_ld, gp, g.g[0].KS, (long)n * O, O, a.p.linear_b, a.p.ln_out_w,
                            a.p.ln_out_b, a.eps_out, a.text_W ? y : text);
         if (a.text_W) {
             g.g[0] = ld_prod(y, a.text_W, gp, n, H, O);
             g.g[1] = g.g[0]; g.g[1].KS = 0;
             hipLaunchKernelGGL(k_ld_gemm, dim3((H + 31) / 32, g.g[0].KS), dim3(256), 0, st, g);
-            hipLaunchKernelGGL(k_ld_rowfin<false>, dim3(n), dim3(256), 0, st, a.state, gp, g.g[0].KS, (long)n * H, H, a.text_b,
+            hipLaunchKernelGGL(k_ld_rowfin<false>, dim3(n), dim3(256), 0, st, a.state, st_ld, gp, g.g[0].KS, (long)n * H, H, a.text_b,
                                (const float *)nullptr, (const float *)nullptr, 0.f, text);
         }
-        hipLaunchKernelGGL(k_ld_scan, dim3(NB, (K + 31) / 32, n), dim3(256), 0, st, a.state, a.frames, a.frame_stride, a.utt, a.rows, text, a.W,
+        hipLaunchKernelGGL(k_ld_scan, dim3(NB, (K + 31) / 32, n), dim3(256), 0, st, a.state, st_ld, a.frames, a.frame_stride, a.utt, a.rows, text, a.W,
                            a.bias, part, K, H, V);
-        hipLaunchKernelGGL(k_ld_update, dim3(n), dim3(128), 0, st, part, K, NB, a.blank, a.utt, a.rows, a.max_length, a.max_per_frame, n, a.state,
-                           a.tokens, ctrl, a.host_flag);
+        if (a.stream) hipLaunchKernelGGL(k_ld_update<true>, dim3(n), dim3(128), 0, st, up);
+        else hipLaunchKernelGGL(k_ld_update<false>, dim3(n), dim3(128), 0, st, up);
     }
 }
 
@@ -951,7 +1058,7 @@ void launch_beam_lstm_step(const BeamLstmStep &a, hipStream_t st)
         g.g[1] = pooled(2 * l, a.par, q.p2g_w, gp + (long)g.g[0].KS * M * 4 * Hd, 4 * Hd);
         hipLaunchKernelGGL(k_bl_gemm, dim3((4 * Hd + 31) / 32, g.g[0].KS + g.g[1].KS, tiles_z.x), dim3(256), 0, st, g);
         LdStep s;
-        s.states = nullptr; s.gp = gp; s.nsp = g.g[0].KS + g.g[1].KS; s.gp_ld = (long)M * 4 * Hd;
+        s.states = nullptr; s.st_ld = 0; s.gp = gp; s.nsp = g.g[0].KS + g.g[1].KS; s.gp_ld = (long)M * 4 * Hd;
         s.xb = a.ln ? nullptr : q.x2g_b;
         s.gw = q.g_norm_w; s.gb = q.g_norm_b; s.cw = q.c_norm_w; s.cb = q.c_norm_b; s.eps = a.eps_lstm;
         s.h = s.c = s.h_out = s.c_out = nullptr;
@@ -1165,6 +1272,31 @@ int rnnt_engine_lstm_predictor_bwd(const int64_t *ids, int B, int U1, int S, int
     return status("rnnt_engine_lstm_predictor_bwd");
 }
 
+// the device's address of a caller's pinned flag word (an ordinary host pointer is refused, never written through); NULL stays NULL
+static int ld_host_flag(int32_t *host_flag, int32_t **dev)
+{
+    *dev = nullptr;
+    if (!host_flag) return RNNT_OK;
+    void *dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, host_flag, 0) != hipSuccess || !dp) {
+        (void)hipGetLastError();
+        return engine_fail(RNNT_ERR_INVALID_ARG, "host_flag is not mapped pinned host memory (hipHostMalloc / torch pin_memory)");
+    }
+    *dev = (int32_t *)dp;
+    return RNNT_OK;
+}
+
+// the model's part of a greedy loop's arguments (checked by the caller)
+static void ld_model(LdArgs &a, const rnnt_lstm_predictor_params *p, int S, int E, int Hd, int O, int L, int layer_norm, float eps_in,
+                     float eps_lstm, float eps_out, const void *text_W, const void *text_b, const void *W, const void *bias, int H, int V,
+                     int blank, int max_length, int max_per_frame, int scan_frames)
+{
+    a.p = *p; a.S = S; a.E = E; a.Hd = Hd; a.O = O; a.L = L; a.ln = layer_norm != 0;
+    a.eps_in = eps_in; a.eps_lstm = eps_lstm; a.eps_out = eps_out;
+    a.text_W = (const float *)text_W; a.text_b = (const float *)text_b; a.W = (const float *)W; a.bias = (const float *)bias;
+    a.H = H; a.V = V; a.blank = blank; a.max_length = max_length; a.max_per_frame = max_per_frame; a.scan_frames = scan_frames;
+}
+
 int rnnt_engine_greedy_decode_lstm_workspace_bytes(int n_utt, int S, int E, int Hd, int O, int L, int layer_norm, int H, int V, int has_text,
                                                    int scan_frames, size_t *out)
 {
@@ -1197,27 +1329,110 @@ int rnnt_engine_greedy_decode_lstm(const void *frames, int64_t frame_stride, int
                            max_per_frame, max_frames, rows, (long long)frame_stride);
     if (blank < 0 || blank >= V) return engine_fail(RNNT_ERR_INVALID_ARG, "blank=%d outside [0,%d)", blank, V);
     if ((long)n_utt * max_length > 0x7fffffffL) return engine_fail(RNNT_ERR_UNSUPPORTED, "n_utt * max_length must stay below 2^31");
-    int32_t *flag_dev = nullptr;
-    if (host_flag) {  // the device's address of the caller's pinned word (an ordinary host pointer is refused, never written through)
-        void *dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, host_flag, 0) != hipSuccess || !dp) {
-            (void)hipGetLastError();
-            return engine_fail(RNNT_ERR_INVALID_ARG, "host_flag is not mapped pinned host memory (hipHostMalloc / torch pin_memory)");
-        }
-        flag_dev = (int32_t *)dp;
-    }
+    int32_t *flag_dev;
+    if (int rc = ld_host_flag(host_flag, &flag_dev)) return rc;
     if (ws_bytes < need) return engine_fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
     LdArgs a;
     a.frames = (const float *)frames; a.frame_stride = (long)frame_stride; a.rows = rows; a.utt = utt; a.n_utt = n_utt;
-    a.p = *p; a.S = S; a.E = E; a.Hd = Hd; a.O = O; a.L = L; a.ln = layer_norm != 0;
-    a.eps_in = eps_in; a.eps_lstm = eps_lstm; a.eps_out = eps_out;
-    a.text_W = (const float *)text_W; a.text_b = (const float *)text_b; a.W = (const float *)W; a.bias = (const float *)bias;
-    a.H = H; a.V = V; a.blank = blank; a.max_length = max_length; a.max_per_frame = max_per_frame; a.scan_frames = scan_frames;
+    ld_model(a, p, S, E, Hd, O, L, layer_norm, eps_in, eps_lstm, eps_out, text_W, text_b, W, bias, H, V, blank, max_length, max_per_frame,
+             scan_frames);
     a.iterations = iterations ? iterations : max_length + (max_frames + scan_frames - 1) / scan_frames + 1;
     a.init = init;
-    a.host_flag = flag_dev; a.state = state; a.tokens = tokens; a.state_out = state_out; a.ws = (float *)workspace;
+    a.host_flag = flag_dev; a.state = state; a.tokens = tokens; a.state_out = state_out;
+    const LdLayout w = ld_layout(n_utt, E, Hd, O, L, H, V, scan_frames);
+    float *ws = (float *)workspace;
+    a.text = ws + w.text; a.x1 = ws + w.x1; a.hc = ws + w.hc; a.y = ws + w.y; a.gp = ws + w.gp;
+    a.part = (float2 *)(ws + w.part); a.ctrl = (int32_t *)(ws + w.ctrl);
     launch_ld_loop(a, (hipStream_t)stream);
     return status("rnnt_engine_greedy_decode_lstm");
+}
+
+int rnnt_engine_greedy_stream_lstm_bytes(int n_streams, int S, int E, int Hd, int O, int L, int layer_norm, int H, int V, int has_text,
+                                         size_t *out)
+{
+    if (!out) return engine_fail(RNNT_ERR_INVALID_ARG, "null size pointer");
+    if (int rc = ld_check_sizes(n_streams, S, E, Hd, O, L, layer_norm != 0, H, V, has_text, 1)) return rc;
+    *out = ls_block(n_streams, Hd, L, H).total * 4;
+    return RNNT_OK;
+}
+
+int rnnt_engine_greedy_stream_lstm_init(int n_streams, int Hd, int L, int H, int blank, int index, void *block, size_t bytes, void *stream)
+{
+    if (n_streams < 1 || Hd < 1 || L < 1 || H < 1 || blank < 0)
+        return engine_fail(RNNT_ERR_INVALID_ARG, "n_streams=%d Hd=%d L=%d H=%d blank=%d", n_streams, Hd, L, H, blank);
+    if (n_streams > 32 || Hd > 1024 || L > 8)
+        return engine_fail(RNNT_ERR_UNSUPPORTED, "the LSTM stream takes n_streams <= 32, Hd <= 1024, L <= 8 (n_streams=%d Hd=%d L=%d)", n_streams, Hd, L);
+    if (index < -1 || index >= n_streams) return engine_fail(RNNT_ERR_INVALID_ARG, "index=%d outside [-1,%d)", index, n_streams);
+    if (!block || ((uintptr_t)block & 255)) return engine_fail(RNNT_ERR_INVALID_ARG, "the block must be non-null and 256-byte aligned");
+    const LsBlock b = ls_block(n_streams, Hd, L, H);
+    if (bytes < b.total * 4) return engine_fail(RNNT_ERR_WORKSPACE, "block %zu < required %zu bytes", bytes, b.total * 4);
+    float *f = (float *)block;
+    const int widest = std::max(std::max(2 * L * Hd, H), (int)LS_WORDS);
+    hipLaunchKernelGGL(k_ls_init, dim3((widest + 255) / 256, index < 0 ? n_streams : 1), dim3(256), 0, (hipStream_t)stream,
+                       (int32_t *)(f + b.state), f + b.hc, f + b.text, n_streams, Hd, L, H, blank, index);
+    return status("rnnt_engine_greedy_stream_lstm_init");
+}
+
+int rnnt_engine_greedy_stream_lstm_push_workspace_bytes(int n_streams, int S, int E, int Hd, int O, int L, int layer_norm, int H, int V,
+                                                        int has_text, int scan_frames, size_t *out)
+{
+    if (!out) return engine_fail(RNNT_ERR_INVALID_ARG, "null size pointer");
+    if (int rc = ld_check_sizes(n_streams, S, E, Hd, O, L, layer_norm != 0, H, V, has_text, scan_frames)) return rc;
+    *out = (ls_layout(n_streams, E, Hd, O, H, V, scan_frames).total * 4 + 255) & ~(size_t)255;
+    return RNNT_OK;
+}
+
+int rnnt_engine_greedy_stream_lstm_push(const void *frames, int64_t frame_stride, int rows, const int32_t *push_table, int n_streams,
+                                        int max_count, const rnnt_lstm_predictor_params *p, int S, int E, int Hd, int O, int L,
+                                        int layer_norm, float eps_in, float eps_lstm, float eps_out, const void *text_W,
+                                        const void *text_b, const void *W, const void *bias, int H, int V, int blank, int max_length,
+                                        int max_per_frame, int scan_frames, int iterations, int begin, int32_t *host_flag,
+                                        int32_t *out_tokens, int out_stride, void *block, size_t bytes, void *workspace, size_t ws_bytes,
+                                        void *stream)
+{
+    size_t need, need_block;
+    if (int rc = rnnt_engine_greedy_stream_lstm_push_workspace_bytes(n_streams, S, E, Hd, O, L, layer_norm, H, V, text_W ? 1 : 0, scan_frames,
+                                                                     &need))
+        return rc;
+    if (int rc = rnnt_engine_greedy_stream_lstm_bytes(n_streams, S, E, Hd, O, L, layer_norm, H, V, text_W ? 1 : 0, &need_block)) return rc;
+    if (iterations < 0) return engine_fail(RNNT_ERR_INVALID_ARG, "iterations=%d", iterations);
+    if (bad(frames) || bad(W) || bad(bias) || !push_table || !out_tokens || !block || !workspace)
+        return engine_fail(RNNT_ERR_INVALID_ARG, "null or not 16-byte aligned pointer argument");
+    if (((uintptr_t)push_table & 7) || ((uintptr_t)out_tokens & 3) || ((uintptr_t)workspace & 255) || ((uintptr_t)block & 255))
+        return engine_fail(RNNT_ERR_INVALID_ARG, "push_table must be 8-byte, out_tokens 4-byte, the workspace and the block 256-byte aligned");
+    if (int rc = check_params(p, L, layer_norm != 0, "parameter")) return rc;
+    if ((text_W == nullptr) != (text_b == nullptr) || (text_W && (bad(text_W) || bad(text_b))))
+        return engine_fail(RNNT_ERR_INVALID_ARG, "text_W / text_b: both or neither, 16-byte aligned");
+    if ((max_length != 0 && max_length < 2) || max_per_frame < 1 || max_count < 0 || rows < 1 || rows < max_count || frame_stride < H ||
+        frame_stride % 4)
+        return engine_fail(RNNT_ERR_INVALID_ARG, "max_length=%d (0 or >= 2) max_per_frame=%d max_count=%d rows=%d frame_stride=%lld", max_length,
+                           max_per_frame, max_count, rows, (long long)frame_stride);
+    if (blank < 0 || blank >= V) return engine_fail(RNNT_ERR_INVALID_ARG, "blank=%d outside [0,%d)", blank, V);
+    const long most = (long)max_count * max_per_frame;  // labels a stream can emit in this push
+    if (out_stride < 1 || out_stride < most)
+        return engine_fail(RNNT_ERR_INVALID_ARG, "out_stride=%d below max_count * max_per_frame = %ld (and 1)", out_stride, most);
+    const long bound = most + (max_count + scan_frames - 1) / scan_frames + 1;
+    if (bound > 0x7fffffffL || (long)n_streams * out_stride > 0x7fffffffL)
+        return engine_fail(RNNT_ERR_UNSUPPORTED, "max_count * max_per_frame and n_streams * out_stride must stay below 2^31");
+    int32_t *flag_dev;
+    if (int rc = ld_host_flag(host_flag, &flag_dev)) return rc;
+    if (ws_bytes < need) return engine_fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
+    if (bytes < need_block) return engine_fail(RNNT_ERR_WORKSPACE, "block %zu < required %zu bytes", bytes, need_block);
+    LdArgs a;
+    a.frames = (const float *)frames; a.frame_stride = (long)frame_stride; a.rows = rows; a.utt = push_table; a.n_utt = n_streams;
+    ld_model(a, p, S, E, Hd, O, L, layer_norm, eps_in, eps_lstm, eps_out, text_W, text_b, W, bias, H, V, blank, max_length, max_per_frame,
+             scan_frames);
+    a.iterations = iterations ? iterations : (int)bound;
+    a.init = begin;
+    a.stream = 1; a.tokens = out_tokens; a.tok_ld = out_stride;
+    a.host_flag = flag_dev; a.state_out = nullptr;
+    const LsBlock b = ls_block(n_streams, Hd, L, H);
+    const LsLayout w = ls_layout(n_streams, E, Hd, O, H, V, scan_frames);
+    float *bl = (float *)block, *ws = (float *)workspace;
+    a.state = (int32_t *)(bl + b.state); a.hc = bl + b.hc; a.text = bl + b.text;
+    a.x1 = ws + w.x1; a.y = ws + w.y; a.gp = ws + w.gp; a.part = (float2 *)(ws + w.part); a.ctrl = (int32_t *)(ws + w.ctrl);
+    launch_ld_loop(a, (hipStream_t)stream);
+    return status("rnnt_engine_greedy_stream_lstm_push");
 }
 
 int rnnt_engine_beam_decode_lstm_workspace_bytes(int n_utt, int S, int E, int Hd, int O, int L, int layer_norm, int H, int V, int has_text,

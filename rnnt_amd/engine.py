@@ -80,6 +80,10 @@ SIGNATURES = {
     "rnnt_engine_greedy_decode": "pqipiiiffppppiiiiiiiippppzp",
     "rnnt_engine_greedy_decode_lstm_workspace_bytes": "iiiiiiiiiiip",
     "rnnt_engine_greedy_decode_lstm": "pqipiipiiiiiifffppppiiiiiiiipppppzp",
+    "rnnt_engine_greedy_stream_lstm_bytes": "iiiiiiiiiip",
+    "rnnt_engine_greedy_stream_lstm_init": "iiiiiipzp",
+    "rnnt_engine_greedy_stream_lstm_push_workspace_bytes": "iiiiiiiiiiip",
+    "rnnt_engine_greedy_stream_lstm_push": "pqipiipiiiiiifffppppiiiiiiiippipzpzp",
     "rnnt_engine_greedy_decode_persistent_workspace_bytes": "iiiiiiip",
     "rnnt_engine_greedy_decode_persistent": "pqipiiiffppppiiiiipppppzp",
     "rnnt_engine_greedy_decode_tables_bytes": "iiiiip",
@@ -180,6 +184,8 @@ EXPORTS = (
     "rnnt_engine_lstm_predictor_fwd", "rnnt_engine_lstm_predictor_bwd",
     "rnnt_engine_greedy_decode_lstm_workspace_bytes", "rnnt_engine_greedy_decode_lstm",
     "rnnt_engine_beam_decode_lstm_workspace_bytes", "rnnt_engine_beam_decode_lstm",
+    "rnnt_engine_greedy_stream_lstm_bytes", "rnnt_engine_greedy_stream_lstm_init",
+    "rnnt_engine_greedy_stream_lstm_push_workspace_bytes", "rnnt_engine_greedy_stream_lstm_push",
 )
 
 # per-call kernel variants (include/rnnt_engine.h RNNT_VARIANT_*): bit-identical results
@@ -1033,6 +1039,108 @@ def greedy_decode_lstm(frames_list, lstm_params, text_W, text_b, W, bias, blank,
         state._keepalive = (flag, utt, packed, params, joint, arr)  # until the caller has synchronised
         text = ws[:N * H * 4].view(torch.float32).view(N, H)
     return state, tokens, state_out, text
+
+
+# ---- streaming greedy decode with the LSTMPredictor, 1 .. 32 streams in lockstep (include/rnnt_engine.h RNNT_LSTM_STREAM_*; DESIGN.md §4p
+# "Device stream")
+LSTM_STREAM_MAX = 32  # rnnt_engine_greedy_stream_lstm_*: 1 <= n_streams <= 32
+LSTM_STREAM_STATE_WORDS = 16
+(LSTM_STREAM_T, LSTM_STREAM_EMITTED, LSTM_STREAM_LABELS, LSTM_STREAM_PAUSED, LSTM_STREAM_NEWTOK, LSTM_STREAM_PUSH_ITERATIONS,
+ LSTM_STREAM_AT_REST, LSTM_STREAM_DONE, LSTM_STREAM_FRAMES, LSTM_STREAM_NEWEST, LSTM_STREAM_PUSH_LABELS, LSTM_STREAM_BASE) = range(12)
+
+
+def greedy_stream_lstm_bytes(n_streams, S, E, Hd, O, L, layer_norm, H, V, has_text):
+    """Bytes of the persistent block of `n_streams` LSTM greedy streams (C ABI rnnt_engine_greedy_stream_lstm_bytes; no device work)."""
+    n = ctypes.c_size_t(0)
+    _check(lib().rnnt_engine_greedy_stream_lstm_bytes(int(n_streams), int(S), int(E), int(Hd), int(O), int(L), int(bool(layer_norm)), int(H),
+                                                      int(V), int(bool(has_text)), ctypes.byref(n)))
+    return n.value
+
+
+def greedy_stream_lstm_supported(n_streams, S, E, Hd, O, L, layer_norm, H, V, has_text, scan_frames=32):
+    """Whether rnnt_engine_greedy_stream_lstm_push takes these sizes (no device work)."""
+    return _supported("rnnt_engine_greedy_stream_lstm_push_workspace_bytes", n_streams, S, E, Hd, O, L, bool(layer_norm), H, V, bool(has_text),
+                      scan_frames)
+
+
+def greedy_stream_lstm_views(block, n_streams, L, Hd, H):
+    """The three sections of a group's block (uint8, as greedy_stream_lstm_bytes sized it) as views: state int32[n, 16], the LSTM state
+    float32[L, 2, n, Hd] and the text vectors float32[n, H] — each section a multiple of 256 bytes."""
+    n = int(n_streams)
+    cuts, at = [], 0
+    for nbytes in (4 * n * LSTM_STREAM_STATE_WORDS, 4 * L * 2 * n * Hd, 4 * n * H):
+        cuts.append((at, at + nbytes))
+        at += (nbytes + 255) & ~255
+    (a0, a1), (b0, b1), (c0, c1) = cuts
+    return (block[a0:a1].view(torch.int32).view(n, LSTM_STREAM_STATE_WORDS), block[b0:b1].view(torch.float32).view(L, 2, n, Hd),
+            block[c0:c1].view(torch.float32).view(n, H))
+
+
+def greedy_stream_lstm_init(block, n_streams, L, Hd, H, blank, index=None):
+    """Start every stream of a group (index None) or stream `index` alone (C ABI rnnt_engine_greedy_stream_lstm_init): `block`
+    uint8[greedy_stream_lstm_bytes(...)] on the device.  Enqueued on the current stream, no synchronisation."""
+    dev = _require_cuda(block)
+    _require_dtype(torch.uint8, block=block)
+    _require_contiguous(block=block)
+    with torch.cuda.device(dev):
+        _check(lib().rnnt_engine_greedy_stream_lstm_init(int(n_streams), int(Hd), int(L), int(H), int(blank), -1 if index is None else int(index),
+                                                         _p(block), ctypes.c_size_t(block.numel()), _stream(dev)))
+
+
+def greedy_stream_lstm_push(frames_list, lstm_params, text_W, text_b, W, bias, blank, max_length, max_per_frame, scan_frames, block,
+                            out_tokens, chunk=8, in_flight=2):
+    """Enqueue one push of a group of LSTM greedy streams (C ABI rnnt_engine_greedy_stream_lstm_push; DESIGN.md §4p "Device stream"):
+    `frames_list` holds one entry per stream, a [k_u, H] fp32 frame tensor (audio_ln applied) or None / k_u = 0 for a stream that sits
+    the push out; they are packed here and the table of first rows and counts is the push's one small host-to-device copy.
+    `lstm_params` as greedy_decode_lstm's, `max_length` 0 = unbounded, `block` the group's persistent block (greedy_stream_lstm_init),
+    `out_tokens` int32[n, stride] with stride >= the largest count * max_per_frame.  Iterations are enqueued in chunks until the device
+    has raised the pinned flag (all streams at rest; polled, never waited for): chunks of `chunk` iterations, fewer for a push of few
+    frames, at most `in_flight` of them ahead of the device.  No synchronisation: afterwards, with state = greedy_stream_lstm_views(block,
+    ...)[0], out_tokens[u, :state[u, LSTM_STREAM_PUSH_LABELS]] are the labels this push gave stream u (if it got frames and was not done)
+    and state[u, LSTM_STREAM_FRAMES] its frames consumed.  A push without any frame enqueues nothing."""
+    from .lstm_predictor import _struct
+    n = int(out_tokens.shape[0])
+    frames_list = list(frames_list)
+    if len(frames_list) != n:
+        raise ValueError(f"greedy_stream_lstm_push: {len(frames_list)} entries for {n} streams")
+    counts = [0 if f is None else int(f.shape[0]) for f in frames_list]
+    if not any(counts):
+        return
+    max_count = max(counts)
+    params, (L, Hd, layer_norm), eps = lstm_params
+    params = [t.contiguous() for t in params]
+    packed, rows = _pack_rows(frames_list, counts)
+    if packed.dim() != 2 or packed.stride(1) != 1:
+        packed = packed.contiguous()
+    joint = [t.contiguous() for t in (W, bias)] + ([text_W.contiguous(), text_b.contiguous()] if text_W is not None else [])
+    dev = _require_cuda(packed, block, out_tokens, *joint, *params)
+    _require_dtype(torch.float32, frames=packed, **{f"joint{i}": t for i, t in enumerate(joint)}, **{f"param{i}": t for i, t in enumerate(params)})
+    _require_dtype(torch.int32, out_tokens=out_tokens)
+    _require_dtype(torch.uint8, block=block)
+    _require_contiguous(block=block, out_tokens=out_tokens)
+    H, V = packed.shape[1], joint[0].shape[0]
+    S, E = params[0].shape
+    O = params[3].shape[0]
+    max_length, max_per_frame, scan_frames = int(max_length), int(max_per_frame), int(scan_frames)
+    bound = max_count * max(1, max_per_frame) + (max_count + scan_frames - 1) // max(1, scan_frames) + 1
+    with torch.cuda.device(dev):
+        nb = ctypes.c_size_t(0)
+        _check(lib().rnnt_engine_greedy_stream_lstm_push_workspace_bytes(n, S, E, Hd, O, L, int(bool(layer_norm)), H, V, int(len(joint) == 4),
+                                                                         scan_frames, ctypes.byref(nb)))
+        ws = workspace(dev, nb.value)
+        table = _rows_table(rows, dev)
+        st, arr = _struct(params, L, layer_norm)
+        head = (_p(packed), ctypes.c_int64(packed.stride(0) if packed.shape[0] > 1 else H), packed.shape[0], _p(table), n, max_count,
+                ctypes.byref(st), S, E, Hd, O, L, int(bool(layer_norm)), *[ctypes.c_float(e) for e in eps],
+                _p(joint[2]) if len(joint) == 4 else None, _p(joint[3]) if len(joint) == 4 else None, _p(joint[0]), _p(joint[1]), H, V,
+                int(blank), max_length, max_per_frame, scan_frames)
+        tail = (_p(out_tokens), int(out_tokens.shape[1]), _p(block), ctypes.c_size_t(block.numel()), _p(ws), ctypes.c_size_t(ws.numel()),
+                _stream(dev))
+        # chunks sized to the push (a 1-frame push needs one iteration, two if it emits a label), and the wait as soon as `in_flight`
+        # chunks are out, before the flag is read again: a short push ends after the chunk that served it
+        flag = _enqueue_rounds(lambda it, first, flag: _check(lib().rnnt_engine_greedy_stream_lstm_push(*head, it, first, flag, *tail)),
+                               bound, min(max(1, int(chunk)), 2 * max_count + 1), in_flight, wait_at_limit=True)
+        out_tokens._keepalive = (flag, table, packed, params, joint, arr)  # until the caller has synchronised
 
 
 # ---- streaming greedy decode (include/rnnt_engine.h RNNT_STREAM_*; DESIGN.md §4i)

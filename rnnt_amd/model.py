@@ -256,12 +256,28 @@ class RNNTModel(torch.nn.Module):
         loop.run(audio)
         return loop.tokens[1:]
 
-    def greedy_stream(self, max_length=None, max_symbols_per_frame=10, persistent=None):
+    def greedy_stream(self, max_length=None, max_symbols_per_frame=10, persistent=None, device_loop=None):
         """A GreedyStream (rnnt_amd/stream.py): greedy decoding push by push — `push(mel_chunk)` through the encoder's
         streaming_forward, or `push_encoded(audio_features)` — whose labels, concatenated, equal greedy_decode of all frames at once with
-        the same max_length (None: unbounded).  The device paths and their choice follow greedy_decode; `persistent` forces one."""
+        the same max_length (None: unbounded).  The device paths and their choice follow greedy_decode; `persistent` forces one.
+        `device_loop=None` keeps the choice every model had before LSTM streams could rest on the device: a ConvPredictor model takes its
+        device paths, an LSTMPredictor model the HOST loop.  `device_loop=True` makes an LSTMPredictor stream a device group of one
+        (greedy_streams; DESIGN.md §4p "Device stream") and raises where no device path applies; `device_loop=False` forces the host loop.
+        Making the device the default of an LSTM stream is left to a follow-up."""
         from .stream import GreedyStream
-        return GreedyStream(self, max_length=max_length, max_symbols_per_frame=max_symbols_per_frame, persistent=persistent)
+        return GreedyStream(self, max_length=max_length, max_symbols_per_frame=max_symbols_per_frame, persistent=persistent,
+                            device_loop=device_loop)
+
+    def greedy_streams(self, n: int, max_length=None, max_symbols_per_frame=10, scan_frames=32, device_loop=None):
+        """A GreedyStreamGroup (rnnt_amd/stream.py; DESIGN.md §4p "Device stream"): `n` (1 .. 32) independent greedy streams of this model
+        — `push_encoded([chunk or None] * n)` returns each stream's new labels, `tokens[i]` equals greedy_decode of the frames stream i has
+        been pushed so far, `reset(i)` starts a new utterance in slot i.  With an LSTMPredictor model the device decode loop takes, the
+        streams rest on the device and a push advances all of them in lockstep with one host synchronisation (`device_loop`: None = where
+        it applies and n >= 4, the sizes at which it beat n host loops at every timed shape, profiles/lstm_stream_bench.txt; True = or
+        raise; False = n host loops); every other model runs n host loops."""
+        from .stream import GreedyStreamGroup
+        return GreedyStreamGroup(self, n, max_length=max_length, max_symbols_per_frame=max_symbols_per_frame, scan_frames=scan_frames,
+                                 device_loop=device_loop)
 
     # greedy_decode_many's default batch with an LSTMPredictor: of 4, 8, 16 and 32 the only one within 10 % of the best time per utterance
     # at both timed lengths (2.0 ms at T = 1000, 0.56 ms at T = 100; profiles/lstm_decode_bench.txt)

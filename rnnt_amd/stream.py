@@ -5,6 +5,9 @@ frames at once with the same max_length, wherever the argmax is not a rounding-l
 
 HostGreedyLoop is greedy_decode's host loop made resumable; greedy_decode and the host path of GreedyStream both run it.
 
+RNNTModel.greedy_streams(n) returns a GreedyStreamGroup: n independent greedy streams of one model.  With an rnnt_amd.LSTMPredictor
+model the streams rest on the device between pushes and advance in lockstep (DESIGN.md §4p "Device stream").
+
 Streaming beam search: RNNTModel.beam_stream() / beam_streams(n) return a BeamStream / a BeamStreamGroup whose n-best
 list after any sequence of pushes equals RNNTModel.beam_search of the frames pushed so far — on the device bit for bit, from a block of
 device memory the stream owns; HostBeamLoop is the host search made resumable, which beam_search's host path runs too.
@@ -142,10 +145,12 @@ class GreedyStream:
     else the kernel-per-layer loop (`persistent=True/False` forces one), with ONE host synchronisation per push — two when a persistent
     push meets an activation beyond +-30 or gives up waiting for a hand-off and is redone on the loop.  The decode tables are built when
     the stream is created: the model's weights must not change while a stream is open.  Everything else, the CPU included, runs
-    HostGreedyLoop.  The encoder's mode is the caller's business: the reference's BatchNorm encoder must be in eval() for its streaming
+    HostGreedyLoop — with `device_loop=None` that includes every rnnt_amd.LSTMPredictor model, as before; `device_loop=True` makes such a
+    stream a device GreedyStreamGroup of one (`last_path` "lstm_stream", one synchronisation per push; DESIGN.md §4p "Device stream") and
+    raises where no device path applies, `device_loop=False` forces the host loop for any model.  The encoder's mode is the caller's business: the reference's BatchNorm encoder must be in eval() for its streaming
     output to equal its whole-utterance output."""
 
-    def __init__(self, model, max_length=None, max_symbols_per_frame=10, persistent=None):
+    def __init__(self, model, max_length=None, max_symbols_per_frame=10, persistent=None, device_loop=None, scan_frames=32):
         from . import engine
         self.model = model
         self.max_length = None if max_length is None else int(max_length)
@@ -161,22 +166,30 @@ class GreedyStream:
         self._audio_state = None  # push_audio: the samples no frame has consumed yet (1, n), on the model's device
         self._pending = None      # push_audio: frames featurized but not yet taken by the encoder (1, F, L)
         dev = model.device
-        self._on_device = (dev.type == "cuda" and not model._predictor_is_stateful()
+        self._on_device = (device_loop is not False and dev.type == "cuda" and not model._predictor_is_stateful()
                            and model._device_loop_ok(torch.zeros(1, 1, device=dev)))
         self._host = None
         self._tables = None
-        if self._on_device:
+        self._group = None
+        if device_loop and not self._on_device:
+            # an LSTM model: a device group of one (raises where the device path does not apply, as for any other predictor)
+            self._group = GreedyStreamGroup(model, 1, max_length, max_symbols_per_frame, scan_frames, device_loop=True)
+        elif self._on_device:
             self._sizes = model._decode_sizes()
             if persistent is not False and engine.greedy_decode_persistent_supported(8, *self._sizes):
                 self._tables = model._decode_tables()  # once per stream, from the weights as they are now
             self._buf = torch.empty(engine.STREAM_STATE_WORDS + 16, dtype=torch.int32, device=dev)  # state block | the push's labels
             engine.greedy_stream_init(self._buf[:engine.STREAM_STATE_WORDS], model.joint.blank_idx)
         else:
-            self._host = HostGreedyLoop(model, self.max_length, self.max_symbols_per_frame, scan_frames=32)
+            self._host = HostGreedyLoop(model, self.max_length, self.max_symbols_per_frame, scan_frames=max(0, min(int(scan_frames), 128)))
 
     @property
     def done(self):
         return self._done
+
+    def lstm_state(self):
+        """Test aid: clones of (LSTM state [L, 2, Hd], text vector [H]) of a stream that is a device group of one."""
+        return self._group.lstm_state(0)
 
     @torch.no_grad()
     def push(self, mel_chunk):
@@ -217,6 +230,12 @@ class GreedyStream:
             raise ValueError(f"GreedyStream.push_encoded takes one chunk of encoder output (1, C, n), got {tuple(audio_features.shape)}")
         if self._done:
             return []
+        if self._group is not None:
+            new = self._group.push_encoded([audio_features])[0]
+            self.frames, self._done = self._group.frames[0], self._group.done[0]
+            self.last_path = self._group.last_path or self.last_path
+            self.tokens.extend(new)
+            return new
         audio = audio_features.permute(0, 2, 1)  # (1, n, C), as rnnt/model.py:93
         new = self._push_device(audio) if self._on_device else self._push_host(audio)
         self.tokens.extend(new)
@@ -272,6 +291,156 @@ class GreedyStream:
         self._done = bool(st[engine.STREAM_DONE])
         self.last_path = path
         return h[W:W + st[engine.STREAM_PUSH_LABELS]].tolist()
+
+
+class GreedyStreamGroup:
+    """`n` (1 .. 32) independent utterances greedy-decoded push by push (RNNTModel.greedy_streams; DESIGN.md §4p "Device stream").
+    `push_encoded(chunks)` takes a list of n chunks of encoder output, each (1, C, k_i) with k_i >= 0, or None for a stream that sits
+    the push out, and returns the list of each stream's new labels.  Per stream i: `tokens[i]` every label so far — `greedy_decode` of
+    the frames stream i has been pushed so far with the same max_length and max_symbols_per_frame, whatever the chunking and whatever the
+    other streams do —, `frames[i]` the frames consumed, `done[i]` the max_length cap was reached (later pushes consume nothing and
+    return []); `reset(i)` starts a new utterance in slot i; `last_path`: "lstm_stream" or "host".
+
+    With an rnnt_amd.LSTMPredictor model that the device decode loop takes (eval mode or p = 0, fp32 HIP tensors, backend not "torch",
+    sizes the kernels cover) the streams rest on the device between pushes, in ONE block the group owns: LSTM state, text vectors and
+    the loop's words (rnnt_engine_greedy_stream_lstm_push).  A push advances all streams in lockstep through one kernel sequence per
+    iteration and ends in ONE host synchronisation; a stream's labels and state are bit for bit those of the same frames decoded alone
+    by the offline device loop.  The parameters are read live at every push, but the carried state is a function of the weights that
+    produced it: do not change them while a group is open.  Everything else — the CPU, backend "torch", a training-mode predictor with
+    dropout, sizes the kernels refuse, any other predictor (ConvPredictor models included) — runs n host streams (HostGreedyLoop) and
+    returns the same results; `device_loop=True` raises where the device path does not apply, `device_loop=False` forces the host.
+    `device_loop=None` takes the device path where it applies AND n >= DEVICE_MIN_STREAMS: at the reference's widths the device group beat
+    n host streams at every timed shape from n = 4 on (1000 frames in 50-frame pushes: 4.5x at n = 4, 16x at n = 32; in 1-frame pushes:
+    1.45x and 3.5x), but ONE stream lost in 1-frame pushes (0.24 ms against 0.06 ms per push: a push enqueues 34 launches where the host
+    loop makes one scan call) while winning 2.5x in 50-frame pushes; n = 2 and 3 were not timed and stay on the host
+    (profiles/lstm_stream_bench.txt)."""
+
+    DEVICE_MIN_STREAMS = 4
+
+    def __init__(self, model, n, max_length=None, max_symbols_per_frame=10, scan_frames=32, device_loop=None):
+        from . import engine
+        n, m = int(n), int(max_symbols_per_frame)
+        if not 1 <= n <= engine.LSTM_STREAM_MAX:
+            raise ValueError(f"greedy_streams: n={n} outside [1, {engine.LSTM_STREAM_MAX}]")
+        if m < 1:
+            raise ValueError(f"greedy_streams: max_symbols_per_frame={max_symbols_per_frame} must be >= 1")
+        self.model, self.n = model, n
+        self.max_length = None if max_length is None else int(max_length)
+        self.max_symbols_per_frame = m
+        self.scan_frames = max(1, min(int(scan_frames) if int(scan_frames) > 0 else 32, 128))
+        self.tokens = [[] for _ in range(n)]
+        self.frames = [0] * n
+        self.last_path = None
+        self._capped = self.max_length is not None and self.max_length < 2  # (the reference's loop never runs: tokens = [blank] is full)
+        self._done = [self._capped] * n
+        dev = model.device
+        ok = dev.type == "cuda" and model._predictor_is_lstm() and model._device_loop_ok(torch.zeros(1, 1, device=dev))
+        if ok:
+            joint = model.joint
+            self._dims = (*model.predictor._decode_sizes(), joint.joint_ln.in_features, joint.joint_ln.out_features, hasattr(joint, "text_ln"))
+            ok = engine.greedy_stream_lstm_supported(n, *self._dims, self.scan_frames)
+        if device_loop and not ok:
+            raise RuntimeError("greedy_streams(device_loop=True) needs the engine's LSTMPredictor in eval mode on a HIP device "
+                               "(fp32, backend not \"torch\", sizes the decode kernels cover)")
+        self._on_device = (ok and n >= self.DEVICE_MIN_STREAMS) if device_loop is None else bool(device_loop)
+        if self._on_device:
+            _, _, Hd, _, L, _, H, _, _ = self._dims
+            self._block = torch.zeros(engine.greedy_stream_lstm_bytes(n, *self._dims), dtype=torch.uint8, device=dev)
+            self._state, self._hc, self._text = engine.greedy_stream_lstm_views(self._block, n, L, Hd, H)
+            self._out = torch.zeros(n, 16, dtype=torch.int32, device=dev)  # the push's labels; grows with the largest push, never with a stream
+            engine.greedy_stream_lstm_init(self._block, n, L, Hd, H, model.joint.blank_idx)
+        else:
+            self._streams = [self._host_stream() for _ in range(n)]
+
+    def _host_stream(self):
+        return GreedyStream(self.model, self.max_length, self.max_symbols_per_frame, device_loop=False, scan_frames=self.scan_frames)
+
+    @property
+    def done(self):
+        return list(self._done)
+
+    def reset(self, i):
+        """Stream i starts a new utterance (the others are untouched)."""
+        i = range(self.n)[i]
+        if self._on_device:
+            from . import engine
+            _, _, Hd, _, L, _, H, _, _ = self._dims
+            engine.greedy_stream_lstm_init(self._block, self.n, L, Hd, H, self.model.joint.blank_idx, index=i)
+        else:
+            self._streams[i] = self._host_stream()
+        self.tokens[i] = []
+        self.frames[i] = 0
+        self._done[i] = self._capped
+
+    def lstm_state(self, i):
+        """Test aid: clones of (LSTM state [L, 2, Hd], text vector [H]) of stream i as it rests — after the last label taken in, the zero
+        state before the stream's first frame."""
+        i = range(self.n)[i]
+        if self._on_device:
+            return self._hc[:, :, i].clone(), self._text[i].clone()
+        loop = self._streams[i]._host
+        text = loop.feats[0, -1]
+        if hasattr(self.model.joint, "text_ln"):
+            text = self.model.joint.text_ln(text)
+        return torch.stack([torch.stack((h[0], c[0])) for h, c in loop.state]), text.clone()
+
+    @torch.no_grad()
+    def push_encoded(self, chunks):
+        """One push: `chunks[i]` is stream i's next chunk of encoder output (1, C, k_i), k_i >= 0, or None.  Returns the list of the
+        streams' new labels."""
+        chunks = list(chunks)
+        if len(chunks) != self.n:
+            raise ValueError(f"GreedyStreamGroup.push_encoded takes {self.n} chunks (None for a stream without new frames), got {len(chunks)}")
+        for c in chunks:
+            if c is not None and (c.dim() != 3 or c.shape[0] != 1):
+                raise ValueError(f"a greedy stream takes one chunk of encoder output (1, C, n), got {tuple(c.shape)}")
+        # (a done stream consumes nothing: it sits every later push out)
+        chunks = [None if c is None or c.shape[2] == 0 or self._done[i] else c for i, c in enumerate(chunks)]
+        new = [[] for _ in range(self.n)]
+        if any(c is not None for c in chunks):
+            (self._push_device if self._on_device else self._push_host)(chunks, new)
+            for i, labels in enumerate(new):
+                self.tokens[i].extend(labels)
+        return new
+
+    def _push_host(self, chunks, new):
+        for i, c in enumerate(chunks):
+            if c is None:
+                continue
+            s = self._streams[i]
+            new[i] = s.push_encoded(c)
+            self.frames[i], self._done[i] = s.frames, s.done
+        self.last_path = "host"
+
+    def _push_device(self, chunks, new):
+        from . import engine
+        model, n, m = self.model, self.n, self.max_symbols_per_frame
+        frames = [None if c is None else model._decode_frames(c.permute(0, 2, 1)) for c in chunks]  # (1, k, C), as rnnt/model.py:93
+        for f in frames:
+            if f is not None and f.device != self._block.device:
+                raise ValueError(f"greedy streams: the group lives on {self._block.device}, the chunk on {f.device}")
+        cap = max(f.shape[0] for f in frames if f is not None) * m
+        if self._out.shape[1] < cap:
+            self._out = torch.zeros(n, cap, dtype=torch.int32, device=self._block.device)
+        joint = model.joint
+        tl = getattr(joint, "text_ln", None)
+        engine.greedy_stream_lstm_push(frames, model.predictor._decode_bundle(), tl.weight if tl is not None else None,
+                                       tl.bias if tl is not None else None, joint.joint_ln.weight, joint.joint_ln.bias, joint.blank_idx,
+                                       self.max_length or 0, m, self.scan_frames, self._block, self._out)
+        W = engine.LSTM_STREAM_STATE_WORDS
+        host = torch.cat((self._state.reshape(-1), self._out.reshape(-1))).cpu()  # the push's one synchronisation
+        sts, out = host[:n * W].view(n, W).tolist(), host[n * W:].view(n, -1)
+        for i, (f, st) in enumerate(zip(frames, sts)):
+            if f is None:
+                continue
+            done = bool(st[engine.LSTM_STREAM_DONE])
+            if not st[engine.LSTM_STREAM_AT_REST] or (not done and st[engine.LSTM_STREAM_FRAMES] != self.frames[i] + f.shape[0]):
+                raise RuntimeError(f"rnnt_engine: greedy stream {i} did not consume its push (frames={st[engine.LSTM_STREAM_FRAMES]}, "
+                                   f"{st[engine.LSTM_STREAM_PUSH_ITERATIONS]} iterations)")
+            new[i] = out[i, :st[engine.LSTM_STREAM_PUSH_LABELS]].tolist()
+            self.frames[i], self._done[i] = st[engine.LSTM_STREAM_FRAMES], done
+        model.predictor.last_backend = "engine"
+        self.last_path = "lstm_stream"
 
 
 class HostBeamLoop:
