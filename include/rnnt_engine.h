@@ -903,6 +903,60 @@ int rnnt_engine_encoder_stream_push(const rnnt_encoder_layer *layers, int n_laye
                                     size_t ws_bytes, void *stream);
 
 /*
+ * The AudioEncoder's TRAINING forward and backward: whole utterances, fp32, exact fp32 products, the same flat
+ * layer list.  Per layer, with X~ = lead[i] zero frames followed by the layer's input:
+ *     y = conv(X~) + bias;  h = norm(y);  z = h (+ the residual branch on a LAST layer);  a = GELU(z) (RESIDUAL and FINAL
+ *     layers: a = z);  o = a * keep / (1 - p) where keep[i] is given, else o = a.
+ * RNNT_ENC_NORM_BATCH normalises with the running statistics (a frozen batch norm: gamma and beta get gradients, mean / var are
+ * constants); batch statistics are not supported.  The backward follows from that definition; instance norm with the biased
+ * variance: g = dz gamma, dy = rstd (g - mean_t g - xhat mean_t(g xhat)).  The gradient of x is not computed.
+ *   lead  HOST array of n_layers frame counts: the zero frames in front of each conv's input,
+ *         (taps-1)*dilation - stride + 1 - look-ahead; 0 <= lead[i] <= (taps-1)*dilation - stride + 1 is checked; entries of
+ *         RESIDUAL / FINAL layers are ignored; NULL = no look-ahead anywhere.  Frames out = (lead + frames in -
+ *         dilation*(taps-1) - 1) / stride + 1.  A block's LAST layer must leave as many frames as its RESIDUAL layer (the
+ *         residual branch is added frame by frame): look-ahead inside a block is RNNT_ERR_INVALID_ARG.
+ *   keep  HOST array of n_layers device pointers or NULL; keep[i] NULL: layer i drops nothing; else one byte per output value,
+ *         [N][frames out][cout] contiguous, non-zero = kept.  A mask on a RESIDUAL / FINAL layer is refused.
+ *   p     HOST array of n_layers drop probabilities in [0, 1) (read where keep[i] is given) or NULL = all 0.
+ *   packed  rnnt_engine_encoder_train_pack: the forward's tables of rnnt_engine_encoder_pack for every layer, then per layer the
+ *         dX conv's table [tap reversed][cin][cout rounded up to 4].  Repack after the weights change.
+ *   saved   caller-owned, 16-byte aligned, rnnt_engine_encoder_train_saved_bytes; written by _train_fwd, read by _train_bwd.  Per
+ *         layer, in list order, each piece rounded up to 256 bytes, rows of ld = cout rounded up to 4 floats:
+ *           o    [N][frames out][ld]  the layer's output, the next layer's input    every layer but RESIDUAL ones and the list's last
+ *           z    [N][frames out][ld]  the value in front of the GELU                every layer but RESIDUAL / FINAL ones
+ *           xhat [N][frames out][ld]  the normalised conv output (y - mean) rstd    layers with a norm
+ *           rstd [N][cout]                                                          RNNT_ENC_NORM_INSTANCE layers
+ *         x, keep, p, lead and the layer list must be the forward's when _train_bwd runs.
+ *   dout    [N][L_out][cout of the last layer] contiguous: the gradient of `out`.
+ *   grads   HOST array of n_layers rnnt_encoder_grads; a NULL member is not computed; weight [cout][cin][taps], the others
+ *         [cout].  They are written, not accumulated into.  gamma / beta of a layer without a norm are refused.
+ * The workspace (rnnt_engine_encoder_train_workspace_bytes: the larger of both calls') carries nothing from _train_fwd to
+ * _train_bwd.  `regime` picks the forward's conv kernel as above; the backward always runs the MFMA kernels.
+ * Limits beside the inference entries': a layer behind the list's first (first two, where the list opens with a block) has
+ * stride 1 (RNNT_ERR_UNSUPPORTED: dX exists for stride 1 only); N * frames in of every such layer <= 65535 * 32.
+ * Launches per layer: forward 2 (conv, k_enc_norm_train); backward 4 (k_enc_bwd_norm, k_enc_dw, k_enc_bwd_sum, the dX conv), 3
+ * where the layer reads the list's input.  No atomics; every sum has a fixed order: results are bitwise reproducible.
+ * Everything is checked before anything is enqueued.
+ */
+typedef struct rnnt_encoder_grads {
+    void *weight, *bias, *gamma, *beta;
+} rnnt_encoder_grads;
+int rnnt_engine_encoder_train_packed_bytes(const rnnt_encoder_layer *layers, int n_layers, size_t *out);
+int rnnt_engine_encoder_train_pack(const rnnt_encoder_layer *layers, int n_layers, void *packed, size_t packed_bytes, void *stream);
+int rnnt_engine_encoder_train_saved_bytes(const rnnt_encoder_layer *layers, int n_layers, int N, int L, const int32_t *lead,
+                                          size_t *out);
+int rnnt_engine_encoder_train_workspace_bytes(const rnnt_encoder_layer *layers, int n_layers, int N, int L, int regime,
+                                              const int32_t *lead, size_t *out);
+int rnnt_engine_encoder_train_fwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x,
+                                  const int64_t x_strides[3], int N, int L, const int32_t *lead, const void *const *keep,
+                                  const float *p, int regime, float *out, void *saved, size_t saved_bytes, void *workspace,
+                                  size_t ws_bytes, void *stream);
+int rnnt_engine_encoder_train_bwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x,
+                                  const int64_t x_strides[3], int N, int L, const int32_t *lead, const void *const *keep,
+                                  const float *p, const float *dout, const void *saved, size_t saved_bytes,
+                                  const rnnt_encoder_grads *grads, void *workspace, size_t ws_bytes, void *stream);
+
+/*
  * The audio featurizer (reference rnnt/featurizer.py): samples to the features the encoder reads.  Frame f,
  * bin k (n_fft / 2 + 1 bins) of utterance n:
  *     p = | sum_j w[j] x[f * hop_length + j] exp(-2 pi i j k / n_fft) |^2        (torch.stft, onesided, not normalized)

@@ -19,6 +19,8 @@
 //                    generalised to stride and dilation: v_mfma_f32_32x32x2_f32, exact fp32 products, the four waves split the
 //                    contraction and add their tiles up through LDS in wave order.
 // No atomics anywhere: the same inputs give the same bits.
+// The second half of the file is the encoder's TRAINING (rnnt_engine_encoder_train_*): the same conv kernels, an epilogue that also
+// saves what the backward reads, and the backward's kernels; see "training" below.
 #include "../../include/rnnt_engine.h"
 
 #include <cstdint>
@@ -41,13 +43,14 @@ struct EncSrc {
     int slen;          // frames of state in front of the chunk
     const float *x;    // chunk
     long xn, xc, xt;   // its strides (floats) per batch entry, channel, frame
-    int xlen;          // its frames
+    int xlen;          // its frames; frames behind the last read as zeros (only the training dX conv asks for any)
     int C;             // channels
 };
 
 __device__ __forceinline__ float enc_src(const EncSrc &s, int n, int c, int tau)
 {
     if (tau < s.slen) return s.st ? s.st[((long)n * s.C + c) * s.slen + tau] : 0.f;
+    if (tau - s.slen >= s.xlen) return 0.f;
     return s.x[n * s.xn + c * s.xc + (long)(tau - s.slen) * s.xt];
 }
 
@@ -166,7 +169,7 @@ __global__ __launch_bounds__(256) void k_enc_conv_mfma(EncConv a)
         const int kk = kok ? k : K - 4;
         const int tau = t * a.stride + tap * a.dil;
         o.x = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (kok) {
+        if (kok && tau - a.src.slen < a.src.xlen) {
             if (tau >= a.src.slen && a.xvec && k + 3 < C) {
                 o.x = *(const f32x4 *)(a.src.x + bn * a.src.xn + (long)(tau - a.src.slen) * a.src.xt + k);
             } else {
@@ -331,6 +334,317 @@ __global__ __launch_bounds__(256) void k_enc_pack_w(const float *__restrict__ w,
     const long to = idx / in_p;
     const int co = (int)(to % out_c), t = (int)(to / out_c);
     wp[idx] = ci < in_c ? w[((long)co * in_c + ci) * taps + t] : 0.f;
+}
+
+// =============================================================================================================== training
+// rnnt_engine_encoder_train_*: a forward that keeps what the backward reads, and the backward.  Per layer the
+// forward is the conv kernel above and k_enc_norm_train; the backward is k_enc_bwd_norm (dO -> dz -> dy, the per-entry partial
+// sums of dgamma / dbeta / dbias, the copy of dz into the residual branch, the sum of the two dx of a block input), k_enc_dw (the
+// weight gradient's products, one slab per row range), k_enc_bwd_sum (slabs and partial sums added in index order, dW stored in
+// torch's [out][in][tap]) and, for every layer but those that read the list's input, k_enc_conv_mfma over dy with the second
+// packed table [tap reversed][in][out rounded up to 4].  Every sum has a fixed order.
+constexpr int ENC_DW_WGS = 512;    // workgroups k_enc_dw aims for by cutting the rows ...
+constexpr int ENC_DW_RANGES = 16;  // ... into at most this many ranges, each a multiple of ...
+constexpr int ENC_DW_STEP = 8;     // ... the rows of one pipeline step
+
+__device__ __forceinline__ float gelu_grad(float z)  // Phi(z) + z phi(z)
+{
+    return 0.5f * (1.f + erff(z * 0.70710678118654752f)) + z * 0.3989422804014327f * expf(-0.5f * z * z);
+}
+
+// The training form of k_enc_norm: whole utterances only (no state blocks).  Besides the layer's output it leaves z (the value in
+// front of the GELU), xhat (the normalised conv output) and, for instance norm, rstd per (n, channel); a keep mask [N][Lout][cout]
+// (one byte per value) zeroes the output or scales it by `scale` = 1 / (1 - p).
+struct EncNormT {
+    const float *slabs; int nsplit;
+    const float *bias, *gamma, *beta, *mean, *var;
+    int norm; float eps;
+    const float *res; long ldres;
+    int act;
+    const uint8_t *keep; float scale;
+    float *out; long ldo;
+    float *z, *xh, *rstd; long lds;  // z, xhat [N][Lout][lds]; rstd [N][cout]; NULL where the layer keeps none
+    int N, Lout, cout;
+};
+
+__global__ __launch_bounds__(ENC_NORM_THREADS) void k_enc_norm_train(EncNormT a)
+{
+    __shared__ float red[ENC_NORM_THREADS];
+    const int tid = threadIdx.x, cl = tid & 15, tl = tid >> 4;
+    const int cgroups = (a.cout + 15) / 16;
+    const int n = (int)blockIdx.x / cgroups, c = ((int)blockIdx.x - n * cgroups) * 16 + cl;
+    const bool ok = c < a.cout;
+    const long M = (long)a.N * a.Lout, row0 = (long)n * a.Lout;
+    const float b = ok && a.bias ? a.bias[c] : 0.f;
+    auto pre = [&](int t) {
+        const float *s = a.slabs + (row0 + t) * a.cout + c;
+        const long step = M * a.cout;
+        float v = s[0];
+        for (int k = 1; k < a.nsplit; ++k) v += s[(long)k * step];  // index order, as k_enc_norm
+        return v + b;
+    };
+    float mu = 0.f, rstd = 1.f;
+    const bool inst = a.norm == RNNT_ENC_NORM_INSTANCE;
+    if (inst) {  // two passes, as k_enc_norm; the conv output is parked in xhat's place
+        float s = 0.f;
+        if (ok)
+            for (int t = tl; t < a.Lout; t += ENC_NORM_LANES) {
+                const float v = pre(t);
+                a.xh[(row0 + t) * a.lds + c] = v;
+                s += v;
+            }
+        red[tid] = s;
+        __syncthreads();
+        s = 0.f;
+        for (int k = 0; k < ENC_NORM_LANES; ++k) s += red[16 * k + cl];
+        mu = s / (float)a.Lout;
+        __syncthreads();
+        float q = 0.f;
+        if (ok)
+            for (int t = tl; t < a.Lout; t += ENC_NORM_LANES) {
+                const float d = a.xh[(row0 + t) * a.lds + c] - mu;
+                q += d * d;
+            }
+        red[tid] = q;
+        __syncthreads();
+        q = 0.f;
+        for (int k = 0; k < ENC_NORM_LANES; ++k) q += red[16 * k + cl];
+        rstd = 1.f / sqrtf(q / (float)a.Lout + a.eps);
+        if (ok && tl == 0) a.rstd[(long)n * a.cout + c] = rstd;
+    } else if (a.norm == RNNT_ENC_NORM_BATCH && ok) {
+        mu = a.mean[c];
+        rstd = 1.f / sqrtf(a.var[c] + a.eps);
+    }
+    if (!ok) return;
+    const float g = a.norm != RNNT_ENC_NORM_NONE && a.gamma ? a.gamma[c] : 1.f;
+    const float be = a.norm != RNNT_ENC_NORM_NONE && a.beta ? a.beta[c] : 0.f;
+    for (int t = tl; t < a.Lout; t += ENC_NORM_LANES) {
+        const long row = row0 + t;
+        float v = inst ? a.xh[row * a.lds + c] : pre(t);
+        if (a.norm != RNNT_ENC_NORM_NONE) {
+            const float xh = (v - mu) * rstd;
+            a.xh[row * a.lds + c] = xh;
+            v = xh * g + be;
+        }
+        if (a.res) v += a.res[row * a.ldres + c];
+        if (a.act) {
+            a.z[row * a.lds + c] = v;
+            v = gelu_exact(v);
+        }
+        if (a.keep) v = a.keep[row * a.cout + c] ? v * a.scale : 0.f;
+        a.out[row * a.ldo + c] = v;
+    }
+}
+
+// ---- dO -> dz -> dy of one layer.  Block (channel group of 16, batch entry n), thread (channel, frame lane), as k_enc_norm.
+// dO[row][c] = the slabs of source a in index order, then those of source b (the two dx of a block input: first layer's, then the
+// residual 1x1's); a caller's gradient or the residual branch's is a source of one slab.
+struct EncGradSrc { const float *p; int nsplit; long split, ld; };
+struct EncNormB {
+    EncGradSrc a, b;
+    const uint8_t *keep; float scale;
+    const float *z; int act;
+    const float *xh, *rstd, *gamma, *var;
+    int norm; float eps; long lds;
+    float *dy; long ldy;
+    float *dres; long ldres;  // LAST layers: dz, the residual layer's dO; else NULL
+    float *part;              // [3][N][cout]: sum_t dz xhat, sum_t dz, sum_t dy of batch entry n
+    int N, Lout, cout;
+};
+
+__global__ __launch_bounds__(ENC_NORM_THREADS) void k_enc_bwd_norm(EncNormB a)
+{
+    __shared__ float red[ENC_NORM_THREADS];
+    const int tid = threadIdx.x, cl = tid & 15, tl = tid >> 4;
+    const int cgroups = (a.cout + 15) / 16;
+    const int n = (int)blockIdx.x / cgroups, c = ((int)blockIdx.x - n * cgroups) * 16 + cl;
+    const bool ok = c < a.cout;
+    const long row0 = (long)n * a.Lout;
+    auto lanes = [&](float s) {  // the 64 frame lanes' partial sums of this channel, in lane order
+        red[tid] = s;
+        __syncthreads();
+        float r = 0.f;
+        for (int k = 0; k < ENC_NORM_LANES; ++k) r += red[16 * k + cl];
+        __syncthreads();
+        return r;
+    };
+    const bool normed = a.norm != RNNT_ENC_NORM_NONE;
+    float s1 = 0.f, s2 = 0.f;
+    if (ok)
+        for (int t = tl; t < a.Lout; t += ENC_NORM_LANES) {
+            const long row = row0 + t;
+            const float *s = a.a.p + row * a.a.ld + c;
+            float v = s[0];
+            for (int k = 1; k < a.a.nsplit; ++k) v += s[(long)k * a.a.split];
+            if (a.b.p) {
+                s = a.b.p + row * a.b.ld + c;
+                for (int k = 0; k < a.b.nsplit; ++k) v += s[(long)k * a.b.split];
+            }
+            if (a.keep) v = a.keep[row * a.cout + c] ? v * a.scale : 0.f;
+            if (a.act) v *= gelu_grad(a.z[row * a.lds + c]);
+            a.dy[row * a.ldy + c] = v;  // dz, parked; this thread reads it back below
+            if (a.dres) a.dres[row * a.ldres + c] = v;
+            s1 += v;
+            if (normed) s2 += v * a.xh[row * a.lds + c];
+        }
+    const float S1 = lanes(s1), S2 = lanes(s2);
+    float s3 = 0.f;
+    if (ok) {
+        const float gam = normed && a.gamma ? a.gamma[c] : 1.f;
+        if (a.norm == RNNT_ENC_NORM_INSTANCE) {
+            const float rs = a.rstd[(long)n * a.cout + c], inv = 1.f / (float)a.Lout;
+            const float mg = gam * S1 * inv, mgx = gam * S2 * inv;  // mean_t g, mean_t (g xhat) with g = dz gamma
+            for (int t = tl; t < a.Lout; t += ENC_NORM_LANES) {
+                const long row = row0 + t;
+                const float v = rs * (a.dy[row * a.ldy + c] * gam - mg - a.xh[row * a.lds + c] * mgx);
+                a.dy[row * a.ldy + c] = v;
+                s3 += v;
+            }
+        } else {
+            const float f = a.norm == RNNT_ENC_NORM_BATCH ? gam * (1.f / sqrtf(a.var[c] + a.eps)) : 1.f;
+            for (int t = tl; t < a.Lout; t += ENC_NORM_LANES) {
+                const long row = row0 + t;
+                const float v = a.dy[row * a.ldy + c] * f;
+                a.dy[row * a.ldy + c] = v;
+                s3 += v;
+            }
+        }
+    }
+    const float S3 = lanes(s3);
+    if (ok && tl == 0) {
+        const long NC = (long)a.N * a.cout, at = (long)n * a.cout + c;
+        a.part[at] = S2;
+        a.part[NC + at] = S1;
+        a.part[2 * NC + at] = S3;
+    }
+}
+
+// ---- the weight gradient's products.  dW[o][i][j] = sum over the rows m = (n, t) of dy[m][o] X~[n][t*stride + j*dil][i]: per tap
+// a cout x cin product contracted over the rows, v_mfma_f32_32x32x2_f32 with A = dy^T (lane: out channel, row parity) and
+// B = the tap-shifted input (lane: in channel, row parity).  grid (taps * ranges, ceil(cin/128), ceil(cout/128)); a workgroup's four
+// waves take 32 out channels each by the same 128 in channels, so nothing is shared but cache lines and nothing is reduced
+// between waves: every element is one wave's fmaf chain over its row range, in row order.  Each row finds its own (n, t), so a
+// step whose rows cross from one batch entry to the next reads each entry's own frames; a row whose frame lies in the zero lead,
+// or behind the range's end, gives a zero operand and is not read.  Slab [range][tap][out][in].
+struct EncDW {
+    EncSrc src;       // the layer's input; src.slen = lead, src.st = NULL
+    const float *dy; long ldy;
+    int cout, taps, stride, dil, N, Lout;
+    float *slabs;
+    int ranges, rows;  // row ranges and rows per range (a multiple of ENC_DW_STEP)
+};
+
+__global__ __launch_bounds__(256) void k_enc_dw(EncDW a)
+{
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int i = lane & 31, half = lane >> 5;
+    const int o0 = blockIdx.z * 128 + 32 * wave, i0 = blockIdx.y * 128;
+    if (o0 >= a.cout) return;
+    const int cin = a.src.C, M = a.N * a.Lout;
+    const int tap = (int)blockIdx.x / a.ranges, rg = (int)blockIdx.x - tap * a.ranges;
+    const int m0 = rg * a.rows, m1 = min(M, m0 + a.rows);
+    const bool ook = o0 + i < a.cout;
+    const float *dyc = a.dy + min(o0 + i, a.cout - 1);
+    bool cok[4];
+    long xcol[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int ci = i0 + 32 * q + i;
+        cok[q] = ci < cin;
+        xcol[q] = (long)min(ci, cin - 1) * a.src.xc;
+    }
+    const int shift = tap * a.dil - a.src.slen;  // input frame of output frame t: t * stride + shift
+
+    f32x16 acc[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+
+    struct Ops { float d[ENC_DW_STEP / 2], x[ENC_DW_STEP / 2][4]; };
+    auto load = [&](Ops &o, int m) {
+#pragma unroll
+        for (int s = 0; s < ENC_DW_STEP / 2; ++s) {
+            const int row = m + 2 * s + half;
+            const bool live = row < m1;
+            const int rr = live ? row : m1 - 1;
+            const int n = rr / a.Lout, t = rr - n * a.Lout;
+            const int f = t * a.stride + shift;
+            o.d[s] = live && ook ? dyc[(long)rr * a.ldy] : 0.f;
+            const bool xl = live && f >= 0;
+            const float *xp = a.src.x + n * a.src.xn + (long)(xl ? f : 0) * a.src.xt;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) o.x[s][q] = xl && cok[q] ? xp[xcol[q]] : 0.f;
+        }
+    };
+    Ops cur, nxt;
+    load(cur, m0);
+    for (int m = m0; m < m1; m += ENC_DW_STEP) {
+        if (m + ENC_DW_STEP < m1) load(nxt, m + ENC_DW_STEP);
+#pragma unroll
+        for (int s = 0; s < ENC_DW_STEP / 2; ++s)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.d[s], cur.x[s][q], acc[q], 0, 0, 0);
+        cur = nxt;
+    }
+    float *slab = a.slabs + ((long)rg * a.taps + tap) * a.cout * cin;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int ci = i0 + 32 * q + i;
+        if (ci >= cin) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int o = o0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (o < a.cout) slab[(long)o * cin + ci] = acc[q][r];
+        }
+    }
+}
+
+// ---- the sums that close a layer's backward.  Blocks 0 .. nb_w-1: thread = one element of a slab [tap][out][in]; the ranges' slabs
+// in index order, stored at dW[out][in][tap].  Blocks behind those: thread = (which of dgamma / dbeta / dbias, channel): the batch
+// entries' partial sums in index order.
+struct EncSumB {
+    const float *slabs; int ranges, taps, cout, cin;
+    float *dw;           // [cout][cin][taps] or NULL
+    int nb_w;
+    const float *part; int N;
+    float *dst[3];       // dgamma, dbeta, dbias or NULL
+};
+
+__global__ __launch_bounds__(256) void k_enc_bwd_sum(EncSumB a)
+{
+    if ((int)blockIdx.x < a.nb_w) {
+        const long per = (long)a.taps * a.cout * a.cin;
+        const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+        if (idx >= per) return;
+        float v = a.slabs[idx];
+        for (int r = 1; r < a.ranges; ++r) v += a.slabs[(long)r * per + idx];
+        const int ci = (int)(idx % a.cin);
+        const long to = idx / a.cin;
+        const int o = (int)(to % a.cout), t = (int)(to / a.cout);
+        a.dw[((long)o * a.cin + ci) * a.taps + t] = v;
+        return;
+    }
+    const int idx = ((int)blockIdx.x - a.nb_w) * 256 + threadIdx.x;
+    if (idx >= 3 * a.cout) return;
+    const int which = idx / a.cout, c = idx - which * a.cout;
+    if (!a.dst[which]) return;
+    const float *p = a.part + (long)which * a.N * a.cout + c;
+    float v = p[0];
+    for (int n = 1; n < a.N; ++n) v += p[(long)n * a.cout];
+    a.dst[which][c] = v;
+}
+
+// the dX conv's table [tap reversed][in][out rounded up to 4, zero filled]: k_enc_conv_mfma's layout with in and out exchanged
+__global__ __launch_bounds__(256) void k_enc_pack_wt(const float *__restrict__ w, float *__restrict__ wp, int out_c, int in_c,
+                                                     int out_p, int taps)
+{
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)taps * in_c * out_p) return;
+    const int co = (int)(idx % out_p);
+    const long ti = idx / out_p;
+    const int ci = (int)(ti % in_c), t = (int)(ti / in_c);
+    wp[idx] = co < out_c ? w[((long)co * in_c + ci) * taps + (taps - 1 - t)] : 0.f;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
@@ -543,6 +857,256 @@ int run(const char *what, const rnnt_encoder_layer *layers, int n_layers, const 
     return status(what);
 }
 
+// ---- training: host side
+size_t packed_t_floats(const rnnt_encoder_layer &l) { return align_up((size_t)l.taps * l.cin * pad4(l.cout) * 4) / 4; }
+inline bool reads_input(const rnnt_encoder_layer *layers, int i) { return i == 0 || (i == 1 && layers[0].role == RNNT_ENC_ROLE_RESIDUAL); }
+constexpr size_t NOT_KEPT = ~(size_t)0;
+
+// The forward's Plan with `lead` for the state lengths, the layout of `saved`, and the backward's splits and workspace.
+struct TrainPlan {
+    Plan P;
+    int32_t lead[RNNT_ENC_MAX_LAYERS];
+    int in_of[RNNT_ENC_MAX_LAYERS];                                 // the layer whose output layer i reads; -1: x
+    size_t off_o[RNNT_ENC_MAX_LAYERS], off_z[RNNT_ENC_MAX_LAYERS];  // floats into `saved`, or NOT_KEPT
+    size_t off_xh[RNNT_ENC_MAX_LAYERS], off_rstd[RNNT_ENC_MAX_LAYERS];
+    size_t saved;                                                   // bytes
+    int dx_split[RNNT_ENC_MAX_LAYERS];                              // tap ranges of the dX conv; 0: no dX
+    int dw_ranges[RNNT_ENC_MAX_LAYERS], dw_rows[RNNT_ENC_MAX_LAYERS];
+    size_t dy, dres, x1, x2, dw, part;                              // floats, each a multiple of 256 bytes
+    size_t ws_fwd, ws_bwd;                                          // bytes; the size query answers the larger
+};
+
+int make_train_plan(const rnnt_encoder_layer *layers, int n_layers, int N, int L, const int32_t *lead, int regime, TrainPlan &T)
+{
+    for (int i = 0; i < n_layers; ++i) {
+        const rnnt_encoder_layer &l = layers[i];
+        const int pad = (l.taps - 1) * l.dilation - l.stride + 1;
+        T.lead[i] = 0;
+        if (is_1x1(l)) continue;
+        if (pad < 0) return fail(RNNT_ERR_UNSUPPORTED, "layer %d: stride %d beyond the kernel's span", i, l.stride);
+        T.lead[i] = lead ? lead[i] : pad;
+        if (T.lead[i] < 0 || T.lead[i] > pad)
+            return fail(RNNT_ERR_INVALID_ARG, "layer %d: lead %d outside 0 .. %d = (taps-1)*dilation - stride + 1", i, T.lead[i], pad);
+        if (!reads_input(layers, i) && l.stride != 1)
+            return fail(RNNT_ERR_UNSUPPORTED, "layer %d: stride %d behind the list's first layer (dX exists for stride 1 only)", i, l.stride);
+    }
+    if (int rc = make_plan(layers, n_layers, N, L, T.lead, regime, T.P)) return rc;
+    for (int i = 0, res = 0; i < n_layers; ++i) {  // a block's last layer adds the residual branch frame by frame
+        if (layers[i].role == RNNT_ENC_ROLE_RESIDUAL) res = i;
+        if ((layers[i].role & RNNT_ENC_ROLE_LAST) && T.P.Lout[i] != T.P.Lout[res])
+            return fail(RNNT_ERR_INVALID_ARG, "layer %d: lead (look-ahead) inside a block leaves %d frames, its residual branch has %d", i,
+                        T.P.Lout[i], T.P.Lout[res]);
+    }
+    size_t off = 0, dy = 0, dres = 0, x1 = 0, x2 = 0, dw = 0, part = 0;
+    auto take = [&](size_t floats) { const size_t at = off; off += align_up(floats * 4) / 4; return at; };
+    int cur = -1;
+    for (int i = 0; i < n_layers; ++i) {
+        const rnnt_encoder_layer &l = layers[i];
+        const size_t M = (size_t)N * T.P.Lout[i], act = M * pad4(l.cout);
+        const bool res = l.role == RNNT_ENC_ROLE_RESIDUAL, gelu = !is_1x1(l);
+        T.in_of[i] = cur;
+        T.off_o[i] = i != n_layers - 1 && !res ? take(act) : NOT_KEPT;
+        T.off_z[i] = gelu ? take(act) : NOT_KEPT;
+        T.off_xh[i] = l.norm != RNNT_ENC_NORM_NONE ? take(act) : NOT_KEPT;
+        T.off_rstd[i] = l.norm == RNNT_ENC_NORM_INSTANCE ? take((size_t)N * l.cout) : NOT_KEPT;
+        if (!res) cur = i;
+        dy = act > dy ? act : dy;
+        if ((l.role & RNNT_ENC_ROLE_LAST) && act > dres) dres = act;
+        const size_t p3 = (size_t)3 * N * l.cout;
+        part = p3 > part ? p3 : part;
+        T.dx_split[i] = 0;
+        if (!reads_input(layers, i)) {
+            const long Min = (long)N * T.P.Lin[i];
+            if (Min > 65535L * 32) return fail(RNNT_ERR_UNSUPPORTED, "N * L too large");
+            const long wgs = ((l.cin + 127) / 128) * ((Min + 31) / 32);
+            long ts = (ENC_MFMA_WGS + wgs - 1) / wgs;
+            ts = ts > l.taps ? l.taps : ts;
+            ts = ts > ENC_MFMA_SPLITS ? ENC_MFMA_SPLITS : ts;
+            T.dx_split[i] = (int)ts;
+            const size_t s = (size_t)ts * Min * l.cin;
+            if (res) x2 = s > x2 ? s : x2; else x1 = s > x1 ? s : x1;
+        }
+        const long tiles = (long)((l.cin + 127) / 128) * ((l.cout + 127) / 128) * l.taps;
+        long R = (ENC_DW_WGS + tiles - 1) / tiles;
+        R = R > ENC_DW_RANGES ? ENC_DW_RANGES : R;
+        long rows = ((long)M + R - 1) / R;
+        rows = (rows + ENC_DW_STEP - 1) / ENC_DW_STEP * ENC_DW_STEP;
+        T.dw_rows[i] = (int)rows;
+        T.dw_ranges[i] = (int)(((long)M + rows - 1) / rows);
+        const size_t s = (size_t)T.dw_ranges[i] * l.taps * l.cout * l.cin;
+        dw = s > dw ? s : dw;
+    }
+    T.saved = off * 4;
+    T.dy = align_up(dy * 4) / 4; T.dres = align_up(dres * 4) / 4; T.x1 = align_up(x1 * 4) / 4; T.x2 = align_up(x2 * 4) / 4;
+    T.dw = align_up(dw * 4) / 4; T.part = align_up(part * 4) / 4;
+    const size_t fwd = (T.P.res + T.P.slab) * 4, bwd = (T.dy + T.dres + T.x1 + T.x2 + T.dw + T.part) * 4;
+    T.ws_fwd = fwd; T.ws_bwd = bwd;  // (the forward's depends on `regime`, the backward's does not)
+    return RNNT_OK;
+}
+
+// what both run entries check before anything is enqueued
+int check_train(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x, const int64_t xs[3],
+                const void *const *keep, const float *p, const void *io, const void *saved, size_t saved_bytes, const void *ws,
+                size_t ws_bytes, size_t ws_need, const TrainPlan &T)
+{
+    if (!packed || !x || !xs || !io || !saved || !ws) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument");
+    if (((uintptr_t)packed & 15) || ((uintptr_t)ws & 15) || ((uintptr_t)saved & 15) || ((uintptr_t)x & 3) || ((uintptr_t)io & 3))
+        return fail(RNNT_ERR_INVALID_ARG, "packed weights, saved and workspace must be 16-byte aligned, x and out / dout 4-byte");
+    if (saved_bytes < T.saved) return fail(RNNT_ERR_WORKSPACE, "saved %zu < required %zu bytes", saved_bytes, T.saved);
+    if (ws_bytes < ws_need) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, ws_need);
+    for (int i = 0; i < n_layers; ++i) {
+        const rnnt_encoder_layer &l = layers[i];
+        if (!l.bias) return fail(RNNT_ERR_INVALID_ARG, "layer %d: null bias", i);
+        if (l.norm == RNNT_ENC_NORM_BATCH && (!l.mean || !l.var)) return fail(RNNT_ERR_INVALID_ARG, "layer %d: batch norm without running statistics", i);
+        if (p && !(p[i] >= 0.f && p[i] < 1.f)) return fail(RNNT_ERR_INVALID_ARG, "layer %d: dropout p=%g outside [0, 1)", i, (double)p[i]);
+        if (keep && keep[i] && is_1x1(l)) return fail(RNNT_ERR_INVALID_ARG, "layer %d: a keep mask on a residual / final layer", i);
+    }
+    return RNNT_OK;
+}
+
+EncSrc train_src(const rnnt_encoder_layer *layers, const TrainPlan &T, int i, const float *x, const int64_t xs[3], int L,
+                 const float *saved, bool *vec)
+{
+    const rnnt_encoder_layer &l = layers[i];
+    EncSrc s;
+    s.st = nullptr; s.slen = T.lead[i]; s.C = l.cin;
+    const int from = T.in_of[i];
+    if (from < 0) {
+        s.x = x; s.xn = (long)xs[0]; s.xc = (long)xs[1]; s.xt = (long)xs[2]; s.xlen = L;
+        *vec = xs[1] == 1 && xs[0] % 4 == 0 && xs[2] % 4 == 0 && ((uintptr_t)x & 15) == 0;
+    } else {
+        const long ld = pad4(l.cin);
+        s.x = saved + T.off_o[from]; s.xn = (long)T.P.Lout[from] * ld; s.xc = 1; s.xt = ld; s.xlen = T.P.Lout[from];
+        *vec = true;
+    }
+    return s;
+}
+
+int train_fwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x, const int64_t xs[3], int N, int L,
+              const int32_t *lead, const void *const *keep, const float *p, int regime, float *out, void *saved_v, size_t saved_bytes,
+              void *ws, size_t ws_bytes, void *stream)
+{
+    if (int rc = check_layers(layers, n_layers)) return rc;
+    TrainPlan T;
+    if (int rc = make_train_plan(layers, n_layers, N, L, lead, regime, T)) return rc;
+    if (int rc = check_train(layers, n_layers, packed, x, xs, keep, p, out, saved_v, saved_bytes, ws, ws_bytes, T.ws_fwd, T)) return rc;
+    const Plan &P = T.P;
+    hipStream_t st = (hipStream_t)stream;
+    float *saved = (float *)saved_v, *res = (float *)ws, *slabs = res + P.res;
+    const float *wp = (const float *)packed;
+    for (int i = 0; i < n_layers; ++i) {
+        const rnnt_encoder_layer &l = layers[i];
+        const int Lout = P.Lout[i], cinp = pad4(l.cin);
+        EncConv c;
+        bool vec;
+        c.src = train_src(layers, T, i, x, xs, L, saved, &vec);
+        c.wp = wp; c.cinp = cinp; c.cout = l.cout; c.taps = l.taps; c.stride = l.stride; c.dil = l.dilation;
+        c.N = N; c.Lout = Lout; c.slabs = slabs; c.tsplit = P.tsplit[i]; c.xvec = vec;
+        if (P.few[i])
+            hipLaunchKernelGGL(k_enc_conv_few, dim3((l.cout + 63) / 64, (cinp + 63) / 64, P.tsplit[i]), dim3(256), 0, st, c);
+        else
+            hipLaunchKernelGGL(k_enc_conv_mfma, dim3((l.cout + 127) / 128, (N * Lout + 31) / 32, P.tsplit[i]), dim3(256), 0, st, c);
+
+        const bool to_res = l.role == RNNT_ENC_ROLE_RESIDUAL, to_out = i == n_layers - 1;
+        auto at = [&](size_t off) { return off == NOT_KEPT ? nullptr : saved + off; };
+        EncNormT nm;
+        nm.slabs = slabs; nm.nsplit = P.nsplit[i];
+        nm.bias = (const float *)l.bias; nm.gamma = (const float *)l.gamma; nm.beta = (const float *)l.beta;
+        nm.mean = (const float *)l.mean; nm.var = (const float *)l.var; nm.norm = l.norm; nm.eps = l.eps;
+        nm.res = (l.role & RNNT_ENC_ROLE_LAST) ? res : nullptr; nm.ldres = pad4(l.cout);
+        nm.act = !is_1x1(l);
+        nm.keep = keep ? (const uint8_t *)keep[i] : nullptr;
+        nm.scale = 1.f / (1.f - (p ? p[i] : 0.f));
+        nm.out = to_out ? out : to_res ? res : at(T.off_o[i]);
+        nm.ldo = to_out ? l.cout : pad4(l.cout);
+        nm.z = at(T.off_z[i]); nm.xh = at(T.off_xh[i]); nm.rstd = at(T.off_rstd[i]); nm.lds = pad4(l.cout);
+        nm.N = N; nm.Lout = Lout; nm.cout = l.cout;
+        hipLaunchKernelGGL(k_enc_norm_train, dim3((unsigned)(N * ((l.cout + 15) / 16))), dim3(ENC_NORM_THREADS), 0, st, nm);
+        wp += packed_floats(l);
+    }
+    return status("rnnt_engine_encoder_train_fwd");
+}
+
+int train_bwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x, const int64_t xs[3], int N, int L,
+              const int32_t *lead, const void *const *keep, const float *p, const float *dout, const void *saved_v, size_t saved_bytes,
+              const rnnt_encoder_grads *grads, void *ws, size_t ws_bytes, void *stream)
+{
+    if (int rc = check_layers(layers, n_layers)) return rc;
+    TrainPlan T;
+    if (int rc = make_train_plan(layers, n_layers, N, L, lead, RNNT_ENC_REGIME_AUTO, T)) return rc;
+    if (int rc = check_train(layers, n_layers, packed, x, xs, keep, p, dout, saved_v, saved_bytes, ws, ws_bytes, T.ws_bwd, T)) return rc;
+    if (!grads) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument");
+    for (int i = 0; i < n_layers; ++i)
+        if (layers[i].norm == RNNT_ENC_NORM_NONE && (grads[i].gamma || grads[i].beta))
+            return fail(RNNT_ERR_INVALID_ARG, "layer %d: a gamma / beta gradient asked of a layer without a norm", i);
+    const Plan &P = T.P;
+    hipStream_t st = (hipStream_t)stream;
+    const float *saved = (const float *)saved_v;
+    float *dy = (float *)ws, *dres = dy + T.dy, *x1 = dres + T.dres, *x2 = x1 + T.x1, *dws = x2 + T.x2, *part = dws + T.dw;
+    const float *wt[RNNT_ENC_MAX_LAYERS];  // the dX tables lie behind the forward's
+    {
+        const float *w = (const float *)packed;
+        for (int i = 0; i < n_layers; ++i) w += packed_floats(layers[i]);
+        for (int i = 0; i < n_layers; ++i) { wt[i] = w; w += packed_t_floats(layers[i]); }
+    }
+    auto at = [&](size_t off) { return off == NOT_KEPT ? nullptr : saved + off; };
+    for (int i = n_layers - 1; i >= 0; --i) {
+        const rnnt_encoder_layer &l = layers[i];
+        const int Lout = P.Lout[i];
+        const long M = (long)N * Lout, ldp = pad4(l.cout);
+        const bool is_res = l.role == RNNT_ENC_ROLE_RESIDUAL;
+        EncNormB nb;
+        nb.b = {nullptr, 0, 0, 0};
+        if (i == n_layers - 1) {
+            nb.a = {dout, 1, 0, l.cout};
+        } else if (is_res) {
+            nb.a = {dres, 1, 0, ldp};
+        } else {  // the dx of the layer(s) that read this output: the next layer, or a block's first layer and its residual 1x1
+            const int j = layers[i + 1].role == RNNT_ENC_ROLE_RESIDUAL ? i + 2 : i + 1;
+            nb.a = {x1, T.dx_split[j], M * l.cout, l.cout};
+            if (j == i + 2) nb.b = {x2, T.dx_split[i + 1], M * l.cout, l.cout};
+        }
+        nb.keep = keep ? (const uint8_t *)keep[i] : nullptr;
+        nb.scale = 1.f / (1.f - (p ? p[i] : 0.f));
+        nb.z = at(T.off_z[i]); nb.act = !is_1x1(l);
+        nb.xh = at(T.off_xh[i]); nb.rstd = at(T.off_rstd[i]);
+        nb.gamma = (const float *)l.gamma; nb.var = (const float *)l.var; nb.norm = l.norm; nb.eps = l.eps; nb.lds = ldp;
+        nb.dy = dy; nb.ldy = ldp;
+        nb.dres = (l.role & RNNT_ENC_ROLE_LAST) ? dres : nullptr; nb.ldres = ldp;
+        nb.part = part; nb.N = N; nb.Lout = Lout; nb.cout = l.cout;
+        hipLaunchKernelGGL(k_enc_bwd_norm, dim3((unsigned)(N * ((l.cout + 15) / 16))), dim3(ENC_NORM_THREADS), 0, st, nb);
+
+        const rnnt_encoder_grads &g = grads[i];
+        bool vec;
+        if (g.weight) {
+            EncDW d;
+            d.src = train_src(layers, T, i, x, xs, L, saved, &vec);
+            d.dy = dy; d.ldy = ldp; d.cout = l.cout; d.taps = l.taps; d.stride = l.stride; d.dil = l.dilation; d.N = N; d.Lout = Lout;
+            d.slabs = dws; d.ranges = T.dw_ranges[i]; d.rows = T.dw_rows[i];
+            hipLaunchKernelGGL(k_enc_dw, dim3((unsigned)(l.taps * d.ranges), (l.cin + 127) / 128, (l.cout + 127) / 128), dim3(256), 0, st, d);
+        }
+        if (g.weight || g.bias || g.gamma || g.beta) {
+            EncSumB s;
+            const long per = (long)l.taps * l.cout * l.cin;
+            s.slabs = dws; s.ranges = T.dw_ranges[i]; s.taps = l.taps; s.cout = l.cout; s.cin = l.cin;
+            s.dw = (float *)g.weight; s.nb_w = g.weight ? (int)((per + 255) / 256) : 0;
+            s.part = part; s.N = N;
+            s.dst[0] = (float *)g.gamma; s.dst[1] = (float *)g.beta; s.dst[2] = (float *)g.bias;
+            hipLaunchKernelGGL(k_enc_bwd_sum, dim3((unsigned)(s.nb_w + (3 * l.cout + 255) / 256)), dim3(256), 0, st, s);
+        }
+        if (T.dx_split[i]) {  // dx = conv of dy, span - lead zero frames in front and zeros behind its last frame, with the reversed taps
+            const int Lin = P.Lin[i];
+            EncConv c;
+            c.src.st = nullptr; c.src.slen = (l.taps - 1) * l.dilation - T.lead[i];
+            c.src.x = dy; c.src.xn = (long)Lout * ldp; c.src.xc = 1; c.src.xt = ldp; c.src.xlen = Lout; c.src.C = l.cout;
+            c.wp = wt[i]; c.cinp = (int)ldp; c.cout = l.cin; c.taps = l.taps; c.stride = 1; c.dil = l.dilation;
+            c.N = N; c.Lout = Lin; c.slabs = is_res ? x2 : x1; c.tsplit = T.dx_split[i]; c.xvec = 1;
+            hipLaunchKernelGGL(k_enc_conv_mfma, dim3((l.cin + 127) / 128, (unsigned)(((long)N * Lin + 31) / 32), T.dx_split[i]), dim3(256), 0, st, c);
+        }
+    }
+    return status("rnnt_engine_encoder_train_bwd");
+}
+
 }  // namespace
 
 extern "C" {
@@ -603,6 +1167,75 @@ int rnnt_engine_encoder_stream_push(const rnnt_encoder_layer *layers, int n_laye
     if (!state_in_lens) return fail(RNNT_ERR_INVALID_ARG, "null state argument");
     return run("rnnt_engine_encoder_stream_push", layers, n_layers, packed, x, x_strides, N, L, state_in, state_in_lens, state_out,
                state_out_lens, regime, out, workspace, ws_bytes, stream);
+}
+
+int rnnt_engine_encoder_train_packed_bytes(const rnnt_encoder_layer *layers, int n_layers, size_t *out)
+{
+    if (!out) return fail(RNNT_ERR_INVALID_ARG, "null output pointer");
+    if (int rc = check_layers(layers, n_layers)) return rc;
+    size_t n = 0;
+    for (int i = 0; i < n_layers; ++i) n += packed_floats(layers[i]) + packed_t_floats(layers[i]);
+    *out = n * 4;
+    return RNNT_OK;
+}
+
+int rnnt_engine_encoder_train_pack(const rnnt_encoder_layer *layers, int n_layers, void *packed, size_t packed_bytes, void *stream)
+{
+    size_t need = 0, fwd = 0;
+    if (int rc = rnnt_engine_encoder_train_packed_bytes(layers, n_layers, &need)) return rc;
+    if (!packed || ((uintptr_t)packed & 15)) return fail(RNNT_ERR_INVALID_ARG, "null or not 16-byte aligned packed buffer");
+    if (packed_bytes < need) return fail(RNNT_ERR_WORKSPACE, "packed buffer %zu < required %zu bytes", packed_bytes, need);
+    if (int rc = rnnt_engine_encoder_packed_bytes(layers, n_layers, &fwd)) return rc;
+    if (int rc = rnnt_engine_encoder_pack(layers, n_layers, packed, fwd, stream)) return rc;  // the forward's tables come first
+    float *wp = (float *)packed + fwd / 4;
+    for (int i = 0; i < n_layers; ++i) {
+        const rnnt_encoder_layer &l = layers[i];
+        const long n = (long)l.taps * l.cin * pad4(l.cout);
+        hipLaunchKernelGGL(k_enc_pack_wt, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                           (const float *)l.weight, wp, l.cout, l.cin, pad4(l.cout), l.taps);
+        wp += packed_t_floats(l);
+    }
+    return status("rnnt_engine_encoder_train_pack");
+}
+
+int rnnt_engine_encoder_train_saved_bytes(const rnnt_encoder_layer *layers, int n_layers, int N, int L, const int32_t *lead,
+                                          size_t *out)
+{
+    if (!out) return fail(RNNT_ERR_INVALID_ARG, "null output pointer");
+    if (int rc = check_layers(layers, n_layers)) return rc;
+    TrainPlan T;
+    if (int rc = make_train_plan(layers, n_layers, N, L, lead, RNNT_ENC_REGIME_AUTO, T)) return rc;
+    *out = T.saved;
+    return RNNT_OK;
+}
+
+int rnnt_engine_encoder_train_workspace_bytes(const rnnt_encoder_layer *layers, int n_layers, int N, int L, int regime,
+                                              const int32_t *lead, size_t *out)
+{
+    if (!out) return fail(RNNT_ERR_INVALID_ARG, "null output pointer");
+    if (int rc = check_layers(layers, n_layers)) return rc;
+    TrainPlan T;
+    if (int rc = make_train_plan(layers, n_layers, N, L, lead, regime, T)) return rc;
+    *out = T.ws_fwd > T.ws_bwd ? T.ws_fwd : T.ws_bwd;
+    return RNNT_OK;
+}
+
+int rnnt_engine_encoder_train_fwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x,
+                                  const int64_t x_strides[3], int N, int L, const int32_t *lead, const void *const *keep,
+                                  const float *p, int regime, float *out, void *saved, size_t saved_bytes, void *workspace,
+                                  size_t ws_bytes, void *stream)
+{
+    return train_fwd(layers, n_layers, packed, x, x_strides, N, L, lead, keep, p, regime, out, saved, saved_bytes, workspace, ws_bytes,
+                     stream);
+}
+
+int rnnt_engine_encoder_train_bwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x,
+                                  const int64_t x_strides[3], int N, int L, const int32_t *lead, const void *const *keep,
+                                  const float *p, const float *dout, const void *saved, size_t saved_bytes,
+                                  const rnnt_encoder_grads *grads, void *workspace, size_t ws_bytes, void *stream)
+{
+    return train_bwd(layers, n_layers, packed, x, x_strides, N, L, lead, keep, p, dout, saved, saved_bytes, grads, workspace, ws_bytes,
+                     stream);
 }
 
 }  // extern "C"

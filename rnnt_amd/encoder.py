@@ -11,10 +11,15 @@ or, for a model that is already built (the reference's own rnnt.jasper.AudioEnco
 
     model.encoder = rnnt_amd.AudioEncoder.from_module(model.encoder)     # shares the Parameters
 
-One definition, two paths.  The torch path is the module stated in plain torch: it is what trains (autograd), what runs on
-the CPU, in float64, with look-ahead (`additional_context`), and it is the oracle of the engine path.  The engine path is
-taken when gradients are off, the module is in eval(), input and parameters are fp32 tensors on a HIP device and no conv
-has look-ahead; `backend` ("auto" | "torch" | "engine") forces either, "engine" raises where it does not apply.
+One definition, two paths.  The torch path is the module stated in plain torch: it trains through autograd, runs on the
+CPU, in float64, streams with look-ahead (`additional_context`), and it is the oracle of the engine path.  The engine path
+is taken by backend "auto" when gradients are off, the module is in eval(), input and parameters are fp32 tensors on a HIP
+device and no conv has look-ahead; `backend` ("auto" | "torch" | "engine") forces either, "engine" raises where it does not
+apply.  Only backend "engine" goes further: whole-utterance calls with look-ahead, and — with grad mode on — TRAINING on
+the engine (C ABI rnnt_engine_encoder_train_*): a forward that keeps what the backward reads and a backward
+for every parameter, through a torch.autograd.Function.  The training path takes instance norm and batch norm on its
+running statistics (the BatchNorm1d modules in eval()), draws one uint8 keep mask per sub-block while a block's dropout is
+active, and refuses inputs that require grad, batch statistics and streamed pushes.  "auto" keeps grad-mode calls on torch.
 
 Definition.  A causal conv (kernel k, stride s, dilation d, P = (k-1)d - s + 1) reads X~ = P zeros (whole utterance) or the
 carried state (streaming) followed by the input; it gives (len(X~) - d(k-1) - 1) // s + 1 frames and leaves X~ from frame
@@ -50,6 +55,10 @@ ENGINE_AUTO_MAX_FRAMES = 224
 class _Layer(ctypes.Structure):  # include/rnnt_engine.h: rnnt_encoder_layer
     _fields_ = [(n, ctypes.c_int) for n in ("cin", "cout", "taps", "stride", "dilation", "norm", "role")] + [
         ("eps", ctypes.c_float)] + [(n, ctypes.c_void_p) for n in ("weight", "bias", "gamma", "beta", "mean", "var")]
+
+
+class _Grads(ctypes.Structure):  # include/rnnt_engine.h: rnnt_encoder_grads
+    _fields_ = [(n, ctypes.c_void_p) for n in ("weight", "bias", "gamma", "beta")]
 
 
 def _make_norm(norm_type, channels):
@@ -104,17 +113,26 @@ class JasperBlock(torch.nn.Module):
         self.residual_norm = _make_norm(norm_type, out_channels)
         self.dropout = torch.nn.Dropout(dropout)
 
-    def forward(self, x):
-        return _block_torch(self, x, None)[0]
+    def forward(self, x, keep_masks=None):
+        return _block_torch(self, x, None, keep_masks)[0]
 
     def streaming_forward(self, x, states):
         return _block_torch(self, x, states)
 
 
-def _block_torch(blk, x, states):
+def _drops(blk):
+    """The block's drop probability while its dropout is active (train() mode and p > 0), else 0."""
+    d = getattr(blk, "dropout", None)
+    return float(d.p) if isinstance(d, torch.nn.Dropout) and d.training and d.p > 0 else 0.0
+
+
+def _block_torch(blk, x, states, keeps=None):
+    """keeps: one keep mask (N, frames, channels) per sub-block, time-major like the engine's activations, used in place of
+    drawing while the block's dropout is active."""
     res = blk.residual_norm(blk.residual_conv(x))
     new_states = []
     last = len(blk.convs) - 1
+    p = _drops(blk)
     for i, (conv, norm) in enumerate(zip(blk.convs, blk.norms)):
         if states is None:
             x = conv(x)
@@ -124,12 +142,22 @@ def _block_torch(blk, x, states):
         x = norm(x)
         if i == last:
             x = x + res
-        x = blk.dropout(torch.nn.functional.gelu(x))
+        x = torch.nn.functional.gelu(x)
+        if keeps is not None and p > 0:
+            x = x * keeps[i].permute(0, 2, 1).to(x.dtype) / (1.0 - p)
+        else:
+            x = blk.dropout(x)
     return x, new_states
 
 
 def _is_causal(m):
     return isinstance(getattr(m, "conv", None), torch.nn.Conv1d) and hasattr(m, "left_padding")
+
+
+def _has_lookahead(holder):
+    conv = holder.conv
+    return (getattr(holder, "additional_context", 0) != 0 or
+            holder.left_padding != (conv.kernel_size[0] - 1) * conv.dilation[0] - conv.stride[0] + 1)
 
 
 def _is_block(m):
@@ -143,6 +171,64 @@ def _norm_kind(m):
     if isinstance(m, torch.nn.InstanceNorm1d):
         return NORM_INSTANCE, not m.track_running_stats
     return None, False
+
+
+class _EncoderTrainFn(torch.autograd.Function):
+    """rnnt_engine_encoder_train_fwd / _train_bwd.  Behind the bookkeeping arguments come the parameters, per layer
+    of the list: conv weight, conv bias and, where the norm is affine, norm weight and bias.  The `saved` block, the keep masks
+    and the packed tables of the forward are held for the backward; the input gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, enc, prep, packed, x, masks, drop, L_out, *params):
+        flat, arr = prep[0], prep[1]
+        dev, nl = x.device, len(flat)
+        N, _, L = x.shape
+        regime = {"auto": REGIME_AUTO, "many_rows": REGIME_MANY_ROWS}[enc.conv_regime]
+        lead = (ctypes.c_int32 * nl)(*[0 if h is None else h.left_padding for h, _, _, _ in flat])
+        keep = (ctypes.c_void_p * nl)(*[None if m is None else m.data_ptr() for m in masks])
+        p = (ctypes.c_float * nl)(*drop)
+        strides = (ctypes.c_int64 * 3)(*x.stride())
+        lib = engine.lib()
+        n = ctypes.c_size_t(0)
+        with torch.cuda.device(dev):
+            engine._check(lib.rnnt_engine_encoder_train_saved_bytes(arr, nl, N, L, lead, ctypes.byref(n)))
+            saved = torch.empty(max(256, int(n.value)), dtype=torch.uint8, device=dev)
+            engine._check(lib.rnnt_engine_encoder_train_workspace_bytes(arr, nl, N, L, regime, lead, ctypes.byref(n)))
+            ws = engine.workspace(dev, n.value)
+            out = torch.empty((N, L_out, flat[-1][1].out_channels), dtype=torch.float32, device=dev)
+            engine._check(lib.rnnt_engine_encoder_train_fwd(arr, nl, engine._p(packed), engine._p(x), strides, N, L, lead, keep, p, regime,
+                                                            engine._p(out), engine._p(saved), ctypes.c_size_t(saved.numel()),
+                                                            engine._p(ws), ctypes.c_size_t(ws.numel()), engine._stream(dev)))
+        ctx.call = (flat, arr, packed, x, masks, lead, keep, p, strides, regime, saved, params)
+        enc.last_saved_bytes = int(saved.numel())
+        return out.permute(0, 2, 1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        flat, arr, packed, x, masks, lead, keep, p, strides, regime, saved, params = ctx.call
+        dev, nl = x.device, len(flat)
+        N, _, L = x.shape
+        dout = grad_out.to(torch.float32).permute(0, 2, 1).contiguous()  # time-major once, like `out`
+        grads, out, k = (_Grads * nl)(), [], 0
+        needs = ctx.needs_input_grad[7:]
+        for G, (_, _, norm, _) in zip(grads, flat):
+            names = ("weight", "bias") + (("gamma", "beta") if norm is not None and norm.weight is not None else ())
+            for name in names:
+                g = torch.empty(params[k].shape, dtype=torch.float32, device=dev) if needs[k] else None
+                if g is not None:
+                    setattr(G, name, g.data_ptr())
+                out.append(g)
+                k += 1
+        lib = engine.lib()
+        n = ctypes.c_size_t(0)
+        with torch.cuda.device(dev):
+            engine._check(lib.rnnt_engine_encoder_train_workspace_bytes(arr, nl, N, L, regime, lead, ctypes.byref(n)))
+            ws = engine.workspace(dev, n.value)
+            engine._check(lib.rnnt_engine_encoder_train_bwd(arr, nl, engine._p(packed), engine._p(x), strides, N, L, lead, keep, p,
+                                                            engine._p(dout), engine._p(saved), ctypes.c_size_t(saved.numel()), grads,
+                                                            engine._p(ws), ctypes.c_size_t(ws.numel()), engine._stream(dev)))
+        return (None,) * 7 + tuple(out)
 
 
 class AudioEncoder(torch.nn.Module):
@@ -191,8 +277,10 @@ class AudioEncoder(torch.nn.Module):
 
     def _reset_cache(self):
         self._cache_key = None
-        self._cache = None  # (layer list, ctypes layer array, packed weights, layer index of each causal conv)
+        self._cache = None  # (layer list, ctypes layer array, packed weights, layer index of each causal conv, has look-ahead)
+        self._train_packed = None  # the training path's two tables (rnnt_engine_encoder_train_pack), under the same key
         self.last_backend = None  # "engine" | "torch": the path of the last call
+        self.last_saved_bytes = None  # bytes the last engine training forward kept for its backward
 
     # ------------------------------------------------------------------------------------------------- structure
     def _causal_convs(self):
@@ -205,9 +293,10 @@ class AudioEncoder(torch.nn.Module):
                 out.extend(m.convs)
         return out
 
-    def _flat(self):
+    def _flat(self, allow_lookahead=False):
         """The module as the engine's layer list: (conv holder or None, Conv1d, norm or None, role) in execution order, or a string
-        saying why the engine cannot take it."""
+        saying why the engine cannot take it.  Look-ahead is a reason unless `allow_lookahead` (whole-utterance calls under
+        backend "engine" carry it as each layer's `left_padding`)."""
         mods = list(self.blocks)
         out, i = [], 0
         while i < len(mods):
@@ -241,9 +330,12 @@ class AudioEncoder(torch.nn.Module):
                 return "a conv with padding, groups or no bias"
             if holder is None and (conv.kernel_size[0] != 1 or conv.stride[0] != 1):
                 return "a residual / output conv that is not 1x1"
-            if holder is not None and (getattr(holder, "additional_context", 0) != 0 or holder.left_padding !=
-                                       (conv.kernel_size[0] - 1) * conv.dilation[0] - conv.stride[0] + 1):
-                return "look-ahead (additional_context != 0)"
+            if holder is not None and _has_lookahead(holder):
+                if not allow_lookahead:
+                    return "look-ahead (additional_context != 0)"
+                if role != ROLE_PLAIN or any(holder is c for m in mods if _is_block(m) for c in m.convs):
+                    # (the torch path raises there as well, and so does the reference: x + residual on unequal lengths)
+                    return "look-ahead inside a JasperBlock: its sub-blocks lose frames, its residual branch keeps the input's length"
             if role not in (ROLE_PLAIN, ROLE_RESIDUAL, ROLE_FINAL) and conv.stride[0] != 1:
                 return "a strided conv inside a block"
             # the limits of rnnt_engine_encoder_* (RNNT_ERR_UNSUPPORTED there: such a module stays on the torch path)
@@ -320,20 +412,24 @@ class AudioEncoder(torch.nn.Module):
         """copy.deepcopy / pickle / torch.save(module): the engine cache (ctypes descriptors with raw pointers, the packed weights) is
         not part of the module's state; a copy builds its own on first engine use."""
         state = dict(self.__dict__)
-        state["_cache_key"] = state["_cache"] = None
+        state["_cache_key"] = state["_cache"] = state["_train_packed"] = None
         return state
 
-    def _use_engine(self, x, rows):
+    def _use_engine(self, x, rows, streaming=False):
         """The prepared engine state (layer list, descriptors, packed weights) when the engine path applies to this call, else None;
-        backend "engine" raises with the reason instead."""
+        backend "engine" raises with the reason instead.  With grad mode on the engine path is the training path (saved forward and
+        backward) and only backend "engine" takes it."""
         if self.backend not in ("auto", "torch", "engine"):
             raise ValueError(f"AudioEncoder.backend {self.backend!r}: 'auto', 'torch' or 'engine'")
         if self.backend == "torch":
             return None
         why = None
-        if torch.is_grad_enabled():
-            why = "grad mode is on"
-        elif self.training:
+        grad = torch.is_grad_enabled()
+        if grad and (self.backend == "auto" or streaming):
+            why = "grad mode is on"  # ("auto" keeps training on the torch path; a streamed push has no engine backward)
+        elif grad and x.requires_grad:
+            why = "the input requires grad (the engine's backward stops at the parameters)"
+        elif not grad and self.training:
             why = "the module is in train() mode"
         elif x.device.type != "cuda" or x.dtype != torch.float32:
             why = f"input is {x.dtype} on {x.device} (needs fp32 on a HIP device)"
@@ -347,21 +443,57 @@ class AudioEncoder(torch.nn.Module):
             prep = self._prepared(x.device)
             if isinstance(prep, str):
                 why = prep
+            elif prep[4] and (self.backend == "auto" or streaming):
+                why = "look-ahead (additional_context != 0)"
+            elif grad and any(isinstance(nm, torch.nn.BatchNorm1d) and nm.training for _, _, nm, _ in prep[0]):
+                why = "batch norm on batch statistics (a BatchNorm1d in train() mode; the engine trains through running statistics)"
         if why is not None:
             if self.backend == "engine":
                 raise RuntimeError(f"AudioEncoder(backend='engine'): the engine path does not apply: {why}")
             return None
         return prep
 
-    def forward(self, x):
+    def forward(self, x, keep_masks=None):
+        """`keep_masks` (test aid): one uint8 keep mask (N, frames, channels) — time-major, like the engine's activations — per
+        sub-block of every JasperBlock, in execution order, used instead of drawing while that block's dropout is active."""
         self._check_input(x)
         rows, L_out = self._lengths(x.shape[2], None)  # raises before anything is launched
+        if keep_masks is not None:
+            keep_masks = list(keep_masks)
+            want, si = [], 0
+            for m in self.blocks:
+                if _is_causal(m):
+                    si += 1
+                elif _is_block(m):
+                    for c in m.convs:
+                        want.append((x.shape[0], rows[si][2], c.conv.out_channels))
+                        si += 1
+            if [tuple(k.shape) for k in keep_masks] != want:
+                raise ValueError(f"AudioEncoder: keep_masks of shapes {[tuple(k.shape) for k in keep_masks]}, the blocks' layers give {want}")
         prep = self._use_engine(x, rows)
         if prep is None:
             self.last_backend = "torch"
-            return self.blocks(x)
+            return self._torch_forward(x, keep_masks)
         self.last_backend = "engine"
+        if torch.is_grad_enabled():
+            return self._engine_train(prep, x, keep_masks, rows, L_out)
+        if prep[4]:  # look-ahead: the push entry with left_padding zero frames of state per conv; the states it leaves are dropped
+            state = [torch.zeros((x.shape[0], h.conv.in_channels, h.left_padding), dtype=torch.float32, device=x.device)
+                     for h in self._causal_convs()]
+            return self._engine_call(prep, x, state, rows, L_out)[0]
         return self._engine_call(prep, x, None, rows, L_out)[0]
+
+    def _torch_forward(self, x, keep_masks):
+        if keep_masks is None:
+            return self.blocks(x)
+        at = 0
+        for m in self.blocks:
+            if _is_block(m):
+                x = _block_torch(m, x, None, keep_masks[at:at + len(m.convs)])[0]
+                at += len(m.convs)
+            else:
+                x = m(x)
+        return x
 
     def streaming_forward(self, x, state):
         self._check_input(x)
@@ -369,7 +501,7 @@ class AudioEncoder(torch.nn.Module):
         if len(state) != n_state:
             raise ValueError(f"AudioEncoder.streaming_forward: {len(state)} state tensors for {n_state} causal convs")
         rows, L_out = self._lengths(x.shape[2], [int(s.shape[2]) for s in state])  # raises with `state` untouched
-        prep = self._use_engine(x, rows)
+        prep = self._use_engine(x, rows, streaming=True)
         if prep is None:
             self.last_backend = "torch"
             return self._stream_torch(x, state)
@@ -399,13 +531,14 @@ class AudioEncoder(torch.nn.Module):
         block's own module lists were edited in place."""
         self._cache_key = None
         self._cache = None
+        self._train_packed = None
 
     def _prepared(self, dev):
         """(layer list, ctypes layer array, packed weights, [layer index of each causal conv]) — or why the engine cannot take the
         module.  Built on first use; the weights are packed again whenever a conv weight's storage or `_version` changed (an
         optimizer step, load_state_dict, .to()); the other parameters are read through their pointers on every call."""
         struct = tuple(map(id, self.blocks))
-        flat = self._cache[0] if self._cache is not None and self._cache_key[0] == struct else self._flat()
+        flat = self._cache[0] if self._cache is not None and self._cache_key[0] == struct else self._flat(allow_lookahead=True)
         if isinstance(flat, str):
             return flat
         key = []
@@ -432,20 +565,69 @@ class AudioEncoder(torch.nn.Module):
                 L.gamma, L.beta = ptr(norm.weight), ptr(norm.bias)
                 if L.norm == NORM_BATCH:
                     L.mean, L.var = ptr(norm.running_mean), ptr(norm.running_var)
-        lib = engine.lib()
-        n = ctypes.c_size_t(0)
-        with torch.cuda.device(dev):
-            engine._check(lib.rnnt_engine_encoder_packed_bytes(arr, len(flat), ctypes.byref(n)))
-            packed = torch.empty(int(n.value), dtype=torch.uint8, device=dev)
-            engine._check(lib.rnnt_engine_encoder_pack(arr, len(flat), engine._p(packed), ctypes.c_size_t(packed.numel()),
-                                                       engine._stream(dev)))
         causal = [i for i, (holder, _, _, _) in enumerate(flat) if holder is not None]
-        self._cache_key, self._cache = key, (flat, arr, packed, causal)
+        lookahead = any(holder is not None and _has_lookahead(holder) for holder, _, _, _ in flat)
+        # the packed tables (entry 2: inference; _train_packed: training) are built by the first call that reads them (_packed)
+        self._cache_key, self._cache, self._train_packed = key, [flat, arr, None, causal, lookahead], None
         return self._cache
 
-    def _engine_call(self, prep, x, state, rows, L_out):
-        flat, arr, packed, causal = prep
+    def _packed(self, prep, dev, train=False):
+        """The inference tables (rnnt_engine_encoder_pack) or the training path's two (rnnt_engine_encoder_train_pack) of the
+        prepared state, packed on first use; _prepared drops both when a conv weight's `_version` or storage changed."""
+        have = self._train_packed if train else prep[2]
+        if have is not None:
+            return have
+        flat, arr = prep[0], prep[1]
+        lib = engine.lib()
+        size, pack = ((lib.rnnt_engine_encoder_train_packed_bytes, lib.rnnt_engine_encoder_train_pack) if train else
+                      (lib.rnnt_engine_encoder_packed_bytes, lib.rnnt_engine_encoder_pack))
+        n = ctypes.c_size_t(0)
+        with torch.cuda.device(dev):
+            engine._check(size(arr, len(flat), ctypes.byref(n)))
+            packed = torch.empty(int(n.value), dtype=torch.uint8, device=dev)
+            engine._check(pack(arr, len(flat), engine._p(packed), ctypes.c_size_t(packed.numel()), engine._stream(dev)))
+        if train:
+            self._train_packed = packed
+        else:
+            prep[2] = packed
+        return packed
+
+    def _engine_train(self, prep, x, keep_masks, rows, L_out):
+        """The training path: draws the keep masks (or takes the given ones) and runs _EncoderTrainFn over the parameters."""
+        flat = prep[0]
         dev = x.device
+        drop, sub = [], []  # per layer of the list: its block's drop probability while that dropout is active; is a sub-block
+        for m in self.blocks:
+            if _is_block(m):
+                drop += [0.0] + [_drops(m)] * len(m.convs)
+                sub += [False] + [True] * len(m.convs)
+            elif _is_causal(m) or isinstance(m, torch.nn.Conv1d):
+                drop.append(0.0)
+                sub.append(False)
+        assert len(drop) == len(flat)
+        row_of = {li: si for si, li in enumerate(prep[3])}
+        masks, k = [None] * len(flat), 0
+        for i, (_, conv, _, _) in enumerate(flat):
+            if not sub[i]:
+                continue
+            if drop[i] > 0.0:
+                if keep_masks is not None:
+                    masks[i] = keep_masks[k].to(device=dev, dtype=torch.uint8).contiguous()
+                else:
+                    shape = (x.shape[0], rows[row_of[i]][2], conv.out_channels)
+                    masks[i] = (torch.rand(shape, device=dev) >= drop[i]).to(torch.uint8)
+            k += 1
+        params = []
+        for _, conv, norm, _ in flat:
+            params += [conv.weight, conv.bias]
+            if norm is not None and norm.weight is not None:
+                params += [norm.weight, norm.bias]
+        return _EncoderTrainFn.apply(self, prep, self._packed(prep, dev, train=True), x, masks, drop, L_out, *params)
+
+    def _engine_call(self, prep, x, state, rows, L_out):
+        flat, arr, _, causal, _ = prep
+        dev = x.device
+        packed = self._packed(prep, dev)
         N, _, L = x.shape
         nl = len(flat)
         regime = {"auto": REGIME_AUTO, "many_rows": REGIME_MANY_ROWS}[self.conv_regime]

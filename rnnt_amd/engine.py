@@ -126,6 +126,12 @@ SIGNATURES = {
     "rnnt_engine_encoder_workspace_bytes": "piiiipp",
     "rnnt_engine_encoder_fwd": "pipppiiippzp",
     "rnnt_engine_encoder_stream_push": "pipppiippppippzp",
+    "rnnt_engine_encoder_train_packed_bytes": "pip",
+    "rnnt_engine_encoder_train_pack": "pipzp",
+    "rnnt_engine_encoder_train_saved_bytes": "piiipp",
+    "rnnt_engine_encoder_train_workspace_bytes": "piiiipp",
+    "rnnt_engine_encoder_train_fwd": "pipppiipppippzpzp",
+    "rnnt_engine_encoder_train_bwd": "pipppiipppppzppzp",
     "rnnt_engine_featurizer_basis_bytes": "pp",
     "rnnt_engine_featurizer_pack": "pppzp",
     "rnnt_engine_featurizer_workspace_bytes": "piip",
@@ -178,6 +184,8 @@ EXPORTS = (
     "rnnt_engine_loss_fwd_bwd_restrict", "rnnt_engine_joint_loss_fwd_bwd_restrict", "rnnt_engine_joint_loss_fwd_restrict",
     "rnnt_engine_encoder_packed_bytes", "rnnt_engine_encoder_pack", "rnnt_engine_encoder_workspace_bytes",
     "rnnt_engine_encoder_fwd", "rnnt_engine_encoder_stream_push",
+    "rnnt_engine_encoder_train_packed_bytes", "rnnt_engine_encoder_train_pack", "rnnt_engine_encoder_train_saved_bytes",
+    "rnnt_engine_encoder_train_workspace_bytes", "rnnt_engine_encoder_train_fwd", "rnnt_engine_encoder_train_bwd",
     "rnnt_engine_featurizer_basis_bytes", "rnnt_engine_featurizer_pack", "rnnt_engine_featurizer_workspace_bytes",
     "rnnt_engine_featurizer_fwd", "rnnt_engine_featurizer_stream_push",
     "rnnt_engine_lstm_predictor_saved_bytes", "rnnt_engine_lstm_predictor_workspace_bytes",
