@@ -934,7 +934,7 @@ int rnnt_engine_encoder_stream_push(const rnnt_encoder_layer *layers, int n_laye
  * _train_bwd.  `regime` picks the forward's conv kernel as above; the backward always runs the MFMA kernels.
  * Limits beside the inference entries': a layer behind the list's first (first two, where the list opens with a block) has
  * stride 1 (RNNT_ERR_UNSUPPORTED: dX exists for stride 1 only); N * frames in of every such layer <= 65535 * 32.
- * Launches per layer: forward 2 (conv, k_enc_norm_train); backward 4 (k_enc_bwd_norm, k_enc_dw, k_enc_bwd_sum, the dX conv), 3
+ * Launches per layer: forward 2 (conv, k_enc_norm<true>); backward 4 (k_enc_bwd_norm, k_enc_dw, k_enc_bwd_sum, the dX conv), 3
  * where the layer reads the list's input.  No atomics; every sum has a fixed order: results are bitwise reproducible.
  * Everything is checked before anything is enqueued.
  */

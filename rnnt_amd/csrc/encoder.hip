@@ -1,6 +1,6 @@
 // encoder.hip — the Jasper AudioEncoder's inference forward (reference rnnt/jasper.py, rnnt/causalconv.py) on the device:
 // whole utterances and streaming pushes.  Every layer is  causal conv -> [norm] -> [+ residual] -> [GELU]  and runs as two
-// launches: a convolution kernel that leaves fp32 partial sums in slabs, and k_enc_norm, which adds the slabs up in a
+// launches: a convolution kernel that leaves fp32 partial sums in slabs, and k_enc_norm<false>, which adds the slabs up in a
 // fixed order and does everything else (bias, norm, residual, GELU, time-major store, the conv's next streaming state).
 //
 // The conv input X~ (N, C, len) is never built: it is `slen` frames of state (N, C, slen) — zeros for a whole utterance —
@@ -19,8 +19,8 @@
 //                    generalised to stride and dilation: v_mfma_f32_32x32x2_f32, exact fp32 products, the four waves split the
 //                    contraction and add their tiles up through LDS in wave order.
 // No atomics anywhere: the same inputs give the same bits.
-// The second half of the file is the encoder's TRAINING (rnnt_engine_encoder_train_*): the same conv kernels, an epilogue that also
-// saves what the backward reads, and the backward's kernels; see "training" below.
+// The second half of the file is the encoder's TRAINING (rnnt_engine_encoder_train_*): the same conv kernels, the same epilogue
+// instantiated as k_enc_norm<true>, which also saves what the backward reads, and the backward's kernels; see "training" below.
 #include "../../include/rnnt_engine.h"
 
 #include <cstdint>
@@ -231,11 +231,46 @@ __global__ __launch_bounds__(256) void k_enc_conv_mfma(EncConv a)
     }
 }
 
+// ---- the two sums every epilogue and k_enc_bwd_norm share.  v + s[0] + s[step] + .. + s[(n-1) step], added in index order, AHEAD
+// slabs requested together: eight, but one in k_enc_norm<true>, which sees at most ENC_MFMA_SPLITS slabs and where eight loads in
+// flight cost the registers that let two workgroups share a CU (80 VGPRs against 35).
+template <int AHEAD = 8>
+__device__ __forceinline__ float enc_slab_sum(float v, const float *s, int n, long step)
+{
+    int k = 0;
+    for (; AHEAD > 1 && k + AHEAD <= n; k += AHEAD) {
+        float p[AHEAD];
+#pragma unroll
+        for (int e = 0; e < AHEAD; ++e) p[e] = s[(long)(k + e) * step];
+#pragma unroll
+        for (int e = 0; e < AHEAD; ++e) v += p[e];
+    }
+    for (; k < n; ++k) v += s[(long)k * step];
+    return v;
+}
+
+// the 64 frame lanes' partial sums of this thread's channel (tid & 15), in lane order; every thread of the workgroup calls it, and
+// red[] is free again when it returns
+__device__ __forceinline__ float enc_lane_sum(float s)
+{
+    __shared__ float red[ENC_NORM_THREADS];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    float r = 0.f;
+    for (int k = 0; k < ENC_NORM_LANES; ++k) r += red[16 * k + (threadIdx.x & 15)];
+    __syncthreads();
+    return r;
+}
+
 // ---- everything after the products.  Blocks 0 .. nb_norm-1: block (channel group of 16, batch entry n), thread (channel
 // tid & 15, frame lane tid >> 4 of 64): v = bias + the slabs in index order; instance norm: mean, then the biased variance about that
 // mean (two passes over the frames of this call, partial sums combined in lane order); batch norm: the running statistics;
-// gamma / beta; + residual; GELU; store time-major.  Blocks behind those: the conv's next streaming state, X~ from frame
-// Lout * stride on, into a buffer of its own (N, C, slen_out).
+// gamma / beta; + residual; GELU; store time-major.  One body, two instantiations that give the same `out` bit for bit:
+//   <false>  inference.  The conv output is parked in `out` between the passes.  Blocks behind nb_norm: the conv's next streaming
+//            state, X~ from frame Lout * stride on, into a buffer of its own (N, C, slen_out).
+//   <true>   training: whole utterances only (no state blocks).  Besides the layer's output it leaves z (the value in front of the
+//            GELU), xhat (the normalised conv output; the conv output is parked in its place) and, for instance norm, rstd per
+//            (n, channel); a keep mask [N][Lout][cout] (one byte per value) zeroes the output or scales it by `scale` = 1 / (1 - p).
 struct EncNorm {
     const float *slabs; int nsplit;
     const float *bias, *gamma, *beta, *mean, *var;
@@ -244,22 +279,26 @@ struct EncNorm {
     int act;
     float *out; long ldo;          // [N][Lout][ldo]
     int N, Lout, cout, nb_norm;
-    EncSrc src; float *state_out; int slen_out, stride;
+    EncSrc src; float *state_out; int slen_out, stride;  // <false> only
+    const uint8_t *keep; float scale;                    // <true> only, as the next line
+    float *z, *xh, *rstd; long lds;  // z, xhat [N][Lout][lds]; rstd [N][cout]; NULL where the layer keeps none
 };
 
+template <bool TRAIN>
 __global__ __launch_bounds__(ENC_NORM_THREADS) void k_enc_norm(EncNorm a)
 {
-    __shared__ float red[ENC_NORM_THREADS];
     const int tid = threadIdx.x;
-    if ((int)blockIdx.x >= a.nb_norm) {
-        const long idx = (long)((int)blockIdx.x - a.nb_norm) * ENC_NORM_THREADS + tid;
-        const long total = (long)a.N * a.src.C * a.slen_out;
-        if (idx >= total) return;
-        const int p = (int)(idx % a.slen_out);
-        const long nc = idx / a.slen_out;
-        const int c = (int)(nc % a.src.C), n = (int)(nc / a.src.C);
-        a.state_out[idx] = enc_src(a.src, n, c, a.Lout * a.stride + p);
-        return;
+    if constexpr (!TRAIN) {
+        if ((int)blockIdx.x >= a.nb_norm) {
+            const long idx = (long)((int)blockIdx.x - a.nb_norm) * ENC_NORM_THREADS + tid;
+            const long total = (long)a.N * a.src.C * a.slen_out;
+            if (idx >= total) return;
+            const int p = (int)(idx % a.slen_out);
+            const long nc = idx / a.slen_out;
+            const int c = (int)(nc % a.src.C), n = (int)(nc / a.src.C);
+            a.state_out[idx] = enc_src(a.src, n, c, a.Lout * a.stride + p);
+            return;
+        }
     }
     const int cl = tid & 15, tl = tid >> 4;
     const int cgroups = (a.cout + 15) / 16;
@@ -270,18 +309,10 @@ __global__ __launch_bounds__(ENC_NORM_THREADS) void k_enc_norm(EncNorm a)
     auto pre = [&](int t) {
         const float *s = a.slabs + (row0 + t) * a.cout + c;
         const long step = M * a.cout;
-        float v = s[0];
-        int k = 1;
-        for (; k + 8 <= a.nsplit; k += 8) {  // eight slabs requested together, added in index order
-            float p[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) p[e] = s[(long)(k + e) * step];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v += p[e];
-        }
-        for (; k < a.nsplit; ++k) v += s[(long)k * step];
-        return v + b;
+        return enc_slab_sum<TRAIN ? 1 : 8>(s[0], s + step, a.nsplit - 1, step) + b;
     };
+    float *const park = TRAIN ? a.xh : a.out;  // the conv output between the passes; each thread reads back what it wrote
+    const long ldp = TRAIN ? a.lds : a.ldo;
     float mu = 0.f, rstd = 1.f;
     const bool inst = a.norm == RNNT_ENC_NORM_INSTANCE;
     if (inst) {
@@ -289,26 +320,19 @@ __global__ __launch_bounds__(ENC_NORM_THREADS) void k_enc_norm(EncNorm a)
         if (ok)
             for (int t = tl; t < a.Lout; t += ENC_NORM_LANES) {
                 const float v = pre(t);
-                a.out[(row0 + t) * a.ldo + c] = v;  // parked; this thread reads it back below
+                park[(row0 + t) * ldp + c] = v;
                 s += v;
             }
-        red[tid] = s;
-        __syncthreads();
-        s = 0.f;
-        for (int k = 0; k < ENC_NORM_LANES; ++k) s += red[16 * k + cl];
-        mu = s / (float)a.Lout;
-        __syncthreads();
+        mu = enc_lane_sum(s) / (float)a.Lout;
         float q = 0.f;
         if (ok)
             for (int t = tl; t < a.Lout; t += ENC_NORM_LANES) {
-                const float d = a.out[(row0 + t) * a.ldo + c] - mu;
+                const float d = park[(row0 + t) * ldp + c] - mu;
                 q += d * d;
             }
-        red[tid] = q;
-        __syncthreads();
-        q = 0.f;
-        for (int k = 0; k < ENC_NORM_LANES; ++k) q += red[16 * k + cl];
-        rstd = 1.f / sqrtf(q / (float)a.Lout + a.eps);
+        rstd = 1.f / sqrtf(enc_lane_sum(q) / (float)a.Lout + a.eps);
+        if constexpr (TRAIN)
+            if (ok && tl == 0) a.rstd[(long)n * a.cout + c] = rstd;
     } else if (a.norm == RNNT_ENC_NORM_BATCH && ok) {
         mu = a.mean[c];
         rstd = 1.f / sqrtf(a.var[c] + a.eps);
@@ -317,28 +341,43 @@ __global__ __launch_bounds__(ENC_NORM_THREADS) void k_enc_norm(EncNorm a)
     const float g = a.norm != RNNT_ENC_NORM_NONE && a.gamma ? a.gamma[c] : 1.f;
     const float be = a.norm != RNNT_ENC_NORM_NONE && a.beta ? a.beta[c] : 0.f;
     for (int t = tl; t < a.Lout; t += ENC_NORM_LANES) {
-        float v = inst ? a.out[(row0 + t) * a.ldo + c] : pre(t);
-        if (a.norm != RNNT_ENC_NORM_NONE) v = (v - mu) * rstd * g + be;
-        if (a.res) v += a.res[(row0 + t) * a.ldres + c];
-        if (a.act) v = gelu_exact(v);
-        a.out[(row0 + t) * a.ldo + c] = v;
+        const long row = row0 + t;
+        float v = inst ? park[row * ldp + c] : pre(t);
+        if (a.norm != RNNT_ENC_NORM_NONE) {
+            v = (v - mu) * rstd;
+            if constexpr (TRAIN) a.xh[row * a.lds + c] = v;
+            v = v * g + be;
+        }
+        if (a.res) v += a.res[row * a.ldres + c];
+        if (a.act) {
+            if constexpr (TRAIN) a.z[row * a.lds + c] = v;
+            v = gelu_exact(v);
+        }
+        if constexpr (TRAIN)
+            if (a.keep) v = a.keep[row * a.cout + c] ? v * a.scale : 0.f;
+        a.out[row * a.ldo + c] = v;
     }
 }
 
-__global__ __launch_bounds__(256) void k_enc_pack_w(const float *__restrict__ w, float *__restrict__ wp, int out_c, int in_c,
-                                                    int in_p, int taps)
+// The packed tables, [tap][rows][cols rounded up to 4, zero filled].  The convs' table: rows = out channels, cols = in channels.
+// transposed: the dX conv's, k_enc_conv_mfma's layout with in and out exchanged and the taps reversed.
+__global__ __launch_bounds__(256) void k_enc_pack(const float *__restrict__ w, float *__restrict__ wp, int out_c, int in_c, int taps,
+                                                  int transposed)
 {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;  // walks the packed layout [tap][out][in_p]
-    if (idx >= (long)taps * out_c * in_p) return;
-    const int ci = (int)(idx % in_p);
-    const long to = idx / in_p;
-    const int co = (int)(to % out_c), t = (int)(to / out_c);
-    wp[idx] = ci < in_c ? w[((long)co * in_c + ci) * taps + t] : 0.f;
+    const int rows = transposed ? in_c : out_c, cols = transposed ? out_c : in_c, colp = (cols + 3) & ~3;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;  // walks the packed layout
+    if (idx >= (long)taps * rows * colp) return;
+    const int col = (int)(idx % colp);
+    const long tr = idx / colp;
+    const int r = (int)(tr % rows), t = (int)(tr / rows);
+    const int co = transposed ? col : r, ci = transposed ? r : col;
+    wp[idx] = col < cols ? w[((long)co * in_c + ci) * taps + (transposed ? taps - 1 - t : t)] : 0.f;
 }
+
 
 // =============================================================================================================== training
 // rnnt_engine_encoder_train_*: a forward that keeps what the backward reads, and the backward.  Per layer the
-// forward is the conv kernel above and k_enc_norm_train; the backward is k_enc_bwd_norm (dO -> dz -> dy, the per-entry partial
+// forward is the conv kernel above and k_enc_norm<true>; the backward is k_enc_bwd_norm (dO -> dz -> dy, the per-entry partial
 // sums of dgamma / dbeta / dbias, the copy of dz into the residual branch, the sum of the two dx of a block input), k_enc_dw (the
 // weight gradient's products, one slab per row range), k_enc_bwd_sum (slabs and partial sums added in index order, dW stored in
 // torch's [out][in][tap]) and, for every layer but those that read the list's input, k_enc_conv_mfma over dy with the second
@@ -350,90 +389,6 @@ constexpr int ENC_DW_STEP = 8;     // ... the rows of one pipeline step
 __device__ __forceinline__ float gelu_grad(float z)  // Phi(z) + z phi(z)
 {
     return 0.5f * (1.f + erff(z * 0.70710678118654752f)) + z * 0.3989422804014327f * expf(-0.5f * z * z);
-}
-
-// The training form of k_enc_norm: whole utterances only (no state blocks).  Besides the layer's output it leaves z (the value in
-// front of the GELU), xhat (the normalised conv output) and, for instance norm, rstd per (n, channel); a keep mask [N][Lout][cout]
-// (one byte per value) zeroes the output or scales it by `scale` = 1 / (1 - p).
-struct EncNormT {
-    const float *slabs; int nsplit;
-    const float *bias, *gamma, *beta, *mean, *var;
-    int norm; float eps;
-    const float *res; long ldres;
-    int act;
-    const uint8_t *keep; float scale;
-    float *out; long ldo;
-    float *z, *xh, *rstd; long lds;  // z, xhat [N][Lout][lds]; rstd [N][cout]; NULL where the layer keeps none
-    int N, Lout, cout;
-};
-
-__global__ __launch_bounds__(ENC_NORM_THREADS) void k_enc_norm_train(EncNormT a)
-{
-    __shared__ float red[ENC_NORM_THREADS];
-    const int tid = threadIdx.x, cl = tid & 15, tl = tid >> 4;
-    const int cgroups = (a.cout + 15) / 16;
-    const int n = (int)blockIdx.x / cgroups, c = ((int)blockIdx.x - n * cgroups) * 16 + cl;
-    const bool ok = c < a.cout;
-    const long M = (long)a.N * a.Lout, row0 = (long)n * a.Lout;
-    const float b = ok && a.bias ? a.bias[c] : 0.f;
-    auto pre = [&](int t) {
-        const float *s = a.slabs + (row0 + t) * a.cout + c;
-        const long step = M * a.cout;
-        float v = s[0];
-        for (int k = 1; k < a.nsplit; ++k) v += s[(long)k * step];  // index order, as k_enc_norm
-        return v + b;
-    };
-    float mu = 0.f, rstd = 1.f;
-    const bool inst = a.norm == RNNT_ENC_NORM_INSTANCE;
-    if (inst) {  // two passes, as k_enc_norm; the conv output is parked in xhat's place
-        float s = 0.f;
-        if (ok)
-            for (int t = tl; t < a.Lout; t += ENC_NORM_LANES) {
-                const float v = pre(t);
-                a.xh[(row0 + t) * a.lds + c] = v;
-                s += v;
-            }
-        red[tid] = s;
-        __syncthreads();
-        s = 0.f;
-        for (int k = 0; k < ENC_NORM_LANES; ++k) s += red[16 * k + cl];
-        mu = s / (float)a.Lout;
-        __syncthreads();
-        float q = 0.f;
-        if (ok)
-            for (int t = tl; t < a.Lout; t += ENC_NORM_LANES) {
-                const float d = a.xh[(row0 + t) * a.lds + c] - mu;
-                q += d * d;
-            }
-        red[tid] = q;
-        __syncthreads();
-        q = 0.f;
-        for (int k = 0; k < ENC_NORM_LANES; ++k) q += red[16 * k + cl];
-        rstd = 1.f / sqrtf(q / (float)a.Lout + a.eps);
-        if (ok && tl == 0) a.rstd[(long)n * a.cout + c] = rstd;
-    } else if (a.norm == RNNT_ENC_NORM_BATCH && ok) {
-        mu = a.mean[c];
-        rstd = 1.f / sqrtf(a.var[c] + a.eps);
-    }
-    if (!ok) return;
-    const float g = a.norm != RNNT_ENC_NORM_NONE && a.gamma ? a.gamma[c] : 1.f;
-    const float be = a.norm != RNNT_ENC_NORM_NONE && a.beta ? a.beta[c] : 0.f;
-    for (int t = tl; t < a.Lout; t += ENC_NORM_LANES) {
-        const long row = row0 + t;
-        float v = inst ? a.xh[row * a.lds + c] : pre(t);
-        if (a.norm != RNNT_ENC_NORM_NONE) {
-            const float xh = (v - mu) * rstd;
-            a.xh[row * a.lds + c] = xh;
-            v = xh * g + be;
-        }
-        if (a.res) v += a.res[row * a.ldres + c];
-        if (a.act) {
-            a.z[row * a.lds + c] = v;
-            v = gelu_exact(v);
-        }
-        if (a.keep) v = a.keep[row * a.cout + c] ? v * a.scale : 0.f;
-        a.out[row * a.ldo + c] = v;
-    }
 }
 
 // ---- dO -> dz -> dy of one layer.  Block (channel group of 16, batch entry n), thread (channel, frame lane), as k_enc_norm.
@@ -454,32 +409,19 @@ struct EncNormB {
 
 __global__ __launch_bounds__(ENC_NORM_THREADS) void k_enc_bwd_norm(EncNormB a)
 {
-    __shared__ float red[ENC_NORM_THREADS];
     const int tid = threadIdx.x, cl = tid & 15, tl = tid >> 4;
     const int cgroups = (a.cout + 15) / 16;
     const int n = (int)blockIdx.x / cgroups, c = ((int)blockIdx.x - n * cgroups) * 16 + cl;
     const bool ok = c < a.cout;
     const long row0 = (long)n * a.Lout;
-    auto lanes = [&](float s) {  // the 64 frame lanes' partial sums of this channel, in lane order
-        red[tid] = s;
-        __syncthreads();
-        float r = 0.f;
-        for (int k = 0; k < ENC_NORM_LANES; ++k) r += red[16 * k + cl];
-        __syncthreads();
-        return r;
-    };
     const bool normed = a.norm != RNNT_ENC_NORM_NONE;
     float s1 = 0.f, s2 = 0.f;
     if (ok)
         for (int t = tl; t < a.Lout; t += ENC_NORM_LANES) {
             const long row = row0 + t;
             const float *s = a.a.p + row * a.a.ld + c;
-            float v = s[0];
-            for (int k = 1; k < a.a.nsplit; ++k) v += s[(long)k * a.a.split];
-            if (a.b.p) {
-                s = a.b.p + row * a.b.ld + c;
-                for (int k = 0; k < a.b.nsplit; ++k) v += s[(long)k * a.b.split];
-            }
+            float v = enc_slab_sum(s[0], s + a.a.split, a.a.nsplit - 1, a.a.split);
+            if (a.b.p) v = enc_slab_sum(v, a.b.p + row * a.b.ld + c, a.b.nsplit, a.b.split);
             if (a.keep) v = a.keep[row * a.cout + c] ? v * a.scale : 0.f;
             if (a.act) v *= gelu_grad(a.z[row * a.lds + c]);
             a.dy[row * a.ldy + c] = v;  // dz, parked; this thread reads it back below
@@ -487,7 +429,7 @@ __global__ __launch_bounds__(ENC_NORM_THREADS) void k_enc_bwd_norm(EncNormB a)
             s1 += v;
             if (normed) s2 += v * a.xh[row * a.lds + c];
         }
-    const float S1 = lanes(s1), S2 = lanes(s2);
+    const float S1 = enc_lane_sum(s1), S2 = enc_lane_sum(s2);
     float s3 = 0.f;
     if (ok) {
         const float gam = normed && a.gamma ? a.gamma[c] : 1.f;
@@ -510,7 +452,7 @@ __global__ __launch_bounds__(ENC_NORM_THREADS) void k_enc_bwd_norm(EncNormB a)
             }
         }
     }
-    const float S3 = lanes(s3);
+    const float S3 = enc_lane_sum(s3);
     if (ok && tl == 0) {
         const long NC = (long)a.N * a.cout, at = (long)n * a.cout + c;
         a.part[at] = S2;
@@ -635,18 +577,6 @@ __global__ __launch_bounds__(256) void k_enc_bwd_sum(EncSumB a)
     a.dst[which][c] = v;
 }
 
-// the dX conv's table [tap reversed][in][out rounded up to 4, zero filled]: k_enc_conv_mfma's layout with in and out exchanged
-__global__ __launch_bounds__(256) void k_enc_pack_wt(const float *__restrict__ w, float *__restrict__ wp, int out_c, int in_c,
-                                                     int out_p, int taps)
-{
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)taps * in_c * out_p) return;
-    const int co = (int)(idx % out_p);
-    const long ti = idx / out_p;
-    const int ci = (int)(ti % in_c), t = (int)(ti / in_c);
-    wp[idx] = co < out_c ? w[((long)co * in_c + ci) * taps + (taps - 1 - t)] : 0.f;
-}
-
 // ---------------------------------------------------------------------------------------------------------------- host side
 #define fail engine_fail
 
@@ -707,7 +637,21 @@ int check_layers(const rnnt_encoder_layer *layers, int n_layers)
     return RNNT_OK;
 }
 
-size_t packed_floats(const rnnt_encoder_layer &l) { return align_up((size_t)l.taps * l.cout * pad4(l.cin) * 4) / 4; }
+// floats of one layer's packed table (k_enc_pack), a multiple of 256 bytes
+size_t packed_floats(const rnnt_encoder_layer &l, bool transposed)
+{
+    const int rows = transposed ? l.cin : l.cout, cols = transposed ? l.cout : l.cin;
+    return align_up((size_t)l.taps * rows * pad4(cols) * 4) / 4;
+}
+
+// tap ranges of an MFMA conv: aim for ENC_MFMA_WGS workgroups, at most `taps`, at most ENC_MFMA_SPLITS
+int mfma_tap_split(long rows, int cout, int taps)
+{
+    const long wgs = ((cout + 127) / 128) * ((rows + 31) / 32);
+    long ts = (ENC_MFMA_WGS + wgs - 1) / wgs;
+    ts = ts > taps ? taps : ts;
+    return (int)(ts > ENC_MFMA_SPLITS ? ENC_MFMA_SPLITS : ts);
+}
 
 // lengths, kernel choice and workspace of one call; state_lens NULL: whole utterance (every state is (taps-1)*dilation-stride+1 zeros)
 struct Plan {
@@ -755,11 +699,7 @@ int make_plan(const rnnt_encoder_layer *layers, int n_layers, int N, int L, cons
             P.tsplit[i] = ts;
             P.nsplit[i] = ((pad4(l.cin) + 63) / 64) * ts;
         } else {
-            const long wgs = ((l.cout + 127) / 128) * ((M + 31) / 32);
-            long ts = (ENC_MFMA_WGS + wgs - 1) / wgs;
-            ts = ts > l.taps ? l.taps : ts;
-            ts = ts > ENC_MFMA_SPLITS ? ENC_MFMA_SPLITS : ts;
-            P.tsplit[i] = P.nsplit[i] = (int)ts;
+            P.tsplit[i] = P.nsplit[i] = mfma_tap_split(M, l.cout, l.taps);
         }
         const size_t s = (size_t)P.nsplit[i] * M * l.cout;
         slab = s > slab ? s : slab;
@@ -781,14 +721,72 @@ int status(const char *what)
     return RNNT_OK;
 }
 
+// what the run entries check of their buffers (saved: the training entries') and of a layer's parameters
+int check_buffers(const void *packed, const float *x, const int64_t xs[3], const void *io, const void *ws, const void *saved, bool train)
+{
+    if (!packed || !x || !xs || !io || !ws || (train && !saved)) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument");
+    if (((uintptr_t)packed & 15) || ((uintptr_t)ws & 15) || ((uintptr_t)saved & 15) || ((uintptr_t)x & 3) || ((uintptr_t)io & 3))
+        return fail(RNNT_ERR_INVALID_ARG, train ? "packed weights, saved and workspace must be 16-byte aligned, x and out / dout 4-byte"
+                                                : "packed weights and workspace must be 16-byte aligned, x and out 4-byte");
+    return RNNT_OK;
+}
+
+int check_params(const rnnt_encoder_layer &l, int i)
+{
+    if (!l.bias) return fail(RNNT_ERR_INVALID_ARG, "layer %d: null bias", i);
+    if (l.norm == RNNT_ENC_NORM_BATCH && (!l.mean || !l.var)) return fail(RNNT_ERR_INVALID_ARG, "layer %d: batch norm without running statistics", i);
+    return RNNT_OK;
+}
+
+// Where a layer reads its chunk (the caller sets src.st / src.slen) and whether k_enc_conv_mfma may read its rows as float4:
+// the caller's x with its strides, or a time-major activation [N][len][ld] of the engine's own.
+struct EncIn { EncSrc src; bool vec; };
+
+EncIn caller_x(const float *x, const int64_t xs[3], int L, int C)
+{
+    return {{nullptr, 0, x, (long)xs[0], (long)xs[1], (long)xs[2], L, C},
+            xs[1] == 1 && xs[0] % 4 == 0 && xs[2] % 4 == 0 && ((uintptr_t)x & 15) == 0};
+}
+
+EncIn time_major(const float *p, long ld, int len, int C) { return {{nullptr, 0, p, (long)len * ld, 1, ld, len, C}, true}; }
+
+// the conv of `in` with the table wp [taps][cout][in's channels rounded up to 4] into `tsplit` slabs, and its launch
+EncConv conv_args(const EncIn &in, const float *wp, int cout, int taps, int stride, int dil, int N, int Lout, float *slabs, int tsplit)
+{
+    EncConv c;
+    c.src = in.src; c.wp = wp; c.cinp = pad4(in.src.C); c.cout = cout; c.taps = taps; c.stride = stride; c.dil = dil;
+    c.N = N; c.Lout = Lout; c.slabs = slabs; c.tsplit = tsplit; c.xvec = in.vec;
+    return c;
+}
+
+void launch_conv(const EncConv &c, bool few, hipStream_t st)
+{
+    if (few)
+        hipLaunchKernelGGL(k_enc_conv_few, dim3((c.cout + 63) / 64, (c.cinp + 63) / 64, c.tsplit), dim3(256), 0, st, c);
+    else
+        hipLaunchKernelGGL(k_enc_conv_mfma, dim3((c.cout + 127) / 128, (unsigned)(((long)c.N * c.Lout + 31) / 32), c.tsplit), dim3(256), 0, st, c);
+}
+
+// the epilogue of layer i into out [N][Lout][ldo], either instantiation's: the caller adds the state blocks or what training keeps
+EncNorm norm_args(const rnnt_encoder_layer &l, const Plan &P, int i, int N, const float *slabs, const float *res, float *out, long ldo)
+{
+    EncNorm nm = {};
+    nm.slabs = slabs; nm.nsplit = P.nsplit[i];
+    nm.bias = (const float *)l.bias; nm.gamma = (const float *)l.gamma; nm.beta = (const float *)l.beta;
+    nm.mean = (const float *)l.mean; nm.var = (const float *)l.var; nm.norm = l.norm; nm.eps = l.eps;
+    nm.res = (l.role & RNNT_ENC_ROLE_LAST) ? res : nullptr; nm.ldres = pad4(l.cout);
+    nm.act = !is_1x1(l);
+    nm.out = out; nm.ldo = ldo; nm.N = N; nm.Lout = P.Lout[i]; nm.cout = l.cout;
+    nm.nb_norm = N * ((l.cout + 15) / 16);
+    return nm;
+}
+
 int run(const char *what, const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x, const int64_t xs[3],
         int N, int L, void *const *state_in, const int32_t *state_in_lens, void *const *state_out, const int32_t *state_out_lens,
         int regime, float *out, void *ws, size_t ws_bytes, void *stream)
 {
     if (int rc = check_layers(layers, n_layers)) return rc;
-    if (!packed || !x || !xs || !out || !ws) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument");
-    if (((uintptr_t)packed & 15) || ((uintptr_t)ws & 15) || ((uintptr_t)x & 3) || ((uintptr_t)out & 3))
-        return fail(RNNT_ERR_INVALID_ARG, "packed weights and workspace must be 16-byte aligned, x and out 4-byte");
+    if (int rc = check_buffers(packed, x, xs, out, ws, nullptr, false)) return rc;
     const bool streaming = state_in_lens != nullptr;
     if (streaming && (!state_in || !state_out || !state_out_lens)) return fail(RNNT_ERR_INVALID_ARG, "null state argument");
     Plan P;
@@ -796,8 +794,7 @@ int run(const char *what, const rnnt_encoder_layer *layers, int n_layers, const 
     if (ws_bytes < P.total) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, P.total);
     for (int i = 0; i < n_layers; ++i) {
         const rnnt_encoder_layer &l = layers[i];
-        if (!l.bias) return fail(RNNT_ERR_INVALID_ARG, "layer %d: null bias", i);
-        if (l.norm == RNNT_ENC_NORM_BATCH && (!l.mean || !l.var)) return fail(RNNT_ERR_INVALID_ARG, "layer %d: batch norm without running statistics", i);
+        if (int rc = check_params(l, i)) return rc;
         if (streaming && !is_1x1(l)) {
             if (state_out_lens[i] != P.slen_out[i])
                 return fail(RNNT_ERR_INVALID_ARG, "layer %d: state_out length %d, this push leaves %d", i, state_out_lens[i], P.slen_out[i]);
@@ -810,55 +807,36 @@ int run(const char *what, const rnnt_encoder_layer *layers, int n_layers, const 
     float *w = (float *)ws;
     float *buf[2] = {w, w + P.act}, *res = w + 2 * P.act, *slabs = res + P.res;
     const float *wp = (const float *)packed;
-
-    struct Cur { const float *p; long sn, sc, stt; int len, C; bool vec; };
-    Cur cur = {x, (long)xs[0], (long)xs[1], (long)xs[2], L, layers[0].cin,
-               xs[1] == 1 && xs[0] % 4 == 0 && xs[2] % 4 == 0 && ((uintptr_t)x & 15) == 0};
+    EncIn cur = caller_x(x, xs, L, layers[0].cin);
     int flip = 0;
     for (int i = 0; i < n_layers; ++i) {
         const rnnt_encoder_layer &l = layers[i];
-        const int Lout = P.Lout[i], cinp = pad4(l.cin);
-        EncSrc src;
-        src.st = streaming && P.slen[i] > 0 ? (const float *)state_in[i] : nullptr;
-        src.slen = P.slen[i];
-        src.x = cur.p; src.xn = cur.sn; src.xc = cur.sc; src.xt = cur.stt; src.xlen = cur.len; src.C = l.cin;
-        EncConv c;
-        c.src = src; c.wp = wp; c.cinp = cinp; c.cout = l.cout; c.taps = l.taps; c.stride = l.stride; c.dil = l.dilation;
-        c.N = N; c.Lout = Lout; c.slabs = slabs; c.tsplit = P.tsplit[i]; c.xvec = cur.vec;
-        if (P.few[i])
-            hipLaunchKernelGGL(k_enc_conv_few, dim3((l.cout + 63) / 64, (cinp + 63) / 64, P.tsplit[i]), dim3(256), 0, st, c);
-        else
-            hipLaunchKernelGGL(k_enc_conv_mfma, dim3((l.cout + 127) / 128, (N * Lout + 31) / 32, P.tsplit[i]), dim3(256), 0, st, c);
+        const int Lout = P.Lout[i];
+        cur.src.st = streaming && P.slen[i] > 0 ? (const float *)state_in[i] : nullptr;
+        cur.src.slen = P.slen[i];
+        launch_conv(conv_args(cur, wp, l.cout, l.taps, l.stride, l.dilation, N, Lout, slabs, P.tsplit[i]), P.few[i], st);
 
-        const bool to_res = l.role == RNNT_ENC_ROLE_RESIDUAL, fin = l.role == RNNT_ENC_ROLE_FINAL;
+        const bool to_res = l.role == RNNT_ENC_ROLE_RESIDUAL;
         const bool to_out = i == n_layers - 1;  // the list's last layer, FINAL or not, leaves `out` [N][L_out][cout]
         float *dst = to_out ? out : to_res ? res : buf[flip];
         const long ldo = to_out ? l.cout : pad4(l.cout);
-        EncNorm nm;
-        nm.slabs = slabs; nm.nsplit = P.nsplit[i];
-        nm.bias = (const float *)l.bias; nm.gamma = (const float *)l.gamma; nm.beta = (const float *)l.beta;
-        nm.mean = (const float *)l.mean; nm.var = (const float *)l.var; nm.norm = l.norm; nm.eps = l.eps;
-        nm.res = (l.role & RNNT_ENC_ROLE_LAST) ? res : nullptr; nm.ldres = pad4(l.cout);
-        nm.act = !(to_res || fin);
-        nm.out = dst; nm.ldo = ldo; nm.N = N; nm.Lout = Lout; nm.cout = l.cout;
-        nm.nb_norm = N * ((l.cout + 15) / 16);
-        nm.src = src; nm.stride = l.stride;
+        EncNorm nm = norm_args(l, P, i, N, slabs, res, dst, ldo);
+        nm.src = cur.src; nm.stride = l.stride;
         const bool wr_state = streaming && !is_1x1(l) && P.slen_out[i] > 0;
         nm.state_out = wr_state ? (float *)state_out[i] : nullptr;
         nm.slen_out = wr_state ? P.slen_out[i] : 0;
         const long nb_state = wr_state ? ((long)N * l.cin * P.slen_out[i] + ENC_NORM_THREADS - 1) / ENC_NORM_THREADS : 0;
-        hipLaunchKernelGGL(k_enc_norm, dim3((unsigned)(nm.nb_norm + nb_state)), dim3(ENC_NORM_THREADS), 0, st, nm);
+        hipLaunchKernelGGL(k_enc_norm<false>, dim3((unsigned)(nm.nb_norm + nb_state)), dim3(ENC_NORM_THREADS), 0, st, nm);
 
-        wp += packed_floats(l);
+        wp += packed_floats(l, false);
         if (to_res) continue;
-        cur = {dst, (long)Lout * ldo, 1, ldo, Lout, l.cout, true};
+        cur = time_major(dst, ldo, Lout, l.cout);
         flip ^= 1;
     }
     return status(what);
 }
 
 // ---- training: host side
-size_t packed_t_floats(const rnnt_encoder_layer &l) { return align_up((size_t)l.taps * l.cin * pad4(l.cout) * 4) / 4; }
 inline bool reads_input(const rnnt_encoder_layer *layers, int i) { return i == 0 || (i == 1 && layers[0].role == RNNT_ENC_ROLE_RESIDUAL); }
 constexpr size_t NOT_KEPT = ~(size_t)0;
 
@@ -918,12 +896,8 @@ int make_train_plan(const rnnt_encoder_layer *layers, int n_layers, int N, int L
         if (!reads_input(layers, i)) {
             const long Min = (long)N * T.P.Lin[i];
             if (Min > 65535L * 32) return fail(RNNT_ERR_UNSUPPORTED, "N * L too large");
-            const long wgs = ((l.cin + 127) / 128) * ((Min + 31) / 32);
-            long ts = (ENC_MFMA_WGS + wgs - 1) / wgs;
-            ts = ts > l.taps ? l.taps : ts;
-            ts = ts > ENC_MFMA_SPLITS ? ENC_MFMA_SPLITS : ts;
-            T.dx_split[i] = (int)ts;
-            const size_t s = (size_t)ts * Min * l.cin;
+            T.dx_split[i] = mfma_tap_split(Min, l.cin, l.taps);
+            const size_t s = (size_t)T.dx_split[i] * Min * l.cin;
             if (res) x2 = s > x2 ? s : x2; else x1 = s > x1 ? s : x1;
         }
         const long tiles = (long)((l.cin + 127) / 128) * ((l.cout + 127) / 128) * l.taps;
@@ -944,47 +918,156 @@ int make_train_plan(const rnnt_encoder_layer *layers, int n_layers, int N, int L
     return RNNT_OK;
 }
 
-// what both run entries check before anything is enqueued
+// what both training run entries check before anything is enqueued
 int check_train(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x, const int64_t xs[3],
                 const void *const *keep, const float *p, const void *io, const void *saved, size_t saved_bytes, const void *ws,
                 size_t ws_bytes, size_t ws_need, const TrainPlan &T)
 {
-    if (!packed || !x || !xs || !io || !saved || !ws) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument");
-    if (((uintptr_t)packed & 15) || ((uintptr_t)ws & 15) || ((uintptr_t)saved & 15) || ((uintptr_t)x & 3) || ((uintptr_t)io & 3))
-        return fail(RNNT_ERR_INVALID_ARG, "packed weights, saved and workspace must be 16-byte aligned, x and out / dout 4-byte");
+    if (int rc = check_buffers(packed, x, xs, io, ws, saved, true)) return rc;
     if (saved_bytes < T.saved) return fail(RNNT_ERR_WORKSPACE, "saved %zu < required %zu bytes", saved_bytes, T.saved);
     if (ws_bytes < ws_need) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, ws_need);
     for (int i = 0; i < n_layers; ++i) {
-        const rnnt_encoder_layer &l = layers[i];
-        if (!l.bias) return fail(RNNT_ERR_INVALID_ARG, "layer %d: null bias", i);
-        if (l.norm == RNNT_ENC_NORM_BATCH && (!l.mean || !l.var)) return fail(RNNT_ERR_INVALID_ARG, "layer %d: batch norm without running statistics", i);
+        if (int rc = check_params(layers[i], i)) return rc;
         if (p && !(p[i] >= 0.f && p[i] < 1.f)) return fail(RNNT_ERR_INVALID_ARG, "layer %d: dropout p=%g outside [0, 1)", i, (double)p[i]);
-        if (keep && keep[i] && is_1x1(l)) return fail(RNNT_ERR_INVALID_ARG, "layer %d: a keep mask on a residual / final layer", i);
+        if (keep && keep[i] && is_1x1(layers[i])) return fail(RNNT_ERR_INVALID_ARG, "layer %d: a keep mask on a residual / final layer", i);
     }
     return RNNT_OK;
 }
 
-EncSrc train_src(const rnnt_encoder_layer *layers, const TrainPlan &T, int i, const float *x, const int64_t xs[3], int L,
-                 const float *saved, bool *vec)
+// layer i's input in training: x or a kept output, `lead` zero frames in front
+EncIn train_in(const rnnt_encoder_layer *layers, const TrainPlan &T, int i, const float *x, const int64_t xs[3], int L, const float *saved)
 {
-    const rnnt_encoder_layer &l = layers[i];
-    EncSrc s;
-    s.st = nullptr; s.slen = T.lead[i]; s.C = l.cin;
-    const int from = T.in_of[i];
-    if (from < 0) {
-        s.x = x; s.xn = (long)xs[0]; s.xc = (long)xs[1]; s.xt = (long)xs[2]; s.xlen = L;
-        *vec = xs[1] == 1 && xs[0] % 4 == 0 && xs[2] % 4 == 0 && ((uintptr_t)x & 15) == 0;
-    } else {
-        const long ld = pad4(l.cin);
-        s.x = saved + T.off_o[from]; s.xn = (long)T.P.Lout[from] * ld; s.xc = 1; s.xt = ld; s.xlen = T.P.Lout[from];
-        *vec = true;
-    }
-    return s;
+    const int from = T.in_of[i], C = layers[i].cin;
+    EncIn in = from < 0 ? caller_x(x, xs, L, C) : time_major(saved + T.off_o[from], pad4(C), T.P.Lout[from], C);
+    in.src.slen = T.lead[i];
+    return in;
 }
 
-int train_fwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x, const int64_t xs[3], int N, int L,
-              const int32_t *lead, const void *const *keep, const float *p, int regime, float *out, void *saved_v, size_t saved_bytes,
-              void *ws, size_t ws_bytes, void *stream)
+// ---- entries: host side
+// what every size query checks first
+int check_query(const rnnt_encoder_layer *layers, int n_layers, const size_t *out)
+{
+    if (!out) return fail(RNNT_ERR_INVALID_ARG, "null output pointer");
+    return check_layers(layers, n_layers);
+}
+
+size_t packed_total(const rnnt_encoder_layer *layers, int n_layers, bool transposed)  // floats
+{
+    size_t n = 0;
+    for (int i = 0; i < n_layers; ++i) n += packed_floats(layers[i], transposed);
+    return n;
+}
+
+int check_packed(const void *packed, size_t packed_bytes, size_t need)
+{
+    if (!packed || ((uintptr_t)packed & 15)) return fail(RNNT_ERR_INVALID_ARG, "null or not 16-byte aligned packed buffer");
+    if (packed_bytes < need) return fail(RNNT_ERR_WORKSPACE, "packed buffer %zu < required %zu bytes", packed_bytes, need);
+    return RNNT_OK;
+}
+
+// one kind of table for the whole list, layer behind layer from wp on
+void pack_tables(const rnnt_encoder_layer *layers, int n_layers, float *wp, bool transposed, hipStream_t st)
+{
+    for (int i = 0; i < n_layers; ++i) {
+        const rnnt_encoder_layer &l = layers[i];
+        const long n = (long)l.taps * (transposed ? (long)l.cin * pad4(l.cout) : (long)l.cout * pad4(l.cin));
+        hipLaunchKernelGGL(k_enc_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float *)l.weight, wp, l.cout, l.cin,
+                           l.taps, (int)transposed);
+        wp += packed_floats(l, transposed);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int rnnt_engine_encoder_packed_bytes(const rnnt_encoder_layer *layers, int n_layers, size_t *out)
+{
+    if (int rc = check_query(layers, n_layers, out)) return rc;
+    *out = packed_total(layers, n_layers, false) * 4;
+    return RNNT_OK;
+}
+
+int rnnt_engine_encoder_pack(const rnnt_encoder_layer *layers, int n_layers, void *packed, size_t packed_bytes, void *stream)
+{
+    size_t need = 0;
+    if (int rc = rnnt_engine_encoder_packed_bytes(layers, n_layers, &need)) return rc;
+    if (int rc = check_packed(packed, packed_bytes, need)) return rc;
+    for (int i = 0; i < n_layers; ++i)
+        if (!layers[i].weight) return fail(RNNT_ERR_INVALID_ARG, "layer %d: null weight", i);
+    pack_tables(layers, n_layers, (float *)packed, false, (hipStream_t)stream);
+    return status("rnnt_engine_encoder_pack");
+}
+
+int rnnt_engine_encoder_workspace_bytes(const rnnt_encoder_layer *layers, int n_layers, int N, int L, int regime,
+                                        const int32_t *state_lens, size_t *out)
+{
+    if (int rc = check_query(layers, n_layers, out)) return rc;
+    Plan P;
+    if (int rc = make_plan(layers, n_layers, N, L, state_lens, regime, P)) return rc;
+    *out = P.total;
+    return RNNT_OK;
+}
+
+int rnnt_engine_encoder_fwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x,
+                            const int64_t x_strides[3], int N, int L, int regime, float *out, void *workspace, size_t ws_bytes,
+                            void *stream)
+{
+    return run("rnnt_engine_encoder_fwd", layers, n_layers, packed, x, x_strides, N, L, nullptr, nullptr, nullptr, nullptr, regime, out,
+               workspace, ws_bytes, stream);
+}
+
+int rnnt_engine_encoder_stream_push(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x,
+                                    const int64_t x_strides[3], int N, int L, void *const *state_in, const int32_t *state_in_lens,
+                                    void *const *state_out, const int32_t *state_out_lens, int regime, float *out, void *workspace,
+                                    size_t ws_bytes, void *stream)
+{
+    if (!state_in_lens) return fail(RNNT_ERR_INVALID_ARG, "null state argument");
+    return run("rnnt_engine_encoder_stream_push", layers, n_layers, packed, x, x_strides, N, L, state_in, state_in_lens, state_out,
+               state_out_lens, regime, out, workspace, ws_bytes, stream);
+}
+
+int rnnt_engine_encoder_train_packed_bytes(const rnnt_encoder_layer *layers, int n_layers, size_t *out)
+{
+    if (int rc = check_query(layers, n_layers, out)) return rc;
+    *out = (packed_total(layers, n_layers, false) + packed_total(layers, n_layers, true)) * 4;
+    return RNNT_OK;
+}
+
+int rnnt_engine_encoder_train_pack(const rnnt_encoder_layer *layers, int n_layers, void *packed, size_t packed_bytes, void *stream)
+{
+    size_t need = 0;
+    if (int rc = rnnt_engine_encoder_train_packed_bytes(layers, n_layers, &need)) return rc;
+    if (int rc = check_packed(packed, packed_bytes, need)) return rc;
+    const size_t fwd = packed_total(layers, n_layers, false);  // the forward's tables come first
+    if (int rc = rnnt_engine_encoder_pack(layers, n_layers, packed, fwd * 4, stream)) return rc;
+    pack_tables(layers, n_layers, (float *)packed + fwd, true, (hipStream_t)stream);
+    return status("rnnt_engine_encoder_train_pack");
+}
+
+int rnnt_engine_encoder_train_saved_bytes(const rnnt_encoder_layer *layers, int n_layers, int N, int L, const int32_t *lead,
+                                          size_t *out)
+{
+    if (int rc = check_query(layers, n_layers, out)) return rc;
+    TrainPlan T;
+    if (int rc = make_train_plan(layers, n_layers, N, L, lead, RNNT_ENC_REGIME_AUTO, T)) return rc;
+    *out = T.saved;
+    return RNNT_OK;
+}
+
+int rnnt_engine_encoder_train_workspace_bytes(const rnnt_encoder_layer *layers, int n_layers, int N, int L, int regime,
+                                              const int32_t *lead, size_t *out)
+{
+    if (int rc = check_query(layers, n_layers, out)) return rc;
+    TrainPlan T;
+    if (int rc = make_train_plan(layers, n_layers, N, L, lead, regime, T)) return rc;
+    *out = T.ws_fwd > T.ws_bwd ? T.ws_fwd : T.ws_bwd;
+    return RNNT_OK;
+}
+
+int rnnt_engine_encoder_train_fwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x,
+                                  const int64_t xs[3], int N, int L, const int32_t *lead, const void *const *keep, const float *p,
+                                  int regime, float *out, void *saved_v, size_t saved_bytes, void *ws, size_t ws_bytes, void *stream)
 {
     if (int rc = check_layers(layers, n_layers)) return rc;
     TrainPlan T;
@@ -996,40 +1079,25 @@ int train_fwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed
     const float *wp = (const float *)packed;
     for (int i = 0; i < n_layers; ++i) {
         const rnnt_encoder_layer &l = layers[i];
-        const int Lout = P.Lout[i], cinp = pad4(l.cin);
-        EncConv c;
-        bool vec;
-        c.src = train_src(layers, T, i, x, xs, L, saved, &vec);
-        c.wp = wp; c.cinp = cinp; c.cout = l.cout; c.taps = l.taps; c.stride = l.stride; c.dil = l.dilation;
-        c.N = N; c.Lout = Lout; c.slabs = slabs; c.tsplit = P.tsplit[i]; c.xvec = vec;
-        if (P.few[i])
-            hipLaunchKernelGGL(k_enc_conv_few, dim3((l.cout + 63) / 64, (cinp + 63) / 64, P.tsplit[i]), dim3(256), 0, st, c);
-        else
-            hipLaunchKernelGGL(k_enc_conv_mfma, dim3((l.cout + 127) / 128, (N * Lout + 31) / 32, P.tsplit[i]), dim3(256), 0, st, c);
+        const EncIn in = train_in(layers, T, i, x, xs, L, saved);
+        launch_conv(conv_args(in, wp, l.cout, l.taps, l.stride, l.dilation, N, P.Lout[i], slabs, P.tsplit[i]), P.few[i], st);
 
         const bool to_res = l.role == RNNT_ENC_ROLE_RESIDUAL, to_out = i == n_layers - 1;
         auto at = [&](size_t off) { return off == NOT_KEPT ? nullptr : saved + off; };
-        EncNormT nm;
-        nm.slabs = slabs; nm.nsplit = P.nsplit[i];
-        nm.bias = (const float *)l.bias; nm.gamma = (const float *)l.gamma; nm.beta = (const float *)l.beta;
-        nm.mean = (const float *)l.mean; nm.var = (const float *)l.var; nm.norm = l.norm; nm.eps = l.eps;
-        nm.res = (l.role & RNNT_ENC_ROLE_LAST) ? res : nullptr; nm.ldres = pad4(l.cout);
-        nm.act = !is_1x1(l);
+        EncNorm nm = norm_args(l, P, i, N, slabs, res, to_out ? out : to_res ? res : at(T.off_o[i]), to_out ? l.cout : pad4(l.cout));
         nm.keep = keep ? (const uint8_t *)keep[i] : nullptr;
         nm.scale = 1.f / (1.f - (p ? p[i] : 0.f));
-        nm.out = to_out ? out : to_res ? res : at(T.off_o[i]);
-        nm.ldo = to_out ? l.cout : pad4(l.cout);
         nm.z = at(T.off_z[i]); nm.xh = at(T.off_xh[i]); nm.rstd = at(T.off_rstd[i]); nm.lds = pad4(l.cout);
-        nm.N = N; nm.Lout = Lout; nm.cout = l.cout;
-        hipLaunchKernelGGL(k_enc_norm_train, dim3((unsigned)(N * ((l.cout + 15) / 16))), dim3(ENC_NORM_THREADS), 0, st, nm);
-        wp += packed_floats(l);
+        hipLaunchKernelGGL(k_enc_norm<true>, dim3((unsigned)nm.nb_norm), dim3(ENC_NORM_THREADS), 0, st, nm);
+        wp += packed_floats(l, false);
     }
     return status("rnnt_engine_encoder_train_fwd");
 }
 
-int train_bwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x, const int64_t xs[3], int N, int L,
-              const int32_t *lead, const void *const *keep, const float *p, const float *dout, const void *saved_v, size_t saved_bytes,
-              const rnnt_encoder_grads *grads, void *ws, size_t ws_bytes, void *stream)
+int rnnt_engine_encoder_train_bwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x,
+                                  const int64_t xs[3], int N, int L, const int32_t *lead, const void *const *keep, const float *p,
+                                  const float *dout, const void *saved_v, size_t saved_bytes, const rnnt_encoder_grads *grads, void *ws,
+                                  size_t ws_bytes, void *stream)
 {
     if (int rc = check_layers(layers, n_layers)) return rc;
     TrainPlan T;
@@ -1045,9 +1113,8 @@ int train_bwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed
     float *dy = (float *)ws, *dres = dy + T.dy, *x1 = dres + T.dres, *x2 = x1 + T.x1, *dws = x2 + T.x2, *part = dws + T.dw;
     const float *wt[RNNT_ENC_MAX_LAYERS];  // the dX tables lie behind the forward's
     {
-        const float *w = (const float *)packed;
-        for (int i = 0; i < n_layers; ++i) w += packed_floats(layers[i]);
-        for (int i = 0; i < n_layers; ++i) { wt[i] = w; w += packed_t_floats(layers[i]); }
+        const float *w = (const float *)packed + packed_total(layers, n_layers, false);
+        for (int i = 0; i < n_layers; ++i) { wt[i] = w; w += packed_floats(layers[i], true); }
     }
     auto at = [&](size_t off) { return off == NOT_KEPT ? nullptr : saved + off; };
     for (int i = n_layers - 1; i >= 0; --i) {
@@ -1077,10 +1144,9 @@ int train_bwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed
         hipLaunchKernelGGL(k_enc_bwd_norm, dim3((unsigned)(N * ((l.cout + 15) / 16))), dim3(ENC_NORM_THREADS), 0, st, nb);
 
         const rnnt_encoder_grads &g = grads[i];
-        bool vec;
         if (g.weight) {
             EncDW d;
-            d.src = train_src(layers, T, i, x, xs, L, saved, &vec);
+            d.src = train_in(layers, T, i, x, xs, L, saved).src;
             d.dy = dy; d.ldy = ldp; d.cout = l.cout; d.taps = l.taps; d.stride = l.stride; d.dil = l.dilation; d.N = N; d.Lout = Lout;
             d.slabs = dws; d.ranges = T.dw_ranges[i]; d.rows = T.dw_rows[i];
             hipLaunchKernelGGL(k_enc_dw, dim3((unsigned)(l.taps * d.ranges), (l.cin + 127) / 128, (l.cout + 127) / 128), dim3(256), 0, st, d);
@@ -1095,147 +1161,12 @@ int train_bwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed
             hipLaunchKernelGGL(k_enc_bwd_sum, dim3((unsigned)(s.nb_w + (3 * l.cout + 255) / 256)), dim3(256), 0, st, s);
         }
         if (T.dx_split[i]) {  // dx = conv of dy, span - lead zero frames in front and zeros behind its last frame, with the reversed taps
-            const int Lin = P.Lin[i];
-            EncConv c;
-            c.src.st = nullptr; c.src.slen = (l.taps - 1) * l.dilation - T.lead[i];
-            c.src.x = dy; c.src.xn = (long)Lout * ldp; c.src.xc = 1; c.src.xt = ldp; c.src.xlen = Lout; c.src.C = l.cout;
-            c.wp = wt[i]; c.cinp = (int)ldp; c.cout = l.cin; c.taps = l.taps; c.stride = 1; c.dil = l.dilation;
-            c.N = N; c.Lout = Lin; c.slabs = is_res ? x2 : x1; c.tsplit = T.dx_split[i]; c.xvec = 1;
-            hipLaunchKernelGGL(k_enc_conv_mfma, dim3((l.cin + 127) / 128, (unsigned)(((long)N * Lin + 31) / 32), T.dx_split[i]), dim3(256), 0, st, c);
+            EncIn in = time_major(dy, ldp, Lout, l.cout);
+            in.src.slen = (l.taps - 1) * l.dilation - T.lead[i];
+            launch_conv(conv_args(in, wt[i], l.cin, l.taps, 1, l.dilation, N, P.Lin[i], is_res ? x2 : x1, T.dx_split[i]), false, st);
         }
     }
     return status("rnnt_engine_encoder_train_bwd");
-}
-
-}  // namespace
-
-extern "C" {
-
-int rnnt_engine_encoder_packed_bytes(const rnnt_encoder_layer *layers, int n_layers, size_t *out)
-{
-    if (!out) return fail(RNNT_ERR_INVALID_ARG, "null output pointer");
-    if (int rc = check_layers(layers, n_layers)) return rc;
-    size_t n = 0;
-    for (int i = 0; i < n_layers; ++i) n += packed_floats(layers[i]);
-    *out = n * 4;
-    return RNNT_OK;
-}
-
-int rnnt_engine_encoder_pack(const rnnt_encoder_layer *layers, int n_layers, void *packed, size_t packed_bytes, void *stream)
-{
-    size_t need = 0;
-    if (int rc = rnnt_engine_encoder_packed_bytes(layers, n_layers, &need)) return rc;
-    if (!packed || ((uintptr_t)packed & 15)) return fail(RNNT_ERR_INVALID_ARG, "null or not 16-byte aligned packed buffer");
-    if (packed_bytes < need) return fail(RNNT_ERR_WORKSPACE, "packed buffer %zu < required %zu bytes", packed_bytes, need);
-    for (int i = 0; i < n_layers; ++i)
-        if (!layers[i].weight) return fail(RNNT_ERR_INVALID_ARG, "layer %d: null weight", i);
-    float *wp = (float *)packed;
-    for (int i = 0; i < n_layers; ++i) {
-        const rnnt_encoder_layer &l = layers[i];
-        const long n = (long)l.taps * l.cout * pad4(l.cin);
-        hipLaunchKernelGGL(k_enc_pack_w, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           (const float *)l.weight, wp, l.cout, l.cin, pad4(l.cin), l.taps);
-        wp += packed_floats(l);
-    }
-    return status("rnnt_engine_encoder_pack");
-}
-
-int rnnt_engine_encoder_workspace_bytes(const rnnt_encoder_layer *layers, int n_layers, int N, int L, int regime,
-                                        const int32_t *state_lens, size_t *out)
-{
-    if (!out) return fail(RNNT_ERR_INVALID_ARG, "null output pointer");
-    if (int rc = check_layers(layers, n_layers)) return rc;
-    Plan P;
-    if (int rc = make_plan(layers, n_layers, N, L, state_lens, regime, P)) return rc;
-    *out = P.total;
-    return RNNT_OK;
-}
-
-int rnnt_engine_encoder_fwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x,
-                            const int64_t x_strides[3], int N, int L, int regime, float *out, void *workspace, size_t ws_bytes,
-                            void *stream)
-{
-    return run("rnnt_engine_encoder_fwd", layers, n_layers, packed, x, x_strides, N, L, nullptr, nullptr, nullptr, nullptr, regime, out,
-               workspace, ws_bytes, stream);
-}
-
-int rnnt_engine_encoder_stream_push(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x,
-                                    const int64_t x_strides[3], int N, int L, void *const *state_in, const int32_t *state_in_lens,
-                                    void *const *state_out, const int32_t *state_out_lens, int regime, float *out, void *workspace,
-                                    size_t ws_bytes, void *stream)
-{
-    if (!state_in_lens) return fail(RNNT_ERR_INVALID_ARG, "null state argument");
-    return run("rnnt_engine_encoder_stream_push", layers, n_layers, packed, x, x_strides, N, L, state_in, state_in_lens, state_out,
-               state_out_lens, regime, out, workspace, ws_bytes, stream);
-}
-
-int rnnt_engine_encoder_train_packed_bytes(const rnnt_encoder_layer *layers, int n_layers, size_t *out)
-{
-    if (!out) return fail(RNNT_ERR_INVALID_ARG, "null output pointer");
-    if (int rc = check_layers(layers, n_layers)) return rc;
-    size_t n = 0;
-    for (int i = 0; i < n_layers; ++i) n += packed_floats(layers[i]) + packed_t_floats(layers[i]);
-    *out = n * 4;
-    return RNNT_OK;
-}
-
-int rnnt_engine_encoder_train_pack(const rnnt_encoder_layer *layers, int n_layers, void *packed, size_t packed_bytes, void *stream)
-{
-    size_t need = 0, fwd = 0;
-    if (int rc = rnnt_engine_encoder_train_packed_bytes(layers, n_layers, &need)) return rc;
-    if (!packed || ((uintptr_t)packed & 15)) return fail(RNNT_ERR_INVALID_ARG, "null or not 16-byte aligned packed buffer");
-    if (packed_bytes < need) return fail(RNNT_ERR_WORKSPACE, "packed buffer %zu < required %zu bytes", packed_bytes, need);
-    if (int rc = rnnt_engine_encoder_packed_bytes(layers, n_layers, &fwd)) return rc;
-    if (int rc = rnnt_engine_encoder_pack(layers, n_layers, packed, fwd, stream)) return rc;  // the forward's tables come first
-    float *wp = (float *)packed + fwd / 4;
-    for (int i = 0; i < n_layers; ++i) {
-        const rnnt_encoder_layer &l = layers[i];
-        const long n = (long)l.taps * l.cin * pad4(l.cout);
-        hipLaunchKernelGGL(k_enc_pack_wt, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           (const float *)l.weight, wp, l.cout, l.cin, pad4(l.cout), l.taps);
-        wp += packed_t_floats(l);
-    }
-    return status("rnnt_engine_encoder_train_pack");
-}
-
-int rnnt_engine_encoder_train_saved_bytes(const rnnt_encoder_layer *layers, int n_layers, int N, int L, const int32_t *lead,
-                                          size_t *out)
-{
-    if (!out) return fail(RNNT_ERR_INVALID_ARG, "null output pointer");
-    if (int rc = check_layers(layers, n_layers)) return rc;
-    TrainPlan T;
-    if (int rc = make_train_plan(layers, n_layers, N, L, lead, RNNT_ENC_REGIME_AUTO, T)) return rc;
-    *out = T.saved;
-    return RNNT_OK;
-}
-
-int rnnt_engine_encoder_train_workspace_bytes(const rnnt_encoder_layer *layers, int n_layers, int N, int L, int regime,
-                                              const int32_t *lead, size_t *out)
-{
-    if (!out) return fail(RNNT_ERR_INVALID_ARG, "null output pointer");
-    if (int rc = check_layers(layers, n_layers)) return rc;
-    TrainPlan T;
-    if (int rc = make_train_plan(layers, n_layers, N, L, lead, regime, T)) return rc;
-    *out = T.ws_fwd > T.ws_bwd ? T.ws_fwd : T.ws_bwd;
-    return RNNT_OK;
-}
-
-int rnnt_engine_encoder_train_fwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x,
-                                  const int64_t x_strides[3], int N, int L, const int32_t *lead, const void *const *keep,
-                                  const float *p, int regime, float *out, void *saved, size_t saved_bytes, void *workspace,
-                                  size_t ws_bytes, void *stream)
-{
-    return train_fwd(layers, n_layers, packed, x, x_strides, N, L, lead, keep, p, regime, out, saved, saved_bytes, workspace, ws_bytes,
-                     stream);
-}
-
-int rnnt_engine_encoder_train_bwd(const rnnt_encoder_layer *layers, int n_layers, const void *packed, const float *x,
-                                  const int64_t x_strides[3], int N, int L, const int32_t *lead, const void *const *keep,
-                                  const float *p, const float *dout, const void *saved, size_t saved_bytes,
-                                  const rnnt_encoder_grads *grads, void *workspace, size_t ws_bytes, void *stream)
-{
-    return train_bwd(layers, n_layers, packed, x, x_strides, N, L, lead, keep, p, dout, saved, saved_bytes, grads, workspace, ws_bytes,
-                     stream);
 }
 
 }  // extern "C"

@@ -5,7 +5,9 @@ the conv sum carried through the norm plus one of the result); a new state is a 
 prints `case, engine error, e_ref, bar` (profiles/encoder_layer_parity.txt holds a run's).
 
 The helper owns every buffer: the workspace has exactly the bytes rnnt_engine_encoder_workspace_bytes reports, `out`, every new state
-and the workspace are pre-filled (signalling NaNs unless a test says otherwise) and followed by 64 guard words that must survive."""
+and the workspace are pre-filled (signalling NaNs unless a test says otherwise) and followed by 64 guard words that must survive; so is
+the packed buffer.  Beside the results abi_run hands back the workspace and the packed tables as the call left them and the sizes
+the queries gave (tests/golden/make_golden_encoder_bits.py pins their bytes)."""
 import ctypes
 from types import SimpleNamespace
 
@@ -73,8 +75,9 @@ def abi_run(case, regime, fill=SNAN):
     with torch.cuda.device(dev):
         n = ctypes.c_size_t(0)
         engine._check(lib.rnnt_engine_encoder_packed_bytes(arr, nl, ctypes.byref(n)))
-        packed = torch.empty(n.value, dtype=torch.uint8, device=dev)
-        engine._check(lib.rnnt_engine_encoder_pack(arr, nl, engine._p(packed), ctypes.c_size_t(n.value), engine._stream(dev)))
+        n_packed = n.value
+        packed = _buffer(n_packed // 4, fill, dev)
+        engine._check(lib.rnnt_engine_encoder_pack(arr, nl, engine._p(packed), ctypes.c_size_t(n_packed), engine._stream(dev)))
         lens_in = None if case.states is None else (ctypes.c_int32 * nl)(*case.state_lens)
         engine._check(lib.rnnt_engine_encoder_workspace_bytes(arr, nl, N, L, regime, lens_in, ctypes.byref(n)))
         assert n.value == P.ws_bytes and n.value % 4 == 0
@@ -94,12 +97,14 @@ def abi_run(case, regime, fill=SNAN):
                                                               ptr_out, lens_out, regime, engine._p(out), engine._p(ws),
                                                               ctypes.c_size_t(n.value), engine._stream(dev)))
     torch.cuda.synchronize()
-    for what, t, words in [("out", out, n_out), ("workspace", ws, n.value // 4)] + [
+    for what, t, words in [("out", out, n_out), ("workspace", ws, n.value // 4), ("packed", packed, n_packed // 4)] + [
             (f"state_out {i}", t, P.rows[i].state_values) for i, t in enumerate(new) if t is not None]:
         assert bool((t[words:] == GUARD).all()), f"{case.name}: the guard words behind {what} were written"
     states = [None if t is None else t[:r.state_values].view(torch.float32).view(N, l.cin, r.slen_out)
               for t, l, r in zip(new, case.layers, P.rows)]
-    return SimpleNamespace(out=out[:n_out].view(torch.float32).view(N, P.L_final, case.cout), states=states or None, plan=P)
+    return SimpleNamespace(out=out[:n_out].view(torch.float32).view(N, P.L_final, case.cout), states=states or None, plan=P,
+                           workspace=ws[:n.value // 4], packed=packed[:n_packed // 4],
+                           sizes=dict(packed_bytes=n_packed, workspace_bytes=n.value))
 
 
 def _bits(t):

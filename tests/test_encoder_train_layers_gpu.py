@@ -1,11 +1,13 @@
 """GPU tests of the encoder's training kernels layer by layer (rnnt_amd/csrc/encoder.hip through the C ABI rnnt_engine_encoder_train_*:
-k_enc_norm_train, k_enc_bwd_norm, k_enc_dw, k_enc_bwd_sum, the dX conv) against the float64 numpy oracle of
+k_enc_norm<true>, k_enc_bwd_norm, k_enc_dw, k_enc_bwd_sum, the dX conv) against the float64 numpy oracle of
 tests/encoder_train_cases.py, at the edges that module states and asserts on the plan mirror.  The bar of every tensor is
 C.bars: 4 x max(the torch composition's own fp32 error against the oracle, one rounding of the largest entry); the exactly zero bias
 gradient of a conv in front of an instance norm is held to M 2^-24 sum|dy| per channel.  Every comparison prints its figures.
 
 The helper owns every buffer: `saved` and the workspace have exactly the bytes the size queries report, they, `out` and every
-gradient are pre-filled with signalling NaNs and followed by guard words that must survive."""
+gradient are pre-filled with signalling NaNs and followed by guard words that must survive; so is the packed buffer.  Beside the results
+abi_run hands back `saved`, the workspace after either call, the packed tables and the sizes the queries gave
+(tests/golden/make_golden_encoder_bits.py pins their bytes)."""
 import ctypes
 from types import SimpleNamespace
 
@@ -56,8 +58,9 @@ def abi_run(case, regime=AUTO):
     with torch.cuda.device(dev):
         n = ctypes.c_size_t(0)
         engine._check(lib.rnnt_engine_encoder_train_packed_bytes(arr, nl, ctypes.byref(n)))
-        packed = torch.empty(n.value, dtype=torch.uint8, device=dev)
-        engine._check(lib.rnnt_engine_encoder_train_pack(arr, nl, engine._p(packed), ctypes.c_size_t(n.value), engine._stream(dev)))
+        n_packed = n.value
+        packed = _buffer(n_packed // 4, SNAN, dev)
+        engine._check(lib.rnnt_engine_encoder_train_pack(arr, nl, engine._p(packed), ctypes.c_size_t(n_packed), engine._stream(dev)))
         engine._check(lib.rnnt_engine_encoder_train_saved_bytes(arr, nl, N, L, lead, ctypes.byref(n)))
         assert n.value == tp.saved_bytes
         sv = n.value
@@ -67,12 +70,13 @@ def abi_run(case, regime=AUTO):
         engine._check(lib.rnnt_engine_encoder_train_fwd(arr, nl, engine._p(packed), engine._p(x), strides, N, L, lead, keep, p, regime,
                                                         engine._p(out), engine._p(saved), ctypes.c_size_t(sv), engine._p(ws),
                                                         ctypes.c_size_t(n.value), engine._stream(dev)))
+        ws_fwd = ws[:n.value // 4].clone()
         ws[:n.value // 4] = SNAN  # the workspace carries nothing from the forward to the backward
         engine._check(lib.rnnt_engine_encoder_train_bwd(arr, nl, engine._p(packed), engine._p(x), strides, N, L, lead, keep, p,
                                                         engine._p(dout), engine._p(saved), ctypes.c_size_t(sv), grads, engine._p(ws),
                                                         ctypes.c_size_t(n.value), engine._stream(dev)))
     torch.cuda.synchronize()
-    named = [("out", out, n_out), ("saved", saved, sv // 4), ("workspace", ws, n.value // 4)]
+    named = [("out", out, n_out), ("saved", saved, sv // 4), ("workspace", ws, n.value // 4), ("packed", packed, n_packed // 4)]
     for i, (g, l) in enumerate(zip(gbuf, case.layers)):
         named += [(f"grad {k} of layer {i}", t, l.W.size if k == "W" else l.cout) for k, t in g.items() if t is not None]
     for what, t, words in named:
@@ -81,7 +85,9 @@ def abi_run(case, regime=AUTO):
     for g, l in zip(gbuf, case.layers):
         res.append({k: None if t is None else t[:(l.W.size if k == "W" else l.cout)].view(torch.float32).cpu().numpy().reshape(
             l.W.shape if k == "W" else (l.cout,)) for k, t in g.items()})
-    return SimpleNamespace(out=out[:n_out].view(torch.float32).view(N, tp.L_final, cout).cpu().numpy(), grads=res)
+    return SimpleNamespace(out=out[:n_out].view(torch.float32).view(N, tp.L_final, cout).cpu().numpy(), grads=res,
+                           saved=saved[:sv // 4], workspace_fwd=ws_fwd, workspace_bwd=ws[:n.value // 4], packed=packed[:n_packed // 4],
+                           sizes=dict(train_packed_bytes=n_packed, train_saved_bytes=sv, train_workspace_bytes=n.value))
 
 
 def _compare(case, want, bars, got, label):
