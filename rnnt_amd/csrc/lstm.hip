@@ -17,7 +17,8 @@
 // Exact fp32 products (v_mfma_f32_32x32x2_f32 / FMA) only.
 // No workgroup waits on another; no atomics on results: every sum has a fixed order.
 // The greedy decode with this predictor as a device loop (rnnt_engine_greedy_decode_lstm, k_ld_*) is at the end of the file, and after it
-// the predictor step of a beam-search round (rnnt_engine_beam_decode_lstm, k_bl_*; the search itself is beam.hip's).
+// the predictor step of a beam-search round (rnnt_engine_beam_decode_lstm, k_bl_*; the search itself is beam.hip's).  The LSTM cell is
+// written once (lstm_cell) for training and the decode loops, and the scratch of a predictor step is laid out once (step_layout).
 #include "../../include/rnnt_engine.h"
 #include "decode_kernels.hpp"
 #include "smallgemm.hpp"
@@ -205,7 +206,83 @@ struct StepF {
     int Hd;
 };
 
-// One workgroup per batch row: gates = xg + rg, g_norm over the row's 4 Hd gates, the nonlinearities, the cell update, c_norm, h.
+// The LSTM cell of ONE row by the workgroup's 256 threads, from the row's summed gates `g` (unit j = tid + 256 k; zeros in a lane j >= Hd):
+// g_norm over the 4 Hd gates, the nonlinearities, the cell update on c_prev[c_row + j] (c_prev NULL: zeros), c_norm, h = o tanh(c).
+// Two sinks: kept(j, q, v) gets what a backward needs, each value where it is known — q < 4: unit j's normalised gate q before its
+// affine, q == 4: its normalised cell before the affine (handing all of it over at the end holds 16 gates per thread in registers
+// through the cell) —, unit(j, cn, h) the unit's new cell and h; unit may write where c_prev lies (a thread has read a unit's cell
+// before it hands the unit over).  Returns (rstd of g_norm, rstd of c_norm).  red: 4 floats of LDS.
+// The training forward and the decode loops share this body and differ in ONE thing that reaches the bits: the order in which they add
+// a row's gates up — xg + (r0 + r1 + ...) there, ((p0 + p1) + ...) + bias here.
+template <bool LN, class Kept, class Unit>
+__device__ __forceinline__ float2 lstm_cell(float (&g)[UNITS][4], const float *c_prev, long c_row, const float *gw, const float *gb, const float *cw,
+                                            const float *cb, float eps, int Hd, float *red, Kept kept, Unit unit)
+{
+    const int tid = threadIdx.x;
+    float rstd_g = 1.f, rstd_c = 1.f;
+    if (LN) {
+        const float n = 4.f * Hd;
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k) s += (g[k][0] + g[k][1]) + (g[k][2] + g[k][3]);
+        s = block_sum(s, red);
+        const float mean = s / n;
+        float q2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k)
+            if (tid + 256 * k < Hd)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) q2 += (g[k][q] - mean) * (g[k][q] - mean);
+        q2 = block_sum(q2, red);
+        rstd_g = rsqrtf(q2 / n + eps);
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) g[k][q] = (g[k][q] - mean) * rstd_g;
+    }
+    float c[UNITS], o[UNITS];
+#pragma unroll
+    for (int k = 0; k < UNITS; ++k) {
+        const int j = tid + 256 * k;
+        c[k] = 0.f; o[k] = 0.f;
+        if (j >= Hd) continue;
+        float pre[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            kept(j, q, g[k][q]);
+            pre[q] = LN ? g[k][q] * gw[q * Hd + j] + gb[q * Hd + j] : g[k][q];
+        }
+        const float cp = c_prev ? c_prev[c_row + j] : 0.f;
+        c[k] = sigmoidf(pre[1]) * cp + sigmoidf(pre[0]) * tanhf(pre[2]);
+        o[k] = sigmoidf(pre[3]);
+    }
+    if (LN) {
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k) s += c[k];
+        s = block_sum(s, red);
+        const float mean = s / Hd;
+        float q2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k)
+            if (tid + 256 * k < Hd) q2 += (c[k] - mean) * (c[k] - mean);
+        q2 = block_sum(q2, red);
+        rstd_c = rsqrtf(q2 / Hd + eps);
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k) c[k] = (c[k] - mean) * rstd_c;
+    }
+#pragma unroll
+    for (int k = 0; k < UNITS; ++k) {
+        const int j = tid + 256 * k;
+        if (j >= Hd) continue;
+        const float cn = LN ? c[k] * cw[j] + cb[j] : c[k];
+        kept(j, 4, c[k]);
+        unit(j, cn, o[k] * tanhf(cn));
+    }
+    return make_float2(rstd_g, rstd_c);
+}
+
+// One workgroup per batch row: gates = xg + rg, the cell, and what the backward needs, the keep mask and the next row of the sequence.
 template <bool LN>
 __global__ __launch_bounds__(256) void k_lstm_step_fwd(StepF a)
 {
@@ -231,72 +308,22 @@ __global__ __launch_bounds__(256) void k_lstm_step_fwd(StepF a)
             g[k][q] = v;
         }
     }
-    float rstd_g = 1.f, rstd_c = 1.f;
-    if (LN) {
-        const float n = 4.f * Hd;
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < UNITS; ++k) s += (g[k][0] + g[k][1]) + (g[k][2] + g[k][3]);
-        s = block_sum(s, red);
-        const float mean = s / n;
-        float q2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < UNITS; ++k)
-            if (tid + 256 * k < Hd)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) q2 += (g[k][q] - mean) * (g[k][q] - mean);
-        q2 = block_sum(q2, red);
-        rstd_g = rsqrtf(q2 / n + a.eps);
-#pragma unroll
-        for (int k = 0; k < UNITS; ++k)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) g[k][q] = (g[k][q] - mean) * rstd_g;
-    }
-    float c[UNITS], o[UNITS];
-#pragma unroll
-    for (int k = 0; k < UNITS; ++k) {
-        const int j = tid + 256 * k;
-        c[k] = 0.f; o[k] = 0.f;
-        if (j >= Hd) continue;
-        float pre[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (a.ghat) a.ghat[b * a.ghat_ld + q * Hd + j] = g[k][q];
-            pre[q] = LN ? g[k][q] * a.gw[q * Hd + j] + a.gb[q * Hd + j] : g[k][q];
-        }
-        const float cp = a.cprev ? a.cprev[b * a.cprev_ld + j] : 0.f;
-        c[k] = sigmoidf(pre[1]) * cp + sigmoidf(pre[0]) * tanhf(pre[2]);
-        o[k] = sigmoidf(pre[3]);
-    }
-    if (LN) {
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < UNITS; ++k) s += c[k];
-        s = block_sum(s, red);
-        const float mean = s / Hd;
-        float q2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < UNITS; ++k)
-            if (tid + 256 * k < Hd) q2 += (c[k] - mean) * (c[k] - mean);
-        q2 = block_sum(q2, red);
-        rstd_c = rsqrtf(q2 / Hd + a.eps);
-#pragma unroll
-        for (int k = 0; k < UNITS; ++k) c[k] = (c[k] - mean) * rstd_c;
-    }
-#pragma unroll
-    for (int k = 0; k < UNITS; ++k) {
-        const int j = tid + 256 * k;
-        if (j >= Hd) continue;
-        if (a.chat) a.chat[b * a.chat_ld + j] = c[k];
-        const float cn = LN ? c[k] * a.cw[j] + a.cb[j] : c[k];
-        const float h = o[k] * tanhf(cn);
-        a.cnext[b * a.cnext_ld + j] = cn;
-        a.hnext[b * a.hnext_ld + j] = h;
-        float yv = h;
-        if (a.keep) yv = a.keep[b * a.keep_ld + j] ? h * a.scale : 0.f;
-        a.y[b * a.y_ld + j] = yv;
-    }
-    if (a.rs && tid == 0) { a.rs[b * a.rs_ld] = rstd_g; a.rs[b * a.rs_ld + 1] = rstd_c; }
+    // (the sinks hold the arguments by value: held by reference, the row offsets were recomputed in every unit pass)
+    const float2 rstd = lstm_cell<LN>(
+        g, a.cprev, b * a.cprev_ld, a.gw, a.gb, a.cw, a.cb, a.eps, Hd, red,
+        [=](int j, int q, float v) {
+            if (q < 4) {
+                if (a.ghat) a.ghat[b * a.ghat_ld + q * Hd + j] = v;
+            } else if (a.chat) a.chat[b * a.chat_ld + j] = v;
+        },
+        [=](int j, float cn, float h) {
+            a.cnext[b * a.cnext_ld + j] = cn;
+            a.hnext[b * a.hnext_ld + j] = h;
+            float yv = h;
+            if (a.keep) yv = a.keep[b * a.keep_ld + j] ? h * a.scale : 0.f;
+            a.y[b * a.y_ld + j] = yv;
+        });
+    if (a.rs && tid == 0) { a.rs[b * a.rs_ld] = rstd.x; a.rs[b * a.rs_ld + 1] = rstd.y; }
 }
 
 struct StepB {
@@ -485,19 +512,22 @@ size_t ld_gp_floats(int E, int Hd, int O, int H)
     return g;
 }
 
-struct LdLayout { size_t text, x1, hc, y, gp, part, ctrl, total; };  // floats; the text vectors [n_utt][H] come first (the ABI says so)
-LdLayout ld_layout(int n_utt, int E, int Hd, int O, int L, int H, int V, int scan_frames)
+// the scratch of a predictor step of `rows` rows, in floats: x1, y and gp; for a greedy loop (scan_frames > 0) the scan's candidates and
+// the control words as well; owns_state: the rows' text vectors [rows][H] — first, the ABI says so — and h, c [L][2][rows][Hd] too (the
+// offline loop; a stream keeps them in its block, a beam round in its pool)
+struct StepLayout { size_t text, x1, hc, y, gp, part, ctrl, total; };
+StepLayout step_layout(int rows, int E, int Hd, int O, int L, int H, int V, int scan_frames, bool owns_state)
 {
-    const size_t n = n_utt;
-    LdLayout w;
+    const size_t n = rows;
+    StepLayout w;
     size_t o = 0;
-    w.text = o; o += al(n * H);
+    w.text = o; if (owns_state) o += al(n * H);
     w.x1 = o;   o += al(n * E);
-    w.hc = o;   o += al((size_t)L * 2 * n * Hd);
+    w.hc = o;   if (owns_state) o += al((size_t)L * 2 * n * Hd);
     w.y = o;    o += al(n * O);
     w.gp = o;   o += al(ld_gp_floats(E, Hd, O, H) * n);
-    w.part = o; o += al(n * scan_frames * ((V + 31) / 32) * 2);
-    w.ctrl = o; o += 64;
+    w.part = o; if (scan_frames) o += al(n * scan_frames * ((V + 31) / 32) * 2);
+    w.ctrl = o; if (scan_frames) o += 64;
     w.total = o;
     return w;
 }
@@ -526,21 +556,6 @@ LsBlock ls_block(int n, int Hd, int L, int H)
     b.text = o;  o += al((size_t)n * H);
     b.total = o;
     return b;
-}
-// a push's scratch (LdLayout without what the block holds)
-struct LsLayout { size_t x1, y, gp, part, ctrl, total; };
-LsLayout ls_layout(int n_streams, int E, int Hd, int O, int H, int V, int scan_frames)
-{
-    const size_t n = n_streams;
-    LsLayout w;
-    size_t o = 0;
-    w.x1 = o;   o += al(n * E);
-    w.y = o;    o += al(n * O);
-    w.gp = o;   o += al(ld_gp_floats(E, Hd, O, H) * n);
-    w.part = o; o += al(n * scan_frames * ((V + 31) / 32) * 2);
-    w.ctrl = o; o += 64;
-    w.total = o;
-    return w;
 }
 
 // whether the predictor has a label of this row's to take in NOW (a stream at rest keeps its start blank for the push that brings it a
@@ -612,7 +627,7 @@ struct LdStep {
     int Hd;
 };
 
-// k_lstm_step_fwd's definition in eval mode, nothing kept, for ONE row (the workgroup's 256 threads; red: 4 floats of LDS): `gp` the
+// k_lstm_step_fwd's cell (lstm_cell) in eval mode, nothing kept, for ONE row (the workgroup's 256 threads; red: 4 floats of LDS): `gp` the
 // row's first partial product, `c_prev` [Hd] the cell it continues, `h` / `c` [Hd] where the new state goes (c may be c_prev: a thread
 // reads a unit's cell before it writes it), `h2` / `c2` a second copy or NULL
 template <bool LN>
@@ -635,63 +650,12 @@ __device__ __forceinline__ void ld_step_row(const LdStep &a, const float *__rest
             g[k][q] = v;
         }
     }
-    if (LN) {
-        const float n = 4.f * Hd;
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < UNITS; ++k) s += (g[k][0] + g[k][1]) + (g[k][2] + g[k][3]);
-        s = block_sum(s, red);
-        const float mean = s / n;
-        float q2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < UNITS; ++k)
-            if (tid + 256 * k < Hd)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) q2 += (g[k][q] - mean) * (g[k][q] - mean);
-        q2 = block_sum(q2, red);
-        const float rstd_g = rsqrtf(q2 / n + a.eps);
-#pragma unroll
-        for (int k = 0; k < UNITS; ++k)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) g[k][q] = (g[k][q] - mean) * rstd_g;
-    }
-    float c[UNITS], o[UNITS];
-#pragma unroll
-    for (int k = 0; k < UNITS; ++k) {
-        const int j = tid + 256 * k;
-        c[k] = 0.f; o[k] = 0.f;
-        if (j >= Hd) continue;
-        float pre[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) pre[q] = LN ? g[k][q] * a.gw[q * Hd + j] + a.gb[q * Hd + j] : g[k][q];
-        c[k] = sigmoidf(pre[1]) * c_prev[j] + sigmoidf(pre[0]) * tanhf(pre[2]);
-        o[k] = sigmoidf(pre[3]);
-    }
-    if (LN) {
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < UNITS; ++k) s += c[k];
-        s = block_sum(s, red);
-        const float mean = s / Hd;
-        float q2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < UNITS; ++k)
-            if (tid + 256 * k < Hd) q2 += (c[k] - mean) * (c[k] - mean);
-        q2 = block_sum(q2, red);
-        const float rstd_c = rsqrtf(q2 / Hd + a.eps);
-#pragma unroll
-        for (int k = 0; k < UNITS; ++k) c[k] = (c[k] - mean) * rstd_c;
-    }
-#pragma unroll
-    for (int k = 0; k < UNITS; ++k) {
-        const int j = tid + 256 * k;
-        if (j >= Hd) continue;
-        const float cn = LN ? c[k] * a.cw[j] + a.cb[j] : c[k];
-        const float hv = o[k] * tanhf(cn);
+    __builtin_assume(c_prev != nullptr);
+    lstm_cell<LN>(g, c_prev, 0, a.gw, a.gb, a.cw, a.cb, a.eps, Hd, red, [](int, int, float) {}, [&](int j, float cn, float hv) {
         c_new[j] = cn;
         h[j] = hv;
         if (h2) { c2[j] = cn; h2[j] = hv; }
-    }
+    });
 }
 
 // the step of the rows whose utterance has a new label: one workgroup per utterance, h and c in place
@@ -1005,19 +969,6 @@ __global__ __launch_bounds__(256) void k_bl_rowfin(BeamLstmStep a, const float *
     ld_rowfin_row<LN>(gp + (long)row * N, nsp, gp_ld, N, bias, gamma, beta, eps, y, red);
 }
 
-struct BlLayout { size_t x1, y, gp, total; };  // floats
-BlLayout bl_layout(int n_utt, int E, int Hd, int O, int H)
-{
-    const size_t M = (size_t)16 * n_utt;
-    BlLayout w;
-    size_t o = 0;
-    w.x1 = o; o += al(M * E);
-    w.y = o;  o += al(M * O);
-    w.gp = o; o += al(ld_gp_floats(E, Hd, O, H) * M);
-    w.total = o;
-    return w;
-}
-
 int ld_check_sizes(int n_utt, int S, int E, int Hd, int O, int L, int ln, int H, int V, int has_text, int scan_frames)
 {
     if (n_utt < 1) return engine_fail(RNNT_ERR_INVALID_ARG, "n_utt=%d must be >= 1", n_utt);
@@ -1034,12 +985,15 @@ int ld_check_sizes(int n_utt, int S, int E, int Hd, int O, int L, int ln, int H,
 
 }  // namespace
 
+// a beam round's predictor step: one row per slot, its state in the search's pool
+static StepLayout bl_layout(int n_utt, int E, int Hd, int O, int H) { return step_layout(16 * n_utt, E, Hd, O, 0, H, 0, 0, false); }
+
 size_t beam_lstm_step_floats(int n_utt, int E, int Hd, int O, int H) { return bl_layout(n_utt, E, Hd, O, H).total; }
 
 void launch_beam_lstm_step(const BeamLstmStep &a, hipStream_t st)
 {
     const int n = a.n_utt, M = 16 * n, E = a.E, Hd = a.Hd, O = a.O, L = a.L, H = a.H;
-    const BlLayout w = bl_layout(n, E, Hd, O, H);
+    const StepLayout w = bl_layout(n, E, Hd, O, H);
     float *x1 = a.scratch + w.x1, *y = a.scratch + w.y, *gp = a.scratch + w.gp;
     const long ld = (long)L * 2 * Hd;  // floats from one pool row to the next
     const dim3 slots(16, n), tiles_z((M + 31) / 32);
@@ -1081,6 +1035,61 @@ void launch_beam_lstm_step(const BeamLstmStep &a, hipStream_t st)
         hipLaunchKernelGGL(k_bl_rowfin<false>, slots, dim3(256), 0, st, a, gp, g.g[0].KS, (long)M * H, H, a.text_b, (const float *)nullptr,
                            (const float *)nullptr, 0.f, y, 1);
     }
+}
+
+// the device's address of a caller's pinned flag word (an ordinary host pointer is refused, never written through); NULL stays NULL
+static int ld_host_flag(int32_t *host_flag, int32_t **dev)
+{
+    *dev = nullptr;
+    if (!host_flag) return RNNT_OK;
+    void *dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, host_flag, 0) != hipSuccess || !dp) {
+        (void)hipGetLastError();
+        return engine_fail(RNNT_ERR_INVALID_ARG, "host_flag is not mapped pinned host memory (hipHostMalloc / torch pin_memory)");
+    }
+    *dev = (int32_t *)dp;
+    return RNNT_OK;
+}
+
+// What the three decode entries (greedy, stream push, beam) check alike, in two halves so that an entry's own geometry, blank and limit
+// checks stand between them and every error is reported in the order it always was.  `need`: the workspace size the entry's query asks
+// for (the query has checked the dimensions).
+struct DecodeCall {
+    const void *frames; const rnnt_lstm_predictor_params *p; int L, ln; const void *text_W, *text_b, *W, *bias;
+    int iterations; int32_t *host_flag; void *workspace; size_t ws_bytes, need;
+};
+// own_null / own_misaligned: one of the entry's own pointers is null / off the alignment `rule` names
+static int ld_check_pointers(const DecodeCall &c, bool own_null, bool own_misaligned, const char *rule)
+{
+    if (c.iterations < 0) return engine_fail(RNNT_ERR_INVALID_ARG, "iterations=%d", c.iterations);
+    if (bad(c.frames) || bad(c.W) || bad(c.bias) || !c.workspace || own_null)
+        return engine_fail(RNNT_ERR_INVALID_ARG, "null or not 16-byte aligned pointer argument");
+    if (((uintptr_t)c.workspace & 255) || own_misaligned) return engine_fail(RNNT_ERR_INVALID_ARG, "%s", rule);
+    if (int rc = check_params(c.p, c.L, c.ln, "parameter")) return rc;
+    if ((c.text_W == nullptr) != (c.text_b == nullptr) || (c.text_W && (bad(c.text_W) || bad(c.text_b))))
+        return engine_fail(RNNT_ERR_INVALID_ARG, "text_W / text_b: both or neither, 16-byte aligned");
+    return RNNT_OK;
+}
+static int ld_check_flag_and_size(const DecodeCall &c, int32_t **flag_dev)
+{
+    if (int rc = ld_host_flag(c.host_flag, flag_dev)) return rc;
+    if (c.ws_bytes < c.need) return engine_fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", c.ws_bytes, c.need);
+    return RNNT_OK;
+}
+static bool bad_stride(int64_t frame_stride, int H) { return frame_stride < H || frame_stride % 4; }
+static int check_blank(int blank, int V)
+{
+    return blank < 0 || blank >= V ? engine_fail(RNNT_ERR_INVALID_ARG, "blank=%d outside [0,%d)", blank, V) : RNNT_OK;
+}
+
+// the model's part of a decode's arguments (checked by the caller): of a greedy loop's LdArgs or a beam search's BeamLstmStep
+template <class Model>
+static void ld_model(Model &a, const rnnt_lstm_predictor_params *p, int S, int E, int Hd, int O, int L, int layer_norm, float eps_in,
+                     float eps_lstm, float eps_out, const void *text_W, const void *text_b, int H)
+{
+    a.p = *p; a.S = S; a.E = E; a.Hd = Hd; a.O = O; a.L = L; a.ln = layer_norm != 0;
+    a.eps_in = eps_in; a.eps_lstm = eps_lstm; a.eps_out = eps_out;
+    a.text_W = (const float *)text_W; a.text_b = (const float *)text_b; a.H = H;
 }
 
 extern "C" {
@@ -1272,37 +1281,12 @@ int rnnt_engine_lstm_predictor_bwd(const int64_t *ids, int B, int U1, int S, int
     return status("rnnt_engine_lstm_predictor_bwd");
 }
 
-// the device's address of a caller's pinned flag word (an ordinary host pointer is refused, never written through); NULL stays NULL
-static int ld_host_flag(int32_t *host_flag, int32_t **dev)
-{
-    *dev = nullptr;
-    if (!host_flag) return RNNT_OK;
-    void *dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, host_flag, 0) != hipSuccess || !dp) {
-        (void)hipGetLastError();
-        return engine_fail(RNNT_ERR_INVALID_ARG, "host_flag is not mapped pinned host memory (hipHostMalloc / torch pin_memory)");
-    }
-    *dev = (int32_t *)dp;
-    return RNNT_OK;
-}
-
-// the model's part of a greedy loop's arguments (checked by the caller)
-static void ld_model(LdArgs &a, const rnnt_lstm_predictor_params *p, int S, int E, int Hd, int O, int L, int layer_norm, float eps_in,
-                     float eps_lstm, float eps_out, const void *text_W, const void *text_b, const void *W, const void *bias, int H, int V,
-                     int blank, int max_length, int max_per_frame, int scan_frames)
-{
-    a.p = *p; a.S = S; a.E = E; a.Hd = Hd; a.O = O; a.L = L; a.ln = layer_norm != 0;
-    a.eps_in = eps_in; a.eps_lstm = eps_lstm; a.eps_out = eps_out;
-    a.text_W = (const float *)text_W; a.text_b = (const float *)text_b; a.W = (const float *)W; a.bias = (const float *)bias;
-    a.H = H; a.V = V; a.blank = blank; a.max_length = max_length; a.max_per_frame = max_per_frame; a.scan_frames = scan_frames;
-}
-
 int rnnt_engine_greedy_decode_lstm_workspace_bytes(int n_utt, int S, int E, int Hd, int O, int L, int layer_norm, int H, int V, int has_text,
                                                    int scan_frames, size_t *out)
 {
     if (!out) return engine_fail(RNNT_ERR_INVALID_ARG, "null size pointer");
     if (int rc = ld_check_sizes(n_utt, S, E, Hd, O, L, layer_norm != 0, H, V, has_text, scan_frames)) return rc;
-    *out = (ld_layout(n_utt, E, Hd, O, L, H, V, scan_frames).total * 4 + 255) & ~(size_t)255;
+    *out = (step_layout(n_utt, E, Hd, O, L, H, V, scan_frames, true).total * 4 + 255) & ~(size_t)255;
     return RNNT_OK;
 }
 
@@ -1316,30 +1300,26 @@ int rnnt_engine_greedy_decode_lstm(const void *frames, int64_t frame_stride, int
     size_t need;
     if (int rc = rnnt_engine_greedy_decode_lstm_workspace_bytes(n_utt, S, E, Hd, O, L, layer_norm, H, V, text_W ? 1 : 0, scan_frames, &need))
         return rc;
-    if (iterations < 0) return engine_fail(RNNT_ERR_INVALID_ARG, "iterations=%d", iterations);
-    if (bad(frames) || bad(W) || bad(bias) || !utt || !state || !tokens || !workspace)
-        return engine_fail(RNNT_ERR_INVALID_ARG, "null or not 16-byte aligned pointer argument");
-    if (((uintptr_t)utt & 7) || ((uintptr_t)workspace & 255) || (state_out && ((uintptr_t)state_out & 15)))
-        return engine_fail(RNNT_ERR_INVALID_ARG, "utt must be 8-byte, state_out 16-byte and the workspace 256-byte aligned");
-    if (int rc = check_params(p, L, layer_norm != 0, "parameter")) return rc;
-    if ((text_W == nullptr) != (text_b == nullptr) || (text_W && (bad(text_W) || bad(text_b))))
-        return engine_fail(RNNT_ERR_INVALID_ARG, "text_W / text_b: both or neither, 16-byte aligned");
-    if (max_length < 2 || max_per_frame < 1 || max_frames < 1 || rows < max_frames || frame_stride < H || frame_stride % 4)
+    const DecodeCall c{frames, p, L, layer_norm != 0, text_W, text_b, W, bias, iterations, host_flag, workspace, ws_bytes, need};
+    int32_t *flag_dev;
+    if (int rc = ld_check_pointers(c, !utt || !state || !tokens, ((uintptr_t)utt & 7) || (state_out && ((uintptr_t)state_out & 15)),
+                                   "utt must be 8-byte, state_out 16-byte and the workspace 256-byte aligned"))
+        return rc;
+    if (max_length < 2 || max_per_frame < 1 || max_frames < 1 || rows < max_frames || bad_stride(frame_stride, H))
         return engine_fail(RNNT_ERR_INVALID_ARG, "max_length=%d max_per_frame=%d max_frames=%d rows=%d frame_stride=%lld", max_length,
                            max_per_frame, max_frames, rows, (long long)frame_stride);
-    if (blank < 0 || blank >= V) return engine_fail(RNNT_ERR_INVALID_ARG, "blank=%d outside [0,%d)", blank, V);
+    if (int rc = check_blank(blank, V)) return rc;
     if ((long)n_utt * max_length > 0x7fffffffL) return engine_fail(RNNT_ERR_UNSUPPORTED, "n_utt * max_length must stay below 2^31");
-    int32_t *flag_dev;
-    if (int rc = ld_host_flag(host_flag, &flag_dev)) return rc;
-    if (ws_bytes < need) return engine_fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
+    if (int rc = ld_check_flag_and_size(c, &flag_dev)) return rc;
     LdArgs a;
     a.frames = (const float *)frames; a.frame_stride = (long)frame_stride; a.rows = rows; a.utt = utt; a.n_utt = n_utt;
-    ld_model(a, p, S, E, Hd, O, L, layer_norm, eps_in, eps_lstm, eps_out, text_W, text_b, W, bias, H, V, blank, max_length, max_per_frame,
-             scan_frames);
+    ld_model(a, p, S, E, Hd, O, L, layer_norm, eps_in, eps_lstm, eps_out, text_W, text_b, H);
+    a.W = (const float *)W; a.bias = (const float *)bias; a.V = V; a.blank = blank; a.max_length = max_length; a.max_per_frame = max_per_frame;
+    a.scan_frames = scan_frames;
     a.iterations = iterations ? iterations : max_length + (max_frames + scan_frames - 1) / scan_frames + 1;
     a.init = init;
     a.host_flag = flag_dev; a.state = state; a.tokens = tokens; a.state_out = state_out;
-    const LdLayout w = ld_layout(n_utt, E, Hd, O, L, H, V, scan_frames);
+    const StepLayout w = step_layout(n_utt, E, Hd, O, L, H, V, scan_frames, true);
     float *ws = (float *)workspace;
     a.text = ws + w.text; a.x1 = ws + w.x1; a.hc = ws + w.hc; a.y = ws + w.y; a.gp = ws + w.gp;
     a.part = (float2 *)(ws + w.part); a.ctrl = (int32_t *)(ws + w.ctrl);
@@ -1378,7 +1358,7 @@ int rnnt_engine_greedy_stream_lstm_push_workspace_bytes(int n_streams, int S, in
 {
     if (!out) return engine_fail(RNNT_ERR_INVALID_ARG, "null size pointer");
     if (int rc = ld_check_sizes(n_streams, S, E, Hd, O, L, layer_norm != 0, H, V, has_text, scan_frames)) return rc;
-    *out = (ls_layout(n_streams, E, Hd, O, H, V, scan_frames).total * 4 + 255) & ~(size_t)255;
+    *out = (step_layout(n_streams, E, Hd, O, L, H, V, scan_frames, false).total * 4 + 255) & ~(size_t)255;
     return RNNT_OK;
 }
 
@@ -1395,39 +1375,35 @@ int rnnt_engine_greedy_stream_lstm_push(const void *frames, int64_t frame_stride
                                                                      &need))
         return rc;
     if (int rc = rnnt_engine_greedy_stream_lstm_bytes(n_streams, S, E, Hd, O, L, layer_norm, H, V, text_W ? 1 : 0, &need_block)) return rc;
-    if (iterations < 0) return engine_fail(RNNT_ERR_INVALID_ARG, "iterations=%d", iterations);
-    if (bad(frames) || bad(W) || bad(bias) || !push_table || !out_tokens || !block || !workspace)
-        return engine_fail(RNNT_ERR_INVALID_ARG, "null or not 16-byte aligned pointer argument");
-    if (((uintptr_t)push_table & 7) || ((uintptr_t)out_tokens & 3) || ((uintptr_t)workspace & 255) || ((uintptr_t)block & 255))
-        return engine_fail(RNNT_ERR_INVALID_ARG, "push_table must be 8-byte, out_tokens 4-byte, the workspace and the block 256-byte aligned");
-    if (int rc = check_params(p, L, layer_norm != 0, "parameter")) return rc;
-    if ((text_W == nullptr) != (text_b == nullptr) || (text_W && (bad(text_W) || bad(text_b))))
-        return engine_fail(RNNT_ERR_INVALID_ARG, "text_W / text_b: both or neither, 16-byte aligned");
-    if ((max_length != 0 && max_length < 2) || max_per_frame < 1 || max_count < 0 || rows < 1 || rows < max_count || frame_stride < H ||
-        frame_stride % 4)
+    const DecodeCall c{frames, p, L, layer_norm != 0, text_W, text_b, W, bias, iterations, host_flag, workspace, ws_bytes, need};
+    int32_t *flag_dev;
+    if (int rc = ld_check_pointers(c, !push_table || !out_tokens || !block,
+                                   ((uintptr_t)push_table & 7) || ((uintptr_t)out_tokens & 3) || ((uintptr_t)block & 255),
+                                   "push_table must be 8-byte, out_tokens 4-byte, the workspace and the block 256-byte aligned"))
+        return rc;
+    if ((max_length != 0 && max_length < 2) || max_per_frame < 1 || max_count < 0 || rows < 1 || rows < max_count || bad_stride(frame_stride, H))
         return engine_fail(RNNT_ERR_INVALID_ARG, "max_length=%d (0 or >= 2) max_per_frame=%d max_count=%d rows=%d frame_stride=%lld", max_length,
                            max_per_frame, max_count, rows, (long long)frame_stride);
-    if (blank < 0 || blank >= V) return engine_fail(RNNT_ERR_INVALID_ARG, "blank=%d outside [0,%d)", blank, V);
+    if (int rc = check_blank(blank, V)) return rc;
     const long most = (long)max_count * max_per_frame;  // labels a stream can emit in this push
     if (out_stride < 1 || out_stride < most)
         return engine_fail(RNNT_ERR_INVALID_ARG, "out_stride=%d below max_count * max_per_frame = %ld (and 1)", out_stride, most);
     const long bound = most + (max_count + scan_frames - 1) / scan_frames + 1;
     if (bound > 0x7fffffffL || (long)n_streams * out_stride > 0x7fffffffL)
         return engine_fail(RNNT_ERR_UNSUPPORTED, "max_count * max_per_frame and n_streams * out_stride must stay below 2^31");
-    int32_t *flag_dev;
-    if (int rc = ld_host_flag(host_flag, &flag_dev)) return rc;
-    if (ws_bytes < need) return engine_fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
+    if (int rc = ld_check_flag_and_size(c, &flag_dev)) return rc;
     if (bytes < need_block) return engine_fail(RNNT_ERR_WORKSPACE, "block %zu < required %zu bytes", bytes, need_block);
     LdArgs a;
     a.frames = (const float *)frames; a.frame_stride = (long)frame_stride; a.rows = rows; a.utt = push_table; a.n_utt = n_streams;
-    ld_model(a, p, S, E, Hd, O, L, layer_norm, eps_in, eps_lstm, eps_out, text_W, text_b, W, bias, H, V, blank, max_length, max_per_frame,
-             scan_frames);
+    ld_model(a, p, S, E, Hd, O, L, layer_norm, eps_in, eps_lstm, eps_out, text_W, text_b, H);
+    a.W = (const float *)W; a.bias = (const float *)bias; a.V = V; a.blank = blank; a.max_length = max_length; a.max_per_frame = max_per_frame;
+    a.scan_frames = scan_frames;
     a.iterations = iterations ? iterations : (int)bound;
     a.init = begin;
     a.stream = 1; a.tokens = out_tokens; a.tok_ld = out_stride;
     a.host_flag = flag_dev; a.state_out = nullptr;
     const LsBlock b = ls_block(n_streams, Hd, L, H);
-    const LsLayout w = ls_layout(n_streams, E, Hd, O, H, V, scan_frames);
+    const StepLayout w = step_layout(n_streams, E, Hd, O, L, H, V, scan_frames, false);
     float *bl = (float *)block, *ws = (float *)workspace;
     a.state = (int32_t *)(bl + b.state); a.hc = bl + b.hc; a.text = bl + b.text;
     a.x1 = ws + w.x1; a.y = ws + w.y; a.gp = ws + w.gp; a.part = (float2 *)(ws + w.part); a.ctrl = (int32_t *)(ws + w.ctrl);
@@ -1458,36 +1434,22 @@ int rnnt_engine_beam_decode_lstm(const void *frames, int64_t frame_stride, int r
     size_t need;
     if (int rc = rnnt_engine_beam_decode_lstm_workspace_bytes(n_utt, S, E, Hd, O, L, layer_norm, H, V, text_W ? 1 : 0, max_length, beam, &need))
         return rc;
-    if (iterations < 0) return engine_fail(RNNT_ERR_INVALID_ARG, "iterations=%d", iterations);
-    if (bad(frames) || bad(W) || bad(bias) || !utt || !state || !tokens || !scores || !workspace)
-        return engine_fail(RNNT_ERR_INVALID_ARG, "null or not 16-byte aligned pointer argument");
-    if (((uintptr_t)utt & 7) || ((uintptr_t)workspace & 255) || ((uintptr_t)scores & 7))
-        return engine_fail(RNNT_ERR_INVALID_ARG, "utt and scores must be 8-byte and the workspace 256-byte aligned");
-    if (int rc = check_params(p, L, layer_norm != 0, "parameter")) return rc;
-    if ((text_W == nullptr) != (text_b == nullptr) || (text_W && (bad(text_W) || bad(text_b))))
-        return engine_fail(RNNT_ERR_INVALID_ARG, "text_W / text_b: both or neither, 16-byte aligned");
-    if (max_per_frame < 1 || max_frames < 1 || rows < max_frames || frame_stride < H || frame_stride % 4)
+    const DecodeCall c{frames, p, L, layer_norm != 0, text_W, text_b, W, bias, iterations, host_flag, workspace, ws_bytes, need};
+    int32_t *flag_dev;
+    if (int rc = ld_check_pointers(c, !utt || !state || !tokens || !scores, ((uintptr_t)utt & 7) || ((uintptr_t)scores & 7),
+                                   "utt and scores must be 8-byte and the workspace 256-byte aligned"))
+        return rc;
+    if (max_per_frame < 1 || max_frames < 1 || rows < max_frames || bad_stride(frame_stride, H))
         return engine_fail(RNNT_ERR_INVALID_ARG, "max_per_frame=%d max_frames=%d rows=%d frame_stride=%lld", max_per_frame, max_frames, rows,
                            (long long)frame_stride);
-    if (blank < 0 || blank >= V) return engine_fail(RNNT_ERR_INVALID_ARG, "blank=%d outside [0,%d)", blank, V);
+    if (int rc = check_blank(blank, V)) return rc;
     if ((long)max_frames * max_per_frame + 1 > 0x7fffffffL)
         return engine_fail(RNNT_ERR_UNSUPPORTED, "max_frames * max_per_frame must stay below 2^31 (max_frames=%d, max_per_frame=%d)", max_frames,
                            max_per_frame);
-    int32_t *flag_dev = nullptr;
-    if (host_flag) {  // the device's address of the caller's pinned word (an ordinary host pointer is refused, never written through)
-        void *dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, host_flag, 0) != hipSuccess || !dp) {
-            (void)hipGetLastError();
-            return engine_fail(RNNT_ERR_INVALID_ARG, "host_flag is not mapped pinned host memory (hipHostMalloc / torch pin_memory)");
-        }
-        flag_dev = (int32_t *)dp;
-    }
-    if (ws_bytes < need) return engine_fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
+    if (int rc = ld_check_flag_and_size(c, &flag_dev)) return rc;
     BeamLstmArgs a{};
     a.s.n_utt = n_utt; a.s.max_length = max_length;
-    a.s.p = *p; a.s.S = S; a.s.E = E; a.s.Hd = Hd; a.s.O = O; a.s.L = L; a.s.ln = layer_norm != 0;
-    a.s.eps_in = eps_in; a.s.eps_lstm = eps_lstm; a.s.eps_out = eps_out;
-    a.s.text_W = (const float *)text_W; a.s.text_b = (const float *)text_b; a.s.H = H;
+    ld_model(a.s, p, S, E, Hd, O, L, layer_norm, eps_in, eps_lstm, eps_out, text_W, text_b, H);
     a.frames = (const float *)frames; a.frame_stride = (long)frame_stride; a.rows = rows; a.utt = utt;
     a.W = (const float *)W; a.bias = (const float *)bias; a.V = V; a.blank = blank; a.max_per_frame = max_per_frame; a.beam = beam;
     a.iterations = iterations ? iterations : max_frames * max_per_frame + 1;
