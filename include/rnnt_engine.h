@@ -281,6 +281,36 @@ int rnnt_engine_joint_align(const void *enc, const int64_t enc_strides[3], const
                             int32_t *frames, void *workspace, size_t ws_bytes, void *stream);
 
 /*
+ * CTC auxiliary head: the CTC loss of a Linear(H, V) head on the encoder output — the companion of the
+ * transducer loss in hybrid training, (1 - w) rnnt + w ctc — and the frame-wise greedy decode of the same logits.  The reference
+ * has neither; the semantics are torch.nn.functional.ctc_loss's on log_softmax(logits) with reduction "none".  Feature test: the
+ * symbols below (the ABI version stays 4).
+ *   logits [N,T,V] fp32 contiguous, V % 4 == 0 (log-softmax is fused); targets [N,U] int32 (U >= 0; entries at u >= target_lens[n]
+ *   are never read; an entry outside [0,V) is read as the nearest valid one); logit_lens / target_lens [N] int32, clamped by the
+ *   kernels into 1 .. T and 0 .. U; blank any index in [0,V); U <= 1023 (two lattice states per lane of a 1024-thread workgroup).
+ * rnnt_engine_ctc_loss_fwd_bwd:
+ *   costs [N] out: -log P(targets | logits) over the T_n x (2 U_n + 1) lattice (fp64 sums).  An utterance without a valid path
+ *       (T_n < U_n + its adjacent equal labels) has cost +inf; a NaN logit in a frame t < T_n makes that utterance's cost NaN;
+ *       the others are unaffected either way.  U_n = 0 is the one-state lattice of all-blank frames.
+ *   grad [N,T,V] out, or NULL (costs only): cost_weights[n] d costs[n] / d logits (cost_weights NULL: 1).  Frames t >= T_n, every
+ *       frame of an utterance whose cost is +inf and every frame of an utterance whose weight is 0 get exact zeros.  No atomics:
+ *       the occupancies of a repeated label are summed in a fixed order, two calls on the same inputs give the same bits.
+ *   ws: scratch of rnnt_engine_ctc_workspace_bytes(N, T, U, V) bytes, 256-byte aligned, no initialisation needed.
+ * rnnt_engine_ctc_greedy_decode: per frame t < T_n the argmax (lowest index on ties), then per utterance frames equal to their
+ *   predecessor and blanks are dropped: tokens[n, 0 .. counts[n]-1] are the labels in order (tokens [N,T] int32, the rest of a
+ *   row is scratch), counts [N].  Two launches for the whole batch, no workspace.
+ * Both only enqueue.  Checked before anything is enqueued: RNNT_ERR_INVALID_ARG (null or misaligned pointers, non-positive N, T
+ * or V, negative U, blank outside [0,V)), RNNT_ERR_UNSUPPORTED (U > 1023, V % 4 != 0), RNNT_ERR_WORKSPACE.
+ */
+int rnnt_engine_ctc_workspace_bytes(int N, int T, int U, int V, size_t *out);
+int rnnt_engine_ctc_loss_fwd_bwd(const void *logits, const int32_t *targets, const int32_t *logit_lens,
+                                 const int32_t *target_lens, int N, int T, int U, int V, int blank,
+                                 const float *cost_weights /* [N] or NULL = 1 */, float *costs /* [N] */,
+                                 float *grad /* [N,T,V] or NULL: forward only */, void *ws, size_t ws_bytes, void *stream);
+int rnnt_engine_ctc_greedy_decode(const void *logits, const int32_t *logit_lens, int N, int T, int V, int blank,
+                                  int32_t *tokens /* [N,T] */, int32_t *counts /* [N] */, void *stream);
+
+/*
  * Backward of the UNFUSED joint: given d loss / d logits (any upstream gradient, [B,T,U1,V]
  * contiguous fp32) returns the gradients autograd sends through reference rnnt/joint.py:32-39
  * (joint_ln, tanh, the broadcast add): grad_enc [B,T,H], grad_pred [B,U1,H], grad_W [V,H],

@@ -6,6 +6,8 @@ rnnt.model.RNNTModel) over hand-written HIP kernels reached through a C ABI
 """
 from . import engine, optim  # noqa: F401
 from .functional import joint_rnnt_loss, rnnt_loss, joint_logits, linear, rnnt_align, joint_rnnt_align  # noqa: F401
+from .functional import ctc_loss, ctc_greedy_decode  # noqa: F401
+from .ctc import CTCHead  # noqa: F401
 from .joint import JointNetwork  # noqa: F401
 from .predictor import ConvPredictor  # noqa: F401
 from .lstm_predictor import LSTMPredictor  # noqa: F401
@@ -15,4 +17,4 @@ from .model import RNNTModel  # noqa: F401
 from .stream import BeamStream, BeamStreamGroup, GreedyStream  # noqa: F401
 from .context import ContextGraph  # noqa: F401
 
-__all__ = ["engine", "optim", "joint_rnnt_loss", "rnnt_loss", "joint_logits", "rnnt_align", "joint_rnnt_align", "JointNetwork", "RNNTModel", "ConvPredictor", "LSTMPredictor", "AudioEncoder", "JasperBlock", "TFJSSpectrogram", "TFJSOldPiecewiseSpectrogram", "NormalizedMelSpectrogram", "GreedyStream", "BeamStream", "BeamStreamGroup", "ContextGraph"]
+__all__ = ["engine", "optim", "joint_rnnt_loss", "rnnt_loss", "joint_logits", "rnnt_align", "joint_rnnt_align", "ctc_loss", "ctc_greedy_decode", "CTCHead", "JointNetwork", "RNNTModel", "ConvPredictor", "LSTMPredictor", "AudioEncoder", "JasperBlock", "TFJSSpectrogram", "TFJSOldPiecewiseSpectrogram", "NormalizedMelSpectrogram", "GreedyStream", "BeamStream", "BeamStreamGroup", "ContextGraph"]

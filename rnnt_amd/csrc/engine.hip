@@ -1405,6 +1405,69 @@ int rnnt_engine_joint_align(const void *enc, const int64_t enc_strides[3], const
     return launch_status("rnnt_engine_joint_align");
 }
 
+// ---- CTC auxiliary head (ctc.hip).  The workspace: denom | lp_blank | lp_label | alpha | beta | links | log P | err
+static int ctc_check_dims(int N, int T, int U, int V)
+{
+    if (N <= 0 || T <= 0 || V <= 0 || U < 0) return fail(RNNT_ERR_INVALID_ARG, "non-positive dimension N=%d T=%d U=%d V=%d", N, T, U, V);
+    if (V % 4 != 0) return fail(RNNT_ERR_UNSUPPORTED, "V=%d must be a multiple of 4 (pad on the host side)", V);
+    if (U > 1023) return fail(RNNT_ERR_UNSUPPORTED, "U=%d exceeds 1023 labels (two CTC states per lane of a 1024-thread workgroup)", U);
+    return RNNT_OK;
+}
+
+static size_t ctc_carve(void *ws, int N, int T, int U, CtcArgs *a)
+{
+    const size_t rows = (size_t)N * T, Us = U > 0 ? U : 1, S2 = 2 * ((size_t)U + 1);
+    const size_t r4 = align_up(rows * 4), l4 = align_up(rows * Us * 4), s8 = align_up(rows * S2 * 8);
+    const size_t lk = align_up((size_t)N * Us * 4), lp = align_up((size_t)N * 8);
+    if (a) {
+        const uintptr_t p = (uintptr_t)ws;
+        a->denom = (float *)p; a->lpb = (float *)(p + r4); a->lpl = (float *)(p + 2 * r4);
+        a->alpha = (double *)(p + 2 * r4 + l4); a->beta = (double *)(p + 2 * r4 + l4 + s8);
+        a->link = (int32_t *)(p + 2 * r4 + l4 + 2 * s8); a->logp = (double *)(p + 2 * r4 + l4 + 2 * s8 + lk);
+        a->err = (unsigned *)(p + 2 * r4 + l4 + 2 * s8 + lk + lp);
+    }
+    return 2 * r4 + l4 + 2 * s8 + lk + lp + 256;
+}
+
+int rnnt_engine_ctc_workspace_bytes(int N, int T, int U, int V, size_t *out)
+{
+    if (!out) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument (out)");
+    if (int rc = ctc_check_dims(N, T, U, V)) return rc;
+    *out = ctc_carve(nullptr, N, T, U, nullptr);
+    return RNNT_OK;
+}
+
+int rnnt_engine_ctc_loss_fwd_bwd(const void *logits, const int32_t *targets, const int32_t *logit_lens,
+                                 const int32_t *target_lens, int N, int T, int U, int V, int blank,
+                                 const float *cost_weights, float *costs, float *grad, void *ws, size_t ws_bytes, void *stream)
+{
+    if (int rc = ctc_check_dims(N, T, U, V)) return rc;
+    if (!logits || !targets || !logit_lens || !target_lens || !costs || !ws) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument");
+    if (blank < 0 || blank >= V) return fail(RNNT_ERR_INVALID_ARG, "blank=%d outside [0,%d)", blank, V);
+    if (!aligned16(logits) || (grad && !aligned16(grad)) || ((uintptr_t)ws & 255))
+        return fail(RNNT_ERR_INVALID_ARG, "pointers must be 16-byte aligned (workspace 256)");
+    const size_t need = ctc_carve(nullptr, N, T, U, nullptr);
+    if (ws_bytes < need) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
+    CtcArgs a{};
+    a.logits = (const float *)logits; a.targets = targets; a.logit_lens = logit_lens; a.target_lens = target_lens;
+    a.weights = cost_weights; a.costs = costs; a.grad = grad;
+    a.N = N; a.T = T; a.U = U; a.V = V; a.blank = blank;
+    ctc_carve(ws, N, T, U, &a);
+    launch_ctc_loss(a, (hipStream_t)stream);
+    return launch_status("rnnt_engine_ctc_loss_fwd_bwd");
+}
+
+int rnnt_engine_ctc_greedy_decode(const void *logits, const int32_t *logit_lens, int N, int T, int V, int blank,
+                                  int32_t *tokens, int32_t *counts, void *stream)
+{
+    if (int rc = ctc_check_dims(N, T, 0, V)) return rc;
+    if (!logits || !logit_lens || !tokens || !counts) return fail(RNNT_ERR_INVALID_ARG, "null pointer argument");
+    if (blank < 0 || blank >= V) return fail(RNNT_ERR_INVALID_ARG, "blank=%d outside [0,%d)", blank, V);
+    if (!aligned16(logits)) return fail(RNNT_ERR_INVALID_ARG, "logits must be 16-byte aligned");
+    launch_ctc_greedy((const float *)logits, logit_lens, N, T, V, blank, tokens, counts, (hipStream_t)stream);
+    return launch_status("rnnt_engine_ctc_greedy_decode");
+}
+
 int rnnt_engine_run_stages(int stage_mask, int variant, const void *enc, const int64_t enc_strides[3],
                            const void *pred, const void *W, const void *bias, const int32_t *targets,
                            const int32_t *logit_lens, const int32_t *target_lens, int B, int T, int U1,

@@ -351,3 +351,17 @@ struct BeamLstmArgs {
 };
 size_t beam_lstm_workspace_bytes(int n_utt, int E, int Hd, int O, int L, int H, int V, int max_length);
 void launch_beam_decode_lstm(const BeamLstmArgs &a, hipStream_t st);  // beam.hip
+
+// ---- ctc.hip: the CTC auxiliary head.  Arrays of the loss, all in the caller's workspace: denom / lpb [N,T], lpl [N,T,max(U,1)],
+// alpha / beta [N,T,2(U+1)] fp64 by lattice state (2u: the blank before label u, 2u+1: label u), link [N,max(U,1)], logp [N] fp64, err one word.
+struct CtcArgs {
+    const float *logits;                                // [N,T,V], V % 4 == 0
+    const int32_t *targets, *logit_lens, *target_lens;  // [N,U], [N], [N]
+    const float *weights;                               // [N] or NULL (= 1): d (weight_n cost_n) / d logits
+    float *costs, *grad;                                // [N]; [N,T,V] or NULL (costs only)
+    float *denom, *lpb, *lpl; double *alpha, *beta; int32_t *link; double *logp; unsigned *err;
+    int N, T, U, V, blank;                              // U <= 1023
+};
+void launch_ctc_loss(const CtcArgs &a, hipStream_t st);
+void launch_ctc_greedy(const float *logits, const int32_t *logit_lens, int N, int T, int V, int blank, int32_t *tokens,
+                       int32_t *counts, hipStream_t st);

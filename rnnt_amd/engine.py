@@ -72,6 +72,9 @@ SIGNATURES = {
     "rnnt_engine_joint_loss_fwd_restrict": "ppppppppiiiiiifpiiippzp",
     "rnnt_engine_align": "ppppiiiiipppzp",
     "rnnt_engine_joint_align": "ppppppppiiiiiiipppzp",
+    "rnnt_engine_ctc_workspace_bytes": "iiiip",
+    "rnnt_engine_ctc_loss_fwd_bwd": "ppppiiiiippppzp",
+    "rnnt_engine_ctc_greedy_decode": "ppiiiippp",
     "rnnt_engine_joint_bwd_workspace_bytes": "iiiiiip",
     "rnnt_engine_joint_bwd": "pppppiiiiiipppppzp",
     "rnnt_engine_greedy_scan_workspace_bytes": "iiip",
@@ -194,6 +197,7 @@ EXPORTS = (
     "rnnt_engine_beam_decode_lstm_workspace_bytes", "rnnt_engine_beam_decode_lstm",
     "rnnt_engine_greedy_stream_lstm_bytes", "rnnt_engine_greedy_stream_lstm_init",
     "rnnt_engine_greedy_stream_lstm_push_workspace_bytes", "rnnt_engine_greedy_stream_lstm_push",
+    "rnnt_engine_ctc_workspace_bytes", "rnnt_engine_ctc_loss_fwd_bwd", "rnnt_engine_ctc_greedy_decode",
 )
 
 # per-call kernel variants (include/rnnt_engine.h RNNT_VARIANT_*): bit-identical results
@@ -683,6 +687,48 @@ def joint_align(enc, pred, W, bias, targets, logit_lens, target_lens, blank, *, 
     """Fused joint + best alignment (C ABI rnnt_engine_joint_align): the joint-forward GEMM of the loss, then the Viterbi sweep
     and the backtrace.  (scores [B] fp32, frames [B,U1-1] int32); workspace: the fused loss entry's."""
     return _fused(enc, pred, W, bias, targets, logit_lens, target_lens, blank, dtype, align=True)
+
+
+CTC_MAX_U = 1023  # rnnt_engine_ctc_loss_fwd_bwd: two lattice states per lane of a 1024-thread workgroup
+
+
+def ctc_loss_fwd_bwd(logits, targets, logit_lens, target_lens, blank, cost_weights=None, want_grad=True):
+    """CTC loss on logits [N,T,V] (C ABI rnnt_engine_ctc_loss_fwd_bwd): (costs [N] fp32, d sum_n cost_weights[n]
+    costs[n] / d logits or None).  targets [N,U] int32, U <= CTC_MAX_U, V % 4 == 0."""
+    dev = _check_logits_inputs(logits, targets, logit_lens, target_lens)
+    if cost_weights is not None:
+        _require_cuda(logits, cost_weights)
+        _require_dtype(torch.float32, cost_weights=cost_weights)
+        _require_contiguous(cost_weights=cost_weights)
+    N, T, V = logits.shape
+    U = targets.shape[1]
+    targets = _nonempty(targets)
+    with torch.cuda.device(dev):
+        n = ctypes.c_size_t(0)
+        _check(lib().rnnt_engine_ctc_workspace_bytes(N, T, U, V, ctypes.byref(n)))
+        ws = workspace(dev, n.value)
+        costs = torch.empty(N, dtype=torch.float32, device=dev)
+        grad = torch.empty_like(logits) if want_grad else None
+        _check(lib().rnnt_engine_ctc_loss_fwd_bwd(_p(logits), _p(targets), _p(logit_lens), _p(target_lens), N, T, U, V, int(blank),
+                                                  _p(cost_weights), _p(costs), _p(grad), _p(ws), ctypes.c_size_t(ws.numel()),
+                                                  _stream(dev)))
+    return costs, grad
+
+
+def ctc_greedy_decode(logits, logit_lens, blank):
+    """CTC greedy decode of logits [N,T,V] (C ABI rnnt_engine_ctc_greedy_decode): (tokens [N,T] int32 whose row n starts with
+    utterance n's labels, counts [N] int32).  Enqueues only."""
+    dev = _require_cuda(logits, logit_lens)
+    _require_dtype(torch.float32, logits=logits)
+    _require_dtype(torch.int32, logit_lens=logit_lens)
+    _require_contiguous(logits=logits, logit_lens=logit_lens)
+    N, T, V = logits.shape
+    with torch.cuda.device(dev):
+        tokens = torch.empty((N, T), dtype=torch.int32, device=dev)
+        counts = torch.empty(N, dtype=torch.int32, device=dev)
+        _check(lib().rnnt_engine_ctc_greedy_decode(_p(logits), _p(logit_lens), N, T, V, int(blank), _p(tokens), _p(counts),
+                                                   _stream(dev)))
+    return tokens, counts
 
 
 def _rows(x):

@@ -13,7 +13,10 @@
   rnnt_align(...), joint_rnnt_align(...)
                         forced alignment on the same lattice: the best path's
                         log-probability and the frame of every label; no autograd.
-Every operator runs on the HIP engine; CPU tensors are rejected (no fallback).
+  ctc_loss(...), ctc_greedy_decode(...)
+                        the CTC auxiliary head's loss and frame-wise decode on logits [N,T,V].
+Every operator runs on the HIP engine; CPU tensors are rejected (no fallback).  The two CTC operators alone
+also have a `backend="torch"` path with the same semantics (any device, float64): it is their oracle's carrier.
 """
 import torch
 
@@ -134,6 +137,155 @@ def rnnt_loss(logits, targets, logit_lengths, target_lengths, blank=-1, clamp=-1
     if reduction == "sum":
         return costs.sum()
     return costs
+
+
+# ---- CTC auxiliary head (DESIGN.md §4r)
+def _ctc_check_args(logits, targets, logit_lengths, target_lengths, blank, check_lengths):
+    if logits.dim() != 3:
+        raise RuntimeError("logits must have 3 dimensions [N, T, V]")
+    N, T, V = logits.shape
+    if N < 1 or T < 1 or V < 1:
+        raise RuntimeError("logits must not be empty")
+    if blank < 0:
+        blank = V + blank
+    if not 0 <= blank < V:
+        raise RuntimeError("blank must be within [0, logits.shape[-1])")
+    if targets is not None:
+        if targets.dim() != 2 or targets.shape[0] != N:
+            raise RuntimeError("targets must be [N, U]")
+        if target_lengths.dim() != 1 or target_lengths.shape[0] != N:
+            raise RuntimeError("target_lengths must be [N]")
+        if targets.dtype != torch.int32 or target_lengths.dtype != torch.int32:
+            raise RuntimeError("targets and target_lengths must be int32 type")
+    if logit_lengths.dim() != 1 or logit_lengths.shape[0] != N:
+        raise RuntimeError("logit_lengths must be [N]")
+    if logit_lengths.dtype != torch.int32:
+        raise RuntimeError("logit_lengths must be int32 type")
+    if check_lengths:  # (host-side: these synchronise, as rnnt_loss's do)
+        if int(logit_lengths.min()) < 1 or int(logit_lengths.max()) > T:
+            raise RuntimeError("logit_lengths must lie in [1, T]")
+        if targets is not None and (int(target_lengths.min()) < 0 or int(target_lengths.max()) > targets.shape[1]):
+            raise RuntimeError("target_lengths must lie in [0, U]")
+    return blank
+
+
+def _ctc_infeasible(targets, logit_lengths, target_lengths, T):
+    """[N] bool: no frame labelling of T_n frames collapses to the utterance's labels, T_n < U_n + (adjacent equal labels); the
+    lengths clamped as the kernels clamp them."""
+    N, U = targets.shape
+    Tn = logit_lengths.long().clamp(1, T)
+    Un = target_lengths.long().clamp(0, U)
+    if U < 2:
+        return Tn < Un
+    pair_live = torch.arange(1, U, device=targets.device)[None, :] < Un[:, None]
+    repeats = ((targets[:, 1:] == targets[:, :-1]) & pair_live).sum(dim=1)
+    return Tn < Un + repeats
+
+
+def _ctc_costs_torch(logits, targets, logit_lengths, target_lengths, blank):
+    """Per-utterance CTC costs by log_softmax + torch.nn.functional.ctc_loss with the engine's conventions: +inf (and, through
+    the `where`, an exactly zero gradient) for an utterance without a valid path, frames t >= T_n and labels u >= U_n ignored
+    whatever they hold.  Any device, float32 or float64."""
+    N, T, V = logits.shape
+    Tn = logit_lengths.long().clamp(1, T)
+    Un = target_lengths.long().clamp(0, targets.shape[1])
+    dead = torch.arange(T, device=logits.device)[None, :] >= Tn[:, None]
+    lp = torch.log_softmax(logits.masked_fill(dead[:, :, None], 0.0), dim=-1).transpose(0, 1)
+    tg = targets.long().clamp(0, V - 1)
+    if tg.shape[1] == 0:
+        tg = tg.new_zeros((N, 1))
+    costs = torch.nn.functional.ctc_loss(lp, tg, Tn, Un, blank=blank, reduction="none", zero_infinity=True)
+    return torch.where(_ctc_infeasible(tg[:, :targets.shape[1]], Tn, Un, T), costs.new_full((), float("inf")), costs)
+
+
+class _CTCLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, targets, logit_lengths, target_lengths, blank):
+        costs, grad = engine.ctc_loss_fwd_bwd(logits, targets, logit_lengths, target_lengths, blank,
+                                              want_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(grad)
+        return costs
+
+    @staticmethod
+    def backward(ctx, grad_costs):
+        (grad,) = ctx.saved_tensors
+        if grad is None:
+            return None, None, None, None, None
+        return grad * grad_costs.view(-1, 1, 1), None, None, None, None
+
+
+def _ctc_backend(backend, logits, U, what):
+    if backend not in ("auto", "engine", "torch"):
+        raise ValueError('backend should be one of "auto", "engine", or "torch"')
+    refusal = None
+    if not logits.is_cuda:
+        refusal = "the engine has no CPU path"
+    elif logits.dtype != torch.float32:
+        refusal = f"the engine takes float32 logits (got {logits.dtype})"
+    elif U > engine.CTC_MAX_U:
+        refusal = f"U={U} exceeds the engine's {engine.CTC_MAX_U} labels"
+    if backend == "engine" and refusal is not None:
+        raise RuntimeError(f"rnnt_amd.{what}(backend=\"engine\"): {refusal}")
+    return "torch" if backend == "torch" or refusal is not None else "engine"
+
+
+def ctc_loss(logits, targets, logit_lengths, target_lengths, blank=-1, reduction="mean", zero_infinity=False,
+             check_lengths=True, backend="auto"):
+    """CTC loss of logits [N,T,V] (batch first, log-softmax fused) against targets [N,U] int32; lengths int32 [N].
+    `reduction`: "none" (the per-utterance costs -log P), "sum", or "mean" = the MEAN OF THE PER-UTTERANCE COSTS, as rnnt_loss
+    defines it here, so that (1 - w) rnnt + w ctc mixes like for like — NOT torch.nn.functional.ctc_loss's mean, which divides
+    each cost by its target length first.  An utterance no frame labelling can produce (T_n < U_n + its adjacent equal labels)
+    has cost +inf and an exactly zero gradient (the alignment-restricted loss's convention); `zero_infinity` also sets that cost
+    to 0.  Frames t >= logit_lengths[n] and labels u >= target_lengths[n] are ignored whatever they hold.
+    `backend`: "engine" = rnnt_engine_ctc_loss_fwd_bwd (float32 HIP tensors, U <= 1023; raises otherwise),
+    "torch" = log_softmax + torch.nn.functional.ctc_loss with the same semantics (any device, float64 too), "auto" = the engine
+    where it runs.  Differentiable once, in the logits."""
+    if reduction not in ("none", "mean", "sum"):
+        raise ValueError('reduction should be one of "none", "mean", or "sum"')
+    blank = _ctc_check_args(logits, targets, logit_lengths, target_lengths, blank, check_lengths)
+    if _ctc_backend(backend, logits, targets.shape[1], "ctc_loss") == "engine":
+        V = logits.shape[-1]
+        x = logits.contiguous()
+        if V % 4 != 0:
+            x = torch.nn.functional.pad(x, (0, 4 - V % 4), value=_PAD_NEG)
+        costs = _CTCLoss.apply(x, targets.contiguous(), logit_lengths.contiguous(), target_lengths.contiguous(), blank)
+    else:
+        costs = _ctc_costs_torch(logits, targets, logit_lengths, target_lengths, blank)
+    if zero_infinity:
+        costs = torch.where(costs == float("inf"), torch.zeros_like(costs), costs)
+    if reduction == "mean":
+        return costs.mean()
+    if reduction == "sum":
+        return costs.sum()
+    return costs
+
+
+def _ctc_collapse(frames, blank):
+    out, prev = [], None
+    for tok in frames:
+        if tok != blank and tok != prev:
+            out.append(tok)
+        prev = tok
+    return out
+
+
+@torch.no_grad()
+def ctc_greedy_decode(logits, logit_lengths, blank=-1, backend="auto"):
+    """CTC greedy decode of logits [N,T,V]: per frame t < logit_lengths[n] the argmax (lowest index on ties), then frames equal
+    to their predecessor and blanks are dropped.  Returns a list of N token lists; ONE host synchronisation per call.
+    `backend` as ctc_loss's: "engine" = rnnt_engine_ctc_greedy_decode (two launches for the whole batch), "torch" = argmax on
+    the tensors' device and the collapse on the host."""
+    blank = _ctc_check_args(logits, None, logit_lengths, None, blank, False)
+    N, T, V = logits.shape
+    if _ctc_backend(backend, logits, 0, "ctc_greedy_decode") == "engine":
+        x = logits.detach().contiguous()
+        if V % 4 != 0:
+            x = torch.nn.functional.pad(x, (0, 4 - V % 4), value=_PAD_NEG)
+        tokens, counts = engine.ctc_greedy_decode(x, logit_lengths.contiguous(), blank)
+        host = torch.cat((counts[:, None], tokens), dim=1).tolist()  # the call's one synchronisation
+        return [row[1:1 + row[0]] for row in host]
+    best = torch.cat((logit_lengths.long().clamp(1, T)[:, None], logits.argmax(dim=-1)), dim=1).tolist()
+    return [_ctc_collapse(row[1:1 + row[0]], blank) for row in best]
 
 
 def _pad_hv(enc, pred, W, bias, mult=4):

@@ -32,6 +32,11 @@ class RNNTModel(torch.nn.Module):
         self.restrict_left = 0
         self.restrict_right = 0
         self._restrict_frames = None  # the frames of the call in progress (__call__)
+        # CTC auxiliary head: with a rnnt_amd.CTCHead as `ctc_head` and 0 < ctc_weight <= 1, `forward` returns
+        # (1 - ctc_weight) * rnnt + ctc_weight * ctc from the one encoder output (CTC blank = blank_idx, the mean of the per-utterance
+        # costs on both sides); None or 0: the transducer loss alone, exactly as without the attributes
+        self.ctc_head = None
+        self.ctc_weight = 0.0
         # the path the last greedy_decode / greedy_decode_many took: "persistent", "loop", "lstm_loop" (DESIGN.md §4p "Device decode")
         # or "host"; greedy_decode_many: "host" only if every utterance took the host loop
         self.last_decode_path = None
@@ -74,11 +79,29 @@ class RNNTModel(torch.nn.Module):
             reg["delay_penalty"] = self.delay_penalty
         if self._restrict_frames is not None:
             reg.update(restrict_frames=self._restrict_frames, restrict_left=self.restrict_left, restrict_right=self.restrict_right)
-        return self.joint.fused_loss(audio_features, decoder_features,
+        loss = self.joint.fused_loss(audio_features, decoder_features,
                                      targets=input_ids.int(),
                                      logit_lengths=audio_feature_lens.int(),
                                      target_lengths=input_id_lens.int(),
                                      blank=-1, reduction="mean", check_lengths=self.check_lengths, **reg)
+        w = float(self.ctc_weight)
+        if self.ctc_head is None or w == 0.0:
+            return loss
+        # hybrid CTC / RNN-T: the CTC branch reads the same encoder output
+        ctc = self.ctc_head.loss(audio_features, input_ids.int(), audio_feature_lens.int(), input_id_lens.int(),
+                                 blank=blank_idx, reduction="mean", check_lengths=self.check_lengths)
+        return (1.0 - w) * loss + w * ctc
+
+    @torch.no_grad()
+    def ctc_greedy_decode(self, mel_features: torch.Tensor, mel_feature_lens: torch.Tensor):
+        """The CTC head's greedy decode of a whole batch: argmax per encoder frame, repeats and blanks dropped —
+        no predictor, no per-token loop, one host synchronisation for the batch.  Returns a list of token lists; the blank is
+        the joint's blank_idx."""
+        if self.ctc_head is None:
+            raise RuntimeError("ctc_greedy_decode needs a ctc_head (rnnt_amd.CTCHead)")
+        audio_features = self.encoder(mel_features).permute(0, 2, 1)
+        audio_feature_lens = self.encoder.calc_output_lens(mel_feature_lens)
+        return self.ctc_head.greedy_decode(audio_features, audio_feature_lens.int(), blank=self.joint.blank_idx)
 
     def _predict(self, ids_with_start, lens_with_start):
         """The predictor's features for `forward` and `align`: a stateless predictor is called as predictor(ids); a stateful one
