@@ -91,7 +91,7 @@ void rnnt_engine_set_debug(void *buf);
 #define RNNT_VARIANT_X3_FP32_FWD 4096       /* forward GEMM + hidden by the fp32 kernel, then k_x3_make_hidden */
 #define RNNT_VARIANT_X3_FP32_DH 8192        /* dHidden + G by the fp32 kernels, then k_x3_split_g (needs _FWD too) */
 /* RNNT_DTYPE_F32_F16X2 only: switch the flush rule off for this call.  By default that route gives every lattice cell whose
- * gradient row its fp16 split provably rounds to zero (|g_scale G| < 2^-26: rnnt_amd/csrc/lattice.hip coef_cell, x2.hip) the
+ * gradient row its fp16 split provably rounds to zero (|g_scale G| < 2^-26: rnnt_amd/csrc/lattice.hip k_coef, x2.hip) the
  * coefficients of a cell outside the lattice; dHidden tiles and 16-cell dW k-steps without a live cell are then skipped.  With this
  * bit no cell is flagged: tiles and k-steps are skipped by the utterances' lengths only.  costs, grad_enc and grad_pred are
  * bit-identical with and without it; grad_W / grad_bias differ in summation order only (the split-K ranges cut the list of live

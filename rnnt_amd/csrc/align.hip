@@ -163,14 +163,12 @@ __global__ __launch_bounds__(64) void k_backtrace(
     for (int j = lane; j < Ub; j += 64) fr[j] = sfr[j];
 }
 
-void launch_align(const float *lpb_s, const float *lpe_s, void *bp, const int32_t *logit_lens,
-                  const int32_t *target_lens, float *scores, int32_t *frames, int B, int U1, int D,
-                  hipStream_t st)
+void launch_align(const LatticeArgs &a, void *bp, float *scores, int32_t *frames, hipStream_t st)
 {
-    const int NT = ((U1 + 63) / 64) * 64;
+    const int NT = ((a.U1 + 63) / 64) * 64;
     const size_t lds = 2 * (size_t)(NT + 1) * sizeof(double);
-    hipLaunchKernelGGL(k_viterbi, dim3(B), dim3(NT), lds, st, lpb_s, lpe_s, (u64 *)bp, logit_lens,
-                       target_lens, scores, U1, D);
-    hipLaunchKernelGGL(k_backtrace, dim3(B), dim3(64), 0, st, (const u64 *)bp, logit_lens,
-                       target_lens, (const float *)scores, frames, U1, D);
+    hipLaunchKernelGGL(k_viterbi, dim3(a.B), dim3(NT), lds, st, a.lpb_s, a.lpe_s, (u64 *)bp, a.logit_lens,
+                       a.target_lens, scores, a.U1, a.D);
+    hipLaunchKernelGGL(k_backtrace, dim3(a.B), dim3(64), 0, st, (const u64 *)bp, a.logit_lens,
+                       a.target_lens, (const float *)scores, frames, a.U1, a.D);
 }

@@ -3,7 +3,7 @@
 //   k_ctc_gather   logits [N,T,V] -> per frame: the fp32 log-sum-exp denom[n,t], lp_blank[n,t], lp_label[n,t,u] (u < U_n)
 //   k_ctc_links    per utterance: "next position with the same label" links, for the deterministic scatter of k_ctc_grad
 //   k_ctc_chain    alpha / beta over the T x (2U+1) lattice, one workgroup per (utterance, direction), two states per lane
-//   k_ctc_status   a failed chain (bounded spin ran out) turns every cost of the call into NaN
+//                  (a failed chain — bounded spin ran out — turns every cost and log P of the call into NaN: launch_chain_status)
 //   k_ctc_grad     d cost / d logits, one wave per frame, every sum in a fixed order
 //   k_ctc_argmax, k_ctc_collapse   greedy decode: argmax per frame, then drop repeats and blanks per utterance
 //
@@ -11,10 +11,8 @@
 // alpha_t(s) and beta_t(s) both INCLUDE the emission of frame t, so the posterior occupancy of state s at frame t is
 // exp(alpha + beta - lp_t(s) - log P).  alpha / beta are fp64 (they reach ~1e4 in magnitude and the occupancy needs
 // alpha + beta - log P, a cancellation fp32 cannot hold to 1e-4); the log-add-exp correction is fp32 on exp2 / log2.
-#include "common.hpp"
+#include "lattice_common.hpp"  // wave_shift, lse2_safe, row_max_sumexp, chain_mailbox_bytes: shared with lattice.hip
 #include "kernels.hpp"
-
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 
 #define CTC_NO_LINK 0xffff    // k_ctc_links: no later position carries this label
 #define CTC_HEAD 0x10000      // k_ctc_links: no earlier position carries this label
@@ -39,20 +37,8 @@ __global__ __launch_bounds__(256) void k_ctc_gather(
     const int n = (int)(row / T), t = (int)(row - (long)n * T);
     if (t >= len_t(logit_lens, n, T)) return;
     const float *x = logits + row * V;
-    float m = RNNT_NEG_INF;
-    for (int v = lane * 4; v < V; v += 256) {
-        const f32x4 q = *(const f32x4 *)(x + v);
-        m = fmaxf(m, fmaxf(fmaxf(q[0], q[1]), fmaxf(q[2], q[3])));
-    }
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) m = fmaxf(m, __shfl_xor(m, k, 64));
-    float s = 0.f;  // (a NaN logit is skipped by the max and lands here: NaN denominator, NaN lp_blank, NaN cost)
-    for (int v = lane * 4; v < V; v += 256) {
-        const f32x4 q = *(const f32x4 *)(x + v);
-        s += __expf(q[0] - m) + __expf(q[1] - m) + __expf(q[2] - m) + __expf(q[3] - m);
-    }
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) s += __shfl_xor(s, k, 64);
+    float m, s;  // (a NaN logit is skipped by the max and lands in the sum: NaN denominator, NaN lp_blank, NaN cost)
+    row_max_sumexp(x, V, lane, m, s);
     const float den = m + logf(s);
     if (lane == 0) {
         denom[row] = den;
@@ -84,25 +70,8 @@ __global__ __launch_bounds__(1024) void k_ctc_links(const int32_t *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------
-// (lattice.hip's wave_shift: a double moved one lane up by two DPP moves; the lane without a source keeps `fill`)
-template <int CTRL>
-__device__ __forceinline__ double ctc_wave_shift(double v, double fill)
-{
-    const u32x2_t x = __builtin_bit_cast(u32x2_t, v), f = __builtin_bit_cast(u32x2_t, fill);
-    u32x2_t r;
-    r[0] = (unsigned)__builtin_amdgcn_update_dpp((int)f[0], (int)x[0], CTRL, 0xf, 0xf, false);
-    r[1] = (unsigned)__builtin_amdgcn_update_dpp((int)f[1], (int)x[1], CTRL, 0xf, 0xf, false);
-    return __builtin_bit_cast(double, r);
-}
-
-// log(exp a + exp b [+ exp c]) with fp64 maximum and fp32 correction (< ln 3) on the hardware exp2 / log2; -inf-safe: a state
-// INSIDE the lattice may have no reachable predecessor (and an infeasible utterance has none at the end)
-__device__ __forceinline__ double ctc_lse2(double a, double b)
-{
-    const double m = fmax(a, b);
-    const float d = m == (double)RNNT_NEG_INF ? 0.f : -fabsf((float)(a - b));
-    return m + (double)(__builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f(d * RNNT_LOG2E)) * 0.6931471805599453f);
-}
+// log(exp a + exp b + exp c) with fp64 maximum and fp32 correction (< ln 3) on the hardware exp2 / log2; -inf-safe as lse2_safe is:
+// a state INSIDE the lattice may have no reachable predecessor (and an infeasible utterance has none at the end)
 __device__ __forceinline__ double ctc_lse3(double a, double b, double c)
 {
     const double m = fmax(a, fmax(b, c));
@@ -211,7 +180,7 @@ __device__ __forceinline__ void ctc_chain(
                 if (has_cons && !gave_up && tg != k) {  // wave-uniform; rare once the waves have settled a step apart
                     for (int spin = 0; tg != k && spin < (1 << 22); ++spin) { tg = mtag[cbase + k - 1]; bv = mval[cbase + k - 1]; }
                     // the producer never published step k - 1 (cannot happen while the workgroup is resident): raise the error
-                    // word — k_ctc_status then turns every cost of the call into NaN — and wait for nothing any more, so that
+                    // word — k_chain_status then turns every cost of the call into NaN — and wait for nothing any more, so that
                     // a failed sweep still ends after ONE exhausted spin per wave
                     if (tg != k) {
                         gave_up = true;
@@ -221,9 +190,9 @@ __device__ __forceinline__ void ctc_chain(
             } else {
                 bv = w > 0 ? mval[((k - 1) & 1) * NW + w - 1] : NINF;
             }
-            const double nb = ctc_wave_shift<0x138>(a1, bv);  // label state of lane j - 1 at step k - 1
+            const double nb = wave_shift<0x138>(a1, bv);  // label state of lane j - 1 at step k - 1
             if (MBOX && has_cons) { tg = mtag[cbase + k]; bv = mval[cbase + k]; }  // next step's, early (k < T: the slot exists)
-            const double v0 = (double)fminf(lb, 0.f) + ctc_lse2(a0, nb);
+            const double v0 = (double)fminf(lb, 0.f) + lse2_safe(a0, nb);
             const double v1 = (double)fminf(ll, 0.f) + ctc_lse3(a1, a0, skip ? nb : NINF);
             a0 = b_ok ? v0 : NINF;
             a1 = l_ok ? v1 : NINF;
@@ -241,7 +210,7 @@ __device__ __forceinline__ void ctc_chain(
     if (Un > 0 && j == Un - 1) s_fin[1] = a1;
     const int any_bad = __syncthreads_or(bad ? 1 : 0);  // (every wave arrives: all spins are bounded)
     if (DIR == 1 && j == 0) {
-        const double lp = ctc_lse2(s_fin[0], s_fin[1]);
+        const double lp = lse2_safe(s_fin[0], s_fin[1]);
         logp[n] = any_bad ? (double)__builtin_nanf("") : lp;
         costs[n] = any_bad ? __builtin_nanf("") : (float)(-lp);
     }
@@ -257,13 +226,6 @@ __global__ __launch_bounds__(1024) void k_ctc_chain(
         ctc_chain<0, MBOX>(lpb, lpl, alpha, targets, logit_lens, target_lens, costs, logp, T, U, V, err);
     else
         ctc_chain<1, MBOX>(lpb, lpl, beta, targets, logit_lens, target_lens, costs, logp, T, U, V, err);
-}
-
-// a wave ran out of its bounded spin: a loud NaN in every cost (and, through log P, in every gradient) of the call
-__global__ void k_ctc_status(const unsigned *__restrict__ err, float *__restrict__ costs, double *__restrict__ logp, int N)
-{
-    if (*err == 0u) return;
-    for (int n = threadIdx.x; n < N; n += blockDim.x) { costs[n] = __builtin_nanf(""); logp[n] = (double)__builtin_nanf(""); }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -399,24 +361,18 @@ __global__ __launch_bounds__(1024) void k_ctc_collapse(const int32_t *__restrict
 }
 
 // ---------------------------------------------------------------------------------------
-size_t ctc_chain_mailbox_bytes(int T, int U)
-{
-    const int NW = (U + 1 + 63) / 64;
-    return (size_t)(NW - 1) * T * 12;  // 8 B value + 4 B tag per boundary and step
-}
-
 void launch_ctc_loss(const CtcArgs &a, hipStream_t st)
 {
     const long rows = (long)a.N * a.T;
     const int NW = (a.U + 1 + 63) / 64;
     hipLaunchKernelGGL(k_ctc_gather, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a.logits, a.targets, a.logit_lens,
                        a.target_lens, a.denom, a.lpb, a.lpl, a.N, a.T, a.U, a.V, a.blank);
-    const size_t mbox = ctc_chain_mailbox_bytes(a.T, a.U);
+    const size_t mbox = chain_mailbox_bytes(a.U + 1, a.T);  // lane j owns the states 2j and 2j + 1: U + 1 columns
     if (mbox <= 64 * 1024) {
         if (NW > 1) launch_fill32(a.err, 0u, 4, st);  // one wave: no mailbox, no spin
         hipLaunchKernelGGL(k_ctc_chain<true>, dim3(a.N, 2), dim3(64 * NW), (mbox + 15) / 16 * 16, st, a.lpb, a.lpl, a.alpha,
                            a.beta, a.targets, a.logit_lens, a.target_lens, a.costs, a.logp, a.T, a.U, a.V, a.err);
-        if (NW > 1) hipLaunchKernelGGL(k_ctc_status, dim3(1), dim3(64), 0, st, a.err, a.costs, a.logp, a.N);
+        if (NW > 1) launch_chain_status(a.err, a.costs, a.logp, a.N, st);  // (NaN in log P: in every gradient of the call too)
     } else {
         hipLaunchKernelGGL(k_ctc_chain<false>, dim3(a.N, 2), dim3(64 * NW), (size_t)2 * NW * 8, st, a.lpb, a.lpl, a.alpha,
                            a.beta, a.targets, a.logit_lens, a.target_lens, a.costs, a.logp, a.T, a.U, a.V, a.err);

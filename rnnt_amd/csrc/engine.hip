@@ -63,15 +63,17 @@ struct ControlBlock {
 static_assert(sizeof(ControlBlock) == 1024 && offsetof(ControlBlock, fwd_tile) == 512 && offsetof(ControlBlock, x2_scales) == 640 &&
               offsetof(ControlBlock, lattice_err) == 768 && offsetof(ControlBlock, ep_flag) == 896, "control block map");
 
-// the loss arrays; carve_loss_ws: the standalone loss entries' workspace, denom_s | lpb_s | lpe_s | alpha_s | beta_s | coef | err (256 bytes)
-struct LossWs { float *denom_s, *lpb_s, *lpe_s; double *alpha_s, *beta_s; CellCoef *coef; unsigned *err; size_t bytes; };
-LossWs carve_loss_ws(void *workspace, int B, int T, int U1)
+// The loss arrays and the dimensions of LatticeArgs (kernels.hpp), filled here for every caller: the standalone loss entries' workspace,
+// denom_s | lpb_s | lpe_s | alpha_s | beta_s | coef | err (256 bytes), which layout() also places inside the fused one.  Returns its bytes.
+size_t carve_loss_ws(void *workspace, int B, int T, int U1, LatticeArgs &a)
 {
     const size_t skew = (size_t)B * ((size_t)T + U1 - 1) * U1, cells = (size_t)B * T * U1;
     const size_t s4 = align_up(skew * 4), s8 = align_up(skew * 8), co = 3 * s4 + 2 * s8, er = co + align_up(cells * 16);
     const uintptr_t p = (uintptr_t)workspace;
-    return LossWs{(float *)p, (float *)(p + s4), (float *)(p + 2 * s4), (double *)(p + 3 * s4), (double *)(p + 3 * s4 + s8),
-                  (CellCoef *)(p + co), (unsigned *)(p + er), er + 256};
+    a.denom_s = (float *)p; a.lpb_s = (float *)(p + s4); a.lpe_s = (float *)(p + 2 * s4); a.alpha_s = (double *)(p + 3 * s4);
+    a.beta_s = (double *)(p + 3 * s4 + s8); a.coef = (CellCoef *)(p + co); a.err = (unsigned *)(p + er);
+    a.B = B; a.T = T; a.U1 = U1; a.D = T + U1 - 1;
+    return er + 256;
 }
 
 int check_dims(int B, int T, int U1, int H, int V, int dtype, bool need_h)
@@ -154,7 +156,8 @@ void layout(int B, int T, int U1, int H, int V, int dtype, rnnt_engine_ws_layout
         L->logits = o;   o += align_up((rows_pad + 16) * V * 4);
         L->hidden = o;   o += align_up((rows_pad + 16) * H * 4);
     }
-    const LossWs w = carve_loss_ws((void *)o, B, T, U1);  // the loss arrays: the standalone entries' carve, without its error word
+    LatticeArgs w{};
+    carve_loss_ws((void *)o, B, T, U1, w);  // the loss arrays: the standalone entries' carve, without its error word
     L->denom_s = (size_t)w.denom_s; L->lpb_s = (size_t)w.lpb_s; L->lpe_s = (size_t)w.lpe_s;
     L->alpha_s = (size_t)w.alpha_s; L->beta_s = (size_t)w.beta_s; L->coef = (size_t)w.coef; o = (size_t)w.err;
     L->wpack = o;
@@ -251,22 +254,27 @@ enum { ST_PROD = 1, ST_FWD = 2, ST_LATTICE = 4, ST_COEF = 8, ST_DH = 16, ST_DH_R
 // bits of the diagnostic word (-DRNNT_ABLATE builds) that are HOST-side experiments of the fp32 route
 enum { ABLATE_NO_HIDDEN = 8, ABLATE_SEPARATE_G = 32, ABLATE_SEPARATE_HIDDEN = 64, ABLATE_FWD_LDS_RING = 128, ABLATE_FWD_ONE_WG = 256 };
 
-// what the lattice and coefficient stages read (loss_stages): the fused routes' and the standalone loss entry's
-struct LossCall {
-    LossWs w;
-    const int32_t *targets, *logit_lens, *target_lens; float *costs;
-    int B, T, U1, stages /* ST_* mask */; float grad_scale, fastemit, delay; hipStream_t st;
-    const int32_t *restrict_frames; int restrict_left, restrict_right;  // the *_restrict entries; null: no restriction
-};
+// what the lattice and coefficient stages read (loss_stages), the fused routes' and the standalone loss entry's: the stages' argument block
+// (carve_loss_ws, then the call's inputs and options: loss_call) and which of them run, where
+struct LossCall : LatticeArgs { int stages /* ST_* mask */; hipStream_t st; };
+void loss_call(LossCall &c, void *arrays, const int32_t *targets, const int32_t *logit_lens, const int32_t *target_lens, float *costs, int B,
+               int T, int U1, int stages, float grad_scale, float fastemit, float delay, hipStream_t st, const int32_t *restrict_frames,
+               int restrict_left, int restrict_right)
+{
+    carve_loss_ws(arrays, B, T, U1, c);
+    c.targets = targets; c.logit_lens = logit_lens; c.target_lens = target_lens; c.costs = costs; c.stages = stages; c.st = st;
+    c.grad_scale = grad_scale; c.fastemit = fastemit; c.delay = delay;
+    c.restrict_frames = restrict_frames; c.restrict_left = restrict_left; c.restrict_right = restrict_right;
+}
 
 // One fused call after validation: what the routes and the argument fillers read.  The standalone joint entries fill
-// what their launches read: fwd_args takes dims, the enc view, pred, bias and logits (cb may be null, w empty); bwd_args also ws, L, cb.
+// what their launches read: fwd_args takes dims, the enc view, pred, bias and logits (cb may be null, the loss arrays too); bwd_args also ws, L, cb.
 struct FusedCall : LossCall {
-    int H, V, blank, n_cu;
+    int H, n_cu;  // (V and blank: LatticeArgs')
     const float *enc, *pred, *W, *bias; long enc_sb, enc_st;  // enc: the resolved view (resolve_enc)
     float *grad_enc, *grad_pred, *grad_W, *grad_bias;
     rnnt_engine_ws_layout L;
-    char *ws; ControlBlock *cb; float *logits;
+    char *ws; ControlBlock *cb; float *joint_logits;
     bool separate_g, separate_hidden, fwd_lds_ring, fwd_one_wg_per_tile, no_hidden;  // the fp32 route's forms: RNNT_VARIANT_*, ABLATE_*
     bool x3_fp32_fwd, x3_fp32_dh;  // split routes: the stage runs on the fp32 route's kernels (RNNT_VARIANT_X3_FP32_*, or a shape not covered)
     bool x2_no_flush;              // f16x2: no cell is flushed (RNNT_VARIANT_X2_NO_FLUSH_SKIP, or a regularised loss)
@@ -280,8 +288,8 @@ JointFwdArgs fwd_args(const FusedCall &c, const float *wpack, const float *hidde
     JointFwdArgs f{};
     f.enc = c.enc; f.enc_sb = c.enc_sb; f.enc_st = c.enc_st; f.pred = c.pred; f.logit_lens = c.logit_lens; f.target_lens = c.target_lens;
     f.B = c.B; f.T = c.T; f.U1 = c.U1; f.H = c.H; f.V = c.V; f.blank = c.blank; f.ablate = c.ablate; f.debug = c.debug;
-    f.wpack = wpack; f.hidden = hidden; f.make_hidden = make_hidden; f.bias = c.bias; f.targets = c.targets; f.logits = c.logits;
-    f.denom_s = c.w.denom_s; f.lpb_s = c.w.lpb_s; f.lpe_s = c.w.lpe_s; f.D = c.L.D; f.counter = c.cb ? c.cb->fwd_tile : nullptr; f.n_cu = c.n_cu;
+    f.wpack = wpack; f.hidden = hidden; f.make_hidden = make_hidden; f.bias = c.bias; f.targets = c.targets; f.logits = c.joint_logits;
+    f.denom_s = c.denom_s; f.lpb_s = c.lpb_s; f.lpe_s = c.lpe_s; f.D = c.L.D; f.counter = c.cb ? c.cb->fwd_tile : nullptr; f.n_cu = c.n_cu;
     return f;
 }
 
@@ -290,7 +298,7 @@ JointBwdArgs bwd_args(const FusedCall &c)
     JointBwdArgs g{};
     g.enc = c.enc; g.enc_sb = c.enc_sb; g.enc_st = c.enc_st; g.pred = c.pred; g.logit_lens = c.logit_lens; g.target_lens = c.target_lens;
     g.B = c.B; g.T = c.T; g.U1 = c.U1; g.H = c.H; g.V = c.V; g.blank = c.blank; g.ablate = c.ablate; g.debug = c.debug;
-    g.W = c.W; g.logits = c.logits; g.coef = c.w.coef; g.hidden = f32_at(c, c.L.hidden); g.rows_pad = (long)c.L.rows_pad;
+    g.W = c.W; g.logits = c.joint_logits; g.coef = c.coef; g.hidden = f32_at(c, c.L.hidden); g.rows_pad = (long)c.L.rows_pad;
     g.slab_enc = f32_at(c, c.L.slab_enc); g.slab_pred = f32_at(c, c.L.slab_pred);
     g.slab_w = f32_at(c, c.L.slab_w); g.slab_b = f32_at(c, c.L.slab_b);
     g.grad_enc = c.grad_enc; g.grad_pred = c.grad_pred; g.grad_W = c.grad_W; g.grad_bias = c.grad_bias;
@@ -305,8 +313,8 @@ template <class Args> Args split_args(const FusedCall &c, size_t wpack_fwd_bytes
     Args h{};
     h.enc = c.enc; h.enc_sb = c.enc_sb; h.enc_st = c.enc_st; h.pred = c.pred; h.logit_lens = c.logit_lens; h.target_lens = c.target_lens;
     h.B = c.B; h.T = c.T; h.U1 = c.U1; h.H = c.H; h.V = c.V; h.blank = c.blank; h.ablate = c.ablate; h.debug = c.debug;
-    h.W = c.W; h.bias = c.bias; h.targets = c.targets; h.coef = c.w.coef; h.hidden = (unsigned short *)(c.ws + c.L.hidden);
-    h.denom_s = c.w.denom_s; h.lpb_s = c.w.lpb_s; h.lpe_s = c.w.lpe_s; h.D = c.L.D;
+    h.W = c.W; h.bias = c.bias; h.targets = c.targets; h.coef = c.coef; h.hidden = (unsigned short *)(c.ws + c.L.hidden);
+    h.denom_s = c.denom_s; h.lpb_s = c.lpb_s; h.lpe_s = c.lpe_s; h.D = c.L.D;
     h.slab_enc = f32_at(c, c.L.slab_enc); h.slab_pred = f32_at(c, c.L.slab_pred);
     h.slab_w = f32_at(c, c.L.slab_w); h.slab_b = f32_at(c, c.L.slab_b);
     h.rows_pad = (long)c.L.rows_pad; h.rows_alloc = bf16_rows_alloc(c.L.rows_pad);
@@ -318,7 +326,7 @@ template <class Args> Args split_args(const FusedCall &c, size_t wpack_fwd_bytes
 Bf16Args bf16_args(const FusedCall &c)
 {
     Bf16Args h = split_args<Bf16Args>(c, bf16_wpack_fwd_bytes(c.H, c.V));
-    h.logits = (unsigned short *)c.logits; h.dw_prog = c.cb->dw_prog(c.B);
+    h.logits = (unsigned short *)c.joint_logits; h.dw_prog = c.cb->dw_prog(c.B);
     return h;
 }
 
@@ -341,46 +349,25 @@ X3Args x3_args(const FusedCall &c, size_t wpack_fwd_bytes, const OperandScales &
     X3Args h = split_args<X3Args>(c, wpack_fwd_bytes);
     h.g_scale = s.g_scale; h.dw_rescale = s.dw_rescale; h.db_rescale = s.db_rescale; h.scales = c.cb->x2_scales;
     h.ep_enc = f32_at(c, c.L.ep); h.ep_pred = h.ep_enc + (size_t)c.B * c.T * c.H; h.ep_flag = c.cb->ep_flag;
-    h.logits = c.logits; h.g_lo = (unsigned short *)(c.ws + c.L.g_lo); h.n_ublk16 = (c.U1 + 15) / 16;
+    h.logits = c.joint_logits; h.g_lo = (unsigned short *)(c.ws + c.L.g_lo); h.n_ublk16 = (c.U1 + 15) / 16;
     h.plane_stride = h.rows_alloc * (long)c.H; h.counter = c.cb->fwd_tile; h.n_cu = c.n_cu;
     return h;
 }
 
-// lattice sweep and coefficients (every route): the delay penalty goes on lp_emit before the sweep and its cost shift comes off after it,
-// FastEmit's coefficients replace k_coef's; zero options launch exactly the plain loss's kernels.
-// flush_log2: the f16x2 route's threshold (lattice.hip coef_cell), or null: the plain coefficients.
-// A restricted call masks lp_emit in the pass that applies the delay penalty and runs the -inf-safe sweep and coefficients.
-void loss_stages(const LossCall &c, const double *flush_log2 = nullptr, float flush_lin = 0.f)
+// lattice sweep and coefficients (every route): the pass over lp_emit — the delay penalty and the alignment restriction
+// (§4n) — before the sweep, the penalty's cost shift off after it, then the coefficients; zero options launch exactly the plain loss's
+// kernels.  flush: the f16x2 route's thresholds (lattice.hip k_coef), or null: no flush rule.  Which sweep and which coefficient kernel run is
+// the launchers' business.
+void loss_stages(const LossCall &c, const OperandScales *flush = nullptr)
 {
-    const LossWs &w = c.w; const int D = c.T + c.U1 - 1;
-    if (c.restrict_frames) {
-        if (c.stages & ST_LATTICE) {
-            launch_restrict(w.lpe_s, c.restrict_frames, c.logit_lens, c.target_lens, c.B, c.T, c.U1, D, c.restrict_left, c.restrict_right,
-                            c.delay, c.st);
-            launch_lattice(w.lpb_s, w.lpe_s, w.alpha_s, w.beta_s, c.logit_lens, c.target_lens, c.costs, c.B, c.U1, D, w.err, c.st, true);
-            if (c.delay > 0.f) launch_delay_cost(w.beta_s, c.logit_lens, c.target_lens, c.costs, c.B, c.T, c.U1, D, c.delay, c.st);
-        }
-        if (c.stages & ST_COEF)
-            launch_coef_restrict(w.alpha_s, w.beta_s, w.denom_s, w.lpb_s, w.lpe_s, c.targets, c.logit_lens, c.target_lens, w.coef,
-                                 c.B, c.T, c.U1, D, c.grad_scale, c.fastemit, flush_log2, flush_lin, c.st);
-        return;
-    }
+    LatticeArgs a = c;
+    if (flush) { a.flush = true; a.flush_log2 = flush->flush_log2; a.flush_lin = flush->flush_lin; }
     if (c.stages & ST_LATTICE) {
-        if (c.delay > 0.f) launch_delay_penalty(w.lpe_s, c.logit_lens, c.target_lens, c.B, c.T, c.U1, D, c.delay, c.st);
-        launch_lattice(w.lpb_s, w.lpe_s, w.alpha_s, w.beta_s, c.logit_lens, c.target_lens, c.costs, c.B, c.U1, D, w.err, c.st);
-        if (c.delay > 0.f) launch_delay_cost(w.beta_s, c.logit_lens, c.target_lens, c.costs, c.B, c.T, c.U1, D, c.delay, c.st);
+        if (a.restrict_frames || a.delay > 0.f) launch_lp_emit(a, c.st);
+        launch_lattice(a, c.st);
+        if (a.delay > 0.f) launch_delay_cost(a, c.st);
     }
-    if (c.stages & ST_COEF) {
-        if (c.fastemit > 0.f)
-            launch_coef_fastemit(w.alpha_s, w.beta_s, w.denom_s, w.lpb_s, w.lpe_s, c.targets, c.logit_lens, c.target_lens, w.coef,
-                                 c.B, c.T, c.U1, D, c.grad_scale, c.fastemit, c.st);
-        else if (flush_log2)
-            launch_coef_flush(w.alpha_s, w.beta_s, w.denom_s, w.lpb_s, w.lpe_s, c.targets, c.logit_lens, c.target_lens, w.coef,
-                              c.B, c.T, c.U1, D, c.grad_scale, *flush_log2, flush_lin, c.st);
-        else
-            launch_coef(w.alpha_s, w.beta_s, w.denom_s, w.lpb_s, w.lpe_s, c.targets, c.logit_lens, c.target_lens, w.coef,
-                        c.B, c.T, c.U1, D, c.grad_scale, c.st);
-    }
+    if (c.stages & ST_COEF) launch_coef(a, c.st);
 }
 
 void zero_unwritten_hidden(const FusedCall &c, float *hidden)  // what a forward filling fp32 hidden leaves: padding rows, dead cells
@@ -497,7 +484,7 @@ int route_f16x2(const FusedCall &c)
     if (c.stages & ST_PROD) { launch_x2_zero_padding(h, 1, c.st); launch_x2_pack_w(h, c.cb->x2_scales, c.st); launch_x2_make_ep(h, c.st); }
     if (c.x3_fp32_fwd) standin_forward(c, h, launch_x2_make_hidden);
     else if (c.stages & ST_FWD) launch_joint_fwd_x2(h, c.st);
-    loss_stages(c, &s.flush_log2, s.flush_lin);
+    loss_stages(c, &s);
     if (c.stages & ST_COEF) launch_x2_live(h, c.st);  // tile flags, k-step and group bitmaps / lists, counts: from the coefficients
     if (c.stages & ST_DH) {
         launch_x2_zero_padding(h, 2, c.st);
@@ -560,13 +547,12 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
                         "shape k_joint_fwd_x3 / k_dhidden_x3 do not cover) needs total + aux_bytes of rnnt_engine_workspace_layout",
                         ws_bytes, c.L.total + c.L.aux_bytes);
     }
-    c.B = B; c.T = T; c.U1 = U1; c.H = H; c.V = V; c.blank = blank; c.pred = (const float *)pred; c.W = (const float *)W;
-    c.bias = (const float *)bias; c.targets = targets; c.logit_lens = logit_lens; c.target_lens = target_lens; c.costs = costs;
+    c.H = H; c.V = V; c.blank = blank; c.pred = (const float *)pred; c.W = (const float *)W; c.bias = (const float *)bias;
     c.grad_enc = (float *)grad_enc; c.grad_pred = (float *)grad_pred; c.grad_W = (float *)grad_W; c.grad_bias = (float *)grad_bias;
-    c.stages = stages; c.grad_scale = grad_scale; c.fastemit = fastemit; c.delay = delay; c.n_cu = device_cus(); c.st = (hipStream_t)stream;
-    c.restrict_frames = restrict_frames; c.restrict_left = restrict_left; c.restrict_right = restrict_right;
-    c.ws = (char *)workspace; c.cb = (ControlBlock *)(c.ws + c.L.counters); c.logits = f32_at(c, c.L.logits);
-    c.w = carve_loss_ws(c.ws + c.L.denom_s, B, T, U1); c.w.err = c.cb->lattice_err;  // (layout() places the arrays by the same carve)
+    c.n_cu = device_cus(); c.ws = (char *)workspace; c.cb = (ControlBlock *)(c.ws + c.L.counters); c.joint_logits = f32_at(c, c.L.logits);
+    loss_call(c, c.ws + c.L.denom_s, targets, logit_lens, target_lens, costs, B, T, U1, stages, grad_scale, fastemit, delay,
+              (hipStream_t)stream, restrict_frames, restrict_left, restrict_right);  // (layout() places the arrays by the same carve)
+    c.err = c.cb->lattice_err;
     resolve_enc(enc, enc_strides, B, T, H, f32_at(c, c.L.enc_copy), c.st, &c.enc, &c.enc_sb, &c.enc_st);
     if (dtype == RNNT_DTYPE_BF16) return route_bf16(c);
     if (dtype == RNNT_DTYPE_F32_BF16X3) return route_bf16x3(c);
@@ -640,7 +626,8 @@ int rnnt_engine_loss_workspace_bytes(int B, int T, int U1, int V, int dtype, siz
 {
     if (!out) return fail(RNNT_ERR_INVALID_ARG, "null size pointer");
     if (int rc = check_dims(B, T, U1, 4, V, dtype, false)) return rc;
-    *out = carve_loss_ws(nullptr, B, T, U1).bytes;
+    LatticeArgs a{};
+    *out = carve_loss_ws(nullptr, B, T, U1, a);
     return RNNT_OK;
 }
 
@@ -668,7 +655,7 @@ int rnnt_engine_joint_fwd(const void *enc, const int64_t enc_strides[3], const v
     if (ws_bytes < need) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
     FusedCall c{};  // the plain joint: no loss arrays, no control block (one workgroup per tile); workspace: W pack | enc copy
     c.B = B; c.T = T; c.U1 = U1; c.H = H; c.V = V; c.blank = V - 1; c.L.D = T + U1 - 1;
-    c.pred = (const float *)pred; c.W = (const float *)W; c.bias = (const float *)bias; c.logits = (float *)logits;
+    c.pred = (const float *)pred; c.W = (const float *)W; c.bias = (const float *)bias; c.joint_logits = (float *)logits;
     c.ablate = g_flags; c.debug = g_debug; c.st = (hipStream_t)stream;
     float *wpack = (float *)workspace, *enc_copy = (float *)((char *)workspace + align_up(wpack_floats(H, V) * 4));
     resolve_enc(enc, enc_strides, B, T, H, enc_copy, c.st, &c.enc, &c.enc_sb, &c.enc_st);
@@ -700,7 +687,7 @@ int rnnt_engine_joint_bwd(const void *enc, const int64_t enc_strides[3], const v
     layout(B, T, U1, H, V, dtype, &c.L);
     if (ws_bytes < c.L.total) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, c.L.total);
     hipStream_t st = c.st = (hipStream_t)stream;
-    c.ws = (char *)workspace; c.cb = (ControlBlock *)(c.ws + c.L.counters); c.logits = f32_at(c, c.L.logits);  // G
+    c.ws = (char *)workspace; c.cb = (ControlBlock *)(c.ws + c.L.counters); c.joint_logits = f32_at(c, c.L.logits);  // G
     // every utterance at full length: the upstream gradient is dense (zero where the caller's loss
     // ignored a cell); the length arrays the kernels read live in the (unused) coefficient region
     int32_t *ll = (int32_t *)(c.ws + c.L.coef), *tl = ll + B;
@@ -712,8 +699,8 @@ int rnnt_engine_joint_bwd(const void *enc, const int64_t enc_strides[3], const v
     launch_fill32(tl, (unsigned)(U1 - 1), (size_t)B * 4, st);
     // G with the zero padding rows the dW GEMM walks past the last cell
     const size_t cells = (size_t)B * T * U1;
-    launch_copy_bytes(c.logits, grad_logits, cells * V * 4, st);
-    launch_fill32(c.logits + cells * V, 0u, (c.L.rows_pad + 16 - cells) * V * 4, st);
+    launch_copy_bytes(c.joint_logits, grad_logits, cells * V * 4, st);
+    launch_fill32(c.joint_logits + cells * V, 0u, (c.L.rows_pad + 16 - cells) * V * 4, st);
     const JointBwdArgs g = bwd_args(c);
     launch_make_hidden(g, st);
     launch_dhidden(g, false, st);  // G is given: the persistent kernel on every column
@@ -1226,15 +1213,13 @@ static int loss_fwd_bwd(const void *logits, const int32_t *targets, const int32_
     size_t need;
     rnnt_engine_loss_workspace_bytes(B, T, U1, V, dtype, &need);
     if (ws_bytes < need) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
-    const LossCall c{carve_loss_ws(workspace, B, T, U1), targets, logit_lens, target_lens, costs, B, T, U1,
-                     grad_logits ? ST_LATTICE | ST_COEF : ST_LATTICE, 1.0f, fastemit, delay, (hipStream_t)stream,
-                     restrict_frames, restrict_left, restrict_right};
-    launch_logsoftmax_gather((const float *)logits, targets, logit_lens, target_lens, c.w.denom_s, c.w.lpb_s,
-                             c.w.lpe_s, B, T, U1, V, T + U1 - 1, blank, c.st);
+    LossCall c{};
+    loss_call(c, workspace, targets, logit_lens, target_lens, costs, B, T, U1, grad_logits ? ST_LATTICE | ST_COEF : ST_LATTICE, 1.0f,
+              fastemit, delay, (hipStream_t)stream, restrict_frames, restrict_left, restrict_right);
+    c.logits = (const float *)logits; c.grad_logits = (float *)grad_logits; c.V = V; c.blank = blank; c.clamp = clamp;
+    launch_logsoftmax_gather(c, c.st);
     loss_stages(c);
-    if (grad_logits)
-        launch_grad_logits((const float *)logits, c.w.coef, (float *)grad_logits, (long)B * T * U1, V,
-                           blank, clamp, c.st);
+    if (grad_logits) launch_grad_logits(c, c.st);
     return launch_status("rnnt_engine_loss_fwd_bwd");
 }
 
@@ -1375,12 +1360,11 @@ int rnnt_engine_align(const void *logits, const int32_t *targets, const int32_t 
     size_t need;
     rnnt_engine_loss_workspace_bytes(B, T, U1, V, RNNT_DTYPE_F32, &need);
     if (ws_bytes < need) return fail(RNNT_ERR_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
-    const int D = T + U1 - 1;
-    const LossWs w = carve_loss_ws(workspace, B, T, U1);  // the loss entry's layout; the backpointer words take the alpha_s region
-    hipStream_t st = (hipStream_t)stream;
-    launch_logsoftmax_gather((const float *)logits, targets, logit_lens, target_lens, w.denom_s, w.lpb_s,
-                             w.lpe_s, B, T, U1, V, D, blank, st);
-    launch_align(w.lpb_s, w.lpe_s, w.alpha_s, logit_lens, target_lens, scores, frames, B, U1, D, st);
+    LossCall c{};  // the loss entry's layout; the backpointer words take the alpha_s region
+    loss_call(c, workspace, targets, logit_lens, target_lens, scores, B, T, U1, 0, 1.0f, 0.f, 0.f, (hipStream_t)stream, nullptr, 0, 0);
+    c.logits = (const float *)logits; c.V = V; c.blank = blank;
+    launch_logsoftmax_gather(c, c.st);
+    launch_align(c, c.alpha_s, scores, frames, c.st);
     return launch_status("rnnt_engine_align");
 }
 
@@ -1399,9 +1383,10 @@ int rnnt_engine_joint_align(const void *enc, const int64_t enc_strides[3], const
         return rc;
     rnnt_engine_ws_layout L;
     layout(B, T, U1, H, V, dtype, &L);
-    char *ws = (char *)workspace;
-    launch_align((const float *)(ws + L.lpb_s), (const float *)(ws + L.lpe_s), ws + L.alpha_s,
-                 logit_lens, target_lens, scores, frames, B, U1, L.D, (hipStream_t)stream);
+    LossCall c{};
+    loss_call(c, (char *)workspace + L.denom_s, targets, logit_lens, target_lens, scores, B, T, U1, 0, 1.0f, 0.f, 0.f, (hipStream_t)stream,
+              nullptr, 0, 0);
+    launch_align(c, c.alpha_s, scores, frames, c.st);
     return launch_status("rnnt_engine_joint_align");
 }
 

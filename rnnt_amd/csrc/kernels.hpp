@@ -13,57 +13,44 @@ void launch_fill32(void *p, unsigned value, size_t bytes, hipStream_t st);
 void launch_copy_bytes(void *dst, const void *src, size_t bytes, hipStream_t st);
 int device_cus();  // compute units of the current device, cached (x2.hip; the engine's and the Linear layers' persistent grids)
 
-// ---- lattice.hip
-void launch_logsoftmax_gather(const float *logits, const int32_t *targets,
-                              const int32_t *logit_lens, const int32_t *target_lens,
-                              float *denom_s, float *lpb_s, float *lpe_s, int B, int T, int U1,
-                              int V, int D, int blank, hipStream_t st);
-void launch_lattice(const float *lpb_s, const float *lpe_s, double *alpha_s, double *beta_s,
-                    const int32_t *logit_lens, const int32_t *target_lens, float *costs, int B,
-                    int U1, int D, unsigned *err /* one word of workspace */, hipStream_t st,
-                    bool restricted = false /* lp_emit went through launch_restrict: the -inf-safe chained sweep */);
-void launch_coef(const double *alpha_s, const double *beta_s, const float *denom_s,
-                 const float *lpb_s, const float *lpe_s, const int32_t *targets,
-                 const int32_t *logit_lens, const int32_t *target_lens, CellCoef *coef, int B,
-                 int T, int U1, int D, float scale, hipStream_t st);
-// the f16x2 route's k_coef: cells whose G the route's fp16 split provably rounds to zero get the coefficients of a cell outside
-// the lattice (lattice.hip coef_cell, FLUSH); flush_log2 = -inf, flush_lin = 0 flag nothing
-void launch_coef_flush(const double *alpha_s, const double *beta_s, const float *denom_s,
-                       const float *lpb_s, const float *lpe_s, const int32_t *targets,
-                       const int32_t *logit_lens, const int32_t *target_lens, CellCoef *coef, int B,
-                       int T, int U1, int D, float scale, double flush_log2, float flush_lin, hipStream_t st);
-// FastEmit / delay penalty: k_coef with lambda > 0; the penalty on lp_emit before
-// launch_lattice and the cost it shifts, put back after it (every call that penalises runs both)
-void launch_coef_fastemit(const double *alpha_s, const double *beta_s, const float *denom_s,
-                          const float *lpb_s, const float *lpe_s, const int32_t *targets,
-                          const int32_t *logit_lens, const int32_t *target_lens, CellCoef *coef, int B,
-                          int T, int U1, int D, float scale, float lambda, hipStream_t st);
-void launch_delay_penalty(float *lpe_s, const int32_t *logit_lens, const int32_t *target_lens, int B,
-                          int T, int U1, int D, float delay, hipStream_t st);
-void launch_delay_cost(const double *beta_s, const int32_t *logit_lens, const int32_t *target_lens,
-                       float *costs, int B, int T, int U1, int D, float delay, hipStream_t st);
-// Alignment restriction.  launch_restrict: label arcs outside frames[b,u] - left .. frames[b,u] + right get
-// lp_emit = -inf, the others the delay penalty (it runs INSTEAD of launch_delay_penalty; delay = 0: none); then
-// launch_lattice(.., restricted = true), launch_delay_cost as usual, and launch_coef_restrict: the coefficients with dead cells
-// (alpha or beta = -inf, cost = +inf) set to those of a cell outside the lattice — FastEmit's when lambda > 0, else the flush
-// rule's when flush_log2 is not null, else the plain ones.
-void launch_restrict(float *lpe_s, const int32_t *frames /* [B, U1-1] */, const int32_t *logit_lens,
-                     const int32_t *target_lens, int B, int T, int U1, int D, int left, int right, float delay,
-                     hipStream_t st);
-void launch_coef_restrict(const double *alpha_s, const double *beta_s, const float *denom_s,
-                          const float *lpb_s, const float *lpe_s, const int32_t *targets,
-                          const int32_t *logit_lens, const int32_t *target_lens, CellCoef *coef, int B,
-                          int T, int U1, int D, float scale, float lambda, const double *flush_log2, float flush_lin,
-                          hipStream_t st);
-void launch_grad_logits(const float *logits, const CellCoef *coef, float *grad, long nrows,
-                        int V, int blank, float clamp, hipStream_t st);
+// ---- lattice.hip: the loss tail on the skewed work arrays (common.hpp), every stage on one argument block.  engine.hip fills it in
+// one place per call (carve_loss_ws + the call's inputs and options); a launcher reads the fields its stage needs.
+struct LatticeArgs {
+    float *denom_s, *lpb_s, *lpe_s;   // skewed [B,D,U1]: log-sum-exp, lp_blank, lp_emit of every lattice cell (the producers' output)
+    double *alpha_s, *beta_s;         // skewed [B,D,U1] fp64
+    CellCoef *coef;                   // [B,T,U1]
+    unsigned *err;                    // one word: raised by a chained sweep whose bounded spin ran out
+    const int32_t *targets, *logit_lens, *target_lens;  // [B,U1-1], [B], [B]
+    float *costs;                     // [B]
+    int B, T, U1, D;                  // D = T + U1 - 1 diagonals
+    float grad_scale;                 // the coefficients are those of grad_scale * sum_b costs[b]
+    float fastemit, delay;            // FastEmit's lambda and the delay penalty's delta; 0: off
+    const int32_t *restrict_frames;   // [B,U1-1] alignment restriction, or null: none
+    int restrict_left, restrict_right;
+    bool flush;                       // the f16x2 route's flush rule (lattice.hip k_coef, FLUSH) with the two thresholds below;
+    double flush_log2; float flush_lin;  // flush_log2 = -inf, flush_lin = 0 flag nothing
+    int V, blank;                     // the vocabulary (V % 4 == 0) and the blank's index
+    // the entries on materialised logits only (launch_logsoftmax_gather, launch_grad_logits), else null / 0:
+    const float *logits; float *grad_logits; float clamp;  // [B,T,U1,V]; clamp > 0 bounds every entry of grad_logits
+};
+void launch_logsoftmax_gather(const LatticeArgs &a, hipStream_t st);  // logits -> denom_s, lpb_s, lpe_s
+// The stages in call order (engine.hip loss_stages).  launch_lp_emit: the pass over lp_emit before the sweep — label arcs outside
+// their window get -inf (restrict_frames), the others the delay penalty; a call with neither does not run it.  launch_lattice:
+// alpha_s, beta_s, costs (the -inf-safe chained sweep on a restricted lattice).  launch_delay_cost: the cost the penalty shifted, put
+// back (delay > 0 only).  launch_coef: the coefficients — FastEmit's when fastemit > 0, else the flush rule's when `flush`, else the
+// plain ones; on a restricted lattice with dead cells (alpha or beta = -inf, cost = +inf) set to those of a cell outside the lattice.
+void launch_lp_emit(const LatticeArgs &a, hipStream_t st);
+void launch_lattice(const LatticeArgs &a, hipStream_t st);
+void launch_delay_cost(const LatticeArgs &a, hipStream_t st);
+void launch_coef(const LatticeArgs &a, hipStream_t st);
+void launch_grad_logits(const LatticeArgs &a, hipStream_t st);  // coef, logits -> grad_logits
+// a chained sweep's failure report (lattice.hip's and ctc.hip's): *err != 0 turns costs[0..n) — and logp[0..n), unless null — into NaN
+void launch_chain_status(const unsigned *err, float *costs, double *logp, int n, hipStream_t st);
 
-// ---- align.hip: forced alignment on the lp arrays of either producer.  `bp`: the
-// backpointer words, B * D * ceil(U1/64) u64 (fits in the alpha_s region of both workspaces);
+// ---- align.hip: forced alignment on the lp arrays of either producer (lpb_s, lpe_s, the lengths and the
+// dimensions of `a`).  `bp`: the backpointer words, B * D * ceil(U1/64) u64 (fits in the alpha_s region of both workspaces);
 // frames [B, U1-1] int32; scores [B].
-void launch_align(const float *lpb_s, const float *lpe_s, void *bp, const int32_t *logit_lens,
-                  const int32_t *target_lens, float *scores, int32_t *frames, int B, int U1, int D,
-                  hipStream_t st);
+void launch_align(const LatticeArgs &a, void *bp, float *scores, int32_t *frames, hipStream_t st);
 
 // ---- joint_fwd.hip
 struct JointFwdArgs {

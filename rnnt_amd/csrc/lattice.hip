@@ -2,81 +2,68 @@
 //
 // Replaces the arithmetic behind torchaudio.functional.rnnt_loss as called at reference
 // rnnt/model.py:35-41 (see SURVEY.md §8c for the recurrences):
-//   k_logsoftmax_gather  logits -> (denom, lp_blank, lp_emit) in skewed layout
-//                        (only for the standalone loss entry; the fused path gets these
-//                         from the joint-forward GEMM epilogue)
-//   k_lattice<DIR>       alpha / beta anti-diagonal wavefront sweep, one workgroup per
-//                        (utterance, direction), previous diagonal staged in LDS
-//   k_coef               per-cell gradient coefficients (CellCoef) from alpha/beta
-//                        (k_coef_fastemit: the same with FastEmit's lambda)
-//   k_delay_penalty      delay penalty on lp_emit before the sweep; k_delay_cost after it
-//   k_restrict           alignment restriction: label arcs outside their window get lp_emit = -inf
-//                        before the sweep; k_lattice_chain_restrict / k_coef_restrict* are the -inf-safe instantiations
-//   k_grad_logits        d cost / d logits, elementwise (standalone loss entry only)
+// Every stage reads one argument block, LatticeArgs (kernels.hpp), and each is one kernel template:
+//   k_logsoftmax_gather      logits -> (denom, lp_blank, lp_emit) in skewed layout (only for the entries on materialised
+//                            logits; the fused routes get these from the joint-forward GEMM epilogue)
+//   k_lp_emit<RS>            the pass over lp_emit before the sweep: the delay penalty and, RS, the alignment
+//                            restriction (§4n: label arcs outside their window get lp_emit = -inf)
+//   k_lattice_chain<RS>      alpha / beta anti-diagonal sweep, one workgroup per (utterance, direction), the waves chained
+//                            through LDS mailboxes (lattice_chain<DIR, RS>; RS: -inf-safe); k_chain_status reports a failed chain
+//   k_lattice                the same sweep with one barrier per step (lattice_sweep<DIR>), when the mailboxes do not fit in LDS
+//   k_delay_cost             puts the cost shift of the delay penalty back after the sweep
+//   k_coef<FE, FLUSH, RS>    per-cell gradient coefficients (CellCoef) from alpha / beta: FastEmit (§4k), the f16x2 route's
+//                            flush rule, dead cells of a restricted lattice; launch_coef holds the rule that selects one
+//   k_grad_logits            d cost / d logits, elementwise (entries on materialised logits only)
 //
 // All per-cell work arrays use the skewed layout of common.hpp (anti-diagonal contiguous),
 // so every sweep load/store is a coalesced row access.  alpha/beta are kept in fp64: the
 // values reach ~1e4 in magnitude at T=1000 and the gradient needs alpha+beta+cost, a
 // cancellation fp32 cannot hold to 1e-4; the per-step log-add-exp correction term is
 // evaluated in fp32 (it is < ln 2 in magnitude).
-#include "common.hpp"
+#include "lattice_common.hpp"
 #include "kernels.hpp"
-
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------
 // log-softmax denominators + the two log-probs each lattice cell needs.
 // One wave per (b,t,u) row; V % 4 == 0.
-__global__ __launch_bounds__(256) void k_logsoftmax_gather(
-    const float *__restrict__ logits, const int32_t *__restrict__ targets,
-    const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
-    float *__restrict__ denom_s, float *__restrict__ lpb_s, float *__restrict__ lpe_s, int B,
-    int T, int U1, int V, int D, int blank)
+__global__ __launch_bounds__(256) void k_logsoftmax_gather(const LatticeArgs a)
 {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const long nrows = (long)B * T * U1;
+    const long nrows = (long)a.B * a.T * a.U1;
     if (row >= nrows) return;
-    const int u = (int)(row % U1);
-    const long bt = row / U1;
-    const int t = (int)(bt % T);
-    const int b = (int)(bt / T);
-    if (t >= len_t(logit_lens, b, T) || u > len_u(target_lens, b, U1)) return;
-    const float *x = logits + row * V;
-    float m = RNNT_NEG_INF;
-    for (int v = lane * 4; v < V; v += 256) {
-        f32x4 q = *(const f32x4 *)(x + v);
-        m = fmaxf(m, fmaxf(fmaxf(q[0], q[1]), fmaxf(q[2], q[3])));
-    }
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) m = fmaxf(m, __shfl_xor(m, k, 64));
-    float s = 0.f;
-    for (int v = lane * 4; v < V; v += 256) {
-        f32x4 q = *(const f32x4 *)(x + v);
-        s += __expf(q[0] - m) + __expf(q[1] - m) + __expf(q[2] - m) + __expf(q[3] - m);
-    }
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) s += __shfl_xor(s, k, 64);
+    const int u = (int)(row % a.U1);
+    const long bt = row / a.U1;
+    const int t = (int)(bt % a.T);
+    const int b = (int)(bt / a.T);
+    if (t >= len_t(a.logit_lens, b, a.T) || u > len_u(a.target_lens, b, a.U1)) return;
+    const float *x = a.logits + row * a.V;
+    float m, s;
+    row_max_sumexp(x, a.V, lane, m, s);
     if (lane == 0) {
         const float den = m + logf(s);
-        const long si = skew_index(b, t, u, D, U1);
-        denom_s[si] = den;
-        lpb_s[si] = x[blank] - den;
-        lpe_s[si] = (u < len_u(target_lens, b, U1)) ? x[targets[(long)b * (U1 - 1) + u]] - den : 0.f;
+        const long si = skew_index(b, t, u, a.D, a.U1);
+        a.denom_s[si] = den;
+        a.lpb_s[si] = x[a.blank] - den;
+        a.lpe_s[si] = (u < len_u(a.target_lens, b, a.U1)) ? x[a.targets[(long)b * (a.U1 - 1) + u]] - den : 0.f;
     }
+}
+
+// A slot of the skewed arrays as the one-thread-per-slot kernels read it: idx -> (b, d, u, t = d - u).  False past the arrays;
+// a slot with t outside 0 .. T-1 holds no cell (each caller tests t against what it needs).
+__device__ __forceinline__ bool skew_slot(long idx, int B, int U1, int D, int &b, int &d, int &u, int &t)
+{
+    const long per = (long)D * U1;
+    if (idx >= per * B) return false;
+    b = (int)(idx / per);
+    const long rem = idx - (long)b * per;
+    d = (int)(rem / U1);
+    u = (int)(rem - (long)d * U1);
+    t = d - u;
+    return true;
 }
 
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ double logaddexp_mixed(double a, double e)
-{
-    const double m = fmax(a, e);
-    if (m == (double)RNNT_NEG_INF) return m;
-    const float dl = (float)(fmin(a, e) - m);
-    // hardware exp2/log2 (v_exp_f32 / v_log_f32): the correction is in (0, ln 2], absolute error
-    // ~1e-7 per step, far below the 1e-4 budget after T+U steps, and it shortens the serial chain
-    return m + (double)__logf(1.0f + __expf(dl));
-}
-
 // One workgroup per (utterance, direction); thread u owns lattice column u.  The previous
 // anti-diagonal is exchanged through a double-buffered LDS line (one barrier per step);
 // the lp values of the next four diagonals are prefetched into registers because they do
@@ -201,18 +188,9 @@ __device__ __forceinline__ void lattice_sweep(
 // instead of LDS write -> s_barrier -> LDS read across four waves (cfg2: 0.36 -> see DESIGN).
 // Every mailbox slot is written exactly once (no ring, no back-pressure); the consumer's spin is
 // bounded, so every wave reaches its exit whatever happens.
-template <int CTRL>
-__device__ __forceinline__ double wave_shift(double v, double fill)
-{
-    const u32x2_t x = __builtin_bit_cast(u32x2_t, v), f = __builtin_bit_cast(u32x2_t, fill);
-    u32x2_t r;
-    r[0] = (unsigned)__builtin_amdgcn_update_dpp((int)f[0], (int)x[0], CTRL, 0xf, 0xf, false);
-    r[1] = (unsigned)__builtin_amdgcn_update_dpp((int)f[1], (int)x[1], CTRL, 0xf, 0xf, false);
-    return __builtin_bit_cast(double, r);
-}
-
+//
 // RS (restricted lattice): lp_emit may be -inf, so a cell INSIDE the lattice may have no finite predecessor; the
-// step then yields -inf instead of the NaN of (-inf) - (-inf).  RS = false is the plain sweep's code unchanged.
+// step then yields -inf instead of the NaN of (-inf) - (-inf) (lse2_safe).  RS = false is the plain sweep's select-free expression.
 #define LAT_PF 6
 template <int DIR, bool RS = false>
 __device__ __forceinline__ void lattice_chain(
@@ -298,7 +276,7 @@ __device__ __forceinline__ void lattice_chain(
             for (int spin = 0; tg != k && spin < (1 << 22); ++spin) { tg = mtag[cb + k - 1]; bv = mval[cb + k - 1]; }
             // bounded spin exhausted (the producer wave never published step k-1: cannot happen
             // while the workgroup is resident, but a silent stale value would be a wrong loss):
-            // raise the error word; k_lattice_status then turns every cost of the call into NaN
+            // raise the error word; k_chain_status then turns every cost of the call into NaN
             if (tg != k && l == 0) atomicOr(err, 1u);
         }
         // neighbour column of the previous diagonal: u-1 (alpha) / u+1 (beta); the lane at the
@@ -316,10 +294,9 @@ __device__ __forceinline__ void lattice_chain(
         // log(exp(a) + exp(e)) = max + log(1 + exp(-|a - e|)); the correction is < ln 2 and
         // evaluated in fp32 with the hardware exp2/log2.  A cell of the lattice has at least one
         // finite predecessor; everything else is overwritten by the select.
-        float dl = -fabsf((float)(a - e));
-        if (RS) dl = fmax(a, e) == NINF ? 0.f : dl;  // both predecessors unreachable: -inf + log 2 = -inf
-        const double v = fmax(a, e) +
-            (double)(__builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f(dl * RNNT_LOG2E)) * 0.6931471805599453f);
+        const float dl = -fabsf((float)(a - e));
+        const double v = RS ? lse2_safe(a, e)  // both predecessors unreachable: -inf + log 2 = -inf
+                            : fmax(a, e) + (double)(__builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f(dl * RNNT_LOG2E)) * 0.6931471805599453f);
         const bool valid = (unsigned)(d - ukey) < (unsigned)Tb;
         if (DIR == 1) bad = bad || (valid && lb_nan);
         prev = valid ? v : NINF;
@@ -351,6 +328,13 @@ __device__ __forceinline__ void lattice_chain(
     }
 }
 
+// grid (B, 2): blockIdx.y selects the direction, so the 2B independent sweeps of a batch run concurrently on 2B compute units in
+// ONE launch.  RS: the chained sweep on a restricted lattice (k_lp_emit<true> ran on lp_emit): unreachable cells come out as
+// -inf, an infeasible utterance as cost +inf.
+// The two sweep kernels keep loose parameters, unpacked from LatticeArgs by launch_lattice: with the struct by value the compiler
+// loads the kernel arguments in other widths and moves two of those loads across the sweep's first barrier; the step loops came
+// out the same, but these kernels' instruction streams are kept as they were (profiles/lattice_refactor_isa.txt).
+template <bool RS>
 __global__ __launch_bounds__(1024) void k_lattice_chain(
     const float *__restrict__ lpb_s, const float *__restrict__ lpe_s,
     double *__restrict__ alpha_s, double *__restrict__ beta_s,
@@ -358,32 +342,33 @@ __global__ __launch_bounds__(1024) void k_lattice_chain(
     float *__restrict__ costs, int U1, int D, unsigned *__restrict__ err)
 {
     if (blockIdx.y == 0)
-        lattice_chain<0>(lpb_s, lpe_s, alpha_s, logit_lens, target_lens, costs, U1, D, err);
+        lattice_chain<0, RS>(lpb_s, lpe_s, alpha_s, logit_lens, target_lens, costs, U1, D, err);
     else
-        lattice_chain<1>(lpb_s, lpe_s, beta_s, logit_lens, target_lens, costs, U1, D, err);
+        lattice_chain<1, RS>(lpb_s, lpe_s, beta_s, logit_lens, target_lens, costs, U1, D, err);
 }
 
-// the chained sweep on a restricted lattice (k_restrict ran on lp_emit): unreachable cells come out as -inf, an infeasible
-// utterance as cost +inf
-__global__ __launch_bounds__(1024) void k_lattice_chain_restrict(
+__global__ __launch_bounds__(1024) void k_lattice(
     const float *__restrict__ lpb_s, const float *__restrict__ lpe_s,
     double *__restrict__ alpha_s, double *__restrict__ beta_s,
     const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
-    float *__restrict__ costs, int U1, int D, unsigned *__restrict__ err)
+    float *__restrict__ costs, int U1, int D)
 {
     if (blockIdx.y == 0)
-        lattice_chain<0, true>(lpb_s, lpe_s, alpha_s, logit_lens, target_lens, costs, U1, D, err);
+        lattice_sweep<0>(lpb_s, lpe_s, alpha_s, logit_lens, target_lens, costs, U1, D);
     else
-        lattice_chain<1, true>(lpb_s, lpe_s, beta_s, logit_lens, target_lens, costs, U1, D, err);
+        lattice_sweep<1>(lpb_s, lpe_s, beta_s, logit_lens, target_lens, costs, U1, D);
 }
 
-// Failure report of the chained sweep: if any wave ran out of its bounded spin, the costs of the
-// whole call become NaN (a loud failure the training loop sees in its loss) instead of numbers
-// computed from a stale mailbox value.
-__global__ void k_lattice_status(const unsigned *__restrict__ err, float *__restrict__ costs, int B)
+// Failure report of a chained sweep (this file's and ctc.hip's): if any wave ran out of its bounded spin, the costs of the
+// whole call become NaN (a loud failure the training loop sees in its loss) — and `logp`, where the caller's gradient reads
+// it, so every gradient too — instead of numbers computed from a stale mailbox value.
+__global__ void k_chain_status(const unsigned *__restrict__ err, float *__restrict__ costs, double *__restrict__ logp, int n)
 {
     if (*err == 0u) return;
-    for (int b = threadIdx.x; b < B; b += blockDim.x) costs[b] = __builtin_nanf("");
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        costs[i] = __builtin_nanf("");
+        if (logp) logp[i] = (double)__builtin_nanf("");
+    }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -418,25 +403,22 @@ __global__ void k_lattice_status(const unsigned *__restrict__ err, float *__rest
 // infeasible utterance (cost = +inf) is DEAD: alpha + cost and FastEmit's beta difference would be (+-inf) - (+-inf) there.  A dead
 // cell gets the coefficients of a cell outside the lattice, so its gradient row is exactly zero on every route and the f16x2
 // backward skips it like a flushed one.  The tests are ordered compares: a NaN cost keeps its cells live and stays NaN.
-template <bool FE, bool FLUSH = false, bool RS = false>
-__device__ __forceinline__ void coef_cell(
-    const double *__restrict__ alpha_s, const double *__restrict__ beta_s,
-    const float *__restrict__ denom_s, const float *__restrict__ lpb_s,
-    const float *__restrict__ lpe_s, const int32_t *__restrict__ targets,
-    const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
-    CellCoef *__restrict__ coef, int B, int T, int U1, int D, float scale, float lambda,
-    double flush_log2 = 0.0, float flush_lin = 0.f)
+template <bool FE, bool FLUSH, bool RS>
+__global__ __launch_bounds__(256) void k_coef(const LatticeArgs p)
 {
+    const double *alpha_s = p.alpha_s, *beta_s = p.beta_s;
+    const float *denom_s = p.denom_s, *lpb_s = p.lpb_s, *lpe_s = p.lpe_s;
+    const int32_t *targets = p.targets;
+    CellCoef *coef = p.coef;
+    const int T = p.T, U1 = p.U1;
+    const float scale = p.grad_scale, lambda = p.fastemit, flush_lin = p.flush_lin;
+    const double flush_log2 = p.flush_log2;
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long per = (long)D * U1;
-    if (idx >= per * B) return;
-    const int b = (int)(idx / per);
-    const long rem = idx - (long)b * per;
-    const int d = (int)(rem / U1);
-    const int u = (int)(rem - (long)d * U1);
-    const int t = d - u;
+    const long per = (long)p.D * U1;
+    int b, d, u, t;
+    if (!skew_slot(idx, p.B, U1, p.D, b, d, u, t)) return;
     if (t < 0 || t >= T) return;
-    const int Tb = len_t(logit_lens, b, T), Ub = len_u(target_lens, b, U1);
+    const int Tb = len_t(p.logit_lens, b, T), Ub = len_u(p.target_lens, b, U1);
     CellCoef c;
     c.c1 = RNNT_NEG_INF; c.sb = 0.f; c.se = 0.f; c.y = -1;
     bool in_lattice = t < Tb && u <= Ub;
@@ -472,74 +454,6 @@ __device__ __forceinline__ void coef_cell(
     coef[((long)b * T + t) * U1 + u] = c;
 }
 
-// k_coef with the f16x2 route's flush rule (coef_cell): launched by that route only
-__global__ __launch_bounds__(256) void k_coef_flush(
-    const double *__restrict__ alpha_s, const double *__restrict__ beta_s,
-    const float *__restrict__ denom_s, const float *__restrict__ lpb_s,
-    const float *__restrict__ lpe_s, const int32_t *__restrict__ targets,
-    const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
-    CellCoef *__restrict__ coef, int B, int T, int U1, int D, float scale, double flush_log2, float flush_lin)
-{
-    coef_cell<false, true>(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B, T, U1, D,
-                           scale, 0.f, flush_log2, flush_lin);
-}
-
-__global__ __launch_bounds__(256) void k_coef(
-    const double *__restrict__ alpha_s, const double *__restrict__ beta_s,
-    const float *__restrict__ denom_s, const float *__restrict__ lpb_s,
-    const float *__restrict__ lpe_s, const int32_t *__restrict__ targets,
-    const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
-    CellCoef *__restrict__ coef, int B, int T, int U1, int D, float scale)
-{
-    coef_cell<false>(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B, T, U1, D,
-                     scale, 0.f);
-}
-
-// the three coefficient kernels on a restricted lattice (coef_cell, RS)
-__global__ __launch_bounds__(256) void k_coef_restrict(
-    const double *__restrict__ alpha_s, const double *__restrict__ beta_s,
-    const float *__restrict__ denom_s, const float *__restrict__ lpb_s,
-    const float *__restrict__ lpe_s, const int32_t *__restrict__ targets,
-    const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
-    CellCoef *__restrict__ coef, int B, int T, int U1, int D, float scale)
-{
-    coef_cell<false, false, true>(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B, T, U1, D,
-                                  scale, 0.f);
-}
-
-__global__ __launch_bounds__(256) void k_coef_restrict_flush(
-    const double *__restrict__ alpha_s, const double *__restrict__ beta_s,
-    const float *__restrict__ denom_s, const float *__restrict__ lpb_s,
-    const float *__restrict__ lpe_s, const int32_t *__restrict__ targets,
-    const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
-    CellCoef *__restrict__ coef, int B, int T, int U1, int D, float scale, double flush_log2, float flush_lin)
-{
-    coef_cell<false, true, true>(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B, T, U1, D,
-                                 scale, 0.f, flush_log2, flush_lin);
-}
-
-__global__ __launch_bounds__(256) void k_coef_restrict_fastemit(
-    const double *__restrict__ alpha_s, const double *__restrict__ beta_s,
-    const float *__restrict__ denom_s, const float *__restrict__ lpb_s,
-    const float *__restrict__ lpe_s, const int32_t *__restrict__ targets,
-    const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
-    CellCoef *__restrict__ coef, int B, int T, int U1, int D, float scale, float lambda)
-{
-    coef_cell<true, false, true>(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B, T, U1, D,
-                                 scale, lambda);
-}
-
-__global__ __launch_bounds__(256) void k_coef_fastemit(
-    const double *__restrict__ alpha_s, const double *__restrict__ beta_s,
-    const float *__restrict__ denom_s, const float *__restrict__ lpb_s,
-    const float *__restrict__ lpe_s, const int32_t *__restrict__ targets,
-    const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
-    CellCoef *__restrict__ coef, int B, int T, int U1, int D, float scale, float lambda)
-{
-    coef_cell<true>(alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B, T, U1, D,
-                    scale, lambda);
-}
-
 // ---------------------------------------------------------------------------------------
 // Delay penalty: the lattice of the penalised cost runs on
 // lp_emit'(t,u) = lp_emit(t,u) + delta ((T_b - 1) / 2 - t).  The chained sweep clamps every lp
@@ -550,58 +464,37 @@ __global__ __launch_bounds__(256) void k_coef_fastemit(
 // every gradient coefficient, is unchanged by such a shift; only the cost moves, and
 // k_delay_cost puts it back after the sweep.  Live label cells only (t < T_b, u < U_b); a NaN
 // stays a NaN.  One thread per skewed slot, in place.
-__global__ __launch_bounds__(256) void k_delay_penalty(float *__restrict__ lpe_s,
-                                                       const int32_t *__restrict__ logit_lens,
-                                                       const int32_t *__restrict__ target_lens,
-                                                       int B, int T, int U1, int D, float delay)
+//
+// RS, the alignment restriction: the label arc (t,u) -> (t,u+1) exists only for frames[b,u] - left <= t <=
+// frames[b,u] + right; outside its window lp_emit becomes -inf, inside it the delay penalty applies as above (delay = 0:
+// unchanged, no load and no store).  frames[b,u] is read for u < U_b alone; the window is formed in 64 bits (any int32 frame and
+// buffer).  RS = false runs only when delay > 0.
+template <bool RS>
+__global__ __launch_bounds__(256) void k_lp_emit(const LatticeArgs a)
 {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long per = (long)D * U1;
-    if (idx >= per * B) return;
-    const int b = (int)(idx / per);
-    const long rem = idx - (long)b * per;
-    const int d = (int)(rem / U1);
-    const int u = (int)(rem - (long)d * U1);
-    const int t = d - u;
-    if (t < 0 || t >= len_t(logit_lens, b, T) || u >= len_u(target_lens, b, U1)) return;
-    lpe_s[idx] -= delay * (float)t;
-}
-
-// Alignment restriction: the label arc (t,u) -> (t,u+1) exists only for frames[b,u] - left <= t <= frames[b,u] +
-// right; outside its window lp_emit becomes -inf, inside it the delay penalty applies as k_delay_penalty applies it (delay = 0:
-// unchanged).  Live label cells only (t < T_b, u < U_b), so frames[b,u] is read for u < U_b alone; the window is formed in 64
-// bits (any int32 frame and buffer).  One thread per skewed slot, in place; runs instead of k_delay_penalty.
-__global__ __launch_bounds__(256) void k_restrict(float *__restrict__ lpe_s, const int32_t *__restrict__ frames,
-                                                  const int32_t *__restrict__ logit_lens,
-                                                  const int32_t *__restrict__ target_lens, int B, int T, int U1,
-                                                  int D, int left, int right, float delay)
-{
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long per = (long)D * U1;
-    if (idx >= per * B) return;
-    const int b = (int)(idx / per);
-    const long rem = idx - (long)b * per;
-    const int d = (int)(rem / U1);
-    const int u = (int)(rem - (long)d * U1);
-    const int t = d - u;
-    if (t < 0 || t >= len_t(logit_lens, b, T) || u >= len_u(target_lens, b, U1)) return;
-    const long f = frames[(long)b * (U1 - 1) + u];
-    if (t < f - left || t > f + right) lpe_s[idx] = RNNT_NEG_INF;
-    else if (delay > 0.f) lpe_s[idx] -= delay * (float)t;
+    int b, d, u, t;
+    if (!skew_slot(idx, a.B, a.U1, a.D, b, d, u, t)) return;
+    if (t < 0 || t >= len_t(a.logit_lens, b, a.T) || u >= len_u(a.target_lens, b, a.U1)) return;
+    if (RS) {
+        const long f = a.restrict_frames[(long)b * (a.U1 - 1) + u];
+        if (t < f - a.restrict_left || t > f + a.restrict_right) a.lpe_s[idx] = RNNT_NEG_INF;
+        else if (a.delay > 0.f) a.lpe_s[idx] -= a.delay * (float)t;
+    } else {
+        a.lpe_s[idx] -= a.delay * (float)t;
+    }
 }
 
 // cost_b = -log P'_b = -beta(0,0) - U_b delta (T_b - 1) / 2, from the fp64 beta of the shifted
 // lattice (one rounding); a NaN cost (NaN input, failed sweep) stays NaN, and +inf (a restricted
 // lattice without a path: beta(0,0) = -inf) stays +inf.
-__global__ void k_delay_cost(const double *__restrict__ beta_s, const int32_t *__restrict__ logit_lens,
-                             const int32_t *__restrict__ target_lens, float *__restrict__ costs, int B,
-                             int T, int U1, int D, float delay)
+__global__ void k_delay_cost(const LatticeArgs a)
 {
-    for (int b = threadIdx.x; b < B; b += blockDim.x) {
-        const float c = costs[b];
+    for (int b = threadIdx.x; b < a.B; b += blockDim.x) {
+        const float c = a.costs[b];
         if (c != c) continue;
-        const int Tb = len_t(logit_lens, b, T), Ub = len_u(target_lens, b, U1);
-        costs[b] = (float)(-beta_s[(long)b * D * U1] - (double)Ub * (double)delay * 0.5 * (double)(Tb - 1));
+        const int Tb = len_t(a.logit_lens, b, a.T), Ub = len_u(a.target_lens, b, a.U1);
+        a.costs[b] = (float)(-a.beta_s[(long)b * a.D * a.U1] - (double)Ub * (double)a.delay * 0.5 * (double)(Tb - 1));
     }
 }
 
@@ -637,133 +530,57 @@ __global__ __launch_bounds__(256) void k_grad_logits(const float *__restrict__ l
 }
 
 // ---------------------------------------------------------------------------------------
-void launch_logsoftmax_gather(const float *logits, const int32_t *targets,
-                              const int32_t *logit_lens, const int32_t *target_lens,
-                              float *denom_s, float *lpb_s, float *lpe_s, int B, int T, int U1,
-                              int V, int D, int blank, hipStream_t st)
+// The launchers.  One thread per skewed slot / one wave per row:
+static dim3 slot_grid(const LatticeArgs &a) { return dim3((unsigned)(((long)a.B * a.D * a.U1 + 255) / 256)); }
+static dim3 row_grid(const LatticeArgs &a) { return dim3((unsigned)(((long)a.B * a.T * a.U1 + 3) / 4)); }
+
+void launch_logsoftmax_gather(const LatticeArgs &a, hipStream_t st)
 {
-    const long nrows = (long)B * T * U1;
-    hipLaunchKernelGGL(k_logsoftmax_gather, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st,
-                       logits, targets, logit_lens, target_lens, denom_s, lpb_s, lpe_s, B, T, U1,
-                       V, D, blank);
+    hipLaunchKernelGGL(k_logsoftmax_gather, row_grid(a), dim3(256), 0, st, a);
 }
 
-// grid (B, 2): blockIdx.y selects the direction, so the 2B independent sweeps of a batch
-// run concurrently on 2B compute units in ONE launch.
-__global__ __launch_bounds__(1024) void k_lattice(
-    const float *__restrict__ lpb_s, const float *__restrict__ lpe_s,
-    double *__restrict__ alpha_s, double *__restrict__ beta_s,
-    const int32_t *__restrict__ logit_lens, const int32_t *__restrict__ target_lens,
-    float *__restrict__ costs, int U1, int D)
+void launch_lp_emit(const LatticeArgs &a, hipStream_t st)
 {
-    if (blockIdx.y == 0)
-        lattice_sweep<0>(lpb_s, lpe_s, alpha_s, logit_lens, target_lens, costs, U1, D);
-    else
-        lattice_sweep<1>(lpb_s, lpe_s, beta_s, logit_lens, target_lens, costs, U1, D);
+    hipLaunchKernelGGL(a.restrict_frames ? k_lp_emit<true> : k_lp_emit<false>, slot_grid(a), dim3(256), 0, st, a);
 }
 
-void launch_lattice(const float *lpb_s, const float *lpe_s, double *alpha_s, double *beta_s,
-                    const int32_t *logit_lens, const int32_t *target_lens, float *costs, int B,
-                    int U1, int D, unsigned *err, hipStream_t st, bool restricted)
+void launch_chain_status(const unsigned *err, float *costs, double *logp, int n, hipStream_t st)
 {
-    const int NW = (U1 + 63) / 64;
-    const size_t mbox = (size_t)(NW - 1) * D * 12;  // chain mailboxes: 8 B value + 4 B tag per boundary and step
+    hipLaunchKernelGGL(k_chain_status, dim3(1), dim3(64), 0, st, err, costs, logp, n);
+}
+
+void launch_lattice(const LatticeArgs &a, hipStream_t st)
+{
+    const int NW = (a.U1 + 63) / 64;
+    const size_t mbox = chain_mailbox_bytes(a.U1, a.D);
     if (mbox <= 64 * 1024) {
-        if (NW > 1) launch_fill32(err, 0u, 4, st);  // one wave: no mailbox, no spin
-        if (restricted)
-            hipLaunchKernelGGL(k_lattice_chain_restrict, dim3(B, 2), dim3(64 * NW), (mbox + 15) / 16 * 16, st, lpb_s, lpe_s,
-                               alpha_s, beta_s, logit_lens, target_lens, costs, U1, D, err);
-        else
-            hipLaunchKernelGGL(k_lattice_chain, dim3(B, 2), dim3(64 * NW), (mbox + 15) / 16 * 16, st, lpb_s, lpe_s, alpha_s,
-                               beta_s, logit_lens, target_lens, costs, U1, D, err);
-        if (NW > 1) hipLaunchKernelGGL(k_lattice_status, dim3(1), dim3(64), 0, st, err, costs, B);
+        if (NW > 1) launch_fill32(a.err, 0u, 4, st);  // one wave: no mailbox, no spin
+        hipLaunchKernelGGL(a.restrict_frames ? k_lattice_chain<true> : k_lattice_chain<false>, dim3(a.B, 2), dim3(64 * NW),
+                           (mbox + 15) / 16 * 16, st, a.lpb_s, a.lpe_s, a.alpha_s, a.beta_s, a.logit_lens, a.target_lens, a.costs, a.U1, a.D,
+                           a.err);
+        if (NW > 1) launch_chain_status(a.err, a.costs, nullptr, a.B, st);
         return;
     }
     // (the barrier sweep needs no restricted form: its log-add-exp and its validity select are -inf-safe as they are)
-    const int NT = ((U1 + 63) / 64) * 64;
-    const size_t lds = 2 * (size_t)(NT + 2) * sizeof(double);
-    hipLaunchKernelGGL(k_lattice, dim3(B, 2), dim3(NT), lds, st, lpb_s, lpe_s, alpha_s, beta_s,
-                       logit_lens, target_lens, costs, U1, D);
+    const size_t lds = 2 * (size_t)(64 * NW + 2) * sizeof(double);
+    hipLaunchKernelGGL(k_lattice, dim3(a.B, 2), dim3(64 * NW), lds, st, a.lpb_s, a.lpe_s, a.alpha_s, a.beta_s, a.logit_lens, a.target_lens,
+                       a.costs, a.U1, a.D);
 }
 
-void launch_coef(const double *alpha_s, const double *beta_s, const float *denom_s,
-                 const float *lpb_s, const float *lpe_s, const int32_t *targets,
-                 const int32_t *logit_lens, const int32_t *target_lens, CellCoef *coef, int B,
-                 int T, int U1, int D, float scale, hipStream_t st)
+void launch_delay_cost(const LatticeArgs &a, hipStream_t st) { hipLaunchKernelGGL(k_delay_cost, dim3(1), dim3(256), 0, st, a); }
+
+// The one place that says which coefficient kernel runs: FastEmit's when lambda > 0 (the regularised entries flush nothing), else
+// the flush rule's when the f16x2 route gave its thresholds, else the plain one; each in its RS form on a restricted lattice.
+void launch_coef(const LatticeArgs &a, hipStream_t st)
 {
-    const long n = (long)B * D * U1;
-    hipLaunchKernelGGL(k_coef, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, alpha_s,
-                       beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B,
-                       T, U1, D, scale);
+    void (*k)(LatticeArgs);
+    if (a.restrict_frames) k = a.fastemit > 0.f ? k_coef<true, false, true> : a.flush ? k_coef<false, true, true> : k_coef<false, false, true>;
+    else k = a.fastemit > 0.f ? k_coef<true, false, false> : a.flush ? k_coef<false, true, false> : k_coef<false, false, false>;
+    hipLaunchKernelGGL(k, slot_grid(a), dim3(256), 0, st, a);
 }
 
-void launch_coef_flush(const double *alpha_s, const double *beta_s, const float *denom_s,
-                       const float *lpb_s, const float *lpe_s, const int32_t *targets,
-                       const int32_t *logit_lens, const int32_t *target_lens, CellCoef *coef, int B,
-                       int T, int U1, int D, float scale, double flush_log2, float flush_lin, hipStream_t st)
+void launch_grad_logits(const LatticeArgs &a, hipStream_t st)
 {
-    const long n = (long)B * D * U1;
-    hipLaunchKernelGGL(k_coef_flush, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, alpha_s,
-                       beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B,
-                       T, U1, D, scale, flush_log2, flush_lin);
-}
-
-void launch_coef_fastemit(const double *alpha_s, const double *beta_s, const float *denom_s,
-                          const float *lpb_s, const float *lpe_s, const int32_t *targets,
-                          const int32_t *logit_lens, const int32_t *target_lens, CellCoef *coef, int B,
-                          int T, int U1, int D, float scale, float lambda, hipStream_t st)
-{
-    const long n = (long)B * D * U1;
-    hipLaunchKernelGGL(k_coef_fastemit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, alpha_s,
-                       beta_s, denom_s, lpb_s, lpe_s, targets, logit_lens, target_lens, coef, B,
-                       T, U1, D, scale, lambda);
-}
-
-void launch_coef_restrict(const double *alpha_s, const double *beta_s, const float *denom_s,
-                          const float *lpb_s, const float *lpe_s, const int32_t *targets,
-                          const int32_t *logit_lens, const int32_t *target_lens, CellCoef *coef, int B,
-                          int T, int U1, int D, float scale, float lambda, const double *flush_log2, float flush_lin,
-                          hipStream_t st)
-{
-    const long n = (long)B * D * U1;
-    const dim3 grid((unsigned)((n + 255) / 256));
-    if (lambda > 0.f)
-        hipLaunchKernelGGL(k_coef_restrict_fastemit, grid, dim3(256), 0, st, alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets,
-                           logit_lens, target_lens, coef, B, T, U1, D, scale, lambda);
-    else if (flush_log2)
-        hipLaunchKernelGGL(k_coef_restrict_flush, grid, dim3(256), 0, st, alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets,
-                           logit_lens, target_lens, coef, B, T, U1, D, scale, *flush_log2, flush_lin);
-    else
-        hipLaunchKernelGGL(k_coef_restrict, grid, dim3(256), 0, st, alpha_s, beta_s, denom_s, lpb_s, lpe_s, targets,
-                           logit_lens, target_lens, coef, B, T, U1, D, scale);
-}
-
-void launch_restrict(float *lpe_s, const int32_t *frames, const int32_t *logit_lens, const int32_t *target_lens, int B,
-                     int T, int U1, int D, int left, int right, float delay, hipStream_t st)
-{
-    const long n = (long)B * D * U1;
-    hipLaunchKernelGGL(k_restrict, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, lpe_s, frames, logit_lens,
-                       target_lens, B, T, U1, D, left, right, delay);
-}
-
-void launch_delay_penalty(float *lpe_s, const int32_t *logit_lens, const int32_t *target_lens, int B,
-                          int T, int U1, int D, float delay, hipStream_t st)
-{
-    const long n = (long)B * D * U1;
-    hipLaunchKernelGGL(k_delay_penalty, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, lpe_s,
-                       logit_lens, target_lens, B, T, U1, D, delay);
-}
-
-void launch_delay_cost(const double *beta_s, const int32_t *logit_lens, const int32_t *target_lens,
-                       float *costs, int B, int T, int U1, int D, float delay, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_delay_cost, dim3(1), dim3(256), 0, st, beta_s, logit_lens, target_lens, costs,
-                       B, T, U1, D, delay);
-}
-
-void launch_grad_logits(const float *logits, const CellCoef *coef, float *grad, long nrows,
-                        int V, int blank, float clamp, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_grad_logits, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, logits,
-                       coef, grad, nrows, V, blank, clamp);
+    hipLaunchKernelGGL(k_grad_logits, row_grid(a), dim3(256), 0, st, a.logits, a.coef, a.grad_logits, (long)a.B * a.T * a.U1, a.V,
+                       a.blank, a.clamp);
 }

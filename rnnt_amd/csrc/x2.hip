@@ -18,7 +18,7 @@
 // one code path); logits, log-softmax, lattice, coefficients and all reductions are the fp32 / fp64 code of the fp32 route.
 // Flush rule (below, "The flush rule and the live structures of the backward"): fp16's narrow exponent makes both planes of g_scale G
 // exactly zero wherever the lattice's occupancy is below ~2^-38 — half the cells of the benchmark's batch.  The coefficient kernel
-// proves that per cell (|g_scale G| < 2^-26, one binade inside what rounds to zero: lattice.hip coef_cell), and the two backward GEMMs
+// proves that per cell (|g_scale G| < 2^-26, one binade inside what rounds to zero: lattice.hip k_coef), and the two backward GEMMs
 // run the dHidden tiles and the 4-cell dW groups that hold another cell, each from an ascending list built on the device: k_dhidden_x2's
 // workgroups are the entries of the live-tile list, a k-step of k_dw_x2 is four entries of the live-group list.  RNNT_VARIANT_X2_NO_FLUSH_SKIP switches the rule off per call (same lists, by length).
 //
@@ -225,7 +225,7 @@ void launch_x2_zero_padding(const X3Args &a, int what, hipStream_t st)
 // g_scale G is split into two fp16 planes with round-to-nearest-even: a value of magnitude <= 2^-25 becomes hi = +-0, mid = +-0, and
 // a zero plane entry adds nothing to an MFMA accumulator.  |G[c,:]| <= grad_scale gamma(c), gamma = exp(alpha + beta - log P) the
 // posterior occupancy of lattice node c: an RNN-T lattice is occupied in a band around the alignment, and about half the cells of the
-// benchmark's batch lie below that threshold.  k_coef_flush (lattice.hip: the bound, its margin and the rounding it covers are
+// benchmark's batch lie below that threshold.  k_coef<.., FLUSH, ..> (lattice.hip: the bound, its margin and the rounding it covers are
 // derived there) gives every such cell the coefficients of a cell OUTSIDE the lattice — for which k_dhidden_x2 always produced
 // G = 0 from the zero padding row — and the kernels below turn the coefficients into what lets the two backward GEMMs skip:
 //   tile_live[b][tt][ub]  the dHidden tile (8 t x 16 u) holds a cell with non-null coefficients;

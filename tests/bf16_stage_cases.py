@@ -112,7 +112,7 @@ def loss64(logits, d):
 
 def coef64(d, work, costs, gs):
     """common.hpp CellCoef in fp64 from the oracle's alpha, beta, denom ([B, T, U1]): G[v] = 2^(logit[v] log2e + c1) - [v = blank] sb -
-    [v = y] se.  Outside the lattice: c1 = -inf, sb = se = 0, y = -1 (lattice.hip coef_cell)."""
+    [v = y] se.  Outside the lattice: c1 = -inf, sb = se = 0, y = -1 (lattice.hip k_coef)."""
     B, T, U1, _, V = dims(d)
     al, be, de = work["alpha"], work["beta"], work["denom"]
     ins = inside(d)

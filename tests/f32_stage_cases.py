@@ -26,7 +26,7 @@ Where the issue's derivations were off:
     yardsticks are therefore the plain chains they were meant to be (chain_six, chain_mm, chain_colsum), + half an ulp for the store;
   * the bf16x3 dot products have 6 x (their length) terms, not (their length): the bounds count them;
   * lp_emit of a cell without a label (u >= U_b) is never read: left out of the statistics' and the lattice's comparisons;
-  * bf16_stage_cases.coef64 rebuilds lp_blank / lp_emit from logits and the oracle's denominator; coef_cell reads the device's own
+  * bf16_stage_cases.coef64 rebuilds lp_blank / lp_emit from logits and the oracle's denominator; k_coef reads the device's own
     fp32 lp planes and takes the cost from beta[0, 0], so the coefficients' reference here is coef_f64 on exactly those planes."""
 import functools
 
@@ -278,7 +278,7 @@ def sweep(lpb, lpe, d, corr=corr64, stale_col=None, beta_from_zero=False):
 
 
 def coef_f64(alpha, beta, denom, lpb, lpe, d, gs):
-    """lattice.hip coef_cell in fp64 from the planes it reads ([B, T, U1] each; the cost is -beta[b, 0, 0]) -> dict of [cells] arrays:
+    """lattice.hip k_coef in fp64 from the planes it reads ([B, T, U1] each; the cost is -beta[b, 0, 0]) -> dict of [cells] arrays:
     c1 (-inf outside the lattices), sb, se, y (-1 where no label), xb / xe, the arguments of the two exponentials, and c1mag, the sum of
     the absolute values of c1's terms."""
     B, T, U1, _, _ = dims(d)
@@ -497,7 +497,7 @@ def exp_yard():
 
 
 def check_coef(coef_dev, y_dev, alpha, beta, denom, lpb, lpe, d, gs):
-    """coef [cells][4] = (c1, sb, se) fp32 and y int32 (lattice.hip coef_cell) against coef_f64 on the planes the device's kernel
+    """coef [cells][4] = (c1, sb, se) fp32 and y int32 (lattice.hip k_coef) against coef_f64 on the planes the device's kernel
     read ([B, T, U1], unskewed).  Exact parts: c1 = -inf, sb = se = 0, y = -1 outside the lattices; y the cell's label; sb = 0 where
     no blank arc leaves (t = T_b - 1, u < U_b); se = 0 where no label arc does.
       c1 = float32((alpha + cost + beta - denom + logf(scale)) log2e), the sum in fp64:  |dev - c1_64| <= ulp_fp32(c1_64) / 2 +

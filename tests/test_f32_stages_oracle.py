@@ -1,7 +1,7 @@
 """CPU: the comparators of tests/f32_stage_cases.py are neither too tight nor too loose, before any GPU time is spent.
   * not too tight: an fp32 numpy emulation of both routes (fast_tanh, fp32 products — on the bf16x3 route the six products of the
     exact 3-way bf16 splits, accumulated in fp32 —, a plain fp32 log-softmax, the lattice recurrence with its correction term in
-    fp32, coef_cell's fp32 roundings, G in fp32 and split, fp32 sums) passes every comparator on every case;
+    fp32, k_coef's fp32 roundings, G in fp32 and split, fp32 sums) passes every comparator on every case;
   * not too loose: each of fifteen seeded faults, applied to that emulation, is rejected on every case that has the geometry for it
     — and four GEMM faults, carried through every later stage, still pass the suite's 1e-4 bar on the final gradients of cfg2_hv;
   * the six products drop no more than x3.hip's header claims; the fp64 twins' final gradients are oracle_fused's."""

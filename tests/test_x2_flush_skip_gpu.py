@@ -1,4 +1,4 @@
-"""-m gpu: the f16x2 route's flush rule (rnnt_amd/csrc/lattice.hip coef_cell FLUSH, x2.hip "flush rule") against its own A/B
+"""-m gpu: the f16x2 route's flush rule (rnnt_amd/csrc/lattice.hip k_coef, FLUSH, x2.hip "flush rule") against its own A/B
 partner, RNNT_VARIANT_X2_NO_FLUSH_SKIP, in one process: skipping dHidden tiles and dW k-steps without a live cell changes no bit
 of costs, grad_enc, grad_pred, and grad_W / grad_bias by no more than the route's own distance from the fp32 route.  The
 shapes (tests/x2_flush_twin.py CASES) are checked on the CPU (tests/test_x2_flush_oracle.py) to leave >= 25 % of the dHidden

@@ -1,4 +1,4 @@
-"""fp64 twin of the f16x2 route's flush rule (rnnt_amd/csrc/lattice.hip coef_cell FLUSH, x2.hip "flush rule").
+"""fp64 twin of the f16x2 route's flush rule (rnnt_amd/csrc/lattice.hip k_coef, FLUSH, x2.hip "flush rule").
 
 The device gives a lattice cell the coefficients of a cell outside the lattice when
     s1 = log2(grad_scale * gamma) < -26 - log2 g_scale     and     sb + se < 2^-26 / g_scale
