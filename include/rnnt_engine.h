@@ -622,7 +622,8 @@ int rnnt_engine_greedy_stream_lstm_push(const void *frames, int64_t frame_stride
 int rnnt_engine_greedy_decode_persistent_workspace_bytes(int T, int S, int E, int O, int H, int V, int has_text, size_t *out);
 /* `tables`: NULL (the tables are rebuilt in the workspace by this call: ~0.13 ms) or a caller-owned buffer filled by
  * rnnt_engine_greedy_decode_build_tables for the SAME parameters (conv2's pack, the conv1 tap tables, the folded text_ln): build once per
- * set of weights, decode any number of utterances — concurrently on several streams too (the tables are only read). */
+ * set of weights, decode any number of utterances — concurrently on several streams too (the tables are only read).  The tables take
+ * any S (the beam searches bring them too); S > 4096 is refused by the persistent loop's own size query, not here. */
 int rnnt_engine_greedy_decode_tables_bytes(int S, int E, int O, int H, int has_text, size_t *out);
 int rnnt_engine_greedy_decode_build_tables(const rnnt_conv_predictor_params *p, int S, int E, int O, float ln_in_eps, const void *text_W,
                                            const void *text_b, int H, void *tables, size_t tables_bytes, void *stream);

@@ -40,9 +40,12 @@ def single_forward(audio_row, text_row, joint_sd):
     return _linear(np.tanh(a + t), joint_sd["joint_ln.weight"], joint_sd["joint_ln.bias"])
 
 
-def greedy_decode(frames, pred_sd, joint_sd, max_length=200, eps=1e-5, window=None):
+def greedy_decode(frames, pred_sd, joint_sd, max_length=200, eps=1e-5, window=None, blank=None, tied=None):
     """frames [T, C]: the encoder output of ONE utterance after the permute of rnnt/model.py:93 (time major).
     Returns (tokens without the leading blank, margins): margins[i] = top-1 minus top-2 logit of the i-th decision.
+    `blank`: the blank's index (None: V - 1, the reference's, rnnt/joint.py:20).  `tied=(a, b)`: two classes whose logits are
+    equal BY CONSTRUCTION (zero weight rows, one bias): the lower index wins between them (numpy's argmax, as torch.argmax), and a
+    decision won by one of them reports its margin to the best logit OUTSIDE the pair — the gap that rounding could still turn.
     `window=None` re-runs the predictor on the whole history like the reference (rnnt/model.py:119-121).  `window=7` feeds only the
     last 7 tokens once the history is longer: the module is causal (k=3 then k=5 convolutions behind left zero padding,
     rnnt/causalconv.py:28-29), so its last frame is a function of exactly those — the same numbers at a cost that does not grow
@@ -50,7 +53,8 @@ def greedy_decode(frames, pred_sd, joint_sd, max_length=200, eps=1e-5, window=No
     frames = np.asarray(frames, dtype=np.float64)
     pred_sd = {k: np.asarray(v, dtype=np.float64) for k, v in pred_sd.items()}
     joint_sd = {k: np.asarray(v, dtype=np.float64) for k, v in joint_sd.items()}
-    blank = joint_sd["joint_ln.weight"].shape[0] - 1  # rnnt/joint.py:20
+    if blank is None:
+        blank = joint_sd["joint_ln.weight"].shape[0] - 1  # rnnt/joint.py:20
     # the projected audio frame does not depend on the loop: same arithmetic, once
     if "audio_ln.weight" in joint_sd:
         frames = _linear(frames, joint_sd["audio_ln.weight"], joint_sd["audio_ln.bias"])
@@ -71,8 +75,12 @@ def greedy_decode(frames, pred_sd, joint_sd, max_length=200, eps=1e-5, window=No
     while t < T and len(tokens) < max_length:
         logits = single_forward(frames[t], feat, jsd)
         tok = int(np.argmax(logits))
-        top2 = np.partition(logits, -2)[-2:]
-        margins.append(float(top2[1] - top2[0]))
+        if tied is not None and tok in tied:
+            assert logits[tied[0]] == logits[tied[1]], "the tied pair's logits differ"
+            margins.append(float(logits[tok] - np.delete(logits, list(tied)).max()))
+        else:
+            top2 = np.partition(logits, -2)[-2:]
+            margins.append(float(top2[1] - top2[0]))
         if tok == blank or emitted >= MAX_PER_FRAME:
             t += 1
             emitted = 0

@@ -1075,7 +1075,10 @@ int rnnt_engine_greedy_decode_tables_bytes(int S, int E, int O, int H, int has_t
 {
     if (!out) return fail(RNNT_ERR_INVALID_ARG, "null size pointer");
     if (S < 1) return fail(RNNT_ERR_INVALID_ARG, "S=%d", S);
-    if (int rc = dec_persist_check(8, S, E, O, H, 1024, has_text, 2)) return rc;  // (the tables do not depend on V or T)
+    // (the tables do not depend on V or T.)  S: the persistent loop's limit of 4096 symbols is that loop's own — its size query states it —
+    // and not the tables': the batched and the streaming beam search bring them too and take any S, as the single search does, which
+    // builds them in its workspace
+    if (int rc = dec_persist_check(8, S > 4096 ? 4096 : S, E, O, H, 1024, has_text, 2)) return rc;
     *out = align_up(dec_tables_floats(S, E, O, H, has_text) * 4);
     return RNNT_OK;
 }

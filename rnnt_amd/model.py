@@ -206,10 +206,19 @@ class RNNTModel(torch.nn.Module):
 
     def _decode_frames(self, audio):
         """Encoder output (1, n, C), permuted as rnnt/model.py:93 -> the [n, H] fp32 frames the decode entries read: audio_ln applied
-        (per frame: the same numbers chunk by chunk), contiguous."""
+        (per frame: the same numbers chunk by chunk), contiguous.  audio_ln runs on the engine's fp32 GEMM (rnnt_engine_linear_fwd: one kernel,
+        a row's sum does not depend on how many rows the call has).  torch.nn.Linear's library GEMM picks its kernel by the row count: at
+        the reference's widths a stream's chunks and the whole utterance then differed in the last bits, and with them the scores of
+        beam_stream and beam_search (1.5e-5 at -175.8 on decode_ref_widths_proj pushed frame by frame) that are promised equal."""
         frames, joint = audio[0], self.joint
         if hasattr(joint, "audio_ln"):
-            frames = joint.audio_ln(frames)
+            ln = joint.audio_ln
+            if (frames.is_cuda and frames.shape[0] > 0 and frames.dtype == ln.weight.dtype == torch.float32 and ln.bias is not None
+                    and ln.in_features % 4 == 0 and ln.out_features % 4 == 0):
+                from . import engine
+                frames = engine.linear_fwd(frames, ln.weight, ln.bias, backend="fp32")
+            else:
+                frames = ln(frames)
         return frames.float().contiguous()
 
     @staticmethod
