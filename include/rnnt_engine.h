@@ -88,8 +88,8 @@ void rnnt_engine_set_debug(void *buf);
 /* RNNT_DTYPE_F32_BF16X3 only: run one stage on the fp32 route's kernel instead of the bf16x3 one (same data
  * layout downstream, plain splitting kernels in between) — how each bf16x3 kernel is checked in isolation.
  * NOT bit-identical to the default bf16x3 kernels (different summation), same tolerance. */
-#define RNNT_VARIANT_X3_FP32_FWD 4096       /* forward GEMM + hidden by the fp32 kernel, then k_x3_make_hidden */
-#define RNNT_VARIANT_X3_FP32_DH 8192        /* dHidden + G by the fp32 kernels, then k_x3_split_g (needs _FWD too) */
+#define RNNT_VARIANT_X3_FP32_FWD 4096       /* forward GEMM + hidden by the fp32 kernel, then k_split_make_hidden */
+#define RNNT_VARIANT_X3_FP32_DH 8192        /* dHidden + G by the fp32 kernels, then k_split_g (needs _FWD too) */
 /* RNNT_DTYPE_F32_F16X2 only: switch the flush rule off for this call.  By default that route gives every lattice cell whose
  * gradient row its fp16 split provably rounds to zero (|g_scale G| < 2^-26: rnnt_amd/csrc/lattice.hip k_coef, x2.hip) the
  * coefficients of a cell outside the lattice; dHidden tiles and 16-cell dW k-steps without a live cell are then skipped.  With this

@@ -29,43 +29,11 @@
 // W is re-packed once per call (2 x 1 MB at H=512,V=1024) into exactly the order the B
 // fragments are consumed, so staging a chunk is a linear copy L2 -> VGPR -> LDS.
 #include "kernels.hpp"
+#include "mma_common.hpp"
 
-// Diagnostic build only (-DBF_CLOCK, with an engine.o built -DRNNT_STAMPS so that Bf16Args::debug is set): workgroup
-// (0,0,0) stamps the core clock counter and the 100 MHz reference at its start and end into debug[SLOT .. SLOT+3] (a buffer nothing
-// else reads): the clock the launch ran at = d(s_memtime) / d(s_memrealtime) x 100 MHz (tools/exp_bf16_clock.py).
-#ifdef BF_CLOCK
-#define BF_CLOCK_STAMP(SLOT)                                                                                               \
-    do {                                                                                                                   \
-        if (a.debug && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) {                        \
-            unsigned long long t_, r_;                                                                                     \
-            asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_), "=s"(r_)::"memory");      \
-            a.debug[SLOT] = t_; a.debug[(SLOT) + 1] = r_;                                                                  \
-        }                                                                                                                  \
-    } while (0)
-#else
-#define BF_CLOCK_STAMP(SLOT) do {} while (0)
-#endif
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 typedef short i16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) i16x4 *lds_i16x4_ptr;
-typedef __attribute__((address_space(3))) void *lds_vptr;
 
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi)
-{
-    bf16x2 v = {(__bf16)lo, (__bf16)hi};  // v_cvt_pk_bf16_f32: RNE, NaN stays NaN
-    return __builtin_bit_cast(unsigned, v);
-}
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-__device__ __forceinline__ unsigned pack_f16(float lo, float hi)
-{
-    const f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));  // v_cvt_pk_f16_f32 (RNE)
-}
 __device__ __forceinline__ unsigned pk_max_f16(unsigned x, unsigned y)  // max of two pairs of halves
 {
     unsigned d;
@@ -77,24 +45,6 @@ __device__ __forceinline__ unsigned max_halves_f16(unsigned x)  // low half of t
     unsigned d;
     asm("v_max_f16_sdwa %0, %1, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_1" : "=v"(d) : "v"(x));
     return d;
-}
-__device__ __forceinline__ float f16_lo(unsigned u) { return (float)__builtin_bit_cast(f16x2, u)[0]; }
-__device__ __forceinline__ float f16_hi(unsigned u) { return (float)__builtin_bit_cast(f16x2, u)[1]; }
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c)
-{
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
-                                                   __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// publish this wave's LDS writes / retire its LDS reads, then join the workgroup.  Not
-// __syncthreads(): that also waits vmcnt(0) and would drain the global prefetch rings.
-__device__ __forceinline__ void lds_barrier()
-{
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -468,7 +418,6 @@ __global__ __launch_bounds__(256, 2) void k_joint_fwd_bf16(Bf16Args a)
 #define FRSTAMP(slot) do {} while (0)
 #endif
 #define FR_SLOT 16384
-template <int N> struct BInt { static constexpr int value = N; };
 
 // W in the order k_joint_fwd_bf16_ra consumes it: [pass][c][s][tile(4)][lane] x 8 bf16, element e =
 // W[v = 128*pass + 32*(rho>>3) + 16*((rho>>2)&1) + 4*tile + (rho&3)][h = 64c + 32*(lane>>5) + 8s + e], rho = lane&31
@@ -648,7 +597,7 @@ __global__ __launch_bounds__(256, (KC <= 8 ? 2 : 1)) void k_joint_fwd_bf16_ra(Bf
     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(8 * KC < 63 ? 8 * KC : 63) : "memory");
     lds_barrier();
     FRSTAMP(3);
-    reads(g0, rb, BInt<0>{});
+    reads(g0, rb, Int<0>{});
 
     // logits staging: lane (j, half) writes its 32 bytes of a g group to row j (64 bytes per row), 16-byte chunk
     // 2*half + k at position chunk ^ ((j>>2)&3); lane l then reads chunk l&3 of rows (l>>2), 16 + (l>>2) and stores it
@@ -669,35 +618,35 @@ __global__ __launch_bounds__(256, (KC <= 8 ? 2 : 1)) void k_joint_fwd_bf16_ra(Bf
             if (pass == 3) FRSTAMP(65 + 3 * c);
             landed(g0, false);
             const int sb = rb + ((n & 3) << 14), sbn = rb + (((n + 1) & 3) << 14);
-            reads(g1, sb, BInt<1>{});
-            mma4(BInt<(c == 0)>{}, A[c][0], g0, n, 0);
+            reads(g1, sb, Int<1>{});
+            mma4(Int<(c == 0)>{}, A[c][0], g0, n, 0);
             landed(g1, true);
-            reads(g0, sb, BInt<2>{});
-            mma4(BInt<0>{}, A[c][1], g1, n, 1);
+            reads(g0, sb, Int<2>{});
+            mma4(Int<0>{}, A[c][1], g1, n, 1);
             landed(g0, true);
-            reads(g1, sb, BInt<3>{});
-            mma4(BInt<0>{}, A[c][2], g0, n, 2);
+            reads(g1, sb, Int<3>{});
+            mma4(Int<0>{}, A[c][2], g0, n, 2);
             landed(g1, true);
-            reads(g0, sbn, BInt<0>{});  // first group of chunk n+1 (published above; past the end: an unused landed slot)
-            mma4(BInt<0>{}, A[c][3], g1, n, 3);
+            reads(g0, sbn, Int<0>{});  // first group of chunk n+1 (published above; past the end: an unused landed slot)
+            mma4(Int<0>{}, A[c][3], g1, n, 3);
             if (pass == 3) FRSTAMP(66 + 3 * c);
         };
-        if constexpr (KC >= 1) chunk(BInt<0>{});
-        if constexpr (KC >= 2) chunk(BInt<1>{});
-        if constexpr (KC >= 3) chunk(BInt<2>{});
-        if constexpr (KC >= 4) chunk(BInt<3>{});
-        if constexpr (KC >= 5) chunk(BInt<4>{});
-        if constexpr (KC >= 6) chunk(BInt<5>{});
-        if constexpr (KC >= 7) chunk(BInt<6>{});
-        if constexpr (KC >= 8) chunk(BInt<7>{});
-        if constexpr (KC >= 9) chunk(BInt<8>{});
-        if constexpr (KC >= 10) chunk(BInt<9>{});
-        if constexpr (KC >= 11) chunk(BInt<10>{});
-        if constexpr (KC >= 12) chunk(BInt<11>{});
-        if constexpr (KC >= 13) chunk(BInt<12>{});
-        if constexpr (KC >= 14) chunk(BInt<13>{});
-        if constexpr (KC >= 15) chunk(BInt<14>{});
-        if constexpr (KC >= 16) chunk(BInt<15>{});
+        if constexpr (KC >= 1) chunk(Int<0>{});
+        if constexpr (KC >= 2) chunk(Int<1>{});
+        if constexpr (KC >= 3) chunk(Int<2>{});
+        if constexpr (KC >= 4) chunk(Int<3>{});
+        if constexpr (KC >= 5) chunk(Int<4>{});
+        if constexpr (KC >= 6) chunk(Int<5>{});
+        if constexpr (KC >= 7) chunk(Int<6>{});
+        if constexpr (KC >= 8) chunk(Int<7>{});
+        if constexpr (KC >= 9) chunk(Int<8>{});
+        if constexpr (KC >= 10) chunk(Int<9>{});
+        if constexpr (KC >= 11) chunk(Int<10>{});
+        if constexpr (KC >= 12) chunk(Int<11>{});
+        if constexpr (KC >= 13) chunk(Int<12>{});
+        if constexpr (KC >= 14) chunk(Int<13>{});
+        if constexpr (KC >= 15) chunk(Int<14>{});
+        if constexpr (KC >= 16) chunk(Int<15>{});
 
         // ---- pass end: + bias, fp16 logits out (through the wave's staging space), statistics from the rounded values
         FRSTAMP(5 + 3 * pass);
@@ -807,14 +756,9 @@ static int bf16_fwd_ra_kc(int H) { return (H == 128 || H == 256 || H == 512 || H
 template <int KC>
 static void launch_fwd_ra(const Bf16Args &a, hipStream_t st)
 {
-    static bool attr_set[16] = {false};
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;
     const int lds = 4 * FR_SLOT + 2 * 512 + 4 * 2048;
-    if (dev < 0 || !attr_set[dev]) {
-        (void)hipFuncSetAttribute((const void *)k_joint_fwd_bf16_ra<KC>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (dev >= 0) attr_set[dev] = true;
-    }
+    static LdsOptIn lds_opt_in;
+    lds_opt_in.raise(lds, k_joint_fwd_bf16_ra<KC>);
     hipLaunchKernelGGL(k_joint_fwd_bf16_ra<KC>, dim3((unsigned)(a.rows_alloc / 128)), dim3(256), lds, st, a);
 }
 
@@ -1390,15 +1334,8 @@ void launch_dw_bf16(const Bf16Args &a, hipStream_t st)
 {
     launch_dw_table(a.logit_lens, a.B, a.T, a.U1, BW_ROWS, a.dw_tab, st);
     const int tiles = ((a.V + 255) / 256) * ((a.H + 255) / 256);
-    // > 64 KiB of dynamic LDS needs the opt-in, once per DEVICE (a function attribute belongs to the
-    // device's code object); a read-mostly fact, like device_cus()
-    static bool attr_set[16] = {false};
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;  // unknown: set it every time
-    if (dev < 0 || !attr_set[dev]) {
-        (void)hipFuncSetAttribute((const void *)k_dw_bf16, hipFuncAttributeMaxDynamicSharedMemorySize, BW_NST * 32768);
-        if (dev >= 0) attr_set[dev] = true;
-    }
+    static LdsOptIn lds_opt_in;
+    lds_opt_in.raise(BW_NST * 32768, k_dw_bf16);
     if (a.dw_prog) launch_fill32(a.dw_prog, 0u, (size_t)a.n_split * 64, st);
     hipLaunchKernelGGL(k_dw_bf16, dim3(tiles * a.n_split), dim3(256), BW_NST * 32768, st, a);
 }

@@ -13,6 +13,7 @@
 #include <string>
 
 #include "kernels.hpp"
+#include "mma_common.hpp"
 
 namespace {
 
@@ -184,8 +185,6 @@ void layout(int B, int T, int U1, int H, int V, int dtype, rnnt_engine_ws_layout
 }
 
 }  // namespace
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(256) void k_fill32(unsigned *__restrict__ p, unsigned value, size_t n_words, int vec)
 {
@@ -444,13 +443,20 @@ int route_bf16(const FusedCall &c)
     return launch_status("rnnt_engine fused pipeline (bf16)");
 }
 
+// the fp32 kernels' view of a split route's call: the dHidden reductions', the stand-in dHidden's
+JointBwdArgs split_bwd_args(const FusedCall &c)
+{
+    JointBwdArgs g = bwd_args(c); g.hidden = aux_hidden(c);
+    if (c.x3_fp32_dh) g.pred_split_col = tile_kernel_cols(c);
+    else { g.gen_bu = 16; g.pred_split_col = c.H; }  // x3 / x2 tiles: 8 t x 16 u, every dPred slab 8 t rows high
+    return g;
+}
+
 // fp32-accurate route on the bf16 matrix pipes (x3.hip)
 int route_bf16x3(const FusedCall &c)
 {
     const X3Args h = x3_args(c, x3_wpack_fwd_bytes(c.H, c.V), operand_scales(c.grad_scale, c.fastemit));
-    JointBwdArgs g = bwd_args(c); g.hidden = aux_hidden(c);  // the fp32 kernels' view: the dHidden reductions', the stand-in dHidden's
-    if (c.x3_fp32_dh) g.pred_split_col = tile_kernel_cols(c);
-    else { g.gen_bu = 16; g.pred_split_col = c.H; }  // x3 / x2 tiles: 8 t x 16 u, every dPred slab 8 t rows high
+    JointBwdArgs g = split_bwd_args(c);
     if (c.stages & ST_PROD) { launch_x3_zero_padding(h, 1, c.st); launch_x3_pack_w(h, c.st); }
     if (c.x3_fp32_fwd) standin_forward(c, h, launch_x3_make_hidden);
     else if (c.stages & ST_FWD) launch_joint_fwd_x3(h, c.st);
@@ -473,13 +479,11 @@ int route_f16x2(const FusedCall &c)
     X3Args h = x3_args(c, x2_wpack_fwd_bytes(c.H, c.V), s);
     h.dw_prog = c.cb->dw_prog(c.B); h.dw_ksteps = x2_dw_walks_ksteps(c.H, c.V) ? 1 : 0;
     x2_live_carve(c.ws + c.L.x2_live, c.B, c.T, c.U1, (long)c.L.rows_pad, h);
-    JointBwdArgs g = bwd_args(c); g.hidden = aux_hidden(c);  // the fp32 kernels' view: the dHidden reductions', the stand-in dHidden's
-    if (c.x3_fp32_dh) g.pred_split_col = tile_kernel_cols(c);
-    else { g.gen_bu = 16; g.pred_split_col = c.H; }  // x3 / x2 tiles: 8 t x 16 u, every dPred slab 8 t rows high
+    JointBwdArgs g = split_bwd_args(c);
     // k_dhidden_x2 runs the live tiles only and no dead tile writes a slab: the reductions skip by the same flags
     if (!c.x3_fp32_dh) { g.tile_flag = h.tile_live; g.flag_ntt = (c.T + 7) / 8; g.flag_nub = h.n_ublk16; }
     // The threshold; -inf flags nothing.  The fp32 kernels standing in for dHidden multiply G in fp32, where a flushed cell's G is small but not
-    // zero: no flush, no tile skipping there (k_x2_split_g writes every row, so the dW list walk still applies)
+    // zero: no flush, no tile skipping there (k_split_g writes every row, so the dW list walk still applies)
     if (c.x2_no_flush || c.x3_fp32_dh) { s.flush_log2 = -HUGE_VAL; s.flush_lin = 0.f; }
     if (c.stages & ST_PROD) { launch_x2_zero_padding(h, 1, c.st); launch_x2_pack_w(h, c.cb->x2_scales, c.st); launch_x2_make_ep(h, c.st); }
     if (c.x3_fp32_fwd) standin_forward(c, h, launch_x2_make_hidden);
@@ -541,7 +545,7 @@ int run_fused(int stages, int variant, const void *enc, const int64_t enc_stride
     if (dtype == RNNT_DTYPE_F32_BF16X3 || dtype == RNNT_DTYPE_F32_F16X2) {
         const bool x2 = dtype == RNNT_DTYPE_F32_F16X2;
         c.x3_fp32_dh = (variant & RNNT_VARIANT_X3_FP32_DH) != 0 || !(x2 ? x2_dhidden_ok(U1, H, V) : x3_dhidden_ok(U1, H, V));
-        c.x3_fp32_fwd = (variant & RNNT_VARIANT_X3_FP32_FWD) != 0 || !(x2 ? x2_fwd_ok(U1, H, V) : x3_fwd_ok(U1, H, V)) || c.x3_fp32_dh;  // fp32 dHidden reads fp32 hidden
+        c.x3_fp32_fwd = (variant & RNNT_VARIANT_X3_FP32_FWD) != 0 || !split_fwd_ok(U1, H, V) || c.x3_fp32_dh;  // fp32 dHidden reads fp32 hidden
         if (c.x3_fp32_fwd && ws_bytes < c.L.total + c.L.aux_bytes)
             return fail(RNNT_ERR_WORKSPACE, "workspace %zu < %zu bytes: a stage on the fp32 route's kernels (RNNT_VARIANT_X3_FP32_*, or a "
                         "shape k_joint_fwd_x3 / k_dhidden_x3 do not cover) needs total + aux_bytes of rnnt_engine_workspace_layout",

@@ -25,10 +25,8 @@
 // main loops.  A lane's 16-byte load supplies either 4 k-steps (k contiguous in memory:
 // G for the dHidden kernels) or 4 interleaved tiles (m/n contiguous in memory: W rows, G and
 // hidden for k_dw), so every global access is a full 16 B per lane.
-#include "common.hpp"
 #include "kernels.hpp"
-
-typedef __attribute__((address_space(3))) void *lds_void_ptr;
+#include "mma_common.hpp"
 
 #define DH_BT 8
 #define DW_KC 16   // cells per dW split-range granule (row padding unit)
@@ -255,7 +253,6 @@ __global__ __launch_bounds__(512, 2) void k_dhidden(JointBwdArgs a, int cb0)
 // accumulators; W fragments straight L2 -> VGPR one chunk ahead; logits three chunks ahead.
 // Tiles with t0 >= T_b (ragged batches) only zero their G rows.  grid (n_ublk, ceil(T/8), B).
 #define DG_BT 8
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 #ifdef RNNT_STAMPS
 // Diagnostic build only (make EXTRA=-DRNNT_STAMPS): s_memtime stamps of every 16th workgroup.
 #define GSTAMP(slot)                                                                          \
@@ -397,7 +394,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_gen(JointBwdArgs a, const in
         return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(lrsrc, xvoff, 32 * (c8 < VK ? c8 : VK - 1), 0));
     };
     auto gstore = [&](const f32x4 &g, int c8) {
-        if (GEN) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, g), lrsrc, svoff, 32 * c8, 0);
+        if (GEN) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, g), lrsrc, svoff, 32 * c8, 0);
     };
 
     f32x4 xr[4];           // raw logits of chunks c+3 .. c+6 (ring, slot = chunk & 3)

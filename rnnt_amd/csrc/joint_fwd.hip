@@ -27,8 +27,8 @@
 //    (RNNT_VARIANT_FWD_LDS_RING).
 //  * Persistent launch: 2 workgroups per CU for the whole kernel, tiles from one atomic counter; the
 //    non-MFMA phases of a tile issue at s_setprio 1 so they overlap the co-resident workgroup's MFMAs.
-#include "common.hpp"
 #include "kernels.hpp"
+#include "mma_common.hpp"
 
 #define FWD_MWAVES 2  // 4 waves = 2 (M) x 2 (N), one per SIMD; TWO workgroups per CU (BREG path)
 #define FWD_ROWS (32 * FWD_MWAVES)
@@ -170,8 +170,6 @@ void launch_copy_enc(const float *enc, long sb, long st_, long sh, float *dst, i
 #define FWD_NBUF 4         // LDS ring of B chunks
 #define FWD_BCHUNK 1024    // float4 per staged chunk: 512 columns x 8 k
 
-typedef __attribute__((address_space(3))) void *lds_void_ptr;
-
 // Register-destination loads that hipcc must NOT see: next to an LDS-DMA in flight it would
 // guard their first use with s_waitcnt vmcnt(0) and drain the DMA ring every chunk.  The
 // destinations are only read after vm_wait<N>(), which names them as in/out operands so no
@@ -241,11 +239,11 @@ __device__ __forceinline__ void fwd_mainloop(const float *erow, const float *pro
     const char *wlane = (const char *)wpass + dlane;  // per-lane source of chunk 0
     auto dma = [&](unsigned chunk_off, int slot) {  // chunk_off: uniform byte offset of the chunk
         f32x4 *dst = ldsb + slot * FWD_BCHUNK + wave * 64 * DPW;  // wave-uniform (goes to M0)
-        __builtin_amdgcn_global_load_lds((const void *)(wlane + chunk_off), (lds_void_ptr)dst, 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((const void *)(wlane + chunk_off), (lds_void_ptr)dst, 16, 1024, 0);
+        __builtin_amdgcn_global_load_lds((const void *)(wlane + chunk_off), (lds_vptr)dst, 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((const void *)(wlane + chunk_off), (lds_vptr)dst, 16, 1024, 0);
         if (DPW == 4) {
-            __builtin_amdgcn_global_load_lds((const void *)(wlane + chunk_off), (lds_void_ptr)dst, 16, 2048, 0);
-            __builtin_amdgcn_global_load_lds((const void *)(wlane + chunk_off), (lds_void_ptr)dst, 16, 3072, 0);
+            __builtin_amdgcn_global_load_lds((const void *)(wlane + chunk_off), (lds_vptr)dst, 16, 2048, 0);
+            __builtin_amdgcn_global_load_lds((const void *)(wlane + chunk_off), (lds_vptr)dst, 16, 3072, 0);
         }
     };
     const int roff = wn * 512 + lane;  // this wave's first fragment inside a staged chunk

@@ -202,7 +202,8 @@ struct X3Args {
 size_t x2_live_bytes(int B, int T, int U1, long rows_pad);  // bytes of the region below
 void x2_live_carve(void *region, int B, int T, int U1, long rows_pad, X3Args &a);  // points tile_live .. grp_list into the region
 void launch_x2_live(const X3Args &a, hipStream_t st);  // builds them all from X3Args::coef
-bool x3_fwd_ok(int U1, int H, int V);      // the bf16x3 forward kernel covers this shape (else: the fp32 route's)
+// the split routes' forward kernels (k_joint_fwd_x3, k_joint_fwd_x2) cover this shape (else: the fp32 route's)
+inline bool split_fwd_ok(int U1, int H, int V) { return H % 128 == 0 && V % 128 == 0 && (long)128 * H * 2 < 0x7fffffffL; }
 bool x3_dhidden_ok(int U1, int H, int V);  // likewise k_dhidden_x3
 size_t x3_wpack_fwd_bytes(int H, int V);
 size_t x3_wpack_dh_bytes(int H, int V);
@@ -214,7 +215,6 @@ void launch_joint_fwd_x3(const X3Args &a, hipStream_t st);   // one 512-register
 void launch_dhidden_x3(const X3Args &a, hipStream_t st);
 void launch_dw_x3(const X3Args &a, hipStream_t st);   // v_mfma_f32_32x32x16_bf16, six products per k-step (default)
 // RNNT_DTYPE_F32_F16X2 (x2.hip): the bf16x3 route's stages on two fp16 planes and three products
-bool x2_fwd_ok(int U1, int H, int V);
 bool x2_dhidden_ok(int U1, int H, int V);
 size_t x2_wpack_fwd_bytes(int H, int V);
 size_t x2_wpack_dh_bytes(int H, int V);

@@ -24,73 +24,11 @@
 //
 // MFMA operand maps (v_mfma_f32_32x32x16_f16, as the bf16 form): lane l = (r = l&31, h = l>>5) holds A[row r][k = 8h+j] and
 // B[k = 8h+j][col r], j = 0..7; C/D: col = l&31, row = (reg&3) + 8*(reg>>2) + 4*(l>>5).
-#include "kernels.hpp"
+#include "split_common.hpp"
 
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((address_space(3))) void *lds_vptr;
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-// Diagnostic build only (-DRNNT_STAMPS): workgroup 0 stamps the core clock counter and the 100 MHz reference at its start and
-// end into debug[SLOT..] (a buffer nothing else reads): the clock this launch ran at (tools/exp_x3_clock.py).
-#ifdef RNNT_STAMPS
-#define X2_CLOCK_STAMP(SLOT)                                                                                               \
-    do {                                                                                                                   \
-        if (a.debug && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) {                        \
-            unsigned long long t_, r_;                                                                                     \
-            asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_), "=s"(r_)::"memory");      \
-            a.debug[SLOT] = t_; a.debug[(SLOT) + 1] = r_;                                                                  \
-        }                                                                                                                  \
-    } while (0)
-#else
-#define X2_CLOCK_STAMP(SLOT) do {} while (0)
-#endif
-
-#define X2_SH 16384.0f          // scale of the hidden operand (|tanh| <= 1)
-#define X2_INV_SH (1.0f / 16384.0f)
-#define X2_F16_MAX 65504.0f
-
-__device__ __forceinline__ unsigned x2_pack(float lo, float hi)
-{
-    f16x2 v = {(_Float16)lo, (_Float16)hi};  // v_cvt_pk_f16_f32: RNE
-    return __builtin_bit_cast(unsigned, v);
-}
-// two (scaled) fp32 values -> their (hi, mid) fp16 pieces, packed pairwise (element 0 in the low half): 4 instructions
-struct X2Pieces { unsigned h, m; };
-__device__ __forceinline__ X2Pieces x2_split2(float a, float b)
-{
-    X2Pieces p;
-    p.h = x2_pack(a, b);
-    float ra, rb;  // x - hi, exact (the residual has <= 14 significant bits): v_fma_mix reads the fp16 half in place
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(ra) : "v"(p.h), "v"(a));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(rb) : "v"(p.h), "v"(b));
-    p.m = x2_pack(ra, rb);
-    return p;
-}
-__device__ __forceinline__ float x2_clamp(float x) { return __builtin_amdgcn_fmed3f(x, -X2_F16_MAX, X2_F16_MAX); }
-// four consecutive (scaled) fp32 values -> 2 packed dwords per plane at dword positions d, d+1 of the plane vectors
-#define X2_SPLIT4(x4, ph, pm, d)                                      \
-    do {                                                              \
-        const X2Pieces p0_ = x2_split2((x4)[0], (x4)[1]);             \
-        const X2Pieces p1_ = x2_split2((x4)[2], (x4)[3]);             \
-        (ph)[d] = p0_.h; (pm)[d] = p0_.m;                             \
-        (ph)[(d) + 1] = p1_.h; (pm)[(d) + 1] = p1_.m;                 \
-    } while (0)
-__device__ __forceinline__ f32x16 x2_mfma(u32x4 a, u32x4 b, f32x16 c)
-{
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void x2_lds_barrier()
-{
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-}
-template <int N> struct X2Int { static constexpr int value = N; };
 #define XW2_ROWS 16  // cells per dW k-step (the live structures below are built in these units)
 #define XG2_BT 8     // the dHidden tile: 8 t x 16 u cells
 #define XG2_BU 16
@@ -143,82 +81,12 @@ __global__ __launch_bounds__(1024) void k_x2_wscale(const float *__restrict__ W,
     }
 }
 
-// ---------------------------------------------------------------------------------------
-// Plain producers (the unfused variants RNNT_VARIANT_X3_FP32_*: every fused kernel is checked against the same pipeline
-// with one stage swapped; also the plain statement of the data layout).
-// ---------------------------------------------------------------------------------------
-// hidden planes [2][rows_alloc][H] fp16 of 2^14 tanh(enc + pred), every cell.  One thread = 8 columns of one row.
-__global__ __launch_bounds__(256) void k_x2_make_hidden(X3Args a)
-{
-    const int H8 = a.H / 8;
-    const long cells = (long)a.B * a.T * a.U1;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= cells * H8) return;
-    const long c = idx / H8;
-    const int h = (int)(idx - c * H8) * 8;
-    const int u = (int)(c % a.U1);
-    const long bt = c / a.U1;
-    const int t = (int)(bt % a.T), b = (int)(bt / a.T);
-    const float *ep = a.enc + (long)b * a.enc_sb + (long)t * a.enc_st + h;
-    const float *pp = a.pred + ((long)b * a.U1 + u) * a.H + h;
-    f32x4 t0 = fast_tanh_sum4(*(const f32x4 *)ep, *(const f32x4 *)pp);
-    f32x4 t1 = fast_tanh_sum4(*(const f32x4 *)(ep + 4), *(const f32x4 *)(pp + 4));
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { t0[k] = x2_clamp(t0[k] * X2_SH); t1[k] = x2_clamp(t1[k] * X2_SH); }  // (hidden = tanh(.) is finite or NaN; v_med3 maps a NaN to -65504: non-finite enc / pred are caught upstream by k_x2_make_ep's flag and run the exact form)
-    u32x4 ph, pm;
-    X2_SPLIT4(t0, ph, pm, 0);
-    X2_SPLIT4(t1, ph, pm, 2);
-    u32x4 *o = (u32x4 *)(a.hidden + c * a.H + h);
-    const long ps = a.plane_stride / 8;  // u32x4 units
-    o[0] = ph; o[ps] = pm;
-}
-
-// fp32 G (what the fp32 route's kernels leave in place of the logits) -> g_scale G as two planes, hi | mid over the same 128
-// bytes of every 32-wide chunk.  One thread = one chunk of one row (it reads the whole 128 bytes before it overwrites them).
-__global__ __launch_bounds__(256) void k_x2_split_g(X3Args a, long rows)
-{
-    const int VC = a.V / 32;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= rows * VC) return;
-    const long r = idx / VC;
-    const int c = (int)(idx - r * VC);
-    f32x4 *p = (f32x4 *)(a.logits + r * a.V + 32 * c);
-    f32x4 x[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        x[i] = p[i];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) x[i][k] = x2_clamp(x[i][k] * a.g_scale);
-    }
-    u32x4 ph[4], pm[4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) X2_SPLIT4(x[i], ph[i >> 1], pm[i >> 1], 2 * (i & 1));
-    u32x4 *o = (u32x4 *)p;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { o[i] = ph[i]; o[4 + i] = pm[i]; }
-}
-
-void launch_x2_make_hidden(const X3Args &a, hipStream_t st)
-{
-    const long n = (long)a.B * a.T * a.U1 * (a.H / 8);
-    hipLaunchKernelGGL(k_x2_make_hidden, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
-}
-void launch_x2_split_g(const X3Args &a, hipStream_t st)
-{
-    const long rows = (long)a.B * a.T * a.U1;
-    const long n = rows * (a.V / 32);
-    hipLaunchKernelGGL(k_x2_split_g, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, rows);
-}
-// zero rows past the last cell, both planes (the dW ring walks up to 96 of them; the "dead row" source of dHidden tiles).
-// `what` 1: hidden (before the forward), 2: G (after the forward, whose last tile writes logits there)
-void launch_x2_zero_padding(const X3Args &a, int what, hipStream_t st)
-{
-    const long cells = (long)a.B * a.T * a.U1;
-    const size_t pad = (size_t)(a.rows_alloc - cells);
-    if (what & 1)
-        for (int p = 0; p < 2; ++p) launch_fill32(a.hidden + p * a.plane_stride + cells * a.H, 0u, pad * a.H * 2, st);
-    if (what & 2) launch_fill32(a.logits + cells * a.V, 0u, pad * a.V * 4, st);
-}
+// The plain producers and the W packs are split_common.hpp's, at the f16x2 format
+void launch_x2_make_hidden(const X3Args &a, hipStream_t st) { launch_split_make_hidden<F16x2>(a, st); }
+void launch_x2_split_g(const X3Args &a, hipStream_t st) { launch_split_g<F16x2>(a, st); }
+void launch_x2_zero_padding(const X3Args &a, int what, hipStream_t st) { launch_split_zero_padding<F16x2>(a, what, st); }
+size_t x2_wpack_fwd_bytes(int H, int V) { return split_wpack_fwd_bytes<F16x2>(H, V); }
+size_t x2_wpack_dh_bytes(int H, int V) { return split_wpack_dh_bytes<F16x2>(H, V); }
 
 // ---------------------------------------------------------------------------------------
 // The flush rule and the live structures of the backward.
@@ -511,12 +379,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t x2_piece_rsrc(const char *base
 {
     return __builtin_amdgcn_make_buffer_rsrc((void *)(base + (unsigned long long)(unsigned)ent * gbytes - imm), 0, (int)gbytes + imm, 0x00020000);
 }
-struct X2Frag { u32x2 lo[4], hi[4]; };  // 4 tiles: cells 0-3 / 4-7 of a lane's 8
-#define X2_LANDED(f, N)                                                                                          \
-    asm volatile("s_waitcnt lgkmcnt(" #N ")"                                                                     \
-                 : "+v"(f.lo[0]), "+v"(f.lo[1]), "+v"(f.lo[2]), "+v"(f.lo[3]), "+v"(f.hi[0]), "+v"(f.hi[1]),     \
-                   "+v"(f.hi[2]), "+v"(f.hi[3])                                                                  \
-                 :: "memory")
 
 // ---------------------------------------------------------------------------------------
 // The dW k-step pipeline: the pieces k_dw_x2<4>, k_dw_x2<4, true> and both tile kinds of k_dw_x2m are built from, each once.  A kernel keeps
@@ -545,9 +407,9 @@ __device__ inline int x2_dw_frag_addr(int lds0, int otile, int m, int sec, int l
     return lds0 + otile * XW2_TILE + 256 * row + 16 * (ch ^ swz) + 8 * (pp & 1);
 }
 // 2 NT transposed reads of plane P, ring stage ST (compile-time: every LDS offset is an immediate) of an operand (inline asm: hipcc guards
-// every LDS read it can see behind an LDS-DMA with vmcnt(0)); results are used only after X2_LANDED named them
+// every LDS read it can see behind an LDS-DMA with vmcnt(0)); results are used only after FRAG8_LANDED named them
 template <int ST, int P, int NT>
-__device__ inline void x2_dw_reads(X2Frag &f, const int (&base)[4][2])
+__device__ inline void x2_dw_reads(Frag8 &f, const int (&base)[4][2])
 {
     constexpr int off = ST * XW2_STAGE + P * XW2_PLANE;
 #pragma unroll
@@ -557,9 +419,9 @@ __device__ inline void x2_dw_reads(X2Frag &f, const int (&base)[4][2])
     }
 }
 // 16 MFMAs of one product with the stage's DMA pieces N0 .. N0+CNT-1 (CNT <= 4) threaded through them, one per row of wave tiles: behind
-// row 0, 1 and 3, a fourth behind row 2.  dma_piece(X2Int<n>) issues piece n; live_n: this wave's h columns exist (wave-uniform)
+// row 0, 1 and 3, a fourth behind row 2.  dma_piece(Int<n>) issues piece n; live_n: this wave's h columns exist (wave-uniform)
 template <int N0, int CNT, class Piece>
-__device__ inline void x2_dw_product(f32x16 (&acc)[4][4], const X2Frag &fa_, const X2Frag &fb_, bool live_n, const Piece &dma_piece)
+__device__ inline void x2_dw_product(f32x16 (&acc)[4][4], const Frag8 &fa_, const Frag8 &fb_, bool live_n, const Piece &dma_piece)
 {
     u32x4 fa[4], fb[4];
 #pragma unroll
@@ -571,12 +433,12 @@ __device__ inline void x2_dw_product(f32x16 (&acc)[4][4], const X2Frag &fa_, con
     for (int qm = 0; qm < 4; ++qm) {
         if (live_n) {
 #pragma unroll
-            for (int qn = 0; qn < 4; ++qn) acc[qm][qn] = x2_mfma(fa[qm], fb[qn], acc[qm][qn]);
+            for (int qn = 0; qn < 4; ++qn) acc[qm][qn] = mfma_f16(fa[qm], fb[qn], acc[qm][qn]);
         }
-        if (qm == 0 && CNT >= 1) dma_piece(X2Int<N0>{});
-        if (qm == 1 && CNT >= 2) dma_piece(X2Int<N0 + (CNT >= 2 ? 1 : 0)>{});
-        if (qm == 2 && CNT >= 4) dma_piece(X2Int<N0 + (CNT >= 4 ? 2 : 0)>{});
-        if (qm == 3 && CNT >= 3) dma_piece(X2Int<N0 + (CNT >= 3 ? CNT - 1 : 0)>{});
+        if (qm == 0 && CNT >= 1) dma_piece(Int<N0>{});
+        if (qm == 1 && CNT >= 2) dma_piece(Int<N0 + (CNT >= 2 ? 1 : 0)>{});
+        if (qm == 2 && CNT >= 4) dma_piece(Int<N0 + (CNT >= 4 ? 2 : 0)>{});
+        if (qm == 3 && CNT >= 3) dma_piece(Int<N0 + (CNT >= 3 ? CNT - 1 : 0)>{});
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -607,19 +469,19 @@ template <int ST, int C0, int C1, int C2, class Piece>
 __device__ inline void x2_dw_kstep(f32x16 (&acc)[4][4], f32x16 &dacc, const int (&abase)[4][2], const int (&bbase)[4][2], const X2DwBias &b,
                                             bool live_n, const Piece &dma_piece)
 {
-    x2_lds_barrier();
-    X2Frag Ah, Bh, Am, Bm;
+    lds_barrier();
+    Frag8 Ah, Bh, Am, Bm;
     u32x2 dl[2], dh[2];
     x2_dw_reads<ST, 0, 4>(Ah, abase);
     x2_dw_reads<ST, 0, 4>(Bh, bbase);
     x2_dw_reads<ST, 1, 4>(Am, abase);
-    X2_LANDED(Ah, 8);
-    X2_LANDED(Bh, 8);
+    FRAG8_LANDED(Ah, 8);
+    FRAG8_LANDED(Bh, 8);
     x2_dw_product<0, C0>(acc, Ah, Bh, live_n, dma_piece);
     x2_dw_reads<ST, 1, 4>(Bm, bbase);
-    X2_LANDED(Am, 8);
+    FRAG8_LANDED(Am, 8);
     x2_dw_product<C0, C1>(acc, Am, Bh, live_n, dma_piece);
-    X2_LANDED(Bm, 0);
+    FRAG8_LANDED(Bm, 0);
     if (b.do_b) { x2_dw_bias_read<ST, 0>(dl[0], dh[0], b.sbase[0]); x2_dw_bias_read<ST, 1>(dl[1], dh[1], b.sbase[0]); }
     x2_dw_product<C0 + C1, C2>(acc, Ah, Bm, live_n, dma_piece);
     if (b.do_b) {
@@ -672,7 +534,7 @@ __device__ inline void x2_dw_lockstep(X2DwLockstep &s, int mine, int tile, int t
     }
 }
 // The ring driver: ONE pipeline run over a split's nks k-steps.  dma_stage(ks, st) issues this wave's DMA pieces of k-step ks into ring
-// stage st (prologue: NST - 1 stages ahead); kstep(X2Int<ST>, ks) is k-step ks on ring stage ST = ks % NST — its counted wait for the
+// stage st (prologue: NST - 1 stages ahead); kstep(Int<ST>, ks) is k-step ks on ring stage ST = ks % NST — its counted wait for the
 // stage (the kernels': two stages in flight behind the one waited for), x2_dw_kstep, and inside it the pieces of k-step ks + NST - 1.
 // The loop is unrolled by NST with a look at the lockstep in front of stage 0.
 template <class KStep, class DmaStage>
@@ -688,16 +550,16 @@ __device__ inline void x2_dw_ring(int nks, X2DwLockstep &ls, int tile, int tid, 
         for (int ks = 0;;) {
             if (ks >= nks) break;
             x2_dw_lockstep(ls, ks, tile, tid);
-            kstep(X2Int<0>{}, ks); ++ks;
+            kstep(Int<0>{}, ks); ++ks;
             if (ks >= nks) break;
-            kstep(X2Int<1>{}, ks); ++ks;
+            kstep(Int<1>{}, ks); ++ks;
             if (ks >= nks) break;
-            kstep(X2Int<2>{}, ks); ++ks;
+            kstep(Int<2>{}, ks); ++ks;
             if (ks >= nks) break;
-            kstep(X2Int<3>{}, ks); ++ks;
+            kstep(Int<3>{}, ks); ++ks;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the over-issued DMAs before the ring
-        x2_lds_barrier();                                  // is refilled / the kernel exits
+        lds_barrier();                                  // is refilled / the kernel exits
     }
 }
 // Epilogue: partial slab [split][V,H]; bias partial [split][V].  Wave tile at (v0, h0); accumulator register r of tile (qm,qn):
@@ -763,7 +625,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
     // (the 64-bit divisions run on the vector ALU: the quotients, at most nlive, are handed back to scalar registers)
     const int g_lo = __builtin_amdgcn_readfirstlane((int)(nlive * split / a.n_split));
     const int g_hi = __builtin_amdgcn_readfirstlane((int)(nlive * (split + 1) / a.n_split));
-    X2_CLOCK_STAMP(128 + 104);
+    X_CLOCK_STAMP(128 + 104);
 
     f32x16 acc[4][QN];
 #pragma unroll
@@ -875,7 +737,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
         x2_dw_ring(g_hi - g_lo, ls, tile, tid, kstep, dma_stage);
     }
 
-    X2_CLOCK_STAMP(128 + 106);
+    X_CLOCK_STAMP(128 + 106);
     x2_dw_store<true>(a, split, vb * 256 + wm * 128, hb * 256 + wn * 32 * QN, lane, acc, dacc, bias.do_b, bias.two_b, bsel0);
 }
 
@@ -1044,8 +906,8 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
         }
         x2_dw_store<false>(a, split, v0, h0, lane, acc, dacc, bias.do_b, false, bsel0);  // (V % 512 == 0, H % 128 == 0: every row and column exists)
     };
-    if (tile >= n_full) body(X2Int<1>{});  // (workgroup-uniform)
-    else body(X2Int<0>{});
+    if (tile >= n_full) body(Int<1>{});  // (workgroup-uniform)
+    else body(Int<0>{});
 }
 
 // the dW kernel launch_dw_x2 picks for this call walks the 16-cell k-step list (k_dw_x2m), not the group list: k_x2_dead_rows walks it too
@@ -1055,54 +917,16 @@ void launch_dw_x2(const X3Args &a, hipStream_t st, bool zero_prog)
 {
     if (a.dw_prog && zero_prog) launch_fill32(a.dw_prog, 0u, (size_t)a.n_split * 64, st);
     const int tiles = x2_dw_tiles(a.H, a.V);
-    static bool attr_set[16] = {false};  // > 64 KiB of dynamic LDS: opt-in once per device (read-mostly fact)
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;
-    if (dev < 0 || !attr_set[dev]) {
-        (void)hipFuncSetAttribute((const void *)k_dw_x2<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * XW2_TILE);
-        (void)hipFuncSetAttribute((const void *)k_dw_x2<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * XW2_TILE);
-        (void)hipFuncSetAttribute((const void *)k_dw_x2m, hipFuncAttributeMaxDynamicSharedMemorySize, 5 * XW2_TILE);
-        if (dev >= 0) attr_set[dev] = true;
-    }
+    static LdsOptIn lds_opt_in;
+    lds_opt_in.raise(4 * XW2_TILE, k_dw_x2<4>, k_dw_x2<4, true>);
+    static LdsOptIn lds_opt_in_m;
+    lds_opt_in_m.raise(5 * XW2_TILE, k_dw_x2m);
     // H % 256 == 128: whole-block tiles + tall tiles over the odd block (k_dw_x2m) where the shape allows; else the half-empty last h block
     if (x2_dw_mixed_ok(a.H, a.V)) hipLaunchKernelGGL(k_dw_x2m, dim3(tiles * a.n_split), dim3(256), 5 * XW2_TILE, st, a);
     else if (a.H % 256 != 0) hipLaunchKernelGGL((k_dw_x2<4, true>), dim3(((a.V + 255) / 256) * ((a.H + 255) / 256) * a.n_split), dim3(256), 4 * XW2_TILE, st, a);
     else hipLaunchKernelGGL(k_dw_x2<4>, dim3(tiles * a.n_split), dim3(256), 4 * XW2_TILE, st, a);
 }
 
-#define XG2_WAIT8(b) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]), "+v"(b[6]), "+v"(b[7]) :: "memory")
-#define XG2_WAIT8_BUT(b, N) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]), "+v"(b[6]), "+v"(b[7]) :: "memory")
-
-// ---------------------------------------------------------------------------------------
-// W (scaled by s_W) for the dHidden product, fragment order, two planes:
-//   [hp (512-column pass)][c (16-deep k-step = 16 vocabulary rows)][plane][tile(16)][lane] x 8 fp16,
-//   element j = piece_plane(s_W W[v = 16c + 8*(lane>>5) + j][h = 512hp + 128*(tile>>2) + 4*(lane&31) + (tile&3)])
-// (columns interleaved by 4: a lane's 4 tiles of a 128-column group are 4 adjacent columns -> 16-byte epilogue accesses).
-// One k-step = 2 x 16 KiB, staged by one linear LDS-DMA copy.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_x2_pack_w_dh(const float *__restrict__ W, const float *__restrict__ scales, u32x4 *__restrict__ out, int H, int V, long n)
-{
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;  // (hp, c, tile, lane): one thread writes both planes
-    if (idx >= n) return;
-    const int lane = (int)(idx & 63), tile = (int)(idx >> 6) & 15;
-    const int VC = V / 16;
-    const int c = (int)((idx >> 10) % VC), hp = (int)((idx >> 10) / VC);
-    const int h = 512 * hp + 128 * (tile >> 2) + 4 * (lane & 31) + (tile & 3);
-    const int v0 = 16 * c + 8 * (lane >> 5);
-    const float sw = scales[0];
-    u32x4 ph = {0u, 0u, 0u, 0u}, pm = ph;
-    if (h < H) {
-        const float *w = W + (long)v0 * H + h;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const X2Pieces q = x2_split2(x2_clamp(w[(long)(2 * j) * H] * sw), x2_clamp(w[(long)(2 * j + 1) * H] * sw));
-            ph[j] = q.h; pm[j] = q.m;
-        }
-    }
-    u32x4 *o = out + ((long)hp * VC + c) * 2048 + tile * 64 + lane;
-    o[0] = ph; o[1024] = pm;
-}
-size_t x2_wpack_dh_bytes(int H, int V) { return (size_t)((H + 511) / 512) * (V / 16) * 2 * 16 * 64 * 16; }
 
 // ---------------------------------------------------------------------------------------
 // k_dhidden_x2: k_dhidden_x3 on two planes.  G from the fp32 logits (exp2 + the two occupancy corrections, as the fp32 route),
@@ -1155,7 +979,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
     const int t0 = tt * XG2_BT, u0 = ub * XG2_BU;
     const int VC = V / 16;
     const int ngrp = PART ? (H - 512 * hp) / 128 : 4;  // live 128-column groups of this pass (H % 128 == 0)
-    if (FIRST) X2_CLOCK_STAMP(128 + 108);  // (one tile of ~0.1 ms: 1e-4 resolution at the 100 MHz reference)
+    if (FIRST) X_CLOCK_STAMP(128 + 108);  // (one tile of ~0.1 ms: 1e-4 resolution at the 100 MHz reference)
 
     // ---- producer role: M tile `wave`, row i = cell (pt, pu)
     const int prow = wave * 32 + i;
@@ -1258,10 +1082,10 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
             }
         } else if (sl == 6) {
             const f32x4 s4 = P.g0 * gs;  // (|G| <= grad_scale: no clamp needed; exact: a power of two)
-            X2_SPLIT4(s4, P.ph, P.pm, 0);
+            F16x2::split4(s4, P.ph, P.pm, 0);
         } else if (sl == 7) {
             const f32x4 s4 = P.g1 * gs;
-            X2_SPLIT4(s4, P.ph, P.pm, 2);
+            F16x2::split4(s4, P.ph, P.pm, 2);
         }
         if (sl == 8) {
             const int dst = xw + (c & 1) * XG2_XSLOT;
@@ -1309,7 +1133,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
             // k-steps, both loaded and consumed (production) before the store is issued.
             if (FIRST) asm volatile(RNNT_VMCNT(16) ::: "memory");
             else asm volatile(RNNT_VMCNT(12) ::: "memory");
-            x2_lds_barrier();
+            lds_barrier();
             const int ws = wb + wsl * XG2_WSLOT, xs = xa + (j & 1) * XG2_XSLOT;
             const int wsn = wsl == 0 ? 2 : wsl - 1;  // (c + 2) % 3
             u32x4 af[2][2], bf[8], bn[8];
@@ -1347,8 +1171,8 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     if (!PART || 2 * wn + (q >> 2) < ngrp) {  // (wave-uniform)
-                        acc[0][q] = x2_mfma(af[0][PA], bcur[q], acc[0][q]);
-                        acc[1][q] = x2_mfma(af[1][PA], bcur[q], acc[1][q]);
+                        acc[0][q] = mfma_f16(af[0][PA], bcur[q], acc[0][q]);
+                        acc[1][q] = mfma_f16(af[1][PA], bcur[q], acc[1][q]);
                     }
                     if (BLK == 0) {
                         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bn[q]) : "v"(ws), "n"(16384 + q * 1024));
@@ -1357,8 +1181,8 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
                     if (BLK == 1) {
                         if (q == 0 && prod_on) produce_slice(P, rawn, c + 1, 8);
                         if (q >= 1) wdma(c + 2, wsn, q - 1);
-                        if (FIRST && q == 2 && !(j & 1) && prod_on) { line_read(ln[0], X2Int<0>{}); line_read(ln[1], X2Int<1>{}); }
-                        if (FIRST && q == 4 && !(j & 1) && prod_on) { line_read(ln[2], X2Int<2>{}); line_read(ln[3], X2Int<3>{}); }
+                        if (FIRST && q == 2 && !(j & 1) && prod_on) { line_read(ln[0], Int<0>{}); line_read(ln[1], Int<1>{}); }
+                        if (FIRST && q == 4 && !(j & 1) && prod_on) { line_read(ln[2], Int<2>{}); line_read(ln[3], Int<3>{}); }
                     }
                     if (BLK == 2) {
                         if (q == 0) wdma(c + 2, wsn, 7);
@@ -1372,10 +1196,10 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
-            block(X2Int<0>{}, bf, X2Int<0>{});   // ah.bh
-            block(X2Int<1>{}, bf, X2Int<1>{});   // am.bh
-            XG2_WAIT8(bn);
-            block(X2Int<0>{}, bn, X2Int<2>{});   // ah.bm
+            block(Int<0>{}, bf, Int<0>{});   // ah.bh
+            block(Int<1>{}, bf, Int<1>{});   // am.bh
+            LDS_WAIT8(bn);
+            block(Int<0>{}, bn, Int<2>{});   // ah.bm
             wsl = wsl == 2 ? 0 : wsl + 1;
         }
     }
@@ -1478,7 +1302,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
             }
         }
     }
-    if (FIRST) X2_CLOCK_STAMP(128 + 110);
+    if (FIRST) X_CLOCK_STAMP(128 + 110);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1564,7 +1388,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2r(X3Args a, const int hp)
             const int c = c0 + j;
             // this wave's pieces of W(c) landed: issued at the end of k-step c-2; younger: k-step c-1's 8 A loads and 2 DMAs
             asm volatile(RNNT_VMCNT(10) ::: "memory");
-            x2_lds_barrier();  // publishes W(c); every wave is past its reads of W(c-1): slot (c + 3) & 3 ... (c + 2) & 3 are free
+            lds_barrier();  // publishes W(c); every wave is past its reads of W(c-1): slot (c + 3) & 3 ... (c + 2) & 3 are free
             const int ws = wb + wsl * XR2_WSLOT;
             u32x4 bh[4], bm[4];
 #pragma unroll
@@ -1578,7 +1402,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2r(X3Args a, const int hp)
             for (int m = 0; m < 4; ++m) {
 #pragma unroll
                 for (int n = 0; n < 4; ++n) {
-                    acc[m][n] = x2_mfma(ac.h[m], bh[n], acc[m][n]);
+                    acc[m][n] = mfma_f16(ac.h[m], bh[n], acc[m][n]);
                     if (m == 0) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bm[n]) : "v"(ws), "n"(4096 + n * 1024));
                     if (n == 1) an.h[m] = arow[m][o];
                     if (n == 3) an.m[m] = arow[m][o + 4];
@@ -1590,7 +1414,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2r(X3Args a, const int hp)
             for (int m = 0; m < 4; ++m)
 #pragma unroll
                 for (int n = 0; n < 4; ++n) {
-                    acc[m][n] = x2_mfma(ac.m[m], bh[n], acc[m][n]);
+                    acc[m][n] = mfma_f16(ac.m[m], bh[n], acc[m][n]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bm[0]), "+v"(bm[1]), "+v"(bm[2]), "+v"(bm[3]) :: "memory");
@@ -1599,7 +1423,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2r(X3Args a, const int hp)
             for (int m = 0; m < 4; ++m)
 #pragma unroll
                 for (int n = 0; n < 4; ++n) {
-                    acc[m][n] = x2_mfma(ac.h[m], bm[n], acc[m][n]);
+                    acc[m][n] = mfma_f16(ac.h[m], bm[n], acc[m][n]);
                     if (m == 3 && n == 0) wdma(c + 2, (wsl + 2) & 3);
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -1725,17 +1549,9 @@ bool x2_dhidden_ok(int U1, int H, int V)
 
 void launch_dhidden_x2(const X3Args &a, hipStream_t st)
 {
-    static bool attr_set[16] = {false};
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;
     const int lds = XG2_NW * XG2_WSLOT + 2 * XG2_XSLOT;
-    if (dev < 0 || !attr_set[dev]) {
-        (void)hipFuncSetAttribute((const void *)k_dhidden_x2<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        (void)hipFuncSetAttribute((const void *)k_dhidden_x2<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        (void)hipFuncSetAttribute((const void *)k_dhidden_x2<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        (void)hipFuncSetAttribute((const void *)k_dhidden_x2<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (dev >= 0) attr_set[dev] = true;
-    }
+    static LdsOptIn lds_opt_in;
+    lds_opt_in.raise(lds, k_dhidden_x2<true, false>, k_dhidden_x2<false, false>, k_dhidden_x2<true, true>, k_dhidden_x2<false, true>);
     // one workgroup per tile; those past the live-tile list's length (known on the device only) return at once
     dim3 grid((unsigned)((long)a.n_ublk16 * ((a.T + XG2_BT - 1) / XG2_BT) * a.B));
     if (a.H < 512) hipLaunchKernelGGL((k_dhidden_x2<true, true>), grid, dim3(256), lds, st, a, 0);
@@ -1797,36 +1613,6 @@ void launch_x2_make_ep(const X3Args &a, hipStream_t st)
     hipLaunchKernelGGL(k_x2_make_ep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
 }
 size_t x2_ep_bytes(int B, int T, int U1, int H) { return ((size_t)B * T + (size_t)B * U1) * H * 4; }
-
-// ---------------------------------------------------------------------------------------
-// W (scaled by s_W) for the forward product, fragment order, two planes:
-//   [pass (512 logits columns)][c (16-deep k-step)][plane][tile(16)][lane] x 8 fp16,
-//   element j = piece_plane(s_W W[v = 512pass + 128*(tile>>2) + 4*(lane&31) + (tile&3)][h = 16c + 8*(lane>>5) + j])
-// (columns interleaved by 4, as in the dHidden pack: a lane's 4 tiles of a 128-column group are 4 adjacent logits).
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_x2_pack_w_fwd(const float *__restrict__ W, const float *__restrict__ scales, u32x4 *__restrict__ out, int H, int V, long n)
-{
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;  // (pass, c, tile, lane): one thread writes both planes
-    if (idx >= n) return;
-    const int lane = (int)(idx & 63), tile = (int)(idx >> 6) & 15;
-    const int KC = H / 16;
-    const int c = (int)((idx >> 10) % KC), pass = (int)((idx >> 10) / KC);
-    const int v = 512 * pass + 128 * (tile >> 2) + 4 * (lane & 31) + (tile & 3);
-    const int h0 = 16 * c + 8 * (lane >> 5);
-    const float sw = scales[0];
-    u32x4 ph = {0u, 0u, 0u, 0u}, pm = ph;
-    if (v < V) {
-        const float *w = W + (long)v * H + h0;
-        f32x4 w0 = *(const f32x4 *)w, w1 = *(const f32x4 *)(w + 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { w0[k] = x2_clamp(w0[k] * sw); w1[k] = x2_clamp(w1[k] * sw); }
-        X2_SPLIT4(w0, ph, pm, 0);
-        X2_SPLIT4(w1, ph, pm, 2);
-    }
-    u32x4 *o = out + ((long)pass * KC + c) * 2048 + tile * 64 + lane;
-    o[0] = ph; o[1024] = pm;
-}
-size_t x2_wpack_fwd_bytes(int H, int V) { return (size_t)((V + 511) / 512) * (H / 16) * 2 * 16 * 64 * 16; }
 
 // ---------------------------------------------------------------------------------------
 // k_joint_fwd_x2: k_joint_fwd_x3 on two planes.  hidden = 2^14 tanh(enc + pred) split into its two fp16 planes (produced per
@@ -1899,7 +1685,7 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(a.wpack_fwd, 0, npass * KC * XF2_WSLOT, 0x00020000);
     const int wvo = lane * 16;
 
-    X2_CLOCK_STAMP(128 + 100);
+    X_CLOCK_STAMP(128 + 100);
     if (tid == 0) s_next[0] = (int)atomicAdd(a.counter, 1u);
     __syncthreads();
     int tile = s_next[0];
@@ -1964,7 +1750,7 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
                 const f32x4 &e = j < 2 ? o.e0 : o.e1, &pv = j < 2 ? o.p0 : o.p1;
                 const int q = 2 * (j & 1);
                 if (LIN) {  // s_X x, clamped into fp16's range (non-finite / garbage operands only)
-                    if (!(k & 1)) P.w[j] = f2{x2_clamp(e[q] * sx), x2_clamp(e[q + 1] * sx)};
+                    if (!(k & 1)) P.w[j] = f2{F16x2::clamp(e[q] * sx), F16x2::clamp(e[q + 1] * sx)};
                 } else if (EP) {  // 2^14 (1 - 2 / (1 + E P)): E P overflows to inf / underflows to 0 exactly where tanh is +-1
                     if (!(k & 1)) {
                         P.w[j] = f2{__builtin_amdgcn_rcpf(fmaf(e[q], pv[q], 1.0f)), __builtin_amdgcn_rcpf(fmaf(e[q + 1], pv[q + 1], 1.0f))};
@@ -1983,12 +1769,12 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
             } else if (k < 16) {
                 const int j = (k - 8) >> 1;
                 if (!(k & 1)) {
-                    const unsigned hh = x2_pack(P.w[j][0], P.w[j][1]);
+                    const unsigned hh = pack_f16_pair(P.w[j][0], P.w[j][1]);
                     P.ph[j] = hh;
                     asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(P.ra) : "v"(hh), "v"(P.w[j][0]));
                     asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(P.rb) : "v"(hh), "v"(P.w[j][1]));
                 } else {
-                    P.pm[j] = x2_pack(P.ra, P.rb);
+                    P.pm[j] = pack_f16_pair(P.ra, P.rb);
                 }
             } else {
                 const int dst = xw;  // (a local: asm operands cannot name a capture of the enclosing generic lambda)
@@ -2013,7 +1799,7 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
                 Opd o; Prod P;
                 op_load(o, kc);
 #pragma unroll
-                for (int pc = 0; pc < 16; ++pc) prod_piece(P, o, X2Int<0>{}, pc);
+                for (int pc = 0; pc < 16; ++pc) prod_piece(P, o, Int<0>{}, pc);
                 hid_store(P, kc);
             }
             tile = next;
@@ -2067,11 +1853,11 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
             op_load(oset[1], KC > 1 ? 1 : 0);
             op_load(o, 0);
 #pragma unroll
-            for (int pc = 0; pc < 17; ++pc) prod_piece(P, o, X2Int<0>{}, pc);
+            for (int pc = 0; pc < 17; ++pc) prod_piece(P, o, Int<0>{}, pc);
             if (!LIN) hid_store(P, 0);  // (the plain GEMM stores nothing beside Y: X3Args::hidden is null there)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // W of k-steps 0-2 (this wave's share), operands, the stores
-            x2_lds_barrier();                                 // ... of every wave; A slot 0 written
-            frag_read(fr[0], X2Int<0>{}, 0);
+            lds_barrier();                                 // ... of every wave; A slot 0 written
+            frag_read(fr[0], Int<0>{}, 0);
             frag_landed(fr[0]);
         }
 
@@ -2110,20 +1896,20 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
                 constexpr int PA = decltype(pa_c)::value, BLK = decltype(blk_c)::value;
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
-                    acc[0][q] = x2_mfma(fc.af[0][PA], bcur[q], acc[0][q]);
-                    acc[1][q] = x2_mfma(fc.af[1][PA], bcur[q], acc[1][q]);
+                    acc[0][q] = mfma_f16(fc.af[0][PA], bcur[q], acc[0][q]);
+                    acc[1][q] = mfma_f16(fc.af[1][PA], bcur[q], acc[1][q]);
                     if (BLK == 0) {
                         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bn[q]) : "v"(ws), "n"(16384 + q * 1024));
-                        prod_piece(P, ocur, X2Int<XN>{}, q);
+                        prod_piece(P, ocur, Int<XN>{}, q);
                     }
                     if (BLK == 1) {
                         if (q < (LIN ? 2 : 4)) op_load1(onext, kcnn, q);  // operands of k-step cs+2 (needed a whole k-step from now): in FRONT of the k-step's DMAs
-                        if (q < 4) { prod_piece(P, ocur, X2Int<XN>{}, 8 + 2 * q); prod_piece(P, ocur, X2Int<XN>{}, 9 + 2 * q); }
-                        if (q == 4) prod_piece(P, ocur, X2Int<XN>{}, 16);  // the ring writes: done well before the barrier's lgkmcnt(0)
+                        if (q < 4) { prod_piece(P, ocur, Int<XN>{}, 8 + 2 * q); prod_piece(P, ocur, Int<XN>{}, 9 + 2 * q); }
+                        if (q == 4) prod_piece(P, ocur, Int<XN>{}, 16);  // the ring writes: done well before the barrier's lgkmcnt(0)
                     }
                     if (BLK == 2) {  // nothing of the k-step is issued outside an MFMA's shadow: the 12 fragment reads of k-step cs+1, the 8 DMAs, the 2 stores
-                        if (q < 4) { frag_read1(fn, X2Int<XN>{}, wsn, 2 * q); frag_read1(fn, X2Int<XN>{}, wsn, 2 * q + 1); }
-                        else frag_read1(fn, X2Int<XN>{}, wsn, 4 + q);
+                        if (q < 4) { frag_read1(fn, Int<XN>{}, wsn, 2 * q); frag_read1(fn, Int<XN>{}, wsn, 2 * q + 1); }
+                        else frag_read1(fn, Int<XN>{}, wsn, 4 + q);
                         wdma(csn, wsl, q);
                         if (STORE && q == 6) hdst[2 * kcn] = P.ph;
                         if (STORE && q == 7) hdst[2 * kcn + ps] = P.pm;
@@ -2131,9 +1917,9 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
-            block(X2Int<0>{}, fc.bf, X2Int<0>{});   // ah.bh
+            block(Int<0>{}, fc.bf, Int<0>{});   // ah.bh
             X2STAMP(1);
-            block(X2Int<1>{}, fc.bf, X2Int<1>{});   // am.bh
+            block(Int<1>{}, fc.bf, Int<1>{});   // am.bh
             X2STAMP(2);
             // this wave's share of W(cs+1) landed: its DMAs were issued in block 2 of k-step cs-2.  vmcnt retires in order; behind
             // them came (first pass) 2 hidden stores, k-step cs-1's 4 operand loads, 8 DMAs and (first pass) 2 stores, and this
@@ -2147,17 +1933,17 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
                 else asm volatile(RNNT_VMCNT(20) ::: "memory");
             }
             X2STAMP(3);
-            x2_lds_barrier();  // (lgkmcnt(0): bn and the ring writes) publishes A(cs+1), W(cs+1); frees W(cs)'s slot
+            lds_barrier();  // (lgkmcnt(0): bn and the ring writes) publishes A(cs+1), W(cs+1); frees W(cs)'s slot
             X2STAMP(4);
             asm volatile("" : "+v"(bn[0]), "+v"(bn[1]), "+v"(bn[2]), "+v"(bn[3]), "+v"(bn[4]), "+v"(bn[5]), "+v"(bn[6]), "+v"(bn[7]));
-            block(X2Int<0>{}, bn, X2Int<2>{});   // ah.bm  (the hidden stores: the youngest memory operations of the k-step; the pass's last k-step re-stores k-step 0)
+            block(Int<0>{}, bn, Int<2>{});   // ah.bm  (the hidden stores: the youngest memory operations of the k-step; the pass's last k-step re-stores k-step 0)
             frag_landed(fn);
             X2STAMP(5);
             (void)kcn;
             ++cs;
             wsl = wsn;
           };
-          for (int kc0 = 0; kc0 < KC; kc0 += 2) { kstep(X2Int<0>{}, kc0); kstep(X2Int<1>{}, kc0 + 1); }
+          for (int kc0 = 0; kc0 < KC; kc0 += 2) { kstep(Int<0>{}, kc0); kstep(Int<1>{}, kc0 + 1); }
           // pass complete: unscale, add the bias, store the logits, update the statistics.  V % 128 == 0: a lane's two 4-column
           // groups exist or not for the whole wave.  The row loop is ONE basic block per case; the store address is a scalar
           // row pointer + one 32-bit per-lane offset.
@@ -2274,13 +2060,13 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
                     s_run = fmaf(s_o, __builtin_amdgcn_exp2f((m_o - mn) * RNNT_LOG2E), S_ * __builtin_amdgcn_exp2f((M - mn) * RNNT_LOG2E));
                 }
             };
-            if (cw + 128 < V) epilogue(X2Int<1>{});
-            else if (cw < V) epilogue(X2Int<0>{});
+            if (cw + 128 < V) epilogue(Int<1>{});
+            else if (cw < V) epilogue(Int<0>{});
           }
         };
-        run_pass(X2Int<(LIN ? 0 : 1)>{}, pass0);
+        run_pass(Int<(LIN ? 0 : 1)>{}, pass0);
         if (!LIN)
-            for (int pass = 1; pass < npass; ++pass) run_pass(X2Int<0>{}, pass);
+            for (int pass = 1; pass < npass; ++pass) run_pass(Int<0>{}, pass);
 
         // ---- log-softmax denominators: the two column halves (wn) of every row.  s_part[wn][row] = the row's (max, sum exp) over
         // that half's columns of every pass: all 256 entries are written, a half without columns (V = 128) leaves (-inf, 0)
@@ -2331,23 +2117,14 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x2(X3Args a, const int nti
         }
         tile = next;
     }
-    X2_CLOCK_STAMP(128 + 102);
+    X_CLOCK_STAMP(128 + 102);
 }
-
-bool x2_fwd_ok(int U1, int H, int V) { return H % 128 == 0 && V % 128 == 0 && (long)128 * H * 2 < 0x7fffffffL; }
 
 void launch_joint_fwd_x2(const X3Args &a, hipStream_t st, bool lin /* the plain-GEMM form, k_joint_fwd_x2<2>: the joint's input projections */)
 {
-    static bool attr_set[16] = {false};
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;
     const int lds = XF2_NW * XF2_WSLOT + 2 * XF2_ASLOT + 128 * 4 + 2 * 128 * 2 * 4 + 16;
-    if (dev < 0 || !attr_set[dev]) {
-        (void)hipFuncSetAttribute((const void *)k_joint_fwd_x2<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        (void)hipFuncSetAttribute((const void *)k_joint_fwd_x2<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        (void)hipFuncSetAttribute((const void *)k_joint_fwd_x2<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (dev >= 0) attr_set[dev] = true;
-    }
+    static LdsOptIn lds_opt_in;
+    lds_opt_in.raise(lds, k_joint_fwd_x2<1>, k_joint_fwd_x2<0>, k_joint_fwd_x2<2>);
     const long cells = (long)a.B * a.T * a.U1;
     const int ntiles = (int)((cells + 127) / 128) * (lin ? (a.V + 511) / 512 : 1);  // (plain GEMM: a tile = one column pass of a row block)
     if (!lin) launch_fill32(a.counter, 0u, 4, st);  // tile counter of the persistent workgroups (plain GEMM: zeroed with its scales, k_x2_lin_scales)
@@ -2361,10 +2138,7 @@ void launch_joint_fwd_x2(const X3Args &a, hipStream_t st, bool lin /* the plain-
 void launch_x2_pack_w(const X3Args &a, float *scales, hipStream_t st)
 {
     hipLaunchKernelGGL(k_x2_wscale, dim3(1), dim3(1024), 0, st, a.W, (long)a.V * a.H / 4, scales);
-    const long nd = (long)((a.H + 511) / 512) * (a.V / 16) * 16 * 64;
-    hipLaunchKernelGGL(k_x2_pack_w_dh, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, a.W, (const float *)scales, (u32x4 *)a.wpack_dh, a.H, a.V, nd);
-    const long nf = (long)((a.V + 511) / 512) * (a.H / 16) * 16 * 64;
-    hipLaunchKernelGGL(k_x2_pack_w_fwd, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, a.W, (const float *)scales, (u32x4 *)a.wpack_fwd, a.H, a.V, nf);
+    launch_split_pack_w<F16x2>(a, scales, st);
 }
 
 
@@ -2472,8 +2246,8 @@ __global__ __launch_bounds__(256) void k_x2_split_rows(const float *__restrict__
         for (int i = 0; i < 8; ++i) {
             f32x4 v = r < rows ? p[i] : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = x2_clamp(v[k] * s);
-            X2_SPLIT4(v, ph[i >> 1], pm[i >> 1], 2 * (i & 1));
+            for (int k = 0; k < 4; ++k) v[k] = F16x2::clamp(v[k] * s);
+            F16x2::split4(v, ph[i >> 1], pm[i >> 1], 2 * (i & 1));
         }
         u32x4 *o = (u32x4 *)((float *)dst + r * cols + 32 * c);
 #pragma unroll
@@ -2487,10 +2261,10 @@ __global__ __launch_bounds__(256) void k_x2_split_rows(const float *__restrict__
         f32x4 t0 = *(const f32x4 *)xr, t1 = *(const f32x4 *)(xr + 4);
         if (r >= rows) t0 = t1 = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { t0[k] = x2_clamp(t0[k] * s); t1[k] = x2_clamp(t1[k] * s); }
+        for (int k = 0; k < 4; ++k) { t0[k] = F16x2::clamp(t0[k] * s); t1[k] = F16x2::clamp(t1[k] * s); }
         u32x4 ph, pm;
-        X2_SPLIT4(t0, ph, pm, 0);
-        X2_SPLIT4(t1, ph, pm, 2);
+        F16x2::split4(t0, ph, pm, 0);
+        F16x2::split4(t1, ph, pm, 2);
         u32x4 *o = (u32x4 *)((unsigned short *)dst + r * cols + h);
         o[0] = ph; o[plane_stride / 8] = pm;
     }
@@ -2564,7 +2338,7 @@ void lin_gemm_nt(const float *x, long ldx, const float *wmat, const float *bias,
                  unsigned *counter, hipStream_t st)
 {
     const long nf = (long)((N + 511) / 512) * (K / 16) * 16 * 64;
-    hipLaunchKernelGGL(k_x2_pack_w_fwd, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, wmat, scales, (u32x4 *)pack, K, N, nf);
+    hipLaunchKernelGGL(k_split_pack_w_fwd<F16x2>, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, wmat, scales, (u32x4 *)pack, K, N, nf);
     X3Args a{};
     a.enc = x; a.enc_sb = ldx; a.enc_st = 0; a.pred = nullptr; a.W = wmat; a.bias = bias;
     a.B = M; a.T = 1; a.U1 = 1; a.H = K; a.V = N; a.logits = y; a.wpack_fwd = pack; a.scales = scales;
@@ -2574,7 +2348,7 @@ void lin_gemm_nt(const float *x, long ldx, const float *wmat, const float *bias,
 }  // namespace
 
 size_t x2_linear_ws_bytes(int M, int K, int N, bool bwd) { return lin_layout(M, K, N, bwd).total; }
-bool x2_linear_ok(int M, int K, int N) { return M > 0 && K % 128 == 0 && N % 128 == 0 && x2_fwd_ok(1, K, N) && x2_fwd_ok(1, N, K); }
+bool x2_linear_ok(int M, int K, int N) { return M > 0 && K % 128 == 0 && N % 128 == 0 && split_fwd_ok(1, K, N) && split_fwd_ok(1, N, K); }
 
 void launch_linear_x2_fwd(const float *x, long ldx, const float *W, const float *bias, int M, int K, int N, float *y, void *ws, hipStream_t st)
 {

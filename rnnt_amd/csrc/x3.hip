@@ -23,145 +23,15 @@
 // and B[k = 8h+j][col r], j = 0..7; C/D: col = l&31, row = (reg&3) + 8*(reg>>2) + 4*(l>>5).
 // Every kernel here is 4 waves (one per SIMD) with 256 accumulator registers per wave, hand-pipelined
 // around long MFMA streams (96 MFMAs = 3072 matrix-pipe cycles per 16-deep k-step), like the fp32 route's.
-#include "kernels.hpp"
+#include "split_common.hpp"
 
-// Diagnostic build only (-DRNNT_STAMPS): workgroup 0 stamps the core clock counter and the 100 MHz reference at its start and
-// end into debug[SLOT..] (a buffer nothing else reads): the clock this launch ran at (tools/exp_x3_clock.py).
-#ifdef RNNT_STAMPS
-#define X3_CLOCK_STAMP(SLOT)                                                                                               \
-    do {                                                                                                                   \
-        if (a.debug && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) {                        \
-            unsigned long long t_, r_;                                                                                     \
-            asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_), "=s"(r_)::"memory");      \
-            a.debug[SLOT] = t_; a.debug[(SLOT) + 1] = r_;                                                                  \
-        }                                                                                                                  \
-    } while (0)
-#else
-#define X3_CLOCK_STAMP(SLOT) do {} while (0)
-#endif
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-typedef __attribute__((address_space(3))) void *lds_vptr;
-
-__device__ __forceinline__ unsigned x3_pack(float lo, float hi)
-{
-    bf16x2 v = {(__bf16)lo, (__bf16)hi};  // v_cvt_pk_bf16_f32: RNE
-    return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float x3_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float x3_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-// two fp32 values -> their (hi, mid, lo) bf16 pieces, packed pairwise (element 0 in the low half)
-struct X3Pieces { unsigned h, m, l; };
-__device__ __forceinline__ X3Pieces x3_split2(float a, float b)
-{
-    X3Pieces p;
-    p.h = x3_pack(a, b);
-    const float ra = a - x3_lo(p.h), rb = b - x3_hi(p.h);  // exact: the residual has <= 16 significant bits
-    p.m = x3_pack(ra, rb);
-    p.l = x3_pack(ra - x3_lo(p.m), rb - x3_hi(p.m));
-    return p;
-}
-// four consecutive fp32 values -> (2 packed dwords per plane) at dword positions d, d+1 of the plane vectors
-#define X3_SPLIT4(x4, ph, pm, pl, d)                                  \
-    do {                                                              \
-        const X3Pieces p0_ = x3_split2((x4)[0], (x4)[1]);             \
-        const X3Pieces p1_ = x3_split2((x4)[2], (x4)[3]);             \
-        (ph)[d] = p0_.h; (pm)[d] = p0_.m; (pl)[d] = p0_.l;            \
-        (ph)[(d) + 1] = p1_.h; (pm)[(d) + 1] = p1_.m; (pl)[(d) + 1] = p1_.l; \
-    } while (0)
-__device__ __forceinline__ f32x16 x3_mfma(u32x4 a, u32x4 b, f32x16 c)
-{
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void x3_lds_barrier()
-{
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-// ---------------------------------------------------------------------------------------
-// Plain producers.  k_x3_make_hidden / k_x3_split_g are the one-thread-per-piece forms of what the
-// forward prologue and k_dhidden_x3 do in their tiles: they serve the unfused variants
-// (RNNT_VARIANT_X3_*), which exist so that every fused kernel can be checked against the same
-// pipeline with one stage swapped, and as the plain statement of the data layout.
-// ---------------------------------------------------------------------------------------
-// hidden planes of every cell (also dead ones: the backward multiplies them by exact zeros, they only
-// have to be finite).  One thread = 8 columns of one row.
-__global__ __launch_bounds__(256) void k_x3_make_hidden(X3Args a)
-{
-    const int H8 = a.H / 8;
-    const long cells = (long)a.B * a.T * a.U1;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= cells * H8) return;
-    const long c = idx / H8;
-    const int h = (int)(idx - c * H8) * 8;
-    const int u = (int)(c % a.U1);
-    const long bt = c / a.U1;
-    const int t = (int)(bt % a.T), b = (int)(bt / a.T);
-    const float *ep = a.enc + (long)b * a.enc_sb + (long)t * a.enc_st + h;
-    const float *pp = a.pred + ((long)b * a.U1 + u) * a.H + h;
-    const f32x4 t0 = fast_tanh_sum4(*(const f32x4 *)ep, *(const f32x4 *)pp);
-    const f32x4 t1 = fast_tanh_sum4(*(const f32x4 *)(ep + 4), *(const f32x4 *)(pp + 4));
-    u32x4 ph, pm, pl;
-    X3_SPLIT4(t0, ph, pm, pl, 0);
-    X3_SPLIT4(t1, ph, pm, pl, 2);
-    u32x4 *o = (u32x4 *)(a.hidden + c * a.H + h);
-    const long ps = a.plane_stride / 8;  // u32x4 units
-    o[0] = ph; o[ps] = pm; o[2 * ps] = pl;
-}
-
-// fp32 G (what the fp32 route's k_dhidden_gen / k_make_g leave in place of the logits) -> the three
-// planes: hi | mid over the same 128 bytes of every 32-wide chunk, lo beside.  One thread = one chunk
-// of one row (it reads the whole 128 bytes before it overwrites them).
-__global__ __launch_bounds__(256) void k_x3_split_g(X3Args a, long rows)
-{
-    const int VC = a.V / 32;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= rows * VC) return;
-    const long r = idx / VC;
-    const int c = (int)(idx - r * VC);
-    f32x4 *p = (f32x4 *)(a.logits + r * a.V + 32 * c);
-    f32x4 x[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) x[i] = p[i];
-    u32x4 ph[4], pm[4], pl[4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) X3_SPLIT4(x[i], ph[i >> 1], pm[i >> 1], pl[i >> 1], 2 * (i & 1));
-    u32x4 *o = (u32x4 *)p;
-    u32x4 *ol = (u32x4 *)(a.g_lo + r * a.V + 32 * c);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { o[i] = ph[i]; o[4 + i] = pm[i]; ol[i] = pl[i]; }
-}
-
-void launch_x3_make_hidden(const X3Args &a, hipStream_t st)
-{
-    const long n = (long)a.B * a.T * a.U1 * (a.H / 8);
-    hipLaunchKernelGGL(k_x3_make_hidden, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
-}
-void launch_x3_split_g(const X3Args &a, hipStream_t st)
-{
-    const long rows = (long)a.B * a.T * a.U1;
-    const long n = rows * (a.V / 32);
-    hipLaunchKernelGGL(k_x3_split_g, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, rows);
-}
-// zero rows past the last cell, all planes (the dW ring walks up to 96 of them; the "dead row" source of dHidden
-// tiles).  `what` 1: hidden (before the forward), 2: G (after the forward, whose last tile writes logits there)
-void launch_x3_zero_padding(const X3Args &a, int what, hipStream_t st)
-{
-    const long cells = (long)a.B * a.T * a.U1;
-    const size_t pad = (size_t)(a.rows_alloc - cells);
-    if (what & 1)
-        for (int p = 0; p < 3; ++p) launch_fill32(a.hidden + p * a.plane_stride + cells * a.H, 0u, pad * a.H * 2, st);
-    if (what & 2) {
-        launch_fill32(a.logits + cells * a.V, 0u, pad * a.V * 4, st);
-        launch_fill32(a.g_lo + cells * a.V, 0u, pad * a.V * 2, st);
-    }
-}
+// The plain producers and the W packs are split_common.hpp's, at the bf16x3 format (no scales: the pointer is null and unread)
+void launch_x3_make_hidden(const X3Args &a, hipStream_t st) { launch_split_make_hidden<Bf16x3>(a, st); }
+void launch_x3_split_g(const X3Args &a, hipStream_t st) { launch_split_g<Bf16x3>(a, st); }
+void launch_x3_zero_padding(const X3Args &a, int what, hipStream_t st) { launch_split_zero_padding<Bf16x3>(a, what, st); }
+void launch_x3_pack_w(const X3Args &a, hipStream_t st) { launch_split_pack_w<Bf16x3>(a, nullptr, st); }
+size_t x3_wpack_fwd_bytes(int H, int V) { return split_wpack_fwd_bytes<Bf16x3>(H, V); }
+size_t x3_wpack_dh_bytes(int H, int V) { return split_wpack_dh_bytes<Bf16x3>(H, V); }
 
 // ---------------------------------------------------------------------------------------
 // k_dw_x3: dW[v,h] = sum_c G[c,v] hidden[c,h] (split-K slabs), db[v] = sum_c G[c,v].
@@ -188,13 +58,6 @@ void launch_x3_zero_padding(const X3Args &a, int what, hipStream_t st)
 #define XW_TILE (XW_NST * XW_STAGE)  // ring of one operand tile: [stage][plane][16 x 256 B] = 36 KiB
 #define XW_GRAN 32  // granule of the live-row table (shared with the bf16 route: 2 k-steps)
 
-struct X3Frag { u32x2 lo[4], hi[4]; };  // 4 tiles: cells 0-3 / 4-7 of a lane's 8
-#define X3_LANDED(f, N)                                                                                          \
-    asm volatile("s_waitcnt lgkmcnt(" #N ")"                                                                     \
-                 : "+v"(f.lo[0]), "+v"(f.lo[1]), "+v"(f.lo[2]), "+v"(f.lo[3]), "+v"(f.hi[0]), "+v"(f.hi[1]),     \
-                   "+v"(f.hi[2]), "+v"(f.hi[3])                                                                  \
-                 :: "memory")
-template <int N> struct X3Int { static constexpr int value = N; };
 
 __global__ __launch_bounds__(256, 1) void k_dw_x3(X3Args a)
 {
@@ -222,7 +85,7 @@ __global__ __launch_bounds__(256, 1) void k_dw_x3(X3Args a)
     const int B = a.B;
     const long nlive = tab[2 * B + 1];
     const long g_lo = nlive * split / a.n_split, g_hi = nlive * (split + 1) / a.n_split;
-    X3_CLOCK_STAMP(128 + 104);
+    X_CLOCK_STAMP(128 + 104);
 
     f32x16 acc[4][4];
 #pragma unroll
@@ -320,8 +183,8 @@ __global__ __launch_bounds__(256, 1) void k_dw_x3(X3Args a)
                                                          16, soff[p][i], 0, 0, 0);
             };
             // 8 transposed reads of plane P of the A / B operand (inline asm: hipcc guards every LDS read it can
-            // see behind an LDS-DMA with vmcnt(0)); results are used only after X3_LANDED named them
-            auto reads = [&](X3Frag &f, const int (&base)[4][2], auto p_c) {
+            // see behind an LDS-DMA with vmcnt(0)); results are used only after FRAG8_LANDED named them
+            auto reads = [&](Frag8 &f, const int (&base)[4][2], auto p_c) {
                 constexpr int off = ST * XW_STAGE + decltype(p_c)::value * XW_PLANE;
                 if (RNNT_XP(a.ablate, 4096)) return;
 #pragma unroll
@@ -331,7 +194,7 @@ __global__ __launch_bounds__(256, 1) void k_dw_x3(X3Args a)
                 }
             };
             // 16 MFMAs of one product with DMA pieces N0, N0+1 threaded through them
-            auto product = [&](const X3Frag &fa_, const X3Frag &fb_, auto n0_c) {
+            auto product = [&](const Frag8 &fa_, const Frag8 &fb_, auto n0_c) {
                 constexpr int N0 = decltype(n0_c)::value;
                 u32x4 fa[4], fb[4];
 #pragma unroll
@@ -343,10 +206,10 @@ __global__ __launch_bounds__(256, 1) void k_dw_x3(X3Args a)
                 for (int qm = 0; qm < 4; ++qm) {
                     if (!RNNT_XP(a.ablate, 1024)) {
 #pragma unroll
-                        for (int qn = 0; qn < 4; ++qn) acc[qm][qn] = x3_mfma(fa[qm], fb[qn], acc[qm][qn]);
+                        for (int qn = 0; qn < 4; ++qn) acc[qm][qn] = mfma_bf16(fa[qm], fb[qn], acc[qm][qn]);
                     }
-                    if (qm == 1) dma_piece(X3Int<N0>{});
-                    if (qm == 3) dma_piece(X3Int<N0 + 1>{});
+                    if (qm == 1) dma_piece(Int<N0>{});
+                    if (qm == 3) dma_piece(Int<N0 + 1>{});
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
@@ -370,32 +233,32 @@ __global__ __launch_bounds__(256, 1) void k_dw_x3(X3Args a)
             // stage ks landed (the 12 younger pieces of ks+1 may still fly); every wave is past its
             // reads of stage ks-1, whose ring stage the DMAs below refill
             asm volatile(RNNT_VMCNT(12) ::: "memory");
-            x3_lds_barrier();
-            X3Frag Ah, Bh, Am, Bm, Al, Bl;  // at most four of the six sets are live at a time (+ one landing)
+            lds_barrier();
+            Frag8 Ah, Bh, Am, Bm, Al, Bl;  // at most four of the six sets are live at a time (+ one landing)
             u32x2 dl[3], dh[3];
-            reads(Ah, abase, X3Int<0>{});
-            reads(Bh, bbase, X3Int<0>{});
-            reads(Am, abase, X3Int<1>{});
-            X3_LANDED(Ah, 8);
-            X3_LANDED(Bh, 8);
-            product(Ah, Bh, X3Int<0>{});
-            reads(Bm, bbase, X3Int<1>{});
-            X3_LANDED(Am, 8);
-            product(Am, Bh, X3Int<2>{});
-            X3_LANDED(Bm, 0);
-            product(Am, Bm, X3Int<4>{});
-            reads(Al, abase, X3Int<2>{});
-            if (do_b) { bias_read(dl[0], dh[0], X3Int<0>{}, 0); bias_read(dl[1], dh[1], X3Int<1>{}, 0); bias_read(dl[2], dh[2], X3Int<2>{}, 0); }
-            product(Ah, Bm, X3Int<6>{});
-            reads(Bl, bbase, X3Int<2>{});
-            X3_LANDED(Al, 8);
-            product(Al, Bh, X3Int<8>{});
-            X3_LANDED(Bl, 0);
-            product(Ah, Bl, X3Int<10>{});
+            reads(Ah, abase, Int<0>{});
+            reads(Bh, bbase, Int<0>{});
+            reads(Am, abase, Int<1>{});
+            FRAG8_LANDED(Ah, 8);
+            FRAG8_LANDED(Bh, 8);
+            product(Ah, Bh, Int<0>{});
+            reads(Bm, bbase, Int<1>{});
+            FRAG8_LANDED(Am, 8);
+            product(Am, Bh, Int<2>{});
+            FRAG8_LANDED(Bm, 0);
+            product(Am, Bm, Int<4>{});
+            reads(Al, abase, Int<2>{});
+            if (do_b) { bias_read(dl[0], dh[0], Int<0>{}, 0); bias_read(dl[1], dh[1], Int<1>{}, 0); bias_read(dl[2], dh[2], Int<2>{}, 0); }
+            product(Ah, Bm, Int<6>{});
+            reads(Bl, bbase, Int<2>{});
+            FRAG8_LANDED(Al, 8);
+            product(Al, Bh, Int<8>{});
+            FRAG8_LANDED(Bl, 0);
+            product(Ah, Bl, Int<10>{});
             if (do_b && !RNNT_XP(a.ablate, 2048)) {
                 bias_mfma(dl[0], dh[0], dacc, 0); bias_mfma(dl[1], dh[1], dacc, 0); bias_mfma(dl[2], dh[2], dacc, 0);
                 if (n_hblk < 2) {  // one h block: the wave's second tile (column 1 of the selector product), H <= 256 only
-                    bias_read(dl[0], dh[0], X3Int<0>{}, 1); bias_read(dl[1], dh[1], X3Int<1>{}, 1); bias_read(dl[2], dh[2], X3Int<2>{}, 1);
+                    bias_read(dl[0], dh[0], Int<0>{}, 1); bias_read(dl[1], dh[1], Int<1>{}, 1); bias_read(dl[2], dh[2], Int<2>{}, 1);
                     bias_mfma(dl[0], dh[0], dacc, 1); bias_mfma(dl[1], dh[1], dacc, 1); bias_mfma(dl[2], dh[2], dacc, 1);
                 }
             }
@@ -424,18 +287,18 @@ __global__ __launch_bounds__(256, 1) void k_dw_x3(X3Args a)
             dma_stage(1, 1);
             for (long ks = 0;;) {  // the ring stage of a k-step is ks % 3: unrolled by 3
                 if (ks >= nks) break;
-                kstep(X3Int<0>{}, ks, dacc); ++ks;
+                kstep(Int<0>{}, ks, dacc); ++ks;
                 if (ks >= nks) break;
-                kstep(X3Int<1>{}, ks, dacc); ++ks;
+                kstep(Int<1>{}, ks, dacc); ++ks;
                 if (ks >= nks) break;
-                kstep(X3Int<2>{}, ks, dacc); ++ks;
+                kstep(Int<2>{}, ks, dacc); ++ks;
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the over-issued DMAs before the ring
-            x3_lds_barrier();                                  // is refilled / the kernel exits
+            lds_barrier();                                  // is refilled / the kernel exits
         }
     }
 
-    X3_CLOCK_STAMP(128 + 106);
+    X_CLOCK_STAMP(128 + 106);
     // ---- epilogue: partial slab [split][V,H]; bias partial [split][V].  Accumulator register r of tile
     // (qm,qn): v = v0 + 32qm + (r&3) + 8(r>>2) + 4half, h = h0 + 32qn + (lane&31).
     const int v0 = vb * 256 + wm * 128, h0 = hb * 256 + wn * 128;
@@ -467,45 +330,11 @@ void launch_dw_x3(const X3Args &a, hipStream_t st)
 {
     launch_dw_table(a.logit_lens, a.B, a.T, a.U1, XW_GRAN, a.dw_tab, st);
     const int tiles = ((a.V + 255) / 256) * ((a.H + 255) / 256);
-    static bool attr_set[16] = {false};  // > 64 KiB of dynamic LDS: opt-in once per device (read-mostly fact)
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;
-    if (dev < 0 || !attr_set[dev]) {
-        (void)hipFuncSetAttribute((const void *)k_dw_x3, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * XW_TILE);
-        if (dev >= 0) attr_set[dev] = true;
-    }
+    static LdsOptIn lds_opt_in;
+    lds_opt_in.raise(4 * XW_TILE, k_dw_x3);
     hipLaunchKernelGGL(k_dw_x3, dim3(tiles * a.n_split), dim3(256), 4 * XW_TILE, st, a);
 }
 
-
-#define XG_WAIT8_BUT(b, N) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]), "+v"(b[6]), "+v"(b[7]) :: "memory")
-#define XG_WAIT8(b) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]), "+v"(b[6]), "+v"(b[7]) :: "memory")
-// ---------------------------------------------------------------------------------------
-// W for the forward product, fragment order, three planes:
-//   [pass (512 logits columns)][c (16-deep k-step)][plane][tile(16)][lane] x 8 bf16,
-//   element j = piece_plane(W[v = 512pass + 128*(tile>>2) + 4*(lane&31) + (tile&3)][h = 16c + 8*(lane>>5) + j])
-// (columns interleaved by 4, as in the dHidden pack: a lane's 4 tiles of a 128-column group are 4 adjacent logits).
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_x3_pack_w_fwd(const float *__restrict__ W, u32x4 *__restrict__ out, int H, int V, long n)
-{
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;  // (pass, c, tile, lane): one thread writes the 3 planes
-    if (idx >= n) return;
-    const int lane = (int)(idx & 63), tile = (int)(idx >> 6) & 15;
-    const int KC = H / 16;
-    const int c = (int)((idx >> 10) % KC), pass = (int)((idx >> 10) / KC);
-    const int v = 512 * pass + 128 * (tile >> 2) + 4 * (lane & 31) + (tile & 3);
-    const int h0 = 16 * c + 8 * (lane >> 5);
-    u32x4 ph = {0u, 0u, 0u, 0u}, pm = ph, pl = ph;
-    if (v < V) {
-        const float *w = W + (long)v * H + h0;
-        const f32x4 w0 = *(const f32x4 *)w, w1 = *(const f32x4 *)(w + 4);
-        X3_SPLIT4(w0, ph, pm, pl, 0);
-        X3_SPLIT4(w1, ph, pm, pl, 2);
-    }
-    u32x4 *o = out + ((long)pass * KC + c) * 3072 + tile * 64 + lane;
-    o[0] = ph; o[1024] = pm; o[2048] = pl;
-}
-size_t x3_wpack_fwd_bytes(int H, int V) { return (size_t)((V + 511) / 512) * (H / 16) * 3 * 16 * 64 * 16; }
 
 // ---------------------------------------------------------------------------------------
 // k_joint_fwd_x3: hidden = tanh(enc + pred) split into its planes (tile prologue), logits = hidden . W^T + bias
@@ -646,13 +475,13 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x3(X3Args a, const int nti
             } else if (k < 16) {
                 const int j = (k - 8) >> 1;
                 if (!(k & 1)) {
-                    const unsigned hh = x3_pack(P.w[j][0], P.w[j][1]);
+                    const unsigned hh = pack_bf16(P.w[j][0], P.w[j][1]);
                     P.ph[j] = hh;
-                    P.ra = P.w[j][0] - x3_lo(hh); P.rb = P.w[j][1] - x3_hi(hh);
+                    P.ra = P.w[j][0] - bf16_lo(hh); P.rb = P.w[j][1] - bf16_hi(hh);
                 } else {
-                    const unsigned mm = x3_pack(P.ra, P.rb);
+                    const unsigned mm = pack_bf16(P.ra, P.rb);
                     P.pm[j] = mm;
-                    P.pl[j] = x3_pack(P.ra - x3_lo(mm), P.rb - x3_hi(mm));
+                    P.pl[j] = pack_bf16(P.ra - bf16_lo(mm), P.rb - bf16_hi(mm));
                 }
             } else {
                 const int dst = xw + slot * XF_ASLOT;
@@ -730,7 +559,7 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x3(X3Args a, const int nti
             else if (STORE) asm volatile(RNNT_VMCNT(3) ::: "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             XSTAMP(1);
-            x3_lds_barrier();  // publishes W slot and A slot of k-step cs; every wave is past its reads of cs-1
+            lds_barrier();  // publishes W slot and A slot of k-step cs; every wave is past its reads of cs-1
             XSTAMP(2);
             const int ws = wb + (cs & 1) * XF_WSLOT, xs = xa + (cs & 1) * XF_ASLOT;
             // the next k-step (past the end: its own, never read) and the one after (operand loads)
@@ -754,8 +583,8 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x3(X3Args a, const int nti
                 constexpr int PA = decltype(pa_c)::value, NB = decltype(nb_c)::value, D0 = decltype(d0_c)::value, PB = decltype(pb_c)::value;
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
-                    acc[0][q] = x3_mfma(af[0][PA], bcur[q], acc[0][q]);
-                    acc[1][q] = x3_mfma(af[1][PA], bcur[q], acc[1][q]);
+                    acc[0][q] = mfma_bf16(af[0][PA], bcur[q], acc[0][q]);
+                    acc[1][q] = mfma_bf16(af[1][PA], bcur[q], acc[1][q]);
                     if (NB >= 0) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bnext[q]) : "v"(ws), "n"((NB < 0 ? 0 : NB) * 16384 + q * 1024));
                     // D0: the tag of the block's W DMA pieces of k-step cs+1 (8: pieces 0-5, -2: pieces 6-11, else none); PB: production pieces PB+q of A's k-step cs+1
                     // six DMA pieces each in blocks 1 and 2, none beside block 0's eight fragment reads
@@ -768,18 +597,18 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x3(X3Args a, const int nti
             };
             // every fragment read is issued at least a block (16 MFMAs) before the wait that covers it
             XSTAMP(3);
-            block(X3Int<0>{}, bf, bn, X3Int<1>{}, X3Int<-1>{}, X3Int<-1>{});   // ah.bh + reads of W mid
-            block(X3Int<1>{}, bf, bn, X3Int<-1>{}, X3Int<8>{}, X3Int<-1>{});   // am.bh + DMA 0-5
+            block(Int<0>{}, bf, bn, Int<1>{}, Int<-1>{}, Int<-1>{});   // ah.bh + reads of W mid
+            block(Int<1>{}, bf, bn, Int<-1>{}, Int<8>{}, Int<-1>{});   // am.bh + DMA 0-5
             XSTAMP(4);
             op_load(onext, kcnn);  // operands of k-step cs+2: behind the DMAs (they are needed a whole k-step from now)
-            block(X3Int<2>{}, bf, bf, X3Int<-1>{}, X3Int<-2>{}, X3Int<0>{});   // al.bh + DMA 6-11 (D0 = -2: the tag of this block) + A(cs+1): tanh pieces
-            XG_WAIT8(bn);
-            block(X3Int<0>{}, bn, bf, X3Int<2>{}, X3Int<-1>{}, X3Int<8>{});    // ah.bm + reads of W lo (into the hi registers), A(cs+1): split pieces
+            block(Int<2>{}, bf, bf, Int<-1>{}, Int<-2>{}, Int<0>{});   // al.bh + DMA 6-11 (D0 = -2: the tag of this block) + A(cs+1): tanh pieces
+            LDS_WAIT8(bn);
+            block(Int<0>{}, bn, bf, Int<2>{}, Int<-1>{}, Int<8>{});    // ah.bm + reads of W lo (into the hi registers), A(cs+1): split pieces
             XSTAMP(5);
-            block(X3Int<1>{}, bn, bn, X3Int<-1>{}, X3Int<-1>{}, X3Int<16>{});  // am.bm + A(cs+1): ring writes
+            block(Int<1>{}, bn, bn, Int<-1>{}, Int<-1>{}, Int<16>{});  // am.bm + A(cs+1): ring writes
             if (STORE) hid_store(P, kcn);  // (the youngest memory operations of the k-step; the pass's last k-step re-stores k-step 0)
-            XG_WAIT8_BUT(bf, 3);           // the three ring writes above may still fly
-            block(X3Int<0>{}, bf, bf, X3Int<-1>{}, X3Int<-1>{}, X3Int<-1>{});  // ah.bl
+            LDS_WAIT8_BUT(bf, 3);           // the three ring writes above may still fly
+            block(Int<0>{}, bf, bf, Int<-1>{}, Int<-1>{}, Int<-1>{});  // ah.bl
             XSTAMP(6);
             (void)kcn;
           }
@@ -833,13 +662,13 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x3(X3Args a, const int nti
                         if ((r & 7) == 7) XESTAMP(32 * pass + 2 + 2 * mt + (r >> 3));
                     }
             };
-            if (cw + 128 < V) epilogue(X3Int<1>{});
-            else if (cw < V) epilogue(X3Int<0>{});
+            if (cw + 128 < V) epilogue(Int<1>{});
+            else if (cw < V) epilogue(Int<0>{});
           }
           XESTAMP(32 * pass + 6);
         };
-        run_pass(X3Int<1>{}, 0);
-        for (int pass = 1; pass < npass; ++pass) run_pass(X3Int<0>{}, pass);
+        run_pass(Int<1>{}, 0);
+        for (int pass = 1; pass < npass; ++pass) run_pass(Int<0>{}, pass);
 
         XESTAMP(96);
         // ---- log-softmax denominators: the two column halves (wn) of every row
@@ -895,18 +724,11 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x3(X3Args a, const int nti
 #endif
 }
 
-bool x3_fwd_ok(int U1, int H, int V) { return H % 128 == 0 && V % 128 == 0 && (long)128 * H * 2 < 0x7fffffffL; }
-
 void launch_joint_fwd_x3(const X3Args &a, hipStream_t st)
 {
-    static bool attr_set[16] = {false};
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;
     const int lds = 2 * XF_WSLOT + 2 * XF_ASLOT + 128 * 4 + 2 * 128 * 2 * 4 + 16;
-    if (dev < 0 || !attr_set[dev]) {
-        (void)hipFuncSetAttribute((const void *)k_joint_fwd_x3, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (dev >= 0) attr_set[dev] = true;
-    }
+    static LdsOptIn lds_opt_in;
+    lds_opt_in.raise(lds, k_joint_fwd_x3);
     const long cells = (long)a.B * a.T * a.U1;
     const int ntiles = (int)((cells + 127) / 128);
     launch_fill32(a.counter, 0u, 4, st);  // tile counter of the persistent workgroups
@@ -914,36 +736,6 @@ void launch_joint_fwd_x3(const X3Args &a, hipStream_t st)
     hipLaunchKernelGGL(k_joint_fwd_x3, dim3((unsigned)nwg), dim3(256), lds, st, a, ntiles);
 }
 
-
-// ---------------------------------------------------------------------------------------
-// W for the dHidden product, fragment order, three planes:
-//   [hp (512-column pass)][c (16-deep k-step = 16 vocabulary rows)][plane][tile(16)][lane] x 8 bf16,
-//   element j = piece_plane(W[v = 16c + 8*(lane>>5) + j][h = 512hp + 128*(tile>>2) + 4*(lane&31) + (tile&3)])
-// (columns interleaved by 4: a lane's 4 tiles of a 128-column group are 4 adjacent columns -> 16-byte
-// epilogue accesses).  One k-step = 3 x 16 KiB, staged by one linear LDS-DMA copy.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_x3_pack_w_dh(const float *__restrict__ W, u32x4 *__restrict__ out, int H, int V, long n)
-{
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;  // (hp, c, tile, lane): one thread writes the 3 planes
-    if (idx >= n) return;
-    const int lane = (int)(idx & 63), tile = (int)(idx >> 6) & 15;
-    const int VC = V / 16;
-    const int c = (int)((idx >> 10) % VC), hp = (int)((idx >> 10) / VC);
-    const int h = 512 * hp + 128 * (tile >> 2) + 4 * (lane & 31) + (tile & 3);
-    const int v0 = 16 * c + 8 * (lane >> 5);
-    u32x4 ph = {0u, 0u, 0u, 0u}, pm = ph, pl = ph;
-    if (h < H) {
-        const float *w = W + (long)v0 * H + h;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const X3Pieces q = x3_split2(w[(long)(2 * j) * H], w[(long)(2 * j + 1) * H]);
-            ph[j] = q.h; pm[j] = q.m; pl[j] = q.l;
-        }
-    }
-    u32x4 *o = out + ((long)hp * VC + c) * 3072 + tile * 64 + lane;
-    o[0] = ph; o[1024] = pm; o[2048] = pl;
-}
-size_t x3_wpack_dh_bytes(int H, int V) { return (size_t)((H + 511) / 512) * (V / 16) * 3 * 16 * 64 * 16; }
 
 // ---------------------------------------------------------------------------------------
 // k_dhidden_x3: G from the fp32 logits (exp2 + the two occupancy corrections, as the fp32 route), split
@@ -996,7 +788,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
     len_tu_uniform(a.logit_lens, a.target_lens, b, a.T, a.U1, Tb, Ub);
     const int t0 = tt * XG_BT, u0 = ub * XG_BU;
     const int VC = V / 16;
-    if (FIRST) X3_CLOCK_STAMP(128 + 108);  // (one tile of ~0.1 ms: 1e-4 resolution at the 100 MHz reference)
+    if (FIRST) X_CLOCK_STAMP(128 + 108);  // (one tile of ~0.1 ms: 1e-4 resolution at the 100 MHz reference)
 
     // ---- producer role: M tile `wave`, row i = cell (pt, pu)
     const int prow = wave * 32 + i;
@@ -1129,9 +921,9 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
                 }
             }
         } else if (sl == 6) {
-            X3_SPLIT4(P.g0, P.ph, P.pm, P.pl, 0);
+            Bf16x3::split4(P.g0, P.ph, P.pm, P.pl, 0);
         } else if (sl == 7) {
-            X3_SPLIT4(P.g1, P.ph, P.pm, P.pl, 2);
+            Bf16x3::split4(P.g1, P.ph, P.pm, P.pl, 2);
         }
         if (sl == 8) {
             const int dst = xw + (c & 1) * XG_XSLOT;
@@ -1173,7 +965,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
             else if (FIRST) asm volatile(RNNT_VMCNT(2) ::: "memory");            // previous k-step odd: 2 raw loads
             else asm volatile(RNNT_VMCNT(3) ::: "memory");
             GXSTAMP(1);
-            x3_lds_barrier();
+            lds_barrier();
             GXSTAMP(2);
             const int ws = wb + (j & 1) * XG_WSLOT, xs = xa + (j & 1) * XG_XSLOT;
             u32x4 af[2][3], bf[8], bn[8];
@@ -1220,8 +1012,8 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
                 constexpr int MEM = decltype(mem_c)::value;
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
-                    acc[0][q] = x3_mfma(af[0][PA], bcur[q], acc[0][q]);
-                    acc[1][q] = x3_mfma(af[1][PA], bcur[q], acc[1][q]);
+                    acc[0][q] = mfma_bf16(af[0][PA], bcur[q], acc[0][q]);
+                    acc[1][q] = mfma_bf16(af[1][PA], bcur[q], acc[1][q]);
                     if (NB >= 0)
                         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bnext[q]) : "v"(ws), "n"((NB < 0 ? 0 : NB) * 16384 + q * 1024));
                     // the 12 W DMAs of k-step c+1 ride in blocks 1 and 2 (six each, one per MFMA pair), none beside block 0's eight
@@ -1232,9 +1024,9 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
                     if (S0 >= 0 && S0 + q < 9 && prod_on) produce_slice(P, rawn, c + 1, (S0 < 0 ? 0 : S0) + q);
                     if (FIRST) {
                         // even k-step c: G of k-steps c and c+1 is in the exchange -> the pair's lines (hi | mid) and lo half lines; every k-step: 2 raw loads
-                        if (MEM == 1 && q == 1 && !(j & 1) && prod_on) { line_read(ln[0], X3Int<0>{}); line_read(ln[1], X3Int<1>{}); }
-                        if (MEM == 1 && q == 3 && !(j & 1) && prod_on) { line_read(ln[2], X3Int<2>{}); line_read(ln[3], X3Int<3>{}); }
-                        if (MEM == 1 && q == 5 && !(j & 1) && prod_on) { lo_read(ll[0], X3Int<0>{}); lo_read(ll[1], X3Int<1>{}); }
+                        if (MEM == 1 && q == 1 && !(j & 1) && prod_on) { line_read(ln[0], Int<0>{}); line_read(ln[1], Int<1>{}); }
+                        if (MEM == 1 && q == 3 && !(j & 1) && prod_on) { line_read(ln[2], Int<2>{}); line_read(ln[3], Int<3>{}); }
+                        if (MEM == 1 && q == 5 && !(j & 1) && prod_on) { lo_read(ll[0], Int<0>{}); lo_read(ll[1], Int<1>{}); }
                         if (MEM == 3 && q == 2 && !(j & 1) && prod_on) lo_store(ll[0], 0, c);
                         if (MEM == 3 && q == 4 && !(j & 1) && prod_on) lo_store(ll[1], 1, c);
                         if (MEM == 2 && q == 1 && !(j & 1) && prod_on) line_store(ln[0], 0, c);
@@ -1252,19 +1044,19 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
             };
             // every fragment read is issued at least a block (16 MFMAs) before the wait that covers it
             GXSTAMP(3);
-            block(X3Int<0>{}, bf, bn, X3Int<1>{}, X3Int<-1>{}, X3Int<0>{}, X3Int<0>{});    // ah.bh + reads of W mid, G slices 0-7 (exp2, corrections, split)
-            block(X3Int<1>{}, bf, bn, X3Int<-1>{}, X3Int<4>{}, X3Int<8>{}, X3Int<0>{});    // am.bh + DMA 0-5, G slice 8 (exchange)
+            block(Int<0>{}, bf, bn, Int<1>{}, Int<-1>{}, Int<0>{}, Int<0>{});    // ah.bh + reads of W mid, G slices 0-7 (exp2, corrections, split)
+            block(Int<1>{}, bf, bn, Int<-1>{}, Int<4>{}, Int<8>{}, Int<0>{});    // am.bh + DMA 0-5, G slice 8 (exchange)
             GXSTAMP(4);
-            block(X3Int<2>{}, bf, bf, X3Int<-1>{}, X3Int<8>{}, X3Int<-1>{}, X3Int<0>{});   // al.bh + DMA 6-11
+            block(Int<2>{}, bf, bf, Int<-1>{}, Int<8>{}, Int<-1>{}, Int<0>{});   // al.bh + DMA 6-11
             // G's stores and the raw ring refill come AFTER the k-step's DMAs (vmcnt retires in order: the next k-step's
             // wait for the DMAs must not also wait out a store acknowledgement or an HBM load needed 4 k-steps from
             // now), one per half block: five back-to-back HBM operations fill the CU's memory queue and block the wave
-            XG_WAIT8(bn);
-            block(X3Int<0>{}, bn, bf, X3Int<2>{}, X3Int<-1>{}, X3Int<-1>{}, X3Int<1>{});   // ah.bm + reads of W lo (into the hi registers); G hi, mid stores
+            LDS_WAIT8(bn);
+            block(Int<0>{}, bn, bf, Int<2>{}, Int<-1>{}, Int<-1>{}, Int<1>{});   // ah.bm + reads of W lo (into the hi registers); G hi, mid stores
             GXSTAMP(5);
-            block(X3Int<1>{}, bn, bn, X3Int<-1>{}, X3Int<-1>{}, X3Int<-1>{}, X3Int<2>{});  // am.bm; G lo store, logits load
-            XG_WAIT8(bf);
-            block(X3Int<0>{}, bf, bf, X3Int<-1>{}, X3Int<-1>{}, X3Int<-1>{}, X3Int<3>{});  // ah.bl; logits load
+            block(Int<1>{}, bn, bn, Int<-1>{}, Int<-1>{}, Int<-1>{}, Int<2>{});  // am.bm; G lo store, logits load
+            LDS_WAIT8(bf);
+            block(Int<0>{}, bf, bf, Int<-1>{}, Int<-1>{}, Int<-1>{}, Int<3>{});  // ah.bl; logits load
             GXSTAMP(6);
         }
     }
@@ -1372,7 +1164,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
             }
         }
     }
-    if (FIRST) X3_CLOCK_STAMP(128 + 110);
+    if (FIRST) X_CLOCK_STAMP(128 + 110);
 }
 
 bool x3_dhidden_ok(int U1, int H, int V)
@@ -1381,25 +1173,11 @@ bool x3_dhidden_ok(int U1, int H, int V)
     return (long)((XG_BT - 1) * (long)U1 + XG_BU) * H * 2 < 0x7fffffffL && V % 128 == 0 && H % 128 == 0;
 }
 
-void launch_x3_pack_w(const X3Args &a, hipStream_t st)
-{
-    const long nd = (long)((a.H + 511) / 512) * (a.V / 16) * 16 * 64;
-    hipLaunchKernelGGL(k_x3_pack_w_dh, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, a.W, (u32x4 *)a.wpack_dh, a.H, a.V, nd);
-    const long nf = (long)((a.V + 511) / 512) * (a.H / 16) * 16 * 64;
-    hipLaunchKernelGGL(k_x3_pack_w_fwd, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, a.W, (u32x4 *)a.wpack_fwd, a.H, a.V, nf);
-}
-
 void launch_dhidden_x3(const X3Args &a, hipStream_t st)
 {
-    static bool attr_set[16] = {false};
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;
     const int lds = 2 * XG_WSLOT + 2 * XG_XSLOT;
-    if (dev < 0 || !attr_set[dev]) {
-        (void)hipFuncSetAttribute((const void *)k_dhidden_x3<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        (void)hipFuncSetAttribute((const void *)k_dhidden_x3<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (dev >= 0) attr_set[dev] = true;
-    }
+    static LdsOptIn lds_opt_in;
+    lds_opt_in.raise(lds, k_dhidden_x3<true>, k_dhidden_x3<false>);
     dim3 grid(a.n_ublk16, (a.T + XG_BT - 1) / XG_BT, a.B);
     hipLaunchKernelGGL(k_dhidden_x3<true>, grid, dim3(256), lds, st, a, 0);
     for (int hp = 1; hp * 512 < a.H; ++hp) hipLaunchKernelGGL(k_dhidden_x3<false>, grid, dim3(256), lds, st, a, hp);

@@ -150,7 +150,7 @@ def table_rows(d, gran):
 
 # ---- the bf16x3 route's exact arithmetic
 def split3(x):
-    """fp32 values -> their (hi, mid, lo) bf16 pieces as float64 (x3.hip x3_split2): hi = bf16(x), mid = bf16(x - hi), lo = bf16(x -
+    """fp32 values -> their (hi, mid, lo) bf16 pieces as float64 (split_common.hpp Bf16x3::split2): hi = bf16(x), mid = bf16(x - hi), lo = bf16(x -
     hi - mid), round-to-nearest-even each; both residuals are exact in fp32, so numpy gives the device's bits."""
     x = np.asarray(x, dtype=F32)
     hi = bf16_round(x)

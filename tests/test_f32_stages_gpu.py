@@ -2,7 +2,7 @@
 (lattice.hip) against fp64 on the operands the device itself produced upstream, through the comparators of tests/f32_stage_cases.py
 (proved on the CPU by tests/test_f32_stages_oracle.py).  Per case a forward mask (fp32: 7, whose logits k_make_g has not yet
 overwritten; bf16x3: 15), the forward-only entry, then the full pipeline; the bf16x3 cases run three ways — every stage on x3.hip, the
-forward on the fp32 route's kernel + k_x3_make_hidden, forward and dHidden on the fp32 route's kernels + k_x3_split_g.  Every
+forward on the fp32 route's kernel + k_split_make_hidden, forward and dHidden on the fp32 route's kernels + k_split_g.  Every
 comparison prints `f32-stage-parity: route[:variant] case stage worst error / bar` (profiles/fp32_stage_parity.txt,
 profiles/x3_stage_parity.txt)."""
 import numpy as np
@@ -198,7 +198,7 @@ def test_bf16x3_route_each_stage_against_fp64_on_the_devices_planes(amd, name, v
     coef, y = w.coef()
     planes, logits = _np64(hid_t), _np64(logits_t)
     report("hidden", check_hidden_x3(planes, d))
-    if fwd32:  # the fp32 route's forward on its own fp32 hidden (k_x3_make_hidden made the planes above)
+    if fwd32:  # the fp32 route's forward on its own fp32 hidden (k_split_make_hidden made the planes above)
         aux = _np64(aux_t)
         report("aux-hidden", check_hidden_f32(aux, d))
         rl, ry = check_logits_f32(logits, aux, d, yard=_np64(chain_mm(aux_t, g["W"].T, 2, first=g["bias"][None, :].expand(cells, V))))

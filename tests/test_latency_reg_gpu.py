@@ -145,7 +145,7 @@ def test_f16x2_large_lambda_on_a_forced_label_path():
 
 def test_f16x2_f32_dh_fallback_shape():
     """A tile's logits rows beyond the 2 GiB buffer range of k_dhidden_x2 (x2_dhidden_ok: U1 = 1024, V = 74 752): the
-    fp32 route's dHidden makes G and k_x2_split_g splits it, with the same (1 + lambda) bound.  Against the exact-fp32 route."""
+    fp32 route's dHidden makes G and k_split_g<F16x2> splits it, with the same (1 + lambda) bound.  Against the exact-fp32 route."""
     B, T, U, H, V = 1, 2, 1023, 128, 74752
     assert (7 * (U + 1) + 16) * V * 4 >= 2 ** 31
     d = make_inputs(B, T, U, H, V, seed=9, ragged=False)

@@ -30,8 +30,8 @@ def amd():
 @pytest.mark.parametrize("shape", [(2, 9, 4, 128, 128), (3, 23, 19, 256, 384), (2, 40, 33, 512, 1024), (2, 13, 20, 1024, 256),
                                    (3, 21, 9, 640, 128), (2, 130, 50, 512, 256)])
 def test_x2_kernels_in_isolation(amd, variant, shape):
-    """With RNNT_VARIANT_X3_FP32_FWD | _DH only k_dw_x2 runs (forward and dHidden on the fp32 route's kernels, k_x2_make_hidden
-    / k_x2_split_g in between), with _FWD alone k_dhidden_x2 + k_dw_x2, without a variant all three — each against the fp64
+    """With RNNT_VARIANT_X3_FP32_FWD | _DH only k_dw_x2 runs (forward and dHidden on the fp32 route's kernels, k_split_make_hidden
+    / k_split_g in between), with _FWD alone k_dhidden_x2 + k_dw_x2, without a variant all three — each against the fp64
     oracle at the fp32 tolerances."""
     e = amd.engine
     var = {"dw_only": e.VARIANT_X3_FP32_FWD | e.VARIANT_X3_FP32_DH, "dw_dhidden": e.VARIANT_X3_FP32_FWD, "all": 0}[variant]

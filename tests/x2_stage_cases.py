@@ -103,7 +103,7 @@ def rows_alloc(cells):
 
 # ---- the route's exact arithmetic
 def split16(x):
-    """fp32 (scaled) values -> their (hi, mid) fp16 pieces as float64 (x2.hip x2_clamp + x2_split2): hi = f16(x), mid = f16(x - hi),
+    """fp32 (scaled) values -> their (hi, mid) fp16 pieces as float64 (split_common.hpp F16x2::prepare + split2): hi = f16(x), mid = f16(x - hi),
     round-to-nearest-even each; the residual is exact in fp32 (v_fma_mix), so numpy's conversions give the device's bits."""
     x = np.clip(np.asarray(x, dtype=F32), F32(-F16_MAX), F32(F16_MAX))
     hi = x.astype(np.float16)
