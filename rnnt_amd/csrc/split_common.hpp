@@ -10,6 +10,8 @@
 //   split4(x4, planes.., d) four consecutive values -> 2 packed dwords per plane at dword positions d, d+1 of the plane vectors,
 //                           the planes as separate vectors or as one array u32x4[NP]
 //   mfma(a, b, c)           its 32x32x16 MFMA
+//   split_g4(g4, gs, p, d)  split4 of four values of G, gs = X3Args::g_scale (a format without a scale ignores it; no clamp: |G| <= grad_scale)
+//   dh_unscale(a)           what dHidden's sums are multiplied by: 4 (its tanh' form) over the operands' scales
 #pragma once
 #include "kernels.hpp"
 #include "mma_common.hpp"
@@ -40,6 +42,8 @@ struct Bf16x3 {
     }
     template <class X4> static __device__ __forceinline__ void split4(const X4 &x4, u32x4 (&p)[NP], int d) { split4(x4, p[0], p[1], p[2], d); }
     static __device__ __forceinline__ void set(u32x4 (&p)[NP], int d, const Pieces &q) { p[0][d] = q.h; p[1][d] = q.m; p[2][d] = q.l; }
+    template <class X4> static __device__ __forceinline__ void split_g4(const X4 &g4, float, u32x4 (&p)[NP], int d) { split4(g4, p, d); }
+    static __device__ __forceinline__ float dh_unscale(const X3Args &) { return 4.0f; }
     static __device__ __forceinline__ f32x16 mfma(u32x4 a, u32x4 b, f32x16 c) { return mfma_bf16(a, b, c); }
 };
 
@@ -81,6 +85,12 @@ struct F16x2 {
     }
     template <class X4> static __device__ __forceinline__ void split4(const X4 &x4, u32x4 (&p)[NP], int d) { split4(x4, p[0], p[1], d); }
     static __device__ __forceinline__ void set(u32x4 (&p)[NP], int d, const Pieces &q) { p[0][d] = q.h; p[1][d] = q.m; }
+    template <class X4> static __device__ __forceinline__ void split_g4(const X4 &g4, float gs, u32x4 (&p)[NP], int d)
+    {
+        const f32x4 s4 = g4 * gs;  // (|G| <= grad_scale: no clamp needed; exact: a power of two)
+        split4(s4, p, d);
+    }
+    static __device__ __forceinline__ float dh_unscale(const X3Args &a) { return 4.0f * a.db_rescale * a.scales[1]; }  // 4 / (g_scale s_W)
     static __device__ __forceinline__ f32x16 mfma(u32x4 a, u32x4 b, f32x16 c) { return mfma_f16(a, b, c); }
 };
 

@@ -24,10 +24,9 @@
 //
 // MFMA operand maps (v_mfma_f32_32x32x16_f16, as the bf16 form): lane l = (r = l&31, h = l>>5) holds A[row r][k = 8h+j] and
 // B[k = 8h+j][col r], j = 0..7; C/D: col = l&31, row = (reg&3) + 8*(reg>>2) + 4*(l>>5).
-#include "split_common.hpp"
+#include "split_dhidden.hpp"
 
 typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef float f2 __attribute__((ext_vector_type(2)));
 
 #define XW2_ROWS 16  // cells per dW k-step (the live structures below are built in these units)
 #define XG2_BT 8     // the dHidden tile: 8 t x 16 u cells
@@ -974,54 +973,24 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
     const int nub = a.n_ublk16, ntt = (T + XG2_BT - 1) / XG2_BT;
     const int ub = __builtin_amdgcn_readfirstlane(tile % nub), tt = __builtin_amdgcn_readfirstlane((tile / nub) % ntt);
     const int b = __builtin_amdgcn_readfirstlane(tile / (nub * ntt));
-    int Tb, Ub;
-    len_tu_uniform(a.logit_lens, a.target_lens, b, a.T, a.U1, Tb, Ub);
-    const int t0 = tt * XG2_BT, u0 = ub * XG2_BU;
+    const DhTile tl = dh_tile(a, b, tt, ub);
     const int VC = V / 16;
     const int ngrp = PART ? (H - 512 * hp) / 128 : 4;  // live 128-column groups of this pass (H % 128 == 0)
     if (FIRST) X_CLOCK_STAMP(128 + 108);  // (one tile of ~0.1 ms: 1e-4 resolution at the 100 MHz reference)
-
-    // ---- producer role: M tile `wave`, row i = cell (pt, pu)
-    const int prow = wave * 32 + i;
-    const int pt = t0 + (prow >> 4), pu = u0 + (prow & 15);
-    const bool pexists = pt < T && pu < U1;
-    const long zrow = (long)a.B * T * U1;  // first zero padding row
-    const long pcell = pexists ? ((long)b * T + pt) * U1 + pu : zrow;
 
     // A live tile holds a cell with non-null coefficients, so it lies inside the lengths (t0 < T_b, u0 <= U_b).  The tiles that are not on
     // the list — past the lengths, or every cell outside the lattice, unreachable or flushed: each would have produced G = 0 — run nowhere
     // and owe nothing here: the G rows the dW GEMM reads of them are zeroed by k_x2_dead_rows, their slab pieces are never written and the
     // reductions leave them out by the same flag (JointBwdArgs::tile_flag).  The later column passes (FIRST = false) walk the same list.
 
-    CellCoef cf = a.coef[pexists ? pcell : 0];
-    const bool live = pexists && pt < Tb && cf.c1 != RNNT_NEG_INF;
-    if (!live) { cf.c1 = RNNT_NEG_INF; cf.sb = 0.f; cf.se = 0.f; cf.y = -1; }
+    DhCell pc;  // producer role: M tile `wave`, row i
+    pc.at(a, tl, wave, lane);
+    pc.load_coef<FIRST>(a, tl);
     const float gs = a.g_scale;
-    // The producer's memory, per k-step c (16 vocabulary entries, this lane: 8 of them, v = 16c + 8half + j):
-    //   logits (fp32): 32 bytes at row + 64c + 32half               (f32x4 index 4c + 2half, +1)
-    //   G hi: 16 bytes at row + 128(c>>1) + 32(c&1) + 16half        (u32x4 index 8(c>>1) + 2(c&1) + half);  G mid: + 64 bytes
-    // rows outside the lattice read the zero padding row (finite) with c1 = -inf -> G = 0; FIRST = false: every existing row
-    // holds its G planes already
-    const float *xsrc = a.logits + ((FIRST ? live : pexists) ? pcell : zrow) * V;
     const int blank = a.blank;
-    // whole-line stores (k_dhidden_x3, round 4): lane L -> row 8n + (L >> 3) of the M tile (n = 0..3: four store instructions,
-    // 8 whole lines each), piece L & 7 = (plane, k-step parity, half), read back from this wave's part of the exchange (both
-    // slots hold the pair between the exchange write of the odd k-step and the next even one's).  Raw-buffer stores over the
-    // tile's rows: rows outside the lattice get an offset past the range (dropped): every wave issues the same instructions.
     const int lds0 = (int)(size_t)(lds_vptr)s_dh;
-    const int lpiece = lane & 7, lrow = lane >> 3;
-    // LDS: [slot = parity][M tile wave][plane][lane slot = row + 32 half]
-    const int xl = lds0 + XG2_NW * XG2_WSLOT + ((lpiece >> 1) & 1) * XG2_XSLOT + wave * 2048 + (lpiece >> 2) * 1024 + 16 * (lrow + 32 * (lpiece & 1));
-    const long tile_cell0 = ((long)b * T + t0) * U1 + u0;  // the tile's first cell (exists: t0 < Tb <= T, u0 <= Ub < U1)
-    const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(a.logits + tile_cell0 * V), 0, (int)((((long)(XG2_BT - 1) * U1 + XG2_BU) * V) * 4), 0x00020000);
-    int lvo[4];  // byte offset of this lane's piece of line n in the buffer: row (t0 + 2 wave + (n >> 1), u0 + 8 (n & 1) + lrow)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-        const int lt = 2 * wave + (n >> 1), lu = 8 * (n & 1) + lrow;
-        const bool ex = t0 + lt < T && u0 + lu < U1;
-        lvo[n] = ex ? (int)(((long)lt * U1 + lu) * V * 4) + 64 * (lpiece >> 2) + 16 * (lpiece & 3) : 0x7ffffff0;
-    }
+    DhLines<F16x2> lines;  // whole-line stores of the pair's G
+    lines.at(a, tl, lds0 + XG2_NW * XG2_WSLOT, wave, lane);
 
     f32x16 acc[2][8];
 #pragma unroll
@@ -1039,65 +1008,18 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((char *)a.wpack_dh + (long)hp * VC * XG2_WSLOT, 0, VC * XG2_WSLOT, 0x00020000);
     const int wvo = lane * 16;
 
-    struct Raw { f32x4 x0, x1; };  // FIRST: 8 fp32 logits; else: hi | mid planes (as x0, x1 bits)
+    typedef DhRaw<F16x2> Raw;    // FIRST: 8 fp32 logits; else: hi | mid planes
+    typedef DhProd<F16x2> Prod;
     auto xload = [&](Raw &r, int c, int part = 3) {  // part: 1 first half, 2 second half, 3 both
         const int cc = c < VC ? c : VC - 1;
-        if (FIRST) {
-            const f32x4 *p = (const f32x4 *)xsrc + 4 * cc + 2 * half;
-            if (part & 1) r.x0 = p[0];
-            if (part & 2) r.x1 = p[1];
-        } else {
-            const u32x4 *p = (const u32x4 *)xsrc + 8 * (cc >> 1) + 2 * (cc & 1) + half;
-            if (part & 1) r.x0 = __builtin_bit_cast(f32x4, p[0]);
-            if (part & 2) r.x1 = __builtin_bit_cast(f32x4, p[4]);
+        if (FIRST) dh_xload_logits(r, pc.xsrc, cc, half, part);
+        else {
+            const u32x4 *p = (const u32x4 *)pc.xsrc + 8 * (cc >> 1) + 2 * (cc & 1) + half;
+            if (part & 1) r.p[0] = p[0];
+            if (part & 2) r.p[1] = p[4];
         }
     };
-    // G of k-step c from the raw values -> exchange slot (c & 1).  The work is cut into slices (0..8) that the main loop
-    // threads through the gaps of its first MFMA blocks.
-    struct Prod { f32x4 g0, g1; u32x4 ph, pm; };
-    auto produce_slice = [&](Prod &P, const Raw &r, int c, int sl) {
-        if (!FIRST) {
-            if (sl == 0) { P.ph = __builtin_bit_cast(u32x4, r.x0); P.pm = __builtin_bit_cast(u32x4, r.x1); }
-        } else if (sl < 4) {
-            P.g0[sl] = __builtin_amdgcn_exp2f(fmaf(r.x0[sl], RNNT_LOG2E, cf.c1));
-            P.g1[sl] = __builtin_amdgcn_exp2f(fmaf(r.x1[sl], RNNT_LOG2E, cf.c1));
-        } else if (sl == 4) {
-            const int vb = 16 * c + 8 * half;
-            const unsigned dy = (unsigned)(cf.y - vb);
-            if (__any(dy < 8u)) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    P.g0[e] = (dy == (unsigned)e) ? P.g0[e] - cf.se : P.g0[e];
-                    P.g1[e] = (dy == (unsigned)(e + 4)) ? P.g1[e] - cf.se : P.g1[e];
-                }
-            }
-        } else if (sl == 5) {
-            const int vb = 16 * c + 8 * half;
-            if ((unsigned)(blank - 16 * c) < 16u) {  // wave-uniform
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    P.g0[e] = (vb + e == blank) ? P.g0[e] - cf.sb : P.g0[e];
-                    P.g1[e] = (vb + e + 4 == blank) ? P.g1[e] - cf.sb : P.g1[e];
-                }
-            }
-        } else if (sl == 6) {
-            const f32x4 s4 = P.g0 * gs;  // (|G| <= grad_scale: no clamp needed; exact: a power of two)
-            F16x2::split4(s4, P.ph, P.pm, 0);
-        } else if (sl == 7) {
-            const f32x4 s4 = P.g1 * gs;
-            F16x2::split4(s4, P.ph, P.pm, 2);
-        }
-        if (sl == 8) {
-            const int dst = xw + (c & 1) * XG2_XSLOT;
-            asm volatile("ds_write_b128 %0, %1" :: "v"(dst), "v"(P.ph) : "memory");
-            asm volatile("ds_write_b128 %0, %1 offset:1024" :: "v"(dst), "v"(P.pm) : "memory");
-        }
-    };
-    auto produce = [&](const Raw &r, int c) {  // all slices at once (pipeline prologue)
-        Prod P;
-#pragma unroll
-        for (int sl = 0; sl < 9; ++sl) produce_slice(P, r, c, sl);
-    };
+    auto produce_slice = [&](Prod &P, const Raw &r, int c, int sl) { dh_produce_slice<F16x2, FIRST>(P, r, c, sl, pc.cf, half, blank, gs, xw); };
     auto wdma = [&](int c, int slot, int n) {  // piece n (0..7) of this wave's share of W k-step c -> ring slot `slot`
         const int cc = c < VC ? c : VC - 1;
         const int vo = (!PART || (((wave * 8 + n) & 15) >> 2) < ngrp) ? wvo : 0x7ffffff0;  // (piece = plane (pc >> 4), tile pc & 15 = group (pc & 15) >> 2)
@@ -1118,7 +1040,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
 #pragma unroll
     for (int n = 0; n < 8; ++n) wdma(1, 1, n);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the in-place stores of the first pair overwrite logits of k-steps 0, 1
-    produce(xr[0], 0);
+    dh_produce<F16x2, FIRST>(xr[0], 0, pc.cf, half, blank, gs, xw);
     xload(xr[0], 4);
 
     int wsl = 0;  // W ring slot of k-step c (c % 3)
@@ -1156,14 +1078,6 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
             constexpr bool prod_on = true;
             const Raw &rawn = xr[(j + 1) & 3];
             u32x4 ln[4];  // the pair's lines, 16 bytes per lane each (even k-steps)
-            auto line_read = [&](u32x4 &v, auto n_c) {  // rows 8n .. 8n+7 of the M tile: lane slot + 8n
-                const int xl_ = xl;  // (a local: asm operands cannot name a capture of the enclosing generic lambda)
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(xl_), "n"(128 * decltype(n_c)::value));
-            };
-            auto line_store = [&](u32x4 &v, int n, int ce) {  // line n of the pair (ce, ce + 1): chunk ce >> 1 of the rows
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v) :: "memory");
-                __builtin_amdgcn_raw_buffer_store_b128(v, grs, lvo[n], 128 * (ce >> 1), 0);
-            };
             // one product block: 16 MFMAs = (2 M tiles) x (8 column tiles) for A plane PA against the B plane held in `bcur`;
             // BLK names the work threaded through it (the kernel comment's table)
             auto block = [&](auto pa_c, const u32x4 (&bcur)[8], auto blk_c) {
@@ -1181,14 +1095,14 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
                     if (BLK == 1) {
                         if (q == 0 && prod_on) produce_slice(P, rawn, c + 1, 8);
                         if (q >= 1) wdma(c + 2, wsn, q - 1);
-                        if (FIRST && q == 2 && !(j & 1) && prod_on) { line_read(ln[0], Int<0>{}); line_read(ln[1], Int<1>{}); }
-                        if (FIRST && q == 4 && !(j & 1) && prod_on) { line_read(ln[2], Int<2>{}); line_read(ln[3], Int<3>{}); }
+                        if (FIRST && q == 2 && !(j & 1) && prod_on) { lines.read<0>(ln[0]); lines.read<1>(ln[1]); }
+                        if (FIRST && q == 4 && !(j & 1) && prod_on) { lines.read<2>(ln[2]); lines.read<3>(ln[3]); }
                     }
                     if (BLK == 2) {
                         if (q == 0) wdma(c + 2, wsn, 7);
                         if (FIRST && q >= 2 && q <= 5 && !(j & 1)) {
-                            if (prod_on) line_store(ln[q - 2 < 0 ? 0 : (q - 2 > 3 ? 3 : q - 2)], q - 2, c);
-                            else { u32x4 z = {0u, 0u, 0u, 0u}; __builtin_amdgcn_raw_buffer_store_b128(z, grs, 0x7ffffff0, 0, 0); }  // (never: VC is even; keeps the count)
+                            if (prod_on) lines.store(ln[q - 2 < 0 ? 0 : (q - 2 > 3 ? 3 : q - 2)], q - 2, c);
+                            else { u32x4 z = {0u, 0u, 0u, 0u}; __builtin_amdgcn_raw_buffer_store_b128(z, lines.grs, 0x7ffffff0, 0, 0); }  // (never: VC is even; keeps the count)
                         }
                         if (q == 6) xload(xr[(j + 1) & 3], c + 5, 1);
                         if (q == 7) xload(xr[(j + 1) & 3], c + 5, 2);
@@ -1203,104 +1117,13 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2(X3Args a, const int hp)
             wsl = wsl == 2 ? 0 : wsl + 1;
         }
     }
-    // the epilogue's pred rows are requested BEFORE the drain below (they ride out the G stores' acknowledgements with it)
-    const int colg[2] = {512 * hp + 256 * wn + 4 * i, 512 * hp + 256 * wn + 128 + 4 * i};
-    const bool colok[2] = {colg[0] < H, colg[1] < H};
-    f32x4 pr[8][2];  // pred rows of this lane's 8 u slots, its 2 x 4 columns (zero where u >= U1 or the column >= H)
-#pragma unroll
-    for (int r7 = 0; r7 < 8; ++r7) {
-        const int u = u0 + 8 * (r7 >> 2) + (r7 & 3) + 4 * half;
-#pragma unroll
-        for (int g = 0; g < 2; ++g)
-            pr[r7][g] = (u < U1 && colok[g]) ? *(const f32x4 *)(a.pred + ((long)b * U1 + u) * H + colg[g]) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    const float unscale = 4.0f * a.db_rescale * a.scales[1];  // 4 (the tanh' form below) / (g_scale s_W)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the over-issued ring loads / DMAs
-    __syncthreads();
-
-    // ---- epilogue (k_dhidden_x3's).  Accumulator register rr = 8rh + r7 of M tile (2wm + mt), column tile q: row (rr&3) +
-    // 8(rr>>2) + 4half of its 32 = t row 2(2wm+mt) + rh, u slot 8(r7>>2) + (r7&3) + 4half; column 512hp + 256wn + 128(q>>2) +
-    // 4i + (q&3).  The tanh' factor 1 - hidden^2 is recomputed from enc and pred: 4 w / (1 + w)^2, w = exp(-2|x|).
-    float (*s_red)[64][65] = (float (*)[64][65])s_dh;  // [wn][lane][8 u slots x 8 columns]
-    const long BTH = (long)a.B * T * H, BUH = (long)a.B * U1 * H;
-    auto dfac_q = [](f2 x) {  // (1 - tanh^2 x) / 4 of two values
-        const f2 a = x * (2.0f * RNNT_LOG2E);
-        const f2 w = {__builtin_amdgcn_exp2f(-__builtin_fabsf(a[0])), __builtin_amdgcn_exp2f(-__builtin_fabsf(a[1]))};
-        const f2 e1 = w + 1.0f;
-        const f2 r = {__builtin_amdgcn_rcpf(e1[0]), __builtin_amdgcn_rcpf(e1[1])};
-        return (w * r) * r;
-    };
-    f2 psum2[8][4];
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) psum2[k][q] = f2{0.f, 0.f};
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int rh = 0; rh < 2; ++rh) {
-            const int tl = 2 * (2 * wm + mt) + rh;  // t row inside the tile
-            const int t = t0 + tl;
-            f2 esum2[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) esum2[q] = f2{0.f, 0.f};
-            f32x4 er[2];
-#pragma unroll
-            for (int g = 0; g < 2; ++g)
-                er[g] = (t < T && colok[g]) ? *(const f32x4 *)(a.enc + (long)b * a.enc_sb + (long)t * a.enc_st + colg[g]) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int r7 = 0; r7 < 8; ++r7)
-#pragma unroll
-                for (int g = 0; g < 2; ++g)
-#pragma unroll
-                    for (int qq = 0; qq < 2; ++qq) {  // columns 2qq, 2qq+1 of the group
-                        const f2 x = {er[g][2 * qq] + pr[r7][g][2 * qq], er[g][2 * qq + 1] + pr[r7][g][2 * qq + 1]};
-                        const f2 av = {acc[mt][g * 4 + 2 * qq][rh * 8 + r7], acc[mt][g * 4 + 2 * qq + 1][rh * 8 + r7]};
-                        const f2 d = av * dfac_q(x);
-                        esum2[g * 2 + qq] += d;
-                        psum2[r7][g * 2 + qq] += d;
-                    }
-            float esum[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) esum[q] = unscale * esum2[q >> 1][q & 1];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) esum[q] += __shfl_xor(esum[q], 32, 64);
-            if (half == 0 && t < Tb) {
-#pragma unroll
-                for (int g = 0; g < 2; ++g)
-                    if (colok[g]) {
-                        const f32x4 o = {esum[g * 4], esum[g * 4 + 1], esum[g * 4 + 2], esum[g * 4 + 3]};
-                        *(f32x4 *)(a.slab_enc + (long)ub * BTH + ((long)b * T + t) * H + colg[g]) = o;
-                    }
-            }
-        }
-    float psum[8][8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-#pragma unroll
-        for (int q = 0; q < 8; ++q) psum[k][q] = unscale * psum2[k][q >> 1][q & 1];
-    if (wm == 1) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-#pragma unroll
-            for (int q = 0; q < 8; ++q) s_red[wn][lane][k * 8 + q] = psum[k][q];
-    }
-    __syncthreads();
-    if (wm == 0) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int u = u0 + 8 * (k >> 2) + (k & 3) + 4 * half;
-            if (u < U1) {
-#pragma unroll
-                for (int g = 0; g < 2; ++g)
-                    if (colok[g]) {
-                        f32x4 o;
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) o[q] = psum[k][g * 4 + q] + s_red[wn][lane][k * 8 + g * 4 + q];
-                        *(f32x4 *)(a.slab_pred + (long)tt * BUH + ((long)b * U1 + u) * H + colg[g]) = o;
-                    }
-            }
-        }
+    {   // the shared epilogue: pred rows requested, drain, barrier, x (1 - hidden^2), the two slabs
+        typedef F16x2 F;
+        constexpr int MT = 2, NG = 2;
+        constexpr bool XWAVE = true;
+        const int mbase = 2 * wm, colbase = 512 * hp + 256 * wn;
+        float (*s_red)[64][65] = (float (*)[64][65])s_dh;  // the W ring is free behind the epilogue's barrier
+#include "split_dhidden_epilogue.inc"
     }
     if (FIRST) X_CLOCK_STAMP(128 + 110);
 }
@@ -1327,10 +1150,8 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2r(X3Args a, const int hp)
     const int i = lane & 31, half = lane >> 5;
     const int T = a.T, U1 = a.U1, H = a.H, V = a.V;
     const int ub = blockIdx.x, tq = blockIdx.y, b = blockIdx.z;
-    int Tb, Ub;
-    len_tu_uniform(a.logit_lens, a.target_lens, b, a.T, a.U1, Tb, Ub);
-    const int u0 = ub * XG2_BU;
-    const int tt = 4 * tq + wave, t0 = tt * XG2_BT;  // this wave's t block
+    const DhTile tl = dh_tile(a, b, 4 * tq + wave, ub);  // this wave's t block
+    const int tt = tl.tt, t0 = tl.t0, u0 = tl.u0, Tb = tl.Tb, Ub = tl.Ub;
     const int VC = V / 16;
     if (4 * tq * XG2_BT >= Tb || u0 > Ub) return;    // workgroup-uniform: no lattice cell in any of the four blocks
     const bool winlen = t0 < Tb;                       // wave-uniform: this wave's block lies inside the lengths (else: zeros in, nothing out)
@@ -1433,57 +1254,14 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x2r(X3Args a, const int hp)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the over-issued loads / DMAs: none may land in an LDS the next workgroup owns
     if (!wlive) return;
 
-    // ---- epilogue (k_dhidden_x2's, one wave = one block).  Accumulator register rr = 8 rh + r7 of M tile m, column tile n: t row
-    // 2m + rh, u slot 8 (r7 >> 2) + (r7 & 3) + 4 half; column 512 hp + 4i + n.
-    const int colg = 512 * hp + 4 * i;
-    const bool colok = colg < H;
-    f32x4 pr[8];
-#pragma unroll
-    for (int r7 = 0; r7 < 8; ++r7) {
-        const int u = u0 + 8 * (r7 >> 2) + (r7 & 3) + 4 * half;
-        pr[r7] = (u < U1 && colok) ? *(const f32x4 *)(a.pred + ((long)b * U1 + u) * H + colg) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    const float unscale = 4.0f * a.db_rescale * a.scales[1];  // 4 (the tanh' form below) / (g_scale s_W)
-    const long BTH = (long)a.B * T * H, BUH = (long)a.B * U1 * H;
-    auto dfac_q = [](f2 x) {  // (1 - tanh^2 x) / 4 of two values
-        const f2 av = x * (2.0f * RNNT_LOG2E);
-        const f2 w = {__builtin_amdgcn_exp2f(-__builtin_fabsf(av[0])), __builtin_amdgcn_exp2f(-__builtin_fabsf(av[1]))};
-        const f2 e1 = w + 1.0f;
-        const f2 r = {__builtin_amdgcn_rcpf(e1[0]), __builtin_amdgcn_rcpf(e1[1])};
-        return (w * r) * r;
-    };
-    f2 psum2[8][2];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { psum2[k][0] = f2{0.f, 0.f}; psum2[k][1] = f2{0.f, 0.f}; }
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int rh = 0; rh < 2; ++rh) {
-            const int t = t0 + 2 * m + rh;
-            const f32x4 er = (t < T && colok) ? *(const f32x4 *)(a.enc + (long)b * a.enc_sb + (long)t * a.enc_st + colg) : f32x4{0.f, 0.f, 0.f, 0.f};
-            f2 esum2[2] = {f2{0.f, 0.f}, f2{0.f, 0.f}};
-#pragma unroll
-            for (int r7 = 0; r7 < 8; ++r7)
-#pragma unroll
-                for (int qq = 0; qq < 2; ++qq) {
-                    const f2 x = {er[2 * qq] + pr[r7][2 * qq], er[2 * qq + 1] + pr[r7][2 * qq + 1]};
-                    const f2 av = {acc[m][2 * qq][rh * 8 + r7], acc[m][2 * qq + 1][rh * 8 + r7]};
-                    const f2 d = av * dfac_q(x);
-                    esum2[qq] += d;
-                    psum2[r7][qq] += d;
-                }
-            f32x4 es = {unscale * esum2[0][0], unscale * esum2[0][1], unscale * esum2[1][0], unscale * esum2[1][1]};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) es[q] += __shfl_xor(es[q], 32, 64);
-            if (half == 0 && t < Tb && colok) *(f32x4 *)(a.slab_enc + (long)ub * BTH + ((long)b * T + t) * H + colg) = es;
-        }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int u = u0 + 8 * (k >> 2) + (k & 3) + 4 * half;
-        if (u < U1 && colok) {
-            const f32x4 o = {unscale * psum2[k][0][0], unscale * psum2[k][0][1], unscale * psum2[k][1][0], unscale * psum2[k][1][1]};
-            *(f32x4 *)(a.slab_pred + (long)tt * BUH + ((long)b * U1 + u) * H + colg) = o;
-        }
+    {   // the shared epilogue: one wave = one block, all 8 t rows sit in this wave: no cross-wave step
+        typedef F16x2 F;
+        constexpr int MT = 4, NG = 1;
+        constexpr bool XWAVE = false;
+        const int mbase = 0, colbase = 512 * hp;
+        float (*s_red)[64][65] = nullptr;
+        const int wm = 0, wn = 0;
+#include "split_dhidden_epilogue.inc"
     }
 }
 

@@ -23,7 +23,7 @@
 // and B[k = 8h+j][col r], j = 0..7; C/D: col = l&31, row = (reg&3) + 8*(reg>>2) + 4*(l>>5).
 // Every kernel here is 4 waves (one per SIMD) with 256 accumulator registers per wave, hand-pipelined
 // around long MFMA streams (96 MFMAs = 3072 matrix-pipe cycles per 16-deep k-step), like the fp32 route's.
-#include "split_common.hpp"
+#include "split_dhidden.hpp"
 
 // The plain producers and the W packs are split_common.hpp's, at the bf16x3 format (no scales: the pointer is null and unread)
 void launch_x3_make_hidden(const X3Args &a, hipStream_t st) { launch_split_make_hidden<Bf16x3>(a, st); }
@@ -394,7 +394,6 @@ __global__ __launch_bounds__(256, 1) void k_joint_fwd_x3(X3Args a, const int nti
     const int npass = (V + 511) / 512;
     const int NS = npass * KC;  // k-steps of a tile
     const long cells = (long)a.B * T * U1;
-    typedef float f2 __attribute__((ext_vector_type(2)));
 
     const int lds0 = (int)(size_t)(lds_vptr)s_fw;
     const int xa = lds0 + 2 * XF_WSLOT + (2 * wm) * 3072 + 16 * lane;  // A read: M tiles 2wm, 2wm+1: [slot][M tile][plane][lane]
@@ -783,28 +782,21 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
     const int wm = wave >> 1, wn = wave & 1;
     const int i = lane & 31, half = lane >> 5;
     const int T = a.T, U1 = a.U1, H = a.H, V = a.V;
-    const int ub = blockIdx.x, tt = blockIdx.y, b = blockIdx.z;
-    int Tb, Ub;
-    len_tu_uniform(a.logit_lens, a.target_lens, b, a.T, a.U1, Tb, Ub);
-    const int t0 = tt * XG_BT, u0 = ub * XG_BU;
+    const DhTile tl = dh_tile(a, blockIdx.z, blockIdx.y, blockIdx.x);
     const int VC = V / 16;
     if (FIRST) X_CLOCK_STAMP(128 + 108);  // (one tile of ~0.1 ms: 1e-4 resolution at the 100 MHz reference)
 
-    // ---- producer role: M tile `wave`, row i = cell (pt, pu)
-    const int prow = wave * 32 + i;
-    const int pt = t0 + (prow >> 4), pu = u0 + (prow & 15);
-    const bool pexists = pt < T && pu < U1;
-    const long zrow = (long)a.B * T * U1;  // first zero padding row
-    const long pcell = pexists ? ((long)b * T + pt) * U1 + pu : zrow;
+    DhCell pc;  // producer role: M tile `wave`, row i
+    pc.at(a, tl, wave, lane);
 
     // workgroup-uniform: no products past the utterance's length or in a u block past U_b (no lattice cell; the
     // reductions skip its slabs), but k_dw_x3 must find zeros in these rows (all three planes)
-    if (t0 >= Tb || u0 > Ub) {
-        if (FIRST && pexists) {
+    if (tl.t0 >= tl.Tb || tl.u0 > tl.Ub) {
+        if (FIRST && pc.pexists) {
             const u32x4 z = {0u, 0u, 0u, 0u};
-            u32x4 *g = (u32x4 *)(a.logits + pcell * V) + half;
-            u32x4 *gl = (u32x4 *)(a.g_lo + pcell * V) + half;
-            for (int c = 0; c < VC; ++c) {  // this lane's 16 B of each plane per k-step (layout below)
+            u32x4 *g = (u32x4 *)(a.logits + pc.pcell * V) + half;
+            u32x4 *gl = (u32x4 *)(a.g_lo + pc.pcell * V) + half;
+            for (int c = 0; c < VC; ++c) {  // this lane's 16 B of each plane per k-step (layout: split_dhidden.hpp, DhCell; lo: below)
                 g[8 * (c >> 1) + 2 * (c & 1)] = z;
                 g[8 * (c >> 1) + 4 + 2 * (c & 1)] = z;
                 gl[2 * c] = z;
@@ -813,42 +805,19 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
         return;
     }
 
-    CellCoef cf = a.coef[pexists ? pcell : 0];
-    const bool live = pexists && pt < Tb && cf.c1 != RNNT_NEG_INF;
-    if (!live) { cf.c1 = RNNT_NEG_INF; cf.sb = 0.f; cf.se = 0.f; cf.y = -1; }
-    // The producer's memory, per k-step c (16 vocabulary entries, this lane: 8 of them, v = 16c + 8half + j):
-    //   logits (fp32): 32 bytes at row + 64c + 32half               (f32x4 index 4c + 2half, +1)
-    //   G hi: 16 bytes at row + 128(c>>1) + 32(c&1) + 16half        (u32x4 index 8(c>>1) + 2(c&1) + half)
-    //   G mid: the same + 64 bytes;  G lo: 16 bytes at lo row + 32c + 16half
-    // rows outside the lattice read the zero padding row (finite) with c1 = -inf -> G = 0; FIRST = false: every
-    // existing row holds its G planes already
-    const float *xsrc = a.logits + ((FIRST ? live : pexists) ? pcell : zrow) * V;
-    const u32x4 *lsrc = (const u32x4 *)(a.g_lo + (pexists ? pcell : zrow) * V) + half;
+    pc.load_coef<FIRST>(a, tl);
+    // G lo of k-step c: 16 bytes at lo row + 32c + 16half
+    const u32x4 *lsrc = (const u32x4 *)(a.g_lo + (pc.pexists ? pc.pcell : pc.zrow) * V) + half;
     const int blank = a.blank;
-    // G's hi | mid planes leave in WHOLE 128-byte lines (round 4): a line = the 32 x hi | 32 x mid of one cell and one
-    // 32-wide chunk = the fragments of two k-steps (c even, c odd) x two wave halves x two planes — eight 16-byte pieces
-    // that the producing wave reads back from ITS part of the LDS exchange (both slots hold the pair between the
-    // exchange write of the odd k-step and the next even one's) in row order: lane L -> row 8n + (L >> 3) of the M
-    // tile (n = 0..3: four store instructions, 8 whole lines each), piece L & 7 = (plane, k-step parity, half).
-    // (Producer-shaped stores wrote 32-byte pieces of these lines in four instructions a k-step apart: WRITE_SIZE
-    // 60.7 GB for 39.5 GB of G, profiles/r03_traffic.json.)  Raw-buffer stores over the tile's rows: rows outside the
-    // lattice get an offset past the range (dropped), so every wave issues the same store instructions.
+    // whole-line stores of the pair's hi | mid planes.  (Producer-shaped stores wrote 32-byte pieces of these lines in four
+    // instructions a k-step apart: WRITE_SIZE 60.7 GB for 39.5 GB of G, profiles/r03_traffic.json.)
     const int lds0 = (int)(size_t)(lds_vptr)s_dh;
-    const int lpiece = lane & 7, lrow = lane >> 3;
-    // LDS: [slot = parity][M tile wave][plane][lane slot = row + 32 half]
-    const int xl = lds0 + 2 * XG_WSLOT + ((lpiece >> 1) & 1) * XG_XSLOT + wave * 3072 + (lpiece >> 2) * 1024 + 16 * (lrow + 32 * (lpiece & 1));
-    const long tile_cell0 = ((long)b * T + t0) * U1 + u0;  // the tile's first cell (exists: t0 < Tb <= T, u0 <= Ub < U1)
-    const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(a.logits + tile_cell0 * V), 0, (int)((((long)(XG_BT - 1) * U1 + XG_BU) * V) * 4), 0x00020000);
+    DhLines<Bf16x3> lines;
+    lines.at(a, tl, lds0 + 2 * XG_WSLOT, wave, lane);
+    const int t0 = tl.t0, u0 = tl.u0;
+    const long tile_cell0 = ((long)tl.b * T + t0) * U1 + u0;  // the tile's first cell (exists: t0 < Tb <= T, u0 <= Ub < U1)
     const __amdgpu_buffer_rsrc_t lrs = __builtin_amdgcn_make_buffer_rsrc(
         (void *)(a.g_lo + tile_cell0 * V), 0, (int)((((long)(XG_BT - 1) * U1 + XG_BU) * V) * 2), 0x00020000);
-    int lvo[4];  // byte offset of this lane's piece of line n in the buffer: row (t0 + 2 wave + (n >> 1), u0 + 8 (n & 1) + lrow)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-        const int lt = 2 * wave + (n >> 1), lu = 8 * (n & 1) + lrow;
-        const bool ex = t0 + lt < T && u0 + lu < U1;
-        lvo[n] = ex ? (int)(((long)lt * U1 + lu) * V * 4) + 64 * (lpiece >> 2) + 16 * (lpiece & 3) : 0x7ffffff0;
-    }
     // lo plane: the pair's 64 bytes per row (half a line: a whole line would need four k-steps of fragments in the exchange),
     // lane L -> row 16n + (L >> 2) (n = 0, 1: two store instructions, 16 half lines each), piece L & 3 = (k-step parity, half)
     const int xl2 = lds0 + 2 * XG_WSLOT + ((lane >> 1) & 1) * XG_XSLOT + wave * 3072 + 2 * 1024 + 16 * ((lane >> 2) + 32 * (lane & 1));
@@ -876,67 +845,20 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((char *)a.wpack_dh + (long)hp * VC * 49152, 0, VC * 49152, 0x00020000);
     const int wvo = lane * 16;
 
-    struct Raw { f32x4 x0, x1; u32x4 l; };  // FIRST: 8 fp32 logits; else: hi | mid (as x0, x1 bits) and lo planes
+    typedef DhRaw<Bf16x3> Raw;    // FIRST: 8 fp32 logits; else: hi | mid | lo planes
+    typedef DhProd<Bf16x3> Prod;
     auto xload = [&](Raw &r, int c, int part = 3) {  // part: 1 first half, 2 second half, 3 both (FIRST)
         const int cc = c < VC ? c : VC - 1;
-        if (FIRST) {
-            const f32x4 *p = (const f32x4 *)xsrc + 4 * cc + 2 * half;
-            if (part & 1) r.x0 = p[0];
-            if (part & 2) r.x1 = p[1];
-        } else if (part & 1) {
-            const u32x4 *p = (const u32x4 *)xsrc + 8 * (cc >> 1) + 2 * (cc & 1) + half;
-            r.x0 = __builtin_bit_cast(f32x4, p[0]); r.x1 = __builtin_bit_cast(f32x4, p[4]);
-            r.l = lsrc[2 * cc];
+        if (FIRST) dh_xload_logits(r, pc.xsrc, cc, half, part);
+        else if (part & 1) {
+            const u32x4 *p = (const u32x4 *)pc.xsrc + 8 * (cc >> 1) + 2 * (cc & 1) + half;
+            r.p[0] = p[0]; r.p[1] = p[4];
+            r.p[2] = lsrc[2 * cc];
         }
     };
     // G of k-step c from the raw values -> exchange slot (c & 1); (FIRST) it leaves for memory from there, as whole lines
-    // (line_read / line_store, lo_read / lo_store below).  The work is cut into
-    // slices (0..8) that the main loop threads through the gaps of its first MFMA blocks: one wave per SIMD
-    // issues ~1 instruction per 4-5 cycles and an MFMA leaves 24 of its 32 cycles to other instructions, so ~150
-    // instructions in FRONT of a k-step's MFMAs would cost a quarter of it.
-    struct Prod { f32x4 g0, g1; u32x4 ph, pm, pl; };
-    auto produce_slice = [&](Prod &P, const Raw &r, int c, int sl) {
-        if (!FIRST) {
-            if (sl == 0) { P.ph = __builtin_bit_cast(u32x4, r.x0); P.pm = __builtin_bit_cast(u32x4, r.x1); P.pl = r.l; }
-        } else if (sl < 4) {
-            P.g0[sl] = __builtin_amdgcn_exp2f(fmaf(r.x0[sl], RNNT_LOG2E, cf.c1));
-            P.g1[sl] = __builtin_amdgcn_exp2f(fmaf(r.x1[sl], RNNT_LOG2E, cf.c1));
-        } else if (sl == 4) {
-            const int vb = 16 * c + 8 * half;
-            const unsigned dy = (unsigned)(cf.y - vb);
-            if (__any(dy < 8u)) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    P.g0[e] = (dy == (unsigned)e) ? P.g0[e] - cf.se : P.g0[e];
-                    P.g1[e] = (dy == (unsigned)(e + 4)) ? P.g1[e] - cf.se : P.g1[e];
-                }
-            }
-        } else if (sl == 5) {
-            const int vb = 16 * c + 8 * half;
-            if ((unsigned)(blank - 16 * c) < 16u) {  // wave-uniform
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    P.g0[e] = (vb + e == blank) ? P.g0[e] - cf.sb : P.g0[e];
-                    P.g1[e] = (vb + e + 4 == blank) ? P.g1[e] - cf.sb : P.g1[e];
-                }
-            }
-        } else if (sl == 6) {
-            Bf16x3::split4(P.g0, P.ph, P.pm, P.pl, 0);
-        } else if (sl == 7) {
-            Bf16x3::split4(P.g1, P.ph, P.pm, P.pl, 2);
-        }
-        if (sl == 8) {
-            const int dst = xw + (c & 1) * XG_XSLOT;
-            asm volatile("ds_write_b128 %0, %1" :: "v"(dst), "v"(P.ph) : "memory");
-            asm volatile("ds_write_b128 %0, %1 offset:1024" :: "v"(dst), "v"(P.pm) : "memory");
-            asm volatile("ds_write_b128 %0, %1 offset:2048" :: "v"(dst), "v"(P.pl) : "memory");
-        }
-    };
-    auto produce = [&](const Raw &r, int c) {  // all slices at once (pipeline prologue)
-        Prod P;
-#pragma unroll
-        for (int sl = 0; sl < 9; ++sl) produce_slice(P, r, c, sl);
-    };
+    // (lines.read / lines.store, lo_read / lo_store below)
+    auto produce_slice = [&](Prod &P, const Raw &r, int c, int sl) { dh_produce_slice<Bf16x3, FIRST>(P, r, c, sl, pc.cf, half, blank, 1.f, xw); };
     auto wdma = [&](int c, int n) {  // piece n (0..11) of this wave's share of W k-step c -> ring slot c & 1
         const int cc = c < VC ? c : VC - 1;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_vptr)(s_dh + (c & 1) * XG_WSLOT + (wave * 12 + n) * 1024), 16, wvo,
@@ -948,7 +870,7 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
 #pragma unroll
     for (int n = 0; n < 12; ++n) wdma(0, n);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the in-place stores of k-step 0 overwrite logits of k-step 1
-    produce(xr[0], 0);
+    dh_produce<Bf16x3, FIRST>(xr[0], 0, pc.cf, half, blank, 1.f, xw);
     xload(xr[0], 4);
 
     for (int c0 = 0; c0 < VC; c0 += 4) {  // VC % 4 == 0 (V % 128 == 0)
@@ -990,10 +912,6 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
             // MEM: the k-step's five HBM operations, spread one per half block behind the DMAs (0: none; 1: G hi + mid
             // stores; 2: G lo store + first logits load; 3: second logits load)
             u32x4 ln[4];  // the pair's lines, 16 bytes per lane each (even k-steps)
-            auto line_read = [&](u32x4 &v, auto n_c) {  // rows 8n .. 8n+7 of the M tile: lane slot + 8n
-                const int xl_ = xl;  // (a local: asm operands cannot name a capture of the enclosing generic lambda)
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(xl_), "n"(128 * decltype(n_c)::value));
-            };
             u32x4 ll[2];  // the pair's lo half lines
             auto lo_read = [&](u32x4 &v, auto n_c) {  // rows 16n .. 16n+15 of the M tile
                 const int xl_ = xl2;
@@ -1002,10 +920,6 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
             auto lo_store = [&](u32x4 &v, int n, int ce) {
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v) :: "memory");
                 __builtin_amdgcn_raw_buffer_store_b128(v, lrs, lvo2[n], 64 * (ce >> 1), 0);
-            };
-            auto line_store = [&](u32x4 &v, int n, int ce) {  // line n of the pair (ce, ce + 1): chunk ce >> 1 of the rows
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v) :: "memory");
-                __builtin_amdgcn_raw_buffer_store_b128(v, grs, lvo[n], 128 * (ce >> 1), 0);
             };
             auto block = [&](auto pa_c, const u32x4 (&bcur)[8], u32x4 (&bnext)[8], auto nb_c, auto d0_c, auto s0_c, auto mem_c) {
                 constexpr int PA = decltype(pa_c)::value, NB = decltype(nb_c)::value, D0 = decltype(d0_c)::value, S0 = decltype(s0_c)::value;
@@ -1024,15 +938,15 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
                     if (S0 >= 0 && S0 + q < 9 && prod_on) produce_slice(P, rawn, c + 1, (S0 < 0 ? 0 : S0) + q);
                     if (FIRST) {
                         // even k-step c: G of k-steps c and c+1 is in the exchange -> the pair's lines (hi | mid) and lo half lines; every k-step: 2 raw loads
-                        if (MEM == 1 && q == 1 && !(j & 1) && prod_on) { line_read(ln[0], Int<0>{}); line_read(ln[1], Int<1>{}); }
-                        if (MEM == 1 && q == 3 && !(j & 1) && prod_on) { line_read(ln[2], Int<2>{}); line_read(ln[3], Int<3>{}); }
+                        if (MEM == 1 && q == 1 && !(j & 1) && prod_on) { lines.read<0>(ln[0]); lines.read<1>(ln[1]); }
+                        if (MEM == 1 && q == 3 && !(j & 1) && prod_on) { lines.read<2>(ln[2]); lines.read<3>(ln[3]); }
                         if (MEM == 1 && q == 5 && !(j & 1) && prod_on) { lo_read(ll[0], Int<0>{}); lo_read(ll[1], Int<1>{}); }
                         if (MEM == 3 && q == 2 && !(j & 1) && prod_on) lo_store(ll[0], 0, c);
                         if (MEM == 3 && q == 4 && !(j & 1) && prod_on) lo_store(ll[1], 1, c);
-                        if (MEM == 2 && q == 1 && !(j & 1) && prod_on) line_store(ln[0], 0, c);
-                        if (MEM == 2 && q == 3 && !(j & 1) && prod_on) line_store(ln[1], 1, c);
-                        if (MEM == 2 && q == 5 && !(j & 1) && prod_on) line_store(ln[2], 2, c);
-                        if (MEM == 3 && q == 1 && !(j & 1) && prod_on) line_store(ln[3], 3, c);
+                        if (MEM == 2 && q == 1 && !(j & 1) && prod_on) lines.store(ln[0], 0, c);
+                        if (MEM == 2 && q == 3 && !(j & 1) && prod_on) lines.store(ln[1], 1, c);
+                        if (MEM == 2 && q == 5 && !(j & 1) && prod_on) lines.store(ln[2], 2, c);
+                        if (MEM == 3 && q == 1 && !(j & 1) && prod_on) lines.store(ln[3], 3, c);
                         if (MEM == 3 && q == 3) xload(xr[(j + 1) & 3], c + 5, 1);
                         if (MEM == 3 && q == 5) xload(xr[(j + 1) & 3], c + 5, 2);
                     } else {  // the later column passes store nothing: the raw ring's refill (hi | mid and lo planes in one go)
@@ -1060,109 +974,13 @@ __global__ __launch_bounds__(256, 1) void k_dhidden_x3(X3Args a, const int hp)
             GXSTAMP(6);
         }
     }
-    // the epilogue's pred rows are requested BEFORE the drain below (they ride out the G stores' acknowledgements with it)
-    const int colg[2] = {512 * hp + 256 * wn + 4 * i, 512 * hp + 256 * wn + 128 + 4 * i};
-    const bool colok[2] = {colg[0] < H, colg[1] < H};
-    f32x4 pr[8][2];  // pred rows of this lane's 8 u slots, its 2 x 4 columns (zero where u >= U1 or the column >= H)
-#pragma unroll
-    for (int r7 = 0; r7 < 8; ++r7) {
-        const int u = u0 + 8 * (r7 >> 2) + (r7 & 3) + 4 * half;
-#pragma unroll
-        for (int g = 0; g < 2; ++g)
-            pr[r7][g] = (u < U1 && colok[g]) ? *(const f32x4 *)(a.pred + ((long)b * U1 + u) * H + colg[g]) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the over-issued ring loads / DMAs
-    __syncthreads();
-
-    // ---- epilogue.  Accumulator register rr = 8rh + r7 of M tile (2wm + mt), column tile q: row (rr&3) + 8(rr>>2) +
-    // 4half of its 32 = t row 2(2wm+mt) + rh, u slot 8(r7>>2) + (r7&3) + 4half; column 512hp + 256wn + 128(q>>2) +
-    // 4i + (q&3).  hidden = hi + mid + lo of the planes (exact), through a raw buffer over the tile's rows.
-    float (*s_red)[64][65] = (float (*)[64][65])s_dh;  // [wn][lane][8 u slots x 8 columns]
-    const long BTH = (long)a.B * T * H, BUH = (long)a.B * U1 * H;
-    // The tanh' factor 1 - hidden^2 is RECOMPUTED from enc and pred (two small, cache-resident operands) instead of re-reading
-    // hidden's three planes (6 bytes per element of HBM traffic), in the form 1 - tanh^2(x) = 4 w / (1 + w)^2, w = exp(-2|x|):
-    // one exp2, one reciprocal and three multiplies per element on register PAIRS (v_pk_*; no MFMA runs beside this phase),
-    // no cancellation near |hidden| = 1, no overflow (w <= 1).  The factor 4 is applied to the sums (exact).
-    // Rows outside the lattice have G = 0 and therefore an exactly zero accumulator: any finite value will do.
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    auto dfac_q = [](f2 x) {  // (1 - tanh^2 x) / 4 of two values
-        const f2 a = x * (2.0f * RNNT_LOG2E);
-        const f2 w = {__builtin_amdgcn_exp2f(-__builtin_fabsf(a[0])), __builtin_amdgcn_exp2f(-__builtin_fabsf(a[1]))};
-        const f2 e1 = w + 1.0f;
-        const f2 r = {__builtin_amdgcn_rcpf(e1[0]), __builtin_amdgcn_rcpf(e1[1])};
-        return (w * r) * r;
-    };
-    f2 psum2[8][4];
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) psum2[k][q] = f2{0.f, 0.f};
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int rh = 0; rh < 2; ++rh) {
-            const int tl = 2 * (2 * wm + mt) + rh;  // t row inside the tile
-            const int t = t0 + tl;
-            f2 esum2[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) esum2[q] = f2{0.f, 0.f};
-            f32x4 er[2];
-#pragma unroll
-            for (int g = 0; g < 2; ++g)
-                er[g] = (t < T && colok[g]) ? *(const f32x4 *)(a.enc + (long)b * a.enc_sb + (long)t * a.enc_st + colg[g]) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int r7 = 0; r7 < 8; ++r7)
-#pragma unroll
-                for (int g = 0; g < 2; ++g)
-#pragma unroll
-                    for (int qq = 0; qq < 2; ++qq) {  // columns 2qq, 2qq+1 of the group
-                        const f2 x = {er[g][2 * qq] + pr[r7][g][2 * qq], er[g][2 * qq + 1] + pr[r7][g][2 * qq + 1]};
-                        const f2 av = {acc[mt][g * 4 + 2 * qq][rh * 8 + r7], acc[mt][g * 4 + 2 * qq + 1][rh * 8 + r7]};
-                        const f2 d = av * dfac_q(x);
-                        esum2[g * 2 + qq] += d;
-                        psum2[r7][g * 2 + qq] += d;
-                    }
-            float esum[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) esum[q] = 4.0f * esum2[q >> 1][q & 1];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) esum[q] += __shfl_xor(esum[q], 32, 64);
-            if (half == 0 && t < Tb) {
-#pragma unroll
-                for (int g = 0; g < 2; ++g)
-                    if (colok[g]) {
-                        const f32x4 o = {esum[g * 4], esum[g * 4 + 1], esum[g * 4 + 2], esum[g * 4 + 3]};
-                        *(f32x4 *)(a.slab_enc + (long)ub * BTH + ((long)b * T + t) * H + colg[g]) = o;
-                    }
-            }
-        }
-    float psum[8][8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-#pragma unroll
-        for (int q = 0; q < 8; ++q) psum[k][q] = 4.0f * psum2[k][q >> 1][q & 1];
-    if (wm == 1) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-#pragma unroll
-            for (int q = 0; q < 8; ++q) s_red[wn][lane][k * 8 + q] = psum[k][q];
-    }
-    __syncthreads();
-    if (wm == 0) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int u = u0 + 8 * (k >> 2) + (k & 3) + 4 * half;
-            if (u < U1) {
-#pragma unroll
-                for (int g = 0; g < 2; ++g)
-                    if (colok[g]) {
-                        f32x4 o;
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) o[q] = psum[k][g * 4 + q] + s_red[wn][lane][k * 8 + g * 4 + q];
-                        *(f32x4 *)(a.slab_pred + (long)tt * BUH + ((long)b * U1 + u) * H + colg[g]) = o;
-                    }
-            }
-        }
+    {   // the shared epilogue: pred rows requested, drain, barrier, x (1 - hidden^2), the two slabs
+        typedef Bf16x3 F;
+        constexpr int MT = 2, NG = 2;
+        constexpr bool XWAVE = true;
+        const int mbase = 2 * wm, colbase = 512 * hp + 256 * wn;
+        float (*s_red)[64][65] = (float (*)[64][65])s_dh;  // the W ring is free behind the epilogue's barrier
+#include "split_dhidden_epilogue.inc"
     }
     if (FIRST) X_CLOCK_STAMP(128 + 110);
 }
