@@ -999,7 +999,7 @@ int rnnt_engine_encoder_train_bwd(const rnnt_encoder_layer *layers, int n_layers
  *                                                                                 F = n_filters, or the bins without one)
  * The window (win_length fp32 values on the device) is centred in n_fft with zeros, as torch.stft does.  center = 1 reflects
  * n_fft / 2 samples at both ends.  Frames per utterance of `len` samples, host arithmetic: (len - n_fft) / hop + 1 (0 below
- * n_fft), or len / hop + 1 with center.
+ * n_fft), or (len + 2 (n_fft / 2) - n_fft) / hop + 1 with center (integer divisions: len / hop + 1 for an even n_fft).
  *
  * rnnt_engine_featurizer_pack writes the windowed DFT basis once (rnnt_engine_featurizer_basis_bytes; 16-byte aligned); the
  * other calls read it.  rnnt_engine_featurizer_fwd: N waveforms of T samples, wave_stride samples apart, fp32

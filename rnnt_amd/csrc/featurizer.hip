@@ -78,7 +78,7 @@ __device__ __forceinline__ float feat_tail(const FeatTail &t, float p, int k)
 
 __device__ __forceinline__ int feat_count(long len, int n_fft, int hop, int center)
 {
-    if (center) return (int)(len / hop) + 1;
+    if (center) return (int)((len + 2 * (n_fft / 2) - n_fft) / hop) + 1;
     return len >= n_fft ? (int)((len - n_fft) / hop) + 1 : 0;
 }
 
@@ -261,7 +261,7 @@ int check_desc(const rnnt_featurizer_desc *d, Geo &g)
 
 inline long frames_of(const rnnt_featurizer_desc *d, long len)
 {
-    if (d->center) return len / d->hop_length + 1;
+    if (d->center) return (len + 2 * (d->n_fft / 2) - d->n_fft) / d->hop_length + 1;
     return len >= d->n_fft ? (len - d->n_fft) / d->hop_length + 1 : 0;
 }
 

@@ -11,7 +11,8 @@ engine path takes fp32 or int16 samples on a HIP device; `backend` ("auto" | "to
 where it does not apply.  The modules hold no parameters and run under no_grad.
 
 Definition.  Frame f covers samples f * hop .. f * hop + n_fft - 1 (of the signal reflected by n_fft / 2 at both ends when
-`center`); an utterance of `len` samples has (len - n_fft) // hop + 1 frames (0 below n_fft), or len // hop + 1 centred.  The
+`center`); an utterance of `len` samples has (len - n_fft) // hop + 1 frames (0 below n_fft), or (len + 2 * (n_fft // 2) - n_fft) // hop + 1
+centred (torch.stft's count: len // hop + 1 for an even n_fft, (len - 1) // hop + 1 for an odd one).  The
 power |stft|^2 (periodic Hann window of win_length, centred in n_fft) goes through an optional filterbank, one of three log
 stages and (v - mean) * invstddev per bin.  Streaming: the state is the samples not yet consumed, (N, len) fp32; a push reads
 state followed by chunk, emits the frames they complete and keeps the samples from frames * hop on.  Every length is host
@@ -41,7 +42,7 @@ class _Desc(ctypes.Structure):  # include/rnnt_engine.h: rnnt_featurizer_desc
 def frame_count(length, n_fft, hop_length, center=False):
     """Frames of an utterance of `length` samples."""
     if center:
-        return length // hop_length + 1
+        return (length + 2 * (n_fft // 2) - n_fft) // hop_length + 1
     return (length - n_fft) // hop_length + 1 if length >= n_fft else 0
 
 

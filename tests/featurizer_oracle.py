@@ -13,7 +13,7 @@ INT16_GAIN = pow(10, 0.05 * (2 * 20 * math.log10(32767)))
 
 def frame_count(length, n_fft, hop, center=False):
     if center:
-        return length // hop + 1
+        return (length + 2 * (n_fft // 2) - n_fft) // hop + 1
     return 0 if length < n_fft else (length - n_fft) // hop + 1
 
 

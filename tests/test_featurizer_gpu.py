@@ -9,64 +9,12 @@ import pytest
 import torch
 
 from tests import featurizer_oracle as fo
-from tests.featurizer_cases import REF, SMALL, e2e_audio_case, noise, per_bin, to_int16
+from tests.featurizer_cases import KINDS, STREAMS, e2e_audio_case, noise, per_bin, to_int16
+from tests.featurizer_cases import as64 as _as64, check as _check, engine_run as _engine, oracle_kw as _kw, stream as _stream, torch32 as _torch32
 
 pytestmark = pytest.mark.gpu
 
-FACTOR = 4.0
 TILE = 32  # featurizer.hip: frames per workgroup tile (the MFMA's 32 columns)
-KINDS = {0: fo.PLAIN, 1: fo.PIECEWISE, 2: fo.GAIN}  # RNNT_FEAT_LOG_*
-
-
-def _check(label, got, want64, torch32):
-    want64 = torch.as_tensor(want64)
-    assert tuple(got.shape) == tuple(want64.shape), (label, got.shape, want64.shape)
-    err = float((got.double().cpu() - want64).abs().max())
-    ref = float((torch32.double().cpu() - want64).abs().max())
-    print(f"featurizer parity {label}: engine max|y - fp64| = {err:.3e}, torch fp32 error = {ref:.3e}, bar = {FACTOR * ref:.3e}")
-    assert torch.isfinite(got).all() and err <= FACTOR * ref, label
-    return err, ref
-
-
-def _kw(mod):
-    """The oracle's arguments for a module."""
-    mean = mod.mean if isinstance(mod.mean, float) else mod.mean.tolist()
-    inv = mod.invstddev if isinstance(mod.invstddev, float) else mod.invstddev.tolist()
-    kw = dict(n_fft=mod.n_fft, hop=mod.hop_length, win_length=mod.win_length, kind=KINDS[mod.log_kind], mean=mean, invstd=inv)
-    if mod.center:
-        kw["center"] = True
-    if mod.fbank is not None:
-        kw["fbank"] = fo.htk_fbank(mod.n_fft // 2 + 1, mod.f_min, mod.f_max, mod.n_mels, mod.sample_rate)
-    return kw
-
-
-def _as64(x):
-    return x.double() / 32768.0 if x.dtype == torch.int16 else x.double()
-
-
-def _torch32(mod, x):
-    """The module's torch path in fp32 on the CPU (list: ragged)."""
-    mod.backend = "torch"
-    try:
-        y = mod(x)
-        assert mod.last_backend == "torch"
-        return y[0] if isinstance(x, list) else y
-    finally:
-        mod.backend = "auto"
-
-
-def _engine(mod, x, **attrs):
-    mod.backend = "engine"
-    for k, v in attrs.items():
-        setattr(mod, k, v)
-    try:
-        y = mod(x)
-        assert mod.last_backend == "engine"
-        return y
-    finally:
-        mod.backend = "auto"
-        for k in attrs:
-            setattr(mod, k, False)
 
 
 def _ref_module(kind=1, scalar=False):
@@ -153,30 +101,6 @@ def test_small_config_filterbank_centred(kind):
     _check(f"64/16/48 mel ragged centred, log kind {KINDS[kind]}", got, want, _torch32(mod, waves))
     with pytest.raises(ValueError, match="reflect"):
         _engine(mod, noise(32, 1).cuda())
-
-
-def _stream(mod, x, sizes, backend="engine", state=None):
-    """Push x (N, time) chunk by chunk; ([feature blocks], final state).  Every input state is checked to be left as it was."""
-    mod.backend = backend
-    try:
-        if state is None:
-            state = mod.streaming_init_state(x.shape[0]).to(x.device)
-        outs, t = [], 0
-        for k in sizes:
-            before = state.clone()
-            y, new = mod.streaming_forward(x[:, t:t + k], state)
-            assert mod.last_backend == backend
-            assert torch.equal(state, before)  # never written in place
-            assert new.shape[1] == 0 or new.data_ptr() != state.data_ptr()
-            outs.append(y)
-            state, t = new, t + k
-        return outs, state
-    finally:
-        mod.backend = "auto"
-
-
-STREAMS = {"edges": (REF, [399, 1, 160, 159, 1, 0, 2000], False), "1280": (REF, [1280] * 4, True),
-           "small": (SMALL, [47, 1, 16, 15, 1, 0, 300, 17], False), "trickle": (REF, [100] * 30, True)}
 
 
 @pytest.mark.parametrize("name", list(STREAMS))

@@ -18,8 +18,18 @@ def _wave(n, seed=0, sigma=0.01, tone=True):
     return x
 
 
-@pytest.mark.parametrize("n_fft,hop,win,center,n", [(400, 160, 400, False, 1200), (64, 16, 48, False, 200), (64, 16, 48, True, 40),
-                                                   (64, 16, 48, True, 200)])
+def _dft_cases():
+    """The tested geometries, each with 3 frames and half a hop; the reference's mel sizes centred at the shortest legal length
+    and at 6 frames."""
+    from tests.featurizer_cases import GEOMETRIES, REF_MEL
+    cases = [(400, 160, 400, False, 1200), (64, 16, 48, False, 200), (64, 16, 48, True, 40), (64, 16, 48, True, 200)]
+    cases += [(g.n_fft, g.hop, g.win, False, g.n_fft + 2 * g.hop + g.hop // 2) for g in GEOMETRIES.values()]
+    cases += [(REF_MEL["n_fft"], REF_MEL["hop_length"], REF_MEL["win_length"], True, n) for n in (257, 800)]
+    cases += [(65, 16, 49, True, 160), (65, 16, 49, True, 170)]
+    return cases
+
+
+@pytest.mark.parametrize("n_fft,hop,win,center,n", _dft_cases())
 def test_oracle_power_is_the_dft(n_fft, hop, win, center, n):
     x = _wave(n, seed=1, sigma=1.0)
     got = fo.power(x, n_fft, hop, win, center).numpy()
@@ -56,6 +66,54 @@ def test_frame_and_state_arithmetic():
         assert total == fo.frame_count(sum(sizes), 400, 160)
 
 
+@pytest.mark.parametrize("n_fft", (64, 65, 400, 401, 512))
+@pytest.mark.parametrize("hop", (1, 16, 17, 160))
+def test_frame_counts_are_the_frames_torch_stft_returns(n_fft, hop):
+    """The module's and the oracle's frame arithmetic against the frames torch.stft gives, centred and not.  Centred lengths start
+    just above the reflect pad and include len % hop in {0, 1, hop - 1}: for an odd n_fft the padded signal has len + n_fft - 1
+    samples, one frame fewer than len // hop + 1 whenever len % hop == 0."""
+    import rnnt_amd.featurizer as F
+    pad = n_fft // 2
+    window = torch.hann_window(n_fft, dtype=torch.float64)
+
+    def stft_frames(n, center):
+        return torch.stft(torch.zeros(n, dtype=torch.float64), n_fft, hop, n_fft, window=window, center=center, pad_mode="reflect",
+                          return_complex=True).shape[1]
+
+    first = (pad // hop + 1) * hop  # the first multiple of the hop above the pad
+    centred = {pad + 1, pad + 2, first, first + 1, first + hop - 1, first + hop, first + 5 * hop, first + 5 * hop + 1,
+               first + 6 * hop - 1, n_fft - 1, n_fft, n_fft + 1, 3 * n_fft}
+    assert {n % hop for n in centred} >= {0, 1 % hop, hop - 1}
+    for n in sorted(centred):
+        assert n > pad
+        assert F.frame_count(n, n_fft, hop, True) == fo.frame_count(n, n_fft, hop, True) == stft_frames(n, True), (n, n_fft, hop)
+    for n in (n_fft, n_fft + 1, n_fft + hop - 1, n_fft + hop, n_fft + 5 * hop, n_fft + 6 * hop - 1, 3 * n_fft):
+        assert F.frame_count(n, n_fft, hop) == fo.frame_count(n, n_fft, hop) == stft_frames(n, False), (n, n_fft, hop)
+    assert F.frame_count(n_fft - 1, n_fft, hop) == fo.frame_count(n_fft - 1, n_fft, hop) == 0
+
+
+def test_odd_n_fft_centred_ragged_torch_path():
+    """65 / 16 / 49 centred with 10 mels: 160 samples (len % hop == 0) give the 10 frames torch.stft returns, and the ragged call
+    runs and equals the oracle."""
+    import rnnt_amd
+    mod = rnnt_amd.NormalizedMelSpectrogram(True, 1.0, 0.5, sample_rate=16000, n_fft=65, win_length=49, hop_length=16, f_min=20.0,
+                                            f_max=7600.0, n_mels=10)
+    kw = dict(n_fft=65, hop=16, win_length=49, kind=fo.GAIN, mean=1.0, invstd=0.5, center=True, fbank=fo.htk_fbank(33, 20.0, 7600.0, 10, 16000))
+    waves = [_wave(160, seed=20), _wave(170, seed=21), _wave(33, seed=22), _wave(800, seed=23)]
+    got, counts = mod(waves)
+    want, want_counts = fo.ragged(waves, **kw)
+    assert mod.last_backend == "torch" and counts.tolist() == want_counts == [10, 11, 3, 50]
+    assert got.shape == want.shape and float((got - want).abs().max()) <= 1e-11 * max(1.0, float(want.abs().max()))
+    for j, c in enumerate(want_counts):
+        assert not got[j, :, c:].any()
+    for w, c in zip(waves, want_counts):
+        assert mod(w[None]).shape == (1, 10, c)
+    # 401 / 160 / 401 with 800 samples, the reference's spectrogram sizes made odd
+    mod = rnnt_amd.NormalizedMelSpectrogram(n_fft=401, hop_length=160, n_mels=20)
+    got, counts = mod([_wave(800, seed=24), _wave(801, seed=25)])
+    assert counts.tolist() == [5, 6] and got.shape == (2, 20, 6) and not got[0, :, 5:].any()
+
+
 @pytest.mark.parametrize("name", list(CHUNKINGS))
 def test_oracle_chunked_equals_whole(name):
     sizes = CHUNKINGS[name]
@@ -77,10 +135,13 @@ def _modules():
         (rnnt_amd.NormalizedMelSpectrogram(True, 1.0, 0.5, sample_rate=16000, n_fft=64, win_length=48, hop_length=16, f_min=20.0, f_max=7600.0,
                                            n_mels=10),
          dict(n_fft=64, hop=16, win_length=48, kind=fo.GAIN, mean=1.0, invstd=0.5, center=True, fbank=fo.htk_fbank(33, 20.0, 7600.0, 10, 16000))),
+        # the reference's main configuration, as config/basic_sp.yaml states it
+        (rnnt_amd.NormalizedMelSpectrogram(n_fft=512, win_length=400, hop_length=160, n_mels=80, f_min=0, f_max=8000, mean=15.0, invstddev=0.25),
+         dict(n_fft=512, hop=160, win_length=400, kind=fo.GAIN, mean=15.0, invstd=0.25, center=True, fbank=fo.htk_fbank(257, 0, 8000, 80, 16000))),
     ]
 
 
-@pytest.mark.parametrize("i", range(4))
+@pytest.mark.parametrize("i", range(5))
 def test_module_torch_path_in_float64_is_the_oracle(i):
     mod, kw = _modules()[i]
     x = _wave(1500, seed=3 + i)
@@ -91,7 +152,7 @@ def test_module_torch_path_in_float64_is_the_oracle(i):
     assert got.shape == want.shape
     assert float((got - want).abs().max()) <= 1e-11 * max(1.0, float(want.abs().max()))
     # batched, and ragged with an utterance shorter than a frame (0 frames; centred: no such utterance)
-    short = 70 if kw.get("center") else 30
+    short = kw["n_fft"] // 2 + 38 if kw.get("center") else 30
     waves = [x, x[:901], x[:short]]
     got_r, counts = mod(waves)
     want_r, want_counts = fo.ragged(waves, **kw)
@@ -111,6 +172,17 @@ def test_mel_filterbank_is_the_published_formula():
     want = fo.htk_fbank(201, 0.0, 8000.0, 80, 16000)
     assert got.shape == (201, 80) and float((got - want).abs().max()) < 1e-12
     assert (got >= 0).all() and float(got.max()) <= 1.0 and (got.sum(0) > 0).all()
+
+
+def test_reference_mel_filterbank():
+    """The filterbank of the reference's main configuration (257 bins, 0 - 8000 Hz, 80 mels): the published formula, no empty filter."""
+    from tests.featurizer_cases import ref_mel_module
+    mod = ref_mel_module()
+    want = fo.htk_fbank(257, 0, 8000, 80, 16000)
+    assert (mod.n_fft, mod.win_length, mod.hop_length, mod.center, mod.n_features) == (512, 400, 160, True, 80)
+    assert mod.fbank.shape == (257, 80) and mod.fbank.dtype == torch.float64
+    assert float((mod.fbank - want).abs().max()) < 1e-12
+    assert int((mod.fbank.sum(0) == 0).sum()) == 0 and (mod.fbank >= 0).all() and float(mod.fbank.max()) <= 1.0
 
 
 def test_module_streaming_torch_path():
