@@ -30,6 +30,7 @@
 // fragments are consumed, so staging a chunk is a linear copy L2 -> VGPR -> LDS.
 #include "kernels.hpp"
 #include "mma_common.hpp"
+#include "split_dw.hpp"
 
 typedef short i16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) i16x4 *lds_i16x4_ptr;
@@ -1081,32 +1082,28 @@ void launch_dhidden_bf16(const Bf16Args &a, hipStream_t st)
 // s_waitcnt vmcnt(16) + one barrier per stage publishes a stage.
 // The bias gradient rides the matrix pipe: an extra B fragment of ones (column 0).
 // ---------------------------------------------------------------------------------------
-#define BW_ROWS 32   // cells per stage (2 MFMA k-steps)
-#define BW_NST 4     // ring stages
+// Tile decode, operand source, swizzled source offsets, the DMA ladder, fragment offsets, the split's share (DwShare) and the dW store are
+// split_dw.hpp's; the range walk and the lockstep are spelled here (why: at the walk, and DESIGN.md §4f); the schedule below — 32-row stages ([slot][operand tile][32 x 256 B]), two k-steps per stage, the X / Y fragment double
+// buffer, mma_step with four pieces, db from v_dot2c sums — is this kernel's own.
+#define BW_ROWS DW_GRAN  // cells per stage (2 MFMA k-steps): one granule of the live-row table
+#define BW_NST 4         // ring stages
+static_assert((BW_NST - 1) * BW_ROWS <= DW_ROWS_PAST, "read-ahead of the ring past the last live row");
+// a stage is two 16-row operand tiles = 2 ND pieces per wave: the prologue's wait leaves the NST - 2 stages behind stage 0 in flight (16),
+// the loop's wait the one stage behind stage st + 1 and the 4 pieces just issued (12)
+typedef DwRing<Bf16x1, BW_NST> BWR;
+static_assert(2 * BWR::ND == 8 && 2 * BWR::ND * (BW_NST - 2) == 16 && 2 * BWR::ND * (BW_NST - 3) + 4 == 12, "the counted waits");
 
 __global__ __launch_bounds__(256, 1) void k_dw_bf16(Bf16Args a)
 {
     extern __shared__ __attribute__((aligned(1024))) char s_ring[];  // BW_NST x 4 tiles x 8 KiB
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
     const int half = lane >> 5;
     const int H = a.H, V = a.V;
-    const int n_vblk = (V + 255) / 256, n_hblk = (H + 255) / 256;
-    const int tiles = n_vblk * n_hblk;
-    const int total = tiles * a.n_split;
-    int id = blockIdx.x;  // XCD-aware remap: the tiles of one split share an XCD's L2
-    {
-        const int q8 = total / 8, r8 = total % 8, x = id % 8;
-        id = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + id / 8;
-    }
-    const int tile = id % tiles, split = id / tiles;
-    const int vb = tile / n_hblk, hb = tile % n_hblk;
+    const DwTile tl = dw_tile(blockIdx.x, wave, H, V, a.n_split);
+    const int wm = tl.wm, wn = tl.wn, tile = tl.tile, tiles = tl.tiles, split = tl.split, hb = tl.hb;
     // this split's share of the LIVE 32-cell stages (k_dw_table): a ragged batch costs its lengths
-    const long *tab = a.dw_tab;
-    const int B = a.B;
-    const long nlive = tab[2 * B + 1];
-    const long g_lo = nlive * split / a.n_split, g_hi = nlive * (split + 1) / a.n_split;
+    const DwShare share = dw_share(a.dw_tab, a.B, split, a.n_split);
     BF_CLOCK_STAMP(308);
 
     f32x16 acc[4][4];
@@ -1122,39 +1119,31 @@ __global__ __launch_bounds__(256, 1) void k_dw_bf16(Bf16Args a)
     float dbl[4] = {0.f, 0.f, 0.f, 0.f};
     const unsigned one_pair_u = 0x3f803f80u;  // (1.0bf16, 1.0bf16)
 
-    if (g_hi > g_lo) {
+    if (share.g_hi > share.g_lo) {
         // ---- DMA source of this wave's operand tile: wave 0/1 -> G column halves, 2/3 -> hidden
         const bool is_g = wave < 2;
-        int col0 = (is_g ? vb : hb) * 256 + 128 * (wave & 1);
-        if (col0 >= (is_g ? V : H)) col0 = 0;  // tile beyond the matrix: never stored, read something valid
-        const long rstride = is_g ? 2L * V : 2L * H;  // bytes between cells
-        const char *src0 = (is_g ? (const char *)a.logits : (const char *)a.hidden) + 2L * col0;
+        DwSource<Bf16x1> srcs;
+        dw_source(srcs, a, is_g, dw_col0(is_g, is_g ? tl.vb : hb, wave & 1, H, V));
+        const long rstride = srcs.rstride[0];  // bytes between cells
+        const char *src0 = srcs.pbase[0];
         const char *src = src0;  // + the first row of the range being walked
-        // DMA i (0..7) of a stage: rows 4i .. 4i+3; lane L: row 4i + (L>>4), LDS chunk position L&15
-        // <- global chunk (L&15) ^ swz(row), swz = ((L>>4)<<2) | (i&3)
+        // DMA i (0..7) of a stage: rows 4i .. 4i+3
         int soff[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
-            soff[i] = (int)((4 * i + (lane >> 4)) * rstride) + 16 * ((lane & 15) ^ (((lane >> 4) << 2) | (i & 3))) - 1024 * (i & 3);
+        for (int i = 0; i < 8; ++i) soff[i] = dw_soff(lane, i, 4 * i, rstride, false, 1024 * (i & 3));
         // (round 5: pieces 4g .. 4g+3 share one LDS base (M0) and carry the immediate offset 1024 (i & 3), which advances the memory address
         // too — taken back out of the per-lane offset above: rstride >= 256 bytes, so 4 i rows >= 1024 (i & 3) bytes)
         // (raw-buffer form: the 32 rows of a stage as a buffer with a wave-uniform base — scalar arithmetic only; the
         // per-lane part of an address is the 32-bit soff.  A global_load_lds with a 64-bit per-lane address costs the
         // issuing wave more: measured on the bf16x3 forward)
         auto stage_rsrc = [&](long st) {
-            return __builtin_amdgcn_make_buffer_rsrc((void *)(src + st * (BW_ROWS * rstride)), 0, (int)(BW_ROWS * rstride), 0x00020000);
+            return dw_rows_rsrc(src, st * BW_ROWS, rstride, BW_ROWS);
         };
         auto dma_stage = [&](long st, int slot) {
             const __amdgpu_buffer_rsrc_t r = stage_rsrc(st);
             char *dst = s_ring + slot * 32768 + wave * 8192;
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                lds_vptr d4 = (lds_vptr)(dst + 4096 * (i >> 2));
-                if ((i & 3) == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d4, 16, soff[i], 0, 0, 0);
-                if ((i & 3) == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d4, 16, soff[i], 0, 1024, 0);
-                if ((i & 3) == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d4, 16, soff[i], 0, 2048, 0);
-                if ((i & 3) == 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d4, 16, soff[i], 0, 3072, 0);
-            }
+            for (int i = 0; i < 8; ++i) dw_dma_imm(r, (lds_vptr)(dst + 4096 * (i >> 2)), soff[i], i);
         };
         // ---- transposed fragment reads.  Fragment of 32-column tile m, k-step ks: lane
         // (g = lane>>4, q = (lane&15)>>2, p = lane&3) reads rows 16ks + 8(g>>1) + 4sec + q at
@@ -1162,25 +1151,15 @@ __global__ __launch_bounds__(256, 1) void k_dw_bf16(Bf16Args a)
         // The reads are inline asm: hipcc guards every LDS read it can see that follows an
         // LDS-DMA with s_waitcnt vmcnt(0), which would drain the ring each stage.  Their
         // results are only used after frag_wait(), which names them as in/out operands.
-        const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3, hh = g >> 1;
-        int foff[4][2];
+        int foff[4][2];  // (+ 16 ks rows)
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
-            for (int sec = 0; sec < 2; ++sec) {
-                const int row = 8 * hh + 4 * sec + q;  // + 16ks
-                const int ch = 4 * m + 2 * (g & 1) + (p >> 1);
-                const int swz = ((row & 3) << 2) | ((row >> 2) & 3);
-                foff[m][sec] = 256 * row + 16 * (ch ^ swz) + 8 * (p & 1);
-            }
+            for (int sec = 0; sec < 2; ++sec) foff[m][sec] = dw_frag_off(m, sec, lane);
         const int lds0 = (int)(size_t)(lds_vptr)s_ring;  // LDS byte address of the ring
         const int a_tile = lds0 + wm * 8192, b_tile = lds0 + 16384 + wn * 8192;
         auto dma_piece = [&](long st, int slot, int i) {  // (i: a constant once the caller's loop is unrolled)
-            lds_vptr d4 = (lds_vptr)(s_ring + slot * 32768 + wave * 8192 + 4096 * (i >> 2));
-            if ((i & 3) == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(stage_rsrc(st), d4, 16, soff[i], 0, 0, 0);
-            if ((i & 3) == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(stage_rsrc(st), d4, 16, soff[i], 0, 1024, 0);
-            if ((i & 3) == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(stage_rsrc(st), d4, 16, soff[i], 0, 2048, 0);
-            if ((i & 3) == 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(stage_rsrc(st), d4, 16, soff[i], 0, 3072, 0);
+            dw_dma_imm(stage_rsrc(st), (lds_vptr)(s_ring + slot * 32768 + wave * 8192 + 4096 * (i >> 2)), soff[i], i);
         };
         struct Frags { u32x2 al[4], ah[4], bl[4], bh[4]; };
         auto reads = [&](Frags &f, int slot, int ks) {  // 16 transposed reads, NOT waited for
@@ -1249,6 +1228,11 @@ __global__ __launch_bounds__(256, 1) void k_dw_bf16(Bf16Args a)
         const int *nb = prog ? prog + (tile + 1 < tiles ? tile + 1 : 0) : nullptr;  // the neighbour's word
         int nb_at = 0x7fffffff;  // the neighbour's stage count as of the last look
         int done = 0;  // stages behind this workgroup, over all ranges
+        // the walk of the live-row table (dw_walk_ranges' loop, spelled here: as a callable's body the k loop below changes its
+        // exit test and the nap counter moves to a vector register — profiles/dw_toolkit_isa.txt)
+        const long *tab = share.tab;
+        const int B = share.B;
+        const long nlive = share.nlive, g_lo = share.g_lo, g_hi = share.g_hi;
         int ub = 0;
         while (ub + 1 < B && tab[B + 1 + ub + 1] <= g_lo) ++ub;  // utterance holding live stage g_lo
         for (long gq = g_lo; gq < g_hi; ++ub) {  // workgroup-uniform: one pipeline run per live range
@@ -1305,21 +1289,8 @@ __global__ __launch_bounds__(256, 1) void k_dw_bf16(Bf16Args a)
     // ---- epilogue: partial slab [split][V,H]; bias partial [split][V].  Accumulator register r
     // of tile (qm,qn): v = v0 + 32qm + (r&3) + 8(r>>2) + 4half, h = h0 + 32qn + (lane&31).
     BF_CLOCK_STAMP(310);
-    const int v0 = vb * 256 + wm * 128, h0 = hb * 256 + wn * 128;
-    float *sw = a.slab_w + (long)split * V * H;
-#pragma unroll
-    for (int qm = 0; qm < 4; ++qm)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int v = v0 + 32 * qm + (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (v < V) {
-#pragma unroll
-                for (int qn = 0; qn < 4; ++qn) {
-                    const int h = h0 + 32 * qn + (lane & 31);
-                    if (h < H) sw[(long)v * H + h] = acc[qm][qn][r];
-                }
-            }
-        }
+    const int v0 = tl.v0;
+    dw_store_w<true, false>(a.slab_w, split, H, V, v0, tl.h0, lane, acc, 1.f);
     if (do_b) {  // lane (v = l&31, half) summed the cells 8*half .. 8*half+7 of every k-step
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
@@ -1332,7 +1303,7 @@ __global__ __launch_bounds__(256, 1) void k_dw_bf16(Bf16Args a)
 
 void launch_dw_bf16(const Bf16Args &a, hipStream_t st)
 {
-    launch_dw_table(a.logit_lens, a.B, a.T, a.U1, BW_ROWS, a.dw_tab, st);
+    launch_dw_table(a.logit_lens, a.B, a.T, a.U1, DW_GRAN, a.dw_tab, st);
     const int tiles = ((a.V + 255) / 256) * ((a.H + 255) / 256);
     static LdsOptIn lds_opt_in;
     lds_opt_in.raise(BW_NST * 32768, k_dw_bf16);

@@ -123,8 +123,8 @@ int dw_splits(int B, int T, int H, int V, int dtype)
     return (int)s;
 }
 
-// forward row tiles of 128; the dW DMA ring over-reads up to 96 (zero) rows past rows_pad
-long bf16_rows_alloc(size_t rows_pad) { return (long)((rows_pad + 96 + 127) / 128 * 128); }
+// forward row tiles of 128; the dW DMA rings over-read up to DW_ROWS_PAST (zero) rows past rows_pad
+long bf16_rows_alloc(size_t rows_pad) { return (long)((rows_pad + DW_ROWS_PAST + 127) / 128 * 128); }
 
 void layout(int B, int T, int U1, int H, int V, int dtype, rnnt_engine_ws_layout *L)
 {

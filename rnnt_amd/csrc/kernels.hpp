@@ -116,6 +116,11 @@ void launch_dhidden(const JointBwdArgs &a, bool tile_kernel, hipStream_t st);
 void launch_dw(const JointBwdArgs &a, hipStream_t st);
 int dw_tiles(int H, int V);  // workgroup tiles per split of k_dw
 void launch_dw_table(const int32_t *logit_lens, int B, int T, int U1, int gran, long *tab, hipStream_t st);
+// the dW GEMMs of the MFMA routes (split_dw.hpp): cells per granule of their live-row table; rows their DMA rings may read past rows_pad
+// (zero padding rows, bf16_rows_alloc: k_dw_bf16 three stages of 32, k_dw_x3 two k-steps of 16, k_dw_x2 none past its lists' padding
+// entries) — each kernel asserts its read-ahead against it
+#define DW_GRAN 32
+#define DW_ROWS_PAST 96
 size_t dw_list_bytes(int B, int T, int U1, int gran);  // bytes of the live-granule region of launch_dw
 void launch_dhidden_reduce(const JointBwdArgs &a, hipStream_t st);
 void launch_dw_reduce(const JointBwdArgs &a, hipStream_t st);
@@ -144,9 +149,9 @@ struct Bf16Args {
     int B, T, U1, H, V, blank;
     int n_ublk, n_split;
     int ablate;  // diagnostic builds: the ablation word of rnnt_engine_set_flags (RNNT_XP; bits 8..: 256 no stores, 512 no statistics, 1024 no MFMA), nothing else
-    long *dw_tab;  // 2B+2 longs: live-row table of k_dw_bf16 (k_dw_table, 32-cell granules)
+    long *dw_tab;  // 2B+2 longs: live-row table of k_dw_bf16 (k_dw_table at DW_GRAN cells per granule; walked as split_dw.hpp's DwShare)
     unsigned long long *debug;  // diagnostic stamp buffer (RNNT_STAMPS builds), else NULL
-    int *dw_prog;  // [n_split][16] progress words of k_dw_bf16's tiles (zeroed by its launcher), or NULL
+    int *dw_prog;  // [n_split][16] progress words of the soft lockstep of k_dw_bf16's tiles: stages done over all ranges, 0x7fffffff at the end (zeroed by its launcher), or NULL
 };
 size_t bf16_wpack_fwd_bytes(int H, int V);
 size_t bf16_wpack_dh_bytes(int H, int V);
@@ -177,7 +182,7 @@ struct X3Args {
     int n_ublk, n_split;
     int n_ublk16;        // u blocks of k_dhidden_x3 (16 wide)
     int ablate;          // diagnostic builds: the ablation word of rnnt_engine_set_flags (RNNT_XP), nothing else
-    long *dw_tab;        // 2B+2 longs: live-row table of k_dw_x3 (k_dw_table, 32-cell granules)
+    long *dw_tab;        // 2B+2 longs: live-row table of k_dw_x3 (k_dw_table at DW_GRAN cells per granule; split_dw.hpp: DwShare, dw_walk_ranges)
     unsigned *counter;   // zeroable word: tile counter of the persistent forward
     int n_cu;
     unsigned long long *debug;  // diagnostic stamp buffer (RNNT_STAMPS builds), else NULL
@@ -185,7 +190,7 @@ struct X3Args {
     float g_scale;              // power of two with |g_scale G| <= 2^13 (from grad_scale)
     float dw_rescale, db_rescale;  // 1 / (g_scale 2^14), 1 / g_scale
     const float *scales;        // device: {s_W, 1 / s_W} (k_x2_wscale, every call)
-    int *dw_prog;               // [n_split][16] progress words of k_dw_x2's tiles (zeroed by its launcher), or NULL
+    int *dw_prog;               // [n_split][16] progress words of k_dw_x2's / k_dw_x2m's tiles (split_dw.hpp: DwLockstep; k-steps of the pipeline run; zeroed by the launcher), or NULL
     float *ep_enc, *ep_pred;    // exp(2 enc) [B][H/16][T][16], exp(2 pred) [B][H/16][U1][16] (k_x2_make_ep, every call)
     unsigned *ep_flag;          // device word: != 0 when an input lies outside the factored tanh's range (the exact forward runs)
     // live structures of the backward (launch_x2_live, after the coefficients; x2.hip "flush rule"); the Linear layer's dW sets ks_list / grp_list / live_stats only

@@ -9,7 +9,9 @@
 //   split2(a, b)            two (prepared) fp32 values -> their pieces, packed pairwise (element 0 in the low half)
 //   split4(x4, planes.., d) four consecutive values -> 2 packed dwords per plane at dword positions d, d+1 of the plane vectors,
 //                           the planes as separate vectors or as one array u32x4[NP]
-//   mfma(a, b, c)           its 32x32x16 MFMA
+//   mfma(a, b, c)           its 32x32x16 MFMA; mfma_v(c, a, b): the same with the accumulator held in VGPRs, spelled as asm (left to hipcc an
+//                           accumulator tile beside 256 others is shuttled through the full AGPR file); ONES: a pair of its ones
+//   SCALED                  its operands carry scales: sums of products are rescaled where they leave (X3Args::dw_rescale, db_rescale)
 //   split_g4(g4, gs, p, d)  split4 of four values of G, gs = X3Args::g_scale (a format without a scale ignores it; no clamp: |G| <= grad_scale)
 //   dh_unscale(a)           what dHidden's sums are multiplied by: 4 (its tanh' form) over the operands' scales
 #pragma once
@@ -45,6 +47,9 @@ struct Bf16x3 {
     template <class X4> static __device__ __forceinline__ void split_g4(const X4 &g4, float, u32x4 (&p)[NP], int d) { split4(g4, p, d); }
     static __device__ __forceinline__ float dh_unscale(const X3Args &) { return 4.0f; }
     static __device__ __forceinline__ f32x16 mfma(u32x4 a, u32x4 b, f32x16 c) { return mfma_bf16(a, b, c); }
+    static constexpr bool SCALED = false;
+    static constexpr unsigned ONES = 0x3f803f80u;
+    static __device__ __forceinline__ void mfma_v(f32x16 &c, u32x4 a, u32x4 b) { asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b)); }
 };
 
 // f16x2: x = (hi + mid) / s, hi = f16(s x), mid = f16(s x - hi) (RNE each), s a power of two that lifts the operand's largest magnitude to
@@ -92,6 +97,9 @@ struct F16x2 {
     }
     static __device__ __forceinline__ float dh_unscale(const X3Args &a) { return 4.0f * a.db_rescale * a.scales[1]; }  // 4 / (g_scale s_W)
     static __device__ __forceinline__ f32x16 mfma(u32x4 a, u32x4 b, f32x16 c) { return mfma_f16(a, b, c); }
+    static constexpr bool SCALED = true;
+    static constexpr unsigned ONES = 0x3c003c00u;
+    static __device__ __forceinline__ void mfma_v(f32x16 &c, u32x4 a, u32x4 b) { asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b)); }
 };
 
 // ---------------------------------------------------------------------------------------

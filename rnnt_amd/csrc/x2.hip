@@ -25,10 +25,11 @@
 // MFMA operand maps (v_mfma_f32_32x32x16_f16, as the bf16 form): lane l = (r = l&31, h = l>>5) holds A[row r][k = 8h+j] and
 // B[k = 8h+j][col r], j = 0..7; C/D: col = l&31, row = (reg&3) + 8*(reg>>2) + 4*(l>>5).
 #include "split_dhidden.hpp"
+#include "split_dw.hpp"
 
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 
-#define XW2_ROWS 16  // cells per dW k-step (the live structures below are built in these units)
+#define XW2_ROWS DW_ROWS  // cells per dW k-step (the live structures below are built in these units)
 #define XG2_BT 8     // the dHidden tile: 8 t x 16 u cells
 #define XG2_BU 16
 
@@ -115,7 +116,7 @@ size_t x2_wpack_dh_bytes(int H, int V) { return split_wpack_dh_bytes<F16x2>(H, V
 #define XL2_BLK 1024
 __device__ __forceinline__ bool x2_coef_live(const CellCoef &c) { return !(c.c1 == RNNT_NEG_INF && c.sb == 0.f && c.se == 0.f); }
 namespace {
-#define XL2_GPAD 32  // padding entries behind the group list (k_dw_x2 reads up to 4 XW2_NST + 3 entries past the live ones: asserted there)
+#define XL2_GPAD 32  // padding entries behind the group list (k_dw_x2 reads up to 4 XW2::NST + 3 entries past the live ones: asserted there)
 struct X2LiveWs { size_t tiles, bitmap, blk, list, tlist, gbitmap, gblk, glist, total; long nks, ntile; int nblk; };
 X2LiveWs x2_live_layout(int B, int T, int U1, long rows_pad)
 {
@@ -347,7 +348,7 @@ void launch_dw_reduce_x2(const X3Args &a, float *grad_W, float *grad_bias, hipSt
 // k_dw_x2: dW[v,h] = sum_c G[c,v] hidden[c,h] (split-K slabs), db[v] = sum_c G[c,v] — k_dw_x3's design on two planes:
 // 4 waves = 2 (M) x 2 (N), workgroup tile 256 v x 256 h, wave 128 x 128 = 16 accumulator tiles (256 registers).  Both
 // operands row-major with K (the cell) as the ROW, two fp16 planes each:
-//  * HBM -> LDS by LDS-DMA, ring of XW2_NST (4) stages of 16 cells x (256 v + 256 h) x 2 planes = 32 KiB; wave w fills operand tile w
+//  * HBM -> LDS by LDS-DMA, ring of XW2::NST (4) stages of 16 cells x (256 v + 256 h) x 2 planes = 32 KiB; wave w fills operand tile w
 //    (0,1: the 128-column halves of the G tile, 2,3: of the hidden tile), 8 DMAs of 1 KiB (4 rows x 256 B) per stage;
 //  * LDS -> VGPR by ds_read_b64_tr_b16 (4x16 transpose read): two reads give a lane its 8 consecutive cells of one column;
 //  * tile image: 256-byte rows, 16-byte chunk ch of row r at 16*(ch ^ swz(r)), swz(r) = ((r&3)<<2) | ((r>>2)&3), applied
@@ -363,11 +364,11 @@ void launch_dw_reduce_x2(const X3Args &a, float *grad_W, float *grad_bias, hipSt
 // is unconditional and in one order, the counted waits do not know the difference).  Rows of a live group that belong to no live cell
 // hold zeros (k_dhidden_x2 writes them inside its live tiles, k_x2_dead_rows those of the tiles that are not live).
 // The accumulators hold g_scale x 2^14 x dW: the epilogue multiplies by X3Args::dw_rescale (a power of two).
+// The pieces of the kernel are split_dw.hpp's (ring geometry, sources, fragment addressing, the k-step on two planes, lockstep, ring driver,
+// store); what stands here is the group-list walk with its counted wait and the placement of the pieces.
 // ---------------------------------------------------------------------------------------
-#define XW2_NST 4   // ring stages: the DMAs of stage ks + NST - 1 are issued during k-step ks
-#define XW2_PLANE 4096            // one operand tile of one plane: 16 rows x 256 B
-#define XW2_STAGE (2 * XW2_PLANE)  // one stage of one operand tile
-#define XW2_TILE (XW2_NST * XW2_STAGE)  // ring of one operand tile: [stage][plane][16 x 256 B] = 24 KiB
+typedef DwRing<F16x2, 4> XW2;  // ring stages: the DMAs of stage ks + NST - 1 are issued during k-step ks; 4 x 8 KiB per operand tile
+typedef DwLockstep<6, XW2::NST> XW2Lockstep;  // lag 6 k-steps, a look every NST k-steps, the count of the one pipeline run
 
 // the four list entries of a k-step (X3Args::grp_list): ONE 16-byte scalar load, then WAIT (a counted vmcnt or nothing), then the wait for
 // the load itself — one statement, so that the entries have landed wherever they are named
@@ -379,222 +380,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t x2_piece_rsrc(const char *base
     return __builtin_amdgcn_make_buffer_rsrc((void *)(base + (unsigned long long)(unsigned)ent * gbytes - imm), 0, (int)gbytes + imm, 0x00020000);
 }
 
-// ---------------------------------------------------------------------------------------
-// The dW k-step pipeline: the pieces k_dw_x2<4>, k_dw_x2<4, true> and both tile kinds of k_dw_x2m are built from, each once.  A kernel keeps
-// what really differs — tile geometry and wave layout, which operand tile a wave stages and from where, its list walk with the counted
-// wait in front of it, dead tiles — and hands the pipeline two callables: the DMA pieces of a stage one by one (threaded through the
-// MFMAs), and all of them at once (prologue).
-// The pieces are plain `inline`, not __forceinline__: the regular inliner takes them bottom-up, as it took the lambdas they replace, and
-// k_dw_x2's k loops come out instruction for instruction as before; inlined by force (before any simplification) every k-step gained eight
-// v_mov of zeros for the db fragments (profiles/x2_dw_refactor_isa.txt).  Nothing here may stay a call: the accumulators go by reference.
-// ---------------------------------------------------------------------------------------
-// XCD-aware remap of the workgroup id: the tiles of one split share an XCD's L2
-__device__ inline int x2_dw_xcd_remap(int id, int total)
-{
-    const int q8 = total / 8, r8 = total % 8, x = id % 8;
-    return (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + id / 8;
-}
-// Transposed fragment reads.  Fragment of 32-column tile m of operand tile otile: lane (g = lane>>4, q = (lane&15)>>2, p = lane&3) reads
-// rows 8(g>>1) + 4sec + q at chunk 4m + 2(g&1) + (p>>1), +8(p&1) bytes, sec = 0,1 — its LDS address in stage 0, plane 0 of the tile's ring
-// (lds0: the ring's), the chunk where the DMA's source-side swizzle put it
-__device__ inline int x2_dw_frag_addr(int lds0, int otile, int m, int sec, int lane)
-{
-    const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3, hh = g >> 1;
-    const int row = 8 * hh + 4 * sec + q;
-    const int swz = ((row & 3) << 2) | ((row >> 2) & 3);
-    const int ch = 4 * m + 2 * (g & 1) + (pp >> 1);
-    return lds0 + otile * XW2_TILE + 256 * row + 16 * (ch ^ swz) + 8 * (pp & 1);
-}
-// 2 NT transposed reads of plane P, ring stage ST (compile-time: every LDS offset is an immediate) of an operand (inline asm: hipcc guards
-// every LDS read it can see behind an LDS-DMA with vmcnt(0)); results are used only after FRAG8_LANDED named them
-template <int ST, int P, int NT>
-__device__ inline void x2_dw_reads(Frag8 &f, const int (&base)[4][2])
-{
-    constexpr int off = ST * XW2_STAGE + P * XW2_PLANE;
-#pragma unroll
-    for (int m = 0; m < NT; ++m) {
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.lo[m]) : "v"(base[m][0]), "n"(off));
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.hi[m]) : "v"(base[m][1]), "n"(off));
-    }
-}
-// 16 MFMAs of one product with the stage's DMA pieces N0 .. N0+CNT-1 (CNT <= 4) threaded through them, one per row of wave tiles: behind
-// row 0, 1 and 3, a fourth behind row 2.  dma_piece(Int<n>) issues piece n; live_n: this wave's h columns exist (wave-uniform)
-template <int N0, int CNT, class Piece>
-__device__ inline void x2_dw_product(f32x16 (&acc)[4][4], const Frag8 &fa_, const Frag8 &fb_, bool live_n, const Piece &dma_piece)
-{
-    u32x4 fa[4], fb[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        fa[m] = u32x4{fa_.lo[m][0], fa_.lo[m][1], fa_.hi[m][0], fa_.hi[m][1]};
-        fb[m] = u32x4{fb_.lo[m][0], fb_.lo[m][1], fb_.hi[m][0], fb_.hi[m][1]};
-    }
-#pragma unroll
-    for (int qm = 0; qm < 4; ++qm) {
-        if (live_n) {
-#pragma unroll
-            for (int qn = 0; qn < 4; ++qn) acc[qm][qn] = mfma_f16(fa[qm], fb[qn], acc[qm][qn]);
-        }
-        if (qm == 0 && CNT >= 1) dma_piece(Int<N0>{});
-        if (qm == 1 && CNT >= 2) dma_piece(Int<N0 + (CNT >= 2 ? 1 : 0)>{});
-        if (qm == 2 && CNT >= 4) dma_piece(Int<N0 + (CNT >= 4 ? 2 : 0)>{});
-        if (qm == 3 && CNT >= 3) dma_piece(Int<N0 + (CNT >= 3 ? CNT - 1 : 0)>{});
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-// db rides the matrix pipe as in k_dw_x3: one more MFMA per plane and k-step against a column SELECTOR of ones (sv: fp16 ones in the
-// selector's column), for one (one h block: two) of the wave's M tiles — fragment bases sbase — into a 17th accumulator tile held in VGPRs
-template <int ST, int P>
-__device__ inline void x2_dw_bias_read(u32x2 &lo, u32x2 &hi, const int (&sbase)[2])
-{
-    constexpr int off = ST * XW2_STAGE + P * XW2_PLANE;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(sbase[0]), "n"(off));
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(sbase[1]), "n"(off));
-}
-__device__ inline void x2_dw_bias_mfma(u32x2 &lo, u32x2 &hi, f32x16 &dacc, unsigned sv)
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo), "+v"(hi) :: "memory");
-    const u32x4 fa = {lo[0], lo[1], hi[0], hi[1]};
-    const u32x4 sel = {sv, sv, sv, sv};
-    // accumulator in VGPRs, spelled as asm (left to hipcc the 17th tile is shuttled through the full AGPR file)
-    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(dacc) : "v"(fa), "v"(sel));
-}
-// what a wave sums into db: nothing, the tile at sbase[0] (selector column 0), or with one h block (two_b, H <= 256 only) also the one at
-// sbase[1] (column 1)
-struct X2DwBias { bool do_b, two_b; unsigned sel0, sel1; int sbase[2][2]; };
-// One k-step on ring stage ST, behind the kernel's counted wait for the stage: one barrier publishes it (every wave is past its reads of
-// the stage before, whose ring slot the DMA pieces refill), then the products ah.bh, am.bh, ah.bm with C0 + C1 + C2 DMA pieces threaded
-// through them; the fragment reads run one product ahead of their MFMAs
-template <int ST, int C0, int C1, int C2, class Piece>
-__device__ inline void x2_dw_kstep(f32x16 (&acc)[4][4], f32x16 &dacc, const int (&abase)[4][2], const int (&bbase)[4][2], const X2DwBias &b,
-                                            bool live_n, const Piece &dma_piece)
-{
-    lds_barrier();
-    Frag8 Ah, Bh, Am, Bm;
-    u32x2 dl[2], dh[2];
-    x2_dw_reads<ST, 0, 4>(Ah, abase);
-    x2_dw_reads<ST, 0, 4>(Bh, bbase);
-    x2_dw_reads<ST, 1, 4>(Am, abase);
-    FRAG8_LANDED(Ah, 8);
-    FRAG8_LANDED(Bh, 8);
-    x2_dw_product<0, C0>(acc, Ah, Bh, live_n, dma_piece);
-    x2_dw_reads<ST, 1, 4>(Bm, bbase);
-    FRAG8_LANDED(Am, 8);
-    x2_dw_product<C0, C1>(acc, Am, Bh, live_n, dma_piece);
-    FRAG8_LANDED(Bm, 0);
-    if (b.do_b) { x2_dw_bias_read<ST, 0>(dl[0], dh[0], b.sbase[0]); x2_dw_bias_read<ST, 1>(dl[1], dh[1], b.sbase[0]); }
-    x2_dw_product<C0 + C1, C2>(acc, Ah, Bm, live_n, dma_piece);
-    if (b.do_b) {
-        x2_dw_bias_mfma(dl[0], dh[0], dacc, b.sel0); x2_dw_bias_mfma(dl[1], dh[1], dacc, b.sel0);
-        if (b.two_b) {
-            x2_dw_bias_read<ST, 0>(dl[0], dh[0], b.sbase[1]); x2_dw_bias_read<ST, 1>(dl[1], dh[1], b.sbase[1]);
-            x2_dw_bias_mfma(dl[0], dh[0], dacc, b.sel1); x2_dw_bias_mfma(dl[1], dh[1], dacc, b.sel1);
-        }
-    }
-}
-// Soft lockstep of the tiles of a split (k_dw_bf16's, round 3).  They walk the same k-steps and share every operand byte
-// through their XCD's L2 (G between the h blocks, hidden between the v blocks); nothing else holds them together, and at
-// this kernel's pace a tile that falls behind finds its lines evicted and becomes its own HBM stream — counted without
-// it: 83 GB fetched for 39.5 GB of operands (profiles/r04_f16x2_hbm_traffic_pmc.txt, first pass).  Every NST k-steps a
-// tile publishes its k-step count and looks at its right-hand neighbour's in the ring of the split's tiles (one coherent
-// scalar load, issued a look before its value is used); a tile more than DW_LAG k-steps ahead of that neighbour naps.
-// Bounded: after DW_NAPS naps without the neighbour catching up (a partner that is not resident) the tile stops looking,
-// so every wave reaches the end whatever the others do.
-struct X2DwLockstep {
-    int *prog;      // the progress words of the split's tiles
-    const int *nb;  // the right-hand neighbour's word
-    int nb_at;      // the neighbour's k-step count as of the last look
-    bool sync_on;
-};
-__device__ inline X2DwLockstep x2_dw_lockstep_init(int *dw_prog, int split, int tile, int tiles)
-{
-    X2DwLockstep s;
-    s.prog = dw_prog ? dw_prog + split * 16 : nullptr;
-    s.sync_on = s.prog != nullptr && tiles > 1 && tiles <= 16;
-    s.nb = s.prog ? s.prog + (tile + 1 < tiles ? tile + 1 : 0) : nullptr;
-    s.nb_at = 0x7fffffff;
-    return s;
-}
-__device__ inline void x2_dw_lockstep(X2DwLockstep &s, int mine, int tile, int tid)  // (wave-uniform)
-{
-    constexpr int DW_LAG = 6, DW_NAPS = 256;
-    // the value requested at the previous look has long landed; the wait names nb_at so that no copy of the register made before
-    // the data arrived can be what the comparison reads (round-4 advice: a stale value only mis-paces, but makes timing and traffic
-    // depend on the compiler's register copies)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(s.nb_at) :: "memory");
-    int naps = 0;
-    while (s.sync_on && s.nb_at + DW_LAG + XW2_NST < mine) {  // (+NST: the value is one look old)
-        if (++naps > DW_NAPS) { s.sync_on = false; break; }
-        __builtin_amdgcn_s_sleep(4);
-        asm volatile("s_load_dword %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=s"(s.nb_at) : "s"(s.nb) : "memory");
-    }
-    if (s.sync_on) {
-        if (tid == 0) __hip_atomic_store(s.prog + tile, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (one more outstanding store only makes the counted waits stricter)
-        asm volatile("s_load_dword %0, %1, 0x0 glc" : "=s"(s.nb_at) : "s"(s.nb) : "memory");  // used at the next look
-    }
-}
-// The ring driver: ONE pipeline run over a split's nks k-steps.  dma_stage(ks, st) issues this wave's DMA pieces of k-step ks into ring
-// stage st (prologue: NST - 1 stages ahead); kstep(Int<ST>, ks) is k-step ks on ring stage ST = ks % NST — its counted wait for the
-// stage (the kernels': two stages in flight behind the one waited for), x2_dw_kstep, and inside it the pieces of k-step ks + NST - 1.
-// The loop is unrolled by NST with a look at the lockstep in front of stage 0.
-template <class KStep, class DmaStage>
-__device__ inline void x2_dw_ring(int nks, X2DwLockstep &ls, int tile, int tid, const KStep &kstep, const DmaStage &dma_stage)
-{
-    static_assert(XW2_NST == 4, "prologue and unrolling below");
-    int runs = 1;  // ONE pipeline run; the count is opaque to hipcc, which keeps the accumulators in their registers across a loop of
-    asm volatile("" : "+s"(runs));  // runs (the per-range walk's shape) and spills all 256 of them around a straight-line run
-    for (int run = 0; run < runs; ++run) {
-        dma_stage(0, 0);
-        dma_stage(1, 1);
-        dma_stage(2, 2);
-        for (int ks = 0;;) {
-            if (ks >= nks) break;
-            x2_dw_lockstep(ls, ks, tile, tid);
-            kstep(Int<0>{}, ks); ++ks;
-            if (ks >= nks) break;
-            kstep(Int<1>{}, ks); ++ks;
-            if (ks >= nks) break;
-            kstep(Int<2>{}, ks); ++ks;
-            if (ks >= nks) break;
-            kstep(Int<3>{}, ks); ++ks;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the over-issued DMAs before the ring
-        lds_barrier();                                  // is refilled / the kernel exits
-    }
-}
-// Epilogue: partial slab [split][V,H]; bias partial [split][V].  Wave tile at (v0, h0); accumulator register r of tile (qm,qn):
-// v = v0 + 32qm + (r&3) + 8(r>>2) + 4half, h = h0 + 32qn + (lane&31).  GUARD: rows / columns beyond V / H are not stored (without it
-// the column is added in 64 bits: the addresses of a row's four tiles differ by immediates).  db: column k of the selector products
-// (lanes k / 32+k) holds M tile bsel0 + 2k, k = 0 (two_b: 0, 1)
-template <bool GUARD>
-__device__ inline void x2_dw_store(const X3Args &a, int split, int v0, int h0, int lane, const f32x16 (&acc)[4][4], const f32x16 &dacc,
-                                            bool do_b, bool two_b, int bsel0)
-{
-    const int half = lane >> 5, H = a.H, V = a.V;
-    float *sw = a.slab_w + (long)split * V * H;
-    const float rw = a.dw_rescale, rb = a.db_rescale;
-#pragma unroll
-    for (int qm = 0; qm < 4; ++qm)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int v = v0 + 32 * qm + (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (!GUARD || v < V) {
-#pragma unroll
-                for (int qn = 0; qn < 4; ++qn) {
-                    const int h = h0 + 32 * qn + (lane & 31);
-                    if (!GUARD || h < H) sw[GUARD ? (long)v * H + h : (long)v * H + h0 + 32 * qn + (lane & 31)] = acc[qm][qn][r] * rw;
-                }
-            }
-        }
-    if (do_b && (lane & 31) < (two_b ? 2 : 1)) {
-        const int m = bsel0 + 2 * (lane & 31);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int v = v0 + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (!GUARD || v < V) a.slab_b[(long)split * V + v] = dacc[r] * rb;
-        }
-    }
-}
-
 // NW = waves per workgroup: 4, one wave per SIMD, wave tile 128 v x 128 h = 16 accumulator tiles.  (Two waves per SIMD with 8 tiles each
 // were measured equal, 15.5 ms both at cfg2: the kernel is bound by the bytes it stages — 32 KiB per k-step and CU at ~12.6 B/clk/CU, the
 // rate the forward's and dHidden's W streams reach — not by issue stalls.  The parameter stays in the kernel's name: profiles/, DESIGN.md.)
@@ -604,73 +389,42 @@ template <int NW, bool PARTH = false>
 __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
 {
     static_assert(NW == 4, "one wave per SIMD");
-    constexpr int WN = 2;  // waves along h
     constexpr int QN = 4;  // 32-column h tiles per wave
     constexpr int ND = 8;  // DMA pieces per wave and stage
     extern __shared__ __attribute__((aligned(1024))) char s_ring[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-    const int H = a.H, V = a.V;
-    const int n_vblk = (V + 255) / 256, n_hblk = (H + 255) / 256;
-    const int tiles = n_vblk * n_hblk;
-    const int id = x2_dw_xcd_remap(blockIdx.x, tiles * a.n_split);
-    const int tile = id % tiles, split = id / tiles;
-    const int vb = tile / n_hblk, hb = tile % n_hblk;
+    const int H = a.H;
+    const DwTile tl = dw_tile(blockIdx.x, wave, H, a.V, a.n_split);
+    const int tile = tl.tile, tiles = tl.tiles, split = tl.split, vb = tl.vb, hb = tl.hb, wm = tl.wm, wn = tl.wn;
     // this split's share [g_lo, g_hi) of the k-steps of LIVE groups, four list entries each (X3Args::grp_list, launch_x2_live; the Linear
     // layer: every group); the last k-step is filled up with the list's padding entries
-    static_assert(XL2_GPAD >= 4 * XW2_NST + 3, "read-ahead of NST k-steps behind a partly filled last one");
+    static_assert(XL2_GPAD >= 4 * XW2::NST + 3, "read-ahead of NST k-steps behind a partly filled last one");
     const long nlive = (__builtin_amdgcn_readfirstlane(a.live_stats[4]) + 3) / 4;  // (uniform by construction; said so: the walk's control flow is scalar)
     // (the 64-bit divisions run on the vector ALU: the quotients, at most nlive, are handed back to scalar registers)
     const int g_lo = __builtin_amdgcn_readfirstlane((int)(nlive * split / a.n_split));
     const int g_hi = __builtin_amdgcn_readfirstlane((int)(nlive * (split + 1) / a.n_split));
     X_CLOCK_STAMP(128 + 104);
 
-    f32x16 acc[4][QN];
-#pragma unroll
-    for (int qm = 0; qm < 4; ++qm)
-#pragma unroll
-        for (int qn = 0; qn < QN; ++qn)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[qm][qn][r] = 0.f;
-    // db (x2_dw_bias_mfma): the waves of h blocks 0 and 1 each take one of their wm half's four M tiles; one h block: two each
-    X2DwBias bias;
-    bias.do_b = hb < 2;  // workgroup-uniform
-    const int bsel0 = n_hblk >= 2 ? (hb & 1) * 2 + wn : wn;
-    bias.two_b = n_hblk < 2;  // each wave takes two tiles, bsel0 and bsel0 + 2
-    f32x16 dacc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dacc[r] = 0.f;
-    bias.sel0 = (lane & 31) == 0 ? 0x3c003c00u : 0u; bias.sel1 = (lane & 31) == 1 ? 0x3c003c00u : 0u;  // fp16 ones
+    // db (dw_bias_mfma): the waves of h blocks 0 and 1 each take one of their wm half's four M tiles; one h block: two each
+    f32x16 acc[4][QN], dacc;
+    dw_zero(acc, dacc);
+    DwBias bias;
+    const int bsel0 = dw_bias_setup<F16x2>(bias, tl.n_hblk, hb, wn, lane);
 
     if (g_hi > g_lo) {
         // ---- DMA source of this wave's operand tile
         const int otile = wave;
         const bool is_g = otile < 2;
-        int col0 = (is_g ? vb : hb) * 256 + 128 * (otile & 1);
-        const bool dead_tile = PARTH && !is_g && col0 >= H;  // (wave-uniform)
-        if (col0 >= (is_g ? V : H)) col0 = 0;  // tile beyond the matrix: never stored, read something valid
-        const char *pbase[2];  // plane p of this wave's operand: base pointer (wave-uniform), row stride in bytes
-        long rstride;
-        if (is_g) {
-            pbase[0] = (const char *)a.logits + 4L * col0;        // hi: first 64 bytes of each 128-byte chunk
-            pbase[1] = (const char *)a.logits + 4L * col0 + 64;   // mid: last 64
-            rstride = 4L * V;
-        } else {
-#pragma unroll
-            for (int p = 0; p < 2; ++p) pbase[p] = (const char *)(a.hidden + p * a.plane_stride) + 2L * col0;
-            rstride = 2L * H;
-        }
-        // DMA i (0..3) of a plane's 16 rows: ring rows 4i .. 4i+3 <- the four rows of the k-step's list entry i, a raw buffer of its own;
-        // lane L: row L>>4 of the group, LDS chunk position L&15 <- global chunk jg = (L&15) ^ swz(ring row), swz = ((L>>4)<<2) | (i&3)
+        const bool dead_tile = PARTH && !is_g && hb * 256 + 128 * (otile & 1) >= H;  // (wave-uniform)
+        DwSource<F16x2> src;
+        dw_source(src, a, is_g, dw_col0(is_g, is_g ? vb : hb, otile & 1, H, a.V));
+        const long rstride = src.rstride[0];  // (both planes')
+        // DMA i (0..3) of a plane's 16 rows: ring rows 4i .. 4i+3 <- the four rows of the k-step's list entry i, a raw buffer of its own
+        // (row 0 of the group: the immediate is taken out of the buffer's base below)
         int soff[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int jg = (lane & 15) ^ (((lane >> 4) << 2) | (i & 3));
-            // interleaved planes (G): chunk jg of the plane is 16 bytes at 128*(jg>>2) + 16*(jg&3)
-            const int cb = is_g ? 128 * (jg >> 2) + 16 * (jg & 3) : 16 * jg;
-            soff[i] = dead_tile ? 0x7ffffff0 : (int)((lane >> 4) * rstride) + cb;
-        }
+        for (int i = 0; i < 4; ++i) soff[i] = dead_tile ? DW_SOFF_DEAD : dw_soff(lane, i, 0, rstride, is_g, 0);
         // The four pieces of a plane share one LDS base (M0); piece i carries the immediate offset 1024 i, which advances the memory
         // address too and counts in the range check.  It is taken back out of the piece's buffer BASE and added to its range (the per-lane
         // offset of the group's row 0 is below 1024 i: subtracting there would wrap, and the range check would hand back zeros)
@@ -691,31 +445,28 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
         for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int sec = 0; sec < 2; ++sec) {
-                abase[m][sec] = x2_dw_frag_addr(lds0, wm, m, sec, lane);
-                bbase[m][sec] = x2_dw_frag_addr(lds0, 2 + wn, m, sec, lane);
+                abase[m][sec] = dw_frag_addr<XW2>(lds0, wm, m, sec, lane);
+                bbase[m][sec] = dw_frag_addr<XW2>(lds0, 2 + wn, m, sec, lane);
             }
-#pragma unroll
-        for (int k = 0; k < 2; ++k)
-#pragma unroll
-            for (int sec = 0; sec < 2; ++sec) bias.sbase[k][sec] = x2_dw_frag_addr(lds0, wm, (bsel0 + 2 * k) & 3, sec, lane);
+        dw_bias_bases<XW2>(bias, lds0, wm, bsel0, lane);
 
         auto kstep = [&](auto st_c, long ks) {
-            constexpr int ST = decltype(st_c)::value, DST = (ST + XW2_NST - 1) % XW2_NST;
+            constexpr int ST = decltype(st_c)::value, DST = (ST + XW2::NST - 1) % XW2::NST;
             // stage ks landed (the 8 (NST - 2) younger pieces of the stages after it may still fly).  In front of the wait: the four list
             // entries of stage ks + NST - 1
             i32x4 ent;
-            const int *ep = lptr + 4 * (ks + (XW2_NST - 1));
-            static_assert(ND * (XW2_NST - 2) == 16, "the counted wait");
+            const int *ep = lptr + 4 * (ks + (XW2::NST - 1));
+            static_assert(ND == XW2::ND && XW2::WAIT == 16, "the counted wait");
             XW2_LOAD_ENT4(ent, ep, RNNT_VMCNT(16) "\n\t");
             // piece n of this wave's share of stage ks+NST-1 -> ring stage DST: plane n>>2, ring rows 4(n&3).. <- the
             // four rows of entry n&3 as a raw buffer (wave-uniform base, built here between the MFMAs; the per-lane part is the 32-bit soff)
             auto dma_piece = [&](auto n_c) {
                 constexpr int n = decltype(n_c)::value, i = n & 3, p = (n >> 2) & 1, imm = 1024 * i;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(x2_piece_rsrc(pbase[p], ent[i], gbytes, imm),
-                                                         (lds_vptr)(s_ring + otile * XW2_TILE + DST * XW2_STAGE + p * XW2_PLANE),
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(x2_piece_rsrc(src.pbase[p], ent[i], gbytes, imm),
+                                                         (lds_vptr)(s_ring + otile * XW2::TILE + DST * XW2::STAGE + p * XW2::PLANE),
                                                          16, soff[i], 0, imm, 0);
             };
-            x2_dw_kstep<ST, 3, 3, 2>(acc, dacc, abase, bbase, bias, live_n, dma_piece);
+            dw_kstep2<XW2, ST, 3, 3, 2>(acc, dacc, abase, bbase, bias, live_n, a.ablate, dma_piece);
         };
         auto dma_stage = [&](long ks, int st) {  // pipeline prologue: this wave's pieces of stage ks
             i32x4 ent;
@@ -724,20 +475,17 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
 #pragma unroll
             for (int n = 0; n < ND; ++n) {
                 const int p = n >> 2, i = n & 3;
-                const __amdgpu_buffer_rsrc_t r = x2_piece_rsrc(pbase[p], ent[i], gbytes, 1024 * i);
-                lds_vptr d = (lds_vptr)(s_ring + otile * XW2_TILE + st * XW2_STAGE + p * XW2_PLANE);
-                if (i == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d, 16, soff[i], 0, 0, 0);
-                if (i == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d, 16, soff[i], 0, 1024, 0);
-                if (i == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d, 16, soff[i], 0, 2048, 0);
-                if (i == 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d, 16, soff[i], 0, 3072, 0);
+                dw_dma_imm(x2_piece_rsrc(src.pbase[p], ent[i], gbytes, 1024 * i), (lds_vptr)(s_ring + otile * XW2::TILE + st * XW2::STAGE + p * XW2::PLANE),
+                           soff[i], i);
             }
         };
-        X2DwLockstep ls = x2_dw_lockstep_init(a.dw_prog, split, tile, tiles);
-        x2_dw_ring(g_hi - g_lo, ls, tile, tid, kstep, dma_stage);
+        XW2Lockstep ls;
+        ls.init(a.dw_prog, split, tile, tiles);
+        dw_ring(g_hi - g_lo, ls, tile, tid, kstep, dma_stage);
     }
 
     X_CLOCK_STAMP(128 + 106);
-    x2_dw_store<true>(a, split, vb * 256 + wm * 128, hb * 256 + wn * 32 * QN, lane, acc, dacc, bias.do_b, bias.two_b, bsel0);
+    dw_store<F16x2, true>(a, split, tl.v0, tl.h0, lane, acc, dacc, bias.do_b, bias.two_b, bsel0);
 }
 
 
@@ -753,7 +501,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_dw_x2(X3Args a)
 // The two tile kinds are two instantiations of the body behind ONE workgroup-uniform branch (a branch inside the k loop would split the
 // hand-placed MFMA / DMA / read schedule into scheduling regions).  Everything but the geometry, the DMA sources (tall: 10 pieces per wave
 // and stage, threaded 4 + 3 + 3) and the walk of the live k-step list (X3Args::ks_list: one entry per k-step, one buffer resource per
-// plane) is "The dW k-step pipeline" above, shared with k_dw_x2<4>; db from whole h blocks 0 and 1 only.
+// plane) is split_dw.hpp's, shared with k_dw_x2<4>; db from whole h blocks 0 and 1 only.
 // ---------------------------------------------------------------------------------------
 int x2_dw_mixed_ok(int H, int V) { return H % 256 == 128 && H >= 640 && V % 512 == 0; }
 int x2_dw_tiles(int H, int V) { return x2_dw_mixed_ok(H, V) ? (V / 256) * (H / 256) + V / 512 : ((V + 255) / 256) * ((H + 255) / 256); }
@@ -766,7 +514,7 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
     const int H = a.H, V = a.V;
     const int n_vblk = V / 256, n_fh = H / 256;  // whole h blocks; the odd block = columns 256 n_fh .. +127
     const int n_full = n_vblk * n_fh, tiles = n_full + n_vblk / 2;
-    const int id = x2_dw_xcd_remap(blockIdx.x, tiles * a.n_split);
+    const int id = dw_xcd_remap(blockIdx.x, tiles * a.n_split);
     const int tile = id % tiles, split = id / tiles;
     // this split's share [g_lo, g_hi) of the live k-steps (k_dw_x2's walk: X3Args::ks_list)
     const long nlive = __builtin_amdgcn_readfirstlane(a.live_stats[0]);
@@ -781,22 +529,14 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
         const int v0 = TALL ? vt * 512 + wave * 128 : vb * 256 + wm * 128;
         const int h0 = TALL ? n_fh * 256 : hb * 256 + wn * 128;
 
-        f32x16 acc[4][4];
-#pragma unroll
-        for (int qm = 0; qm < 4; ++qm)
-#pragma unroll
-            for (int qn = 0; qn < 4; ++qn)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[qm][qn][r] = 0.f;
         // db as in k_dw_x2<4>: the waves of the whole-block tiles of h blocks 0 and 1 each take one of their wm half's four M tiles
-        X2DwBias bias;
+        f32x16 acc[4][4], dacc;
+        dw_zero(acc, dacc);
+        DwBias bias;
         bias.do_b = !TALL && hb < 2;  // workgroup-uniform
         bias.two_b = false;
         const int bsel0 = (hb & 1) * 2 + wn;
-        f32x16 dacc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dacc[r] = 0.f;
-        bias.sel0 = (lane & 31) == 0 ? 0x3c003c00u : 0u; bias.sel1 = 0u;  // fp16 ones in column 0 of the selector fragment
+        bias.sel0 = (lane & 31) == 0 ? F16x2::ONES : 0u; bias.sel1 = 0u;  // ones in column 0 of the selector fragment
 
         if (g_hi > g_lo) {
             // ---- DMA sources.  Own operand tile (8 pieces per stage): whole-block tile: waves 0, 1 the G tile's 128-column halves, waves 2, 3
@@ -804,34 +544,18 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
             // 2 (wave & 1) + 1 of plane wave >> 1 of the ONE hidden operand tile all four waves multiply by.
             const bool is_g = TALL || wave < 2;
             const int col0 = TALL ? v0 : (is_g ? vb : hb) * 256 + 128 * (wave & 1);
-            const char *pbase[2];
-            long rstride;
-            if (is_g) {
-                pbase[0] = (const char *)a.logits + 4L * col0;        // hi: first 64 bytes of each 128-byte chunk
-                pbase[1] = (const char *)a.logits + 4L * col0 + 64;   // mid: last 64
-                rstride = 4L * V;
-            } else {
+            DwSource<F16x2> src;
+            dw_source(src, a, is_g, col0);
+            const long rstride = src.rstride[0];  // (both planes')
+            int soff[4];  // (the piece's immediate offset 1024 i advances the memory address too: taken out here)
 #pragma unroll
-                for (int p = 0; p < 2; ++p) pbase[p] = (const char *)(a.hidden + p * a.plane_stride) + 2L * col0;
-                rstride = 2L * H;
-            }
-            int soff[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int jg = (lane & 15) ^ (((lane >> 4) << 2) | (i & 3));
-                const int cb = is_g ? 128 * (jg >> 2) + 16 * (jg & 3) : 16 * jg;
-                soff[i] = (int)((4 * i + (lane >> 4)) * rstride) + cb - 1024 * i;  // (the piece's immediate offset 1024 i advances the memory address too)
-            }
+            for (int i = 0; i < 4; ++i) soff[i] = dw_soff(lane, i, 4 * i, rstride, is_g, 1024 * i);
             const int xp = wave >> 1, xi0 = 2 * (wave & 1);  // tall: this wave's two pieces of the hidden tile — plane xp, pieces xi0, xi0 + 1
             const char *xbase = (const char *)(a.hidden + xp * a.plane_stride) + 2L * h0;
             const long xstride = 2L * H;
             int xoff[2];
 #pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int i = xi0 + k;
-                const int jg = (lane & 15) ^ (((lane >> 4) << 2) | (i & 3));
-                xoff[k] = (int)((4 * i + (lane >> 4)) * xstride) + 16 * jg;
-            }
+            for (int k = 0; k < 2; ++k) xoff[k] = dw_soff(lane, xi0 + k, 4 * (xi0 + k), xstride, false, 0);
             const int *lptr = a.ks_list + g_lo;  // k-step ks multiplies the 16 rows of k-step lptr[ks] (k_dw_x2's walk)
             // ---- fragment bases: A from operand tile wm (tall: wave), the tile this wave stages when TALL; B from the hidden tile(s)
             const int lds0 = (int)(size_t)(lds_vptr)s_ring;
@@ -841,39 +565,37 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
             for (int m = 0; m < 4; ++m)
 #pragma unroll
                 for (int sec = 0; sec < 2; ++sec) {
-                    abase[m][sec] = x2_dw_frag_addr(lds0, wm, m, sec, lane);
-                    bbase[m][sec] = x2_dw_frag_addr(lds0, TALL ? 4 : 2 + wn, m, sec, lane);
-                    bias.sbase[1][sec] = bias.sbase[0][sec] = x2_dw_frag_addr(lds0, wm, bsel0 & 3, sec, lane);
+                    abase[m][sec] = dw_frag_addr<XW2>(lds0, wm, m, sec, lane);
+                    bbase[m][sec] = dw_frag_addr<XW2>(lds0, TALL ? 4 : 2 + wn, m, sec, lane);
+                    bias.sbase[1][sec] = bias.sbase[0][sec] = dw_frag_addr<XW2>(lds0, wm, bsel0 & 3, sec, lane);
                 }
 
             auto kstep = [&](auto st_c, long ks) {
-                constexpr int ST = decltype(st_c)::value, DST = (ST + XW2_NST - 1) % XW2_NST;
+                constexpr int ST = decltype(st_c)::value, DST = (ST + XW2::NST - 1) % XW2::NST;
                 // stage ks landed (the ND (NST - 2) younger pieces of the stages after it may still fly: ND = 8, tall 10).  In front of the
                 // wait: the list entry of stage ks + NST - 1 (k_dw_x2's)
                 int ent;
-                const int *ep = lptr + ks + (XW2_NST - 1);
+                const int *ep = lptr + ks + (XW2::NST - 1);
+                static_assert(XW2::WAIT == 16 && (XW2::ND + 2) * (XW2::NST - 2) == 20, "the counted waits: 8 pieces per wave and stage, tall 10");
                 if (TALL) asm volatile("s_load_dword %0, %1, 0x0\n\t" RNNT_VMCNT(20) "\n\ts_waitcnt lgkmcnt(0)" : "=s"(ent) : "s"(ep) : "memory");
                 else asm volatile("s_load_dword %0, %1, 0x0\n\t" RNNT_VMCNT(16) "\n\ts_waitcnt lgkmcnt(0)" : "=s"(ent) : "s"(ep) : "memory");
                 __amdgpu_buffer_rsrc_t rs[2];
 #pragma unroll
-                for (int p = 0; p < 2; ++p)
-                    rs[p] = __builtin_amdgcn_make_buffer_rsrc((void *)(pbase[p] + ((long)ent * XW2_ROWS) * rstride), 0,
-                                                              (int)(XW2_ROWS * rstride), 0x00020000);
-                const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
-                    (void *)(xbase + ((long)ent * XW2_ROWS) * xstride), 0, (int)(XW2_ROWS * xstride), 0x00020000);
+                for (int p = 0; p < 2; ++p) rs[p] = dw_rows_rsrc(src.pbase[p], (long)ent * DW_ROWS, rstride, DW_ROWS);
+                const __amdgpu_buffer_rsrc_t xrs = dw_rows_rsrc(xbase, (long)ent * DW_ROWS, xstride, DW_ROWS);
                 auto dma_piece = [&](auto n_c) {  // piece n of this wave's share of stage ks+NST-1 -> ring stage DST
                     constexpr int n = decltype(n_c)::value;
                     if constexpr (n < 8) {
                         constexpr int i = n & 3, p = (n >> 2) & 1;
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[p], (lds_vptr)(s_ring + own_tile * XW2_TILE + DST * XW2_STAGE + p * XW2_PLANE),
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[p], (lds_vptr)(s_ring + own_tile * XW2::TILE + DST * XW2::STAGE + p * XW2::PLANE),
                                                                  16, soff[i], 0, 1024 * i, 0);
                     } else {  // (tall) the hidden tile: operand tile 4
                         constexpr int k = n - 8;
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_vptr)(s_ring + 4 * XW2_TILE + DST * XW2_STAGE + xp * XW2_PLANE + 1024 * (xi0 + k)),
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_vptr)(s_ring + 4 * XW2::TILE + DST * XW2::STAGE + xp * XW2::PLANE + 1024 * (xi0 + k)),
                                                                  16, xoff[k], 0, 0, 0);
                     }
                 };
-                x2_dw_kstep<ST, (TALL ? 4 : 3), 3, (TALL ? 3 : 2)>(acc, dacc, abase, bbase, bias, true, dma_piece);
+                dw_kstep2<XW2, ST, (TALL ? 4 : 3), 3, (TALL ? 3 : 2)>(acc, dacc, abase, bbase, bias, true, a.ablate, dma_piece);
             };
             auto dma_stage = [&](long ks, int st) {  // pipeline prologue: this wave's pieces of stage ks
                 int ent;
@@ -882,28 +604,23 @@ __global__ __launch_bounds__(256, 1) void k_dw_x2m(X3Args a)
 #pragma unroll
                 for (int n = 0; n < 8; ++n) {
                     const int p = n >> 2, i = n & 3;
-                    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
-                        (void *)(pbase[p] + ((long)ent * XW2_ROWS) * rstride), 0, (int)(XW2_ROWS * rstride), 0x00020000);
-                    lds_vptr d = (lds_vptr)(s_ring + own_tile * XW2_TILE + st * XW2_STAGE + p * XW2_PLANE);
-                    if (i == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d, 16, soff[i], 0, 0, 0);
-                    if (i == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d, 16, soff[i], 0, 1024, 0);
-                    if (i == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d, 16, soff[i], 0, 2048, 0);
-                    if (i == 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, d, 16, soff[i], 0, 3072, 0);
+                    dw_dma_imm(dw_rows_rsrc(src.pbase[p], (long)ent * DW_ROWS, rstride, DW_ROWS),
+                               (lds_vptr)(s_ring + own_tile * XW2::TILE + st * XW2::STAGE + p * XW2::PLANE), soff[i], i);
                 }
                 if (TALL) {
-                    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
-                        (void *)(xbase + ((long)ent * XW2_ROWS) * xstride), 0, (int)(XW2_ROWS * xstride), 0x00020000);
+                    const __amdgpu_buffer_rsrc_t r = dw_rows_rsrc(xbase, (long)ent * DW_ROWS, xstride, DW_ROWS);
 #pragma unroll
                     for (int k = 0; k < 2; ++k)
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_vptr)(s_ring + 4 * XW2_TILE + st * XW2_STAGE + xp * XW2_PLANE + 1024 * (xi0 + k)),
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_vptr)(s_ring + 4 * XW2::TILE + st * XW2::STAGE + xp * XW2::PLANE + 1024 * (xi0 + k)),
                                                                  16, xoff[k], 0, 0, 0);
                 }
             };
             // (tall and whole-block tiles walk the same k-steps and share G through L2: one lockstep ring)
-            X2DwLockstep ls = x2_dw_lockstep_init(a.dw_prog, split, tile, tiles);
-            x2_dw_ring(g_hi - g_lo, ls, tile, tid, kstep, dma_stage);
+            XW2Lockstep ls;
+            ls.init(a.dw_prog, split, tile, tiles);
+            dw_ring(g_hi - g_lo, ls, tile, tid, kstep, dma_stage);
         }
-        x2_dw_store<false>(a, split, v0, h0, lane, acc, dacc, bias.do_b, false, bsel0);  // (V % 512 == 0, H % 128 == 0: every row and column exists)
+        dw_store<F16x2, false>(a, split, v0, h0, lane, acc, dacc, bias.do_b, false, bsel0);  // (V % 512 == 0, H % 128 == 0: every row and column exists)
     };
     if (tile >= n_full) body(Int<1>{});  // (workgroup-uniform)
     else body(Int<0>{});
@@ -917,13 +634,13 @@ void launch_dw_x2(const X3Args &a, hipStream_t st, bool zero_prog)
     if (a.dw_prog && zero_prog) launch_fill32(a.dw_prog, 0u, (size_t)a.n_split * 64, st);
     const int tiles = x2_dw_tiles(a.H, a.V);
     static LdsOptIn lds_opt_in;
-    lds_opt_in.raise(4 * XW2_TILE, k_dw_x2<4>, k_dw_x2<4, true>);
+    lds_opt_in.raise(4 * XW2::TILE, k_dw_x2<4>, k_dw_x2<4, true>);
     static LdsOptIn lds_opt_in_m;
-    lds_opt_in_m.raise(5 * XW2_TILE, k_dw_x2m);
+    lds_opt_in_m.raise(5 * XW2::TILE, k_dw_x2m);
     // H % 256 == 128: whole-block tiles + tall tiles over the odd block (k_dw_x2m) where the shape allows; else the half-empty last h block
-    if (x2_dw_mixed_ok(a.H, a.V)) hipLaunchKernelGGL(k_dw_x2m, dim3(tiles * a.n_split), dim3(256), 5 * XW2_TILE, st, a);
-    else if (a.H % 256 != 0) hipLaunchKernelGGL((k_dw_x2<4, true>), dim3(((a.V + 255) / 256) * ((a.H + 255) / 256) * a.n_split), dim3(256), 4 * XW2_TILE, st, a);
-    else hipLaunchKernelGGL(k_dw_x2<4>, dim3(tiles * a.n_split), dim3(256), 4 * XW2_TILE, st, a);
+    if (x2_dw_mixed_ok(a.H, a.V)) hipLaunchKernelGGL(k_dw_x2m, dim3(tiles * a.n_split), dim3(256), 5 * XW2::TILE, st, a);
+    else if (a.H % 256 != 0) hipLaunchKernelGGL((k_dw_x2<4, true>), dim3(((a.V + 255) / 256) * ((a.H + 255) / 256) * a.n_split), dim3(256), 4 * XW2::TILE, st, a);
+    else hipLaunchKernelGGL(k_dw_x2<4>, dim3(tiles * a.n_split), dim3(256), 4 * XW2::TILE, st, a);
 }
 
 

@@ -24,6 +24,7 @@
 // Every kernel here is 4 waves (one per SIMD) with 256 accumulator registers per wave, hand-pipelined
 // around long MFMA streams (96 MFMAs = 3072 matrix-pipe cycles per 16-deep k-step), like the fp32 route's.
 #include "split_dhidden.hpp"
+#include "split_dw.hpp"
 
 // The plain producers and the W packs are split_common.hpp's, at the bf16x3 format (no scales: the pointer is null and unread)
 void launch_x3_make_hidden(const X3Args &a, hipStream_t st) { launch_split_make_hidden<Bf16x3>(a, st); }
@@ -51,13 +52,9 @@ size_t x3_wpack_dh_bytes(int H, int V) { return split_wpack_dh_bytes<Bf16x3>(H, 
 // ahead of their MFMAs.  Product order ah.bh, am.bh, am.bm, ah.bm, al.bh, ah.bl keeps at most five of the
 // six 16-register fragment sets live.
 // ---------------------------------------------------------------------------------------
-#define XW_ROWS 16
-#define XW_NST 3
-#define XW_PLANE 4096          // one operand tile of one plane: 16 rows x 256 B
-#define XW_STAGE (3 * XW_PLANE)  // one stage of one operand tile
-#define XW_TILE (XW_NST * XW_STAGE)  // ring of one operand tile: [stage][plane][16 x 256 B] = 36 KiB
-#define XW_GRAN 32  // granule of the live-row table (shared with the bf16 route: 2 k-steps)
-
+typedef DwRing<Bf16x3, 3> XW;  // ring of 3 stages: the DMAs of stage ks + 2 are issued during k-step ks; 3 x 12 KiB per operand tile
+// a range's last k-step issues the pieces of the two k-steps behind it: 32 rows past the range's end, at most that far past rows_pad
+static_assert((XW::NST - 1) * DW_ROWS <= DW_ROWS_PAST, "read-ahead of the ring past the last live row");
 
 __global__ __launch_bounds__(256, 1) void k_dw_x3(X3Args a)
 {
@@ -68,271 +65,95 @@ __global__ __launch_bounds__(256, 1) void k_dw_x3(X3Args a)
     extern __shared__ __attribute__((aligned(1024))) char s_ring[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int half = lane >> 5;
-    const int H = a.H, V = a.V;
-    const int n_vblk = (V + 255) / 256, n_hblk = (H + 255) / 256;
-    const int tiles = n_vblk * n_hblk;
-    const int total = tiles * a.n_split;
-    int id = blockIdx.x;  // XCD-aware remap: the tiles of one split share an XCD's L2
-    {
-        const int q8 = total / 8, r8 = total % 8, x = id % 8;
-        id = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + id / 8;
-    }
-    const int tile = id % tiles, split = id / tiles;
-    const int vb = tile / n_hblk, hb = tile % n_hblk;
-    const long *tab = a.dw_tab;
-    const int B = a.B;
-    const long nlive = tab[2 * B + 1];
-    const long g_lo = nlive * split / a.n_split, g_hi = nlive * (split + 1) / a.n_split;
+    const DwTile tl = dw_tile(blockIdx.x, wave, a.H, a.V, a.n_split);
+    const DwShare share = dw_share(a.dw_tab, a.B, tl.split, a.n_split);
     X_CLOCK_STAMP(128 + 104);
 
-    f32x16 acc[4][4];
-#pragma unroll
-    for (int qm = 0; qm < 4; ++qm)
-#pragma unroll
-        for (int qn = 0; qn < 4; ++qn)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[qm][qn][r] = 0.f;
-    // db[v] = sum_c G[c,v] rides the matrix pipe: one more MFMA per plane and k-step against a B fragment of
-    // ones, for ONE of the wave's 4 M tiles, into a 17th accumulator tile (VGPRs).  The 8 M tiles of a v block
-    // are shared out over the waves of the h blocks 0 and 1: (hb, wn) -> M tile `bsel0` of this wave's wm half
-    // (one h block, H <= 256: each wave takes two tiles, bsel0 and bsel0 + 2).  (fp32 adds of unpacked halves
-    // cost ~50 VALU per k-step; v_dot2c_f32_bf16 with a pair of ones — the bf16 route's form — is not
-    // fp32-exact: 9e-3 relative error on db.)
-    // Two tiles share the one accumulator through column SELECTORS: a B fragment that is ones in column j
-    // only puts the row sums of its M tile into column j of the product.
-    const bool do_b = hb < 2;  // workgroup-uniform
-    const int bsel0 = n_hblk >= 2 ? (hb & 1) * 2 + wn : wn;
-    f32x16 dacc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dacc[r] = 0.f;
-    const unsigned sel0 = (lane & 31) == 0 ? 0x3f803f80u : 0u, sel1 = (lane & 31) == 1 ? 0x3f803f80u : 0u;
+    f32x16 acc[4][4], dacc;
+    dw_zero(acc, dacc);
+    DwBias bias;
+    const int bsel0 = dw_bias_setup<Bf16x3>(bias, tl.n_hblk, tl.hb, tl.wn, lane);
 
-    if (g_hi > g_lo) {
-        // ---- DMA source of this wave's operand tile
+    if (share.g_hi > share.g_lo) {
+        // ---- DMA source of this wave's operand tile; DMA i (0..3) of a plane's 16 rows: rows 4i .. 4i+3 of the stage's buffer
         const bool is_g = wave < 2;
-        int col0 = (is_g ? vb : hb) * 256 + 128 * (wave & 1);
-        if (col0 >= (is_g ? V : H)) col0 = 0;  // tile beyond the matrix: never stored, read something valid
-        const char *pbase[3];  // plane p of this wave's operand: base pointer (wave-uniform), row stride in bytes
-        long rstride[3];
-        if (is_g) {
-            pbase[0] = (const char *)a.logits + 4L * col0;        // hi: first 64 bytes of each 128-byte chunk
-            pbase[1] = (const char *)a.logits + 4L * col0 + 64;   // mid: last 64
-            pbase[2] = (const char *)a.g_lo + 2L * col0;
-            rstride[0] = rstride[1] = 4L * V; rstride[2] = 2L * V;
-        } else {
-#pragma unroll
-            for (int p = 0; p < 3; ++p) { pbase[p] = (const char *)(a.hidden + p * a.plane_stride) + 2L * col0; rstride[p] = 2L * H; }
-        }
-        // DMA i (0..3) of a plane's 16 rows: rows 4i .. 4i+3; lane L: row 4i + (L>>4), LDS chunk position L&15
-        // <- global chunk jg = (L&15) ^ swz(row), swz = ((L>>4)<<2) | (i&3)
+        DwSource<Bf16x3> src;
+        dw_source(src, a, is_g, dw_col0(is_g, is_g ? tl.vb : tl.hb, wave & 1, a.H, a.V));
         int soff[3][4];
 #pragma unroll
         for (int p = 0; p < 3; ++p)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int jg = (lane & 15) ^ (((lane >> 4) << 2) | (i & 3));
-                // interleaved planes (G hi / mid): chunk jg of the plane is 16 bytes at 128*(jg>>2) + 16*(jg&3)
-                const int cb = (is_g && p < 2) ? 128 * (jg >> 2) + 16 * (jg & 3) : 16 * jg;
-                soff[p][i] = (int)((4 * i + (lane >> 4)) * rstride[p]) + cb;
-            }
+            for (int i = 0; i < 4; ++i) soff[p][i] = dw_soff(lane, i, 4 * i, src.rstride[p], is_g && p < 2, 0);
         long row_first = 0;  // first cell of the range being walked
-        // ---- transposed fragment reads.  Fragment of 32-column tile m: lane (g = lane>>4, q = (lane&15)>>2,
-        // p = lane&3) reads rows 8(g>>1) + 4sec + q at chunk 4m + 2(g&1) + (p>>1), +8(p&1) bytes, sec = 0,1.
-        const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3, hh = g >> 1;
+        // ---- fragment bases: A from operand tile wm, B from operand tile 2 + wn; db: the M tile(s) this wave sums
         const int lds0 = (int)(size_t)(lds_vptr)s_ring;
         int abase[4][2], bbase[4][2];
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int sec = 0; sec < 2; ++sec) {
-                const int row = 8 * hh + 4 * sec + q;
-                const int ch = 4 * m + 2 * (g & 1) + (pp >> 1);
-                const int swz = ((row & 3) << 2) | ((row >> 2) & 3);
-                const int fo = 256 * row + 16 * (ch ^ swz) + 8 * (pp & 1);
-                abase[m][sec] = lds0 + wm * XW_TILE + fo;
-                bbase[m][sec] = lds0 + (2 + wn) * XW_TILE + fo;
+                abase[m][sec] = dw_frag_addr<XW>(lds0, tl.wm, m, sec, lane);
+                bbase[m][sec] = dw_frag_addr<XW>(lds0, 2 + tl.wn, m, sec, lane);
             }
-        int sbase[2][2];  // db: fragment bases of the M tile(s) this wave sums (bsel0, and bsel0 + 2 with one h block)
-#pragma unroll
-        for (int k = 0; k < 2; ++k)
-#pragma unroll
-            for (int sec = 0; sec < 2; ++sec) {
-                const int m = (bsel0 + 2 * k) & 3;
-                const int row = 8 * hh + 4 * sec + q;
-                const int ch = 4 * m + 2 * (g & 1) + (pp >> 1);
-                const int swz = ((row & 3) << 2) | ((row >> 2) & 3);
-                sbase[k][sec] = lds0 + wm * XW_TILE + 256 * row + 16 * (ch ^ swz) + 8 * (pp & 1);
-            }
+        dw_bias_bases<XW>(bias, lds0, tl.wm, bsel0, lane);
 
         // one k-step on ring stage ST (compile-time: every LDS offset is an immediate)
-        auto kstep = [&](auto st_c, long ks, f32x16 &dacc) {
+        auto kstep = [&](auto st_c, long ks) {
             constexpr int ST = decltype(st_c)::value, DST = (ST + 2) % 3;
-            // the 16 rows of stage ks+2 as three raw buffers (wave-uniform base: scalar arithmetic only; the
-            // per-lane part of a DMA address is the 32-bit soff)
+            // the 16 rows of stage ks+2 as three raw buffers
             __amdgpu_buffer_rsrc_t rs[3];
 #pragma unroll
-            for (int p = 0; p < 3; ++p)
-                rs[p] = __builtin_amdgcn_make_buffer_rsrc((void *)(pbase[p] + (row_first + (ks + 2) * XW_ROWS) * rstride[p]), 0,
-                                                          (int)(XW_ROWS * rstride[p]), 0x00020000);
+            for (int p = 0; p < 3; ++p) rs[p] = dw_rows_rsrc(src.pbase[p], row_first + (ks + 2) * DW_ROWS, src.rstride[p], DW_ROWS);
             auto dma_piece = [&](auto n_c) {  // piece n of stage ks+2 -> ring stage DST: plane n>>2, rows 4(n&3)..
                 constexpr int n = decltype(n_c)::value, p = n >> 2, i = n & 3;
-                if (RNNT_XP(a.ablate, 8192)) return;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[p], (lds_vptr)(s_ring + wave * XW_TILE + DST * XW_STAGE + p * XW_PLANE + 1024 * i),
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[p], (lds_vptr)(s_ring + wave * XW::TILE + DST * XW::STAGE + p * XW::PLANE + 1024 * i),
                                                          16, soff[p][i], 0, 0, 0);
             };
-            // 8 transposed reads of plane P of the A / B operand (inline asm: hipcc guards every LDS read it can
-            // see behind an LDS-DMA with vmcnt(0)); results are used only after FRAG8_LANDED named them
-            auto reads = [&](Frag8 &f, const int (&base)[4][2], auto p_c) {
-                constexpr int off = ST * XW_STAGE + decltype(p_c)::value * XW_PLANE;
-                if (RNNT_XP(a.ablate, 4096)) return;
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.lo[m]) : "v"(base[m][0]), "n"(off));
-                    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.hi[m]) : "v"(base[m][1]), "n"(off));
-                }
-            };
-            // 16 MFMAs of one product with DMA pieces N0, N0+1 threaded through them
-            auto product = [&](const Frag8 &fa_, const Frag8 &fb_, auto n0_c) {
-                constexpr int N0 = decltype(n0_c)::value;
-                u32x4 fa[4], fb[4];
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    fa[m] = u32x4{fa_.lo[m][0], fa_.lo[m][1], fa_.hi[m][0], fa_.hi[m][1]};
-                    fb[m] = u32x4{fb_.lo[m][0], fb_.lo[m][1], fb_.hi[m][0], fb_.hi[m][1]};
-                }
-#pragma unroll
-                for (int qm = 0; qm < 4; ++qm) {
-                    if (!RNNT_XP(a.ablate, 1024)) {
-#pragma unroll
-                        for (int qn = 0; qn < 4; ++qn) acc[qm][qn] = mfma_bf16(fa[qm], fb[qn], acc[qm][qn]);
-                    }
-                    if (qm == 1) dma_piece(Int<N0>{});
-                    if (qm == 3) dma_piece(Int<N0 + 1>{});
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            };
-            // db: the selected M tile's fragment of plane P is read once more through its own base registers (a
-            // run-time choice among the wave's four fragment sets would be branches or selects around the MFMA)
-            auto bias_read = [&](u32x2 &lo, u32x2 &hi, auto p_c, int k) {
-                constexpr int off = ST * XW_STAGE + decltype(p_c)::value * XW_PLANE;
-                const int b0 = sbase[k][0], b1 = sbase[k][1];  // (locals: asm operands cannot name a capture of the enclosing generic lambda)
-                asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(b0), "n"(off));
-                asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(b1), "n"(off));
-            };
-            auto bias_mfma = [&](u32x2 &lo, u32x2 &hi, f32x16 &dacc, int k) {
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo), "+v"(hi) :: "memory");
-                const u32x4 fa = {lo[0], lo[1], hi[0], hi[1]};
-                const unsigned sv = k ? sel1 : sel0;
-                const u32x4 sel = {sv, sv, sv, sv};
-                // accumulator in VGPRs, spelled as asm: left to hipcc, the 17th tile is shuttled through the
-                // (full) AGPR file around every one of these MFMAs (672 v_accvgpr moves per k-step)
-                asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(dacc) : "v"(fa), "v"(sel));
-            };
-            // stage ks landed (the 12 younger pieces of ks+1 may still fly); every wave is past its
-            // reads of stage ks-1, whose ring stage the DMAs below refill
+            // stage ks landed (the 12 younger pieces of ks+1 may still fly); the k-step's barrier: every wave is past its
+            // reads of stage ks-1, whose ring stage the pieces refill
+            static_assert(XW::WAIT == 12, "the counted wait");
             asm volatile(RNNT_VMCNT(12) ::: "memory");
-            lds_barrier();
-            Frag8 Ah, Bh, Am, Bm, Al, Bl;  // at most four of the six sets are live at a time (+ one landing)
-            u32x2 dl[3], dh[3];
-            reads(Ah, abase, Int<0>{});
-            reads(Bh, bbase, Int<0>{});
-            reads(Am, abase, Int<1>{});
-            FRAG8_LANDED(Ah, 8);
-            FRAG8_LANDED(Bh, 8);
-            product(Ah, Bh, Int<0>{});
-            reads(Bm, bbase, Int<1>{});
-            FRAG8_LANDED(Am, 8);
-            product(Am, Bh, Int<2>{});
-            FRAG8_LANDED(Bm, 0);
-            product(Am, Bm, Int<4>{});
-            reads(Al, abase, Int<2>{});
-            if (do_b) { bias_read(dl[0], dh[0], Int<0>{}, 0); bias_read(dl[1], dh[1], Int<1>{}, 0); bias_read(dl[2], dh[2], Int<2>{}, 0); }
-            product(Ah, Bm, Int<6>{});
-            reads(Bl, bbase, Int<2>{});
-            FRAG8_LANDED(Al, 8);
-            product(Al, Bh, Int<8>{});
-            FRAG8_LANDED(Bl, 0);
-            product(Ah, Bl, Int<10>{});
-            if (do_b && !RNNT_XP(a.ablate, 2048)) {
-                bias_mfma(dl[0], dh[0], dacc, 0); bias_mfma(dl[1], dh[1], dacc, 0); bias_mfma(dl[2], dh[2], dacc, 0);
-                if (n_hblk < 2) {  // one h block: the wave's second tile (column 1 of the selector product), H <= 256 only
-                    bias_read(dl[0], dh[0], Int<0>{}, 1); bias_read(dl[1], dh[1], Int<1>{}, 1); bias_read(dl[2], dh[2], Int<2>{}, 1);
-                    bias_mfma(dl[0], dh[0], dacc, 1); bias_mfma(dl[1], dh[1], dacc, 1); bias_mfma(dl[2], dh[2], dacc, 1);
-                }
-            }
+            dw_kstep3<XW, ST>(acc, dacc, abase, bbase, bias, a.ablate, dma_piece);
         };
         auto dma_stage = [&](long ks, int st) {  // pipeline prologue: all 12 pieces of stage ks
 #pragma unroll
-            for (int n = 0; n < 12; ++n) {
+            for (int n = 0; n < XW::ND; ++n) {
                 const int p = n >> 2, i = n & 3;
-                const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
-                    (void *)(pbase[p] + (row_first + ks * XW_ROWS) * rstride[p]), 0, (int)(XW_ROWS * rstride[p]), 0x00020000);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_vptr)(s_ring + wave * XW_TILE + st * XW_STAGE + p * XW_PLANE + 1024 * i),
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(dw_rows_rsrc(src.pbase[p], row_first + ks * DW_ROWS, src.rstride[p], DW_ROWS),
+                                                         (lds_vptr)(s_ring + wave * XW::TILE + st * XW::STAGE + p * XW::PLANE + 1024 * i),
                                                          16, soff[p][i], 0, 0, 0);
             }
         };
-
-        int ub = 0;
-        while (ub + 1 < B && tab[B + 1 + ub + 1] <= g_lo) ++ub;
-        for (long gq = g_lo; gq < g_hi; ++ub) {  // workgroup-uniform: one pipeline run per live range
-            const long cum0 = tab[B + 1 + ub], cum1 = ub + 1 < B ? tab[B + 1 + ub + 1] : nlive;
-            const long ge = cum1 < g_hi ? cum1 : g_hi;
-            if (ge <= gq) continue;
-            const long nks = 2 * (ge - gq);  // 16-cell k-steps of this range
-            row_first = (tab[ub] + (gq - cum0)) * XW_GRAN;
-            gq = ge;
+        dw_walk_ranges(share, [&](long first, long ngran) {  // one pipeline run per live range
+            __builtin_assume(ngran > 0);  // (dw_walk_ranges hands over non-empty ranges; said here, the k loop keeps its unsigned exit compares: do not delete)
+            const long nks = (DW_GRAN / DW_ROWS) * ngran;  // 16-cell k-steps of this range
+            row_first = first;
             dma_stage(0, 0);
             dma_stage(1, 1);
             for (long ks = 0;;) {  // the ring stage of a k-step is ks % 3: unrolled by 3
                 if (ks >= nks) break;
-                kstep(Int<0>{}, ks, dacc); ++ks;
+                kstep(Int<0>{}, ks); ++ks;
                 if (ks >= nks) break;
-                kstep(Int<1>{}, ks, dacc); ++ks;
+                kstep(Int<1>{}, ks); ++ks;
                 if (ks >= nks) break;
-                kstep(Int<2>{}, ks, dacc); ++ks;
+                kstep(Int<2>{}, ks); ++ks;
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the over-issued DMAs before the ring
             lds_barrier();                                  // is refilled / the kernel exits
-        }
+        });
     }
 
     X_CLOCK_STAMP(128 + 106);
-    // ---- epilogue: partial slab [split][V,H]; bias partial [split][V].  Accumulator register r of tile
-    // (qm,qn): v = v0 + 32qm + (r&3) + 8(r>>2) + 4half, h = h0 + 32qn + (lane&31).
-    const int v0 = vb * 256 + wm * 128, h0 = hb * 256 + wn * 128;
-    float *sw = a.slab_w + (long)split * V * H;
-#pragma unroll
-    for (int qm = 0; qm < 4; ++qm)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int v = v0 + 32 * qm + (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (v < V) {
-#pragma unroll
-                for (int qn = 0; qn < 4; ++qn) {
-                    const int h = h0 + 32 * qn + (lane & 31);
-                    if (h < H) sw[(long)v * H + h] = acc[qm][qn][r];
-                }
-            }
-        }
-    if (do_b && (lane & 31) < (n_hblk >= 2 ? 1 : 2)) {  // column k of the selector products: lanes k / 32+k store
-        const int m = bsel0 + 2 * (lane & 31);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int v = v0 + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (v < V) a.slab_b[(long)split * V + v] = dacc[r];
-        }
-    }
+    dw_store<Bf16x3, true>(a, tl.split, tl.v0, tl.h0, lane, acc, dacc, bias.do_b, bias.two_b, bsel0);
 }
 
 void launch_dw_x3(const X3Args &a, hipStream_t st)
 {
-    launch_dw_table(a.logit_lens, a.B, a.T, a.U1, XW_GRAN, a.dw_tab, st);
+    launch_dw_table(a.logit_lens, a.B, a.T, a.U1, DW_GRAN, a.dw_tab, st);
     const int tiles = ((a.V + 255) / 256) * ((a.H + 255) / 256);
     static LdsOptIn lds_opt_in;
-    lds_opt_in.raise(4 * XW_TILE, k_dw_x3);
-    hipLaunchKernelGGL(k_dw_x3, dim3(tiles * a.n_split), dim3(256), 4 * XW_TILE, st, a);
+    lds_opt_in.raise(4 * XW::TILE, k_dw_x3);
+    hipLaunchKernelGGL(k_dw_x3, dim3(tiles * a.n_split), dim3(256), 4 * XW::TILE, st, a);
 }
 
 

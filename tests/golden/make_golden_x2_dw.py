@@ -1,5 +1,5 @@
 """Record what the f16x2 dW GEMM (rnnt_amd/csrc/x2.hip: k_dw_x2<4>, k_dw_x2<4, true>, k_dw_x2m) leaves behind, for
-tests/test_x2_dw_bits_gpu.py: every kernel form and every branch of the k-step pipeline the three share — several h blocks (db from
+tests/test_x2_dw_bits_gpu.py: every kernel form and every branch of the k-step pipeline the three share (rnnt_amd/csrc/split_dw.hpp: dw_kstep2, dw_ring) — several h blocks (db from
 blocks 0 and 1, operand tiles shared between workgroups under the lockstep), empty split shares, a walk longer than the ring, the
 walk without the flush rule, and the Linear layer's lists (identity, padding rows) — so that the kernels' source can be rearranged
 freely as long as every case keeps every bit of dW and db (the route is bitwise reproducible: fixed list order, fixed slab order).

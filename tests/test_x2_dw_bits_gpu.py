@@ -1,5 +1,5 @@
 """The f16x2 dW GEMM keeps EVERY BIT of dW and db (and of the step's other outputs) that the library left before k_dw_x2<4>,
-k_dw_x2<4, true> and k_dw_x2m were rebuilt from one set of k-step pipeline pieces (rnnt_amd/csrc/x2.hip, "The dW k-step pipeline"):
+k_dw_x2<4, true> and k_dw_x2m were rebuilt from one set of k-step pipeline pieces (now rnnt_amd/csrc/split_dw.hpp, the dW tile toolkit: dw_kstep2, dw_ring):
 SHA-256 against tests/golden/x2_dw.npz, written by tests/golden/make_golden_x2_dw.py, which also holds the cases, what each one
 reaches and the code that runs them.  The route is bitwise reproducible (tests/test_x2_dw_groups_gpu.py), so the bar is equality.
 tests/test_fused_routes_bits_gpu.py pins one small shape per kernel form; the cases here add several h blocks, empty split shares,

@@ -1,4 +1,4 @@
-"""-m gpu: the f16x2 dW GEMM over its list of live 4-cell groups (rnnt_amd/csrc/x2.hip: grp_list, k_dw_x2, k_x2_dead_rows).  A k-step of
+"""-m gpu: the f16x2 dW GEMM over its list of live 4-cell groups (rnnt_amd/csrc/x2.hip: grp_list, k_dw_x2, k_x2_dead_rows; the k-step pipeline: split_dw.hpp).  A k-step of
 k_dw_x2 multiplies the 16 rows of four list entries, each DMA piece reads the four rows of one entry through a raw buffer of its own, and
 the last k-step of the list is filled up with padding entries.  What could go wrong shows as
   * a count that disagrees with the fp64 twin's bounds or with the k-step / tile counts (which keep their meaning),
